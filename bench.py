@@ -50,6 +50,26 @@ def lib_sha16():
         return None
 
 
+DUMP_BYTES_MAX = 64 * 10**6
+
+
+def dump_outputs(dirpath, plan, B):
+    """--dump-outputs DIR: what the timed plan's last step left for a caller of EpiPlan.download (bestD, minC; u32 [H][W]
+    per frame) on a fixed sample of frames spread over the batch (first and last included), as float64 (exact for u32)
+    stacked [frames][H][W]: DIR/bestD.npy, DIR/minC.npy.  As many frames as fit in DUMP_BYTES_MAX, at most 8."""
+    import numpy as np
+    n = max(1, min(8, B, DUMP_BYTES_MAX // (2 * 8 * W * H)))
+    frames = sorted({int(round(i * (B - 1) / (n - 1))) for i in range(n)}) if n > 1 else [0]
+    got = [plan.download(f) for f in frames]
+    os.makedirs(dirpath, exist_ok=True)
+    files = {}
+    for k, name in enumerate(("bestD", "minC")):
+        a = np.stack([g[k] for g in got]).astype(np.float64)
+        np.save(os.path.join(dirpath, name + ".npy"), a)
+        files[name] = list(a.shape)
+    return {"dir": dirpath, "frames": frames, "dtype": "float64", "files": files}
+
+
 def cpu_baseline(sample_rows=48, PATHS=PATHS):
     """The CPU oracle (a port: oracle/fsgm_oracle_epi.cpp, 1 thread like the reference) timed on a
     bounded sample of the same workload: 8-path aggregation of a 1242 x sample_rows x 128 strip."""
@@ -310,6 +330,7 @@ def in_process(args):
     for pl in plans:
         pl.sync()
     dt = time.perf_counter() - t0
+    dumped = dump_outputs(args.dump_outputs, plans[0], B) if args.dump_outputs else None
     # self-check: frame 0 of every entry against the line kernels on the same volume
     ok = True
     for slot, pl in enumerate(plans):
@@ -337,6 +358,8 @@ def in_process(args):
            "roofline": {"bound": "hbm", "kernel": "aggregation stage of entry 0 alone", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                         "frac": achieved / HBM_PEAK_GBS, "traffic": None, "algorithmic_bytes": alg, "stage_ms": stage_ms},
            "checked": True, "argv": " ".join(sys.argv[1:])}
+    if dumped:
+        out["dump_outputs"] = dumped
     for pl in plans:
         pl.close()
     print(json.dumps(out), flush=True)
@@ -371,7 +394,14 @@ def main():
     ap.add_argument("--in-process", type=int, default=0,
                     help="N > 0: the headline step on N device-list entries from this one process (entry i on device i mod the device "
                          "count; what a single MATLAB process gets through the C ABI's device lists); prints the distinct PCI bus ids")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (bestD, minC of a fixed sample of frames, "
+                         "float64) as DIR/<name>.npy, to compare two builds output for output (epi8 workload)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.in_process <= 0 and args.workload != "epi8":
+        ap.error("--dump-outputs covers the epi8 workload (the headline step) only")
     if args.in_process > 0:
         return in_process(args)
     if args.workload == "pyramid3":
@@ -465,6 +495,7 @@ def main():
         t = torch.tensor([dt], device="cuda" if args.backend == "nccl" else "cpu", dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    dumped = dump_outputs(args.dump_outputs, plan, B) if args.dump_outputs and rank == 0 else None
 
     # self-check of what the timed loop left behind: two frames of the timed plan against the per-direction line
     # kernels (agg mode 1: a different implementation of the same recurrence, itself checked against the oracle
@@ -539,6 +570,8 @@ def main():
             "checked": bool(checked),
             "check": f"frames {check_frames} of the timed plan == line kernels ({ref_kernel}) on the same volumes, bestD and minC, all pixels",
         }
+        if dumped:
+            out["dump_outputs"] = dumped
         try:
             import ctypes as C
             g = C.c_double()

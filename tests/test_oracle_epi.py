@@ -1,8 +1,8 @@
 """CPU tests of the oracle for the calc_cost_sgm path (no GPU).
 
 * census: pinned bit-for-bit against the reference's own common.cpp (oracle/_ref, built in the
-  build container; the committed golden vector was generated from it by
-  tests/golden/make_census_golden.py).
+  build container; the committed golden vectors were generated from it by
+  tests/golden/make_census_golden.py and tests/golden/make_census_cases_golden.py).
 * everything else: PARITY UNPINNED w.r.t. the compiled reference (its MEX sources need MATLAB's
   mex.h).  Checked here against an independent second restatement (tests/py_restatement.py) and
   against structural properties of the algorithm.
@@ -23,13 +23,20 @@ def test_census_golden_from_reference(oracle):
 
 
 def test_census_matches_reference_build(oracle):
-    if not oracle.ref_census_available():
-        pytest.skip("oracle/_ref not built (reference tree absent on this box)")
+    """Against the reference's census codes stored by tests/golden/make_census_cases_golden.py, and against
+    the reference build itself where oracle/_ref has been built."""
+    g = np.load(os.path.join(GOLD, "census_ref_cases.npz"))
+    live = oracle.ref_census_available()
     for (W, H, seed) in [(1, 1, 1), (2, 3, 2), (5, 5, 3), (64, 48, 4), (131, 7, 5), (3, 97, 6)]:
         img = synth.uniform_u8(seed, (H, W))
-        np.testing.assert_array_equal(oracle.census(img), oracle.ref_census(img))
+        np.testing.assert_array_equal(img, g[f"img_{W}x{H}_{seed}"])
+        np.testing.assert_array_equal(oracle.census(img), g[f"cen_{W}x{H}_{seed}"])
+        if live:
+            np.testing.assert_array_equal(oracle.census(img), oracle.ref_census(img))
     flat = np.full((9, 11), 77, np.uint8)                       # ties: nbr >= ctr is true everywhere
-    np.testing.assert_array_equal(oracle.census(flat), oracle.ref_census(flat))
+    np.testing.assert_array_equal(oracle.census(flat), g["cen_flat"])
+    if live:
+        np.testing.assert_array_equal(oracle.census(flat), oracle.ref_census(flat))
     assert (oracle.census(flat) == 0x3FFFFFE).all()
 
 
