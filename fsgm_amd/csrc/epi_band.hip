@@ -106,6 +106,58 @@ __device__ __forceinline__ void unpack_p9(const uint4 v, const uint32_t bits, ui
     }
 }
 
+// The final pass's per-pixel WTA: the record of wta_row_record_at (epi_step.h) bit for bit, with fewer instructions per step
+// (the block sweeps keep theirs):
+//   * keys S*16 + index as one 32-bit shift-or per register: S < 0x7C0 (band_ok), so no bit crosses into the high half;
+//   * the neighbours S[best-1] / S[best+1] through a per-workgroup table instead of two srow_index computations and two
+//     boundary branches: entry d holds the byte offsets of S[d-1] and S[d+1] from the pixel's first sRow slot (an in-range
+//     slot where a neighbour does not exist) and the mask that zeroes an absent one (c_1 = 0 at best = 0, c1 = 0 at
+//     best = D-1, where the finish kernel takes the next pixel's S[0]).
+template <int LPP, int NT>
+__device__ __forceinline__ uint2 band_nb_entry(const uint32_t d) {
+    constexpr uint32_t D = LPP * 16;
+    const uint32_t lo = d > 0 ? srow_index<NT>(0, d - 1) * 2u : 0u, hi = d + 1 < D ? srow_index<NT>(0, d + 1) * 2u : 0u;
+    return make_uint2(lo | (hi << 16), (d > 0 ? 0x0000FFFFu : 0u) | (d + 1 < D ? 0xFFFF0000u : 0u));
+}
+// a 32-bit constant in a scalar register: VOP3 encodings take no literal on gfx950, and the compiler would otherwise
+// rebuild it with a v_mov_b32 every step
+template <uint32_t X>
+__device__ __forceinline__ uint32_t sconst() { uint32_t r; asm("s_mov_b32 %0, %1" : "=s"(r) : "i"(X)); return r; }
+
+template <int LPP, int NT, bool STAGE>
+__device__ __forceinline__ void band_wta_record(const uint32_t (&ST)[8], uint32_t* sRow, const uint2* sNb, int tid, int j,
+                                                bool ok, uint8_t* recb, uint8_t* s0b, uint32_t pix,
+                                                uint2* stg_rec, uint16_t* stg_s0) {
+    srow_store<NT>(sRow, tid, ST);
+    const uint32_t IDX[8] = {sconst<0x80000u>(), sconst<0x90001u>(), sconst<0xA0002u>(), sconst<0xB0003u>(),
+                             sconst<0xC0004u>(), sconst<0xD0005u>(), sconst<0xE0006u>(), sconst<0xF0007u>()};
+    uint32_t K[8];
+#pragma unroll
+    for (int i = 0; i < 8; i++) K[i] = (ST[i] << 4) | IDX[i];           // (i, i + 8): index in the lane
+    const uint32_t kmin = pk_min(pk_min3(K[0], K[1], K[2]), pk_min3(K[3], K[4], pk_min3(K[5], K[6], K[7])));
+    const uint32_t k16 = min_halves(kmin);                               // S * 16 + e, d = 16 j + e
+    uint32_t key;                                                        // (S << 8) | d: v_and, v_and_or, v_lshl_or
+    asm("v_lshl_or_b32 %0, %1, 4, %2" : "=v"(key) : "v"(k16 & ~15u), "v"((k16 & 15u) | ((uint32_t)j << 4)));
+    key = group_min_u32<LPP>(key);
+    __builtin_amdgcn_wave_barrier();
+    if (j == 0 && ok) {
+        const uint2 nb = sNb[key & 0xFFu];
+        const uint8_t* row = (const uint8_t*)sRow + tid * 16;           // the pixel's first lane (this one)
+        u16x2 c;
+        c[0] = *(const uint16_t*)(row + (nb.x & 0xFFFFu));
+        c[1] = *(const uint16_t*)(row + (nb.x >> 16));
+        const uint2 rec = make_uint2(__builtin_amdgcn_perm(0u, key, sconst<0x02010C00u>()),    // best | minC << 16
+                                     __builtin_bit_cast(uint32_t, c) & nb.y);                  // c_1 | c1 << 16
+        if (STAGE) {
+            *stg_rec = rec;
+            *stg_s0 = (uint16_t)ST[0];
+        } else {
+            *(uint2*)(recb + pix * 8u) = rec;
+            *(uint16_t*)(s0b + pix * 2u) = (uint16_t)ST[0];
+        }
+    }
+}
+
 template <int LPP, int MODE, int NWV, int PATHS, bool BITS, bool TAP, bool CHAIN>
 __global__ __launch_bounds__(NWV * 64, FSGM_BAND_MINW) void band_kernel(BandArgs a) {
     constexpr bool UP = MODE != 0;
@@ -121,6 +173,7 @@ __global__ __launch_bounds__(NWV * 64, FSGM_BAND_MINW) void band_kernel(BandArgs
     // more LDS (67 KB: still two workgroups per CU; the second pass needs that room for its WTA rows)
     constexpr bool R16 = P8 && MODE == 0 && !CHAIN && FSGM_BAND_R16 != 0;   // (the chained form has no registers to spare for it)
     constexpr int NSL = R16 ? 2 : NST;                       // states that cross rows as packed bytes
+    __shared__ uint2 sNb[MODE == 2 ? D : 1];                  // final pass: the WTA's neighbour table (band_nb_entry)
     __shared__ uint4 sR16[R16 ? 2 : 1][2][R16 ? (R + 1) * LPP : 1];   // [step parity][plane: registers 0-3 / 4-7][row slot][lane of pixel]
     __shared__ uint4 sSt[2][NSL][(R + 1) * LPP];              // [step parity][state][row slot (row + 1; slot 0 = the row above the band)][lane of pixel]
     __shared__ __attribute__((aligned(16))) uint32_t sRow[MODE == 2 ? NWV * 64 * 8 : 4];   // final pass: S of the wave's pixels (u16, two planes: epi_step.h)
@@ -163,6 +216,8 @@ __global__ __launch_bounds__(NWV * 64, FSGM_BAND_MINW) void band_kernel(BandArgs
     const uint4 startP = make_uint4(P2 * 0x01010101u, P2 * 0x01010101u, P2 * 0x01010101u, P2 * 0x01010101u);
     const LaneSel sel = lane_sel<LPP>(j);
     const int elane = min(lane, NST * LPP - 1);                // wave 0: lane = state * LPP + lane-of-pixel of the hand-off words
+
+    if (MODE == 2 && tid < D) sNb[tid] = band_nb_entry<LPP, NWV * 64>((uint32_t)tid);    // (visible after the band's first barrier)
 
     auto pix_of = [&](int x, int y) -> int { const int p = y * W + x; return UP ? NP - 1 - p : p; };
 
@@ -400,11 +455,11 @@ __global__ __launch_bounds__(NWV * 64, FSGM_BAND_MINW) void band_kernel(BandArgs
                 // S = PATHS*(C + P2) - (this pass's y + the first pass's), WTA on the spot (:227-232, :259-275)
                 uint32_t ST[8];
 #pragma unroll
-                for (int i = 0; i < 8; i++) ST[i] = pk_mad16(CP[i], (uint32_t)PATHS * 0x10001u, 0u) - YS[i];    // the P1 biases of CP and YS cancel; no borrow between the halves
+                for (int i = 0; i < 8; i++) ST[i] = CP[i] * (uint32_t)PATHS - YS[i];    // the P1 biases of CP and YS cancel; no carry or borrow between the halves (CP < 2^9)
                 if constexpr (RECLDS)
-                    wta_row_record_at<LPP, NWV * 64, true, true>(ST, sRow, tid, j, inside, recb, s0b, 0u, &sRec[wave * 64 + g * 8 + (u & 7)], &sRs0[wave * 64 + g * 8 + (u & 7)]);
+                    band_wta_record<LPP, NWV * 64, true>(ST, sRow, sNb, tid, j, inside, recb, s0b, 0u, &sRec[wave * 64 + g * 8 + (u & 7)], &sRs0[wave * 64 + g * 8 + (u & 7)]);
                 else
-                    wta_row_record_at<LPP, NWV * 64, true>(ST, sRow, tid, j, inside, recb, s0b, (uint32_t)pix_of(xc, yc));
+                    band_wta_record<LPP, NWV * 64, false>(ST, sRow, sNb, tid, j, inside, recb, s0b, (uint32_t)pix_of(xc, yc), nullptr, nullptr);
                 if (TAP && inside) {                           // debug tap (an instantiation of its own): S in natural d order
                     uint32_t* o = a.Sdbg + (f * (size_t)NP + pix_of(xc, yc)) * D + j * 16;
 #pragma unroll
