@@ -34,7 +34,7 @@
 // inter-workgroup synchronisation of any kind, no tickets, no polling.
 //
 // Path starts (:152-180): a predecessor outside the image means the path starts here -- the consumer presets the state to
-// P2 in every element and masks the stored minimum to 0 (epi_step.h); waves whose eight pixels are all strictly inside
+// P2 in every element and sets the stored minimum to 0 (step_x: its offset K0); waves whose eight pixels are all strictly inside
 // the image run a variant without those selects.
 //
 // What it needs: many frames.  One band of one frame is in flight per workgroup, two workgroups of 8 waves per CU: 512
@@ -103,6 +103,47 @@ __device__ __forceinline__ void unpack_p9(const uint4 v, const uint32_t bits, ui
         const uint32_t hk = (bits >> k) & 0x01010101u;
         R[2 * k] = __builtin_amdgcn_perm(hk, w[k], 0x06020400u);          // (w.0, h.0, w.2, h.2)
         R[2 * k + 1] = __builtin_amdgcn_perm(hk, w[k], 0x07030501u);      // (w.1, h.1, w.3, h.3)
+    }
+}
+
+// 16 natural-order cost bytes of a lane -> C[i] = (C[i], C[i+8]), unbiased (unpack_cb of epi_step.h without its add)
+__device__ __forceinline__ void band_unpack_c(const uint4 w, uint32_t (&C)[8]) {
+    C[0] = __builtin_amdgcn_perm(w.z, w.x, 0x0C040C00u);
+    C[1] = __builtin_amdgcn_perm(w.z, w.x, 0x0C050C01u);
+    C[2] = __builtin_amdgcn_perm(w.z, w.x, 0x0C060C02u);
+    C[3] = __builtin_amdgcn_perm(w.z, w.x, 0x0C070C03u);
+    C[4] = __builtin_amdgcn_perm(w.w, w.y, 0x0C040C00u);
+    C[5] = __builtin_amdgcn_perm(w.w, w.y, 0x0C050C01u);
+    C[6] = __builtin_amdgcn_perm(w.w, w.y, 0x0C060C02u);
+    C[7] = __builtin_amdgcn_perm(w.w, w.y, 0x0C070C03u);
+}
+// The DP step of the band sweeps: step_b (epi_step.h) with the costs' bias folded into the subtraction.  YB = y + P1 <= P1 + P2
+// <= 127 (band_ok), so YB ^ 0x7F = 127 - YB in each half with no borrow, and n' = (YB ^ 0x7F) + C = n + K0 with
+// K0 = 127 - (P1 + P2) >= 0: one v_xad_u32 a register from the unbiased costs, no bias add after the unpack.  The offset
+// cancels in S = max(P2 + m' - n', 0) with m' = min n' = m + K0; a path start presets m' = K0 (m = 0 there).  n' <= 255 + 127,
+// far below 0x7C00: the fp16 3-input minimum still orders it as integers.  O: YB (first pass: its sum crosses to the final
+// pass) or n' (final pass: S is rebuilt from the n' of its own paths, see band_kernel).
+template <int LPP, bool MASKED, bool OUT_N>
+__device__ __forceinline__ void step_x(uint32_t (&S)[8], const uint32_t (&C)[8], uint32_t (&O)[8], const uint32_t P1pk,
+                                       const uint32_t P2pk, const uint32_t kx, const uint32_t K0, const LaneSel sel,
+                                       const bool start) {
+    uint32_t N[8], YB[8];
+    // d-1 of register 0 = (previous lane's d = 15, own d = 7); d+1 of register 7 = (own d = 8, next lane's d = 0)
+    const uint32_t LT = __builtin_amdgcn_perm(S[7], (uint32_t)__builtin_amdgcn_mov_dpp((int)S[7], DPP_ROW_SHR1, 0xF, 0xF, true), sel.lo);
+    const uint32_t RT = __builtin_amdgcn_perm((uint32_t)__builtin_amdgcn_mov_dpp((int)S[0], DPP_ROW_SHL1, 0xF, 0xF, true), S[0], sel.hi);
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        YB[i] = pk_max3(S[i] + P1pk, i ? S[i - 1] : LT, i < 7 ? S[i + 1] : RT);
+        asm("v_xad_u32 %0, %1, %2, %3" : "=v"(N[i]) : "v"(YB[i]), "s"(kx), "v"(C[i]));   // (YB ^ kx) + C, as one instruction
+    }
+    const uint32_t mm = pk_min(pk_min3(N[0], N[1], N[2]), pk_min3(N[3], N[4], pk_min3(N[5], N[6], N[7])));
+    uint32_t mx = group_min_u32<LPP>(min_halves(mm));
+    if (MASKED && start) mx = K0;
+    const uint32_t p2m = __umul24(mx, 0x10001u) + P2pk;
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        S[i] = pk_subs(p2m, N[i]);
+        O[i] = OUT_N ? N[i] : YB[i];
     }
 }
 
@@ -212,7 +253,10 @@ __global__ __launch_bounds__(NWV * 64, FSGM_BAND_MINW) void band_kernel(BandArgs
     uint8_t* __restrict__ s0b = MODE == 2 ? (uint8_t*)(a.s0 + f * (size_t)NP) : nullptr;
     // every global access below is a wave-uniform base + a 32-bit byte offset per lane (no 64-bit address registers)
     const uint32_t P1pk = (uint32_t)a.P1 * 0x10001u, P2 = (uint32_t)a.P2, P2pk = P2 * 0x10001u;
-    const uint32_t Bpk = (P2 + (uint32_t)a.P1) * 0x10001u;     // the costs' bias in the step's variable (epi_step.h, step_b): P2 + P1
+    // the step's variable (step_x): n' = n + K0; the final pass rebuilds S = PATHS*(C + P2) - sum(y) as
+    // (PATHS/2)*C + sum of its own paths' n' - Y_dn + K1 (Y_dn: the first pass's sum of (PATHS/2) YB = y + P1, as stored)
+    const uint32_t KX = sconst<0x007F007Fu>(), K0 = 127u - (P2 + (uint32_t)a.P1);
+    const uint32_t K1pk = (uint32_t)(PATHS * (a.P1 + a.P2) - (PATHS / 2) * 127) * 0x10001u;   // (may be negative: exact mod 2^32, see do_step)
     const uint4 startP = make_uint4(P2 * 0x01010101u, P2 * 0x01010101u, P2 * 0x01010101u, P2 * 0x01010101u);
     const LaneSel sel = lane_sel<LPP>(j);
     const int elane = min(lane, NST * LPP - 1);                // wave 0: lane = state * LPP + lane-of-pixel of the hand-off words
@@ -287,13 +331,16 @@ __global__ __launch_bounds__(NWV * 64, FSGM_BAND_MINW) void band_kernel(BandArgs
 #pragma unroll
         for (int i = 0; i < 8; i++) FS[i] = P2pk;
         // from above / from above-left of the row above, read one / two steps before they are used
-        uint4 hU = startP, hD1 = startP, hD2 = startP;
+        // (from-above-left: the read of step u sits in hDp[u & 1] until step u + 2 uses it -- no register moves; the loops below
+        // run an even number of steps an iteration, so u & 1 is known where it is used.  Waves other than 0 start with startP in
+        // both; wave 0's first step is u = 0)
+        uint4 hU = startP, hDp[2] = {startP, startP};
         if (P8 && have_above && wave == 0) {                   // row 0: column 0 of the band above ("read at step -1"); wave-uniform
             const bool mine = r == 0;
             const uint8_t* q0 = Ein + (uint32_t)(0 * LPP + j) * 16u;
             const uint8_t* q1 = Ein + (uint32_t)(1 * LPP + j) * 16u;
             const uint4 v0 = settle(mine ? eload(q0) : startP, q0, mine), v1 = settle(mine ? eload(q1) : startP, q1, mine);
-            if (mine) { hU = v0; hD1 = v1; }
+            if (mine) { hU = v0; hDp[1] = v1; }
         }
         if (CHAIN && wave == 0 && have_above) {
             // Start only once the band above is FSGM_BAND_SLACK columns further than the first step needs: both bands then
@@ -307,7 +354,12 @@ __global__ __launch_bounds__(NWV * 64, FSGM_BAND_MINW) void band_kernel(BandArgs
             const uint4 v = settle(loader ? eload(q) : startP, q, loader);
             if (loader) put_above(1, v);
         }
-        uint4 ringC[PF], ringY[MODE == 2 ? PF : 1];
+        // the final pass keeps PF + 1 slots of each ring and walks them by step (slot u % NR): a step's words stay where they
+        // were loaded while the next ones arrive in the other slot -- no register moves (with PF slots the words of step u
+        // would have to be copied out before the load of step u + PF lands in their slot)
+        constexpr int NR = MODE == 2 && P8 ? PF + 1 : PF;
+        constexpr int UN = P8 && (NR & 1) ? 2 * NR : NR;       // steps per loop iteration: a multiple of NR, even for hDp
+        uint4 ringC[NR], ringY[MODE == 2 ? NR : 1];
         // wave 0: the band above's states for the coming steps.  Sequential form: one step ahead (the lines were written a band
         // earlier: L2 / Infinity Cache).  Chained form: the words were written moments ago by another CU with write-through stores
         // and come from beyond the L2 -- a round trip of about a step's time -- so several steps are kept in flight.
@@ -315,8 +367,8 @@ __global__ __launch_bounds__(NWV * 64, FSGM_BAND_MINW) void band_kernel(BandArgs
         uint4 ringE[PFE];
 #pragma unroll
         for (int i = 0; i < PFE; i++) ringE[i] = startP;
-        uint32_t ringB[MODE == 2 && BITS && !Y16 ? PF : 1];
-        uint4 ringB4[MODE == 2 && Y16 ? PF : 1];
+        uint32_t ringB[MODE == 2 && BITS && !Y16 ? NR : 1];
+        uint4 ringB4[MODE == 2 && Y16 ? NR : 1];
 #pragma unroll
         for (int i = 0; i < PF; i++) {
             const uint32_t off = vox_off(i);
@@ -336,7 +388,7 @@ __global__ __launch_bounds__(NWV * 64, FSGM_BAND_MINW) void band_kernel(BandArgs
 
         // one step of this wave's rows.  EDGE: a pixel of the wave is at / outside an image border or in row 0, or a row
         // of the wave lies below the image (selects allowed); the plain variant has none.
-        auto do_step = [&](const int u, const uint4 cw, const uint4 cy, const uint32_t cb, const uint4 cb4, auto edge_tag) {
+        auto do_step = [&](const int u, const int hp, const uint4 cw, const uint4 cy, const uint32_t cb, const uint4 cb4, auto edge_tag) {
             constexpr bool EDGE = decltype(edge_tag)::value;
             const int par = u & 1;
             const int x = u - SKEW * r;
@@ -348,7 +400,7 @@ __global__ __launch_bounds__(NWV * 64, FSGM_BAND_MINW) void band_kernel(BandArgs
             if constexpr (R16) { nLo = sR16[par ^ 1][0][r * LPP + j]; nHi = sR16[par ^ 1][1][r * LPP + j]; }
             else nNow = sSt[par ^ 1][P8 ? 2 : 0][r * LPP + j];
             uint32_t CP[8], Y[8], YS[8], S[8];
-            unpack_cb(cw, CP, Bpk);
+            band_unpack_c(cw, CP);
             const bool top = EDGE && y == 0;                   // row 0 of the frame: every path from above starts (:152-180)
             // from the left (-1,0): :183-191
             {
@@ -357,16 +409,17 @@ __global__ __launch_bounds__(NWV * 64, FSGM_BAND_MINW) void band_kernel(BandArgs
 #pragma unroll
                     for (int i = 0; i < 8; i++) FS[i] = P2pk;
                 }
-                step_b<LPP, EDGE>(FS, CP, YS, P1pk, P2, sel, st ? 0u : 0xFFFFu);
+                step_x<LPP, EDGE, MODE == 2>(FS, CP, YS, P1pk, P2pk, KX, K0, sel, st);
             }
             if (MODE == 2) {
-                // the first pass's sum joins the running sum right away: its five registers are free for the rest of the step
+                // the first pass's sum leaves the running sum right away: its five registers are free for the rest of the step
+                // (a half of YS may go below zero here; only the final S has to lie in [0, 2^16) per half, and it does)
                 uint32_t E2[8];
                 if (Y16) { E2[0] = cy.x; E2[1] = cy.y; E2[2] = cy.z; E2[3] = cy.w; E2[4] = cb4.x; E2[5] = cb4.y; E2[6] = cb4.z; E2[7] = cb4.w; }
                 else if (BITS) unpack_p9(cy, cb, E2);
                 else unpack_p(cy, E2);
 #pragma unroll
-                for (int i = 0; i < 8; i++) YS[i] += E2[i];
+                for (int i = 0; i < 8; i++) YS[i] -= E2[i];
             }
             __builtin_amdgcn_sched_barrier(0);
             // from above (0,-1): :193-202
@@ -377,29 +430,28 @@ __global__ __launch_bounds__(NWV * 64, FSGM_BAND_MINW) void band_kernel(BandArgs
 #pragma unroll
                     for (int i = 0; i < 8; i++) S[i] = P2pk;
                 }
-                step_b<LPP, EDGE>(S, CP, Y, P1pk, P2, sel, top ? 0u : 0xFFFFu);
+                step_x<LPP, EDGE, MODE == 2>(S, CP, Y, P1pk, P2pk, KX, K0, sel, top);
                 newU = pack_p(S);
                 sSt[par][0][(r + 1) * LPP + j] = newU;
 #pragma unroll
-                for (int i = 0; i < 8; i++) YS[i] += Y[i];
+                for (int i = 0; i < 8; i++) YS[i] += MODE == 2 ? Y[i] + K1pk : Y[i];     // (v_add3_u32)
             }
             __builtin_amdgcn_sched_barrier(0);                 // one path after the other: interleaving them costs registers (spills)
             if constexpr (P8) {
                 // from above-left (-1,-1): :205-213
                 {
                     const bool st = top || (EDGE && x <= 0);
-                    unpack_p(hD2, S);
+                    unpack_p(hDp[hp], S);
                     if (st) {
 #pragma unroll
                         for (int i = 0; i < 8; i++) S[i] = P2pk;
                     }
-                    step_b<LPP, EDGE>(S, CP, Y, P1pk, P2, sel, st ? 0u : 0xFFFFu);
+                    step_x<LPP, EDGE, MODE == 2>(S, CP, Y, P1pk, P2pk, KX, K0, sel, st);
                     newD = pack_p(S);
                     sSt[par][1][(r + 1) * LPP + j] = newD;
 #pragma unroll
                     for (int i = 0; i < 8; i++) YS[i] += Y[i];
-                    hD2 = hD1;
-                    hD1 = sSt[par ^ 1][1][r * LPP + j];          // pixel x+1's from-above-left state: used two steps on
+                    hDp[hp] = sSt[par ^ 1][1][r * LPP + j];      // pixel x+1's from-above-left state: used two steps on
                     hU = sSt[par ^ 1][0][r * LPP + j];           // its from-above state: used next step
                 }
                 __builtin_amdgcn_sched_barrier(0);
@@ -412,7 +464,7 @@ __global__ __launch_bounds__(NWV * 64, FSGM_BAND_MINW) void band_kernel(BandArgs
 #pragma unroll
                         for (int i = 0; i < 8; i++) S[i] = P2pk;
                     }
-                    step_b<LPP, EDGE>(S, CP, Y, P1pk, P2, sel, st ? 0u : 0xFFFFu);
+                    step_x<LPP, EDGE, MODE == 2>(S, CP, Y, P1pk, P2pk, KX, K0, sel, st);
                     if constexpr (R16) {
                         sR16[par][0][(r + 1) * LPP + j] = make_uint4(S[0], S[1], S[2], S[3]);
                         sR16[par][1][(r + 1) * LPP + j] = make_uint4(S[4], S[5], S[6], S[7]);
@@ -452,10 +504,12 @@ __global__ __launch_bounds__(NWV * 64, FSGM_BAND_MINW) void band_kernel(BandArgs
                     }
                 }
             } else {
-                // S = PATHS*(C + P2) - (this pass's y + the first pass's), WTA on the spot (:227-232, :259-275)
+                // S = PATHS*(C + P2) - (this pass's y + the first pass's) = (PATHS/2)*C + sum(n') - Y_dn + K1, WTA on the spot
+                // (:227-232, :259-275): one v_lshl_add_u32 a register.  Every term is a pair of 16-bit halves in 32 bits and the
+                // arithmetic is exact mod 2^32, so the result holds S in each half whatever the intermediate borrows (S < 2^16)
                 uint32_t ST[8];
 #pragma unroll
-                for (int i = 0; i < 8; i++) ST[i] = CP[i] * (uint32_t)PATHS - YS[i];    // the P1 biases of CP and YS cancel; no carry or borrow between the halves (CP < 2^9)
+                for (int i = 0; i < 8; i++) ST[i] = (CP[i] << (P8 ? 2 : 1)) + YS[i];
                 if constexpr (RECLDS)
                     band_wta_record<LPP, NWV * 64, true>(ST, sRow, sNb, tid, j, inside, recb, s0b, 0u, &sRec[wave * 64 + g * 8 + (u & 7)], &sRs0[wave * 64 + g * 8 + (u & 7)]);
                 else
@@ -487,7 +541,7 @@ __global__ __launch_bounds__(NWV * 64, FSGM_BAND_MINW) void band_kernel(BandArgs
                 __builtin_amdgcn_wave_barrier();
             }
         };
-        auto step = [&](const int u, const uint4 cw, const uint4 cy, const uint32_t cb, const uint4 cb4) {
+        auto step = [&](const int u, const int hp, const uint4 cw, const uint4 cy, const uint32_t cb, const uint4 cb4) {
             if (wave == 0 && have_above) {                                            // "row -1" of step u: column u + SKEW of the band above
                 const uint4 v = settle(ringE[0], edge_at(u + SKEW), loader);
 #pragma unroll
@@ -498,8 +552,8 @@ __global__ __launch_bounds__(NWV * 64, FSGM_BAND_MINW) void band_kernel(BandArgs
                 }
             }
             if (wave_rows && u >= act_lo && u <= act_hi) {                            // wave-uniform
-                if (wave_plain_rows && u >= pl_lo && u <= pl_hi) do_step(u, cw, cy, cb, cb4, std::false_type{});
-                else do_step(u, cw, cy, cb, cb4, std::true_type{});
+                if (wave_plain_rows && u >= pl_lo && u <= pl_hi) do_step(u, hp, cw, cy, cb, cb4, std::false_type{});
+                else do_step(u, hp, cw, cy, cb, cb4, std::true_type{});
             }
             if constexpr (RECLDS) {
                 if ((u & 7) == 7) flush_records(u);                                   // workgroup-uniform
@@ -509,28 +563,31 @@ __global__ __launch_bounds__(NWV * 64, FSGM_BAND_MINW) void band_kernel(BandArgs
 #endif
         };
 
-        int u0 = 0;
-        for (; u0 + PF <= nsteps; u0 += PF) {
-#pragma unroll
-            for (int i = 0; i < PF; i++) {
-                const int u = u0 + i;
-                const uint4 cw = ringC[i];
-                const uint4 cy = ringY[MODE == 2 ? i : 0];
-                const uint32_t cb = ringB[MODE == 2 && BITS && !Y16 ? i : 0];
-                const uint4 cb4 = ringB4[MODE == 2 && Y16 ? i : 0];
-                const uint32_t off = vox_off(u + PF);
-                ringC[i] = *(const uint4*)(Cf + off);
-                if (MODE == 2) {
-                    ringY[i] = vol_load(Yf + off);
-                    if (Y16) ringB4[i] = vol_load(Bf + off);
-                    else if (BITS) ringB[i] = *(const uint32_t*)(Bf + bit_off(u + PF));
-                }
-                step(u, cw, cy, cb, cb4);
+        // step u = u0 + i (u0 a multiple of UN): its words from slot i % NR, the loads of step u + PF into slot (i + PF) % NR
+        // (the same slot when NR = PF: read out first)
+        auto ring_step = [&](const int u, const int i) {
+            const int k = i % NR, kl = (i + PF) % NR;
+            const uint4 cw = ringC[k];
+            const uint4 cy = ringY[MODE == 2 ? k : 0];
+            const uint32_t cb = ringB[MODE == 2 && BITS && !Y16 ? k : 0];
+            const uint4 cb4 = ringB4[MODE == 2 && Y16 ? k : 0];
+            const uint32_t off = vox_off(u + PF);
+            ringC[kl] = *(const uint4*)(Cf + off);
+            if (MODE == 2) {
+                ringY[kl] = vol_load(Yf + off);
+                if (Y16) ringB4[kl] = vol_load(Bf + off);
+                else if (BITS) ringB[kl] = *(const uint32_t*)(Bf + bit_off(u + PF));
             }
+            step(u, i & 1, cw, cy, cb, cb4);
+        };
+        int u0 = 0;
+        for (; u0 + UN <= nsteps; u0 += UN) {
+#pragma unroll
+            for (int i = 0; i < UN; i++) ring_step(u0 + i, i);
         }
 #pragma unroll
-        for (int i = 0; i < PF - 1; i++)
-            if (u0 + i < nsteps) step(u0 + i, ringC[i], ringY[MODE == 2 ? i : 0], ringB[MODE == 2 && BITS && !Y16 ? i : 0], ringB4[MODE == 2 && Y16 ? i : 0]);   // workgroup-uniform
+        for (int i = 0; i < UN - 1; i++)
+            if (u0 + i < nsteps) ring_step(u0 + i, i);                               // workgroup-uniform
         if constexpr (RECLDS) {
             if ((nsteps & 7) != 0) flush_records(nsteps - 1);  // the last, partial group of steps
         }
