@@ -1,0 +1,88 @@
+// capi_device.hip -- shared pieces of the device-pointer entry points (capi_device.h): pointer checks, capture refusal,
+// the event join with the caller's stream and the status kernel.
+#include "capi_device.h"
+#include <algorithm>
+
+namespace fsgm {
+
+fsgm_status device_check_stream(hipStream_t s, const char* who) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    const hipError_t e = hipStreamIsCapturing(s, &cs);
+    if (e == hipErrorStreamCaptureImplicit || (e == hipSuccess && cs != hipStreamCaptureStatusNone)) {
+        (void)hipGetLastError();
+        return fail(FSGM_ERR_UNSUPPORTED, "%s: the stream is being captured into a graph (graph capture is not supported)", who);
+    }
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(FSGM_ERR_HIP, "%s: hipStreamIsCapturing failed: %s", who, hipGetErrorString(e));
+    }
+    return FSGM_OK;
+}
+
+fsgm_status device_check_ptr(const void* p, size_t bytes, size_t align, int device, bool required, const char* who, const char* what) {
+    if (!p) {
+        if (required) return fail(FSGM_ERR_INVALID, "%s: %s is NULL", who, what);
+        return FSGM_OK;
+    }
+    if ((uintptr_t)p % align != 0)
+        return fail(FSGM_ERR_INVALID, "%s: %s (%p) is not aligned to %zu bytes", who, what, p, align);
+    hipPointerAttribute_t a{};
+    hipError_t e = hipPointerGetAttributes(&a, p);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(FSGM_ERR_INVALID, "%s: %s (%p) is not memory known to the HIP runtime (%s)", who, what, p, hipGetErrorString(e));
+    }
+    if (a.type != hipMemoryTypeDevice)
+        return fail(FSGM_ERR_INVALID, "%s: %s (%p) is not device memory (memory type %d): pass HBM of device %d", who, what, p, (int)a.type, device);
+    if (a.device != device)
+        return fail(FSGM_ERR_INVALID, "%s: %s (%p) lives on device %d, the call runs on device %d", who, what, p, a.device, device);
+    void* base = nullptr;
+    size_t size = 0;
+    e = hipMemGetAddressRange(&base, &size, const_cast<void*>(p));
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(FSGM_ERR_INVALID, "%s: %s (%p): no allocation found (%s)", who, what, p, hipGetErrorString(e));
+    }
+    const size_t used = (size_t)((const char*)p - (const char*)base);
+    if (used > size || size - used < bytes)
+        return fail(FSGM_ERR_INVALID, "%s: %s (%p) needs %zu bytes, its allocation holds %zu from there", who, what, p, bytes, size - std::min(used, size));
+    return FSGM_OK;
+}
+
+fsgm_status DeviceJoin::ensure() {
+    if (!in) FSGM_HIP(hipEventCreateWithFlags(&in, hipEventDisableTiming));
+    if (!out) FSGM_HIP(hipEventCreateWithFlags(&out, hipEventDisableTiming));
+    return FSGM_OK;
+}
+
+void DeviceJoin::destroy() {
+    if (in) (void)hipEventDestroy(in);
+    if (out) (void)hipEventDestroy(out);
+    in = out = nullptr;
+}
+
+fsgm_status DeviceJoin::enter(hipStream_t caller, hipStream_t plan) {
+    FSGM_HIP(hipEventRecord(in, caller));
+    FSGM_HIP(hipStreamWaitEvent(plan, in, 0));
+    return FSGM_OK;
+}
+
+fsgm_status DeviceJoin::leave(hipStream_t plan, hipStream_t caller) {
+    FSGM_HIP(hipEventRecord(out, plan));
+    FSGM_HIP(hipStreamWaitEvent(caller, out, 0));
+    return FSGM_OK;
+}
+
+__global__ __launch_bounds__(64) void device_status_kernel(uint32_t* __restrict__ flag, int32_t* __restrict__ status) {
+    if (threadIdx.x != 0) return;
+    uint32_t f = 0;
+    if (flag) { f = *flag; *flag = 0; }
+    if (status) *status = f != 0 ? (int32_t)FSGM_ERR_HIP : 0;
+}
+
+void launch_device_status(hipStream_t st, uint32_t* flag, int32_t* status) {
+    if (!flag && !status) return;
+    hipLaunchKernelGGL(device_status_kernel, dim3(1), dim3(64), 0, st, flag, status);
+}
+
+}  // namespace fsgm

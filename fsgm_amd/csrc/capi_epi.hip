@@ -1,6 +1,7 @@
 // capi_epi.hip -- C ABI for the calc_cost_sgm path: device-resident plan + host-pointer entry
 // points (what the calc_cost_sgm mexFunction gateway calls).  See include/fsgm.h.
 #include "capi_common.h"
+#include "capi_device.h"
 #include "epi_kernels.h"
 #include "geometry_kernels.h"
 #include "pyramid_kernels.h"
@@ -70,6 +71,7 @@ struct fsgm_epi_plan {
     int cus = 256;                       // compute units of the device (band sweeps: one workgroup per frame, two per CU)
     int kernel_kind = AGG_GENERIC;
     bool packed = false;
+    DeviceJoin join;                     // device-pointer entry points: the events that order the plan's stream with the caller's
 };
 
 // batch sizes at which auto mode moves from the line kernels to the parallel sweeps and on to the full sweep pipeline
@@ -275,6 +277,7 @@ void fsgm_epi_plan_destroy(fsgm_epi_plan* p) {
     if (p->ev1) (void)hipEventDestroy(p->ev1);
     for (hipEvent_t e : {p->ev_fork, p->ev_h, p->ev_b, p->ev_c, p->ev_hl[0], p->ev_hl[1], p->ev_hl[2]})
         if (e) (void)hipEventDestroy(e);
+    p->join.destroy();
     for (hipStream_t st : {p->stream, p->stream_h, p->stream_b, p->stream_c})
         if (st) (void)hipStreamDestroy(st);
     delete p;
@@ -1334,6 +1337,145 @@ fsgm_status fsgm_epipolar_sgm_of_host(const uint8_t* I0, const uint8_t* I1, int3
     FSGM_HIP(hipStreamSynchronize(p->stream));
     guard.dismiss();
     return FSGM_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// device-pointer entry points (include/fsgm.h): the caller's HBM arrays stand in for the plan's image, map and result buffers
+// for the length of one enqueue; the plan's stream is joined with the caller's at both ends.
+// ---------------------------------------------------------------------------------------------
+static fsgm_status epi_device_args(const char* who, int32_t n, const fsgm_epi_in* in, const fsgm_epi_out* out) {
+    FSGM_REQUIRE(n >= 1, "%s: n_frames must be >= 1 (got %d)", who, n);
+    FSGM_REQUIRE(in && out, "%s: null argument", who);
+    FSGM_REQUIRE(in->I1 && in->I2 && in->pixelPosD0 && in->normDir && in->offset, "%s: null input", who);
+    FSGM_REQUIRE(out->bestD && out->minC, "%s: null output", who);
+    FSGM_REQUIRE(in->width >= 1 && in->height >= 1 && in->dMax >= 1, "%s: width/height/dMax must be >= 1 (got %d x %d x %d)", who,
+                 in->width, in->height, in->dMax);
+    if (out->C || out->S) return fail(FSGM_ERR_UNSUPPORTED, "%s: the debug taps C / S are not offered on device pointers", who);
+    return FSGM_OK;
+}
+
+// What a warm call must not do -- allocate, upload a table, synchronise -- happens here on a plan's first call, before the
+// join with the caller's stream.
+static fsgm_status epi_device_prepare(fsgm_epi_plan* p, int P1, int P2, double vMax) {
+    fsgm_status st;
+    if ((st = fsgm_epi_plan_set_penalties(p, P1, P2, vMax)) != FSGM_OK) return st;
+    if ((st = ensure_cost_buffers(p)) != FSGM_OK) return st;
+    if ((st = ensure_vz(p)) != FSGM_OK) return st;
+    if ((st = prepare(p, FSGM_STAGE_ALL)) != FSGM_OK) return st;
+    return p->join.ensure();
+}
+
+// the status word, then the caller's stream waits for the plan's (also after a failed enqueue: whatever was queued stays
+// ordered before the caller's later work)
+static fsgm_status epi_device_finish(fsgm_epi_plan* p, hipStream_t cs, int32_t* status, fsgm_status st) {
+    if (st == FSGM_OK) launch_device_status(p->stream, p->dBandErr, status);
+    const fsgm_status js = p->join.leave(p->stream, cs);
+    if (st != FSGM_OK) return st;
+    FSGM_HIP(hipGetLastError());
+    return js;
+}
+
+static fsgm_status epi_run_device(const char* who, fsgm_epi_plan* p, int32_t n, const fsgm_epi_in* in, const fsgm_epi_out* out,
+                                  hipStream_t cs, int32_t* status) {
+    FSGM_REQUIRE(n == p->batch, "%s: n_frames %d differs from the plan's batch %d", who, n, p->batch);
+    FSGM_REQUIRE(in->width == p->W && in->height == p->H && in->dMax == p->D, "%s: shape %d x %d x %d differs from the plan's %d x %d x %d",
+                 who, in->width, in->height, in->dMax, p->W, p->H, p->D);
+    const int dev = p->prm.device;
+    const size_t np = (size_t)n * p->NP;
+    const bool fb = p->prm.fb_check != 0;
+    FSGM_HIP(hipSetDevice(dev));
+    fsgm_status st;
+    if ((st = device_check_stream(cs, who)) != FSGM_OK) return st;
+    if ((st = device_check_ptr(in->I1, np, 1, dev, true, who, "I1")) != FSGM_OK ||
+        (st = device_check_ptr(in->I2, np, 1, dev, true, who, "I2")) != FSGM_OK ||
+        (st = device_check_ptr(in->pixelPosD0, np * 16, 8, dev, true, who, "pixelPosD0")) != FSGM_OK ||
+        (st = device_check_ptr(in->normDir, np * 16, 8, dev, true, who, "normDir")) != FSGM_OK ||
+        (st = device_check_ptr(in->offset, np * 8, 8, dev, true, who, "offset")) != FSGM_OK ||
+        (st = device_check_ptr(out->bestD, np * 4, 4, dev, true, who, "bestD")) != FSGM_OK ||
+        (st = device_check_ptr(out->minC, np * 4, 4, dev, true, who, "minC")) != FSGM_OK ||
+        (fb && (st = device_check_ptr(out->conf, np, 1, dev, false, who, "conf")) != FSGM_OK) ||
+        (fb && (st = device_check_ptr(out->bestD2, np * 4, 4, dev, false, who, "bestD2")) != FSGM_OK) ||
+        (st = device_check_ptr(status, 4, 4, dev, false, who, "status")) != FSGM_OK)
+        return st;
+    if ((st = epi_device_prepare(p, in->P1, in->P2, in->vMax)) != FSGM_OK) return st;
+    if ((st = p->join.enter(cs, p->stream)) != FSGM_OK) return st;
+    {
+        Bind<uint8_t> i1(p->dI1, const_cast<uint8_t*>(in->I1)), i2(p->dI2, const_cast<uint8_t*>(in->I2));
+        Bind<double> pd0(p->dPd0, const_cast<double*>(in->pixelPosD0)), nd(p->dNd, const_cast<double*>(in->normDir));
+        Bind<double> off(p->dOff, const_cast<double*>(in->offset));
+        Bind<uint32_t> bd(p->dBestD, out->bestD), mc(p->dMinC, out->minC), d2(p->dD2, fb ? out->bestD2 : nullptr);
+        Bind<uint8_t> conf(p->dConf, fb ? out->conf : nullptr);
+        st = enqueue(p, FSGM_STAGE_ALL);
+    }
+    return epi_device_finish(p, cs, status, st);
+}
+
+fsgm_status fsgm_epi_plan_run_device(fsgm_epi_plan* p, int32_t n, const fsgm_epi_in* in, const fsgm_epi_out* out, void* stream,
+                                     int32_t* status) {
+    const char* who = "fsgm_epi_plan_run_device";
+    FSGM_REQUIRE(p, "%s: null plan", who);
+    fsgm_status st = epi_device_args(who, n, in, out);
+    if (st != FSGM_OK) return st;
+    return epi_run_device(who, p, n, in, out, (hipStream_t)stream, status);
+}
+
+fsgm_status fsgm_calc_cost_sgm_device(int32_t n, const fsgm_epi_in* in, const fsgm_epi_out* out, const fsgm_epi_params* prm,
+                                      void* stream, int32_t* status) {
+    const char* who = "fsgm_calc_cost_sgm_device";
+    fsgm_status st = epi_device_args(who, n, in, out);
+    if (st != FSGM_OK) return st;
+    const fsgm_epi_params pr = prm ? *prm : fsgm_epi_params_default();
+    FSGM_DEVICE_SLOT(pr.device);
+    std::lock_guard<std::mutex> lk(g_epi.mu[pr.device]);
+    fsgm_epi_plan* p = nullptr;
+    if ((st = cached_plan(&p, in->width, in->height, in->dMax, n, pr)) != FSGM_OK) return st;
+    return epi_run_device(who, p, n, in, out, (hipStream_t)stream, status);
+}
+
+fsgm_status fsgm_epipolar_sgm_of_device(int32_t n, const uint8_t* I0, const uint8_t* I1, int32_t W, int32_t H, int32_t channels,
+                                        const fsgm_epi_geometry* g, int32_t dMax, double vMax, const fsgm_epi_params* prm,
+                                        double* flow, uint32_t* minC, void* stream, int32_t* status) {
+    const char* who = "fsgm_epipolar_sgm_of_device";
+    FSGM_REQUIRE(n >= 1, "%s: n_frames must be >= 1 (got %d)", who, n);
+    FSGM_REQUIRE(I0 && I1 && g && flow, "%s: null argument", who);
+    FSGM_REQUIRE(W >= 1 && H >= 1 && dMax >= 1, "%s: width/height/dMax must be >= 1 (got %d x %d x %d)", who, W, H, dMax);
+    FSGM_REQUIRE(channels == 1 || channels == 3, "%s: channels must be 1 (gray) or 3 (RGB planes), got %d", who, channels);
+    fsgm_epi_params pr = prm ? *prm : fsgm_epi_params_default();
+    FSGM_REQUIRE(pr.vz_to_disp && !pr.fb_check, "%s: the flow needs disparities (vz_to_disp = 1, fb_check = 0)", who);
+    FSGM_DEVICE_SLOT(pr.device);
+    std::lock_guard<std::mutex> lk(g_epi.mu[pr.device]);
+    fsgm_epi_plan* p = nullptr;
+    fsgm_status st = cached_plan(&p, W, H, dMax, n, pr);
+    if (st != FSGM_OK) return st;
+    const int dev = pr.device;
+    const size_t NP = p->NP, np = (size_t)n * NP;
+    hipStream_t cs = (hipStream_t)stream;
+    FSGM_HIP(hipSetDevice(dev));
+    if ((st = device_check_stream(cs, who)) != FSGM_OK) return st;
+    if ((st = device_check_ptr(I0, np * channels, 1, dev, true, who, "I0")) != FSGM_OK ||
+        (st = device_check_ptr(I1, np * channels, 1, dev, true, who, "I1")) != FSGM_OK ||
+        (st = device_check_ptr(flow, np * 24, 8, dev, true, who, "flow")) != FSGM_OK ||
+        (st = device_check_ptr(minC, np * 4, 4, dev, false, who, "minC")) != FSGM_OK ||
+        (st = device_check_ptr(status, 4, 4, dev, false, who, "status")) != FSGM_OK)
+        return st;
+    if ((st = ensure_driver_buffers(p, 1)) != FSGM_OK) return st;                        // (RGB goes to gray straight from the caller's planes)
+    if ((st = epi_device_prepare(p, 6, 64, vMax)) != FSGM_OK) return st;                  // epipolar_sgm_of.m:19
+    if ((st = p->join.enter(cs, p->stream)) != FSGM_OK) return st;
+    {
+        Bind<uint8_t> i1(p->dI1, channels == 1 ? const_cast<uint8_t*>(I0) : nullptr), i2(p->dI2, channels == 1 ? const_cast<uint8_t*>(I1) : nullptr);
+        Bind<uint32_t> mc(p->dMinC, minC);
+        if (channels == 3) {                                                              // epipolar_sgm_of.m:35-38
+            launch_pyr_gray(p->stream, I0, p->dI1, W, H, n);
+            launch_pyr_gray(p->stream, I1, p->dI2, W, H, n);
+        }
+        for (int f = 0; f < n; f++)                                                       // :24, the geometry by value
+            launch_epi_maps(p->stream, geom_args(&g[f], W, H, p->dPd0 + f * 2 * NP, p->dNd + f * 2 * NP, p->dOff + f * NP, p->dRflow + f * 2 * NP));
+        st = enqueue(p, FSGM_STAGE_ALL);                                                  // :45
+        if (st == FSGM_OK)
+            for (int f = 0; f < n; f++)                                                   // :46-51
+                launch_epi_flow(p->stream, p->dBestD + f * NP, p->dNd + f * 2 * NP, p->dRflow + f * 2 * NP, flow + f * 3 * NP, W, H);
+    }
+    return epi_device_finish(p, cs, status, st);
 }
 
 }  // extern "C"

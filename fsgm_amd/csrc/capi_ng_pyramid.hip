@@ -4,6 +4,7 @@
 // The candidate volume (12 B per entry) and the sum volume are shared by the levels -- they run in order on
 // one stream -- and sized for the finest.
 #include "capi_common.h"
+#include "capi_device.h"
 #include "epi_kernels.h"
 #include "ng_kernels.h"
 #include "pyramid_kernels.h"
@@ -35,6 +36,7 @@ struct fsgm_ng_pyramid_plan {
     Cand* dC = nullptr;
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    DeviceJoin join;                                 // device-pointer entry point: ordering with the caller's stream
 };
 
 extern "C" {
@@ -59,6 +61,7 @@ void fsgm_ng_pyramid_plan_destroy(fsgm_ng_pyramid_plan* p) {
     for (void* b : one) if (b) (void)hipFree(b);
     if (p->ev0) (void)hipEventDestroy(p->ev0);
     if (p->ev1) (void)hipEventDestroy(p->ev1);
+    p->join.destroy();
     if (p->stream) (void)hipStreamDestroy(p->stream);
     delete p;
 }
@@ -265,24 +268,33 @@ void fsgm_ng_pyramid_shutdown_internal(void) {
     }
 }
 
-fsgm_status fsgm_pyramidal_sgm_ng_host(const uint8_t* I0, const uint8_t* I1, int32_t width, int32_t height, int32_t channels,
-                                       const fsgm_ng_pyramid_params* prm, double* flow, uint32_t* minC, double* const* flowPyd) {
-    FSGM_REQUIRE(I0 && I1 && prm && flow, "fsgm_pyramidal_sgm_ng: null argument");
-    FSGM_DEVICE_SLOT(prm->device);
-    std::lock_guard<std::mutex> lk(g_ngpyr.mu[prm->device]);
+// the cached plan of this shape, parameter set and batch (the caller holds the device's lock)
+static fsgm_status ng_pyramid_cached(fsgm_ng_pyramid_plan** out, int W, int H, int channels, const fsgm_ng_pyramid_params* prm, int batch) {
     std::vector<fsgm_ng_pyramid_plan*>& g_ngpyr_cache = g_ngpyr.v[prm->device];
     fsgm_ng_pyramid_plan* p = nullptr;
     for (fsgm_ng_pyramid_plan* q : g_ngpyr_cache)
-        if (q->W == width && q->H == height && q->channels == channels && q->batch == 1 && memcmp(&q->prm, prm, sizeof *prm) == 0) p = q;
-    fsgm_status st;
+        if (q->W == W && q->H == H && q->channels == channels && q->batch == batch && memcmp(&q->prm, prm, sizeof *prm) == 0) p = q;
     if (!p) {
-        if ((st = fsgm_ng_pyramid_plan_create(&p, width, height, channels, prm)) != FSGM_OK) return st;
+        fsgm_status st = fsgm_ng_pyramid_plan_create_batch(&p, W, H, channels, batch, prm);
+        if (st != FSGM_OK) return st;
         if (g_ngpyr_cache.size() >= 2) {
             fsgm_ng_pyramid_plan_destroy(g_ngpyr_cache.front());
             g_ngpyr_cache.erase(g_ngpyr_cache.begin());
         }
         g_ngpyr_cache.push_back(p);
     }
+    *out = p;
+    return FSGM_OK;
+}
+
+fsgm_status fsgm_pyramidal_sgm_ng_host(const uint8_t* I0, const uint8_t* I1, int32_t width, int32_t height, int32_t channels,
+                                       const fsgm_ng_pyramid_params* prm, double* flow, uint32_t* minC, double* const* flowPyd) {
+    FSGM_REQUIRE(I0 && I1 && prm && flow, "fsgm_pyramidal_sgm_ng: null argument");
+    FSGM_DEVICE_SLOT(prm->device);
+    std::lock_guard<std::mutex> lk(g_ngpyr.mu[prm->device]);
+    fsgm_ng_pyramid_plan* p = nullptr;
+    fsgm_status st;
+    if ((st = ng_pyramid_cached(&p, width, height, channels, prm, 1)) != FSGM_OK) return st;
     // one stream-ordered sequence, a single host wait (see fsgm_pyramidal_sgm_host)
     FSGM_HIP(hipSetDevice(p->device));
     StreamGuard guard(p->stream);
@@ -300,6 +312,47 @@ fsgm_status fsgm_pyramidal_sgm_ng_host(const uint8_t* I0, const uint8_t* I1, int
     FSGM_HIP(hipStreamSynchronize(p->stream));
     guard.dismiss();
     return FSGM_OK;
+}
+
+// device pointers in and out, ordered on the caller's stream (include/fsgm.h): the level-1 images are read in place by the
+// first reduce / gray / census kernels, the level-1 flow and minC are written in place -- no copy at either end
+fsgm_status fsgm_pyramidal_sgm_ng_device(int32_t n, const uint8_t* I0, const uint8_t* I1, int32_t width, int32_t height, int32_t channels,
+                                         const fsgm_ng_pyramid_params* prm, double* flow, uint32_t* minC, void* stream, int32_t* status) {
+    const char* who = "fsgm_pyramidal_sgm_ng_device";
+    FSGM_REQUIRE(n >= 1, "%s: n_frames must be >= 1 (got %d)", who, n);
+    FSGM_REQUIRE(I0 && I1 && prm && flow, "%s: null argument", who);
+    FSGM_REQUIRE(width >= 1 && height >= 1, "%s: width/height must be >= 1 (got %d x %d)", who, width, height);
+    FSGM_REQUIRE(channels == 1 || channels == 3, "%s: channels must be 1 (gray) or 3 (RGB planes), got %d", who, channels);
+    FSGM_DEVICE_SLOT(prm->device);
+    std::lock_guard<std::mutex> lk(g_ngpyr.mu[prm->device]);
+    fsgm_ng_pyramid_plan* p = nullptr;
+    fsgm_status st;
+    if ((st = ng_pyramid_cached(&p, width, height, channels, prm, n)) != FSGM_OK) return st;
+    const int dev = p->device;
+    const size_t np = (size_t)n * width * height;
+    hipStream_t cs = (hipStream_t)stream;
+    FSGM_HIP(hipSetDevice(dev));
+    if ((st = device_check_stream(cs, who)) != FSGM_OK) return st;
+    if ((st = device_check_ptr(I0, np * channels, 1, dev, true, who, "I0")) != FSGM_OK ||
+        (st = device_check_ptr(I1, np * channels, 1, dev, true, who, "I1")) != FSGM_OK ||
+        (st = device_check_ptr(flow, np * 16, 8, dev, true, who, "flow")) != FSGM_OK ||
+        (st = device_check_ptr(minC, np * 4, 4, dev, false, who, "minC")) != FSGM_OK ||
+        (st = device_check_ptr(status, 4, 4, dev, false, who, "status")) != FSGM_OK)
+        return st;
+    if ((st = p->join.ensure()) != FSGM_OK) return st;
+    if ((st = p->join.enter(cs, p->stream)) != FSGM_OK) return st;
+    {
+        Bind<uint8_t> i0(channels == 3 ? p->dP0[0] : p->dG0[0], const_cast<uint8_t*>(I0));
+        Bind<uint8_t> i1(channels == 3 ? p->dP1[0] : p->dG1[0], const_cast<uint8_t*>(I1));
+        Bind<double> fl(p->dFlow[0], flow);
+        Bind<uint32_t> mc(p->dMinC[0], minC);
+        st = ng_pyramid_enqueue(p);
+    }
+    if (st == FSGM_OK) launch_device_status(p->stream, nullptr, status);
+    const fsgm_status js = p->join.leave(p->stream, cs);
+    if (st != FSGM_OK) return st;
+    FSGM_HIP(hipGetLastError());
+    return js;
 }
 
 }  // extern "C"

@@ -3,6 +3,7 @@
 // uploads the image pair and downloads the flow; nothing crosses PCIe between levels (the
 // reference's loop does one MEX call, i.e. one round trip, per level: pyramidal_sgm.m:37-75).
 #include "capi_common.h"
+#include "capi_device.h"
 #include "pyd_kernels.h"
 #include "pyd_plan.h"
 #include "pyramid_kernels.h"
@@ -21,6 +22,7 @@ struct fsgm_pyramid_plan {
     std::vector<double*> dFlow;                      // mvPyd{l}: [2][h][w]
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    DeviceJoin join;                                 // device-pointer entry point: ordering with the caller's stream
 };
 
 extern "C" {
@@ -48,6 +50,7 @@ void fsgm_pyramid_plan_destroy(fsgm_pyramid_plan* p) {
     for (double* b : p->dFlow) if (b) (void)hipFree(b);
     if (p->ev0) (void)hipEventDestroy(p->ev0);
     if (p->ev1) (void)hipEventDestroy(p->ev1);
+    p->join.destroy();
     if (p->stream) (void)hipStreamDestroy(p->stream);
     delete p;
 }
@@ -257,24 +260,33 @@ void fsgm_pyramid_shutdown_internal(void) {
     }
 }
 
-fsgm_status fsgm_pyramidal_sgm_host(const uint8_t* I0, const uint8_t* I1, int32_t width, int32_t height, int32_t channels,
-                                    const fsgm_pyramid_params* prm, double* mv, uint32_t* minC, double* const* mvPyd) {
-    FSGM_REQUIRE(I0 && I1 && prm && mv, "fsgm_pyramidal_sgm: null argument");
-    FSGM_DEVICE_SLOT(prm->device);
-    std::lock_guard<std::mutex> lk(g_pyr.mu[prm->device]);
+// the cached plan of this shape, parameter set and batch (the caller holds the device's lock)
+static fsgm_status pyramid_cached(fsgm_pyramid_plan** out, int W, int H, int channels, const fsgm_pyramid_params* prm, int batch) {
     std::vector<fsgm_pyramid_plan*>& g_pyr_cache = g_pyr.v[prm->device];
     fsgm_pyramid_plan* p = nullptr;
     for (fsgm_pyramid_plan* q : g_pyr_cache)
-        if (q->W == width && q->H == height && q->channels == channels && q->batch == 1 && memcmp(&q->prm, prm, sizeof *prm) == 0) p = q;
-    fsgm_status st;
+        if (q->W == W && q->H == H && q->channels == channels && q->batch == batch && memcmp(&q->prm, prm, sizeof *prm) == 0) p = q;
     if (!p) {
-        if ((st = fsgm_pyramid_plan_create(&p, width, height, channels, prm)) != FSGM_OK) return st;
+        fsgm_status st = fsgm_pyramid_plan_create_batch(&p, W, H, channels, prm, batch);
+        if (st != FSGM_OK) return st;
         if (g_pyr_cache.size() >= 2) {
             fsgm_pyramid_plan_destroy(g_pyr_cache.front());
             g_pyr_cache.erase(g_pyr_cache.begin());
         }
         g_pyr_cache.push_back(p);
     }
+    *out = p;
+    return FSGM_OK;
+}
+
+fsgm_status fsgm_pyramidal_sgm_host(const uint8_t* I0, const uint8_t* I1, int32_t width, int32_t height, int32_t channels,
+                                    const fsgm_pyramid_params* prm, double* mv, uint32_t* minC, double* const* mvPyd) {
+    FSGM_REQUIRE(I0 && I1 && prm && mv, "fsgm_pyramidal_sgm: null argument");
+    FSGM_DEVICE_SLOT(prm->device);
+    std::lock_guard<std::mutex> lk(g_pyr.mu[prm->device]);
+    fsgm_pyramid_plan* p = nullptr;
+    fsgm_status st;
+    if ((st = pyramid_cached(&p, width, height, channels, prm, 1)) != FSGM_OK) return st;
     // One call = one stream-ordered sequence with a single host wait (like fsgm_calc_cost_sgm_batch_host): the image pair goes up
     // asynchronously, the level loop follows, every requested map comes down behind it.  (Round 3's form waited after the
     // upload, after the run and once per downloaded map, with blocking copies: 6.3 ms per call around 1.4 ms of kernels.)
@@ -294,6 +306,47 @@ fsgm_status fsgm_pyramidal_sgm_host(const uint8_t* I0, const uint8_t* I1, int32_
     FSGM_HIP(hipStreamSynchronize(p->stream));
     guard.dismiss();
     return FSGM_OK;
+}
+
+// device pointers in and out, ordered on the caller's stream (include/fsgm.h): the level-1 images are read in place by the
+// first reduce / gray / census kernels, the level-1 flow and minC are written in place -- no copy at either end
+fsgm_status fsgm_pyramidal_sgm_device(int32_t n, const uint8_t* I0, const uint8_t* I1, int32_t width, int32_t height, int32_t channels,
+                                      const fsgm_pyramid_params* prm, double* mv, uint32_t* minC, void* stream, int32_t* status) {
+    const char* who = "fsgm_pyramidal_sgm_device";
+    FSGM_REQUIRE(n >= 1, "%s: n_frames must be >= 1 (got %d)", who, n);
+    FSGM_REQUIRE(I0 && I1 && prm && mv, "%s: null argument", who);
+    FSGM_REQUIRE(width >= 1 && height >= 1, "%s: width/height must be >= 1 (got %d x %d)", who, width, height);
+    FSGM_REQUIRE(channels == 1 || channels == 3, "%s: channels must be 1 (gray) or 3 (RGB planes), got %d", who, channels);
+    FSGM_DEVICE_SLOT(prm->device);
+    std::lock_guard<std::mutex> lk(g_pyr.mu[prm->device]);
+    fsgm_pyramid_plan* p = nullptr;
+    fsgm_status st;
+    if ((st = pyramid_cached(&p, width, height, channels, prm, n)) != FSGM_OK) return st;
+    const int dev = p->device;
+    const size_t np = (size_t)n * width * height;
+    hipStream_t cs = (hipStream_t)stream;
+    FSGM_HIP(hipSetDevice(dev));
+    if ((st = device_check_stream(cs, who)) != FSGM_OK) return st;
+    if ((st = device_check_ptr(I0, np * channels, 1, dev, true, who, "I0")) != FSGM_OK ||
+        (st = device_check_ptr(I1, np * channels, 1, dev, true, who, "I1")) != FSGM_OK ||
+        (st = device_check_ptr(mv, np * 16, 8, dev, true, who, "mv")) != FSGM_OK ||
+        (st = device_check_ptr(minC, np * 4, 4, dev, false, who, "minC")) != FSGM_OK ||
+        (st = device_check_ptr(status, 4, 4, dev, false, who, "status")) != FSGM_OK)
+        return st;
+    if ((st = p->join.ensure()) != FSGM_OK) return st;
+    if ((st = p->join.enter(cs, p->stream)) != FSGM_OK) return st;
+    {
+        Bind<uint8_t> i0(channels == 3 ? p->dP0[0] : p->lv[0]->dI1, const_cast<uint8_t*>(I0));
+        Bind<uint8_t> i1(channels == 3 ? p->dP1[0] : p->lv[0]->dI2, const_cast<uint8_t*>(I1));
+        Bind<double> fl(p->dFlow[0], mv);
+        Bind<uint32_t> mc(p->lv[0]->dMinC, minC);
+        st = pyramid_enqueue(p);
+    }
+    if (st == FSGM_OK) launch_device_status(p->stream, nullptr, status);
+    const fsgm_status js = p->join.leave(p->stream, cs);
+    if (st != FSGM_OK) return st;
+    FSGM_HIP(hipGetLastError());
+    return js;
 }
 
 }  // extern "C"

@@ -127,6 +127,8 @@ class EpiPlan:
     def __init__(self, width, height, dMax, batch=1, *, paths=4, subpixel=1, vz_to_disp=1, device=0, fb_check=0):
         self.lib = _lib.load()
         self.W, self.H, self.D, self.batch, self.paths = int(width), int(height), int(dMax), int(batch), int(paths)
+        self.device, self.fb_check = int(device), int(fb_check)
+        self.penalties = (6, 64, 0.3)                        # (P1, P2, vMax) of a fresh plan (epipolar_sgm_of.m:16,19)
         self._h = C.c_void_p()
         prm = _params(paths, subpixel, vz_to_disp, device, fb_check)
         check(self.lib.fsgm_epi_plan_create(C.byref(self._h), self.W, self.H, self.D, self.batch, C.byref(prm)))
@@ -150,6 +152,7 @@ class EpiPlan:
 
     def set_penalties(self, P1, P2, vMax=0.3):
         check(self.lib.fsgm_epi_plan_set_penalties(self._h, int(P1), int(P2), float(vMax)))
+        self.penalties = (int(P1), int(P2), float(vMax))
 
     def set_agg_mode(self, mode):
         """0 auto, 1 per-direction line kernels, 2 fused pipeline when eligible, 3 parallel sweeps (8 paths) when eligible,
@@ -219,6 +222,12 @@ class EpiPlan:
         ms = C.c_float()
         check(self.lib.fsgm_epi_plan_time(self._h, int(stages), int(warmup), int(iters), C.byref(ms)))
         return float(ms.value)
+
+    def run_tensors(self, I1, I2, pd0, nd, off, **kw):
+        """All frames of the plan from torch tensors on the GPU to torch tensors on the GPU, ordered on the current stream
+        (fsgm_amd.torch_ops.run_tensors; import torch before the library is loaded)."""
+        from . import torch_ops
+        return torch_ops.run_tensors(self, I1, I2, pd0, nd, off, **kw)
 
     @property
     def kernel_name(self):

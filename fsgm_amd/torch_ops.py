@@ -1,0 +1,354 @@
+"""torch tensors on the GPU in, torch tensors on the GPU out, ordered on the caller's current stream: the device-pointer entry
+points of include/fsgm.h ("Device-pointer entry points") as torch custom ops and friendly wrappers.
+
+    import torch                                   # first: the library must bind to torch's HIP runtime
+    from fsgm_amd import torch_ops
+    bestD, minC = torch_ops.calc_cost_sgm(I1, I2, 128, 0.3, pd0, nd, off, 6, 64, paths=8)   # cuda tensors
+
+No host<->device copy and no host wait once a plan for the shape exists: the work is queued behind what the current stream
+already holds, and what is queued on that stream afterwards runs after it.  Ops registered: fsgm::calc_cost_sgm,
+fsgm::epipolar_sgm_of, fsgm::pyramidal_sgm, fsgm::pyramidal_sgm_ng (each also returns a 0-d int32 status tensor: 0, or
+FSGM_ERR_HIP when an aggregation hand-off gave up; check=True in the wrappers synchronises and raises on it).
+
+One process must hold one HIP runtime.  torch brings its own libamdhip64; libfsgm_hip.so binds to it by soname when torch is
+imported first.  When the library was loaded first, torch afterwards maps a second runtime, and a stream or pointer of one
+is meaningless to the other: importing this module then raises ImportError.
+"""
+import torch  # noqa: I001 -- first, before the library: its HIP runtime is the one libfsgm_hip.so must bind to
+
+import ctypes as C
+from typing import List, Tuple
+
+import numpy as np
+
+from . import _lib
+from ._lib import EpiIn, EpiOut, EpiParams, FsgmError
+from .epi import EpiGeometry, _params as _epi_params
+from .pyramid import PyramidParams, NgPyramidParams, _bind as _bind_pyramid, _bind_ng
+
+FSGM_ERR_HIP = 2
+
+
+def hip_runtimes():
+    """The distinct libamdhip64 files mapped into this process (/proc/self/maps)."""
+    files = set()
+    with open("/proc/self/maps") as f:
+        for line in f:
+            parts = line.split(None, 5)
+            if len(parts) == 6 and "libamdhip64" in parts[5].rsplit("/", 1)[-1]:
+                files.add(parts[5].strip())
+    return sorted(files)
+
+
+_L = _lib.load()
+_runtimes = hip_runtimes()
+if len(_runtimes) != 1:
+    raise ImportError(
+        "fsgm_amd.torch_ops needs one HIP runtime in the process, found %d: %s.  libfsgm_hip.so was loaded before torch "
+        "(e.g. by fsgm_amd.load_library() or a compute call), so torch brought a second runtime whose streams and pointers the "
+        "library cannot use.  Import torch (or fsgm_amd.torch_ops) before anything that loads libfsgm_hip.so."
+        % (len(_runtimes), ", ".join(_runtimes) or "none"))
+
+_vp, _i32 = C.c_void_p, C.c_int32
+_bind_pyramid(_L)
+_bind_ng(_L)
+_L.fsgm_calc_cost_sgm_device.argtypes = [_i32, C.POINTER(EpiIn), C.POINTER(EpiOut), C.POINTER(EpiParams), _vp, _vp]
+_L.fsgm_epi_plan_run_device.argtypes = [_vp, _i32, C.POINTER(EpiIn), C.POINTER(EpiOut), _vp, _vp]
+_L.fsgm_epipolar_sgm_of_device.argtypes = [_i32, _vp, _vp, _i32, _i32, _i32, C.POINTER(EpiGeometry), _i32, C.c_double,
+                                           C.POINTER(EpiParams), _vp, _vp, _vp, _vp]
+_L.fsgm_pyramidal_sgm_device.argtypes = [_i32, _vp, _vp, _i32, _i32, _i32, C.POINTER(PyramidParams), _vp, _vp, _vp, _vp]
+_L.fsgm_pyramidal_sgm_ng_device.argtypes = [_i32, _vp, _vp, _i32, _i32, _i32, C.POINTER(NgPyramidParams), _vp, _vp, _vp, _vp]
+
+# the overridable fields of the pyramids' parameter structs, in the order the ops take them
+PYRAMID_FIELDS = ("P1", "P2", "aggHalfWinSize", "verSearchHalfWinSize", "horSearchHalfWinSize", "enableDiagonal", "totalPass", "adaptiveP2")
+NG_PYRAMID_FIELDS = ("P1", "P2", "halfSearchWinSize", "aggSize", "subPixelRefine")
+GEOMETRY_NUMBERS = 21            # F (9), H (9), epipole (2), direction (1) per frame
+
+
+def _p(t):
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def _ready(t):
+    """t itself when it is contiguous and aligned on its element size, else a contiguous copy (on the current stream)."""
+    if t.is_contiguous() and t.data_ptr() % t.element_size() == 0:
+        return t
+    return t.clone(memory_format=torch.contiguous_format)
+
+
+def _call(dev, fn, *args):
+    with torch.cuda.device(dev):                  # the library sets the HIP device of the calling thread: give it back
+        _lib.check(fn(*args))
+
+
+def _stream(dev):
+    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+def _u32(shape, dev):
+    return torch.empty(shape, dtype=torch.uint32, device=dev)
+
+
+def _status(dev):
+    return torch.empty((), dtype=torch.int32, device=dev)
+
+
+# ---------------------------------------------------------------------------------------------
+# custom ops: every tensor argument is batched (leading N) and on one GPU; outputs freshly allocated there
+# ---------------------------------------------------------------------------------------------
+@torch.library.custom_op("fsgm::calc_cost_sgm", mutates_args=())
+def _calc_cost_sgm_op(I1: torch.Tensor, I2: torch.Tensor, pd0: torch.Tensor, nd: torch.Tensor, off: torch.Tensor, dMax: int,
+                      vMax: float, P1: int, P2: int, paths: int, subpixel: int, vz_to_disp: int,
+                      fb_check: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    N, H, W = I1.shape
+    dev = I1.device
+    I1, I2, pd0, nd, off = (_ready(t) for t in (I1, I2, pd0, nd, off))
+    bestD, minC, status = _u32((N, H, W), dev), _u32((N, H, W), dev), _status(dev)
+    conf = torch.empty((N, H, W) if fb_check else (0,), dtype=torch.uint8, device=dev)
+    bestD2 = _u32((N, H, W) if fb_check else (0,), dev)
+    e, o = EpiIn(), EpiOut()
+    e.I1, e.I2, e.width, e.height, e.dMax, e.vMax = _p(I1), _p(I2), W, H, int(dMax), float(vMax)
+    e.pixelPosD0, e.normDir, e.offset, e.P1, e.P2 = _p(pd0), _p(nd), _p(off), int(P1), int(P2)
+    o.bestD, o.minC = _p(bestD), _p(minC)
+    if fb_check:
+        o.conf, o.bestD2 = _p(conf), _p(bestD2)
+    prm = _epi_params(paths, subpixel, vz_to_disp, dev.index, fb_check)
+    _call(dev, _L.fsgm_calc_cost_sgm_device, N, C.byref(e), C.byref(o), C.byref(prm), _stream(dev), _p(status))
+    return bestD, minC, conf, bestD2, status
+
+
+@_calc_cost_sgm_op.register_fake
+def _(I1, I2, pd0, nd, off, dMax, vMax, P1, P2, paths, subpixel, vz_to_disp, fb_check):
+    N, H, W = I1.shape
+    dev = I1.device
+    return (_u32((N, H, W), dev), _u32((N, H, W), dev),
+            torch.empty((N, H, W) if fb_check else (0,), dtype=torch.uint8, device=dev),
+            _u32((N, H, W) if fb_check else (0,), dev), _status(dev))
+
+
+@torch.library.custom_op("fsgm::epipolar_sgm_of", mutates_args=())
+def _epipolar_sgm_of_op(I0: torch.Tensor, I1: torch.Tensor, geometry: List[float], dMax: int, vMax: float,
+                        paths: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    N, H, W = I0.shape[0], I0.shape[-2], I0.shape[-1]
+    ch = 1 if I0.dim() == 3 else 3
+    dev = I0.device
+    if len(geometry) != N * GEOMETRY_NUMBERS:
+        raise ValueError(f"geometry must hold {GEOMETRY_NUMBERS} numbers per frame ({N * GEOMETRY_NUMBERS}), got {len(geometry)}")
+    I0, I1 = _ready(I0), _ready(I1)
+    flow, minC, status = torch.empty((N, 3, H, W), dtype=torch.float64, device=dev), _u32((N, H, W), dev), _status(dev)
+    g = (EpiGeometry * N)()
+    for f in range(N):
+        v = geometry[f * GEOMETRY_NUMBERS:(f + 1) * GEOMETRY_NUMBERS]
+        g[f].F[:] = [float(x) for x in v[0:9]]
+        g[f].H[:] = [float(x) for x in v[9:18]]
+        g[f].epipole[:] = [float(v[18]), float(v[19])]
+        g[f].direction = int(v[20] != 0)
+    prm = _epi_params(paths, 1, 1, dev.index, 0)
+    _call(dev, _L.fsgm_epipolar_sgm_of_device, N, _p(I0), _p(I1), W, H, ch, g, int(dMax), float(vMax), C.byref(prm),
+          _p(flow), _p(minC), _stream(dev), _p(status))
+    return flow, minC, status
+
+
+@_epipolar_sgm_of_op.register_fake
+def _(I0, I1, geometry, dMax, vMax, paths):
+    N, H, W = I0.shape[0], I0.shape[-2], I0.shape[-1]
+    dev = I0.device
+    return torch.empty((N, 3, H, W), dtype=torch.float64, device=dev), _u32((N, H, W), dev), _status(dev)
+
+
+def _pyramid_run(fn, prm, I0, I1):
+    N, H, W = I0.shape[0], I0.shape[-2], I0.shape[-1]
+    ch = 1 if I0.dim() == 3 else 3
+    dev = I0.device
+    prm.device = dev.index
+    I0, I1 = _ready(I0), _ready(I1)
+    mv, minC, status = torch.empty((N, 2, H, W), dtype=torch.float64, device=dev), _u32((N, H, W), dev), _status(dev)
+    _call(dev, fn, N, _p(I0), _p(I1), W, H, ch, C.byref(prm), _p(mv), _p(minC), _stream(dev), _p(status))
+    return mv, minC, status
+
+
+def _pyramid_fake(I0):
+    N, H, W = I0.shape[0], I0.shape[-2], I0.shape[-1]
+    dev = I0.device
+    return torch.empty((N, 2, H, W), dtype=torch.float64, device=dev), _u32((N, H, W), dev), _status(dev)
+
+
+@torch.library.custom_op("fsgm::pyramidal_sgm", mutates_args=())
+def _pyramidal_sgm_op(I0: torch.Tensor, I1: torch.Tensor, numPyd: int,
+                      params: List[int]) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    prm = _L.fsgm_pyramid_params_default()
+    prm.numPyd = int(numPyd)
+    for k, v in zip(PYRAMID_FIELDS, params, strict=True):
+        setattr(prm, k, int(v))
+    return _pyramid_run(_L.fsgm_pyramidal_sgm_device, prm, I0, I1)
+
+
+@_pyramidal_sgm_op.register_fake
+def _(I0, I1, numPyd, params):
+    return _pyramid_fake(I0)
+
+
+@torch.library.custom_op("fsgm::pyramidal_sgm_ng", mutates_args=())
+def _pyramidal_sgm_ng_op(I0: torch.Tensor, I1: torch.Tensor, numPyd: int,
+                         params: List[int]) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    prm = _L.fsgm_ng_pyramid_params_default()
+    prm.numPyd = int(numPyd)
+    for k, v in zip(NG_PYRAMID_FIELDS, params, strict=True):
+        setattr(prm, k, int(v))
+    return _pyramid_run(_L.fsgm_pyramidal_sgm_ng_device, prm, I0, I1)
+
+
+@_pyramidal_sgm_ng_op.register_fake
+def _(I0, I1, numPyd, params):
+    return _pyramid_fake(I0)
+
+
+# ---------------------------------------------------------------------------------------------
+# wrappers: the argument order of the numpy API, one frame or a batch with a leading N
+# ---------------------------------------------------------------------------------------------
+def _tensors(named, device=None):
+    """TypeError unless every value is a GPU tensor of the dtype asked for, all on one device; returns that device."""
+    for name, (t, dtype) in named.items():
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name} must be a torch.Tensor (got {type(t).__name__})")
+        if t.device.type != "cuda":
+            raise TypeError(f"{name} is on {t.device}: pass tensors on the GPU (no silent transfer)")
+        if t.dtype != dtype:
+            raise TypeError(f"{name} must be {dtype} (got {t.dtype})")
+        if device is None:
+            device = t.device
+        elif t.device != device:
+            raise TypeError(f"{name} is on {t.device}, the other arguments on {device}")
+    return device
+
+
+def _shape(name, t, shape):
+    if tuple(t.shape) != tuple(shape):
+        raise TypeError(f"{name} must have shape {tuple(shape)} (got {tuple(t.shape)})")
+
+
+def _finish(outs, status, batched, check, return_status):
+    if check:
+        torch.cuda.current_stream(status.device).synchronize()
+        s = int(status.item())
+        if s != 0:
+            raise FsgmError(s, "the device reported a failed run (an aggregation hand-off gave up): results are invalid")
+    outs = tuple(outs if batched else (o[0] for o in outs))
+    return outs + (status,) if return_status else outs
+
+
+def calc_cost_sgm(I1, I2, dMax, vMax, pixelPosD0, normlizeDirection, offsetFromPosD0, P1, P2, *, paths=4, subpixel=1,
+                  vz_to_disp=1, fb_check=0, check=False, return_status=False):
+    """[bestD, minC] = calc_cost_sgm(...) as fsgm_amd.calc_cost_sgm, on torch tensors on the GPU.  One frame: I1, I2 (H, W) uint8,
+    pixelPosD0 / normlizeDirection (2, H, W) and offsetFromPosD0 (H, W) float64; a batch: the same with a leading N.
+    Returns uint32 tensors of the same leading shape (and conf uint8 / bestD2 uint32 with fb_check=1; the status tensor last
+    with return_status=True).  check=True synchronises the current stream and raises FsgmError on a non-zero status."""
+    _tensors({"I1": (I1, torch.uint8), "I2": (I2, torch.uint8), "pixelPosD0": (pixelPosD0, torch.float64),
+                    "normlizeDirection": (normlizeDirection, torch.float64), "offsetFromPosD0": (offsetFromPosD0, torch.float64)})
+    if I1.dim() not in (2, 3):
+        raise TypeError(f"I1 must be (H, W) or (N, H, W) (got {tuple(I1.shape)})")
+    batched = I1.dim() == 3
+    lead = tuple(I1.shape[:-2])
+    H, W = I1.shape[-2:]
+    _shape("I2", I2, lead + (H, W))
+    _shape("pixelPosD0", pixelPosD0, lead + (2, H, W))
+    _shape("normlizeDirection", normlizeDirection, lead + (2, H, W))
+    _shape("offsetFromPosD0", offsetFromPosD0, lead + (H, W))
+    if not batched:
+        I1, I2, pixelPosD0, normlizeDirection, offsetFromPosD0 = (t.unsqueeze(0) for t in (I1, I2, pixelPosD0, normlizeDirection, offsetFromPosD0))
+    bestD, minC, conf, bestD2, status = torch.ops.fsgm.calc_cost_sgm(I1, I2, pixelPosD0, normlizeDirection, offsetFromPosD0, int(dMax),
+                                                                      float(vMax), int(P1), int(P2), int(paths), int(subpixel),
+                                                                      int(vz_to_disp), int(fb_check))
+    outs = (bestD, minC, conf, bestD2) if fb_check else (bestD, minC)
+    return _finish(outs, status, batched, check, return_status)
+
+
+def epipolar_sgm_of(I0, I1, F, H, epipole, direction, dMax=64, vMax=0.3, *, paths=4, check=False, return_status=False):
+    """[flow, minC] = epipolar_sgm_of(...) as fsgm_amd.epipolar_sgm_of, on torch tensors on the GPU.  One frame: I0, I1
+    (H, W) or RGB (3, H, W) uint8 with F, H (3x3), epipole (x, y), direction; a batch: images with a leading N and lists of N
+    geometries (F then a sequence of 3x3 matrices).  flow (.., 3, H, W) float64, minC (.., H, W) uint32."""
+    batched = np.asarray(F, dtype=np.float64).ndim == 3
+    Fs, Hs, es, ds = (F, H, epipole, direction) if batched else ([F], [H], [epipole], [direction])
+    if not (len(Fs) == len(Hs) == len(es) == len(ds)):
+        raise ValueError("F, H, epipole and direction must hold one entry per frame")
+    _tensors({"I0": (I0, torch.uint8), "I1": (I1, torch.uint8)})
+    _shape("I1", I1, I0.shape)
+    per = I0.dim() - (1 if batched else 0)
+    if per not in (2, 3) or (per == 3 and I0.shape[-3] != 3):
+        raise TypeError(f"images must be (H, W) or (3, H, W) per frame (got {tuple(I0.shape)})")
+    if batched and I0.shape[0] != len(Fs):
+        raise ValueError(f"{I0.shape[0]} image pairs but {len(Fs)} geometries")
+    geometry = []
+    for Fm, Hm, e, d in zip(Fs, Hs, es, ds):
+        Fm, Hm = np.asarray(Fm, np.float64), np.asarray(Hm, np.float64)
+        if Fm.shape != (3, 3) or Hm.shape != (3, 3):
+            raise TypeError("F and H must be 3x3 matrices")
+        geometry += [float(x) for x in Fm.reshape(-1)] + [float(x) for x in Hm.reshape(-1)]
+        geometry += [float(e[0]), float(e[1]), float(bool(d))]
+    if not batched:
+        I0, I1 = I0.unsqueeze(0), I1.unsqueeze(0)
+    flow, minC, status = torch.ops.fsgm.epipolar_sgm_of(I0, I1, geometry, int(dMax), float(vMax), int(paths))
+    return _finish((flow, minC), status, batched, check, return_status)
+
+
+def _pyramid_images(I0, I1, batch):
+    _tensors({"I0": (I0, torch.uint8), "I1": (I1, torch.uint8)})
+    _shape("I1", I1, I0.shape)
+    if batch is None:                                    # (3, H, W) is one RGB pair unless batch=True says three gray ones
+        batch = I0.dim() == 4 or (I0.dim() == 3 and I0.shape[0] != 3)
+    per = I0.dim() - (1 if batch else 0)
+    if per not in (2, 3) or (per == 3 and I0.shape[-3] != 3):
+        raise TypeError(f"images must be (H, W) or (3, H, W) per pair (got {tuple(I0.shape)}, batch={batch})")
+    return (I0, I1, True) if batch else (I0.unsqueeze(0), I1.unsqueeze(0), False)
+
+
+def _overrides(fields, defaults, overrides, name):
+    for k in overrides:
+        if k not in fields:
+            raise TypeError(f"unknown {name} parameter {k!r}")
+    return [int(overrides.get(k, getattr(defaults, k))) for k in fields]
+
+
+def pyramidal_sgm(I0, I1, numPyd=5, *, batch=None, check=False, return_status=False, **overrides):
+    """(mv, minC) of level 1 of pyramidal_sgm(I0, I1, numPyd) as fsgm_amd.pyramidal_sgm, on torch tensors on the GPU (the per-level
+    flows are not offered).  Images (H, W) or RGB (3, H, W) uint8, or a batch with a leading N; batch=None infers it (a 3-D tensor
+    with 3 planes is one RGB pair).  mv (.., 2, H, W) float64, minC (.., H, W) uint32.  Keyword overrides as fsgm_amd.pyramidal_sgm."""
+    I0, I1, batched = _pyramid_images(I0, I1, batch)
+    params = _overrides(PYRAMID_FIELDS, _L.fsgm_pyramid_params_default(), overrides, "pyramidal_sgm")
+    mv, minC, status = torch.ops.fsgm.pyramidal_sgm(I0, I1, int(numPyd), params)
+    return _finish((mv, minC), status, batched, check, return_status)
+
+
+def pyramidal_sgm_ng(I0, I1, numPyd=3, *, batch=None, check=False, return_status=False, **overrides):
+    """(flow, minC) of level 1 of the pyramidal loop around calc_pyd_cost_sgm_ng as fsgm_amd.pyramidal_sgm_ng, on torch tensors
+    on the GPU; shapes and batch as pyramidal_sgm."""
+    I0, I1, batched = _pyramid_images(I0, I1, batch)
+    params = _overrides(NG_PYRAMID_FIELDS, _L.fsgm_ng_pyramid_params_default(), overrides, "pyramidal_sgm_ng")
+    flow, minC, status = torch.ops.fsgm.pyramidal_sgm_ng(I0, I1, int(numPyd), params)
+    return _finish((flow, minC), status, batched, check, return_status)
+
+
+def run_tensors(plan, I1, I2, pd0, nd, off, *, check=False, return_status=False):
+    """All `plan.batch` frames of an EpiPlan (fsgm_epi_plan_run_device) in the plan's aggregation mode and penalties
+    (set_agg_mode / set_penalties): I1, I2 (N, H, W) uint8, pd0 / nd (N, 2, H, W), off (N, H, W) float64 on the plan's GPU,
+    N = plan.batch.  Returns (bestD, minC) uint32 (N, H, W), plus (conf, bestD2) for plans made with fb_check=1."""
+    dev = _tensors({"I1": (I1, torch.uint8), "I2": (I2, torch.uint8), "pd0": (pd0, torch.float64), "nd": (nd, torch.float64),
+                    "off": (off, torch.float64)})
+    if dev.index != plan.device:
+        raise TypeError(f"the tensors are on {dev}, the plan on device {plan.device}")
+    N, H, W = plan.batch, plan.H, plan.W
+    for name, t, shape in (("I1", I1, (N, H, W)), ("I2", I2, (N, H, W)), ("pd0", pd0, (N, 2, H, W)), ("nd", nd, (N, 2, H, W)),
+                           ("off", off, (N, H, W))):
+        _shape(name, t, shape)
+    I1, I2, pd0, nd, off = (_ready(t) for t in (I1, I2, pd0, nd, off))
+    bestD, minC, status = _u32((N, H, W), dev), _u32((N, H, W), dev), _status(dev)
+    conf = torch.empty((N, H, W), dtype=torch.uint8, device=dev) if plan.fb_check else None
+    bestD2 = _u32((N, H, W), dev) if plan.fb_check else None
+    P1, P2, vMax = plan.penalties
+    e, o = EpiIn(), EpiOut()
+    e.I1, e.I2, e.width, e.height, e.dMax, e.vMax = _p(I1), _p(I2), W, H, plan.D, float(vMax)
+    e.pixelPosD0, e.normDir, e.offset, e.P1, e.P2 = _p(pd0), _p(nd), _p(off), int(P1), int(P2)
+    o.bestD, o.minC, o.conf, o.bestD2 = _p(bestD), _p(minC), _p(conf), _p(bestD2)
+    _call(dev, _L.fsgm_epi_plan_run_device, plan._h, N, C.byref(e), C.byref(o), _stream(dev), _p(status))
+    outs = (bestD, minC, conf, bestD2) if plan.fb_check else (bestD, minC)
+    return _finish(outs, status, True, check, return_status)

@@ -534,6 +534,54 @@ int32_t fsgm_parse_device_list(const char* text, int32_t* devices, int32_t max_d
  * (frames may be NULL to get the count only) */
 void fsgm_shard_frames(int32_t n_frames, int32_t n_devices, int32_t slot, int32_t* frames, int32_t* count);
 
+/* ------------------------------------------------------------------------------------------
+ * Device-pointer entry points: inputs already in HBM, outputs left in HBM, work ordered on the caller's stream
+ * (what a torch pipeline on the GPU calls: fsgm_amd/torch_ops.py).
+ *
+ * All array pointers are device memory of the device named in the params (prm->device / the plan's device).  A batch of
+ * n frames is contiguous: frame f of an image at I + f*H*W (RGB: I + f*3*H*W), of a 2-plane map at map + f*2*H*W, etc. --
+ * the layouts of the host entry points, one frame after another.  Alignment: every pointer on its element size (u32 4 B,
+ * f64 8 B, u8 any).  Pointers are checked before anything is queued (hipPointerGetAttributes / hipMemGetAddressRange):
+ * memory of another device, host memory (pinned or not), unregistered pointers, misaligned pointers and arrays that run
+ * past the end of their allocation are FSGM_ERR_INVALID.
+ *
+ * The work is ordered after everything already queued on `stream` (a hipStream_t of that device; NULL = the null stream):
+ * the plan's stream waits on an event recorded on `stream`, and after the last kernel of the call -- the plan's internal
+ * streams joined back first -- `stream` waits on an event recorded on the plan's stream.  Everything queued on `stream`
+ * after the call returns runs after it.  Calls from several streams that share one cached plan serialise on that plan's
+ * stream; memory the caller frees after the call is only reused by work ordered after the join.
+ * No host<->device copy and no wait for the device once a plan for this shape and these parameters exists (the first call
+ * may create the plan and upload its tables).  The caller's arrays are read and written where they lie; the plans' own
+ * buffers of the host entry points are not touched for them.
+ * status (device memory, may be NULL): one int32, written on `stream` at the end -- 0, or FSGM_ERR_HIP when a bounded
+ * hand-off poll of the aggregation gave up (what fsgm_epi_plan_sync reports on the host paths).
+ * A stream that is being captured into a graph is refused with FSGM_ERR_UNSUPPORTED before anything is queued.
+ * The debug taps (out->C / out->S, per-level pyramid flows) are not offered: a non-NULL C or S is FSGM_ERR_UNSUPPORTED.
+ * Results are bit for bit those of the host entry points for the same inputs.
+ * ------------------------------------------------------------------------------------------ */
+/* All `batch` frames of a plan (n_frames must equal the plan's batch), cost stage + aggregation + WTA in the plan's
+ * aggregation mode (fsgm_epi_plan_set_agg_mode); in->width / height / dMax must match the plan, in->P1 / P2 / vMax
+ * are set on it.  bestD, minC, and with fb_check conf / bestD2 (each may be NULL there) as for the host entry points. */
+fsgm_status fsgm_epi_plan_run_device(fsgm_epi_plan* plan, int32_t n_frames, const fsgm_epi_in* in, const fsgm_epi_out* out,
+                                     void* stream, int32_t* status);
+/* calc_cost_sgm on n_frames contiguous frames (one cached plan of batch n_frames, as fsgm_calc_cost_sgm_batch_host) */
+fsgm_status fsgm_calc_cost_sgm_device(int32_t n_frames, const fsgm_epi_in* in, const fsgm_epi_out* out,
+                                      const fsgm_epi_params* prm, void* stream, int32_t* status);
+/* epipolar_sgm_of on n_frames image pairs, one plan of batch n_frames: g (HOST memory) holds n_frames geometries, each
+ * passed to the maps kernel by value.  I0 / I1 u8 [n][channels][H][W]; flow f64 [n][3][H][W]; minC (may be NULL) u32 [n][H][W]. */
+fsgm_status fsgm_epipolar_sgm_of_device(int32_t n_frames, const uint8_t* I0, const uint8_t* I1, int32_t width,
+                                        int32_t height, int32_t channels, const fsgm_epi_geometry* g,
+                                        int32_t dMax, double vMax, const fsgm_epi_params* prm,
+                                        double* flow, uint32_t* minC, void* stream, int32_t* status);
+/* the pyramids on n_frames image pairs (one plan of batch n_frames): the level-1 flow f64 [n][2][H][W] and minC (may be
+ * NULL) u32 [n][H][W].  The level-1 images are read in place by the first reduce / gray / census kernels. */
+fsgm_status fsgm_pyramidal_sgm_device(int32_t n_frames, const uint8_t* I0, const uint8_t* I1, int32_t width,
+                                      int32_t height, int32_t channels, const fsgm_pyramid_params* prm,
+                                      double* mv, uint32_t* minC, void* stream, int32_t* status);
+fsgm_status fsgm_pyramidal_sgm_ng_device(int32_t n_frames, const uint8_t* I0, const uint8_t* I1, int32_t width,
+                                         int32_t height, int32_t channels, const fsgm_ng_pyramid_params* prm,
+                                         double* flow, uint32_t* minC, void* stream, int32_t* status);
+
 #ifdef __cplusplus
 }
 #endif
