@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include <array>
 
 #define FSGM_NG_MAX_D 512        // candidates per pixel of the hint-map variant: 9*(2r+1)^2, r <= 3
 
@@ -88,24 +89,49 @@ struct OtfArgs {
     int exact;              // 1: start in the exact matcher (FSGM_OTF_EXACT=1; otherwise entered when a motion vector leaves the packed range)
 };
 
-void launch_ng_cost(hipStream_t st, const NgCostArgs& a, int frames);
-void launch_ng_aggregate(hipStream_t st, NgAggArgs a, int frames);
 // repeats among the D <= 128 candidates of every pixel (same motion vector and same cost), see ng_dedupe_kernel
 enum { NG_ROLE_ANY = 0, NG_ROLE_GRID = 1, NG_ROLE_LIST = 2, NG_ROLE_COMPACT = 3, NG_ROLE_REST = 4 };
 constexpr int NG_KSTAT_WORDS = 259;
 constexpr int NG_L4_PER_PIXEL = 4 * 64;      // int16 entries of L4 per pixel
-// kstat: NG_KSTAT_WORDS words, zeroed here; ck / cm may be null (no compact kernel)
-void launch_ng_dedupe(hipStream_t st, const Cand* C, uint16_t* dd, uint8_t* dk, uint32_t* dbox, uint32_t* kstat, uint32_t* ck, uint16_t* cm, int W, int H, int D, int frames,
-                      const uint32_t* K4 = nullptr, const uint32_t* flags = nullptr);
-// With 4-byte entries (K4 in the memory of S): after the dedupe kernel and before launch_ng_aggregate -- decides on the device whether the
-// compact matcher runs (kstat[258]); if not, expands the keys to the Cand list the general matchers read and zeroes S
-void launch_ng_prepare_matchers(hipStream_t st, const NgAggArgs& a, const uint32_t* K4, Cand* C, const uint32_t* flags, int frames);
+
+// Scratch of one level of the hint-map variant for all frames of a batch (frame-major); ng_level_bufs sizes it
+struct NgLevelBufs {
+    uint32_t *cen1, *cen2;  // census of both images
+    Cand* C;                // candidate lists
+    uint32_t* S;            // sums; the 4-byte entries until the matchers need S
+    uint32_t* unsafe;       // the cost kernel's two flag words
+    uint16_t* dd;           // launch_ng_dedupe's tables (NgAggArgs): dd, dk, dbox, kstat, ck, cm
+    uint8_t* dk;
+    uint32_t* box;
+    uint32_t* kstat;
+    uint32_t* ck;
+    uint16_t* cm;
+    int16_t* L4;            // the compact kernel's per-path costs (D <= 128; 0 bytes otherwise)
+};
+struct NgBuf { void** slot; size_t bytes; };
+// every slot of `b` with its size in bytes for `frames` frames of W x H pixels and D candidates: the caller carves or allocates them
+std::array<NgBuf, 12> ng_level_bufs(NgLevelBufs& b, int W, int H, int D, int frames);
+
+// One level of calc_pyd_cost_sgm_ng (:470-517) for all frames of a batch: caller-owned images, hint map and results
+struct NgLevel {
+    const uint8_t* I1;      // [frames][H][W]
+    const uint8_t* I2;
+    const double* mv;       // [frames][2][mvH][mvW]
+    uint32_t* minC;         // [frames][H][W]
+    double* flow;           // [frames][2][H][W]
+    int W, H, mvW, mvH;
+    int r, rAgg;            // halfSearchWinSize, aggSize / 2: D = 9 (2r+1)^2 candidates
+    int P1, P2;
+    int subPixelRefine;
+};
+// Queues the level on `st`: census of both images, candidate costs, repeat removal, matcher, WTA and, when asked, the census
+// sub-pixel step.  Reads the A/B switches and decides the 4-byte entries.  With D <= 128 the matchers leave
+// S incomplete: a caller that reads S back queues launch_ng_l4_to_s and launch_ng_fill_repeats behind the level.
+hipError_t ng_level_enqueue(hipStream_t st, const NgLevelBufs& b, const NgLevel& lv, int frames);
 // S of the repeats := S of the entries they repeat (only needed when S itself is read back: the WTA looks them up)
 void launch_ng_fill_repeats(hipStream_t st, uint32_t* S, const uint16_t* dd, const uint16_t* cm, int W, int H, int D, int frames);
 // S at the kept entries' first-member indices := the sum of L4's four slots, when the compact kernel ran (kstat[257]): only for reading S back
 void launch_ng_l4_to_s(hipStream_t st, uint32_t* S, const int16_t* L4, const uint16_t* cm, const uint8_t* dk, const uint32_t* kstat, int W, int H, int D, int frames);
-void launch_ng_wta(hipStream_t st, const NgWtaArgs& a, int frames);
-void launch_ng_subpixel(hipStream_t st, const NgSubpixArgs& a, int frames);
 void launch_otf(hipStream_t st, const OtfArgs& a, int frames);
 
 }  // namespace fsgm

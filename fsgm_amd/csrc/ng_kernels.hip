@@ -4,6 +4,7 @@
 //   calc_cost_sgm_ng.cpp     : candidates come from the path buffers of pixels already visited
 //                              (+ a rand() hint), so the frame is inherently raster-serial.
 #include "ng_kernels.h"
+#include "epi_kernels.h"
 #include "fsgm_device.h"
 #include <stdlib.h>
 
@@ -1729,9 +1730,36 @@ __global__ __launch_bounds__(896) void otf_pipe_kernel(OtfArgs a) {
 // =============================================================================================
 // launchers
 // =============================================================================================
-void launch_ng_cost(hipStream_t st, const NgCostArgs& a, int frames) {
-    static const bool by_hint = [] { const char* e = getenv("FSGM_NG_COST_HINT"); return !(e && e[0] == '0'); }();   // A/B switch
-    if (by_hint && a.rX == 1 && a.rY == 1 && a.rAgg == 1) {
+// The A/B switches of the hint-map variant, read from the environment once per level enqueue -- the tests
+// flip them between calls -- and handed to the launchers; nothing else reads them.
+struct NgSwitches {
+    bool dedupe;            // FSGM_NG_DEDUPE (1): 0 = the matchers stage every candidate (the dedupe kernel still runs for the WTA)
+    int split;              // FSGM_NG_SPLIT (2): parts per matcher for one or two frames (0/1: one thread per (line, candidate))
+    int grid;               // FSGM_NG_GRID: 0 never the grid form, 1 the only form, -1 (unset) picked on the device
+    int compact;            // FSGM_NG_COMPACT: 0 never the compact kernel, -1 (unset) picked on the device
+    int compact_g;          // FSGM_NG_COMPACT_G: 16 / 32 / 64 fixes the compact kernel's lanes a line; 0 (unset) by the lists
+    bool cost_hint;         // FSGM_NG_COST_HINT (1): 0 = candidate costs one thread per candidate (the generic cost kernel)
+    bool k4;                // FSGM_NG_K4 (1): 0 = 12-byte entries always
+};
+static NgSwitches ng_read_switches() {
+    const auto num = [](const char* name, int unset) { const char* e = getenv(name); return e && *e ? atoi(e) : unset; };
+    const char* split = getenv("FSGM_NG_SPLIT");
+    const char* dedupe = getenv("FSGM_NG_DEDUPE");
+    const char* hint = getenv("FSGM_NG_COST_HINT");
+    const char* k4 = getenv("FSGM_NG_K4");
+    NgSwitches sw;
+    sw.dedupe = !(dedupe && atoi(dedupe) == 0);
+    sw.split = split ? atoi(split) : 2;
+    sw.grid = num("FSGM_NG_GRID", -1);
+    sw.compact = num("FSGM_NG_COMPACT", -1);
+    sw.compact_g = num("FSGM_NG_COMPACT_G", 0);
+    sw.cost_hint = !(hint && hint[0] == '0');
+    sw.k4 = !(k4 && k4[0] == '0');
+    return sw;
+}
+
+static void launch_ng_cost(hipStream_t st, const NgCostArgs& a, int frames, const NgSwitches& sw) {
+    if (sw.cost_hint && a.rX == 1 && a.rY == 1 && a.rAgg == 1) {
         const long long n = (long long)a.W * a.H * 9;
         const dim3 grid((unsigned)((n + 255) / 256), frames);
         if (a.K4 && a.flags) {                                // 4-byte entries, and the 12-byte list only if a key did not fit (gated on the device)
@@ -1749,7 +1777,7 @@ void launch_ng_cost(hipStream_t st, const NgCostArgs& a, int frames) {
     hipLaunchKernelGGL(ng_cost_kernel, grid, dim3(256), 0, st, a);
 }
 
-void launch_ng_aggregate(hipStream_t st, NgAggArgs a, int frames) {
+static void launch_ng_aggregate(hipStream_t st, NgAggArgs a, int frames, const NgSwitches& sw) {
     // slots: 0 along x, 1 along y, 2/3 their point mirrors (pass 1)
     int acc = 0;
     for (int i = 0; i < 4; i++) {
@@ -1758,24 +1786,19 @@ void launch_ng_aggregate(hipStream_t st, NgAggArgs a, int frames) {
     }
     a.blk_begin[4] = acc;
     a.role = NG_ROLE_ANY; a.with_compact = 0; a.compact_force = 0; a.compact_g = 0;
-    { const char* e = getenv("FSGM_NG_DEDUPE"); if (e && atoi(e) == 0) { a.dd = nullptr; a.dk = nullptr; a.dbox = nullptr; a.ck = nullptr; a.cm = nullptr; } }   // A/B switch: stage every candidate
+    if (!sw.dedupe) { a.dd = nullptr; a.dk = nullptr; a.dbox = nullptr; a.ck = nullptr; a.cm = nullptr; }   // stage every candidate
     if (a.D <= 128 && a.unsafe) {
         const int lpb = 256 / a.D, Dp = (a.D + 3) & ~3;
         // long lines first: with few frames their blocks decide when the launch ends
-        const char* env = getenv("FSGM_NG_SPLIT");               // A/B switch: parts per matcher (0/1: one thread per (line, candidate))
-        const int nparts = frames <= 2 ? (env ? atoi(env) : 2) : 1;   // 1242x375, 3-level pyramid: 9.64 / 7.34 / 7.98 / 7.66 ms with 1 / 2 / 3 / 4 parts
+        const int nparts = frames <= 2 ? sw.split : 1;   // 1242x375, 3-level pyramid: 9.64 / 7.34 / 7.98 / 7.66 ms with 1 / 2 / 3 / 4 parts
         const bool split = nparts >= 2 && nparts <= 4;
         const int ord_x[4] = {0, 2, 1, 3}, ord_y[4] = {1, 3, 0, 2};
         // Which kernel runs is settled on the device from what the dedupe kernel saw (ng_agg_not_mine): every candidate
         // is launched, the ones not favoured return at once.  A/B switches: FSGM_NG_COMPACT=0 / FSGM_NG_GRID=0 take a kernel out
         // of the set, FSGM_NG_GRID=1 makes the grid kernel the only one, FSGM_NG_COMPACT_G=16|32|64 fixes the compact kernel's
         // lanes a line (it still steps aside for lists it cannot hold).
-        const char* cenv = getenv("FSGM_NG_COMPACT");
-        const int compact_env = cenv && *cenv ? atoi(cenv) : -1;
-        const char* genv = getenv("FSGM_NG_GRID");
-        const int grid_env = genv && *genv ? atoi(genv) : -1;
         const bool can_stat = a.dd && a.dk && a.kstat;
-        if (can_stat && a.ck && a.cm && a.L4 && compact_env != 0 && grid_env != 1) {
+        if (can_stat && a.ck && a.cm && a.L4 && sw.compact != 0 && sw.grid != 1) {
             acc = 0;
             for (int i = 0; i < 4; i++) {
                 const int sl = a.W >= a.H ? ord_x[i] : ord_y[i];
@@ -1787,8 +1810,7 @@ void launch_ng_aggregate(hipStream_t st, NgAggArgs a, int frames) {
             a.with_compact = 1;
             a.role = NG_ROLE_COMPACT;
             // one launch per lanes-a-line class (16 / 32 / 64 for lists up to that long); the dedupe kernel's flags pick one
-            const char* gforce = getenv("FSGM_NG_COMPACT_G");     // 16 / 32 / 64: that class only, whatever the lists look like (tests)
-            const int g_only = gforce && *gforce ? atoi(gforce) : 0;
+            const int g_only = sw.compact_g;                     // 16 / 32 / 64: that class only, whatever the lists look like (tests)
             a.compact_force = g_only == 16 || g_only == 32 || g_only == 64;
             for (int G = 16; G <= 64; G *= 2) {
                 if (a.compact_force && G != g_only) continue;
@@ -1815,12 +1837,12 @@ void launch_ng_aggregate(hipStream_t st, NgAggArgs a, int frames) {
         a.blk_begin[4] = acc;
         // The grid form of the matcher costs the same at any list length, the list form grows with it: lists of a few
         // entries (nearly constant hint maps) are faster walked, anything richer is faster looked up.
-        const bool with_grid = can_stat && a.dbox && grid_env != 0 && (grid_env == 1 || !split);
+        const bool with_grid = can_stat && a.dbox && sw.grid != 0 && (sw.grid == 1 || !split);
         if (with_grid) {
             const size_t lds = ((size_t)lpb * 8 * Dp + (size_t)lpb * 6 * NG_GCELLS + lpb * 8 + 2 * lpb) * sizeof(uint32_t);
-            a.role = grid_env == 1 ? NG_ROLE_ANY : NG_ROLE_GRID;
+            a.role = sw.grid == 1 ? NG_ROLE_ANY : NG_ROLE_GRID;
             hipLaunchKernelGGL(ng_agg_grid_kernel, dim3(acc, frames), dim3(256), lds, st, a);
-            if (grid_env == 1) return;
+            if (sw.grid == 1) return;
         }
         a.role = with_grid ? NG_ROLE_LIST : (a.with_compact ? NG_ROLE_REST : NG_ROLE_ANY);
         if (split) {
@@ -1842,11 +1864,11 @@ void launch_ng_fill_repeats(hipStream_t st, uint32_t* S, const uint16_t* dd, con
     hipLaunchKernelGGL(ng_fill_repeats_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, S, dd, cm, n, D);
 }
 
-void launch_ng_dedupe(hipStream_t st, const Cand* C, uint16_t* dd, uint8_t* dk, uint32_t* dbox, uint32_t* kstat, uint32_t* ck, uint16_t* cm, int W, int H, int D, int frames,
-                      const uint32_t* K4, const uint32_t* flags) {
+// kstat: NG_KSTAT_WORDS words, zeroed here; dbox may be null (no grid kernel in the set: no boxes needed)
+static void launch_ng_dedupe(hipStream_t st, const Cand* C, uint16_t* dd, uint8_t* dk, uint32_t* dbox, uint32_t* kstat, uint32_t* ck, uint16_t* cm, int W, int H, int D, int frames,
+                             const uint32_t* K4, const uint32_t* flags) {
     const int n = W * H * frames;                            // frames are contiguous in all arrays
     if (kstat) (void)hipMemsetAsync(kstat, 0, NG_KSTAT_WORDS * sizeof(uint32_t), st);
-    { const char* e = getenv("FSGM_NG_GRID"); if (e && e[0] == '0') dbox = nullptr; }      // no grid kernel in the set: no boxes needed
     hipLaunchKernelGGL(ng_dedupe_kernel, dim3((n + 3) / 4), dim3(256), 0, st, C, (K4 && flags) ? K4 : nullptr, flags, dd, dk, dbox, kstat, ck, cm, n, D);
 }
 
@@ -1897,21 +1919,20 @@ __global__ __launch_bounds__(256) void ng_dbox_kernel(const uint32_t* __restrict
     }
 }
 
-bool ng_compact_possible(const NgAggArgs& a) {
-    const char* cenv = getenv("FSGM_NG_COMPACT");
-    const int compact_env = cenv && *cenv ? atoi(cenv) : -1;
-    const char* genv = getenv("FSGM_NG_GRID");
-    const int grid_env = genv && *genv ? atoi(genv) : -1;
-    const char* denv = getenv("FSGM_NG_DEDUPE");
-    if (denv && atoi(denv) == 0) return false;
+// whether a compact kernel in launch_ng_aggregate's set can be the one that runs (ng_decide_kernel's with_compact)
+static bool ng_compact_possible(const NgAggArgs& a, const NgSwitches& sw) {
+    if (!sw.dedupe) return false;
     // (the kernel walks a frame with 32-bit byte offsets: entries x 4 bytes and pixels x 512 bytes of L4 must stay below 4 GB)
     if ((long long)a.W * a.H * a.D >= (1LL << 30) || (long long)a.W * a.H >= (1LL << 23)) return false;
-    return a.D <= 128 && a.unsafe && a.dd && a.dk && a.kstat && a.ck && a.cm && a.L4 && compact_env != 0 && grid_env != 1;
+    return a.D <= 128 && a.unsafe && a.dd && a.dk && a.kstat && a.ck && a.cm && a.L4 && sw.compact != 0 && sw.grid != 1;
 }
 
-void launch_ng_prepare_matchers(hipStream_t st, const NgAggArgs& a, const uint32_t* K4, Cand* C, const uint32_t* flags, int frames) {
+// With 4-byte entries (K4 in the memory of S): after the dedupe kernel and before launch_ng_aggregate -- decides on the device whether the
+// compact matcher runs (kstat[258]); if not, expands the keys to the Cand list the general matchers read and zeroes S
+static void launch_ng_prepare_matchers(hipStream_t st, const NgAggArgs& a, const uint32_t* K4, Cand* C, const uint32_t* flags, int frames,
+                                       const NgSwitches& sw) {
     const long long npix = (long long)a.W * a.H * frames, n = npix * a.D;
-    hipLaunchKernelGGL(ng_decide_kernel, dim3(1), dim3(256), 0, st, a.kstat, npix, ng_compact_possible(a) ? 1 : 0);
+    hipLaunchKernelGGL(ng_decide_kernel, dim3(1), dim3(256), 0, st, a.kstat, npix, ng_compact_possible(a, sw) ? 1 : 0);
     hipLaunchKernelGGL(ng_expand_kernel, dim3((unsigned)std::min<long long>((n + 255) / 256, 4096)), dim3(256), 0, st, K4, C, flags, (const uint32_t*)a.kstat, n);
     if (a.dbox) hipLaunchKernelGGL(ng_dbox_kernel, dim3((unsigned)std::min<long long>((npix + 3) / 4, 4096)), dim3(256), 0, st, K4, flags, (const uint32_t*)a.kstat,
                                    const_cast<uint32_t*>(a.dbox), (int)npix, a.D);
@@ -1934,12 +1955,64 @@ void launch_ng_l4_to_s(hipStream_t st, uint32_t* S, const int16_t* L4, const uin
     hipLaunchKernelGGL(ng_l4_to_s_kernel, dim3((unsigned)((npix * 64 + 255) / 256)), dim3(256), 0, st, S, L4, cm, dk, kstat, npix, D);
 }
 
-void launch_ng_wta(hipStream_t st, const NgWtaArgs& a, int frames) {
+static void launch_ng_wta(hipStream_t st, const NgWtaArgs& a, int frames) {
     hipLaunchKernelGGL(ng_wta_kernel, dim3((a.W * a.H + 15) / 16, frames), dim3(256), 0, st, a);
 }
 
-void launch_ng_subpixel(hipStream_t st, const NgSubpixArgs& a, int frames) {
+static void launch_ng_subpixel(hipStream_t st, const NgSubpixArgs& a, int frames) {
     hipLaunchKernelGGL(ng_subpixel_kernel, dim3((a.W * a.H + 255) / 256, frames), dim3(256), 0, st, a);
+}
+
+std::array<NgBuf, 12> ng_level_bufs(NgLevelBufs& b, int W, int H, int D, int frames) {
+    const size_t NP = (size_t)W * H * frames, N = NP * D;
+    return {{{(void**)&b.unsafe, 8},                     // { a vector beyond the packed matcher's range, a key that does not fit 4 bytes }
+             {(void**)&b.cen1, NP * 4},
+             {(void**)&b.cen2, NP * 4},
+             {(void**)&b.C, N * sizeof(Cand)},
+             {(void**)&b.S, N * 4},
+             {(void**)&b.dd, N * 2},
+             {(void**)&b.dk, NP},
+             {(void**)&b.box, NP * 4},
+             {(void**)&b.kstat, NG_KSTAT_WORDS * 4},
+             {(void**)&b.ck, N * 4},
+             {(void**)&b.cm, N * 2},
+             {(void**)&b.L4, D <= 128 ? NP * NG_L4_PER_PIXEL * sizeof(int16_t) : 0}}};
+}
+
+hipError_t ng_level_enqueue(hipStream_t st, const NgLevelBufs& b, const NgLevel& lv, int frames) {
+    const NgSwitches sw = ng_read_switches();
+    const int W = lv.W, H = lv.H, D = 9 * (2 * lv.r + 1) * (2 * lv.r + 1);
+    // 4-byte candidate entries (the 3x3 hint kernel's sizes, D = 81): the keys live in S's memory until the matchers need S
+    const bool k4 = sw.k4 && sw.cost_hint && sw.dedupe && lv.r == 1 && lv.rAgg == 1 && D <= 128;
+    hipError_t e;
+    if (!k4 && (e = hipMemsetAsync(b.S, 0, (size_t)W * H * D * frames * 4, st)) != hipSuccess) return e;   // calc_pyd_cost_sgm_ng.cpp:111
+    if ((e = hipMemsetAsync(b.unsafe, 0, 8, st)) != hipSuccess) return e;
+    launch_census(st, lv.I1, b.cen1, W, H, frames);                           // :485-486
+    launch_census(st, lv.I2, b.cen2, W, H, frames);
+    NgCostArgs ca;
+    ca.K4 = k4 ? b.S : nullptr; ca.flags = k4 ? b.unsafe : nullptr;
+    ca.cen1 = b.cen1; ca.cen2 = b.cen2; ca.mv = lv.mv; ca.C = b.C; ca.unsafe = b.unsafe; ca.W = W; ca.H = H;
+    ca.mvW = lv.mvW; ca.mvH = lv.mvH; ca.rAgg = lv.rAgg; ca.rX = lv.r; ca.rY = lv.r;
+    launch_ng_cost(st, ca, frames, sw);
+    NgAggArgs ga;
+    ga.C = b.C; ga.S = b.S; ga.unsafe = b.unsafe; ga.W = W; ga.H = H; ga.D = D; ga.P1 = lv.P1; ga.P2 = lv.P2;
+    ga.dd = nullptr; ga.dk = nullptr; ga.dbox = nullptr; ga.kstat = nullptr; ga.ck = nullptr; ga.cm = nullptr; ga.L4 = nullptr;
+    if (D <= 128) {                                  // repeats in the candidate lists: the matchers scan each distinct entry once
+        launch_ng_dedupe(st, b.C, b.dd, b.dk, sw.grid == 0 ? nullptr : b.box, b.kstat, b.ck, b.cm, W, H, D, frames, ca.K4, ca.flags);
+        ga.dd = b.dd; ga.dk = b.dk; ga.dbox = b.box; ga.kstat = b.kstat; ga.ck = b.ck; ga.cm = b.cm; ga.L4 = b.L4;
+        if (k4) launch_ng_prepare_matchers(st, ga, b.S, b.C, b.unsafe, frames, sw);
+    }
+    launch_ng_aggregate(st, ga, frames, sw);
+    NgWtaArgs wa;
+    wa.C = b.C; wa.S = b.S; wa.minC = lv.minC; wa.flow = lv.flow; wa.W = W; wa.H = H; wa.D = D;
+    wa.cm = ga.cm; wa.dk = ga.dk; wa.L4 = ga.L4; wa.kstat = ga.kstat; wa.K4 = ca.K4; wa.flags = ca.flags;
+    launch_ng_wta(st, wa, frames);
+    if (lv.subPixelRefine) {                                                  // :516-517
+        NgSubpixArgs sa;
+        sa.cen1 = b.cen1; sa.cen2 = b.cen2; sa.flow = lv.flow; sa.W = W; sa.H = H;
+        launch_ng_subpixel(st, sa, frames);
+    }
+    return hipSuccess;
 }
 
 void launch_otf(hipStream_t st, const OtfArgs& a, int frames) {

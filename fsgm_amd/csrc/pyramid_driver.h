@@ -1,0 +1,315 @@
+// pyramid_driver.h -- the level loop of pyramidal_sgm.m (:24-76) shared by the two pyramidal drivers of include/fsgm.h:
+// capi_pyramid.hip runs calc_pyd_cost_sgm at every level, capi_ng_pyramid.hip the neighbour-guided matcher.  Every level's
+// images, hint maps and flows stay in HBM; one host call uploads the image pair and downloads the flows (the reference's
+// loop does one MEX call, i.e. one round trip, per level: pyramidal_sgm.m:37-75).
+//
+// A plan type P (the opaque plan struct of include/fsgm.h) holds `PyramidCore core` and `Params prm` and supplies what
+// depends on its matcher:
+//   using Params; static constexpr int max_batch;                      its parameter struct (numPyd, device) and batch limit
+//   static constexpr const char *plan_name, *entry_name, *flow_name;   names in error messages
+//   static fsgm_status check(const Params&, int W, int H);              parameter checks beyond the shared ones
+//   fsgm_status create_levels(); void destroy_levels();                its own per-level state (core is set up before, released after)
+//   uint8_t*& gray(int img, int l); uint32_t*& minC(int l);            the slots of level l's gray images (img 0 / 1) and minC
+//   fsgm_status enqueue_level(int l);                                  level l on core.stream, the hint map of level l - 1 included
+// The entry points reach the gray images and minC through those slots, so that Bind<> in the device entry point swaps what
+// the kernels read and write.
+#pragma once
+#include "capi_common.h"
+#include "capi_device.h"
+#include "pyramid_kernels.h"
+#include <mutex>
+#include <string.h>
+#include <vector>
+
+namespace fsgm {
+
+struct PyramidCore {
+    int W = 0, H = 0, channels = 1, batch = 1;   // batch: image pairs resident at once, every buffer holds `batch` frames, frame-major
+    std::vector<int> Ws, Hs;                     // level l (0-based) size
+    std::vector<int> mvW, mvH;                   // level l's hint map
+    std::vector<uint8_t*> dP0, dP1;              // colour pyramids [3][h][w] (channels == 3 only)
+    std::vector<double*> dFlow;                  // flow of level l (mvPyd{l}): [2][h][w]
+    hipStream_t stream = nullptr;                // every level runs on it, in order
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    DeviceJoin join;                             // device-pointer entry point: ordering with the caller's stream
+};
+
+inline fsgm_status hip_status(hipError_t e) {
+    if (e == hipSuccess) return FSGM_OK;
+    return fail(e == hipErrorOutOfMemory ? FSGM_ERR_NOMEM : FSGM_ERR_HIP, "%s", hipGetErrorString(e));
+}
+
+template <class P>
+void pyramid_destroy(P* p) {
+    if (!p) return;
+    PyramidCore& c = p->core;
+    (void)hipSetDevice(p->prm.device);
+    p->destroy_levels();
+    for (auto* v : {&c.dP0, &c.dP1})
+        for (uint8_t* b : *v) if (b) (void)hipFree(b);
+    for (double* b : c.dFlow) if (b) (void)hipFree(b);
+    if (c.ev0) (void)hipEventDestroy(c.ev0);
+    if (c.ev1) (void)hipEventDestroy(c.ev1);
+    c.join.destroy();
+    if (c.stream) (void)hipStreamDestroy(c.stream);
+    delete p;
+}
+
+template <class P>
+fsgm_status pyramid_create(P** out, int W, int H, int channels, int batch, const typename P::Params* prm) {
+    FSGM_REQUIRE(out, "%s_create: null plan pointer", P::plan_name);
+    *out = nullptr;
+    FSGM_REQUIRE(batch >= 1 && batch <= P::max_batch, "batch must be in 1..%d (got %d)", P::max_batch, batch);
+    FSGM_REQUIRE(prm, "%s_create: null parameters", P::plan_name);
+    FSGM_REQUIRE(W >= 1 && H >= 1, "width/height must be >= 1 (got %d x %d)", W, H);
+    FSGM_REQUIRE(channels == 1 || channels == 3, "channels must be 1 (gray) or 3 (RGB planes), got %d", channels);
+    FSGM_REQUIRE(prm->numPyd >= 1 && prm->numPyd <= 16, "numPyd must be in 1..16 (got %d)", prm->numPyd);
+    fsgm_status st = P::check(*prm, W, H);
+    if (st != FSGM_OK) return st;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
+        return fail(FSGM_ERR_HIP, "no HIP device available (libfsgm_hip has no CPU fallback)");
+    FSGM_REQUIRE(prm->device >= 0 && prm->device < ndev, "device %d out of range (have %d)", prm->device, ndev);
+    FSGM_HIP(hipSetDevice(prm->device));
+    P* p = new P;
+    p->prm = *prm;
+    PyramidCore& c = p->core;
+    c.W = W; c.H = H; c.channels = channels; c.batch = batch;
+    const int n = prm->numPyd;
+    c.Ws.assign(n, W); c.Hs.assign(n, H); c.mvW.resize(n); c.mvH.resize(n);
+    for (int l = 1; l < n; l++) { c.Ws[l] = (c.Ws[l - 1] + 1) / 2; c.Hs[l] = (c.Hs[l - 1] + 1) / 2; }   // impyramid: ceil(size/2)
+    for (int l = 0; l < n; l++) {
+        // the coarsest level starts from a zero map of its own size (:34); every other level gets
+        // 2*imresize(flow, 2, 'nearest') of the level above, twice that level's size (:72)
+        c.mvW[l] = l == n - 1 ? c.Ws[l] : 2 * c.Ws[l + 1];
+        c.mvH[l] = l == n - 1 ? c.Hs[l] : 2 * c.Hs[l + 1];
+    }
+    c.dP0.assign(n, nullptr); c.dP1.assign(n, nullptr); c.dFlow.assign(n, nullptr);
+    hipError_t e = hipStreamCreateWithFlags(&c.stream, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipEventCreate(&c.ev0);
+    if (e == hipSuccess) e = hipEventCreate(&c.ev1);
+    for (int l = 0; l < n && e == hipSuccess; l++) {
+        const size_t np = (size_t)batch * c.Ws[l] * c.Hs[l];
+        if (channels == 3) {
+            e = hipMalloc((void**)&c.dP0[l], 3 * np);
+            if (e == hipSuccess) e = hipMalloc((void**)&c.dP1[l], 3 * np);
+        }
+        if (e == hipSuccess) e = hipMalloc((void**)&c.dFlow[l], 2 * np * sizeof(double));
+    }
+    st = e == hipSuccess ? p->create_levels() : hip_status(e);
+    if (st != FSGM_OK) {
+        char msg[512];
+        snprintf(msg, sizeof msg, "%s", fsgm_last_error());
+        pyramid_destroy(p);
+        return fail(st, "%s_create: %s", P::plan_name, msg);
+    }
+    *out = p;
+    return FSGM_OK;
+}
+
+// the slot that image `img` of level 1 is uploaded to: its colour pyramid, or for gray input the matcher's gray image
+template <class P>
+uint8_t*& pyramid_input(P* p, int img) {
+    return p->core.channels == 3 ? (img ? p->core.dP1 : p->core.dP0)[0] : p->gray(img, 0);
+}
+
+template <class P>
+fsgm_status pyramid_level_size(P* p, int level, int32_t* w, int32_t* h) {
+    FSGM_REQUIRE(p && w && h, "%s_level_size: null argument", P::plan_name);
+    FSGM_REQUIRE(level >= 1 && level <= p->prm.numPyd, "level %d out of range 1..%d", level, p->prm.numPyd);
+    *w = p->core.Ws[level - 1]; *h = p->core.Hs[level - 1];
+    return FSGM_OK;
+}
+
+template <class P>
+fsgm_status pyramid_upload_frame(P* p, int frame, const uint8_t* I0, const uint8_t* I1) {
+    FSGM_REQUIRE(p && I0 && I1, "%s_upload: null argument", P::plan_name);
+    FSGM_REQUIRE(frame >= 0 && frame < p->core.batch, "frame %d out of range (batch %d)", frame, p->core.batch);
+    FSGM_HIP(hipSetDevice(p->prm.device));
+    const size_t n = (size_t)p->core.channels * p->core.W * p->core.H;
+    hipStream_t s = p->core.stream;
+    StreamGuard guard(s);   // an early exit drains the stream: queued copies use the caller's memory
+    FSGM_HIP(hipMemcpyAsync(pyramid_input(p, 0) + frame * n, I0, n, hipMemcpyHostToDevice, s));
+    FSGM_HIP(hipMemcpyAsync(pyramid_input(p, 1) + frame * n, I1, n, hipMemcpyHostToDevice, s));
+    FSGM_HIP(hipStreamSynchronize(s));
+    guard.dismiss();
+    return FSGM_OK;
+}
+
+template <class P>
+fsgm_status pyramid_download_frame(P* p, int frame, int level, double* flow, uint32_t* minC) {
+    FSGM_REQUIRE(p, "null plan");
+    FSGM_REQUIRE(frame >= 0 && frame < p->core.batch, "frame %d out of range (batch %d)", frame, p->core.batch);
+    FSGM_REQUIRE(level >= 1 && level <= p->prm.numPyd, "level %d out of range 1..%d", level, p->prm.numPyd);
+    FSGM_HIP(hipSetDevice(p->prm.device));
+    FSGM_HIP(hipStreamSynchronize(p->core.stream));
+    const int l = level - 1;
+    const size_t np = (size_t)p->core.Ws[l] * p->core.Hs[l];
+    if (flow) FSGM_HIP(hipMemcpy(flow, p->core.dFlow[l] + (size_t)frame * 2 * np, 2 * np * sizeof(double), hipMemcpyDeviceToHost));
+    if (minC) FSGM_HIP(hipMemcpy(minC, p->minC(l) + (size_t)frame * np, np * 4, hipMemcpyDeviceToHost));
+    return FSGM_OK;
+}
+
+// impyramid 'reduce' (:28-31) and rgb2gray (:44-45) of every level, all frames' planes in one launch
+template <class P>
+void pyramid_enqueue_images(P* p) {
+    const PyramidCore& c = p->core;
+    const int n = p->prm.numPyd, ch = c.channels;
+    for (int l = 1; l < n; l++)
+        for (int i = 0; i < 2; i++) {
+            const std::vector<uint8_t*>& rgb = i ? c.dP1 : c.dP0;
+            launch_pyr_reduce(c.stream, ch == 3 ? rgb[l - 1] : p->gray(i, l - 1), ch == 3 ? rgb[l] : p->gray(i, l), c.Ws[l - 1], c.Hs[l - 1], ch * c.batch);
+        }
+    if (ch == 3)
+        for (int l = 0; l < n; l++) {
+            launch_pyr_gray(c.stream, c.dP0[l], p->gray(0, l), c.Ws[l], c.Hs[l], c.batch);
+            launch_pyr_gray(c.stream, c.dP1[l], p->gray(1, l), c.Ws[l], c.Hs[l], c.batch);
+        }
+}
+
+template <class P>
+fsgm_status pyramid_enqueue(P* p) {
+    pyramid_enqueue_images(p);
+    for (int l = p->prm.numPyd - 1; l >= 0; l--) {                               // :37
+        const fsgm_status st = p->enqueue_level(l);
+        if (st != FSGM_OK) return st;
+    }
+    FSGM_HIP(hipGetLastError());
+    return FSGM_OK;
+}
+
+template <class P>
+fsgm_status pyramid_run(P* p) {
+    FSGM_REQUIRE(p, "null plan");
+    FSGM_HIP(hipSetDevice(p->prm.device));
+    return pyramid_enqueue(p);
+}
+
+template <class P>
+fsgm_status pyramid_time(P* p, int warmup, int iters, float* ms_avg) {
+    FSGM_REQUIRE(p && ms_avg && iters >= 1 && warmup >= 0, "%s_time: bad argument", P::plan_name);
+    FSGM_HIP(hipSetDevice(p->prm.device));
+    const PyramidCore& c = p->core;
+    fsgm_status st;
+    for (int i = 0; i < warmup; i++)
+        if ((st = pyramid_enqueue(p)) != FSGM_OK) return st;
+    FSGM_HIP(hipEventRecord(c.ev0, c.stream));
+    for (int i = 0; i < iters; i++)
+        if ((st = pyramid_enqueue(p)) != FSGM_OK) return st;
+    FSGM_HIP(hipEventRecord(c.ev1, c.stream));
+    FSGM_HIP(hipEventSynchronize(c.ev1));
+    float ms = 0;
+    FSGM_HIP(hipEventElapsedTime(&ms, c.ev0, c.ev1));
+    *ms_avg = ms / iters;
+    return FSGM_OK;
+}
+
+// The plans behind the host- and device-pointer entry points: the last two per device, keyed by shape, parameters and batch,
+// each device's under that device's lock
+template <class P>
+struct PyramidCache {
+    PerDevice<std::vector<P*>> plans;
+
+    void clear() {
+        for (int d = 0; d < FSGM_MAX_DEVICES; d++) {
+            std::lock_guard<std::mutex> lk(plans.mu[d]);
+            for (P* p : plans.v[d]) pyramid_destroy(p);
+            plans.v[d].clear();
+        }
+    }
+    // the cached plan of this shape, parameter set and batch (the caller holds the device's lock)
+    fsgm_status get(P** out, int W, int H, int channels, const typename P::Params* prm, int batch) {
+        std::vector<P*>& cache = plans.v[prm->device];
+        P* p = nullptr;
+        for (P* q : cache)
+            if (q->core.W == W && q->core.H == H && q->core.channels == channels && q->core.batch == batch && memcmp(&q->prm, prm, sizeof *prm) == 0) p = q;
+        if (!p) {
+            fsgm_status st = pyramid_create(&p, W, H, channels, batch, prm);
+            if (st != FSGM_OK) return st;
+            if (cache.size() >= 2) {
+                pyramid_destroy(cache.front());
+                cache.erase(cache.begin());
+            }
+            cache.push_back(p);
+        }
+        *out = p;
+        return FSGM_OK;
+    }
+};
+
+// host pointers: one call = the whole loop on a cached plan
+template <class P>
+fsgm_status pyramid_host(PyramidCache<P>& cache, const uint8_t* I0, const uint8_t* I1, int W, int H, int channels,
+                         const typename P::Params* prm, double* flow, uint32_t* minC, double* const* flowPyd) {
+    FSGM_REQUIRE(I0 && I1 && prm && flow, "%s: null argument", P::entry_name);
+    FSGM_DEVICE_SLOT(prm->device);
+    std::lock_guard<std::mutex> lk(cache.plans.mu[prm->device]);
+    P* p = nullptr;
+    fsgm_status st;
+    if ((st = cache.get(&p, W, H, channels, prm, 1)) != FSGM_OK) return st;
+    // One call = one stream-ordered sequence with a single host wait (like fsgm_calc_cost_sgm_batch_host): the image pair goes up
+    // asynchronously, the level loop follows, every requested map comes down behind it.  (Round 3's form waited after the
+    // upload, after the run and once per downloaded map, with blocking copies: 6.3 ms per call around 1.4 ms of kernels.)
+    const PyramidCore& c = p->core;
+    FSGM_HIP(hipSetDevice(prm->device));
+    StreamGuard guard(c.stream);                         // an early exit drains the stream: queued copies use the caller's memory
+    const size_t nimg = (size_t)channels * W * H;
+    FSGM_HIP(hipMemcpyAsync(pyramid_input(p, 0), I0, nimg, hipMemcpyHostToDevice, c.stream));
+    FSGM_HIP(hipMemcpyAsync(pyramid_input(p, 1), I1, nimg, hipMemcpyHostToDevice, c.stream));
+    if ((st = pyramid_enqueue(p)) != FSGM_OK) return st;
+    const size_t np1 = (size_t)W * H;
+    FSGM_HIP(hipMemcpyAsync(flow, c.dFlow[0], 2 * np1 * sizeof(double), hipMemcpyDeviceToHost, c.stream));
+    if (minC) FSGM_HIP(hipMemcpyAsync(minC, p->minC(0), np1 * 4, hipMemcpyDeviceToHost, c.stream));
+    if (flowPyd)
+        for (int l = 0; l < prm->numPyd; l++)
+            if (flowPyd[l] && flowPyd[l] != flow)
+                FSGM_HIP(hipMemcpyAsync(flowPyd[l], c.dFlow[l], 2 * (size_t)c.Ws[l] * c.Hs[l] * sizeof(double), hipMemcpyDeviceToHost, c.stream));
+    FSGM_HIP(hipStreamSynchronize(c.stream));
+    guard.dismiss();
+    return FSGM_OK;
+}
+
+// device pointers in and out, ordered on the caller's stream (include/fsgm.h): the level-1 images are read in place by the
+// first reduce / gray / census kernels, the level-1 flow and minC are written in place -- no copy at either end
+template <class P>
+fsgm_status pyramid_device(PyramidCache<P>& cache, int32_t n, const uint8_t* I0, const uint8_t* I1, int W, int H, int channels,
+                           const typename P::Params* prm, double* flow, uint32_t* minC, void* stream, int32_t* status) {
+    char who[64];
+    snprintf(who, sizeof who, "%s_device", P::entry_name);
+    FSGM_REQUIRE(n >= 1, "%s: n_frames must be >= 1 (got %d)", who, n);
+    FSGM_REQUIRE(I0 && I1 && prm && flow, "%s: null argument", who);
+    FSGM_REQUIRE(W >= 1 && H >= 1, "%s: width/height must be >= 1 (got %d x %d)", who, W, H);
+    FSGM_REQUIRE(channels == 1 || channels == 3, "%s: channels must be 1 (gray) or 3 (RGB planes), got %d", who, channels);
+    FSGM_DEVICE_SLOT(prm->device);
+    std::lock_guard<std::mutex> lk(cache.plans.mu[prm->device]);
+    P* p = nullptr;
+    fsgm_status st;
+    if ((st = cache.get(&p, W, H, channels, prm, n)) != FSGM_OK) return st;
+    const int dev = prm->device;
+    const size_t np = (size_t)n * W * H;
+    hipStream_t cs = (hipStream_t)stream, ps = p->core.stream;
+    FSGM_HIP(hipSetDevice(dev));
+    if ((st = device_check_stream(cs, who)) != FSGM_OK) return st;
+    if ((st = device_check_ptr(I0, np * channels, 1, dev, true, who, "I0")) != FSGM_OK ||
+        (st = device_check_ptr(I1, np * channels, 1, dev, true, who, "I1")) != FSGM_OK ||
+        (st = device_check_ptr(flow, np * 16, 8, dev, true, who, P::flow_name)) != FSGM_OK ||
+        (st = device_check_ptr(minC, np * 4, 4, dev, false, who, "minC")) != FSGM_OK ||
+        (st = device_check_ptr(status, 4, 4, dev, false, who, "status")) != FSGM_OK)
+        return st;
+    if ((st = p->core.join.ensure()) != FSGM_OK) return st;
+    if ((st = p->core.join.enter(cs, ps)) != FSGM_OK) return st;
+    {
+        Bind<uint8_t> i0(pyramid_input(p, 0), const_cast<uint8_t*>(I0));
+        Bind<uint8_t> i1(pyramid_input(p, 1), const_cast<uint8_t*>(I1));
+        Bind<double> fl(p->core.dFlow[0], flow);
+        Bind<uint32_t> mc(p->minC(0), minC);
+        st = pyramid_enqueue(p);
+    }
+    if (st == FSGM_OK) launch_device_status(ps, nullptr, status);
+    const fsgm_status js = p->core.join.leave(ps, cs);
+    if (st != FSGM_OK) return st;
+    FSGM_HIP(hipGetLastError());
+    return js;
+}
+
+}  // namespace fsgm

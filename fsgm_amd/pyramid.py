@@ -40,14 +40,23 @@ def _bind(lib):
     lib._pyramid_bound = True
 
 
-def _params(lib, numPyd, device, overrides):
-    prm = lib.fsgm_pyramid_params_default()
+def _params(default, numPyd, device, overrides, what):
+    """The parameter struct default() returns, with numPyd, device and the keyword overrides (its field names) set."""
+    prm = default()
     prm.numPyd, prm.device = int(numPyd), int(device)
     for k, v in overrides.items():
         if not hasattr(prm, k):
-            raise TypeError(f"unknown pyramidal_sgm parameter {k!r}")
+            raise TypeError(f"unknown {what} parameter {k!r}")
         setattr(prm, k, int(v))
     return prm
+
+
+def _level_sizes(W, H, numPyd):
+    """(width, height) of every level, finest first (impyramid: ceil(size / 2))."""
+    sizes = [(W, H)]
+    for _ in range(1, numPyd):
+        sizes.append(((sizes[-1][0] + 1) // 2, (sizes[-1][1] + 1) // 2))
+    return sizes
 
 
 def _check_images(I0, I1):
@@ -69,10 +78,8 @@ def pyramidal_sgm(I0, I1, numPyd=5, *, device=0, out=None, **overrides):
     _bind(lib)
     I0, I1, ch = _check_images(I0, I1)
     H, W = I0.shape[-2:]
-    prm = _params(lib, numPyd, device, overrides)
-    sizes = [(W, H)]
-    for _ in range(1, prm.numPyd):
-        sizes.append(((sizes[-1][0] + 1) // 2, (sizes[-1][1] + 1) // 2))
+    prm = _params(lib.fsgm_pyramid_params_default, numPyd, device, overrides, "pyramidal_sgm")
+    sizes = _level_sizes(W, H, prm.numPyd)
     if out is not None:
         mv, mvPyd, minC = out
         ok = (mv.shape == (2, H, W) and mv.dtype == np.float64 and minC.shape == (H, W) and minC.dtype == np.uint32 and len(mvPyd) == len(sizes)
@@ -103,9 +110,7 @@ def _pairs_over_devices(fn, prm, pairs, devices):
         if shape not in (None, (W, H, ch)):
             raise ValueError("all pairs of a batch must share one shape")
         shape = (W, H, ch)
-        sizes = [(W, H)]
-        for _ in range(1, prm.numPyd):
-            sizes.append(((sizes[-1][0] + 1) // 2, (sizes[-1][1] + 1) // 2))
+        sizes = _level_sizes(W, H, prm.numPyd)
         mv, minC = np.zeros((2, H, W), np.float64), np.zeros((H, W), np.uint32)
         lv = [np.zeros((2, h, w), np.float64) for (w, h) in sizes]
         ptrs = (C.c_void_p * len(lv))(*[a.ctypes.data for a in lv])
@@ -126,23 +131,29 @@ def pyramidal_sgm_batch(pairs, numPyd=5, *, devices=(0,), **overrides):
     _bind(lib)
     lib.fsgm_pyramidal_sgm_batch_devices_host.argtypes = [C.c_int32, C.POINTER(PyramidPair), C.c_int32, C.c_int32, C.c_int32,
                                                           C.POINTER(PyramidParams), C.c_int32, C.POINTER(C.c_int32)]
-    return _pairs_over_devices(lib.fsgm_pyramidal_sgm_batch_devices_host, _params(lib, numPyd, 0, overrides), pairs, devices)
+    prm = _params(lib.fsgm_pyramid_params_default, numPyd, 0, overrides, "pyramidal_sgm")
+    return _pairs_over_devices(lib.fsgm_pyramidal_sgm_batch_devices_host, prm, pairs, devices)
 
 
-class PyramidPlan:
-    """Device-resident pyramid for one image shape: upload a pair, run, download any level."""
+class _Plan:
+    """Device-resident pyramid for one image shape: upload a pair, run, download any level.  A subclass names its C functions'
+    prefix (_prefix) and creates the plan (_create)."""
+    _prefix = None
 
-    def __init__(self, width, height, channels=1, numPyd=5, *, device=0, batch=1, **overrides):
+    def __init__(self, bind, default, what, width, height, channels, numPyd, device, batch, overrides):
         self.lib = _lib.load()
-        _bind(self.lib)
-        self.prm = _params(self.lib, numPyd, device, overrides)
+        bind(self.lib)
+        self.prm = _params(getattr(self.lib, default), numPyd, device, overrides, what)
         self.W, self.H, self.channels, self.batch = int(width), int(height), int(channels), int(batch)
         self._h = C.c_void_p()
-        check(self.lib.fsgm_pyramid_plan_create_batch(C.byref(self._h), self.W, self.H, self.channels, C.byref(self.prm), self.batch))
+        check(self._create())
+
+    def _call(self, name, *args):
+        return getattr(self.lib, self._prefix + name)(self._h, *args)
 
     def close(self):
         if self._h:
-            self.lib.fsgm_pyramid_plan_destroy(self._h)
+            self._call("destroy")
             self._h = C.c_void_p()
 
     def __enter__(self):
@@ -159,44 +170,55 @@ class PyramidPlan:
 
     def level_size(self, level):
         w, h = C.c_int32(), C.c_int32()
-        check(self.lib.fsgm_pyramid_plan_level_size(self._h, int(level), C.byref(w), C.byref(h)))
+        check(self._call("level_size", int(level), C.byref(w), C.byref(h)))
         return w.value, h.value
 
     def upload(self, I0, I1, frame=0):
         I0, I1, ch = _check_images(I0, I1)
         if ch != self.channels or I0.shape[-2:] != (self.H, self.W):
             raise ValueError("shape mismatch with the plan")
-        check(self.lib.fsgm_pyramid_plan_upload_frame(self._h, int(frame), ptr(I0), ptr(I1)))
+        check(self._call("upload_frame", int(frame), ptr(I0), ptr(I1)))
 
     def run(self):
-        check(self.lib.fsgm_pyramid_plan_run(self._h))
-
-    def sync(self):
-        """Wait for the queued work; plans started with run() before any sync() overlap on the device."""
-        check(self.lib.fsgm_pyramid_plan_sync(self._h))
-
-    def run_images(self):
-        """Only impyramid / rgb2gray (the level images), no matching."""
-        check(self.lib.fsgm_pyramid_plan_run_images(self._h))
+        check(self._call("run"))
 
     def download(self, level=1, frame=0):
         w, h = self.level_size(level)
-        mv = np.empty((2, h, w), np.float64)
+        flow = np.empty((2, h, w), np.float64)
         minC = np.empty((h, w), np.uint32)
-        check(self.lib.fsgm_pyramid_plan_download_frame(self._h, int(frame), int(level), ptr(mv), ptr(minC)))
-        return mv, minC
+        check(self._call("download_frame", int(frame), int(level), ptr(flow), ptr(minC)))
+        return flow, minC
+
+    def time(self, warmup=1, iters=5):
+        ms = C.c_float()
+        check(self._call("time", int(warmup), int(iters), C.byref(ms)))
+        return float(ms.value)
+
+
+class PyramidPlan(_Plan):
+    """Device-resident pyramid for one image shape: upload a pair, run, download any level."""
+    _prefix = "fsgm_pyramid_plan_"
+
+    def __init__(self, width, height, channels=1, numPyd=5, *, device=0, batch=1, **overrides):
+        super().__init__(_bind, "fsgm_pyramid_params_default", "pyramidal_sgm", width, height, channels, numPyd, device, batch, overrides)
+
+    def _create(self):
+        return self.lib.fsgm_pyramid_plan_create_batch(C.byref(self._h), self.W, self.H, self.channels, C.byref(self.prm), self.batch)
+
+    def sync(self):
+        """Wait for the queued work; plans started with run() before any sync() overlap on the device."""
+        check(self._call("sync"))
+
+    def run_images(self):
+        """Only impyramid / rgb2gray (the level images), no matching."""
+        check(self._call("run_images"))
 
     def download_gray(self, level=1, frame=0):
         """The gray image pair calc_pyd_cost_sgm saw at `level` (after impyramid / rgb2gray), of pair `frame` of the batch."""
         w, h = self.level_size(level)
         g0, g1 = np.empty((h, w), np.uint8), np.empty((h, w), np.uint8)
-        check(self.lib.fsgm_pyramid_plan_download_gray_frame(self._h, int(frame), int(level), ptr(g0), ptr(g1)))
+        check(self._call("download_gray_frame", int(frame), int(level), ptr(g0), ptr(g1)))
         return g0, g1
-
-    def time(self, warmup=1, iters=5):
-        ms = C.c_float()
-        check(self.lib.fsgm_pyramid_plan_time(self._h, int(warmup), int(iters), C.byref(ms)))
-        return float(ms.value)
 
 
 class NgPyramidParams(C.Structure):
@@ -223,67 +245,17 @@ def _bind_ng(lib):
     lib._ng_pyramid_bound = True
 
 
-class NgPyramidPlan:
+class NgPyramidPlan(_Plan):
     """Device-resident level loop around calc_pyd_cost_sgm_ng for one image shape (see pyramidal_sgm_ng); `batch` image
     pairs stay resident and go through every level together."""
+    _prefix = "fsgm_ng_pyramid_plan_"
 
     def __init__(self, width, height, channels=1, numPyd=3, *, device=0, batch=1, **overrides):
-        self.lib = _lib.load()
-        _bind_ng(self.lib)
-        prm = self.lib.fsgm_ng_pyramid_params_default()
-        prm.numPyd, prm.device = int(numPyd), int(device)
-        for k, v in overrides.items():
-            if not hasattr(prm, k):
-                raise TypeError(f"unknown pyramidal_sgm_ng parameter {k!r}")
-            setattr(prm, k, int(v))
-        self.prm = prm
-        self.W, self.H, self.channels = int(width), int(height), int(channels)
-        self.batch = int(batch)
-        self._h = C.c_void_p()
-        check(self.lib.fsgm_ng_pyramid_plan_create_batch(C.byref(self._h), self.W, self.H, self.channels, self.batch, C.byref(prm)))
+        super().__init__(_bind_ng, "fsgm_ng_pyramid_params_default", "pyramidal_sgm_ng", width, height, channels, numPyd, device, batch,
+                         overrides)
 
-    def close(self):
-        if self._h:
-            self.lib.fsgm_ng_pyramid_plan_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def level_size(self, level):
-        w, h = C.c_int32(), C.c_int32()
-        check(self.lib.fsgm_ng_pyramid_plan_level_size(self._h, int(level), C.byref(w), C.byref(h)))
-        return w.value, h.value
-
-    def upload(self, I0, I1, frame=0):
-        I0, I1, ch = _check_images(I0, I1)
-        if ch != self.channels or I0.shape[-2:] != (self.H, self.W):
-            raise ValueError("shape mismatch with the plan")
-        check(self.lib.fsgm_ng_pyramid_plan_upload_frame(self._h, int(frame), ptr(I0), ptr(I1)))
-
-    def run(self):
-        check(self.lib.fsgm_ng_pyramid_plan_run(self._h))
-
-    def download(self, level=1, frame=0):
-        w, h = self.level_size(level)
-        flow = np.empty((2, h, w), np.float64)
-        minC = np.empty((h, w), np.uint32)
-        check(self.lib.fsgm_ng_pyramid_plan_download_frame(self._h, int(frame), int(level), ptr(flow), ptr(minC)))
-        return flow, minC
-
-    def time(self, warmup=1, iters=5):
-        ms = C.c_float()
-        check(self.lib.fsgm_ng_pyramid_plan_time(self._h, int(warmup), int(iters), C.byref(ms)))
-        return float(ms.value)
+    def _create(self):
+        return self.lib.fsgm_ng_pyramid_plan_create_batch(C.byref(self._h), self.W, self.H, self.channels, self.batch, C.byref(self.prm))
 
 
 def pyramidal_sgm_ng_batch(pairs, numPyd=3, *, devices=(0,), **overrides):
@@ -293,12 +265,7 @@ def pyramidal_sgm_ng_batch(pairs, numPyd=3, *, devices=(0,), **overrides):
     _bind_ng(lib)
     lib.fsgm_pyramidal_sgm_ng_batch_devices_host.argtypes = [C.c_int32, C.POINTER(PyramidPair), C.c_int32, C.c_int32, C.c_int32,
                                                              C.POINTER(NgPyramidParams), C.c_int32, C.POINTER(C.c_int32)]
-    prm = lib.fsgm_ng_pyramid_params_default()
-    prm.numPyd = int(numPyd)
-    for k, v in overrides.items():
-        if not hasattr(prm, k):
-            raise TypeError(f"unknown pyramidal_sgm_ng parameter {k!r}")
-        setattr(prm, k, int(v))
+    prm = _params(lib.fsgm_ng_pyramid_params_default, numPyd, 0, overrides, "pyramidal_sgm_ng")
     return _pairs_over_devices(lib.fsgm_pyramidal_sgm_ng_batch_devices_host, prm, pairs, devices)
 
 
@@ -315,15 +282,8 @@ def pyramidal_sgm_ng(I0, I1, numPyd=3, *, device=0, out=None, **overrides):
     _bind_ng(lib)
     I0, I1, ch = _check_images(I0, I1)
     H, W = I0.shape[-2:]
-    prm = lib.fsgm_ng_pyramid_params_default()
-    prm.numPyd, prm.device = int(numPyd), int(device)
-    for k, v in overrides.items():
-        if not hasattr(prm, k):
-            raise TypeError(f"unknown pyramidal_sgm_ng parameter {k!r}")
-        setattr(prm, k, int(v))
-    sizes = [(W, H)]
-    for _ in range(1, prm.numPyd):
-        sizes.append(((sizes[-1][0] + 1) // 2, (sizes[-1][1] + 1) // 2))
+    prm = _params(lib.fsgm_ng_pyramid_params_default, numPyd, device, overrides, "pyramidal_sgm_ng")
+    sizes = _level_sizes(W, H, prm.numPyd)
     if out is not None:                                      # a previous call's result tuple, overwritten (see pyramidal_sgm)
         flow, lv, minC = out
         lv = list(lv)[::-1]                                  # returned coarsest first, filled finest first
