@@ -4,6 +4,8 @@
 #include "capi_device.h"
 #include "epi_kernels.h"
 #include "geometry_kernels.h"
+#include "post_kernels.h"
+#include "post_plan.h"
 #include "pyramid_kernels.h"
 #include <algorithm>
 #include <cmath>
@@ -57,6 +59,9 @@ struct fsgm_epi_plan {
     // epipolar driver (fsgm_epipolar_sgm_of_host): rotation flow, composed flow, RGB staging
     double *dRflow = nullptr, *dFlow = nullptr;
     uint8_t* dRgb = nullptr;
+    // test.m's frame body (fsgm_epipolar_flow_pp_*): the vz-index map, the host form's flow2, the chain's scratch plan
+    double *dD1 = nullptr, *dFlow2 = nullptr;
+    fsgm_post_plan* post = nullptr;
     uint2* dRec = nullptr;
     uint16_t* dS0 = nullptr;
     size_t state_stride = 0;
@@ -270,9 +275,11 @@ void fsgm_epi_plan_destroy(fsgm_epi_plan* p) {
     if (!p) return;
     (void)hipSetDevice(p->prm.device);
     void* bufs[] = {p->dI1, p->dI2, p->dCen1, p->dCen2, p->dPd0, p->dNd, p->dOff, p->dVz,
-                    p->dCraw, p->dC, p->dL, p->dBestD, p->dMinC, p->dS, p->dD2enc, p->dD2, p->dConf, p->dLh, p->dX, p->dXup, p->dXupAll, p->dStateUp, p->dLx, p->dState, p->dCkpt, p->dCkptV, p->dRec, p->dS0, p->dRflow, p->dFlow, p->dRgb, p->dBits, p->dBandEdge, p->dBandTicket, p->dBandErr};
+                    p->dCraw, p->dC, p->dL, p->dBestD, p->dMinC, p->dS, p->dD2enc, p->dD2, p->dConf, p->dLh, p->dX, p->dXup, p->dXupAll, p->dStateUp, p->dLx, p->dState, p->dCkpt, p->dCkptV, p->dRec, p->dS0, p->dRflow, p->dFlow, p->dRgb, p->dBits, p->dBandEdge, p->dBandTicket, p->dBandErr,
+                    p->dD1, p->dFlow2};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
+    fsgm_post_plan_destroy(p->post);
     if (p->ev0) (void)hipEventDestroy(p->ev0);
     if (p->ev1) (void)hipEventDestroy(p->ev1);
     for (hipEvent_t e : {p->ev_fork, p->ev_h, p->ev_b, p->ev_c, p->ev_hl[0], p->ev_hl[1], p->ev_hl[2]})
@@ -1123,7 +1130,7 @@ static fsgm_status cached_plan(fsgm_epi_plan** out, int W, int H, int D, int bat
     std::vector<fsgm_epi_plan*>& g_cache = g_epi.v[pr.device];   // (the caller holds g_epi.mu[pr.device])
     for (fsgm_epi_plan* p : g_cache)
         if (p->W == W && p->H == H && p->D == D && p->batch == batch && p->prm.paths == pr.paths &&
-            p->prm.device == pr.device && p->prm.fb_check == pr.fb_check) {
+            p->prm.device == pr.device && p->prm.fb_check == pr.fb_check && p->prm.vz_to_disp == pr.vz_to_disp) {
             p->prm = pr;
             *out = p;
             return FSGM_OK;
@@ -1474,6 +1481,130 @@ fsgm_status fsgm_epipolar_sgm_of_device(int32_t n, const uint8_t* I0, const uint
         if (st == FSGM_OK)
             for (int f = 0; f < n; f++)                                                   // :46-51
                 launch_epi_flow(p->stream, p->dBestD + f * NP, p->dNd + f * 2 * NP, p->dRflow + f * 2 * NP, flow + f * 3 * NP, W, H);
+    }
+    return epi_device_finish(p, cs, status, st);
+}
+
+// ---------------------------------------------------------------------------------------------
+// test.m's frame body (:32-54), the geometry given: the matcher in vz-index mode, D1 = bestD/256, flow, the post-processing
+// chain and flow2, all on the plan's stream
+// ---------------------------------------------------------------------------------------------
+static fsgm_status pp_args(const char* who, int32_t n, const uint8_t* I0, const uint8_t* I1, int32_t W, int32_t H, int32_t channels,
+                           const fsgm_epi_geometry* g, int32_t dMax, const fsgm_epi_params* prm, const double* flow,
+                           const double* flow2, fsgm_epi_params* pr) {
+    FSGM_REQUIRE(n >= 1, "%s: n_frames must be >= 1 (got %d)", who, n);
+    FSGM_REQUIRE(I0 && I1 && g && flow && flow2, "%s: null argument", who);
+    FSGM_REQUIRE(W >= 1 && H >= 1 && dMax >= 1, "%s: width/height/dMax must be >= 1 (got %d x %d x %d)", who, W, H, dMax);
+    FSGM_REQUIRE(channels == 1 || channels == 3, "%s: channels must be 1 (gray) or 3 (RGB planes), got %d", who, channels);
+    *pr = prm ? *prm : fsgm_epi_params_default();
+    FSGM_REQUIRE(!pr->fb_check, "%s: fb_check must be 0 (the chain does its own forward-backward check)", who);
+    if ((double)n * W * H >= 2147483648.0)
+        return fail(FSGM_ERR_UNSUPPORTED, "%s: n_frames * width * height = %.0f reaches 2^31 (32-bit pixel indices)", who, (double)n * W * H);
+    FSGM_DEVICE_SLOT(pr->device);
+    pr->vz_to_disp = 0;                                                                  // the chain works on vz indices
+    return FSGM_OK;
+}
+
+static fsgm_status ensure_pp_buffers(fsgm_epi_plan* p, bool host) {
+    const size_t np = (size_t)p->batch * p->NP;
+    if (!p->post) {
+        fsgm_status st = post_plan_create_batch(&p->post, p->W, p->H, p->batch, p->prm.device, false);
+        if (st != FSGM_OK) return st;
+    }
+    if (!p->dD1) FSGM_HIP(hipMalloc((void**)&p->dD1, np * 8));
+    if (host && !p->dFlow2) FSGM_HIP(hipMalloc((void**)&p->dFlow2, np * 24));
+    return FSGM_OK;
+}
+
+// images in dI1 / dI2 and the maps in dPd0 / dNd / dOff / dRflow: :36 -> flow (:38-42) and flow2 (:45-54); D1 [batch][H][W]
+static fsgm_status enqueue_pp(fsgm_epi_plan* p, int dMax, double vMax, double* flow, double* flow2, double* D1) {
+    fsgm_status st = enqueue(p, FSGM_STAGE_ALL);                                         // :36
+    if (st != FSGM_OK) return st;
+    const int W = p->W, H = p->H, nf = p->batch;
+    const double n = (double)dMax + 1.0;                                                 // :6
+    const PostScratch s = post_plan_scratch(p->post);
+    launch_vz_from_bestd(p->stream, p->dBestD, D1, (size_t)nf * p->NP);
+    post_enqueue_batch(p->stream, s, nf, W, H, D1, p->dPd0, p->dNd, p->dOff, vMax, n, (double)dMax, s.B, s.D2, nullptr, nullptr);
+    launch_epi_pp_flow(p->stream, D1, s.B, p->dOff, p->dNd, p->dRflow, flow, flow2, W, H, nf, vMax, n);
+    FSGM_HIP(hipGetLastError());
+    return FSGM_OK;
+}
+
+fsgm_status fsgm_epipolar_flow_pp_host(int32_t n, const uint8_t* I0, const uint8_t* I1, int32_t W, int32_t H, int32_t channels,
+                                       const fsgm_epi_geometry* g, int32_t dMax, double vMax, const fsgm_epi_params* prm,
+                                       double* flow, double* flow2, double* D1, uint32_t* minC) {
+    fsgm_epi_params pr;
+    fsgm_status st = pp_args("fsgm_epipolar_flow_pp_host", n, I0, I1, W, H, channels, g, dMax, prm, flow, flow2, &pr);
+    if (st != FSGM_OK) return st;
+    std::lock_guard<std::mutex> lk(g_epi.mu[pr.device]);
+    fsgm_epi_plan* p = nullptr;
+    if ((st = cached_plan(&p, W, H, dMax, n, pr)) != FSGM_OK) return st;
+    FSGM_HIP(hipSetDevice(pr.device));
+    if ((st = fsgm_epi_plan_set_penalties(p, 6, 64, vMax)) != FSGM_OK) return st;       // test.m:36
+    if ((st = ensure_driver_buffers(p, channels)) != FSGM_OK) return st;
+    if ((st = ensure_pp_buffers(p, true)) != FSGM_OK) return st;
+    const size_t NP = p->NP, np = (size_t)n * NP;
+    StreamGuard guard(p->stream);
+    for (int f = 0; f < n; f++) {
+        if (channels == 3) {                                                             // one RGB staging pair, reused in stream order
+            FSGM_HIP(hipMemcpyAsync(p->dRgb, I0 + f * 3 * NP, 3 * NP, hipMemcpyHostToDevice, p->stream));
+            FSGM_HIP(hipMemcpyAsync(p->dRgb + 3 * NP, I1 + f * 3 * NP, 3 * NP, hipMemcpyHostToDevice, p->stream));
+            launch_pyr_gray(p->stream, p->dRgb, p->dI1 + f * NP, W, H);
+            launch_pyr_gray(p->stream, p->dRgb + 3 * NP, p->dI2 + f * NP, W, H);
+        }
+        launch_epi_maps(p->stream, geom_args(&g[f], W, H, p->dPd0 + f * 2 * NP, p->dNd + f * 2 * NP, p->dOff + f * NP, p->dRflow + f * 2 * NP));
+    }
+    if (channels == 1) {
+        FSGM_HIP(hipMemcpyAsync(p->dI1, I0, np, hipMemcpyHostToDevice, p->stream));
+        FSGM_HIP(hipMemcpyAsync(p->dI2, I1, np, hipMemcpyHostToDevice, p->stream));
+    }
+    if ((st = enqueue_pp(p, dMax, vMax, p->dFlow, p->dFlow2, p->dD1)) != FSGM_OK) return st;
+    FSGM_HIP(hipMemcpyAsync(flow, p->dFlow, np * 24, hipMemcpyDeviceToHost, p->stream));
+    FSGM_HIP(hipMemcpyAsync(flow2, p->dFlow2, np * 24, hipMemcpyDeviceToHost, p->stream));
+    if (D1) FSGM_HIP(hipMemcpyAsync(D1, p->dD1, np * 8, hipMemcpyDeviceToHost, p->stream));
+    if (minC) FSGM_HIP(hipMemcpyAsync(minC, p->dMinC, np * 4, hipMemcpyDeviceToHost, p->stream));
+    FSGM_HIP(hipStreamSynchronize(p->stream));
+    guard.dismiss();
+    return check_handoff(p);
+}
+
+fsgm_status fsgm_epipolar_flow_pp_device(int32_t n, const uint8_t* I0, const uint8_t* I1, int32_t W, int32_t H, int32_t channels,
+                                         const fsgm_epi_geometry* g, int32_t dMax, double vMax, const fsgm_epi_params* prm,
+                                         double* flow, double* flow2, double* D1, uint32_t* minC, void* stream, int32_t* status) {
+    const char* who = "fsgm_epipolar_flow_pp_device";
+    fsgm_epi_params pr;
+    fsgm_status st = pp_args(who, n, I0, I1, W, H, channels, g, dMax, prm, flow, flow2, &pr);
+    if (st != FSGM_OK) return st;
+    std::lock_guard<std::mutex> lk(g_epi.mu[pr.device]);
+    fsgm_epi_plan* p = nullptr;
+    if ((st = cached_plan(&p, W, H, dMax, n, pr)) != FSGM_OK) return st;
+    const int dev = pr.device;
+    const size_t NP = p->NP, np = (size_t)n * NP;
+    hipStream_t cs = (hipStream_t)stream;
+    FSGM_HIP(hipSetDevice(dev));
+    if ((st = device_check_stream(cs, who)) != FSGM_OK) return st;
+    if ((st = device_check_ptr(I0, np * channels, 1, dev, true, who, "I0")) != FSGM_OK ||
+        (st = device_check_ptr(I1, np * channels, 1, dev, true, who, "I1")) != FSGM_OK ||
+        (st = device_check_ptr(flow, np * 24, 8, dev, true, who, "flow")) != FSGM_OK ||
+        (st = device_check_ptr(flow2, np * 24, 8, dev, true, who, "flow2")) != FSGM_OK ||
+        (st = device_check_ptr(D1, np * 8, 8, dev, false, who, "D1")) != FSGM_OK ||
+        (st = device_check_ptr(minC, np * 4, 4, dev, false, who, "minC")) != FSGM_OK ||
+        (st = device_check_ptr(status, 4, 4, dev, false, who, "status")) != FSGM_OK)
+        return st;
+    if ((st = ensure_driver_buffers(p, 1)) != FSGM_OK) return st;
+    if ((st = ensure_pp_buffers(p, false)) != FSGM_OK) return st;
+    if ((st = epi_device_prepare(p, 6, 64, vMax)) != FSGM_OK) return st;                  // test.m:36
+    if ((st = p->join.enter(cs, p->stream)) != FSGM_OK) return st;
+    {
+        Bind<uint8_t> i1(p->dI1, channels == 1 ? const_cast<uint8_t*>(I0) : nullptr), i2(p->dI2, channels == 1 ? const_cast<uint8_t*>(I1) : nullptr);
+        Bind<uint32_t> mc(p->dMinC, minC);
+        if (channels == 3) {
+            launch_pyr_gray(p->stream, I0, p->dI1, W, H, n);
+            launch_pyr_gray(p->stream, I1, p->dI2, W, H, n);
+        }
+        for (int f = 0; f < n; f++)                                                       // :32, the geometry by value
+            launch_epi_maps(p->stream, geom_args(&g[f], W, H, p->dPd0 + f * 2 * NP, p->dNd + f * 2 * NP, p->dOff + f * NP, p->dRflow + f * 2 * NP));
+        st = enqueue_pp(p, dMax, vMax, flow, flow2, D1 ? D1 : p->dD1);
     }
     return epi_device_finish(p, cs, status, st);
 }

@@ -1,24 +1,65 @@
 // capi_post.hip -- C ABI for the post-processing functions the reference chains after SGM
 // (test.m:45-50): speckle_filter.m, calc_disp_from_first.m, forward_backward_check.m,
-// scanline_in_fill.m, vzInd2Disp.m.  One entry point per MATLAB function (host pointers in / out) and a
-// device-resident plan that runs the whole chain without leaving HBM.
+// scanline_in_fill.m, vzInd2Disp.m.  One entry point per MATLAB function (host pointers in / out), a
+// device-resident plan that runs the whole chain without leaving HBM, and the chain on a batch of maps (host
+// pointers, or device pointers ordered on the caller's stream).
 #include "capi_common.h"
+#include "capi_device.h"
 #include "post_kernels.h"
+#include "post_plan.h"
 #include <math.h>
 #include <mutex>
 #include <vector>
 
 using namespace fsgm;
 
+// A plan for `batch` maps of W x H.  The scratch set (dA, dB, dD2, dParent, dSize, dLeft) is always there; the staging
+// maps of the host entry points (dIn, dOut, dDisp, dPd0, dNd, dO) come with the first host call (a plan of batch 1
+// made by fsgm_post_plan_create has them from the start), the labels' buffers only with batch 1.
 struct fsgm_post_plan {
-    int W = 0, H = 0, device = 0;
-    size_t NP = 0;
+    int W = 0, H = 0, batch = 1, device = 0;
+    size_t NP = 0;                       // pixels of one map
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     double *dIn = nullptr, *dA = nullptr, *dB = nullptr, *dD2 = nullptr, *dOut = nullptr, *dDisp = nullptr;
     double *dPd0 = nullptr, *dNd = nullptr, *dO = nullptr;
     int32_t *dParent = nullptr, *dSize = nullptr, *dScan = nullptr, *dLabels = nullptr, *dLeft = nullptr;
+    uint32_t* dNeg = nullptr;            // device chain: some D1 value was negative (cleared by the status kernel)
+    DeviceJoin join;                     // device-pointer entry points: the events that order the plan's stream with the caller's
 };
+
+namespace fsgm {
+
+// test.m:45-50 on nf maps: D1 -> filterD1 (out), filterD2, disp (may be null).  Every stage is one launch for the batch.
+// filterD1 must not be s.A; it may be s.B (the last read of B is before the fill writes it).
+void post_enqueue_batch(hipStream_t st, const PostScratch& s, int nf, int W, int H, const double* D1, const double* Pd0,
+                        const double* nd, const double* O, double vMax, double n, double dMax, double* filterD1,
+                        double* filterD2, double* disp, uint32_t* neg) {
+    const PostGeom g{Pd0, nd, O, vMax, n};
+    launch_speckle_filter(st, D1, s.A, nullptr, s.parent, s.size, nullptr, W, H, 2.0, 100.0, nf, neg);               // :45
+    launch_disp_from_first(st, s.A, filterD2, g, W, H, nf);                                                           // :46
+    launch_fb_check(st, s.A, filterD2, s.B, g, W, H, nf);                                                             // :47
+    launch_speckle_filter(st, s.B, s.A, nullptr, s.parent, s.size, nullptr, W, H, dMax,
+                          (double)H * (double)W / 10.0, nf);                                                          // :48 rows*cols/10 of one map
+    launch_scanline_in_fill(st, s.A, filterD1, s.left, W, H, nf);                                                     // :49
+    if (disp) launch_vzind2disp(st, filterD1, O, disp, (size_t)W * H * nf, vMax, n);                                  // :50
+}
+
+PostScratch post_plan_scratch(fsgm_post_plan* p) { return PostScratch{p->dA, p->dB, p->dD2, p->dParent, p->dSize, p->dLeft}; }
+
+}  // namespace fsgm
+
+static fsgm_status ensure_staging(fsgm_post_plan* p) {
+    const size_t np = p->NP * p->batch;
+    hipError_t e = hipSuccess;
+    auto alloc = [&](double** b, size_t bytes) { if (e == hipSuccess && !*b) e = hipMalloc((void**)b, bytes); };
+    for (double** b : {&p->dIn, &p->dOut, &p->dDisp, &p->dO}) alloc(b, np * 8);
+    alloc(&p->dPd0, np * 16);
+    alloc(&p->dNd, np * 16);
+    if (e != hipSuccess)
+        return fail(e == hipErrorOutOfMemory ? FSGM_ERR_NOMEM : FSGM_ERR_HIP, "post-processing plan: %s", hipGetErrorString(e));
+    return FSGM_OK;
+}
 
 extern "C" {
 
@@ -26,34 +67,42 @@ void fsgm_post_plan_destroy(fsgm_post_plan* p) {
     if (!p) return;
     (void)hipSetDevice(p->device);
     void* bufs[] = {p->dIn, p->dA, p->dB, p->dD2, p->dOut, p->dDisp, p->dPd0, p->dNd, p->dO,
-                    p->dParent, p->dSize, p->dScan, p->dLabels, p->dLeft};
+                    p->dParent, p->dSize, p->dScan, p->dLabels, p->dLeft, p->dNeg};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     if (p->ev0) (void)hipEventDestroy(p->ev0);
     if (p->ev1) (void)hipEventDestroy(p->ev1);
+    p->join.destroy();
     if (p->stream) (void)hipStreamDestroy(p->stream);
     delete p;
 }
 
-fsgm_status fsgm_post_plan_create(fsgm_post_plan** out, int32_t W, int32_t H, int32_t device) {
+}  // extern "C"
+
+fsgm_status fsgm::post_plan_create_batch(fsgm_post_plan** out, int32_t W, int32_t H, int32_t batch, int32_t device, bool staging) {
     FSGM_REQUIRE(out, "fsgm_post_plan_create: null plan pointer");
     *out = nullptr;
     FSGM_REQUIRE(W >= 1 && H >= 1, "width/height must be >= 1 (got %d x %d)", W, H);
-    if ((double)W * H >= 2147483648.0) return fail(FSGM_ERR_UNSUPPORTED, "map exceeds 2^31 pixels");
+    FSGM_REQUIRE(batch >= 1, "n_frames must be >= 1 (got %d)", batch);
+    if ((double)W * H * batch >= 2147483648.0) return fail(FSGM_ERR_UNSUPPORTED, "n_frames * width * height reaches 2^31 pixels");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
         return fail(FSGM_ERR_HIP, "no HIP device available (libfsgm_hip has no CPU fallback)");
     FSGM_REQUIRE(device >= 0 && device < ndev, "device %d out of range (have %d)", device, ndev);
     FSGM_HIP(hipSetDevice(device));
     fsgm_post_plan* p = new fsgm_post_plan;
-    p->W = W; p->H = H; p->device = device; p->NP = (size_t)W * H;
+    p->W = W; p->H = H; p->batch = batch; p->device = device; p->NP = (size_t)W * H;
+    const size_t np = p->NP * batch;
     hipError_t e = hipSuccess;
     auto alloc = [&](void** ptr, size_t bytes) { if (e == hipSuccess) e = hipMalloc(ptr, bytes); };
-    for (double** b : {&p->dIn, &p->dA, &p->dB, &p->dD2, &p->dOut, &p->dDisp, &p->dO}) alloc((void**)b, p->NP * 8);
-    alloc((void**)&p->dPd0, p->NP * 16);
-    alloc((void**)&p->dNd, p->NP * 16);
-    for (int32_t** b : {&p->dParent, &p->dSize, &p->dLabels, &p->dLeft}) alloc((void**)b, p->NP * 4);
-    alloc((void**)&p->dScan, (p->NP / 1024 + 2) * 4);
+    for (double** b : {&p->dA, &p->dB, &p->dD2}) alloc((void**)b, np * 8);
+    for (int32_t** b : {&p->dParent, &p->dSize, &p->dLeft}) alloc((void**)b, np * 4);
+    if (batch == 1) {
+        alloc((void**)&p->dLabels, p->NP * 4);
+        alloc((void**)&p->dScan, (p->NP / 1024 + 2) * 4);
+    }
+    alloc((void**)&p->dNeg, 4);
+    if (e == hipSuccess) e = hipMemset(p->dNeg, 0, 4);
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking);
     if (e == hipSuccess) e = hipEventCreate(&p->ev0);
     if (e == hipSuccess) e = hipEventCreate(&p->ev1);
@@ -61,8 +110,19 @@ fsgm_status fsgm_post_plan_create(fsgm_post_plan** out, int32_t W, int32_t H, in
         fsgm_post_plan_destroy(p);
         return fail(e == hipErrorOutOfMemory ? FSGM_ERR_NOMEM : FSGM_ERR_HIP, "fsgm_post_plan_create: %s", hipGetErrorString(e));
     }
+    fsgm_status st;
+    if (staging && (st = ensure_staging(p)) != FSGM_OK) {
+        fsgm_post_plan_destroy(p);
+        return st;
+    }
     *out = p;
     return FSGM_OK;
+}
+
+extern "C" {
+
+fsgm_status fsgm_post_plan_create(fsgm_post_plan** out, int32_t W, int32_t H, int32_t device) {
+    return post_plan_create_batch(out, W, H, 1, device, true);
 }
 
 fsgm_status fsgm_post_plan_upload(fsgm_post_plan* p, const double* D1, const double* Pd0, const double* normDirect, const double* O) {
@@ -78,17 +138,10 @@ fsgm_status fsgm_post_plan_upload(fsgm_post_plan* p, const double* D1, const dou
     return FSGM_OK;
 }
 
-// test.m:45-50 on the uploaded map: dIn -> dOut (filterD1), dD2 (filterD2), dDisp
+// test.m:45-50 on the uploaded maps: dIn -> dOut (filterD1), dD2 (filterD2), dDisp
 static fsgm_status post_enqueue(fsgm_post_plan* p, double vMax, double n, double dMax) {
-    PostGeom g{p->dPd0, p->dNd, p->dO, vMax, n};
-    const int W = p->W, H = p->H;
-    launch_speckle_filter(p->stream, p->dIn, p->dA, nullptr, p->dParent, p->dSize, p->dScan, W, H, 2.0, 100.0);      // :45
-    launch_disp_from_first(p->stream, p->dA, p->dD2, g, W, H);                                                        // :46
-    launch_fb_check(p->stream, p->dA, p->dD2, p->dB, g, W, H);                                                        // :47
-    launch_speckle_filter(p->stream, p->dB, p->dA, nullptr, p->dParent, p->dSize, p->dScan, W, H, dMax,
-                          (double)H * (double)W / 10.0);                                                              // :48 rows*cols/10
-    launch_scanline_in_fill(p->stream, p->dA, p->dOut, p->dLeft, W, H);                                               // :49
-    launch_vzind2disp(p->stream, p->dOut, p->dO, p->dDisp, p->NP, vMax, n);                                           // :50
+    post_enqueue_batch(p->stream, post_plan_scratch(p), p->batch, p->W, p->H, p->dIn, p->dPd0, p->dNd, p->dO, vMax, n, dMax,
+                       p->dOut, p->dD2, p->dDisp, nullptr);
     FSGM_HIP(hipGetLastError());
     return FSGM_OK;
 }
@@ -136,12 +189,17 @@ void fsgm_post_shutdown_internal(void) {
     g_post_cache.clear();
 }
 
-static fsgm_status cached_plan(fsgm_post_plan** out, int W, int H, int device) {
+// plans per (W, H, batch, device); staging: the host entry points' maps are wanted (added to a cached plan that lacks them)
+static fsgm_status cached_plan(fsgm_post_plan** out, int W, int H, int device, int batch = 1, bool staging = true) {
     for (fsgm_post_plan* q : g_post_cache)
-        if (q->W == W && q->H == H && q->device == device) { *out = q; return hipSetDevice(device) == hipSuccess ? FSGM_OK : fail(FSGM_ERR_HIP, "hipSetDevice failed"); }
-    fsgm_status st = fsgm_post_plan_create(out, W, H, device);
+        if (q->W == W && q->H == H && q->batch == batch && q->device == device) {
+            *out = q;
+            if (hipSetDevice(device) != hipSuccess) return fail(FSGM_ERR_HIP, "hipSetDevice failed");
+            return staging ? ensure_staging(q) : FSGM_OK;
+        }
+    fsgm_status st = post_plan_create_batch(out, W, H, batch, device, staging);
     if (st != FSGM_OK) return st;
-    if (g_post_cache.size() >= 2) {
+    if (g_post_cache.size() >= 4) {
         fsgm_post_plan_destroy(g_post_cache.front());
         g_post_cache.erase(g_post_cache.begin());
     }
@@ -278,6 +336,93 @@ fsgm_status fsgm_epi_postprocess_host(const double* D1, int32_t W, int32_t H, co
     if ((st = fsgm_post_plan_upload(p, D1, Pd0, normDirect, O)) != FSGM_OK) return st;
     if ((st = post_enqueue(p, vMax, n, dMax)) != FSGM_OK) return st;
     return fsgm_post_plan_download(p, filterD1, filterD2, disp);
+}
+
+// ---- the chain on a batch of maps ----
+static fsgm_status batch_args(const char* who, int32_t n_frames, int32_t W, int32_t H, bool ok_ptrs, int32_t device) {
+    FSGM_REQUIRE(n_frames >= 1, "%s: n_frames must be >= 1 (got %d)", who, n_frames);
+    FSGM_REQUIRE(ok_ptrs, "%s: null argument", who);
+    FSGM_REQUIRE(W >= 1 && H >= 1, "%s: width/height must be >= 1 (got %d x %d)", who, W, H);
+    if ((double)n_frames * W * H >= 2147483648.0)
+        return fail(FSGM_ERR_UNSUPPORTED, "%s: n_frames * width * height = %.0f reaches 2^31 (32-bit pixel indices)", who, (double)n_frames * W * H);
+    FSGM_DEVICE_SLOT(device);
+    return FSGM_OK;
+}
+
+fsgm_status fsgm_epi_postprocess_batch_host(int32_t n_frames, const double* D1, int32_t W, int32_t H, const double* Pd0,
+                                            const double* normDirect, const double* O, double vMax, double n, double dMax,
+                                            double* filterD1, double* filterD2, double* disp, int32_t device) {
+    const char* who = "fsgm_epi_postprocess_batch";
+    fsgm_status st = batch_args(who, n_frames, W, H, D1 && Pd0 && normDirect && O && filterD1, device);
+    if (st != FSGM_OK) return st;
+    const size_t np = (size_t)n_frames * W * H;
+    if ((st = require_non_negative(D1, np, who)) != FSGM_OK) return st;
+    std::lock_guard<std::mutex> lk(g_post_mu);
+    fsgm_post_plan* p;
+    if ((st = cached_plan(&p, W, H, device, n_frames, true)) != FSGM_OK) return st;
+    StreamGuard guard(p->stream);   // an early exit drains the stream: queued copies use the caller's memory
+    FSGM_HIP(hipMemcpyAsync(p->dIn, D1, np * 8, hipMemcpyHostToDevice, p->stream));
+    FSGM_HIP(hipMemcpyAsync(p->dPd0, Pd0, np * 16, hipMemcpyHostToDevice, p->stream));
+    FSGM_HIP(hipMemcpyAsync(p->dNd, normDirect, np * 16, hipMemcpyHostToDevice, p->stream));
+    FSGM_HIP(hipMemcpyAsync(p->dO, O, np * 8, hipMemcpyHostToDevice, p->stream));
+    if ((st = post_enqueue(p, vMax, n, dMax)) != FSGM_OK) return st;
+    FSGM_HIP(hipMemcpyAsync(filterD1, p->dOut, np * 8, hipMemcpyDeviceToHost, p->stream));
+    if (filterD2) FSGM_HIP(hipMemcpyAsync(filterD2, p->dD2, np * 8, hipMemcpyDeviceToHost, p->stream));
+    if (disp) FSGM_HIP(hipMemcpyAsync(disp, p->dDisp, np * 8, hipMemcpyDeviceToHost, p->stream));
+    FSGM_HIP(hipStreamSynchronize(p->stream));
+    guard.dismiss();
+    return FSGM_OK;
+}
+
+fsgm_status fsgm_epi_postprocess_device(int32_t n_frames, const double* D1, int32_t W, int32_t H, const double* Pd0,
+                                        const double* normDirect, const double* O, double vMax, double n, double dMax,
+                                        double* filterD1, double* filterD2, double* disp, int32_t device, void* stream,
+                                        int32_t* status) {
+    const char* who = "fsgm_epi_postprocess_device";
+    fsgm_status st = batch_args(who, n_frames, W, H, D1 && Pd0 && normDirect && O && filterD1, device);
+    if (st != FSGM_OK) return st;
+    const size_t np = (size_t)n_frames * W * H;
+    hipStream_t cs = (hipStream_t)stream;
+    std::lock_guard<std::mutex> lk(g_post_mu);
+    fsgm_post_plan* p;
+    if ((st = cached_plan(&p, W, H, device, n_frames, false)) != FSGM_OK) return st;
+    if ((st = device_check_stream(cs, who)) != FSGM_OK) return st;
+    if ((st = device_check_ptr(D1, np * 8, 8, device, true, who, "D1")) != FSGM_OK ||
+        (st = device_check_ptr(Pd0, np * 16, 8, device, true, who, "Pd0")) != FSGM_OK ||
+        (st = device_check_ptr(normDirect, np * 16, 8, device, true, who, "normDirect")) != FSGM_OK ||
+        (st = device_check_ptr(O, np * 8, 8, device, true, who, "O")) != FSGM_OK ||
+        (st = device_check_ptr(filterD1, np * 8, 8, device, true, who, "filterD1")) != FSGM_OK ||
+        (st = device_check_ptr(filterD2, np * 8, 8, device, false, who, "filterD2")) != FSGM_OK ||
+        (st = device_check_ptr(disp, np * 8, 8, device, false, who, "disp")) != FSGM_OK ||
+        (st = device_check_ptr(status, 4, 4, device, false, who, "status")) != FSGM_OK)
+        return st;
+    if ((st = p->join.ensure()) != FSGM_OK) return st;
+    if ((st = p->join.enter(cs, p->stream)) != FSGM_OK) return st;
+    post_enqueue_batch(p->stream, post_plan_scratch(p), n_frames, W, H, D1, Pd0, normDirect, O, vMax, n, dMax, filterD1,
+                       filterD2 ? filterD2 : p->dD2, disp, status ? p->dNeg : nullptr);
+    if (status) launch_post_status(p->stream, p->dNeg, status);
+    const hipError_t le = hipGetLastError();
+    const fsgm_status js = p->join.leave(p->stream, cs);
+    if (le != hipSuccess) return fail(FSGM_ERR_HIP, "%s: launch failed: %s", who, hipGetErrorString(le));
+    return js;
+}
+
+fsgm_status fsgm_vmf_device(int32_t n_frames, const double* flow, int32_t W, int32_t H, int32_t channels, double* flowMed,
+                            int32_t device, void* stream) {
+    const char* who = "fsgm_vmf_device";
+    fsgm_status st = batch_args(who, n_frames, W, H, flow && flowMed, device);
+    if (st != FSGM_OK) return st;
+    FSGM_REQUIRE(channels >= 1 && channels <= 3, "%s: 1..3 channels (got %d)", who, channels);
+    const size_t nv = (size_t)n_frames * channels * W * H;
+    hipStream_t cs = (hipStream_t)stream;
+    FSGM_HIP(hipSetDevice(device));
+    if ((st = device_check_stream(cs, who)) != FSGM_OK) return st;
+    if ((st = device_check_ptr(flow, nv * 8, 8, device, true, who, "flow")) != FSGM_OK ||
+        (st = device_check_ptr(flowMed, nv * 8, 8, device, true, who, "flowMed")) != FSGM_OK)
+        return st;
+    launch_vmf(cs, flow, flowMed, W, H, n_frames * channels);   // no scratch: queued on the caller's stream itself
+    FSGM_HIP(hipGetLastError());
+    return FSGM_OK;
 }
 
 }  // extern "C"

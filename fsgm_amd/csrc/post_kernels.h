@@ -15,18 +15,34 @@ struct PostGeom {           // the three maps of epipolar_geometry.m that the di
     double vMax, n;
 };
 
+// Every launcher takes a frame count nf: the maps are nf contiguous frames in the layouts above ([nf][H][W],
+// [nf][2][H][W]), one launch per kernel covers the whole batch, and no stage reads or writes across a frame boundary.
+// With nf = 1 each kernel computes exactly what the single-map form did.  nf*W*H must stay below 2^31 (i32 indices).
+
 // speckle_filter.m: out = image with every 4-connected region (neighbours joined when both valid and
-// |a-b| < maxDiff) of fewer than maxSpeckleSize pixels set to NaN.  parent, size: i32 [H*W] scratch
-// (parent ends up holding each pixel's region root = the region's first pixel in raster order).
-// labels (may be null): i32 [H*W], regions numbered in raster order of their first pixel, 0 = invalid;
-// scan: i32 [H*W/1024 + 2] scratch for it.
+// |a-b| < maxDiff) of fewer than maxSpeckleSize pixels set to NaN (maxSpeckleSize is per region, i.e. per frame).
+// parent, size: i32 [nf*H*W] scratch (parent ends up holding each pixel's region root = the region's first pixel in
+// raster order of its frame).  labels (may be null; nf must then be 1): i32 [H*W], regions numbered in raster order of
+// their first pixel, 0 = invalid; scan: i32 [H*W/1024 + 2] scratch for it.  neg (may be null): set to 1 when some
+// pixel of `image` is negative (the device chain's report of a precondition the host entry points check on the host).
 void launch_speckle_filter(hipStream_t st, const double* image, double* out, int32_t* labels, int32_t* parent,
-                           int32_t* size, int32_t* scan, int W, int H, double maxDiff, double maxSpeckleSize);
-void launch_disp_from_first(hipStream_t st, const double* D1, double* D2, const PostGeom& g, int W, int H);
-void launch_fb_check(hipStream_t st, const double* D1, const double* D2, double* out, const PostGeom& g, int W, int H);
-// left: i32 [H*W] scratch
-void launch_scanline_in_fill(hipStream_t st, const double* in, double* out, int32_t* left, int W, int H);
-void launch_vmf(hipStream_t st, const double* in, double* out, int W, int H, int channels);   // vmf.m: 5x5 median per plane
+                           int32_t* size, int32_t* scan, int W, int H, double maxDiff, double maxSpeckleSize,
+                           int nf = 1, uint32_t* neg = nullptr);
+void launch_disp_from_first(hipStream_t st, const double* D1, double* D2, const PostGeom& g, int W, int H, int nf = 1);
+void launch_fb_check(hipStream_t st, const double* D1, const double* D2, double* out, const PostGeom& g, int W, int H, int nf = 1);
+// left: i32 [nf*H*W] scratch
+void launch_scanline_in_fill(hipStream_t st, const double* in, double* out, int32_t* left, int W, int H, int nf = 1);
+// vmf.m: 5x5 median per plane, `planes` planes of H x W (a batch of flows: nf * channels)
+void launch_vmf(hipStream_t st, const double* in, double* out, int W, int H, int planes);
 void launch_vzind2disp(hipStream_t st, const double* w, const double* O, double* D, size_t n_px, double vMax, double n);
+
+// D1 = bestD / 256 (the matcher's fixed-point vz index, vz_to_disp = 0, as a vz index map; exact)
+void launch_vz_from_bestd(hipStream_t st, const uint32_t* bestD, double* D1, size_t n_px);
+// test.m:38-42 and :50-54 in one pass over nf frames: flow [nf][3][H][W] from D1, flow2 from filterD1;
+// O [nf][H][W], nd / rflow [nf][2][H][W]
+void launch_epi_pp_flow(hipStream_t st, const double* D1, const double* filterD1, const double* O, const double* nd,
+                        const double* rflow, double* flow, double* flow2, int W, int H, int nf, double vMax, double n);
+// one wave: *status = *neg ? FSGM_ERR_INVALID : 0, *neg cleared (status may be null)
+void launch_post_status(hipStream_t st, uint32_t* neg, int32_t* status);
 
 }  // namespace fsgm

@@ -3,6 +3,8 @@
 // kernel computes the same result in an order-free form and says why that is the same thing.
 #include "post_kernels.h"
 #include "fsgm_device.h"
+#include "../../include/fsgm.h"
+#include <algorithm>
 
 namespace fsgm {
 
@@ -13,6 +15,9 @@ namespace fsgm {
 // (:94-97, and :27-30 for its later pixels).  Components by lock-free union-find: the root of a
 // region is its smallest pixel index = the flood fill's seed (first pixel in raster order), so
 // numbering the roots in index order reproduces the reference's labels (:37,:101).
+// A batch of nf frames is one graph over the global indices f*W*H + i with no edge across a frame boundary (the merge
+// tests y + 1 < H against the frame's own H), so every component lies inside one frame and its root -- the smallest
+// global index -- is the smallest index of its frame: the per-frame results are those of nf single-map runs.
 // =============================================================================================
 __device__ __forceinline__ int ccl_find(int32_t* parent, int i) {
     int p = __hip_atomic_load(&parent[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -35,15 +40,21 @@ __device__ __forceinline__ void ccl_union(int32_t* parent, int a, int b) {
     }
 }
 
-__global__ __launch_bounds__(256) void ccl_init_kernel(int32_t* parent, int32_t* size, int n) {
+__global__ __launch_bounds__(256) void ccl_init_kernel(int32_t* parent, int32_t* size, int n, const double* __restrict__ img,
+                                                      uint32_t* neg) {
     const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < n) { parent[i] = i; size[i] = 0; }
+    if (i < n) {
+        parent[i] = i;
+        size[i] = 0;
+        if (neg && img[i] < 0.0) *neg = 1u;                      // every writer stores the same value
+    }
 }
 
-__global__ __launch_bounds__(256) void ccl_merge_kernel(const double* __restrict__ img, int32_t* parent, int W, int H, double maxDiff) {
+// frames f0 + blockIdx.z
+__global__ __launch_bounds__(256) void ccl_merge_kernel(const double* __restrict__ img, int32_t* parent, int W, int H, int f0, double maxDiff) {
     const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
     if (x >= W || y >= H) return;
-    const int i = y * W + x;
+    const int i = (f0 + (int)blockIdx.z) * W * H + y * W + x;
     const double v = img[i];
     if (isnan(v)) return;
     if (x + 1 < W) {                                             // :53-60 (and :63-70 seen from the other side)
@@ -166,39 +177,40 @@ __global__ __launch_bounds__(256) void fill_kernel(double* p, double v, size_t n
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i < n) p[i] = v;
 }
-__global__ __launch_bounds__(256) void disp_from_first_kernel(const double* __restrict__ D1, double* D2, PostGeom g, int W, int H) {
+// frames f0 + blockIdx.z: D1 / D2 / O at f*NP, Pd0 / nd at f*2*NP; every target lies in the pixel's own frame
+__global__ __launch_bounds__(256) void disp_from_first_kernel(const double* __restrict__ D1, double* D2, PostGeom g, int W, int H, int f0) {
     const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
     if (x >= W || y >= H) return;
-    const size_t NP = (size_t)W * H, p = (size_t)y * W + x;
+    const size_t NP = (size_t)W * H, f = (size_t)f0 + blockIdx.z, p = f * NP + (size_t)y * W + x, q = f * NP + p;
     const double v = D1[p];
     const double disp = vzind2disp(v, g.O[p], g.vMax, g.n);                                      // :11
-    const double p2x = __dadd_rn(g.Pd0[p], __dmul_rn(disp, g.nd[p]));                            // :13-14
-    const double p2y = __dadd_rn(g.Pd0[NP + p], __dmul_rn(disp, g.nd[NP + p]));
+    const double p2x = __dadd_rn(g.Pd0[q], __dmul_rn(disp, g.nd[q]));                            // :13-14
+    const double p2y = __dadd_rn(g.Pd0[NP + q], __dmul_rn(disp, g.nd[NP + q]));
     const double sx0 = floor(p2x), sy0 = floor(p2y);                                             // :16
 #pragma unroll
     for (int k = 0; k < 4; k++) {
         const double sx = sx0 + (double)(k & 1), sy = sy0 + (double)(k >> 1);                    // :17, four corners :24-46
         if (sx >= 1.0 && sx <= (double)W && sy >= 1.0 && sy <= (double)H)
-            atomicMax((long long*)&D2[(size_t)((int)sy - 1) * W + ((int)sx - 1)], __double_as_longlong(v));
+            atomicMax((long long*)&D2[f * NP + (size_t)((int)sy - 1) * W + ((int)sx - 1)], __double_as_longlong(v));
     }
 }
 
 // forward_backward_check.m:1-39: each pixel decides about itself only
 __global__ __launch_bounds__(256) void fb_check_map_kernel(const double* __restrict__ D1, const double* __restrict__ D2,
-                                                           double* __restrict__ out, PostGeom g, int W, int H) {
+                                                           double* __restrict__ out, PostGeom g, int W, int H, int f0) {
     const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
     if (x >= W || y >= H) return;
-    const size_t NP = (size_t)W * H, p = (size_t)y * W + x;
+    const size_t NP = (size_t)W * H, f = (size_t)f0 + blockIdx.z, p = f * NP + (size_t)y * W + x, q = f * NP + p;
     const double nan = __longlong_as_double(0x7FF8000000000000LL);
     const double v = D1[p];
     double r = v;
     if (!isnan(v)) {                                                                             // :12
         const double disp = vzind2disp(v, g.O[p], g.vMax, g.n);                                  // :15
-        const double p2x = round(__dadd_rn(g.Pd0[p], __dmul_rn(disp, g.nd[p])));                 // :17-20, half away from zero
-        const double p2y = round(__dadd_rn(g.Pd0[NP + p], __dmul_rn(disp, g.nd[NP + p])));
+        const double p2x = round(__dadd_rn(g.Pd0[q], __dmul_rn(disp, g.nd[q])));                 // :17-20, half away from zero
+        const double p2y = round(__dadd_rn(g.Pd0[NP + q], __dmul_rn(disp, g.nd[NP + q])));
         if (!(p2x >= 1.0 && p2x <= (double)W && p2y >= 1.0 && p2y <= (double)H)) r = nan;        // :22 (a NaN target fails every test of :22 and reads D2(NaN): MATLAB errors; here: invalid)
         else {
-            const double d2 = D2[(size_t)((int)p2y - 1) * W + ((int)p2x - 1)];
+            const double d2 = D2[f * NP + (size_t)((int)p2y - 1) * W + ((int)p2x - 1)];
             if (d2 == -1.0 || fabs(__dsub_rn(v, d2)) > 2.0) r = nan;                             // :27,:32 (thr :6)
         }
     }
@@ -213,6 +225,8 @@ __global__ __launch_bounds__(256) void fb_check_map_kernel(const double* __restr
 // min(v[l], v[r]), v[r] or v[l].  l by a running-maximum scan, r by a running-minimum scan from the
 // right (one workgroup per row).  Column pass (:50-69): only the cells above the first / below the
 // last valid cell of a column are filled; one thread per column walks it (coalesced across columns).
+// A batch: the row pass sees nf*H independent rows; the column pass has one thread per (frame, column), which walks
+// the H rows of its own frame only.
 // =============================================================================================
 __device__ __forceinline__ int block_scan_max_256(int v, int* sh) {      // inclusive, in thread order
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -266,9 +280,11 @@ __global__ __launch_bounds__(256) void infill_rows_kernel(const double* __restri
         __syncthreads();
     }
 }
-__global__ __launch_bounds__(256) void infill_cols_kernel(double* io, int W, int H) {
-    const int x = blockIdx.x * 256 + threadIdx.x;
-    if (x >= W) return;
+__global__ __launch_bounds__(256) void infill_cols_kernel(double* io, int W, int H, int nf) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= nf * W) return;
+    const int f = t / W, x = t - f * W;
+    io += (size_t)f * W * H;
     int first = -1, last = -1;
     for (int y = 0; y < H; y++)
         if (!isnan(io[(size_t)y * W + x])) { if (first < 0) first = y; last = y; }
@@ -283,10 +299,10 @@ __global__ __launch_bounds__(256) void infill_cols_kernel(double* io, int W, int
 // per pixel; the minimum of the remaining values is removed 12 times, the 13th minimum is the median
 // (selection by repeated min/max exchange over a register array: no data-dependent indexing).
 // =============================================================================================
-__global__ __launch_bounds__(256) void vmf_kernel(const double* __restrict__ in, double* __restrict__ out, int W, int H) {
+__global__ __launch_bounds__(256) void vmf_kernel(const double* __restrict__ in, double* __restrict__ out, int W, int H, int z0) {
     const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
     if (x >= W || y >= H) return;
-    const size_t plane = (size_t)blockIdx.z * W * H;
+    const size_t plane = ((size_t)z0 + blockIdx.z) * W * H;
     double w[25];
 #pragma unroll
     for (int dy = -2; dy <= 2; dy++)
@@ -308,21 +324,76 @@ __global__ __launch_bounds__(256) void vmf_kernel(const double* __restrict__ in,
     out[plane + (size_t)y * W + x] = w[12];
 }
 
-void launch_vmf(hipStream_t st, const double* in, double* out, int W, int H, int channels) {
-    hipLaunchKernelGGL(vmf_kernel, dim3((W + 63) / 64, (H + 3) / 4, channels), dim3(256), 0, st, in, out, W, H);
+// =============================================================================================
+// test.m's per-frame body around the chain: D1 = bestD/256, then flow (:38-42) and flow2 (:50-54) in one pass
+// =============================================================================================
+__global__ __launch_bounds__(256) void vz_from_bestd_kernel(const uint32_t* __restrict__ bestD, double* __restrict__ D1, size_t n_px) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n_px) D1[i] = __ddiv_rn((double)bestD[i], 256.0);
+}
+
+__global__ __launch_bounds__(256) void epi_pp_flow_kernel(const double* __restrict__ D1, const double* __restrict__ filterD1,
+                                                          const double* __restrict__ O, const double* __restrict__ nd,
+                                                          const double* __restrict__ rflow, double* __restrict__ flow,
+                                                          double* __restrict__ flow2, size_t NP, size_t n_px, double vMax, double n) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_px) return;
+    const size_t f = i / NP, p = i - f * NP, m = 2 * f * NP + p, q = 3 * f * NP + p;
+    const double w = D1[i], fw = filterD1[i], o = O[i];
+    const double nx = nd[m], ny = nd[m + NP], rx = rflow[m], ry = rflow[m + NP];
+    const double d = vzind2disp(w, o, vMax, n);                                                    // :39
+    flow[q] = __dadd_rn(__dmul_rn(d, nx), rx);                                                     // :40-41
+    flow[q + NP] = __dadd_rn(__dmul_rn(d, ny), ry);
+    flow[q + 2 * NP] = isnan(w) ? 0.0 : 1.0;                                                       // :42
+    const double fd = vzind2disp(fw, o, vMax, n);                                                  // :50
+    flow2[q] = __dadd_rn(__dmul_rn(fd, nx), rx);                                                   // :51-52
+    flow2[q + NP] = __dadd_rn(__dmul_rn(fd, ny), ry);
+    flow2[q + 2 * NP] = isnan(fw) ? 0.0 : 1.0;                                                     // :53
+}
+
+__global__ __launch_bounds__(64) void post_status_kernel(uint32_t* __restrict__ neg, int32_t* __restrict__ status) {
+    if (threadIdx.x != 0) return;
+    const uint32_t v = *neg;
+    *neg = 0;
+    if (status) *status = v ? (int32_t)FSGM_ERR_INVALID : 0;
 }
 
 // =============================================================================================
-// launchers
+// launchers.  Frame-indexed grids put the frame in blockIdx.z, whose range is 65535: more frames (only tiny maps
+// can have that many below 2^31 pixels) take one launch per 65535.
 // =============================================================================================
+constexpr int MAX_GRID_Z = 65535;
+
+void launch_vmf(hipStream_t st, const double* in, double* out, int W, int H, int planes) {
+    for (int z0 = 0; z0 < planes; z0 += MAX_GRID_Z)
+        hipLaunchKernelGGL(vmf_kernel, dim3((W + 63) / 64, (H + 3) / 4, std::min(planes - z0, MAX_GRID_Z)), dim3(256), 0, st, in, out, W, H, z0);
+}
+
+void launch_vz_from_bestd(hipStream_t st, const uint32_t* bestD, double* D1, size_t n_px) {
+    hipLaunchKernelGGL(vz_from_bestd_kernel, dim3((unsigned)((n_px + 255) / 256)), dim3(256), 0, st, bestD, D1, n_px);
+}
+
+void launch_epi_pp_flow(hipStream_t st, const double* D1, const double* filterD1, const double* O, const double* nd,
+                        const double* rflow, double* flow, double* flow2, int W, int H, int nf, double vMax, double n) {
+    const size_t NP = (size_t)W * H, n_px = NP * nf;
+    hipLaunchKernelGGL(epi_pp_flow_kernel, dim3((unsigned)((n_px + 255) / 256)), dim3(256), 0, st, D1, filterD1, O, nd, rflow,
+                       flow, flow2, NP, n_px, vMax, n);
+}
+
+void launch_post_status(hipStream_t st, uint32_t* neg, int32_t* status) {
+    hipLaunchKernelGGL(post_status_kernel, dim3(1), dim3(64), 0, st, neg, status);
+}
+
 void launch_speckle_filter(hipStream_t st, const double* image, double* out, int32_t* labels, int32_t* parent,
-                           int32_t* size, int32_t* scan, int W, int H, double maxDiff, double maxSpeckleSize) {
-    const int n = W * H, nb = (n + 255) / 256;
-    hipLaunchKernelGGL(ccl_init_kernel, dim3(nb), dim3(256), 0, st, parent, size, n);
-    hipLaunchKernelGGL(ccl_merge_kernel, dim3((W + 63) / 64, (H + 3) / 4), dim3(256), 0, st, image, parent, W, H, maxDiff);
+                           int32_t* size, int32_t* scan, int W, int H, double maxDiff, double maxSpeckleSize, int nf, uint32_t* neg) {
+    const int n = W * H * nf, nb = (n + 255) / 256;
+    hipLaunchKernelGGL(ccl_init_kernel, dim3(nb), dim3(256), 0, st, parent, size, n, image, neg);
+    for (int f0 = 0; f0 < nf; f0 += MAX_GRID_Z)
+        hipLaunchKernelGGL(ccl_merge_kernel, dim3((W + 63) / 64, (H + 3) / 4, std::min(nf - f0, MAX_GRID_Z)), dim3(256), 0, st, image, parent,
+                           W, H, f0, maxDiff);
     hipLaunchKernelGGL(ccl_count_kernel, dim3(nb), dim3(256), 0, st, image, parent, size, n);
     hipLaunchKernelGGL(speckle_apply_kernel, dim3(nb), dim3(256), 0, st, image, out, parent, size, n, maxSpeckleSize);
-    if (labels) {
+    if (labels && nf == 1) {
         const int nc = (n + SCAN_CHUNK - 1) / SCAN_CHUNK;
         hipLaunchKernelGGL(roots_count_kernel, dim3(nc), dim3(256), 0, st, image, parent, scan, n);
         hipLaunchKernelGGL(roots_scan_kernel, dim3(1), dim3(64), 0, st, scan, nc);
@@ -331,19 +402,23 @@ void launch_speckle_filter(hipStream_t st, const double* image, double* out, int
     }
 }
 
-void launch_disp_from_first(hipStream_t st, const double* D1, double* D2, const PostGeom& g, int W, int H) {
-    const size_t n = (size_t)W * H;
+void launch_disp_from_first(hipStream_t st, const double* D1, double* D2, const PostGeom& g, int W, int H, int nf) {
+    const size_t n = (size_t)W * H * nf;
     hipLaunchKernelGGL(fill_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, D2, -1.0, n);   // :6
-    hipLaunchKernelGGL(disp_from_first_kernel, dim3((W + 63) / 64, (H + 3) / 4), dim3(256), 0, st, D1, D2, g, W, H);
+    for (int f0 = 0; f0 < nf; f0 += MAX_GRID_Z)
+        hipLaunchKernelGGL(disp_from_first_kernel, dim3((W + 63) / 64, (H + 3) / 4, std::min(nf - f0, MAX_GRID_Z)), dim3(256), 0, st,
+                           D1, D2, g, W, H, f0);
 }
 
-void launch_fb_check(hipStream_t st, const double* D1, const double* D2, double* out, const PostGeom& g, int W, int H) {
-    hipLaunchKernelGGL(fb_check_map_kernel, dim3((W + 63) / 64, (H + 3) / 4), dim3(256), 0, st, D1, D2, out, g, W, H);
+void launch_fb_check(hipStream_t st, const double* D1, const double* D2, double* out, const PostGeom& g, int W, int H, int nf) {
+    for (int f0 = 0; f0 < nf; f0 += MAX_GRID_Z)
+        hipLaunchKernelGGL(fb_check_map_kernel, dim3((W + 63) / 64, (H + 3) / 4, std::min(nf - f0, MAX_GRID_Z)), dim3(256), 0, st,
+                           D1, D2, out, g, W, H, f0);
 }
 
-void launch_scanline_in_fill(hipStream_t st, const double* in, double* out, int32_t* left, int W, int H) {
-    hipLaunchKernelGGL(infill_rows_kernel, dim3(H), dim3(256), 0, st, in, out, left, W);
-    hipLaunchKernelGGL(infill_cols_kernel, dim3((W + 255) / 256), dim3(256), 0, st, out, W, H);
+void launch_scanline_in_fill(hipStream_t st, const double* in, double* out, int32_t* left, int W, int H, int nf) {
+    hipLaunchKernelGGL(infill_rows_kernel, dim3(H * nf), dim3(256), 0, st, in, out, left, W);
+    hipLaunchKernelGGL(infill_cols_kernel, dim3((W * nf + 255) / 256), dim3(256), 0, st, out, W, H, nf);
 }
 
 void launch_vzind2disp(hipStream_t st, const double* w, const double* O, double* D, size_t n_px, double vMax, double n) {

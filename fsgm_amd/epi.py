@@ -261,6 +261,8 @@ def _bind_driver(lib):
     lib.fsgm_epipolar_maps_host.argtypes = [C.POINTER(EpiGeometry), i32, i32, vp, vp, vp, vp, i32]
     lib.fsgm_epipolar_sgm_of_host.argtypes = [vp, vp, i32, i32, i32, C.POINTER(EpiGeometry), i32, C.c_double,
                                               C.POINTER(_lib.EpiParams), vp, vp]
+    lib.fsgm_epipolar_flow_pp_host.argtypes = [i32, vp, vp, i32, i32, i32, C.POINTER(EpiGeometry), i32, C.c_double,
+                                               C.POINTER(_lib.EpiParams), vp, vp, vp, vp]
     lib._epi_driver_bound = True
 
 
@@ -317,3 +319,36 @@ def epipolar_sgm_of(I0, I1, F, H, epipole, direction, dMax=64, vMax=0.3, *, path
     check(lib.fsgm_epipolar_sgm_of_host(ptr(I0), ptr(I1), Wd, Hd, 1 if I0.ndim == 2 else 3, C.byref(g), int(dMax), float(vMax),
                                         C.byref(prm), ptr(flow), ptr(minC)))
     return flow, minC
+
+
+def epipolar_flow_pp(I0, I1, F, H, epipole, direction, dMax=64, vMax=0.3, *, paths=4, device=0):
+    """(flow, flow2, D1, minC) of test.m's frame body (:32-54) with the sparse geometry given: calc_cost_sgm in vz-index mode
+    (P1 = 6, P2 = 64), D1 = bestD/256, flow (:38-42), the post-processing chain with n = dMax + 1 and flow2 (:50-54).
+    One frame: I0/I1 (height, width) or (3, height, width) uint8 with F, H (3x3), epipole (x, y), direction; a batch: images
+    with a leading N and lists of N geometries (F then a sequence of 3x3 matrices).  flow / flow2 (.., 3, height, width)
+    float64 (third plane 1 where D1 / filterD1 is valid), D1 (.., height, width) float64, minC (.., height, width) uint32.
+    D1 is the MEX's vz index (calc_cost_sgm's WTA); test.m's own comes from calc_cost.m + sgm.m."""
+    lib = _lib.load()
+    _bind_driver(lib)
+    batched = np.asarray(F, dtype=np.float64).ndim == 3
+    Fs, Hs, es, ds = (F, H, epipole, direction) if batched else ([F], [H], [epipole], [direction])
+    if not (len(Fs) == len(Hs) == len(es) == len(ds)):
+        raise ValueError("F, H, epipole and direction must hold one entry per frame")
+    I0, I1 = np.ascontiguousarray(I0), np.ascontiguousarray(I1)
+    if I0.dtype != np.uint8 or I1.dtype != np.uint8 or I0.shape != I1.shape:
+        raise TypeError("I0/I1 must be uint8 images of one shape")
+    if not batched:
+        I0, I1 = I0[None], I1[None]
+    if I0.shape[0] != len(Fs):
+        raise ValueError(f"{I0.shape[0]} image pairs but {len(Fs)} geometries")
+    if not (I0.ndim == 3 or (I0.ndim == 4 and I0.shape[1] == 3)):
+        raise TypeError("images must be (height, width) or (3, height, width) per frame")
+    N, (Hd, Wd) = I0.shape[0], I0.shape[-2:]
+    g = (EpiGeometry * N)(*[_geometry(*x) for x in zip(Fs, Hs, es, ds)])
+    prm = _params(paths, 1, 0, device, 0)
+    flow, flow2 = np.empty((N, 3, Hd, Wd), np.float64), np.empty((N, 3, Hd, Wd), np.float64)
+    D1, minC = np.empty((N, Hd, Wd), np.float64), np.empty((N, Hd, Wd), np.uint32)
+    check(lib.fsgm_epipolar_flow_pp_host(N, ptr(I0), ptr(I1), Wd, Hd, 1 if I0.ndim == 3 else 3, g, int(dMax), float(vMax),
+                                         C.byref(prm), ptr(flow), ptr(flow2), ptr(D1), ptr(minC)))
+    outs = (flow, flow2, D1, minC)
+    return outs if batched else tuple(o[0] for o in outs)

@@ -22,6 +22,9 @@ def _bind(lib):
     lib.fsgm_vzind2disp_host.argtypes = [vp, vp, i32, i32, f64, f64, vp, i32]
     lib.fsgm_vmf_host.argtypes = [vp, i32, i32, i32, vp, i32]
     lib.fsgm_epi_postprocess_host.argtypes = [vp, i32, i32, vp, vp, vp, f64, f64, f64, vp, vp, vp, i32]
+    lib.fsgm_epi_postprocess_batch_host.argtypes = [i32, vp, i32, i32, vp, vp, vp, f64, f64, f64, vp, vp, vp, i32]
+    lib.fsgm_epi_postprocess_device.argtypes = [i32, vp, i32, i32, vp, vp, vp, f64, f64, f64, vp, vp, vp, i32, vp, vp]
+    lib.fsgm_vmf_device.argtypes = [i32, vp, i32, i32, i32, vp, i32, vp]
     lib.fsgm_post_plan_create.argtypes = [C.POINTER(vp), i32, i32, i32]
     lib.fsgm_post_plan_destroy.argtypes = [vp]
     lib.fsgm_post_plan_destroy.restype = None
@@ -132,6 +135,25 @@ def epi_postprocess(D1, Pd0, normDirect, O, vMax, n, dMax, *, device=0):
     f1, f2, disp = np.empty_like(D1), np.empty_like(D1), np.empty_like(D1)
     check(lib.fsgm_epi_postprocess_host(ptr(D1), W, H, ptr(Pd0), ptr(normDirect), ptr(O), float(vMax), float(n), float(dMax),
                                         ptr(f1), ptr(f2), ptr(disp), int(device)))
+    return f1, f2, disp
+
+
+def epi_postprocess_batch(D1, Pd0, normDirect, O, vMax, n, dMax, *, device=0):
+    """test.m:45-50 on a batch of maps in one call: D1, O (N, height, width), Pd0 / normDirect (N, 2, height, width), all
+    float64.  Returns (filterD1, filterD2, filterdisparites), each (N, height, width); frame f equals epi_postprocess of
+    frame f alone."""
+    lib = _lib_bound()
+    D1 = np.ascontiguousarray(D1)
+    if D1.dtype != np.float64 or D1.ndim != 3:
+        raise TypeError("D1 must be a float64 (N, height, width) batch of maps")
+    N, H, W = D1.shape
+    Pd0, normDirect, O = (np.ascontiguousarray(a) for a in (Pd0, normDirect, O))
+    for a, name, shape in ((Pd0, "Pd0", (N, 2, H, W)), (normDirect, "normDirect", (N, 2, H, W)), (O, "O", (N, H, W))):
+        if a.dtype != np.float64 or a.shape != shape:
+            raise TypeError(f"{name} must be float64 of shape {shape}")
+    f1, f2, disp = np.empty_like(D1), np.empty_like(D1), np.empty_like(D1)
+    check(lib.fsgm_epi_postprocess_batch_host(N, ptr(D1), W, H, ptr(Pd0), ptr(normDirect), ptr(O), float(vMax), float(n),
+                                              float(dMax), ptr(f1), ptr(f2), ptr(disp), int(device)))
     return f1, f2, disp
 
 

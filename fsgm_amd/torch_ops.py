@@ -7,8 +7,9 @@ points of include/fsgm.h ("Device-pointer entry points") as torch custom ops and
 
 No host<->device copy and no host wait once a plan for the shape exists: the work is queued behind what the current stream
 already holds, and what is queued on that stream afterwards runs after it.  Ops registered: fsgm::calc_cost_sgm,
-fsgm::epipolar_sgm_of, fsgm::pyramidal_sgm, fsgm::pyramidal_sgm_ng (each also returns a 0-d int32 status tensor: 0, or
-FSGM_ERR_HIP when an aggregation hand-off gave up; check=True in the wrappers synchronises and raises on it).
+fsgm::epipolar_sgm_of, fsgm::pyramidal_sgm, fsgm::pyramidal_sgm_ng, fsgm::epipolar_flow_pp (each also returns a 0-d int32
+status tensor: 0, or FSGM_ERR_HIP when an aggregation hand-off gave up; check=True in the wrappers synchronises and raises
+on it), fsgm::epi_postprocess (status FSGM_ERR_INVALID when a D1 value is negative) and fsgm::vmf.
 
 One process must hold one HIP runtime.  torch brings its own libamdhip64; libfsgm_hip.so binds to it by soname when torch is
 imported first.  When the library was loaded first, torch afterwards maps a second runtime, and a stream or pointer of one
@@ -24,9 +25,10 @@ import numpy as np
 from . import _lib
 from ._lib import EpiIn, EpiOut, EpiParams, FsgmError
 from .epi import EpiGeometry, _params as _epi_params
+from .post import _bind as _bind_post
 from .pyramid import PyramidParams, NgPyramidParams, _bind as _bind_pyramid, _bind_ng
 
-FSGM_ERR_HIP = 2
+FSGM_ERR_INVALID, FSGM_ERR_HIP = 1, 2
 
 
 def hip_runtimes():
@@ -52,10 +54,13 @@ if len(_runtimes) != 1:
 _vp, _i32 = C.c_void_p, C.c_int32
 _bind_pyramid(_L)
 _bind_ng(_L)
+_bind_post(_L)
 _L.fsgm_calc_cost_sgm_device.argtypes = [_i32, C.POINTER(EpiIn), C.POINTER(EpiOut), C.POINTER(EpiParams), _vp, _vp]
 _L.fsgm_epi_plan_run_device.argtypes = [_vp, _i32, C.POINTER(EpiIn), C.POINTER(EpiOut), _vp, _vp]
 _L.fsgm_epipolar_sgm_of_device.argtypes = [_i32, _vp, _vp, _i32, _i32, _i32, C.POINTER(EpiGeometry), _i32, C.c_double,
                                            C.POINTER(EpiParams), _vp, _vp, _vp, _vp]
+_L.fsgm_epipolar_flow_pp_device.argtypes = [_i32, _vp, _vp, _i32, _i32, _i32, C.POINTER(EpiGeometry), _i32, C.c_double,
+                                             C.POINTER(EpiParams), _vp, _vp, _vp, _vp, _vp, _vp]
 _L.fsgm_pyramidal_sgm_device.argtypes = [_i32, _vp, _vp, _i32, _i32, _i32, C.POINTER(PyramidParams), _vp, _vp, _vp, _vp]
 _L.fsgm_pyramidal_sgm_ng_device.argtypes = [_i32, _vp, _vp, _i32, _i32, _i32, C.POINTER(NgPyramidParams), _vp, _vp, _vp, _vp]
 
@@ -91,6 +96,24 @@ def _u32(shape, dev):
 
 def _status(dev):
     return torch.empty((), dtype=torch.int32, device=dev)
+
+
+def _f64(shape, dev):
+    return torch.empty(shape, dtype=torch.float64, device=dev)
+
+
+def _geometries(geometry, N):
+    """N fsgm_epi_geometry structs from the flat list of the ops (GEOMETRY_NUMBERS per frame)."""
+    if len(geometry) != N * GEOMETRY_NUMBERS:
+        raise ValueError(f"geometry must hold {GEOMETRY_NUMBERS} numbers per frame ({N * GEOMETRY_NUMBERS}), got {len(geometry)}")
+    g = (EpiGeometry * N)()
+    for f in range(N):
+        v = geometry[f * GEOMETRY_NUMBERS:(f + 1) * GEOMETRY_NUMBERS]
+        g[f].F[:] = [float(x) for x in v[0:9]]
+        g[f].H[:] = [float(x) for x in v[9:18]]
+        g[f].epipole[:] = [float(v[18]), float(v[19])]
+        g[f].direction = int(v[20] != 0)
+    return g
 
 
 # ---------------------------------------------------------------------------------------------
@@ -132,17 +155,9 @@ def _epipolar_sgm_of_op(I0: torch.Tensor, I1: torch.Tensor, geometry: List[float
     N, H, W = I0.shape[0], I0.shape[-2], I0.shape[-1]
     ch = 1 if I0.dim() == 3 else 3
     dev = I0.device
-    if len(geometry) != N * GEOMETRY_NUMBERS:
-        raise ValueError(f"geometry must hold {GEOMETRY_NUMBERS} numbers per frame ({N * GEOMETRY_NUMBERS}), got {len(geometry)}")
+    g = _geometries(geometry, N)
     I0, I1 = _ready(I0), _ready(I1)
     flow, minC, status = torch.empty((N, 3, H, W), dtype=torch.float64, device=dev), _u32((N, H, W), dev), _status(dev)
-    g = (EpiGeometry * N)()
-    for f in range(N):
-        v = geometry[f * GEOMETRY_NUMBERS:(f + 1) * GEOMETRY_NUMBERS]
-        g[f].F[:] = [float(x) for x in v[0:9]]
-        g[f].H[:] = [float(x) for x in v[9:18]]
-        g[f].epipole[:] = [float(v[18]), float(v[19])]
-        g[f].direction = int(v[20] != 0)
     prm = _epi_params(paths, 1, 1, dev.index, 0)
     _call(dev, _L.fsgm_epipolar_sgm_of_device, N, _p(I0), _p(I1), W, H, ch, g, int(dMax), float(vMax), C.byref(prm),
           _p(flow), _p(minC), _stream(dev), _p(status))
@@ -154,6 +169,63 @@ def _(I0, I1, geometry, dMax, vMax, paths):
     N, H, W = I0.shape[0], I0.shape[-2], I0.shape[-1]
     dev = I0.device
     return torch.empty((N, 3, H, W), dtype=torch.float64, device=dev), _u32((N, H, W), dev), _status(dev)
+
+
+@torch.library.custom_op("fsgm::epipolar_flow_pp", mutates_args=())
+def _epipolar_flow_pp_op(I0: torch.Tensor, I1: torch.Tensor, geometry: List[float], dMax: int, vMax: float,
+                         paths: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    N, H, W = I0.shape[0], I0.shape[-2], I0.shape[-1]
+    ch = 1 if I0.dim() == 3 else 3
+    dev = I0.device
+    g = _geometries(geometry, N)
+    I0, I1 = _ready(I0), _ready(I1)
+    flow, flow2, D1 = _f64((N, 3, H, W), dev), _f64((N, 3, H, W), dev), _f64((N, H, W), dev)
+    minC, status = _u32((N, H, W), dev), _status(dev)
+    prm = _epi_params(paths, 1, 0, dev.index, 0)
+    _call(dev, _L.fsgm_epipolar_flow_pp_device, N, _p(I0), _p(I1), W, H, ch, g, int(dMax), float(vMax), C.byref(prm),
+          _p(flow), _p(flow2), _p(D1), _p(minC), _stream(dev), _p(status))
+    return flow, flow2, D1, minC, status
+
+
+@_epipolar_flow_pp_op.register_fake
+def _(I0, I1, geometry, dMax, vMax, paths):
+    N, H, W = I0.shape[0], I0.shape[-2], I0.shape[-1]
+    dev = I0.device
+    return _f64((N, 3, H, W), dev), _f64((N, 3, H, W), dev), _f64((N, H, W), dev), _u32((N, H, W), dev), _status(dev)
+
+
+@torch.library.custom_op("fsgm::epi_postprocess", mutates_args=())
+def _epi_postprocess_op(D1: torch.Tensor, Pd0: torch.Tensor, nd: torch.Tensor, O: torch.Tensor, vMax: float, n: float,
+                        dMax: float) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    N, H, W = D1.shape
+    dev = D1.device
+    D1, Pd0, nd, O = (_ready(t) for t in (D1, Pd0, nd, O))
+    f1, f2, disp, status = _f64((N, H, W), dev), _f64((N, H, W), dev), _f64((N, H, W), dev), _status(dev)
+    _call(dev, _L.fsgm_epi_postprocess_device, N, _p(D1), W, H, _p(Pd0), _p(nd), _p(O), float(vMax), float(n), float(dMax),
+          _p(f1), _p(f2), _p(disp), dev.index, _stream(dev), _p(status))
+    return f1, f2, disp, status
+
+
+@_epi_postprocess_op.register_fake
+def _(D1, Pd0, nd, O, vMax, n, dMax):
+    N, H, W = D1.shape
+    dev = D1.device
+    return _f64((N, H, W), dev), _f64((N, H, W), dev), _f64((N, H, W), dev), _status(dev)
+
+
+@torch.library.custom_op("fsgm::vmf", mutates_args=())
+def _vmf_op(flow: torch.Tensor) -> torch.Tensor:
+    N, ch, H, W = flow.shape
+    dev = flow.device
+    flow = _ready(flow)
+    out = _f64((N, ch, H, W), dev)
+    _call(dev, _L.fsgm_vmf_device, N, _p(flow), W, H, ch, _p(out), dev.index, _stream(dev))
+    return out
+
+
+@_vmf_op.register_fake
+def _(flow):
+    return torch.empty_like(flow, memory_format=torch.contiguous_format)
 
 
 def _pyramid_run(fn, prm, I0, I1):
@@ -227,12 +299,12 @@ def _shape(name, t, shape):
         raise TypeError(f"{name} must have shape {tuple(shape)} (got {tuple(t.shape)})")
 
 
-def _finish(outs, status, batched, check, return_status):
+def _finish(outs, status, batched, check, return_status, why="an aggregation hand-off gave up"):
     if check:
         torch.cuda.current_stream(status.device).synchronize()
         s = int(status.item())
         if s != 0:
-            raise FsgmError(s, "the device reported a failed run (an aggregation hand-off gave up): results are invalid")
+            raise FsgmError(s, f"the device reported a failed run ({why}): results are invalid")
     outs = tuple(outs if batched else (o[0] for o in outs))
     return outs + (status,) if return_status else outs
 
@@ -263,10 +335,8 @@ def calc_cost_sgm(I1, I2, dMax, vMax, pixelPosD0, normlizeDirection, offsetFromP
     return _finish(outs, status, batched, check, return_status)
 
 
-def epipolar_sgm_of(I0, I1, F, H, epipole, direction, dMax=64, vMax=0.3, *, paths=4, check=False, return_status=False):
-    """[flow, minC] = epipolar_sgm_of(...) as fsgm_amd.epipolar_sgm_of, on torch tensors on the GPU.  One frame: I0, I1
-    (H, W) or RGB (3, H, W) uint8 with F, H (3x3), epipole (x, y), direction; a batch: images with a leading N and lists of N
-    geometries (F then a sequence of 3x3 matrices).  flow (.., 3, H, W) float64, minC (.., H, W) uint32."""
+def _epipolar_inputs(I0, I1, F, H, epipole, direction):
+    """(I0, I1 with a leading N, the ops' flat geometry list, batched) of the epipolar wrappers' arguments."""
     batched = np.asarray(F, dtype=np.float64).ndim == 3
     Fs, Hs, es, ds = (F, H, epipole, direction) if batched else ([F], [H], [epipole], [direction])
     if not (len(Fs) == len(Hs) == len(es) == len(ds)):
@@ -287,8 +357,56 @@ def epipolar_sgm_of(I0, I1, F, H, epipole, direction, dMax=64, vMax=0.3, *, path
         geometry += [float(e[0]), float(e[1]), float(bool(d))]
     if not batched:
         I0, I1 = I0.unsqueeze(0), I1.unsqueeze(0)
+    return I0, I1, geometry, batched
+
+
+def epipolar_sgm_of(I0, I1, F, H, epipole, direction, dMax=64, vMax=0.3, *, paths=4, check=False, return_status=False):
+    """[flow, minC] = epipolar_sgm_of(...) as fsgm_amd.epipolar_sgm_of, on torch tensors on the GPU.  One frame: I0, I1
+    (H, W) or RGB (3, H, W) uint8 with F, H (3x3), epipole (x, y), direction; a batch: images with a leading N and lists of N
+    geometries (F then a sequence of 3x3 matrices).  flow (.., 3, H, W) float64, minC (.., H, W) uint32."""
+    I0, I1, geometry, batched = _epipolar_inputs(I0, I1, F, H, epipole, direction)
     flow, minC, status = torch.ops.fsgm.epipolar_sgm_of(I0, I1, geometry, int(dMax), float(vMax), int(paths))
     return _finish((flow, minC), status, batched, check, return_status)
+
+
+def epipolar_flow_pp(I0, I1, F, H, epipole, direction, dMax=64, vMax=0.3, *, paths=4, check=False, return_status=False):
+    """(flow, flow2, D1, minC) of test.m's frame body as fsgm_amd.epipolar_flow_pp, on torch tensors on the GPU; images and
+    geometries as epipolar_sgm_of.  flow / flow2 (.., 3, H, W) float64, D1 (.., H, W) float64, minC (.., H, W) uint32."""
+    I0, I1, geometry, batched = _epipolar_inputs(I0, I1, F, H, epipole, direction)
+    flow, flow2, D1, minC, status = torch.ops.fsgm.epipolar_flow_pp(I0, I1, geometry, int(dMax), float(vMax), int(paths))
+    return _finish((flow, flow2, D1, minC), status, batched, check, return_status)
+
+
+def epi_postprocess(D1, Pd0, normDirect, O, vMax, n, dMax, *, check=False, return_status=False):
+    """test.m:45-50 as fsgm_amd.epi_postprocess(_batch), on torch tensors on the GPU.  One map: D1, O (H, W) and Pd0, normDirect
+    (2, H, W) float64; a batch: the same with a leading N.  Returns (filterD1, filterD2, filterdisparites) float64 of D1's
+    shape (the status tensor last with return_status=True: FSGM_ERR_INVALID when some D1 value is negative; check=True
+    synchronises and raises on it)."""
+    _tensors({"D1": (D1, torch.float64), "Pd0": (Pd0, torch.float64), "normDirect": (normDirect, torch.float64),
+              "O": (O, torch.float64)})
+    if D1.dim() not in (2, 3):
+        raise TypeError(f"D1 must be (H, W) or (N, H, W) (got {tuple(D1.shape)})")
+    batched = D1.dim() == 3
+    lead = tuple(D1.shape[:-2])
+    Hd, Wd = D1.shape[-2:]
+    _shape("Pd0", Pd0, lead + (2, Hd, Wd))
+    _shape("normDirect", normDirect, lead + (2, Hd, Wd))
+    _shape("O", O, lead + (Hd, Wd))
+    if not batched:
+        D1, Pd0, normDirect, O = (t.unsqueeze(0) for t in (D1, Pd0, normDirect, O))
+    f1, f2, disp, status = torch.ops.fsgm.epi_postprocess(D1, Pd0, normDirect, O, float(vMax), float(n), float(dMax))
+    return _finish((f1, f2, disp), status, batched, check, return_status, "a D1 value is negative")
+
+
+def vmf(flow):
+    """flowMed = vmf(flow) as fsgm_amd.vmf, on a torch tensor on the GPU: (channels, H, W) float64 with 1..3 channels, or a
+    batch (N, channels, H, W).  No status: the kernel has no failure to report."""
+    _tensors({"flow": (flow, torch.float64)})
+    if flow.dim() not in (3, 4) or not 1 <= flow.shape[-3] <= 3:
+        raise TypeError(f"flow must be (1..3, H, W) or (N, 1..3, H, W) (got {tuple(flow.shape)})")
+    if flow.dim() == 3:
+        return torch.ops.fsgm.vmf(flow.unsqueeze(0))[0]
+    return torch.ops.fsgm.vmf(flow)
 
 
 def _pyramid_images(I0, I1, batch):

@@ -429,6 +429,16 @@ fsgm_status fsgm_epi_postprocess_host(const double* D1, int32_t width, int32_t h
                                       double dMax, double* filterD1, double* filterD2, double* disp,
                                       int32_t device);
 
+/* test.m:45-50 on n_frames maps, one after another: D1, O, filterD1, filterD2, disp f64 [n][H][W], Pd0 / normDirect
+ * f64 [n][2][H][W].  Each frame's results are those of fsgm_epi_postprocess_host on that frame alone (one launch per
+ * stage for the whole batch; no stage looks across a frame boundary; the second speckle pass's size limit is
+ * rows*cols/10 of one frame).  filterD2 / disp may be NULL.  n_frames*width*height must stay below 2^31
+ * (FSGM_ERR_UNSUPPORTED, answered before any device is touched). */
+fsgm_status fsgm_epi_postprocess_batch_host(int32_t n_frames, const double* D1, int32_t width, int32_t height,
+                                            const double* Pd0, const double* normDirect, const double* O, double vMax,
+                                            double n, double dMax, double* filterD1, double* filterD2, double* disp,
+                                            int32_t device);
+
 typedef struct fsgm_post_plan fsgm_post_plan;
 fsgm_status fsgm_post_plan_create(fsgm_post_plan** plan, int32_t width, int32_t height, int32_t device);
 void        fsgm_post_plan_destroy(fsgm_post_plan* plan);
@@ -573,6 +583,36 @@ fsgm_status fsgm_epipolar_sgm_of_device(int32_t n_frames, const uint8_t* I0, con
                                         int32_t height, int32_t channels, const fsgm_epi_geometry* g,
                                         int32_t dMax, double vMax, const fsgm_epi_params* prm,
                                         double* flow, uint32_t* minC, void* stream, int32_t* status);
+/* fsgm_epi_postprocess_batch_host on device pointers, ordered on `stream` (a cached post-processing plan per width,
+ * height, n_frames and device holds the scratch; outputs must not overlap the inputs).  filterD2 / disp may be NULL.
+ * status (may be NULL): 0, or FSGM_ERR_INVALID when some D1 value is negative -- the host entry points refuse such maps
+ * on the host; here the chain still runs (every write stays in bounds) and its results are meaningless. */
+fsgm_status fsgm_epi_postprocess_device(int32_t n_frames, const double* D1, int32_t width, int32_t height,
+                                        const double* Pd0, const double* normDirect, const double* O, double vMax,
+                                        double n, double dMax, double* filterD1, double* filterD2, double* disp,
+                                        int32_t device, void* stream, int32_t* status);
+/* vmf.m on n_frames flows f64 [n][channels][H][W] (1..3 channels): flowMed of the same layout.  Needs no scratch: the
+ * kernel is queued on `stream` itself. */
+fsgm_status fsgm_vmf_device(int32_t n_frames, const double* flow, int32_t width, int32_t height, int32_t channels,
+                            double* flowMed, int32_t device, void* stream);
+/* test.m's frame body (:32-54) with the sparse geometry given, on n_frames image pairs (one epi plan of batch n_frames
+ * with vz_to_disp = 0, cached apart from epipolar_sgm_of's): gray conversion of RGB input, the epipolar maps,
+ * calc_cost_sgm in vz-index mode with P1 = 6, P2 = 64 (:36), D1 = bestD/256, flow (:38-42), the chain of :45-49 with
+ * n = dMax + 1 (:6), flow2 (:50-54).  Nothing leaves HBM between the matcher and flow2.
+ * D1 is the MEX's vz index (calc_cost_sgm's WTA, 1/256 steps); test.m's own D1 comes from calc_cost.m + sgm.m, which differ
+ * from the MEX as described for fsgm_sgm_host.
+ * I0 / I1 u8 [n][channels][H][W] (1 or 3 planes); g holds n geometries (HOST memory); flow, flow2 f64 [n][3][H][W]
+ * (third plane: 1 where D1 / filterD1 is valid); D1 (may be NULL) f64 [n][H][W]; minC (may be NULL) u32 [n][H][W].
+ * prm (may be NULL): paths, subpixel and device honoured, vz_to_disp ignored, fb_check must be 0.
+ * The device form follows the contract above; its status word means what it means for fsgm_epipolar_sgm_of_device. */
+fsgm_status fsgm_epipolar_flow_pp_host(int32_t n_frames, const uint8_t* I0, const uint8_t* I1, int32_t width,
+                                       int32_t height, int32_t channels, const fsgm_epi_geometry* g, int32_t dMax,
+                                       double vMax, const fsgm_epi_params* prm, double* flow, double* flow2, double* D1,
+                                       uint32_t* minC);
+fsgm_status fsgm_epipolar_flow_pp_device(int32_t n_frames, const uint8_t* I0, const uint8_t* I1, int32_t width,
+                                         int32_t height, int32_t channels, const fsgm_epi_geometry* g, int32_t dMax,
+                                         double vMax, const fsgm_epi_params* prm, double* flow, double* flow2, double* D1,
+                                         uint32_t* minC, void* stream, int32_t* status);
 /* the pyramids on n_frames image pairs (one plan of batch n_frames): the level-1 flow f64 [n][2][H][W] and minC (may be
  * NULL) u32 [n][H][W].  The level-1 images are read in place by the first reduce / gray / census kernels. */
 fsgm_status fsgm_pyramidal_sgm_device(int32_t n_frames, const uint8_t* I0, const uint8_t* I1, int32_t width,
