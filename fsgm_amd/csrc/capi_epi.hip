@@ -23,6 +23,30 @@ char* last_error_buf() {
 
 using namespace fsgm;
 
+// What aggregates a plan's volumes: one member per pipeline (choose_pipeline), named by kPipelineName
+enum Pipeline {
+    PIPE_GENERIC, PIPE_PACKED_NOWRAP, PIPE_PACKED_WRAP,  // per-direction line kernels + WTA kernel
+    PIPE_SWEEP,                                          // fused sweeps: horizontal pair, two frame lanes sweeping down then up
+    PIPE_SWEEP_PAR,                                      // down and up sweeps side by side, WTA kernel over the three Y volumes
+    PIPE_SWEEP_MID,                                      // as PIPE_SWEEP_PAR, the two sweeps meeting in the middle with the WTA inside
+    PIPE_PAIRS,                                          // 4 paths: horizontal pair, vertical pair with the WTA inside
+    PIPE_BAND,                                           // band sweeps: one workgroup per frame
+    PIPE_BAND_CHAIN,                                     // band sweeps: one workgroup per (band, frame)
+};
+static const char* const kPipelineName[] = {"generic", "packed16/nowrap", "packed16/wrap", "sweep16/nowrap", "sweep16par/nowrap",
+                                            "sweep16mid/nowrap", "pairs16/nowrap", "band16/nowrap", "band16chain/nowrap"};
+static bool pipe_lines(Pipeline k) { return k <= PIPE_PACKED_WRAP; }
+static bool pipe_sweep(Pipeline k) { return k == PIPE_SWEEP || k == PIPE_SWEEP_PAR || k == PIPE_SWEEP_MID; }
+
+// The sub-forms of the selected pipeline, settled with it by select_kernel: decisions only, never device pointers (the
+// device entry points swap some of the plan's for the length of one enqueue).
+struct PipelineForm {
+    int x_fine = 0;      // pairs, parallel sweeps: the along-x pair as pairx_* kernels (8 costs a lane), Y_h in natural d order
+    int x_lines = 0;     // parallel sweeps: the along-x pair as two line-kernel slots instead (dLx)
+    int tall = 0;        // parallel sweeps: 8-wave workgroups, half the launches of a sweep
+    int mid_tall = 0;    // sweeps meeting in the middle: their final halves as 8-wave workgroups too
+};
+
 struct fsgm_epi_plan {
     int W = 0, H = 0, D = 0, batch = 0;
     fsgm_epi_params prm{};
@@ -40,21 +64,18 @@ struct fsgm_epi_plan {
     uint32_t *dD2enc = nullptr, *dD2 = nullptr;          // forward-backward check (prm.fb_check)
     uint8_t* dConf = nullptr;
     // fused-sweep aggregation (epi_sweep.hip): horizontal path costs, u16 sums, block-boundary states
-    // (see enqueue(): horizontal kernel on stream_h; the frames split into two lanes that sweep
+    // (see agg_sweep(): horizontal kernel on stream_h; the frames split into two lanes that sweep
     // down then up on stream / stream_b)
     uint8_t *dLh = nullptr, *dX = nullptr, *dXup = nullptr, *dState = nullptr, *dCkpt = nullptr, *dCkptV = nullptr;
-    // parallel sweeps (sweep_par): Y_up of every frame and the up sweep's own block-boundary states
+    // parallel sweeps: Y_up of every frame and the up sweep's own block-boundary states
     uint8_t *dXupAll = nullptr, *dStateUp = nullptr;
-    uint8_t* dLx = nullptr;              // parallel sweeps of few frames: the two along-x path volumes [batch][2][N] (par_x_lines)
-    bool sweep_par = false;              // AGG_SWEEP only: down and up sweeps side by side, WTA over the three Y volumes
-    bool sweep_mid = false;              // sweep_par only: the two sweeps meet in the middle, each finishing the other's half with the WTA inside
+    uint8_t* dLx = nullptr;              // parallel sweeps of few frames: the two along-x path volumes [batch][2][N] (form.x_lines)
     // band sweeps (epi_band.hip): the first pass's 9th bits, the hand-off between the bands of a frame; dX, dRec, dS0 as above
     uint32_t* dBits = nullptr;
     uint4* dBandEdge = nullptr;
     size_t band_edge_maps = 0;           // hand-off maps per frame the buffer holds (1: bands in sequence; bands - 1: chained)
     uint32_t *dBandTicket = nullptr, *dBandErr = nullptr;   // chained band sweeps: work counter, give-up flag of the bounded waits
     uint32_t band_salt = 0;              // launch sequence number of the chained form (hand-off tags)
-    bool band_chain = false;             // AGG_BAND only: one workgroup per (band, frame) instead of one per frame
     bool band_edge_untagged = false;     // the hand-off maps hold words without this scheme's tags (sequential form, S tap): refill before a chained launch
     // epipolar driver (fsgm_epipolar_sgm_of_host): rotation flow, composed flow, RGB staging
     double *dRflow = nullptr, *dFlow = nullptr;
@@ -64,18 +85,15 @@ struct fsgm_epi_plan {
     fsgm_post_plan* post = nullptr;
     uint2* dRec = nullptr;
     uint16_t* dS0 = nullptr;
-    size_t state_stride = 0;
-    hipStream_t stream_h = nullptr, stream_b = nullptr, stream_c = nullptr;
+    hipStream_t stream_h = nullptr, stream_b = nullptr;
     hipEvent_t ev_fork = nullptr, ev_h = nullptr, ev_b = nullptr, ev_c = nullptr;
-    hipEvent_t ev_hl[3] = {nullptr, nullptr, nullptr};   // the horizontal pair of each frame lane done (sweep pipeline)
-    bool pair_split = true;              // FSGM_EPI_PAIRSPLIT=0: one pair launch for all lanes (A/B switch)
-    int lanes = 2;                       // frame lanes of the sweeps (FSGM_EPI_LANES, 1..3)
+    hipEvent_t ev_hl[2] = {nullptr, nullptr};   // the horizontal pair of each frame lane done (sweep pipeline)
     std::vector<int> cmax;               // per frame: upper bound of the cost values in dC
     bool vz_valid = false;
     int agg_mode = 0;                    // 0 auto, 1 per-direction line kernels, 2 fused sweeps (if eligible), 3 parallel sweeps, 4 / 5 band sweeps, 6 sweeps meeting in the middle
     int cus = 256;                       // compute units of the device (band sweeps: one workgroup per frame, two per CU)
-    int kernel_kind = AGG_GENERIC;
-    bool packed = false;
+    Pipeline pipe = PIPE_GENERIC;
+    PipelineForm form;
     DeviceJoin join;                     // device-pointer entry points: the events that order the plan's stream with the caller's
 };
 
@@ -138,12 +156,10 @@ static int pairs_min_batch(int W, int H, int D) { return switch_batch("FSGM_EPI_
 
 // What runs for a plan of this shape, batch and parameter set (cm: the largest cost in the volumes): a function of its
 // arguments and the FSGM_EPI_* environment only, so that fsgm_epi_auto_pipeline can answer without a plan.
-struct PipelineChoice { int kind; bool sweep_par, band_chain, sweep_mid; };
-static PipelineChoice choose_pipeline(int W, int H, int D, int batch, int paths, int P1, int P2, int cm, int agg_mode, int cus) {
-    PipelineChoice c = {AGG_GENERIC, false, false, false};
-    if (agg_packed_lpp(D) == 0) return c;
+static Pipeline choose_pipeline(int W, int H, int D, int batch, int paths, int P1, int P2, int cm, int agg_mode, int cus) {
+    if (agg_packed_lpp(D) == 0) return PIPE_GENERIC;
     const bool nowrap = P1 >= 0 && P2 >= 0 && cm + P2 + std::max(P1, P2) <= 255;
-    c.kind = nowrap ? AGG_PACKED_NOWRAP : AGG_PACKED_WRAP;
+    Pipeline c = nowrap ? PIPE_PACKED_NOWRAP : PIPE_PACKED_WRAP;
     // the fused sweeps cover the 8-path no-wrap case; everything else stays on the line kernels
     // Auto mode takes the fused pipelines only for batches: their latency (H rows in sequence for a sweep, down then
     // up; three passes along 1242-pixel rows for a pair) is 1.0 / 2.0 ms (4 / 8 paths) whatever the frame count,
@@ -155,85 +171,97 @@ static PipelineChoice choose_pipeline(int W, int H, int D, int batch, int paths,
     const bool fusable = nowrap && P1 <= P2;
     // (the Y volumes hold y + P1 per path since round 3 -- step_b, epi_step.h -- so three / two of them must fit a byte with the bias)
     if (fusable && 3 * (P1 + P2) <= 255 && paths == 8 && want) {
-        c.kind = AGG_SWEEP;
         // Between the line kernels and the full pipeline: the down and the up sweep side by side (H rows in sequence
         // instead of 2 H) with Y_up written out and a WTA kernel over C, Y_dn, Y_up, Y_h: 3 B per voxel more traffic,
         // half the latency.  Mode 3 forces it; auto takes it while the batch is too small to hide the longer chain.
-        c.sweep_par = agg_mode == 3 || agg_mode == 6 || (agg_mode == 0 && batch < par_max_batch(W, H, D));
+        const bool par = agg_mode == 3 || agg_mode == 6 || (agg_mode == 0 && batch < par_max_batch(W, H, D));
         // Mode 6, and auto for the larger of the batches that take the parallel sweeps: the two sweeps meet in the middle.  Each
         // writes its Y for its first half of the rows only and crosses the other's half as a final sweep (the other's Y, Y_h,
         // WTA in registers): the traffic of the full pipeline (9.6 B per voxel measured, no WTA kernel over four volumes) on the
         // parallel sweeps' chain of H rows.
         const int mid_min = mid_min_batch(W, H, D);
-        c.sweep_mid = agg_mode == 6 || (agg_mode == 0 && c.sweep_par && mid_min > 0 && batch >= mid_min);
+        const bool mid = agg_mode == 6 || (agg_mode == 0 && par && mid_min > 0 && batch >= mid_min);
+        c = mid ? PIPE_SWEEP_MID : par ? PIPE_SWEEP_PAR : PIPE_SWEEP;
     }
     // the shipped 4-path configuration: both axes as pair kernels, the vertical one final
-    if (fusable && 2 * (P1 + P2) <= 255 && paths == 4 && want) c.kind = AGG_PAIRS;
+    if (fusable && 2 * (P1 + P2) <= 255 && paths == 4 && want) c = PIPE_PAIRS;
     // very large batches (or mode 4 / 5): the band sweeps
     const int band = agg_mode == 0 ? band_choice(batch, cus, paths, W, H, D) : 0;
     if (fusable && band_ok(D, paths, P1, P2, cm) && (agg_mode == 4 || agg_mode == 5 || band != 0)) {
-        c.kind = AGG_BAND;
-        c.sweep_par = false;
-        c.sweep_mid = false;
         // mode 5 / auto between the sequential form's rounds: the bands of a frame as workgroups of their own (chained)
-        c.band_chain = agg_mode == 5 || band == 2;
+        c = agg_mode == 5 || band == 2 ? PIPE_BAND_CHAIN : PIPE_BAND;
     }
     return c;
 }
 
-static const char* pipeline_name(int kind, bool sweep_par, bool band_chain, bool sweep_mid = false) {
-    switch (kind) {
-        case AGG_PACKED_NOWRAP: return "packed16/nowrap";
-        case AGG_PACKED_WRAP: return "packed16/wrap";
-        case AGG_SWEEP: return sweep_mid ? "sweep16mid/nowrap" : sweep_par ? "sweep16par/nowrap" : "sweep16/nowrap";
-        case AGG_PAIRS: return "pairs16/nowrap";
-        case AGG_BAND: return band_chain ? "band16chain/nowrap" : "band16/nowrap";
-        default: return "generic";
-    }
-}
-
+// The pipeline and its sub-forms, settled together: enqueue() and the S tap read them and re-derive nothing.  The sub-form
+// switches (A/B) are read here, once per process.
 static void select_kernel(fsgm_epi_plan* p) {
-    p->packed = agg_packed_lpp(p->D) != 0;
     const int cm = *std::max_element(p->cmax.begin(), p->cmax.end());
-    const PipelineChoice c = choose_pipeline(p->W, p->H, p->D, p->batch, p->prm.paths, p->P1, p->P2, cm, p->agg_mode, p->cus);
-    p->kernel_kind = c.kind;
-    p->sweep_par = c.sweep_par;
-    p->sweep_mid = c.sweep_mid;
-    p->band_chain = c.band_chain;
+    const Pipeline k = choose_pipeline(p->W, p->H, p->D, p->batch, p->prm.paths, p->P1, p->P2, cm, p->agg_mode, p->cus);
+    const int B = p->batch;
+    const bool fine_ok = pair_x_fine_ok(p->D) != 0;
+    PipelineForm f;
+    // 4-path pipeline: the along-x pair as pairx_* kernels (8 costs a lane).  Small batches wait for that pair's serial chain,
+    // which the finer split shortens (2 / 9 frames at 1242x375x128: 0.96 -> 0.82 / 1.24 -> 1.12 ms); from 16 frames the
+    // pipeline is bound by its HBM traffic (7.5 B per voxel at ~5 TB/s) and the coarser kernels' fewer instructions win
+    // (40 frames: 3.47 against 3.68 ms).  FSGM_PAIR_XFINE=0 / 1: never / always (A/B switch).
+    static const int pair_xfine = env_int("FSGM_PAIR_XFINE", -1);
+    if (k == PIPE_PAIRS) f.x_fine = fine_ok && pair_xfine != 0 && (pair_xfine == 1 || B < 16);
+    // Parallel sweeps (8 paths, 5..17 frames): what the batch waits for are serial chains -- the along-x pair's 3 x W steps and
+    // the sweeps' H / 16 launches.  FSGM_EPI_PAR_FINE / FSGM_EPI_PAR_TALL = 0 / 1 force the two shortenings off / on (A/B).
+    static const int par_fine = env_int("FSGM_EPI_PAR_FINE", -1), par_tall = env_int("FSGM_EPI_PAR_TALL", -1);
+    if (k == PIPE_SWEEP_PAR || k == PIPE_SWEEP_MID) {
+        f.x_fine = fine_ok && par_fine != 0 && (par_fine == 1 || B <= 10);   // 8 frames 1.46 -> 1.32 ms with both; from 12 frames neither pays
+        f.tall = par_tall >= 0 ? par_tall != 0 : B <= 10;
+    }
+    // Parallel sweeps (not the form that meets in the middle, whose final sweeps read Y_h): the along-x pair as two line-kernel slots.
+    // FSGM_EPI_PAR_XLINES: 0 never, 1 whenever possible; default: up to 5 frames -- 4 frames 0.871 -> 0.832 ms, 6 frames 0.970 -> 1.050:
+    // with more frames the two volumes' bytes and the lines' instructions cost more than the pair's longer chain
+    // (profiles/r04_par_xlines.txt).
+    static const int xlines = env_int("FSGM_EPI_PAR_XLINES", -1);
+    if (k == PIPE_SWEEP_PAR) f.x_lines = xlines != 0 && (xlines == 1 || B <= 5);
+    // the final halves of the sweeps that meet in the middle as 8-wave workgroups too (FSGM_EPI_MID_TALL: A/B switch)
+    static const int mid_tall = env_int("FSGM_EPI_MID_TALL", -1);
+    if (k == PIPE_SWEEP_MID) f.mid_tall = mid_tall >= 0 ? mid_tall != 0 : f.tall;
+    p->pipe = k;
+    p->form = f;
 }
 
-// Lazily allocated buffer sets of the two fused pipelines.  Everything is created into locals and committed to
-// the plan only when the whole set exists, so a failure midway leaves the plan as it was (nothing leaked,
-// nothing half-initialised for the next call to trip over).
+// Lazily created buffer sets.  Everything is created aside and committed to the plan only when the whole set exists, so
+// a failure midway leaves the plan as it was (nothing leaked, nothing half-initialised for the next call to trip over).
 namespace {
 struct LazySet {
-    std::vector<void*> bufs;
-    std::vector<hipStream_t> streams;
-    std::vector<hipEvent_t> events;
+    struct Item { void** slot; void* v; int kind; };     // kind 0: buffer, 1: stream, 2: event
+    std::vector<Item> items;
     hipError_t err = hipSuccess;
-    template <class T> void alloc(T** p, size_t bytes) {
-        *p = nullptr;
-        if (err != hipSuccess) return;
+    // a buffer for `slot` when wanted and the slot is empty (or to replace it); returns it, null when none was created
+    template <class T> T* alloc(T*& slot, size_t bytes, bool want = true, bool replace = false) {
+        if (!want || (slot && !replace) || err != hipSuccess) return nullptr;
         void* v = nullptr;
         err = hipMalloc(&v, bytes ? bytes : 1);
-        if (err == hipSuccess) { bufs.push_back(v); *p = (T*)v; }
+        if (err != hipSuccess) return nullptr;
+        items.push_back({(void**)&slot, v, 0});
+        return (T*)v;
     }
-    void stream(hipStream_t* s) {
-        *s = nullptr;
-        if (err != hipSuccess) return;
-        err = hipStreamCreateWithFlags(s, hipStreamNonBlocking);
-        if (err == hipSuccess) streams.push_back(*s);
+    void stream(hipStream_t& slot, bool want = true) {
+        hipStream_t s = nullptr;
+        if (!want || slot || err != hipSuccess) return;
+        if ((err = hipStreamCreateWithFlags(&s, hipStreamNonBlocking)) == hipSuccess) items.push_back({(void**)&slot, s, 1});
     }
-    void event(hipEvent_t* e) {
-        *e = nullptr;
-        if (err != hipSuccess) return;
-        err = hipEventCreateWithFlags(e, hipEventDisableTiming);
-        if (err == hipSuccess) events.push_back(*e);
+    void event(hipEvent_t& slot, bool want = true) {
+        hipEvent_t e = nullptr;
+        if (!want || slot || err != hipSuccess) return;
+        if ((err = hipEventCreateWithFlags(&e, hipEventDisableTiming)) == hipSuccess) items.push_back({(void**)&slot, e, 2});
+    }
+    void commit() {
+        for (Item& i : items) *i.slot = i.v;
     }
     void rollback() {
-        for (void* b : bufs) (void)hipFree(b);
-        for (hipStream_t s : streams) (void)hipStreamDestroy(s);
-        for (hipEvent_t e : events) (void)hipEventDestroy(e);
+        for (Item& i : items)
+            if (i.kind == 0) (void)hipFree(i.v);
+            else if (i.kind == 1) (void)hipStreamDestroy((hipStream_t)i.v);
+            else (void)hipEventDestroy((hipEvent_t)i.v);
     }
 };
 fsgm_status lazy_fail(LazySet& ls, const char* what) {
@@ -241,6 +269,8 @@ fsgm_status lazy_fail(LazySet& ls, const char* what) {
     ls.rollback();
     return fail(e == hipErrorOutOfMemory ? FSGM_ERR_NOMEM : FSGM_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
 }
+// frame offset into a buffer the selected pipeline may not have
+template <class T> T* frame_at(T* base, size_t off) { return base ? base + off : nullptr; }
 }  // namespace
 
 extern "C" {
@@ -282,10 +312,10 @@ void fsgm_epi_plan_destroy(fsgm_epi_plan* p) {
     fsgm_post_plan_destroy(p->post);
     if (p->ev0) (void)hipEventDestroy(p->ev0);
     if (p->ev1) (void)hipEventDestroy(p->ev1);
-    for (hipEvent_t e : {p->ev_fork, p->ev_h, p->ev_b, p->ev_c, p->ev_hl[0], p->ev_hl[1], p->ev_hl[2]})
+    for (hipEvent_t e : {p->ev_fork, p->ev_h, p->ev_b, p->ev_c, p->ev_hl[0], p->ev_hl[1]})
         if (e) (void)hipEventDestroy(e);
     p->join.destroy();
-    for (hipStream_t st : {p->stream, p->stream_h, p->stream_b, p->stream_c})
+    for (hipStream_t st : {p->stream, p->stream_h, p->stream_b})
         if (st) (void)hipStreamDestroy(st);
     delete p;
 }
@@ -371,16 +401,15 @@ static fsgm_status ensure_cost_buffers(fsgm_epi_plan* p) {
     if (p->dCraw) return FSGM_OK;                                // the set's own marker: created last
     const size_t B = p->batch;
     LazySet ls;
-    uint8_t *i1, *i2, *craw; uint32_t *c1, *c2; double *pd0, *nd;
-    ls.alloc(&i1, B * p->NP);
-    ls.alloc(&i2, B * p->NP);
-    ls.alloc(&c1, B * p->NP * 4);
-    ls.alloc(&c2, B * p->NP * 4);
-    ls.alloc(&pd0, B * p->NP * 16);
-    ls.alloc(&nd, B * p->NP * 16);
-    ls.alloc(&craw, B * p->N);
+    ls.alloc(p->dI1, B * p->NP);
+    ls.alloc(p->dI2, B * p->NP);
+    ls.alloc(p->dCen1, B * p->NP * 4);
+    ls.alloc(p->dCen2, B * p->NP * 4);
+    ls.alloc(p->dPd0, B * p->NP * 16);
+    ls.alloc(p->dNd, B * p->NP * 16);
+    ls.alloc(p->dCraw, B * p->N);
     if (ls.err != hipSuccess) return lazy_fail(ls, "cost stage buffers");
-    p->dI1 = i1; p->dI2 = i2; p->dCen1 = c1; p->dCen2 = c2; p->dPd0 = pd0; p->dNd = nd; p->dCraw = craw;
+    ls.commit();
     return FSGM_OK;
 }
 
@@ -411,20 +440,48 @@ static fsgm_status ensure_vz(fsgm_epi_plan* p) {
     return FSGM_OK;
 }
 
+// the chained band sweeps' bounded hand-off waits raise a device flag instead of hanging: surface it after a sync
+static fsgm_status check_handoff(fsgm_epi_plan* p) {
+    if (p->dBandErr) {                                           // a chained launch happened at some point (the selection may have moved on since)
+        uint32_t e = 0;
+        FSGM_HIP(hipMemcpy(&e, p->dBandErr, sizeof(e), hipMemcpyDeviceToHost));
+        if (e != 0) {
+            (void)hipMemset(p->dBandErr, 0, sizeof(e));
+            return fail(FSGM_ERR_HIP, "band sweep: a hand-off between the bands of a frame timed out (results of this run are invalid)");
+        }
+    }
+    return FSGM_OK;
+}
+
+// An entry point's frame f: in range, the device current, and (drain 1) the plan's stream drained, (drain 2) with the chained
+// band sweeps' hand-off flag checked
+static fsgm_status frame_ready(fsgm_epi_plan* p, int f, int drain) {
+    FSGM_REQUIRE(f >= 0 && f < p->batch, "frame %d out of range (batch %d)", f, p->batch);
+    FSGM_HIP(hipSetDevice(p->prm.device));
+    if (drain) FSGM_HIP(hipStreamSynchronize(p->stream));
+    return drain == 2 ? check_handoff(p) : FSGM_OK;
+}
+
+// frame f's images and maps up on the plan's stream (the caller drains it before the host buffers may change)
+static fsgm_status upload_async(fsgm_epi_plan* p, int f, const uint8_t* I1, const uint8_t* I2, const double* pd0, const double* nd,
+                                const double* off) {
+    const size_t NP = p->NP, o = (size_t)f;
+    FSGM_HIP(hipMemcpyAsync(p->dI1 + o * NP, I1, NP, hipMemcpyHostToDevice, p->stream));
+    FSGM_HIP(hipMemcpyAsync(p->dI2 + o * NP, I2, NP, hipMemcpyHostToDevice, p->stream));
+    FSGM_HIP(hipMemcpyAsync(p->dPd0 + o * 2 * NP, pd0, NP * 16, hipMemcpyHostToDevice, p->stream));
+    FSGM_HIP(hipMemcpyAsync(p->dNd + o * 2 * NP, nd, NP * 16, hipMemcpyHostToDevice, p->stream));
+    FSGM_HIP(hipMemcpyAsync(p->dOff + o * NP, off, NP * 8, hipMemcpyHostToDevice, p->stream));
+    return FSGM_OK;
+}
+
 fsgm_status fsgm_epi_plan_upload(fsgm_epi_plan* p, int32_t f, const uint8_t* I1, const uint8_t* I2,
                                  const double* pd0, const double* nd, const double* off) {
     FSGM_REQUIRE(p, "null plan");
-    FSGM_REQUIRE(f >= 0 && f < p->batch, "frame %d out of range (batch %d)", f, p->batch);
+    { fsgm_status fs = frame_ready(p, f, 0); if (fs != FSGM_OK) return fs; }
     FSGM_REQUIRE(I1 && I2 && pd0 && nd && off, "fsgm_epi_plan_upload: null input");
-    FSGM_HIP(hipSetDevice(p->prm.device));
     { fsgm_status cs = ensure_cost_buffers(p); if (cs != FSGM_OK) return cs; }
-    const size_t NP = p->NP;
     StreamGuard guard(p->stream);
-    FSGM_HIP(hipMemcpyAsync(p->dI1 + f * NP, I1, NP, hipMemcpyHostToDevice, p->stream));
-    FSGM_HIP(hipMemcpyAsync(p->dI2 + f * NP, I2, NP, hipMemcpyHostToDevice, p->stream));
-    FSGM_HIP(hipMemcpyAsync(p->dPd0 + f * 2 * NP, pd0, NP * 16, hipMemcpyHostToDevice, p->stream));
-    FSGM_HIP(hipMemcpyAsync(p->dNd + f * 2 * NP, nd, NP * 16, hipMemcpyHostToDevice, p->stream));
-    FSGM_HIP(hipMemcpyAsync(p->dOff + f * NP, off, NP * 8, hipMemcpyHostToDevice, p->stream));
+    { fsgm_status us = upload_async(p, f, I1, I2, pd0, nd, off); if (us != FSGM_OK) return us; }
     FSGM_HIP(hipStreamSynchronize(p->stream));   // pageable host memory: keep the caller's buffers free to reuse
     guard.dismiss();
     return FSGM_OK;
@@ -432,8 +489,7 @@ fsgm_status fsgm_epi_plan_upload(fsgm_epi_plan* p, int32_t f, const uint8_t* I1,
 
 fsgm_status fsgm_epi_plan_upload_cost(fsgm_epi_plan* p, int32_t f, const uint8_t* C) {
     FSGM_REQUIRE(p && C, "fsgm_epi_plan_upload_cost: null argument");
-    FSGM_REQUIRE(f >= 0 && f < p->batch, "frame %d out of range (batch %d)", f, p->batch);
-    FSGM_HIP(hipSetDevice(p->prm.device));
+    { fsgm_status fs = frame_ready(p, f, 0); if (fs != FSGM_OK) return fs; }
     int cm = 0;
     for (size_t i = 0; i < p->N; i++) cm = C[i] > cm ? C[i] : cm;
     p->cmax[f] = cm;
@@ -466,144 +522,53 @@ fsgm_status fsgm_epi_plan_copy_cost(fsgm_epi_plan* p, int32_t dst, int32_t src, 
 
 fsgm_status fsgm_epi_plan_upload_offset(fsgm_epi_plan* p, int32_t f, const double* off) {
     FSGM_REQUIRE(p && off, "fsgm_epi_plan_upload_offset: null argument");
-    FSGM_REQUIRE(f >= 0 && f < p->batch, "frame %d out of range (batch %d)", f, p->batch);
-    FSGM_HIP(hipSetDevice(p->prm.device));
+    { fsgm_status fs = frame_ready(p, f, 0); if (fs != FSGM_OK) return fs; }
     FSGM_HIP(hipMemcpyAsync(p->dOff + f * p->NP, off, p->NP * 8, hipMemcpyHostToDevice, p->stream));
     FSGM_HIP(hipStreamSynchronize(p->stream));
     return FSGM_OK;
 }
 
-// 4-path pipeline: the along-x pair as pairx_* kernels (8 costs a lane).  Small batches wait for that pair's serial chain,
-// which the finer split shortens (2 / 9 frames at 1242x375x128: 0.96 -> 0.82 / 1.24 -> 1.12 ms); from 16 frames the
-// pipeline is bound by its HBM traffic (7.5 B per voxel at ~5 TB/s) and the coarser kernels' fewer instructions win
-// (40 frames: 3.47 against 3.68 ms).  FSGM_PAIR_XFINE=0 / 1: never / always (A/B switch).
-static int pairs_x_fine(const fsgm_epi_plan* p) {
-    static const int env = [] { const char* e = getenv("FSGM_PAIR_XFINE"); return (e && *e) ? atoi(e) : -1; }();
-    if (!pair_x_fine_ok(p->D) || env == 0) return 0;
-    return env == 1 || p->batch < 16 ? 1 : 0;
-}
-
-// Parallel sweeps (8 paths, 5..17 frames): what the batch waits for are serial chains -- the along-x pair's 3 x W steps and
-// the sweeps' H / 16 launches.  FSGM_EPI_PAR_FINE / FSGM_EPI_PAR_TALL = 0 / 1 force the two shortenings off / on (A/B).
-static int par_pair_fine(const fsgm_epi_plan* p) {
-    static const int env = env_int("FSGM_EPI_PAR_FINE", -1);
-    if (!pair_x_fine_ok(p->D) || env == 0) return 0;
-    return env == 1 || p->batch <= 10 ? 1 : 0;       // 8 frames 1.46 -> 1.32 ms with both; from 12 frames neither pays
-}
-static int par_tall(const fsgm_epi_plan* p) {
-    static const int env = env_int("FSGM_EPI_PAR_TALL", -1);
-    if (env >= 0) return env != 0;
-    return p->batch <= 10 ? 1 : 0;
-}
-
-// the final halves of the sweeps that meet in the middle as 8-wave workgroups too (FSGM_EPI_MID_TALL: A/B switch)
-static int mid_tall(const fsgm_epi_plan* p) {
-    static const int env = env_int("FSGM_EPI_MID_TALL", -1);
-    if (env >= 0) return env != 0;
-    return par_tall(p);
-}
-
-// Parallel sweeps (not the form that meets in the middle, whose final sweeps read Y_h): the along-x pair as two line-kernel slots.
-// FSGM_EPI_PAR_XLINES: 0 never, 1 whenever possible; default: up to 5 frames -- 4 frames 0.871 -> 0.832 ms, 6 frames 0.970 -> 1.050:
-// with more frames the two volumes' bytes and the lines' instructions cost more than the pair's longer chain
-// (profiles/r04_par_xlines.txt).
-static int par_x_lines(const fsgm_epi_plan* p) {
-    static const int env = env_int("FSGM_EPI_PAR_XLINES", -1);
-    if (!p->sweep_par || p->sweep_mid || env == 0) return 0;
-    return env == 1 || p->batch <= 5 ? 1 : 0;
-}
-
-// (the pipelines share some buffers -- records, S[0] words, Y volumes, the pair's stream -- and a plan may be switched from
-// one to another: each set creates only what is still missing)
-static fsgm_status ensure_pairs_buffers(fsgm_epi_plan* p) {
-    if (p->dCkptV && p->dLh && p->dCkpt && p->dRec && p->dS0 && p->stream_h) return FSGM_OK;
-    const size_t B = p->batch;
-    LazySet ls;
-    uint8_t *lh = p->dLh, *ck = p->dCkpt, *ckv = p->dCkptV; uint2* rec = p->dRec; uint16_t* s0 = p->dS0;
-    hipStream_t sh = p->stream_h; hipEvent_t ef = p->ev_fork, eh = p->ev_h;
-    if (!lh) ls.alloc(&lh, B * p->N);
-    if (!ck) ls.alloc(&ck, B * pair_ckpt_bytes(p->W, p->H, p->D, 0));
-    if (!ckv) ls.alloc(&ckv, B * pair_ckpt_bytes(p->W, p->H, p->D, 1));
-    if (!rec) ls.alloc(&rec, B * p->NP * sizeof(uint2));
-    if (!s0) ls.alloc(&s0, B * p->NP * sizeof(uint16_t));
-    if (!sh) ls.stream(&sh);
-    if (!ef) ls.event(&ef);
-    if (!eh) ls.event(&eh);
-    if (ls.err != hipSuccess) return lazy_fail(ls, "pair pipeline buffers");
-    p->dLh = lh; p->dCkpt = ck; p->dCkptV = ckv; p->dRec = rec; p->dS0 = s0;
-    p->stream_h = sh; p->ev_fork = ef; p->ev_h = eh;
-    return FSGM_OK;
-}
-
-static fsgm_status ensure_sweep_buffers(fsgm_epi_plan* p) {
-    if (p->dState) return FSGM_OK;                               // the set's own marker: created last
-    const size_t B = p->batch;
-    const size_t state_stride = sweep_state_bytes(p->W, p->D);
-    LazySet ls;
-    uint8_t *lh = p->dLh, *ck = p->dCkpt, *state = nullptr, *x = p->dX; uint2* rec = p->dRec; uint16_t* s0 = p->dS0;
-    hipStream_t sh = p->stream_h, sb = p->stream_b, sc = p->stream_c;
-    hipEvent_t ef = p->ev_fork, eh = p->ev_h, eb = p->ev_b, ec = p->ev_c, ehl[3] = {p->ev_hl[0], p->ev_hl[1], p->ev_hl[2]};
-    if (!lh) ls.alloc(&lh, B * p->N);
-    if (!ck) ls.alloc(&ck, B * pair_ckpt_bytes(p->W, p->H, p->D, 0));
-    if (!rec) ls.alloc(&rec, B * p->NP * sizeof(uint2));
-    if (!s0) ls.alloc(&s0, B * p->NP * sizeof(uint16_t));
-    if (!x) ls.alloc(&x, B * p->N);
-    if (!sh) ls.stream(&sh);
-    if (!sb) ls.stream(&sb);
-    if (!sc) ls.stream(&sc);
-    if (!ef) ls.event(&ef);
-    if (!eh) ls.event(&eh);
-    if (!eb) ls.event(&eb);
-    if (!ec) ls.event(&ec);
-    for (int l = 0; l < 3; l++) if (!ehl[l]) ls.event(&ehl[l]);
-    ls.alloc(&state, 2 * B * state_stride);
-    if (ls.err != hipSuccess) return lazy_fail(ls, "sweep pipeline buffers");
-    p->state_stride = state_stride;
-    p->dLh = lh; p->dCkpt = ck; p->dState = state; p->dRec = rec; p->dS0 = s0; p->dX = x;
-    p->stream_h = sh; p->stream_b = sb; p->stream_c = sc;
-    p->ev_fork = ef; p->ev_h = eh; p->ev_b = eb; p->ev_c = ec;
-    for (int l = 0; l < 3; l++) p->ev_hl[l] = ehl[l];
-    { const char* e = getenv("FSGM_EPI_PAIRSPLIT"); p->pair_split = !(e && *e && atoi(e) == 0); }
-    { const char* e = getenv("FSGM_EPI_LANES"); const int v = (e && *e) ? atoi(e) : 2; p->lanes = v < 1 ? 1 : (v > 3 ? 3 : v); }
-    return FSGM_OK;
-}
-
-static fsgm_status ensure_band_buffers(fsgm_epi_plan* p) {
+// The buffers of the selected pipeline that are still missing, created together and committed only when all of them exist.
+// The pipelines share some -- records, S[0] words, Y volumes, the pair's stream, the boundary states -- and a plan may be
+// switched from one to another: only what is still missing is created.
+static fsgm_status ensure_agg_buffers(fsgm_epi_plan* p) {
+    const Pipeline k = p->pipe;
+    const bool lines = pipe_lines(k), pairs = k == PIPE_PAIRS, sweep = pipe_sweep(k), band = k == PIPE_BAND || k == PIPE_BAND_CHAIN;
+    const bool par = k == PIPE_SWEEP_PAR || k == PIPE_SWEEP_MID, chain = k == PIPE_BAND_CHAIN;
+    const size_t B = p->batch, N = p->N, NP = p->NP, state_bytes = sweep_state_bytes(p->W, p->D);
+    // band sweeps: one hand-off map per frame, one per band boundary in the chained form (the buffer only grows)
     const int R = band_rows(p->D);
     const size_t nbands = R ? (size_t)(p->H + R - 1) / R : 1;
-    const size_t maps = p->band_chain ? (nbands > 1 ? nbands - 1 : 1) : 1;
-    if (p->dBandEdge && p->band_edge_maps >= maps && p->dX && p->dRec && p->dS0 && (!p->band_chain || p->dBandTicket)) return FSGM_OK;
-    const size_t B = p->batch;
-    LazySet ls;
-    uint8_t* x = p->dX; uint2* rec = p->dRec; uint4* edge = p->dBandEdge; uint16_t* s0 = p->dS0; uint32_t *bits = p->dBits, *ticket = p->dBandTicket, *err = p->dBandErr;
-    const bool new_edge = !edge || p->band_edge_maps < maps;
+    const size_t maps = chain ? (nbands > 1 ? nbands - 1 : 1) : 1;
+    const bool new_edge = band && (!p->dBandEdge || p->band_edge_maps < maps);
     const size_t edge_bytes = B * maps * band_edge_uint4s(p->W, p->D, 8) * sizeof(uint4);
-    if (!x) ls.alloc(&x, B * p->N);
-    if (!rec) ls.alloc(&rec, B * p->NP * sizeof(uint2));
-    if (!s0) ls.alloc(&s0, B * p->NP * sizeof(uint16_t));
-    if (new_edge) ls.alloc(&edge, edge_bytes);
-    if (!bits && p->prm.paths == 8) ls.alloc(&bits, B * band_bits_u32s(p->W, p->H, p->D) * sizeof(uint32_t));
-    if (p->band_chain && !ticket) { ls.alloc(&ticket, sizeof(uint32_t)); ls.alloc(&err, sizeof(uint32_t)); }
-    // chained form: hand-off dwords carry a launch tag in their bytes' top bits; all ones = "older than any launch"
-    if (ls.err == hipSuccess && new_edge && p->band_chain) ls.err = hipMemsetAsync(edge, 0xFF, edge_bytes, p->stream);
-    if (ls.err == hipSuccess && p->band_chain && !p->dBandErr) ls.err = hipMemsetAsync(err, 0, sizeof(uint32_t), p->stream);
-    if (ls.err != hipSuccess) return lazy_fail(ls, "band pipeline buffers");
-    if (new_edge && p->dBandEdge) { (void)hipStreamSynchronize(p->stream); (void)hipFree(p->dBandEdge); }
-    if (new_edge) p->band_salt = 0;
-    p->dX = x; p->dRec = rec; p->dS0 = s0; p->dBandEdge = edge; p->band_edge_maps = new_edge ? maps : p->band_edge_maps; p->dBits = bits;
-    p->dBandTicket = ticket; p->dBandErr = err;
-    return FSGM_OK;
-}
-
-static fsgm_status ensure_par_buffers(fsgm_epi_plan* p) {
-    if (p->dXupAll && (p->dLx || !par_x_lines(p))) return FSGM_OK;
     LazySet ls;
-    uint8_t *xu = p->dXupAll, *su = p->dStateUp, *lx = p->dLx;
-    if (!xu) ls.alloc(&xu, (size_t)p->batch * p->N);
-    if (!su) ls.alloc(&su, 2 * (size_t)p->batch * sweep_state_bytes(p->W, p->D));
-    if (!lx && par_x_lines(p)) ls.alloc(&lx, 2 * (size_t)p->batch * p->N);
-    if (ls.err != hipSuccess) return lazy_fail(ls, "parallel sweep buffers");
-    p->dXupAll = xu; p->dStateUp = su; p->dLx = lx;
+    ls.alloc(p->dL, B * N * p->prm.paths, lines);
+    ls.alloc(p->dLh, B * N, pairs || sweep);
+    ls.alloc(p->dCkpt, B * pair_ckpt_bytes(p->W, p->H, p->D, 0), pairs || sweep);
+    ls.alloc(p->dCkptV, B * pair_ckpt_bytes(p->W, p->H, p->D, 1), pairs);
+    ls.alloc(p->dRec, B * NP * sizeof(uint2), !lines);
+    ls.alloc(p->dS0, B * NP * sizeof(uint16_t), !lines);
+    ls.alloc(p->dX, B * N, sweep || band);
+    ls.alloc(p->dState, 2 * B * state_bytes, sweep);
+    ls.alloc(p->dXupAll, B * N, par);
+    ls.alloc(p->dStateUp, 2 * B * state_bytes, par);
+    ls.alloc(p->dLx, 2 * B * N, p->form.x_lines != 0);
+    uint4* edge = ls.alloc(p->dBandEdge, edge_bytes, new_edge, true);
+    ls.alloc(p->dBits, B * band_bits_u32s(p->W, p->H, p->D) * sizeof(uint32_t), band && p->prm.paths == 8);
+    ls.alloc(p->dBandTicket, sizeof(uint32_t), chain);
+    uint32_t* err = ls.alloc(p->dBandErr, sizeof(uint32_t), chain);
+    ls.stream(p->stream_h, pairs || sweep);
+    ls.stream(p->stream_b, sweep);
+    for (hipEvent_t* e : {&p->ev_fork, &p->ev_h}) ls.event(*e, pairs || sweep);
+    for (hipEvent_t* e : {&p->ev_b, &p->ev_c, &p->ev_hl[0], &p->ev_hl[1]}) ls.event(*e, sweep);
+    // chained form: hand-off dwords carry a launch tag in their bytes' top bits; all ones = "older than any launch"
+    if (ls.err == hipSuccess && edge && chain) ls.err = hipMemsetAsync(edge, 0xFF, edge_bytes, p->stream);
+    if (ls.err == hipSuccess && err) ls.err = hipMemsetAsync(err, 0, sizeof(uint32_t), p->stream);
+    if (ls.err != hipSuccess) return lazy_fail(ls, "aggregation buffers");
+    if (edge && p->dBandEdge) { (void)hipStreamSynchronize(p->stream); (void)hipFree(p->dBandEdge); }
+    if (edge) { p->band_salt = 0; p->band_edge_maps = maps; }
+    ls.commit();
     return FSGM_OK;
 }
 
@@ -620,21 +585,13 @@ static fsgm_status prepare(fsgm_epi_plan* p, int stages) {
         for (int& c : p->cmax) { if (c != 24) changed = true; c = 24; }
         if (changed) select_kernel(p);
     }
-    if (stages & (FSGM_STAGE_AGGREGATE | FSGM_STAGE_WTA)) {
-        if (p->kernel_kind == AGG_SWEEP) {
-            fsgm_status st = ensure_sweep_buffers(p);
-            if (st == FSGM_OK && p->sweep_par) st = ensure_par_buffers(p);
-            return st;
-        }
-        if (p->kernel_kind == AGG_PAIRS) return ensure_pairs_buffers(p);
-        if (p->kernel_kind == AGG_BAND) return ensure_band_buffers(p);
-    }
+    if (stages & (FSGM_STAGE_AGGREGATE | FSGM_STAGE_WTA)) return ensure_agg_buffers(p);
     return FSGM_OK;
 }
 
 // Where the sweeps that meet in the middle meet: the row count of the down sweep's first half, a whole number of its launches
 // (the up sweep's first half, H - hm rows, ends with a short launch).
-static int sweep_mid_row(int H, int D) {
+static int meet_row(int H, int D) {
     const int t = 2 * sweep_rows_per_launch(D);                  // rows per launch of the 8-wave form
     const int hm = ((H + 1) / 2 + t - 1) / t * t;
     return std::min(hm, H);
@@ -651,201 +608,270 @@ static void enqueue_cost(fsgm_epi_plan* p, int f0, int nf) {
     launch_epi_cost(p->stream, a, p->dC + o * p->N, nf);
 }
 
-static fsgm_status enqueue(fsgm_epi_plan* p, int stages) {
-    {
-        fsgm_status st = prepare(p, stages);
-        if (st != FSGM_OK) return st;
+// ---- launch arguments from frame f0 on.  They read the plan's buffer pointers when called, at enqueue time: the device
+// entry points swap some of them for the caller's for the length of one enqueue. ----
+
+// an opposite pair of paths along x (axis 0) or y (axis 1), not the final pass
+static PairArgs pair_args(const fsgm_epi_plan* p, int f0, int axis = 0) {
+    const size_t o = (size_t)f0, ckb = pair_ckpt_bytes(p->W, p->H, p->D, axis);
+    PairArgs a{};
+    a.C = p->dC + o * p->N; a.c_frame_stride = p->N;
+    a.X = frame_at(p->dLh, o * p->N); a.x_frame_stride = p->N;
+    a.ckpt = frame_at(axis ? p->dCkptV : p->dCkpt, o * ckb); a.ckpt_frame_stride = ckb;
+    a.W = p->W; a.H = p->H; a.D = p->D; a.P1 = p->P1; a.P2 = p->P2;
+    return a;
+}
+
+// a sweep of the block-sweep pipelines: a final one adds Y_h and writes the WTA records, the others write their Y only
+static SweepArgs sweep_args(const fsgm_epi_plan* p, int f0, bool final = true) {
+    const size_t o = (size_t)f0;
+    SweepArgs a{};
+    a.C = p->dC + o * p->N; a.c_frame_stride = p->N;
+    a.X = p->dX + o * p->N; a.x_frame_stride = p->N;
+    a.Lh = p->dLh + o * p->N; a.lh_frame_stride = p->N; a.lh_natural = p->form.x_fine;
+    a.rec = p->dRec + o * p->NP; a.s0 = p->dS0 + o * p->NP;
+    a.state_frame_stride = sweep_state_bytes(p->W, p->D);
+    a.state_in = a.state_out = p->dState + 2 * o * a.state_frame_stride;
+    a.W = p->W; a.H = p->H; a.D = p->D; a.P1 = p->P1; a.P2 = p->P2; a.y0 = 0; a.rows = 0;
+    if (!final) { a.Lh = nullptr; a.lh_frame_stride = 0; a.lh_natural = 0; a.rec = nullptr; a.s0 = nullptr; }
+    return a;
+}
+
+// the line kernels over `slots` path slots a frame, into L
+static AggArgs agg_args(const fsgm_epi_plan* p, uint8_t* L, int slots) {
+    AggArgs a;
+    a.C = p->dC; a.L = L; a.c_frame_stride = p->N; a.l_frame_stride = slots * p->N; a.l_dir_stride = p->N;
+    a.W = p->W; a.H = p->H; a.D = p->D; a.P1 = p->P1; a.P2 = p->P2;
+    return a;
+}
+
+static BandArgs band_args(const fsgm_epi_plan* p, int f0) {
+    const size_t o = (size_t)f0;
+    BandArgs a{};
+    a.C = p->dC + o * p->N; a.c_frame_stride = p->N;
+    a.Y = p->dX + o * p->N; a.y_frame_stride = p->N;
+    a.yb_frame_stride = band_bits_u32s(p->W, p->H, p->D);
+    a.Yb = frame_at(p->dBits, o * a.yb_frame_stride);
+    a.edge_frame_stride = p->band_edge_maps * band_edge_uint4s(p->W, p->D, 8);
+    a.edge = p->dBandEdge + o * a.edge_frame_stride;
+    a.rec = p->dRec + o * p->NP; a.s0 = p->dS0 + o * p->NP; a.Sdbg = nullptr;
+    a.W = p->W; a.H = p->H; a.D = p->D; a.P1 = p->P1; a.P2 = p->P2;
+    a.chain = p->pipe == PIPE_BAND_CHAIN ? 1 : 0;
+    a.frames = p->batch; a.nbands = (p->H + band_rows(p->D) - 1) / band_rows(p->D);
+    a.group = p->batch;                                  // frames whose bands are dealt band-major: all (groups of 16-64 measured: no gain)
+    a.ticket = p->dBandTicket; a.err = p->dBandErr;
+    return a;
+}
+
+// vz_to_disp: the runs convert after the forward-backward check (prm.vz_to_disp && !prm.fb_check), the S tap in place
+static WtaArgs wta_args(const fsgm_epi_plan* p, int f0, int vz_to_disp) {
+    const size_t o = (size_t)f0 * p->NP;
+    WtaArgs a{};
+    a.off = p->dOff + o; a.bestD = p->dBestD + o; a.minC = p->dMinC + o; a.vMax = p->vMax;
+    a.W = p->W; a.H = p->H; a.D = p->D; a.ndirs = p->prm.paths;
+    a.subpixel = p->prm.subpixel; a.vz_to_disp = vz_to_disp;
+    return a;
+}
+
+// the parallel sweeps' S = 8 (C + bias) - (Y_dn + Y_up + Y_h), or with the along-x lines 6 (C + bias) - (Y_dn + Y_up) + L_fwd + L_bwd
+static SweepSumArgs sum_args(const fsgm_epi_plan* p, int f0) {
+    const size_t o = (size_t)f0 * p->N;
+    SweepSumArgs q{};
+    q.C = p->dC + o; q.Xdn = frame_at(p->dX, o); q.Xup = frame_at(p->dXupAll, o); q.v_frame_stride = p->N;
+    q.Lh = p->dLh + o; q.lh_frame_stride = p->N; q.lh_natural = p->form.x_fine;
+    q.nC = 8; q.bias = p->P2 + p->P1; q.Sdbg = nullptr;
+    if (p->form.x_lines) { q.Lh = nullptr; q.Lx = p->dLx + 2 * o; q.lx_frame_stride = 2 * p->N; q.nC = 6; }
+    return q;
+}
+
+// ---- the pipelines: each one's aggregation and its S debug tap (fsgm_epi_plan_download_sum: frame f's S into dS) ----
+
+// per-direction line kernels: the path volumes L, then a WTA kernel over them
+static fsgm_status agg_lines(fsgm_epi_plan* p) {
+    const int kind = p->pipe == PIPE_GENERIC ? AGG_GENERIC : p->pipe == PIPE_PACKED_WRAP ? AGG_PACKED_WRAP : AGG_PACKED_NOWRAP;
+    launch_aggregate(p->stream, agg_args(p, p->dL, p->prm.paths), p->prm.paths, p->batch, kind);
+    return FSGM_OK;
+}
+static void tap_lines(fsgm_epi_plan* p, int f) {
+    launch_sum_paths(p->stream, p->dL + (size_t)f * p->N * p->prm.paths, p->dS, p->N, p->N, p->prm.paths);
+}
+
+// 4 paths: the horizontal pair -> X_h on stream_h while the vertical pair's checkpoint pass runs
+// here; then the vertical sum pass adds X_h + 4*C and does the WTA (7.5 B per voxel, S never in HBM)
+static fsgm_status agg_pairs(fsgm_epi_plan* p) {
+    FSGM_HIP(hipEventRecord(p->ev_fork, p->stream));
+    FSGM_HIP(hipStreamWaitEvent(p->stream_h, p->ev_fork, 0));
+    const PairArgs h = pair_args(p, 0);
+    if (p->form.x_fine) launch_pair_x_fine(p->stream_h, h, p->batch);   // its chain is what this pipeline waits for
+    else                launch_pair(p->stream_h, h, p->batch, 0, false);
+    FSGM_HIP(hipEventRecord(p->ev_h, p->stream_h));
+    PairArgs v = pair_args(p, 0, 1);
+    v.X = nullptr; v.x_frame_stride = 0;
+    v.Xother = p->dLh; v.xo_frame_stride = p->N; v.xo_natural = p->form.x_fine;
+    v.rec = p->dRec; v.s0 = p->dS0; v.nC = 4;
+    launch_pair(p->stream, v, p->batch, 1, true, 1);
+    FSGM_HIP(hipStreamWaitEvent(p->stream, p->ev_h, 0));
+    launch_pair(p->stream, v, p->batch, 1, true, 2);
+    return FSGM_OK;
+}
+// materialise the vertical pair's X_v of that frame with a non-final sum pass into dXup (one frame of scratch: dX is a
+// whole-batch buffer of other pipelines), then wta_sweep_kernel rebuilds S = X_v + X_h + 4C
+static void tap_pairs(fsgm_epi_plan* p, int f) {
+    PairArgs v = pair_args(p, f, 1);
+    v.X = p->dXup;
+    launch_pair(p->stream, v, 1, 1, false);
+    SweepSumArgs q = sum_args(p, f);
+    q.Xdn = p->dXup; q.Xup = nullptr; q.nC = 4; q.Sdbg = p->dS;
+    launch_wta_sweep(p->stream, wta_args(p, f, p->prm.vz_to_disp), q, 1);
+}
+
+// One sweep launch (strips x frames workgroups) cannot fill 256 CUs, so the work is forked:
+// the horizontal pair runs on stream_h, and the frames split into two lanes (one for a single frame),
+// each sweeping down and then up (the final up sweep needs its lane's X_dn and the horizontal pair).
+static fsgm_status agg_sweep(fsgm_epi_plan* p) {
+    const int lanes = std::min(2, p->batch), first[3] = {0, (p->batch + 1) / 2, p->batch};   // lane l: frames [first[l], first[l + 1])
+    const hipStream_t lane_stream[2] = {p->stream, p->stream_b};
+    FSGM_HIP(hipEventRecord(p->ev_fork, p->stream));
+    FSGM_HIP(hipStreamWaitEvent(p->stream_h, p->ev_fork, 0));
+    if (lanes > 1) FSGM_HIP(hipStreamWaitEvent(p->stream_b, p->ev_fork, 0));
+    // the two horizontal paths as one sum Y_h, lane by lane: a lane's final sweep waits for its own frames only
+    for (int l = 0; l < lanes; l++) {
+        launch_pair(p->stream_h, pair_args(p, first[l]), first[l + 1] - first[l], 0, false);
+        FSGM_HIP(hipEventRecord(p->ev_hl[l], p->stream_h));
     }
+    for (int l = 0; l < lanes; l++) {
+        const SweepArgs w = sweep_args(p, first[l]);
+        const int nf = first[l + 1] - first[l];
+        launch_sweep(lane_stream[l], w, nf, 0);                  // pass-0 paths from above -> Y_dn
+        FSGM_HIP(hipStreamWaitEvent(lane_stream[l], p->ev_hl[l], 0));
+        launch_sweep(lane_stream[l], w, nf, 2);                  // pass-1 paths + everything else + WTA
+    }
+    if (lanes > 1) {
+        FSGM_HIP(hipEventRecord(p->ev_b, p->stream_b));
+        FSGM_HIP(hipStreamWaitEvent(p->stream, p->ev_b, 0));
+    }
+    return FSGM_OK;
+}
+
+// Parallel sweeps: three independent chains, the horizontal pair (stream_h), the down sweep (here), the up sweep (stream_b)
+static fsgm_status agg_par_sweeps(fsgm_epi_plan* p) {
+    FSGM_HIP(hipEventRecord(p->ev_fork, p->stream));
+    FSGM_HIP(hipStreamWaitEvent(p->stream_h, p->ev_fork, 0));
+    FSGM_HIP(hipStreamWaitEvent(p->stream_b, p->ev_fork, 0));
+    // small batches wait for the pair's serial chain (3 x W steps): 8 costs a lane shorten it (Y_h then in natural d order)
+    if (p->form.x_lines) {
+        // few frames: the two along-x paths as line kernels (hand-written step, chains of W steps instead of the pair's 3 W;
+        // L_fwd and L_bwd written out: 2 B per voxel more than Y_h, added up by the WTA kernel)
+        launch_aggregate(p->stream_h, agg_args(p, p->dLx, 2), 2, p->batch, AGG_PACKED_NOWRAP);
+    }
+    else if (p->form.x_fine) launch_pair_x_fine(p->stream_h, pair_args(p, 0), p->batch);
+    else                     launch_pair(p->stream_h, pair_args(p, 0), p->batch, 0, false);
+    FSGM_HIP(hipEventRecord(p->ev_h, p->stream_h));
+    const SweepArgs fin = sweep_args(p, 0);
+    SweepArgs dn = sweep_args(p, 0, false), up = dn;
+    up.X = p->dXupAll; up.state_in = up.state_out = p->dStateUp;
+    const int tall = p->form.tall;                                // 8-wave workgroups: half the launches of a sweep
+    if (p->pipe == PIPE_SWEEP_MID) {
+        // the sweeps meet in the middle: rows [0, hm) of the frame belong to the down sweep's first half, rows [hm, H) to the
+        // up sweep's (its rows [0, H - hm) of the mirrored frame); then each crosses the other's half as a final sweep
+        const int hm = meet_row(p->H, p->D);
+        int par_dn = 0, par_up = 0;
+        launch_sweep_rows(p->stream, dn, p->batch, 0, tall, 0, hm, &par_dn);                 // -> Y_dn of rows [0, hm)
+        FSGM_HIP(hipEventRecord(p->ev_c, p->stream));
+        launch_sweep_rows(p->stream_b, up, p->batch, 1, tall, 0, p->H - hm, &par_up);         // -> Y_up of rows [hm, H)
+        FSGM_HIP(hipEventRecord(p->ev_b, p->stream_b));
+        SweepArgs dnf = fin, upf = fin;                                                     // what a final sweep reads: the other's Y
+        dnf.X = p->dXupAll;
+        upf.X = p->dX; upf.state_in = upf.state_out = p->dStateUp;
+        FSGM_HIP(hipStreamWaitEvent(p->stream, p->ev_h, 0));
+        FSGM_HIP(hipStreamWaitEvent(p->stream, p->ev_b, 0));
+        launch_sweep_rows(p->stream, dnf, p->batch, 3, p->form.mid_tall, hm, p->H, &par_dn);       // rows [hm, H): + Y_up + Y_h, WTA
+        FSGM_HIP(hipStreamWaitEvent(p->stream_b, p->ev_h, 0));
+        FSGM_HIP(hipStreamWaitEvent(p->stream_b, p->ev_c, 0));
+        launch_sweep_rows(p->stream_b, upf, p->batch, 2, p->form.mid_tall, p->H - hm, p->H, &par_up);  // rows [0, hm): + Y_dn + Y_h, WTA
+        FSGM_HIP(hipEventRecord(p->ev_hl[0], p->stream_b));
+        FSGM_HIP(hipStreamWaitEvent(p->stream, p->ev_hl[0], 0));
+    } else {
+        launch_sweep(p->stream, dn, p->batch, 0, tall);               // pass-0 paths from above -> Y_dn
+        launch_sweep(p->stream_b, up, p->batch, 1, tall);             // pass-1 paths -> Y_up
+        FSGM_HIP(hipEventRecord(p->ev_b, p->stream_b));
+        FSGM_HIP(hipStreamWaitEvent(p->stream, p->ev_h, 0));
+        FSGM_HIP(hipStreamWaitEvent(p->stream, p->ev_b, 0));
+    }
+    return FSGM_OK;
+}
+// S never exists in HBM in sweep mode.  Debug tap: materialise X_up of that frame with a non-final up sweep into dXup
+// (frame f's boundary states are idle now: scratch), then let wta_sweep_kernel rebuild S = X_dn + X_up + 6C + L_left + L_right.
+static void tap_sweep(fsgm_epi_plan* p, int f) {
+    SweepArgs w = sweep_args(p, f, false);
+    w.X = p->dXup;
+    launch_sweep(p->stream, w, 1, 1);
+    if (p->pipe == PIPE_SWEEP_MID) {                             // the meeting sweeps leave Y_dn for the upper half of the rows only
+        w.X = p->dX + (size_t)f * p->N;
+        launch_sweep(p->stream, w, 1, 0);
+    }
+    SweepSumArgs q = sum_args(p, f);
+    q.Xup = p->dXup; q.Sdbg = p->dS;
+    launch_wta_sweep(p->stream, wta_args(p, f, p->prm.vz_to_disp), q, 1);
+}
+
+// all four paths of a raster pass in one sweep, one workgroup per frame: first pass -> Y (+ 9th bits), second pass + WTA
+static fsgm_status agg_band(fsgm_epi_plan* p) {
+    BandArgs b = band_args(p, 0);
+    if (b.chain && p->band_edge_untagged) {              // words of the sequential form / the S tap could pass for tag 0: all ones is never a tag
+        FSGM_HIP(hipMemsetAsync(p->dBandEdge, 0xFF, (size_t)p->batch * b.edge_frame_stride * sizeof(uint4), p->stream));
+        p->band_edge_untagged = false;
+    }
+    if (!b.chain) p->band_edge_untagged = true;
+    for (int mode = 0; mode <= 2; mode += 2) {
+        if (b.chain) {                                   // the work counter restarts on the stream ahead of every launch; a fresh hand-off tag
+            const uint32_t t = p->band_salt++ % 15u;     // 0..14: the all-ones pattern of the initial fill is never a valid tag
+            b.tag = ((t & 1u) << 7) | ((t & 2u) << 14) | ((t & 4u) << 21) | ((t & 8u) << 28);
+            FSGM_HIP(hipMemsetAsync(b.ticket, 0, sizeof(uint32_t), p->stream));
+        }
+        launch_band(p->stream, b, p->batch, p->prm.paths, mode);
+    }
+    return FSGM_OK;
+}
+// S never exists in HBM in band mode either.  Debug tap: the second pass of that frame again, in the sequential form (its
+// first pass's Y is still in place), with the kernel's natural-order dump of S switched on.
+static void tap_band(fsgm_epi_plan* p, int f) {
+    BandArgs b = band_args(p, f);
+    b.chain = 0; b.Sdbg = p->dS;                         // (frames, nbands, group, ticket, err: read by the chained form only)
+    launch_band(p->stream, b, 1, p->prm.paths, 2);
+    p->band_edge_untagged = true;
+}
+
+// (Replaying the fused-sweep stage -- ~100 launches on three streams -- as one HIP graph was measured on MI355X / ROCm 7.2, 32 frames,
+// same box, alternating runs: 9 % SLOWER, 5.23 vs 4.79 ms per step; the runtime does not overlap the three captured branches as well
+// as the three streams do.  Removed in round 3.)
+static fsgm_status enqueue(fsgm_epi_plan* p, int stages) {
+    fsgm_status st = prepare(p, stages);
+    if (st != FSGM_OK) return st;
     if (stages & FSGM_STAGE_COST) {
-        fsgm_status st = ensure_vz(p);
-        if (st != FSGM_OK) return st;
+        if ((st = ensure_vz(p)) != FSGM_OK) return st;
         enqueue_cost(p, 0, p->batch);
     }
-    if ((stages & FSGM_STAGE_AGGREGATE) && p->kernel_kind == AGG_SWEEP && p->sweep_par) {
-        // three independent chains: the horizontal pair (stream_h), the down sweep (here), the up sweep (stream_b)
-        FSGM_HIP(hipEventRecord(p->ev_fork, p->stream));
-        FSGM_HIP(hipStreamWaitEvent(p->stream_h, p->ev_fork, 0));
-        FSGM_HIP(hipStreamWaitEvent(p->stream_b, p->ev_fork, 0));
-        const size_t ckb = pair_ckpt_bytes(p->W, p->H, p->D, 0);
-        PairArgs h{};
-        h.C = p->dC; h.c_frame_stride = p->N; h.X = p->dLh; h.x_frame_stride = p->N;
-        h.ckpt = p->dCkpt; h.ckpt_frame_stride = ckb;
-        h.W = p->W; h.H = p->H; h.D = p->D; h.P1 = p->P1; h.P2 = p->P2;
-        // small batches wait for the pair's serial chain (3 x W steps): 8 costs a lane shorten it (Y_h then in natural d order)
-        if (par_x_lines(p)) {
-            // few frames: the two along-x paths as line kernels (hand-written step, chains of W steps instead of the pair's 3 W;
-            // L_fwd and L_bwd written out: 2 B per voxel more than Y_h, added up by the WTA kernel)
-            AggArgs ax;
-            ax.C = p->dC; ax.L = p->dLx; ax.c_frame_stride = p->N; ax.l_frame_stride = 2 * p->N; ax.l_dir_stride = p->N;
-            ax.W = p->W; ax.H = p->H; ax.D = p->D; ax.P1 = p->P1; ax.P2 = p->P2;
-            launch_aggregate(p->stream_h, ax, 2, p->batch, AGG_PACKED_NOWRAP);
+    if (stages & FSGM_STAGE_AGGREGATE) {
+        switch (p->pipe) {
+            case PIPE_SWEEP: st = agg_sweep(p); break;
+            case PIPE_SWEEP_PAR: case PIPE_SWEEP_MID: st = agg_par_sweeps(p); break;
+            case PIPE_PAIRS: st = agg_pairs(p); break;
+            case PIPE_BAND: case PIPE_BAND_CHAIN: st = agg_band(p); break;
+            default: st = agg_lines(p); break;
         }
-        else if (par_pair_fine(p)) launch_pair_x_fine(p->stream_h, h, p->batch);
-        else                  launch_pair(p->stream_h, h, p->batch, 0, false);
-        FSGM_HIP(hipEventRecord(p->ev_h, p->stream_h));
-        SweepArgs w{};
-        w.C = p->dC; w.c_frame_stride = p->N;
-        w.X = p->dX; w.x_frame_stride = p->N;
-        w.Lh = nullptr; w.lh_frame_stride = 0; w.rec = nullptr; w.s0 = nullptr;
-        w.state_in = w.state_out = p->dState; w.state_frame_stride = p->state_stride;
-        w.W = p->W; w.H = p->H; w.D = p->D; w.P1 = p->P1; w.P2 = p->P2; w.y0 = 0; w.rows = 0;
-        const int tall = par_tall(p);                                 // 8-wave workgroups: half the launches of a sweep
-        if (p->sweep_mid) {
-            // the sweeps meet in the middle: rows [0, hm) of the frame belong to the down sweep's first half, rows [hm, H) to the
-            // up sweep's (its rows [0, H - hm) of the mirrored frame); then each crosses the other's half as a final sweep
-            const int hm = sweep_mid_row(p->H, p->D);
-            int par_dn = 0, par_up = 0;
-            SweepArgs up = w;
-            up.state_in = up.state_out = p->dStateUp;
-            w.X = p->dX; up.X = p->dXupAll;
-            launch_sweep_rows(p->stream, w, p->batch, 0, tall, 0, hm, &par_dn);                  // -> Y_dn of rows [0, hm)
-            FSGM_HIP(hipEventRecord(p->ev_c, p->stream));
-            launch_sweep_rows(p->stream_b, up, p->batch, 1, tall, 0, p->H - hm, &par_up);          // -> Y_up of rows [hm, H)
-            FSGM_HIP(hipEventRecord(p->ev_b, p->stream_b));
-            w.Lh = up.Lh = p->dLh; w.lh_frame_stride = up.lh_frame_stride = p->N; w.lh_natural = up.lh_natural = par_pair_fine(p);
-            w.rec = up.rec = p->dRec; w.s0 = up.s0 = p->dS0;
-            w.X = p->dXupAll; up.X = p->dX;                                                      // what a final sweep reads: the other's Y
-            FSGM_HIP(hipStreamWaitEvent(p->stream, p->ev_h, 0));
-            FSGM_HIP(hipStreamWaitEvent(p->stream, p->ev_b, 0));
-            launch_sweep_rows(p->stream, w, p->batch, 3, mid_tall(p), hm, p->H, &par_dn);                  // rows [hm, H): + Y_up + Y_h, WTA
-            FSGM_HIP(hipStreamWaitEvent(p->stream_b, p->ev_h, 0));
-            FSGM_HIP(hipStreamWaitEvent(p->stream_b, p->ev_c, 0));
-            launch_sweep_rows(p->stream_b, up, p->batch, 2, mid_tall(p), p->H - hm, p->H, &par_up);          // rows [0, hm): + Y_dn + Y_h, WTA
-            FSGM_HIP(hipEventRecord(p->ev_hl[0], p->stream_b));
-            FSGM_HIP(hipStreamWaitEvent(p->stream, p->ev_hl[0], 0));
-        } else {
-            launch_sweep(p->stream, w, p->batch, 0, tall);                // pass-0 paths from above -> Y_dn
-            w.X = p->dXupAll; w.state_in = w.state_out = p->dStateUp;
-            launch_sweep(p->stream_b, w, p->batch, 1, tall);              // pass-1 paths -> Y_up
-            FSGM_HIP(hipEventRecord(p->ev_b, p->stream_b));
-            FSGM_HIP(hipStreamWaitEvent(p->stream, p->ev_h, 0));
-            FSGM_HIP(hipStreamWaitEvent(p->stream, p->ev_b, 0));
-        }
-    } else if ((stages & FSGM_STAGE_AGGREGATE) && p->kernel_kind == AGG_SWEEP) {
-        // One sweep launch (strips x frames workgroups) cannot fill 256 CUs, so the work is forked:
-        // the horizontal pair runs on stream_h, and the frames split into two lanes, each sweeping
-        // down and then up (the final up sweep needs its lane's X_dn and the horizontal pair).
-        const int NLN = std::min(p->lanes, p->batch);
-        hipStream_t lane_stream[3] = {p->stream, p->stream_b, p->stream_c};
-        hipEvent_t lane_done[3] = {nullptr, p->ev_b, p->ev_c};
-        FSGM_HIP(hipEventRecord(p->ev_fork, p->stream));
-        FSGM_HIP(hipStreamWaitEvent(p->stream_h, p->ev_fork, 0));
-        for (int l = 1; l < NLN; l++) FSGM_HIP(hipStreamWaitEvent(lane_stream[l], p->ev_fork, 0));
-        // the two horizontal paths as one sum Y_h, lane by lane: a lane's final sweep waits for its own frames only
-        for (int lane = 0, f0 = 0; lane < NLN; lane++) {
-            const int nf = p->pair_split ? p->batch / NLN + (lane < p->batch % NLN ? 1 : 0) : p->batch;
-            const size_t ckb = pair_ckpt_bytes(p->W, p->H, p->D, 0);
-            PairArgs h{};
-            h.C = p->dC + (size_t)f0 * p->N; h.c_frame_stride = p->N; h.X = p->dLh + (size_t)f0 * p->N; h.x_frame_stride = p->N;
-            h.ckpt = p->dCkpt + (size_t)f0 * ckb; h.ckpt_frame_stride = ckb;
-            h.W = p->W; h.H = p->H; h.D = p->D; h.P1 = p->P1; h.P2 = p->P2;
-            launch_pair(p->stream_h, h, nf, 0, false);
-            FSGM_HIP(hipEventRecord(p->ev_hl[lane], p->stream_h));
-            f0 += nf;
-            if (!p->pair_split) { for (int l = 1; l < NLN; l++) FSGM_HIP(hipEventRecord(p->ev_hl[l], p->stream_h)); break; }
-        }
-        for (int lane = 0, f0 = 0; lane < NLN; lane++) {
-            const int nf = p->batch / NLN + (lane < p->batch % NLN ? 1 : 0);
-            hipStream_t st = lane_stream[lane];
-            SweepArgs w{};
-            w.C = p->dC + (size_t)f0 * p->N; w.c_frame_stride = p->N;
-            w.X = p->dX + (size_t)f0 * p->N; w.x_frame_stride = p->N;
-            w.Lh = p->dLh + (size_t)f0 * p->N; w.lh_frame_stride = p->N;
-            w.rec = p->dRec + (size_t)f0 * p->NP; w.s0 = p->dS0 + (size_t)f0 * p->NP;
-            w.state_in = w.state_out = p->dState + (size_t)2 * f0 * p->state_stride;
-            w.state_frame_stride = p->state_stride;
-            w.W = p->W; w.H = p->H; w.D = p->D; w.P1 = p->P1; w.P2 = p->P2; w.y0 = 0; w.rows = 0;
-            launch_sweep(st, w, nf, 0);                              // pass-0 paths from above -> Y_dn
-            FSGM_HIP(hipStreamWaitEvent(st, p->ev_hl[lane], 0));
-            launch_sweep(st, w, nf, 2);                              // pass-1 paths + everything else + WTA
-            if (lane) {
-                FSGM_HIP(hipEventRecord(lane_done[lane], st));
-                FSGM_HIP(hipStreamWaitEvent(p->stream, lane_done[lane], 0));
-            }
-            f0 += nf;
-        }
-    } else if ((stages & FSGM_STAGE_AGGREGATE) && p->kernel_kind == AGG_BAND) {
-        // all four paths of a raster pass in one sweep, one workgroup per frame: first pass -> Y (+ 9th bits), second pass + WTA
-        BandArgs b{};
-        b.C = p->dC; b.c_frame_stride = p->N;
-        b.Y = p->dX; b.y_frame_stride = p->N;
-        b.Yb = p->dBits; b.yb_frame_stride = band_bits_u32s(p->W, p->H, p->D);
-        b.edge = p->dBandEdge; b.edge_frame_stride = p->band_edge_maps * band_edge_uint4s(p->W, p->D, 8);
-        b.rec = p->dRec; b.s0 = p->dS0; b.Sdbg = nullptr;
-        b.W = p->W; b.H = p->H; b.D = p->D; b.P1 = p->P1; b.P2 = p->P2;
-        b.chain = p->band_chain ? 1 : 0;
-        b.frames = p->batch; b.nbands = (p->H + band_rows(p->D) - 1) / band_rows(p->D);
-        b.group = p->batch;                                  // frames whose bands are dealt band-major: all (groups of 16-64 measured: no gain)
-        b.ticket = p->dBandTicket; b.err = p->dBandErr;
-        if (b.chain && p->band_edge_untagged) {              // words of the sequential form / the S tap could pass for tag 0: all ones is never a tag
-            FSGM_HIP(hipMemsetAsync(p->dBandEdge, 0xFF, (size_t)p->batch * b.edge_frame_stride * sizeof(uint4), p->stream));
-            p->band_edge_untagged = false;
-        }
-        if (!b.chain) p->band_edge_untagged = true;
-        for (int mode = 0; mode <= 2; mode += 2) {
-            if (b.chain) {                                   // the work counter restarts on the stream ahead of every launch; a fresh hand-off tag
-                const uint32_t t = p->band_salt++ % 15u;     // 0..14: the all-ones pattern of the initial fill is never a valid tag
-                b.tag = ((t & 1u) << 7) | ((t & 2u) << 14) | ((t & 4u) << 21) | ((t & 8u) << 28);
-                FSGM_HIP(hipMemsetAsync(b.ticket, 0, sizeof(uint32_t), p->stream));
-            }
-            launch_band(p->stream, b, p->batch, p->prm.paths, mode);
-        }
-    } else if ((stages & FSGM_STAGE_AGGREGATE) && p->kernel_kind == AGG_PAIRS) {
-        // 4 paths: the horizontal pair -> X_h on stream_h while the vertical pair's checkpoint pass runs
-        // here; then the vertical sum pass adds X_h + 4*C and does the WTA (7.5 B per voxel, S never in HBM)
-        FSGM_HIP(hipEventRecord(p->ev_fork, p->stream));
-        FSGM_HIP(hipStreamWaitEvent(p->stream_h, p->ev_fork, 0));
-        PairArgs h{};
-        h.C = p->dC; h.c_frame_stride = p->N; h.X = p->dLh; h.x_frame_stride = p->N;
-        h.ckpt = p->dCkpt; h.ckpt_frame_stride = pair_ckpt_bytes(p->W, p->H, p->D, 0);
-        h.W = p->W; h.H = p->H; h.D = p->D; h.P1 = p->P1; h.P2 = p->P2;
-        const int fine = pairs_x_fine(p);                       // the along-x pair with 8 costs a lane: its chain is what this pipeline waits for
-        if (fine) launch_pair_x_fine(p->stream_h, h, p->batch);
-        else      launch_pair(p->stream_h, h, p->batch, 0, false);
-        FSGM_HIP(hipEventRecord(p->ev_h, p->stream_h));
-        PairArgs v = h;
-        v.xo_natural = fine;
-        v.X = nullptr; v.x_frame_stride = 0;
-        v.ckpt = p->dCkptV; v.ckpt_frame_stride = pair_ckpt_bytes(p->W, p->H, p->D, 1);
-        v.Xother = p->dLh; v.xo_frame_stride = p->N; v.rec = p->dRec; v.s0 = p->dS0; v.nC = 4;
-        launch_pair(p->stream, v, p->batch, 1, true, 1);
-        FSGM_HIP(hipStreamWaitEvent(p->stream, p->ev_h, 0));
-        launch_pair(p->stream, v, p->batch, 1, true, 2);
-    } else if (stages & FSGM_STAGE_AGGREGATE) {
-        if (!p->dL) FSGM_HIP(hipMalloc((void**)&p->dL, (size_t)p->batch * p->N * p->prm.paths));
-        AggArgs a;
-        a.C = p->dC; a.L = p->dL;
-        a.c_frame_stride = p->N; a.l_frame_stride = p->N * p->prm.paths; a.l_dir_stride = p->N;
-        a.W = p->W; a.H = p->H; a.D = p->D; a.P1 = p->P1; a.P2 = p->P2;
-        launch_aggregate(p->stream, a, p->prm.paths, p->batch, p->kernel_kind);
+        if (st != FSGM_OK) return st;
     }
-    if ((stages & FSGM_STAGE_WTA) && p->kernel_kind == AGG_SWEEP && p->sweep_par && !p->sweep_mid) {
-        WtaArgs a;                                   // S = 8 (C + P2) - (Y_dn + Y_up + Y_h), argmin, parabola, vz -> disp
-        a.L = nullptr; a.l_frame_stride = 0; a.l_dir_stride = 0;
-        a.off = p->dOff; a.bestD = p->dBestD; a.minC = p->dMinC; a.vMax = p->vMax;
-        a.W = p->W; a.H = p->H; a.D = p->D; a.ndirs = p->prm.paths;
-        a.subpixel = p->prm.subpixel; a.vz_to_disp = p->prm.vz_to_disp && !p->prm.fb_check;
-        SweepSumArgs q;
-        q.C = p->dC; q.Xdn = p->dX; q.Xup = p->dXupAll; q.v_frame_stride = p->N;
-        q.Lh = p->dLh; q.lh_frame_stride = p->N; q.lh_natural = par_pair_fine(p);
-        q.nC = 8; q.bias = p->P2 + p->P1; q.Sdbg = nullptr;
-        q.Lx = nullptr; q.lx_frame_stride = 0;
-        if (par_x_lines(p)) { q.Lh = nullptr; q.Lx = p->dLx; q.lx_frame_stride = 2 * p->N; q.nC = 6; }   // S = 6 (C + bias) - (Y_dn + Y_up) + L_fwd + L_bwd
-        launch_wta_sweep(p->stream, a, q, p->batch);
-    } else if ((stages & FSGM_STAGE_WTA) && (p->kernel_kind == AGG_SWEEP || p->kernel_kind == AGG_PAIRS || p->kernel_kind == AGG_BAND)) {
-        WtaArgs a;                                   // the argmin happened inside the final sweep / pair pass; finish the records
-        a.L = nullptr; a.l_frame_stride = 0; a.l_dir_stride = 0;
-        a.off = p->dOff; a.bestD = p->dBestD; a.minC = p->dMinC; a.vMax = p->vMax;
-        a.W = p->W; a.H = p->H; a.D = p->D; a.ndirs = p->prm.paths;
-        a.subpixel = p->prm.subpixel; a.vz_to_disp = p->prm.vz_to_disp && !p->prm.fb_check;
-        launch_sweep_finish(p->stream, a, p->dRec, p->dS0, p->batch);
-    } else if (stages & FSGM_STAGE_WTA) {
-        WtaArgs a;
-        a.L = p->dL; a.l_frame_stride = p->N * p->prm.paths; a.l_dir_stride = p->N;
-        a.off = p->dOff; a.bestD = p->dBestD; a.minC = p->dMinC; a.vMax = p->vMax;
-        a.W = p->W; a.H = p->H; a.D = p->D; a.ndirs = p->prm.paths;
-        a.subpixel = p->prm.subpixel; a.vz_to_disp = p->prm.vz_to_disp && !p->prm.fb_check;
-        launch_wta(p->stream, a, p->batch, p->packed);
+    if (stages & FSGM_STAGE_WTA) {
+        WtaArgs a = wta_args(p, 0, p->prm.vz_to_disp && !p->prm.fb_check);
+        if (p->pipe == PIPE_SWEEP_PAR) {                 // S = 8 (C + P2) - (Y_dn + Y_up + Y_h), argmin, parabola, vz -> disp
+            launch_wta_sweep(p->stream, a, sum_args(p, 0), p->batch);
+        } else if (!pipe_lines(p->pipe)) {               // the argmin happened inside the final sweep / pair pass
+            launch_sweep_finish(p->stream, a, p->dRec, p->dS0, p->batch);
+        } else {                                         // a WTA kernel over the path volumes
+            a.L = p->dL; a.l_frame_stride = p->N * p->prm.paths; a.l_dir_stride = p->N;
+            launch_wta(p->stream, a, p->batch, agg_packed_lpp(p->D) != 0);
+        }
     }
     if ((stages & FSGM_STAGE_WTA) && p->prm.fb_check) {
         // the check sees bestD before the vz conversion (order of calc_cost_sgm.cpp:584-594)
@@ -860,16 +886,11 @@ static fsgm_status enqueue(fsgm_epi_plan* p, int stages) {
     return FSGM_OK;
 }
 
-// (Replaying the fused-sweep stage -- ~100 launches on three streams -- as one HIP graph was measured on MI355X / ROCm 7.2, 32 frames,
-// same box, alternating runs: 9 % SLOWER, 5.23 vs 4.79 ms per step; the runtime does not overlap the three captured branches as well
-// as the three streams do.  Removed in round 3.)
-static fsgm_status run_stages(fsgm_epi_plan* p, int stages) { return enqueue(p, stages); }
-
 fsgm_status fsgm_epi_plan_run(fsgm_epi_plan* p, int32_t stages) {
     FSGM_REQUIRE(p, "null plan");
     FSGM_REQUIRE((stages & ~FSGM_STAGE_ALL) == 0 && stages != 0, "bad stage mask %d", stages);
     FSGM_HIP(hipSetDevice(p->prm.device));
-    return run_stages(p, stages);
+    return enqueue(p, stages);
 }
 
 fsgm_status fsgm_epi_plan_set_agg_mode(fsgm_epi_plan* p, int32_t mode) {
@@ -880,32 +901,14 @@ fsgm_status fsgm_epi_plan_set_agg_mode(fsgm_epi_plan* p, int32_t mode) {
     return FSGM_OK;
 }
 
-// the chained band sweeps' bounded hand-off waits raise a device flag instead of hanging: surface it after a sync
-static fsgm_status check_handoff(fsgm_epi_plan* p) {
-    if (p->dBandErr) {                                           // a chained launch happened at some point (the selection may have moved on since)
-        uint32_t e = 0;
-        FSGM_HIP(hipMemcpy(&e, p->dBandErr, sizeof(e), hipMemcpyDeviceToHost));
-        if (e != 0) {
-            (void)hipMemset(p->dBandErr, 0, sizeof(e));
-            return fail(FSGM_ERR_HIP, "band sweep: a hand-off between the bands of a frame timed out (results of this run are invalid)");
-        }
-    }
-    return FSGM_OK;
-}
-
 fsgm_status fsgm_epi_plan_sync(fsgm_epi_plan* p) {
     FSGM_REQUIRE(p, "null plan");
-    FSGM_HIP(hipSetDevice(p->prm.device));
-    FSGM_HIP(hipStreamSynchronize(p->stream));
-    return check_handoff(p);
+    return frame_ready(p, 0, 2);                                 // (frame 0: every plan has it)
 }
 
 fsgm_status fsgm_epi_plan_download(fsgm_epi_plan* p, int32_t f, uint32_t* bestD, uint32_t* minC) {
     FSGM_REQUIRE(p, "null plan");
-    FSGM_REQUIRE(f >= 0 && f < p->batch, "frame %d out of range (batch %d)", f, p->batch);
-    FSGM_HIP(hipSetDevice(p->prm.device));
-    FSGM_HIP(hipStreamSynchronize(p->stream));
-    { fsgm_status hs = check_handoff(p); if (hs != FSGM_OK) return hs; }
+    { fsgm_status fs = frame_ready(p, f, 2); if (fs != FSGM_OK) return fs; }
     if (bestD) FSGM_HIP(hipMemcpy(bestD, p->dBestD + f * p->NP, p->NP * 4, hipMemcpyDeviceToHost));
     if (minC) FSGM_HIP(hipMemcpy(minC, p->dMinC + f * p->NP, p->NP * 4, hipMemcpyDeviceToHost));
     return FSGM_OK;
@@ -913,11 +916,8 @@ fsgm_status fsgm_epi_plan_download(fsgm_epi_plan* p, int32_t f, uint32_t* bestD,
 
 fsgm_status fsgm_epi_plan_download_fb(fsgm_epi_plan* p, int32_t f, uint8_t* conf, uint32_t* bestD2) {
     FSGM_REQUIRE(p, "null plan");
-    FSGM_REQUIRE(f >= 0 && f < p->batch, "frame %d out of range (batch %d)", f, p->batch);
+    { fsgm_status fs = frame_ready(p, f, 2); if (fs != FSGM_OK) return fs; }
     FSGM_REQUIRE(p->prm.fb_check, "the plan was created without fb_check");
-    FSGM_HIP(hipSetDevice(p->prm.device));
-    FSGM_HIP(hipStreamSynchronize(p->stream));
-    { fsgm_status hs = check_handoff(p); if (hs != FSGM_OK) return hs; }
     if (conf) FSGM_HIP(hipMemcpy(conf, p->dConf + f * p->NP, p->NP, hipMemcpyDeviceToHost));
     if (bestD2) FSGM_HIP(hipMemcpy(bestD2, p->dD2 + f * p->NP, p->NP * 4, hipMemcpyDeviceToHost));
     return FSGM_OK;
@@ -925,19 +925,15 @@ fsgm_status fsgm_epi_plan_download_fb(fsgm_epi_plan* p, int32_t f, uint8_t* conf
 
 fsgm_status fsgm_epi_plan_download_cost(fsgm_epi_plan* p, int32_t f, uint8_t* C) {
     FSGM_REQUIRE(p && C, "fsgm_epi_plan_download_cost: null argument");
-    FSGM_REQUIRE(f >= 0 && f < p->batch, "frame %d out of range (batch %d)", f, p->batch);
-    FSGM_HIP(hipSetDevice(p->prm.device));
-    FSGM_HIP(hipStreamSynchronize(p->stream));
+    { fsgm_status fs = frame_ready(p, f, 1); if (fs != FSGM_OK) return fs; }
     FSGM_HIP(hipMemcpy(C, p->dC + f * p->N, p->N, hipMemcpyDeviceToHost));
     return FSGM_OK;
 }
 
 fsgm_status fsgm_epi_plan_download_census(fsgm_epi_plan* p, int32_t f, uint32_t* cen1, uint32_t* cen2) {
     FSGM_REQUIRE(p, "null plan");
-    FSGM_REQUIRE(f >= 0 && f < p->batch, "frame %d out of range (batch %d)", f, p->batch);
-    FSGM_HIP(hipSetDevice(p->prm.device));
+    { fsgm_status fs = frame_ready(p, f, 1); if (fs != FSGM_OK) return fs; }
     FSGM_REQUIRE(p->dCen1, "fsgm_epi_plan_download_census: the cost stage has not run on this plan");
-    FSGM_HIP(hipStreamSynchronize(p->stream));
     if (cen1) FSGM_HIP(hipMemcpy(cen1, p->dCen1 + f * p->NP, p->NP * 4, hipMemcpyDeviceToHost));
     if (cen2) FSGM_HIP(hipMemcpy(cen2, p->dCen2 + f * p->NP, p->NP * 4, hipMemcpyDeviceToHost));
     return FSGM_OK;
@@ -945,102 +941,17 @@ fsgm_status fsgm_epi_plan_download_census(fsgm_epi_plan* p, int32_t f, uint32_t*
 
 fsgm_status fsgm_epi_plan_download_sum(fsgm_epi_plan* p, int32_t f, uint32_t* S) {
     FSGM_REQUIRE(p && S, "fsgm_epi_plan_download_sum: null argument");
-    FSGM_REQUIRE(f >= 0 && f < p->batch, "frame %d out of range (batch %d)", f, p->batch);
-    FSGM_HIP(hipSetDevice(p->prm.device));
-    FSGM_HIP(hipStreamSynchronize(p->stream));
-    { fsgm_status hs = check_handoff(p); if (hs != FSGM_OK) return hs; }
-    if (p->kernel_kind == AGG_SWEEP) {
-        // S never exists in HBM in sweep mode.  Debug tap: materialise X_up of that frame with a
-        // non-final up sweep, then let wta_sweep_kernel rebuild S = X_dn + X_up + 6C + L_left + L_right.
-        FSGM_HIP(hipStreamSynchronize(p->stream));
-        fsgm_status es = ensure_sweep_buffers(p);
-        if (es != FSGM_OK) return es;
-        if (!p->dS) FSGM_HIP(hipMalloc((void**)&p->dS, p->N * 4));
-        if (!p->dXup) FSGM_HIP(hipMalloc((void**)&p->dXup, p->N));
-        SweepArgs w{};
-        w.C = p->dC + (size_t)f * p->N; w.c_frame_stride = p->N;
-        w.X = p->dXup; w.x_frame_stride = p->N;
-        w.Lh = nullptr; w.lh_frame_stride = 0; w.rec = nullptr; w.s0 = nullptr;
-        w.state_in = w.state_out = p->dState + (size_t)2 * f * p->state_stride;   // idle now: scratch for one frame
-        w.state_frame_stride = p->state_stride;
-        w.W = p->W; w.H = p->H; w.D = p->D; w.P1 = p->P1; w.P2 = p->P2; w.y0 = 0; w.rows = 0;
-        launch_sweep(p->stream, w, 1, 1);
-        if (p->sweep_mid) {                                      // the meeting sweeps leave Y_dn for the upper half of the rows only
-            w.X = p->dX + (size_t)f * p->N;
-            launch_sweep(p->stream, w, 1, 0);
-        }
-        WtaArgs a;
-        a.L = nullptr; a.l_frame_stride = 0; a.l_dir_stride = 0;
-        a.off = p->dOff + f * p->NP; a.bestD = p->dBestD + f * p->NP; a.minC = p->dMinC + f * p->NP; a.vMax = p->vMax;
-        a.W = p->W; a.H = p->H; a.D = p->D; a.ndirs = p->prm.paths;
-        a.subpixel = p->prm.subpixel; a.vz_to_disp = p->prm.vz_to_disp;
-        SweepSumArgs q;
-        q.C = p->dC + (size_t)f * p->N; q.Xdn = p->dX + (size_t)f * p->N; q.Xup = p->dXup; q.v_frame_stride = p->N;
-        q.Lh = p->dLh + (size_t)f * p->N; q.lh_frame_stride = p->N; q.lh_natural = p->sweep_par ? par_pair_fine(p) : 0;
-        q.nC = 8; q.bias = p->P2 + p->P1; q.Sdbg = p->dS;
-        q.Lx = nullptr; q.lx_frame_stride = 0;
-        if (par_x_lines(p)) { q.Lh = nullptr; q.Lx = p->dLx + (size_t)f * 2 * p->N; q.lx_frame_stride = 2 * p->N; q.nC = 6; }
-        launch_wta_sweep(p->stream, a, q, 1);
-        FSGM_HIP(hipGetLastError());
-        FSGM_HIP(hipStreamSynchronize(p->stream));
-        FSGM_HIP(hipMemcpy(S, p->dS, p->N * 4, hipMemcpyDeviceToHost));
-        return FSGM_OK;
-    }
-    if (p->kernel_kind == AGG_PAIRS) {
-        // Debug tap of the 4-path pair pipeline: materialise the vertical pair's X_v of that frame with a
-        // non-final sum pass, then wta_sweep_kernel rebuilds S = X_v + X_h + 4C.
-        FSGM_HIP(hipStreamSynchronize(p->stream));
-        fsgm_status es = ensure_pairs_buffers(p);
-        if (es != FSGM_OK) return es;
-        if (!p->dS) FSGM_HIP(hipMalloc((void**)&p->dS, p->N * 4));
-        if (!p->dXup) FSGM_HIP(hipMalloc((void**)&p->dXup, p->N));          // one frame of scratch (dX is a whole-batch buffer of other pipelines)
-        PairArgs v{};
-        v.C = p->dC + (size_t)f * p->N; v.c_frame_stride = p->N; v.X = p->dXup; v.x_frame_stride = p->N;
-        v.ckpt = p->dCkptV; v.ckpt_frame_stride = pair_ckpt_bytes(p->W, p->H, p->D, 1);
-        v.W = p->W; v.H = p->H; v.D = p->D; v.P1 = p->P1; v.P2 = p->P2;
-        launch_pair(p->stream, v, 1, 1, false);
-        WtaArgs a;
-        a.L = nullptr; a.l_frame_stride = 0; a.l_dir_stride = 0;
-        a.off = p->dOff + f * p->NP; a.bestD = p->dBestD + f * p->NP; a.minC = p->dMinC + f * p->NP; a.vMax = p->vMax;
-        a.W = p->W; a.H = p->H; a.D = p->D; a.ndirs = p->prm.paths;
-        a.subpixel = p->prm.subpixel; a.vz_to_disp = p->prm.vz_to_disp;
-        SweepSumArgs q;
-        q.C = p->dC + (size_t)f * p->N; q.Xdn = p->dXup; q.Xup = nullptr; q.v_frame_stride = p->N;
-        q.Lh = p->dLh + (size_t)f * p->N; q.lh_frame_stride = p->N; q.lh_natural = pairs_x_fine(p);
-        q.nC = 4; q.bias = p->P2 + p->P1; q.Sdbg = p->dS;
-        q.Lx = nullptr; q.lx_frame_stride = 0;
-        launch_wta_sweep(p->stream, a, q, 1);
-        FSGM_HIP(hipGetLastError());
-        FSGM_HIP(hipStreamSynchronize(p->stream));
-        FSGM_HIP(hipMemcpy(S, p->dS, p->N * 4, hipMemcpyDeviceToHost));
-        return FSGM_OK;
-    }
-    if (p->kernel_kind == AGG_BAND) {
-        // S never exists in HBM in band mode either.  Debug tap: the second pass of that frame again (its first pass's Y is
-        // still in place), with the kernel's natural-order dump of S switched on.
-        FSGM_HIP(hipStreamSynchronize(p->stream));
-        fsgm_status es = ensure_band_buffers(p);
-        if (es != FSGM_OK) return es;
-        if (!p->dS) FSGM_HIP(hipMalloc((void**)&p->dS, p->N * 4));
-        BandArgs b{};
-        const size_t fs = (size_t)f;
-        b.C = p->dC + fs * p->N; b.c_frame_stride = p->N;
-        b.Y = p->dX + fs * p->N; b.y_frame_stride = p->N;
-        b.yb_frame_stride = band_bits_u32s(p->W, p->H, p->D);
-        b.Yb = p->dBits ? p->dBits + fs * b.yb_frame_stride : nullptr;
-        b.edge_frame_stride = p->band_edge_maps * band_edge_uint4s(p->W, p->D, 8);
-        b.edge = p->dBandEdge + fs * b.edge_frame_stride;
-        b.rec = p->dRec + fs * p->NP; b.s0 = p->dS0 + fs * p->NP; b.Sdbg = p->dS;
-        b.W = p->W; b.H = p->H; b.D = p->D; b.P1 = p->P1; b.P2 = p->P2;
-        launch_band(p->stream, b, 1, p->prm.paths, 2);
-        p->band_edge_untagged = true;
-        FSGM_HIP(hipGetLastError());
-        FSGM_HIP(hipStreamSynchronize(p->stream));
-        FSGM_HIP(hipMemcpy(S, p->dS, p->N * 4, hipMemcpyDeviceToHost));
-        return FSGM_OK;
-    }
+    { fsgm_status fs = frame_ready(p, f, 2); if (fs != FSGM_OK) return fs; }
+    // the line kernels sum the frame's path volumes; the fused pipelines never hold S in HBM and rebuild it (tap_*)
+    { fsgm_status es = ensure_agg_buffers(p); if (es != FSGM_OK) return es; }
     if (!p->dS) FSGM_HIP(hipMalloc((void**)&p->dS, p->N * 4));
-    launch_sum_paths(p->stream, p->dL + (size_t)f * p->N * p->prm.paths, p->dS, p->N, p->N, p->prm.paths);
+    if (!p->dXup && (pipe_sweep(p->pipe) || p->pipe == PIPE_PAIRS)) FSGM_HIP(hipMalloc((void**)&p->dXup, p->N));
+    switch (p->pipe) {
+        case PIPE_SWEEP: case PIPE_SWEEP_PAR: case PIPE_SWEEP_MID: tap_sweep(p, f); break;
+        case PIPE_PAIRS: tap_pairs(p, f); break;
+        case PIPE_BAND: case PIPE_BAND_CHAIN: tap_band(p, f); break;
+        default: tap_lines(p, f); break;
+    }
     FSGM_HIP(hipGetLastError());
     FSGM_HIP(hipStreamSynchronize(p->stream));
     FSGM_HIP(hipMemcpy(S, p->dS, p->N * 4, hipMemcpyDeviceToHost));
@@ -1052,13 +963,9 @@ fsgm_status fsgm_epi_plan_time(fsgm_epi_plan* p, int32_t stages, int32_t warmup,
     FSGM_REQUIRE(iters >= 1 && warmup >= 0, "fsgm_epi_plan_time: iters must be >= 1");
     FSGM_REQUIRE((stages & ~FSGM_STAGE_ALL) == 0 && stages != 0, "bad stage mask %d", stages);
     FSGM_HIP(hipSetDevice(p->prm.device));
-    for (int i = 0; i < warmup; i++) {
-        fsgm_status st = run_stages(p, stages);
-        if (st != FSGM_OK) return st;
-    }
-    FSGM_HIP(hipEventRecord(p->ev0, p->stream));
-    for (int i = 0; i < iters; i++) {
-        fsgm_status st = run_stages(p, stages);
+    for (int i = 0; i < warmup + iters; i++) {
+        if (i == warmup) FSGM_HIP(hipEventRecord(p->ev0, p->stream));
+        fsgm_status st = enqueue(p, stages);
         if (st != FSGM_OK) return st;
     }
     FSGM_HIP(hipEventRecord(p->ev1, p->stream));
@@ -1073,14 +980,13 @@ void* fsgm_epi_plan_stream(fsgm_epi_plan* p) { return p ? (void*)p->stream : nul
 
 const char* fsgm_epi_plan_kernel_name(fsgm_epi_plan* p) {
     if (!p) return "";
-    return pipeline_name(p->kernel_kind, p->sweep_par, p->band_chain, p->sweep_mid);
+    return kPipelineName[p->pipe];
 }
 
 const char* fsgm_epi_auto_pipeline(int32_t width, int32_t height, int32_t dMax, int32_t batch, int32_t paths, int32_t P1, int32_t P2,
                                    int32_t cmax, int32_t cus) {
     if (width <= 0 || height <= 0 || dMax <= 0 || batch <= 0 || (paths != 4 && paths != 8) || cus <= 0) return "";
-    const PipelineChoice c = choose_pipeline(width, height, dMax, batch, paths, P1, P2, cmax, 0, cus);
-    return pipeline_name(c.kind, c.sweep_par, c.band_chain, c.sweep_mid);
+    return kPipelineName[choose_pipeline(width, height, dMax, batch, paths, P1, P2, cmax, 0, cus)];
 }
 
 // The achievable HBM rate of this device, measured the way the aggregation kernels move bytes: a grid-stride
@@ -1126,24 +1032,29 @@ fsgm_status fsgm_measure_copy_bandwidth(int32_t device, size_t bytes, int32_t it
 // ---------------------------------------------------------------------------------------------
 static PerDevice<std::vector<fsgm_epi_plan*>> g_epi;            // cached plans per device, under that device's lock
 
-static fsgm_status cached_plan(fsgm_epi_plan** out, int W, int H, int D, int batch, const fsgm_epi_params& pr) {
-    std::vector<fsgm_epi_plan*>& g_cache = g_epi.v[pr.device];   // (the caller holds g_epi.mu[pr.device])
-    for (fsgm_epi_plan* p : g_cache)
-        if (p->W == W && p->H == H && p->D == D && p->batch == batch && p->prm.paths == pr.paths &&
-            p->prm.device == pr.device && p->prm.fb_check == pr.fb_check && p->prm.vz_to_disp == pr.vz_to_disp) {
-            p->prm = pr;
-            *out = p;
-            return FSGM_OK;
-        }
+// The cached plan of this shape for an entry point: `lk` holds its device's lock for the length of the call, the device is current.
+static fsgm_status cached_plan(std::unique_lock<std::mutex>& lk, fsgm_epi_plan** out, int W, int H, int D, int batch,
+                               const fsgm_epi_params& pr) {
+    FSGM_DEVICE_SLOT(pr.device);
+    lk = std::unique_lock<std::mutex>(g_epi.mu[pr.device]);
+    std::vector<fsgm_epi_plan*>& g_cache = g_epi.v[pr.device];
     fsgm_epi_plan* p = nullptr;
-    fsgm_status st = fsgm_epi_plan_create(&p, W, H, D, batch, &pr);
-    if (st != FSGM_OK) return st;
-    if (g_cache.size() >= 4) {           // bound the HBM held by stale shapes
-        fsgm_epi_plan_destroy(g_cache.front());
-        g_cache.erase(g_cache.begin());
+    for (fsgm_epi_plan* q : g_cache)
+        if (q->W == W && q->H == H && q->D == D && q->batch == batch && q->prm.paths == pr.paths &&
+            q->prm.device == pr.device && q->prm.fb_check == pr.fb_check && q->prm.vz_to_disp == pr.vz_to_disp)
+            p = q;
+    if (p) p->prm = pr;
+    else {
+        fsgm_status st = fsgm_epi_plan_create(&p, W, H, D, batch, &pr);
+        if (st != FSGM_OK) return st;
+        if (g_cache.size() >= 4) {           // bound the HBM held by stale shapes
+            fsgm_epi_plan_destroy(g_cache.front());
+            g_cache.erase(g_cache.begin());
+        }
+        g_cache.push_back(p);
     }
-    g_cache.push_back(p);
     *out = p;
+    FSGM_HIP(hipSetDevice(pr.device));
     return FSGM_OK;
 }
 
@@ -1178,13 +1089,11 @@ fsgm_status fsgm_calc_cost_sgm_batch_host(int32_t n, const fsgm_epi_in* in, cons
                      in[i].P1 == in[0].P1 && in[i].P2 == in[0].P2 && in[i].vMax == in[0].vMax,
                      "fsgm_calc_cost_sgm: frames of one batch must share shape and parameters (frame %d differs)", i);
     }
-    FSGM_DEVICE_SLOT(pr.device);
-    std::lock_guard<std::mutex> lk(g_epi.mu[pr.device]);
+    std::unique_lock<std::mutex> lk;
     fsgm_epi_plan* p = nullptr;
-    fsgm_status st = cached_plan(&p, in[0].width, in[0].height, in[0].dMax, n, pr);
+    fsgm_status st = cached_plan(lk, &p, in[0].width, in[0].height, in[0].dMax, n, pr);
     if (st != FSGM_OK) return st;
     if ((st = fsgm_epi_plan_set_penalties(p, in[0].P1, in[0].P2, in[0].vMax)) != FSGM_OK) return st;
-    FSGM_HIP(hipSetDevice(p->prm.device));
     if ((st = ensure_cost_buffers(p)) != FSGM_OK) return st;
     // One call = one stream-ordered sequence with a single host wait: every frame's inputs go up asynchronously on the
     // plan's stream (hipMemcpyAsync from the caller's pageable memory runs at the pinned rate here, ~50 GB/s, so there is
@@ -1194,14 +1103,9 @@ fsgm_status fsgm_calc_cost_sgm_batch_host(int32_t n, const fsgm_epi_in* in, cons
     // 1242x375x128 frame, 9.2 vs 7.9 ms for eight); a pinned staging ring (an extra host copy at 25-34 GB/s).
     StreamGuard guard(p->stream);                                // every early exit drains the stream: the copies use caller memory
     const size_t NP = p->NP;
-    for (int i = 0; i < n; i++) {
-        FSGM_HIP(hipMemcpyAsync(p->dI1 + i * NP, in[i].I1, NP, hipMemcpyHostToDevice, p->stream));
-        FSGM_HIP(hipMemcpyAsync(p->dI2 + i * NP, in[i].I2, NP, hipMemcpyHostToDevice, p->stream));
-        FSGM_HIP(hipMemcpyAsync(p->dPd0 + (size_t)i * 2 * NP, in[i].pixelPosD0, NP * 16, hipMemcpyHostToDevice, p->stream));
-        FSGM_HIP(hipMemcpyAsync(p->dNd + (size_t)i * 2 * NP, in[i].normDir, NP * 16, hipMemcpyHostToDevice, p->stream));
-        FSGM_HIP(hipMemcpyAsync(p->dOff + i * NP, in[i].offset, NP * 8, hipMemcpyHostToDevice, p->stream));
-    }
-    if ((st = run_stages(p, FSGM_STAGE_ALL)) != FSGM_OK) return st;
+    for (int i = 0; i < n; i++)
+        if ((st = upload_async(p, i, in[i].I1, in[i].I2, in[i].pixelPosD0, in[i].normDir, in[i].offset)) != FSGM_OK) return st;
+    if ((st = enqueue(p, FSGM_STAGE_ALL)) != FSGM_OK) return st;
     bool taps = false;
     for (int i = 0; i < n; i++) {
         FSGM_HIP(hipMemcpyAsync(out[i].bestD, p->dBestD + i * NP, NP * 4, hipMemcpyDeviceToHost, p->stream));
@@ -1230,10 +1134,9 @@ fsgm_status fsgm_sgm_host(const uint8_t* C, int32_t W, int32_t H, int32_t D, int
     FSGM_REQUIRE(C && bestD && minC, "fsgm_sgm: null argument");
     fsgm_epi_params pr = fsgm_epi_params_default();
     pr.paths = paths; pr.device = device; pr.vz_to_disp = 0; pr.subpixel = 1;
-    FSGM_DEVICE_SLOT(device);
-    std::lock_guard<std::mutex> lk(g_epi.mu[device]);
+    std::unique_lock<std::mutex> lk;
     fsgm_epi_plan* p = nullptr;
-    fsgm_status st = cached_plan(&p, W, H, D, 1, pr);
+    fsgm_status st = cached_plan(lk, &p, W, H, D, 1, pr);
     if (st != FSGM_OK) return st;
     if ((st = fsgm_epi_plan_set_penalties(p, P1, P2, p->vMax)) != FSGM_OK) return st;
     if ((st = fsgm_epi_plan_upload_cost(p, 0, C)) != FSGM_OK) return st;
@@ -1249,12 +1152,10 @@ fsgm_status fsgm_census_host(const uint8_t* img, int32_t W, int32_t H, uint32_t*
     FSGM_REQUIRE(W >= 1 && H >= 1, "width/height must be >= 1 (got %d x %d)", W, H);
     fsgm_epi_params pr = fsgm_epi_params_default();
     pr.device = device;
-    FSGM_DEVICE_SLOT(device);
-    std::lock_guard<std::mutex> lk(g_epi.mu[device]);
+    std::unique_lock<std::mutex> lk;
     fsgm_epi_plan* p = nullptr;
-    fsgm_status st = cached_plan(&p, W, H, 16, 1, pr);           // any dMax: only the image / census buffers are used
+    fsgm_status st = cached_plan(lk, &p, W, H, 16, 1, pr);       // any dMax: only the image / census buffers are used
     if (st != FSGM_OK) return st;
-    FSGM_HIP(hipSetDevice(device));
     if ((st = ensure_cost_buffers(p)) != FSGM_OK) return st;
     StreamGuard guard(p->stream);
     FSGM_HIP(hipMemcpyAsync(p->dI1, img, p->NP, hipMemcpyHostToDevice, p->stream));
@@ -1275,11 +1176,20 @@ static EpiGeomArgs geom_args(const fsgm_epi_geometry* g, int W, int H, double* P
     return a;
 }
 
-static fsgm_status ensure_driver_buffers(fsgm_epi_plan* p, int channels) {
+// The epipolar drivers' buffers (RGB staging: host forms with RGB planes); test.m's frame body (pp) also has the
+// post-processing chain's scratch plan and D1, and its host form flow2.
+static fsgm_status ensure_driver_buffers(fsgm_epi_plan* p, int channels, bool pp = false, bool host = false) {
     { fsgm_status cs = ensure_cost_buffers(p); if (cs != FSGM_OK) return cs; }
-    if (!p->dRflow) FSGM_HIP(hipMalloc((void**)&p->dRflow, (size_t)p->batch * p->NP * 16));
-    if (!p->dFlow) FSGM_HIP(hipMalloc((void**)&p->dFlow, (size_t)p->batch * p->NP * 24));
+    const size_t np = (size_t)p->batch * p->NP;
+    if (!p->dRflow) FSGM_HIP(hipMalloc((void**)&p->dRflow, np * 16));
+    if (!p->dFlow) FSGM_HIP(hipMalloc((void**)&p->dFlow, np * 24));
     if (channels == 3 && !p->dRgb) FSGM_HIP(hipMalloc((void**)&p->dRgb, p->NP * 3 * 2));
+    if (pp && !p->post) {
+        fsgm_status st = post_plan_create_batch(&p->post, p->W, p->H, p->batch, p->prm.device, false);
+        if (st != FSGM_OK) return st;
+    }
+    if (pp && !p->dD1) FSGM_HIP(hipMalloc((void**)&p->dD1, np * 8));
+    if (pp && host && !p->dFlow2) FSGM_HIP(hipMalloc((void**)&p->dFlow2, np * 24));
     return FSGM_OK;
 }
 
@@ -1289,12 +1199,10 @@ fsgm_status fsgm_epipolar_maps_host(const fsgm_epi_geometry* g, int32_t W, int32
     FSGM_REQUIRE(W >= 1 && H >= 1, "width/height must be >= 1 (got %d x %d)", W, H);
     fsgm_epi_params pr = fsgm_epi_params_default();
     pr.device = device;
-    FSGM_DEVICE_SLOT(device);
-    std::lock_guard<std::mutex> lk(g_epi.mu[device]);
+    std::unique_lock<std::mutex> lk;
     fsgm_epi_plan* p = nullptr;
-    fsgm_status st = cached_plan(&p, W, H, 16, 1, pr);           // any dMax: only the map buffers are used
+    fsgm_status st = cached_plan(lk, &p, W, H, 16, 1, pr);       // any dMax: only the map buffers are used
     if (st != FSGM_OK) return st;
-    FSGM_HIP(hipSetDevice(device));
     if ((st = ensure_driver_buffers(p, 1)) != FSGM_OK) return st;
     StreamGuard guard(p->stream);
     launch_epi_maps(p->stream, geom_args(g, W, H, p->dPd0, p->dNd, p->dOff, p->dRflow));
@@ -1303,44 +1211,6 @@ fsgm_status fsgm_epipolar_maps_host(const fsgm_epi_geometry* g, int32_t W, int32
     FSGM_HIP(hipMemcpyAsync(normDirect, p->dNd, p->NP * 16, hipMemcpyDeviceToHost, p->stream));
     FSGM_HIP(hipMemcpyAsync(Offset, p->dOff, p->NP * 8, hipMemcpyDeviceToHost, p->stream));
     FSGM_HIP(hipMemcpyAsync(Rflow, p->dRflow, p->NP * 16, hipMemcpyDeviceToHost, p->stream));
-    FSGM_HIP(hipStreamSynchronize(p->stream));
-    guard.dismiss();
-    return FSGM_OK;
-}
-
-fsgm_status fsgm_epipolar_sgm_of_host(const uint8_t* I0, const uint8_t* I1, int32_t W, int32_t H, int32_t channels,
-                                      const fsgm_epi_geometry* g, int32_t dMax, double vMax, const fsgm_epi_params* prm,
-                                      double* flow, uint32_t* minC) {
-    FSGM_REQUIRE(I0 && I1 && g && flow, "fsgm_epipolar_sgm_of: null argument");
-    FSGM_REQUIRE(W >= 1 && H >= 1, "width/height must be >= 1 (got %d x %d)", W, H);
-    FSGM_REQUIRE(channels == 1 || channels == 3, "channels must be 1 (gray) or 3 (RGB planes), got %d", channels);
-    fsgm_epi_params pr = prm ? *prm : fsgm_epi_params_default();
-    FSGM_REQUIRE(pr.vz_to_disp && !pr.fb_check, "fsgm_epipolar_sgm_of: the flow needs disparities (vz_to_disp = 1, fb_check = 0)");
-    FSGM_DEVICE_SLOT(pr.device);
-    std::lock_guard<std::mutex> lk(g_epi.mu[pr.device]);
-    fsgm_epi_plan* p = nullptr;
-    fsgm_status st = cached_plan(&p, W, H, dMax, 1, pr);
-    if (st != FSGM_OK) return st;
-    FSGM_HIP(hipSetDevice(pr.device));
-    if ((st = fsgm_epi_plan_set_penalties(p, 6, 64, vMax)) != FSGM_OK) return st;        // epipolar_sgm_of.m:19
-    if ((st = ensure_driver_buffers(p, channels)) != FSGM_OK) return st;
-    const size_t NP = p->NP;
-    StreamGuard guard(p->stream);
-    if (channels == 3) {                                                                 // epipolar_sgm_of.m:35-38
-        FSGM_HIP(hipMemcpyAsync(p->dRgb, I0, 3 * NP, hipMemcpyHostToDevice, p->stream));
-        FSGM_HIP(hipMemcpyAsync(p->dRgb + 3 * NP, I1, 3 * NP, hipMemcpyHostToDevice, p->stream));
-        launch_pyr_gray(p->stream, p->dRgb, p->dI1, W, H);
-        launch_pyr_gray(p->stream, p->dRgb + 3 * NP, p->dI2, W, H);
-    } else {
-        FSGM_HIP(hipMemcpyAsync(p->dI1, I0, NP, hipMemcpyHostToDevice, p->stream));
-        FSGM_HIP(hipMemcpyAsync(p->dI2, I1, NP, hipMemcpyHostToDevice, p->stream));
-    }
-    launch_epi_maps(p->stream, geom_args(g, W, H, p->dPd0, p->dNd, p->dOff, p->dRflow));  // epipolar_sgm_of.m:24
-    if ((st = enqueue(p, FSGM_STAGE_ALL)) != FSGM_OK) return st;                          // :45
-    launch_epi_flow(p->stream, p->dBestD, p->dNd, p->dRflow, p->dFlow, W, H);             // :46-51
-    FSGM_HIP(hipGetLastError());
-    FSGM_HIP(hipMemcpyAsync(flow, p->dFlow, NP * 24, hipMemcpyDeviceToHost, p->stream));
-    if (minC) FSGM_HIP(hipMemcpyAsync(minC, p->dMinC, NP * 4, hipMemcpyDeviceToHost, p->stream));
     FSGM_HIP(hipStreamSynchronize(p->stream));
     guard.dismiss();
     return FSGM_OK;
@@ -1363,13 +1233,14 @@ static fsgm_status epi_device_args(const char* who, int32_t n, const fsgm_epi_in
 
 // What a warm call must not do -- allocate, upload a table, synchronise -- happens here on a plan's first call, before the
 // join with the caller's stream.
-static fsgm_status epi_device_prepare(fsgm_epi_plan* p, int P1, int P2, double vMax) {
+static fsgm_status epi_device_enter(fsgm_epi_plan* p, int P1, int P2, double vMax, hipStream_t cs) {
     fsgm_status st;
     if ((st = fsgm_epi_plan_set_penalties(p, P1, P2, vMax)) != FSGM_OK) return st;
     if ((st = ensure_cost_buffers(p)) != FSGM_OK) return st;
     if ((st = ensure_vz(p)) != FSGM_OK) return st;
     if ((st = prepare(p, FSGM_STAGE_ALL)) != FSGM_OK) return st;
-    return p->join.ensure();
+    if ((st = p->join.ensure()) != FSGM_OK) return st;
+    return p->join.enter(cs, p->stream);
 }
 
 // the status word, then the caller's stream waits for the plan's (also after a failed enqueue: whatever was queued stays
@@ -1382,8 +1253,15 @@ static fsgm_status epi_device_finish(fsgm_epi_plan* p, hipStream_t cs, int32_t* 
     return js;
 }
 
-static fsgm_status epi_run_device(const char* who, fsgm_epi_plan* p, int32_t n, const fsgm_epi_in* in, const fsgm_epi_out* out,
-                                  hipStream_t cs, int32_t* status) {
+// a batch on device pointers through the caller's plan p, or (p null) through the cached plan for prm
+static fsgm_status epi_run_device(const char* who, fsgm_epi_plan* p, const fsgm_epi_params* prm, int32_t n, const fsgm_epi_in* in,
+                                  const fsgm_epi_out* out, void* stream, int32_t* status) {
+    fsgm_status st = epi_device_args(who, n, in, out);
+    if (st != FSGM_OK) return st;
+    std::unique_lock<std::mutex> lk;
+    if (!p && (st = cached_plan(lk, &p, in->width, in->height, in->dMax, n, prm ? *prm : fsgm_epi_params_default())) != FSGM_OK)
+        return st;
+    const hipStream_t cs = (hipStream_t)stream;
     FSGM_REQUIRE(n == p->batch, "%s: n_frames %d differs from the plan's batch %d", who, n, p->batch);
     FSGM_REQUIRE(in->width == p->W && in->height == p->H && in->dMax == p->D, "%s: shape %d x %d x %d differs from the plan's %d x %d x %d",
                  who, in->width, in->height, in->dMax, p->W, p->H, p->D);
@@ -1391,9 +1269,8 @@ static fsgm_status epi_run_device(const char* who, fsgm_epi_plan* p, int32_t n, 
     const size_t np = (size_t)n * p->NP;
     const bool fb = p->prm.fb_check != 0;
     FSGM_HIP(hipSetDevice(dev));
-    fsgm_status st;
-    if ((st = device_check_stream(cs, who)) != FSGM_OK) return st;
-    if ((st = device_check_ptr(in->I1, np, 1, dev, true, who, "I1")) != FSGM_OK ||
+    if ((st = device_check_stream(cs, who)) != FSGM_OK ||
+        (st = device_check_ptr(in->I1, np, 1, dev, true, who, "I1")) != FSGM_OK ||
         (st = device_check_ptr(in->I2, np, 1, dev, true, who, "I2")) != FSGM_OK ||
         (st = device_check_ptr(in->pixelPosD0, np * 16, 8, dev, true, who, "pixelPosD0")) != FSGM_OK ||
         (st = device_check_ptr(in->normDir, np * 16, 8, dev, true, who, "normDir")) != FSGM_OK ||
@@ -1404,8 +1281,7 @@ static fsgm_status epi_run_device(const char* who, fsgm_epi_plan* p, int32_t n, 
         (fb && (st = device_check_ptr(out->bestD2, np * 4, 4, dev, false, who, "bestD2")) != FSGM_OK) ||
         (st = device_check_ptr(status, 4, 4, dev, false, who, "status")) != FSGM_OK)
         return st;
-    if ((st = epi_device_prepare(p, in->P1, in->P2, in->vMax)) != FSGM_OK) return st;
-    if ((st = p->join.enter(cs, p->stream)) != FSGM_OK) return st;
+    if ((st = epi_device_enter(p, in->P1, in->P2, in->vMax, cs)) != FSGM_OK) return st;
     {
         Bind<uint8_t> i1(p->dI1, const_cast<uint8_t*>(in->I1)), i2(p->dI2, const_cast<uint8_t*>(in->I2));
         Bind<double> pd0(p->dPd0, const_cast<double*>(in->pixelPosD0)), nd(p->dNd, const_cast<double*>(in->normDir));
@@ -1419,134 +1295,79 @@ static fsgm_status epi_run_device(const char* who, fsgm_epi_plan* p, int32_t n, 
 
 fsgm_status fsgm_epi_plan_run_device(fsgm_epi_plan* p, int32_t n, const fsgm_epi_in* in, const fsgm_epi_out* out, void* stream,
                                      int32_t* status) {
-    const char* who = "fsgm_epi_plan_run_device";
-    FSGM_REQUIRE(p, "%s: null plan", who);
-    fsgm_status st = epi_device_args(who, n, in, out);
-    if (st != FSGM_OK) return st;
-    return epi_run_device(who, p, n, in, out, (hipStream_t)stream, status);
+    FSGM_REQUIRE(p, "fsgm_epi_plan_run_device: null plan");
+    return epi_run_device("fsgm_epi_plan_run_device", p, nullptr, n, in, out, stream, status);
 }
 
 fsgm_status fsgm_calc_cost_sgm_device(int32_t n, const fsgm_epi_in* in, const fsgm_epi_out* out, const fsgm_epi_params* prm,
                                       void* stream, int32_t* status) {
-    const char* who = "fsgm_calc_cost_sgm_device";
-    fsgm_status st = epi_device_args(who, n, in, out);
-    if (st != FSGM_OK) return st;
-    const fsgm_epi_params pr = prm ? *prm : fsgm_epi_params_default();
-    FSGM_DEVICE_SLOT(pr.device);
-    std::lock_guard<std::mutex> lk(g_epi.mu[pr.device]);
-    fsgm_epi_plan* p = nullptr;
-    if ((st = cached_plan(&p, in->width, in->height, in->dMax, n, pr)) != FSGM_OK) return st;
-    return epi_run_device(who, p, n, in, out, (hipStream_t)stream, status);
-}
-
-fsgm_status fsgm_epipolar_sgm_of_device(int32_t n, const uint8_t* I0, const uint8_t* I1, int32_t W, int32_t H, int32_t channels,
-                                        const fsgm_epi_geometry* g, int32_t dMax, double vMax, const fsgm_epi_params* prm,
-                                        double* flow, uint32_t* minC, void* stream, int32_t* status) {
-    const char* who = "fsgm_epipolar_sgm_of_device";
-    FSGM_REQUIRE(n >= 1, "%s: n_frames must be >= 1 (got %d)", who, n);
-    FSGM_REQUIRE(I0 && I1 && g && flow, "%s: null argument", who);
-    FSGM_REQUIRE(W >= 1 && H >= 1 && dMax >= 1, "%s: width/height/dMax must be >= 1 (got %d x %d x %d)", who, W, H, dMax);
-    FSGM_REQUIRE(channels == 1 || channels == 3, "%s: channels must be 1 (gray) or 3 (RGB planes), got %d", who, channels);
-    fsgm_epi_params pr = prm ? *prm : fsgm_epi_params_default();
-    FSGM_REQUIRE(pr.vz_to_disp && !pr.fb_check, "%s: the flow needs disparities (vz_to_disp = 1, fb_check = 0)", who);
-    FSGM_DEVICE_SLOT(pr.device);
-    std::lock_guard<std::mutex> lk(g_epi.mu[pr.device]);
-    fsgm_epi_plan* p = nullptr;
-    fsgm_status st = cached_plan(&p, W, H, dMax, n, pr);
-    if (st != FSGM_OK) return st;
-    const int dev = pr.device;
-    const size_t NP = p->NP, np = (size_t)n * NP;
-    hipStream_t cs = (hipStream_t)stream;
-    FSGM_HIP(hipSetDevice(dev));
-    if ((st = device_check_stream(cs, who)) != FSGM_OK) return st;
-    if ((st = device_check_ptr(I0, np * channels, 1, dev, true, who, "I0")) != FSGM_OK ||
-        (st = device_check_ptr(I1, np * channels, 1, dev, true, who, "I1")) != FSGM_OK ||
-        (st = device_check_ptr(flow, np * 24, 8, dev, true, who, "flow")) != FSGM_OK ||
-        (st = device_check_ptr(minC, np * 4, 4, dev, false, who, "minC")) != FSGM_OK ||
-        (st = device_check_ptr(status, 4, 4, dev, false, who, "status")) != FSGM_OK)
-        return st;
-    if ((st = ensure_driver_buffers(p, 1)) != FSGM_OK) return st;                        // (RGB goes to gray straight from the caller's planes)
-    if ((st = epi_device_prepare(p, 6, 64, vMax)) != FSGM_OK) return st;                  // epipolar_sgm_of.m:19
-    if ((st = p->join.enter(cs, p->stream)) != FSGM_OK) return st;
-    {
-        Bind<uint8_t> i1(p->dI1, channels == 1 ? const_cast<uint8_t*>(I0) : nullptr), i2(p->dI2, channels == 1 ? const_cast<uint8_t*>(I1) : nullptr);
-        Bind<uint32_t> mc(p->dMinC, minC);
-        if (channels == 3) {                                                              // epipolar_sgm_of.m:35-38
-            launch_pyr_gray(p->stream, I0, p->dI1, W, H, n);
-            launch_pyr_gray(p->stream, I1, p->dI2, W, H, n);
-        }
-        for (int f = 0; f < n; f++)                                                       // :24, the geometry by value
-            launch_epi_maps(p->stream, geom_args(&g[f], W, H, p->dPd0 + f * 2 * NP, p->dNd + f * 2 * NP, p->dOff + f * NP, p->dRflow + f * 2 * NP));
-        st = enqueue(p, FSGM_STAGE_ALL);                                                  // :45
-        if (st == FSGM_OK)
-            for (int f = 0; f < n; f++)                                                   // :46-51
-                launch_epi_flow(p->stream, p->dBestD + f * NP, p->dNd + f * 2 * NP, p->dRflow + f * 2 * NP, flow + f * 3 * NP, W, H);
-    }
-    return epi_device_finish(p, cs, status, st);
+    return epi_run_device("fsgm_calc_cost_sgm_device", nullptr, prm, n, in, out, stream, status);
 }
 
 // ---------------------------------------------------------------------------------------------
-// test.m's frame body (:32-54), the geometry given: the matcher in vz-index mode, D1 = bestD/256, flow, the post-processing
-// chain and flow2, all on the plan's stream
+// The epipolar drivers: epipolar_sgm_of (the matcher, then the flow) and test.m's frame body (pp; :32-54), the geometry given:
+// the matcher in vz-index mode, D1 = bestD/256, flow, the post-processing chain and flow2, all on the plan's stream
 // ---------------------------------------------------------------------------------------------
-static fsgm_status pp_args(const char* who, int32_t n, const uint8_t* I0, const uint8_t* I1, int32_t W, int32_t H, int32_t channels,
-                           const fsgm_epi_geometry* g, int32_t dMax, const fsgm_epi_params* prm, const double* flow,
-                           const double* flow2, fsgm_epi_params* pr) {
+// the arguments of both forms of test.m's frame body (pp: flow2 required) and of fsgm_epipolar_sgm_of_device
+static fsgm_status driver_args(const char* who, bool pp, int32_t n, const uint8_t* I0, const uint8_t* I1, int32_t W, int32_t H,
+                               int32_t channels, const fsgm_epi_geometry* g, int32_t dMax, const fsgm_epi_params* prm, const double* flow,
+                               const double* flow2, fsgm_epi_params* pr) {
     FSGM_REQUIRE(n >= 1, "%s: n_frames must be >= 1 (got %d)", who, n);
-    FSGM_REQUIRE(I0 && I1 && g && flow && flow2, "%s: null argument", who);
+    FSGM_REQUIRE(I0 && I1 && g && flow && (flow2 || !pp), "%s: null argument", who);
     FSGM_REQUIRE(W >= 1 && H >= 1 && dMax >= 1, "%s: width/height/dMax must be >= 1 (got %d x %d x %d)", who, W, H, dMax);
     FSGM_REQUIRE(channels == 1 || channels == 3, "%s: channels must be 1 (gray) or 3 (RGB planes), got %d", who, channels);
     *pr = prm ? *prm : fsgm_epi_params_default();
-    FSGM_REQUIRE(!pr->fb_check, "%s: fb_check must be 0 (the chain does its own forward-backward check)", who);
-    if ((double)n * W * H >= 2147483648.0)
-        return fail(FSGM_ERR_UNSUPPORTED, "%s: n_frames * width * height = %.0f reaches 2^31 (32-bit pixel indices)", who, (double)n * W * H);
-    FSGM_DEVICE_SLOT(pr->device);
-    pr->vz_to_disp = 0;                                                                  // the chain works on vz indices
-    return FSGM_OK;
-}
-
-static fsgm_status ensure_pp_buffers(fsgm_epi_plan* p, bool host) {
-    const size_t np = (size_t)p->batch * p->NP;
-    if (!p->post) {
-        fsgm_status st = post_plan_create_batch(&p->post, p->W, p->H, p->batch, p->prm.device, false);
-        if (st != FSGM_OK) return st;
+    if (!pp) {
+        FSGM_REQUIRE(pr->vz_to_disp && !pr->fb_check, "%s: the flow needs disparities (vz_to_disp = 1, fb_check = 0)", who);
+    } else {
+        FSGM_REQUIRE(!pr->fb_check, "%s: fb_check must be 0 (the chain does its own forward-backward check)", who);
+        if ((double)n * W * H >= 2147483648.0)
+            return fail(FSGM_ERR_UNSUPPORTED, "%s: n_frames * width * height = %.0f reaches 2^31 (32-bit pixel indices)", who, (double)n * W * H);
     }
-    if (!p->dD1) FSGM_HIP(hipMalloc((void**)&p->dD1, np * 8));
-    if (host && !p->dFlow2) FSGM_HIP(hipMalloc((void**)&p->dFlow2, np * 24));
+    if (pp) pr->vz_to_disp = 0;                                                          // the chain works on vz indices
     return FSGM_OK;
 }
 
-// images in dI1 / dI2 and the maps in dPd0 / dNd / dOff / dRflow: :36 -> flow (:38-42) and flow2 (:45-54); D1 [batch][H][W]
-static fsgm_status enqueue_pp(fsgm_epi_plan* p, int dMax, double vMax, double* flow, double* flow2, double* D1) {
-    fsgm_status st = enqueue(p, FSGM_STAGE_ALL);                                         // :36
+// images in dI1 / dI2 and the maps in dPd0 / dNd / dOff / dRflow: the matcher (epipolar_sgm_of.m:45, test.m:36), then each
+// frame's flow (epipolar_sgm_of.m:46-51) or (pp) test.m's flow (:38-42) and flow2 (:45-54); D1 [batch][H][W]
+static fsgm_status enqueue_flow(fsgm_epi_plan* p, bool pp, int dMax, double vMax, double* flow, double* flow2, double* D1) {
+    fsgm_status st = enqueue(p, FSGM_STAGE_ALL);
     if (st != FSGM_OK) return st;
     const int W = p->W, H = p->H, nf = p->batch;
-    const double n = (double)dMax + 1.0;                                                 // :6
-    const PostScratch s = post_plan_scratch(p->post);
-    launch_vz_from_bestd(p->stream, p->dBestD, D1, (size_t)nf * p->NP);
-    post_enqueue_batch(p->stream, s, nf, W, H, D1, p->dPd0, p->dNd, p->dOff, vMax, n, (double)dMax, s.B, s.D2, nullptr, nullptr);
-    launch_epi_pp_flow(p->stream, D1, s.B, p->dOff, p->dNd, p->dRflow, flow, flow2, W, H, nf, vMax, n);
+    const size_t NP = p->NP;
+    if (!pp) {
+        for (int f = 0; f < nf; f++)
+            launch_epi_flow(p->stream, p->dBestD + f * NP, p->dNd + f * 2 * NP, p->dRflow + f * 2 * NP, flow + f * 3 * NP, W, H);
+    } else {
+        const double n = (double)dMax + 1.0;                                             // test.m:6
+        const PostScratch s = post_plan_scratch(p->post);
+        launch_vz_from_bestd(p->stream, p->dBestD, D1, (size_t)nf * NP);
+        post_enqueue_batch(p->stream, s, nf, W, H, D1, p->dPd0, p->dNd, p->dOff, vMax, n, (double)dMax, s.B, s.D2, nullptr, nullptr);
+        launch_epi_pp_flow(p->stream, D1, s.B, p->dOff, p->dNd, p->dRflow, flow, flow2, W, H, nf, vMax, n);
+    }
     FSGM_HIP(hipGetLastError());
     return FSGM_OK;
 }
 
-fsgm_status fsgm_epipolar_flow_pp_host(int32_t n, const uint8_t* I0, const uint8_t* I1, int32_t W, int32_t H, int32_t channels,
-                                       const fsgm_epi_geometry* g, int32_t dMax, double vMax, const fsgm_epi_params* prm,
-                                       double* flow, double* flow2, double* D1, uint32_t* minC) {
-    fsgm_epi_params pr;
-    fsgm_status st = pp_args("fsgm_epipolar_flow_pp_host", n, I0, I1, W, H, channels, g, dMax, prm, flow, flow2, &pr);
-    if (st != FSGM_OK) return st;
-    std::lock_guard<std::mutex> lk(g_epi.mu[pr.device]);
+// Host forms: on the plan's stream the n image pairs as gray (:35-38; RGB planes through one staging pair, reused in stream
+// order) and each frame's coordinate maps (:24), the matcher (:45) and the flow (:46-51), the results down.
+static fsgm_status host_drive(bool pp, int32_t n, const uint8_t* I0, const uint8_t* I1, int32_t W, int32_t H, int32_t channels,
+                              const fsgm_epi_geometry* g, int32_t dMax, double vMax, const fsgm_epi_params& pr, double* flow,
+                              double* flow2, double* D1, uint32_t* minC) {
+    std::unique_lock<std::mutex> lk;
     fsgm_epi_plan* p = nullptr;
-    if ((st = cached_plan(&p, W, H, dMax, n, pr)) != FSGM_OK) return st;
-    FSGM_HIP(hipSetDevice(pr.device));
-    if ((st = fsgm_epi_plan_set_penalties(p, 6, 64, vMax)) != FSGM_OK) return st;       // test.m:36
-    if ((st = ensure_driver_buffers(p, channels)) != FSGM_OK) return st;
-    if ((st = ensure_pp_buffers(p, true)) != FSGM_OK) return st;
+    fsgm_status st = cached_plan(lk, &p, W, H, dMax, n, pr);
+    if (st != FSGM_OK) return st;
+    if ((st = fsgm_epi_plan_set_penalties(p, 6, 64, vMax)) != FSGM_OK) return st;       // epipolar_sgm_of.m:19, test.m:36
+    if ((st = ensure_driver_buffers(p, channels, pp, true)) != FSGM_OK) return st;
     const size_t NP = p->NP, np = (size_t)n * NP;
     StreamGuard guard(p->stream);
+    if (channels == 1) {
+        FSGM_HIP(hipMemcpyAsync(p->dI1, I0, np, hipMemcpyHostToDevice, p->stream));
+        FSGM_HIP(hipMemcpyAsync(p->dI2, I1, np, hipMemcpyHostToDevice, p->stream));
+    }
     for (int f = 0; f < n; f++) {
-        if (channels == 3) {                                                             // one RGB staging pair, reused in stream order
+        if (channels == 3) {
             FSGM_HIP(hipMemcpyAsync(p->dRgb, I0 + f * 3 * NP, 3 * NP, hipMemcpyHostToDevice, p->stream));
             FSGM_HIP(hipMemcpyAsync(p->dRgb + 3 * NP, I1 + f * 3 * NP, 3 * NP, hipMemcpyHostToDevice, p->stream));
             launch_pyr_gray(p->stream, p->dRgb, p->dI1 + f * NP, W, H);
@@ -1554,13 +1375,9 @@ fsgm_status fsgm_epipolar_flow_pp_host(int32_t n, const uint8_t* I0, const uint8
         }
         launch_epi_maps(p->stream, geom_args(&g[f], W, H, p->dPd0 + f * 2 * NP, p->dNd + f * 2 * NP, p->dOff + f * NP, p->dRflow + f * 2 * NP));
     }
-    if (channels == 1) {
-        FSGM_HIP(hipMemcpyAsync(p->dI1, I0, np, hipMemcpyHostToDevice, p->stream));
-        FSGM_HIP(hipMemcpyAsync(p->dI2, I1, np, hipMemcpyHostToDevice, p->stream));
-    }
-    if ((st = enqueue_pp(p, dMax, vMax, p->dFlow, p->dFlow2, p->dD1)) != FSGM_OK) return st;
+    if ((st = enqueue_flow(p, pp, dMax, vMax, p->dFlow, p->dFlow2, p->dD1)) != FSGM_OK) return st;
     FSGM_HIP(hipMemcpyAsync(flow, p->dFlow, np * 24, hipMemcpyDeviceToHost, p->stream));
-    FSGM_HIP(hipMemcpyAsync(flow2, p->dFlow2, np * 24, hipMemcpyDeviceToHost, p->stream));
+    if (flow2) FSGM_HIP(hipMemcpyAsync(flow2, p->dFlow2, np * 24, hipMemcpyDeviceToHost, p->stream));
     if (D1) FSGM_HIP(hipMemcpyAsync(D1, p->dD1, np * 8, hipMemcpyDeviceToHost, p->stream));
     if (minC) FSGM_HIP(hipMemcpyAsync(minC, p->dMinC, np * 4, hipMemcpyDeviceToHost, p->stream));
     FSGM_HIP(hipStreamSynchronize(p->stream));
@@ -1568,33 +1385,52 @@ fsgm_status fsgm_epipolar_flow_pp_host(int32_t n, const uint8_t* I0, const uint8
     return check_handoff(p);
 }
 
-fsgm_status fsgm_epipolar_flow_pp_device(int32_t n, const uint8_t* I0, const uint8_t* I1, int32_t W, int32_t H, int32_t channels,
-                                         const fsgm_epi_geometry* g, int32_t dMax, double vMax, const fsgm_epi_params* prm,
-                                         double* flow, double* flow2, double* D1, uint32_t* minC, void* stream, int32_t* status) {
-    const char* who = "fsgm_epipolar_flow_pp_device";
+fsgm_status fsgm_epipolar_sgm_of_host(const uint8_t* I0, const uint8_t* I1, int32_t W, int32_t H, int32_t channels,
+                                      const fsgm_epi_geometry* g, int32_t dMax, double vMax, const fsgm_epi_params* prm,
+                                      double* flow, uint32_t* minC) {
+    FSGM_REQUIRE(I0 && I1 && g && flow, "fsgm_epipolar_sgm_of: null argument");
+    FSGM_REQUIRE(W >= 1 && H >= 1, "width/height must be >= 1 (got %d x %d)", W, H);
+    FSGM_REQUIRE(channels == 1 || channels == 3, "channels must be 1 (gray) or 3 (RGB planes), got %d", channels);
+    fsgm_epi_params pr = prm ? *prm : fsgm_epi_params_default();
+    FSGM_REQUIRE(pr.vz_to_disp && !pr.fb_check, "fsgm_epipolar_sgm_of: the flow needs disparities (vz_to_disp = 1, fb_check = 0)");
+    return host_drive(false, 1, I0, I1, W, H, channels, g, dMax, vMax, pr, flow, nullptr, nullptr, minC);
+}
+
+fsgm_status fsgm_epipolar_flow_pp_host(int32_t n, const uint8_t* I0, const uint8_t* I1, int32_t W, int32_t H, int32_t channels,
+                                       const fsgm_epi_geometry* g, int32_t dMax, double vMax, const fsgm_epi_params* prm,
+                                       double* flow, double* flow2, double* D1, uint32_t* minC) {
     fsgm_epi_params pr;
-    fsgm_status st = pp_args(who, n, I0, I1, W, H, channels, g, dMax, prm, flow, flow2, &pr);
+    fsgm_status st = driver_args("fsgm_epipolar_flow_pp_host", true, n, I0, I1, W, H, channels, g, dMax, prm, flow, flow2, &pr);
     if (st != FSGM_OK) return st;
-    std::lock_guard<std::mutex> lk(g_epi.mu[pr.device]);
+    return host_drive(true, n, I0, I1, W, H, channels, g, dMax, vMax, pr, flow, flow2, D1, minC);
+}
+
+// Device forms: the caller's arrays checked, the plan prepared before the join with the caller's stream, then on the plan's
+// stream the caller's images as gray (:35-38, straight from its planes) and each frame's maps (:24, the geometry by value),
+// with the caller's images and minC bound to the plan.
+static fsgm_status device_drive(const char* who, bool pp, int32_t n, const uint8_t* I0, const uint8_t* I1, int32_t W, int32_t H,
+                                int32_t channels, const fsgm_epi_geometry* g, int32_t dMax, double vMax, const fsgm_epi_params* prm,
+                                double* flow, double* flow2, double* D1, uint32_t* minC, void* stream, int32_t* status) {
+    fsgm_epi_params pr;
+    fsgm_status st = driver_args(who, pp, n, I0, I1, W, H, channels, g, dMax, prm, flow, flow2, &pr);
+    if (st != FSGM_OK) return st;
+    std::unique_lock<std::mutex> lk;
     fsgm_epi_plan* p = nullptr;
-    if ((st = cached_plan(&p, W, H, dMax, n, pr)) != FSGM_OK) return st;
+    if ((st = cached_plan(lk, &p, W, H, dMax, n, pr)) != FSGM_OK) return st;
     const int dev = pr.device;
     const size_t NP = p->NP, np = (size_t)n * NP;
-    hipStream_t cs = (hipStream_t)stream;
-    FSGM_HIP(hipSetDevice(dev));
-    if ((st = device_check_stream(cs, who)) != FSGM_OK) return st;
-    if ((st = device_check_ptr(I0, np * channels, 1, dev, true, who, "I0")) != FSGM_OK ||
+    const hipStream_t cs = (hipStream_t)stream;
+    if ((st = device_check_stream(cs, who)) != FSGM_OK ||
+        (st = device_check_ptr(I0, np * channels, 1, dev, true, who, "I0")) != FSGM_OK ||
         (st = device_check_ptr(I1, np * channels, 1, dev, true, who, "I1")) != FSGM_OK ||
         (st = device_check_ptr(flow, np * 24, 8, dev, true, who, "flow")) != FSGM_OK ||
-        (st = device_check_ptr(flow2, np * 24, 8, dev, true, who, "flow2")) != FSGM_OK ||
-        (st = device_check_ptr(D1, np * 8, 8, dev, false, who, "D1")) != FSGM_OK ||
+        (pp && (st = device_check_ptr(flow2, np * 24, 8, dev, true, who, "flow2")) != FSGM_OK) ||
+        (pp && (st = device_check_ptr(D1, np * 8, 8, dev, false, who, "D1")) != FSGM_OK) ||
         (st = device_check_ptr(minC, np * 4, 4, dev, false, who, "minC")) != FSGM_OK ||
         (st = device_check_ptr(status, 4, 4, dev, false, who, "status")) != FSGM_OK)
         return st;
-    if ((st = ensure_driver_buffers(p, 1)) != FSGM_OK) return st;
-    if ((st = ensure_pp_buffers(p, false)) != FSGM_OK) return st;
-    if ((st = epi_device_prepare(p, 6, 64, vMax)) != FSGM_OK) return st;                  // test.m:36
-    if ((st = p->join.enter(cs, p->stream)) != FSGM_OK) return st;
+    if ((st = ensure_driver_buffers(p, 1, pp)) != FSGM_OK) return st;
+    if ((st = epi_device_enter(p, 6, 64, vMax, cs)) != FSGM_OK) return st;               // epipolar_sgm_of.m:19, test.m:36
     {
         Bind<uint8_t> i1(p->dI1, channels == 1 ? const_cast<uint8_t*>(I0) : nullptr), i2(p->dI2, channels == 1 ? const_cast<uint8_t*>(I1) : nullptr);
         Bind<uint32_t> mc(p->dMinC, minC);
@@ -1602,11 +1438,25 @@ fsgm_status fsgm_epipolar_flow_pp_device(int32_t n, const uint8_t* I0, const uin
             launch_pyr_gray(p->stream, I0, p->dI1, W, H, n);
             launch_pyr_gray(p->stream, I1, p->dI2, W, H, n);
         }
-        for (int f = 0; f < n; f++)                                                       // :32, the geometry by value
+        for (int f = 0; f < n; f++)
             launch_epi_maps(p->stream, geom_args(&g[f], W, H, p->dPd0 + f * 2 * NP, p->dNd + f * 2 * NP, p->dOff + f * NP, p->dRflow + f * 2 * NP));
-        st = enqueue_pp(p, dMax, vMax, flow, flow2, D1 ? D1 : p->dD1);
+        st = enqueue_flow(p, pp, dMax, vMax, flow, flow2, D1 ? D1 : p->dD1);
     }
     return epi_device_finish(p, cs, status, st);
+}
+
+fsgm_status fsgm_epipolar_sgm_of_device(int32_t n, const uint8_t* I0, const uint8_t* I1, int32_t W, int32_t H, int32_t channels,
+                                        const fsgm_epi_geometry* g, int32_t dMax, double vMax, const fsgm_epi_params* prm,
+                                        double* flow, uint32_t* minC, void* stream, int32_t* status) {
+    return device_drive("fsgm_epipolar_sgm_of_device", false, n, I0, I1, W, H, channels, g, dMax, vMax, prm, flow, nullptr, nullptr, minC,
+                        stream, status);
+}
+
+fsgm_status fsgm_epipolar_flow_pp_device(int32_t n, const uint8_t* I0, const uint8_t* I1, int32_t W, int32_t H, int32_t channels,
+                                         const fsgm_epi_geometry* g, int32_t dMax, double vMax, const fsgm_epi_params* prm,
+                                         double* flow, double* flow2, double* D1, uint32_t* minC, void* stream, int32_t* status) {
+    return device_drive("fsgm_epipolar_flow_pp_device", true, n, I0, I1, W, H, channels, g, dMax, vMax, prm, flow, flow2, D1, minC,
+                        stream, status);
 }
 
 }  // extern "C"

@@ -161,7 +161,8 @@ fsgm_status fsgm_epi_plan_time(fsgm_epi_plan* plan, int32_t stages, int32_t warm
 void*       fsgm_epi_plan_stream(fsgm_epi_plan* plan);
 /* which aggregation kernel the plan selected: "band16/nowrap" (band sweeps, one workgroup per frame: hundreds of frames),
  * "band16chain/nowrap" (band sweeps, the bands of a frame as workgroups of their own), "sweep16/nowrap" (8 paths, block sweep
- * pipeline), "sweep16par/nowrap" (8 paths, parallel sweeps: auto mode for 4..17 frames), "pairs16/nowrap" (4 paths, pair
+ * pipeline), "sweep16par/nowrap" (8 paths, parallel sweeps: auto mode for 4..17 frames), "sweep16mid/nowrap" (8 paths, parallel
+ * sweeps meeting in the middle), "pairs16/nowrap" (4 paths, pair
  * pipeline), "packed16/nowrap", "packed16/wrap" (per-direction line kernels), "generic" (any dMax).  New names may be added:
  * dispatch on these with a default branch. */
 const char* fsgm_epi_plan_kernel_name(fsgm_epi_plan* plan);
