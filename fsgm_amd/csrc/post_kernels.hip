@@ -171,7 +171,9 @@ __global__ __launch_bounds__(256) void vzind2disp_kernel(const double* __restric
 // (:24-46); a cell starts at -1 (:6) and takes an offer when it holds 0 or something smaller, which
 // for maps of non-negative values (vz indices; the precondition of this kernel) is "keep the
 // maximum": atomicMax on the bit patterns (non-negative doubles order like integers, -1.0 is a
-// negative integer).  A NaN value makes every comparison of :24 false: no offer.
+// negative integer).  A NaN value makes every comparison of :24 false: no offer.  -0.0 passes the
+// non-negative check but its pattern is INT64_MIN, below -1.0's: the offer is v + 0.0, which turns -0.0
+// into +0.0 (the MATLAB rule stores -0.0 there; the two compare equal in forward_backward_check.m:27,32).
 // =============================================================================================
 __global__ __launch_bounds__(256) void fill_kernel(double* p, double v, size_t n) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
@@ -191,7 +193,7 @@ __global__ __launch_bounds__(256) void disp_from_first_kernel(const double* __re
     for (int k = 0; k < 4; k++) {
         const double sx = sx0 + (double)(k & 1), sy = sy0 + (double)(k >> 1);                    // :17, four corners :24-46
         if (sx >= 1.0 && sx <= (double)W && sy >= 1.0 && sy <= (double)H)
-            atomicMax((long long*)&D2[f * NP + (size_t)((int)sy - 1) * W + ((int)sx - 1)], __double_as_longlong(v));
+            atomicMax((long long*)&D2[f * NP + (size_t)((int)sy - 1) * W + ((int)sx - 1)], __double_as_longlong(v + 0.0));
     }
 }
 
@@ -298,19 +300,25 @@ __global__ __launch_bounds__(256) void infill_cols_kernel(double* io, int W, int
 // vmf.m:1-14: a 5x5 median per channel (medfilt2, zero padding): the 13th smallest of 25.  One thread
 // per pixel; the minimum of the remaining values is removed 12 times, the 13th minimum is the median
 // (selection by repeated min/max exchange over a register array: no data-dependent indexing).
+// NaN sorts above every number (MATLAB's sort; medfilt2's own rule is unpinned): a NaN enters the
+// selection as +Inf, which leaves the 13th smallest unchanged while at least 13 window values are numbers; with fewer,
+// the 13th smallest is a NaN.
 // =============================================================================================
 __global__ __launch_bounds__(256) void vmf_kernel(const double* __restrict__ in, double* __restrict__ out, int W, int H, int z0) {
     const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
     if (x >= W || y >= H) return;
     const size_t plane = ((size_t)z0 + blockIdx.z) * W * H;
     double w[25];
+    int nans = 0;
 #pragma unroll
     for (int dy = -2; dy <= 2; dy++)
 #pragma unroll
         for (int dx = -2; dx <= 2; dx++) {
             const int yy = y + dy, xx = x + dx;
             const bool in_img = yy >= 0 && yy < H && xx >= 0 && xx < W;
-            w[(dy + 2) * 5 + dx + 2] = in_img ? in[plane + (size_t)(in_img ? yy : 0) * W + (in_img ? xx : 0)] : 0.0;   // zero padding
+            const double v = in_img ? in[plane + (size_t)(in_img ? yy : 0) * W + (in_img ? xx : 0)] : 0.0;   // zero padding
+            nans += isnan(v) ? 1 : 0;
+            w[(dy + 2) * 5 + dx + 2] = isnan(v) ? __longlong_as_double(0x7FF0000000000000LL) : v;
         }
     // partial selection sort: after pass i, w[i] holds the (i+1)-th smallest
 #pragma unroll
@@ -321,7 +329,7 @@ __global__ __launch_bounds__(256) void vmf_kernel(const double* __restrict__ in,
             w[i] = fmin(a, b);
             w[j] = fmax(a, b);
         }
-    out[plane + (size_t)y * W + x] = w[12];
+    out[plane + (size_t)y * W + x] = nans > 12 ? __longlong_as_double(0x7FF8000000000000LL) : w[12];
 }
 
 // =============================================================================================

@@ -155,7 +155,9 @@ void fsgm_oracle_scanline_in_fill(double* out, const double* in, int W, int H) {
 }
 
 /* vmf.m:1-14: medfilt2(flow(:,:,c), [5 5]) per channel.  medfilt2 (toolbox, not in the reference tree)
- * pads with zeros and returns the median of the 25 window values: the 13th smallest. */
+ * pads with zeros and returns the median of the 25 window values: the 13th smallest.  What it does with
+ * NaN is unpinned; the rule here is MATLAB sort's: NaN orders above every number (so the result is NaN
+ * only when fewer than 13 window values are numbers). */
 void fsgm_oracle_vmf(double* out, const double* flow, int W, int H, int channels) {
     const size_t NP = (size_t)W * H;
     for (int c = 0; c < channels; c++)
@@ -171,7 +173,7 @@ void fsgm_oracle_vmf(double* out, const double* flow, int W, int H, int channels
                 for (int i = 1; i < 25; i++) {                         /* insertion sort */
                     const double v = w[i];
                     int j = i - 1;
-                    while (j >= 0 && w[j] > v) { w[j + 1] = w[j]; j--; }
+                    while (j >= 0 && (w[j] > v || (isnan(w[j]) && !isnan(v)))) { w[j + 1] = w[j]; j--; }
                     w[j + 1] = v;
                 }
                 out[c * NP + (size_t)y * W + x] = w[12];

@@ -669,18 +669,22 @@ def calc_disp_from_first(D1, Pd0, nd, O, vMax, n):      # calc_disp_from_first.m
     return D2
 
 
+def matlab_round(v):                                    # round: half away from zero, exact (v - trunc(v) is exact in binary64)
+    t = np.trunc(v)
+    return t + np.copysign(1.0, v) if np.isfinite(v) and abs(v - t) >= 0.5 else t
+
+
 def forward_backward_check(D1, D2, Pd0, nd, O, vMax, n):   # forward_backward_check.m
     rows, cols = D1.shape
     out = D1.copy()
-    rnd = lambda v: np.floor(abs(v) + 0.5) * (1 if v >= 0 else -1)       # MATLAB round: half away from zero
     for j in range(rows):
         for i in range(cols):
             v = out[j, i]
             if np.isnan(v):
                 continue
             disp = vzInd2Disp(v, O[j, i], vMax, n)
-            px, py = rnd(Pd0[0, j, i] + disp * nd[0, j, i]), rnd(Pd0[1, j, i] + disp * nd[1, j, i])
-            if px < 1 or px > cols or py < 1 or py > rows:
+            px, py = matlab_round(Pd0[0, j, i] + disp * nd[0, j, i]), matlab_round(Pd0[1, j, i] + disp * nd[1, j, i])
+            if not (1 <= px <= cols and 1 <= py <= rows):   # :22; a NaN target (MATLAB: an indexing error) counts as outside
                 out[j, i] = np.nan
                 continue
             d2 = D2[int(py) - 1, int(px) - 1]

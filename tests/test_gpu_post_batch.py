@@ -9,6 +9,7 @@ torch = pytest.importorskip("torch")
 import fsgm_amd  # noqa: E402
 from fsgm_amd import torch_ops, synth  # noqa: E402  (torch first, then the library)
 from fsgm_amd._lib import FsgmError  # noqa: E402
+from tests.edge_inputs import oracle_flow_pp_frame  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -162,22 +163,8 @@ def _rgb(W, H, seed):
 
 
 def _oracle_frame(oracle, I0, I1, geo, paths):
-    """test.m:32-54 composed from the oracle's pieces (the MEX's vz index for D1)."""
-    H, W = I0.shape[-2:]
-    pd0, nd, off, rflow = oracle.epipolar_maps(*geo, W, H)
-    if I0.ndim == 3:
-        I0, I1 = oracle.rgb2gray(I0), oracle.rgb2gray(I1)
-    S = oracle.epi_aggregate(oracle.epi_cost(I0, I1, D, VMAX, pd0, nd, off), 6, 64, paths)
-    bestD, minC = oracle.epi_wta(S, W, H, D, 1)
-    D1 = bestD.astype(np.float64) / 256.0
-    flow = np.empty((3, H, W))
-    flow[:2] = oracle.vzind2disp(D1, off, VMAX, D + 1) * nd + rflow
-    flow[2] = 1.0
-    f1, _, _ = oracle.postprocess(D1, pd0, nd, off, VMAX, D + 1, D)
-    flow2 = np.empty((3, H, W))
-    flow2[:2] = oracle.vzind2disp(f1, off, VMAX, D + 1) * nd + rflow
-    flow2[2] = ~np.isnan(f1)
-    return flow, flow2, D1, minC
+    """test.m:32-54 composed from the oracle's pieces (tests/edge_inputs.py) at this file's dMax and vMax."""
+    return oracle_flow_pp_frame(oracle, I0, I1, geo, paths, D, VMAX)
 
 
 @pytest.mark.parametrize("rgb", [False, True])

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 from fsgm_amd import synth, pyramidal_sgm, PyramidPlan
+from tests.edge_inputs import oracle_pyramidal_ng
 
 pytestmark = pytest.mark.gpu
 
@@ -139,20 +140,7 @@ def test_pyramidal_loop_with_the_neighbour_guided_matcher(gpu_lib, oracle, W, H,
     else:
         I0, I1 = g0, g1
     flow, flows, minC = pyramidal_sgm_ng(I0, I1, numPyd, subPixelRefine=sub)
-    # oracle composition
-    lv = [(I0, I1)]
-    for _ in range(1, numPyd):
-        a, b = lv[-1]
-        red = (lambda im: np.stack([oracle.impyramid_reduce(c) for c in im])) if ch == 3 else oracle.impyramid_reduce
-        lv.append((red(a), red(b)))
-    gray = [(oracle.rgb2gray(a), oracle.rgb2gray(b)) if ch == 3 else (a, b) for a, b in lv]
-    hc, wc = gray[-1][0].shape
-    mvPre = np.zeros((2, hc, wc))
-    want = []
-    for l in range(numPyd, 0, -1):
-        mc, fl = oracle.calc_pyd_cost_sgm_ng(gray[l - 1][0], gray[l - 1][1], mvPre, 1, 2, sub, 6, 32)
-        want.append(fl)
-        mvPre = np.ascontiguousarray(2.0 * np.repeat(np.repeat(fl, 2, axis=1), 2, axis=2))
+    want, mc = oracle_pyramidal_ng(oracle, I0, I1, numPyd, 1, 2, sub, 6, 32)        # the oracle composition (tests/edge_inputs.py)
     assert len(flows) == numPyd
     for got, w in zip(flows, want):
         np.testing.assert_array_equal(got, w)
@@ -166,14 +154,12 @@ def test_pyramidal_loop_ng_with_a_wider_search(gpu_lib, oracle):
     W, H = 29, 22
     I0, I1 = synth.image_pair(W, H, 8, seed=3)
     flow, flows, minC = pyramidal_sgm_ng(I0, I1, 2, halfSearchWinSize=2, aggSize=3, P2=64)
-    g = [(I0, I1), (oracle.impyramid_reduce(I0), oracle.impyramid_reduce(I1))]
-    mvPre = np.zeros((2,) + g[1][0].shape)
-    for l in (2, 1):
-        mc, fl = oracle.calc_pyd_cost_sgm_ng(g[l - 1][0], g[l - 1][1], mvPre, 2, 3, 0, 6, 64)
-        np.testing.assert_array_equal(flows[2 - l], fl)
-        mvPre = np.ascontiguousarray(2.0 * np.repeat(np.repeat(fl, 2, axis=1), 2, axis=2))
+    want, mc = oracle_pyramidal_ng(oracle, I0, I1, 2, 2, 3, 0, 6, 64)
+    assert len(flows) == 2
+    for l, (got, w) in zip((2, 1), zip(flows, want)):
+        np.testing.assert_array_equal(got, w, err_msg=f"level {l}")
     np.testing.assert_array_equal(minC, mc)
-    np.testing.assert_array_equal(flow, fl)
+    np.testing.assert_array_equal(flow, want[-1])
 
 
 def test_ng_pyramid_batch_matches_single_pairs(gpu_lib, oracle):

@@ -98,3 +98,18 @@ def test_vmf_vs_scipy_median_filter(oracle):
     for c in range(3):
         np.testing.assert_array_equal(got[c], median_filter(flow[c], size=5, mode="constant", cval=0.0))
     assert got[2, 0, 0] == 0.0 and got[2, 9, 9] == 1.0      # corner: 16 of 25 window cells are padding zeros
+
+
+def test_vmf_nan_sorts_above_every_number(oracle):
+    """medfilt2's NaN rule is unpinned; vmf orders NaN above every number (MATLAB's sort): the median is the 13th smallest of the
+    window, NaN only when fewer than 13 of its 25 values are numbers (a NaN is never skipped, nor a neighbour counted twice)."""
+    flow = np.arange(1.0, 50.0).reshape(1, 7, 7)
+    flow[0, 3, :] = np.nan                                 # centre window: 5 NaN, 20 numbers
+    got = oracle.vmf(flow)
+    w = np.sort(flow[0, 1:6, 1:6].reshape(-1))             # NaN last
+    assert got[0, 3, 3] == w[12] == 32.0
+    flow[0, 1:3, 1:6] = np.nan                             # centre window: 15 NaN (rows 1, 2 and the NaN row 3), 10 numbers
+    assert np.isnan(oracle.vmf(flow)[0, 3, 3])
+    flow = np.full((1, 5, 5), np.nan)
+    flow[0, 2, 2] = 3.0                                    # corner windows: 16 padding zeros, so the median is 0 whatever else
+    assert oracle.vmf(flow)[0, 0, 0] == 0.0 and np.isnan(oracle.vmf(flow)[0, 2, 2])
