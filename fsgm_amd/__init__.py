@@ -9,8 +9,9 @@ Everything computes on the GPU through libfsgm_hip.so (C ABI in include/fsgm.h).
 from .epi import (calc_cost_sgm, calc_cost_sgm_batch, EpiPlan, epipolar_maps, epipolar_sgm_of, epipolar_flow_pp, epipolar_from_F,  # noqa: F401
                   census, sgm, auto_pipeline)
 from .pyd import calc_pyd_cost_sgm, calc_pyd_cost_sgm_batch, PydPlan  # noqa: F401
-from .pyramid import pyramidal_sgm, pyramidal_sgm_ng, pyramidal_sgm_batch, pyramidal_sgm_ng_batch, PyramidPlan, NgPyramidPlan  # noqa: F401
+from .pyramid import (pyramidal_sgm, pyramidal_sgm_ng, pyramidal_sgm_batch, pyramidal_sgm_ng_batch, PyramidPlan, NgPyramidPlan,  # noqa: F401
+                      pyramidal_flow_pp)
 from .post import (speckle_filter, calc_disp_from_first, forward_backward_check, scanline_in_fill, vzInd2Disp, vmf,  # noqa: F401
-                   epi_postprocess, epi_postprocess_batch, PostPlan)
+                   epi_postprocess, epi_postprocess_batch, PostPlan, flow_speckle_filter, flow_fb_check, flow_in_fill)
 from .ng import calc_pyd_cost_sgm_ng, calc_cost_sgm_ng, calc_pyd_cost_sgm_ng_batch, calc_cost_sgm_ng_batch  # noqa: F401
 from ._lib import FsgmError, load as load_library  # noqa: F401

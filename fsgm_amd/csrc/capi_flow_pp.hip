@@ -1,0 +1,398 @@
+// capi_flow_pp.hip -- C ABI of the filtered flow for the pyramidal matchers (include/fsgm.h, "Consistency-checked, filtered
+// flow"): the chain of test.m:45-49 on two-channel flows (flow_post_kernels.hip), its stages on their own, and the pipeline
+// behind a batch-2n run of either pyramidal driver (flow_pp.h).
+#include "capi_common.h"
+#include "capi_device.h"
+#include "flow_post_kernels.h"
+#include "flow_pp.h"
+#include "post_kernels.h"
+#include <math.h>
+#include <mutex>
+#include <vector>
+
+using namespace fsgm;
+
+// Scratch for n flows of W x H.  S holds 4n planes (the speckle-filtered forward and backward flows; later the checked and
+// the filled flow), C 2n planes (the forward-backward result; later the median), parent / size 2n maps, left n maps.
+// The stages' device forms run on `stream`, the pipeline on its pyramid plan's stream: `busy` is recorded behind the last
+// user of the scratch and waited for by the next, whichever stream that is.
+struct fsgm_flow_pp_plan {
+    int W = 0, H = 0, n = 0, device = 0;
+    size_t NP = 0;
+    hipStream_t stream = nullptr;
+    hipEvent_t busy = nullptr;
+    DeviceJoin join;
+    double *dS = nullptr, *dC = nullptr, *dPP = nullptr;         // dPP: flow_pp of the host form, 3n planes, on first use
+    int32_t *dParent = nullptr, *dSize = nullptr, *dLeft = nullptr;
+};
+
+static std::mutex g_flow_mu;
+static std::vector<fsgm_flow_pp_plan*> g_flow_cache;
+
+static void flow_plan_destroy(fsgm_flow_pp_plan* p) {
+    if (!p) return;
+    (void)hipSetDevice(p->device);
+    void* bufs[] = {p->dS, p->dC, p->dPP, p->dParent, p->dSize, p->dLeft};
+    for (void* b : bufs)
+        if (b) (void)hipFree(b);
+    if (p->busy) (void)hipEventDestroy(p->busy);
+    p->join.destroy();
+    if (p->stream) (void)hipStreamDestroy(p->stream);
+    delete p;
+}
+
+extern "C" void fsgm_flow_pp_shutdown_internal(void) {
+    std::lock_guard<std::mutex> lk(g_flow_mu);
+    for (fsgm_flow_pp_plan* p : g_flow_cache) flow_plan_destroy(p);
+    g_flow_cache.clear();
+}
+
+static fsgm_status flow_args(const char* who, int32_t n, int32_t W, int32_t H, bool ok_ptrs, int32_t device) {
+    FSGM_REQUIRE(n >= 1, "%s: n_frames must be >= 1 (got %d)", who, n);
+    FSGM_REQUIRE(ok_ptrs, "%s: null argument", who);
+    FSGM_REQUIRE(W >= 1 && H >= 1, "%s: width/height must be >= 1 (got %d x %d)", who, W, H);
+    if (2.0 * n * W * H >= 2147483648.0)
+        return fail(FSGM_ERR_UNSUPPORTED, "%s: 2 * n_frames * width * height = %.0f reaches 2^31 (32-bit pixel indices)", who, 2.0 * n * W * H);
+    FSGM_DEVICE_SLOT(device);
+    return FSGM_OK;
+}
+
+// the cached plan of this shape (the caller holds g_flow_mu); sets the device
+static fsgm_status flow_plan_get(fsgm_flow_pp_plan** out, int W, int H, int n, int device) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
+        return fail(FSGM_ERR_HIP, "no HIP device available (libfsgm_hip has no CPU fallback)");
+    FSGM_REQUIRE(device >= 0 && device < ndev, "device %d out of range (have %d)", device, ndev);
+    FSGM_HIP(hipSetDevice(device));
+    for (fsgm_flow_pp_plan* q : g_flow_cache)
+        if (q->W == W && q->H == H && q->n == n && q->device == device) {
+            *out = q;
+            return FSGM_OK;
+        }
+    fsgm_flow_pp_plan* p = new fsgm_flow_pp_plan;
+    p->W = W; p->H = H; p->n = n; p->device = device; p->NP = (size_t)W * H;
+    const size_t np = p->NP * n;
+    hipError_t e = hipMalloc((void**)&p->dS, 4 * np * 8);
+    if (e == hipSuccess) e = hipMalloc((void**)&p->dC, 2 * np * 8);
+    if (e == hipSuccess) e = hipMalloc((void**)&p->dParent, 2 * np * 4);
+    if (e == hipSuccess) e = hipMalloc((void**)&p->dSize, 2 * np * 4);
+    if (e == hipSuccess) e = hipMalloc((void**)&p->dLeft, np * 4);
+    if (e == hipSuccess) e = hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&p->busy, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventRecord(p->busy, p->stream);
+    if (e != hipSuccess) {
+        flow_plan_destroy(p);
+        return fail(e == hipErrorOutOfMemory ? FSGM_ERR_NOMEM : FSGM_ERR_HIP, "filtered-flow plan: %s", hipGetErrorString(e));
+    }
+    if (g_flow_cache.size() >= 4) {
+        flow_plan_destroy(g_flow_cache.front());
+        g_flow_cache.erase(g_flow_cache.begin());
+    }
+    g_flow_cache.push_back(p);
+    *out = p;
+    return FSGM_OK;
+}
+
+// ---- the stages on their own ----
+enum FlowStage { STAGE_SPECKLE, STAGE_FB, STAGE_FILL };
+struct StageArgs {
+    const double *in, *b;            // b: fb_check only
+    double* out;
+    double p0, p1;                   // speckle: maxDiff, maxSpeckleSize; fb_check: thr
+};
+
+static void stage_enqueue(hipStream_t st, fsgm_flow_pp_plan* p, FlowStage stage, const StageArgs& a) {
+    switch (stage) {
+    case STAGE_SPECKLE: launch_flow_speckle_filter(st, a.in, a.out, p->dParent, p->dSize, p->W, p->H, a.p0, a.p1, p->n); break;
+    case STAGE_FB: launch_flow_fb_check(st, a.in, a.b, a.out, p->W, p->H, a.p0, p->n); break;
+    case STAGE_FILL: launch_flow_in_fill(st, a.in, a.out, p->dLeft, p->W, p->H, p->n); break;
+    }
+}
+
+static fsgm_status stage_check(const char* who, FlowStage stage, const StageArgs& a) {
+    if (stage == STAGE_FB) FSGM_REQUIRE(a.p0 >= 0.0, "%s: thr must be >= 0 (got %g)", who, a.p0);
+    if (stage == STAGE_SPECKLE) FSGM_REQUIRE(!isnan(a.p0) && !isnan(a.p1), "%s: maxDiff / maxSpeckleSize must be numbers", who);
+    return FSGM_OK;
+}
+
+static fsgm_status stage_host(const char* who, FlowStage stage, int32_t n, int32_t W, int32_t H, StageArgs a, int32_t device) {
+    fsgm_status st = flow_args(who, n, W, H, a.in && a.out && (stage != STAGE_FB || a.b), device);
+    if (st != FSGM_OK || (st = stage_check(who, stage, a)) != FSGM_OK) return st;
+    std::lock_guard<std::mutex> lk(g_flow_mu);
+    fsgm_flow_pp_plan* p;
+    if ((st = flow_plan_get(&p, W, H, n, device)) != FSGM_OK) return st;
+    const size_t bytes = 2 * p->NP * n * 8;
+    double *dIn = p->dS, *dB = p->dS + 2 * p->NP * n;
+    StreamGuard guard(p->stream);   // an early exit drains the stream: queued copies use the caller's memory
+    FSGM_HIP(hipStreamWaitEvent(p->stream, p->busy, 0));
+    FSGM_HIP(hipMemcpyAsync(dIn, a.in, bytes, hipMemcpyHostToDevice, p->stream));
+    if (stage == STAGE_FB) FSGM_HIP(hipMemcpyAsync(dB, a.b, bytes, hipMemcpyHostToDevice, p->stream));
+    double* host_out = a.out;
+    a.in = dIn; a.b = dB; a.out = p->dC;
+    stage_enqueue(p->stream, p, stage, a);
+    FSGM_HIP(hipGetLastError());
+    FSGM_HIP(hipMemcpyAsync(host_out, p->dC, bytes, hipMemcpyDeviceToHost, p->stream));
+    FSGM_HIP(hipEventRecord(p->busy, p->stream));
+    FSGM_HIP(hipStreamSynchronize(p->stream));
+    guard.dismiss();
+    return FSGM_OK;
+}
+
+// sets the device, refuses a captured stream -- before any plan is looked up: nothing may be allocated under a capture
+static fsgm_status device_enter(const char* who, int device, hipStream_t cs) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
+        return fail(FSGM_ERR_HIP, "no HIP device available (libfsgm_hip has no CPU fallback)");
+    FSGM_REQUIRE(device < ndev, "%s: device %d out of range (have %d)", who, device, ndev);
+    FSGM_HIP(hipSetDevice(device));
+    return device_check_stream(cs, who);
+}
+
+static fsgm_status stage_device(const char* who, FlowStage stage, int32_t n, int32_t W, int32_t H, const StageArgs& a, int32_t device,
+                                void* stream) {
+    fsgm_status st = flow_args(who, n, W, H, a.in && a.out && (stage != STAGE_FB || a.b), device);
+    if (st != FSGM_OK || (st = stage_check(who, stage, a)) != FSGM_OK) return st;
+    hipStream_t cs = (hipStream_t)stream;
+    if ((st = device_enter(who, device, cs)) != FSGM_OK) return st;
+    const size_t bytes = 2 * (size_t)W * H * n * 8;
+    if ((st = device_check_ptr(a.in, bytes, 8, device, true, who, stage == STAGE_FB ? "f" : "flow")) != FSGM_OK ||
+        (st = device_check_ptr(a.b, bytes, 8, device, stage == STAGE_FB, who, "b")) != FSGM_OK ||
+        (st = device_check_ptr(a.out, bytes, 8, device, true, who, "the output flow")) != FSGM_OK)
+        return st;
+    if (stage == STAGE_FB) {                                     // no scratch: on the caller's stream itself
+        launch_flow_fb_check(cs, a.in, a.b, a.out, W, H, a.p0, n);
+        FSGM_HIP(hipGetLastError());
+        return FSGM_OK;
+    }
+    std::lock_guard<std::mutex> lk(g_flow_mu);
+    fsgm_flow_pp_plan* p;
+    if ((st = flow_plan_get(&p, W, H, n, device)) != FSGM_OK) return st;
+    if ((st = p->join.ensure()) != FSGM_OK) return st;
+    if ((st = p->join.enter(cs, p->stream)) != FSGM_OK) return st;
+    FSGM_HIP(hipStreamWaitEvent(p->stream, p->busy, 0));
+    stage_enqueue(p->stream, p, stage, a);
+    const hipError_t le = hipGetLastError();
+    (void)hipEventRecord(p->busy, p->stream);
+    const fsgm_status js = p->join.leave(p->stream, cs);
+    if (le != hipSuccess) return fail(FSGM_ERR_HIP, "%s: launch failed: %s", who, hipGetErrorString(le));
+    return js;
+}
+
+// ---- the pipeline ----
+struct FlowOutputs {
+    double *flow_pp, *flow_checked, *flow_fwd, *flow_bwd;
+    uint32_t* minC;
+};
+
+static fsgm_status params_check(const char* who, const fsgm_flow_pp_params* prm) {
+    FSGM_REQUIRE(prm, "%s: null parameters", who);
+    FSGM_REQUIRE(prm->matcher == FSGM_MATCHER_PYD || prm->matcher == FSGM_MATCHER_NG, "%s: matcher must be FSGM_MATCHER_PYD or FSGM_MATCHER_NG (got %d)", who, prm->matcher);
+    FSGM_REQUIRE(prm->fb_thr >= 0.0, "%s: fb_thr must be >= 0 (got %g)", who, prm->fb_thr);
+    FSGM_REQUIRE(prm->island_fraction >= 0.0 && prm->island_fraction <= 1.0, "%s: island_fraction must be in [0, 1] (got %g)", who, prm->island_fraction);
+    FSGM_REQUIRE(!isnan(prm->speckle_max_diff) && !isnan(prm->speckle_max_size), "%s: speckle_max_diff / speckle_max_size must be numbers", who);
+    FSGM_REQUIRE(prm->median == 0 || prm->median == 1, "%s: median must be 0 or 1 (got %d)", who, prm->median);
+    return FSGM_OK;
+}
+
+// the chain on the pair's stream: pair.flow (f then b) -> flow_pp and checked (the plan's when the caller wants none)
+static void chain_enqueue(hipStream_t st, fsgm_flow_pp_plan* p, const fsgm_flow_pp_params& prm, const double* flows, double* flow_pp,
+                          double* checked) {
+    const int W = p->W, H = p->H, n = p->n;
+    const size_t half = 2 * p->NP * n;
+    double *sf = p->dS, *sb = p->dS + half;
+    launch_flow_speckle_filter(st, flows, sf, p->dParent, p->dSize, W, H, prm.speckle_max_diff, prm.speckle_max_size, 2 * n);   // test.m:45, f and b
+    launch_flow_fb_check(st, sf, sb, p->dC, W, H, prm.fb_thr, n);                                                             // :47
+    double* c = checked ? checked : sf;
+    launch_flow_speckle_filter(st, p->dC, c, p->dParent, p->dSize, W, H, INFINITY, (double)((long long)H * W) * prm.island_fraction, n);   // :48
+    launch_flow_in_fill(st, c, sb, p->dLeft, W, H, n);                                                                        // :49
+    const double* g = sb;
+    if (prm.median) {
+        launch_vmf(st, sb, p->dC, W, H, 2 * n);                                                                               // vmf.m
+        g = p->dC;
+    }
+    launch_flow_pack(st, g, c, flow_pp, W, H, n);                                                                             // :53
+}
+
+// frames n..2n-1 of the plan's inputs are frames 0..n-1 with the images swapped (first-half sources: the plan's own or the caller's)
+static fsgm_status swap_enqueue(const PyramidPair& pr, const uint8_t* I0, const uint8_t* I1, size_t bytes) {
+    FSGM_HIP(hipMemcpyAsync(pr.in0 + bytes, I1, bytes, hipMemcpyDeviceToDevice, pr.stream));
+    FSGM_HIP(hipMemcpyAsync(pr.in1 + bytes, I0, bytes, hipMemcpyDeviceToDevice, pr.stream));
+    return FSGM_OK;
+}
+
+static fsgm_status with_pair(int n, int W, int H, int channels, const fsgm_flow_pp_params& prm, const PairBody& body) {
+    if (prm.matcher == FSGM_MATCHER_NG) {
+        fsgm_ng_pyramid_params q = prm.ng;
+        q.device = prm.device;
+        return ng_pyramid_with_pair(n, W, H, channels, &q, body);
+    }
+    fsgm_pyramid_params q = prm.pyd;
+    q.device = prm.device;
+    return pyd_pyramid_with_pair(n, W, H, channels, &q, body);
+}
+
+extern "C" {
+
+fsgm_flow_pp_params fsgm_flow_pp_params_default(int32_t matcher) {
+    fsgm_flow_pp_params p;
+    p.matcher = matcher;
+    p.pyd = fsgm_pyramid_params_default();
+    p.ng = fsgm_ng_pyramid_params_default();
+    p.speckle_max_diff = 2.0;          // test.m:45
+    p.speckle_max_size = 100.0;
+    p.fb_thr = 2.0;                    // forward_backward_check.m:6
+    p.island_fraction = 0.1;           // test.m:48
+    p.median = 0;
+    p.device = 0;
+    return p;
+}
+
+fsgm_status fsgm_flow_speckle_filter_host(int32_t n, const double* flow, int32_t W, int32_t H, double maxDiff, double maxSpeckleSize,
+                                          double* out, int32_t device) {
+    return stage_host("fsgm_flow_speckle_filter", STAGE_SPECKLE, n, W, H, StageArgs{flow, nullptr, out, maxDiff, maxSpeckleSize}, device);
+}
+fsgm_status fsgm_flow_speckle_filter_device(int32_t n, const double* flow, int32_t W, int32_t H, double maxDiff, double maxSpeckleSize,
+                                            double* out, int32_t device, void* stream) {
+    return stage_device("fsgm_flow_speckle_filter_device", STAGE_SPECKLE, n, W, H, StageArgs{flow, nullptr, out, maxDiff, maxSpeckleSize}, device, stream);
+}
+fsgm_status fsgm_flow_fb_check_host(int32_t n, const double* f, const double* b, int32_t W, int32_t H, double thr, double* out, int32_t device) {
+    return stage_host("fsgm_flow_fb_check", STAGE_FB, n, W, H, StageArgs{f, b, out, thr, 0.0}, device);
+}
+fsgm_status fsgm_flow_fb_check_device(int32_t n, const double* f, const double* b, int32_t W, int32_t H, double thr, double* out,
+                                      int32_t device, void* stream) {
+    return stage_device("fsgm_flow_fb_check_device", STAGE_FB, n, W, H, StageArgs{f, b, out, thr, 0.0}, device, stream);
+}
+fsgm_status fsgm_flow_in_fill_host(int32_t n, const double* flow, int32_t W, int32_t H, double* out, int32_t device) {
+    return stage_host("fsgm_flow_in_fill", STAGE_FILL, n, W, H, StageArgs{flow, nullptr, out, 0.0, 0.0}, device);
+}
+fsgm_status fsgm_flow_in_fill_device(int32_t n, const double* flow, int32_t W, int32_t H, double* out, int32_t device, void* stream) {
+    return stage_device("fsgm_flow_in_fill_device", STAGE_FILL, n, W, H, StageArgs{flow, nullptr, out, 0.0, 0.0}, device, stream);
+}
+
+fsgm_status fsgm_pyramidal_flow_pp_host(int32_t n, const uint8_t* I0, const uint8_t* I1, int32_t W, int32_t H, int32_t channels,
+                                        const fsgm_flow_pp_params* prm, double* flow_pp, double* flow_checked, double* flow_fwd,
+                                        double* flow_bwd, uint32_t* minC) {
+    const char* who = "fsgm_pyramidal_flow_pp";
+    fsgm_status st = params_check(who, prm);
+    if (st != FSGM_OK || (st = flow_args(who, n, W, H, I0 && I1 && flow_pp, prm->device)) != FSGM_OK) return st;
+    std::lock_guard<std::mutex> lk(g_flow_mu);
+    fsgm_flow_pp_plan* p;
+    if ((st = flow_plan_get(&p, W, H, n, prm->device)) != FSGM_OK) return st;
+    const size_t np = p->NP * n;
+    if (!p->dPP) {
+        const hipError_t e = hipMalloc((void**)&p->dPP, 3 * np * 8);
+        if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? FSGM_ERR_NOMEM : FSGM_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+    }
+    return with_pair(n, W, H, channels, *prm, [&](const PyramidPair& pr) -> fsgm_status {
+        hipStream_t s = pr.stream;
+        const size_t img = np * channels;
+        StreamGuard guard(s);   // an early exit drains the stream: queued copies use the caller's memory
+        FSGM_HIP(hipMemcpyAsync(pr.in0, I0, img, hipMemcpyHostToDevice, s));
+        FSGM_HIP(hipMemcpyAsync(pr.in1, I1, img, hipMemcpyHostToDevice, s));
+        fsgm_status r = swap_enqueue(pr, pr.in0, pr.in1, img);
+        if (r != FSGM_OK || (r = pr.run(pr.plan)) != FSGM_OK) return r;
+        FSGM_HIP(hipStreamWaitEvent(s, p->busy, 0));
+        chain_enqueue(s, p, *prm, pr.flow, p->dPP, nullptr);
+        FSGM_HIP(hipGetLastError());
+        FSGM_HIP(hipMemcpyAsync(flow_pp, p->dPP, 3 * np * 8, hipMemcpyDeviceToHost, s));
+        if (flow_checked) FSGM_HIP(hipMemcpyAsync(flow_checked, p->dS, 2 * np * 8, hipMemcpyDeviceToHost, s));
+        if (flow_fwd) FSGM_HIP(hipMemcpyAsync(flow_fwd, pr.flow, 2 * np * 8, hipMemcpyDeviceToHost, s));
+        if (flow_bwd) FSGM_HIP(hipMemcpyAsync(flow_bwd, pr.flow + 2 * np, 2 * np * 8, hipMemcpyDeviceToHost, s));
+        if (minC) FSGM_HIP(hipMemcpyAsync(minC, pr.minC, np * 4, hipMemcpyDeviceToHost, s));
+        FSGM_HIP(hipEventRecord(p->busy, s));
+        FSGM_HIP(hipStreamSynchronize(s));
+        guard.dismiss();
+        return FSGM_OK;
+    });
+}
+
+fsgm_status fsgm_pyramidal_flow_pp_device(int32_t n, const uint8_t* I0, const uint8_t* I1, int32_t W, int32_t H, int32_t channels,
+                                          const fsgm_flow_pp_params* prm, double* flow_pp, double* flow_checked, double* flow_fwd,
+                                          double* flow_bwd, uint32_t* minC, void* stream, int32_t* status) {
+    const char* who = "fsgm_pyramidal_flow_pp_device";
+    fsgm_status st = params_check(who, prm);
+    if (st != FSGM_OK || (st = flow_args(who, n, W, H, I0 && I1 && flow_pp, prm->device)) != FSGM_OK) return st;
+    FSGM_REQUIRE(channels == 1 || channels == 3, "%s: channels must be 1 (gray) or 3 (RGB planes), got %d", who, channels);
+    hipStream_t cs = (hipStream_t)stream;
+    const size_t np = (size_t)W * H * n, img = np * channels;
+    const int dev = prm->device;
+    if ((st = device_enter(who, dev, cs)) != FSGM_OK) return st;
+    if ((st = device_check_ptr(I0, img, 1, dev, true, who, "I0")) != FSGM_OK ||
+        (st = device_check_ptr(I1, img, 1, dev, true, who, "I1")) != FSGM_OK ||
+        (st = device_check_ptr(flow_pp, 3 * np * 8, 8, dev, true, who, "flow_pp")) != FSGM_OK ||
+        (st = device_check_ptr(flow_checked, 2 * np * 8, 8, dev, false, who, "flow_checked")) != FSGM_OK ||
+        (st = device_check_ptr(flow_fwd, 2 * np * 8, 8, dev, false, who, "flow_fwd")) != FSGM_OK ||
+        (st = device_check_ptr(flow_bwd, 2 * np * 8, 8, dev, false, who, "flow_bwd")) != FSGM_OK ||
+        (st = device_check_ptr(minC, np * 4, 4, dev, false, who, "minC")) != FSGM_OK ||
+        (st = device_check_ptr(status, 4, 4, dev, false, who, "status")) != FSGM_OK)
+        return st;
+    std::lock_guard<std::mutex> lk(g_flow_mu);
+    fsgm_flow_pp_plan* p;
+    if ((st = flow_plan_get(&p, W, H, n, dev)) != FSGM_OK) return st;
+    return with_pair(n, W, H, channels, *prm, [&](const PyramidPair& pr) -> fsgm_status {
+        hipStream_t s = pr.stream;
+        fsgm_status r;
+        if ((r = pr.join->ensure()) != FSGM_OK || (r = pr.join->enter(cs, s)) != FSGM_OK) return r;
+        auto work = [&]() -> fsgm_status {
+            FSGM_HIP(hipMemcpyAsync(pr.in0, I0, img, hipMemcpyDeviceToDevice, s));
+            FSGM_HIP(hipMemcpyAsync(pr.in1, I1, img, hipMemcpyDeviceToDevice, s));
+            fsgm_status w = swap_enqueue(pr, I0, I1, img);
+            if (w != FSGM_OK || (w = pr.run(pr.plan)) != FSGM_OK) return w;
+            FSGM_HIP(hipStreamWaitEvent(s, p->busy, 0));
+            chain_enqueue(s, p, *prm, pr.flow, flow_pp, flow_checked);
+            FSGM_HIP(hipGetLastError());
+            if (flow_fwd) FSGM_HIP(hipMemcpyAsync(flow_fwd, pr.flow, 2 * np * 8, hipMemcpyDeviceToDevice, s));
+            if (flow_bwd) FSGM_HIP(hipMemcpyAsync(flow_bwd, pr.flow + 2 * np, 2 * np * 8, hipMemcpyDeviceToDevice, s));
+            if (minC) FSGM_HIP(hipMemcpyAsync(minC, pr.minC, np * 4, hipMemcpyDeviceToDevice, s));
+            launch_device_status(s, nullptr, status);
+            FSGM_HIP(hipEventRecord(p->busy, s));
+            return FSGM_OK;
+        };
+        r = work();
+        const fsgm_status js = pr.join->leave(s, cs);            // on every exit: the caller's stream stays ordered behind what was queued
+        return r != FSGM_OK ? r : js;
+    });
+}
+
+fsgm_status fsgm_pyramidal_flow_pp_time(int32_t n, const uint8_t* I0, const uint8_t* I1, int32_t W, int32_t H, int32_t channels,
+                                        const fsgm_flow_pp_params* prm, int32_t warmup, int32_t iters, float* ms) {
+    const char* who = "fsgm_pyramidal_flow_pp_time";
+    fsgm_status st = params_check(who, prm);
+    if (st != FSGM_OK || (st = flow_args(who, n, W, H, I0 && I1 && ms, prm->device)) != FSGM_OK) return st;
+    FSGM_REQUIRE(iters >= 1 && warmup >= 0, "%s: iters must be >= 1 and warmup >= 0", who);
+    std::lock_guard<std::mutex> lk(g_flow_mu);
+    fsgm_flow_pp_plan* p;
+    if ((st = flow_plan_get(&p, W, H, n, prm->device)) != FSGM_OK) return st;
+    const size_t np = p->NP * n;
+    if (!p->dPP) {
+        const hipError_t e = hipMalloc((void**)&p->dPP, 3 * np * 8);
+        if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? FSGM_ERR_NOMEM : FSGM_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
+    }
+    return with_pair(n, W, H, channels, *prm, [&](const PyramidPair& pr) -> fsgm_status {
+        hipStream_t s = pr.stream;
+        const size_t img = np * channels;
+        StreamGuard guard(s);
+        FSGM_HIP(hipMemcpyAsync(pr.in0, I0, img, hipMemcpyHostToDevice, s));
+        FSGM_HIP(hipMemcpyAsync(pr.in1, I1, img, hipMemcpyHostToDevice, s));
+        fsgm_status r = swap_enqueue(pr, pr.in0, pr.in1, img);
+        if (r != FSGM_OK) return r;
+        FSGM_HIP(hipStreamWaitEvent(s, p->busy, 0));
+        for (int part = 0; part < 2; part++) {                   // 0: the level loop, 1: the chain on its flows
+            for (int i = -warmup; i < iters; i++) {
+                if (i == 0) FSGM_HIP(hipEventRecord(pr.ev0, s));
+                if (part == 0 && (r = pr.run(pr.plan)) != FSGM_OK) return r;
+                if (part == 1) chain_enqueue(s, p, *prm, pr.flow, p->dPP, nullptr);
+            }
+            FSGM_HIP(hipGetLastError());
+            FSGM_HIP(hipEventRecord(pr.ev1, s));
+            FSGM_HIP(hipEventSynchronize(pr.ev1));
+            FSGM_HIP(hipEventElapsedTime(&ms[part], pr.ev0, pr.ev1));
+            ms[part] /= iters;
+        }
+        FSGM_HIP(hipEventRecord(p->busy, s));
+        guard.dismiss();
+        return FSGM_OK;
+    });
+}
+
+}  // extern "C"

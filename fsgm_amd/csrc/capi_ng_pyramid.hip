@@ -4,6 +4,7 @@
 // ...) is shared by the levels -- they run in order on one stream -- and sized for the finest.
 #include "ng_kernels.h"
 #include "pyramid_driver.h"
+#include "flow_pp.h"
 
 using namespace fsgm;
 
@@ -65,6 +66,10 @@ struct fsgm_ng_pyramid_plan {
 };
 
 static PyramidCache<fsgm_ng_pyramid_plan> g_ngpyr;
+
+fsgm_status fsgm::ng_pyramid_with_pair(int n, int W, int H, int channels, const fsgm_ng_pyramid_params* prm, const PairBody& body) {
+    return pyramid_with_pair(g_ngpyr, n, W, H, channels, prm, body);
+}
 
 extern "C" {
 

@@ -3,6 +3,7 @@
 #include "pyd_kernels.h"
 #include "pyd_plan.h"
 #include "pyramid_driver.h"
+#include "flow_pp.h"
 
 using namespace fsgm;
 
@@ -53,6 +54,10 @@ struct fsgm_pyramid_plan {
 };
 
 static PyramidCache<fsgm_pyramid_plan> g_pyr;
+
+fsgm_status fsgm::pyd_pyramid_with_pair(int n, int W, int H, int channels, const fsgm_pyramid_params* prm, const PairBody& body) {
+    return pyramid_with_pair(g_pyr, n, W, H, channels, prm, body);
+}
 
 extern "C" {
 

@@ -1,0 +1,13 @@
+// flow_pp.h -- what the filtered-flow pipeline (capi_flow_pp.hip) borrows from the two pyramidal drivers: the cached plan of
+// batch 2n of either matcher, under its device lock (pyramid_driver.h: PyramidPair, pyramid_with_pair)
+#pragma once
+#include "pyramid_driver.h"
+#include <functional>
+
+namespace fsgm {
+
+using PairBody = std::function<fsgm_status(const PyramidPair&)>;
+fsgm_status pyd_pyramid_with_pair(int n, int W, int H, int channels, const fsgm_pyramid_params* prm, const PairBody& body);   // capi_pyramid.hip
+fsgm_status ng_pyramid_with_pair(int n, int W, int H, int channels, const fsgm_ng_pyramid_params* prm, const PairBody& body);  // capi_ng_pyramid.hip
+
+}  // namespace fsgm

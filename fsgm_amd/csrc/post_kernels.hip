@@ -2,6 +2,7 @@
 // The MATLAB originals are sequential (raster scans, a FIFO flood fill, first-come writes); each
 // kernel computes the same result in an order-free form and says why that is the same thing.
 #include "post_kernels.h"
+#include "post_device.h"
 #include "fsgm_device.h"
 #include "../../include/fsgm.h"
 #include <algorithm>
@@ -19,27 +20,6 @@ namespace fsgm {
 // tests y + 1 < H against the frame's own H), so every component lies inside one frame and its root -- the smallest
 // global index -- is the smallest index of its frame: the per-frame results are those of nf single-map runs.
 // =============================================================================================
-__device__ __forceinline__ int ccl_find(int32_t* parent, int i) {
-    int p = __hip_atomic_load(&parent[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    while (p != i) {
-        i = p;
-        p = __hip_atomic_load(&parent[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    return i;
-}
-
-__device__ __forceinline__ void ccl_union(int32_t* parent, int a, int b) {
-    while (true) {
-        a = ccl_find(parent, a);
-        b = ccl_find(parent, b);
-        if (a == b) return;
-        if (a > b) { const int t = a; a = b; b = t; }            // hang the larger root under the smaller
-        const int old = atomicMin(&parent[b], a);
-        if (old == b) return;                                    // b was still a root: joined
-        b = old;                                                 // somebody re-parented b meanwhile: retry from there
-    }
-}
-
 __global__ __launch_bounds__(256) void ccl_init_kernel(int32_t* parent, int32_t* size, int n, const double* __restrict__ img,
                                                       uint32_t* neg) {
     const int i = blockIdx.x * 256 + threadIdx.x;
@@ -75,16 +55,7 @@ __global__ __launch_bounds__(256) void ccl_count_kernel(const double* __restrict
         r = ccl_find(parent, i);
         parent[i] = r;                                           // only ever replaces an ancestor by the root
     }
-    // :48 regionPixelNum.  Neighbouring pixels mostly share a root, and one big region would otherwise
-    // serialise hundreds of thousands of atomics on a single counter: add once per distinct root per wave.
-    unsigned long long todo = __builtin_amdgcn_ballot_w64(valid);
-    while (todo) {
-        const int leader = __builtin_ctzll(todo);
-        const int lr = __builtin_amdgcn_readlane(r, leader);
-        const unsigned long long same = __builtin_amdgcn_ballot_w64(valid && r == lr) & todo;
-        if ((int)(threadIdx.x & 63) == leader) atomicAdd(&size[lr], __popcll(same));
-        todo &= ~same;
-    }
+    ccl_add_sizes(valid, r, size);                               // :48 regionPixelNum
 }
 
 __global__ __launch_bounds__(256) void speckle_apply_kernel(const double* __restrict__ img, double* __restrict__ out,
@@ -230,20 +201,6 @@ __global__ __launch_bounds__(256) void fb_check_map_kernel(const double* __restr
 // A batch: the row pass sees nf*H independent rows; the column pass has one thread per (frame, column), which walks
 // the H rows of its own frame only.
 // =============================================================================================
-__device__ __forceinline__ int block_scan_max_256(int v, int* sh) {      // inclusive, in thread order
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int s = 1; s < 64; s <<= 1) {
-        const int t = __shfl_up(v, s);
-        if (lane >= s) v = max(v, t);
-    }
-    if (lane == 63) sh[wave] = v;
-    __syncthreads();
-    int pre = INT32_MIN;
-    for (int w = 0; w < wave; w++) pre = max(pre, sh[w]);
-    __syncthreads();
-    return max(v, pre);
-}
 __global__ __launch_bounds__(256) void infill_rows_kernel(const double* __restrict__ in, double* __restrict__ out, int32_t* __restrict__ left, int W) {
     __shared__ int sh[4];
     __shared__ int carry_sh;

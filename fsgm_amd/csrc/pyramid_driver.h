@@ -237,6 +237,35 @@ struct PyramidCache {
     }
 };
 
+// A cached plan of batch 2n seen from the flow chain (capi_flow_pp.hip): frames 0..n-1 match I0 -> I1, frames n..2n-1
+// I1 -> I0, so one run of the level loop leaves the forward and the backward flow side by side.
+struct PyramidPair {
+    hipStream_t stream;                          // the plan's: images in, enqueue(), and whatever reads the results
+    hipEvent_t ev0, ev1;
+    DeviceJoin* join;
+    uint8_t *in0, *in1;                          // level-1 inputs, u8 [2n][channels][H][W]: first / second image of each frame
+    const double* flow;                          // level-1 flow  [2n][2][H][W]
+    const uint32_t* minC;                        // level-1 minC  [2n][H][W]
+    void* plan;
+    fsgm_status (*run)(void* plan);              // the level loop on `stream`
+};
+
+// body(pair) under the device's lock, on the cached plan for 2n frames of this shape and these parameters
+template <class P, class Body>
+fsgm_status pyramid_with_pair(PyramidCache<P>& cache, int n, int W, int H, int channels, const typename P::Params* prm, Body&& body) {
+    FSGM_REQUIRE(n >= 1 && n <= P::max_batch / 2, "%s: n_frames must be in 1..%d (got %d)", P::entry_name, P::max_batch / 2, n);
+    FSGM_DEVICE_SLOT(prm->device);
+    std::lock_guard<std::mutex> lk(cache.plans.mu[prm->device]);
+    P* p = nullptr;
+    fsgm_status st;
+    if ((st = cache.get(&p, W, H, channels, prm, 2 * n)) != FSGM_OK) return st;
+    FSGM_HIP(hipSetDevice(prm->device));
+    PyramidCore& c = p->core;
+    const PyramidPair pr{c.stream, c.ev0, c.ev1, &c.join, pyramid_input(p, 0), pyramid_input(p, 1), c.dFlow[0], p->minC(0), p,
+                         [](void* q) { return pyramid_enqueue(static_cast<P*>(q)); }};
+    return body(pr);
+}
+
 // host pointers: one call = the whole loop on a cached plan
 template <class P>
 fsgm_status pyramid_host(PyramidCache<P>& cache, const uint8_t* I0, const uint8_t* I1, int W, int H, int channels,

@@ -32,6 +32,12 @@ def _bind(lib):
     lib.fsgm_post_plan_run.argtypes = [vp, f64, f64, f64]
     lib.fsgm_post_plan_download.argtypes = [vp, vp, vp, vp]
     lib.fsgm_post_plan_time.argtypes = [vp, f64, f64, f64, i32, i32, C.POINTER(C.c_float)]
+    lib.fsgm_flow_speckle_filter_host.argtypes = [i32, vp, i32, i32, f64, f64, vp, i32]
+    lib.fsgm_flow_speckle_filter_device.argtypes = [i32, vp, i32, i32, f64, f64, vp, i32, vp]
+    lib.fsgm_flow_fb_check_host.argtypes = [i32, vp, vp, i32, i32, f64, vp, i32]
+    lib.fsgm_flow_fb_check_device.argtypes = [i32, vp, vp, i32, i32, f64, vp, i32, vp]
+    lib.fsgm_flow_in_fill_host.argtypes = [i32, vp, i32, i32, vp, i32]
+    lib.fsgm_flow_in_fill_device.argtypes = [i32, vp, i32, i32, vp, i32, vp]
     lib._post_bound = True
 
 
@@ -155,6 +161,54 @@ def epi_postprocess_batch(D1, Pd0, normDirect, O, vMax, n, dMax, *, device=0):
     check(lib.fsgm_epi_postprocess_batch_host(N, ptr(D1), W, H, ptr(Pd0), ptr(normDirect), ptr(O), float(vMax), float(n),
                                               float(dMax), ptr(f1), ptr(f2), ptr(disp), int(device)))
     return f1, f2, disp
+
+
+def _flows(flow, name, shape=None):
+    """(flow as a contiguous (N, 2, height, width) float64 batch, whether it came with the leading N)"""
+    flow = np.ascontiguousarray(flow)
+    if flow.dtype != np.float64 or flow.ndim not in (3, 4) or flow.shape[-3] != 2:
+        raise TypeError(f"{name} must be float64 of shape (2, height, width) or (N, 2, height, width)")
+    batched = flow.ndim == 4
+    flow = flow if batched else flow[None]
+    if shape is not None and flow.shape != shape:
+        raise ValueError(f"{name} must have shape {shape if batched else shape[1:]}")
+    return flow, batched
+
+
+def flow_speckle_filter(flow, maxDiff=2, maxSpeckleSize=100, *, device=0):
+    """speckle_filter.m on a two-channel flow (2, height, width), or a batch (N, 2, height, width): two 4-connected valid
+    pixels join when |du| < maxDiff and |dv| < maxDiff; a region of fewer than maxSpeckleSize pixels becomes NaN in both
+    channels.  A pixel is valid when neither channel is NaN."""
+    lib = _lib_bound()
+    flow, batched = _flows(flow, "flow")
+    N, _, H, W = flow.shape
+    out = np.empty_like(flow)
+    check(lib.fsgm_flow_speckle_filter_host(N, ptr(flow), W, H, float(maxDiff), float(maxSpeckleSize), ptr(out), int(device)))
+    return out if batched else out[0]
+
+
+def flow_fb_check(f, b, thr=2.0, *, device=0):
+    """forward_backward_check.m for 2-D flow: a valid pixel p of the forward flow f becomes NaN when p2 = round(p + f(p))
+    (1-based p, round half away from zero) is outside the image, the backward flow b is invalid at p2, or
+    |f_u(p) + b_u(p2)| > thr or |f_v(p) + b_v(p2)| > thr.  f, b (2, height, width) or (N, 2, height, width)."""
+    lib = _lib_bound()
+    f, batched = _flows(f, "f")
+    b, _ = _flows(b, "b", f.shape)
+    N, _, H, W = f.shape
+    out = np.empty_like(f)
+    check(lib.fsgm_flow_fb_check_host(N, ptr(f), ptr(b), W, H, float(thr), ptr(out), int(device)))
+    return out if batched else out[0]
+
+
+def flow_in_fill(flow, *, device=0):
+    """scanline_in_fill.m on both channels of a flow (lines 16 and 19 of the original restored): the holes are those of
+    channel u; channel u of the result equals scanline_in_fill(u).  flow (2, height, width) or (N, 2, height, width)."""
+    lib = _lib_bound()
+    flow, batched = _flows(flow, "flow")
+    N, _, H, W = flow.shape
+    out = np.empty_like(flow)
+    check(lib.fsgm_flow_in_fill_host(N, ptr(flow), W, H, ptr(out), int(device)))
+    return out if batched else out[0]
 
 
 class PostPlan:

@@ -298,3 +298,97 @@ def pyramidal_sgm_ng(I0, I1, numPyd=3, *, device=0, out=None, **overrides):
     ptrs = (C.c_void_p * len(lv))(*[a.ctypes.data for a in lv])
     check(lib.fsgm_pyramidal_sgm_ng_host(ptr(I0), ptr(I1), W, H, ch, C.byref(prm), ptr(flow), ptr(minC), ptrs))
     return flow, lv[::-1], minC
+
+
+class FlowPPParams(C.Structure):
+    _fields_ = [("matcher", C.c_int32), ("pyd", PyramidParams), ("ng", NgPyramidParams), ("speckle_max_diff", C.c_double),
+                ("speckle_max_size", C.c_double), ("fb_thr", C.c_double), ("island_fraction", C.c_double), ("median", C.c_int32),
+                ("device", C.c_int32)]
+
+
+MATCHERS = {"pyd": 0, "ng": 1}
+FLOW_PP_FIELDS = ("speckle_max_diff", "speckle_max_size", "fb_thr", "island_fraction")
+
+
+def _bind_flow_pp(lib):
+    if getattr(lib, "_flow_pp_bound", False):
+        return
+    vp, i32, prm = C.c_void_p, C.c_int32, C.POINTER(FlowPPParams)
+    lib.fsgm_flow_pp_params_default.argtypes = [i32]
+    lib.fsgm_flow_pp_params_default.restype = FlowPPParams
+    lib.fsgm_pyramidal_flow_pp_host.argtypes = [i32, vp, vp, i32, i32, i32, prm, vp, vp, vp, vp, vp]
+    lib.fsgm_pyramidal_flow_pp_device.argtypes = [i32, vp, vp, i32, i32, i32, prm, vp, vp, vp, vp, vp, vp, vp]
+    lib.fsgm_pyramidal_flow_pp_time.argtypes = [i32, vp, vp, i32, i32, i32, prm, i32, i32, C.POINTER(C.c_float)]
+    lib._flow_pp_bound = True
+
+
+def flow_pp_params(lib, matcher, numPyd, device, median, overrides):
+    """fsgm_flow_pp_params for `matcher` ("pyd" / "ng"): the chain's own fields and the matcher's overrides by name."""
+    if matcher not in MATCHERS:
+        raise ValueError(f"matcher must be 'pyd' or 'ng' (got {matcher!r})")
+    _bind_flow_pp(lib)
+    prm = lib.fsgm_flow_pp_params_default(MATCHERS[matcher])
+    prm.device, prm.median = int(device), int(median)
+    sub = prm.pyd if matcher == "pyd" else prm.ng
+    if numPyd is not None:
+        sub.numPyd = int(numPyd)
+    for k, v in overrides.items():
+        if k in FLOW_PP_FIELDS:
+            setattr(prm, k, float(v))
+        elif k not in ("numPyd", "device") and hasattr(sub, k):
+            setattr(sub, k, int(v))
+        else:
+            raise TypeError(f"unknown pyramidal_flow_pp parameter {k!r} for matcher {matcher!r}")
+    return prm
+
+
+def _flow_pp_images(I0, I1, batch):
+    I0, I1 = np.ascontiguousarray(I0), np.ascontiguousarray(I1)
+    if I0.dtype != np.uint8 or I1.dtype != np.uint8 or I0.shape != I1.shape:
+        raise TypeError("I0/I1 must be uint8 images of one shape")
+    if batch is None:                                        # (3, H, W) is one RGB pair unless batch=True says three gray ones
+        batch = I0.ndim == 4 or (I0.ndim == 3 and I0.shape[0] != 3)
+    per = I0.ndim - (1 if batch else 0)
+    if per not in (2, 3) or (per == 3 and I0.shape[-3] != 3):
+        raise TypeError("images must be (height, width) or (3, height, width) per pair")
+    if not batch:
+        I0, I1 = I0[None], I1[None]
+    return I0, I1, 1 if per == 2 else 3, batch
+
+
+def pyramidal_flow_pp(I0, I1, numPyd=None, matcher="pyd", *, median=0, batch=None, device=0, **overrides):
+    """The consistency-checked, filtered flow of a pyramidal matcher (matcher="pyd": pyramidal_sgm, "ng": pyramidal_sgm_ng):
+    forward and backward flow from one run of a plan of twice the batch, then on the device the chain of test.m:45-49 on
+    vectors -- speckle filter of both flows, forward-backward check, island removal, KITTI hole fill, and vmf's median with
+    median=1.  Images (height, width) or RGB (3, height, width) uint8, or a batch with a leading N (batch=None infers it).
+    numPyd=None is the matcher's default.  Keyword overrides: speckle_max_diff (2), speckle_max_size (100), fb_thr (2.0),
+    island_fraction (0.1) and the matcher's own parameters by name.
+
+    Returns (flow_pp, flow_checked, flow_fwd, flow_bwd, minC): flow_pp (.., 3, height, width) float64 -- the filled u, v and
+    the validity plane (1 where flow_checked is a number); flow_checked (.., 2, height, width) with NaN where rejected; the
+    raw flows of both directions; minC (.., height, width) uint32 of the forward run."""
+    lib = _lib.load()
+    _bind(lib)
+    _bind_ng(lib)
+    I0, I1, ch, batched = _flow_pp_images(I0, I1, batch)
+    N, H, W = I0.shape[0], I0.shape[-2], I0.shape[-1]
+    prm = flow_pp_params(lib, matcher, numPyd, device, median, overrides)
+    pp = np.empty((N, 3, H, W), np.float64)
+    checked, fwd, bwd = (np.empty((N, 2, H, W), np.float64) for _ in range(3))
+    minC = np.empty((N, H, W), np.uint32)
+    check(lib.fsgm_pyramidal_flow_pp_host(N, ptr(I0), ptr(I1), W, H, ch, C.byref(prm), ptr(pp), ptr(checked), ptr(fwd), ptr(bwd), ptr(minC)))
+    outs = (pp, checked, fwd, bwd, minC)
+    return outs if batched else tuple(o[0] for o in outs)
+
+
+def pyramidal_flow_pp_time(I0, I1, numPyd=None, matcher="pyd", *, warmup=2, iters=10, batch=None, device=0, **overrides):
+    """(ms of the batch-2N pyramid run, ms of the chain behind it), averages over `iters` runs by HIP events on the plan's stream."""
+    lib = _lib.load()
+    _bind(lib)
+    _bind_ng(lib)
+    I0, I1, ch, _ = _flow_pp_images(I0, I1, batch)
+    N, H, W = I0.shape[0], I0.shape[-2], I0.shape[-1]
+    prm = flow_pp_params(lib, matcher, numPyd, device, 0, overrides)
+    ms = (C.c_float * 2)()
+    check(lib.fsgm_pyramidal_flow_pp_time(N, ptr(I0), ptr(I1), W, H, ch, C.byref(prm), int(warmup), int(iters), ms))
+    return float(ms[0]), float(ms[1])

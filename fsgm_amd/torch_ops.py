@@ -7,9 +7,9 @@ points of include/fsgm.h ("Device-pointer entry points") as torch custom ops and
 
 No host<->device copy and no host wait once a plan for the shape exists: the work is queued behind what the current stream
 already holds, and what is queued on that stream afterwards runs after it.  Ops registered: fsgm::calc_cost_sgm,
-fsgm::epipolar_sgm_of, fsgm::pyramidal_sgm, fsgm::pyramidal_sgm_ng, fsgm::epipolar_flow_pp (each also returns a 0-d int32
+fsgm::epipolar_sgm_of, fsgm::pyramidal_sgm, fsgm::pyramidal_sgm_ng, fsgm::epipolar_flow_pp, fsgm::pyramidal_flow_pp (each also returns a 0-d int32
 status tensor: 0, or FSGM_ERR_HIP when an aggregation hand-off gave up; check=True in the wrappers synchronises and raises
-on it), fsgm::epi_postprocess (status FSGM_ERR_INVALID when a D1 value is negative) and fsgm::vmf.
+on it), fsgm::epi_postprocess (status FSGM_ERR_INVALID when a D1 value is negative), fsgm::vmf and fsgm::flow_fb_check.
 
 One process must hold one HIP runtime.  torch brings its own libamdhip64; libfsgm_hip.so binds to it by soname when torch is
 imported first.  When the library was loaded first, torch afterwards maps a second runtime, and a stream or pointer of one
@@ -26,7 +26,7 @@ from . import _lib
 from ._lib import EpiIn, EpiOut, EpiParams, FsgmError
 from .epi import EpiGeometry, _params as _epi_params
 from .post import _bind as _bind_post
-from .pyramid import PyramidParams, NgPyramidParams, _bind as _bind_pyramid, _bind_ng
+from .pyramid import PyramidParams, NgPyramidParams, FLOW_PP_FIELDS, MATCHERS, _bind as _bind_pyramid, _bind_flow_pp, _bind_ng
 
 FSGM_ERR_INVALID, FSGM_ERR_HIP = 1, 2
 
@@ -55,6 +55,7 @@ _vp, _i32 = C.c_void_p, C.c_int32
 _bind_pyramid(_L)
 _bind_ng(_L)
 _bind_post(_L)
+_bind_flow_pp(_L)
 _L.fsgm_calc_cost_sgm_device.argtypes = [_i32, C.POINTER(EpiIn), C.POINTER(EpiOut), C.POINTER(EpiParams), _vp, _vp]
 _L.fsgm_epi_plan_run_device.argtypes = [_vp, _i32, C.POINTER(EpiIn), C.POINTER(EpiOut), _vp, _vp]
 _L.fsgm_epipolar_sgm_of_device.argtypes = [_i32, _vp, _vp, _i32, _i32, _i32, C.POINTER(EpiGeometry), _i32, C.c_double,
@@ -275,6 +276,51 @@ def _(I0, I1, numPyd, params):
     return _pyramid_fake(I0)
 
 
+@torch.library.custom_op("fsgm::pyramidal_flow_pp", mutates_args=())
+def _pyramidal_flow_pp_op(I0: torch.Tensor, I1: torch.Tensor, matcher: int, numPyd: int, params: List[int], chain: List[float],
+                          median: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    N, H, W = I0.shape[0], I0.shape[-2], I0.shape[-1]
+    ch = 1 if I0.dim() == 3 else 3
+    dev = I0.device
+    prm = _L.fsgm_flow_pp_params_default(int(matcher))
+    sub, fields = (prm.ng, NG_PYRAMID_FIELDS) if matcher == MATCHERS["ng"] else (prm.pyd, PYRAMID_FIELDS)
+    sub.numPyd = int(numPyd)
+    for k, v in zip(fields, params, strict=True):
+        setattr(sub, k, int(v))
+    for k, v in zip(FLOW_PP_FIELDS, chain, strict=True):
+        setattr(prm, k, float(v))
+    prm.median, prm.device = int(median), dev.index
+    I0, I1 = _ready(I0), _ready(I1)
+    pp, checked, fwd, bwd = _f64((N, 3, H, W), dev), _f64((N, 2, H, W), dev), _f64((N, 2, H, W), dev), _f64((N, 2, H, W), dev)
+    minC, status = _u32((N, H, W), dev), _status(dev)
+    _call(dev, _L.fsgm_pyramidal_flow_pp_device, N, _p(I0), _p(I1), W, H, ch, C.byref(prm), _p(pp), _p(checked), _p(fwd), _p(bwd),
+          _p(minC), _stream(dev), _p(status))
+    return pp, checked, fwd, bwd, minC, status
+
+
+@_pyramidal_flow_pp_op.register_fake
+def _(I0, I1, matcher, numPyd, params, chain, median):
+    N, H, W = I0.shape[0], I0.shape[-2], I0.shape[-1]
+    dev = I0.device
+    return (_f64((N, 3, H, W), dev), _f64((N, 2, H, W), dev), _f64((N, 2, H, W), dev), _f64((N, 2, H, W), dev),
+            _u32((N, H, W), dev), _status(dev))
+
+
+@torch.library.custom_op("fsgm::flow_fb_check", mutates_args=())
+def _flow_fb_check_op(f: torch.Tensor, b: torch.Tensor, thr: float) -> torch.Tensor:
+    N, _, H, W = f.shape
+    dev = f.device
+    f, b = _ready(f), _ready(b)
+    out = _f64((N, 2, H, W), dev)
+    _call(dev, _L.fsgm_flow_fb_check_device, N, _p(f), _p(b), W, H, float(thr), _p(out), dev.index, _stream(dev))
+    return out
+
+
+@_flow_fb_check_op.register_fake
+def _(f, b, thr):
+    return torch.empty_like(f, memory_format=torch.contiguous_format)
+
+
 # ---------------------------------------------------------------------------------------------
 # wrappers: the argument order of the numpy API, one frame or a batch with a leading N
 # ---------------------------------------------------------------------------------------------
@@ -445,6 +491,32 @@ def pyramidal_sgm_ng(I0, I1, numPyd=3, *, batch=None, check=False, return_status
     flow, minC, status = torch.ops.fsgm.pyramidal_sgm_ng(I0, I1, int(numPyd), params)
     return _finish((flow, minC), status, batched, check, return_status)
 
+
+def pyramidal_flow_pp(I0, I1, numPyd=None, matcher="pyd", *, median=0, batch=None, check=False, return_status=False, **overrides):
+    """(flow_pp, flow_checked, flow_fwd, flow_bwd, minC) as fsgm_amd.pyramidal_flow_pp, on torch tensors on the GPU; images and
+    batch as pyramidal_sgm.  flow_pp (.., 3, H, W), the flows (.., 2, H, W) float64, minC (.., H, W) uint32."""
+    if matcher not in MATCHERS:
+        raise ValueError(f"matcher must be 'pyd' or 'ng' (got {matcher!r})")
+    I0, I1, batched = _pyramid_images(I0, I1, batch)
+    defaults = _L.fsgm_flow_pp_params_default(MATCHERS[matcher])
+    sub, fields = (defaults.ng, NG_PYRAMID_FIELDS) if matcher == "ng" else (defaults.pyd, PYRAMID_FIELDS)
+    chain = [float(overrides.pop(k, getattr(defaults, k))) for k in FLOW_PP_FIELDS]
+    params = _overrides(fields, sub, overrides, "pyramidal_flow_pp")
+    *outs, status = torch.ops.fsgm.pyramidal_flow_pp(I0, I1, MATCHERS[matcher], int(sub.numPyd if numPyd is None else numPyd), params,
+                                                     chain, int(median))
+    return _finish(outs, status, batched, check, return_status)
+
+
+def flow_fb_check(f, b, thr=2.0):
+    """fsgm_amd.flow_fb_check on torch tensors on the GPU: f, b (2, H, W) or (N, 2, H, W) float64.  No status: the kernel has no
+    failure to report."""
+    _tensors({"f": (f, torch.float64), "b": (b, torch.float64)})
+    if f.dim() not in (3, 4) or f.shape[-3] != 2:
+        raise TypeError(f"f must be (2, H, W) or (N, 2, H, W) (got {tuple(f.shape)})")
+    _shape("b", b, f.shape)
+    if f.dim() == 3:
+        return torch.ops.fsgm.flow_fb_check(f.unsqueeze(0), b.unsqueeze(0), float(thr))[0]
+    return torch.ops.fsgm.flow_fb_check(f, b, float(thr))
 
 def run_tensors(plan, I1, I2, pd0, nd, off, *, check=False, return_status=False):
     """All `plan.batch` frames of an EpiPlan (fsgm_epi_plan_run_device) in the plan's aggregation mode and penalties

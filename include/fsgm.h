@@ -452,6 +452,83 @@ fsgm_status fsgm_post_plan_time(fsgm_post_plan* plan, double vMax, double n, dou
                                 int32_t iters, float* ms_avg);
 
 /* ------------------------------------------------------------------------------------------
+ * Consistency-checked, filtered flow for the pyramidal matchers.
+ *
+ * The chain test.m:45-49 applies to the epipolar method's scalar map, on the two-channel flow of fsgm_pyramidal_sgm /
+ * fsgm_pyramidal_sgm_ng.  The reference has no such layer for 2-D flow: each stage restates the scalar MATLAB function
+ * with the one rule that a vector needs, and those rules are this library's ("Filtered flow for the pyramids").
+ * Flows are f64 [2][height][width], plane 0 = u (x); a pixel is valid when neither channel is NaN.
+ *
+ *  speckle    speckle_filter.m: two 4-connected valid pixels join when |du| < maxDiff and |dv| < maxDiff (strict, :55);
+ *             a region of fewer than maxSpeckleSize pixels becomes NaN in both channels.  Invalid pixels are copied.
+ *  fb_check   forward_backward_check.m with p2 = round(p + f(p)), p in MATLAB's 1-based pixel coordinates, round half away
+ *             from zero (:20): a valid pixel of f becomes NaN (both channels) when p2 is outside the image (:22), b(p2) is
+ *             invalid (:27) or |f_u(p) + b_u(p2)| > thr or |f_v(p) + b_v(p2)| > thr (:32).  b is only read.
+ *  in_fill    scanline_in_fill.m with lines 16 and 19 restored: the holes are those of channel u (input(v, u) of a 3-D
+ *             array is its first plane); interior gaps take min(left, right) per channel, the row ends and then the column
+ *             ends copy the nearest vector.  Channel u of the result is fsgm_scanline_in_fill_host of u alone.
+ *
+ * Every stage takes n_frames contiguous flows.  The host forms copy in and out; the device forms follow the contract of the
+ * device-pointer entry points below (caller's stream, pointer checks, captured streams refused; outputs must not overlap
+ * inputs).  The scratch lives in a plan cached per width, height, n_frames and device.
+ * ------------------------------------------------------------------------------------------ */
+fsgm_status fsgm_flow_speckle_filter_host(int32_t n_frames, const double* flow, int32_t width, int32_t height, double maxDiff,
+                                          double maxSpeckleSize, double* flowFiltered, int32_t device);
+fsgm_status fsgm_flow_speckle_filter_device(int32_t n_frames, const double* flow, int32_t width, int32_t height, double maxDiff,
+                                            double maxSpeckleSize, double* flowFiltered, int32_t device, void* stream);
+fsgm_status fsgm_flow_fb_check_host(int32_t n_frames, const double* f, const double* b, int32_t width, int32_t height,
+                                    double thr, double* fChecked, int32_t device);
+/* needs no scratch: the kernel is queued on `stream` itself */
+fsgm_status fsgm_flow_fb_check_device(int32_t n_frames, const double* f, const double* b, int32_t width, int32_t height,
+                                      double thr, double* fChecked, int32_t device, void* stream);
+fsgm_status fsgm_flow_in_fill_host(int32_t n_frames, const double* flow, int32_t width, int32_t height, double* flowFilled,
+                                   int32_t device);
+fsgm_status fsgm_flow_in_fill_device(int32_t n_frames, const double* flow, int32_t width, int32_t height, double* flowFilled,
+                                     int32_t device, void* stream);
+
+#define FSGM_MATCHER_PYD 0   /* fsgm_pyramidal_sgm     (calc_pyd_cost_sgm per level) */
+#define FSGM_MATCHER_NG  1   /* fsgm_pyramidal_sgm_ng  (calc_pyd_cost_sgm_ng per level) */
+typedef struct {
+    int32_t matcher;                /* FSGM_MATCHER_PYD / FSGM_MATCHER_NG */
+    fsgm_pyramid_params pyd;        /* the matcher's own parameters (numPyd inside); only the struct of `matcher` is read, */
+    fsgm_ng_pyramid_params ng;      /* and its device field is replaced by `device` below */
+    double  speckle_max_diff;       /* 2    (test.m:45) */
+    double  speckle_max_size;       /* 100  (test.m:45) */
+    double  fb_thr;                 /* 2.0  (forward_backward_check.m:6), >= 0 */
+    double  island_fraction;        /* 0.1  (test.m:48: rows*cols/10), in [0, 1] */
+    int32_t median;                 /* 0; 1 = vmf.m's 5x5 median on the filled flow */
+    int32_t device;
+} fsgm_flow_pp_params;
+/* the defaults of fsgm_pyramid_params_default / fsgm_ng_pyramid_params_default and the values above */
+fsgm_flow_pp_params fsgm_flow_pp_params_default(int32_t matcher);
+
+/* n_frames image pairs (I0, I1 u8 [n][channels][H][W]) through one run of a pyramid plan of batch 2n -- frames 0..n-1 match
+ * I0 -> I1 (the forward flow f), frames n..2n-1 match I1 -> I0 (the backward flow b) -- and then, without leaving HBM:
+ *   f, b = speckle(f, b; speckle_max_diff, speckle_max_size)          one launch sequence over the 2n flows
+ *   c    = fb_check(f, b; fb_thr)
+ *   c    = speckle(c; +inf, (double)(H*W) * island_fraction)          island removal: any two valid neighbours join
+ *   g    = in_fill(c);  g = vmf(g) when median
+ * flow_pp      f64 [n][3][H][W]: g's two planes and 1.0 / 0.0 where c is valid / invalid (the layout of
+ *              fsgm_epipolar_flow_pp's flow2)
+ * flow_checked f64 [n][2][H][W] (may be NULL): c, NaN where rejected
+ * flow_fwd, flow_bwd f64 [n][2][H][W] (may be NULL): the raw flows; flow_fwd is what the matcher's own entry point returns
+ * minC         u32 [n][H][W] (may be NULL): level-1 minC of the forward run
+ * The host form uploads each image once and fills the second half of the plan's input on the device.  The device form
+ * follows the device-pointer contract below, except that the images are gathered into the plan's 2n-frame input by two
+ * on-device copies per image (u8, H*W*channels bytes a frame) instead of being read where they lie; status (may be NULL)
+ * receives 0. */
+fsgm_status fsgm_pyramidal_flow_pp_host(int32_t n_frames, const uint8_t* I0, const uint8_t* I1, int32_t width, int32_t height,
+                                        int32_t channels, const fsgm_flow_pp_params* prm, double* flow_pp, double* flow_checked,
+                                        double* flow_fwd, double* flow_bwd, uint32_t* minC);
+fsgm_status fsgm_pyramidal_flow_pp_device(int32_t n_frames, const uint8_t* I0, const uint8_t* I1, int32_t width, int32_t height,
+                                          int32_t channels, const fsgm_flow_pp_params* prm, double* flow_pp, double* flow_checked,
+                                          double* flow_fwd, double* flow_bwd, uint32_t* minC, void* stream, int32_t* status);
+/* average milliseconds (HIP events on the plan's stream, images uploaded once before) of the batch-2n pyramid run, ms[0],
+ * and of the chain behind it, ms[1], for host images as fsgm_pyramidal_flow_pp_host takes them */
+fsgm_status fsgm_pyramidal_flow_pp_time(int32_t n_frames, const uint8_t* I0, const uint8_t* I1, int32_t width, int32_t height,
+                                        int32_t channels, const fsgm_flow_pp_params* prm, int32_t warmup, int32_t iters, float* ms);
+
+/* ------------------------------------------------------------------------------------------
  * calc_pyd_cost_sgm_ng  (calc_pyd_cost_sgm_ng.cpp:448-523; same 8-argument list as the call in
  * ng_sgm.m:20, no caller in the reference tree)
  * ------------------------------------------------------------------------------------------ */
