@@ -210,6 +210,20 @@ def epi_shape(r, hi=96):
     return W, H
 
 
+def epi_random_case(seed, oracle):
+    """The draws of tests/test_gpu_edge_sweeps.py::test_epipolar_random_geometries, in its order (shared with the comparison of
+    the oracle against the reference's compiled code, tests/ref_cases.py): (r, W, H, D, vMax, paths, ch, B, geos, pairs); r is
+    the generator after these draws."""
+    r = rng(3000 + seed)
+    W, H = epi_shape(r, hi=80)
+    D, vMax, paths = int(r.choice([16, 20, 32, 48, 64, 128])), float(r.choice([0.3, 0.5, 0.125])), int(r.choice([4, 8]))
+    ch = int(r.choice([1, 3]))
+    B = int(r.randint(1, 5))
+    geos = [epi_geometry(r, W, H, oracle) for _ in range(B)]
+    pairs = [image_pair(r, W, H, ch, seed=seed * 10 + f) for f in range(B)]
+    return r, W, H, D, vMax, paths, ch, B, geos, pairs
+
+
 # ------------------------------------------------------------------------------------------------ oracle compositions
 def oracle_flow_pp_frame(oracle, I0, I1, geo, paths, D, vMax):
     """test.m:32-54 composed from the oracle's pieces (the MEX's vz index for D1): (flow, flow2, D1, minC)."""

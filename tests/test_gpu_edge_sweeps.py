@@ -335,13 +335,7 @@ def test_ng_batch_half0(gpu_lib, oracle, B):
 # ============================================================================================== C. epipolar maps, flow_pp
 @pytest.mark.parametrize("seed", _seeds(10))
 def test_epipolar_random_geometries(gpu_lib, oracle, seed):
-    r = E.rng(3000 + seed)
-    W, H = E.epi_shape(r, hi=80)
-    D, vMax, paths = int(r.choice([16, 20, 32, 48, 64, 128])), float(r.choice([0.3, 0.5, 0.125])), int(r.choice([4, 8]))
-    ch = int(r.choice([1, 3]))
-    B = int(r.randint(1, 5))
-    geos = [E.epi_geometry(r, W, H, oracle) for _ in range(B)]
-    pairs = [E.image_pair(r, W, H, ch, seed=seed * 10 + f) for f in range(B)]
+    r, W, H, D, vMax, paths, ch, B, geos, pairs = E.epi_random_case(seed, oracle)
     cfg = f"seed {seed} W{W} H{H} D{D} vMax {vMax} paths {paths} ch{ch} B{B} epipoles {[g[4] for g in geos]}"
     for f, g in enumerate(geos):
         msg = f"{cfg} frame {f} epipole {g[2]} direction {g[3]}"

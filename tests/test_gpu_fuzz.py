@@ -9,6 +9,8 @@ import pytest
 from fsgm_amd import synth, EpiPlan, PydPlan, calc_pyd_cost_sgm_ng, calc_cost_sgm_ng
 from fsgm_amd._lib import STAGE_AGGREGATE, STAGE_WTA, STAGE_ALL
 
+from tests import fuzz_configs          # the draws, shared with tests/test_oracle_ref_parity.py
+
 pytestmark = pytest.mark.gpu
 
 # FSGM_FUZZ_SEEDS=N in the environment runs every sweep below with N seeds instead of its default count (a soak run)
@@ -19,22 +21,10 @@ def _seeds(default):
     return range(_SOAK if _SOAK > 0 else default)
 
 
-def _rng(seed):
-    return np.random.RandomState(seed)          # only picks test configurations; data comes from synth
-
-
 @pytest.mark.parametrize("seed", _seeds(24))
 def test_epi_random_configs(gpu_lib, oracle, seed):
-    r = _rng(seed)
-    D = int(r.choice([16, 32, 64, 128, 256, 8, 20, 48, 100]))
-    W, H = int(r.randint(1, 90)), int(r.randint(1, 70))
-    paths = int(r.choice([4, 8]))
-    if r.rand() < 0.6:
-        P1, P2, cmax = int(r.randint(0, 20)), int(r.randint(0, 86)), 24        # no-wrap side
-    else:
-        P1, P2, cmax = int(r.randint(0, 256)), int(r.randint(0, 256)), int(r.choice([24, 255]))
-    sub, vz = int(r.rand() < 0.7), int(r.rand() < 0.5)
-    B = int(r.choice([1, 2, 5]))
+    c = fuzz_configs.epi_config(seed)
+    D, W, H, paths, P1, P2, cmax, sub, vz, B = (c[k] for k in ("D", "W", "H", "paths", "P1", "P2", "cmax", "sub", "vz", "B"))
     vols = [synth.cost_volume(W, H, D, seed=seed * 10 + f, cmax=cmax) for f in range(B)]
     _, _, off = synth.epi_maps(W, H, "general", seed=seed)
     with EpiPlan(W, H, D, B, paths=paths, subpixel=sub, vz_to_disp=vz) as plan:
@@ -60,14 +50,8 @@ def test_epi_random_configs(gpu_lib, oracle, seed):
 @pytest.mark.parametrize("seed", _seeds(16))
 def test_epi_random_tall_configs(gpu_lib, oracle, seed):
     """Tall narrow frames: several bands of the band sweeps (both forms), several row blocks of the block sweeps."""
-    r = _rng(500 + seed)
-    D = int(r.choice([16, 32, 64, 128, 128, 256]))
-    W, H = int(r.randint(1, 40)), int(r.randint(60, 330))
-    paths = int(r.choice([4, 8]))
-    P1 = int(r.randint(0, 30))
-    P2 = int(r.randint(P1, 100))                            # P1 <= P2; some beyond the fused kernels' byte budgets
-    sub, vz = int(r.rand() < 0.7), int(r.rand() < 0.5)
-    B = int(r.choice([1, 2, 3]))
+    c = fuzz_configs.epi_tall_config(seed)
+    D, W, H, paths, P1, P2, sub, vz, B = (c[k] for k in ("D", "W", "H", "paths", "P1", "P2", "sub", "vz", "B"))
     vols = [synth.cost_volume(W, H, D, seed=seed * 10 + f, cmax=24) for f in range(B)]
     for v in vols:
         v[:, ::4, :] = 0
@@ -96,16 +80,12 @@ def test_epi_random_tall_configs(gpu_lib, oracle, seed):
 
 @pytest.mark.parametrize("seed", _seeds(12))
 def test_pyd_random_configs(gpu_lib, oracle, seed):
-    r = _rng(100 + seed)
-    W, H = int(r.randint(1, 60)), int(r.randint(1, 45))
-    rX, rY, rAgg = int(r.randint(0, 6)), int(r.randint(0, 6)), int(r.randint(0, 4))
-    mvW, mvH = W + int(r.randint(0, 4)), H + int(r.randint(0, 4))
-    kind = str(r.choice(["zero", "even", "general"]))
-    P1, P2 = (6, 32) if r.rand() < 0.6 else (int(r.randint(0, 256)), int(r.randint(0, 256)))
-    diag, passes, adaptive, sub = int(r.rand() < 0.7), int(r.choice([1, 2, 2, 3])), int(r.rand() < 0.5), int(r.rand() < 0.5)
+    c = fuzz_configs.pyd_config(seed)
+    W, H, rX, rY, rAgg, mvW, mvH, kind = (c[k] for k in ("W", "H", "rX", "rY", "rAgg", "mvW", "mvH", "kind"))
+    P1, P2, diag, passes, adaptive, sub = (c[k] for k in ("P1", "P2", "diag", "passes", "adaptive", "sub"))
     I1, I2 = synth.image_pair(W, H, 16, seed=seed)
     I1 = (I1.astype(np.int32) * 3 % 256).astype(np.uint8)
-    mv = synth.hint_map(mvW, mvH, kind, seed=seed, amp=float(r.choice([1.5, 4.0, 9.0])))
+    mv = synth.hint_map(mvW, mvH, kind, seed=seed, amp=c["amp"])
     bd, mc, ms, Cv, S = oracle.calc_pyd_cost_sgm(I1, I2, mv, rX, rY, rAgg, sub, P1, P2, diag, passes, adaptive, want_volumes=True)
     with PydPlan(W, H, mvW, mvH, rX, rY, rAgg) as plan:
         plan.set_params(P1, P2, diag, passes, adaptive, sub)
@@ -122,13 +102,9 @@ def test_pyd_random_configs(gpu_lib, oracle, seed):
 
 @pytest.mark.parametrize("seed", _seeds(16))
 def test_ng_random_configs(gpu_lib, oracle, seed):
-    r = _rng(200 + seed)
-    W, H = int(r.randint(1, 40)), int(r.randint(1, 30))
-    mvW, mvH = int(r.randint(1, W + 3)), int(r.randint(1, H + 3))
-    P1, P2 = (6, 32) if r.rand() < 0.5 else (int(r.randint(0, 256)), int(r.randint(0, 256)))
-    half, agg, sub = int(r.choice([0, 1, 1, 2])), int(r.randint(0, 6)), int(r.rand() < 0.5)
+    c = fuzz_configs.ng_config(seed)
+    W, H, mvW, mvH, P1, P2, half, agg, sub, kind, amp = (c[k] for k in ("W", "H", "mvW", "mvH", "P1", "P2", "half", "agg", "sub", "kind", "amp"))
     I1, I2 = synth.image_pair(W, H, 16, seed=seed + 50)
-    kind, amp = str(r.choice(["zero", "even", "int", "general"])), float(r.choice([0.7, 2.0, 6.0]))   # few to many repeated candidates
     mv = synth.hint_map(mvW, mvH, kind, seed=seed, amp=amp)
     mc, fl, _, S = oracle.calc_pyd_cost_sgm_ng(I1, I2, mv, half, agg, sub, P1, P2, want_volumes=True)
     gmc, gfl, gS = calc_pyd_cost_sgm_ng(I1, I2, mv, half, agg, sub, P1, P2, return_sum=True)
