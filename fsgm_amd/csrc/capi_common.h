@@ -1,9 +1,11 @@
-// capi_common.h -- error plumbing shared by the C-ABI translation units
+// capi_common.h -- plumbing shared by the C-ABI translation units: error reporting, device selection, the per-device
+// plan caches and the event timer of the *_time entry points
 #pragma once
 #include <hip/hip_runtime.h>
 #include <mutex>
 #include <stdarg.h>
 #include <stdio.h>
+#include <vector>
 #include "../../include/fsgm.h"
 
 namespace fsgm {
@@ -30,6 +32,29 @@ inline fsgm_status fail(fsgm_status st, const char* fmt, ...) {
         if (!(cond)) return ::fsgm::fail(FSGM_ERR_INVALID, __VA_ARGS__); \
     } while (0)
 
+// NOMEM for an allocation that did not fit, HIP for every other failure; the message is "what: <HIP's text>"
+inline fsgm_status hip_status(hipError_t e, const char* what = nullptr) {
+    if (e == hipSuccess) return FSGM_OK;
+    const fsgm_status st = e == hipErrorOutOfMemory ? FSGM_ERR_NOMEM : FSGM_ERR_HIP;
+    return what ? fail(st, "%s: %s", what, hipGetErrorString(e)) : fail(st, "%s", hipGetErrorString(e));
+}
+
+inline fsgm_status device_count(int* ndev) {
+    *ndev = 0;
+    if (hipGetDeviceCount(ndev) != hipSuccess || *ndev == 0)
+        return fail(FSGM_ERR_HIP, "no HIP device available (libfsgm_hip has no CPU fallback)");
+    return FSGM_OK;
+}
+// makes `device` current (entry points call it after their argument checks: it is the first thing that needs a GPU)
+inline fsgm_status use_device(int device) {
+    int ndev;
+    const fsgm_status st = device_count(&ndev);
+    if (st != FSGM_OK) return st;
+    FSGM_REQUIRE(device >= 0 && device < ndev, "device %d out of range (have %d)", device, ndev);
+    FSGM_HIP(hipSetDevice(device));
+    return FSGM_OK;
+}
+
 // The host-pointer entry points keep their cached plans / arenas PER DEVICE and hold that device's lock for the length of a
 // call: calls on different devices run side by side (fsgm_*_batch_devices_host starts one host thread per device of its
 // list), calls on one device take turns -- they would share the GPU anyway.
@@ -40,6 +65,56 @@ struct PerDevice {
     T v[FSGM_MAX_DEVICES];
 };
 #define FSGM_DEVICE_SLOT(dev) FSGM_REQUIRE((dev) >= 0 && (dev) < ::fsgm::FSGM_MAX_DEVICES, "device %d out of range", (int)(dev))
+
+// The plans behind the host- and device-pointer entry points of one kind: per device the last `cap` that were made, oldest
+// evicted first.  find / insert want the device's lock held (mu(device), for the length of the call that uses the plan).
+template <class P>
+struct PlanCache {
+    PerDevice<std::vector<P*>> plans;
+    const size_t cap;
+    void (*const destroy)(P*);
+    PlanCache(size_t cap_, void (*destroy_)(P*)) : cap(cap_), destroy(destroy_) {}
+
+    std::mutex& mu(int device) { return plans.mu[device]; }
+    template <class Match>
+    P* find(int device, Match&& match) {
+        for (P* p : plans.v[device])
+            if (match(p)) return p;
+        return nullptr;
+    }
+    void insert(int device, P* p) {
+        std::vector<P*>& v = plans.v[device];
+        if (v.size() >= cap) {
+            destroy(v.front());
+            v.erase(v.begin());
+        }
+        v.push_back(p);
+    }
+    void clear() {
+        for (int d = 0; d < FSGM_MAX_DEVICES; d++) {
+            std::lock_guard<std::mutex> lk(plans.mu[d]);
+            for (P* p : plans.v[d]) destroy(p);
+            plans.v[d].clear();
+        }
+    }
+};
+
+// ms_avg = the time of one enqueue() (a callable returning fsgm_status that queues work on `stream`), averaged over
+// `iters` of them behind `warmup` untimed ones
+template <class Enqueue>
+fsgm_status time_enqueues(hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, int warmup, int iters, Enqueue&& enqueue, float* ms_avg) {
+    for (int i = -warmup; i < iters; i++) {
+        if (i == 0) FSGM_HIP(hipEventRecord(ev0, stream));
+        const fsgm_status st = enqueue();
+        if (st != FSGM_OK) return st;
+    }
+    FSGM_HIP(hipEventRecord(ev1, stream));
+    FSGM_HIP(hipEventSynchronize(ev1));
+    float ms = 0;
+    FSGM_HIP(hipEventElapsedTime(&ms, ev0, ev1));
+    *ms_avg = ms / iters;
+    return FSGM_OK;
+}
 
 // Scope guard for host-pointer entry points: work queued on `st` may still read the caller's input
 // buffers or write its output buffers (async copies), so every exit that is not the normal one

@@ -265,9 +265,8 @@ struct LazySet {
     }
 };
 fsgm_status lazy_fail(LazySet& ls, const char* what) {
-    const hipError_t e = ls.err;
     ls.rollback();
-    return fail(e == hipErrorOutOfMemory ? FSGM_ERR_NOMEM : FSGM_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
+    return hip_status(ls.err, what);
 }
 // frame offset into a buffer the selected pipeline may not have
 template <class T> T* frame_at(T* base, size_t off) { return base ? base + off : nullptr; }
@@ -335,11 +334,7 @@ fsgm_status fsgm_epi_plan_create(fsgm_epi_plan** out, int32_t W, int32_t H, int3
         return fail(FSGM_ERR_UNSUPPORTED, "dMax %d exceeds the supported maximum %d", D, FSGM_GENERIC_MAX_D);
     if ((double)W * H * D >= 2147483648.0)
         return fail(FSGM_ERR_UNSUPPORTED, "cost volume %d x %d x %d exceeds 2^31 voxels per frame", W, H, D);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-        return fail(FSGM_ERR_HIP, "no HIP device available (libfsgm_hip has no CPU fallback)");
-    FSGM_REQUIRE(pr.device >= 0 && pr.device < ndev, "device %d out of range (have %d)", pr.device, ndev);
-    FSGM_HIP(hipSetDevice(pr.device));
+    { const fsgm_status ds = use_device(pr.device); if (ds != FSGM_OK) return ds; }
 
     fsgm_epi_plan* p = new fsgm_epi_plan;
     p->W = W; p->H = H; p->D = D; p->batch = batch; p->prm = pr;
@@ -369,8 +364,7 @@ fsgm_status fsgm_epi_plan_create(fsgm_epi_plan** out, int32_t W, int32_t H, int3
     if (e == hipSuccess) e = hipMemsetAsync(p->dOff, 0, B * p->NP * 8, p->stream);
     if (e != hipSuccess) {
         fsgm_epi_plan_destroy(p);
-        return fail(e == hipErrorOutOfMemory ? FSGM_ERR_NOMEM : FSGM_ERR_HIP,
-                    "fsgm_epi_plan_create: %s", hipGetErrorString(e));
+        return hip_status(e, "fsgm_epi_plan_create");
     }
     // once per device: the fused kernels' packed 3-input max / min must be exact u16 operations (epi_sweep.hip)
     {
@@ -963,16 +957,8 @@ fsgm_status fsgm_epi_plan_time(fsgm_epi_plan* p, int32_t stages, int32_t warmup,
     FSGM_REQUIRE(iters >= 1 && warmup >= 0, "fsgm_epi_plan_time: iters must be >= 1");
     FSGM_REQUIRE((stages & ~FSGM_STAGE_ALL) == 0 && stages != 0, "bad stage mask %d", stages);
     FSGM_HIP(hipSetDevice(p->prm.device));
-    for (int i = 0; i < warmup + iters; i++) {
-        if (i == warmup) FSGM_HIP(hipEventRecord(p->ev0, p->stream));
-        fsgm_status st = enqueue(p, stages);
-        if (st != FSGM_OK) return st;
-    }
-    FSGM_HIP(hipEventRecord(p->ev1, p->stream));
-    FSGM_HIP(hipEventSynchronize(p->ev1));
-    float ms = 0;
-    FSGM_HIP(hipEventElapsedTime(&ms, p->ev0, p->ev1));
-    *ms_avg = ms / iters;
+    const fsgm_status st = time_enqueues(p->stream, p->ev0, p->ev1, warmup, iters, [&] { return enqueue(p, stages); }, ms_avg);
+    if (st != FSGM_OK) return st;
     return check_handoff(p);                                     // a timed run that gave up on a hand-off is not a measurement
 }
 
@@ -1030,28 +1016,22 @@ fsgm_status fsgm_measure_copy_bandwidth(int32_t device, size_t bytes, int32_t it
 // host-pointer entry points (the MEX boundary).  Plans are cached per shape for the lifetime of
 // the process so repeated MEX calls do not re-allocate HBM (SURVEY 8b "ownership").
 // ---------------------------------------------------------------------------------------------
-static PerDevice<std::vector<fsgm_epi_plan*>> g_epi;            // cached plans per device, under that device's lock
+static PlanCache<fsgm_epi_plan> g_epi(4, fsgm_epi_plan_destroy);   // cached plans per device (the cap bounds the HBM held by stale shapes)
 
 // The cached plan of this shape for an entry point: `lk` holds its device's lock for the length of the call, the device is current.
 static fsgm_status cached_plan(std::unique_lock<std::mutex>& lk, fsgm_epi_plan** out, int W, int H, int D, int batch,
                                const fsgm_epi_params& pr) {
     FSGM_DEVICE_SLOT(pr.device);
-    lk = std::unique_lock<std::mutex>(g_epi.mu[pr.device]);
-    std::vector<fsgm_epi_plan*>& g_cache = g_epi.v[pr.device];
-    fsgm_epi_plan* p = nullptr;
-    for (fsgm_epi_plan* q : g_cache)
-        if (q->W == W && q->H == H && q->D == D && q->batch == batch && q->prm.paths == pr.paths &&
-            q->prm.device == pr.device && q->prm.fb_check == pr.fb_check && q->prm.vz_to_disp == pr.vz_to_disp)
-            p = q;
+    lk = std::unique_lock<std::mutex>(g_epi.mu(pr.device));
+    fsgm_epi_plan* p = g_epi.find(pr.device, [&](const fsgm_epi_plan* q) {
+        return q->W == W && q->H == H && q->D == D && q->batch == batch && q->prm.paths == pr.paths &&
+               q->prm.fb_check == pr.fb_check && q->prm.vz_to_disp == pr.vz_to_disp;
+    });
     if (p) p->prm = pr;
     else {
         fsgm_status st = fsgm_epi_plan_create(&p, W, H, D, batch, &pr);
         if (st != FSGM_OK) return st;
-        if (g_cache.size() >= 4) {           // bound the HBM held by stale shapes
-            fsgm_epi_plan_destroy(g_cache.front());
-            g_cache.erase(g_cache.begin());
-        }
-        g_cache.push_back(p);
+        g_epi.insert(pr.device, p);
     }
     *out = p;
     FSGM_HIP(hipSetDevice(pr.device));
@@ -1072,11 +1052,7 @@ void fsgm_shutdown(void) {
     fsgm_post_shutdown_internal();
     fsgm_pyramid_shutdown_internal();
     fsgm_pyd_shutdown_internal();
-    for (int d = 0; d < FSGM_MAX_DEVICES; d++) {
-        std::lock_guard<std::mutex> lk(g_epi.mu[d]);
-        for (fsgm_epi_plan* p : g_epi.v[d]) fsgm_epi_plan_destroy(p);
-        g_epi.v[d].clear();
-    }
+    g_epi.clear();
 }
 
 fsgm_status fsgm_calc_cost_sgm_batch_host(int32_t n, const fsgm_epi_in* in, const fsgm_epi_out* out,

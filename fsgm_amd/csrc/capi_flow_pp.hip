@@ -1,14 +1,12 @@
 // capi_flow_pp.hip -- C ABI of the filtered flow for the pyramidal matchers (include/fsgm.h, "Consistency-checked, filtered
-// flow"): the chain of test.m:45-49 on two-channel flows (flow_post_kernels.hip), its stages on their own, and the pipeline
+// flow"): the chain of test.m:45-49 on two-channel flows (post_kernels.hip), its stages on their own, and the pipeline
 // behind a batch-2n run of either pyramidal driver (flow_pp.h).
 #include "capi_common.h"
 #include "capi_device.h"
-#include "flow_post_kernels.h"
 #include "flow_pp.h"
 #include "post_kernels.h"
 #include <math.h>
 #include <mutex>
-#include <vector>
 
 using namespace fsgm;
 
@@ -26,9 +24,6 @@ struct fsgm_flow_pp_plan {
     int32_t *dParent = nullptr, *dSize = nullptr, *dLeft = nullptr;
 };
 
-static std::mutex g_flow_mu;
-static std::vector<fsgm_flow_pp_plan*> g_flow_cache;
-
 static void flow_plan_destroy(fsgm_flow_pp_plan* p) {
     if (!p) return;
     (void)hipSetDevice(p->device);
@@ -41,11 +36,9 @@ static void flow_plan_destroy(fsgm_flow_pp_plan* p) {
     delete p;
 }
 
-extern "C" void fsgm_flow_pp_shutdown_internal(void) {
-    std::lock_guard<std::mutex> lk(g_flow_mu);
-    for (fsgm_flow_pp_plan* p : g_flow_cache) flow_plan_destroy(p);
-    g_flow_cache.clear();
-}
+static PlanCache<fsgm_flow_pp_plan> g_flow(4, flow_plan_destroy);   // cached plans per device, under that device's lock
+
+extern "C" void fsgm_flow_pp_shutdown_internal(void) { g_flow.clear(); }
 
 static fsgm_status flow_args(const char* who, int32_t n, int32_t W, int32_t H, bool ok_ptrs, int32_t device) {
     FSGM_REQUIRE(n >= 1, "%s: n_frames must be >= 1 (got %d)", who, n);
@@ -57,18 +50,13 @@ static fsgm_status flow_args(const char* who, int32_t n, int32_t W, int32_t H, b
     return FSGM_OK;
 }
 
-// the cached plan of this shape (the caller holds g_flow_mu); sets the device
-static fsgm_status flow_plan_get(fsgm_flow_pp_plan** out, int W, int H, int n, int device) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-        return fail(FSGM_ERR_HIP, "no HIP device available (libfsgm_hip has no CPU fallback)");
-    FSGM_REQUIRE(device >= 0 && device < ndev, "device %d out of range (have %d)", device, ndev);
-    FSGM_HIP(hipSetDevice(device));
-    for (fsgm_flow_pp_plan* q : g_flow_cache)
-        if (q->W == W && q->H == H && q->n == n && q->device == device) {
-            *out = q;
-            return FSGM_OK;
-        }
+// The cached plan of this shape for an entry point (flow_args has checked the device's slot): `lk` holds its device's lock
+// for the length of the call, the device is current.
+static fsgm_status flow_plan_get(std::unique_lock<std::mutex>& lk, fsgm_flow_pp_plan** out, int W, int H, int n, int device) {
+    const fsgm_status st = use_device(device);
+    if (st != FSGM_OK) return st;
+    lk = std::unique_lock<std::mutex>(g_flow.mu(device));
+    if ((*out = g_flow.find(device, [&](const fsgm_flow_pp_plan* q) { return q->W == W && q->H == H && q->n == n; }))) return FSGM_OK;
     fsgm_flow_pp_plan* p = new fsgm_flow_pp_plan;
     p->W = W; p->H = H; p->n = n; p->device = device; p->NP = (size_t)W * H;
     const size_t np = p->NP * n;
@@ -82,15 +70,16 @@ static fsgm_status flow_plan_get(fsgm_flow_pp_plan** out, int W, int H, int n, i
     if (e == hipSuccess) e = hipEventRecord(p->busy, p->stream);
     if (e != hipSuccess) {
         flow_plan_destroy(p);
-        return fail(e == hipErrorOutOfMemory ? FSGM_ERR_NOMEM : FSGM_ERR_HIP, "filtered-flow plan: %s", hipGetErrorString(e));
+        return hip_status(e, "filtered-flow plan");
     }
-    if (g_flow_cache.size() >= 4) {
-        flow_plan_destroy(g_flow_cache.front());
-        g_flow_cache.erase(g_flow_cache.begin());
-    }
-    g_flow_cache.push_back(p);
+    g_flow.insert(device, p);
     *out = p;
     return FSGM_OK;
+}
+
+// flow_pp of the host forms, 3n planes, on first use
+static fsgm_status ensure_pp(fsgm_flow_pp_plan* p, const char* who) {
+    return p->dPP ? FSGM_OK : hip_status(hipMalloc((void**)&p->dPP, 3 * p->NP * p->n * 8), who);
 }
 
 // ---- the stages on their own ----
@@ -118,9 +107,9 @@ static fsgm_status stage_check(const char* who, FlowStage stage, const StageArgs
 static fsgm_status stage_host(const char* who, FlowStage stage, int32_t n, int32_t W, int32_t H, StageArgs a, int32_t device) {
     fsgm_status st = flow_args(who, n, W, H, a.in && a.out && (stage != STAGE_FB || a.b), device);
     if (st != FSGM_OK || (st = stage_check(who, stage, a)) != FSGM_OK) return st;
-    std::lock_guard<std::mutex> lk(g_flow_mu);
+    std::unique_lock<std::mutex> lk;
     fsgm_flow_pp_plan* p;
-    if ((st = flow_plan_get(&p, W, H, n, device)) != FSGM_OK) return st;
+    if ((st = flow_plan_get(lk, &p, W, H, n, device)) != FSGM_OK) return st;
     const size_t bytes = 2 * p->NP * n * 8;
     double *dIn = p->dS, *dB = p->dS + 2 * p->NP * n;
     StreamGuard guard(p->stream);   // an early exit drains the stream: queued copies use the caller's memory
@@ -140,12 +129,8 @@ static fsgm_status stage_host(const char* who, FlowStage stage, int32_t n, int32
 
 // sets the device, refuses a captured stream -- before any plan is looked up: nothing may be allocated under a capture
 static fsgm_status device_enter(const char* who, int device, hipStream_t cs) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-        return fail(FSGM_ERR_HIP, "no HIP device available (libfsgm_hip has no CPU fallback)");
-    FSGM_REQUIRE(device < ndev, "%s: device %d out of range (have %d)", who, device, ndev);
-    FSGM_HIP(hipSetDevice(device));
-    return device_check_stream(cs, who);
+    const fsgm_status st = use_device(device);
+    return st != FSGM_OK ? st : device_check_stream(cs, who);
 }
 
 static fsgm_status stage_device(const char* who, FlowStage stage, int32_t n, int32_t W, int32_t H, const StageArgs& a, int32_t device,
@@ -164,9 +149,9 @@ static fsgm_status stage_device(const char* who, FlowStage stage, int32_t n, int
         FSGM_HIP(hipGetLastError());
         return FSGM_OK;
     }
-    std::lock_guard<std::mutex> lk(g_flow_mu);
+    std::unique_lock<std::mutex> lk;
     fsgm_flow_pp_plan* p;
-    if ((st = flow_plan_get(&p, W, H, n, device)) != FSGM_OK) return st;
+    if ((st = flow_plan_get(lk, &p, W, H, n, device)) != FSGM_OK) return st;
     if ((st = p->join.ensure()) != FSGM_OK) return st;
     if ((st = p->join.enter(cs, p->stream)) != FSGM_OK) return st;
     FSGM_HIP(hipStreamWaitEvent(p->stream, p->busy, 0));
@@ -275,14 +260,11 @@ fsgm_status fsgm_pyramidal_flow_pp_host(int32_t n, const uint8_t* I0, const uint
     const char* who = "fsgm_pyramidal_flow_pp";
     fsgm_status st = params_check(who, prm);
     if (st != FSGM_OK || (st = flow_args(who, n, W, H, I0 && I1 && flow_pp, prm->device)) != FSGM_OK) return st;
-    std::lock_guard<std::mutex> lk(g_flow_mu);
+    std::unique_lock<std::mutex> lk;
     fsgm_flow_pp_plan* p;
-    if ((st = flow_plan_get(&p, W, H, n, prm->device)) != FSGM_OK) return st;
+    if ((st = flow_plan_get(lk, &p, W, H, n, prm->device)) != FSGM_OK) return st;
     const size_t np = p->NP * n;
-    if (!p->dPP) {
-        const hipError_t e = hipMalloc((void**)&p->dPP, 3 * np * 8);
-        if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? FSGM_ERR_NOMEM : FSGM_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
-    }
+    if ((st = ensure_pp(p, who)) != FSGM_OK) return st;
     return with_pair(n, W, H, channels, *prm, [&](const PyramidPair& pr) -> fsgm_status {
         hipStream_t s = pr.stream;
         const size_t img = np * channels;
@@ -326,9 +308,9 @@ fsgm_status fsgm_pyramidal_flow_pp_device(int32_t n, const uint8_t* I0, const ui
         (st = device_check_ptr(minC, np * 4, 4, dev, false, who, "minC")) != FSGM_OK ||
         (st = device_check_ptr(status, 4, 4, dev, false, who, "status")) != FSGM_OK)
         return st;
-    std::lock_guard<std::mutex> lk(g_flow_mu);
+    std::unique_lock<std::mutex> lk;
     fsgm_flow_pp_plan* p;
-    if ((st = flow_plan_get(&p, W, H, n, dev)) != FSGM_OK) return st;
+    if ((st = flow_plan_get(lk, &p, W, H, n, dev)) != FSGM_OK) return st;
     return with_pair(n, W, H, channels, *prm, [&](const PyramidPair& pr) -> fsgm_status {
         hipStream_t s = pr.stream;
         fsgm_status r;
@@ -360,14 +342,11 @@ fsgm_status fsgm_pyramidal_flow_pp_time(int32_t n, const uint8_t* I0, const uint
     fsgm_status st = params_check(who, prm);
     if (st != FSGM_OK || (st = flow_args(who, n, W, H, I0 && I1 && ms, prm->device)) != FSGM_OK) return st;
     FSGM_REQUIRE(iters >= 1 && warmup >= 0, "%s: iters must be >= 1 and warmup >= 0", who);
-    std::lock_guard<std::mutex> lk(g_flow_mu);
+    std::unique_lock<std::mutex> lk;
     fsgm_flow_pp_plan* p;
-    if ((st = flow_plan_get(&p, W, H, n, prm->device)) != FSGM_OK) return st;
+    if ((st = flow_plan_get(lk, &p, W, H, n, prm->device)) != FSGM_OK) return st;
     const size_t np = p->NP * n;
-    if (!p->dPP) {
-        const hipError_t e = hipMalloc((void**)&p->dPP, 3 * np * 8);
-        if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? FSGM_ERR_NOMEM : FSGM_ERR_HIP, "%s: %s", who, hipGetErrorString(e));
-    }
+    if ((st = ensure_pp(p, who)) != FSGM_OK) return st;
     return with_pair(n, W, H, channels, *prm, [&](const PyramidPair& pr) -> fsgm_status {
         hipStream_t s = pr.stream;
         const size_t img = np * channels;
@@ -377,18 +356,14 @@ fsgm_status fsgm_pyramidal_flow_pp_time(int32_t n, const uint8_t* I0, const uint
         fsgm_status r = swap_enqueue(pr, pr.in0, pr.in1, img);
         if (r != FSGM_OK) return r;
         FSGM_HIP(hipStreamWaitEvent(s, p->busy, 0));
-        for (int part = 0; part < 2; part++) {                   // 0: the level loop, 1: the chain on its flows
-            for (int i = -warmup; i < iters; i++) {
-                if (i == 0) FSGM_HIP(hipEventRecord(pr.ev0, s));
-                if (part == 0 && (r = pr.run(pr.plan)) != FSGM_OK) return r;
-                if (part == 1) chain_enqueue(s, p, *prm, pr.flow, p->dPP, nullptr);
-            }
+        // ms[0]: the level loop, ms[1]: the chain on its flows
+        if ((r = time_enqueues(s, pr.ev0, pr.ev1, warmup, iters, [&] { return pr.run(pr.plan); }, &ms[0])) != FSGM_OK) return r;
+        r = time_enqueues(s, pr.ev0, pr.ev1, warmup, iters, [&]() -> fsgm_status {
+            chain_enqueue(s, p, *prm, pr.flow, p->dPP, nullptr);
             FSGM_HIP(hipGetLastError());
-            FSGM_HIP(hipEventRecord(pr.ev1, s));
-            FSGM_HIP(hipEventSynchronize(pr.ev1));
-            FSGM_HIP(hipEventElapsedTime(&ms[part], pr.ev0, pr.ev1));
-            ms[part] /= iters;
-        }
+            return FSGM_OK;
+        }, &ms[1]);
+        if (r != FSGM_OK) return r;
         FSGM_HIP(hipEventRecord(p->busy, s));
         guard.dismiss();
         return FSGM_OK;

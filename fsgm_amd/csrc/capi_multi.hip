@@ -27,9 +27,9 @@ struct SlotResult {
 fsgm_status resolve_devices(int32_t n_devices, const int32_t* devices, std::vector<int>& out) {
     FSGM_REQUIRE(n_devices >= 1 && devices, "device list: empty");
     FSGM_REQUIRE(n_devices <= 1024, "device list: %d entries", n_devices);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-        return fail(FSGM_ERR_HIP, "no HIP device available (libfsgm_hip has no CPU fallback)");
+    int ndev;
+    const fsgm_status st = device_count(&ndev);
+    if (st != FSGM_OK) return st;
     out.resize(n_devices);
     for (int i = 0; i < n_devices; i++) {
         FSGM_REQUIRE(devices[i] >= 0, "device list: entry %d is negative (%d)", i, devices[i]);

@@ -60,11 +60,9 @@ struct DevBufs {                       // the arena of `device` for the duration
 };
 
 fsgm_status pick_device(int device) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-        return fail(FSGM_ERR_HIP, "no HIP device available (libfsgm_hip has no CPU fallback)");
-    FSGM_REQUIRE(device >= 0 && device < ndev && device < FSGM_MAX_DEVICES, "device %d out of range (have %d)", device, ndev);
-    FSGM_HIP(hipSetDevice(device));
+    const fsgm_status st = use_device(device);
+    if (st != FSGM_OK) return st;
+    FSGM_DEVICE_SLOT(device);                                    // g_pools
     return FSGM_OK;
 }
 }  // namespace
@@ -111,7 +109,7 @@ fsgm_status fsgm_calc_pyd_cost_sgm_ng_batch_host(int32_t n, const fsgm_ng_in* in
     d.want((void**)&dMinC, B * NP * 4);
     d.want((void**)&dFlow, B * NP * 16);
     for (const NgBuf& b : ng_level_bufs(nb, W, H, (int)D, n)) d.want(b.slot, b.bytes);
-    { const hipError_t e = d.commit(device); if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? FSGM_ERR_NOMEM : FSGM_ERR_HIP, "fsgm_calc_pyd_cost_sgm_ng: %s", hipGetErrorString(e)); }
+    if ((st = hip_status(d.commit(device), "fsgm_calc_pyd_cost_sgm_ng")) != FSGM_OK) return st;
     for (int i = 0; i < n; i++) {
         FSGM_HIP(hipMemcpyAsync(dI1 + i * NP, in[i].I1, NP, hipMemcpyHostToDevice, d.stream));
         FSGM_HIP(hipMemcpyAsync(dI2 + i * NP, in[i].I2, NP, hipMemcpyHostToDevice, d.stream));
@@ -163,7 +161,7 @@ fsgm_status fsgm_calc_cost_sgm_ng_batch_host(int32_t n, const fsgm_otf_in* in, c
     d.want((void**)&dLrow, B * 6 * rowE * sizeof(Cand));
     d.want((void**)&dMinC, B * NP * 4);
     d.want((void**)&dFlow, B * NP * 16);
-    { const hipError_t e = d.commit(device); if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? FSGM_ERR_NOMEM : FSGM_ERR_HIP, "fsgm_calc_cost_sgm_ng: %s", hipGetErrorString(e)); }
+    if ((st = hip_status(d.commit(device), "fsgm_calc_cost_sgm_ng")) != FSGM_OK) return st;
     std::vector<int32_t> drawn;
     for (int i = 0; i < n; i++) {
         const int32_t* rs = in[i].rand_stream;

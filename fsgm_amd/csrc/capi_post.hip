@@ -9,7 +9,6 @@
 #include "post_plan.h"
 #include <math.h>
 #include <mutex>
-#include <vector>
 
 using namespace fsgm;
 
@@ -56,9 +55,7 @@ static fsgm_status ensure_staging(fsgm_post_plan* p) {
     for (double** b : {&p->dIn, &p->dOut, &p->dDisp, &p->dO}) alloc(b, np * 8);
     alloc(&p->dPd0, np * 16);
     alloc(&p->dNd, np * 16);
-    if (e != hipSuccess)
-        return fail(e == hipErrorOutOfMemory ? FSGM_ERR_NOMEM : FSGM_ERR_HIP, "post-processing plan: %s", hipGetErrorString(e));
-    return FSGM_OK;
+    return hip_status(e, "post-processing plan");
 }
 
 extern "C" {
@@ -85,11 +82,8 @@ fsgm_status fsgm::post_plan_create_batch(fsgm_post_plan** out, int32_t W, int32_
     FSGM_REQUIRE(W >= 1 && H >= 1, "width/height must be >= 1 (got %d x %d)", W, H);
     FSGM_REQUIRE(batch >= 1, "n_frames must be >= 1 (got %d)", batch);
     if ((double)W * H * batch >= 2147483648.0) return fail(FSGM_ERR_UNSUPPORTED, "n_frames * width * height reaches 2^31 pixels");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-        return fail(FSGM_ERR_HIP, "no HIP device available (libfsgm_hip has no CPU fallback)");
-    FSGM_REQUIRE(device >= 0 && device < ndev, "device %d out of range (have %d)", device, ndev);
-    FSGM_HIP(hipSetDevice(device));
+    fsgm_status st = use_device(device);
+    if (st != FSGM_OK) return st;
     fsgm_post_plan* p = new fsgm_post_plan;
     p->W = W; p->H = H; p->batch = batch; p->device = device; p->NP = (size_t)W * H;
     const size_t np = p->NP * batch;
@@ -108,9 +102,8 @@ fsgm_status fsgm::post_plan_create_batch(fsgm_post_plan** out, int32_t W, int32_
     if (e == hipSuccess) e = hipEventCreate(&p->ev1);
     if (e != hipSuccess) {
         fsgm_post_plan_destroy(p);
-        return fail(e == hipErrorOutOfMemory ? FSGM_ERR_NOMEM : FSGM_ERR_HIP, "fsgm_post_plan_create: %s", hipGetErrorString(e));
+        return hip_status(e, "fsgm_post_plan_create");
     }
-    fsgm_status st;
     if (staging && (st = ensure_staging(p)) != FSGM_OK) {
         fsgm_post_plan_destroy(p);
         return st;
@@ -165,46 +158,28 @@ fsgm_status fsgm_post_plan_download(fsgm_post_plan* p, double* filterD1, double*
 fsgm_status fsgm_post_plan_time(fsgm_post_plan* p, double vMax, double n, double dMax, int32_t warmup, int32_t iters, float* ms_avg) {
     FSGM_REQUIRE(p && ms_avg && iters >= 1 && warmup >= 0, "fsgm_post_plan_time: bad argument");
     FSGM_HIP(hipSetDevice(p->device));
-    fsgm_status st;
-    for (int i = 0; i < warmup; i++)
-        if ((st = post_enqueue(p, vMax, n, dMax)) != FSGM_OK) return st;
-    FSGM_HIP(hipEventRecord(p->ev0, p->stream));
-    for (int i = 0; i < iters; i++)
-        if ((st = post_enqueue(p, vMax, n, dMax)) != FSGM_OK) return st;
-    FSGM_HIP(hipEventRecord(p->ev1, p->stream));
-    FSGM_HIP(hipEventSynchronize(p->ev1));
-    float ms = 0;
-    FSGM_HIP(hipEventElapsedTime(&ms, p->ev0, p->ev1));
-    *ms_avg = ms / iters;
-    return FSGM_OK;
+    return time_enqueues(p->stream, p->ev0, p->ev1, warmup, iters, [&] { return post_enqueue(p, vMax, n, dMax); }, ms_avg);
 }
 
 // ---- one host-pointer entry point per MATLAB function, on a cached plan ----
-static std::mutex g_post_mu;
-static std::vector<fsgm_post_plan*> g_post_cache;
+static PlanCache<fsgm_post_plan> g_post(4, fsgm_post_plan_destroy);   // cached plans per device, under that device's lock
 
-void fsgm_post_shutdown_internal(void) {
-    std::lock_guard<std::mutex> lk(g_post_mu);
-    for (fsgm_post_plan* p : g_post_cache) fsgm_post_plan_destroy(p);
-    g_post_cache.clear();
-}
+void fsgm_post_shutdown_internal(void) { g_post.clear(); }
 
-// plans per (W, H, batch, device); staging: the host entry points' maps are wanted (added to a cached plan that lacks them)
-static fsgm_status cached_plan(fsgm_post_plan** out, int W, int H, int device, int batch = 1, bool staging = true) {
-    for (fsgm_post_plan* q : g_post_cache)
-        if (q->W == W && q->H == H && q->batch == batch && q->device == device) {
-            *out = q;
-            if (hipSetDevice(device) != hipSuccess) return fail(FSGM_ERR_HIP, "hipSetDevice failed");
-            return staging ? ensure_staging(q) : FSGM_OK;
-        }
-    fsgm_status st = post_plan_create_batch(out, W, H, batch, device, staging);
-    if (st != FSGM_OK) return st;
-    if (g_post_cache.size() >= 4) {
-        fsgm_post_plan_destroy(g_post_cache.front());
-        g_post_cache.erase(g_post_cache.begin());
+// The cached plan per (W, H, batch) for an entry point: `lk` holds its device's lock for the length of the call, the device is
+// current.  staging: the host entry points' maps are wanted (added to a cached plan that lacks them)
+static fsgm_status cached_plan(std::unique_lock<std::mutex>& lk, fsgm_post_plan** out, int W, int H, int device, int batch = 1,
+                               bool staging = true) {
+    FSGM_DEVICE_SLOT(device);
+    lk = std::unique_lock<std::mutex>(g_post.mu(device));
+    *out = g_post.find(device, [&](const fsgm_post_plan* q) { return q->W == W && q->H == H && q->batch == batch; });
+    if (*out) {
+        if (hipSetDevice(device) != hipSuccess) return fail(FSGM_ERR_HIP, "hipSetDevice failed");
+        return staging ? ensure_staging(*out) : FSGM_OK;
     }
-    g_post_cache.push_back(*out);
-    return FSGM_OK;
+    const fsgm_status st = post_plan_create_batch(out, W, H, batch, device, staging);
+    if (st == FSGM_OK) g_post.insert(device, *out);
+    return st;
 }
 
 static fsgm_status require_non_negative(const double* D1, size_t n, const char* fn) {
@@ -216,9 +191,9 @@ static fsgm_status require_non_negative(const double* D1, size_t n, const char* 
 fsgm_status fsgm_speckle_filter_host(const double* image, int32_t W, int32_t H, double maxDiff, double maxSpeckleSize,
                                      double* imageFiltered, int32_t* labelImage, int32_t device) {
     FSGM_REQUIRE(image && imageFiltered, "fsgm_speckle_filter: null argument");
-    std::lock_guard<std::mutex> lk(g_post_mu);
+    std::unique_lock<std::mutex> lk;
     fsgm_post_plan* p;
-    fsgm_status st = cached_plan(&p, W, H, device);
+    fsgm_status st = cached_plan(lk, &p, W, H, device);
     if (st != FSGM_OK) return st;
     StreamGuard guard(p->stream);   // an early exit drains the stream: queued copies use the caller's memory
     FSGM_HIP(hipMemcpyAsync(p->dIn, image, p->NP * 8, hipMemcpyHostToDevice, p->stream));
@@ -238,9 +213,9 @@ fsgm_status fsgm_calc_disp_from_first_host(const double* D1, int32_t W, int32_t 
     FSGM_REQUIRE(W >= 1 && H >= 1, "width/height must be >= 1");
     fsgm_status st = require_non_negative(D1, (size_t)W * H, "fsgm_calc_disp_from_first");
     if (st != FSGM_OK) return st;
-    std::lock_guard<std::mutex> lk(g_post_mu);
+    std::unique_lock<std::mutex> lk;
     fsgm_post_plan* p;
-    if ((st = cached_plan(&p, W, H, device)) != FSGM_OK) return st;
+    if ((st = cached_plan(lk, &p, W, H, device)) != FSGM_OK) return st;
     if ((st = fsgm_post_plan_upload(p, D1, Pd0, normDirect, O)) != FSGM_OK) return st;
     launch_disp_from_first(p->stream, p->dIn, p->dD2, PostGeom{p->dPd0, p->dNd, p->dO, vMax, n}, W, H);
     FSGM_HIP(hipGetLastError());
@@ -255,9 +230,9 @@ fsgm_status fsgm_forward_backward_check_host(const double* D1, const double* D2,
                                              const double* normDirect, const double* O, double vMax, double n,
                                              double* D1checked, int32_t device) {
     FSGM_REQUIRE(D1 && D2 && Pd0 && normDirect && O && D1checked, "fsgm_forward_backward_check: null argument");
-    std::lock_guard<std::mutex> lk(g_post_mu);
+    std::unique_lock<std::mutex> lk;
     fsgm_post_plan* p;
-    fsgm_status st = cached_plan(&p, W, H, device);
+    fsgm_status st = cached_plan(lk, &p, W, H, device);
     if (st != FSGM_OK) return st;
     if ((st = fsgm_post_plan_upload(p, D1, Pd0, normDirect, O)) != FSGM_OK) return st;
     StreamGuard guard(p->stream);   // an early exit drains the stream: queued copies use the caller's memory
@@ -272,9 +247,9 @@ fsgm_status fsgm_forward_backward_check_host(const double* D1, const double* D2,
 
 fsgm_status fsgm_scanline_in_fill_host(const double* input, int32_t W, int32_t H, double* output, int32_t device) {
     FSGM_REQUIRE(input && output, "fsgm_scanline_in_fill: null argument");
-    std::lock_guard<std::mutex> lk(g_post_mu);
+    std::unique_lock<std::mutex> lk;
     fsgm_post_plan* p;
-    fsgm_status st = cached_plan(&p, W, H, device);
+    fsgm_status st = cached_plan(lk, &p, W, H, device);
     if (st != FSGM_OK) return st;
     StreamGuard guard(p->stream);   // an early exit drains the stream: queued copies use the caller's memory
     FSGM_HIP(hipMemcpyAsync(p->dIn, input, p->NP * 8, hipMemcpyHostToDevice, p->stream));
@@ -288,9 +263,9 @@ fsgm_status fsgm_scanline_in_fill_host(const double* input, int32_t W, int32_t H
 
 fsgm_status fsgm_vzind2disp_host(const double* w, const double* O, int32_t W, int32_t H, double vMax, double n, double* D, int32_t device) {
     FSGM_REQUIRE(w && O && D, "fsgm_vzind2disp: null argument");
-    std::lock_guard<std::mutex> lk(g_post_mu);
+    std::unique_lock<std::mutex> lk;
     fsgm_post_plan* p;
-    fsgm_status st = cached_plan(&p, W, H, device);
+    fsgm_status st = cached_plan(lk, &p, W, H, device);
     if (st != FSGM_OK) return st;
     StreamGuard guard(p->stream);   // an early exit drains the stream: queued copies use the caller's memory
     FSGM_HIP(hipMemcpyAsync(p->dIn, w, p->NP * 8, hipMemcpyHostToDevice, p->stream));
@@ -306,9 +281,9 @@ fsgm_status fsgm_vzind2disp_host(const double* w, const double* O, int32_t W, in
 fsgm_status fsgm_vmf_host(const double* flow, int32_t W, int32_t H, int32_t channels, double* flowMed, int32_t device) {
     FSGM_REQUIRE(flow && flowMed, "fsgm_vmf: null argument");
     FSGM_REQUIRE(channels >= 1 && channels <= 3, "fsgm_vmf: 1..3 channels (got %d)", channels);
-    std::lock_guard<std::mutex> lk(g_post_mu);
+    std::unique_lock<std::mutex> lk;
     fsgm_post_plan* p;
-    fsgm_status st = cached_plan(&p, W, H, device);
+    fsgm_status st = cached_plan(lk, &p, W, H, device);
     if (st != FSGM_OK) return st;
     double* src[3] = {p->dIn, p->dA, p->dB};                     // one plane per scratch map
     double* dst[3] = {p->dOut, p->dD2, p->dDisp};
@@ -330,9 +305,9 @@ fsgm_status fsgm_epi_postprocess_host(const double* D1, int32_t W, int32_t H, co
     FSGM_REQUIRE(W >= 1 && H >= 1, "width/height must be >= 1");
     fsgm_status st = require_non_negative(D1, (size_t)W * H, "fsgm_epi_postprocess");
     if (st != FSGM_OK) return st;
-    std::lock_guard<std::mutex> lk(g_post_mu);
+    std::unique_lock<std::mutex> lk;
     fsgm_post_plan* p;
-    if ((st = cached_plan(&p, W, H, device)) != FSGM_OK) return st;
+    if ((st = cached_plan(lk, &p, W, H, device)) != FSGM_OK) return st;
     if ((st = fsgm_post_plan_upload(p, D1, Pd0, normDirect, O)) != FSGM_OK) return st;
     if ((st = post_enqueue(p, vMax, n, dMax)) != FSGM_OK) return st;
     return fsgm_post_plan_download(p, filterD1, filterD2, disp);
@@ -357,9 +332,9 @@ fsgm_status fsgm_epi_postprocess_batch_host(int32_t n_frames, const double* D1, 
     if (st != FSGM_OK) return st;
     const size_t np = (size_t)n_frames * W * H;
     if ((st = require_non_negative(D1, np, who)) != FSGM_OK) return st;
-    std::lock_guard<std::mutex> lk(g_post_mu);
+    std::unique_lock<std::mutex> lk;
     fsgm_post_plan* p;
-    if ((st = cached_plan(&p, W, H, device, n_frames, true)) != FSGM_OK) return st;
+    if ((st = cached_plan(lk, &p, W, H, device, n_frames, true)) != FSGM_OK) return st;
     StreamGuard guard(p->stream);   // an early exit drains the stream: queued copies use the caller's memory
     FSGM_HIP(hipMemcpyAsync(p->dIn, D1, np * 8, hipMemcpyHostToDevice, p->stream));
     FSGM_HIP(hipMemcpyAsync(p->dPd0, Pd0, np * 16, hipMemcpyHostToDevice, p->stream));
@@ -383,9 +358,9 @@ fsgm_status fsgm_epi_postprocess_device(int32_t n_frames, const double* D1, int3
     if (st != FSGM_OK) return st;
     const size_t np = (size_t)n_frames * W * H;
     hipStream_t cs = (hipStream_t)stream;
-    std::lock_guard<std::mutex> lk(g_post_mu);
+    std::unique_lock<std::mutex> lk;
     fsgm_post_plan* p;
-    if ((st = cached_plan(&p, W, H, device, n_frames, false)) != FSGM_OK) return st;
+    if ((st = cached_plan(lk, &p, W, H, device, n_frames, false)) != FSGM_OK) return st;
     if ((st = device_check_stream(cs, who)) != FSGM_OK) return st;
     if ((st = device_check_ptr(D1, np * 8, 8, device, true, who, "D1")) != FSGM_OK ||
         (st = device_check_ptr(Pd0, np * 16, 8, device, true, who, "Pd0")) != FSGM_OK ||

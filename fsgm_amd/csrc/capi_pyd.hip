@@ -39,11 +39,7 @@ fsgm_status fsgm_pyd_plan_create(fsgm_pyd_plan** out, int32_t W, int32_t H, int3
     const long long D = (long long)(2 * rX + 1) * (2 * rY + 1);
     if (D > FSGM_PYD_MAX_D) return fail(FSGM_ERR_UNSUPPORTED, "search window %lld candidates exceeds %d", D, FSGM_PYD_MAX_D);
     if ((double)W * H * D >= 2147483648.0) return fail(FSGM_ERR_UNSUPPORTED, "cost volume exceeds 2^31 voxels per frame");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-        return fail(FSGM_ERR_HIP, "no HIP device available (libfsgm_hip has no CPU fallback)");
-    FSGM_REQUIRE(device >= 0 && device < ndev, "device %d out of range (have %d)", device, ndev);
-    FSGM_HIP(hipSetDevice(device));
+    { const fsgm_status ds = use_device(device); if (ds != FSGM_OK) return ds; }
     fsgm_pyd_plan* p = new fsgm_pyd_plan;
     p->W = W; p->H = H; p->mvW = mvW; p->mvH = mvH; p->rX = rX; p->rY = rY; p->rAgg = rAgg;
     p->batch = batch; p->device = device;
@@ -71,7 +67,7 @@ fsgm_status fsgm_pyd_plan_create(fsgm_pyd_plan** out, int32_t W, int32_t H, int3
     if (e == hipSuccess) e = hipEventCreate(&p->ev1);
     if (e != hipSuccess) {
         fsgm_pyd_plan_destroy(p);
-        return fail(e == hipErrorOutOfMemory ? FSGM_ERR_NOMEM : FSGM_ERR_HIP, "fsgm_pyd_plan_create: %s", hipGetErrorString(e));
+        return hip_status(e, "fsgm_pyd_plan_create");
     }
     // once per device: the row-packed aggregation's 3-input minima (v_pk_minimum3_f16 on denormal patterns, epi_sweep.hip's self-test)
     // must be exact u16 operations; where they are not, the plan has no descriptors and the generic kernels run
@@ -238,30 +234,13 @@ fsgm_status fsgm_pyd_plan_time(fsgm_pyd_plan* p, int32_t stages, int32_t warmup,
     FSGM_REQUIRE(p && ms_avg && iters >= 1 && warmup >= 0, "fsgm_pyd_plan_time: bad argument");
     FSGM_REQUIRE((stages & ~FSGM_STAGE_ALL) == 0 && stages != 0, "bad stage mask %d", stages);
     FSGM_HIP(hipSetDevice(p->device));
-    fsgm_status st;
-    for (int i = 0; i < warmup; i++)
-        if ((st = pyd_enqueue(p, stages, nullptr)) != FSGM_OK) return st;
-    FSGM_HIP(hipEventRecord(p->ev0, p->stream));
-    for (int i = 0; i < iters; i++)
-        if ((st = pyd_enqueue(p, stages, nullptr)) != FSGM_OK) return st;
-    FSGM_HIP(hipEventRecord(p->ev1, p->stream));
-    FSGM_HIP(hipEventSynchronize(p->ev1));
-    float ms = 0;
-    FSGM_HIP(hipEventElapsedTime(&ms, p->ev0, p->ev1));
-    *ms_avg = ms / iters;
-    return FSGM_OK;
+    return time_enqueues(p->stream, p->ev0, p->ev1, warmup, iters, [&] { return pyd_enqueue(p, stages, nullptr); }, ms_avg);
 }
 
 // ---- host-pointer entry points (the calc_pyd_cost_sgm gateway) ----
-static PerDevice<std::vector<fsgm_pyd_plan*>> g_pyd;            // cached plans per device, under that device's lock
+static PlanCache<fsgm_pyd_plan> g_pyd(6, fsgm_pyd_plan_destroy);   // cached plans per device; a pyramid visits ~5 shapes per frame pair
 
-void fsgm_pyd_shutdown_internal(void) {
-    for (int d = 0; d < FSGM_MAX_DEVICES; d++) {
-        std::lock_guard<std::mutex> lk(g_pyd.mu[d]);
-        for (fsgm_pyd_plan* p : g_pyd.v[d]) fsgm_pyd_plan_destroy(p);
-        g_pyd.v[d].clear();
-    }
-}
+void fsgm_pyd_shutdown_internal(void) { g_pyd.clear(); }
 
 fsgm_status fsgm_calc_pyd_cost_sgm_batch_host(int32_t n, const fsgm_pyd_in* in, const fsgm_pyd_out* out, int32_t device) {
     FSGM_REQUIRE(n >= 1 && in && out, "fsgm_calc_pyd_cost_sgm: null argument");
@@ -278,23 +257,17 @@ fsgm_status fsgm_calc_pyd_cost_sgm_batch_host(int32_t n, const fsgm_pyd_in* in, 
                      "frames of one batch must share shape and parameters (frame %d differs)", i);
     }
     FSGM_DEVICE_SLOT(device);
-    std::lock_guard<std::mutex> lk(g_pyd.mu[device]);
-    std::vector<fsgm_pyd_plan*>& g_pyd_cache = g_pyd.v[device];
-    fsgm_pyd_plan* p = nullptr;
-    for (fsgm_pyd_plan* q : g_pyd_cache)
-        if (q->W == a.width && q->H == a.height && q->mvW == a.mvWidth && q->mvH == a.mvHeight &&
-            q->rX == a.halfSearchWinSizeX && q->rY == a.halfSearchWinSizeY && q->rAgg == a.aggHalfWinSize &&
-            q->batch == n && q->device == device) p = q;
+    std::lock_guard<std::mutex> lk(g_pyd.mu(device));
+    fsgm_pyd_plan* p = g_pyd.find(device, [&](const fsgm_pyd_plan* q) {
+        return q->W == a.width && q->H == a.height && q->mvW == a.mvWidth && q->mvH == a.mvHeight &&
+               q->rX == a.halfSearchWinSizeX && q->rY == a.halfSearchWinSizeY && q->rAgg == a.aggHalfWinSize && q->batch == n;
+    });
     fsgm_status st;
     if (!p) {
         st = fsgm_pyd_plan_create(&p, a.width, a.height, a.mvWidth, a.mvHeight, a.halfSearchWinSizeX,
                                   a.halfSearchWinSizeY, a.aggHalfWinSize, n, device);
         if (st != FSGM_OK) return st;
-        if (g_pyd_cache.size() >= 6) {       // a pyramid visits ~5 shapes per frame pair
-            fsgm_pyd_plan_destroy(g_pyd_cache.front());
-            g_pyd_cache.erase(g_pyd_cache.begin());
-        }
-        g_pyd_cache.push_back(p);
+        g_pyd.insert(device, p);
     }
     if ((st = fsgm_pyd_plan_set_params(p, a.P1, a.P2, a.enableDiagnalPath, a.totalPass, a.adpativeP2, a.subPixelRefine)) != FSGM_OK) return st;
     for (int i = 0; i < n; i++)

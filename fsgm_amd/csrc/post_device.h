@@ -1,11 +1,60 @@
-// post_device.h -- device helpers shared by the scalar post-processing kernels (post_kernels.hip) and the two-channel flow
-// chain (flow_post_kernels.hip): the lock-free union-find of the connected-component labelling and the row scan of the
-// hole fill.
+// post_device.h -- device helpers of the post-processing kernels (post_kernels.hip), which run on scalar maps (CH = 1) and
+// on two-channel flows (CH = 2) alike: where a pixel's channels live and the two rules that depend on the channel count
+// ("valid", "joins"), the lock-free union-find of the connected-component labelling and the row scan of the hole fill.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 namespace fsgm {
+
+#define FSGM_NAN __longlong_as_double(0x7FF8000000000000LL)
+
+// A batch of CH-channel maps is f64 [nf][CH][H][W].  Pixel g = f*NP + p of the union-find (frame f, NP = W*H) has its
+// first channel at f*CH*NP + p and channel c c*NP further: for a scalar map that is g itself (no frame needed, i32 as g).
+template <int CH, class I>
+__device__ __forceinline__ auto px_first(I g, I f, size_t NP) {
+    if constexpr (CH == 1) return g;
+    else return (size_t)g + (size_t)f * (CH - 1) * NP;
+}
+template <int CH>
+__device__ __forceinline__ auto px_first(int g, int NP) {
+    if constexpr (CH == 1) return g;
+    else return px_first<CH>(g, g / NP, (size_t)NP);
+}
+
+template <int CH>
+struct Px { double c[CH]; };
+template <int CH>
+__device__ __forceinline__ Px<CH> px_load(const double* first, size_t NP) {
+    Px<CH> v;
+#pragma unroll
+    for (int c = 0; c < CH; c++) v.c[c] = first[c * NP];
+    return v;
+}
+// valid: no channel is NaN (of a loaded pixel; of the pixel whose first channel is at `first`, a later channel read only
+// behind a number)
+template <int CH>
+__device__ __forceinline__ bool px_valid(const double* first, size_t NP) {
+#pragma unroll
+    for (int c = 0; c < CH; c++)
+        if (isnan(first[c * NP])) return false;
+    return true;
+}
+template <int CH>
+__device__ __forceinline__ bool px_valid(const Px<CH>& v) {
+    bool ok = true;
+#pragma unroll
+    for (int c = 0; c < CH; c++) ok = ok && !isnan(v.c[c]);
+    return ok;
+}
+// speckle_filter.m:55 for a valid pixel a and its neighbour b: b valid and |a - b| < maxDiff, in every channel, all strict
+template <int CH>
+__device__ __forceinline__ bool px_joins(const Px<CH>& a, const Px<CH>& b, double maxDiff) {
+    bool j = px_valid(b);
+#pragma unroll
+    for (int c = 0; c < CH; c++) j = j && fabs(__dsub_rn(a.c[c], b.c[c])) < maxDiff;
+    return j;
+}
 
 __device__ __forceinline__ int ccl_find(int32_t* parent, int i) {
     int p = __hip_atomic_load(&parent[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

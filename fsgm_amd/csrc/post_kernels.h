@@ -1,6 +1,7 @@
 // post_kernels.h -- launch interface of the post-processing kernels (the reference's MATLAB functions
 // speckle_filter.m, calc_disp_from_first.m, forward_backward_check.m, scanline_in_fill.m, vzInd2Disp.m;
-// chained by test.m:45-50).  Maps are f64 [H][W], NaN = invalid, x fastest.
+// chained by test.m:45-50), and of the same chain on two-channel flows (at the end).  Maps are f64 [H][W], NaN = invalid,
+// x fastest.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -44,5 +45,23 @@ void launch_epi_pp_flow(hipStream_t st, const double* D1, const double* filterD1
                         const double* rflow, double* flow, double* flow2, int W, int H, int nf, double vMax, double n);
 // one wave: *status = *neg ? FSGM_ERR_INVALID : 0, *neg cleared (status may be null)
 void launch_post_status(hipStream_t st, uint32_t* neg, int32_t* status);
+
+// ---- the same chain on 2-D flows (the scalar vz-index map replaced by a two-channel flow) ----
+// Flows are f64 [nf][2][H][W], plane 0 = u (x), x fastest; a pixel is valid when neither channel is NaN.
+// 2*nf*W*H must stay below 2^31.
+
+// speckle_filter.m with the neighbour test of :55 on vectors: two 4-connected valid pixels join when |du| < maxDiff and
+// |dv| < maxDiff; a region of fewer than maxSpeckleSize pixels becomes NaN in both channels; invalid pixels are copied.
+// parent, size: i32 [nf*H*W] scratch.
+void launch_flow_speckle_filter(hipStream_t st, const double* flow, double* out, int32_t* parent, int32_t* size, int W, int H,
+                                double maxDiff, double maxSpeckleSize, int nf);
+// forward_backward_check.m with the target p2 = round(p + f(p)) (:20, p in MATLAB's 1-based coordinates): a valid pixel of
+// f becomes NaN when p2 leaves the image (:22), b(p2) is invalid (:27) or |f_u + b_u(p2)| > thr or |f_v + b_v(p2)| > thr (:32)
+void launch_flow_fb_check(hipStream_t st, const double* f, const double* b, double* out, int W, int H, double thr, int nf);
+// scanline_in_fill.m with lines 16 and 19 restored: the gaps are those of channel u (input(v, u) of a 3-D array is its first
+// plane), both channels are filled.  left: i32 [nf*H*W] scratch
+void launch_flow_in_fill(hipStream_t st, const double* in, double* out, int32_t* left, int W, int H, int nf);
+// flow_pp [nf][3][H][W]: the two planes of `filled`, and 1.0 where `checked` is valid, else 0.0
+void launch_flow_pack(hipStream_t st, const double* filled, const double* checked, double* flow_pp, int W, int H, int nf);
 
 }  // namespace fsgm

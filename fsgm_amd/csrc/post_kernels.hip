@@ -1,6 +1,8 @@
-// post_kernels.hip -- gfx950 kernels for the reference's post-processing chain (test.m:45-50).
-// The MATLAB originals are sequential (raster scans, a FIFO flood fill, first-come writes); each
-// kernel computes the same result in an order-free form and says why that is the same thing.
+// post_kernels.hip -- gfx950 kernels for the reference's post-processing chain (test.m:45-50), on scalar maps and on
+// two-channel flows.  The MATLAB originals are sequential (raster scans, a FIFO flood fill, first-come writes); each
+// kernel computes the same result in an order-free form and says why that is the same thing.  The speckle filter and the
+// hole fill are one kernel set for both (templated on the channel count); the consistency checks differ in kind -- the
+// epipolar one walks the geometry, the flow one follows the vector -- and stay two kernels.
 #include "post_kernels.h"
 #include "post_device.h"
 #include "fsgm_device.h"
@@ -19,53 +21,60 @@ namespace fsgm {
 // A batch of nf frames is one graph over the global indices f*W*H + i with no edge across a frame boundary (the merge
 // tests y + 1 < H against the frame's own H), so every component lies inside one frame and its root -- the smallest
 // global index -- is the smallest index of its frame: the per-frame results are those of nf single-map runs.
+// The kernels take the channel count CH: a scalar map (CH = 1) or a flow (CH = 2, u then v; a pixel is valid when neither
+// is NaN, and two pixels join when |du| < maxDiff and |dv| < maxDiff -- symmetric too, so the argument above holds unchanged).
+// post_device.h has the three rules that depend on CH.  neg (may be null) is for scalar maps only.
 // =============================================================================================
+template <int CH>
 __global__ __launch_bounds__(256) void ccl_init_kernel(int32_t* parent, int32_t* size, int n, const double* __restrict__ img,
                                                       uint32_t* neg) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i < n) {
         parent[i] = i;
         size[i] = 0;
-        if (neg && img[i] < 0.0) *neg = 1u;                      // every writer stores the same value
+        if constexpr (CH == 1)
+            if (neg && img[i] < 0.0) *neg = 1u;                  // every writer stores the same value
     }
 }
 
 // frames f0 + blockIdx.z
+template <int CH>
 __global__ __launch_bounds__(256) void ccl_merge_kernel(const double* __restrict__ img, int32_t* parent, int W, int H, int f0, double maxDiff) {
     const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
     if (x >= W || y >= H) return;
-    const int i = (f0 + (int)blockIdx.z) * W * H + y * W + x;
-    const double v = img[i];
-    if (isnan(v)) return;
-    if (x + 1 < W) {                                             // :53-60 (and :63-70 seen from the other side)
-        const double r = img[i + 1];
-        if (!isnan(r) && fabs(__dsub_rn(v, r)) < maxDiff) ccl_union(parent, i, i + 1);
-    }
-    if (y + 1 < H) {                                             // :73-80 / :83-90
-        const double b = img[i + W];
-        if (!isnan(b) && fabs(__dsub_rn(v, b)) < maxDiff) ccl_union(parent, i, i + W);
-    }
+    const int NP = W * H, f = f0 + (int)blockIdx.z, g = f * NP + y * W + x;
+    const double* p = img + px_first<CH>(g, f, NP);
+    const Px<CH> v = px_load<CH>(p, NP);
+    if (!px_valid(v)) return;
+    if (x + 1 < W && px_joins(v, px_load<CH>(p + 1, NP), maxDiff)) ccl_union(parent, g, g + 1);          // :53-60 (and :63-70 seen from the other side)
+    if (y + 1 < H && px_joins(v, px_load<CH>(p + W, NP), maxDiff)) ccl_union(parent, g, g + W);          // :73-80 / :83-90
 }
 
-__global__ __launch_bounds__(256) void ccl_count_kernel(const double* __restrict__ img, int32_t* parent, int32_t* size, int n) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    const bool valid = i < n && !isnan(img[i]);
+template <int CH>
+__global__ __launch_bounds__(256) void ccl_count_kernel(const double* __restrict__ img, int32_t* parent, int32_t* size, int NP, int n) {
+    const int g = blockIdx.x * 256 + threadIdx.x;
+    const bool valid = g < n && px_valid<CH>(img + px_first<CH>(g, NP), NP);
     int r = -1;
     if (valid) {
-        r = ccl_find(parent, i);
-        parent[i] = r;                                           // only ever replaces an ancestor by the root
+        r = ccl_find(parent, g);
+        parent[g] = r;                                           // only ever replaces an ancestor by the root
     }
     ccl_add_sizes(valid, r, size);                               // :48 regionPixelNum
 }
 
+template <int CH>
 __global__ __launch_bounds__(256) void speckle_apply_kernel(const double* __restrict__ img, double* __restrict__ out,
                                                             const int32_t* __restrict__ parent, const int32_t* __restrict__ size,
-                                                            int n, double maxSpeckleSize) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const double v = img[i];
-    const bool drop = !isnan(v) && (double)size[parent[i]] < maxSpeckleSize;      // :94
-    out[i] = drop ? __longlong_as_double(0x7FF8000000000000LL) : v;
+                                                            int NP, int n, double maxSpeckleSize) {
+    const int g = blockIdx.x * 256 + threadIdx.x;
+    if (g >= n) return;
+    const auto q = px_first<CH>(g, NP);
+    Px<CH> v = px_load<CH>(img + q, NP);
+    if (px_valid(v) && (double)size[parent[g]] < maxSpeckleSize)                                         // :94
+#pragma unroll
+        for (int c = 0; c < CH; c++) v.c[c] = FSGM_NAN;
+#pragma unroll
+    for (int c = 0; c < CH; c++) out[q + c * NP] = v.c[c];
 }
 
 // labels: rank of each region's root among all roots, in index order (3 small kernels: per-block
@@ -174,20 +183,45 @@ __global__ __launch_bounds__(256) void fb_check_map_kernel(const double* __restr
     const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
     if (x >= W || y >= H) return;
     const size_t NP = (size_t)W * H, f = (size_t)f0 + blockIdx.z, p = f * NP + (size_t)y * W + x, q = f * NP + p;
-    const double nan = __longlong_as_double(0x7FF8000000000000LL);
     const double v = D1[p];
     double r = v;
     if (!isnan(v)) {                                                                             // :12
         const double disp = vzind2disp(v, g.O[p], g.vMax, g.n);                                  // :15
         const double p2x = round(__dadd_rn(g.Pd0[q], __dmul_rn(disp, g.nd[q])));                 // :17-20, half away from zero
         const double p2y = round(__dadd_rn(g.Pd0[NP + q], __dmul_rn(disp, g.nd[NP + q])));
-        if (!(p2x >= 1.0 && p2x <= (double)W && p2y >= 1.0 && p2y <= (double)H)) r = nan;        // :22 (a NaN target fails every test of :22 and reads D2(NaN): MATLAB errors; here: invalid)
+        if (!(p2x >= 1.0 && p2x <= (double)W && p2y >= 1.0 && p2y <= (double)H)) r = FSGM_NAN;        // :22 (a NaN target fails every test of :22 and reads D2(NaN): MATLAB errors; here: invalid)
         else {
             const double d2 = D2[f * NP + (size_t)((int)p2y - 1) * W + ((int)p2x - 1)];
-            if (d2 == -1.0 || fabs(__dsub_rn(v, d2)) > 2.0) r = nan;                             // :27,:32 (thr :6)
+            if (d2 == -1.0 || fabs(__dsub_rn(v, d2)) > 2.0) r = FSGM_NAN;                             // :27,:32 (thr :6)
         }
     }
     out[p] = r;
+}
+
+// =============================================================================================
+// forward_backward_check.m:1-39 with the epipolar walk (:15-18) replaced by the flow vector: each pixel decides about
+// itself only.  The two sums of :32 are one fp64 add each (no product next to them: nothing to contract).
+// =============================================================================================
+__global__ __launch_bounds__(256) void flow_fb_check_kernel(const double* __restrict__ fw, const double* __restrict__ bw,
+                                                            double* __restrict__ out, int W, int H, int f0, double thr) {
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (x >= W || y >= H) return;
+    const size_t NP = (size_t)W * H, base = ((size_t)f0 + blockIdx.z) * 2 * NP, q = base + (size_t)y * W + x;
+    const double u = fw[q], v = fw[q + NP];
+    bool keep = true;
+    if (!isnan(u) && !isnan(v)) {                                                                        // :12
+        const double p2x = round(__dadd_rn((double)(x + 1), u));                                         // :20, half away from zero
+        const double p2y = round(__dadd_rn((double)(y + 1), v));
+        if (!(p2x >= 1.0 && p2x <= (double)W && p2y >= 1.0 && p2y <= (double)H)) keep = false;           // :22
+        else {
+            const size_t t = base + (size_t)((int)p2y - 1) * W + ((int)p2x - 1);
+            const double bu = bw[t], bv = bw[t + NP];
+            if (isnan(bu) || isnan(bv)) keep = false;                                                    // :27, NaN for the -1 marker
+            else if (fabs(__dadd_rn(u, bu)) > thr || fabs(__dadd_rn(v, bv)) > thr) keep = false;         // :32
+        }
+    }
+    out[q] = keep ? u : FSGM_NAN;
+    out[q + NP] = keep ? v : FSGM_NAN;
 }
 
 // =============================================================================================
@@ -200,18 +234,24 @@ __global__ __launch_bounds__(256) void fb_check_map_kernel(const double* __restr
 // last valid cell of a column are filled; one thread per column walks it (coalesced across columns).
 // A batch: the row pass sees nf*H independent rows; the column pass has one thread per (frame, column), which walks
 // the H rows of its own frame only.
+// On a flow (CH = 2; scanline_in_fill.m with :16 and :19 restored) the gaps are those of channel u: l / r and the first /
+// last row are those whose u is a number, and every channel takes its own min(c[l], c[r]), c[r] or c[l] there.
 // =============================================================================================
-__global__ __launch_bounds__(256) void infill_rows_kernel(const double* __restrict__ in, double* __restrict__ out, int32_t* __restrict__ left, int W) {
+template <int CH>
+__global__ __launch_bounds__(256) void infill_rows_kernel(const double* __restrict__ in, double* __restrict__ out, int32_t* __restrict__ left,
+                                                          int W, int H) {
     __shared__ int sh[4];
     __shared__ int carry_sh;
-    const size_t row = (size_t)blockIdx.x * W;
+    const size_t NP = (size_t)W * H, lrow = (size_t)blockIdx.x * W;      // lrow: the (frame, row)'s place in `left`
+    size_t row = lrow;
+    if constexpr (CH > 1) row = px_first<CH>(lrow, (size_t)(blockIdx.x / H), NP);
     const double* v = in + row;
     int carry = -1;                                              // nearest valid column so far, from the left
     for (int base = 0; base < W; base += 256) {
         const int x = base + threadIdx.x;
         const int mine = (x < W && !isnan(v[x])) ? x : -1;
         const int l = max(block_scan_max_256(mine, sh), carry);
-        if (x < W) left[row + x] = l;
+        if (x < W) left[lrow + x] = l;
         if (threadIdx.x == 255) carry_sh = l;
         __syncthreads();
         carry = carry_sh;
@@ -223,15 +263,19 @@ __global__ __launch_bounds__(256) void infill_rows_kernel(const double* __restri
         const int mine = (xr < W && !isnan(v[x])) ? xr : -1;     // max over xr = min over x
         const int rr = max(block_scan_max_256(mine, sh), carry);
         if (xr < W) {
-            const double c = v[x];
-            double res = c;
-            if (isnan(c)) {
-                const int l = left[row + x], r = rr < 0 ? -1 : W - 1 - rr;
-                if (l >= 0 && r >= 0) res = fmin(v[l], v[r]);    // :16
-                else if (r >= 0) res = v[r];                     // :30-37
-                else if (l >= 0) res = v[l];                     // :39-46
+            Px<CH> res = px_load<CH>(v + x, NP);
+            if (isnan(res.c[0])) {
+                const int l = left[lrow + x], r = rr < 0 ? -1 : W - 1 - rr;
+#pragma unroll
+                for (int c = 0; c < CH; c++) {
+                    const double* vc = v + c * NP;
+                    if (l >= 0 && r >= 0) res.c[c] = fmin(vc[l], vc[r]);   // :15-16
+                    else if (r >= 0) res.c[c] = vc[r];                     // :30-37
+                    else if (l >= 0) res.c[c] = vc[l];                     // :39-46
+                }
             }
-            out[row + x] = res;
+#pragma unroll
+            for (int c = 0; c < CH; c++) out[row + c * NP + x] = res.c[c];
         }
         if (threadIdx.x == 255) carry_sh = rr;
         __syncthreads();
@@ -239,18 +283,23 @@ __global__ __launch_bounds__(256) void infill_rows_kernel(const double* __restri
         __syncthreads();
     }
 }
+template <int CH>
 __global__ __launch_bounds__(256) void infill_cols_kernel(double* io, int W, int H, int nf) {
     const int t = blockIdx.x * 256 + threadIdx.x;
     if (t >= nf * W) return;
     const int f = t / W, x = t - f * W;
-    io += (size_t)f * W * H;
+    const size_t NP = (size_t)W * H;
+    io += (size_t)f * CH * NP + x;
     int first = -1, last = -1;
     for (int y = 0; y < H; y++)
-        if (!isnan(io[(size_t)y * W + x])) { if (first < 0) first = y; last = y; }
+        if (!isnan(io[(size_t)y * W])) { if (first < 0) first = y; last = y; }
     if (first < 0) return;
-    const double top = io[(size_t)first * W + x], bot = io[(size_t)last * W + x];
-    for (int y = 0; y < first; y++) io[(size_t)y * W + x] = top;            // :52-59
-    for (int y = last + 1; y < H; y++) io[(size_t)y * W + x] = bot;         // :61-68
+    for (int c = 0; c < CH; c++) {
+        double* p = io + c * NP;
+        const double top = p[(size_t)first * W], bot = p[(size_t)last * W];
+        for (int y = 0; y < first; y++) p[(size_t)y * W] = top;                  // :52-59
+        for (int y = last + 1; y < H; y++) p[(size_t)y * W] = bot;               // :61-68
+    }
 }
 
 // =============================================================================================
@@ -286,7 +335,7 @@ __global__ __launch_bounds__(256) void vmf_kernel(const double* __restrict__ in,
             w[i] = fmin(a, b);
             w[j] = fmax(a, b);
         }
-    out[plane + (size_t)y * W + x] = nans > 12 ? __longlong_as_double(0x7FF8000000000000LL) : w[12];
+    out[plane + (size_t)y * W + x] = nans > 12 ? FSGM_NAN : w[12];
 }
 
 // =============================================================================================
@@ -314,6 +363,17 @@ __global__ __launch_bounds__(256) void epi_pp_flow_kernel(const double* __restri
     flow2[q] = __dadd_rn(__dmul_rn(fd, nx), rx);                                                   // :51-52
     flow2[q + NP] = __dadd_rn(__dmul_rn(fd, ny), ry);
     flow2[q + 2 * NP] = isnan(fw) ? 0.0 : 1.0;                                                     // :53
+}
+
+// the filled flow and the validity of the checked one (test.m:53's third plane) as one [3][H][W] frame
+__global__ __launch_bounds__(256) void flow_pack_kernel(const double* __restrict__ filled, const double* __restrict__ checked,
+                                                        double* __restrict__ flow_pp, size_t NP, size_t n_px) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_px) return;
+    const size_t f = i / NP, q = i + f * NP, o = q + f * NP;
+    flow_pp[o] = filled[q];
+    flow_pp[o + NP] = filled[q + NP];
+    flow_pp[o + 2 * NP] = (isnan(checked[q]) || isnan(checked[q + NP])) ? 0.0 : 1.0;
 }
 
 __global__ __launch_bounds__(64) void post_status_kernel(uint32_t* __restrict__ neg, int32_t* __restrict__ status) {
@@ -349,22 +409,33 @@ void launch_post_status(hipStream_t st, uint32_t* neg, int32_t* status) {
     hipLaunchKernelGGL(post_status_kernel, dim3(1), dim3(64), 0, st, neg, status);
 }
 
+template <int CH>
+static void speckle_enqueue(hipStream_t st, const double* img, double* out, int32_t* parent, int32_t* size, int W, int H,
+                            double maxDiff, double maxSpeckleSize, int nf, uint32_t* neg) {
+    const int NP = W * H, n = NP * nf, nb = (n + 255) / 256;
+    hipLaunchKernelGGL(ccl_init_kernel<CH>, dim3(nb), dim3(256), 0, st, parent, size, n, img, neg);
+    for (int f0 = 0; f0 < nf; f0 += MAX_GRID_Z)
+        hipLaunchKernelGGL(ccl_merge_kernel<CH>, dim3((W + 63) / 64, (H + 3) / 4, std::min(nf - f0, MAX_GRID_Z)), dim3(256), 0, st, img, parent,
+                           W, H, f0, maxDiff);
+    hipLaunchKernelGGL(ccl_count_kernel<CH>, dim3(nb), dim3(256), 0, st, img, parent, size, NP, n);
+    hipLaunchKernelGGL(speckle_apply_kernel<CH>, dim3(nb), dim3(256), 0, st, img, out, parent, size, NP, n, maxSpeckleSize);
+}
+
 void launch_speckle_filter(hipStream_t st, const double* image, double* out, int32_t* labels, int32_t* parent,
                            int32_t* size, int32_t* scan, int W, int H, double maxDiff, double maxSpeckleSize, int nf, uint32_t* neg) {
-    const int n = W * H * nf, nb = (n + 255) / 256;
-    hipLaunchKernelGGL(ccl_init_kernel, dim3(nb), dim3(256), 0, st, parent, size, n, image, neg);
-    for (int f0 = 0; f0 < nf; f0 += MAX_GRID_Z)
-        hipLaunchKernelGGL(ccl_merge_kernel, dim3((W + 63) / 64, (H + 3) / 4, std::min(nf - f0, MAX_GRID_Z)), dim3(256), 0, st, image, parent,
-                           W, H, f0, maxDiff);
-    hipLaunchKernelGGL(ccl_count_kernel, dim3(nb), dim3(256), 0, st, image, parent, size, n);
-    hipLaunchKernelGGL(speckle_apply_kernel, dim3(nb), dim3(256), 0, st, image, out, parent, size, n, maxSpeckleSize);
+    speckle_enqueue<1>(st, image, out, parent, size, W, H, maxDiff, maxSpeckleSize, nf, neg);
     if (labels && nf == 1) {
-        const int nc = (n + SCAN_CHUNK - 1) / SCAN_CHUNK;
+        const int n = W * H, nb = (n + 255) / 256, nc = (n + SCAN_CHUNK - 1) / SCAN_CHUNK;
         hipLaunchKernelGGL(roots_count_kernel, dim3(nc), dim3(256), 0, st, image, parent, scan, n);
         hipLaunchKernelGGL(roots_scan_kernel, dim3(1), dim3(64), 0, st, scan, nc);
         hipLaunchKernelGGL(roots_rank_kernel, dim3(nc), dim3(256), 0, st, image, parent, scan, size, n);    // size reused as rank
         hipLaunchKernelGGL(labels_kernel, dim3(nb), dim3(256), 0, st, image, parent, size, labels, n);
     }
+}
+
+void launch_flow_speckle_filter(hipStream_t st, const double* flow, double* out, int32_t* parent, int32_t* size, int W, int H,
+                                double maxDiff, double maxSpeckleSize, int nf) {
+    speckle_enqueue<2>(st, flow, out, parent, size, W, H, maxDiff, maxSpeckleSize, nf, nullptr);
 }
 
 void launch_disp_from_first(hipStream_t st, const double* D1, double* D2, const PostGeom& g, int W, int H, int nf) {
@@ -381,9 +452,27 @@ void launch_fb_check(hipStream_t st, const double* D1, const double* D2, double*
                            D1, D2, out, g, W, H, f0);
 }
 
+void launch_flow_fb_check(hipStream_t st, const double* f, const double* b, double* out, int W, int H, double thr, int nf) {
+    for (int f0 = 0; f0 < nf; f0 += MAX_GRID_Z)
+        hipLaunchKernelGGL(flow_fb_check_kernel, dim3((W + 63) / 64, (H + 3) / 4, std::min(nf - f0, MAX_GRID_Z)), dim3(256), 0, st,
+                           f, b, out, W, H, f0, thr);
+}
+
+template <int CH>
+static void in_fill_enqueue(hipStream_t st, const double* in, double* out, int32_t* left, int W, int H, int nf) {
+    hipLaunchKernelGGL(infill_rows_kernel<CH>, dim3(H * nf), dim3(256), 0, st, in, out, left, W, H);
+    hipLaunchKernelGGL(infill_cols_kernel<CH>, dim3((W * nf + 255) / 256), dim3(256), 0, st, out, W, H, nf);
+}
 void launch_scanline_in_fill(hipStream_t st, const double* in, double* out, int32_t* left, int W, int H, int nf) {
-    hipLaunchKernelGGL(infill_rows_kernel, dim3(H * nf), dim3(256), 0, st, in, out, left, W);
-    hipLaunchKernelGGL(infill_cols_kernel, dim3((W * nf + 255) / 256), dim3(256), 0, st, out, W, H, nf);
+    in_fill_enqueue<1>(st, in, out, left, W, H, nf);
+}
+void launch_flow_in_fill(hipStream_t st, const double* in, double* out, int32_t* left, int W, int H, int nf) {
+    in_fill_enqueue<2>(st, in, out, left, W, H, nf);
+}
+
+void launch_flow_pack(hipStream_t st, const double* filled, const double* checked, double* flow_pp, int W, int H, int nf) {
+    const size_t NP = (size_t)W * H, n_px = NP * nf;
+    hipLaunchKernelGGL(flow_pack_kernel, dim3((unsigned)((n_px + 255) / 256)), dim3(256), 0, st, filled, checked, flow_pp, NP, n_px);
 }
 
 void launch_vzind2disp(hipStream_t st, const double* w, const double* O, double* D, size_t n_px, double vMax, double n) {

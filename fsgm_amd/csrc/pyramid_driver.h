@@ -34,11 +34,6 @@ struct PyramidCore {
     DeviceJoin join;                             // device-pointer entry point: ordering with the caller's stream
 };
 
-inline fsgm_status hip_status(hipError_t e) {
-    if (e == hipSuccess) return FSGM_OK;
-    return fail(e == hipErrorOutOfMemory ? FSGM_ERR_NOMEM : FSGM_ERR_HIP, "%s", hipGetErrorString(e));
-}
-
 template <class P>
 void pyramid_destroy(P* p) {
     if (!p) return;
@@ -66,11 +61,7 @@ fsgm_status pyramid_create(P** out, int W, int H, int channels, int batch, const
     FSGM_REQUIRE(prm->numPyd >= 1 && prm->numPyd <= 16, "numPyd must be in 1..16 (got %d)", prm->numPyd);
     fsgm_status st = P::check(*prm, W, H);
     if (st != FSGM_OK) return st;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-        return fail(FSGM_ERR_HIP, "no HIP device available (libfsgm_hip has no CPU fallback)");
-    FSGM_REQUIRE(prm->device >= 0 && prm->device < ndev, "device %d out of range (have %d)", prm->device, ndev);
-    FSGM_HIP(hipSetDevice(prm->device));
+    if ((st = use_device(prm->device)) != FSGM_OK) return st;
     P* p = new P;
     p->prm = *prm;
     PyramidCore& c = p->core;
@@ -190,50 +181,22 @@ fsgm_status pyramid_time(P* p, int warmup, int iters, float* ms_avg) {
     FSGM_REQUIRE(p && ms_avg && iters >= 1 && warmup >= 0, "%s_time: bad argument", P::plan_name);
     FSGM_HIP(hipSetDevice(p->prm.device));
     const PyramidCore& c = p->core;
-    fsgm_status st;
-    for (int i = 0; i < warmup; i++)
-        if ((st = pyramid_enqueue(p)) != FSGM_OK) return st;
-    FSGM_HIP(hipEventRecord(c.ev0, c.stream));
-    for (int i = 0; i < iters; i++)
-        if ((st = pyramid_enqueue(p)) != FSGM_OK) return st;
-    FSGM_HIP(hipEventRecord(c.ev1, c.stream));
-    FSGM_HIP(hipEventSynchronize(c.ev1));
-    float ms = 0;
-    FSGM_HIP(hipEventElapsedTime(&ms, c.ev0, c.ev1));
-    *ms_avg = ms / iters;
-    return FSGM_OK;
+    return time_enqueues(c.stream, c.ev0, c.ev1, warmup, iters, [&] { return pyramid_enqueue(p); }, ms_avg);
 }
 
-// The plans behind the host- and device-pointer entry points: the last two per device, keyed by shape, parameters and batch,
-// each device's under that device's lock
+// The plans behind the host- and device-pointer entry points: the last two per device, keyed by shape, parameters and batch
 template <class P>
-struct PyramidCache {
-    PerDevice<std::vector<P*>> plans;
-
-    void clear() {
-        for (int d = 0; d < FSGM_MAX_DEVICES; d++) {
-            std::lock_guard<std::mutex> lk(plans.mu[d]);
-            for (P* p : plans.v[d]) pyramid_destroy(p);
-            plans.v[d].clear();
-        }
-    }
+struct PyramidCache : PlanCache<P> {
+    PyramidCache() : PlanCache<P>(2, pyramid_destroy<P>) {}
     // the cached plan of this shape, parameter set and batch (the caller holds the device's lock)
     fsgm_status get(P** out, int W, int H, int channels, const typename P::Params* prm, int batch) {
-        std::vector<P*>& cache = plans.v[prm->device];
-        P* p = nullptr;
-        for (P* q : cache)
-            if (q->core.W == W && q->core.H == H && q->core.channels == channels && q->core.batch == batch && memcmp(&q->prm, prm, sizeof *prm) == 0) p = q;
-        if (!p) {
-            fsgm_status st = pyramid_create(&p, W, H, channels, batch, prm);
-            if (st != FSGM_OK) return st;
-            if (cache.size() >= 2) {
-                pyramid_destroy(cache.front());
-                cache.erase(cache.begin());
-            }
-            cache.push_back(p);
-        }
-        *out = p;
-        return FSGM_OK;
+        *out = this->find(prm->device, [&](const P* q) {
+            return q->core.W == W && q->core.H == H && q->core.channels == channels && q->core.batch == batch && memcmp(&q->prm, prm, sizeof *prm) == 0;
+        });
+        if (*out) return FSGM_OK;
+        const fsgm_status st = pyramid_create(out, W, H, channels, batch, prm);
+        if (st == FSGM_OK) this->insert(prm->device, *out);
+        return st;
     }
 };
 
@@ -255,7 +218,7 @@ template <class P, class Body>
 fsgm_status pyramid_with_pair(PyramidCache<P>& cache, int n, int W, int H, int channels, const typename P::Params* prm, Body&& body) {
     FSGM_REQUIRE(n >= 1 && n <= P::max_batch / 2, "%s: n_frames must be in 1..%d (got %d)", P::entry_name, P::max_batch / 2, n);
     FSGM_DEVICE_SLOT(prm->device);
-    std::lock_guard<std::mutex> lk(cache.plans.mu[prm->device]);
+    std::lock_guard<std::mutex> lk(cache.mu(prm->device));
     P* p = nullptr;
     fsgm_status st;
     if ((st = cache.get(&p, W, H, channels, prm, 2 * n)) != FSGM_OK) return st;
@@ -272,7 +235,7 @@ fsgm_status pyramid_host(PyramidCache<P>& cache, const uint8_t* I0, const uint8_
                          const typename P::Params* prm, double* flow, uint32_t* minC, double* const* flowPyd) {
     FSGM_REQUIRE(I0 && I1 && prm && flow, "%s: null argument", P::entry_name);
     FSGM_DEVICE_SLOT(prm->device);
-    std::lock_guard<std::mutex> lk(cache.plans.mu[prm->device]);
+    std::lock_guard<std::mutex> lk(cache.mu(prm->device));
     P* p = nullptr;
     fsgm_status st;
     if ((st = cache.get(&p, W, H, channels, prm, 1)) != FSGM_OK) return st;
@@ -310,7 +273,7 @@ fsgm_status pyramid_device(PyramidCache<P>& cache, int32_t n, const uint8_t* I0,
     FSGM_REQUIRE(W >= 1 && H >= 1, "%s: width/height must be >= 1 (got %d x %d)", who, W, H);
     FSGM_REQUIRE(channels == 1 || channels == 3, "%s: channels must be 1 (gray) or 3 (RGB planes), got %d", who, channels);
     FSGM_DEVICE_SLOT(prm->device);
-    std::lock_guard<std::mutex> lk(cache.plans.mu[prm->device]);
+    std::lock_guard<std::mutex> lk(cache.mu(prm->device));
     P* p = nullptr;
     fsgm_status st;
     if ((st = cache.get(&p, W, H, channels, prm, n)) != FSGM_OK) return st;

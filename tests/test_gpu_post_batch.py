@@ -1,6 +1,8 @@
 """GPU tests of the post-processing chain on batches of maps (fsgm_epi_postprocess_batch_host / _device, fsgm_vmf_device) and of
 test.m's frame body on the device (fsgm_epipolar_flow_pp_*), against the CPU oracle frame by frame.  Values are copies / minima /
 IEEE expressions of the inputs: compared exactly, NaN positions included."""
+import threading
+
 import numpy as np
 import pytest
 
@@ -9,6 +11,8 @@ torch = pytest.importorskip("torch")
 import fsgm_amd  # noqa: E402
 from fsgm_amd import torch_ops, synth  # noqa: E402  (torch first, then the library)
 from fsgm_amd._lib import FsgmError  # noqa: E402
+from tests import flow_pp_inputs  # noqa: E402
+from tests import flow_pp_restatement as R  # noqa: E402
 from tests.edge_inputs import oracle_flow_pp_frame  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -102,6 +106,65 @@ def test_frames_stay_isolated(gpu_lib, oracle):
     _check_frames(got, *maps, oracle, "host batch")
     got = torch_ops.epi_postprocess(*[_t(a) for a in maps], VMAX, D + 1, D, check=True)
     _check_frames([_n(g) for g in got], *maps, oracle, "device batch")
+
+
+# ---------------------------------------------------------------------------------------------- the plan caches
+CACHE_SHAPES = [(W, 7) for W in range(5, 11)] + [(5, 7)]         # six shapes, two more than a cache holds; then the first again
+
+
+def _flows(W, H, N, seed):
+    kinds = ("general", "int", "even", "zero")
+    return np.stack([flow_pp_inputs.flow_pair(W, H, kinds[(k + W) % 4], seed=seed + k)[0] for k in range(N)])
+
+
+def test_post_plan_cache_evicts_and_rebuilds(gpu_lib, oracle):
+    for W, H in CACHE_SHAPES:
+        maps = _batch(W, H, 2, seed=W)
+        _check_frames(fsgm_amd.epi_postprocess_batch(*maps, VMAX, D + 1, D), *maps, oracle, f"host batch {W}x{H}")
+
+
+def test_flow_plan_cache_evicts_and_rebuilds(gpu_lib):
+    """maxSpeckleSize 4: maps of 35 to 70 pixels keep some regions and lose others."""
+    for W, H in CACHE_SHAPES:
+        f = _flows(W, H, 2, seed=W)
+        _same(fsgm_amd.flow_speckle_filter(f, 2, 4), np.stack([R.flow_speckle_filter(a, 2, 4)[0] for a in f]), f"speckle {W}x{H}")
+        _same(fsgm_amd.flow_in_fill(f), np.stack([R.flow_in_fill(a) for a in f]), f"fill {W}x{H}")
+
+
+def test_two_host_threads_on_one_device(gpu_lib):
+    """The map chain and the flow stages from two host threads at once (ctypes calls run without the GIL): each keeps its
+    own plans under the device's lock, and every call gives what it gave alone."""
+    maps = _batch(37, 23, 3, seed=3)
+    flows = _flows(61, 47, 2, seed=5)
+    want_pp = fsgm_amd.epi_postprocess_batch(*maps, VMAX, D + 1, D)
+    want_sp = fsgm_amd.flow_speckle_filter(flows, 2, 100)
+    want_fill = fsgm_amd.flow_in_fill(want_sp)
+    assert not np.isnan(want_pp[0][0]).all() and np.isnan(want_sp).any() and not np.isnan(want_sp).all()
+    failures = []
+
+    def post(i):
+        for g, w, name in zip(fsgm_amd.epi_postprocess_batch(*maps, VMAX, D + 1, D), want_pp, ("filterD1", "filterD2", "disp")):
+            _same(g, w, f"{name}, iteration {i}")
+
+    def flow(i):
+        sp = fsgm_amd.flow_speckle_filter(flows, 2, 100)
+        _same(sp, want_sp, f"flow speckle filter, iteration {i}")
+        _same(fsgm_amd.flow_in_fill(sp), want_fill, f"flow fill, iteration {i}")
+
+    def loop(body):
+        try:
+            for i in range(20):
+                body(i)
+        except BaseException as e:  # noqa: BLE001  (reported by the main thread)
+            failures.append(e)
+
+    threads = [threading.Thread(target=loop, args=(body,), daemon=True) for body in (post, flow)]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join(60.0)
+        assert not t.is_alive(), "a thread is still inside the library after 60 s"
+    assert not failures, failures
 
 
 # ---------------------------------------------------------------------------------------------- device = host
