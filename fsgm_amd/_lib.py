@@ -25,6 +25,14 @@ class EpiParams(C.Structure):
                 ("fb_check", C.c_int32)]
 
 
+class StereoParams(C.Structure):
+    _fields_ = [("paths", C.c_int32), ("subpixel", C.c_int32), ("fb_check", C.c_int32), ("direction", C.c_int32),
+                ("device", C.c_int32)]
+
+
+SAMPLING_VZ, SAMPLING_LINEAR, SAMPLING_RECTIFIED = 0, 1, 2
+
+
 class EpiIn(C.Structure):
     _fields_ = [("I1", C.c_void_p), ("I2", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32),
                 ("dMax", C.c_int32), ("vMax", C.c_double), ("pixelPosD0", C.c_void_p),
@@ -57,6 +65,12 @@ def load():
     lib.fsgm_epi_params_default.restype = EpiParams
     lib.fsgm_calc_cost_sgm_host.argtypes = [C.POINTER(EpiIn), C.POINTER(EpiOut), C.POINTER(EpiParams)]
     lib.fsgm_calc_cost_sgm_batch_host.argtypes = [i32, C.POINTER(EpiIn), C.POINTER(EpiOut), C.POINTER(EpiParams)]
+    lib.fsgm_calc_cost_sgm_linear_host.argtypes = [C.POINTER(EpiIn), C.POINTER(EpiOut), C.POINTER(EpiParams)]
+    lib.fsgm_calc_cost_sgm_linear_batch_host.argtypes = [i32, C.POINTER(EpiIn), C.POINTER(EpiOut), C.POINTER(EpiParams)]
+    lib.fsgm_stereo_params_default.restype = StereoParams
+    lib.fsgm_stereo_sgm_host.argtypes = [i32, vp, vp, i32, i32, i32, i32, i32, C.POINTER(StereoParams), vp, vp, vp, vp]
+    lib.fsgm_epi_plan_create_sampling.argtypes = [C.POINTER(vp), i32, i32, i32, i32, C.POINTER(EpiParams), i32, i32]
+    lib.fsgm_epi_plan_upload_images.argtypes = [vp, i32, vp, vp]
     i32p = C.POINTER(C.c_int32)
     lib.fsgm_calc_cost_sgm_batch_devices_host.argtypes = [i32, C.POINTER(EpiIn), C.POINTER(EpiOut), C.POINTER(EpiParams), i32, i32p]
     lib.fsgm_parse_device_list.argtypes = [C.c_char_p, i32p, i32]

@@ -50,6 +50,10 @@ struct PipelineForm {
 struct fsgm_epi_plan {
     int W = 0, H = 0, D = 0, batch = 0;
     fsgm_epi_params prm{};
+    // How candidate d is sampled (fixed at creation): FSGM_SAMPLING_VZ at offset * vzInd(d) along the direction (the reference as
+    // shipped), _LINEAR at d pixels along it (the reference built without USE_VZIND: the vz table holds d, the offsets 1.0),
+    // _RECTIFIED a rectified pair -- Pd0 = (x + 1, y + 1), direction (direction, 0): no maps exist
+    int sampling = FSGM_SAMPLING_VZ, direction = -1;
     int P1 = 6, P2 = 64;                 // epipolar_sgm_of.m:19
     double vMax = 0.3;                   // epipolar_sgm_of.m:16
     size_t NP = 0, N = 0;                // pixels, voxels per frame
@@ -321,12 +325,22 @@ void fsgm_epi_plan_destroy(fsgm_epi_plan* p) {
 
 fsgm_status fsgm_epi_plan_create(fsgm_epi_plan** out, int32_t W, int32_t H, int32_t D, int32_t batch,
                                  const fsgm_epi_params* prm) {
+    return fsgm_epi_plan_create_sampling(out, W, H, D, batch, prm, FSGM_SAMPLING_VZ, 0);
+}
+
+fsgm_status fsgm_epi_plan_create_sampling(fsgm_epi_plan** out, int32_t W, int32_t H, int32_t D, int32_t batch,
+                                          const fsgm_epi_params* prm, int32_t sampling, int32_t direction) {
     FSGM_REQUIRE(out, "fsgm_epi_plan_create: null plan pointer");
     *out = nullptr;
+    FSGM_REQUIRE(sampling == FSGM_SAMPLING_VZ || sampling == FSGM_SAMPLING_LINEAR || sampling == FSGM_SAMPLING_RECTIFIED,
+                 "fsgm_epi_plan_create: sampling must be FSGM_SAMPLING_VZ, _LINEAR or _RECTIFIED (got %d)", sampling);
+    FSGM_REQUIRE(sampling != FSGM_SAMPLING_RECTIFIED || direction == -1 || direction == 1,
+                 "fsgm_epi_plan_create: a rectified plan's direction must be -1 or +1 (got %d)", direction);
     FSGM_REQUIRE(W >= 1 && H >= 1, "fsgm_epi_plan_create: width/height must be >= 1 (got %d x %d)", W, H);
     FSGM_REQUIRE(D >= 1, "fsgm_epi_plan_create: dMax must be >= 1 (got %d)", D);
     FSGM_REQUIRE(batch >= 1, "fsgm_epi_plan_create: batch must be >= 1");
-    const fsgm_epi_params pr = prm ? *prm : fsgm_epi_params_default();
+    fsgm_epi_params pr = prm ? *prm : fsgm_epi_params_default();
+    if (sampling != FSGM_SAMPLING_VZ) pr.vz_to_disp = 0;         // bestD is the index * 256, never converted (:592-594)
     FSGM_REQUIRE(pr.paths == 4 || pr.paths == 8, "fsgm_epi_plan_create: paths must be 4 or 8 (got %d)", pr.paths);
     if (pr.fb_check && D > 511)
         return fail(FSGM_ERR_UNSUPPORTED, "fb_check needs dMax <= 511 (bestD must stay below INVALID_DISPARITY)");
@@ -338,6 +352,8 @@ fsgm_status fsgm_epi_plan_create(fsgm_epi_plan** out, int32_t W, int32_t H, int3
 
     fsgm_epi_plan* p = new fsgm_epi_plan;
     p->W = W; p->H = H; p->D = D; p->batch = batch; p->prm = pr;
+    p->sampling = sampling; p->direction = sampling == FSGM_SAMPLING_RECTIFIED ? direction : 0;
+    const bool rect = sampling == FSGM_SAMPLING_RECTIFIED;
     { int n = 0; if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, pr.device) == hipSuccess && n > 0) p->cus = n; }
     p->NP = (size_t)W * H; p->N = p->NP * D;
     p->cmax.assign(batch, 24);           // census 5x5: 24 informative bits
@@ -346,7 +362,7 @@ fsgm_status fsgm_epi_plan_create(fsgm_epi_plan** out, int32_t W, int32_t H, int3
     auto alloc = [&](void** ptr, size_t bytes) { if (e == hipSuccess) e = hipMalloc(ptr, bytes); };
     // images, census codes, the two fp64 coordinate maps and the raw cost volume belong to the cost stage and are allocated
     // on first use (ensure_cost_buffers): an aggregation-only plan holds C, the offsets and its pipeline's volumes only
-    alloc((void**)&p->dOff, B * p->NP * 8);
+    if (!rect) alloc((void**)&p->dOff, B * p->NP * 8);           // (a rectified plan has no maps)
     alloc((void**)&p->dVz, (size_t)D * 8);
     alloc((void**)&p->dC, B * p->N);
     // the per-voxel intermediates of the two aggregation strategies (L_r for the line kernels;
@@ -361,7 +377,11 @@ fsgm_status fsgm_epi_plan_create(fsgm_epi_plan** out, int32_t W, int32_t H, int3
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking);
     if (e == hipSuccess) e = hipEventCreate(&p->ev0);
     if (e == hipSuccess) e = hipEventCreate(&p->ev1);
-    if (e == hipSuccess) e = hipMemsetAsync(p->dOff, 0, B * p->NP * 8, p->stream);
+    if (e == hipSuccess && sampling == FSGM_SAMPLING_VZ) e = hipMemsetAsync(p->dOff, 0, B * p->NP * 8, p->stream);
+    if (e == hipSuccess && sampling == FSGM_SAMPLING_LINEAR) {   // offset == 1.0 for good: (1.0 * d) * u is the reference's d * u (:368-369)
+        const std::vector<double> ones(B * p->NP, 1.0);
+        e = hipMemcpy(p->dOff, ones.data(), B * p->NP * 8, hipMemcpyHostToDevice);
+    }
     if (e != hipSuccess) {
         fsgm_epi_plan_destroy(p);
         return hip_status(e, "fsgm_epi_plan_create");
@@ -399,8 +419,8 @@ static fsgm_status ensure_cost_buffers(fsgm_epi_plan* p) {
     ls.alloc(p->dI2, B * p->NP);
     ls.alloc(p->dCen1, B * p->NP * 4);
     ls.alloc(p->dCen2, B * p->NP * 4);
-    ls.alloc(p->dPd0, B * p->NP * 16);
-    ls.alloc(p->dNd, B * p->NP * 16);
+    ls.alloc(p->dPd0, B * p->NP * 16, p->sampling != FSGM_SAMPLING_RECTIFIED);
+    ls.alloc(p->dNd, B * p->NP * 16, p->sampling != FSGM_SAMPLING_RECTIFIED);
     ls.alloc(p->dCraw, B * p->N);
     if (ls.err != hipSuccess) return lazy_fail(ls, "cost stage buffers");
     ls.commit();
@@ -424,7 +444,7 @@ static fsgm_status ensure_vz(fsgm_epi_plan* p) {
     const double n = p->D + 1;
     for (int d = 0; d < p->D; d++) {
         const double vzRatio = 1.0 * d / n * p->vMax;
-        vz[d] = vzRatio / (1 - vzRatio);
+        vz[d] = p->sampling == FSGM_SAMPLING_VZ ? vzRatio / (1 - vzRatio) : (double)d;   // linear: d itself (:368-369)
         vzmax = std::isfinite(vz[d]) ? std::max(vzmax, std::fabs(vz[d])) : INFINITY;
     }
     FSGM_HIP(hipMemcpyAsync(p->dVz, vz.data(), (size_t)p->D * 8, hipMemcpyHostToDevice, p->stream));
@@ -464,7 +484,7 @@ static fsgm_status upload_async(fsgm_epi_plan* p, int f, const uint8_t* I1, cons
     FSGM_HIP(hipMemcpyAsync(p->dI2 + o * NP, I2, NP, hipMemcpyHostToDevice, p->stream));
     FSGM_HIP(hipMemcpyAsync(p->dPd0 + o * 2 * NP, pd0, NP * 16, hipMemcpyHostToDevice, p->stream));
     FSGM_HIP(hipMemcpyAsync(p->dNd + o * 2 * NP, nd, NP * 16, hipMemcpyHostToDevice, p->stream));
-    FSGM_HIP(hipMemcpyAsync(p->dOff + o * NP, off, NP * 8, hipMemcpyHostToDevice, p->stream));
+    if (p->sampling == FSGM_SAMPLING_VZ) FSGM_HIP(hipMemcpyAsync(p->dOff + o * NP, off, NP * 8, hipMemcpyHostToDevice, p->stream));
     return FSGM_OK;
 }
 
@@ -472,11 +492,25 @@ fsgm_status fsgm_epi_plan_upload(fsgm_epi_plan* p, int32_t f, const uint8_t* I1,
                                  const double* pd0, const double* nd, const double* off) {
     FSGM_REQUIRE(p, "null plan");
     { fsgm_status fs = frame_ready(p, f, 0); if (fs != FSGM_OK) return fs; }
-    FSGM_REQUIRE(I1 && I2 && pd0 && nd && off, "fsgm_epi_plan_upload: null input");
+    FSGM_REQUIRE(p->sampling != FSGM_SAMPLING_RECTIFIED, "fsgm_epi_plan_upload: a rectified plan takes images only (fsgm_epi_plan_upload_images)");
+    FSGM_REQUIRE(I1 && I2 && pd0 && nd && (off || p->sampling == FSGM_SAMPLING_LINEAR), "fsgm_epi_plan_upload: null input");
     { fsgm_status cs = ensure_cost_buffers(p); if (cs != FSGM_OK) return cs; }
     StreamGuard guard(p->stream);
     { fsgm_status us = upload_async(p, f, I1, I2, pd0, nd, off); if (us != FSGM_OK) return us; }
     FSGM_HIP(hipStreamSynchronize(p->stream));   // pageable host memory: keep the caller's buffers free to reuse
+    guard.dismiss();
+    return FSGM_OK;
+}
+
+fsgm_status fsgm_epi_plan_upload_images(fsgm_epi_plan* p, int32_t f, const uint8_t* I1, const uint8_t* I2) {
+    FSGM_REQUIRE(p, "null plan");
+    { fsgm_status fs = frame_ready(p, f, 0); if (fs != FSGM_OK) return fs; }
+    FSGM_REQUIRE(I1 && I2, "fsgm_epi_plan_upload_images: null input");
+    { fsgm_status cs = ensure_cost_buffers(p); if (cs != FSGM_OK) return cs; }
+    StreamGuard guard(p->stream);
+    FSGM_HIP(hipMemcpyAsync(p->dI1 + (size_t)f * p->NP, I1, p->NP, hipMemcpyHostToDevice, p->stream));
+    FSGM_HIP(hipMemcpyAsync(p->dI2 + (size_t)f * p->NP, I2, p->NP, hipMemcpyHostToDevice, p->stream));
+    FSGM_HIP(hipStreamSynchronize(p->stream));
     guard.dismiss();
     return FSGM_OK;
 }
@@ -516,6 +550,7 @@ fsgm_status fsgm_epi_plan_copy_cost(fsgm_epi_plan* p, int32_t dst, int32_t src, 
 
 fsgm_status fsgm_epi_plan_upload_offset(fsgm_epi_plan* p, int32_t f, const double* off) {
     FSGM_REQUIRE(p && off, "fsgm_epi_plan_upload_offset: null argument");
+    FSGM_REQUIRE(p->sampling == FSGM_SAMPLING_VZ, "fsgm_epi_plan_upload_offset: only vz-index plans have an offset map");
     { fsgm_status fs = frame_ready(p, f, 0); if (fs != FSGM_OK) return fs; }
     FSGM_HIP(hipMemcpyAsync(p->dOff + f * p->NP, off, p->NP * 8, hipMemcpyHostToDevice, p->stream));
     FSGM_HIP(hipStreamSynchronize(p->stream));
@@ -596,6 +631,11 @@ static void enqueue_cost(fsgm_epi_plan* p, int f0, int nf) {
     const size_t NP = p->NP, o = (size_t)f0;
     launch_census(p->stream, p->dI1 + o * NP, p->dCen1 + o * NP, p->W, p->H, nf);
     launch_census(p->stream, p->dI2 + o * NP, p->dCen2 + o * NP, p->W, p->H, nf);
+    if (p->sampling == FSGM_SAMPLING_RECTIFIED) {
+        launch_stereo_cost(p->stream, p->dCen1 + o * NP, p->dCen2 + o * NP, p->dCraw + o * p->N, p->dC + o * p->N, p->W, p->H, p->D,
+                           p->direction, nf);
+        return;
+    }
     EpiCostArgs a;
     a.cen1 = p->dCen1 + o * NP; a.cen2 = p->dCen2 + o * NP; a.pd0 = p->dPd0 + o * 2 * NP; a.nd = p->dNd + o * 2 * NP;
     a.off = p->dOff + o * NP; a.vz = p->dVz; a.vzmax = p->vzmax; a.Craw = p->dCraw + o * p->N; a.W = p->W; a.H = p->H; a.D = p->D;
@@ -661,7 +701,7 @@ static BandArgs band_args(const fsgm_epi_plan* p, int f0) {
 static WtaArgs wta_args(const fsgm_epi_plan* p, int f0, int vz_to_disp) {
     const size_t o = (size_t)f0 * p->NP;
     WtaArgs a{};
-    a.off = p->dOff + o; a.bestD = p->dBestD + o; a.minC = p->dMinC + o; a.vMax = p->vMax;
+    a.off = frame_at(p->dOff, o); a.bestD = p->dBestD + o; a.minC = p->dMinC + o; a.vMax = p->vMax;
     a.W = p->W; a.H = p->H; a.D = p->D; a.ndirs = p->prm.paths;
     a.subpixel = p->prm.subpixel; a.vz_to_disp = vz_to_disp;
     return a;
@@ -873,6 +913,7 @@ static fsgm_status enqueue(fsgm_epi_plan* p, int stages) {
         b.D1 = p->dBestD; b.pd0 = p->dPd0; b.nd = p->dNd; b.off = p->dOff;
         b.D2enc = p->dD2enc; b.D2 = p->dD2; b.conf = p->dConf;
         b.vMax = p->vMax; b.W = p->W; b.H = p->H; b.n = p->D + 1; b.thr = 2;      // :483 thr = 2
+        b.linear = p->sampling != FSGM_SAMPLING_VZ; b.rect = p->direction;
         launch_fb_check(p->stream, b, p->batch);
         if (p->prm.vz_to_disp) launch_vz_convert(p->stream, p->dBestD, p->dOff, p->W, p->H, p->D, p->vMax, p->batch);
     }
@@ -1019,17 +1060,19 @@ fsgm_status fsgm_measure_copy_bandwidth(int32_t device, size_t bytes, int32_t it
 static PlanCache<fsgm_epi_plan> g_epi(4, fsgm_epi_plan_destroy);   // cached plans per device (the cap bounds the HBM held by stale shapes)
 
 // The cached plan of this shape for an entry point: `lk` holds its device's lock for the length of the call, the device is current.
+// (a plan serves one sampling mode and, rectified, one direction: the modes share no cached state)
 static fsgm_status cached_plan(std::unique_lock<std::mutex>& lk, fsgm_epi_plan** out, int W, int H, int D, int batch,
-                               const fsgm_epi_params& pr) {
+                               const fsgm_epi_params& pr, int sampling = FSGM_SAMPLING_VZ, int direction = 0) {
     FSGM_DEVICE_SLOT(pr.device);
     lk = std::unique_lock<std::mutex>(g_epi.mu(pr.device));
     fsgm_epi_plan* p = g_epi.find(pr.device, [&](const fsgm_epi_plan* q) {
         return q->W == W && q->H == H && q->D == D && q->batch == batch && q->prm.paths == pr.paths &&
-               q->prm.fb_check == pr.fb_check && q->prm.vz_to_disp == pr.vz_to_disp;
+               q->prm.fb_check == pr.fb_check && q->prm.vz_to_disp == pr.vz_to_disp && q->sampling == sampling &&
+               q->direction == direction;
     });
     if (p) p->prm = pr;
     else {
-        fsgm_status st = fsgm_epi_plan_create(&p, W, H, D, batch, &pr);
+        fsgm_status st = fsgm_epi_plan_create_sampling(&p, W, H, D, batch, &pr, sampling, direction);
         if (st != FSGM_OK) return st;
         g_epi.insert(pr.device, p);
     }
@@ -1055,23 +1098,25 @@ void fsgm_shutdown(void) {
     g_epi.clear();
 }
 
-fsgm_status fsgm_calc_cost_sgm_batch_host(int32_t n, const fsgm_epi_in* in, const fsgm_epi_out* out,
-                                          const fsgm_epi_params* prm) {
+// calc_cost_sgm on host pointers in either build of the reference: vz-index sampling, or linear (offset and vMax unused)
+static fsgm_status epi_batch_host(int sampling, int32_t n, const fsgm_epi_in* in, const fsgm_epi_out* out, const fsgm_epi_params* prm) {
     FSGM_REQUIRE(n >= 1 && in && out, "fsgm_calc_cost_sgm: null argument");
-    const fsgm_epi_params pr = prm ? *prm : fsgm_epi_params_default();
+    fsgm_epi_params pr = prm ? *prm : fsgm_epi_params_default();
+    const bool linear = sampling == FSGM_SAMPLING_LINEAR;
+    if (linear) pr.vz_to_disp = 0;
     for (int i = 0; i < n; i++) {
-        FSGM_REQUIRE(in[i].I1 && in[i].I2 && in[i].pixelPosD0 && in[i].normDir && in[i].offset,
+        FSGM_REQUIRE(in[i].I1 && in[i].I2 && in[i].pixelPosD0 && in[i].normDir && (in[i].offset || linear),
                      "fsgm_calc_cost_sgm: frame %d has a null input", i);
         FSGM_REQUIRE(out[i].bestD && out[i].minC, "fsgm_calc_cost_sgm: frame %d has a null output", i);
         FSGM_REQUIRE(in[i].width == in[0].width && in[i].height == in[0].height && in[i].dMax == in[0].dMax &&
-                     in[i].P1 == in[0].P1 && in[i].P2 == in[0].P2 && in[i].vMax == in[0].vMax,
+                     in[i].P1 == in[0].P1 && in[i].P2 == in[0].P2 && (linear || in[i].vMax == in[0].vMax),
                      "fsgm_calc_cost_sgm: frames of one batch must share shape and parameters (frame %d differs)", i);
     }
     std::unique_lock<std::mutex> lk;
     fsgm_epi_plan* p = nullptr;
-    fsgm_status st = cached_plan(lk, &p, in[0].width, in[0].height, in[0].dMax, n, pr);
+    fsgm_status st = cached_plan(lk, &p, in[0].width, in[0].height, in[0].dMax, n, pr, sampling);
     if (st != FSGM_OK) return st;
-    if ((st = fsgm_epi_plan_set_penalties(p, in[0].P1, in[0].P2, in[0].vMax)) != FSGM_OK) return st;
+    if ((st = fsgm_epi_plan_set_penalties(p, in[0].P1, in[0].P2, linear ? p->vMax : in[0].vMax)) != FSGM_OK) return st;
     if ((st = ensure_cost_buffers(p)) != FSGM_OK) return st;
     // One call = one stream-ordered sequence with a single host wait: every frame's inputs go up asynchronously on the
     // plan's stream (hipMemcpyAsync from the caller's pageable memory runs at the pinned rate here, ~50 GB/s, so there is
@@ -1102,8 +1147,66 @@ fsgm_status fsgm_calc_cost_sgm_batch_host(int32_t n, const fsgm_epi_in* in, cons
     return FSGM_OK;
 }
 
+fsgm_status fsgm_calc_cost_sgm_batch_host(int32_t n, const fsgm_epi_in* in, const fsgm_epi_out* out, const fsgm_epi_params* prm) {
+    return epi_batch_host(FSGM_SAMPLING_VZ, n, in, out, prm);
+}
+
 fsgm_status fsgm_calc_cost_sgm_host(const fsgm_epi_in* in, const fsgm_epi_out* out, const fsgm_epi_params* prm) {
     return fsgm_calc_cost_sgm_batch_host(1, in, out, prm);
+}
+
+fsgm_status fsgm_calc_cost_sgm_linear_batch_host(int32_t n, const fsgm_epi_in* in, const fsgm_epi_out* out, const fsgm_epi_params* prm) {
+    return epi_batch_host(FSGM_SAMPLING_LINEAR, n, in, out, prm);
+}
+
+fsgm_status fsgm_calc_cost_sgm_linear_host(const fsgm_epi_in* in, const fsgm_epi_out* out, const fsgm_epi_params* prm) {
+    return epi_batch_host(FSGM_SAMPLING_LINEAR, 1, in, out, prm);
+}
+
+// ---- rectified stereo on host pointers: n contiguous frames, images up, everything else as calc_cost_sgm ----
+fsgm_stereo_params fsgm_stereo_params_default(void) {
+    fsgm_stereo_params p;
+    p.paths = 4; p.subpixel = 1; p.fb_check = 0; p.direction = -1; p.device = 0;
+    return p;
+}
+
+static fsgm_status stereo_args(const char* who, int32_t n, const uint8_t* I1, const uint8_t* I2, int32_t W, int32_t H, int32_t dMax,
+                               const fsgm_stereo_params* prm, const uint32_t* disp, const uint32_t* minC, fsgm_stereo_params* sp,
+                               fsgm_epi_params* pr) {
+    FSGM_REQUIRE(n >= 1, "%s: n_frames must be >= 1 (got %d)", who, n);
+    FSGM_REQUIRE(I1 && I2 && disp && minC, "%s: null argument", who);
+    FSGM_REQUIRE(W >= 1 && H >= 1 && dMax >= 1, "%s: width/height/dMax must be >= 1 (got %d x %d x %d)", who, W, H, dMax);
+    *sp = prm ? *prm : fsgm_stereo_params_default();
+    FSGM_REQUIRE(sp->direction == -1 || sp->direction == 1, "%s: direction must be -1 (match at x - d) or +1 (x + d), got %d", who, sp->direction);
+    *pr = fsgm_epi_params_default();
+    pr->paths = sp->paths; pr->subpixel = sp->subpixel; pr->fb_check = sp->fb_check; pr->device = sp->device; pr->vz_to_disp = 0;
+    return FSGM_OK;
+}
+
+fsgm_status fsgm_stereo_sgm_host(int32_t n, const uint8_t* I1, const uint8_t* I2, int32_t W, int32_t H, int32_t dMax, int32_t P1,
+                                 int32_t P2, const fsgm_stereo_params* prm, uint32_t* disp, uint32_t* minC, uint8_t* conf,
+                                 uint32_t* disp2) {
+    fsgm_stereo_params sp;
+    fsgm_epi_params pr;
+    fsgm_status st = stereo_args("fsgm_stereo_sgm_host", n, I1, I2, W, H, dMax, prm, disp, minC, &sp, &pr);
+    if (st != FSGM_OK) return st;
+    std::unique_lock<std::mutex> lk;
+    fsgm_epi_plan* p = nullptr;
+    if ((st = cached_plan(lk, &p, W, H, dMax, n, pr, FSGM_SAMPLING_RECTIFIED, sp.direction)) != FSGM_OK) return st;
+    if ((st = fsgm_epi_plan_set_penalties(p, P1, P2, p->vMax)) != FSGM_OK) return st;
+    if ((st = ensure_cost_buffers(p)) != FSGM_OK) return st;
+    const size_t np = (size_t)n * p->NP;
+    StreamGuard guard(p->stream);                                // every early exit drains the stream: the copies use caller memory
+    FSGM_HIP(hipMemcpyAsync(p->dI1, I1, np, hipMemcpyHostToDevice, p->stream));
+    FSGM_HIP(hipMemcpyAsync(p->dI2, I2, np, hipMemcpyHostToDevice, p->stream));
+    if ((st = enqueue(p, FSGM_STAGE_ALL)) != FSGM_OK) return st;
+    FSGM_HIP(hipMemcpyAsync(disp, p->dBestD, np * 4, hipMemcpyDeviceToHost, p->stream));
+    FSGM_HIP(hipMemcpyAsync(minC, p->dMinC, np * 4, hipMemcpyDeviceToHost, p->stream));
+    if (pr.fb_check && conf) FSGM_HIP(hipMemcpyAsync(conf, p->dConf, np, hipMemcpyDeviceToHost, p->stream));
+    if (pr.fb_check && disp2) FSGM_HIP(hipMemcpyAsync(disp2, p->dD2, np * 4, hipMemcpyDeviceToHost, p->stream));
+    FSGM_HIP(hipStreamSynchronize(p->stream));
+    guard.dismiss();
+    return check_handoff(p);
 }
 
 // sgm(C, P1, P2): sgm.m's call shape on the MEX's aggregation + WTA (MEX semantics: include/fsgm.h)
@@ -1198,10 +1301,10 @@ fsgm_status fsgm_epipolar_maps_host(const fsgm_epi_geometry* g, int32_t W, int32
 // device-pointer entry points (include/fsgm.h): the caller's HBM arrays stand in for the plan's image, map and result buffers
 // for the length of one enqueue; the plan's stream is joined with the caller's at both ends.
 // ---------------------------------------------------------------------------------------------
-static fsgm_status epi_device_args(const char* who, int32_t n, const fsgm_epi_in* in, const fsgm_epi_out* out) {
+static fsgm_status epi_device_args(const char* who, int32_t n, const fsgm_epi_in* in, const fsgm_epi_out* out, bool linear) {
     FSGM_REQUIRE(n >= 1, "%s: n_frames must be >= 1 (got %d)", who, n);
     FSGM_REQUIRE(in && out, "%s: null argument", who);
-    FSGM_REQUIRE(in->I1 && in->I2 && in->pixelPosD0 && in->normDir && in->offset, "%s: null input", who);
+    FSGM_REQUIRE(in->I1 && in->I2 && in->pixelPosD0 && in->normDir && (in->offset || linear), "%s: null input", who);
     FSGM_REQUIRE(out->bestD && out->minC, "%s: null output", who);
     FSGM_REQUIRE(in->width >= 1 && in->height >= 1 && in->dMax >= 1, "%s: width/height/dMax must be >= 1 (got %d x %d x %d)", who,
                  in->width, in->height, in->dMax);
@@ -1233,12 +1336,17 @@ static fsgm_status epi_device_finish(fsgm_epi_plan* p, hipStream_t cs, int32_t* 
 
 // a batch on device pointers through the caller's plan p, or (p null) through the cached plan for prm
 static fsgm_status epi_run_device(const char* who, fsgm_epi_plan* p, const fsgm_epi_params* prm, int32_t n, const fsgm_epi_in* in,
-                                  const fsgm_epi_out* out, void* stream, int32_t* status) {
-    fsgm_status st = epi_device_args(who, n, in, out);
+                                  const fsgm_epi_out* out, void* stream, int32_t* status, int sampling = FSGM_SAMPLING_VZ) {
+    const bool linear = (p ? p->sampling : sampling) == FSGM_SAMPLING_LINEAR;
+    fsgm_status st = epi_device_args(who, n, in, out, linear);
     if (st != FSGM_OK) return st;
     std::unique_lock<std::mutex> lk;
-    if (!p && (st = cached_plan(lk, &p, in->width, in->height, in->dMax, n, prm ? *prm : fsgm_epi_params_default())) != FSGM_OK)
-        return st;
+    if (!p) {
+        fsgm_epi_params pr = prm ? *prm : fsgm_epi_params_default();
+        if (linear) pr.vz_to_disp = 0;
+        if ((st = cached_plan(lk, &p, in->width, in->height, in->dMax, n, pr, sampling)) != FSGM_OK) return st;
+    }
+    FSGM_REQUIRE(p->sampling != FSGM_SAMPLING_RECTIFIED, "%s: a rectified plan runs through fsgm_stereo_sgm_device", who);
     const hipStream_t cs = (hipStream_t)stream;
     FSGM_REQUIRE(n == p->batch, "%s: n_frames %d differs from the plan's batch %d", who, n, p->batch);
     FSGM_REQUIRE(in->width == p->W && in->height == p->H && in->dMax == p->D, "%s: shape %d x %d x %d differs from the plan's %d x %d x %d",
@@ -1252,18 +1360,18 @@ static fsgm_status epi_run_device(const char* who, fsgm_epi_plan* p, const fsgm_
         (st = device_check_ptr(in->I2, np, 1, dev, true, who, "I2")) != FSGM_OK ||
         (st = device_check_ptr(in->pixelPosD0, np * 16, 8, dev, true, who, "pixelPosD0")) != FSGM_OK ||
         (st = device_check_ptr(in->normDir, np * 16, 8, dev, true, who, "normDir")) != FSGM_OK ||
-        (st = device_check_ptr(in->offset, np * 8, 8, dev, true, who, "offset")) != FSGM_OK ||
+        (!linear && (st = device_check_ptr(in->offset, np * 8, 8, dev, true, who, "offset")) != FSGM_OK) ||
         (st = device_check_ptr(out->bestD, np * 4, 4, dev, true, who, "bestD")) != FSGM_OK ||
         (st = device_check_ptr(out->minC, np * 4, 4, dev, true, who, "minC")) != FSGM_OK ||
         (fb && (st = device_check_ptr(out->conf, np, 1, dev, false, who, "conf")) != FSGM_OK) ||
         (fb && (st = device_check_ptr(out->bestD2, np * 4, 4, dev, false, who, "bestD2")) != FSGM_OK) ||
         (st = device_check_ptr(status, 4, 4, dev, false, who, "status")) != FSGM_OK)
         return st;
-    if ((st = epi_device_enter(p, in->P1, in->P2, in->vMax, cs)) != FSGM_OK) return st;
+    if ((st = epi_device_enter(p, in->P1, in->P2, linear ? p->vMax : in->vMax, cs)) != FSGM_OK) return st;
     {
         Bind<uint8_t> i1(p->dI1, const_cast<uint8_t*>(in->I1)), i2(p->dI2, const_cast<uint8_t*>(in->I2));
         Bind<double> pd0(p->dPd0, const_cast<double*>(in->pixelPosD0)), nd(p->dNd, const_cast<double*>(in->normDir));
-        Bind<double> off(p->dOff, const_cast<double*>(in->offset));
+        Bind<double> off(p->dOff, linear ? nullptr : const_cast<double*>(in->offset));   // (linear: the plan's own 1.0 map)
         Bind<uint32_t> bd(p->dBestD, out->bestD), mc(p->dMinC, out->minC), d2(p->dD2, fb ? out->bestD2 : nullptr);
         Bind<uint8_t> conf(p->dConf, fb ? out->conf : nullptr);
         st = enqueue(p, FSGM_STAGE_ALL);
@@ -1280,6 +1388,47 @@ fsgm_status fsgm_epi_plan_run_device(fsgm_epi_plan* p, int32_t n, const fsgm_epi
 fsgm_status fsgm_calc_cost_sgm_device(int32_t n, const fsgm_epi_in* in, const fsgm_epi_out* out, const fsgm_epi_params* prm,
                                       void* stream, int32_t* status) {
     return epi_run_device("fsgm_calc_cost_sgm_device", nullptr, prm, n, in, out, stream, status);
+}
+
+fsgm_status fsgm_calc_cost_sgm_linear_device(int32_t n, const fsgm_epi_in* in, const fsgm_epi_out* out, const fsgm_epi_params* prm,
+                                             void* stream, int32_t* status) {
+    return epi_run_device("fsgm_calc_cost_sgm_linear_device", nullptr, prm, n, in, out, stream, status, FSGM_SAMPLING_LINEAR);
+}
+
+fsgm_status fsgm_stereo_sgm_device(int32_t n, const uint8_t* I1, const uint8_t* I2, int32_t W, int32_t H, int32_t dMax, int32_t P1,
+                                   int32_t P2, const fsgm_stereo_params* prm, uint32_t* disp, uint32_t* minC, uint8_t* conf,
+                                   uint32_t* disp2, void* stream, int32_t* status) {
+    const char* who = "fsgm_stereo_sgm_device";
+    fsgm_stereo_params sp;
+    fsgm_epi_params pr;
+    fsgm_status st = stereo_args(who, n, I1, I2, W, H, dMax, prm, disp, minC, &sp, &pr);
+    if (st != FSGM_OK) return st;
+    // checks first, also on a shape's first call: nothing is allocated for a captured stream or a pointer that is refused
+    const int dev = pr.device;
+    const size_t np = (size_t)n * (size_t)W * (size_t)H;
+    const bool fb = pr.fb_check != 0;
+    const hipStream_t cs = (hipStream_t)stream;
+    if ((st = use_device(dev)) != FSGM_OK) return st;
+    if ((st = device_check_stream(cs, who)) != FSGM_OK ||
+        (st = device_check_ptr(I1, np, 1, dev, true, who, "I1")) != FSGM_OK ||
+        (st = device_check_ptr(I2, np, 1, dev, true, who, "I2")) != FSGM_OK ||
+        (st = device_check_ptr(disp, np * 4, 4, dev, true, who, "disp")) != FSGM_OK ||
+        (st = device_check_ptr(minC, np * 4, 4, dev, true, who, "minC")) != FSGM_OK ||
+        (fb && (st = device_check_ptr(conf, np, 1, dev, false, who, "conf")) != FSGM_OK) ||
+        (fb && (st = device_check_ptr(disp2, np * 4, 4, dev, false, who, "disp2")) != FSGM_OK) ||
+        (st = device_check_ptr(status, 4, 4, dev, false, who, "status")) != FSGM_OK)
+        return st;
+    std::unique_lock<std::mutex> lk;
+    fsgm_epi_plan* p = nullptr;
+    if ((st = cached_plan(lk, &p, W, H, dMax, n, pr, FSGM_SAMPLING_RECTIFIED, sp.direction)) != FSGM_OK) return st;
+    if ((st = epi_device_enter(p, P1, P2, p->vMax, cs)) != FSGM_OK) return st;
+    {
+        Bind<uint8_t> i1(p->dI1, const_cast<uint8_t*>(I1)), i2(p->dI2, const_cast<uint8_t*>(I2));
+        Bind<uint32_t> bd(p->dBestD, disp), mc(p->dMinC, minC), d2(p->dD2, fb ? disp2 : nullptr);
+        Bind<uint8_t> cf(p->dConf, fb ? conf : nullptr);
+        st = enqueue(p, FSGM_STAGE_ALL);
+    }
+    return epi_device_finish(p, cs, status, st);
 }
 
 // ---------------------------------------------------------------------------------------------

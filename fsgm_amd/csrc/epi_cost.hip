@@ -25,6 +25,16 @@
 //
 // Recomputed apron: 64 / 60 columns x (rows + 4) / rows per segment -- 13 % at 64-row segments, 10 % at 125 -- against a
 // second kernel that re-reads the raw volume five rows deep (box5x5_sliding16_kernel: 120 MB per 1242x375x128 frame, 0.035 ms).
+//
+// Rectified form (RECT): Pd0 = (x + 1, y + 1) and direction (-1, 0) or (+1, 0), so the sample of candidate d is
+// cen2[y][clamp(x -+ d)] and a strip's samples of one row are a contiguous window of 64 + D - 1 census words (replicate clamp at
+// the image edge).  Only the fill differs: per row the workgroup puts that window into LDS once and a lane reads its 16
+// consecutive words from there -- no fp64, no gather, no maps, no row_small test.  The window is kept four times, copy c
+// shifted by c words, so that a lane whose first word sits at s reads copy s & 3 at the 16-byte aligned word s - (s & 3) as four
+// ds_read_b128.  Copies are 16 words (mod 64) apart: the lanes 4 m .. 4 m + 3 of a ds_read_b128 group read one word index in the
+// four copies, bank quad m + 4 c, and a group's m values ({0, 3, 5, 6} or {1, 2, 4, 7} mod 8) differ mod 4 -- no conflict.
+// The next row's words are requested before this row's tail and written to the other of two LDS rows a step later: one
+// workgroup barrier per row.
 #include "epi_kernels.h"
 #include "fsgm_device.h"
 #include <algorithm>
@@ -60,10 +70,15 @@ struct CbPix {
     uint32_t c1;
 };
 
-template <int NW>
-__global__ __launch_bounds__(NW * 64, 4) void epi_costbox_kernel(EpiCostArgs a, uint8_t* __restrict__ Cout, int seg_rows, uint32_t total_items) {
+// a.pd0 / nd / off / vz unused when RECT; rect_dir: -1 / +1 (RECT only)
+template <int NW, bool RECT>
+__global__ __launch_bounds__(NW * 64, 4) void epi_costbox_kernel(EpiCostArgs a, uint8_t* __restrict__ Cout, int seg_rows, uint32_t total_items, int rect_dir) {
     __shared__ __attribute__((aligned(16))) uint4 xch[NW][68];              // a wave's raw row: slots 2 .. 65, two spare either side
     __shared__ __attribute__((aligned(16))) uint4 outt[2][64][NW + 1];      // a row of C, [pixel][16-byte piece], one piece of padding
+    constexpr int REACH = 64 + 16 * NW - 1;                                  // RECT: census words a strip's samples of one row span
+    constexpr int PITCH = (REACH + 63) / 64 * 64 + 16;                       // words between the shifted copies (16 mod 64)
+    constexpr int NPRE = (REACH + NW * 64 - 1) / (NW * 64);                  // words of the window a thread fetches
+    __shared__ __attribute__((aligned(16))) uint4 win[RECT ? 2 : 1][RECT ? 4 : 1][RECT ? PITCH / 4 : 1];
     const int W = a.W, H = a.H, D = a.D;
     // Work item of this workgroup.  Workgroups go to the 8 XCDs round-robin by their linear id; the items (strip fastest, then
     // row segment, then frame) are dealt so that every XCD walks a contiguous eighth of the list: the workgroups resident on an
@@ -94,14 +109,15 @@ __global__ __launch_bounds__(NW * 64, 4) void epi_costbox_kernel(EpiCostArgs a, 
     const uint32_t W4 = 4u * (uint32_t)W;                                    // (the general path's byte offsets)
     double vz[16];                                                           // wave-uniform: scalar registers
 #pragma unroll
-    for (int k = 0; k < 16; k++) vz[k] = a.vz[d0 + k];
+    for (int k = 0; k < 16; k++) vz[k] = RECT ? 0.0 : a.vz[d0 + k];
     const double vzmax = a.vzmax;
     uint4* const myslot = &xch[w][2 + lane];
 
     auto load_pix = [&](int step) -> CbPix {
         const uint32_t i = (uint32_t)clampi(y0 - 2 + step, 0, yhi) * (uint32_t)W + (uint32_t)px;
         CbPix q;
-        q.px = p0[i]; q.py = p0[NP + i]; q.ux = nd[i]; q.uy = nd[NP + i]; q.off = of[i]; q.c1 = cen1[i];
+        if constexpr (RECT) { q.px = q.py = q.ux = q.uy = q.off = 0.0; q.c1 = cen1[i]; }
+        else { q.px = p0[i]; q.py = p0[NP + i]; q.ux = nd[i]; q.uy = nd[NP + i]; q.off = of[i]; q.c1 = cen1[i]; }
         return q;
     };
     // The fast rounding (round_clamp_small) differs from x86's (int)round(v) only where v + 0.5 reaches 2^31 (cvttsd2si
@@ -240,12 +256,59 @@ __global__ __launch_bounds__(NW * 64, 4) void epi_costbox_kernel(EpiCostArgs a, 
         hamming(c1, w1, raw.z, raw.w);
     };
 
+    // ---- RECT: the window of image 2's census row.  xb: the image column of window word 0; the lane's pixel px (its raw
+    // column, clamped) samples words (px - xb) + dir * d, all inside [0, REACH): see the launcher's comment ----
+    const int xb = rect_dir < 0 ? xs - 2 - (16 * NW - 1) : xs - 2;
+    const int s0w = rect_dir < 0 ? px - xb - d0 - 15 : px - xb + d0;         // the lowest of the lane's 16 window words
+    const int wc = s0w & 3, wq = s0w >> 2;                                   // its copy and 16-byte slot there
+    uint32_t pre[NPRE];
+    auto load_window = [&](int step) {
+        const uint32_t* row = (const uint32_t*)cen2 + (uint32_t)clampi(y0 - 2 + step, 0, yhi) * (uint32_t)W;
+#pragma unroll
+        for (int n = 0; n < NPRE; n++) {
+            const int i = (int)threadIdx.x + n * NW * 64;
+            pre[n] = i < REACH ? row[clampi(xb + i, 0, xhi)] : 0u;
+        }
+    };
+    auto fill_rect = [&](const int st, uint32_t (&pslot)[8]) {
+        uint32_t* const wrow = (uint32_t*)&win[st & 1][0][0];
+#pragma unroll
+        for (int n = 0; n < NPRE; n++) {
+            const int i = (int)threadIdx.x + n * NW * 64;
+            if (i < REACH) {
+#pragma unroll
+                for (int c = 0; c < 4; c++)
+                    if (i >= c) wrow[c * PITCH + i - c] = pre[n];            // copy c: word j = window word j + c
+            }
+        }
+        const uint32_t c1 = cur.c1;
+        load_window(min(st + 1, nsteps - 1));
+        cur = load_pix(min(st + 1, nsteps - 1));
+        __syncthreads();                                                     // every wave runs the same steps: uniform
+        const uint4* const wp = &win[st & 1][wc][wq];
+        const uint4 q0 = wp[0], q1 = wp[1], q2 = wp[2], q3 = wp[3];
+        if (st >= 1) tail(st - 1, pslot);                                    // wave-uniform
+        const uint32_t wd[16] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w, q2.x, q2.y, q2.z, q2.w, q3.x, q3.y, q3.z, q3.w};
+        uint32_t up[8], dn[8];                                               // window words in ascending order = d ascending (+1) or descending (-1)
+        if (rect_dir < 0) {                                                  // uniform
+#pragma unroll
+            for (int k = 0; k < 8; k++) { up[k] = wd[15 - k]; dn[k] = wd[7 - k]; }
+        } else {
+#pragma unroll
+            for (int k = 0; k < 8; k++) { up[k] = wd[k]; dn[k] = wd[8 + k]; }
+        }
+        hamming(c1, up, raw.x, raw.y);
+        hamming(c1, dn, raw.z, raw.w);
+    };
+
+    if constexpr (RECT) load_window(0);
     for (int base = 0; base < nsteps; base += 5) {
 #pragma unroll
         for (int k = 0; k < 5; k++)
             if (base + k < nsteps) {                                         // wave-uniform
-                if (row_small(cur)) fill(base + k, ring[(k + 4) % 5]);
-                else                fill_general(base + k, ring[(k + 4) % 5]);
+                if constexpr (RECT) fill_rect(base + k, ring[(k + 4) % 5]);
+                else if (row_small(cur)) fill(base + k, ring[(k + 4) % 5]);
+                else                     fill_general(base + k, ring[(k + 4) % 5]);
             }
     }
     // the last raw row's tail
@@ -298,7 +361,7 @@ int costbox_seg_rows(int W, int H, int D, int frames, int cus) {
     return best_rows;
 }
 
-void launch_epi_costbox(hipStream_t st, const EpiCostArgs& a, uint8_t* C, int frames) {
+static void launch_costbox(hipStream_t st, const EpiCostArgs& a, uint8_t* C, int frames, int rect_dir) {
     static const int cus = [] {
         int dev = 0, n = 0;
         if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
@@ -307,11 +370,57 @@ void launch_epi_costbox(hipStream_t st, const EpiCostArgs& a, uint8_t* C, int fr
     const int seg = costbox_seg_rows(a.W, a.H, a.D, frames, cus);
     const uint32_t total = (uint32_t)((a.W + CB_OUT - 1) / CB_OUT) * (uint32_t)((a.H + seg - 1) / seg) * (uint32_t)frames;
     dim3 grid(8u * ((total + 7u) / 8u));
-    switch (a.D >> 4) {
-#define FSGM_CB(NW) case NW: hipLaunchKernelGGL(epi_costbox_kernel<NW>, grid, dim3(NW * 64), 0, st, a, C, seg, total); break;
-        FSGM_CB(1) FSGM_CB(2) FSGM_CB(4) FSGM_CB(8) FSGM_CB(16)
+    if (rect_dir == 0) {
+        switch (a.D >> 4) {
+#define FSGM_CB(NW) case NW: hipLaunchKernelGGL((epi_costbox_kernel<NW, false>), grid, dim3(NW * 64), 0, st, a, C, seg, total, 0); break;
+            FSGM_CB(1) FSGM_CB(2) FSGM_CB(4) FSGM_CB(8) FSGM_CB(16)
 #undef FSGM_CB
+        }
+    } else {
+        switch (a.D >> 4) {
+#define FSGM_CB(NW) case NW: hipLaunchKernelGGL((epi_costbox_kernel<NW, true>), grid, dim3(NW * 64), 0, st, a, C, seg, total, rect_dir); break;
+            FSGM_CB(1) FSGM_CB(2) FSGM_CB(4) FSGM_CB(8) FSGM_CB(16)
+#undef FSGM_CB
+        }
     }
+}
+
+void launch_epi_costbox(hipStream_t st, const EpiCostArgs& a, uint8_t* C, int frames) { launch_costbox(st, a, C, frames, 0); }
+
+// Rectified pair, any dMax: raw costs of one (pixel, d) per thread into the raw volume for the box kernels
+__global__ __launch_bounds__(256) void stereo_rawcost_kernel(const uint32_t* __restrict__ cen1, const uint32_t* __restrict__ cen2,
+                                                             uint8_t* __restrict__ Craw, int W, int H, int D, int dir) {
+    const size_t NP = (size_t)W * H;
+    const size_t gid = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (gid >= NP * D) return;
+    const uint32_t p = (uint32_t)(gid / D), d = (uint32_t)(gid - (size_t)p * D);
+    const int y = (int)(p / (uint32_t)W), x = (int)(p - (uint32_t)y * (uint32_t)W);
+    const size_t fo = (size_t)blockIdx.y * NP;
+    const int x2 = clampi(x + dir * (int)d, 0, W - 1);                       // :368-375 with Pd0 = (x + 1, y + 1), u = (dir, 0)
+    Craw[fo * D + gid] = (uint8_t)__popc(cen1[fo + p] ^ cen2[fo + (size_t)y * W + x2]);   // :377-378
+}
+
+// Window words of the fused kernel (see its comment): with xq = xs - 2 + lane the lane's raw column and px = clamp(xq, 0, W - 1),
+// word (px - xb) + dir * d lies in [0, REACH) for every d < D.  Above: px <= xq, so the word is at most lane + D - 1 <= REACH - 1.
+// Below: px >= min(xq, xs) -- the clamp at W - 1 never goes below xs, a strip starts inside the image, and the clamp at 0 only
+// raises px -- and xq >= xs - 2 = xb (dir +1) or xb + D - 1 (dir -1), so the word is >= 0 (the two left apron lanes of a strip
+// reach words 0 and 1).  Copy c of the window holds every word from c upwards at index word - c, and a lane reads copy s & 3
+// from s - (s & 3) >= 0 on, 16 words up to s + 15 <= REACH - 1: all written.  The window itself is filled with the clamp on the
+// image columns, so a word's content is cen2[y][clamp(px + dir * d)].
+void launch_stereo_cost(hipStream_t st, const uint32_t* cen1, const uint32_t* cen2, uint8_t* Craw, uint8_t* C, int W, int H, int D,
+                        int direction, int frames) {
+    const int dir = direction < 0 ? -1 : 1;
+    // FSGM_COST_FUSED=0: the two-kernel form, as for launch_epi_cost
+    const bool fused = [] { const char* e = getenv("FSGM_COST_FUSED"); return !(e && e[0] == '0'); }();
+    if (fused && costbox_ok(W, H, D)) {
+        EpiCostArgs a{};
+        a.cen1 = cen1; a.cen2 = cen2; a.W = W; a.H = H; a.D = D;
+        launch_costbox(st, a, C, frames, dir);
+        return;
+    }
+    const size_t n = (size_t)W * H * D;                                      // < 2^31 (plan creation)
+    hipLaunchKernelGGL(stereo_rawcost_kernel, dim3((unsigned)((n + 255) / 256), frames), dim3(256), 0, st, cen1, cen2, Craw, W, H, D, dir);
+    launch_box5x5(st, Craw, C, W, H, D, frames);
 }
 
 }  // namespace fsgm

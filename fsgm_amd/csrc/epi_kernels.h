@@ -129,6 +129,8 @@ struct FbArgs {                // forward-backward check (calc_cost_sgm.cpp:429-
     uint8_t* conf;            // [frames][NP] out: 1 = consistent
     double vMax;
     int W, H, n, thr;
+    int linear = 0;           // the reference built without USE_VZIND: the displacement along the direction is D1 / 256 itself (:453, :508)
+    int rect = 0;             // +-1: rectified pair -- Pd0 = (x + 1, y + 1), direction (rect, 0) computed in the kernel, pd0 / nd / off not read
 };
 
 enum { AGG_PACKED_NOWRAP = 0, AGG_PACKED_WRAP = 1, AGG_GENERIC = 2, AGG_SWEEP = 3, AGG_PAIRS = 4, AGG_BAND = 5 };
@@ -139,6 +141,11 @@ void launch_epi_cost(hipStream_t st, const EpiCostArgs& a, uint8_t* C, int frame
 // the cost stage as one kernel (epi_cost.hip): raw costs + 5x5 box mean, a.Craw unused
 bool costbox_ok(int W, int H, int D);
 void launch_epi_costbox(hipStream_t st, const EpiCostArgs& a, uint8_t* C, int frames);
+// the cost stage of a rectified pair (epi_cost.hip): sample cen2[y][clamp(x + direction * d)], direction = -1 / +1; D = 16 << k
+// as one kernel, any other D as a raw-cost kernel into Craw and the box kernels
+void launch_stereo_cost(hipStream_t st, const uint32_t* cen1, const uint32_t* cen2, uint8_t* Craw, uint8_t* C, int W, int H, int D,
+                        int direction, int frames);
+void launch_box5x5(hipStream_t st, const uint8_t* Craw, uint8_t* C, int W, int H, int D, int frames);
 int  costbox_selftest(hipStream_t st);      // 0: the mean's fp16 multiply is exact on this device; > 0: mismatches; < 0: could not run
 void launch_aggregate(hipStream_t st, AggArgs a, int paths, int frames, int kernel_kind);
 void launch_wta(hipStream_t st, const WtaArgs& a, int frames, bool packed);

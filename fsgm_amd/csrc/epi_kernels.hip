@@ -1126,9 +1126,29 @@ __global__ __launch_bounds__(256) void wta_generic_kernel(WtaArgs a) {
 // =============================================================================================
 __device__ __forceinline__ double fb_displacement(const FbArgs& a, size_t f, int p, uint32_t d1) {
     const double d = __ddiv_rn((double)d1, 256.0);                                 // :447 / :502
+    if (a.linear) return d;                                                        // :453 / :508 (built without USE_VZIND)
     const double r = __dmul_rn(__ddiv_rn(d, (double)a.n), a.vMax);
     const double vz = __ddiv_rn(r, __dsub_rn(1.0, r));
     return __dmul_rn(a.off[f * (size_t)a.W * a.H + p], vz);                        // :451 / :506
+}
+
+// start position - 1 (:456-457 / :510-511) and direction (:459-460 / :513-514) of pixel p: read from the maps, or those of a
+// rectified pair -- Pd0 = (x + 1, y + 1), direction (+-1, 0) -- through the same fp64 operations
+struct FbRay { double bx, by, ux, uy; };
+__device__ __forceinline__ FbRay fb_ray(const FbArgs& a, size_t f, int p) {
+    const int NP = a.W * a.H;
+    FbRay r;
+    if (a.rect) {
+        const int y = p / a.W, x = p - y * a.W;
+        r.bx = __dsub_rn((double)(x + 1), 1.0); r.by = __dsub_rn((double)(y + 1), 1.0);
+        r.ux = (double)a.rect; r.uy = 0.0;
+    } else {
+        const double* p0 = a.pd0 + f * 2 * (size_t)NP;
+        const double* nd = a.nd + f * 2 * (size_t)NP;
+        r.bx = __dsub_rn(p0[p], 1.0); r.by = __dsub_rn(p0[NP + p], 1.0);
+        r.ux = nd[p]; r.uy = nd[NP + p];
+    }
+    return r;
 }
 
 __global__ __launch_bounds__(256) void fb_scatter_kernel(FbArgs a) {
@@ -1138,10 +1158,9 @@ __global__ __launch_bounds__(256) void fb_scatter_kernel(FbArgs a) {
     const size_t f = blockIdx.y;
     const uint32_t d1 = a.D1[f * (size_t)NP + p];
     const double d = fb_displacement(a, f, p, d1);
-    const double* p0 = a.pd0 + f * 2 * (size_t)NP;
-    const double* nd = a.nd + f * 2 * (size_t)NP;
-    const int p2x = f64_to_i32_x86(__dadd_rn(__dsub_rn(p0[p], 1.0), __dmul_rn(d, nd[p])));            // :462
-    const int p2y = f64_to_i32_x86(__dadd_rn(__dsub_rn(p0[NP + p], 1.0), __dmul_rn(d, nd[NP + p])));  // :463
+    const FbRay r = fb_ray(a, f, p);
+    const int p2x = f64_to_i32_x86(__dadd_rn(r.bx, __dmul_rn(d, r.ux)));            // :462
+    const int p2y = f64_to_i32_x86(__dadd_rn(r.by, __dmul_rn(d, r.uy)));            // :463
     uint32_t* enc = a.D2enc + f * (size_t)NP;
 #pragma unroll
     for (int dy = 0; dy <= 1; dy++)
@@ -1163,10 +1182,9 @@ __global__ __launch_bounds__(256) void fb_check_kernel(FbArgs a) {
     a.D2[f * (size_t)NP + p] = mine ? mine - 1u : INVALID;                         // plhs[3] in natural form
     const uint32_t d1 = a.D1[f * (size_t)NP + p];
     const double d = fb_displacement(a, f, p, d1);
-    const double* p0 = a.pd0 + f * 2 * (size_t)NP;
-    const double* nd = a.nd + f * 2 * (size_t)NP;
-    const int p2x = round_to_i32_x86(__dadd_rn(__dsub_rn(p0[p], 1.0), __dmul_rn(d, nd[p])));            // :516
-    const int p2y = round_to_i32_x86(__dadd_rn(__dsub_rn(p0[NP + p], 1.0), __dmul_rn(d, nd[NP + p])));  // :517
+    const FbRay r = fb_ray(a, f, p);
+    const int p2x = round_to_i32_x86(__dadd_rn(r.bx, __dmul_rn(d, r.ux)));          // :516
+    const int p2y = round_to_i32_x86(__dadd_rn(r.by, __dmul_rn(d, r.uy)));          // :517
     uint8_t ok = 1;                                                                // :485
     if (p2x < 0 || p2x > a.W - 1 || p2y < 0 || p2y > a.H - 1) ok = 0;              // :519-522
     else {
@@ -1234,17 +1252,23 @@ void launch_epi_cost(hipStream_t st, const EpiCostArgs& a, uint8_t* C, int frame
         hipLaunchKernelGGL(epi_rawcost_px_kernel, dim3((unsigned)(((long long)a.W * a.H + 255) / 256), frames), dim3(256), 0, st, a);
     } else if ((a.D & 3) == 0) hipLaunchKernelGGL(epi_rawcost_kernel<true>, grid, dim3(256), 0, st, a);
     else                       hipLaunchKernelGGL(epi_rawcost_kernel<false>, grid, dim3(256), 0, st, a);
+    launch_box5x5(st, a.Craw, C, a.W, a.H, a.D, frames);
+}
+
+// the 5x5 box mean of a raw volume in HBM (the two-kernel form of the cost stage)
+void launch_box5x5(hipStream_t st, const uint8_t* Craw, uint8_t* C, int W, int H, int D, int frames) {
     static const bool box16 = [] { const char* e = getenv("FSGM_BOX16"); return !(e && e[0] == '0'); }();   // A/B switch
-    if (box16 && (a.D & 15) == 0 && a.D <= 1024) {
-        const int cols = 256 / (a.D >> 4);
-        dim3 g2((a.W + cols - 1) / cols, (a.H + BOX_ROWS - 1) / BOX_ROWS, frames);
-        hipLaunchKernelGGL(box5x5_sliding16_kernel, g2, dim3(256), 0, st, (const uint8_t*)a.Craw, C, a.W, a.H, a.D);
-    } else if ((a.D & 3) == 0 && a.D <= 1024) {
-        const int cols = 256 / (a.D >> 2);
-        dim3 g2((a.W + cols - 1) / cols, (a.H + BOX_ROWS - 1) / BOX_ROWS, frames);
-        hipLaunchKernelGGL(box5x5_sliding_kernel, g2, dim3(256), 0, st, (const uint8_t*)a.Craw, C, a.W, a.H, a.D);
+    if (box16 && (D & 15) == 0 && D <= 1024) {
+        const int cols = 256 / (D >> 4);
+        dim3 g2((W + cols - 1) / cols, (H + BOX_ROWS - 1) / BOX_ROWS, frames);
+        hipLaunchKernelGGL(box5x5_sliding16_kernel, g2, dim3(256), 0, st, Craw, C, W, H, D);
+    } else if ((D & 3) == 0 && D <= 1024) {
+        const int cols = 256 / (D >> 2);
+        dim3 g2((W + cols - 1) / cols, (H + BOX_ROWS - 1) / BOX_ROWS, frames);
+        hipLaunchKernelGGL(box5x5_sliding_kernel, g2, dim3(256), 0, st, Craw, C, W, H, D);
     } else {
-        hipLaunchKernelGGL(box5x5_kernel, grid, dim3(256), 0, st, (const uint8_t*)a.Craw, C, a.W, a.H, a.D);
+        const long long n = (long long)W * H * ((D + 3) / 4);
+        hipLaunchKernelGGL(box5x5_kernel, dim3((unsigned)((n + 255) / 256), frames), dim3(256), 0, st, Craw, C, W, H, D);
     }
 }
 

@@ -96,6 +96,95 @@ def calc_cost_sgm(I1, I2, dMax, vMax, pixelPosD0, normlizeDirection, offsetFromP
                                return_volumes=return_volumes, fb_check=fb_check)[0]
 
 
+def calc_cost_sgm_linear_batch(frames, dMax, P1, P2, *, paths=4, subpixel=1, device=0, return_volumes=False, fb_check=0):
+    """frames: list of (I1, I2, pixelPosD0, normDir) of one shape through fsgm_calc_cost_sgm_linear_batch_host."""
+    lib = _lib.load()
+    n = len(frames)
+    if n == 0:
+        return []
+    ins, outs, keep, res = (EpiIn * n)(), (EpiOut * n)(), [], []
+    H, W = np.asarray(frames[0][0]).shape
+    D = int(dMax)
+    for i, (I1, I2, pd0, nd) in enumerate(frames):
+        I1, I2 = _u8img(I1, "I1"), _u8img(I2, "I2")
+        if I1.shape != (H, W) or I2.shape != (H, W):
+            raise ValueError("all images of a batch must share one shape")
+        pd0 = _f64(pd0, (2, H, W), "pixelPosD0")
+        nd = _f64(nd, (2, H, W), "normlizeDirection")
+        bestD, minC = np.zeros((H, W), np.uint32), np.zeros((H, W), np.uint32)
+        Cv = np.zeros((H, W, D), np.uint8) if return_volumes else None
+        Sv = np.zeros((H, W, D), np.uint32) if return_volumes else None
+        conf = np.zeros((H, W), np.uint8) if fb_check else None
+        bestD2 = np.zeros((H, W), np.uint32) if fb_check else None
+        keep.append((I1, I2, pd0, nd))
+        e = ins[i]
+        e.I1, e.I2, e.width, e.height, e.dMax, e.vMax = ptr(I1), ptr(I2), W, H, D, 0.0
+        e.pixelPosD0, e.normDir, e.offset, e.P1, e.P2 = ptr(pd0), ptr(nd), None, int(P1), int(P2)
+        o = outs[i]
+        o.bestD, o.minC, o.C, o.S, o.conf, o.bestD2 = ptr(bestD), ptr(minC), ptr(Cv), ptr(Sv), ptr(conf), ptr(bestD2)
+        r = (bestD, minC, Cv, Sv) if return_volumes else (bestD, minC)
+        res.append(r + (conf, bestD2) if fb_check else r)
+    prm = _params(paths, subpixel, 0, device, fb_check)
+    check(lib.fsgm_calc_cost_sgm_linear_batch_host(n, ins, outs, C.byref(prm)))
+    return res
+
+
+def calc_cost_sgm_linear(I1, I2, dMax, pixelPosD0, normlizeDirection, P1, P2, *, paths=4, subpixel=1, fb_check=0, device=0,
+                         return_volumes=False):
+    """[bestD, minC] of calc_cost_sgm.cpp built without its line 4 (USE_VZIND): candidate d is sampled d pixels along the
+    per-pixel direction (:368-375), bestD is the index * 256 and never converted.  I1, I2 (height, width) uint8, pixelPosD0 and
+    normlizeDirection (2, height, width) float64 (1-based start positions, as for calc_cost_sgm).  fb_check=1 also returns
+    (conf, bestD2) of the forward-backward check on bestD / 256 (:429-536)."""
+    return calc_cost_sgm_linear_batch([(I1, I2, pixelPosD0, normlizeDirection)], dMax, P1, P2, paths=paths, subpixel=subpixel,
+                                      device=device, return_volumes=return_volumes, fb_check=fb_check)[0]
+
+
+def _stereo_params(paths, subpixel, direction, fb_check, device):
+    if int(direction) not in (-1, 1):
+        raise ValueError(f"direction must be -1 (the match lies at x - d) or +1 (x + d), got {direction!r}")
+    if int(paths) not in (4, 8):
+        raise ValueError(f"paths must be 4 or 8 (got {paths!r})")
+    p = _lib.StereoParams()
+    p.paths, p.subpixel, p.fb_check, p.direction, p.device = int(paths), int(subpixel), int(bool(fb_check)), int(direction), int(device)
+    return p
+
+
+def stereo_sgm(left, right, dMax, P1=6, P2=64, *, paths=4, subpixel=1, direction=-1, fb_check=0, device=0):
+    """disp, minC = stereo_sgm(left, right, dMax): semi-global matching of a rectified pair.  left, right (height, width) uint8
+    or a batch (N, height, width); disp uint32 = disparity * 256 (whole disparities with subpixel=0), minC uint32, of the
+    images' shape.  direction=-1: `left` is the left view and its match in `right` lies at x - d; +1: at x + d.  fb_check=1
+    also returns (conf, disp2): the reference's forward-backward check (threshold 2 on the * 256 values; dMax <= 511)."""
+    left, right = np.asarray(left), np.asarray(right)
+    if left.dtype != np.uint8 or right.dtype != np.uint8 or left.ndim not in (2, 3):
+        raise TypeError(f"left / right must be uint8 arrays (height, width) or (N, height, width) (got {left.dtype} {left.shape})")
+    if right.shape != left.shape:
+        raise TypeError(f"right must have left's shape {left.shape} (got {right.shape})")
+    if int(dMax) < 1:
+        raise ValueError(f"dMax must be >= 1 (got {dMax!r})")
+    prm = _stereo_params(paths, subpixel, direction, fb_check, device)
+    lib = _lib.load()
+    left, right = np.ascontiguousarray(left), np.ascontiguousarray(right)
+    H, W = left.shape[-2:]
+    n = 1 if left.ndim == 2 else left.shape[0]
+    if n == 0:
+        raise ValueError("empty batch")
+    disp, minC = np.zeros(left.shape, np.uint32), np.zeros(left.shape, np.uint32)
+    conf = np.zeros(left.shape, np.uint8) if fb_check else None
+    disp2 = np.zeros(left.shape, np.uint32) if fb_check else None
+    check(lib.fsgm_stereo_sgm_host(n, ptr(left), ptr(right), W, H, int(dMax), int(P1), int(P2), C.byref(prm), ptr(disp), ptr(minC),
+                                   ptr(conf), ptr(disp2)))
+    return (disp, minC, conf, disp2) if fb_check else (disp, minC)
+
+
+def stereo_maps(width, height, direction=-1):
+    """(pixelPosD0, normlizeDirection) that calc_cost_sgm_linear takes for what stereo_sgm computes: Pd0 = (x + 1, y + 1),
+    direction (direction, 0)."""
+    yy, xx = np.mgrid[0:int(height), 0:int(width)].astype(np.float64)
+    pd0 = np.ascontiguousarray(np.stack([xx + 1.0, yy + 1.0]))
+    nd = np.ascontiguousarray(np.stack([np.full_like(xx, float(direction)), np.zeros_like(xx)]))
+    return pd0, nd
+
+
 def sgm(Cvol, P1=7, P2=100, *, paths=4, device=0, return_sum=False):
     """[bestD, minC] = sgm(C, P1, P2): sgm.m's call shape (sgm.m:1, defaults :4-10; test.m:36 passes 6, 64) on the MEX's
     aggregation and WTA.  C: (height, width, dMax) uint8.  bestD = disparity index * 256 (MEX parabola).  MEX semantics
@@ -124,14 +213,22 @@ def census(img, *, device=0):
 class EpiPlan:
     """Device-resident plan: `batch` frames of width x height x dMax stay in HBM across calls."""
 
-    def __init__(self, width, height, dMax, batch=1, *, paths=4, subpixel=1, vz_to_disp=1, device=0, fb_check=0):
+    def __init__(self, width, height, dMax, batch=1, *, paths=4, subpixel=1, vz_to_disp=1, device=0, fb_check=0,
+                 sampling=_lib.SAMPLING_VZ, direction=-1):
+        """sampling: _lib.SAMPLING_VZ (the reference as shipped), SAMPLING_LINEAR (its build without USE_VZIND: upload() takes
+        off=None) or SAMPLING_RECTIFIED (a rectified pair with match at x + direction * d: upload_images() only, no maps)."""
         self.lib = _lib.load()
         self.W, self.H, self.D, self.batch, self.paths = int(width), int(height), int(dMax), int(batch), int(paths)
         self.device, self.fb_check = int(device), int(fb_check)
         self.penalties = (6, 64, 0.3)                        # (P1, P2, vMax) of a fresh plan (epipolar_sgm_of.m:16,19)
         self._h = C.c_void_p()
+        self.sampling = int(sampling)
         prm = _params(paths, subpixel, vz_to_disp, device, fb_check)
-        check(self.lib.fsgm_epi_plan_create(C.byref(self._h), self.W, self.H, self.D, self.batch, C.byref(prm)))
+        if self.sampling == _lib.SAMPLING_VZ:
+            check(self.lib.fsgm_epi_plan_create(C.byref(self._h), self.W, self.H, self.D, self.batch, C.byref(prm)))
+        else:
+            check(self.lib.fsgm_epi_plan_create_sampling(C.byref(self._h), self.W, self.H, self.D, self.batch, C.byref(prm),
+                                                         self.sampling, int(direction)))
 
     def close(self):
         if self._h:
@@ -165,8 +262,14 @@ class EpiPlan:
         I1, I2 = _u8img(I1, "I1"), _u8img(I2, "I2")
         pd0 = _f64(pd0, (2, self.H, self.W), "pixelPosD0")
         nd = _f64(nd, (2, self.H, self.W), "normlizeDirection")
-        off = _f64(off, (self.H, self.W), "offsetFromPosD0")
+        off = None if off is None and self.sampling == _lib.SAMPLING_LINEAR else _f64(off, (self.H, self.W), "offsetFromPosD0")
         check(self.lib.fsgm_epi_plan_upload(self._h, frame, ptr(I1), ptr(I2), ptr(pd0), ptr(nd), ptr(off)))
+
+    def upload_images(self, frame, I1, I2):
+        I1, I2 = _u8img(I1, "I1"), _u8img(I2, "I2")
+        if I1.shape != (self.H, self.W) or I2.shape != (self.H, self.W):
+            raise TypeError(f"images must have shape {(self.H, self.W)}")
+        check(self.lib.fsgm_epi_plan_upload_images(self._h, frame, ptr(I1), ptr(I2)))
 
     def upload_cost(self, frame, Cvol):
         Cvol = np.ascontiguousarray(Cvol)

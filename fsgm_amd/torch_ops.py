@@ -7,6 +7,7 @@ points of include/fsgm.h ("Device-pointer entry points") as torch custom ops and
 
 No host<->device copy and no host wait once a plan for the shape exists: the work is queued behind what the current stream
 already holds, and what is queued on that stream afterwards runs after it.  Ops registered: fsgm::calc_cost_sgm,
+fsgm::calc_cost_sgm_linear, fsgm::stereo_sgm,
 fsgm::epipolar_sgm_of, fsgm::pyramidal_sgm, fsgm::pyramidal_sgm_ng, fsgm::epipolar_flow_pp, fsgm::pyramidal_flow_pp (each also returns a 0-d int32
 status tensor: 0, or FSGM_ERR_HIP when an aggregation hand-off gave up; check=True in the wrappers synchronises and raises
 on it), fsgm::epi_postprocess (status FSGM_ERR_INVALID when a D1 value is negative), fsgm::vmf and fsgm::flow_fb_check.
@@ -23,8 +24,8 @@ from typing import List, Tuple
 import numpy as np
 
 from . import _lib
-from ._lib import EpiIn, EpiOut, EpiParams, FsgmError
-from .epi import EpiGeometry, _params as _epi_params
+from ._lib import EpiIn, EpiOut, EpiParams, FsgmError, StereoParams
+from .epi import EpiGeometry, _params as _epi_params, _stereo_params
 from .post import _bind as _bind_post
 from .pyramid import PyramidParams, NgPyramidParams, FLOW_PP_FIELDS, MATCHERS, _bind as _bind_pyramid, _bind_flow_pp, _bind_ng
 
@@ -57,6 +58,8 @@ _bind_ng(_L)
 _bind_post(_L)
 _bind_flow_pp(_L)
 _L.fsgm_calc_cost_sgm_device.argtypes = [_i32, C.POINTER(EpiIn), C.POINTER(EpiOut), C.POINTER(EpiParams), _vp, _vp]
+_L.fsgm_calc_cost_sgm_linear_device.argtypes = [_i32, C.POINTER(EpiIn), C.POINTER(EpiOut), C.POINTER(EpiParams), _vp, _vp]
+_L.fsgm_stereo_sgm_device.argtypes = [_i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, C.POINTER(StereoParams), _vp, _vp, _vp, _vp, _vp, _vp]
 _L.fsgm_epi_plan_run_device.argtypes = [_vp, _i32, C.POINTER(EpiIn), C.POINTER(EpiOut), _vp, _vp]
 _L.fsgm_epipolar_sgm_of_device.argtypes = [_i32, _vp, _vp, _i32, _i32, _i32, C.POINTER(EpiGeometry), _i32, C.c_double,
                                            C.POINTER(EpiParams), _vp, _vp, _vp, _vp]
@@ -148,6 +151,58 @@ def _(I1, I2, pd0, nd, off, dMax, vMax, P1, P2, paths, subpixel, vz_to_disp, fb_
     return (_u32((N, H, W), dev), _u32((N, H, W), dev),
             torch.empty((N, H, W) if fb_check else (0,), dtype=torch.uint8, device=dev),
             _u32((N, H, W) if fb_check else (0,), dev), _status(dev))
+
+
+def _fb_outputs(N, H, W, fb_check, dev):
+    return (torch.empty((N, H, W) if fb_check else (0,), dtype=torch.uint8, device=dev), _u32((N, H, W) if fb_check else (0,), dev))
+
+
+@torch.library.custom_op("fsgm::calc_cost_sgm_linear", mutates_args=())
+def _calc_cost_sgm_linear_op(I1: torch.Tensor, I2: torch.Tensor, pd0: torch.Tensor, nd: torch.Tensor, dMax: int, P1: int, P2: int,
+                             paths: int, subpixel: int,
+                             fb_check: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    N, H, W = I1.shape
+    dev = I1.device
+    I1, I2, pd0, nd = (_ready(t) for t in (I1, I2, pd0, nd))
+    bestD, minC, status = _u32((N, H, W), dev), _u32((N, H, W), dev), _status(dev)
+    conf, bestD2 = _fb_outputs(N, H, W, fb_check, dev)
+    e, o = EpiIn(), EpiOut()
+    e.I1, e.I2, e.width, e.height, e.dMax, e.vMax = _p(I1), _p(I2), W, H, int(dMax), 0.0
+    e.pixelPosD0, e.normDir, e.offset, e.P1, e.P2 = _p(pd0), _p(nd), None, int(P1), int(P2)
+    o.bestD, o.minC = _p(bestD), _p(minC)
+    if fb_check:
+        o.conf, o.bestD2 = _p(conf), _p(bestD2)
+    prm = _epi_params(paths, subpixel, 0, dev.index, fb_check)
+    _call(dev, _L.fsgm_calc_cost_sgm_linear_device, N, C.byref(e), C.byref(o), C.byref(prm), _stream(dev), _p(status))
+    return bestD, minC, conf, bestD2, status
+
+
+@_calc_cost_sgm_linear_op.register_fake
+def _(I1, I2, pd0, nd, dMax, P1, P2, paths, subpixel, fb_check):
+    N, H, W = I1.shape
+    dev = I1.device
+    return (_u32((N, H, W), dev), _u32((N, H, W), dev)) + _fb_outputs(N, H, W, fb_check, dev) + (_status(dev),)
+
+
+@torch.library.custom_op("fsgm::stereo_sgm", mutates_args=())
+def _stereo_sgm_op(left: torch.Tensor, right: torch.Tensor, dMax: int, P1: int, P2: int, paths: int, subpixel: int, direction: int,
+                   fb_check: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    N, H, W = left.shape
+    dev = left.device
+    left, right = _ready(left), _ready(right)
+    disp, minC, status = _u32((N, H, W), dev), _u32((N, H, W), dev), _status(dev)
+    conf, disp2 = _fb_outputs(N, H, W, fb_check, dev)
+    prm = _stereo_params(paths, subpixel, direction, fb_check, dev.index)
+    _call(dev, _L.fsgm_stereo_sgm_device, N, _p(left), _p(right), W, H, int(dMax), int(P1), int(P2), C.byref(prm), _p(disp), _p(minC),
+          _p(conf) if fb_check else None, _p(disp2) if fb_check else None, _stream(dev), _p(status))
+    return disp, minC, conf, disp2, status
+
+
+@_stereo_sgm_op.register_fake
+def _(left, right, dMax, P1, P2, paths, subpixel, direction, fb_check):
+    N, H, W = left.shape
+    dev = left.device
+    return (_u32((N, H, W), dev), _u32((N, H, W), dev)) + _fb_outputs(N, H, W, fb_check, dev) + (_status(dev),)
 
 
 @torch.library.custom_op("fsgm::epipolar_sgm_of", mutates_args=())
@@ -378,6 +433,49 @@ def calc_cost_sgm(I1, I2, dMax, vMax, pixelPosD0, normlizeDirection, offsetFromP
                                                                       float(vMax), int(P1), int(P2), int(paths), int(subpixel),
                                                                       int(vz_to_disp), int(fb_check))
     outs = (bestD, minC, conf, bestD2) if fb_check else (bestD, minC)
+    return _finish(outs, status, batched, check, return_status)
+
+
+def calc_cost_sgm_linear(I1, I2, dMax, pixelPosD0, normlizeDirection, P1, P2, *, paths=4, subpixel=1, fb_check=0, check=False,
+                         return_status=False):
+    """[bestD, minC] as fsgm_amd.calc_cost_sgm_linear (the reference built without USE_VZIND), on torch tensors on the GPU.  One
+    frame: I1, I2 (H, W) uint8, pixelPosD0 / normlizeDirection (2, H, W) float64; a batch: the same with a leading N.  Outputs,
+    fb_check, check and return_status as calc_cost_sgm."""
+    _tensors({"I1": (I1, torch.uint8), "I2": (I2, torch.uint8), "pixelPosD0": (pixelPosD0, torch.float64),
+              "normlizeDirection": (normlizeDirection, torch.float64)})
+    if I1.dim() not in (2, 3):
+        raise TypeError(f"I1 must be (H, W) or (N, H, W) (got {tuple(I1.shape)})")
+    batched = I1.dim() == 3
+    lead = tuple(I1.shape[:-2])
+    H, W = I1.shape[-2:]
+    _shape("I2", I2, lead + (H, W))
+    _shape("pixelPosD0", pixelPosD0, lead + (2, H, W))
+    _shape("normlizeDirection", normlizeDirection, lead + (2, H, W))
+    if not batched:
+        I1, I2, pixelPosD0, normlizeDirection = (t.unsqueeze(0) for t in (I1, I2, pixelPosD0, normlizeDirection))
+    bestD, minC, conf, bestD2, status = torch.ops.fsgm.calc_cost_sgm_linear(I1, I2, pixelPosD0, normlizeDirection, int(dMax), int(P1),
+                                                                             int(P2), int(paths), int(subpixel), int(fb_check))
+    outs = (bestD, minC, conf, bestD2) if fb_check else (bestD, minC)
+    return _finish(outs, status, batched, check, return_status)
+
+
+def stereo_sgm(left, right, dMax, P1=6, P2=64, *, paths=4, subpixel=1, direction=-1, fb_check=0, check=False, return_status=False):
+    """disp, minC = stereo_sgm(left, right, dMax) as fsgm_amd.stereo_sgm, on torch tensors on the GPU: left, right (H, W) uint8
+    or a batch (N, H, W); disp (disparity * 256) and minC uint32 of the same shape, plus conf uint8 / disp2 uint32 with
+    fb_check=1.  The outputs stay in HBM; the work is queued on the current stream."""
+    _tensors({"left": (left, torch.uint8), "right": (right, torch.uint8)})
+    if left.dim() not in (2, 3):
+        raise TypeError(f"left must be (H, W) or (N, H, W) (got {tuple(left.shape)})")
+    _shape("right", right, left.shape)
+    if int(dMax) < 1:
+        raise ValueError(f"dMax must be >= 1 (got {dMax!r})")
+    _stereo_params(paths, subpixel, direction, fb_check, 0)                 # the value checks, before anything is queued
+    batched = left.dim() == 3
+    if not batched:
+        left, right = left.unsqueeze(0), right.unsqueeze(0)
+    disp, minC, conf, disp2, status = torch.ops.fsgm.stereo_sgm(left, right, int(dMax), int(P1), int(P2), int(paths), int(subpixel),
+                                                                 int(direction), int(bool(fb_check)))
+    outs = (disp, minC, conf, disp2) if fb_check else (disp, minC)
     return _finish(outs, status, batched, check, return_status)
 
 

@@ -97,6 +97,41 @@ fsgm_status fsgm_calc_cost_sgm_host(const fsgm_epi_in* in, const fsgm_epi_out* o
 fsgm_status fsgm_calc_cost_sgm_batch_host(int32_t n_frames, const fsgm_epi_in* in,
                                           const fsgm_epi_out* out, const fsgm_epi_params* prm);
 
+/* calc_cost_sgm as the reference builds it WITHOUT line 4 (#define USE_VZIND): a plain 1-D matcher along an arbitrary direction
+ * field.  Candidate d is sampled d pixels along the per-pixel direction,
+ *   x2 = clamp((int)round((Pd0x - 1) + d * ux), 0, W - 1), likewise y                     (calc_cost_sgm.cpp:368-375),
+ * no vz -> disparity conversion runs (:592-594: bestD is the index * 256, truncating) and the forward-backward check works on
+ * bestD / 256 directly (:452-453, :507-508).  Same structs as the vz-index entry points: in->vMax and in->offset are accepted
+ * and ignored (offset may be NULL), prm->vz_to_disp is ignored; paths, subpixel, device and fb_check are honoured
+ * (fb_check = 1 needs dMax <= 511).  Box mean, aggregation, WTA and parabola are those of fsgm_calc_cost_sgm_host. */
+fsgm_status fsgm_calc_cost_sgm_linear_host(const fsgm_epi_in* in, const fsgm_epi_out* out,
+                                           const fsgm_epi_params* prm);
+fsgm_status fsgm_calc_cost_sgm_linear_batch_host(int32_t n_frames, const fsgm_epi_in* in,
+                                                 const fsgm_epi_out* out, const fsgm_epi_params* prm);
+
+/* ------------------------------------------------------------------------------------------
+ * Rectified stereo: a left/right pair in, a disparity map out.  The linear matcher above with Pd0 = (x + 1, y + 1) and
+ * direction (direction, 0) -- the sample of candidate d is cen2[y][clamp(x + direction * d, 0, W - 1)] -- without any map:
+ * the cost stage is a kernel of its own and only the two images are uploaded.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct {
+    int32_t paths;        /* 4 or 8, as fsgm_epi_params */
+    int32_t subpixel;     /* 1 = parabola refinement (disparity in 1/256 steps), 0 = whole disparities * 256 */
+    int32_t fb_check;     /* 1 = the reference's forward-backward check (calc_cost_sgm.cpp:429-536, threshold 2): conf, disp2; dMax <= 511 */
+    int32_t direction;    /* -1: I1 is the left view, the match in I2 lies at x - d; +1: the match lies at x + d */
+    int32_t device;       /* HIP device ordinal */
+} fsgm_stereo_params;
+
+fsgm_stereo_params fsgm_stereo_params_default(void);   /* 4, 1, 0, -1, 0 */
+
+/* n_frames contiguous pairs I1 / I2 u8 [n][H][W] -> disp u32 [n][H][W] (disparity * 256) and minC u32 [n][H][W]; with
+ * fb_check = 1 also conf u8 [n][H][W] (1 = consistent) and disp2 u32 [n][H][W] (second view, 512<<8 where invalid), each of
+ * which may be NULL; without fb_check they are not written.  prm may be NULL (the defaults).  Aggregation pipelines are
+ * selected as for fsgm_calc_cost_sgm_batch_host. */
+fsgm_status fsgm_stereo_sgm_host(int32_t n_frames, const uint8_t* I1, const uint8_t* I2, int32_t width, int32_t height,
+                                 int32_t dMax, int32_t P1, int32_t P2, const fsgm_stereo_params* prm, uint32_t* disp,
+                                 uint32_t* minC, uint8_t* conf, uint32_t* disp2);
+
 /* ---- device-resident plan: buffers for `batch` frames stay in HBM across calls ---- */
 typedef struct fsgm_epi_plan fsgm_epi_plan;
 
@@ -108,6 +143,15 @@ typedef struct fsgm_epi_plan fsgm_epi_plan;
 
 fsgm_status fsgm_epi_plan_create(fsgm_epi_plan** plan, int32_t width, int32_t height,
                                  int32_t dMax, int32_t batch, const fsgm_epi_params* prm);
+/* How a plan samples candidate d, fixed at creation.  fsgm_epi_plan_create makes FSGM_SAMPLING_VZ plans. */
+#define FSGM_SAMPLING_VZ        0   /* offset * vzInd(d) along the direction: the reference as shipped (USE_VZIND) */
+#define FSGM_SAMPLING_LINEAR    1   /* d pixels along the direction: the reference without USE_VZIND; the offset map is unused
+                                       (fsgm_epi_plan_upload accepts NULL for it), vz_to_disp is off */
+#define FSGM_SAMPLING_RECTIFIED 2   /* rectified pair: Pd0 = (x + 1, y + 1), direction (direction, 0), direction = -1 or +1.  The plan
+                                       never allocates coordinate or offset maps and takes images only
+                                       (fsgm_epi_plan_upload_images); its FSGM_STAGE_COST is the rectified cost kernel */
+fsgm_status fsgm_epi_plan_create_sampling(fsgm_epi_plan** plan, int32_t width, int32_t height, int32_t dMax, int32_t batch,
+                                          const fsgm_epi_params* prm, int32_t sampling, int32_t direction);
 void        fsgm_epi_plan_destroy(fsgm_epi_plan* plan);
 fsgm_status fsgm_epi_plan_set_penalties(fsgm_epi_plan* plan, int32_t P1, int32_t P2, double vMax);
 /* Aggregation strategy: 0 = auto, 1 = the per-direction line kernels, 2 = the fused pipeline whenever eligible
@@ -136,6 +180,8 @@ fsgm_status fsgm_epi_plan_set_agg_mode(fsgm_epi_plan* plan, int32_t mode);
 fsgm_status fsgm_epi_plan_upload(fsgm_epi_plan* plan, int32_t frame, const uint8_t* I1,
                                  const uint8_t* I2, const double* pixelPosD0,
                                  const double* normDir, const double* offset);
+/* the image pair of slot `frame` alone (any plan; all a rectified plan takes) */
+fsgm_status fsgm_epi_plan_upload_images(fsgm_epi_plan* plan, int32_t frame, const uint8_t* I1, const uint8_t* I2);
 /* aggregation-only use: put a ready cost volume into slot `frame` (skips FSGM_STAGE_COST) */
 fsgm_status fsgm_epi_plan_upload_cost(fsgm_epi_plan* plan, int32_t frame, const uint8_t* C);
 /* resident cost volume of frame dst <- frame src with the columns rotated by roll_cols (dst[y][(x + roll) % W] = src[y][x]),
@@ -655,6 +701,13 @@ fsgm_status fsgm_epi_plan_run_device(fsgm_epi_plan* plan, int32_t n_frames, cons
 /* calc_cost_sgm on n_frames contiguous frames (one cached plan of batch n_frames, as fsgm_calc_cost_sgm_batch_host) */
 fsgm_status fsgm_calc_cost_sgm_device(int32_t n_frames, const fsgm_epi_in* in, const fsgm_epi_out* out,
                                       const fsgm_epi_params* prm, void* stream, int32_t* status);
+/* fsgm_calc_cost_sgm_linear_batch_host on n_frames contiguous frames: in->offset is not read (may be NULL) */
+fsgm_status fsgm_calc_cost_sgm_linear_device(int32_t n_frames, const fsgm_epi_in* in, const fsgm_epi_out* out,
+                                             const fsgm_epi_params* prm, void* stream, int32_t* status);
+/* fsgm_stereo_sgm_host on device pointers (one cached rectified plan of batch n_frames) */
+fsgm_status fsgm_stereo_sgm_device(int32_t n_frames, const uint8_t* I1, const uint8_t* I2, int32_t width, int32_t height,
+                                   int32_t dMax, int32_t P1, int32_t P2, const fsgm_stereo_params* prm, uint32_t* disp,
+                                   uint32_t* minC, uint8_t* conf, uint32_t* disp2, void* stream, int32_t* status);
 /* epipolar_sgm_of on n_frames image pairs, one plan of batch n_frames: g (HOST memory) holds n_frames geometries, each
  * passed to the maps kernel by value.  I0 / I1 u8 [n][channels][H][W]; flow f64 [n][3][H][W]; minC (may be NULL) u32 [n][H][W]. */
 fsgm_status fsgm_epipolar_sgm_of_device(int32_t n_frames, const uint8_t* I0, const uint8_t* I1, int32_t width,
