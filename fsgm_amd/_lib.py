@@ -33,6 +33,17 @@ class StereoParams(C.Structure):
 SAMPLING_VZ, SAMPLING_LINEAR, SAMPLING_RECTIFIED = 0, 1, 2
 
 
+class EpiOptions(C.Structure):
+    """fsgm_epi_options: what the *_opts entry points take next to EpiParams / StereoParams (which keep their size)."""
+    _fields_ = [("adaptive_p2", C.c_int32), ("reserved", C.c_int32 * 7)]
+
+
+def options(adaptive_p2=0):
+    o = EpiOptions()
+    o.adaptive_p2 = int(adaptive_p2)
+    return o
+
+
 class EpiIn(C.Structure):
     _fields_ = [("I1", C.c_void_p), ("I2", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32),
                 ("dMax", C.c_int32), ("vMax", C.c_double), ("pixelPosD0", C.c_void_p),
@@ -69,6 +80,16 @@ def load():
     lib.fsgm_calc_cost_sgm_linear_batch_host.argtypes = [i32, C.POINTER(EpiIn), C.POINTER(EpiOut), C.POINTER(EpiParams)]
     lib.fsgm_stereo_params_default.restype = StereoParams
     lib.fsgm_stereo_sgm_host.argtypes = [i32, vp, vp, i32, i32, i32, i32, i32, C.POINTER(StereoParams), vp, vp, vp, vp]
+    opt = C.POINTER(EpiOptions)
+    lib.fsgm_epi_options_default.restype = EpiOptions
+    lib.fsgm_calc_cost_sgm_host_opts.argtypes = [C.POINTER(EpiIn), C.POINTER(EpiOut), C.POINTER(EpiParams), opt]
+    lib.fsgm_calc_cost_sgm_batch_host_opts.argtypes = [i32, C.POINTER(EpiIn), C.POINTER(EpiOut), C.POINTER(EpiParams), opt]
+    lib.fsgm_calc_cost_sgm_linear_host_opts.argtypes = [C.POINTER(EpiIn), C.POINTER(EpiOut), C.POINTER(EpiParams), opt]
+    lib.fsgm_calc_cost_sgm_linear_batch_host_opts.argtypes = [i32, C.POINTER(EpiIn), C.POINTER(EpiOut), C.POINTER(EpiParams), opt]
+    lib.fsgm_stereo_sgm_host_opts.argtypes = [i32, vp, vp, i32, i32, i32, i32, i32, C.POINTER(StereoParams), opt, vp, vp, vp, vp]
+    lib.fsgm_epi_plan_set_adaptive_p2.argtypes = [vp, i32]
+    lib.fsgm_epi_auto_pipeline_opts.argtypes = [i32] * 9 + [opt]
+    lib.fsgm_epi_auto_pipeline_opts.restype = C.c_char_p
     lib.fsgm_epi_plan_create_sampling.argtypes = [C.POINTER(vp), i32, i32, i32, i32, C.POINTER(EpiParams), i32, i32]
     lib.fsgm_epi_plan_upload_images.argtypes = [vp, i32, vp, vp]
     i32p = C.POINTER(C.c_int32)

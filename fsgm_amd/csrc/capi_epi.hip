@@ -94,6 +94,8 @@ struct fsgm_epi_plan {
     hipEvent_t ev_hl[2] = {nullptr, nullptr};   // the horizontal pair of each frame lane done (sweep pipeline)
     std::vector<int> cmax;               // per frame: upper bound of the cost values in dC
     bool vz_valid = false;
+    int adaptive = 0;                    // adaptive P2 (calc_cost_sgm.cpp:68-72): line kernels at every batch size, the aggregation reads dI1
+    std::vector<char> have_img;          // per frame: its image pair has been put into dI1 / dI2 (what an adaptive aggregation reads)
     int agg_mode = 0;                    // 0 auto, 1 per-direction line kernels, 2 fused sweeps (if eligible), 3 parallel sweeps, 4 / 5 band sweeps, 6 sweeps meeting in the middle
     int cus = 256;                       // compute units of the device (band sweeps: one workgroup per frame, two per CU)
     Pipeline pipe = PIPE_GENERIC;
@@ -160,10 +162,13 @@ static int pairs_min_batch(int W, int H, int D) { return switch_batch("FSGM_EPI_
 
 // What runs for a plan of this shape, batch and parameter set (cm: the largest cost in the volumes): a function of its
 // arguments and the FSGM_EPI_* environment only, so that fsgm_epi_auto_pipeline can answer without a plan.
-static Pipeline choose_pipeline(int W, int H, int D, int batch, int paths, int P1, int P2, int cm, int agg_mode, int cus) {
+static Pipeline choose_pipeline(int W, int H, int D, int batch, int paths, int P1, int P2, int cm, int agg_mode, int cus,
+                                int adaptive = 0) {
     if (agg_packed_lpp(D) == 0) return PIPE_GENERIC;
+    // (adaptive P2 lowers P2 per step, never raises it: the no-wrap test with the full P2 covers every step)
     const bool nowrap = P1 >= 0 && P2 >= 0 && cm + P2 + std::max(P1, P2) <= 255;
     Pipeline c = nowrap ? PIPE_PACKED_NOWRAP : PIPE_PACKED_WRAP;
+    if (adaptive) return c;                                      // the fused pipelines have no per-step P2: line kernels at every batch size
     // the fused sweeps cover the 8-path no-wrap case; everything else stays on the line kernels
     // Auto mode takes the fused pipelines only for batches: their latency (H rows in sequence for a sweep, down then
     // up; three passes along 1242-pixel rows for a pair) is 1.0 / 2.0 ms (4 / 8 paths) whatever the frame count,
@@ -202,7 +207,7 @@ static Pipeline choose_pipeline(int W, int H, int D, int batch, int paths, int P
 // switches (A/B) are read here, once per process.
 static void select_kernel(fsgm_epi_plan* p) {
     const int cm = *std::max_element(p->cmax.begin(), p->cmax.end());
-    const Pipeline k = choose_pipeline(p->W, p->H, p->D, p->batch, p->prm.paths, p->P1, p->P2, cm, p->agg_mode, p->cus);
+    const Pipeline k = choose_pipeline(p->W, p->H, p->D, p->batch, p->prm.paths, p->P1, p->P2, cm, p->agg_mode, p->cus, p->adaptive);
     const int B = p->batch;
     const bool fine_ok = pair_x_fine_ok(p->D) != 0;
     PipelineForm f;
@@ -357,6 +362,7 @@ fsgm_status fsgm_epi_plan_create_sampling(fsgm_epi_plan** out, int32_t W, int32_
     { int n = 0; if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, pr.device) == hipSuccess && n > 0) p->cus = n; }
     p->NP = (size_t)W * H; p->N = p->NP * D;
     p->cmax.assign(batch, 24);           // census 5x5: 24 informative bits
+    p->have_img.assign(batch, 0);
     const size_t B = batch;
     hipError_t e = hipSuccess;
     auto alloc = [&](void** ptr, size_t bytes) { if (e == hipSuccess) e = hipMalloc(ptr, bytes); };
@@ -415,7 +421,7 @@ static fsgm_status ensure_cost_buffers(fsgm_epi_plan* p) {
     if (p->dCraw) return FSGM_OK;                                // the set's own marker: created last
     const size_t B = p->batch;
     LazySet ls;
-    ls.alloc(p->dI1, B * p->NP);
+    ls.alloc(p->dI1, B * p->NP);                                 // (a slot that is filled already stays: ensure_image_buffers)
     ls.alloc(p->dI2, B * p->NP);
     ls.alloc(p->dCen1, B * p->NP * 4);
     ls.alloc(p->dCen2, B * p->NP * 4);
@@ -423,6 +429,18 @@ static fsgm_status ensure_cost_buffers(fsgm_epi_plan* p) {
     ls.alloc(p->dNd, B * p->NP * 16, p->sampling != FSGM_SAMPLING_RECTIFIED);
     ls.alloc(p->dCraw, B * p->N);
     if (ls.err != hipSuccess) return lazy_fail(ls, "cost stage buffers");
+    ls.commit();
+    return FSGM_OK;
+}
+
+// The image pair alone: what fsgm_epi_plan_upload_images fills.  An aggregation-only plan with adaptive P2 holds these and
+// none of the cost stage's other buffers.
+static fsgm_status ensure_image_buffers(fsgm_epi_plan* p) {
+    if (p->dI1 && p->dI2) return FSGM_OK;
+    LazySet ls;
+    ls.alloc(p->dI1, (size_t)p->batch * p->NP);
+    ls.alloc(p->dI2, (size_t)p->batch * p->NP);
+    if (ls.err != hipSuccess) return lazy_fail(ls, "image buffers");
     ls.commit();
     return FSGM_OK;
 }
@@ -499,6 +517,7 @@ fsgm_status fsgm_epi_plan_upload(fsgm_epi_plan* p, int32_t f, const uint8_t* I1,
     { fsgm_status us = upload_async(p, f, I1, I2, pd0, nd, off); if (us != FSGM_OK) return us; }
     FSGM_HIP(hipStreamSynchronize(p->stream));   // pageable host memory: keep the caller's buffers free to reuse
     guard.dismiss();
+    p->have_img[f] = 1;
     return FSGM_OK;
 }
 
@@ -506,12 +525,13 @@ fsgm_status fsgm_epi_plan_upload_images(fsgm_epi_plan* p, int32_t f, const uint8
     FSGM_REQUIRE(p, "null plan");
     { fsgm_status fs = frame_ready(p, f, 0); if (fs != FSGM_OK) return fs; }
     FSGM_REQUIRE(I1 && I2, "fsgm_epi_plan_upload_images: null input");
-    { fsgm_status cs = ensure_cost_buffers(p); if (cs != FSGM_OK) return cs; }
+    { fsgm_status cs = ensure_image_buffers(p); if (cs != FSGM_OK) return cs; }   // (the cost stage's other buffers: prepare())
     StreamGuard guard(p->stream);
     FSGM_HIP(hipMemcpyAsync(p->dI1 + (size_t)f * p->NP, I1, p->NP, hipMemcpyHostToDevice, p->stream));
     FSGM_HIP(hipMemcpyAsync(p->dI2 + (size_t)f * p->NP, I2, p->NP, hipMemcpyHostToDevice, p->stream));
     FSGM_HIP(hipStreamSynchronize(p->stream));
     guard.dismiss();
+    p->have_img[f] = 1;
     return FSGM_OK;
 }
 
@@ -605,6 +625,11 @@ static fsgm_status ensure_agg_buffers(fsgm_epi_plan* p) {
 // (values <= 24), so the bound of the cost values -- and with it the kernel selection -- is settled first;
 // then the buffer set of the selected pipeline.
 static fsgm_status prepare(fsgm_epi_plan* p, int stages) {
+    if (p->adaptive && (stages & FSGM_STAGE_AGGREGATE)) {        // the aggregation reads I1 of every slot: refuse before anything is queued
+        for (int f = 0; f < p->batch; f++)
+            if (!p->dI1 || !p->have_img[f])
+                return fail(FSGM_ERR_INVALID, "adaptive P2: no image uploaded for frame %d (fsgm_epi_plan_upload / _upload_images)", f);
+    }
     if ((stages & FSGM_STAGE_COST) || p->prm.fb_check) {
         fsgm_status cs = ensure_cost_buffers(p);
         if (cs != FSGM_OK) return cs;
@@ -676,6 +701,7 @@ static AggArgs agg_args(const fsgm_epi_plan* p, uint8_t* L, int slots) {
     AggArgs a;
     a.C = p->dC; a.L = L; a.c_frame_stride = p->N; a.l_frame_stride = slots * p->N; a.l_dir_stride = p->N;
     a.W = p->W; a.H = p->H; a.D = p->D; a.P1 = p->P1; a.P2 = p->P2;
+    a.adaptive = p->adaptive; a.I1 = p->adaptive ? p->dI1 : nullptr; a.i_frame_stride = p->NP;
     return a;
 }
 
@@ -931,8 +957,35 @@ fsgm_status fsgm_epi_plan_run(fsgm_epi_plan* p, int32_t stages) {
 fsgm_status fsgm_epi_plan_set_agg_mode(fsgm_epi_plan* p, int32_t mode) {
     FSGM_REQUIRE(p, "null plan");
     FSGM_REQUIRE(mode >= 0 && mode <= 6, "agg mode must be 0 (auto), 1 (per-direction kernels), 2 (fused sweeps), 3 (parallel sweeps), 4 (band sweeps), 5 (chained band sweeps) or 6 (sweeps meeting in the middle)");
+    if (p->adaptive && mode >= 2)
+        return fail(FSGM_ERR_UNSUPPORTED, "agg mode %d on an adaptive-P2 plan: only the line kernels (modes 0 and 1) take a per-step P2", mode);
     p->agg_mode = mode;
     select_kernel(p);
+    return FSGM_OK;
+}
+
+fsgm_status fsgm_epi_plan_set_adaptive_p2(fsgm_epi_plan* p, int32_t on) {
+    FSGM_REQUIRE(p, "null plan");
+    FSGM_REQUIRE(on == 0 || on == 1, "fsgm_epi_plan_set_adaptive_p2: on must be 0 or 1 (got %d)", on);
+    if (on && p->agg_mode >= 2)
+        return fail(FSGM_ERR_UNSUPPORTED, "adaptive P2 on a plan forced to agg mode %d: only the line kernels (modes 0 and 1) take a per-step P2",
+                    p->agg_mode);
+    p->adaptive = on;
+    select_kernel(p);
+    return FSGM_OK;
+}
+
+fsgm_epi_options fsgm_epi_options_default(void) {
+    fsgm_epi_options o;
+    memset(&o, 0, sizeof(o));
+    return o;
+}
+
+// the options of an *_opts entry point (null: the defaults), checked
+static fsgm_status read_options(const char* who, const fsgm_epi_options* opt, fsgm_epi_options* o) {
+    *o = opt ? *opt : fsgm_epi_options_default();
+    FSGM_REQUIRE(o->adaptive_p2 == 0 || o->adaptive_p2 == 1, "%s: adaptive_p2 must be 0 or 1 (got %d)", who, o->adaptive_p2);
+    for (int r : o->reserved) FSGM_REQUIRE(r == 0, "%s: the reserved words of fsgm_epi_options must be zero", who);
     return FSGM_OK;
 }
 
@@ -1016,6 +1069,12 @@ const char* fsgm_epi_auto_pipeline(int32_t width, int32_t height, int32_t dMax, 
     return kPipelineName[choose_pipeline(width, height, dMax, batch, paths, P1, P2, cmax, 0, cus)];
 }
 
+const char* fsgm_epi_auto_pipeline_opts(int32_t width, int32_t height, int32_t dMax, int32_t batch, int32_t paths, int32_t P1, int32_t P2,
+                                        int32_t cmax, int32_t cus, const fsgm_epi_options* opt) {
+    if (width <= 0 || height <= 0 || dMax <= 0 || batch <= 0 || (paths != 4 && paths != 8) || cus <= 0) return "";
+    return kPipelineName[choose_pipeline(width, height, dMax, batch, paths, P1, P2, cmax, 0, cus, opt && opt->adaptive_p2)];
+}
+
 // The achievable HBM rate of this device, measured the way the aggregation kernels move bytes: a grid-stride
 // copy kernel, 16 B per lane per access (launch_copy16, epi_kernels.hip), device memory to device memory, read + written
 // bytes counted.  mode 0: that kernel; mode 1: hipMemcpyAsync D2D (the runtime's blit kernel), for comparison.
@@ -1062,17 +1121,18 @@ static PlanCache<fsgm_epi_plan> g_epi(4, fsgm_epi_plan_destroy);   // cached pla
 // The cached plan of this shape for an entry point: `lk` holds its device's lock for the length of the call, the device is current.
 // (a plan serves one sampling mode and, rectified, one direction: the modes share no cached state)
 static fsgm_status cached_plan(std::unique_lock<std::mutex>& lk, fsgm_epi_plan** out, int W, int H, int D, int batch,
-                               const fsgm_epi_params& pr, int sampling = FSGM_SAMPLING_VZ, int direction = 0) {
+                               const fsgm_epi_params& pr, int sampling = FSGM_SAMPLING_VZ, int direction = 0, int adaptive = 0) {
     FSGM_DEVICE_SLOT(pr.device);
     lk = std::unique_lock<std::mutex>(g_epi.mu(pr.device));
     fsgm_epi_plan* p = g_epi.find(pr.device, [&](const fsgm_epi_plan* q) {
         return q->W == W && q->H == H && q->D == D && q->batch == batch && q->prm.paths == pr.paths &&
                q->prm.fb_check == pr.fb_check && q->prm.vz_to_disp == pr.vz_to_disp && q->sampling == sampling &&
-               q->direction == direction;
+               q->direction == direction && q->adaptive == adaptive;     // (adaptive and non-adaptive callers never share a plan)
     });
     if (p) p->prm = pr;
     else {
         fsgm_status st = fsgm_epi_plan_create_sampling(&p, W, H, D, batch, &pr, sampling, direction);
+        if (st == FSGM_OK && adaptive && (st = fsgm_epi_plan_set_adaptive_p2(p, 1)) != FSGM_OK) fsgm_epi_plan_destroy(p);
         if (st != FSGM_OK) return st;
         g_epi.insert(pr.device, p);
     }
@@ -1099,8 +1159,11 @@ void fsgm_shutdown(void) {
 }
 
 // calc_cost_sgm on host pointers in either build of the reference: vz-index sampling, or linear (offset and vMax unused)
-static fsgm_status epi_batch_host(int sampling, int32_t n, const fsgm_epi_in* in, const fsgm_epi_out* out, const fsgm_epi_params* prm) {
+static fsgm_status epi_batch_host(int sampling, int32_t n, const fsgm_epi_in* in, const fsgm_epi_out* out, const fsgm_epi_params* prm,
+                                  const fsgm_epi_options* opt) {
     FSGM_REQUIRE(n >= 1 && in && out, "fsgm_calc_cost_sgm: null argument");
+    fsgm_epi_options o;
+    { const fsgm_status os = read_options("fsgm_calc_cost_sgm", opt, &o); if (os != FSGM_OK) return os; }
     fsgm_epi_params pr = prm ? *prm : fsgm_epi_params_default();
     const bool linear = sampling == FSGM_SAMPLING_LINEAR;
     if (linear) pr.vz_to_disp = 0;
@@ -1114,10 +1177,11 @@ static fsgm_status epi_batch_host(int sampling, int32_t n, const fsgm_epi_in* in
     }
     std::unique_lock<std::mutex> lk;
     fsgm_epi_plan* p = nullptr;
-    fsgm_status st = cached_plan(lk, &p, in[0].width, in[0].height, in[0].dMax, n, pr, sampling);
+    fsgm_status st = cached_plan(lk, &p, in[0].width, in[0].height, in[0].dMax, n, pr, sampling, 0, o.adaptive_p2);
     if (st != FSGM_OK) return st;
     if ((st = fsgm_epi_plan_set_penalties(p, in[0].P1, in[0].P2, linear ? p->vMax : in[0].vMax)) != FSGM_OK) return st;
     if ((st = ensure_cost_buffers(p)) != FSGM_OK) return st;
+    p->have_img.assign(n, 1);                                    // every frame's pair goes up below, ahead of the kernels
     // One call = one stream-ordered sequence with a single host wait: every frame's inputs go up asynchronously on the
     // plan's stream (hipMemcpyAsync from the caller's pageable memory runs at the pinned rate here, ~50 GB/s, so there is
     // no staging copy: tools/ubench/h2d_rates.hip), the batched kernels follow, the results come down at the end.
@@ -1147,20 +1211,38 @@ static fsgm_status epi_batch_host(int sampling, int32_t n, const fsgm_epi_in* in
     return FSGM_OK;
 }
 
+fsgm_status fsgm_calc_cost_sgm_batch_host_opts(int32_t n, const fsgm_epi_in* in, const fsgm_epi_out* out, const fsgm_epi_params* prm,
+                                               const fsgm_epi_options* opt) {
+    return epi_batch_host(FSGM_SAMPLING_VZ, n, in, out, prm, opt);
+}
+fsgm_status fsgm_calc_cost_sgm_host_opts(const fsgm_epi_in* in, const fsgm_epi_out* out, const fsgm_epi_params* prm,
+                                         const fsgm_epi_options* opt) {
+    return epi_batch_host(FSGM_SAMPLING_VZ, 1, in, out, prm, opt);
+}
+fsgm_status fsgm_calc_cost_sgm_linear_batch_host_opts(int32_t n, const fsgm_epi_in* in, const fsgm_epi_out* out,
+                                                      const fsgm_epi_params* prm, const fsgm_epi_options* opt) {
+    return epi_batch_host(FSGM_SAMPLING_LINEAR, n, in, out, prm, opt);
+}
+fsgm_status fsgm_calc_cost_sgm_linear_host_opts(const fsgm_epi_in* in, const fsgm_epi_out* out, const fsgm_epi_params* prm,
+                                                const fsgm_epi_options* opt) {
+    return epi_batch_host(FSGM_SAMPLING_LINEAR, 1, in, out, prm, opt);
+}
+
+// the entry points without options: the same calls with every option off
 fsgm_status fsgm_calc_cost_sgm_batch_host(int32_t n, const fsgm_epi_in* in, const fsgm_epi_out* out, const fsgm_epi_params* prm) {
-    return epi_batch_host(FSGM_SAMPLING_VZ, n, in, out, prm);
+    return fsgm_calc_cost_sgm_batch_host_opts(n, in, out, prm, nullptr);
 }
 
 fsgm_status fsgm_calc_cost_sgm_host(const fsgm_epi_in* in, const fsgm_epi_out* out, const fsgm_epi_params* prm) {
-    return fsgm_calc_cost_sgm_batch_host(1, in, out, prm);
+    return fsgm_calc_cost_sgm_batch_host_opts(1, in, out, prm, nullptr);
 }
 
 fsgm_status fsgm_calc_cost_sgm_linear_batch_host(int32_t n, const fsgm_epi_in* in, const fsgm_epi_out* out, const fsgm_epi_params* prm) {
-    return epi_batch_host(FSGM_SAMPLING_LINEAR, n, in, out, prm);
+    return fsgm_calc_cost_sgm_linear_batch_host_opts(n, in, out, prm, nullptr);
 }
 
 fsgm_status fsgm_calc_cost_sgm_linear_host(const fsgm_epi_in* in, const fsgm_epi_out* out, const fsgm_epi_params* prm) {
-    return epi_batch_host(FSGM_SAMPLING_LINEAR, 1, in, out, prm);
+    return fsgm_calc_cost_sgm_linear_batch_host_opts(1, in, out, prm, nullptr);
 }
 
 // ---- rectified stereo on host pointers: n contiguous frames, images up, everything else as calc_cost_sgm ----
@@ -1186,15 +1268,24 @@ static fsgm_status stereo_args(const char* who, int32_t n, const uint8_t* I1, co
 fsgm_status fsgm_stereo_sgm_host(int32_t n, const uint8_t* I1, const uint8_t* I2, int32_t W, int32_t H, int32_t dMax, int32_t P1,
                                  int32_t P2, const fsgm_stereo_params* prm, uint32_t* disp, uint32_t* minC, uint8_t* conf,
                                  uint32_t* disp2) {
+    return fsgm_stereo_sgm_host_opts(n, I1, I2, W, H, dMax, P1, P2, prm, nullptr, disp, minC, conf, disp2);
+}
+
+fsgm_status fsgm_stereo_sgm_host_opts(int32_t n, const uint8_t* I1, const uint8_t* I2, int32_t W, int32_t H, int32_t dMax, int32_t P1,
+                                      int32_t P2, const fsgm_stereo_params* prm, const fsgm_epi_options* opt, uint32_t* disp,
+                                      uint32_t* minC, uint8_t* conf, uint32_t* disp2) {
     fsgm_stereo_params sp;
     fsgm_epi_params pr;
+    fsgm_epi_options o;
     fsgm_status st = stereo_args("fsgm_stereo_sgm_host", n, I1, I2, W, H, dMax, prm, disp, minC, &sp, &pr);
     if (st != FSGM_OK) return st;
+    if ((st = read_options("fsgm_stereo_sgm_host", opt, &o)) != FSGM_OK) return st;
     std::unique_lock<std::mutex> lk;
     fsgm_epi_plan* p = nullptr;
-    if ((st = cached_plan(lk, &p, W, H, dMax, n, pr, FSGM_SAMPLING_RECTIFIED, sp.direction)) != FSGM_OK) return st;
+    if ((st = cached_plan(lk, &p, W, H, dMax, n, pr, FSGM_SAMPLING_RECTIFIED, sp.direction, o.adaptive_p2)) != FSGM_OK) return st;
     if ((st = fsgm_epi_plan_set_penalties(p, P1, P2, p->vMax)) != FSGM_OK) return st;
     if ((st = ensure_cost_buffers(p)) != FSGM_OK) return st;
+    p->have_img.assign(n, 1);                                    // the pairs go up below, ahead of the kernels
     const size_t np = (size_t)n * p->NP;
     StreamGuard guard(p->stream);                                // every early exit drains the stream: the copies use caller memory
     FSGM_HIP(hipMemcpyAsync(p->dI1, I1, np, hipMemcpyHostToDevice, p->stream));
@@ -1319,6 +1410,7 @@ static fsgm_status epi_device_enter(fsgm_epi_plan* p, int P1, int P2, double vMa
     if ((st = fsgm_epi_plan_set_penalties(p, P1, P2, vMax)) != FSGM_OK) return st;
     if ((st = ensure_cost_buffers(p)) != FSGM_OK) return st;
     if ((st = ensure_vz(p)) != FSGM_OK) return st;
+    p->have_img.assign(p->batch, 1);                             // the caller's images stand in for the plan's for this enqueue
     if ((st = prepare(p, FSGM_STAGE_ALL)) != FSGM_OK) return st;
     if ((st = p->join.ensure()) != FSGM_OK) return st;
     return p->join.enter(cs, p->stream);
@@ -1336,7 +1428,8 @@ static fsgm_status epi_device_finish(fsgm_epi_plan* p, hipStream_t cs, int32_t* 
 
 // a batch on device pointers through the caller's plan p, or (p null) through the cached plan for prm
 static fsgm_status epi_run_device(const char* who, fsgm_epi_plan* p, const fsgm_epi_params* prm, int32_t n, const fsgm_epi_in* in,
-                                  const fsgm_epi_out* out, void* stream, int32_t* status, int sampling = FSGM_SAMPLING_VZ) {
+                                  const fsgm_epi_out* out, void* stream, int32_t* status, int sampling = FSGM_SAMPLING_VZ,
+                                  const fsgm_epi_options* opt = nullptr) {
     const bool linear = (p ? p->sampling : sampling) == FSGM_SAMPLING_LINEAR;
     fsgm_status st = epi_device_args(who, n, in, out, linear);
     if (st != FSGM_OK) return st;
@@ -1344,7 +1437,9 @@ static fsgm_status epi_run_device(const char* who, fsgm_epi_plan* p, const fsgm_
     if (!p) {
         fsgm_epi_params pr = prm ? *prm : fsgm_epi_params_default();
         if (linear) pr.vz_to_disp = 0;
-        if ((st = cached_plan(lk, &p, in->width, in->height, in->dMax, n, pr, sampling)) != FSGM_OK) return st;
+        fsgm_epi_options o;
+        if ((st = read_options(who, opt, &o)) != FSGM_OK) return st;
+        if ((st = cached_plan(lk, &p, in->width, in->height, in->dMax, n, pr, sampling, 0, o.adaptive_p2)) != FSGM_OK) return st;
     }
     FSGM_REQUIRE(p->sampling != FSGM_SAMPLING_RECTIFIED, "%s: a rectified plan runs through fsgm_stereo_sgm_device", who);
     const hipStream_t cs = (hipStream_t)stream;
@@ -1385,24 +1480,42 @@ fsgm_status fsgm_epi_plan_run_device(fsgm_epi_plan* p, int32_t n, const fsgm_epi
     return epi_run_device("fsgm_epi_plan_run_device", p, nullptr, n, in, out, stream, status);
 }
 
+fsgm_status fsgm_calc_cost_sgm_device_opts(int32_t n, const fsgm_epi_in* in, const fsgm_epi_out* out, const fsgm_epi_params* prm,
+                                           const fsgm_epi_options* opt, void* stream, int32_t* status) {
+    return epi_run_device("fsgm_calc_cost_sgm_device", nullptr, prm, n, in, out, stream, status, FSGM_SAMPLING_VZ, opt);
+}
+
+fsgm_status fsgm_calc_cost_sgm_linear_device_opts(int32_t n, const fsgm_epi_in* in, const fsgm_epi_out* out, const fsgm_epi_params* prm,
+                                                  const fsgm_epi_options* opt, void* stream, int32_t* status) {
+    return epi_run_device("fsgm_calc_cost_sgm_linear_device", nullptr, prm, n, in, out, stream, status, FSGM_SAMPLING_LINEAR, opt);
+}
+
 fsgm_status fsgm_calc_cost_sgm_device(int32_t n, const fsgm_epi_in* in, const fsgm_epi_out* out, const fsgm_epi_params* prm,
                                       void* stream, int32_t* status) {
-    return epi_run_device("fsgm_calc_cost_sgm_device", nullptr, prm, n, in, out, stream, status);
+    return fsgm_calc_cost_sgm_device_opts(n, in, out, prm, nullptr, stream, status);
 }
 
 fsgm_status fsgm_calc_cost_sgm_linear_device(int32_t n, const fsgm_epi_in* in, const fsgm_epi_out* out, const fsgm_epi_params* prm,
                                              void* stream, int32_t* status) {
-    return epi_run_device("fsgm_calc_cost_sgm_linear_device", nullptr, prm, n, in, out, stream, status, FSGM_SAMPLING_LINEAR);
+    return fsgm_calc_cost_sgm_linear_device_opts(n, in, out, prm, nullptr, stream, status);
 }
 
 fsgm_status fsgm_stereo_sgm_device(int32_t n, const uint8_t* I1, const uint8_t* I2, int32_t W, int32_t H, int32_t dMax, int32_t P1,
                                    int32_t P2, const fsgm_stereo_params* prm, uint32_t* disp, uint32_t* minC, uint8_t* conf,
                                    uint32_t* disp2, void* stream, int32_t* status) {
+    return fsgm_stereo_sgm_device_opts(n, I1, I2, W, H, dMax, P1, P2, prm, nullptr, disp, minC, conf, disp2, stream, status);
+}
+
+fsgm_status fsgm_stereo_sgm_device_opts(int32_t n, const uint8_t* I1, const uint8_t* I2, int32_t W, int32_t H, int32_t dMax, int32_t P1,
+                                        int32_t P2, const fsgm_stereo_params* prm, const fsgm_epi_options* opt, uint32_t* disp,
+                                        uint32_t* minC, uint8_t* conf, uint32_t* disp2, void* stream, int32_t* status) {
     const char* who = "fsgm_stereo_sgm_device";
     fsgm_stereo_params sp;
     fsgm_epi_params pr;
+    fsgm_epi_options o;
     fsgm_status st = stereo_args(who, n, I1, I2, W, H, dMax, prm, disp, minC, &sp, &pr);
     if (st != FSGM_OK) return st;
+    if ((st = read_options(who, opt, &o)) != FSGM_OK) return st;
     // checks first, also on a shape's first call: nothing is allocated for a captured stream or a pointer that is refused
     const int dev = pr.device;
     const size_t np = (size_t)n * (size_t)W * (size_t)H;
@@ -1420,7 +1533,7 @@ fsgm_status fsgm_stereo_sgm_device(int32_t n, const uint8_t* I1, const uint8_t* 
         return st;
     std::unique_lock<std::mutex> lk;
     fsgm_epi_plan* p = nullptr;
-    if ((st = cached_plan(lk, &p, W, H, dMax, n, pr, FSGM_SAMPLING_RECTIFIED, sp.direction)) != FSGM_OK) return st;
+    if ((st = cached_plan(lk, &p, W, H, dMax, n, pr, FSGM_SAMPLING_RECTIFIED, sp.direction, o.adaptive_p2)) != FSGM_OK) return st;
     if ((st = epi_device_enter(p, P1, P2, p->vMax, cs)) != FSGM_OK) return st;
     {
         Bind<uint8_t> i1(p->dI1, const_cast<uint8_t*>(I1)), i2(p->dI2, const_cast<uint8_t*>(I2));

@@ -31,6 +31,10 @@ struct AggArgs {
     int ndirs;              // path slots (4 or 8)
     int blk_begin[9];       // first block of each slot, [8] = total
     int dir_code[8];        // bits 1:0 = 0 along x, 1 along y, 2 (+1,+1), 3 (-1,+1); bit 2 = point-mirrored (pass 1)
+    // adaptive P2 (calc_cost_sgm.cpp:68-72, adpativeP2 = true): a step uses P2 / 8 where |I1[cur] - I1[pre]| > 25 along the path
+    int adaptive = 0;       // line kernels only: 1 selects the ADAPT instantiations
+    const uint8_t* I1 = nullptr;   // [frames][NP] the call's first image (read when adaptive)
+    size_t i_frame_stride = 0;     // bytes between frames of I1
 };
 
 struct WtaArgs {

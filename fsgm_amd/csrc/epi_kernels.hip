@@ -440,7 +440,12 @@ __global__ __launch_bounds__(256) void box5x5_sliding16_kernel(const uint8_t* __
 #ifndef FSGM_AGG_PFO
 #define FSGM_AGG_PFO 4
 #endif
-template <int D, int DPL, bool WRAP, int BASE>
+// ADAPT (adaptive P2, calc_cost_sgm.cpp:68-72 with adpativeP2 = true): a step uses P2 / 8 in place of P2 where the first image
+// differs by more than 25 between the pixel and its predecessor on the path.  The pixel bytes ride with the cost words: one
+// byte load a step into a ring of its own, PF steps ahead with the same clamped cursor (the LPP lanes of a pixel read the same
+// byte: one request), the predecessor's byte carried in a register; the choice is a compare and a select, no branch.  A path
+// start takes no step and reads no pair (:152-180), so what the carried byte holds there never matters.
+template <int D, int DPL, bool WRAP, int BASE, bool ADAPT = false>
 __device__ __forceinline__ void agg_packed_body(const AggArgs& a, const int slot, const bool mirror) {
     constexpr int LPP = D / DPL;        // lanes per pixel
     constexpr int NK = DPL / 4;         // cost dwords per lane
@@ -487,6 +492,11 @@ __device__ __forceinline__ void agg_packed_body(const AggArgs& a, const int slot
     };
     // the load cursor runs PF steps ahead of the line's end: keep its address inside the volume
     auto load_c = [&](int cpix) -> Words { return *(const Words*)(Cf + byte_off(min(cpix, NP - 1))); };
+    const uint8_t* __restrict__ If = ADAPT ? a.I1 + (size_t)blockIdx.y * a.i_frame_stride : nullptr;
+    auto load_i = [&](int cpix) -> uint32_t {              // the pixel of step cpix, clamped as load_c: index 0 .. NP-1
+        const int q = min(cpix, NP - 1);
+        return If[mirror ? NP - 1 - q : q];
+    };
     // the path volumes are written once and read once by the WTA kernel: streamed past the caches (FSGM_LINE_NT)
     auto store_words = [&](uint8_t* p, const Words& w) {
         if (FSGM_LINE_NT) {
@@ -501,6 +511,10 @@ __device__ __forceinline__ void agg_packed_body(const AggArgs& a, const int slot
     const uint32_t P1pk = WRAP ? (uint32_t)(a.P1 & 0xFF) * 0x10001u : (uint32_t)a.P1 * 0x10001u;
     const uint32_t P2pk = (uint32_t)a.P2 * 0x10001u;        // NOWRAP only
     const uint32_t P2b = (uint32_t)(a.P2 & 0xFF);           // WRAP only
+    const uint32_t P2apk = (uint32_t)(a.P2 / 8) * 0x10001u; // ADAPT: P2 / 8, C's truncating division (:71); NOWRAP (P2 >= 0)
+    const uint32_t P2ab = (uint32_t)((a.P2 / 8) & 0xFF);    // ADAPT, WRAP
+    uint32_t ipre = 0;                                       // ADAPT: the previous pixel of the path
+    bool edge = false;                                       // ADAPT: the step being computed crosses an intensity edge and takes P2 / 8
 
     uint32_t LE[NK], LO[NK];                                 // previous pixel's path costs
 #pragma unroll
@@ -524,7 +538,7 @@ __device__ __forceinline__ void agg_packed_body(const AggArgs& a, const int slot
         const uint32_t mpk = m | (m << 16);
         uint32_t NE[NK], NO[NK];
         if (!WRAP) {
-            const uint32_t p2lane = start ? 0u : P2pk;   // min(.,0)=0 -> L = C at a path start
+            const uint32_t p2lane = start ? 0u : (ADAPT && edge) ? P2apk : P2pk;   // min(.,0)=0 -> L = C at a path start
 #pragma unroll
             for (int k = 0; k < NK; k++) {
                 const uint32_t nbE = pk_min(align16(LO[k], k ? LO[k - 1] : prevO3), LO[k]);
@@ -536,7 +550,7 @@ __device__ __forceinline__ void agg_packed_body(const AggArgs& a, const int slot
                 NO[k] = pk_add(CO[k], pk_min(pk_sub(tO, mpk), p2lane));
             }
         } else {
-            const uint32_t jump = (m + P2b) & 0xFFu;                       // :46 u8(LpreMin + P2)
+            const uint32_t jump = (m + ((ADAPT && edge) ? P2ab : P2b)) & 0xFFu;   // :46 u8(LpreMin + P2)
             const uint32_t jpk = jump | (jump << 16);
             // mod-256 adds do not commute with min: narrow each neighbour + P1 first (:47-48),
             // and give the two non-existent neighbours the neutral candidate 255.
@@ -582,9 +596,21 @@ __device__ __forceinline__ void agg_packed_body(const AggArgs& a, const int slot
     };
     auto is_start = [&](int t) -> bool { return (t == 0) || (BASE == 2 && x == 0) || (BASE == 3 && x == W - 1); };
 
+    // ADAPT: does the step onto pixel value icur cross an edge (:71); icur becomes the predecessor
+    auto crosses = [&](const uint32_t icur) -> bool {
+        const int diff = (int)icur - (int)ipre;
+        ipre = icur;
+        return (diff < 0 ? -diff : diff) > 25;
+    };
+
     Words ring[PF];
+    uint32_t iring[ADAPT ? PF : 1];                          // the pixels of the steps whose costs are in ring[]
 #pragma unroll
-    for (int i = 0; i < PF; i++) { ring[i] = load_c(pixl); advance(xl, pixl); }
+    for (int i = 0; i < PF; i++) {
+        ring[i] = load_c(pixl);
+        if constexpr (ADAPT) iring[i] = load_i(pixl);
+        advance(xl, pixl);
+    }
 
     // steady state: no branches inside, so the PF loads stay in flight across iterations
     int t0 = 0;
@@ -592,7 +618,9 @@ __device__ __forceinline__ void agg_packed_body(const AggArgs& a, const int slot
 #pragma unroll
         for (int i = 0; i < PF; i++) {
             const Words cw = ring[i];
+            if constexpr (ADAPT) edge = crosses(iring[i]);
             ring[i] = load_c(pixl);
+            if constexpr (ADAPT) iring[i] = load_i(pixl);
             advance(xl, pixl);
             const Words o = step(cw, is_start(t0 + i));
             store_words(Lf + byte_off(pix), o);
@@ -603,6 +631,7 @@ __device__ __forceinline__ void agg_packed_body(const AggArgs& a, const int slot
 #pragma unroll
     for (int i = 0; i < PF - 1; i++) {
         if (t0 + i < len) {
+            if constexpr (ADAPT) edge = crosses(iring[i]);
             const Words o = step(ring[i], is_start(t0 + i));
             store_words(Lf + byte_off(pix), o);
             advance(x, pix);
@@ -930,8 +959,9 @@ template <int D> struct AggSplit {
     static constexpr int other = D >= 256 && FSGM_AGG_DO < 8 ? 8 : FSGM_AGG_DO;
 };
 
-template <int D, bool WRAP, bool FINE>
-__global__ __launch_bounds__(256) void agg_packed_kernel(AggArgs a) {
+// ADAPT: every direction on the general body (the hand-written bodies have no per-step P2), the along-x lines split finely
+template <int D, bool WRAP, bool FINE, bool ADAPT>
+__device__ __forceinline__ void agg_packed_dispatch(const AggArgs& a) {
     // which direction slot does this block belong to (block-uniform)
     int slot = 0;
 #pragma unroll
@@ -942,13 +972,13 @@ __global__ __launch_bounds__(256) void agg_packed_kernel(AggArgs a) {
     constexpr int DO = AggSplit<D>::other, DX = FINE ? AggSplit<D>::along_x : DO;
     switch (code & 3) {                 // 0: along x, 1: along y, 2: x+1,y+1, 3: x-1,y+1
         case 0:
-            if constexpr ((D == 32 || D == 64 || D == 128) && !WRAP && FINE && FSGM_AGG_XLEAN) {
+            if constexpr ((D == 32 || D == 64 || D == 128) && !WRAP && FINE && FSGM_AGG_XLEAN && !ADAPT) {
                 if (mirror) agg_x_lean_body<D, true>(a, slot); else agg_x_lean_body<D, false>(a, slot);
-            } else agg_packed_body<D, DX, WRAP, 0>(a, slot, mirror);
+            } else agg_packed_body<D, DX, WRAP, 0, ADAPT>(a, slot, mirror);
             break;
 #define FSGM_AGG_OTHER(BASE) \
-            if constexpr (!WRAP && DO == 16 && D >= 32 && D <= 256 && FSGM_AGG_LEAN) agg_lean_body<D, BASE>(a, slot, mirror); \
-            else agg_packed_body<D, DO, WRAP, BASE>(a, slot, mirror);
+            if constexpr (!WRAP && DO == 16 && D >= 32 && D <= 256 && FSGM_AGG_LEAN && !ADAPT) agg_lean_body<D, BASE>(a, slot, mirror); \
+            else agg_packed_body<D, DO, WRAP, BASE, ADAPT>(a, slot, mirror);
         case 1: FSGM_AGG_OTHER(1) break;
         case 2: FSGM_AGG_OTHER(2) break;
         default: FSGM_AGG_OTHER(3) break;
@@ -956,11 +986,18 @@ __global__ __launch_bounds__(256) void agg_packed_kernel(AggArgs a) {
     }
 }
 
+template <int D, bool WRAP, bool FINE>
+__global__ __launch_bounds__(256) void agg_packed_kernel(AggArgs a) { agg_packed_dispatch<D, WRAP, FINE, false>(a); }
+
+template <int D, bool WRAP>
+__global__ __launch_bounds__(256) void agg_packed_adaptive_kernel(AggArgs a) { agg_packed_dispatch<D, WRAP, true, true>(a); }
+
 // =============================================================================================
 // Path aggregation, generic kernel: any D (<= FSGM_GENERIC_MAX_D), exact u8 semantics.
 // One wave per line, Lpre/Lcur in LDS, lanes stride over d.  Correctness path for disparity
 // ranges the packed kernel does not cover; not tuned.
 // =============================================================================================
+template <bool ADAPT>
 __global__ __launch_bounds__(256) void agg_generic_kernel(AggArgs a) {
     __shared__ uint8_t sL[4][2][FSGM_GENERIC_MAX_D + 2];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -984,11 +1021,20 @@ __global__ __launch_bounds__(256) void agg_generic_kernel(AggArgs a) {
     uint8_t* pre = sL[wave][0];
     uint8_t* cur = sL[wave][1];
     uint32_t m = 0;
+    const uint8_t* __restrict__ If = ADAPT ? a.I1 + (size_t)blockIdx.y * a.i_frame_stride : nullptr;
+    int ipre = 0;                                            // ADAPT: the previous pixel of the path (unused at a path start)
     for (int t = 0; t < len; t++) {
         const bool start = (t == 0) || (base == 2 && x == 0) || (base == 3 && x == W - 1);
         const size_t off = (size_t)(mirror ? NP - 1 - pix : pix) * D;
         uint32_t lo = 255;
-        const uint32_t jump = (m + (uint32_t)a.P2) & 0xFF;
+        bool edge = false;
+        if constexpr (ADAPT) {                               // calc_cost_sgm.cpp:68-72
+            const int icur = If[mirror ? NP - 1 - pix : pix];
+            const int diff = icur - ipre;
+            edge = (diff < 0 ? -diff : diff) > 25;
+            ipre = icur;
+        }
+        const uint32_t jump = (m + (uint32_t)(edge ? a.P2 / 8 : a.P2)) & 0xFF;
         for (int d = lane; d < D; d += 64) {
             const uint32_t c = Cf[off + d];
             uint32_t v;
@@ -1317,8 +1363,15 @@ static bool agg_fine() {
 
 template <int D>
 static void launch_packed(hipStream_t st, AggArgs& a, int paths, int frames, bool wrap) {
-    const bool fine = agg_fine();
     constexpr int DO = AggSplit<D>::other, DX = AggSplit<D>::along_x;
+    if (a.adaptive) {                                            // the general body for every direction, along x split finely
+        plan_dirs(a, paths, 4 * (64 / (D / DX)), 4 * (64 / (D / DO)));
+        dim3 grid(a.blk_begin[8], frames);
+        if (wrap) hipLaunchKernelGGL((agg_packed_adaptive_kernel<D, true>), grid, dim3(256), 0, st, a);
+        else      hipLaunchKernelGGL((agg_packed_adaptive_kernel<D, false>), grid, dim3(256), 0, st, a);
+        return;
+    }
+    const bool fine = agg_fine();
     const bool lean = (D == 32 || D == 64 || D == 128) && !wrap && fine && FSGM_AGG_XLEAN;      // agg_x_lean_body: two costs a lane
     plan_dirs(a, paths, lean ? 4 * (128 / D) : 4 * (64 / (D / (fine ? DX : DO))), 4 * (64 / (D / DO)));
     dim3 grid(a.blk_begin[8], frames);
@@ -1335,7 +1388,8 @@ void launch_aggregate(hipStream_t st, AggArgs a, int paths, int frames, int kern
     if (kernel_kind == AGG_GENERIC) {
         plan_dirs(a, paths, 4, 4);
         dim3 grid(a.blk_begin[8], frames);
-        hipLaunchKernelGGL(agg_generic_kernel, grid, dim3(256), 0, st, a);
+        if (a.adaptive) hipLaunchKernelGGL(agg_generic_kernel<true>, grid, dim3(256), 0, st, a);
+        else            hipLaunchKernelGGL(agg_generic_kernel<false>, grid, dim3(256), 0, st, a);
         return;
     }
     const bool wrap = kernel_kind == AGG_PACKED_WRAP;

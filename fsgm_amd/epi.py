@@ -32,19 +32,26 @@ def _params(paths, subpixel, vz_to_disp, device, fb_check=0):
     return p
 
 
-def auto_pipeline(width, height, dMax, batch, paths=4, P1=6, P2=64, cmax=24, cus=256):
+def auto_pipeline(width, height, dMax, batch, paths=4, P1=6, P2=64, cmax=24, cus=256, adaptive_p2=0):
     """Which aggregation pipeline auto mode takes for `batch` frames of this shape (fsgm_epi_auto_pipeline): a pure function of
-    its arguments and the FSGM_EPI_* environment, no device needed."""
+    its arguments and the FSGM_EPI_* environment, no device needed.  adaptive_p2=1: the line kernels at every batch size."""
+    if adaptive_p2:
+        o = _lib.options(adaptive_p2)
+        return _lib.load().fsgm_epi_auto_pipeline_opts(int(width), int(height), int(dMax), int(batch), int(paths), int(P1), int(P2),
+                                                       int(cmax), int(cus), C.byref(o)).decode()
     return _lib.load().fsgm_epi_auto_pipeline(int(width), int(height), int(dMax), int(batch), int(paths), int(P1), int(P2), int(cmax), int(cus)).decode()
 
 
 def calc_cost_sgm_batch(frames, dMax, vMax, P1, P2, *, paths=4, subpixel=1, vz_to_disp=1, device=0,
-                        return_volumes=False, fb_check=0, devices=None):
+                        return_volumes=False, fb_check=0, devices=None, adaptive_p2=0):
     """frames: list of (I1, I2, pixelPosD0, normDir, offset) of one shape, processed concurrently.
 
     devices: a device list (sequence of HIP ordinals, or text "0,1,2" like FSGM_DEVICES) -- frame i runs on
     devices[i % len(devices)], one host thread per entry inside the library, no collective
-    (fsgm_calc_cost_sgm_batch_devices_host); `device` is ignored then.  Results do not depend on the list."""
+    (fsgm_calc_cost_sgm_batch_devices_host); `device` is ignored then.  Results do not depend on the list.
+    adaptive_p2=1: the reference's edge-aware large penalty (see calc_cost_sgm); not offered with a device list."""
+    if devices is not None and adaptive_p2:
+        raise ValueError("adaptive_p2 is not offered with a device list")
     lib = _lib.load()
     n = len(frames)
     if n == 0:
@@ -77,26 +84,32 @@ def calc_cost_sgm_batch(frames, dMax, vMax, P1, P2, *, paths=4, subpixel=1, vz_t
     if devices is not None:
         nd, darr = _lib.device_array(devices)
         check(lib.fsgm_calc_cost_sgm_batch_devices_host(n, ins, outs, C.byref(prm), nd, darr))
+    elif adaptive_p2:
+        opt = _lib.options(adaptive_p2)
+        check(lib.fsgm_calc_cost_sgm_batch_host_opts(n, ins, outs, C.byref(prm), C.byref(opt)))
     else:
         check(lib.fsgm_calc_cost_sgm_batch_host(n, ins, outs, C.byref(prm)))
     return res
 
 
 def calc_cost_sgm(I1, I2, dMax, vMax, pixelPosD0, normlizeDirection, offsetFromPosD0, P1, P2, *,
-                  paths=4, subpixel=1, vz_to_disp=1, device=0, return_volumes=False, fb_check=0):
+                  paths=4, subpixel=1, vz_to_disp=1, device=0, return_volumes=False, fb_check=0, adaptive_p2=0):
     """[bestD, minC] = calc_cost_sgm(I1, I2, dMax, vMax, pixelPosD0, normlizeDirection,
     offsetFromPosD0, P1, P2)  -- same argument order and meaning as the MEX.
 
     Keyword arguments are the reference's compile-time switches (defaults = as shipped).
     fb_check=1 additionally returns (conf, bestD2): the forward-backward check the reference has
     commented out (calc_cost_sgm.cpp:482-536, :589-590).
+    adaptive_p2=1 is `adpativeP2 = true` (:102): every path step uses P2 / 8 in place of P2 where I1 differs by more than 25
+    between the pixel and its predecessor on the path (:68-72).
     """
     return calc_cost_sgm_batch([(I1, I2, pixelPosD0, normlizeDirection, offsetFromPosD0)], dMax, vMax, P1, P2,
                                paths=paths, subpixel=subpixel, vz_to_disp=vz_to_disp, device=device,
-                               return_volumes=return_volumes, fb_check=fb_check)[0]
+                               return_volumes=return_volumes, fb_check=fb_check, adaptive_p2=adaptive_p2)[0]
 
 
-def calc_cost_sgm_linear_batch(frames, dMax, P1, P2, *, paths=4, subpixel=1, device=0, return_volumes=False, fb_check=0):
+def calc_cost_sgm_linear_batch(frames, dMax, P1, P2, *, paths=4, subpixel=1, device=0, return_volumes=False, fb_check=0,
+                               adaptive_p2=0):
     """frames: list of (I1, I2, pixelPosD0, normDir) of one shape through fsgm_calc_cost_sgm_linear_batch_host."""
     lib = _lib.load()
     n = len(frames)
@@ -125,18 +138,22 @@ def calc_cost_sgm_linear_batch(frames, dMax, P1, P2, *, paths=4, subpixel=1, dev
         r = (bestD, minC, Cv, Sv) if return_volumes else (bestD, minC)
         res.append(r + (conf, bestD2) if fb_check else r)
     prm = _params(paths, subpixel, 0, device, fb_check)
-    check(lib.fsgm_calc_cost_sgm_linear_batch_host(n, ins, outs, C.byref(prm)))
+    if adaptive_p2:
+        opt = _lib.options(adaptive_p2)
+        check(lib.fsgm_calc_cost_sgm_linear_batch_host_opts(n, ins, outs, C.byref(prm), C.byref(opt)))
+    else:
+        check(lib.fsgm_calc_cost_sgm_linear_batch_host(n, ins, outs, C.byref(prm)))
     return res
 
 
 def calc_cost_sgm_linear(I1, I2, dMax, pixelPosD0, normlizeDirection, P1, P2, *, paths=4, subpixel=1, fb_check=0, device=0,
-                         return_volumes=False):
+                         return_volumes=False, adaptive_p2=0):
     """[bestD, minC] of calc_cost_sgm.cpp built without its line 4 (USE_VZIND): candidate d is sampled d pixels along the
     per-pixel direction (:368-375), bestD is the index * 256 and never converted.  I1, I2 (height, width) uint8, pixelPosD0 and
     normlizeDirection (2, height, width) float64 (1-based start positions, as for calc_cost_sgm).  fb_check=1 also returns
-    (conf, bestD2) of the forward-backward check on bestD / 256 (:429-536)."""
+    (conf, bestD2) of the forward-backward check on bestD / 256 (:429-536).  adaptive_p2=1: the edge-aware P2 of :68-72."""
     return calc_cost_sgm_linear_batch([(I1, I2, pixelPosD0, normlizeDirection)], dMax, P1, P2, paths=paths, subpixel=subpixel,
-                                      device=device, return_volumes=return_volumes, fb_check=fb_check)[0]
+                                      device=device, return_volumes=return_volumes, fb_check=fb_check, adaptive_p2=adaptive_p2)[0]
 
 
 def _stereo_params(paths, subpixel, direction, fb_check, device):
@@ -149,11 +166,13 @@ def _stereo_params(paths, subpixel, direction, fb_check, device):
     return p
 
 
-def stereo_sgm(left, right, dMax, P1=6, P2=64, *, paths=4, subpixel=1, direction=-1, fb_check=0, device=0):
+def stereo_sgm(left, right, dMax, P1=6, P2=64, *, paths=4, subpixel=1, direction=-1, fb_check=0, device=0, adaptive_p2=0):
     """disp, minC = stereo_sgm(left, right, dMax): semi-global matching of a rectified pair.  left, right (height, width) uint8
     or a batch (N, height, width); disp uint32 = disparity * 256 (whole disparities with subpixel=0), minC uint32, of the
     images' shape.  direction=-1: `left` is the left view and its match in `right` lies at x - d; +1: at x + d.  fb_check=1
-    also returns (conf, disp2): the reference's forward-backward check (threshold 2 on the * 256 values; dMax <= 511)."""
+    also returns (conf, disp2): the reference's forward-backward check (threshold 2 on the * 256 values; dMax <= 511).
+    adaptive_p2=1: edge-aware large penalty -- a path step across an intensity edge of `left` (a difference above 25 between
+    the pixel and its predecessor on the path) pays P2 / 8 instead of P2 (calc_cost_sgm.cpp:68-72)."""
     left, right = np.asarray(left), np.asarray(right)
     if left.dtype != np.uint8 or right.dtype != np.uint8 or left.ndim not in (2, 3):
         raise TypeError(f"left / right must be uint8 arrays (height, width) or (N, height, width) (got {left.dtype} {left.shape})")
@@ -171,8 +190,13 @@ def stereo_sgm(left, right, dMax, P1=6, P2=64, *, paths=4, subpixel=1, direction
     disp, minC = np.zeros(left.shape, np.uint32), np.zeros(left.shape, np.uint32)
     conf = np.zeros(left.shape, np.uint8) if fb_check else None
     disp2 = np.zeros(left.shape, np.uint32) if fb_check else None
-    check(lib.fsgm_stereo_sgm_host(n, ptr(left), ptr(right), W, H, int(dMax), int(P1), int(P2), C.byref(prm), ptr(disp), ptr(minC),
-                                   ptr(conf), ptr(disp2)))
+    if adaptive_p2:
+        opt = _lib.options(adaptive_p2)
+        check(lib.fsgm_stereo_sgm_host_opts(n, ptr(left), ptr(right), W, H, int(dMax), int(P1), int(P2), C.byref(prm), C.byref(opt),
+                                            ptr(disp), ptr(minC), ptr(conf), ptr(disp2)))
+    else:
+        check(lib.fsgm_stereo_sgm_host(n, ptr(left), ptr(right), W, H, int(dMax), int(P1), int(P2), C.byref(prm), ptr(disp), ptr(minC),
+                                       ptr(conf), ptr(disp2)))
     return (disp, minC, conf, disp2) if fb_check else (disp, minC)
 
 
@@ -214,9 +238,10 @@ class EpiPlan:
     """Device-resident plan: `batch` frames of width x height x dMax stay in HBM across calls."""
 
     def __init__(self, width, height, dMax, batch=1, *, paths=4, subpixel=1, vz_to_disp=1, device=0, fb_check=0,
-                 sampling=_lib.SAMPLING_VZ, direction=-1):
+                 sampling=_lib.SAMPLING_VZ, direction=-1, adaptive_p2=0):
         """sampling: _lib.SAMPLING_VZ (the reference as shipped), SAMPLING_LINEAR (its build without USE_VZIND: upload() takes
-        off=None) or SAMPLING_RECTIFIED (a rectified pair with match at x + direction * d: upload_images() only, no maps)."""
+        off=None) or SAMPLING_RECTIFIED (a rectified pair with match at x + direction * d: upload_images() only, no maps).
+        adaptive_p2=1: set_adaptive_p2(1) on the fresh plan."""
         self.lib = _lib.load()
         self.W, self.H, self.D, self.batch, self.paths = int(width), int(height), int(dMax), int(batch), int(paths)
         self.device, self.fb_check = int(device), int(fb_check)
@@ -229,6 +254,13 @@ class EpiPlan:
         else:
             check(self.lib.fsgm_epi_plan_create_sampling(C.byref(self._h), self.W, self.H, self.D, self.batch, C.byref(prm),
                                                          self.sampling, int(direction)))
+        self.adaptive_p2 = 0
+        if adaptive_p2:
+            try:
+                self.set_adaptive_p2(adaptive_p2)
+            except Exception:
+                self.close()
+                raise
 
     def close(self):
         if self._h:
@@ -257,6 +289,13 @@ class EpiPlan:
         bands of a frame as workgroups of their own that hand over while they run (chained: batches from ~100 frames), 6 the
         parallel sweeps meeting in the middle (each finishes the other's half of the rows with the WTA inside: 10-25 frames)."""
         check(self.lib.fsgm_epi_plan_set_agg_mode(self._h, int(mode)))
+
+    def set_adaptive_p2(self, on):
+        """Adaptive P2 (calc_cost_sgm.cpp:68-72) on / off.  An adaptive plan runs the line kernels at every batch size:
+        refused (status 4) while modes 2-6 are forced, as set_agg_mode(2..6) is on an adaptive plan; its aggregate stage reads
+        I1 of every slot (upload / upload_images), also when the costs came from upload_cost."""
+        check(self.lib.fsgm_epi_plan_set_adaptive_p2(self._h, int(on)))
+        self.adaptive_p2 = int(on)
 
     def upload(self, frame, I1, I2, pd0, nd, off):
         I1, I2 = _u8img(I1, "I1"), _u8img(I2, "I2")

@@ -5,7 +5,9 @@
 // libfsgm_hip.so; this file only unpacks mxArrays.
 // Environment: FSGM_DEVICE (HIP ordinal, default 0); FSGM_DEVICES (a list, for batches: below); FSGM_EPI_PATHS=8 enables the diagonal paths
 // the reference compiles out (calc_cost_sgm.cpp:104) -- default 4 = as shipped; FSGM_EPI_FB_CHECK=1
-// runs the forward-backward check the reference has commented out (:589-590) and fills conf/bestD2.
+// runs the forward-backward check the reference has commented out (:589-590) and fills conf/bestD2; FSGM_EPI_ADAPTIVE_P2=1 is the
+// reference's `adpativeP2 = true` (:102, :68-72: P2 / 8 across intensity edges of I1) -- default 0 = as shipped; a batch with
+// FSGM_EPI_ADAPTIVE_P2=1 runs on one device (FSGM_DEVICES with more than one entry is refused).
 #include "gateway_common.h"
 #include <vector>
 
@@ -59,8 +61,13 @@ static void batch_call(int nlhs, mxArray* plhs[], const mxArray* prhs[]) {
     int32_t nd_list = (list && *list) ? fsgm_parse_device_list(list, devs, 64) : 0;
     if (nd_list < 0) mexErrMsgIdAndTxt("fsgm:invalid", "%s: FSGM_DEVICES=\"%s\" is not a list of device ordinals", fn, list);
     if (nd_list == 0) { devs[0] = prm.device; nd_list = 1; }
+    fsgm_epi_options opt = fsgm_epi_options_default();
+    opt.adaptive_p2 = fsgm_env_int("FSGM_EPI_ADAPTIVE_P2", 0) != 0;
+    if (opt.adaptive_p2 && nd_list > 1) mexErrMsgIdAndTxt("fsgm:unsupported", "%s: FSGM_EPI_ADAPTIVE_P2=1 is not offered with a device list", fn);
     fsgm_register_atexit();
-    const fsgm_status st = fsgm_calc_cost_sgm_batch_devices_host((int32_t)n, in.data(), out.data(), &prm, nd_list, devs);
+    if (opt.adaptive_p2) prm.device = devs[0];
+    const fsgm_status st = opt.adaptive_p2 ? fsgm_calc_cost_sgm_batch_host_opts((int32_t)n, in.data(), out.data(), &prm, &opt)
+                                           : fsgm_calc_cost_sgm_batch_devices_host((int32_t)n, in.data(), out.data(), &prm, nd_list, devs);
     if (nlhs <= 1) mxDestroyArray(minC);
     check_status(fn, st);
 }
@@ -102,8 +109,10 @@ extern "C" void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* 
     prm.device = fsgm_env_int("FSGM_DEVICE", 0);
     prm.paths = fsgm_env_int("FSGM_EPI_PATHS", 4);
     prm.fb_check = fsgm_env_int("FSGM_EPI_FB_CHECK", 0) != 0;
+    fsgm_epi_options opt = fsgm_epi_options_default();
+    opt.adaptive_p2 = fsgm_env_int("FSGM_EPI_ADAPTIVE_P2", 0) != 0;
     fsgm_register_atexit();
-    const fsgm_status st = fsgm_calc_cost_sgm_host(&in, &out, &prm);
+    const fsgm_status st = fsgm_calc_cost_sgm_host_opts(&in, &out, &prm, &opt);
     if (nlhs <= 1) mxDestroyArray(minC);
     check_status(fn, st);
 }

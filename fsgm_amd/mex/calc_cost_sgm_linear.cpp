@@ -4,7 +4,8 @@
 //                                                      offsetFromPosD0, P1, P2)
 // The nine arguments and four outputs of calc_cost_sgm; vMax and offsetFromPosD0 are read and checked like there and, as in that
 // build of the reference, not used: candidate d lies d pixels along the direction (:368-369) and bestD is the index * 256.
-// Environment: FSGM_DEVICE, FSGM_EPI_PATHS and FSGM_EPI_FB_CHECK as for calc_cost_sgm (the check works on bestD / 256, :453, :508).
+// Environment: FSGM_DEVICE, FSGM_EPI_PATHS, FSGM_EPI_ADAPTIVE_P2 and FSGM_EPI_FB_CHECK as for calc_cost_sgm (the check works on
+// bestD / 256, :453, :508).
 // Everything computes on the GPU through libfsgm_hip.so; this file only unpacks mxArrays.
 #include "gateway_common.h"
 
@@ -43,8 +44,10 @@ extern "C" void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* 
     prm.device = fsgm_env_int("FSGM_DEVICE", 0);
     prm.paths = fsgm_env_int("FSGM_EPI_PATHS", 4);
     prm.fb_check = fsgm_env_int("FSGM_EPI_FB_CHECK", 0) != 0;
+    fsgm_epi_options opt = fsgm_epi_options_default();
+    opt.adaptive_p2 = fsgm_env_int("FSGM_EPI_ADAPTIVE_P2", 0) != 0;
     fsgm_register_atexit();
-    const fsgm_status st = fsgm_calc_cost_sgm_linear_host(&in, &out, &prm);
+    const fsgm_status st = fsgm_calc_cost_sgm_linear_host_opts(&in, &out, &prm, &opt);
     if (nlhs <= 1) mxDestroyArray(minC);
     check_status(fn, st);
 }

@@ -24,7 +24,7 @@ from typing import List, Tuple
 import numpy as np
 
 from . import _lib
-from ._lib import EpiIn, EpiOut, EpiParams, FsgmError, StereoParams
+from ._lib import EpiIn, EpiOut, EpiOptions, EpiParams, FsgmError, StereoParams
 from .epi import EpiGeometry, _params as _epi_params, _stereo_params
 from .post import _bind as _bind_post
 from .pyramid import PyramidParams, NgPyramidParams, FLOW_PP_FIELDS, MATCHERS, _bind as _bind_pyramid, _bind_flow_pp, _bind_ng
@@ -60,6 +60,11 @@ _bind_flow_pp(_L)
 _L.fsgm_calc_cost_sgm_device.argtypes = [_i32, C.POINTER(EpiIn), C.POINTER(EpiOut), C.POINTER(EpiParams), _vp, _vp]
 _L.fsgm_calc_cost_sgm_linear_device.argtypes = [_i32, C.POINTER(EpiIn), C.POINTER(EpiOut), C.POINTER(EpiParams), _vp, _vp]
 _L.fsgm_stereo_sgm_device.argtypes = [_i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, C.POINTER(StereoParams), _vp, _vp, _vp, _vp, _vp, _vp]
+_opt = C.POINTER(EpiOptions)
+_L.fsgm_calc_cost_sgm_device_opts.argtypes = [_i32, C.POINTER(EpiIn), C.POINTER(EpiOut), C.POINTER(EpiParams), _opt, _vp, _vp]
+_L.fsgm_calc_cost_sgm_linear_device_opts.argtypes = [_i32, C.POINTER(EpiIn), C.POINTER(EpiOut), C.POINTER(EpiParams), _opt, _vp, _vp]
+_L.fsgm_stereo_sgm_device_opts.argtypes = [_i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, C.POINTER(StereoParams), _opt, _vp, _vp, _vp, _vp,
+                                           _vp, _vp]
 _L.fsgm_epi_plan_run_device.argtypes = [_vp, _i32, C.POINTER(EpiIn), C.POINTER(EpiOut), _vp, _vp]
 _L.fsgm_epipolar_sgm_of_device.argtypes = [_i32, _vp, _vp, _i32, _i32, _i32, C.POINTER(EpiGeometry), _i32, C.c_double,
                                            C.POINTER(EpiParams), _vp, _vp, _vp, _vp]
@@ -126,7 +131,7 @@ def _geometries(geometry, N):
 @torch.library.custom_op("fsgm::calc_cost_sgm", mutates_args=())
 def _calc_cost_sgm_op(I1: torch.Tensor, I2: torch.Tensor, pd0: torch.Tensor, nd: torch.Tensor, off: torch.Tensor, dMax: int,
                       vMax: float, P1: int, P2: int, paths: int, subpixel: int, vz_to_disp: int,
-                      fb_check: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+                      fb_check: int, adaptive_p2: int = 0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
     N, H, W = I1.shape
     dev = I1.device
     I1, I2, pd0, nd, off = (_ready(t) for t in (I1, I2, pd0, nd, off))
@@ -140,12 +145,13 @@ def _calc_cost_sgm_op(I1: torch.Tensor, I2: torch.Tensor, pd0: torch.Tensor, nd:
     if fb_check:
         o.conf, o.bestD2 = _p(conf), _p(bestD2)
     prm = _epi_params(paths, subpixel, vz_to_disp, dev.index, fb_check)
-    _call(dev, _L.fsgm_calc_cost_sgm_device, N, C.byref(e), C.byref(o), C.byref(prm), _stream(dev), _p(status))
+    opt = _lib.options(adaptive_p2)
+    _call(dev, _L.fsgm_calc_cost_sgm_device_opts, N, C.byref(e), C.byref(o), C.byref(prm), C.byref(opt), _stream(dev), _p(status))
     return bestD, minC, conf, bestD2, status
 
 
 @_calc_cost_sgm_op.register_fake
-def _(I1, I2, pd0, nd, off, dMax, vMax, P1, P2, paths, subpixel, vz_to_disp, fb_check):
+def _(I1, I2, pd0, nd, off, dMax, vMax, P1, P2, paths, subpixel, vz_to_disp, fb_check, adaptive_p2=0):
     N, H, W = I1.shape
     dev = I1.device
     return (_u32((N, H, W), dev), _u32((N, H, W), dev),
@@ -160,7 +166,7 @@ def _fb_outputs(N, H, W, fb_check, dev):
 @torch.library.custom_op("fsgm::calc_cost_sgm_linear", mutates_args=())
 def _calc_cost_sgm_linear_op(I1: torch.Tensor, I2: torch.Tensor, pd0: torch.Tensor, nd: torch.Tensor, dMax: int, P1: int, P2: int,
                              paths: int, subpixel: int,
-                             fb_check: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+                             fb_check: int, adaptive_p2: int = 0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
     N, H, W = I1.shape
     dev = I1.device
     I1, I2, pd0, nd = (_ready(t) for t in (I1, I2, pd0, nd))
@@ -173,12 +179,13 @@ def _calc_cost_sgm_linear_op(I1: torch.Tensor, I2: torch.Tensor, pd0: torch.Tens
     if fb_check:
         o.conf, o.bestD2 = _p(conf), _p(bestD2)
     prm = _epi_params(paths, subpixel, 0, dev.index, fb_check)
-    _call(dev, _L.fsgm_calc_cost_sgm_linear_device, N, C.byref(e), C.byref(o), C.byref(prm), _stream(dev), _p(status))
+    opt = _lib.options(adaptive_p2)
+    _call(dev, _L.fsgm_calc_cost_sgm_linear_device_opts, N, C.byref(e), C.byref(o), C.byref(prm), C.byref(opt), _stream(dev), _p(status))
     return bestD, minC, conf, bestD2, status
 
 
 @_calc_cost_sgm_linear_op.register_fake
-def _(I1, I2, pd0, nd, dMax, P1, P2, paths, subpixel, fb_check):
+def _(I1, I2, pd0, nd, dMax, P1, P2, paths, subpixel, fb_check, adaptive_p2=0):
     N, H, W = I1.shape
     dev = I1.device
     return (_u32((N, H, W), dev), _u32((N, H, W), dev)) + _fb_outputs(N, H, W, fb_check, dev) + (_status(dev),)
@@ -186,20 +193,21 @@ def _(I1, I2, pd0, nd, dMax, P1, P2, paths, subpixel, fb_check):
 
 @torch.library.custom_op("fsgm::stereo_sgm", mutates_args=())
 def _stereo_sgm_op(left: torch.Tensor, right: torch.Tensor, dMax: int, P1: int, P2: int, paths: int, subpixel: int, direction: int,
-                   fb_check: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+                   fb_check: int, adaptive_p2: int = 0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
     N, H, W = left.shape
     dev = left.device
     left, right = _ready(left), _ready(right)
     disp, minC, status = _u32((N, H, W), dev), _u32((N, H, W), dev), _status(dev)
     conf, disp2 = _fb_outputs(N, H, W, fb_check, dev)
     prm = _stereo_params(paths, subpixel, direction, fb_check, dev.index)
-    _call(dev, _L.fsgm_stereo_sgm_device, N, _p(left), _p(right), W, H, int(dMax), int(P1), int(P2), C.byref(prm), _p(disp), _p(minC),
-          _p(conf) if fb_check else None, _p(disp2) if fb_check else None, _stream(dev), _p(status))
+    opt = _lib.options(adaptive_p2)
+    _call(dev, _L.fsgm_stereo_sgm_device_opts, N, _p(left), _p(right), W, H, int(dMax), int(P1), int(P2), C.byref(prm), C.byref(opt),
+          _p(disp), _p(minC), _p(conf) if fb_check else None, _p(disp2) if fb_check else None, _stream(dev), _p(status))
     return disp, minC, conf, disp2, status
 
 
 @_stereo_sgm_op.register_fake
-def _(left, right, dMax, P1, P2, paths, subpixel, direction, fb_check):
+def _(left, right, dMax, P1, P2, paths, subpixel, direction, fb_check, adaptive_p2=0):
     N, H, W = left.shape
     dev = left.device
     return (_u32((N, H, W), dev), _u32((N, H, W), dev)) + _fb_outputs(N, H, W, fb_check, dev) + (_status(dev),)
@@ -411,11 +419,12 @@ def _finish(outs, status, batched, check, return_status, why="an aggregation han
 
 
 def calc_cost_sgm(I1, I2, dMax, vMax, pixelPosD0, normlizeDirection, offsetFromPosD0, P1, P2, *, paths=4, subpixel=1,
-                  vz_to_disp=1, fb_check=0, check=False, return_status=False):
+                  vz_to_disp=1, fb_check=0, check=False, return_status=False, adaptive_p2=0):
     """[bestD, minC] = calc_cost_sgm(...) as fsgm_amd.calc_cost_sgm, on torch tensors on the GPU.  One frame: I1, I2 (H, W) uint8,
     pixelPosD0 / normlizeDirection (2, H, W) and offsetFromPosD0 (H, W) float64; a batch: the same with a leading N.
     Returns uint32 tensors of the same leading shape (and conf uint8 / bestD2 uint32 with fb_check=1; the status tensor last
-    with return_status=True).  check=True synchronises the current stream and raises FsgmError on a non-zero status."""
+    with return_status=True).  check=True synchronises the current stream and raises FsgmError on a non-zero status.
+    adaptive_p2=1: the reference's edge-aware large penalty (calc_cost_sgm.cpp:68-72), as fsgm_amd.calc_cost_sgm."""
     _tensors({"I1": (I1, torch.uint8), "I2": (I2, torch.uint8), "pixelPosD0": (pixelPosD0, torch.float64),
                     "normlizeDirection": (normlizeDirection, torch.float64), "offsetFromPosD0": (offsetFromPosD0, torch.float64)})
     if I1.dim() not in (2, 3):
@@ -431,16 +440,16 @@ def calc_cost_sgm(I1, I2, dMax, vMax, pixelPosD0, normlizeDirection, offsetFromP
         I1, I2, pixelPosD0, normlizeDirection, offsetFromPosD0 = (t.unsqueeze(0) for t in (I1, I2, pixelPosD0, normlizeDirection, offsetFromPosD0))
     bestD, minC, conf, bestD2, status = torch.ops.fsgm.calc_cost_sgm(I1, I2, pixelPosD0, normlizeDirection, offsetFromPosD0, int(dMax),
                                                                       float(vMax), int(P1), int(P2), int(paths), int(subpixel),
-                                                                      int(vz_to_disp), int(fb_check))
+                                                                      int(vz_to_disp), int(fb_check), int(adaptive_p2))
     outs = (bestD, minC, conf, bestD2) if fb_check else (bestD, minC)
     return _finish(outs, status, batched, check, return_status)
 
 
 def calc_cost_sgm_linear(I1, I2, dMax, pixelPosD0, normlizeDirection, P1, P2, *, paths=4, subpixel=1, fb_check=0, check=False,
-                         return_status=False):
+                         return_status=False, adaptive_p2=0):
     """[bestD, minC] as fsgm_amd.calc_cost_sgm_linear (the reference built without USE_VZIND), on torch tensors on the GPU.  One
     frame: I1, I2 (H, W) uint8, pixelPosD0 / normlizeDirection (2, H, W) float64; a batch: the same with a leading N.  Outputs,
-    fb_check, check and return_status as calc_cost_sgm."""
+    fb_check, check, return_status and adaptive_p2 as calc_cost_sgm."""
     _tensors({"I1": (I1, torch.uint8), "I2": (I2, torch.uint8), "pixelPosD0": (pixelPosD0, torch.float64),
               "normlizeDirection": (normlizeDirection, torch.float64)})
     if I1.dim() not in (2, 3):
@@ -454,15 +463,17 @@ def calc_cost_sgm_linear(I1, I2, dMax, pixelPosD0, normlizeDirection, P1, P2, *,
     if not batched:
         I1, I2, pixelPosD0, normlizeDirection = (t.unsqueeze(0) for t in (I1, I2, pixelPosD0, normlizeDirection))
     bestD, minC, conf, bestD2, status = torch.ops.fsgm.calc_cost_sgm_linear(I1, I2, pixelPosD0, normlizeDirection, int(dMax), int(P1),
-                                                                             int(P2), int(paths), int(subpixel), int(fb_check))
+                                                                             int(P2), int(paths), int(subpixel), int(fb_check),
+                                                                             int(adaptive_p2))
     outs = (bestD, minC, conf, bestD2) if fb_check else (bestD, minC)
     return _finish(outs, status, batched, check, return_status)
 
 
-def stereo_sgm(left, right, dMax, P1=6, P2=64, *, paths=4, subpixel=1, direction=-1, fb_check=0, check=False, return_status=False):
+def stereo_sgm(left, right, dMax, P1=6, P2=64, *, paths=4, subpixel=1, direction=-1, fb_check=0, check=False, return_status=False,
+               adaptive_p2=0):
     """disp, minC = stereo_sgm(left, right, dMax) as fsgm_amd.stereo_sgm, on torch tensors on the GPU: left, right (H, W) uint8
     or a batch (N, H, W); disp (disparity * 256) and minC uint32 of the same shape, plus conf uint8 / disp2 uint32 with
-    fb_check=1.  The outputs stay in HBM; the work is queued on the current stream."""
+    fb_check=1.  The outputs stay in HBM; the work is queued on the current stream.  adaptive_p2=1: edge-aware P2 on `left`."""
     _tensors({"left": (left, torch.uint8), "right": (right, torch.uint8)})
     if left.dim() not in (2, 3):
         raise TypeError(f"left must be (H, W) or (N, H, W) (got {tuple(left.shape)})")
@@ -470,11 +481,13 @@ def stereo_sgm(left, right, dMax, P1=6, P2=64, *, paths=4, subpixel=1, direction
     if int(dMax) < 1:
         raise ValueError(f"dMax must be >= 1 (got {dMax!r})")
     _stereo_params(paths, subpixel, direction, fb_check, 0)                 # the value checks, before anything is queued
+    if int(adaptive_p2) not in (0, 1):
+        raise ValueError(f"adaptive_p2 must be 0 or 1 (got {adaptive_p2!r})")
     batched = left.dim() == 3
     if not batched:
         left, right = left.unsqueeze(0), right.unsqueeze(0)
     disp, minC, conf, disp2, status = torch.ops.fsgm.stereo_sgm(left, right, int(dMax), int(P1), int(P2), int(paths), int(subpixel),
-                                                                 int(direction), int(bool(fb_check)))
+                                                                 int(direction), int(bool(fb_check)), int(adaptive_p2))
     outs = (disp, minC, conf, disp2) if fb_check else (disp, minC)
     return _finish(outs, status, batched, check, return_status)
 

@@ -109,6 +109,32 @@ fsgm_status fsgm_calc_cost_sgm_linear_host(const fsgm_epi_in* in, const fsgm_epi
 fsgm_status fsgm_calc_cost_sgm_linear_batch_host(int32_t n_frames, const fsgm_epi_in* in,
                                                  const fsgm_epi_out* out, const fsgm_epi_params* prm);
 
+/* Options beyond fsgm_epi_params / fsgm_stereo_params, which keep their size: the *_opts entry points below and further down take
+ * one of these (NULL = the defaults, all zero) next to the parameter struct of the entry point they extend, and compute
+ * exactly what that entry point computes when every option is off -- the older entry points forward to them with NULL.
+ *   adaptive_p2: 0 = as shipped (`const bool adpativeP2 = false`, calc_cost_sgm.cpp:102); 1 = the reference's edge-aware large
+ *   penalty (adaptive_P2, :68-72): every step of every path uses P2cur = |I1[cur] - I1[pre]| > 25 ? P2 / 8 : P2 in place of
+ *   P2, the division C's truncating int division, cur the pixel being computed, pre its predecessor on that path, I1 the call's
+ *   first image (all three samplings).  Path starts take no step.  Everything downstream is unchanged.  Adaptive calls
+ *   aggregate with the per-direction line kernels at every batch size (aggregation mode 1); the exact / mod-256 choice is
+ *   still made with the full P2.
+ * `reserved` must be zero. */
+typedef struct {
+    int32_t adaptive_p2;
+    int32_t reserved[7];
+} fsgm_epi_options;
+
+fsgm_epi_options fsgm_epi_options_default(void);       /* all zero */
+
+fsgm_status fsgm_calc_cost_sgm_host_opts(const fsgm_epi_in* in, const fsgm_epi_out* out, const fsgm_epi_params* prm,
+                                         const fsgm_epi_options* opt);
+fsgm_status fsgm_calc_cost_sgm_batch_host_opts(int32_t n_frames, const fsgm_epi_in* in, const fsgm_epi_out* out,
+                                               const fsgm_epi_params* prm, const fsgm_epi_options* opt);
+fsgm_status fsgm_calc_cost_sgm_linear_host_opts(const fsgm_epi_in* in, const fsgm_epi_out* out, const fsgm_epi_params* prm,
+                                                const fsgm_epi_options* opt);
+fsgm_status fsgm_calc_cost_sgm_linear_batch_host_opts(int32_t n_frames, const fsgm_epi_in* in, const fsgm_epi_out* out,
+                                                      const fsgm_epi_params* prm, const fsgm_epi_options* opt);
+
 /* ------------------------------------------------------------------------------------------
  * Rectified stereo: a left/right pair in, a disparity map out.  The linear matcher above with Pd0 = (x + 1, y + 1) and
  * direction (direction, 0) -- the sample of candidate d is cen2[y][clamp(x + direction * d, 0, W - 1)] -- without any map:
@@ -131,6 +157,10 @@ fsgm_stereo_params fsgm_stereo_params_default(void);   /* 4, 1, 0, -1, 0 */
 fsgm_status fsgm_stereo_sgm_host(int32_t n_frames, const uint8_t* I1, const uint8_t* I2, int32_t width, int32_t height,
                                  int32_t dMax, int32_t P1, int32_t P2, const fsgm_stereo_params* prm, uint32_t* disp,
                                  uint32_t* minC, uint8_t* conf, uint32_t* disp2);
+/* the same with options (fsgm_epi_options above: adaptive_p2 reads I1, the left view when direction = -1) */
+fsgm_status fsgm_stereo_sgm_host_opts(int32_t n_frames, const uint8_t* I1, const uint8_t* I2, int32_t width, int32_t height,
+                                      int32_t dMax, int32_t P1, int32_t P2, const fsgm_stereo_params* prm,
+                                      const fsgm_epi_options* opt, uint32_t* disp, uint32_t* minC, uint8_t* conf, uint32_t* disp2);
 
 /* ---- device-resident plan: buffers for `batch` frames stay in HBM across calls ---- */
 typedef struct fsgm_epi_plan fsgm_epi_plan;
@@ -176,6 +206,13 @@ fsgm_status fsgm_epi_plan_set_penalties(fsgm_epi_plan* plan, int32_t P1, int32_t
  * _time report as FSGM_ERR_HIP.  The cost stage's own buffers (images, census, coordinate maps) appear with the first upload
  * or FSGM_STAGE_COST run: an aggregation-only plan never allocates them. */
 fsgm_status fsgm_epi_plan_set_agg_mode(fsgm_epi_plan* plan, int32_t mode);
+/* Adaptive P2 for this plan (fsgm_epi_options.adaptive_p2; 0 at creation).  An adaptive plan resolves to the line kernels
+ * whatever its batch ("packed16/nowrap", "packed16/wrap" or "generic"): switching it on after modes 2-6 were forced, and
+ * fsgm_epi_plan_set_agg_mode(2..6) on an adaptive plan, return FSGM_ERR_UNSUPPORTED and change nothing.  The aggregate stage
+ * then reads the first image of every slot: an aggregation-only plan (fsgm_epi_plan_upload_cost) supplies it through
+ * fsgm_epi_plan_upload_images, and a run with a slot whose image was never uploaded returns FSGM_ERR_INVALID before
+ * anything is queued.  With 0 every output and every kernel selection is what it was before the switch existed. */
+fsgm_status fsgm_epi_plan_set_adaptive_p2(fsgm_epi_plan* plan, int32_t on);
 /* host -> HBM (async on the plan's stream) */
 fsgm_status fsgm_epi_plan_upload(fsgm_epi_plan* plan, int32_t frame, const uint8_t* I1,
                                  const uint8_t* I2, const double* pixelPosD0,
@@ -218,6 +255,9 @@ const char* fsgm_epi_plan_kernel_name(fsgm_epi_plan* plan);
  * FSGM_EPI_PAR_MIN / _PAR_MAX / _PAIRS_MIN / _BAND_MIN in the environment override them.  "" for invalid arguments. */
 const char* fsgm_epi_auto_pipeline(int32_t width, int32_t height, int32_t dMax, int32_t batch, int32_t paths, int32_t P1, int32_t P2,
                                    int32_t cmax, int32_t cus);
+/* the same for a call with options: an adaptive-P2 call takes the line kernels at every batch size */
+const char* fsgm_epi_auto_pipeline_opts(int32_t width, int32_t height, int32_t dMax, int32_t batch, int32_t paths, int32_t P1,
+                                        int32_t P2, int32_t cmax, int32_t cus, const fsgm_epi_options* opt);
 /* device-to-device copy bandwidth probe (GB/s, read+written bytes counted) used by bench.py: the library's own
  * grid-stride copy kernel, 16 B per lane per access -- the access width of the aggregation kernels */
 fsgm_status fsgm_measure_copy_bandwidth(int32_t device, size_t bytes, int32_t iters, double* gbps);
@@ -704,10 +744,20 @@ fsgm_status fsgm_calc_cost_sgm_device(int32_t n_frames, const fsgm_epi_in* in, c
 /* fsgm_calc_cost_sgm_linear_batch_host on n_frames contiguous frames: in->offset is not read (may be NULL) */
 fsgm_status fsgm_calc_cost_sgm_linear_device(int32_t n_frames, const fsgm_epi_in* in, const fsgm_epi_out* out,
                                              const fsgm_epi_params* prm, void* stream, int32_t* status);
+/* the two above with options (fsgm_epi_options; the cached plans of adaptive and non-adaptive calls are distinct) */
+fsgm_status fsgm_calc_cost_sgm_device_opts(int32_t n_frames, const fsgm_epi_in* in, const fsgm_epi_out* out,
+                                           const fsgm_epi_params* prm, const fsgm_epi_options* opt, void* stream, int32_t* status);
+fsgm_status fsgm_calc_cost_sgm_linear_device_opts(int32_t n_frames, const fsgm_epi_in* in, const fsgm_epi_out* out,
+                                                  const fsgm_epi_params* prm, const fsgm_epi_options* opt, void* stream,
+                                                  int32_t* status);
 /* fsgm_stereo_sgm_host on device pointers (one cached rectified plan of batch n_frames) */
 fsgm_status fsgm_stereo_sgm_device(int32_t n_frames, const uint8_t* I1, const uint8_t* I2, int32_t width, int32_t height,
                                    int32_t dMax, int32_t P1, int32_t P2, const fsgm_stereo_params* prm, uint32_t* disp,
                                    uint32_t* minC, uint8_t* conf, uint32_t* disp2, void* stream, int32_t* status);
+fsgm_status fsgm_stereo_sgm_device_opts(int32_t n_frames, const uint8_t* I1, const uint8_t* I2, int32_t width, int32_t height,
+                                        int32_t dMax, int32_t P1, int32_t P2, const fsgm_stereo_params* prm,
+                                        const fsgm_epi_options* opt, uint32_t* disp, uint32_t* minC, uint8_t* conf, uint32_t* disp2,
+                                        void* stream, int32_t* status);
 /* epipolar_sgm_of on n_frames image pairs, one plan of batch n_frames: g (HOST memory) holds n_frames geometries, each
  * passed to the maps kernel by value.  I0 / I1 u8 [n][channels][H][W]; flow f64 [n][3][H][W]; minC (may be NULL) u32 [n][H][W]. */
 fsgm_status fsgm_epipolar_sgm_of_device(int32_t n_frames, const uint8_t* I0, const uint8_t* I1, int32_t width,
