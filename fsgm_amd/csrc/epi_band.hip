@@ -243,10 +243,15 @@ __global__ __launch_bounds__(NWV * 64, FSGM_BAND_MINW) void band_kernel(BandArgs
         f = (size_t)grp * a.group + rem % fin;
         if (cband >= a.nbands || f >= (size_t)a.frames) return;                                        // (never: the grid is frames x bands)
     }
-    const uint8_t* __restrict__ Cf = a.C + f * a.c_frame_stride;
-    uint8_t* __restrict__ Yf = a.Y + f * a.y_frame_stride;
+    // The volumes' byte offsets carry a constant VB, taken back out of the bases: a row's offset runs linearly in x (vox_lin
+    // below: +-D per step, kept in a register) from before the row's first pixel to past its last, and with VB it stays at or
+    // above zero in the first row of a frame too -- unsigned clamps hold it inside the row.  The bit plane's offset is a quarter
+    // of it (D = 16 LPP: (pix * LPP + j) * 4 = (pix * D + 16 j) / 4).
+    constexpr uint32_t VB = (uint32_t)(SKEW * R + PF) * D;
     constexpr bool Y16 = BITS && FSGM_BAND_Y16 != 0;         // BITS: the second volume is registers 4-7 as they are (Yf: registers 0-3), not a bit plane
-    uint8_t* __restrict__ Bf = BITS ? (uint8_t*)(a.Yb + f * a.yb_frame_stride) : nullptr;     // [NP][LPP] dwords (Y16: [NP][LPP] uint4)
+    const uint8_t* __restrict__ Cf = a.C + f * a.c_frame_stride - VB;
+    uint8_t* __restrict__ Yf = a.Y + f * a.y_frame_stride - VB;
+    uint8_t* __restrict__ Bf = BITS ? (uint8_t*)(a.Yb + f * a.yb_frame_stride) - (Y16 ? VB : VB / 4) : nullptr;     // [NP][LPP] dwords (Y16: [NP][LPP] uint4)
     uint8_t* __restrict__ Ef = (uint8_t*)(a.edge + f * a.edge_frame_stride);                  // [W][NST][LPP] uint4 (CHAIN: one such map per band boundary)
     const uint32_t tag = CHAIN ? a.tag : 0u;
     uint8_t* __restrict__ recb = MODE == 2 ? (uint8_t*)(a.rec + f * (size_t)NP) : nullptr;
@@ -258,6 +263,7 @@ __global__ __launch_bounds__(NWV * 64, FSGM_BAND_MINW) void band_kernel(BandArgs
     const uint32_t KX = sconst<0x007F007Fu>(), K0 = 127u - (P2 + (uint32_t)a.P1);
     const uint32_t K1pk = (uint32_t)(PATHS * (a.P1 + a.P2) - (PATHS / 2) * 127) * 0x10001u;   // (may be negative: exact mod 2^32, see do_step)
     const uint4 startP = make_uint4(P2 * 0x01010101u, P2 * 0x01010101u, P2 * 0x01010101u, P2 * 0x01010101u);
+    const uint32_t DS = sconst<(uint32_t)D>();               // (a literal would double the carried offset's add)
     const LaneSel sel = lane_sel<LPP>(j);
     const int elane = min(lane, NST * LPP - 1);                // wave 0: lane = state * LPP + lane-of-pixel of the hand-off words
 
@@ -281,14 +287,14 @@ __global__ __launch_bounds__(NWV * 64, FSGM_BAND_MINW) void band_kernel(BandArgs
         const int pl_lo = SKEW * r_hi + 1, pl_hi = W - 2 + SKEW * r_lo;
         const bool wave_plain_rows = r_hi < Rp && yb + r_lo >= 1;
 
-        auto vox_off = [&](int u) -> uint32_t {               // byte offset of this lane's 16 bytes at step u (clamped into the image)
-            const int x = min(max(u - SKEW * r, 0), W - 1);
-            return (uint32_t)pix_of(x, yc) * D + (uint32_t)j * 16;
-        };
-        auto bit_off = [&](int u) -> uint32_t {                // byte offset of this lane's dword of the bit plane
-            const int x = min(max(u - SKEW * r, 0), W - 1);
-            return ((uint32_t)pix_of(x, yc) * LPP + (uint32_t)j) * 4u;
-        };
+        // byte offset (+ VB) of this lane's 16 bytes of pixel x of its row: linear in x, also outside the row (exact mod 2^32)
+        auto vox_lin = [&](int x) -> uint32_t { return (uint32_t)pix_of(x, yc) * D + ((uint32_t)j * 16 + VB); };
+        auto vox_off = [&](int u) -> uint32_t { return vox_lin(min(max(u - SKEW * r, 0), W - 1)); };   // at step u, clamped into the image
+        // The prefetch offset, carried: step u loads the words of step u + PF, pixel x + PF of the row -- one add a step
+        // and one clamp against the row's two ends instead of the chain from u (the tail steps carry on with it; the
+        // prologue's loads take the long way)
+        uint32_t vpf = vox_lin(PF - 1 - SKEW * r);
+        const uint32_t v_lo = vox_lin(UP ? W - 1 : 0), v_hi = vox_lin(UP ? 0 : W - 1);
         // hand-off maps of this band: the one it reads (written by the band above) and the one it writes
         const uint32_t emap = (uint32_t)W * (NST * LPP) * 16u;
         const uint8_t* __restrict__ Ein = CHAIN ? Ef + (uint32_t)max(cband - 1, 0) * emap : Ef;
@@ -376,7 +382,7 @@ __global__ __launch_bounds__(NWV * 64, FSGM_BAND_MINW) void band_kernel(BandArgs
             if (MODE == 2) {
                 ringY[i] = vol_load(Yf + off);
                 if (Y16) ringB4[i] = vol_load(Bf + off);
-                else if (BITS) ringB[i] = *(const uint32_t*)(Bf + bit_off(i));
+                else if (BITS) ringB[i] = *(const uint32_t*)(Bf + (off >> 2));
             }
         }
         if (loader) {
@@ -494,13 +500,16 @@ __global__ __launch_bounds__(NWV * 64, FSGM_BAND_MINW) void band_kernel(BandArgs
             if (MODE != 2) {
                 // the sum of this pass's y (:227-232): low bytes + 9th bits
                 if (inside) {
-                    const uint32_t px = (uint32_t)pix_of(xc, yc);
+                    // plain: the prefetch offset of PF steps ago (0 < x < W - 1: no clamp came in between), the constant
+                    // in the instruction's offset field
+                    const uint32_t so = EDGE ? vox_lin(xc) : vpf;
+                    constexpr int SB = EDGE ? 0 : PF * D;
                     if (Y16) {
-                        vol_store(Yf + px * D + (uint32_t)j * 16, make_uint4(YS[0], YS[1], YS[2], YS[3]));
-                        vol_store(Bf + px * D + (uint32_t)j * 16, make_uint4(YS[4], YS[5], YS[6], YS[7]));
+                        vol_store(Yf + so - SB, make_uint4(YS[0], YS[1], YS[2], YS[3]));
+                        vol_store(Bf + so - SB, make_uint4(YS[4], YS[5], YS[6], YS[7]));
                     } else {
-                        vol_store(Yf + px * D + (uint32_t)j * 16, pack_p(YS));
-                        if (BITS) *(uint32_t*)(Bf + (px * LPP + (uint32_t)j) * 4u) = pack_hi_bits(YS);
+                        vol_store(Yf + so - SB, pack_p(YS));
+                        if (BITS) *(uint32_t*)(Bf + (so >> 2) - SB / 4) = pack_hi_bits(YS);
                     }
                 }
             } else {
@@ -571,12 +580,15 @@ __global__ __launch_bounds__(NWV * 64, FSGM_BAND_MINW) void band_kernel(BandArgs
             const uint4 cy = ringY[MODE == 2 ? k : 0];
             const uint32_t cb = ringB[MODE == 2 && BITS && !Y16 ? k : 0];
             const uint4 cb4 = ringB4[MODE == 2 && Y16 ? k : 0];
-            const uint32_t off = vox_off(u + PF);
+            vpf = UP ? vpf - DS : vpf + DS;
+            asm("" : "+v"(vpf));                               // one register, one add: not split into a base and induction variables
+            uint32_t off;                                      // = vox_off(u + PF)
+            asm("v_med3_u32 %0, %1, %2, %3" : "=v"(off) : "v"(vpf), "v"(v_lo), "v"(v_hi));
             ringC[kl] = *(const uint4*)(Cf + off);
             if (MODE == 2) {
                 ringY[kl] = vol_load(Yf + off);
                 if (Y16) ringB4[kl] = vol_load(Bf + off);
-                else if (BITS) ringB[kl] = *(const uint32_t*)(Bf + bit_off(u + PF));
+                else if (BITS) ringB[kl] = *(const uint32_t*)(Bf + (off >> 2));
             }
             step(u, i & 1, cw, cy, cb, cb4);
         };
