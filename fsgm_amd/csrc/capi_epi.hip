@@ -164,11 +164,14 @@ static int pairs_min_batch(int W, int H, int D) { return switch_batch("FSGM_EPI_
 // arguments and the FSGM_EPI_* environment only, so that fsgm_epi_auto_pipeline can answer without a plan.
 static Pipeline choose_pipeline(int W, int H, int D, int batch, int paths, int P1, int P2, int cm, int agg_mode, int cus,
                                 int adaptive = 0) {
-    if (agg_packed_lpp(D) == 0) return PIPE_GENERIC;
+    if (!agg_line_split(D)) return PIPE_GENERIC;
     // (adaptive P2 lowers P2 per step, never raises it: the no-wrap test with the full P2 covers every step)
     const bool nowrap = P1 >= 0 && P2 >= 0 && cm + P2 + std::max(P1, P2) <= 255;
     Pipeline c = nowrap ? PIPE_PACKED_NOWRAP : PIPE_PACKED_WRAP;
     if (adaptive) return c;                                      // the fused pipelines have no per-step P2: line kernels at every batch size
+    // 48 .. 224 (12, 20 or 28 costs a lane): the fused pipelines' register layout is 16 costs a lane -- line kernels at every
+    // batch size and under every forced mode, as for a dMax the generic kernels take
+    if (agg_packed_lpp(D) == 0) return c;
     // the fused sweeps cover the 8-path no-wrap case; everything else stays on the line kernels
     // Auto mode takes the fused pipelines only for batches: their latency (H rows in sequence for a sweep, down then
     // up; three passes along 1242-pixel rows for a pair) is 1.0 / 2.0 ms (4 / 8 paths) whatever the frame count,
@@ -930,7 +933,7 @@ static fsgm_status enqueue(fsgm_epi_plan* p, int stages) {
             launch_sweep_finish(p->stream, a, p->dRec, p->dS0, p->batch);
         } else {                                         // a WTA kernel over the path volumes
             a.L = p->dL; a.l_frame_stride = p->N * p->prm.paths; a.l_dir_stride = p->N;
-            launch_wta(p->stream, a, p->batch, agg_packed_lpp(p->D) != 0);
+            launch_wta(p->stream, a, p->batch, agg_line_split(p->D));
         }
     }
     if ((stages & FSGM_STAGE_WTA) && p->prm.fb_check) {

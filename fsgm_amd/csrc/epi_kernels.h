@@ -139,7 +139,10 @@ struct FbArgs {                // forward-backward check (calc_cost_sgm.cpp:429-
 
 enum { AGG_PACKED_NOWRAP = 0, AGG_PACKED_WRAP = 1, AGG_GENERIC = 2, AGG_SWEEP = 3, AGG_PAIRS = 4, AGG_BAND = 5 };
 
-int  agg_packed_lpp(int D);   // lanes per pixel of the packed kernels, 0 if D is not 16<<k, k<=4
+int  agg_packed_lpp(int D);   // lanes per pixel at 16 d per lane -- what the fused pipelines need --, 0 if D is not 16<<k, k<=4
+// the general line kernels' and the packed WTA's split of D: lpp lanes of dpl costs a pixel (either may be null).  16 << k as above
+// with dpl = 16; 48, 96, 192 (dpl 12), 80, 160 (20), 112, 224 (28); false for every other D: the generic kernels
+bool agg_line_split(int D, int* lpp = nullptr, int* dpl = nullptr);
 void launch_census(hipStream_t st, const uint8_t* img, uint32_t* cen, int W, int H, int frames);
 void launch_epi_cost(hipStream_t st, const EpiCostArgs& a, uint8_t* C, int frames);
 // the cost stage as one kernel (epi_cost.hip): raw costs + 5x5 box mean, a.Craw unused

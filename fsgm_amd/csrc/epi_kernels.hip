@@ -440,6 +440,35 @@ __global__ __launch_bounds__(256) void box5x5_sliding16_kernel(const uint8_t* __
 #ifndef FSGM_AGG_PFO
 #define FSGM_AGG_PFO 4
 #endif
+// N dwords at a 4-byte aligned address past the caches, as pieces of 4, 2 and 1 dwords (a three-element vector would be stored
+// as four): what the splits with 12, 20 or 28 costs a lane move (agg_line_split).  Exactly 4 N bytes are read or written.
+typedef uint32_t u32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));
+typedef uint32_t u32x2_a4 __attribute__((ext_vector_type(2), aligned(4)));
+template <int N>
+__device__ __forceinline__ void store_nt_words(uint8_t* p, const uint32_t* w) {
+    if constexpr (N >= 4) {
+        const u32x4_a4 t = {w[0], w[1], w[2], w[3]};
+        __builtin_nontemporal_store(t, (u32x4_a4*)p);
+        store_nt_words<N - 4>(p + 16, w + 4);
+    } else if constexpr (N >= 2) {
+        const u32x2_a4 t = {w[0], w[1]};
+        __builtin_nontemporal_store(t, (u32x2_a4*)p);
+        store_nt_words<N - 2>(p + 8, w + 2);
+    } else if constexpr (N == 1) __builtin_nontemporal_store(w[0], (uint32_t*)p);
+}
+template <int N>
+__device__ __forceinline__ void load_nt_words(const uint8_t* p, uint32_t* w) {
+    if constexpr (N >= 4) {
+        const u32x4_a4 t = __builtin_nontemporal_load((const u32x4_a4*)p);
+        w[0] = t.x; w[1] = t.y; w[2] = t.z; w[3] = t.w;
+        load_nt_words<N - 4>(p + 16, w + 4);
+    } else if constexpr (N >= 2) {
+        const u32x2_a4 t = __builtin_nontemporal_load((const u32x2_a4*)p);
+        w[0] = t.x; w[1] = t.y;
+        load_nt_words<N - 2>(p + 8, w + 2);
+    } else if constexpr (N == 1) w[0] = __builtin_nontemporal_load((const uint32_t*)p);
+}
+
 // ADAPT (adaptive P2, calc_cost_sgm.cpp:68-72 with adpativeP2 = true): a step uses P2 / 8 in place of P2 where the first image
 // differs by more than 25 between the pixel and its predecessor on the path.  The pixel bytes ride with the cost words: one
 // byte load a step into a ring of its own, PF steps ahead with the same clamped cursor (the LPP lanes of a pixel read the same
@@ -455,8 +484,11 @@ __device__ __forceinline__ void agg_packed_body(const AggArgs& a, const int slot
     constexpr int PF = (BASE == 0 && NK == 1) ? FSGM_AGG_PFX : FSGM_AGG_PFO;
     constexpr uint32_t SENT = 0xFFFFFFFFu;
     constexpr uint32_t MASK = 0x00FF00FFu;
-    static_assert(LPP >= 1 && LPP <= 32 && (NK == 1 || NK == 2 || NK == 4), "lane split");
-    struct __attribute__((aligned(NK * 4))) Words { uint32_t v[NK]; };
+    static_assert(LPP >= 1 && LPP <= 32 && (LPP & (LPP - 1)) == 0 && DPL % 4 == 0 && NK >= 1 && NK <= 7 && (NK <= 2 || NK == 4 || LPP <= 16),
+                  "lane split");
+    // NK = 3, 5, 7 (D = 48 .. 224, agg_line_split): a lane's costs start at pix * D + j * DPL, a multiple of 4 only
+    constexpr bool POW2 = (NK & (NK - 1)) == 0;
+    struct __attribute__((aligned(POW2 ? NK * 4 : 4))) Words { uint32_t v[NK]; };
 
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int g = lane / LPP, j = lane % LPP;
@@ -499,7 +531,9 @@ __device__ __forceinline__ void agg_packed_body(const AggArgs& a, const int slot
     };
     // the path volumes are written once and read once by the WTA kernel: streamed past the caches (FSGM_LINE_NT)
     auto store_words = [&](uint8_t* p, const Words& w) {
-        if (FSGM_LINE_NT) {
+        if constexpr (!POW2) {
+            if (FSGM_LINE_NT) store_nt_words<NK>(p, w.v); else *(Words*)p = w;       // 4 + 2 + 1 dwords, each piece 4-byte aligned
+        } else if (FSGM_LINE_NT) {
             typedef uint32_t wv __attribute__((ext_vector_type(NK)));
             wv t;
 #pragma unroll
@@ -992,6 +1026,24 @@ __global__ __launch_bounds__(256) void agg_packed_kernel(AggArgs a) { agg_packed
 template <int D, bool WRAP>
 __global__ __launch_bounds__(256) void agg_packed_adaptive_kernel(AggArgs a) { agg_packed_dispatch<D, WRAP, true, true>(a); }
 
+// D = 48 .. 224 (agg_line_split: LPP x DPL with DPL = 12, 20 or 28): the general body for every direction with that one split
+// -- no finer split along x, none of the hand-written steps, whose register layouts are 2 or 16 costs a lane
+template <int D, int DPL, bool WRAP, bool ADAPT>
+__global__ __launch_bounds__(256) void agg_split_kernel(AggArgs a) {
+    int slot = 0;                       // which direction slot does this block belong to (block-uniform)
+#pragma unroll
+    for (int i = 1; i < 8; i++)
+        if (i < a.ndirs && (int)blockIdx.x >= a.blk_begin[i]) slot = i;
+    const int code = a.dir_code[slot];
+    const bool mirror = (code & 4) != 0;
+    switch (code & 3) {                 // 0: along x, 1: along y, 2: x+1,y+1, 3: x-1,y+1
+        case 0: agg_packed_body<D, DPL, WRAP, 0, ADAPT>(a, slot, mirror); break;
+        case 1: agg_packed_body<D, DPL, WRAP, 1, ADAPT>(a, slot, mirror); break;
+        case 2: agg_packed_body<D, DPL, WRAP, 2, ADAPT>(a, slot, mirror); break;
+        default: agg_packed_body<D, DPL, WRAP, 3, ADAPT>(a, slot, mirror); break;
+    }
+}
+
 // =============================================================================================
 // Path aggregation, generic kernel: any D (<= FSGM_GENERIC_MAX_D), exact u8 semantics.
 // One wave per line, Lpre/Lcur in LDS, lanes stride over d.  Correctness path for disparity
@@ -1085,13 +1137,14 @@ __device__ __forceinline__ uint32_t sum_at(const uint8_t* Lf, size_t dir_stride,
     return s;
 }
 
-// packed WTA: LPP lanes per pixel, 16 d per lane; sums kept as 2 x u16 (8 paths x 255 < 65536)
-template <int LPP>
-__global__ __launch_bounds__(256) void wta_packed_kernel(WtaArgs a) {
-    constexpr int D = LPP * 16;
+// packed WTA: LPP lanes per pixel, DPL d per lane (16, or 12 / 20 / 28 for D = 48 .. 224); sums kept as 2 x u16 (8 paths x 255 < 65536)
+template <int LPP, int DPL>
+__device__ __forceinline__ void wta_packed_body(const WtaArgs& a) {
+    constexpr int D = LPP * DPL, NK = DPL / 4;
     constexpr int PPB = 256 / LPP;                           // pixels per block
     constexpr uint32_t MASK = 0x00FF00FFu;
-    __shared__ uint32_t sS[256 * 8];                         // u16 S[PPB][D]
+    static_assert(DPL % 4 == 0 && D <= 256, "the key holds d in 8 bits");
+    __shared__ uint32_t sS[256 * DPL / 2];                   // u16 S[PPB][D]
     const int tid = threadIdx.x;
     const int NP = a.W * a.H;
     const int gp = blockIdx.x * PPB + tid / LPP, j = tid % LPP;
@@ -1099,26 +1152,31 @@ __global__ __launch_bounds__(256) void wta_packed_kernel(WtaArgs a) {
     const int p = valid ? gp : NP - 1;
     const size_t f = blockIdx.y;
     const uint8_t* __restrict__ Lf = a.L + f * a.l_frame_stride;
-    uint32_t E[4] = {0, 0, 0, 0}, O[4] = {0, 0, 0, 0};
-    const size_t off = (size_t)p * D + (size_t)j * 16;
+    uint32_t E[NK], O[NK];
+#pragma unroll
+    for (int k = 0; k < NK; k++) E[k] = O[k] = 0;
+    const size_t off = (size_t)p * D + (size_t)j * DPL;
 #pragma unroll
     for (int r = 0; r < 8; r++) {
         if (r < a.ndirs) {
-            const uint4 v = FSGM_LINE_NT ? load_nt(Lf + (size_t)r * a.l_dir_stride + off) : *(const uint4*)(Lf + (size_t)r * a.l_dir_stride + off);
-            const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+            uint32_t w[NK];
+            if constexpr (NK == 4) {
+                const uint4 v = FSGM_LINE_NT ? load_nt(Lf + (size_t)r * a.l_dir_stride + off) : *(const uint4*)(Lf + (size_t)r * a.l_dir_stride + off);
+                w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
+            } else load_nt_words<NK>(Lf + (size_t)r * a.l_dir_stride + off, w);     // the lane's DPL bytes, no more
 #pragma unroll
-            for (int k = 0; k < 4; k++) { E[k] += w[k] & MASK; O[k] += (w[k] >> 8) & MASK; }
+            for (int k = 0; k < NK; k++) { E[k] += w[k] & MASK; O[k] += (w[k] >> 8) & MASK; }
         }
     }
     // S to LDS in natural d order; key = (S << 8) | d, minimum key = first minimum (:267)
     uint32_t key = 0xFFFFFFFFu;
-    uint32_t* row = sS + (size_t)(tid / LPP) * (D / 2) + j * 8;
+    uint32_t* row = sS + (size_t)(tid / LPP) * (D / 2) + j * (DPL / 2);
 #pragma unroll
-    for (int k = 0; k < 4; k++) {
+    for (int k = 0; k < NK; k++) {
         const uint32_t s0 = E[k] & 0xFFFF, s1 = O[k] & 0xFFFF, s2 = E[k] >> 16, s3 = O[k] >> 16;
         row[2 * k] = s0 | (s1 << 16);
         row[2 * k + 1] = s2 | (s3 << 16);
-        const uint32_t d0 = (uint32_t)j * 16 + 4 * k;
+        const uint32_t d0 = (uint32_t)j * DPL + 4 * k;
         key = min(key, min(min((s0 << 8) | d0, (s1 << 8) | (d0 + 1)), min((s2 << 8) | (d0 + 2), (s3 << 8) | (d0 + 3))));
     }
     key = group_min_u32<LPP>(key);
@@ -1136,6 +1194,10 @@ __global__ __launch_bounds__(256) void wta_packed_kernel(WtaArgs a) {
         wta_finish(a, f, p, best, minc, c_1, c1);
     }
 }
+template <int LPP>
+__global__ __launch_bounds__(256) void wta_packed_kernel(WtaArgs a) { wta_packed_body<LPP, 16>(a); }
+template <int LPP, int DPL>
+__global__ __launch_bounds__(256) void wta_split_kernel(WtaArgs a) { wta_packed_body<LPP, DPL>(a); }
 
 // generic WTA: one wave per pixel, lanes stride over d
 __global__ __launch_bounds__(256) void wta_generic_kernel(WtaArgs a) {
@@ -1336,6 +1398,27 @@ int agg_packed_lpp(int D) {
     return 0;
 }
 
+// How the general line kernels and the packed WTA split D over the lanes of a pixel: lpp lanes (a power of two, at most 16: one
+// DPP row) of dpl costs (a multiple of 4).  16 costs a lane where agg_packed_lpp() knows D; 12, 20 or 28 for the seven ranges
+// below.  144, 176, 208 and 240 would take 36 .. 60 costs a lane (18 .. 30 state registers and a ring of as many dwords a
+// prefetched step): not offered, the generic kernels take them.
+bool agg_line_split(int D, int* lpp, int* dpl) {
+    int l = agg_packed_lpp(D), c = 16;
+    switch (D) {
+        case 48: l = 4; c = 12; break;
+        case 96: l = 8; c = 12; break;
+        case 192: l = 16; c = 12; break;
+        case 80: l = 4; c = 20; break;
+        case 160: l = 8; c = 20; break;
+        case 112: l = 4; c = 28; break;
+        case 224: l = 8; c = 28; break;
+    }
+    if (l == 0) return false;
+    if (lpp) *lpp = l;
+    if (dpl) *dpl = c;
+    return true;
+}
+
 // Fill blk_begin / dir_code for `paths` directions.  Long (horizontal) lines first so that the
 // W-step chains start before the H-step ones.
 static void plan_dirs(AggArgs& a, int paths, int lines_per_block_x, int lines_per_block) {
@@ -1384,6 +1467,20 @@ static void launch_packed(hipStream_t st, AggArgs& a, int paths, int frames, boo
     }
 }
 
+template <int D, int DPL>
+static void launch_split(hipStream_t st, AggArgs& a, int paths, int frames, bool wrap) {
+    constexpr int LPB = 4 * (64 / (D / DPL));                    // lines per block, every direction
+    plan_dirs(a, paths, LPB, LPB);
+    dim3 grid(a.blk_begin[8], frames);
+    if (a.adaptive) {
+        if (wrap) hipLaunchKernelGGL((agg_split_kernel<D, DPL, true, true>), grid, dim3(256), 0, st, a);
+        else      hipLaunchKernelGGL((agg_split_kernel<D, DPL, false, true>), grid, dim3(256), 0, st, a);
+    } else {
+        if (wrap) hipLaunchKernelGGL((agg_split_kernel<D, DPL, true, false>), grid, dim3(256), 0, st, a);
+        else      hipLaunchKernelGGL((agg_split_kernel<D, DPL, false, false>), grid, dim3(256), 0, st, a);
+    }
+}
+
 void launch_aggregate(hipStream_t st, AggArgs a, int paths, int frames, int kernel_kind) {
     if (kernel_kind == AGG_GENERIC) {
         plan_dirs(a, paths, 4, 4);
@@ -1399,6 +1496,13 @@ void launch_aggregate(hipStream_t st, AggArgs a, int paths, int frames, int kern
         case 64: launch_packed<64>(st, a, paths, frames, wrap); break;
         case 128: launch_packed<128>(st, a, paths, frames, wrap); break;
         case 256: launch_packed<256>(st, a, paths, frames, wrap); break;
+        case 48: launch_split<48, 12>(st, a, paths, frames, wrap); break;
+        case 96: launch_split<96, 12>(st, a, paths, frames, wrap); break;
+        case 192: launch_split<192, 12>(st, a, paths, frames, wrap); break;
+        case 80: launch_split<80, 20>(st, a, paths, frames, wrap); break;
+        case 160: launch_split<160, 20>(st, a, paths, frames, wrap); break;
+        case 112: launch_split<112, 28>(st, a, paths, frames, wrap); break;
+        case 224: launch_split<224, 28>(st, a, paths, frames, wrap); break;
         default: break;
     }
 }
@@ -1406,8 +1510,18 @@ void launch_aggregate(hipStream_t st, AggArgs a, int paths, int frames, int kern
 void launch_wta(hipStream_t st, const WtaArgs& a, int frames, bool packed) {
     const int NP = a.W * a.H;
     if (packed) {
-        const int lpp = agg_packed_lpp(a.D);
+        int lpp = 0, dpl = 0;
+        if (!agg_line_split(a.D, &lpp, &dpl)) return;            // (the callers ask the same predicate)
         dim3 grid((NP + 256 / lpp - 1) / (256 / lpp), frames);
+        switch (a.D) {
+            case 48: hipLaunchKernelGGL((wta_split_kernel<4, 12>), grid, dim3(256), 0, st, a); return;
+            case 96: hipLaunchKernelGGL((wta_split_kernel<8, 12>), grid, dim3(256), 0, st, a); return;
+            case 192: hipLaunchKernelGGL((wta_split_kernel<16, 12>), grid, dim3(256), 0, st, a); return;
+            case 80: hipLaunchKernelGGL((wta_split_kernel<4, 20>), grid, dim3(256), 0, st, a); return;
+            case 160: hipLaunchKernelGGL((wta_split_kernel<8, 20>), grid, dim3(256), 0, st, a); return;
+            case 112: hipLaunchKernelGGL((wta_split_kernel<4, 28>), grid, dim3(256), 0, st, a); return;
+            case 224: hipLaunchKernelGGL((wta_split_kernel<8, 28>), grid, dim3(256), 0, st, a); return;
+        }
         switch (lpp) {
             case 1: hipLaunchKernelGGL(wta_packed_kernel<1>, grid, dim3(256), 0, st, a); break;
             case 2: hipLaunchKernelGGL(wta_packed_kernel<2>, grid, dim3(256), 0, st, a); break;

@@ -197,7 +197,8 @@ fsgm_status fsgm_epi_plan_set_penalties(fsgm_epi_plan* plan, int32_t P1, int32_t
  * fsgm_epi_plan_kernel_name() for a plan.  At 1242x375x128, 256 CUs: 8 paths -- line kernels below 4 frames, 3 below 10, 6 below 26,
  * 2 up to ~229, then 4 where a round of one workgroup per frame pays (230-256, 473-512, ...) and 5 between those rounds; 4 paths --
  * line kernels below 9 frames, then 2, then 4 / 5 likewise.  The switch points move with the frame shape by voxels^(-2/3)
- * (FSGM_EPI_SHAPE_SCALE).  Results are identical in every mode.
+ * (FSGM_EPI_SHAPE_SCALE).  Results are identical in every mode.  Modes 2-6 leave the line kernels in place where they do
+ * not apply: wrapping penalties, and every dMax other than 16, 32, 64, 128, 256 (fsgm_epi_plan_kernel_name below).
  * HBM a plan holds per frame beyond C (allocated when a mode first runs, kept until the plan is destroyed; N = W*H*D bytes):
  * mode 1: paths x N (path volumes); mode 2: 2 N + N/8 + boundary states (8 paths) / N + 2 N/8 (4 paths); modes 3, 6: one more N;
  * modes 4, 5: N + N/4 (9th-bit plane, 8 paths only) + one hand-off map of 3*W*D bytes (mode 5: one per band boundary,
@@ -246,8 +247,10 @@ void*       fsgm_epi_plan_stream(fsgm_epi_plan* plan);
  * "band16chain/nowrap" (band sweeps, the bands of a frame as workgroups of their own), "sweep16/nowrap" (8 paths, block sweep
  * pipeline), "sweep16par/nowrap" (8 paths, parallel sweeps: auto mode for 4..17 frames), "sweep16mid/nowrap" (8 paths, parallel
  * sweeps meeting in the middle), "pairs16/nowrap" (4 paths, pair
- * pipeline), "packed16/nowrap", "packed16/wrap" (per-direction line kernels), "generic" (any dMax).  New names may be added:
- * dispatch on these with a default branch. */
+ * pipeline), "packed16/nowrap", "packed16/wrap" (per-direction line kernels: dMax = 16, 32, 64, 128, 256 at 16 costs a lane,
+ * and 48, 96, 192 / 80, 160 / 112, 224 at 12 / 20 / 28 costs a lane -- these seven take the line kernels at every batch size
+ * and under every forced mode, the fused pipelines being built for 16 costs a lane), "generic" (any other dMax, 144, 176, 208
+ * and 240 included).  New names may be added: dispatch on these with a default branch. */
 const char* fsgm_epi_plan_kernel_name(fsgm_epi_plan* plan);
 /* The same answer without a plan: what auto mode takes for `batch` frames of width x height x dMax with these penalties, costs
  * up to cmax (24 for volumes built by the cost stage) and a device of `cus` compute units (MI355X: 256).  The switch points
