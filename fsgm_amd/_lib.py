@@ -88,6 +88,8 @@ def load():
     lib.fsgm_calc_cost_sgm_linear_batch_host_opts.argtypes = [i32, C.POINTER(EpiIn), C.POINTER(EpiOut), C.POINTER(EpiParams), opt]
     lib.fsgm_stereo_sgm_host_opts.argtypes = [i32, vp, vp, i32, i32, i32, i32, i32, C.POINTER(StereoParams), opt, vp, vp, vp, vp]
     lib.fsgm_epi_plan_set_adaptive_p2.argtypes = [vp, i32]
+    lib.fsgm_stereo_sgm_host_range.argtypes = [i32, vp, vp, i32, i32, i32, i32, i32, C.POINTER(StereoParams), opt, i32, vp, vp, vp, vp]
+    lib.fsgm_epi_plan_set_d_min.argtypes = [vp, i32]
     lib.fsgm_epi_auto_pipeline_opts.argtypes = [i32] * 9 + [opt]
     lib.fsgm_epi_auto_pipeline_opts.restype = C.c_char_p
     lib.fsgm_epi_plan_create_sampling.argtypes = [C.POINTER(vp), i32, i32, i32, i32, C.POINTER(EpiParams), i32, i32]

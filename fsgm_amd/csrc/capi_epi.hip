@@ -54,6 +54,7 @@ struct fsgm_epi_plan {
     // shipped), _LINEAR at d pixels along it (the reference built without USE_VZIND: the vz table holds d, the offsets 1.0),
     // _RECTIFIED a rectified pair -- Pd0 = (x + 1, y + 1), direction (direction, 0): no maps exist
     int sampling = FSGM_SAMPLING_VZ, direction = -1;
+    int d_min = 0;                       // rectified: candidate index i stands for disparity d_min + i (fsgm_epi_plan_set_d_min)
     int P1 = 6, P2 = 64;                 // epipolar_sgm_of.m:19
     double vMax = 0.3;                   // epipolar_sgm_of.m:16
     size_t NP = 0, N = 0;                // pixels, voxels per frame
@@ -661,7 +662,7 @@ static void enqueue_cost(fsgm_epi_plan* p, int f0, int nf) {
     launch_census(p->stream, p->dI2 + o * NP, p->dCen2 + o * NP, p->W, p->H, nf);
     if (p->sampling == FSGM_SAMPLING_RECTIFIED) {
         launch_stereo_cost(p->stream, p->dCen1 + o * NP, p->dCen2 + o * NP, p->dCraw + o * p->N, p->dC + o * p->N, p->W, p->H, p->D,
-                           p->direction, nf);
+                           p->direction, nf, p->d_min);
         return;
     }
     EpiCostArgs a;
@@ -942,7 +943,7 @@ static fsgm_status enqueue(fsgm_epi_plan* p, int stages) {
         b.D1 = p->dBestD; b.pd0 = p->dPd0; b.nd = p->dNd; b.off = p->dOff;
         b.D2enc = p->dD2enc; b.D2 = p->dD2; b.conf = p->dConf;
         b.vMax = p->vMax; b.W = p->W; b.H = p->H; b.n = p->D + 1; b.thr = 2;      // :483 thr = 2
-        b.linear = p->sampling != FSGM_SAMPLING_VZ; b.rect = p->direction;
+        b.linear = p->sampling != FSGM_SAMPLING_VZ; b.rect = p->direction; b.rect_shift = p->direction * p->d_min;
         launch_fb_check(p->stream, b, p->batch);
         if (p->prm.vz_to_disp) launch_vz_convert(p->stream, p->dBestD, p->dOff, p->W, p->H, p->D, p->vMax, p->batch);
     }
@@ -975,6 +976,15 @@ fsgm_status fsgm_epi_plan_set_adaptive_p2(fsgm_epi_plan* p, int32_t on) {
                     p->agg_mode);
     p->adaptive = on;
     select_kernel(p);
+    return FSGM_OK;
+}
+
+fsgm_status fsgm_epi_plan_set_d_min(fsgm_epi_plan* p, int32_t d_min) {
+    FSGM_REQUIRE(p, "null plan");
+    if (p->sampling != FSGM_SAMPLING_RECTIFIED)
+        return fail(FSGM_ERR_UNSUPPORTED, "fsgm_epi_plan_set_d_min: only a rectified plan has a disparity range to move (the caller of the others owns the maps)");
+    FSGM_REQUIRE(d_min >= -FSGM_D_MIN_LIMIT && d_min <= FSGM_D_MIN_LIMIT, "fsgm_epi_plan_set_d_min: |d_min| must be <= %d (got %d)", FSGM_D_MIN_LIMIT, d_min);
+    p->d_min = d_min;                                            // read by the next cost stage and forward-backward check
     return FSGM_OK;
 }
 
@@ -1274,18 +1284,23 @@ fsgm_status fsgm_stereo_sgm_host(int32_t n, const uint8_t* I1, const uint8_t* I2
     return fsgm_stereo_sgm_host_opts(n, I1, I2, W, H, dMax, P1, P2, prm, nullptr, disp, minC, conf, disp2);
 }
 
-fsgm_status fsgm_stereo_sgm_host_opts(int32_t n, const uint8_t* I1, const uint8_t* I2, int32_t W, int32_t H, int32_t dMax, int32_t P1,
-                                      int32_t P2, const fsgm_stereo_params* prm, const fsgm_epi_options* opt, uint32_t* disp,
-                                      uint32_t* minC, uint8_t* conf, uint32_t* disp2) {
+// The cached rectified plan is shared by every d_min (the key does not hold it): each stereo entry point sets the plan's shift
+// under the plan's lock before it queues anything, the older ones to 0.  ranged: the _range forms, whose disp / disp2 leave as
+// int32 true disparities.
+static fsgm_status stereo_host(const char* who, int32_t n, const uint8_t* I1, const uint8_t* I2, int32_t W, int32_t H, int32_t dMax,
+                               int32_t P1, int32_t P2, const fsgm_stereo_params* prm, const fsgm_epi_options* opt, int32_t d_min,
+                               bool ranged, uint32_t* disp, uint32_t* minC, uint8_t* conf, uint32_t* disp2) {
     fsgm_stereo_params sp;
     fsgm_epi_params pr;
     fsgm_epi_options o;
-    fsgm_status st = stereo_args("fsgm_stereo_sgm_host", n, I1, I2, W, H, dMax, prm, disp, minC, &sp, &pr);
+    fsgm_status st = stereo_args(who, n, I1, I2, W, H, dMax, prm, disp, minC, &sp, &pr);
     if (st != FSGM_OK) return st;
-    if ((st = read_options("fsgm_stereo_sgm_host", opt, &o)) != FSGM_OK) return st;
+    if ((st = read_options(who, opt, &o)) != FSGM_OK) return st;
+    FSGM_REQUIRE(d_min >= -FSGM_D_MIN_LIMIT && d_min <= FSGM_D_MIN_LIMIT, "%s: |d_min| must be <= %d (got %d)", who, FSGM_D_MIN_LIMIT, d_min);
     std::unique_lock<std::mutex> lk;
     fsgm_epi_plan* p = nullptr;
     if ((st = cached_plan(lk, &p, W, H, dMax, n, pr, FSGM_SAMPLING_RECTIFIED, sp.direction, o.adaptive_p2)) != FSGM_OK) return st;
+    p->d_min = d_min;
     if ((st = fsgm_epi_plan_set_penalties(p, P1, P2, p->vMax)) != FSGM_OK) return st;
     if ((st = ensure_cost_buffers(p)) != FSGM_OK) return st;
     p->have_img.assign(n, 1);                                    // the pairs go up below, ahead of the kernels
@@ -1294,6 +1309,10 @@ fsgm_status fsgm_stereo_sgm_host_opts(int32_t n, const uint8_t* I1, const uint8_
     FSGM_HIP(hipMemcpyAsync(p->dI1, I1, np, hipMemcpyHostToDevice, p->stream));
     FSGM_HIP(hipMemcpyAsync(p->dI2, I2, np, hipMemcpyHostToDevice, p->stream));
     if ((st = enqueue(p, FSGM_STAGE_ALL)) != FSGM_OK) return st;
+    if (ranged) {
+        launch_stereo_range(p->stream, p->dBestD, pr.fb_check ? p->dD2 : nullptr, np, d_min);
+        FSGM_HIP(hipGetLastError());
+    }
     FSGM_HIP(hipMemcpyAsync(disp, p->dBestD, np * 4, hipMemcpyDeviceToHost, p->stream));
     FSGM_HIP(hipMemcpyAsync(minC, p->dMinC, np * 4, hipMemcpyDeviceToHost, p->stream));
     if (pr.fb_check && conf) FSGM_HIP(hipMemcpyAsync(conf, p->dConf, np, hipMemcpyDeviceToHost, p->stream));
@@ -1301,6 +1320,19 @@ fsgm_status fsgm_stereo_sgm_host_opts(int32_t n, const uint8_t* I1, const uint8_
     FSGM_HIP(hipStreamSynchronize(p->stream));
     guard.dismiss();
     return check_handoff(p);
+}
+
+fsgm_status fsgm_stereo_sgm_host_opts(int32_t n, const uint8_t* I1, const uint8_t* I2, int32_t W, int32_t H, int32_t dMax, int32_t P1,
+                                      int32_t P2, const fsgm_stereo_params* prm, const fsgm_epi_options* opt, uint32_t* disp,
+                                      uint32_t* minC, uint8_t* conf, uint32_t* disp2) {
+    return stereo_host("fsgm_stereo_sgm_host", n, I1, I2, W, H, dMax, P1, P2, prm, opt, 0, false, disp, minC, conf, disp2);
+}
+
+fsgm_status fsgm_stereo_sgm_host_range(int32_t n, const uint8_t* I1, const uint8_t* I2, int32_t W, int32_t H, int32_t dMax, int32_t P1,
+                                       int32_t P2, const fsgm_stereo_params* prm, const fsgm_epi_options* opt, int32_t d_min,
+                                       int32_t* disp, uint32_t* minC, uint8_t* conf, int32_t* disp2) {
+    return stereo_host("fsgm_stereo_sgm_host_range", n, I1, I2, W, H, dMax, P1, P2, prm, opt, d_min, true, (uint32_t*)disp, minC, conf,
+                       (uint32_t*)disp2);
 }
 
 // sgm(C, P1, P2): sgm.m's call shape on the MEX's aggregation + WTA (MEX semantics: include/fsgm.h)
@@ -1509,16 +1541,18 @@ fsgm_status fsgm_stereo_sgm_device(int32_t n, const uint8_t* I1, const uint8_t* 
     return fsgm_stereo_sgm_device_opts(n, I1, I2, W, H, dMax, P1, P2, prm, nullptr, disp, minC, conf, disp2, stream, status);
 }
 
-fsgm_status fsgm_stereo_sgm_device_opts(int32_t n, const uint8_t* I1, const uint8_t* I2, int32_t W, int32_t H, int32_t dMax, int32_t P1,
-                                        int32_t P2, const fsgm_stereo_params* prm, const fsgm_epi_options* opt, uint32_t* disp,
-                                        uint32_t* minC, uint8_t* conf, uint32_t* disp2, void* stream, int32_t* status) {
-    const char* who = "fsgm_stereo_sgm_device";
+// (the shift and the cached plan: as stereo_host)
+static fsgm_status stereo_device(const char* who, int32_t n, const uint8_t* I1, const uint8_t* I2, int32_t W, int32_t H, int32_t dMax,
+                                 int32_t P1, int32_t P2, const fsgm_stereo_params* prm, const fsgm_epi_options* opt, int32_t d_min,
+                                 bool ranged, uint32_t* disp, uint32_t* minC, uint8_t* conf, uint32_t* disp2, void* stream,
+                                 int32_t* status) {
     fsgm_stereo_params sp;
     fsgm_epi_params pr;
     fsgm_epi_options o;
     fsgm_status st = stereo_args(who, n, I1, I2, W, H, dMax, prm, disp, minC, &sp, &pr);
     if (st != FSGM_OK) return st;
     if ((st = read_options(who, opt, &o)) != FSGM_OK) return st;
+    FSGM_REQUIRE(d_min >= -FSGM_D_MIN_LIMIT && d_min <= FSGM_D_MIN_LIMIT, "%s: |d_min| must be <= %d (got %d)", who, FSGM_D_MIN_LIMIT, d_min);
     // checks first, also on a shape's first call: nothing is allocated for a captured stream or a pointer that is refused
     const int dev = pr.device;
     const size_t np = (size_t)n * (size_t)W * (size_t)H;
@@ -1537,14 +1571,29 @@ fsgm_status fsgm_stereo_sgm_device_opts(int32_t n, const uint8_t* I1, const uint
     std::unique_lock<std::mutex> lk;
     fsgm_epi_plan* p = nullptr;
     if ((st = cached_plan(lk, &p, W, H, dMax, n, pr, FSGM_SAMPLING_RECTIFIED, sp.direction, o.adaptive_p2)) != FSGM_OK) return st;
+    p->d_min = d_min;
     if ((st = epi_device_enter(p, P1, P2, p->vMax, cs)) != FSGM_OK) return st;
     {
         Bind<uint8_t> i1(p->dI1, const_cast<uint8_t*>(I1)), i2(p->dI2, const_cast<uint8_t*>(I2));
         Bind<uint32_t> bd(p->dBestD, disp), mc(p->dMinC, minC), d2(p->dD2, fb ? disp2 : nullptr);
         Bind<uint8_t> cf(p->dConf, fb ? conf : nullptr);
         st = enqueue(p, FSGM_STAGE_ALL);
+        if (st == FSGM_OK && ranged) launch_stereo_range(p->stream, disp, fb ? disp2 : nullptr, np, d_min);
     }
     return epi_device_finish(p, cs, status, st);
+}
+
+fsgm_status fsgm_stereo_sgm_device_opts(int32_t n, const uint8_t* I1, const uint8_t* I2, int32_t W, int32_t H, int32_t dMax, int32_t P1,
+                                        int32_t P2, const fsgm_stereo_params* prm, const fsgm_epi_options* opt, uint32_t* disp,
+                                        uint32_t* minC, uint8_t* conf, uint32_t* disp2, void* stream, int32_t* status) {
+    return stereo_device("fsgm_stereo_sgm_device", n, I1, I2, W, H, dMax, P1, P2, prm, opt, 0, false, disp, minC, conf, disp2, stream, status);
+}
+
+fsgm_status fsgm_stereo_sgm_device_range(int32_t n, const uint8_t* I1, const uint8_t* I2, int32_t W, int32_t H, int32_t dMax, int32_t P1,
+                                         int32_t P2, const fsgm_stereo_params* prm, const fsgm_epi_options* opt, int32_t d_min,
+                                         int32_t* disp, uint32_t* minC, uint8_t* conf, int32_t* disp2, void* stream, int32_t* status) {
+    return stereo_device("fsgm_stereo_sgm_device_range", n, I1, I2, W, H, dMax, P1, P2, prm, opt, d_min, true, (uint32_t*)disp, minC, conf,
+                         (uint32_t*)disp2, stream, status);
 }
 
 // ---------------------------------------------------------------------------------------------

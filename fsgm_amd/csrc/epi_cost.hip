@@ -70,9 +70,11 @@ struct CbPix {
     uint32_t c1;
 };
 
-// a.pd0 / nd / off / vz unused when RECT; rect_dir: -1 / +1 (RECT only)
+// a.pd0 / nd / off / vz unused when RECT; rect_dir: -1 / +1, rect_shift: rect_dir * d_min, the columns the window's content lies
+// off its place (both RECT only)
 template <int NW, bool RECT>
-__global__ __launch_bounds__(NW * 64, 4) void epi_costbox_kernel(EpiCostArgs a, uint8_t* __restrict__ Cout, int seg_rows, uint32_t total_items, int rect_dir) {
+__global__ __launch_bounds__(NW * 64, 4) void epi_costbox_kernel(EpiCostArgs a, uint8_t* __restrict__ Cout, int seg_rows, uint32_t total_items, int rect_dir,
+                                                                 int rect_shift) {
     __shared__ __attribute__((aligned(16))) uint4 xch[NW][68];              // a wave's raw row: slots 2 .. 65, two spare either side
     __shared__ __attribute__((aligned(16))) uint4 outt[2][64][NW + 1];      // a row of C, [pixel][16-byte piece], one piece of padding
     constexpr int REACH = 64 + 16 * NW - 1;                                  // RECT: census words a strip's samples of one row span
@@ -257,8 +259,11 @@ __global__ __launch_bounds__(NW * 64, 4) void epi_costbox_kernel(EpiCostArgs a, 
     };
 
     // ---- RECT: the window of image 2's census row.  xb: the image column of window word 0; the lane's pixel px (its raw
-    // column, clamped) samples words (px - xb) + dir * d, all inside [0, REACH): see the launcher's comment ----
+    // column, clamped) samples words (px - xb) + dir * d, all inside [0, REACH): see the launcher's comment.  A search range that
+    // starts at d_min moves what the words HOLD, never which word a lane reads: word i is image column xb + rect_shift + i,
+    // clamped at either image edge by the fill (xc: that column of word 0; |rect_shift| <= 1024, the sum stays far inside int) ----
     const int xb = rect_dir < 0 ? xs - 2 - (16 * NW - 1) : xs - 2;
+    const int xc = xb + rect_shift;
     const int s0w = rect_dir < 0 ? px - xb - d0 - 15 : px - xb + d0;         // the lowest of the lane's 16 window words
     const int wc = s0w & 3, wq = s0w >> 2;                                   // its copy and 16-byte slot there
     uint32_t pre[NPRE];
@@ -267,7 +272,7 @@ __global__ __launch_bounds__(NW * 64, 4) void epi_costbox_kernel(EpiCostArgs a, 
 #pragma unroll
         for (int n = 0; n < NPRE; n++) {
             const int i = (int)threadIdx.x + n * NW * 64;
-            pre[n] = i < REACH ? row[clampi(xb + i, 0, xhi)] : 0u;
+            pre[n] = i < REACH ? row[clampi(xc + i, 0, xhi)] : 0u;
         }
     };
     auto fill_rect = [&](const int st, uint32_t (&pslot)[8]) {
@@ -361,7 +366,7 @@ int costbox_seg_rows(int W, int H, int D, int frames, int cus) {
     return best_rows;
 }
 
-static void launch_costbox(hipStream_t st, const EpiCostArgs& a, uint8_t* C, int frames, int rect_dir) {
+static void launch_costbox(hipStream_t st, const EpiCostArgs& a, uint8_t* C, int frames, int rect_dir, int rect_shift = 0) {
     static const int cus = [] {
         int dev = 0, n = 0;
         if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
@@ -372,13 +377,13 @@ static void launch_costbox(hipStream_t st, const EpiCostArgs& a, uint8_t* C, int
     dim3 grid(8u * ((total + 7u) / 8u));
     if (rect_dir == 0) {
         switch (a.D >> 4) {
-#define FSGM_CB(NW) case NW: hipLaunchKernelGGL((epi_costbox_kernel<NW, false>), grid, dim3(NW * 64), 0, st, a, C, seg, total, 0); break;
+#define FSGM_CB(NW) case NW: hipLaunchKernelGGL((epi_costbox_kernel<NW, false>), grid, dim3(NW * 64), 0, st, a, C, seg, total, 0, 0); break;
             FSGM_CB(1) FSGM_CB(2) FSGM_CB(4) FSGM_CB(8) FSGM_CB(16)
 #undef FSGM_CB
         }
     } else {
         switch (a.D >> 4) {
-#define FSGM_CB(NW) case NW: hipLaunchKernelGGL((epi_costbox_kernel<NW, true>), grid, dim3(NW * 64), 0, st, a, C, seg, total, rect_dir); break;
+#define FSGM_CB(NW) case NW: hipLaunchKernelGGL((epi_costbox_kernel<NW, true>), grid, dim3(NW * 64), 0, st, a, C, seg, total, rect_dir, rect_shift); break;
             FSGM_CB(1) FSGM_CB(2) FSGM_CB(4) FSGM_CB(8) FSGM_CB(16)
 #undef FSGM_CB
         }
@@ -387,16 +392,17 @@ static void launch_costbox(hipStream_t st, const EpiCostArgs& a, uint8_t* C, int
 
 void launch_epi_costbox(hipStream_t st, const EpiCostArgs& a, uint8_t* C, int frames) { launch_costbox(st, a, C, frames, 0); }
 
-// Rectified pair, any dMax: raw costs of one (pixel, d) per thread into the raw volume for the box kernels
+// Rectified pair, any dMax: raw costs of one (pixel, d) per thread into the raw volume for the box kernels; index d stands for
+// disparity d_min + d
 __global__ __launch_bounds__(256) void stereo_rawcost_kernel(const uint32_t* __restrict__ cen1, const uint32_t* __restrict__ cen2,
-                                                             uint8_t* __restrict__ Craw, int W, int H, int D, int dir) {
+                                                             uint8_t* __restrict__ Craw, int W, int H, int D, int dir, int d_min) {
     const size_t NP = (size_t)W * H;
     const size_t gid = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (gid >= NP * D) return;
     const uint32_t p = (uint32_t)(gid / D), d = (uint32_t)(gid - (size_t)p * D);
     const int y = (int)(p / (uint32_t)W), x = (int)(p - (uint32_t)y * (uint32_t)W);
     const size_t fo = (size_t)blockIdx.y * NP;
-    const int x2 = clampi(x + dir * (int)d, 0, W - 1);                       // :368-375 with Pd0 = (x + 1, y + 1), u = (dir, 0)
+    const int x2 = clampi(x + dir * (d_min + (int)d), 0, W - 1);             // :368-375 with Pd0 = (x + 1 + dir * d_min, y + 1), u = (dir, 0)
     Craw[fo * D + gid] = (uint8_t)__popc(cen1[fo + p] ^ cen2[fo + (size_t)y * W + x2]);   // :377-378
 }
 
@@ -407,20 +413,48 @@ __global__ __launch_bounds__(256) void stereo_rawcost_kernel(const uint32_t* __r
 // reach words 0 and 1).  Copy c of the window holds every word from c upwards at index word - c, and a lane reads copy s & 3
 // from s - (s & 3) >= 0 on, 16 words up to s + 15 <= REACH - 1: all written.  The window itself is filled with the clamp on the
 // image columns, so a word's content is cen2[y][clamp(px + dir * d)].
+//
+// A search range that starts at d_min (index d = disparity d_min + d): the sample is cen2[y][clamp(px + dir * (d_min + d))], the
+// sample of the unshifted range dir * d_min columns further on.  The kernel keeps xb, the word index (px - xb) + dir * d and so
+// every bound above -- none of them mentions what a word holds -- and fills word i with cen2[y][clamp(xb + dir * d_min + i)]
+// instead of cen2[y][clamp(xb + i)]: the word the lane reads then holds cen2[y][clamp(xb + dir * d_min + (px - xb) + dir * d)] =
+// cen2[y][clamp(px + dir * (d_min + d))].  That is why the four-copy layout, PITCH, the copies' alignment and the [0, REACH)
+// word bounds are untouched: they are properties of word INDICES, which depend on lane, strip, dir and d alone.  What does
+// change is the fill's address, xb + dir * d_min + i with i < REACH: it can now leave the image on EITHER side (dir = -1 with a
+// negative d_min runs off the right edge, as dir = +1 always could; |d_min| > W + REACH puts every word at one clamped column),
+// so the fill clamps to [0, W - 1] on both sides -- one clampi, as before -- and reads row[0 .. W - 1] only.  |dir * d_min| <=
+// 1024 (the entry points refuse more) and |xb + i| < 2^22 + 2^9, so the sum cannot wrap.
 void launch_stereo_cost(hipStream_t st, const uint32_t* cen1, const uint32_t* cen2, uint8_t* Craw, uint8_t* C, int W, int H, int D,
-                        int direction, int frames) {
+                        int direction, int frames, int d_min) {
     const int dir = direction < 0 ? -1 : 1;
     // FSGM_COST_FUSED=0: the two-kernel form, as for launch_epi_cost
     const bool fused = [] { const char* e = getenv("FSGM_COST_FUSED"); return !(e && e[0] == '0'); }();
     if (fused && costbox_ok(W, H, D)) {
         EpiCostArgs a{};
         a.cen1 = cen1; a.cen2 = cen2; a.W = W; a.H = H; a.D = D;
-        launch_costbox(st, a, C, frames, dir);
+        launch_costbox(st, a, C, frames, dir, dir * d_min);
         return;
     }
     const size_t n = (size_t)W * H * D;                                      // < 2^31 (plan creation)
-    hipLaunchKernelGGL(stereo_rawcost_kernel, dim3((unsigned)((n + 255) / 256), frames), dim3(256), 0, st, cen1, cen2, Craw, W, H, D, dir);
+    hipLaunchKernelGGL(stereo_rawcost_kernel, dim3((unsigned)((n + 255) / 256), frames), dim3(256), 0, st, cen1, cen2, Craw, W, H, D, dir, d_min);
     launch_box5x5(st, Craw, C, W, H, D, frames);
+}
+
+// The outputs of a search range that starts at d_min as true disparities: candidate index * 256 (+ the parabola's offset) becomes
+// the int32 256 * d_min + value, and the second view's invalid marker 512 << 8 -- a valid value once d_min > 0 -- INT32_MIN.
+// In place, one thread per pixel of the whole batch; disp2 null without the forward-backward check.
+__global__ __launch_bounds__(256) void stereo_range_kernel(uint32_t* __restrict__ disp, uint32_t* __restrict__ disp2, size_t n, int base) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    disp[i] = (uint32_t)(base + (int)disp[i]);
+    if (disp2) {
+        const uint32_t v = disp2[i];
+        disp2[i] = v == (512u << 8) ? 0x80000000u : (uint32_t)(base + (int)v);
+    }
+}
+
+void launch_stereo_range(hipStream_t st, uint32_t* disp, uint32_t* disp2, size_t n, int d_min) {
+    hipLaunchKernelGGL(stereo_range_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, disp, disp2, n, 256 * d_min);
 }
 
 }  // namespace fsgm

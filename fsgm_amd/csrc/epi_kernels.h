@@ -135,6 +135,7 @@ struct FbArgs {                // forward-backward check (calc_cost_sgm.cpp:429-
     int W, H, n, thr;
     int linear = 0;           // the reference built without USE_VZIND: the displacement along the direction is D1 / 256 itself (:453, :508)
     int rect = 0;             // +-1: rectified pair -- Pd0 = (x + 1, y + 1), direction (rect, 0) computed in the kernel, pd0 / nd / off not read
+    int rect_shift = 0;       // rect * d_min of a search range that starts at d_min: Pd0 = (x + 1 + rect_shift, y + 1)
 };
 
 enum { AGG_PACKED_NOWRAP = 0, AGG_PACKED_WRAP = 1, AGG_GENERIC = 2, AGG_SWEEP = 3, AGG_PAIRS = 4, AGG_BAND = 5 };
@@ -149,9 +150,12 @@ void launch_epi_cost(hipStream_t st, const EpiCostArgs& a, uint8_t* C, int frame
 bool costbox_ok(int W, int H, int D);
 void launch_epi_costbox(hipStream_t st, const EpiCostArgs& a, uint8_t* C, int frames);
 // the cost stage of a rectified pair (epi_cost.hip): sample cen2[y][clamp(x + direction * d)], direction = -1 / +1; D = 16 << k
-// as one kernel, any other D as a raw-cost kernel into Craw and the box kernels
+// as one kernel, any other D as a raw-cost kernel into Craw and the box kernels.  d_min (|d_min| <= 1024): index d stands for
+// disparity d_min + d, the sample is cen2[y][clamp(x + direction * (d_min + d))]
 void launch_stereo_cost(hipStream_t st, const uint32_t* cen1, const uint32_t* cen2, uint8_t* Craw, uint8_t* C, int W, int H, int D,
-                        int direction, int frames);
+                        int direction, int frames, int d_min = 0);
+// disp (and disp2 unless null) of n pixels in place as int32 true disparities: 256 * d_min + value, disp2's 512 << 8 -> INT32_MIN
+void launch_stereo_range(hipStream_t st, uint32_t* disp, uint32_t* disp2, size_t n, int d_min);
 void launch_box5x5(hipStream_t st, const uint8_t* Craw, uint8_t* C, int W, int H, int D, int frames);
 int  costbox_selftest(hipStream_t st);      // 0: the mean's fp16 multiply is exact on this device; > 0: mismatches; < 0: could not run
 void launch_aggregate(hipStream_t st, AggArgs a, int paths, int frames, int kernel_kind);

@@ -1241,14 +1241,14 @@ __device__ __forceinline__ double fb_displacement(const FbArgs& a, size_t f, int
 }
 
 // start position - 1 (:456-457 / :510-511) and direction (:459-460 / :513-514) of pixel p: read from the maps, or those of a
-// rectified pair -- Pd0 = (x + 1, y + 1), direction (+-1, 0) -- through the same fp64 operations
+// rectified pair -- Pd0 = (x + 1 + rect_shift, y + 1), direction (+-1, 0) -- through the same fp64 operations
 struct FbRay { double bx, by, ux, uy; };
 __device__ __forceinline__ FbRay fb_ray(const FbArgs& a, size_t f, int p) {
     const int NP = a.W * a.H;
     FbRay r;
     if (a.rect) {
         const int y = p / a.W, x = p - y * a.W;
-        r.bx = __dsub_rn((double)(x + 1), 1.0); r.by = __dsub_rn((double)(y + 1), 1.0);
+        r.bx = __dsub_rn((double)(x + 1 + a.rect_shift), 1.0); r.by = __dsub_rn((double)(y + 1), 1.0);
         r.ux = (double)a.rect; r.uy = 0.0;
     } else {
         const double* p0 = a.pd0 + f * 2 * (size_t)NP;

@@ -166,13 +166,36 @@ def _stereo_params(paths, subpixel, direction, fb_check, device):
     return p
 
 
-def stereo_sgm(left, right, dMax, P1=6, P2=64, *, paths=4, subpixel=1, direction=-1, fb_check=0, device=0, adaptive_p2=0):
+D_MIN_LIMIT = 1024                                             # FSGM_D_MIN_LIMIT
+
+
+def _d_min(d_min):
+    """d_min of the stereo wrappers as an int (None stays None), checked as the library checks it"""
+    if d_min is None:
+        return None
+    try:
+        whole = not isinstance(d_min, bool) and int(d_min) == d_min
+    except (TypeError, ValueError):
+        whole = False
+    if not whole:
+        raise TypeError(f"d_min must be an integer or None (got {d_min!r})")
+    if abs(int(d_min)) > D_MIN_LIMIT:
+        raise ValueError(f"|d_min| must be <= {D_MIN_LIMIT} (got {d_min!r})")
+    return int(d_min)
+
+
+def stereo_sgm(left, right, dMax, P1=6, P2=64, *, paths=4, subpixel=1, direction=-1, fb_check=0, device=0, adaptive_p2=0, d_min=None):
     """disp, minC = stereo_sgm(left, right, dMax): semi-global matching of a rectified pair.  left, right (height, width) uint8
     or a batch (N, height, width); disp uint32 = disparity * 256 (whole disparities with subpixel=0), minC uint32, of the
     images' shape.  direction=-1: `left` is the left view and its match in `right` lies at x - d; +1: at x + d.  fb_check=1
     also returns (conf, disp2): the reference's forward-backward check (threshold 2 on the * 256 values; dMax <= 511).
     adaptive_p2=1: edge-aware large penalty -- a path step across an intensity edge of `left` (a difference above 25 between
-    the pixel and its predecessor on the path) pays P2 / 8 instead of P2 (calc_cost_sgm.cpp:68-72)."""
+    the pixel and its predecessor on the path) pays P2 / 8 instead of P2 (calc_cost_sgm.cpp:68-72).
+    d_min: an integer (|d_min| <= 1024, may be negative) starts the search range there -- the dMax candidates are the disparities
+    d_min .. d_min + dMax - 1, sampled at clamp(x + direction * d) -- and disp / disp2 come back as int32 TRUE disparities * 256
+    (disp2: INT32_MIN where invalid).  The dtype follows the argument, not its value: d_min=0 gives int32 arrays with the values
+    of d_min=None, which takes the path and the uint32 outputs (disp2: 512 << 8 where invalid) this function always had."""
+    d_min = _d_min(d_min)
     left, right = np.asarray(left), np.asarray(right)
     if left.dtype != np.uint8 or right.dtype != np.uint8 or left.ndim not in (2, 3):
         raise TypeError(f"left / right must be uint8 arrays (height, width) or (N, height, width) (got {left.dtype} {left.shape})")
@@ -187,10 +210,15 @@ def stereo_sgm(left, right, dMax, P1=6, P2=64, *, paths=4, subpixel=1, direction
     n = 1 if left.ndim == 2 else left.shape[0]
     if n == 0:
         raise ValueError("empty batch")
-    disp, minC = np.zeros(left.shape, np.uint32), np.zeros(left.shape, np.uint32)
+    dtype = np.uint32 if d_min is None else np.int32
+    disp, minC = np.zeros(left.shape, dtype), np.zeros(left.shape, np.uint32)
     conf = np.zeros(left.shape, np.uint8) if fb_check else None
-    disp2 = np.zeros(left.shape, np.uint32) if fb_check else None
-    if adaptive_p2:
+    disp2 = np.zeros(left.shape, dtype) if fb_check else None
+    if d_min is not None:
+        opt = _lib.options(adaptive_p2)
+        check(lib.fsgm_stereo_sgm_host_range(n, ptr(left), ptr(right), W, H, int(dMax), int(P1), int(P2), C.byref(prm), C.byref(opt),
+                                             d_min, ptr(disp), ptr(minC), ptr(conf), ptr(disp2)))
+    elif adaptive_p2:
         opt = _lib.options(adaptive_p2)
         check(lib.fsgm_stereo_sgm_host_opts(n, ptr(left), ptr(right), W, H, int(dMax), int(P1), int(P2), C.byref(prm), C.byref(opt),
                                             ptr(disp), ptr(minC), ptr(conf), ptr(disp2)))
@@ -255,6 +283,7 @@ class EpiPlan:
             check(self.lib.fsgm_epi_plan_create_sampling(C.byref(self._h), self.W, self.H, self.D, self.batch, C.byref(prm),
                                                          self.sampling, int(direction)))
         self.adaptive_p2 = 0
+        self.d_min = 0
         if adaptive_p2:
             try:
                 self.set_adaptive_p2(adaptive_p2)
@@ -296,6 +325,13 @@ class EpiPlan:
         I1 of every slot (upload / upload_images), also when the costs came from upload_cost."""
         check(self.lib.fsgm_epi_plan_set_adaptive_p2(self._h, int(on)))
         self.adaptive_p2 = int(on)
+
+    def set_d_min(self, d_min):
+        """A rectified plan's search range starts at disparity d_min (|d_min| <= 1024; 0 at creation): candidate i is sampled at
+        clamp(x + direction * (d_min + i)).  download() / download_fb() keep returning candidate indices * 256; any other plan
+        refuses (status 4)."""
+        check(self.lib.fsgm_epi_plan_set_d_min(self._h, int(d_min)))
+        self.d_min = int(d_min)
 
     def upload(self, frame, I1, I2, pd0, nd, off):
         I1, I2 = _u8img(I1, "I1"), _u8img(I2, "I2")

@@ -7,7 +7,7 @@ points of include/fsgm.h ("Device-pointer entry points") as torch custom ops and
 
 No host<->device copy and no host wait once a plan for the shape exists: the work is queued behind what the current stream
 already holds, and what is queued on that stream afterwards runs after it.  Ops registered: fsgm::calc_cost_sgm,
-fsgm::calc_cost_sgm_linear, fsgm::stereo_sgm,
+fsgm::calc_cost_sgm_linear, fsgm::stereo_sgm, fsgm::stereo_sgm_range,
 fsgm::epipolar_sgm_of, fsgm::pyramidal_sgm, fsgm::pyramidal_sgm_ng, fsgm::epipolar_flow_pp, fsgm::pyramidal_flow_pp (each also returns a 0-d int32
 status tensor: 0, or FSGM_ERR_HIP when an aggregation hand-off gave up; check=True in the wrappers synchronises and raises
 on it), fsgm::epi_postprocess (status FSGM_ERR_INVALID when a D1 value is negative), fsgm::vmf and fsgm::flow_fb_check.
@@ -25,7 +25,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import EpiIn, EpiOut, EpiOptions, EpiParams, FsgmError, StereoParams
-from .epi import EpiGeometry, _params as _epi_params, _stereo_params
+from .epi import EpiGeometry, _d_min, _params as _epi_params, _stereo_params
 from .post import _bind as _bind_post
 from .pyramid import PyramidParams, NgPyramidParams, FLOW_PP_FIELDS, MATCHERS, _bind as _bind_pyramid, _bind_flow_pp, _bind_ng
 
@@ -65,6 +65,8 @@ _L.fsgm_calc_cost_sgm_device_opts.argtypes = [_i32, C.POINTER(EpiIn), C.POINTER(
 _L.fsgm_calc_cost_sgm_linear_device_opts.argtypes = [_i32, C.POINTER(EpiIn), C.POINTER(EpiOut), C.POINTER(EpiParams), _opt, _vp, _vp]
 _L.fsgm_stereo_sgm_device_opts.argtypes = [_i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, C.POINTER(StereoParams), _opt, _vp, _vp, _vp, _vp,
                                            _vp, _vp]
+_L.fsgm_stereo_sgm_device_range.argtypes = [_i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, C.POINTER(StereoParams), _opt, _i32, _vp, _vp, _vp,
+                                            _vp, _vp, _vp]
 _L.fsgm_epi_plan_run_device.argtypes = [_vp, _i32, C.POINTER(EpiIn), C.POINTER(EpiOut), _vp, _vp]
 _L.fsgm_epipolar_sgm_of_device.argtypes = [_i32, _vp, _vp, _i32, _i32, _i32, C.POINTER(EpiGeometry), _i32, C.c_double,
                                            C.POINTER(EpiParams), _vp, _vp, _vp, _vp]
@@ -211,6 +213,35 @@ def _(left, right, dMax, P1, P2, paths, subpixel, direction, fb_check, adaptive_
     N, H, W = left.shape
     dev = left.device
     return (_u32((N, H, W), dev), _u32((N, H, W), dev)) + _fb_outputs(N, H, W, fb_check, dev) + (_status(dev),)
+
+
+def _fb_outputs_i32(N, H, W, fb_check, dev):
+    return (torch.empty((N, H, W) if fb_check else (0,), dtype=torch.uint8, device=dev),
+            torch.empty((N, H, W) if fb_check else (0,), dtype=torch.int32, device=dev))
+
+
+@torch.library.custom_op("fsgm::stereo_sgm_range", mutates_args=())
+def _stereo_sgm_range_op(left: torch.Tensor, right: torch.Tensor, dMax: int, d_min: int, P1: int, P2: int, paths: int, subpixel: int,
+                         direction: int, fb_check: int,
+                         adaptive_p2: int = 0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    N, H, W = left.shape
+    dev = left.device
+    left, right = _ready(left), _ready(right)
+    disp, minC, status = torch.empty((N, H, W), dtype=torch.int32, device=dev), _u32((N, H, W), dev), _status(dev)
+    conf, disp2 = _fb_outputs_i32(N, H, W, fb_check, dev)
+    prm = _stereo_params(paths, subpixel, direction, fb_check, dev.index)
+    opt = _lib.options(adaptive_p2)
+    _call(dev, _L.fsgm_stereo_sgm_device_range, N, _p(left), _p(right), W, H, int(dMax), int(P1), int(P2), C.byref(prm), C.byref(opt),
+          int(d_min), _p(disp), _p(minC), _p(conf) if fb_check else None, _p(disp2) if fb_check else None, _stream(dev), _p(status))
+    return disp, minC, conf, disp2, status
+
+
+@_stereo_sgm_range_op.register_fake
+def _(left, right, dMax, d_min, P1, P2, paths, subpixel, direction, fb_check, adaptive_p2=0):
+    N, H, W = left.shape
+    dev = left.device
+    return ((torch.empty((N, H, W), dtype=torch.int32, device=dev), _u32((N, H, W), dev)) + _fb_outputs_i32(N, H, W, fb_check, dev)
+            + (_status(dev),))
 
 
 @torch.library.custom_op("fsgm::epipolar_sgm_of", mutates_args=())
@@ -470,10 +501,14 @@ def calc_cost_sgm_linear(I1, I2, dMax, pixelPosD0, normlizeDirection, P1, P2, *,
 
 
 def stereo_sgm(left, right, dMax, P1=6, P2=64, *, paths=4, subpixel=1, direction=-1, fb_check=0, check=False, return_status=False,
-               adaptive_p2=0):
+               adaptive_p2=0, d_min=None):
     """disp, minC = stereo_sgm(left, right, dMax) as fsgm_amd.stereo_sgm, on torch tensors on the GPU: left, right (H, W) uint8
     or a batch (N, H, W); disp (disparity * 256) and minC uint32 of the same shape, plus conf uint8 / disp2 uint32 with
-    fb_check=1.  The outputs stay in HBM; the work is queued on the current stream.  adaptive_p2=1: edge-aware P2 on `left`."""
+    fb_check=1.  The outputs stay in HBM; the work is queued on the current stream.  adaptive_p2=1: edge-aware P2 on `left`.
+    d_min: an integer starts the search range at that disparity (fsgm::stereo_sgm_range) and makes disp / disp2 int32 true
+    disparities * 256 (disp2 INT32_MIN where invalid); the dtype follows the argument, not its value: None (fsgm::stereo_sgm)
+    keeps the uint32 outputs, 0 gives the same values as int32."""
+    d_min = _d_min(d_min)
     _tensors({"left": (left, torch.uint8), "right": (right, torch.uint8)})
     if left.dim() not in (2, 3):
         raise TypeError(f"left must be (H, W) or (N, H, W) (got {tuple(left.shape)})")
@@ -486,8 +521,13 @@ def stereo_sgm(left, right, dMax, P1=6, P2=64, *, paths=4, subpixel=1, direction
     batched = left.dim() == 3
     if not batched:
         left, right = left.unsqueeze(0), right.unsqueeze(0)
-    disp, minC, conf, disp2, status = torch.ops.fsgm.stereo_sgm(left, right, int(dMax), int(P1), int(P2), int(paths), int(subpixel),
-                                                                 int(direction), int(bool(fb_check)), int(adaptive_p2))
+    if d_min is None:
+        disp, minC, conf, disp2, status = torch.ops.fsgm.stereo_sgm(left, right, int(dMax), int(P1), int(P2), int(paths), int(subpixel),
+                                                                     int(direction), int(bool(fb_check)), int(adaptive_p2))
+    else:
+        disp, minC, conf, disp2, status = torch.ops.fsgm.stereo_sgm_range(left, right, int(dMax), d_min, int(P1), int(P2), int(paths),
+                                                                           int(subpixel), int(direction), int(bool(fb_check)),
+                                                                           int(adaptive_p2))
     outs = (disp, minC, conf, disp2) if fb_check else (disp, minC)
     return _finish(outs, status, batched, check, return_status)
 

@@ -162,6 +162,24 @@ fsgm_status fsgm_stereo_sgm_host_opts(int32_t n_frames, const uint8_t* I1, const
                                       int32_t dMax, int32_t P1, int32_t P2, const fsgm_stereo_params* prm,
                                       const fsgm_epi_options* opt, uint32_t* disp, uint32_t* minC, uint8_t* conf, uint32_t* disp2);
 
+/* A search range that starts at d_min instead of 0: candidate index i in [0, dMax) stands for disparity d_min + i, sampled at
+ * cen2[y][clamp(x + direction * (d_min + i), 0, W - 1)] -- the linear matcher on Pd0 = (x + 1 + direction * d_min, y + 1),
+ * direction (direction, 0), which is also what the forward-backward check works on.  d_min may be negative (converged or
+ * shifted principal points); |d_min| <= FSGM_D_MIN_LIMIT, anything else is FSGM_ERR_INVALID before a device is touched.
+ * Arguments as fsgm_stereo_sgm_host_opts plus d_min; the outputs that carry disparities are int32 TRUE disparities * 256:
+ *   disp  = 256 * d_min + (index * 256 + parabola offset)
+ *   disp2 = the same for the second view, INT32_MIN where invalid (512 << 8, the marker of the entry points above, is a valid
+ *           value once d_min > 0)
+ * minC and conf are as above.  d_min = 0 gives the values of fsgm_stereo_sgm_host_opts read as int32, with INT32_MIN for
+ * disp2's marker.  Aggregation, WTA and pipeline selection are those of the same dMax without d_min.
+ * The cached plan is shared by every d_min of a shape: the key does not hold it; each stereo entry point -- these and the ones
+ * above, which set 0 -- sets the plan's shift under the plan's lock before it queues anything, so no call sees another's. */
+#define FSGM_D_MIN_LIMIT 1024
+fsgm_status fsgm_stereo_sgm_host_range(int32_t n_frames, const uint8_t* I1, const uint8_t* I2, int32_t width, int32_t height,
+                                       int32_t dMax, int32_t P1, int32_t P2, const fsgm_stereo_params* prm,
+                                       const fsgm_epi_options* opt, int32_t d_min, int32_t* disp, uint32_t* minC, uint8_t* conf,
+                                       int32_t* disp2);
+
 /* ---- device-resident plan: buffers for `batch` frames stay in HBM across calls ---- */
 typedef struct fsgm_epi_plan fsgm_epi_plan;
 
@@ -214,6 +232,11 @@ fsgm_status fsgm_epi_plan_set_agg_mode(fsgm_epi_plan* plan, int32_t mode);
  * fsgm_epi_plan_upload_images, and a run with a slot whose image was never uploaded returns FSGM_ERR_INVALID before
  * anything is queued.  With 0 every output and every kernel selection is what it was before the switch existed. */
 fsgm_status fsgm_epi_plan_set_adaptive_p2(fsgm_epi_plan* plan, int32_t on);
+/* The first disparity of a FSGM_SAMPLING_RECTIFIED plan's search range (0 at creation; fsgm_stereo_sgm_host_range above): read
+ * by the next cost stage and forward-backward check.  The plan's own outputs stay candidate indices * 256 (fsgm_epi_plan_download,
+ * _download_fb with 512 << 8 for invalid).  Any other plan: FSGM_ERR_UNSUPPORTED; |d_min| > FSGM_D_MIN_LIMIT: FSGM_ERR_INVALID;
+ * neither touches the device. */
+fsgm_status fsgm_epi_plan_set_d_min(fsgm_epi_plan* plan, int32_t d_min);
 /* host -> HBM (async on the plan's stream) */
 fsgm_status fsgm_epi_plan_upload(fsgm_epi_plan* plan, int32_t frame, const uint8_t* I1,
                                  const uint8_t* I2, const double* pixelPosD0,
@@ -761,6 +784,12 @@ fsgm_status fsgm_stereo_sgm_device_opts(int32_t n_frames, const uint8_t* I1, con
                                         int32_t dMax, int32_t P1, int32_t P2, const fsgm_stereo_params* prm,
                                         const fsgm_epi_options* opt, uint32_t* disp, uint32_t* minC, uint8_t* conf, uint32_t* disp2,
                                         void* stream, int32_t* status);
+/* fsgm_stereo_sgm_host_range on device pointers: disp / disp2 int32 true disparities * 256 (disp2 INT32_MIN where invalid); the
+ * rules of the entry points above (the caller's stream, no graph capture, no host memory, no C / S taps) */
+fsgm_status fsgm_stereo_sgm_device_range(int32_t n_frames, const uint8_t* I1, const uint8_t* I2, int32_t width, int32_t height,
+                                         int32_t dMax, int32_t P1, int32_t P2, const fsgm_stereo_params* prm,
+                                         const fsgm_epi_options* opt, int32_t d_min, int32_t* disp, uint32_t* minC, uint8_t* conf,
+                                         int32_t* disp2, void* stream, int32_t* status);
 /* epipolar_sgm_of on n_frames image pairs, one plan of batch n_frames: g (HOST memory) holds n_frames geometries, each
  * passed to the maps kernel by value.  I0 / I1 u8 [n][channels][H][W]; flow f64 [n][3][H][W]; minC (may be NULL) u32 [n][H][W]. */
 fsgm_status fsgm_epipolar_sgm_of_device(int32_t n_frames, const uint8_t* I0, const uint8_t* I1, int32_t width,
