@@ -22,6 +22,11 @@ struct NgPool {
     size_t cap = 0;
     int small_calls = 0;               // consecutive calls that used at most a quarter of the arena
     hipStream_t stream = nullptr;
+    // the last level of the hint-map variant's host entry points, for fsgm_ng_last_decision (kstat: in the arena; null: none)
+    const uint32_t* kstat = nullptr;
+    NgMatcherSet set;
+    int frames = 0;
+    long long pixels = 0;
 };
 NgPool g_pools[FSGM_MAX_DEVICES];      // one arena per device: calls on different devices run side by side
 
@@ -40,6 +45,7 @@ struct DevBufs {                       // the arena of `device` for the duration
         size_t total = 0;
         for (auto& r : req) total += r.second;
         hipError_t e = hipSuccess;
+        g_pool.kstat = nullptr;                                  // the arena is carved anew
         // the arena grows to the largest call and shrinks again once eight calls in a row used at most a quarter of it
         // (a session that moved on to smaller frames does not hold the large frames' memory until fsgm_shutdown)
         g_pool.small_calls = (g_pool.cap >= (1u << 24) && total <= g_pool.cap / 4) ? g_pool.small_calls + 1 : 0;
@@ -75,7 +81,7 @@ void fsgm_ng_shutdown_internal(void) {
         if (g_pool.device >= 0) (void)hipSetDevice(g_pool.device);
         if (g_pool.base) (void)hipFree(g_pool.base);
         if (g_pool.stream) (void)hipStreamDestroy(g_pool.stream);
-        g_pool.base = nullptr; g_pool.cap = 0; g_pool.stream = nullptr; g_pool.device = -1;
+        g_pool.base = nullptr; g_pool.cap = 0; g_pool.stream = nullptr; g_pool.device = -1; g_pool.kstat = nullptr;
     }
 }
 
@@ -116,7 +122,8 @@ fsgm_status fsgm_calc_pyd_cost_sgm_ng_batch_host(int32_t n, const fsgm_ng_in* in
         FSGM_HIP(hipMemcpyAsync(dMv + i * 2 * MV, in[i].preMv, MV * 16, hipMemcpyHostToDevice, d.stream));
     }
     const NgLevel lv = {dI1, dI2, dMv, dMinC, dFlow, W, H, a.mvWidth, a.mvHeight, r, rAgg, a.P1, a.P2, a.subPixelRefine};
-    FSGM_HIP(ng_level_enqueue(d.stream, nb, lv, n));
+    NgMatcherSet ms;
+    FSGM_HIP(ng_level_enqueue(d.stream, nb, lv, n, &ms));
     bool want_S = false;
     for (int i = 0; i < n; i++) want_S = want_S || out[i].S;
     if (want_S && D <= 128) {
@@ -125,6 +132,7 @@ fsgm_status fsgm_calc_pyd_cost_sgm_ng_batch_host(int32_t n, const fsgm_ng_in* in
     }
     FSGM_HIP(hipGetLastError());
     FSGM_HIP(hipStreamSynchronize(d.stream));
+    d.g_pool.kstat = nb.kstat; d.g_pool.set = ms; d.g_pool.frames = n; d.g_pool.pixels = (long long)NP * n;
     for (int i = 0; i < n; i++) {
         FSGM_HIP(hipMemcpy(out[i].minC, dMinC + i * NP, NP * 4, hipMemcpyDeviceToHost));
         FSGM_HIP(hipMemcpy(out[i].flow, dFlow + i * 2 * NP, NP * 16, hipMemcpyDeviceToHost));
@@ -135,6 +143,34 @@ fsgm_status fsgm_calc_pyd_cost_sgm_ng_batch_host(int32_t n, const fsgm_ng_in* in
 
 fsgm_status fsgm_calc_pyd_cost_sgm_ng_host(const fsgm_ng_in* in, const fsgm_ng_out* out, int32_t device) {
     return fsgm_calc_pyd_cost_sgm_ng_batch_host(1, in, out, device);
+}
+
+const char* fsgm_ng_auto_matcher(int32_t width, int32_t height, int32_t D, int32_t frames, uint64_t list_sum, uint64_t sample_pixels,
+                                 uint32_t flags) {
+    if (width < 1 || height < 1 || D < 1 || frames < 1) return "";
+    return ng_auto_matcher(width, height, D, frames, list_sum, sample_pixels, flags);
+}
+
+uint64_t fsgm_ng_sample_pixels(uint64_t pixels) { return ng_sample_pixels(pixels); }
+
+fsgm_status fsgm_ng_last_decision(int32_t device, const char** matcher, uint64_t* list_sum, uint64_t* sample_pixels, uint32_t* flags) {
+    FSGM_REQUIRE(matcher && list_sum && sample_pixels && flags, "fsgm_ng_last_decision: null argument");
+    const fsgm_status st = pick_device(device);
+    if (st != FSGM_OK) return st;
+    NgPool& g_pool = g_pools[device];
+    std::lock_guard<std::mutex> lk(g_pool.mu);
+    FSGM_REQUIRE(g_pool.kstat, "fsgm_ng_last_decision: no level of calc_pyd_cost_sgm_ng has run on device %d", device);
+    *list_sum = 0; *sample_pixels = 0; *flags = 0;
+    uint32_t choice = ng_choose(g_pool.set, g_pool.frames, 0, 0, 0);                 // the host's, where the set leaves no choice
+    if (g_pool.set.device_choice()) {
+        uint32_t k[NG_KSTAT_WORDS];
+        FSGM_HIP(hipMemcpy(k, g_pool.kstat, sizeof k, hipMemcpyDeviceToHost));
+        uint32_t sum = 0;                                                            // (as ng_decide_kernel adds them)
+        for (int i = 0; i < 256; i++) sum += k[i];
+        choice = k[NG_KSTAT_CHOICE]; *list_sum = sum; *sample_pixels = ng_sample_pixels((unsigned long long)g_pool.pixels); *flags = k[NG_KSTAT_FLAGS];
+    }
+    *matcher = ng_matcher_name(g_pool.set, choice);
+    return FSGM_OK;
 }
 
 int64_t fsgm_sgm_ng_rand_draws(int32_t W, int32_t H) { return (int64_t)W * H * 8; }

@@ -34,19 +34,16 @@ struct NgAggArgs {
                             // than the grid matcher takes (launch_ng_dedupe); null: list matcher only
     const uint32_t* ck;     // [frames][NP][D] packed motion vector (ng_pack_mv) of the kept entry at each place   } launch_ng_dedupe; the
     const uint16_t* cm;     // [frames][NP][D] (index of the group's first member << 8) | cost of the kept entry     } compact kernel's input
-    int role;               // which of the launch's aggregation kernels this is (NG_ROLE_*): each decides on the device whether it runs
-    int with_compact;       // the compact kernel is part of this launch set
-    int compact_g;          // compact kernel: lanes a line of this launch (16 / 32 / 64); the one the list statistics favour runs
-    int compact_force;      // ... or this one whatever they say (FSGM_NG_COMPACT_G, tests)
+    int me;                 // this kernel's matcher id (NG_COMPACT16 ...): it runs when kstat's choice word names it; NG_ANY: it always runs
     int blk_begin_c[5];     // compact kernel: first block of each range (4 lines a workgroup)
     int slot_of_c[4];
     int16_t* L4;            // [frames][NP][4 path slots][64] the compact kernel's path costs of the kept entries, by place in the pixel's list:
                             // plain 2-byte stores, contiguous per pixel and path, instead of one atomic add to S per kept entry and path
                             // (208 M scattered atomics per batch of 8 at 1242x375: 1.6 of 8.3 ms).  The WTA sums the four slots.
                             // Null: the compact kernel is not launched
-    uint32_t* kstat;        // [256] partial sums of the list lengths of a sample of this launch's pixels, [256] flags: bit 0 a list longer
-                            // than 64 entries, bit 1 a pixel whose entries do not fit the packed key (launch_ng_dedupe); [257] set by the
-                            // compact kernel when it is the one that runs: S holds nothing then, the sums are in L4
+    uint32_t* kstat;        // [0, 256) partial sums of the list lengths of a sample of this launch's pixels; [NG_KSTAT_FLAGS] bit 0 a list longer
+                            // than 64 entries, bit 1 a pixel whose entries do not fit the packed key (launch_ng_dedupe); [NG_KSTAT_CHOICE] the
+                            // id of the matcher that runs (ng_decide_kernel; a compact id: S holds nothing, the sums are in L4)
     int W, H, D;
     int P1, P2;
     int blk_begin[5];
@@ -58,8 +55,8 @@ struct NgWtaArgs {
     const uint32_t* S;
     const uint16_t* cm;     // launch_ng_dedupe's kept-entry table and list lengths: the search runs over the groups of repeats,
     const uint8_t* dk;      // whose sums sit at their first members' indices; both null: over all D candidates
-    const int16_t* L4;      // the compact kernel's per-path costs and the launch's statistics words (kstat[257] != 0: sums = the four
-    const uint32_t* kstat;  // slots of L4 at the entry's place; else S); null: S
+    const int16_t* L4;      // the compact kernel's per-path costs and the launch's statistics words (the choice word a compact id: sums =
+    const uint32_t* kstat;  // the four slots of L4 at the entry's place; else S); null: S
     const uint32_t* K4;     // 4-byte entries and the cost kernel's flags (flags[1] == 0: every key fits): the winner's motion vector comes
     const uint32_t* flags;  // from its key when the compact kernel ran; null: from C
     uint32_t* minC;         // [frames][NP]
@@ -89,9 +86,11 @@ struct OtfArgs {
     int exact;              // 1: start in the exact matcher (FSGM_OTF_EXACT=1; otherwise entered when a motion vector leaves the packed range)
 };
 
-// repeats among the D <= 128 candidates of every pixel (same motion vector and same cost), see ng_dedupe_kernel
-enum { NG_ROLE_ANY = 0, NG_ROLE_GRID = 1, NG_ROLE_LIST = 2, NG_ROLE_COMPACT = 3, NG_ROLE_REST = 4 };
-constexpr int NG_KSTAT_WORDS = 259;
+// The aggregation kernels of a level with D <= 128.  NG_ANY: the level's only matcher; NG_REST: the split or
+// lines kernel next to the compact kernels, when the grid kernel is not in the set; NG_LIST: the lines kernel next to the grid kernel
+enum { NG_ANY = 0, NG_COMPACT16 = 1, NG_COMPACT32 = 2, NG_COMPACT64 = 3, NG_GRID = 4, NG_LIST = 5, NG_REST = 6 };
+__host__ __device__ inline bool ng_is_compact(uint32_t id) { return id >= NG_COMPACT16 && id <= NG_COMPACT64; }
+constexpr int NG_KSTAT_FLAGS = 256, NG_KSTAT_CHOICE = 257, NG_KSTAT_WORDS = 258;
 constexpr int NG_L4_PER_PIXEL = 4 * 64;      // int16 entries of L4 per pixel
 
 // Scratch of one level of the hint-map variant for all frames of a batch (frame-major); ng_level_bufs sizes it
@@ -124,13 +123,48 @@ struct NgLevel {
     int P1, P2;
     int subPixelRefine;
 };
+// The aggregation kernels a level launches: ng_matcher_set fills it from the level's shape, its frame count and the
+// A/B switches, once per level enqueue.  With more than one member the device picks: ng_decide_kernel feeds the dedupe kernel's
+// statistics to ng_choose and leaves the id in kstat's choice word, and every matcher returns unless the word names it.
+struct NgMatcherSet {
+    bool plain;             // D > 128: ng_agg_kernel, the only member
+    bool compact;           // the compact kernels.  They walk a frame with 32-bit byte offsets (entries x 4 bytes, pixels x 512 bytes
+                            // of L4): not for W*H*D >= 2^30 or W*H >= 2^23
+    int compact_g;          // 16 / 32 / 64: that lanes-a-line class is the only compact member (FSGM_NG_COMPACT_G); 0: all three
+    bool grid, grid_only;   // the grid kernel is a member / the only one (FSGM_NG_GRID=1)
+    int parts;              // the split kernel's parts (2 .. 4: FSGM_NG_SPLIT, one or two frames); 1: the lines kernel
+    bool device_choice() const { return compact || (grid && !grid_only); }
+};
+// the dedupe kernel's sample of n pixels: every 16th workgroup of 4 pixels
+__host__ __device__ inline unsigned long long ng_sample_pixels(unsigned long long n) { return (((n + 3) / 4 + 15) / 16) * 4; }
+// The rule: which member runs, from the sum of the sampled list lengths, the sample's pixel count and kstat's flags word.
+// Compact (one wave per 64/G lines over the kept entries only, work ~ K^2): every list <= 64 entries and inside the packed key's
+// range, mean length below 40; its class by the mean length for batches (throughput: more lines a wave), 64 lanes for one or two
+// frames (their long lines are serial chains: one line a wave is the shortest step); a forced class still steps aside for lists
+// it cannot hold.  Otherwise grid from a mean length of 16 (it costs the same at any length), list below it.
+__host__ __device__ inline uint32_t ng_choose(const NgMatcherSet& ms, int frames, unsigned long long sum, unsigned long long npix, uint32_t flags) {
+    constexpr unsigned long long NG_COMPACT_MAX_K = 40, NG_GRID_MIN_K = 16;
+    if (ms.compact && (flags & 3u) == 0u && sum < NG_COMPACT_MAX_K * npix) {
+        if (ms.compact_g) return ms.compact_g == 16 ? NG_COMPACT16 : ms.compact_g == 32 ? NG_COMPACT32 : NG_COMPACT64;
+        return frames <= 2 ? NG_COMPACT64 : sum < 14 * npix ? NG_COMPACT16 : sum < 28 * npix ? NG_COMPACT32 : NG_COMPACT64;
+    }
+    if (ms.grid_only) return NG_GRID;
+    if (ms.grid) return sum >= NG_GRID_MIN_K * npix ? NG_GRID : NG_LIST;
+    return ms.compact ? NG_REST : NG_ANY;
+}
+// "compact16" / "compact32" / "compact64", "grid", "list", "split2" .. "split4", "lines", "generic": the kernel behind an id of this set
+const char* ng_matcher_name(const NgMatcherSet& ms, uint32_t id);
+// what the rule answers for a level of this shape under the current FSGM_NG_* environment: no device needed
+const char* ng_auto_matcher(int W, int H, int D, int frames, unsigned long long sum, unsigned long long npix, uint32_t flags);
+
 // Queues the level on `st`: census of both images, candidate costs, repeat removal, matcher, WTA and, when asked, the census
 // sub-pixel step.  Reads the A/B switches and decides the 4-byte entries.  With D <= 128 the matchers leave
 // S incomplete: a caller that reads S back queues launch_ng_l4_to_s and launch_ng_fill_repeats behind the level.
-hipError_t ng_level_enqueue(hipStream_t st, const NgLevelBufs& b, const NgLevel& lv, int frames);
+// `used` (may be null): the level's matcher set, for fsgm_ng_last_decision.
+hipError_t ng_level_enqueue(hipStream_t st, const NgLevelBufs& b, const NgLevel& lv, int frames, NgMatcherSet* used = nullptr);
 // S of the repeats := S of the entries they repeat (only needed when S itself is read back: the WTA looks them up)
 void launch_ng_fill_repeats(hipStream_t st, uint32_t* S, const uint16_t* dd, const uint16_t* cm, int W, int H, int D, int frames);
-// S at the kept entries' first-member indices := the sum of L4's four slots, when the compact kernel ran (kstat[257]): only for reading S back
+// S at the kept entries' first-member indices := the sum of L4's four slots, when a compact kernel ran (kstat's choice word): only for reading S back
 void launch_ng_l4_to_s(hipStream_t st, uint32_t* S, const int16_t* L4, const uint16_t* cm, const uint8_t* dk, const uint32_t* kstat, int W, int H, int D, int frames);
 void launch_otf(hipStream_t st, const OtfArgs& a, int frames);
 

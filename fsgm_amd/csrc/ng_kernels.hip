@@ -305,39 +305,6 @@ constexpr int NG_GB = 12;
 constexpr int NG_GS = NG_GB + 8;
 constexpr int NG_GCELLS = NG_GS * NG_GS;
 constexpr uint32_t NG_BOX_WIDE = 0xFFFFFFFFu;
-constexpr uint32_t NG_GRID_MIN_K = 16;   // mean list length from which the grid form is the faster one (it costs the same at any length)
-
-constexpr uint32_t NG_COMPACT_MAX_K = 40;   // mean list length up to which the compact kernel (work ~ K^2) beats the grid form (flat)
-
-// Choice between the aggregation kernels of a launch, made on the device: all candidates are launched, each sums the
-// 256 partial list-length sums of the dedupe kernel, reads its flags, and those the lists do not favour return
-// (block-uniform).  Compact (one wave a line over the kept entries only): every list <= 64 entries, every entry inside
-// the packed key's range, mean length below NG_COMPACT_MAX_K.  Otherwise grid from a mean length of NG_GRID_MIN_K, list
-// below it; NG_ROLE_REST: whatever runs when the compact kernel does not (the split kernel of one or two frames).
-__device__ __forceinline__ bool ng_agg_not_mine(const NgAggArgs& a, uint32_t* scratch) {
-    if (a.role == NG_ROLE_ANY) return false;
-    if (threadIdx.x == 0) *scratch = 0;
-    __syncthreads();
-    uint32_t v = threadIdx.x < 256 ? a.kstat[threadIdx.x] : 0u;
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) v += (uint32_t)__shfl_xor((int)v, s);
-    if ((threadIdx.x & 63) == 0) atomicAdd(scratch, v);
-    __syncthreads();
-    const unsigned long long npix = ((((unsigned long long)a.W * a.H * gridDim.y + 3) / 4 + 15) / 16) * 4;   // the dedupe kernel's sample: every 16th workgroup of 4 pixels
-    const unsigned long long sum = *scratch;
-    const bool high = sum >= (unsigned long long)NG_GRID_MIN_K * npix;
-    const uint32_t flags = a.kstat[256];
-    const bool compact = a.with_compact && (flags & 3u) == 0u && sum < (unsigned long long)NG_COMPACT_MAX_K * npix;
-    __syncthreads();
-    switch (a.role) {
-        // one launch per lanes-a-line class: by the mean length for batches (throughput: more lines a wave), 64 for one or two
-        // frames (their long lines are serial chains: one line a wave is the shortest step)
-        case NG_ROLE_COMPACT: return !compact || (!a.compact_force && a.compact_g != (gridDim.y <= 2 ? 64 : sum < 14ull * npix ? 16 : sum < 28ull * npix ? 32 : 64));
-        case NG_ROLE_GRID: return compact || !high;
-        case NG_ROLE_LIST: return compact || high;
-        default: return compact;                                 // NG_ROLE_REST
-    }
-}
 
 // motion vector as 2 x u16 (valid for |mv| < 0x3FF0: the launch's unsafe flag is raised otherwise)
 constexpr uint32_t NG_PADKEY = 0xC000C000u;   // a staged key no candidate in the packed range is equal or near to
@@ -422,7 +389,7 @@ __device__ __forceinline__ void ng_match4_pair(const NgPre& q, int D, int mvxa, 
 // without repeats gives every candidate the same minima as the full list, as long as of every group of repeats
 // the LAST is kept ("last exact match wins", :60-62: the kept entries stay in their order).  One wave per pixel:
 // keys (mvx, mvy, C) packed into 31 bits, every lane finds the last index holding its key, kept entries are
-// ranked with two ballots.  A pixel with a vector outside +-4095 keeps its whole list.
+// ranked with two ballots.  A pixel with a vector outside +-4095 (no key) finds its repeats by comparing all pairs of entries.
 //
 // "The last index holding my key" without comparing all pairs: up to three rounds over a 256-slot table in LDS.
 // In a round every unsettled entry posts its index + 1 to the slot its key hashes to (ds_max), then reads the slot's
@@ -506,6 +473,18 @@ __global__ __launch_bounds__(256) void ng_dedupe_kernel(const Cand* __restrict__
                 }
             }
         }
+    } else {
+        // a vector outside the key's range: the keys do not tell the entries apart, so every entry is compared with all D
+        // (rare: hints beyond +-4095; the hash table's memory holds the vectors, the keys' the costs)
+        uint32_t* ex = stab[wave];
+        if (has0) { ex[d0] = (uint32_t)e0.mvx; ex[128 + d0] = (uint32_t)e0.mvy; sk[wave][d0] = (uint32_t)e0.cost; }
+        if (has1) { ex[d1] = (uint32_t)e1.mvx; ex[128 + d1] = (uint32_t)e1.mvy; sk[wave][d1] = (uint32_t)e1.cost; }
+        __builtin_amdgcn_wave_barrier();
+        for (int e = 0; e < D; e++) {
+            const uint32_t x = ex[e], y = ex[128 + e], c = sk[wave][e];
+            last0 = (x == (uint32_t)e0.mvx && y == (uint32_t)e0.mvy && c == (uint32_t)e0.cost) ? e : last0;
+            last1 = (x == (uint32_t)e1.mvx && y == (uint32_t)e1.mvy && c == (uint32_t)e1.cost) ? e : last1;
+        }
     }
     const bool keep0 = has0 && last0 == d0, keep1 = has1 && last1 == d1;
     const unsigned long long b0 = __builtin_amdgcn_ballot_w64(keep0), b1 = __builtin_amdgcn_ballot_w64(keep1);
@@ -550,7 +529,7 @@ __global__ __launch_bounds__(256) void ng_dedupe_kernel(const Cand* __restrict__
 // one barrier per step.
 __global__ __launch_bounds__(256) void ng_agg_lines_kernel(NgAggArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint32_t sNg[];   // [line][2 buffers][4 arrays][Dp], then [line][8]: 3 minima, the staged lists' lengths at [4 + step parity]
-    if (ng_agg_not_mine(a, sNg)) return;
+    if (a.me != NG_ANY && a.kstat[NG_KSTAT_CHOICE] != (uint32_t)a.me) return;   // block-uniform: another member of the set runs (ng_choose)
     int slot = 0;
 #pragma unroll
     for (int i = 1; i < 4; i++)
@@ -653,7 +632,7 @@ __global__ __launch_bounds__(256) void ng_agg_lines_kernel(NgAggArgs a) {
 // fit a box takes the list matcher: same results either way.
 __global__ __launch_bounds__(256) void ng_agg_grid_kernel(NgAggArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint32_t sNg[];   // lists [line][2][4][Dp]; grids [line][3][2][NG_GCELLS]; [line][8] minima ring + lengths; [2][line] box flags
-    if (ng_agg_not_mine(a, sNg)) return;
+    if (a.me != NG_ANY && a.kstat[NG_KSTAT_CHOICE] != (uint32_t)a.me) return;   // block-uniform: another member of the set runs (ng_choose)
     int slot = 0;
 #pragma unroll
     for (int i = 1; i < 4; i++)
@@ -803,7 +782,7 @@ __global__ __launch_bounds__(256) void ng_agg_grid_kernel(NgAggArgs a) {
 // (ng_wta_kernel; launch_ng_fill_repeats when S itself is wanted).  With the lists of real hint maps (10-20 of 81
 // entries distinct) that is a quarter of the matcher work and of the atomic adds; the line's minimum is a wave
 // reduction and a step has no workgroup barrier at all -- the four waves of a workgroup walk four lines independently.
-// Runs when every list of the launch has at most 64 entries inside the packed key's range (ng_agg_not_mine).
+// Runs when every list of the launch has at most 64 entries inside the packed key's range (ng_choose).
 // four entries of the predecessor against one candidate key: first-class "last exact match wins" (min1 follows the entry
 // order) and the minimum over the near, not equal entries
 __device__ __forceinline__ void ng_match4_group(const uint4 k4, const uint4 c8, const uint4 cp, const uint32_t ck2, uint32_t& min1, uint32_t& near2min) {
@@ -882,9 +861,7 @@ __global__ __launch_bounds__(256) void ng_agg_compact_kernel(NgAggArgs a) {
     constexpr int LPW = 64 / G;                               // lines per wave
     constexpr int LS = 68;                                    // LDS stride of one array: 64 entries + 4 (a multiple of 4: 16-byte reads)
     __shared__ __attribute__((aligned(16))) uint32_t sC[4 * LPW][2][3][LS];    // [line of the workgroup][buffer][key, cost & 0xFF, (cost + P1) & 0xFF][place]
-    __shared__ uint32_t sPick;
-    if (ng_agg_not_mine(a, &sPick)) return;
-    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) a.kstat[257] = 1u;   // tells the WTA where the sums are (L4, not S)
+    if (a.me != NG_ANY && a.kstat[NG_KSTAT_CHOICE] != (uint32_t)a.me) return;   // block-uniform: another member of the set runs (ng_choose)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int sub = lane / G, pl_ = lane % G;                 // line of the wave, first place in its list
     int bb = 0;
@@ -1084,7 +1061,7 @@ __device__ __forceinline__ void ng_match_range(const NgPre& q, int e0, int e1, i
 template <int PARTS>
 __global__ __launch_bounds__(256 * PARTS) void ng_agg_split_kernel(NgAggArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint32_t sNg[];
-    if (ng_agg_not_mine(a, sNg)) return;
+    if (a.me != NG_ANY && a.kstat[NG_KSTAT_CHOICE] != (uint32_t)a.me) return;   // block-uniform: another member of the set runs (ng_choose)
     // [line][2 buffers][4 arrays][Dp] | [line][8]: 3 minima, staged lengths at [4 + step parity] | [line][Dp] candidate mvx | [line][Dp] mvy | [PARTS - 1][line][Dp][2]
     int k = 0;
 #pragma unroll
@@ -1216,7 +1193,7 @@ __global__ __launch_bounds__(256) void ng_wta_kernel(NgWtaArgs a) {
     const uint32_t* Sp = a.S + f * (size_t)NP * D + (size_t)p * D;
     const uint16_t* cmp = a.cm ? a.cm + f * (size_t)NP * D + (size_t)p * D : nullptr;
     const int n = cmp ? (int)a.dk[f * (size_t)NP + p] : D;
-    const bool l4 = cmp && a.L4 && a.kstat && a.kstat[257] != 0;              // launch-uniform: the compact kernel ran
+    const bool l4 = cmp && a.L4 && a.kstat && ng_is_compact(a.kstat[NG_KSTAT_CHOICE]);   // launch-uniform: a compact kernel ran
     const int16_t* Lp = a.L4 + (f * (size_t)NP + p) * NG_L4_PER_PIXEL;
     uint32_t lo = 0xFFFFFFFFu, idx = 0xFFFFFFFFu;
     for (int e = l16; e < n; e += 16) {
@@ -1758,6 +1735,40 @@ static NgSwitches ng_read_switches() {
     return sw;
 }
 
+static NgMatcherSet ng_matcher_set(int W, int H, int D, int frames, const NgSwitches& sw) {
+    NgMatcherSet ms = {};
+    ms.plain = D > 128;
+    ms.parts = 1;
+    if (ms.plain) return ms;
+    // 1242x375, 3-level pyramid: 9.64 / 7.34 / 7.98 / 7.66 ms with 1 / 2 / 3 / 4 parts
+    if (frames <= 2 && sw.split >= 2 && sw.split <= 4) ms.parts = sw.split;
+    if (!sw.dedupe) return ms;                                // the matchers stage every candidate: no tables, no statistics
+    ms.grid_only = sw.grid == 1;
+    // The grid form of the matcher costs the same at any list length, the list form grows with it: lists of a few
+    // entries (nearly constant hint maps) are faster walked, anything richer is faster looked up.
+    ms.grid = ms.grid_only || (sw.grid != 0 && ms.parts == 1);
+    ms.compact = sw.compact != 0 && !ms.grid_only && (long long)W * H * D < (1LL << 30) && (long long)W * H < (1LL << 23);
+    if (ms.compact && (sw.compact_g == 16 || sw.compact_g == 32 || sw.compact_g == 64)) ms.compact_g = sw.compact_g;
+    return ms;
+}
+
+const char* ng_matcher_name(const NgMatcherSet& ms, uint32_t id) {
+    static const char* const split[] = {"lines", "lines", "split2", "split3", "split4"};
+    switch (id) {
+        case NG_COMPACT16: return "compact16";
+        case NG_COMPACT32: return "compact32";
+        case NG_COMPACT64: return "compact64";
+        case NG_GRID: return "grid";
+        case NG_LIST: return "list";
+        default: return ms.plain ? "generic" : split[ms.parts];   // NG_REST, NG_ANY
+    }
+}
+
+const char* ng_auto_matcher(int W, int H, int D, int frames, unsigned long long sum, unsigned long long npix, uint32_t flags) {
+    const NgMatcherSet ms = ng_matcher_set(W, H, D, frames, ng_read_switches());
+    return ng_matcher_name(ms, ng_choose(ms, frames, sum, npix, flags));
+}
+
 static void launch_ng_cost(hipStream_t st, const NgCostArgs& a, int frames, const NgSwitches& sw) {
     if (sw.cost_hint && a.rX == 1 && a.rY == 1 && a.rAgg == 1) {
         const long long n = (long long)a.W * a.H * 9;
@@ -1777,7 +1788,7 @@ static void launch_ng_cost(hipStream_t st, const NgCostArgs& a, int frames, cons
     hipLaunchKernelGGL(ng_cost_kernel, grid, dim3(256), 0, st, a);
 }
 
-static void launch_ng_aggregate(hipStream_t st, NgAggArgs a, int frames, const NgSwitches& sw) {
+static void launch_ng_aggregate(hipStream_t st, NgAggArgs a, int frames, const NgMatcherSet& ms, bool dedupe) {
     // slots: 0 along x, 1 along y, 2/3 their point mirrors (pass 1)
     int acc = 0;
     for (int i = 0; i < 4; i++) {
@@ -1785,78 +1796,57 @@ static void launch_ng_aggregate(hipStream_t st, NgAggArgs a, int frames, const N
         acc += (((i & 1) == 0 ? a.H : a.W) + 3) / 4;
     }
     a.blk_begin[4] = acc;
-    a.role = NG_ROLE_ANY; a.with_compact = 0; a.compact_force = 0; a.compact_g = 0;
-    if (!sw.dedupe) { a.dd = nullptr; a.dk = nullptr; a.dbox = nullptr; a.ck = nullptr; a.cm = nullptr; }   // stage every candidate
-    if (a.D <= 128 && a.unsafe) {
-        const int lpb = 256 / a.D, Dp = (a.D + 3) & ~3;
-        // long lines first: with few frames their blocks decide when the launch ends
-        const int nparts = frames <= 2 ? sw.split : 1;   // 1242x375, 3-level pyramid: 9.64 / 7.34 / 7.98 / 7.66 ms with 1 / 2 / 3 / 4 parts
-        const bool split = nparts >= 2 && nparts <= 4;
-        const int ord_x[4] = {0, 2, 1, 3}, ord_y[4] = {1, 3, 0, 2};
-        // Which kernel runs is settled on the device from what the dedupe kernel saw (ng_agg_not_mine): every candidate
-        // is launched, the ones not favoured return at once.  A/B switches: FSGM_NG_COMPACT=0 / FSGM_NG_GRID=0 take a kernel out
-        // of the set, FSGM_NG_GRID=1 makes the grid kernel the only one, FSGM_NG_COMPACT_G=16|32|64 fixes the compact kernel's
-        // lanes a line (it still steps aside for lists it cannot hold).
-        const bool can_stat = a.dd && a.dk && a.kstat;
-        if (can_stat && a.ck && a.cm && a.L4 && sw.compact != 0 && sw.grid != 1) {
-            acc = 0;
-            for (int i = 0; i < 4; i++) {
-                const int sl = a.W >= a.H ? ord_x[i] : ord_y[i];
-                a.slot_of_c[i] = sl;
-                a.blk_begin_c[i] = acc;
-                acc += (((sl & 1) == 0 ? a.H : a.W) + 3) / 4;
-            }
-            a.blk_begin_c[4] = acc;
-            a.with_compact = 1;
-            a.role = NG_ROLE_COMPACT;
-            // one launch per lanes-a-line class (16 / 32 / 64 for lists up to that long); the dedupe kernel's flags pick one
-            const int g_only = sw.compact_g;                     // 16 / 32 / 64: that class only, whatever the lists look like (tests)
-            a.compact_force = g_only == 16 || g_only == 32 || g_only == 64;
-            for (int G = 16; G <= 64; G *= 2) {
-                if (a.compact_force && G != g_only) continue;
-                const int lpb = 4 * (64 / G);                    // lines a workgroup
-                acc = 0;
-                for (int i = 0; i < 4; i++) {
-                    a.blk_begin_c[i] = acc;
-                    acc += (((a.slot_of_c[i] & 1) == 0 ? a.H : a.W) + lpb - 1) / lpb;
-                }
-                a.blk_begin_c[4] = acc;
-                a.compact_g = G;
-                if (G == 16)      hipLaunchKernelGGL(ng_agg_compact_kernel<16>, dim3(acc, frames), dim3(256), 0, st, a);
-                else if (G == 32) hipLaunchKernelGGL(ng_agg_compact_kernel<32>, dim3(acc, frames), dim3(256), 0, st, a);
-                else              hipLaunchKernelGGL(ng_agg_compact_kernel<64>, dim3(acc, frames), dim3(256), 0, st, a);
-            }
-        }
-        acc = 0;
-        for (int i = 0; i < 4; i++) {
-            const int sl = split ? (a.W >= a.H ? ord_x[i] : ord_y[i]) : i;
-            a.slot_of[i] = sl;
-            a.blk_begin[i] = acc;
-            acc += (((sl & 1) == 0 ? a.H : a.W) + lpb - 1) / lpb;
-        }
-        a.blk_begin[4] = acc;
-        // The grid form of the matcher costs the same at any list length, the list form grows with it: lists of a few
-        // entries (nearly constant hint maps) are faster walked, anything richer is faster looked up.
-        const bool with_grid = can_stat && a.dbox && sw.grid != 0 && (sw.grid == 1 || !split);
-        if (with_grid) {
-            const size_t lds = ((size_t)lpb * 8 * Dp + (size_t)lpb * 6 * NG_GCELLS + lpb * 8 + 2 * lpb) * sizeof(uint32_t);
-            a.role = sw.grid == 1 ? NG_ROLE_ANY : NG_ROLE_GRID;
-            hipLaunchKernelGGL(ng_agg_grid_kernel, dim3(acc, frames), dim3(256), lds, st, a);
-            if (sw.grid == 1) return;
-        }
-        a.role = with_grid ? NG_ROLE_LIST : (a.with_compact ? NG_ROLE_REST : NG_ROLE_ANY);
-        if (split) {
-            const size_t lds = ((size_t)lpb * (10 * Dp + 8) + (size_t)(nparts - 1) * lpb * Dp * 2) * sizeof(uint32_t);
-            if (nparts == 2)      hipLaunchKernelGGL(ng_agg_split_kernel<2>, dim3(acc, frames), dim3(512), lds, st, a);
-            else if (nparts == 3) hipLaunchKernelGGL(ng_agg_split_kernel<3>, dim3(acc, frames), dim3(768), lds, st, a);
-            else                  hipLaunchKernelGGL(ng_agg_split_kernel<4>, dim3(acc, frames), dim3(1024), lds, st, a);
-            return;
-        }
-        const size_t lds = ((size_t)lpb * 8 * Dp + lpb * 8) * sizeof(uint32_t);
-        hipLaunchKernelGGL(ng_agg_lines_kernel, dim3(acc, frames), dim3(256), lds, st, a);
+    a.me = NG_ANY;
+    if (ms.plain) {
+        hipLaunchKernelGGL(ng_agg_kernel, dim3(acc, frames), dim3(256), 0, st, a);
         return;
     }
-    hipLaunchKernelGGL(ng_agg_kernel, dim3(acc, frames), dim3(256), 0, st, a);
+    if (!dedupe) { a.dd = nullptr; a.dk = nullptr; a.dbox = nullptr; a.ck = nullptr; a.cm = nullptr; }   // stage every candidate
+    const int lpb = 256 / a.D, Dp = (a.D + 3) & ~3;
+    // long lines first: with few frames their blocks decide when the launch ends
+    const int ord_x[4] = {0, 2, 1, 3}, ord_y[4] = {1, 3, 0, 2};
+    // Every member of the set is launched; where the set leaves a choice, the ones kstat's choice word does not name return at once.
+    if (ms.compact) {
+        for (int i = 0; i < 4; i++) a.slot_of_c[i] = a.W >= a.H ? ord_x[i] : ord_y[i];
+        // one launch per lanes-a-line class (16 / 32 / 64), or the forced one alone
+        for (int G = 16; G <= 64; G *= 2) {
+            if (ms.compact_g && G != ms.compact_g) continue;
+            const int lpbc = 4 * (64 / G);                   // lines a workgroup
+            acc = 0;
+            for (int i = 0; i < 4; i++) {
+                a.blk_begin_c[i] = acc;
+                acc += (((a.slot_of_c[i] & 1) == 0 ? a.H : a.W) + lpbc - 1) / lpbc;
+            }
+            a.blk_begin_c[4] = acc;
+            if (G == 16)      { a.me = NG_COMPACT16; hipLaunchKernelGGL(ng_agg_compact_kernel<16>, dim3(acc, frames), dim3(256), 0, st, a); }
+            else if (G == 32) { a.me = NG_COMPACT32; hipLaunchKernelGGL(ng_agg_compact_kernel<32>, dim3(acc, frames), dim3(256), 0, st, a); }
+            else              { a.me = NG_COMPACT64; hipLaunchKernelGGL(ng_agg_compact_kernel<64>, dim3(acc, frames), dim3(256), 0, st, a); }
+        }
+    }
+    acc = 0;
+    for (int i = 0; i < 4; i++) {
+        const int sl = ms.parts > 1 ? (a.W >= a.H ? ord_x[i] : ord_y[i]) : i;
+        a.slot_of[i] = sl;
+        a.blk_begin[i] = acc;
+        acc += (((sl & 1) == 0 ? a.H : a.W) + lpb - 1) / lpb;
+    }
+    a.blk_begin[4] = acc;
+    if (ms.grid) {
+        const size_t lds = ((size_t)lpb * 8 * Dp + (size_t)lpb * 6 * NG_GCELLS + lpb * 8 + 2 * lpb) * sizeof(uint32_t);
+        a.me = ms.grid_only ? NG_ANY : NG_GRID;
+        hipLaunchKernelGGL(ng_agg_grid_kernel, dim3(acc, frames), dim3(256), lds, st, a);
+        if (ms.grid_only) return;
+    }
+    a.me = ms.grid ? NG_LIST : ms.compact ? NG_REST : NG_ANY;
+    if (ms.parts > 1) {
+        const size_t lds = ((size_t)lpb * (10 * Dp + 8) + (size_t)(ms.parts - 1) * lpb * Dp * 2) * sizeof(uint32_t);
+        if (ms.parts == 2)      hipLaunchKernelGGL(ng_agg_split_kernel<2>, dim3(acc, frames), dim3(512), lds, st, a);
+        else if (ms.parts == 3) hipLaunchKernelGGL(ng_agg_split_kernel<3>, dim3(acc, frames), dim3(768), lds, st, a);
+        else                    hipLaunchKernelGGL(ng_agg_split_kernel<4>, dim3(acc, frames), dim3(1024), lds, st, a);
+        return;
+    }
+    const size_t lds = ((size_t)lpb * 8 * Dp + lpb * 8) * sizeof(uint32_t);
+    hipLaunchKernelGGL(ng_agg_lines_kernel, dim3(acc, frames), dim3(256), lds, st, a);
 }
 
 void launch_ng_fill_repeats(hipStream_t st, uint32_t* S, const uint16_t* dd, const uint16_t* cm, int W, int H, int D, int frames) {
@@ -1872,10 +1862,8 @@ static void launch_ng_dedupe(hipStream_t st, const Cand* C, uint16_t* dd, uint8_
     hipLaunchKernelGGL(ng_dedupe_kernel, dim3((n + 3) / 4), dim3(256), 0, st, C, (K4 && flags) ? K4 : nullptr, flags, dd, dk, dbox, kstat, ck, cm, n, D);
 }
 
-// ---- 4-byte entries: what happens between the dedupe kernel and the matchers (all decided on the device, nothing read back) ----
-// kstat[258] := 1 when the compact matcher is the one that will run (the predicate of ng_agg_not_mine): S is not used then, and
-// with every key in range neither is the 12-byte list
-__global__ __launch_bounds__(256) void ng_decide_kernel(uint32_t* __restrict__ kstat, long long npix_all, int with_compact) {
+// The level's one decision, after the dedupe kernel (one workgroup): kstat's choice word := ng_choose of the launch's statistics
+__global__ __launch_bounds__(256) void ng_decide_kernel(uint32_t* __restrict__ kstat, NgMatcherSet ms, int frames, long long npix_all) {
     __shared__ uint32_t sSum;
     if (threadIdx.x == 0) sSum = 0;
     __syncthreads();
@@ -1884,20 +1872,20 @@ __global__ __launch_bounds__(256) void ng_decide_kernel(uint32_t* __restrict__ k
     for (int s = 32; s >= 1; s >>= 1) v += (uint32_t)__shfl_xor((int)v, s);
     if ((threadIdx.x & 63) == 0) atomicAdd(&sSum, v);
     __syncthreads();
-    if (threadIdx.x == 0) {
-        const unsigned long long npix = (((unsigned long long)(npix_all + 3) / 4 + 15) / 16) * 4;      // the dedupe kernel's sample
-        kstat[258] = (with_compact && (kstat[256] & 3u) == 0u && (unsigned long long)sSum < (unsigned long long)NG_COMPACT_MAX_K * npix) ? 1u : 0u;
-    }
+    if (threadIdx.x == 0) kstat[NG_KSTAT_CHOICE] = ng_choose(ms, frames, sSum, ng_sample_pixels((unsigned long long)npix_all), kstat[NG_KSTAT_FLAGS]);
 }
+
+// ---- 4-byte entries: what happens between the decision and the matchers (gated on the device, nothing read back) ----
+// With a compact matcher S is not used, and with every key in range neither is the 12-byte list.
 // the general matchers read 12-byte entries: made from the keys when the keys are all there is (in range, but the lists too long for the compact matcher)
 __global__ __launch_bounds__(256) void ng_expand_kernel(const uint32_t* __restrict__ K4, Cand* __restrict__ C, const uint32_t* __restrict__ flags,
                                                         const uint32_t* __restrict__ kstat, long long n) {
-    if (flags[1] != 0 || kstat[258] != 0) return;            // (a few thousand workgroups that loop: an early return costs nothing then)
+    if (flags[1] != 0 || ng_is_compact(kstat[NG_KSTAT_CHOICE])) return;   // (a few thousand workgroups that loop: an early return costs nothing then)
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) C[i] = ng_unkey4(K4[i]);
 }
 // S shares its memory with the keys: zeroed (calc_pyd_cost_sgm_ng.cpp:111) once they are no longer needed, and only when a matcher will add to it
 __global__ __launch_bounds__(256) void ng_zero_s_kernel(uint4* __restrict__ S4, const uint32_t* __restrict__ kstat, long long n16, int tail) {
-    if (kstat[258] != 0) return;
+    if (ng_is_compact(kstat[NG_KSTAT_CHOICE])) return;
     const long long i0 = (long long)blockIdx.x * 256 + threadIdx.x;
     for (long long i = i0; i < n16; i += (long long)gridDim.x * 256) S4[i] = make_uint4(0, 0, 0, 0);
     if (i0 == 0) { uint32_t* t = (uint32_t*)(S4 + n16); for (int k = 0; k < tail; k++) t[k] = 0; }
@@ -1908,7 +1896,7 @@ __global__ __launch_bounds__(256) void ng_zero_s_kernel(uint4* __restrict__ S4, 
 // runs when the compact matcher does not
 __global__ __launch_bounds__(256) void ng_dbox_kernel(const uint32_t* __restrict__ K4, const uint32_t* __restrict__ flags, const uint32_t* __restrict__ kstat,
                                                       uint32_t* __restrict__ dbox, int NPtot, int D) {
-    if (flags[1] != 0 || kstat[258] != 0) return;            // (flags[1] != 0: the dedupe kernel read 12-byte entries and made the boxes itself)
+    if (flags[1] != 0 || ng_is_compact(kstat[NG_KSTAT_CHOICE])) return;   // (flags[1] != 0: the dedupe kernel read 12-byte entries and made the boxes itself)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     for (int p = blockIdx.x * 4 + wave; p < NPtot; p += gridDim.x * 4) {
         const uint32_t* k = K4 + (size_t)p * D;
@@ -1919,29 +1907,20 @@ __global__ __launch_bounds__(256) void ng_dbox_kernel(const uint32_t* __restrict
     }
 }
 
-// whether a compact kernel in launch_ng_aggregate's set can be the one that runs (ng_decide_kernel's with_compact)
-static bool ng_compact_possible(const NgAggArgs& a, const NgSwitches& sw) {
-    if (!sw.dedupe) return false;
-    // (the kernel walks a frame with 32-bit byte offsets: entries x 4 bytes and pixels x 512 bytes of L4 must stay below 4 GB)
-    if ((long long)a.W * a.H * a.D >= (1LL << 30) || (long long)a.W * a.H >= (1LL << 23)) return false;
-    return a.D <= 128 && a.unsafe && a.dd && a.dk && a.kstat && a.ck && a.cm && a.L4 && sw.compact != 0 && sw.grid != 1;
-}
-
-// With 4-byte entries (K4 in the memory of S): after the dedupe kernel and before launch_ng_aggregate -- decides on the device whether the
-// compact matcher runs (kstat[258]); if not, expands the keys to the Cand list the general matchers read and zeroes S
+// With 4-byte entries (K4 in the memory of S): after the decision and before launch_ng_aggregate -- unless a compact matcher runs,
+// expands the keys to the Cand list the general matchers read, makes the grid matcher's boxes and zeroes S
 static void launch_ng_prepare_matchers(hipStream_t st, const NgAggArgs& a, const uint32_t* K4, Cand* C, const uint32_t* flags, int frames,
-                                       const NgSwitches& sw) {
+                                       const NgMatcherSet& ms) {
     const long long npix = (long long)a.W * a.H * frames, n = npix * a.D;
-    hipLaunchKernelGGL(ng_decide_kernel, dim3(1), dim3(256), 0, st, a.kstat, npix, ng_compact_possible(a, sw) ? 1 : 0);
     hipLaunchKernelGGL(ng_expand_kernel, dim3((unsigned)std::min<long long>((n + 255) / 256, 4096)), dim3(256), 0, st, K4, C, flags, (const uint32_t*)a.kstat, n);
-    if (a.dbox) hipLaunchKernelGGL(ng_dbox_kernel, dim3((unsigned)std::min<long long>((npix + 3) / 4, 4096)), dim3(256), 0, st, K4, flags, (const uint32_t*)a.kstat,
-                                   const_cast<uint32_t*>(a.dbox), (int)npix, a.D);
+    if (ms.grid) hipLaunchKernelGGL(ng_dbox_kernel, dim3((unsigned)std::min<long long>((npix + 3) / 4, 4096)), dim3(256), 0, st, K4, flags, (const uint32_t*)a.kstat,
+                                    const_cast<uint32_t*>(a.dbox), (int)npix, a.D);
     hipLaunchKernelGGL(ng_zero_s_kernel, dim3((unsigned)std::min<long long>((n / 4 + 256) / 256, 4096)), dim3(256), 0, st, (uint4*)a.S, (const uint32_t*)a.kstat, n / 4, (int)(n % 4));
 }
 
 __global__ __launch_bounds__(256) void ng_l4_to_s_kernel(uint32_t* __restrict__ S, const int16_t* __restrict__ L4, const uint16_t* __restrict__ cm,
                                                          const uint8_t* __restrict__ dk, const uint32_t* __restrict__ kstat, long long npix, int D) {
-    if (kstat[257] == 0) return;                              // another matcher ran: S is complete already
+    if (!ng_is_compact(kstat[NG_KSTAT_CHOICE])) return;       // another matcher ran: S is complete already
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     const long long p = i >> 6;
     const int e = (int)(i & 63);
@@ -1979,9 +1958,11 @@ std::array<NgBuf, 12> ng_level_bufs(NgLevelBufs& b, int W, int H, int D, int fra
              {(void**)&b.L4, D <= 128 ? NP * NG_L4_PER_PIXEL * sizeof(int16_t) : 0}}};
 }
 
-hipError_t ng_level_enqueue(hipStream_t st, const NgLevelBufs& b, const NgLevel& lv, int frames) {
+hipError_t ng_level_enqueue(hipStream_t st, const NgLevelBufs& b, const NgLevel& lv, int frames, NgMatcherSet* used) {
     const NgSwitches sw = ng_read_switches();
     const int W = lv.W, H = lv.H, D = 9 * (2 * lv.r + 1) * (2 * lv.r + 1);
+    const NgMatcherSet ms = ng_matcher_set(W, H, D, frames, sw);
+    if (used) *used = ms;
     // 4-byte candidate entries (the 3x3 hint kernel's sizes, D = 81): the keys live in S's memory until the matchers need S
     const bool k4 = sw.k4 && sw.cost_hint && sw.dedupe && lv.r == 1 && lv.rAgg == 1 && D <= 128;
     hipError_t e;
@@ -1998,11 +1979,13 @@ hipError_t ng_level_enqueue(hipStream_t st, const NgLevelBufs& b, const NgLevel&
     ga.C = b.C; ga.S = b.S; ga.unsafe = b.unsafe; ga.W = W; ga.H = H; ga.D = D; ga.P1 = lv.P1; ga.P2 = lv.P2;
     ga.dd = nullptr; ga.dk = nullptr; ga.dbox = nullptr; ga.kstat = nullptr; ga.ck = nullptr; ga.cm = nullptr; ga.L4 = nullptr;
     if (D <= 128) {                                  // repeats in the candidate lists: the matchers scan each distinct entry once
-        launch_ng_dedupe(st, b.C, b.dd, b.dk, sw.grid == 0 ? nullptr : b.box, b.kstat, b.ck, b.cm, W, H, D, frames, ca.K4, ca.flags);
+        launch_ng_dedupe(st, b.C, b.dd, b.dk, ms.grid ? b.box : nullptr, b.kstat, b.ck, b.cm, W, H, D, frames, ca.K4, ca.flags);
         ga.dd = b.dd; ga.dk = b.dk; ga.dbox = b.box; ga.kstat = b.kstat; ga.ck = b.ck; ga.cm = b.cm; ga.L4 = b.L4;
-        if (k4) launch_ng_prepare_matchers(st, ga, b.S, b.C, b.unsafe, frames, sw);
+        // (without a choice the word stays 0 = NG_ANY, not a compact id: the sums are in S)
+        if (ms.device_choice()) hipLaunchKernelGGL(ng_decide_kernel, dim3(1), dim3(256), 0, st, b.kstat, ms, frames, (long long)W * H * frames);
+        if (k4) launch_ng_prepare_matchers(st, ga, b.S, b.C, b.unsafe, frames, ms);
     }
-    launch_ng_aggregate(st, ga, frames, sw);
+    launch_ng_aggregate(st, ga, frames, ms, sw.dedupe);
     NgWtaArgs wa;
     wa.C = b.C; wa.S = b.S; wa.minC = lv.minC; wa.flow = lv.flow; wa.W = W; wa.H = H; wa.D = D;
     wa.cm = ga.cm; wa.dk = ga.dk; wa.L4 = ga.L4; wa.kstat = ga.kstat; wa.K4 = ca.K4; wa.flags = ca.flags;

@@ -44,6 +44,12 @@ def _bind(lib):
     lib.fsgm_calc_cost_sgm_ng_batch_devices_host.argtypes = [C.c_int32, C.POINTER(OtfIn), C.POINTER(OtfOut), C.c_int32, C.POINTER(C.c_int32)]
     lib.fsgm_sgm_ng_rand_draws.argtypes = [C.c_int32, C.c_int32]
     lib.fsgm_sgm_ng_rand_draws.restype = C.c_int64
+    lib.fsgm_ng_auto_matcher.argtypes = [C.c_int32] * 4 + [C.c_uint64, C.c_uint64, C.c_uint32]
+    lib.fsgm_ng_auto_matcher.restype = C.c_char_p
+    lib.fsgm_ng_sample_pixels.argtypes = [C.c_uint64]
+    lib.fsgm_ng_sample_pixels.restype = C.c_uint64
+    lib.fsgm_ng_last_decision.argtypes = [C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                          C.POINTER(C.c_uint32)]
     lib._ng_bound = True
 
 
@@ -77,6 +83,32 @@ def calc_pyd_cost_sgm_ng(I1, I2, preMv, halfSearchWinSize, aggSize, subPixelRefi
     o.minC, o.flow, o.S = ptr(minC), ptr(flow), ptr(S)
     check(lib.fsgm_calc_pyd_cost_sgm_ng_host(C.byref(a), C.byref(o), int(device)))
     return (minC, flow, S) if return_sum else (minC, flow)
+
+
+def sample_pixels(pixels):
+    """Pixels in the sample of list lengths that a level of `pixels` pixels (width * height * frames) takes (fsgm_ng_sample_pixels)."""
+    lib = _lib.load()
+    _bind(lib)
+    return int(lib.fsgm_ng_sample_pixels(int(pixels)))
+
+
+def auto_matcher(width, height, D, frames, list_sum, sample_pixels, flags=0):
+    """Which aggregation kernel a level of calc_pyd_cost_sgm_ng takes (fsgm_ng_auto_matcher): a pure function of the arguments
+    and the FSGM_NG_* environment, no device needed.  list_sum / sample_pixels: the mean length of the candidate lists without
+    repeats; flags: bit 0 a list longer than 64 entries, bit 1 an entry outside the 4-byte key's range."""
+    lib = _lib.load()
+    _bind(lib)
+    return lib.fsgm_ng_auto_matcher(int(width), int(height), int(D), int(frames), int(list_sum), int(sample_pixels), int(flags)).decode()
+
+
+def last_decision(device=0):
+    """(matcher, list_sum, sample_pixels, flags) of the most recent level calc_pyd_cost_sgm_ng / _batch ran on `device`
+    (fsgm_ng_last_decision): a diagnostic, the results do not depend on the matcher."""
+    lib = _lib.load()
+    _bind(lib)
+    name, s, n, f = C.c_char_p(), C.c_uint64(), C.c_uint64(), C.c_uint32()
+    check(lib.fsgm_ng_last_decision(int(device), C.byref(name), C.byref(s), C.byref(n), C.byref(f)))
+    return name.value.decode(), s.value, n.value, f.value
 
 
 def sgm_ng_rand_draws(width, height):

@@ -666,6 +666,23 @@ fsgm_status fsgm_calc_pyd_cost_sgm_ng_host(const fsgm_ng_in* in, const fsgm_ng_o
 fsgm_status fsgm_calc_pyd_cost_sgm_ng_batch_host(int32_t n_frames, const fsgm_ng_in* in,
                                                  const fsgm_ng_out* out, int32_t device);
 
+/* Diagnostics: which aggregation kernel a level of calc_pyd_cost_sgm_ng takes.  All of them give the same results; the choice
+ * is one of speed, made per level from the level's shape, the frame count, the FSGM_NG_* environment and -- on the device -- the
+ * lengths of the candidate lists without repeats (a 1-in-16 sample of the pixels) and two flags (bit 0: a list longer than 64
+ * entries, bit 1: an entry outside the packed 4-byte key's range).
+ * fsgm_ng_auto_matcher: what the rule answers for D candidates per pixel, the sum of the sampled list lengths, the sample's pixel
+ * count (fsgm_ng_sample_pixels(width * height * frames) for a real level) and the flags: "compact16" / "compact32" / "compact64",
+ * "grid", "list", "split2" .. "split4", "lines" or "generic"; "" for a size below 1.  A pure function of its arguments and the
+ * environment: no device is touched.
+ * fsgm_ng_last_decision: the name of the kernel that ran and the three statistics of the most recent level that
+ * fsgm_calc_pyd_cost_sgm_ng_host / _batch_host ran on `device` (read from that call's scratch memory; FSGM_ERR_INVALID when
+ * there is none, or when fsgm_calc_cost_sgm_ng_host has reused the memory since).  A level whose environment and size leave a
+ * single kernel reports that kernel and zero statistics. */
+const char* fsgm_ng_auto_matcher(int32_t width, int32_t height, int32_t D, int32_t frames, uint64_t list_sum, uint64_t sample_pixels,
+                                 uint32_t flags);
+uint64_t    fsgm_ng_sample_pixels(uint64_t pixels);
+fsgm_status fsgm_ng_last_decision(int32_t device, const char** matcher, uint64_t* list_sum, uint64_t* sample_pixels, uint32_t* flags);
+
 /* ------------------------------------------------------------------------------------------
  * calc_cost_sgm_ng  (calc_cost_sgm_ng.cpp:484-526, called from ng_sgm.m:20; prhs[2..5] ignored)
  * ------------------------------------------------------------------------------------------ */

@@ -226,3 +226,159 @@ def test_ng_batches_match_single_calls(gpu_lib, oracle):
     for (gmc, gfl), (mc, fl) in zip(calc_cost_sgm_ng_batch(frames, 6, 32), want):
         np.testing.assert_array_equal(gmc, mc)
         np.testing.assert_array_equal(gfl, fl)
+
+
+# ---- which matcher ran (fsgm_ng_last_decision): every form gives the same results, so only this diagnostic can tell ----
+COMPACT_NAMES = ("compact16", "compact32", "compact64")
+
+
+def _kept(Cc):
+    """per pixel, the number of distinct (vector, cost) entries in the oracle's candidate volume: the list the matchers stage"""
+    k = (Cc["mvx"].astype(np.int64) << 40) ^ ((Cc["mvy"].astype(np.int64) & 0xFFFFFFFF) << 8) ^ Cc["cost"].astype(np.int64)
+    k = np.sort(k.reshape(-1, k.shape[-1]), axis=1)
+    return 1 + (np.diff(k, axis=1) != 0).sum(axis=1)
+
+
+def _decision(W, H, D, frames):
+    """The device and the host apply one rule to the same numbers: the name of the choice word is what auto_matcher answers
+    for the statistics the level left behind."""
+    from fsgm_amd import ng
+    name, s, n, flags = ng.last_decision()
+    assert name == ng.auto_matcher(W, H, D, frames, s, n, flags), (name, s, n, flags)
+    if n:
+        assert n == ng.sample_pixels(W * H * frames)
+    return name, s, n, flags
+
+
+def _ng_frames(oracle, W, H, n, kind, amp, r=1, sub=0, edit=None):
+    frames, want = [], []
+    for i in range(n):
+        I1, I2 = synth.image_pair(W, H, 16, seed=50 + i)
+        mv = synth.hint_map(W, H, kind, seed=60 + i, amp=amp)
+        if edit:
+            edit(mv)
+        frames.append((I1, I2, mv))
+        want.append(oracle.calc_pyd_cost_sgm_ng(I1, I2, mv, r, 2, sub, 6, 32, want_volumes=True))
+    return frames, want
+
+
+def _run_and_compare(frames, want, r=1, sub=0):
+    """one frame: S, minC and flow through the single call; more: minC and flow through the batch call"""
+    from fsgm_amd import calc_pyd_cost_sgm_ng_batch
+    if len(frames) == 1:
+        gmc, gfl, gS = calc_pyd_cost_sgm_ng(*frames[0], r, 2, sub, 6, 32, return_sum=True)
+        np.testing.assert_array_equal(gS, want[0][3])
+        got = [(gmc, gfl)]
+    else:
+        got = calc_pyd_cost_sgm_ng_batch(frames, r, 2, sub, 6, 32)
+    for i, ((gmc, gfl), w) in enumerate(zip(got, want)):
+        np.testing.assert_array_equal(gmc, w[0], err_msg=f"frame {i}")
+        np.testing.assert_array_equal(gfl, w[1], err_msg=f"frame {i}")
+
+
+def _shift_5000(mv):
+    mv += 5000.0
+
+
+# band: the mean list lengths [lo, hi) for which the rule names `expect`; an end that is no threshold of the rule (a mean cannot
+# go below it / above it) is None.  over64: the expectation rests on a list beyond 64 entries (flag bit 0) as well.
+@pytest.mark.parametrize("kind,amp,n,edit,expect,band,over64", [
+    ("zero", 1.0, 1, None, "compact64", (None, 40), False),
+    ("zero", 1.0, 3, None, "compact16", (None, 14), False),
+    ("int", 1.0, 3, None, "compact32", (14, 28), False),
+    ("int", 3.0, 3, None, "grid", (16, None), True),
+    ("int", 3.0, 1, None, "split2", (None, None), True),
+    ("zero", 1.0, 3, _shift_5000, "list", (None, 16), False),
+], ids=["zero-1", "zero-3", "int1-3", "int3-3", "int3-1", "zero+5000-3"])
+def test_calc_pyd_cost_sgm_ng_names_the_matcher_that_ran(gpu_lib, oracle, kind, amp, n, edit, expect, band, over64):
+    """Inputs whose decision is a property of the input: the mean distinct-(vector, cost) list length of the oracle's candidate
+    volume lies at least a quarter of its band's width inside the band (an open end counts as 1 or 81, the shortest and the
+    longest list there is).  61 x 37, r = 1, seeds 50 + i / 60 + i -- means found with the oracle: 'zero' 9.00 (every list 9
+    entries); 'int' amp 1: 22.50 (three frames, longest list 25); 'int' amp 3: 48.12 / 48.03 (one / three frames, longest list
+    67: flag bit 0); 'zero' + 5000: 9.00.
+
+    'zero' + 5000: no entry fits the 4-byte key (flag bit 1); the dedupe kernel finds such a pixel's repeats by comparing all
+    pairs of entries, so the lists are still the 9 distinct entries and the rule, with the compact kernels out, names "list"."""
+    W, H = 61, 37
+    frames, want = _ng_frames(oracle, W, H, n, kind, amp, edit=edit)
+    kept = np.concatenate([_kept(w[2]) for w in want])
+    mean = kept.mean()
+    lo, hi = band
+    quarter = ((hi or 81) - (lo or 1)) / 4
+    print(f"mean list length {mean:.2f}, longest {kept.max()}, band {band}")
+    assert (lo is None or mean >= lo + quarter) and (hi is None or mean <= hi - quarter), (mean, band)
+    assert (kept.max() > 64) == over64
+    _run_and_compare(frames, want)
+    name, s, npx, flags = _decision(W, H, 81, n)
+    print(f"decision {name}: sum {s} over {npx} sampled pixels, flags {flags}")
+    assert name == expect, (name, s, npx, flags)
+    assert bool(flags & 1) == over64
+
+
+def test_calc_pyd_cost_sgm_ng_wide_window_is_generic(gpu_lib, oracle):
+    W, H = 21, 15
+    frames, want = _ng_frames(oracle, W, H, 1, "even", 6.0, r=2)
+    _run_and_compare(frames, want, r=2)
+    assert _decision(W, H, 225, 1) == ("generic", 0, 0, 0)
+
+
+@pytest.mark.parametrize("env,fits,falls_back", [
+    ({"FSGM_NG_COMPACT_G": "16"}, "compact16", None),
+    ({"FSGM_NG_COMPACT_G": "32"}, "compact32", None),
+    ({"FSGM_NG_COMPACT": "0"}, None, None),
+    ({"FSGM_NG_GRID": "1"}, "grid", "grid"),
+], ids=["G16", "G32", "compact-off", "grid-only"])
+def test_calc_pyd_cost_sgm_ng_forced_matchers(gpu_lib, oracle, monkeypatch, env, fits, falls_back):
+    """A forced member is the one that runs when the lists fit it ('zero': 9 entries); 'int' amp 3 has lists beyond 64 entries
+    (flag bit 0), which no compact class holds: the level falls back to the grid kernel (three frames, mean 48) or the split
+    kernel (one frame).  Without the compact kernels: list below a mean of 16, grid from it, split for one frame."""
+    W, H = 61, 37
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    for n in (1, 3):
+        rest = "split2" if n == 1 else None
+        for kind, amp, want_name in (("zero", 1.0, fits or rest or "list"), ("int", 3.0, falls_back or rest or "grid")):
+            frames, want = _ng_frames(oracle, W, H, n, kind, amp)
+            _run_and_compare(frames, want)
+            assert _decision(W, H, 81, n)[0] == want_name, (n, kind)
+
+
+def _far_patch(mv):
+    mv[0, 5:14, 10:24] = 5000.0
+    mv[1, 20:30, 30:50] = -5000.0
+    mv[0, 25:33, 3:12] = -4999.0
+
+
+def _key_edge(mv):
+    mv[0, 8:20, 12:16], mv[0, 8:20, 16:20], mv[0, 8:20, 20:24], mv[0, 8:20, 24:28] = 4094.0, 4095.0, 4096.0, 4097.0
+    mv[1, 22:30, 40:44], mv[1, 22:30, 44:48], mv[1, 22:30, 48:52], mv[1, 22:30, 52:56] = -4094.0, -4095.0, -4096.0, -4097.0
+
+
+@pytest.mark.parametrize("n", (1, 8))
+@pytest.mark.parametrize("edit", (_far_patch, _key_edge), ids=["patch-5000", "edge-4095"])
+def test_calc_pyd_cost_sgm_ng_keys_beyond_four_bytes(gpu_lib, oracle, monkeypatch, edit, n):
+    """Motion vectors in 4096 <= |v| < 0x3FF0: the 4-byte keys do not hold them (flag bit 1) but the packed matchers still do, so
+    the level goes on with 12-byte entries read from C, S zeroed behind the keys and a matcher that is never a compact one -- by
+    default and with a compact class forced.  'int' hints of amplitude 2 around the far patches."""
+    W, H = 61, 37
+    frames, want = _ng_frames(oracle, W, H, n, "int", 2.0, sub=1, edit=edit)
+    for g in (None, "16"):
+        if g:
+            monkeypatch.setenv("FSGM_NG_COMPACT_G", g)
+        _run_and_compare(frames, want, sub=1)
+        name, _, _, flags = _decision(W, H, 81, n)
+        assert name not in COMPACT_NAMES and name == ("split2" if n == 1 else "grid"), (g, name)
+        assert flags & 2, (g, flags)
+
+
+def test_calc_pyd_cost_sgm_ng_batch_decides_anew_every_run(gpu_lib, oracle):
+    """The choice word is reset with the statistics: one process runs a batch of short lists, one of long lists and the first
+    again, each twice, and every run decides and computes the same."""
+    W, H = 61, 37
+    short, long_ = _ng_frames(oracle, W, H, 3, "zero", 1.0), _ng_frames(oracle, W, H, 3, "int", 3.0)
+    seen = []
+    for frames, want in (short, short, long_, long_, short, short):
+        _run_and_compare(frames, want)
+        seen.append(_decision(W, H, 81, 3))
+    assert seen[0] == seen[1] == seen[4] == seen[5] and seen[2] == seen[3]
+    assert (seen[0][0], seen[2][0]) == ("compact16", "grid")
