@@ -151,6 +151,11 @@ const char* fsgm_ng_auto_matcher(int32_t width, int32_t height, int32_t D, int32
     return ng_auto_matcher(width, height, D, frames, list_sum, sample_pixels, flags);
 }
 
+uint64_t fsgm_ng_auto_matcher_lds(int32_t width, int32_t height, int32_t D, int32_t frames) {
+    if (width < 1 || height < 1 || D < 1 || D > 256 || frames < 1) return 0;   // (256 / D lines a workgroup)
+    return ng_auto_matcher_lds(width, height, D, frames);
+}
+
 uint64_t fsgm_ng_sample_pixels(uint64_t pixels) { return ng_sample_pixels(pixels); }
 
 fsgm_status fsgm_ng_last_decision(int32_t device, const char** matcher, uint64_t* list_sum, uint64_t* sample_pixels, uint32_t* flags) {

@@ -142,20 +142,25 @@ __host__ __device__ inline unsigned long long ng_sample_pixels(unsigned long lon
 // range, mean length below 40; its class by the mean length for batches (throughput: more lines a wave), 64 lanes for one or two
 // frames (their long lines are serial chains: one line a wave is the shortest step); a forced class still steps aside for lists
 // it cannot hold.  Otherwise grid from a mean length of 16 (it costs the same at any length), list below it.
+constexpr int NG_GRID_MIN_K = 16;   // (also ng_matcher_set: with fewer candidates than this the grid kernel is no member)
 __host__ __device__ inline uint32_t ng_choose(const NgMatcherSet& ms, int frames, unsigned long long sum, unsigned long long npix, uint32_t flags) {
-    constexpr unsigned long long NG_COMPACT_MAX_K = 40, NG_GRID_MIN_K = 16;
+    constexpr unsigned long long NG_COMPACT_MAX_K = 40;
     if (ms.compact && (flags & 3u) == 0u && sum < NG_COMPACT_MAX_K * npix) {
         if (ms.compact_g) return ms.compact_g == 16 ? NG_COMPACT16 : ms.compact_g == 32 ? NG_COMPACT32 : NG_COMPACT64;
         return frames <= 2 ? NG_COMPACT64 : sum < 14 * npix ? NG_COMPACT16 : sum < 28 * npix ? NG_COMPACT32 : NG_COMPACT64;
     }
     if (ms.grid_only) return NG_GRID;
-    if (ms.grid) return sum >= NG_GRID_MIN_K * npix ? NG_GRID : NG_LIST;
+    if (ms.grid) return sum >= (unsigned long long)NG_GRID_MIN_K * npix ? NG_GRID : NG_LIST;
     return ms.compact ? NG_REST : NG_ANY;
 }
 // "compact16" / "compact32" / "compact64", "grid", "list", "split2" .. "split4", "lines", "generic": the kernel behind an id of this set
 const char* ng_matcher_name(const NgMatcherSet& ms, uint32_t id);
 // what the rule answers for a level of this shape under the current FSGM_NG_* environment: no device needed
 const char* ng_auto_matcher(int W, int H, int D, int frames, unsigned long long sum, unsigned long long npix, uint32_t flags);
+
+// the largest dynamic LDS request, in bytes, among the kernels such a level launches under the current environment (no device
+// needed); ng_level_enqueue returns hipErrorInvalidConfiguration, with nothing queued, for a level whose request exceeds 64 KiB
+size_t ng_auto_matcher_lds(int W, int H, int D, int frames);
 
 // Queues the level on `st`: census of both images, candidate costs, repeat removal, matcher, WTA and, when asked, the census
 // sub-pixel step.  Reads the A/B switches and decides the 4-byte entries.  With D <= 128 the matchers leave

@@ -7,6 +7,7 @@
 #include "epi_kernels.h"
 #include "fsgm_device.h"
 #include <stdlib.h>
+#include <algorithm>
 
 #ifndef FSGM_NG_PRIO
 #define FSGM_NG_PRIO 1
@@ -1743,10 +1744,14 @@ static NgMatcherSet ng_matcher_set(int W, int H, int D, int frames, const NgSwit
     // 1242x375, 3-level pyramid: 9.64 / 7.34 / 7.98 / 7.66 ms with 1 / 2 / 3 / 4 parts
     if (frames <= 2 && sw.split >= 2 && sw.split <= 4) ms.parts = sw.split;
     if (!sw.dedupe) return ms;                                // the matchers stage every candidate: no tables, no statistics
-    ms.grid_only = sw.grid == 1;
     // The grid form of the matcher costs the same at any list length, the list form grows with it: lists of a few
-    // entries (nearly constant hint maps) are faster walked, anything richer is faster looked up.
-    ms.grid = ms.grid_only || (sw.grid != 0 && ms.parts == 1);
+    // entries (nearly constant hint maps) are faster walked, anything richer is faster looked up.  The rule names it from a
+    // mean list length of NG_GRID_MIN_K only, and no list is longer than D: below that D it is no member at all -- not even as
+    // the only one (FSGM_NG_GRID=1 then leaves the set as it is without the switch) -- and its boxes are not made.  (With
+    // D = 9 it would also advance 28 lines a workgroup on 28 sets of grids: 280 672 bytes of LDS, more than a workgroup has.)
+    const bool grid_fits = D >= NG_GRID_MIN_K;
+    ms.grid_only = sw.grid == 1 && grid_fits;
+    ms.grid = ms.grid_only || (sw.grid != 0 && ms.parts == 1 && grid_fits);
     ms.compact = sw.compact != 0 && !ms.grid_only && (long long)W * H * D < (1LL << 30) && (long long)W * H < (1LL << 23);
     if (ms.compact && (sw.compact_g == 16 || sw.compact_g == 32 || sw.compact_g == 64)) ms.compact_g = sw.compact_g;
     return ms;
@@ -1788,6 +1793,28 @@ static void launch_ng_cost(hipStream_t st, const NgCostArgs& a, int frames, cons
     hipLaunchKernelGGL(ng_cost_kernel, grid, dim3(256), 0, st, a);
 }
 
+// Dynamic LDS of the members that size theirs at launch (256 / D lines a workgroup), in bytes
+static size_t ng_lines_lds(int D) { const size_t lpb = 256 / D, Dp = (D + 3) & ~3; return (lpb * 8 * Dp + lpb * 8) * sizeof(uint32_t); }
+static size_t ng_grid_lds(int D) {
+    const size_t lpb = 256 / D, Dp = (D + 3) & ~3;
+    return (lpb * 8 * Dp + lpb * 6 * NG_GCELLS + lpb * 8 + 2 * lpb) * sizeof(uint32_t);
+}
+static size_t ng_split_lds(int D, int parts) {
+    const size_t lpb = 256 / D, Dp = (D + 3) & ~3;
+    return (lpb * (10 * Dp + 8) + (size_t)(parts - 1) * lpb * Dp * 2) * sizeof(uint32_t);
+}
+// the largest request of the set's members: what launch_ng_aggregate will ask for.  No kernel of this file raises its limit
+// (hipFuncSetAttribute), so a request above NG_MAX_DYNAMIC_LDS fails its launch: ng_level_enqueue refuses such a level first
+constexpr size_t NG_MAX_DYNAMIC_LDS = 64 * 1024;
+static size_t ng_matcher_set_lds(const NgMatcherSet& ms, int D) {
+    if (ms.plain) return 0;
+    size_t lds = 0;
+    if (ms.grid) lds = ng_grid_lds(D);
+    if (!ms.grid_only) lds = std::max(lds, ms.parts > 1 ? ng_split_lds(D, ms.parts) : ng_lines_lds(D));
+    return lds;
+}
+size_t ng_auto_matcher_lds(int W, int H, int D, int frames) { return ng_matcher_set_lds(ng_matcher_set(W, H, D, frames, ng_read_switches()), D); }
+
 static void launch_ng_aggregate(hipStream_t st, NgAggArgs a, int frames, const NgMatcherSet& ms, bool dedupe) {
     // slots: 0 along x, 1 along y, 2/3 their point mirrors (pass 1)
     int acc = 0;
@@ -1802,7 +1829,7 @@ static void launch_ng_aggregate(hipStream_t st, NgAggArgs a, int frames, const N
         return;
     }
     if (!dedupe) { a.dd = nullptr; a.dk = nullptr; a.dbox = nullptr; a.ck = nullptr; a.cm = nullptr; }   // stage every candidate
-    const int lpb = 256 / a.D, Dp = (a.D + 3) & ~3;
+    const int lpb = 256 / a.D;
     // long lines first: with few frames their blocks decide when the launch ends
     const int ord_x[4] = {0, 2, 1, 3}, ord_y[4] = {1, 3, 0, 2};
     // Every member of the set is launched; where the set leaves a choice, the ones kstat's choice word does not name return at once.
@@ -1832,20 +1859,20 @@ static void launch_ng_aggregate(hipStream_t st, NgAggArgs a, int frames, const N
     }
     a.blk_begin[4] = acc;
     if (ms.grid) {
-        const size_t lds = ((size_t)lpb * 8 * Dp + (size_t)lpb * 6 * NG_GCELLS + lpb * 8 + 2 * lpb) * sizeof(uint32_t);
+        const size_t lds = ng_grid_lds(a.D);
         a.me = ms.grid_only ? NG_ANY : NG_GRID;
         hipLaunchKernelGGL(ng_agg_grid_kernel, dim3(acc, frames), dim3(256), lds, st, a);
         if (ms.grid_only) return;
     }
     a.me = ms.grid ? NG_LIST : ms.compact ? NG_REST : NG_ANY;
     if (ms.parts > 1) {
-        const size_t lds = ((size_t)lpb * (10 * Dp + 8) + (size_t)(ms.parts - 1) * lpb * Dp * 2) * sizeof(uint32_t);
+        const size_t lds = ng_split_lds(a.D, ms.parts);
         if (ms.parts == 2)      hipLaunchKernelGGL(ng_agg_split_kernel<2>, dim3(acc, frames), dim3(512), lds, st, a);
         else if (ms.parts == 3) hipLaunchKernelGGL(ng_agg_split_kernel<3>, dim3(acc, frames), dim3(768), lds, st, a);
         else                    hipLaunchKernelGGL(ng_agg_split_kernel<4>, dim3(acc, frames), dim3(1024), lds, st, a);
         return;
     }
-    const size_t lds = ((size_t)lpb * 8 * Dp + lpb * 8) * sizeof(uint32_t);
+    const size_t lds = ng_lines_lds(a.D);
     hipLaunchKernelGGL(ng_agg_lines_kernel, dim3(acc, frames), dim3(256), lds, st, a);
 }
 
@@ -1963,6 +1990,7 @@ hipError_t ng_level_enqueue(hipStream_t st, const NgLevelBufs& b, const NgLevel&
     const int W = lv.W, H = lv.H, D = 9 * (2 * lv.r + 1) * (2 * lv.r + 1);
     const NgMatcherSet ms = ng_matcher_set(W, H, D, frames, sw);
     if (used) *used = ms;
+    if (ng_matcher_set_lds(ms, D) > NG_MAX_DYNAMIC_LDS) return hipErrorInvalidConfiguration;   // before anything is queued: no launch fails mid-sequence
     // 4-byte candidate entries (the 3x3 hint kernel's sizes, D = 81): the keys live in S's memory until the matchers need S
     const bool k4 = sw.k4 && sw.cost_hint && sw.dedupe && lv.r == 1 && lv.rAgg == 1 && D <= 128;
     hipError_t e;

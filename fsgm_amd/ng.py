@@ -46,6 +46,8 @@ def _bind(lib):
     lib.fsgm_sgm_ng_rand_draws.restype = C.c_int64
     lib.fsgm_ng_auto_matcher.argtypes = [C.c_int32] * 4 + [C.c_uint64, C.c_uint64, C.c_uint32]
     lib.fsgm_ng_auto_matcher.restype = C.c_char_p
+    lib.fsgm_ng_auto_matcher_lds.argtypes = [C.c_int32] * 4
+    lib.fsgm_ng_auto_matcher_lds.restype = C.c_uint64
     lib.fsgm_ng_sample_pixels.argtypes = [C.c_uint64]
     lib.fsgm_ng_sample_pixels.restype = C.c_uint64
     lib.fsgm_ng_last_decision.argtypes = [C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
@@ -99,6 +101,14 @@ def auto_matcher(width, height, D, frames, list_sum, sample_pixels, flags=0):
     lib = _lib.load()
     _bind(lib)
     return lib.fsgm_ng_auto_matcher(int(width), int(height), int(D), int(frames), int(list_sum), int(sample_pixels), int(flags)).decode()
+
+
+def auto_matcher_lds(width, height, D, frames):
+    """The largest dynamic LDS request, in bytes, among the aggregation kernels a level of this shape launches under the current
+    FSGM_NG_* environment (fsgm_ng_auto_matcher_lds): no device needed.  Above 64 KiB the level is refused before anything is queued."""
+    lib = _lib.load()
+    _bind(lib)
+    return int(lib.fsgm_ng_auto_matcher_lds(int(width), int(height), int(D), int(frames)))
 
 
 def last_decision(device=0):

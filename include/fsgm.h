@@ -674,12 +674,15 @@ fsgm_status fsgm_calc_pyd_cost_sgm_ng_batch_host(int32_t n_frames, const fsgm_ng
  * count (fsgm_ng_sample_pixels(width * height * frames) for a real level) and the flags: "compact16" / "compact32" / "compact64",
  * "grid", "list", "split2" .. "split4", "lines" or "generic"; "" for a size below 1.  A pure function of its arguments and the
  * environment: no device is touched.
+ * fsgm_ng_auto_matcher_lds: the largest dynamic LDS request, in bytes, among the kernels such a level launches (0 for a size
+ * below 1).  A level whose request exceeds 64 KiB is refused before anything is queued.  No device is touched.
  * fsgm_ng_last_decision: the name of the kernel that ran and the three statistics of the most recent level that
  * fsgm_calc_pyd_cost_sgm_ng_host / _batch_host ran on `device` (read from that call's scratch memory; FSGM_ERR_INVALID when
  * there is none, or when fsgm_calc_cost_sgm_ng_host has reused the memory since).  A level whose environment and size leave a
  * single kernel reports that kernel and zero statistics. */
 const char* fsgm_ng_auto_matcher(int32_t width, int32_t height, int32_t D, int32_t frames, uint64_t list_sum, uint64_t sample_pixels,
                                  uint32_t flags);
+uint64_t    fsgm_ng_auto_matcher_lds(int32_t width, int32_t height, int32_t D, int32_t frames);
 uint64_t    fsgm_ng_sample_pixels(uint64_t pixels);
 fsgm_status fsgm_ng_last_decision(int32_t device, const char** matcher, uint64_t* list_sum, uint64_t* sample_pixels, uint32_t* flags);
 

@@ -279,8 +279,6 @@ def test_pyramidal_sgm_ng_random_configs(gpu_lib, oracle, seed):
     np.testing.assert_array_equal(flow, want[-1], err_msg=cfg)
     if seed % 4 == 1:
         B = int(r.randint(2, 5))
-        if o["halfSearchWinSize"] == 0:                          # 3+ frames with 9 candidates: the open fault pinned by test_ng_batch_half0
-            B = min(B, 2)
         pairs = [(I0, I1)] + [E.image_pair(r, W, H, ch, seed=seed * 10 + f) for f in range(1, B)]
         with NgPyramidPlan(W, H, ch, numPyd, batch=B, **o) as plan:
             for f, (a, b) in enumerate(pairs):
@@ -298,16 +296,9 @@ def test_pyramidal_sgm_ng_random_configs(gpu_lib, oracle, seed):
         np.testing.assert_array_equal(_n(dminC), minC, err_msg=cfg + " torch op")
 
 
-# Open fault, left for its own change (the aggregation launch of the ng core): with 3+ frames launch_ng_aggregate turns the split
-# matcher off (ng_kernels.hip, nparts = 1) and launches ng_agg_grid_kernel, whose dynamic LDS is
-# (lpb * 8 * Dp + lpb * 6 * NG_GCELLS + lpb * 8 + 2 * lpb) * 4 bytes.  halfSearchWinSize 0 gives D = 9 candidates, lpb = 28, Dp = 12:
-# 280 672 bytes, above the 160 KiB a gfx950 workgroup may have, so the launch fails with "invalid argument".  One or two frames take
-# the split matcher; halfSearchWinSize >= 1 (D >= 81) needs at most ~37 KB.
-_NG_LDS_FAULT = pytest.mark.xfail(strict=True, raises=fsgm_amd.FsgmError,
-                                  reason="ng_agg_grid_kernel asks for 280 672 B of LDS with 9 candidates and 3+ frames")
-
-
-@pytest.mark.parametrize("B", [1, 2, pytest.param(3, marks=_NG_LDS_FAULT), pytest.param(4, marks=_NG_LDS_FAULT)])
+# 3+ frames of 9 candidates: the grid kernel, which would ask for 280 672 bytes of LDS there (28 lines a workgroup), is no member of
+# the matcher set below 16 candidates (ng_matcher_set); tests/test_gpu_ng_forms.py runs every form at this window
+@pytest.mark.parametrize("B", [1, 2, 3, 4])
 def test_ng_batch_half0(gpu_lib, oracle, B):
     """halfSearchWinSize 0 on a batch of B frames, through NgPyramidPlan and the batched single-level call, against the oracle."""
     r = E.rng(4000 + B)

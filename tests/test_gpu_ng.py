@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 from fsgm_amd import synth, calc_pyd_cost_sgm_ng, calc_cost_sgm_ng
+from tests.ng_helpers import COMPACT_NAMES, decision as _decision, kept as _kept, ng_frames as _ng_frames, run_and_compare as _run_and_compare
 
 pytestmark = pytest.mark.gpu
 
@@ -229,53 +230,7 @@ def test_ng_batches_match_single_calls(gpu_lib, oracle):
 
 
 # ---- which matcher ran (fsgm_ng_last_decision): every form gives the same results, so only this diagnostic can tell ----
-COMPACT_NAMES = ("compact16", "compact32", "compact64")
-
-
-def _kept(Cc):
-    """per pixel, the number of distinct (vector, cost) entries in the oracle's candidate volume: the list the matchers stage"""
-    k = (Cc["mvx"].astype(np.int64) << 40) ^ ((Cc["mvy"].astype(np.int64) & 0xFFFFFFFF) << 8) ^ Cc["cost"].astype(np.int64)
-    k = np.sort(k.reshape(-1, k.shape[-1]), axis=1)
-    return 1 + (np.diff(k, axis=1) != 0).sum(axis=1)
-
-
-def _decision(W, H, D, frames):
-    """The device and the host apply one rule to the same numbers: the name of the choice word is what auto_matcher answers
-    for the statistics the level left behind."""
-    from fsgm_amd import ng
-    name, s, n, flags = ng.last_decision()
-    assert name == ng.auto_matcher(W, H, D, frames, s, n, flags), (name, s, n, flags)
-    if n:
-        assert n == ng.sample_pixels(W * H * frames)
-    return name, s, n, flags
-
-
-def _ng_frames(oracle, W, H, n, kind, amp, r=1, sub=0, edit=None):
-    frames, want = [], []
-    for i in range(n):
-        I1, I2 = synth.image_pair(W, H, 16, seed=50 + i)
-        mv = synth.hint_map(W, H, kind, seed=60 + i, amp=amp)
-        if edit:
-            edit(mv)
-        frames.append((I1, I2, mv))
-        want.append(oracle.calc_pyd_cost_sgm_ng(I1, I2, mv, r, 2, sub, 6, 32, want_volumes=True))
-    return frames, want
-
-
-def _run_and_compare(frames, want, r=1, sub=0):
-    """one frame: S, minC and flow through the single call; more: minC and flow through the batch call"""
-    from fsgm_amd import calc_pyd_cost_sgm_ng_batch
-    if len(frames) == 1:
-        gmc, gfl, gS = calc_pyd_cost_sgm_ng(*frames[0], r, 2, sub, 6, 32, return_sum=True)
-        np.testing.assert_array_equal(gS, want[0][3])
-        got = [(gmc, gfl)]
-    else:
-        got = calc_pyd_cost_sgm_ng_batch(frames, r, 2, sub, 6, 32)
-    for i, ((gmc, gfl), w) in enumerate(zip(got, want)):
-        np.testing.assert_array_equal(gmc, w[0], err_msg=f"frame {i}")
-        np.testing.assert_array_equal(gfl, w[1], err_msg=f"frame {i}")
-
-
+# (the helpers are shared with test_gpu_ng_forms.py: tests/ng_helpers.py)
 def _shift_5000(mv):
     mv += 5000.0
 

@@ -34,10 +34,6 @@ def _same(got, want, names, tag=""):
         np.testing.assert_array_equal(g, w, err_msg=f"{n} {tag}")
 
 
-def _launches_grid_kernel(form):
-    return form.get("FSGM_NG_GRID") == "1" or form.get("FSGM_NG_SPLIT") == "0"
-
-
 def _set_form(monkeypatch, form):
     for k in _NG_VARS:
         monkeypatch.delenv(k, raising=False)
@@ -79,23 +75,15 @@ def _form_id(form):
 
 
 def _ng_pairs():
-    """Every (fixture case, forced form) pair but the halfSearchWinSize-0 case under the forms that launch ng_agg_grid_kernel:
-    with 9 candidates that launch asks for more LDS than a workgroup has -- the open fault that
-    tests/test_gpu_edge_sweeps.py::test_ng_batch_half0 pins with a strict xfail and that has its own change.  The pairs come back
-    by themselves once halfSearchWinSize 0 can take that kernel: delete the condition then."""
-    pairs = []
-    for name, i in G.ids("calc_pyd_cost_sgm_ng"):
-        half = int(G.case(name, i)["args"][0])
-        for form in NG_FORMS:
-            if half == 0 and _launches_grid_kernel(form):
-                continue
-            pairs.append(pytest.param(name, i, form, id=f"{i}-{_form_id(form)}"))
-    return pairs
+    """Every (fixture case, forced form) pair.  The halfSearchWinSize-0 case runs under every form too: with 9 candidates the grid
+    kernel is no member of the matcher set (ng_matcher_set), so FSGM_NG_GRID=1 and FSGM_NG_SPLIT=0 run the compact kernel there
+    (tests/test_gpu_ng_forms.py names the kernel of every form at that window)."""
+    return [pytest.param(name, i, form, id=f"{i}-{_form_id(form)}") for name, i in G.ids("calc_pyd_cost_sgm_ng") for form in NG_FORMS]
 
 
 @pytest.mark.parametrize("name,i,form", _ng_pairs())
 def test_calc_pyd_cost_sgm_ng(gpu_lib, monkeypatch, name, i, form):
-    """Every fixture case under every forced matcher form (see _ng_pairs for the two pairs left out)."""
+    """Every fixture case under every forced matcher form."""
     c = G.case(name, i)
     _set_form(monkeypatch, form)
     _same(calc_pyd_cost_sgm_ng(c["I1"], c["I2"], c["preMv"], *G.ints(c["args"])), c["outs"], ("minC", "flow"))

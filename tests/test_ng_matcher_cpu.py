@@ -117,3 +117,88 @@ def test_no_compact_kernel_beyond_32_bit_offsets(monkeypatch, frames):
     monkeypatch.delenv("FSGM_NG_COMPACT_G")
     assert pick(frames, 9, w=4096, h=2048) == ("list" if frames > 2 else "split2")
     assert pick(frames, 9, w=4096, h=2047) == pick(frames, 9, w=2896, h=2896) == ("compact16" if frames > 2 else "compact64")
+
+
+# ---- 9 candidates (halfSearchWinSize 0): no list is longer than 9 entries, so a mean beyond 9 cannot occur; the rule is asked anyway
+MEANS9 = (1, 5, 9)
+
+
+def test_nine_candidates_never_name_the_grid_kernel(monkeypatch):
+    """Below 16 candidates (the mean list length from which the rule names it) the grid kernel is no member of the set: with 28
+    lines a workgroup it would ask for 280 672 bytes of LDS.  FSGM_NG_GRID=1 there leaves the set as it is without the switch."""
+    for grid in (None, "1", "0"):
+        if grid:
+            monkeypatch.setenv("FSGM_NG_GRID", grid)
+        for m in MEANS9 + (16, 50):                           # (means no level of 9 candidates can have: still no grid kernel)
+            for flags in (0, 1, 2):
+                for frames in (1, 2, 3, 8):
+                    assert pick(frames, m, flags, d=9) not in ("grid", "list"), (grid, m, flags, frames)
+        for m in MEANS9:
+            assert pick(1, m, d=9) == pick(2, m, d=9) == "compact64"
+            assert pick(3, m, d=9) == pick(8, m, d=9) == "compact16"
+            assert pick(1, m, 2, d=9) == "split2" and pick(3, m, 2, d=9) == "lines"
+    monkeypatch.setenv("FSGM_NG_GRID", "1")
+    assert pick(3, 20, d=15) == "compact32" and pick(3, 20, d=16) == "grid"    # the gate is D < 16
+
+
+def test_nine_candidates_switches(monkeypatch):
+    for g in (16, 32, 64):
+        monkeypatch.setenv("FSGM_NG_COMPACT_G", str(g))
+        assert all(pick(frames, m, d=9) == f"compact{g}" for frames in (1, 3) for m in MEANS9)
+    monkeypatch.delenv("FSGM_NG_COMPACT_G")
+    monkeypatch.setenv("FSGM_NG_COMPACT", "0")
+    for m in MEANS9:
+        assert pick(3, m, d=9) == "lines" and pick(1, m, d=9) == pick(2, m, d=9) == "split2"
+    for grid in ("0", "1"):
+        monkeypatch.setenv("FSGM_NG_GRID", grid)
+        assert pick(3, 9, d=9) == "lines" and pick(1, 9, d=9) == "split2"
+    monkeypatch.delenv("FSGM_NG_GRID")
+    for parts, name in (("0", "lines"), ("1", "lines"), ("2", "split2"), ("3", "split3"), ("4", "split4"), ("5", "lines")):
+        monkeypatch.setenv("FSGM_NG_SPLIT", parts)
+        assert pick(1, 9, d=9) == pick(2, 9, d=9) == name
+        assert pick(3, 9, d=9) == "lines"
+    monkeypatch.delenv("FSGM_NG_SPLIT")
+    monkeypatch.delenv("FSGM_NG_COMPACT")
+    monkeypatch.setenv("FSGM_NG_DEDUPE", "0")
+    assert all(pick(1, m, d=9) == "split2" and pick(3, m, d=9) == "lines" for m in MEANS9)
+
+
+def test_dynamic_lds_of_every_set_fits_a_workgroup(monkeypatch):
+    """The lines, grid and split kernels size their LDS at launch (256 / D lines a workgroup) and none raises its limit: 64 KiB.
+    ng_level_enqueue refuses a level whose set asks for more before anything is queued; with the candidate counts the entry points
+    accept below 128 (9 and 81) no set does, under any switch.  The grid kernel at D = 9 would: 280 672 bytes, the request that
+    failed every batch of three frames before the kernel left the set there; at D = 16, the smallest D it is a member at, 16 lines
+    ask for (16 * 8 * 16 + 16 * 6 * 400 + 16 * 8 + 2 * 16) * 4 = 162 432 bytes -- such a level would be refused, not launched."""
+    LIMIT = 64 * 1024
+    for d in (9, 81):
+        for env in ({}, {"COMPACT": "0"}, {"GRID": "0"}, {"GRID": "1"}, {"DEDUPE": "0"}, {"SPLIT": "0"}, {"SPLIT": "3"}, {"SPLIT": "4"}):
+            for k, v in env.items():
+                monkeypatch.setenv("FSGM_NG_" + k, v)
+            for frames in (1, 2, 3, 8):
+                assert 0 < ng.auto_matcher_lds(W, H, d, frames) <= LIMIT, (d, env, frames)
+            for k in env:
+                monkeypatch.delenv("FSGM_NG_" + k)
+    assert ng.auto_matcher_lds(W, H, 9, 3) == (28 * 8 * 12 + 28 * 8) * 4                       # the lines kernel alone
+    assert ng.auto_matcher_lds(W, H, 81, 3) == (3 * 8 * 84 + 3 * 6 * 400 + 3 * 8 + 2 * 3) * 4   # the grid kernel: 36 984 bytes
+    assert ng.auto_matcher_lds(W, H, 81, 1) == (3 * (10 * 84 + 8) + 3 * 84 * 2) * 4             # two-way split
+    monkeypatch.setenv("FSGM_NG_SPLIT", "4")
+    assert ng.auto_matcher_lds(W, H, 9, 1) == (28 * (10 * 12 + 8) + 3 * 28 * 12 * 2) * 4
+    monkeypatch.delenv("FSGM_NG_SPLIT")
+    assert ng.auto_matcher_lds(W, H, 16, 3) == 162432 > LIMIT
+    assert ng.auto_matcher_lds(W, H, 225, 3) == ng.auto_matcher_lds(W, H, 441, 1) == 0         # ng_agg_kernel: static LDS only
+
+
+def test_729_candidates_are_refused_without_a_device():
+    """halfSearchWinSize 4 is beyond FSGM_NG_MAX_D (512): the single call, the batch call and the plan answer FSGM_ERR_UNSUPPORTED
+    from their argument checks, before a device is looked for (this test runs without one)."""
+    import numpy as np
+    import fsgm_amd
+    from fsgm_amd._lib import FsgmError
+    I = np.zeros((15, 21), np.uint8)
+    mv = np.zeros((2, 15, 21))
+    for call in (lambda: fsgm_amd.calc_pyd_cost_sgm_ng(I, I, mv, 4, 2, 0, 6, 32),
+                 lambda: fsgm_amd.calc_pyd_cost_sgm_ng_batch([(I, I, mv)] * 3, 4, 2, 0, 6, 32),
+                 lambda: fsgm_amd.NgPyramidPlan(21, 15, 1, 2, batch=3, halfSearchWinSize=4)):
+        with pytest.raises(FsgmError) as ei:
+            call()
+        assert ei.value.status == 4 and "729" in str(ei.value)

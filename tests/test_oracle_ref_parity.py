@@ -115,6 +115,38 @@ def test_calc_pyd_cost_sgm_ng_oracle_equals_reference(oracle, build):
     assert printed.startswith(f"width: {W}, height: {H}, dMax: {9 * (2 * a[3] + 1) ** 2}, ")
 
 
+# The frames of tests/test_gpu_ng_forms.py at 9 and at 441 candidates (halfSearchWinSize 0 and 3): the windows the GPU forms are
+# compared with the oracle at, the oracle itself against the reference's compiled code
+def _ng_window_case(W, H, i, kind, amp, r, sub, P1, P2, oracle, mv_shape=None):
+    from tests.ng_helpers import ng_frame
+    a = ng_frame(W, H, i, kind, amp, mv_shape=mv_shape) + (r, 2, sub, P1, P2)
+    (ref, printed), want = _both(lambda: pyref.call_calc_pyd_cost_sgm_ng(*a), lambda: oracle.calc_pyd_cost_sgm_ng(*a))
+    _same(ref, want, (f"minC {W}x{H} frame {i} {kind} r{r} sub{sub} P{P1},{P2}", "flow"))
+    assert printed.startswith(f"width: {W}, height: {H}, dMax: {9 * (2 * r + 1) ** 2}, ")
+
+
+@pytest.mark.parametrize("W,H", [(61, 37), (29, 28), (28, 57), (27, 5), (1, 12), (12, 1)])
+def test_calc_pyd_cost_sgm_ng_oracle_equals_reference_at_9_candidates(oracle, W, H):
+    _need("calc_pyd_cost_sgm_ng")
+    for kind, amp in (("zero", 1.0), ("int", 2.0), ("general", 0.8)):
+        for i in range(8 if (W, H) == (61, 37) else 3):
+            for sub, P1, P2 in ((0, 6, 32), (1, 6, 32), (0, 90, 120), (1, 90, 120)):
+                _ng_window_case(W, H, i, kind, amp, 0, sub, P1, P2, oracle)
+    if (W, H) == (61, 37):
+        for mv_shape in ((50, 30), (70, 45)):
+            for i in range(3):
+                _ng_window_case(W, H, i, "general", 0.8, 0, 1, 6, 32, oracle, mv_shape=mv_shape)
+
+
+@pytest.mark.parametrize("sub", (0, 1))
+@pytest.mark.parametrize("P1,P2", ((6, 32), (90, 120)))
+def test_calc_pyd_cost_sgm_ng_oracle_equals_reference_at_441_candidates(oracle, P1, P2, sub):
+    _need("calc_pyd_cost_sgm_ng")
+    for W, H in ((21, 15), (1, 12), (12, 1)):
+        for i in range(3):
+            _ng_window_case(W, H, i, "int", 2.0, 3, sub, P1, P2, oracle)
+
+
 # ------------------------------------------------------------------------------------------------ calc_cost_sgm_ng
 OTF = R.otf_cases() + R.otf_fuzz_cases() + [R.KITTI_OTF]
 
