@@ -11,7 +11,40 @@
 using namespace fsgm;
 
 
+// the search windows the 2-D kernels accept, checked before a device is touched: the sides, then the candidate count
+// (two steps, so that fsgm_pyd_plan_create keeps its order of checks: sides, batch, count)
+static fsgm_status pyd_check_sides(int32_t rX, int32_t rY, int32_t rAgg) {
+    FSGM_REQUIRE(rX >= 0 && rY >= 0 && rAgg >= 0, "window half sizes must be >= 0");
+    if (2 * (long long)rX + 1 > FSGM_PYD_MAX_SIDE || 2 * (long long)rY + 1 > FSGM_PYD_MAX_SIDE)
+        return fail(FSGM_ERR_UNSUPPORTED, "search window side exceeds %d", FSGM_PYD_MAX_SIDE);
+    return FSGM_OK;
+}
+static fsgm_status pyd_check_count(int32_t rX, int32_t rY) {
+    const long long D = (long long)(2 * rX + 1) * (2 * rY + 1);
+    if (D > FSGM_PYD_MAX_D) return fail(FSGM_ERR_UNSUPPORTED, "search window %lld candidates exceeds %d", D, FSGM_PYD_MAX_D);
+    return FSGM_OK;
+}
+
 extern "C" {
+
+fsgm_status fsgm_pyd_launch_lds(int32_t rX, int32_t rY, int32_t rAgg, int32_t* cost_kernel, uint64_t* cost_lds, uint64_t* patch_lds,
+                                uint64_t* agg_lds, uint64_t* rows_agg_lds) {
+    FSGM_REQUIRE(cost_kernel && cost_lds && patch_lds && agg_lds && rows_agg_lds, "fsgm_pyd_launch_lds: null argument");
+    fsgm_status st = pyd_check_sides(rX, rY, rAgg);
+    if (st == FSGM_OK) st = pyd_check_count(rX, rY);
+    if (st != FSGM_OK) return st;
+    const int Sx = 2 * rX + 1, Sy = 2 * rY + 1;
+    PydCostArgs a = {};
+    a.W = 1; a.H = 1; a.rX = rX; a.rY = rY; a.rAgg = rAgg;
+    a.RS = pyd_row_stride(Sx, Sy); a.PS = Sx * a.RS;         // as fsgm_pyd_plan_create lays the volume out
+    const PydCostKernel k = pyd_cost_choice(a);
+    *cost_kernel = (int32_t)k;
+    *patch_lds = pyd_cost_patch_lds(rX, rY, rAgg);
+    *cost_lds = k == PYD_COST_ROWS ? pyd_rows_cost_lds(Sx) : k == PYD_COST_PATCH ? *patch_lds : 0;
+    *agg_lds = pyd_agg_lds(Sx, Sy);
+    *rows_agg_lds = pyd_rows_layout(Sx, Sy) ? pyd_rows_agg_lds() : 0;
+    return FSGM_OK;
+}
 
 void fsgm_pyd_plan_destroy(fsgm_pyd_plan* p) {
     if (!p) return;
@@ -32,12 +65,10 @@ fsgm_status fsgm_pyd_plan_create(fsgm_pyd_plan** out, int32_t W, int32_t H, int3
     FSGM_REQUIRE(W >= 1 && H >= 1, "width/height must be >= 1 (got %d x %d)", W, H);
     FSGM_REQUIRE(mvW >= W && mvH >= H, "preMv (%d x %d) must be at least as large as the image (%d x %d): the reference "
                  "indexes it with image coordinates (calc_pyd_cost_sgm.cpp:388-389)", mvW, mvH, W, H);
-    FSGM_REQUIRE(rX >= 0 && rY >= 0 && rAgg >= 0, "window half sizes must be >= 0");
-    if (2 * rX + 1 > FSGM_PYD_MAX_SIDE || 2 * rY + 1 > FSGM_PYD_MAX_SIDE)
-        return fail(FSGM_ERR_UNSUPPORTED, "search window side exceeds %d", FSGM_PYD_MAX_SIDE);
+    { const fsgm_status ws = pyd_check_sides(rX, rY, rAgg); if (ws != FSGM_OK) return ws; }
     FSGM_REQUIRE(batch >= 1, "batch must be >= 1");
+    { const fsgm_status ws = pyd_check_count(rX, rY); if (ws != FSGM_OK) return ws; }
     const long long D = (long long)(2 * rX + 1) * (2 * rY + 1);
-    if (D > FSGM_PYD_MAX_D) return fail(FSGM_ERR_UNSUPPORTED, "search window %lld candidates exceeds %d", D, FSGM_PYD_MAX_D);
     if ((double)W * H * D >= 2147483648.0) return fail(FSGM_ERR_UNSUPPORTED, "cost volume exceeds 2^31 voxels per frame");
     { const fsgm_status ds = use_device(device); if (ds != FSGM_OK) return ds; }
     fsgm_pyd_plan* p = new fsgm_pyd_plan;

@@ -55,6 +55,24 @@ struct PydWtaArgs {
 inline bool pyd_rows_layout(int Sx, int Sy) { return Sx <= 11 && Sy <= 11; }
 inline int  pyd_row_stride(int Sx, int Sy) { return pyd_rows_layout(Sx, Sy) ? 4 * ((Sy + 3) / 4) : Sy; }
 
+// Dynamic LDS requests, each computed in one place for the launcher and for fsgm_pyd_launch_lds (include/fsgm.h).
+// pyd_cost_patch_kernel: the (Sx+2r) x (Sy+2r) patch of image 2, the (2r+1)^2 codes of image 1 and the two sample tables;
+// the cost stage takes it while the request stays within PYD_PATCH_LDS_MAX.
+constexpr size_t PYD_PATCH_LDS_MAX = 48 * 1024;
+inline size_t pyd_cost_patch_lds(int rX, int rY, int rAgg) {
+    const size_t PX = 2 * (size_t)rX + 1 + 2 * (size_t)rAgg, PY = 2 * (size_t)rY + 1 + 2 * (size_t)rAgg, AW = 2 * (size_t)rAgg + 1;
+    return (PX * PY + AW * AW + PX + PY) * sizeof(uint32_t);
+}
+// pyd_agg_kernel: per wave (4 a workgroup) two padded grids of u32 cells and the two shift tables
+constexpr int PYD_PADW = 5;             // clamp(shifted centre) +- 2 stays inside the padded grid
+constexpr int PYD_MAXS = 64;            // max search-window side supported by the tables
+inline size_t pyd_agg_lds(int Sx, int Sy) {
+    const size_t GN = (size_t)(Sx + 2 * PYD_PADW) * (Sy + 2 * PYD_PADW);
+    return 4 * (2 * GN + 2 * PYD_MAXS) * sizeof(uint32_t);
+}
+
+enum PydCostKernel { PYD_COST_ROWS = 0, PYD_COST_PATCH = 1, PYD_COST_CANDIDATE = 2 };   // FSGM_PYD_COST_* of include/fsgm.h
+PydCostKernel pyd_cost_choice(const PydCostArgs& a);         // the kernel launch_pyd_cost takes
 void launch_pyd_cost(hipStream_t st, const PydCostArgs& a, int frames);
 // returns the number of path slots it planned (nd or 2*nd); lines_per_block = 4 (generic kernel) or 16
 // (row-packed); wide_rows: the horizontal slots of the row-packed kernel take its one-line-per-wave
@@ -67,6 +85,8 @@ void launch_pyd_wta(hipStream_t st, const PydWtaArgs& a, int frames);
 // ---- row-packed kernels (pyd_rows.hip): rows layout, no-wrap penalties ----
 bool pyd_rows_cost_ok(const PydCostArgs& a);                 // rows layout and aggregation radius <= 2
 bool pyd_rows_wta_ok(const PydWtaArgs& a);                   // rows layout and weighted sums fit u16
+size_t pyd_rows_cost_lds(int Sx);                            // dynamic LDS of pyd_rows_cost_kernel / pyd_rows_agg_kernel
+size_t pyd_rows_agg_lds();
 void launch_pyd_rows_cost(hipStream_t st, const PydCostArgs& a, int frames);
 void launch_pyd_rows_desc(hipStream_t st, const PydAggArgs& a, int frames);
 void launch_pyd_rows_aggregate(hipStream_t st, const PydAggArgs& a, int frames);

@@ -158,9 +158,6 @@ __global__ __launch_bounds__(128) void pyd_cost_patch_kernel(PydCostArgs a) {
 // large number); WRAP=true narrows every neighbour + P1 to u8 first and excludes the centre,
 // exactly like the reference, for any P1/P2.
 // =============================================================================================
-constexpr int PYD_PADW = 5;             // clamp(shifted centre) +- 2 stays inside the padded grid
-constexpr int PYD_MAXS = 64;            // max search-window side supported by the tables
-
 template <bool WRAP, int NCMAX>                            // NCMAX >= ceil(Sx*Sy / 64) candidates per lane
 __global__ __launch_bounds__(256) void pyd_agg_kernel(PydAggArgs a) {
     extern __shared__ uint32_t sDynPyd[];   // u32 cells: aligned ds_read2_b32 for the neighbourhood rows
@@ -354,15 +351,21 @@ __global__ __launch_bounds__(256) void pyd_wta_kernel(PydWtaArgs a) {
 // =============================================================================================
 // launchers
 // =============================================================================================
+PydCostKernel pyd_cost_choice(const PydCostArgs& a) {
+    if (pyd_rows_cost_ok(a)) return PYD_COST_ROWS;
+    // the normal case of the other windows: one workgroup per pixel
+    if (pyd_cost_patch_lds(a.rX, a.rY, a.rAgg) <= PYD_PATCH_LDS_MAX && (long long)a.W * a.H < 2147483647LL) return PYD_COST_PATCH;
+    return PYD_COST_CANDIDATE;
+}
+
 void launch_pyd_cost(hipStream_t st, const PydCostArgs& a, int frames) {
-    if (pyd_rows_cost_ok(a)) { launch_pyd_rows_cost(st, a, frames); return; }
-    const long long n = (long long)a.W * a.H * (2 * a.rX + 1) * (2 * a.rY + 1);
-    const int PX = 2 * a.rX + 1 + 2 * a.rAgg, PY = 2 * a.rY + 1 + 2 * a.rAgg, AW = 2 * a.rAgg + 1;
-    const size_t lds = (size_t)(PX * PY + AW * AW + PX + PY) * 4;
-    if (lds <= 48 * 1024 && (long long)a.W * a.H < 2147483647LL) {      // the normal case: one workgroup per pixel
-        hipLaunchKernelGGL(pyd_cost_patch_kernel, dim3(a.W * a.H, frames), dim3(128), lds, st, a);
+    const PydCostKernel k = pyd_cost_choice(a);
+    if (k == PYD_COST_ROWS) { launch_pyd_rows_cost(st, a, frames); return; }
+    if (k == PYD_COST_PATCH) {
+        hipLaunchKernelGGL(pyd_cost_patch_kernel, dim3(a.W * a.H, frames), dim3(128), pyd_cost_patch_lds(a.rX, a.rY, a.rAgg), st, a);
         return;
     }
+    const long long n = (long long)a.W * a.H * (2 * a.rX + 1) * (2 * a.rY + 1);
     dim3 grid((unsigned)((n + 255) / 256), frames);
     hipLaunchKernelGGL(pyd_cost_kernel, grid, dim3(256), 0, st, a);
 }
@@ -404,8 +407,7 @@ int plan_pyd_dirs(PydAggArgs& a, int diagonal, int totalPass, uint32_t weight[8]
 void launch_pyd_aggregate(hipStream_t st, const PydAggArgs& a, int frames, bool wrap) {
     if (a.ndirs == 0) return;
     dim3 grid(a.blk_begin[8], frames);
-    const int GN = (a.Sx + 2 * PYD_PADW) * (a.Sy + 2 * PYD_PADW);
-    const size_t lds = (size_t)4 * (2 * GN + 2 * PYD_MAXS) * sizeof(uint32_t);
+    const size_t lds = pyd_agg_lds(a.Sx, a.Sy);
     const int nc = (a.Sx * a.Sy + 63) / 64;
 #define FSGM_PYD_LAUNCH(NCM)                                                                        \
     do {                                                                                            \

@@ -738,14 +738,18 @@ bool pyd_rows_wta_ok(const PydWtaArgs& a) {
         else { constexpr int NW = 3; CALL; }     \
     } while (0)
 
+size_t pyd_rows_cost_lds(int Sx) { return (size_t)4 * cost_ppw(Sx) * COST_SLOT * sizeof(uint32_t); }
+size_t pyd_rows_agg_lds() { return (size_t)4 * ROWS_WAVE_BYTES; }
+
 void launch_pyd_rows_cost(hipStream_t st, const PydCostArgs& a, int frames) {
     const int Sx = 2 * a.rX + 1, per_block = 4 * cost_ppw(Sx);
     dim3 grid((unsigned)((a.W * a.H + per_block - 1) / per_block), frames);
-    const size_t lds = (size_t)4 * cost_ppw(Sx) * COST_SLOT * sizeof(uint32_t);
+    const size_t lds = pyd_rows_cost_lds(Sx);
     FSGM_ROWS_DISPATCH(a.RS / 4, hipLaunchKernelGGL((pyd_rows_cost_kernel<NW>), grid, dim3(256), lds, st, a));
 }
 
 void launch_pyd_rows_desc(hipStream_t st, const PydAggArgs& a, int frames) {
+    if (a.ndirs == 0) return;                                // totalPass 0: no path slot, and a grid of 0 x-y-z blocks is no launch
     dim3 grid((unsigned)((a.W * a.H + 255) / 256), a.ndirs, frames);
     hipLaunchKernelGGL(pyd_rows_desc_kernel, grid, dim3(256), 0, st, a);
 }
@@ -753,7 +757,7 @@ void launch_pyd_rows_desc(hipStream_t st, const PydAggArgs& a, int frames) {
 void launch_pyd_rows_aggregate(hipStream_t st, const PydAggArgs& a, int frames) {
     if (a.ndirs == 0) return;
     dim3 grid(a.blk_begin[8], frames);
-    const size_t lds = (size_t)4 * ROWS_WAVE_BYTES;
+    const size_t lds = pyd_rows_agg_lds();
     FSGM_ROWS_DISPATCH(a.RS / 4, hipLaunchKernelGGL((pyd_rows_agg_kernel<NW>), grid, dim3(256), lds, st, a));
 }
 

@@ -40,7 +40,25 @@ def _bind(lib):
     lib.fsgm_pyd_plan_download_cost.argtypes = [vp, i32, vp]
     lib.fsgm_pyd_plan_download_sum.argtypes = [vp, i32, vp]
     lib.fsgm_pyd_plan_time.argtypes = [vp, i32, i32, i32, C.POINTER(C.c_float)]
+    u64p = C.POINTER(C.c_uint64)
+    lib.fsgm_pyd_launch_lds.argtypes = [i32, i32, i32, C.POINTER(i32), u64p, u64p, u64p, u64p]
     lib._pyd_bound = True
+
+
+COST_KERNELS = ("rows", "patch", "candidate")      # FSGM_PYD_COST_ROWS / _PATCH / _CANDIDATE
+
+
+def launch_lds(rX, rY, rAgg):
+    """Which kernel the cost stage launches for search half sizes (rX, rY) and aggregation radius rAgg, and the dynamic LDS
+    bytes of the launches (fsgm_pyd_launch_lds): a dict with cost_kernel ("rows" / "patch" / "candidate"), cost_lds,
+    patch_lds, agg_lds, rows_agg_lds.  No device needed; a window the plans refuse raises FsgmError here too."""
+    lib = _lib.load()
+    _bind(lib)
+    k = C.c_int32()
+    v = [C.c_uint64() for _ in range(4)]
+    check(lib.fsgm_pyd_launch_lds(int(rX), int(rY), int(rAgg), C.byref(k), *[C.byref(x) for x in v]))
+    return dict(cost_kernel=COST_KERNELS[k.value], cost_lds=int(v[0].value), patch_lds=int(v[1].value),
+                agg_lds=int(v[2].value), rows_agg_lds=int(v[3].value))
 
 
 def _check_inputs(I1, I2, preMv):

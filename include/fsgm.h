@@ -394,6 +394,28 @@ fsgm_status fsgm_pyd_plan_download_sum(fsgm_pyd_plan* plan, int32_t frame, uint3
 fsgm_status fsgm_pyd_plan_time(fsgm_pyd_plan* plan, int32_t stages, int32_t warmup,
                                int32_t iters, float* ms_avg);
 
+/* Search windows and launches.  Every entry point on this path accepts a search window with sides 2*half+1 <= 64 (so 63 at
+ * the most) and at most 1024 candidates (31x33 = 1023 is the largest count); anything else is FSGM_ERR_UNSUPPORTED before a
+ * device is touched.
+ * fsgm_pyd_launch_lds: for such a window and an aggregation radius, which kernel the cost stage launches and the dynamic LDS
+ * bytes of the launches, computed by the expressions the launchers themselves use; the same refusals as fsgm_pyd_plan_create.
+ * No device is touched.
+ *   cost_kernel   FSGM_PYD_COST_ROWS (row-packed: windows up to 11x11 with a radius up to 2), _PATCH (one workgroup a pixel,
+ *                 while its request stays within 48 KiB) or _CANDIDATE (one thread a candidate, no LDS).  The report is that
+ *                 of a one-pixel frame: it holds for every frame below 2^30 pixels, the size up to which the row-packed kernel's
+ *                 and the patch kernel's grids are legal (larger frames take _PATCH instead of _ROWS, and _CANDIDATE from
+ *                 2^31 - 1 pixels on, which no accepted cost volume reaches)
+ *   cost_lds      the request of that launch
+ *   patch_lds     what the patch kernel would ask for, whether it runs or not
+ *   agg_lds       pyd_agg_kernel's request (any window; the only aggregation kernel for wrapping penalties or windows above 11x11)
+ *   rows_agg_lds  the row-packed aggregation kernel's request, 0 for a window it does not take */
+#define FSGM_PYD_COST_ROWS 0
+#define FSGM_PYD_COST_PATCH 1
+#define FSGM_PYD_COST_CANDIDATE 2
+fsgm_status fsgm_pyd_launch_lds(int32_t halfSearchWinSizeX, int32_t halfSearchWinSizeY, int32_t aggHalfWinSize,
+                                int32_t* cost_kernel, uint64_t* cost_lds, uint64_t* patch_lds, uint64_t* agg_lds,
+                                uint64_t* rows_agg_lds);
+
 /* ------------------------------------------------------------------------------------------
  * pyramidal_sgm  (pyramidal_sgm.m:1-77 -- the MATLAB driver around calc_pyd_cost_sgm)
  *

@@ -1,7 +1,7 @@
 """Generates tests/golden/ref_mex_<file>.npz, one per MEX file, from the REFERENCE's own compiled MEX code (oracle/_ref/ref_*.so,
 built by oracle/Makefile from the unmodified sources against the stand-in runtime oracle/refmex/; called through
 oracle/pyref.py).  Run in the build container (the reference tree is not on the GPU box), after the build:
-    python tests/golden/make_ref_mex_golden.py
+    python tests/golden/make_ref_mex_golden.py [MEX file name ...]        (no name: all four)
 Each fixture holds data only, as numeric arrays: per case i the inputs (c<i>_I1, c<i>_I2, the hint map c<i>_preMv or the epipolar
 maps c<i>_pd0 / _nd / _off, the scalar arguments in MEX order as c<i>_args) and every output the reference wrote (c<i>_out<k>);
 `n` is the number of cases.  calc_cost_sgm_ng's c<i>_args ends with the srand seed, and c<i>_rand holds the values libc rand()
@@ -39,7 +39,7 @@ def run(name, a):
     return ins, outs
 
 
-for name in pyref.NAMES:
+for name in sys.argv[1:] or pyref.NAMES:
     arrays = {}
     cases = ref_cases.golden_cases(name)
     for i, (cid, build) in enumerate(cases):

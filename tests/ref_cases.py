@@ -143,13 +143,39 @@ def epi_fuzz_cases():
 
 
 # ------------------------------------------------------------------------------------------------ calc_pyd_cost_sgm
+def window_hints(mvW, mvH, kind, seed, amp=3.0):
+    """synth.hint_map's kinds, "far" (whole numbers up to +-14), "zigzag" (x mod 2, y mod 2: +-1 from pixel to pixel) and three
+    maps for the large search windows:
+    "outside": every value beyond +-100, either sign: with a window side up to 63 and frames up to 24 pixels every sample of
+               every candidate falls outside the second image;
+    "jumpy":   levels 70 apart that change between any two pixels a path joins (x by (x + 2y) mod 4, y by (2x + y) mod 4), plus
+               a fraction: every difference along a path exceeds side + 3 in one axis at least, in either sign, so both clamps
+               of the shift tables are hit and every shifted centre is absent;
+    "steps":   x by 80 * [x mod 4 in (1, 2)], y by 80 * [y mod 4 in (1, 2)]: a path meets a step beyond any window, then a
+               pixel with the same hint as the one before (tests/test_gpu_pyd_windows.py's penalty budgets)."""
+    if kind == "far":
+        return synth.hint_map(mvW, mvH, "int", seed=seed, amp=14.0)
+    yy, xx = np.mgrid[0:mvH, 0:mvW]
+    if kind == "outside":
+        u = synth.uniform_f64(seed, (2, mvH, mvW))
+        sign = np.where(synth.uniform_f64(seed + 1, (2, mvH, mvW)) < 0.5, -1.0, 1.0)
+        return np.ascontiguousarray(sign * (100.0 + np.round(u * 80.0) / 4))
+    if kind == "jumpy":
+        lv = np.stack([(xx + 2 * yy) % 4, (2 * xx + yy) % 4]).astype(np.float64)
+        return np.ascontiguousarray(70.0 * lv + np.round(synth.uniform_f64(seed, (2, mvH, mvW)) * 8.0) / 4 - 1.0)
+    if kind == "steps":
+        return np.ascontiguousarray(80.0 * np.stack([(xx % 4 == 1) | (xx % 4 == 2), (yy % 4 == 1) | (yy % 4 == 2)]).astype(np.float64))
+    if kind == "zigzag":
+        return np.ascontiguousarray(np.stack([xx % 2, yy % 2]).astype(np.float64))
+    return synth.hint_map(mvW, mvH, kind, seed=seed, amp=amp)
+
+
 def _pyd(W, H, mvW, mvH, rX, rY, rAgg, sub, P1, P2, diag, passes, adaptive, kind, iseed, mseed, amp=3.0, grad=1, edge=False):
     def build():
         I1, I2 = _images(W, H, 16, iseed, edge)
         if grad != 1:
             I1 = (I1.astype(np.int32) * grad % 256).astype(np.uint8)              # larger gradients: adaptive P2 branch taken
-        far = kind == "far"
-        mv = synth.hint_map(mvW, mvH, "int" if far else kind, seed=mseed, amp=14.0 if far else amp)
+        mv = window_hints(mvW, mvH, kind, mseed, amp)
         return I1, I2, mv, rX, rY, rAgg, sub, P1, P2, diag, passes, adaptive
     return (f"{W}x{H}-mv{mvW}x{mvH}-r{rX}_{rY}_{rAgg}-sub{sub}-P{P1}_{P2}-d{diag}p{passes}a{adaptive}-{kind}{amp}-g{grad}-s{iseed}_{mseed}" + ("-edgeimg" if edge else ""),
             build)
@@ -184,6 +210,92 @@ def pyd_fuzz_cases():
         c.append(_pyd(g["W"], g["H"], g["mvW"], g["mvH"], g["rX"], g["rY"], g["rAgg"], g["sub"], g["P1"], g["P2"], g["diag"],
                       g["passes"], g["adaptive"], g["kind"], seed, seed, amp=g["amp"], grad=3))
     return c
+
+
+# ---- search windows from 13 to 63 candidates a side (tests/test_gpu_pyd_windows.py; the lists are shared with it)
+# half sizes (rX, rY) of 13x9, 15x17, 17x15, 17x17, 31x33, 63x15, 15x63, 63x1, 1x63, 11x13, 13x11
+WINDOWS = [(6, 4), (7, 8), (8, 7), (8, 8), (15, 16), (31, 7), (7, 31), (31, 0), (0, 31), (5, 6), (6, 5)]
+# line counts 1, 4, 5 and 7 (the generic aggregation kernel advances 4 lines a workgroup), more than one workgroup (9, 13)
+WINDOW_FRAMES = [(9, 7), (13, 5), (5, 13), (8, 4), (1, 6), (6, 1)]
+# the smallest aggregation radius at which an accepted window leaves the patch kernel, the window there with the fewest
+# candidates, and the nearest radius that still takes the patch kernel (tests/test_pyd_limits_cpu.py checks both by enumeration)
+COST_FALLBACK = (7, 30, 29)            # rX, rY, rAgg: 15x61
+COST_LAST_PATCH = (7, 30, 28)
+COST_PATCH_AT_BOUND = (20, 11, 30)     # 41x23: the patch kernel's request is 49152 bytes, the bound itself
+
+
+def window_cost_cases():
+    """(W, H, rX, rY, rAgg, hint kind): every window at aggregation radius 0, 2 and 3 with each hint map, the frames in rotation;
+    then the per-candidate kernel's case, its neighbour and the patch kernel at its bound on a frame of six pixels."""
+    c, n = [], 0
+    for rX, rY in WINDOWS:
+        for rAgg in (0, 2, 3):
+            for kind in ("general", "int", "outside"):
+                c.append(WINDOW_FRAMES[n % len(WINDOW_FRAMES)] + (rX, rY, rAgg, kind))
+                n += 1
+    c += [(3, 2) + w + ("general",) for w in (COST_FALLBACK, COST_LAST_PATCH, COST_PATCH_AT_BOUND)]
+    return c
+
+
+# diagonals, totalPass, adaptive P2, hint kind: each value of each with either penalty set (the whole-MEX counterparts)
+WINDOW_AGG_COMBOS = [(1, 2, 0, "general"), (0, 1, 1, "int"), (1, 3, 1, "jumpy"), (0, 2, 0, "jumpy"), (1, 1, 0, "int"), (0, 3, 1, "general")]
+# and their full cross, which the GPU test runs
+WINDOW_AGG_CROSS = [(diag, passes, adaptive, kind) for diag in (1, 0) for passes in (1, 2, 3) for adaptive in (0, 1)
+                    for kind in ("general", "int", "jumpy")]
+WINDOW_PENALTIES = [(6, 32, 24), (100, 200, 255)]          # P1, P2, the uploaded volume's maximum: no-wrap and wrapping
+
+
+def window_agg_cases(combos=WINDOW_AGG_COMBOS):
+    """(W, H, rX, rY, P1, P2, cmax, diagonals, totalPass, adaptive, hint kind)"""
+    c, n = [], 0
+    for rX, rY in WINDOWS:
+        for pen in WINDOW_PENALTIES:
+            for combo in combos:
+                c.append(WINDOW_FRAMES[n % len(WINDOW_FRAMES)] + (rX, rY) + pen + combo)
+                n += 1
+            n += 1                                            # (so that the two penalty sets meet different frames)
+    return c
+
+
+def window_whole_cases():
+    """(W, H, rX, rY, rAgg, sub, P1, P2, diagonals, totalPass, adaptive, hint kind): one whole call a window"""
+    return [WINDOW_FRAMES[i % len(WINDOW_FRAMES)] + (rX, rY, 2, 1, 6, 32, 1, 2, i % 2, "general" if i % 3 else "int")
+            for i, (rX, rY) in enumerate(WINDOWS)]
+
+
+# totalPass around the row-packed WTA's bound (sum of weights * 255 <= 65535: 64 with diagonals, 128 without), a weight above
+# a byte (257), and no pass at all
+WINDOW_PASSES = [(1, 64), (1, 65), (1, 257), (0, 128), (0, 129), (1, 0), (0, 0)]      # diagonals, totalPass
+RULE_WINDOWS = [(5, 5), (2, 2)]                                                      # the reference's 11x11, and 5x5
+RULE_FRAMES = [(5, 4), (6, 3)]
+
+
+def _window(W, H, rX, rY, rAgg, sub, P1, P2, diag, passes, adaptive, kind, grad=1):
+    return _pyd(W, H, W + 2, H + 1, rX, rY, rAgg, sub, P1, P2, diag, passes, adaptive, kind, 3 + rX, 5 + rY, amp=4.0, grad=grad)
+
+
+def pyd_window_cases():
+    """The whole-MEX counterparts of tests/test_gpu_pyd_windows.py: its cost cases with the reference's penalties, its aggregation
+    cases with the volume the MEX computes itself (so its maximum is 24 whatever the GPU case uploads), its whole calls, and the
+    totalPass values and penalty sets of its rule boundaries."""
+    c = [_window(W, H, rX, rY, rAgg, 1, 6, 32, 1, 2, 0, kind) for W, H, rX, rY, rAgg, kind in window_cost_cases()]
+    c += [_window(W, H, rX, rY, 2, 1, P1, P2, diag, passes, adaptive, kind, grad=3)
+          for W, H, rX, rY, P1, P2, _, diag, passes, adaptive, kind in window_agg_cases()]
+    c += [_window(*a) for a in window_whole_cases()]
+    for (rX, rY), (W, H) in zip(RULE_WINDOWS, RULE_FRAMES):
+        c += [_window(W, H, rX, rY, 2, 1, P1, P2, diag, passes, a, "general", grad=3)
+              for diag, passes in WINDOW_PASSES for a, (P1, P2) in enumerate(((0, 0), (6, 32)))]
+        c += [_window(W, H, rX, rY, 0, 1, P1, P2, 1, 2, 0, kind)
+              for P1, P2 in ((6, 100), (200, 31), (201, 31), (116, 115), (117, 115)) for kind in ("steps", "zigzag")]
+    return _dedupe(c)
+
+
+def budget_images(W, H):
+    """An image pair whose census codes differ in all 24 bits wherever both pixels have their whole 5x5 neighbourhood inside
+    the image: a strictly increasing ramp (W * H <= 256) and its complement."""
+    assert W * H <= 256
+    I1 = np.arange(W * H, dtype=np.uint8).reshape(H, W)
+    return np.ascontiguousarray(I1), np.ascontiguousarray(255 - I1)
 
 
 # ------------------------------------------------------------------------------------------------ calc_pyd_cost_sgm_ng
@@ -322,7 +434,14 @@ def golden_cases(name):
                 _pyd(12, 1, 13, 2, 2, 2, 2, 1, 6, 32, 1, 2, 0, "general", 9, 10), _pyd(2, 2, 2, 2, 1, 1, 1, 1, 6, 32, 1, 2, 0, "int", 11, 12),
                 _pyd(19, 13, 19, 13, 2, 3, 2, 1, 0, 255, 1, 1, 0, "general", 13, 14, grad=3),
                 _pyd(19, 13, 20, 15, 2, 3, 2, 1, 100, 200, 1, 3, 1, "even", 15, 16, grad=3), _pyd(16, 12, 16, 12, 0, 0, 0, 0, 6, 32, 0, 3, 1, "general", 17, 18),
-                _pyd(22, 12, 24, 13, 5, 5, 2, 1, 255, 0, 1, 2, 0, "far", 19, 20), _pyd(18, 11, 18, 11, 6, 2, 3, 0, 6, 32, 0, 1, 1, "int", 21, 22, amp=4.0, grad=3)]
+                _pyd(22, 12, 24, 13, 5, 5, 2, 1, 255, 0, 1, 2, 0, "far", 19, 20), _pyd(18, 11, 18, 11, 6, 2, 3, 0, 6, 32, 0, 1, 1, "int", 21, 22, amp=4.0, grad=3),
+                # search windows of 17x17 (the smallest with 16 candidates a lane), 31x33 (1023 candidates), 63x15, 15x63, 1x63
+                # and 63x1, and totalPass on either side of the row-packed WTA's bound at 11x11
+                _window(9, 7, 8, 8, 2, 1, 6, 32, 1, 2, 0, "general"), _window(13, 5, 15, 16, 2, 1, 100, 200, 1, 3, 1, "int", grad=3),
+                _window(5, 13, 31, 7, 3, 1, 6, 32, 0, 2, 0, "jumpy"), _window(8, 4, 7, 31, 0, 1, 6, 32, 1, 1, 1, "general", grad=3),
+                _window(6, 1, 0, 31, 2, 1, 6, 32, 1, 2, 0, "int"), _window(1, 6, 31, 0, 2, 1, 100, 200, 1, 2, 0, "general"),
+                _window(5, 4, 5, 5, 2, 1, 6, 32, 1, 64, 0, "general"), _window(5, 4, 5, 5, 2, 1, 6, 32, 1, 65, 1, "general", grad=3),
+                _window(6, 3, 5, 5, 2, 1, 0, 0, 0, 129, 0, "int"), _window(6, 3, 2, 2, 2, 1, 6, 32, 1, 257, 0, "general")]
     if name == "calc_pyd_cost_sgm_ng":
         return [_ng(20, 14, 20, 14, 1, 2, 0, 6, 32, "zero", 1, 2, 1.0), _ng(22, 16, 15, 10, 1, 5, 1, 6, 32, "general", 3, 4, 6.0),
                 _ng(19, 13, 24, 17, 1, 2, 1, 90, 120, "int", 5, 6, 2.0), _ng(14, 10, 14, 10, 2, 3, 0, 6, 32, "even", 7, 8, 3.0),

@@ -6,7 +6,7 @@ import numpy as np
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 NAMES = ("calc_cost_sgm", "calc_cost_sgm_ng", "calc_pyd_cost_sgm", "calc_pyd_cost_sgm_ng")
-COUNTS = {"calc_cost_sgm": 11, "calc_cost_sgm_ng": 10, "calc_pyd_cost_sgm": 11, "calc_pyd_cost_sgm_ng": 12}
+COUNTS = {"calc_cost_sgm": 11, "calc_cost_sgm_ng": 10, "calc_pyd_cost_sgm": 21, "calc_pyd_cost_sgm_ng": 12}
 _INPUTS = ("I1", "I2", "preMv", "pd0", "nd", "off", "args", "rand")
 _cache = {}
 

@@ -80,14 +80,16 @@ def test_calc_cost_sgm_oracle_equals_reference(oracle, build):
 
 
 # ------------------------------------------------------------------------------------------------ calc_pyd_cost_sgm
-PYD = R.pyd_cases() + R.pyd_fuzz_cases() + [R.KITTI_PYD_CPU]
+PYD = R.pyd_cases() + R.pyd_fuzz_cases() + [R.KITTI_PYD_CPU] + R.pyd_window_cases()
 
 
 @pytest.mark.parametrize("build", [c[1] for c in PYD], ids=_ids(PYD))
 def test_calc_pyd_cost_sgm_oracle_equals_reference(oracle, build):
-    """calc_pyd_cost_sgm: bestD, minC, mvSub and the printed line.  69 cases: 56 from test_gpu_pyd.py's parametrisations and
+    """calc_pyd_cost_sgm: bestD, minC, mvSub and the printed line.  362 cases: 56 from test_gpu_pyd.py's parametrisations and
     the edge values (two of them on tests/edge_inputs.py's image pairs: strong gradients, a saturated area), 12 from the random
-    sweep's draws, and the KITTI shape (5x5 window) at its full width of 1242 and 32 of its 375 rows: the suite has no slow marker, and the full frame costs 18 s here."""
+    sweep's draws, and the KITTI shape (5x5 window) at its full width of 1242 and 32 of its 375 rows: the suite has no slow marker, and the full frame costs 18 s here;
+    and 293 at search windows from 13x9 to 63x15 and 31x33 = 1023 candidates on frames of a few pixels, the whole-MEX counterparts of
+    tests/test_gpu_pyd_windows.py (tests/ref_cases.py: pyd_window_cases), totalPass 0 / 64 / 65 / 128 / 129 / 257 among them."""
     _need("calc_pyd_cost_sgm")
     a = build()
     I1, I2, mv, rX, rY = a[:5]
