@@ -13,5 +13,6 @@ from .pyramid import (pyramidal_sgm, pyramidal_sgm_ng, pyramidal_sgm_batch, pyra
                       pyramidal_flow_pp)
 from .post import (speckle_filter, calc_disp_from_first, forward_backward_check, scanline_in_fill, vzInd2Disp, vmf,  # noqa: F401
                    epi_postprocess, epi_postprocess_batch, PostPlan, flow_speckle_filter, flow_fb_check, flow_in_fill)
+from .stereo_pp import stereo_sgm_pp, stereo_disp_from_first, stereo_fb_check  # noqa: F401
 from .ng import calc_pyd_cost_sgm_ng, calc_cost_sgm_ng, calc_pyd_cost_sgm_ng_batch, calc_cost_sgm_ng_batch  # noqa: F401
 from ._lib import FsgmError, load as load_library  # noqa: F401

@@ -10,7 +10,8 @@ already holds, and what is queued on that stream afterwards runs after it.  Ops 
 fsgm::calc_cost_sgm_linear, fsgm::stereo_sgm, fsgm::stereo_sgm_range,
 fsgm::epipolar_sgm_of, fsgm::pyramidal_sgm, fsgm::pyramidal_sgm_ng, fsgm::epipolar_flow_pp, fsgm::pyramidal_flow_pp (each also returns a 0-d int32
 status tensor: 0, or FSGM_ERR_HIP when an aggregation hand-off gave up; check=True in the wrappers synchronises and raises
-on it), fsgm::epi_postprocess (status FSGM_ERR_INVALID when a D1 value is negative), fsgm::vmf and fsgm::flow_fb_check.
+on it), fsgm::epi_postprocess (status FSGM_ERR_INVALID when a D1 value is negative), fsgm::vmf and fsgm::flow_fb_check; for rectified
+stereo fsgm::stereo_sgm_pp (the matcher and the chain of test.m:45-50) and fsgm::stereo_fb_check (status as fsgm::epi_postprocess).
 
 One process must hold one HIP runtime.  torch brings its own libamdhip64; libfsgm_hip.so binds to it by soname when torch is
 imported first.  When the library was loaded first, torch afterwards maps a second runtime, and a stream or pointer of one
@@ -27,6 +28,7 @@ from . import _lib
 from ._lib import EpiIn, EpiOut, EpiOptions, EpiParams, FsgmError, StereoParams
 from .epi import EpiGeometry, _d_min, _params as _epi_params, _stereo_params
 from .post import _bind as _bind_post
+from .stereo_pp import CHAIN_FIELDS as STEREO_PP_FIELDS, _bind as _bind_stereo_pp, pp_params as _stereo_pp_params
 from .pyramid import PyramidParams, NgPyramidParams, FLOW_PP_FIELDS, MATCHERS, _bind as _bind_pyramid, _bind_flow_pp, _bind_ng
 
 FSGM_ERR_INVALID, FSGM_ERR_HIP = 1, 2
@@ -57,6 +59,7 @@ _bind_pyramid(_L)
 _bind_ng(_L)
 _bind_post(_L)
 _bind_flow_pp(_L)
+_bind_stereo_pp(_L)
 _L.fsgm_calc_cost_sgm_device.argtypes = [_i32, C.POINTER(EpiIn), C.POINTER(EpiOut), C.POINTER(EpiParams), _vp, _vp]
 _L.fsgm_calc_cost_sgm_linear_device.argtypes = [_i32, C.POINTER(EpiIn), C.POINTER(EpiOut), C.POINTER(EpiParams), _vp, _vp]
 _L.fsgm_stereo_sgm_device.argtypes = [_i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, C.POINTER(StereoParams), _vp, _vp, _vp, _vp, _vp, _vp]
@@ -415,6 +418,57 @@ def _(f, b, thr):
     return torch.empty_like(f, memory_format=torch.contiguous_format)
 
 
+@torch.library.custom_op("fsgm::stereo_sgm_pp", mutates_args=())
+def _stereo_sgm_pp_op(left: torch.Tensor, right: torch.Tensor, dMax: int, d_min: int, P1: int, P2: int, paths: int, subpixel: int,
+                      direction: int, adaptive_p2: int, chain: List[float],
+                      in_fill: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    N, H, W = left.shape
+    dev = left.device
+    left, right = _ready(left), _ready(right)
+    disp_pp, checked, disp2 = _f64((N, H, W), dev), _f64((N, H, W), dev), _f64((N, H, W), dev)
+    disp, minC, status = torch.empty((N, H, W), dtype=torch.int32, device=dev), _u32((N, H, W), dev), _status(dev)
+    prm = _stereo_params(paths, subpixel, direction, 0, dev.index)
+    opt = _lib.options(adaptive_p2)
+    pp = _stereo_pp_params(_L, in_fill, dict(zip(STEREO_PP_FIELDS, chain, strict=True)))
+    _call(dev, _L.fsgm_stereo_sgm_pp_device, N, _p(left), _p(right), W, H, int(dMax), int(P1), int(P2), C.byref(prm), C.byref(opt),
+          int(d_min), C.byref(pp), _p(disp_pp), _p(checked), _p(disp), _p(minC), _p(disp2), _stream(dev), _p(status))
+    return disp_pp, checked, disp, minC, disp2, status
+
+
+@_stereo_sgm_pp_op.register_fake
+def _(left, right, dMax, d_min, P1, P2, paths, subpixel, direction, adaptive_p2, chain, in_fill):
+    N, H, W = left.shape
+    dev = left.device
+    return (_f64((N, H, W), dev), _f64((N, H, W), dev), torch.empty((N, H, W), dtype=torch.int32, device=dev), _u32((N, H, W), dev),
+            _f64((N, H, W), dev), _status(dev))
+
+
+@torch.library.custom_op("fsgm::stereo_fb_check", mutates_args=())
+def _stereo_fb_check_op(D1: torch.Tensor, D2: torch.Tensor, fused: int, d_min: int, direction: int,
+                        thr: float) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    N, H, W = D1.shape
+    dev = D1.device
+    D1 = _ready(D1)
+    out, status = _f64((N, H, W), dev), _status(dev)
+    if fused:                                        # D2 is not read: the second-view map is made from D1 and returned
+        second = _f64((N, H, W), dev)
+        _call(dev, _L.fsgm_stereo_fb_check_device, N, _p(D1), None, W, H, int(d_min), int(direction), float(thr), _p(out), _p(second),
+              dev.index, _stream(dev), _p(status))
+    else:
+        D2 = _ready(D2)
+        second = _f64((0,), dev)
+        _call(dev, _L.fsgm_stereo_fb_check_device, N, _p(D1), _p(D2), W, H, int(d_min), int(direction), float(thr), _p(out), None,
+              dev.index, _stream(dev), _p(status))
+    return out, second, status
+
+
+@_stereo_fb_check_op.register_fake
+def _(D1, D2, fused, d_min, direction, thr):
+    N, H, W = D1.shape
+    dev = D1.device
+    return _f64((N, H, W), dev), _f64((N, H, W) if fused else (0,), dev), _status(dev)
+
+
 # ---------------------------------------------------------------------------------------------
 # wrappers: the argument order of the numpy API, one frame or a batch with a leading N
 # ---------------------------------------------------------------------------------------------
@@ -530,6 +584,54 @@ def stereo_sgm(left, right, dMax, P1=6, P2=64, *, paths=4, subpixel=1, direction
                                                                            int(adaptive_p2))
     outs = (disp, minC, conf, disp2) if fb_check else (disp, minC)
     return _finish(outs, status, batched, check, return_status)
+
+
+def stereo_sgm_pp(left, right, dMax, P1=6, P2=64, *, paths=4, subpixel=1, direction=-1, adaptive_p2=0, d_min=0, in_fill=1, check=False,
+                  return_status=False, **chain):
+    """(disp_pp, disp_checked, disp, minC, disp2) as fsgm_amd.stereo_sgm_pp, on torch tensors on the GPU: left, right (H, W)
+    uint8 or a batch (N, H, W).  The images are read where they lie, every output stays in HBM, the work is queued on the
+    current stream.  disp_pp / disp_checked / disp2 float64, disp int32 (true disparity * 256), minC uint32."""
+    d_min = _d_min(0 if d_min is None else d_min)
+    _tensors({"left": (left, torch.uint8), "right": (right, torch.uint8)})
+    if left.dim() not in (2, 3):
+        raise TypeError(f"left must be (H, W) or (N, H, W) (got {tuple(left.shape)})")
+    _shape("right", right, left.shape)
+    if int(dMax) < 1:
+        raise ValueError(f"dMax must be >= 1 (got {dMax!r})")
+    _stereo_params(paths, subpixel, direction, 0, 0)                        # the value checks, before anything is queued
+    if int(adaptive_p2) not in (0, 1):
+        raise ValueError(f"adaptive_p2 must be 0 or 1 (got {adaptive_p2!r})")
+    defaults = _stereo_pp_params(_L, in_fill, chain)                        # (unknown names raise here)
+    batched = left.dim() == 3
+    if not batched:
+        left, right = left.unsqueeze(0), right.unsqueeze(0)
+    *outs, status = torch.ops.fsgm.stereo_sgm_pp(left, right, int(dMax), d_min, int(P1), int(P2), int(paths), int(subpixel), int(direction),
+                                                 int(adaptive_p2), [float(getattr(defaults, k)) for k in STEREO_PP_FIELDS], int(in_fill))
+    return _finish(outs, status, batched, check, return_status)
+
+
+def stereo_fb_check(D1, D2=None, d_min=0, direction=-1, thr=2.0, *, return_second=False, check=False, return_status=False):
+    """fsgm_amd.stereo_fb_check on torch tensors on the GPU: D1 (and D2) (H, W) or (N, H, W) float64.  D2=None: the second-view
+    map is made from D1 in the same kernel (return_second=True also returns it).  The status tensor (return_status=True) is
+    FSGM_ERR_INVALID when that form met a negative D1 value; check=True synchronises and raises on it."""
+    d_min = _d_min(d_min)
+    named = {"D1": (D1, torch.float64)}
+    if D2 is not None:
+        named["D2"] = (D2, torch.float64)
+    _tensors(named)
+    if D1.dim() not in (2, 3):
+        raise TypeError(f"D1 must be (H, W) or (N, H, W) (got {tuple(D1.shape)})")
+    if D2 is not None:
+        _shape("D2", D2, D1.shape)
+        if return_second:
+            raise ValueError("return_second needs D2=None")
+    batched = D1.dim() == 3
+    a = D1 if batched else D1.unsqueeze(0)
+    b = a if D2 is None else (D2 if batched else D2.unsqueeze(0))
+    out, second, status = torch.ops.fsgm.stereo_fb_check(a, b, int(D2 is None), d_min, int(direction), float(thr))
+    outs = (out, second) if return_second else (out,)
+    res = _finish(outs, status, batched, check, return_status, "a D1 value is negative")
+    return res if return_second or return_status else res[0]
 
 
 def _epipolar_inputs(I0, I1, F, H, epipole, direction):

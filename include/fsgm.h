@@ -663,6 +663,80 @@ fsgm_status fsgm_pyramidal_flow_pp_time(int32_t n_frames, const uint8_t* I0, con
                                         int32_t channels, const fsgm_flow_pp_params* prm, int32_t warmup, int32_t iters, float* ms);
 
 /* ------------------------------------------------------------------------------------------
+ * Rectified stereo: checked, filtered and filled disparity maps.
+ *
+ * The chain test.m:45-50 applies to the epipolar matcher's vz-index map, behind fsgm_stereo_sgm_*_range, with the rectified
+ * geometry substituted into the reference's functions: Pd0 = (x + 1, y + 1) in MATLAB's 1-based coordinates, direction
+ * (direction, 0), and disp = d_min + w in place of vzInd2Disp.  w is the candidate-index map bestD / 256: f64, exact, NaN
+ * where invalid, >= 0 whatever d_min is (the speckle filter needs non-negative values and calc_disp_from_first.m marks an
+ * empty cell with -1); the true disparity of a pixel is d_min + w.
+ *
+ *  second view  calc_disp_from_first.m:6-47: D2 starts at -1; a pixel with value w offers it to the cells (s0x | s1x, s0y | s1y)
+ *               around p2 = (x + 1 + (d_min + w) * direction, y + 1), s0 = floor(p2), s1 = s0 + 1, that lie inside the image;
+ *               a cell keeps the largest offer (:25 on non-negative values).  NaN offers nothing.  Row y writes rows y and y + 1.
+ *  check        forward_backward_check.m:8-37: a valid pixel becomes NaN when p2x = round(x + 1 + (d_min + w) * direction)
+ *               (half away from zero) leaves [1, width], when D2(p2) is -1, or when |w - D2(p2)| > thr.
+ *  chain        w1 = speckle_filter(w, speckle_max_diff, speckle_max_size); D2 = second view of w1; c = check(w1, D2);
+ *               c = speckle_filter(c, dMax, (double)(height * width) * island_fraction); g = in_fill ? scanline_in_fill(c) : c
+ *
+ * Maps are f64 [n_frames][height][width]; no stage looks across a frame boundary.  Second view and check run as one kernel
+ * with the second-view row in LDS: width <= 8192 (8 * width bytes within 64 KiB), FSGM_ERR_UNSUPPORTED beyond, as is
+ * n_frames * width * height >= 2^31; both are answered before a device is touched.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct {
+    double  speckle_max_diff;       /* 2    (test.m:45) */
+    double  speckle_max_size;       /* 100  (test.m:45) */
+    double  fb_threshold;           /* 2.0  (forward_backward_check.m:6), >= 0 */
+    double  island_fraction;        /* 0.1  (test.m:48: rows*cols/10), in [0, 1] */
+    int32_t in_fill;                /* 1    (test.m:49); 0 = disp_pp is disp_checked */
+    int32_t reserved[7];            /* must be zero */
+} fsgm_stereo_pp_params;
+fsgm_stereo_pp_params fsgm_stereo_pp_params_default(void);
+
+/* the dynamic LDS bytes the row kernel asks for at this width, by the expression its launcher uses; the width refusal of every
+ * entry point below.  No device is touched. */
+fsgm_status fsgm_stereo_pp_launch_lds(int32_t width, uint64_t* row_lds);
+
+/* fsgm_stereo_sgm_host_range and the chain without leaving HBM.  Arguments as fsgm_stereo_sgm_host_range (prm->fb_check must
+ * be 0, FSGM_ERR_INVALID otherwise: the chain has its own check, so the dMax <= 511 of the fixed-point check does not apply)
+ * plus pp (NULL = the defaults).  Outputs, [n][H][W] each, every one optional except disp_pp:
+ *   disp_pp      f64  d_min + g, NaN where nothing could be filled
+ *   disp_checked f64  d_min + c: its NaN pattern is the validity mask of test.m:53
+ *   disp, minC   the matcher's raw int32 true disparities * 256 and u32 minC (fsgm_stereo_sgm_host_range's)
+ *   disp2        f64  -1 where D2 is empty, d_min + D2 elsewhere
+ * The device form follows the device-pointer contract below (caller's stream, pointer checks, captured streams refused, no
+ * host wait once the shape is warm; outputs must not overlap); the images are read where they lie; status as
+ * fsgm_stereo_sgm_device_range. */
+fsgm_status fsgm_stereo_sgm_pp_host(int32_t n_frames, const uint8_t* I1, const uint8_t* I2, int32_t width, int32_t height,
+                                    int32_t dMax, int32_t P1, int32_t P2, const fsgm_stereo_params* prm, const fsgm_epi_options* opt,
+                                    int32_t d_min, const fsgm_stereo_pp_params* pp, double* disp_pp, double* disp_checked,
+                                    int32_t* disp, uint32_t* minC, double* disp2);
+fsgm_status fsgm_stereo_sgm_pp_device(int32_t n_frames, const uint8_t* I1, const uint8_t* I2, int32_t width, int32_t height,
+                                      int32_t dMax, int32_t P1, int32_t P2, const fsgm_stereo_params* prm, const fsgm_epi_options* opt,
+                                      int32_t d_min, const fsgm_stereo_pp_params* pp, double* disp_pp, double* disp_checked,
+                                      int32_t* disp, uint32_t* minC, double* disp2, void* stream, int32_t* status);
+/* The two stages on their own, on maps of arbitrary non-negative doubles or NaN (a negative value is FSGM_ERR_INVALID: the
+ * host forms answer on the host, the device forms through status, as fsgm_epi_postprocess_device does).  direction -1 or +1,
+ * |d_min| <= FSGM_D_MIN_LIMIT, thr >= 0.  Outputs must not overlap inputs.
+ * fsgm_stereo_fb_check: D2 given -- the check of D1 against that map (D2out must be NULL); D2 NULL -- the second-view map is
+ * made from D1 itself by the fused row kernel, the form the chain runs, and D2out (may be NULL) receives it. */
+fsgm_status fsgm_stereo_disp_from_first_host(int32_t n_frames, const double* D1, int32_t width, int32_t height, int32_t d_min,
+                                             int32_t direction, double* D2, int32_t device);
+fsgm_status fsgm_stereo_disp_from_first_device(int32_t n_frames, const double* D1, int32_t width, int32_t height, int32_t d_min,
+                                               int32_t direction, double* D2, int32_t device, void* stream, int32_t* status);
+fsgm_status fsgm_stereo_fb_check_host(int32_t n_frames, const double* D1, const double* D2, int32_t width, int32_t height,
+                                      int32_t d_min, int32_t direction, double thr, double* D1checked, double* D2out, int32_t device);
+fsgm_status fsgm_stereo_fb_check_device(int32_t n_frames, const double* D1, const double* D2, int32_t width, int32_t height,
+                                        int32_t d_min, int32_t direction, double thr, double* D1checked, double* D2out, int32_t device,
+                                        void* stream, int32_t* status);
+/* average milliseconds (HIP events, warm, host images as fsgm_stereo_sgm_pp_host takes them): ms[0] the matcher, ms[1] the
+ * chain, ms[2] the fused row kernel alone, ms[3] the epipolar chain's two generic kernels on explicit rectified maps (a cost
+ * comparison: their disparity function differs) */
+fsgm_status fsgm_stereo_sgm_pp_time(int32_t n_frames, const uint8_t* I1, const uint8_t* I2, int32_t width, int32_t height,
+                                    int32_t dMax, int32_t P1, int32_t P2, const fsgm_stereo_params* prm, const fsgm_epi_options* opt,
+                                    int32_t d_min, const fsgm_stereo_pp_params* pp, int32_t warmup, int32_t iters, float* ms);
+
+/* ------------------------------------------------------------------------------------------
  * calc_pyd_cost_sgm_ng  (calc_pyd_cost_sgm_ng.cpp:448-523; same 8-argument list as the call in
  * ng_sgm.m:20, no caller in the reference tree)
  * ------------------------------------------------------------------------------------------ */
