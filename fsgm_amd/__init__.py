@@ -6,6 +6,7 @@ multi-path SGM aggregation hot path, behind the reference's MEX argument lists.
 
 Everything computes on the GPU through libfsgm_hip.so (C ABI in include/fsgm.h).
 """
+from .sgm import sgm_batch  # noqa: F401  (ahead of .epi: the name fsgm_amd.sgm stays the function imported below, not this submodule)
 from .epi import (calc_cost_sgm, calc_cost_sgm_batch, EpiPlan, epipolar_maps, epipolar_sgm_of, epipolar_flow_pp, epipolar_from_F,  # noqa: F401
                   census, sgm, auto_pipeline, calc_cost_sgm_linear, calc_cost_sgm_linear_batch, stereo_sgm, stereo_maps)
 from .pyd import calc_pyd_cost_sgm, calc_pyd_cost_sgm_batch, PydPlan  # noqa: F401

@@ -2,11 +2,13 @@
 // points (what the calc_cost_sgm mexFunction gateway calls).  See include/fsgm.h.
 #include "capi_common.h"
 #include "capi_device.h"
+#include "capi_sgm.h"
 #include "epi_kernels.h"
 #include "geometry_kernels.h"
 #include "post_kernels.h"
 #include "post_plan.h"
 #include "pyramid_kernels.h"
+#include "sgm_ingest.h"
 #include <algorithm>
 #include <cmath>
 #include <mutex>
@@ -90,6 +92,10 @@ struct fsgm_epi_plan {
     fsgm_post_plan* post = nullptr;
     uint2* dRec = nullptr;
     uint16_t* dS0 = nullptr;
+    // caller-supplied volumes (fsgm_sgm_batch_host / fsgm_sgm_device): the host form's staging of [D][H][W] volumes, the flag
+    // the ingest kernel raises for a byte above the declared bound
+    uint8_t* dIngest = nullptr;
+    uint32_t* dIngestFlag = nullptr;
     hipStream_t stream_h = nullptr, stream_b = nullptr;
     hipEvent_t ev_fork = nullptr, ev_h = nullptr, ev_b = nullptr, ev_c = nullptr;
     hipEvent_t ev_hl[2] = {nullptr, nullptr};   // the horizontal pair of each frame lane done (sweep pipeline)
@@ -318,7 +324,7 @@ void fsgm_epi_plan_destroy(fsgm_epi_plan* p) {
     (void)hipSetDevice(p->prm.device);
     void* bufs[] = {p->dI1, p->dI2, p->dCen1, p->dCen2, p->dPd0, p->dNd, p->dOff, p->dVz,
                     p->dCraw, p->dC, p->dL, p->dBestD, p->dMinC, p->dS, p->dD2enc, p->dD2, p->dConf, p->dLh, p->dX, p->dXup, p->dXupAll, p->dStateUp, p->dLx, p->dState, p->dCkpt, p->dCkptV, p->dRec, p->dS0, p->dRflow, p->dFlow, p->dRgb, p->dBits, p->dBandEdge, p->dBandTicket, p->dBandErr,
-                    p->dD1, p->dFlow2};
+                    p->dD1, p->dFlow2, p->dIngest, p->dIngestFlag};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     fsgm_post_plan_destroy(p->post);
@@ -1040,19 +1046,29 @@ fsgm_status fsgm_epi_plan_download_census(fsgm_epi_plan* p, int32_t f, uint32_t*
     return FSGM_OK;
 }
 
-fsgm_status fsgm_epi_plan_download_sum(fsgm_epi_plan* p, int32_t f, uint32_t* S) {
-    FSGM_REQUIRE(p && S, "fsgm_epi_plan_download_sum: null argument");
-    { fsgm_status fs = frame_ready(p, f, 2); if (fs != FSGM_OK) return fs; }
-    // the line kernels sum the frame's path volumes; the fused pipelines never hold S in HBM and rebuild it (tap_*)
-    { fsgm_status es = ensure_agg_buffers(p); if (es != FSGM_OK) return es; }
+// the S tap's own buffers (one frame each), created on first use
+static fsgm_status ensure_tap_buffers(fsgm_epi_plan* p) {
     if (!p->dS) FSGM_HIP(hipMalloc((void**)&p->dS, p->N * 4));
     if (!p->dXup && (pipe_sweep(p->pipe) || p->pipe == PIPE_PAIRS)) FSGM_HIP(hipMalloc((void**)&p->dXup, p->N));
+    return FSGM_OK;
+}
+// frame f's S into dS on the plan's stream, by the selected pipeline's tap
+static void tap_sum(fsgm_epi_plan* p, int f) {
     switch (p->pipe) {
         case PIPE_SWEEP: case PIPE_SWEEP_PAR: case PIPE_SWEEP_MID: tap_sweep(p, f); break;
         case PIPE_PAIRS: tap_pairs(p, f); break;
         case PIPE_BAND: case PIPE_BAND_CHAIN: tap_band(p, f); break;
         default: tap_lines(p, f); break;
     }
+}
+
+fsgm_status fsgm_epi_plan_download_sum(fsgm_epi_plan* p, int32_t f, uint32_t* S) {
+    FSGM_REQUIRE(p && S, "fsgm_epi_plan_download_sum: null argument");
+    { fsgm_status fs = frame_ready(p, f, 2); if (fs != FSGM_OK) return fs; }
+    // the line kernels sum the frame's path volumes; the fused pipelines never hold S in HBM and rebuild it (tap_*)
+    { fsgm_status es = ensure_agg_buffers(p); if (es != FSGM_OK) return es; }
+    { fsgm_status es = ensure_tap_buffers(p); if (es != FSGM_OK) return es; }
+    tap_sum(p, f);
     FSGM_HIP(hipGetLastError());
     FSGM_HIP(hipStreamSynchronize(p->stream));
     FSGM_HIP(hipMemcpy(S, p->dS, p->N * 4, hipMemcpyDeviceToHost));
@@ -1134,18 +1150,21 @@ static PlanCache<fsgm_epi_plan> g_epi(4, fsgm_epi_plan_destroy);   // cached pla
 // The cached plan of this shape for an entry point: `lk` holds its device's lock for the length of the call, the device is current.
 // (a plan serves one sampling mode and, rectified, one direction: the modes share no cached state)
 static fsgm_status cached_plan(std::unique_lock<std::mutex>& lk, fsgm_epi_plan** out, int W, int H, int D, int batch,
-                               const fsgm_epi_params& pr, int sampling = FSGM_SAMPLING_VZ, int direction = 0, int adaptive = 0) {
+                               const fsgm_epi_params& pr, int sampling = FSGM_SAMPLING_VZ, int direction = 0, int adaptive = 0,
+                               int agg_mode = 0) {
     FSGM_DEVICE_SLOT(pr.device);
     lk = std::unique_lock<std::mutex>(g_epi.mu(pr.device));
     fsgm_epi_plan* p = g_epi.find(pr.device, [&](const fsgm_epi_plan* q) {
         return q->W == W && q->H == H && q->D == D && q->batch == batch && q->prm.paths == pr.paths &&
                q->prm.fb_check == pr.fb_check && q->prm.vz_to_disp == pr.vz_to_disp && q->sampling == sampling &&
-               q->direction == direction && q->adaptive == adaptive;     // (adaptive and non-adaptive callers never share a plan)
+               q->direction == direction && q->adaptive == adaptive &&   // (adaptive and non-adaptive callers never share a plan)
+               q->agg_mode == agg_mode;                                  // (nor do forced modes: only the sgm batch forms ask for one)
     });
     if (p) p->prm = pr;
     else {
         fsgm_status st = fsgm_epi_plan_create_sampling(&p, W, H, D, batch, &pr, sampling, direction);
         if (st == FSGM_OK && adaptive && (st = fsgm_epi_plan_set_adaptive_p2(p, 1)) != FSGM_OK) fsgm_epi_plan_destroy(p);
+        else if (st == FSGM_OK && agg_mode && (st = fsgm_epi_plan_set_agg_mode(p, agg_mode)) != FSGM_OK) fsgm_epi_plan_destroy(p);
         if (st != FSGM_OK) return st;
         g_epi.insert(pr.device, p);
     }
@@ -1353,6 +1372,129 @@ fsgm_status fsgm_sgm_host(const uint8_t* C, int32_t W, int32_t H, int32_t D, int
     if ((st = fsgm_epi_plan_download(p, 0, bestD, minC)) != FSGM_OK) return st;
     if (S && (st = fsgm_epi_plan_download_sum(p, 0, S)) != FSGM_OK) return st;
     return FSGM_OK;
+}
+
+}  // extern "C"
+
+// ---- sgm(C, P1, P2) on batches of caller-supplied volumes (capi_sgm.hip has checked the call) ----
+namespace fsgm {
+
+static thread_local const char* g_sgm_kernel = "";
+
+// the cached plan of a checked call: its batch, mode and adaptive switch are part of the key
+static fsgm_status sgm_plan(std::unique_lock<std::mutex>& lk, fsgm_epi_plan** p, const SgmCall& c) {
+    fsgm_epi_params pr = fsgm_epi_params_default();
+    pr.paths = c.prm.paths; pr.subpixel = c.prm.subpixel; pr.device = c.prm.device; pr.vz_to_disp = 0; pr.fb_check = 0;
+    return cached_plan(lk, p, c.W, c.H, c.D, c.n, pr, FSGM_SAMPLING_VZ, 0, c.prm.adaptive_p2, c.prm.agg_mode);
+}
+
+static fsgm_status ensure_ingest_flag(fsgm_epi_plan* p) {
+    if (p->dIngestFlag) return FSGM_OK;
+    FSGM_HIP(hipMalloc((void**)&p->dIngestFlag, sizeof(uint32_t)));
+    FSGM_HIP(hipMemsetAsync(p->dIngestFlag, 0, sizeof(uint32_t), p->stream));
+    return FSGM_OK;
+}
+
+fsgm_status sgm_run_host(const SgmCall& c, const int* cmax) {
+    std::unique_lock<std::mutex> lk;
+    fsgm_epi_plan* p = nullptr;
+    fsgm_status st = sgm_plan(lk, &p, c);
+    if (st != FSGM_OK) return st;
+    const size_t NP = p->NP, nv = (size_t)c.n * p->N;
+    for (int f = 0; f < c.n; f++) p->cmax[f] = cmax[f];
+    if ((st = fsgm_epi_plan_set_penalties(p, c.P1, c.P2, p->vMax)) != FSGM_OK) return st;    // (selects the kernels for cmax)
+    if (c.guide)                                                 // the aggregation reads I1 only: the guide stands for both images
+        for (int f = 0; f < c.n; f++)
+            if ((st = fsgm_epi_plan_upload_images(p, f, c.guide + f * NP, c.guide + f * NP)) != FSGM_OK) return st;
+    if ((st = prepare(p, FSGM_STAGE_AGGREGATE | FSGM_STAGE_WTA)) != FSGM_OK) return st;
+    const bool dhw = c.prm.layout == FSGM_COST_LAYOUT_DHW;       // staged as it came, transposed on the device
+    if (dhw && !p->dIngest) FSGM_HIP(hipMalloc((void**)&p->dIngest, nv));
+    StreamGuard guard(p->stream);                                // every early exit drains the stream: the copies use caller memory
+    FSGM_HIP(hipMemcpyAsync(dhw ? p->dIngest : p->dC, c.C, nv, hipMemcpyHostToDevice, p->stream));
+    if (dhw) launch_sgm_ingest(p->stream, p->dIngest, p->dC, c.n, c.W, c.H, c.D, FSGM_COST_LAYOUT_DHW, 255, nullptr);
+    if ((st = enqueue(p, FSGM_STAGE_AGGREGATE | FSGM_STAGE_WTA)) != FSGM_OK) return st;
+    g_sgm_kernel = kPipelineName[p->pipe];
+    FSGM_HIP(hipMemcpyAsync(c.bestD, p->dBestD, (size_t)c.n * NP * 4, hipMemcpyDeviceToHost, p->stream));
+    FSGM_HIP(hipMemcpyAsync(c.minC, p->dMinC, (size_t)c.n * NP * 4, hipMemcpyDeviceToHost, p->stream));
+    FSGM_HIP(hipStreamSynchronize(p->stream));
+    guard.dismiss();
+    if ((st = check_handoff(p)) != FSGM_OK) return st;
+    for (int f = 0; c.S && f < c.n; f++)
+        if ((st = fsgm_epi_plan_download_sum(p, f, c.S + (size_t)f * p->N)) != FSGM_OK) return st;
+    return FSGM_OK;
+}
+
+fsgm_status sgm_run_device(const SgmCall& c, hipStream_t cs, int32_t* status) {
+    std::unique_lock<std::mutex> lk;
+    fsgm_epi_plan* p = nullptr;
+    fsgm_status st = sgm_plan(lk, &p, c);
+    if (st != FSGM_OK) return st;
+    // What a warm call must not do happens here, before the join with the caller's stream.  The device cannot be asked for the
+    // true maximum without a wait: the declared bound selects the kernels, the ingest kernel saturates at it.
+    p->cmax.assign(c.n, c.prm.cost_bound);
+    if ((st = fsgm_epi_plan_set_penalties(p, c.P1, c.P2, p->vMax)) != FSGM_OK) return st;
+    if (c.guide) {
+        if ((st = ensure_image_buffers(p)) != FSGM_OK) return st;
+        p->have_img.assign(c.n, 1);                              // the guide goes into dI1 below, ahead of the kernels
+    }
+    if ((st = prepare(p, FSGM_STAGE_AGGREGATE | FSGM_STAGE_WTA)) != FSGM_OK) return st;
+    if ((st = ensure_ingest_flag(p)) != FSGM_OK) return st;
+    if (c.S && (st = ensure_tap_buffers(p)) != FSGM_OK) return st;
+    if ((st = p->join.ensure()) != FSGM_OK) return st;
+    if ((st = p->join.enter(cs, p->stream)) != FSGM_OK) return st;
+    st = [&]() -> fsgm_status {
+        launch_sgm_ingest(p->stream, c.C, p->dC, c.n, c.W, c.H, c.D, c.prm.layout, c.prm.cost_bound, p->dIngestFlag);
+        if (c.guide) FSGM_HIP(hipMemcpyAsync(p->dI1, c.guide, (size_t)c.n * p->NP, hipMemcpyDeviceToDevice, p->stream));
+        Bind<uint32_t> bd(p->dBestD, c.bestD), mc(p->dMinC, c.minC);
+        const fsgm_status es = enqueue(p, FSGM_STAGE_AGGREGATE | FSGM_STAGE_WTA);
+        if (es != FSGM_OK) return es;
+        g_sgm_kernel = kPipelineName[p->pipe];
+        for (int f = 0; c.S && f < c.n; f++) {                   // S never exists for a batch: frame by frame through the tap's buffer
+            tap_sum(p, f);
+            FSGM_HIP(hipMemcpyAsync(c.S + (size_t)f * p->N, p->dS, p->N * 4, hipMemcpyDeviceToDevice, p->stream));
+        }
+        return FSGM_OK;
+    }();
+    // the status word, then the caller's stream waits for the plan's (also after a failed enqueue, as epi_device_finish)
+    if (st == FSGM_OK) launch_sgm_status(p->stream, p->dBandErr, p->dIngestFlag, status);
+    const fsgm_status js = p->join.leave(p->stream, cs);
+    if (st != FSGM_OK) return st;
+    FSGM_HIP(hipGetLastError());
+    return js;
+}
+
+}  // namespace fsgm
+
+extern "C" {
+
+const char* fsgm_sgm_last_kernel(void) { return g_sgm_kernel; }
+
+fsgm_status fsgm_epi_plan_ingest_cost_device(fsgm_epi_plan* p, int32_t n, const uint8_t* C, int32_t layout, int32_t cost_bound,
+                                             void* stream, int32_t* status) {
+    const char* who = "fsgm_epi_plan_ingest_cost_device";
+    FSGM_REQUIRE(p && C, "%s: null argument", who);
+    FSGM_REQUIRE(n == p->batch, "%s: n_frames %d differs from the plan's batch %d", who, n, p->batch);
+    FSGM_REQUIRE(layout == FSGM_COST_LAYOUT_HWD || layout == FSGM_COST_LAYOUT_DHW,
+                 "%s: layout must be FSGM_COST_LAYOUT_HWD (0) or FSGM_COST_LAYOUT_DHW (1), got %d", who, layout);
+    FSGM_REQUIRE(cost_bound >= 1 && cost_bound <= 255, "%s: cost_bound must be 1..255 (got %d)", who, cost_bound);
+    const int dev = p->prm.device;
+    const hipStream_t cs = (hipStream_t)stream;
+    fsgm_status st;
+    FSGM_HIP(hipSetDevice(dev));
+    if ((st = device_check_stream(cs, who)) != FSGM_OK ||
+        (st = device_check_ptr(C, (size_t)n * p->N, 1, dev, true, who, "C")) != FSGM_OK ||
+        (st = device_check_ptr(status, 4, 4, dev, false, who, "status")) != FSGM_OK)
+        return st;
+    if ((st = ensure_ingest_flag(p)) != FSGM_OK) return st;
+    p->cmax.assign(n, cost_bound);
+    select_kernel(p);
+    if ((st = p->join.ensure()) != FSGM_OK) return st;
+    if ((st = p->join.enter(cs, p->stream)) != FSGM_OK) return st;
+    launch_sgm_ingest(p->stream, C, p->dC, n, p->W, p->H, p->D, layout, cost_bound, p->dIngestFlag);
+    launch_sgm_status(p->stream, nullptr, p->dIngestFlag, status);
+    st = p->join.leave(p->stream, cs);
+    FSGM_HIP(hipGetLastError());
+    return st;
 }
 
 // census() of common.cpp:3-27 alone (the one function of the path that the reference's own sources pin here)

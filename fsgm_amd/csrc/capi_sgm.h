@@ -1,0 +1,20 @@
+// capi_sgm.h -- what capi_sgm.hip (argument and pointer checks of the sgm batch entry points) hands to capi_epi.hip (the
+// cached plans and their pipelines): a checked call.
+#pragma once
+#include "capi_common.h"
+
+namespace fsgm {
+
+struct SgmCall {
+    int n, W, H, D, P1, P2;
+    fsgm_sgm_params prm;                 // checked, never the caller's NULL
+    const uint8_t *C, *guide;            // guide: non-NULL exactly when prm.adaptive_p2
+    uint32_t *bestD, *minC, *S;          // S may be NULL
+};
+
+// host pointers; cmax: the largest byte of each frame's volume (none above prm.cost_bound)
+fsgm_status sgm_run_host(const SgmCall& c, const int* cmax);
+// device pointers, checked (device_check_ptr / device_check_stream) by the caller; cs: the caller's stream
+fsgm_status sgm_run_device(const SgmCall& c, hipStream_t cs, int32_t* status);
+
+}  // namespace fsgm

@@ -1,0 +1,92 @@
+// capi_sgm.hip -- C ABI of sgm(C, P1, P2) on batches of caller-supplied cost volumes, in host memory or in HBM (include/fsgm.h:
+// fsgm_sgm_batch_host, fsgm_sgm_device).  Everything that can be refused without a device is refused here; the cached plans
+// and their pipelines live in capi_epi.hip (capi_sgm.h).
+#include "capi_sgm.h"
+#include "capi_device.h"
+#include <algorithm>
+#include <string.h>
+#include <vector>
+
+using namespace fsgm;
+
+// the checks both forms share: prm (NULL: the defaults) into c->prm, the scalars and the pointers every call needs
+static fsgm_status sgm_args(const char* who, int32_t n, const uint8_t* C, int32_t W, int32_t H, int32_t D, int32_t P1, int32_t P2,
+                            const fsgm_sgm_params* prm, const uint8_t* guide, uint32_t* bestD, uint32_t* minC, uint32_t* S, SgmCall* c) {
+    FSGM_REQUIRE(n >= 1, "%s: n_frames must be >= 1 (got %d)", who, n);
+    FSGM_REQUIRE(C && bestD && minC, "%s: null argument", who);
+    FSGM_REQUIRE(W >= 1 && H >= 1, "%s: width/height must be >= 1 (got %d x %d)", who, W, H);
+    FSGM_REQUIRE(D >= 1 && D <= 1024, "%s: dMax must be 1..1024 (got %d)", who, D);
+    const fsgm_sgm_params sp = prm ? *prm : fsgm_sgm_params_default();
+    for (int r : sp.reserved) FSGM_REQUIRE(r == 0, "%s: the reserved words of fsgm_sgm_params must be zero", who);
+    FSGM_REQUIRE(sp.paths == 4 || sp.paths == 8, "%s: paths must be 4 or 8 (got %d)", who, sp.paths);
+    FSGM_REQUIRE(sp.subpixel == 0 || sp.subpixel == 1, "%s: subpixel must be 0 or 1 (got %d)", who, sp.subpixel);
+    FSGM_REQUIRE(sp.layout == FSGM_COST_LAYOUT_HWD || sp.layout == FSGM_COST_LAYOUT_DHW,
+                 "%s: layout must be FSGM_COST_LAYOUT_HWD (0) or FSGM_COST_LAYOUT_DHW (1), got %d", who, sp.layout);
+    FSGM_REQUIRE(sp.cost_bound >= 1 && sp.cost_bound <= 255, "%s: cost_bound must be 1..255 (got %d)", who, sp.cost_bound);
+    FSGM_REQUIRE(sp.agg_mode >= 0 && sp.agg_mode <= 6, "%s: agg_mode must be 0..6 (got %d)", who, sp.agg_mode);
+    FSGM_REQUIRE(sp.adaptive_p2 == 0 || sp.adaptive_p2 == 1, "%s: adaptive_p2 must be 0 or 1 (got %d)", who, sp.adaptive_p2);
+    FSGM_REQUIRE(sp.device >= 0 && sp.device < FSGM_MAX_DEVICES, "%s: device %d out of range", who, sp.device);
+    FSGM_REQUIRE(!sp.adaptive_p2 || guide, "%s: adaptive_p2 needs the guide image (guide is NULL)", who);
+    if (sp.adaptive_p2 && sp.agg_mode >= 2)
+        return fail(FSGM_ERR_UNSUPPORTED, "%s: agg_mode %d with adaptive_p2: only the line kernels (modes 0 and 1) take a per-step P2", who,
+                    sp.agg_mode);
+    if ((double)W * H * D >= 2147483648.0)
+        return fail(FSGM_ERR_UNSUPPORTED, "%s: cost volume %d x %d x %d exceeds 2^31 voxels per frame", who, W, H, D);
+    *c = SgmCall{n, W, H, D, P1, P2, sp, C, sp.adaptive_p2 ? guide : nullptr, bestD, minC, S};
+    return FSGM_OK;
+}
+
+extern "C" {
+
+fsgm_sgm_params fsgm_sgm_params_default(void) {
+    fsgm_sgm_params p;
+    memset(&p, 0, sizeof(p));
+    p.paths = 4;                         // sgm.m's enableDiagonalPath = false, as fsgm_sgm_host's callers pass
+    p.subpixel = 1;
+    p.layout = FSGM_COST_LAYOUT_HWD;
+    p.cost_bound = 255;
+    return p;
+}
+
+fsgm_status fsgm_sgm_batch_host(int32_t n, const uint8_t* C, int32_t W, int32_t H, int32_t D, int32_t P1, int32_t P2,
+                                const fsgm_sgm_params* prm, const uint8_t* guide, uint32_t* bestD, uint32_t* minC, uint32_t* S) {
+    SgmCall c;
+    const fsgm_status st = sgm_args("fsgm_sgm_batch_host", n, C, W, H, D, P1, P2, prm, guide, bestD, minC, S, &c);
+    if (st != FSGM_OK) return st;
+    // the true maximum of every frame, as fsgm_epi_plan_upload_cost takes it (either layout holds the same bytes)
+    const size_t N = (size_t)W * H * D;
+    std::vector<int> cmax(n, 0);
+    for (int f = 0; f < n; f++) {
+        const uint8_t* v = C + (size_t)f * N;
+        int m = 0;
+        for (size_t i = 0; i < N; i++) m = v[i] > m ? v[i] : m;
+        FSGM_REQUIRE(m <= c.prm.cost_bound, "fsgm_sgm_batch_host: frame %d holds a cost of %d, above cost_bound %d", f, m, c.prm.cost_bound);
+        cmax[f] = m;
+    }
+    return sgm_run_host(c, cmax.data());
+}
+
+fsgm_status fsgm_sgm_device(int32_t n, const uint8_t* C, int32_t W, int32_t H, int32_t D, int32_t P1, int32_t P2,
+                            const fsgm_sgm_params* prm, const uint8_t* guide, uint32_t* bestD, uint32_t* minC, uint32_t* S, void* stream,
+                            int32_t* status) {
+    const char* who = "fsgm_sgm_device";
+    SgmCall c;
+    fsgm_status st = sgm_args(who, n, C, W, H, D, P1, P2, prm, guide, bestD, minC, S, &c);
+    if (st != FSGM_OK) return st;
+    // checks first, also on a shape's first call: nothing is allocated for a captured stream or a pointer that is refused
+    const int dev = c.prm.device;
+    const size_t np = (size_t)n * W * H, nv = np * D;
+    const hipStream_t cs = (hipStream_t)stream;
+    if ((st = use_device(dev)) != FSGM_OK) return st;
+    if ((st = device_check_stream(cs, who)) != FSGM_OK ||
+        (st = device_check_ptr(C, nv, 1, dev, true, who, "C")) != FSGM_OK ||
+        (st = device_check_ptr(c.guide, np, 1, dev, false, who, "guide")) != FSGM_OK ||
+        (st = device_check_ptr(bestD, np * 4, 4, dev, true, who, "bestD")) != FSGM_OK ||
+        (st = device_check_ptr(minC, np * 4, 4, dev, true, who, "minC")) != FSGM_OK ||
+        (st = device_check_ptr(S, nv * 4, 4, dev, false, who, "S")) != FSGM_OK ||
+        (st = device_check_ptr(status, 4, 4, dev, false, who, "status")) != FSGM_OK)
+        return st;
+    return sgm_run_device(c, cs, status);
+}
+
+}  // extern "C"

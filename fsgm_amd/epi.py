@@ -407,6 +407,12 @@ class EpiPlan:
         from . import torch_ops
         return torch_ops.run_tensors(self, I1, I2, pd0, nd, off, **kw)
 
+    def ingest_cost(self, Cvol, **kw):
+        """All frames' cost volumes from a uint8 torch tensor on the GPU, in either layout, ordered on the current stream
+        (fsgm_amd.torch_ops.ingest_cost; import torch before the library is loaded)."""
+        from . import torch_ops
+        return torch_ops.ingest_cost(self, Cvol, **kw)
+
     @property
     def kernel_name(self):
         return self.lib.fsgm_epi_plan_kernel_name(self._h).decode()

@@ -1,0 +1,90 @@
+"""sgm(C, P1, P2) on batches of caller-supplied cost volumes (include/fsgm.h: fsgm_sgm_batch_host; the same call on torch
+tensors in HBM is fsgm_amd.torch_ops.sgm): either layout, a declared bound of the costs, every aggregation pipeline."""
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from ._lib import check, ptr
+
+LAYOUTS = {"hwd": 0, "dhw": 1}          # FSGM_COST_LAYOUT_HWD / _DHW
+
+
+class SgmParams(C.Structure):
+    _fields_ = [("paths", C.c_int32), ("subpixel", C.c_int32), ("device", C.c_int32), ("agg_mode", C.c_int32), ("layout", C.c_int32),
+                ("cost_bound", C.c_int32), ("adaptive_p2", C.c_int32), ("reserved", C.c_int32 * 5)]
+
+
+def _bind(lib):
+    vp, i32 = C.c_void_p, C.c_int32
+    lib.fsgm_sgm_params_default.restype = SgmParams
+    lib.fsgm_sgm_batch_host.argtypes = [i32, vp, i32, i32, i32, i32, i32, C.POINTER(SgmParams), vp, vp, vp, vp]
+    lib.fsgm_sgm_device.argtypes = [i32, vp, i32, i32, i32, i32, i32, C.POINTER(SgmParams), vp, vp, vp, vp, vp, vp]
+    lib.fsgm_sgm_last_kernel.restype = C.c_char_p
+    lib.fsgm_sgm_ingest_lds.argtypes = [i32, i32, C.POINTER(C.c_uint64)]
+    lib.fsgm_epi_plan_ingest_cost_device.argtypes = [vp, i32, vp, i32, i32, vp, vp]
+    return lib
+
+
+def layout_code(layout):
+    if layout not in LAYOUTS:
+        raise ValueError(f"layout must be 'hwd' or 'dhw' (got {layout!r})")
+    return LAYOUTS[layout]
+
+
+def params(lib, *, paths=4, subpixel=1, device=0, agg_mode=0, layout="hwd", cost_bound=255, adaptive_p2=0):
+    p = lib.fsgm_sgm_params_default()
+    p.paths, p.subpixel, p.device, p.agg_mode = int(paths), int(subpixel), int(device), int(agg_mode)
+    p.layout, p.cost_bound, p.adaptive_p2 = layout_code(layout), int(cost_bound), int(adaptive_p2)
+    return p
+
+
+def shape_of(shape, layout):
+    """(N or None, H, W, D) of a volume's or a batch's shape in that layout."""
+    if len(shape) not in (3, 4):
+        want = "(H, W, D) or (N, H, W, D)" if layout == "hwd" else "(D, H, W) or (N, D, H, W)"
+        raise TypeError(f"C must be {want} for layout {layout!r} (got {tuple(shape)})")
+    n = None if len(shape) == 3 else int(shape[0])
+    a, b, c = (int(v) for v in shape[-3:])
+    return (n, a, b, c) if layout == "hwd" else (n, b, c, a)
+
+
+def last_kernel():
+    """The pipeline that this thread's last sgm_batch / torch_ops.sgm call ran (EpiPlan.kernel_name's names)."""
+    return _bind(_lib.load()).fsgm_sgm_last_kernel().decode()
+
+
+def ingest_lds(layout, dMax):
+    """Bytes of LDS per workgroup of the kernel that brings volumes of this layout into a plan (no device needed)."""
+    b = C.c_uint64()
+    check(_bind(_lib.load()).fsgm_sgm_ingest_lds(layout_code(layout), int(dMax), C.byref(b)))
+    return int(b.value)
+
+
+def sgm_batch(Cvol, P1=7, P2=100, *, paths=4, layout="hwd", cost_bound=255, agg_mode=0, adaptive_p2=0, guide=None, subpixel=1,
+              return_sum=False, device=0):
+    """[bestD, minC] = sgm(C, P1, P2) (fsgm_amd.sgm) on a batch of volumes in one call, through one cached plan of that batch:
+    C uint8 (N, H, W, D) for layout "hwd" or (N, D, H, W) for "dhw" (a cost-volume network's output; transposed on the device);
+    one volume without the leading N.  bestD, minC uint32 (N, H, W); return_sum adds S uint32 (N, H, W, D).
+    cost_bound (1..255): no cost is larger -- small bounds open the fused pipelines, as census costs do; a volume above a bound
+    below 255 is refused (status 1).  agg_mode: EpiPlan.set_agg_mode's.  adaptive_p2=1 reads the edge-aware P2 from guide, the
+    first image, uint8 (N, H, W)."""
+    lib = _bind(_lib.load())
+    code = layout_code(layout)
+    Cvol = np.ascontiguousarray(Cvol)
+    if Cvol.dtype != np.uint8:
+        raise TypeError("C must be uint8")
+    n, H, W, D = shape_of(Cvol.shape, layout)
+    N = 1 if n is None else n
+    if guide is not None:
+        guide = np.ascontiguousarray(guide)
+        if guide.dtype != np.uint8 or guide.shape != (() if n is None else (n,)) + (H, W):
+            raise TypeError(f"guide must be uint8 of shape {(() if n is None else (n,)) + (H, W)}")
+    prm = params(lib, paths=paths, subpixel=subpixel, device=device, agg_mode=agg_mode, layout=layout, cost_bound=cost_bound,
+                 adaptive_p2=adaptive_p2)
+    assert prm.layout == code
+    bestD, minC = np.empty((N, H, W), np.uint32), np.empty((N, H, W), np.uint32)
+    S = np.empty((N, H, W, D), np.uint32) if return_sum else None
+    check(lib.fsgm_sgm_batch_host(N, ptr(Cvol), W, H, D, int(P1), int(P2), C.byref(prm), ptr(guide), ptr(bestD), ptr(minC), ptr(S)))
+    outs = (bestD, minC, S) if return_sum else (bestD, minC)
+    return outs if n is not None else tuple(o[0] for o in outs)

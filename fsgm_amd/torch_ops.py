@@ -7,7 +7,8 @@ points of include/fsgm.h ("Device-pointer entry points") as torch custom ops and
 
 No host<->device copy and no host wait once a plan for the shape exists: the work is queued behind what the current stream
 already holds, and what is queued on that stream afterwards runs after it.  Ops registered: fsgm::calc_cost_sgm,
-fsgm::calc_cost_sgm_linear, fsgm::stereo_sgm, fsgm::stereo_sgm_range,
+fsgm::calc_cost_sgm_linear, fsgm::stereo_sgm, fsgm::stereo_sgm_range, fsgm::sgm (a caller's cost volumes; status also
+FSGM_ERR_INVALID when a cost was above the declared bound),
 fsgm::epipolar_sgm_of, fsgm::pyramidal_sgm, fsgm::pyramidal_sgm_ng, fsgm::epipolar_flow_pp, fsgm::pyramidal_flow_pp (each also returns a 0-d int32
 status tensor: 0, or FSGM_ERR_HIP when an aggregation hand-off gave up; check=True in the wrappers synchronises and raises
 on it), fsgm::epi_postprocess (status FSGM_ERR_INVALID when a D1 value is negative), fsgm::vmf and fsgm::flow_fb_check; for rectified
@@ -29,6 +30,7 @@ from ._lib import EpiIn, EpiOut, EpiOptions, EpiParams, FsgmError, StereoParams
 from .epi import EpiGeometry, _d_min, _params as _epi_params, _stereo_params
 from .post import _bind as _bind_post
 from .stereo_pp import CHAIN_FIELDS as STEREO_PP_FIELDS, _bind as _bind_stereo_pp, pp_params as _stereo_pp_params
+from .sgm import _bind as _bind_sgm, layout_code as _layout_code, params as _sgm_params, shape_of as _sgm_shape
 from .pyramid import PyramidParams, NgPyramidParams, FLOW_PP_FIELDS, MATCHERS, _bind as _bind_pyramid, _bind_flow_pp, _bind_ng
 
 FSGM_ERR_INVALID, FSGM_ERR_HIP = 1, 2
@@ -60,6 +62,7 @@ _bind_ng(_L)
 _bind_post(_L)
 _bind_flow_pp(_L)
 _bind_stereo_pp(_L)
+_bind_sgm(_L)
 _L.fsgm_calc_cost_sgm_device.argtypes = [_i32, C.POINTER(EpiIn), C.POINTER(EpiOut), C.POINTER(EpiParams), _vp, _vp]
 _L.fsgm_calc_cost_sgm_linear_device.argtypes = [_i32, C.POINTER(EpiIn), C.POINTER(EpiOut), C.POINTER(EpiParams), _vp, _vp]
 _L.fsgm_stereo_sgm_device.argtypes = [_i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, C.POINTER(StereoParams), _vp, _vp, _vp, _vp, _vp, _vp]
@@ -245,6 +248,37 @@ def _(left, right, dMax, d_min, P1, P2, paths, subpixel, direction, fb_check, ad
     dev = left.device
     return ((torch.empty((N, H, W), dtype=torch.int32, device=dev), _u32((N, H, W), dev)) + _fb_outputs_i32(N, H, W, fb_check, dev)
             + (_status(dev),))
+
+
+@torch.library.custom_op("fsgm::sgm", mutates_args=())
+def _sgm_op(C_: torch.Tensor, guide: torch.Tensor, P1: int, P2: int, paths: int, layout: int, cost_bound: int, agg_mode: int,
+            adaptive_p2: int, subpixel: int, return_sum: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """C_ (N, H, W, D) for layout 0 or (N, D, H, W) for layout 1; guide (N, H, W), read with adaptive_p2 only."""
+    N, H, W, D = _sgm_out_shape(C_, layout)
+    dev = C_.device
+    C_ = C_.contiguous()                                  # (any byte offset will do: the ingest kernel assumes no alignment)
+    guide = guide.contiguous() if adaptive_p2 else None
+    bestD, minC, status = _u32((N, H, W), dev), _u32((N, H, W), dev), _status(dev)
+    S = _u32((N, H, W, D) if return_sum else (0,), dev)
+    prm = _sgm_params(_L, paths=paths, subpixel=subpixel, device=dev.index, agg_mode=agg_mode, layout="dhw" if layout else "hwd",
+                      cost_bound=cost_bound, adaptive_p2=adaptive_p2)
+    _call(dev, _L.fsgm_sgm_device, N, _p(C_), W, H, D, int(P1), int(P2), C.byref(prm), _p(guide), _p(bestD), _p(minC),
+          _p(S) if return_sum else None, _stream(dev), _p(status))
+    return bestD, minC, S, status
+
+
+def _sgm_out_shape(C_, layout):
+    if layout not in (0, 1):
+        raise ValueError(f"layout must be 0 (hwd) or 1 (dhw), got {layout}")
+    N, a, b, c = C_.shape
+    return (N, a, b, c) if layout == 0 else (N, b, c, a)
+
+
+@_sgm_op.register_fake
+def _(C_, guide, P1, P2, paths, layout, cost_bound, agg_mode, adaptive_p2, subpixel, return_sum):
+    N, H, W, D = _sgm_out_shape(C_, layout)
+    dev = C_.device
+    return _u32((N, H, W), dev), _u32((N, H, W), dev), _u32((N, H, W, D) if return_sum else (0,), dev), _status(dev)
 
 
 @torch.library.custom_op("fsgm::epipolar_sgm_of", mutates_args=())
@@ -552,6 +586,53 @@ def calc_cost_sgm_linear(I1, I2, dMax, pixelPosD0, normlizeDirection, P1, P2, *,
                                                                              int(adaptive_p2))
     outs = (bestD, minC, conf, bestD2) if fb_check else (bestD, minC)
     return _finish(outs, status, batched, check, return_status)
+
+
+def sgm(Cvol, P1=7, P2=100, *, layout="dhw", paths=4, cost_bound=255, agg_mode=0, adaptive_p2=0, guide=None, subpixel=1,
+        return_sum=False, check=False, return_status=False):
+    """bestD, minC = sgm(C, P1, P2) as fsgm_amd.sgm_batch, on a cost volume that is already in HBM: C uint8 (D, H, W) or a batch
+    (N, D, H, W) for layout "dhw" (a cost-volume network's output), (H, W, D) / (N, H, W, D) for "hwd".  The volume is read where
+    it lies, every output stays in HBM, the work is queued on the current stream.  bestD, minC uint32 (.., H, W); return_sum
+    adds S uint32 (.., H, W, D).  cost_bound: the caller's declaration that no cost is larger; the kernels are selected for it
+    and every cost is saturated at it on the way in.  The status tensor (return_status=True) is FSGM_ERR_INVALID when a cost was
+    above the bound (the outputs are then those of the saturated volume), FSGM_ERR_HIP when an aggregation hand-off gave up;
+    check=True synchronises and raises on either.  adaptive_p2=1 needs guide, the first image, uint8 (.., H, W)."""
+    code = _layout_code(layout)
+    named = {"C": (Cvol, torch.uint8)}
+    if guide is not None:
+        named["guide"] = (guide, torch.uint8)
+    _tensors(named)
+    n, H, W, D = _sgm_shape(Cvol.shape, layout)
+    batched = n is not None
+    if int(adaptive_p2) not in (0, 1):
+        raise ValueError(f"adaptive_p2 must be 0 or 1 (got {adaptive_p2!r})")
+    if guide is not None:                                  # (adaptive_p2 without one: the library refuses, status 1)
+        _shape("guide", guide, ((n,) if batched else ()) + (H, W))
+    if not batched:
+        Cvol = Cvol.unsqueeze(0)
+        guide = None if guide is None else guide.unsqueeze(0)
+    if guide is None or not adaptive_p2:
+        guide = torch.empty((0,), dtype=torch.uint8, device=Cvol.device)
+    bestD, minC, S, status = torch.ops.fsgm.sgm(Cvol, guide, int(P1), int(P2), int(paths), code, int(cost_bound), int(agg_mode),
+                                                int(adaptive_p2), int(subpixel), int(bool(return_sum)))
+    outs = (bestD, minC, S) if return_sum else (bestD, minC)
+    return _finish(outs, status, batched, check, return_status, "a cost above cost_bound, or an aggregation hand-off that gave up")
+
+
+def ingest_cost(plan, Cvol, *, layout="dhw", cost_bound=255, check=False, return_status=False):
+    """All `plan.batch` cost volumes of an EpiPlan from a uint8 tensor on the plan's GPU (fsgm_epi_plan_ingest_cost_device): (N, D, H, W)
+    for layout "dhw", (N, H, W, D) for "hwd", saturated at cost_bound, which the plan then selects its kernels by.  What
+    EpiPlan.upload_cost does from the host, frame by frame.  Returns the status tensor with return_status=True, else None."""
+    code = _layout_code(layout)
+    dev = _tensors({"C": (Cvol, torch.uint8)})
+    if dev.index != plan.device:
+        raise TypeError(f"the tensor is on {dev}, the plan on device {plan.device}")
+    _shape("C", Cvol, (plan.batch, plan.H, plan.W, plan.D) if layout == "hwd" else (plan.batch, plan.D, plan.H, plan.W))
+    Cvol = Cvol.contiguous()
+    status = _status(dev)
+    _call(dev, _L.fsgm_epi_plan_ingest_cost_device, plan._h, plan.batch, _p(Cvol), code, int(cost_bound), _stream(dev), _p(status))
+    res = _finish((), status, True, check, return_status, "a cost above cost_bound")
+    return res[0] if return_status else None
 
 
 def stereo_sgm(left, right, dMax, P1=6, P2=64, *, paths=4, subpixel=1, direction=-1, fb_check=0, check=False, return_status=False,

@@ -300,6 +300,39 @@ fsgm_status fsgm_measure_copy_bandwidth2(int32_t device, size_t bytes, int32_t i
 fsgm_status fsgm_sgm_host(const uint8_t* C, int32_t width, int32_t height, int32_t dMax, int32_t P1, int32_t P2,
                           int32_t paths, uint32_t* bestD, uint32_t* minC, uint32_t* S, int32_t device);
 
+/* sgm(C, P1, P2) on a batch of caller-supplied volumes, with every aggregation pipeline of the plans within reach (the
+ * call above: one frame, a batch-1 plan, the line kernels only).  fsgm_sgm_device, under "Device-pointer entry points"
+ * below, is the same call on volumes that are already in HBM.
+ * C: n_frames contiguous u8 volumes, each [H][W][dMax] (FSGM_COST_LAYOUT_HWD, d fastest: fsgm_sgm_host's) or [dMax][H][W]
+ * (FSGM_COST_LAYOUT_DHW: a contiguous torch (N, D, H, W) tensor, transposed on the device on the way in).
+ * bestD, minC u32 [n][H][W] as fsgm_sgm_host's; S (may be NULL) u32 [n][H][W][dMax], d fastest in either layout.
+ * cost_bound, 1..255: the caller's declaration that no byte of C is larger.  The pipelines' no-wrap budgets are chosen from
+ * it (a volume of small costs reaches the fused pipelines, as census costs <= 24 do), which is why the device form, which
+ * may not wait for the device to learn the true maximum, needs it.  The host form scans C as fsgm_sgm_host does and uses
+ * min(true maximum, cost_bound); a volume with a byte above a cost_bound below 255 is FSGM_ERR_INVALID and nothing is written.
+ * agg_mode: fsgm_epi_plan_set_agg_mode's (0 auto, by n_frames) on the cached plan; plans of different modes are distinct.
+ * adaptive_p2 = 1: the reference's edge-aware P2 (fsgm_epi_options), read from guide, the first image, u8 [n][H][W];
+ * guide NULL with adaptive_p2 is FSGM_ERR_INVALID, agg_mode 2..6 with it FSGM_ERR_UNSUPPORTED (line kernels only).
+ * Refused before a device is touched: n_frames / width / height < 1, dMax outside 1..1024, paths other than 4 or 8, a
+ * layout or cost_bound outside the above, subpixel / adaptive_p2 other than 0 or 1, agg_mode outside 0..6, a NULL C, bestD
+ * or minC, non-zero reserved words (all FSGM_ERR_INVALID). */
+#define FSGM_COST_LAYOUT_HWD 0
+#define FSGM_COST_LAYOUT_DHW 1
+typedef struct {
+    int32_t paths, subpixel, device, agg_mode, layout, cost_bound, adaptive_p2;
+    int32_t reserved[5];       /* must be zero */
+} fsgm_sgm_params;
+fsgm_sgm_params fsgm_sgm_params_default(void);   /* 4, 1, 0, 0 (auto), FSGM_COST_LAYOUT_HWD, 255, 0 */
+fsgm_status fsgm_sgm_batch_host(int32_t n_frames, const uint8_t* C, int32_t width, int32_t height, int32_t dMax, int32_t P1,
+                                int32_t P2, const fsgm_sgm_params* prm, const uint8_t* guide, uint32_t* bestD, uint32_t* minC,
+                                uint32_t* S);
+/* the pipeline (fsgm_epi_plan_kernel_name's names) that the calling thread's last fsgm_sgm_batch_host / fsgm_sgm_device ran,
+ * "" before the first */
+const char* fsgm_sgm_last_kernel(void);
+/* The static LDS (bytes per workgroup) of the kernel that brings volumes of this layout into a plan, answered without a
+ * device: 0 for FSGM_COST_LAYOUT_HWD (a copy), one padded tile for FSGM_COST_LAYOUT_DHW whatever dMax (1..1024) is. */
+fsgm_status fsgm_sgm_ingest_lds(int32_t layout, int32_t dMax, uint64_t* bytes);
+
 /* census(img, cen, width, height) of common.cpp:3-27 on its own: u8 [H][W] -> u32 [H][W], 5x5 window, replicate
  * border, `neighbour >= centre`, first tap at bit 25, trailing shift (bit 0 = 0).  Any width/height >= 1. */
 fsgm_status fsgm_census_host(const uint8_t* img, int32_t width, int32_t height, uint32_t* cen, int32_t device);
@@ -872,7 +905,8 @@ void fsgm_shard_frames(int32_t n_frames, int32_t n_devices, int32_t slot, int32_
  * status (device memory, may be NULL): one int32, written on `stream` at the end -- 0, or FSGM_ERR_HIP when a bounded
  * hand-off poll of the aggregation gave up (what fsgm_epi_plan_sync reports on the host paths).
  * A stream that is being captured into a graph is refused with FSGM_ERR_UNSUPPORTED before anything is queued.
- * The debug taps (out->C / out->S, per-level pyramid flows) are not offered: a non-NULL C or S is FSGM_ERR_UNSUPPORTED.
+ * The debug taps (out->C / out->S, per-level pyramid flows) are not offered: a non-NULL C or S is FSGM_ERR_UNSUPPORTED
+ * (fsgm_sgm_device alone offers S).
  * Results are bit for bit those of the host entry points for the same inputs.
  * ------------------------------------------------------------------------------------------ */
 /* All `batch` frames of a plan (n_frames must equal the plan's batch), cost stage + aggregation + WTA in the plan's
@@ -906,6 +940,22 @@ fsgm_status fsgm_stereo_sgm_device_range(int32_t n_frames, const uint8_t* I1, co
                                          int32_t dMax, int32_t P1, int32_t P2, const fsgm_stereo_params* prm,
                                          const fsgm_epi_options* opt, int32_t d_min, int32_t* disp, uint32_t* minC, uint8_t* conf,
                                          int32_t* disp2, void* stream, int32_t* status);
+/* fsgm_sgm_batch_host on device pointers (one cached plan of batch n_frames per shape, paths, agg_mode and adaptive_p2): C in
+ * either layout is brought into the plan's own volume by one kernel pass that stores min(byte, prm->cost_bound), then the
+ * aggregation and WTA selected for cost_bound run on it -- saturating keeps every kernel inside the no-wrap budget it was
+ * selected for.  status: 0, FSGM_ERR_HIP when an aggregation hand-off gave up, or FSGM_ERR_INVALID when some byte of C was
+ * above cost_bound: the outputs are then those of the saturated volume.  guide (adaptive_p2) is copied device to device.
+ * Unlike every other entry point of this section this one offers S (may be NULL; device memory, u32 [n][H][W][dMax]): it is
+ * rebuilt frame by frame after the run, as fsgm_epi_plan_download_sum does, and copied device to device.  Everything else
+ * follows the contract above. */
+fsgm_status fsgm_sgm_device(int32_t n_frames, const uint8_t* C, int32_t width, int32_t height, int32_t dMax, int32_t P1, int32_t P2,
+                            const fsgm_sgm_params* prm, const uint8_t* guide, uint32_t* bestD, uint32_t* minC, uint32_t* S,
+                            void* stream, int32_t* status);
+/* The first step of fsgm_sgm_device on its own, into a caller's plan: n_frames (= the plan's batch) volumes in `layout` from
+ * device memory into the plan's cost volumes (what fsgm_epi_plan_upload_cost fills from the host), saturated at cost_bound,
+ * which becomes the bound the plan selects its kernels by.  status: 0 or FSGM_ERR_INVALID (a byte above cost_bound). */
+fsgm_status fsgm_epi_plan_ingest_cost_device(fsgm_epi_plan* plan, int32_t n_frames, const uint8_t* C, int32_t layout,
+                                             int32_t cost_bound, void* stream, int32_t* status);
 /* epipolar_sgm_of on n_frames image pairs, one plan of batch n_frames: g (HOST memory) holds n_frames geometries, each
  * passed to the maps kernel by value.  I0 / I1 u8 [n][channels][H][W]; flow f64 [n][3][H][W]; minC (may be NULL) u32 [n][H][W]. */
 fsgm_status fsgm_epipolar_sgm_of_device(int32_t n_frames, const uint8_t* I0, const uint8_t* I1, int32_t width,
