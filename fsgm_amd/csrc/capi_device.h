@@ -2,15 +2,24 @@
 // pointer checks, the capture refusal, the event join with the caller's stream and the status word.
 #pragma once
 #include "capi_common.h"
+#include <initializer_list>
 
 namespace fsgm {
 
-// FSGM_ERR_UNSUPPORTED when `s` is being captured into a graph (nothing may be queued then), FSGM_ERR_HIP when the
-// runtime cannot tell
-fsgm_status device_check_stream(hipStream_t s, const char* who);
-// `p` (may be NULL when !required) must be device memory of `device`, aligned to `align`, with `bytes` bytes inside its
-// allocation; a failed runtime query is cleared so that it does not surface in a later hipGetLastError
-fsgm_status device_check_ptr(const void* p, size_t bytes, size_t align, int device, bool required, const char* who, const char* what);
+// One row of an entry point's check table: `p` (may be NULL when !required) must be device memory of the call's device,
+// aligned to `align`, with `bytes` bytes inside its allocation.  A pointer that the call reads only under a condition is
+// passed as `cond ? ptr : nullptr`, one that is required only under a condition with `required = cond`.
+struct DevicePtr {
+    const void* p;
+    size_t bytes, align;
+    bool required;
+    const char* what;
+};
+// The checks of every device entry point behind its own argument checks, in this order: `device` made current
+// (use_device), the caller's stream `cs` refused while it is captured into a graph (FSGM_ERR_UNSUPPORTED: nothing may be
+// queued then), each pointer checked in list order (FSGM_ERR_INVALID).  Entry points call it before they look up or build
+// a plan: a call refused here has allocated nothing.
+fsgm_status device_check_args(const char* who, int device, hipStream_t cs, std::initializer_list<DevicePtr> ptrs);
 
 // The two events of a plan's device calls: `in` recorded on the caller's stream and waited for by the plan's stream,
 // `out` recorded on the plan's stream and waited for by the caller's.  Created on a plan's first device call.
@@ -22,8 +31,25 @@ struct DeviceJoin {
     fsgm_status leave(hipStream_t plan, hipStream_t caller);
 };
 
-// One wave on `st`: *status = (flag && *flag) ? FSGM_ERR_HIP : 0, *flag cleared (either pointer may be NULL)
-void launch_device_status(hipStream_t st, uint32_t* flag, int32_t* status);
+// One device call on a plan: the plan's stream waits for the caller's, work() queues everything on the plan's stream (the
+// status word last, and only when it succeeds), the caller's stream waits for the plan's -- on every exit once the join is
+// entered, so whatever was queued stays ordered before the caller's later work.  Returns work's status, else a failed
+// launch as FSGM_ERR_HIP, else the join's.
+template <class Work>
+fsgm_status device_call(DeviceJoin& j, hipStream_t caller, hipStream_t plan, Work&& work) {
+    fsgm_status st;
+    if ((st = j.ensure()) != FSGM_OK || (st = j.enter(caller, plan)) != FSGM_OK) return st;
+    st = work();
+    const hipError_t le = hipGetLastError();                     // (collected on every path: no later call inherits it)
+    const fsgm_status js = j.leave(plan, caller);
+    if (st != FSGM_OK) return st;
+    if (le != hipSuccess) return fail(FSGM_ERR_HIP, "a launch of the device call failed: %s", hipGetErrorString(le));
+    return js;
+}
+
+// One wave on `st`: *status = *hip_flag ? FSGM_ERR_HIP : *invalid_flag ? FSGM_ERR_INVALID : 0, both flags cleared (each
+// pointer may be NULL; nothing is launched when all three are)
+void launch_device_status(hipStream_t st, uint32_t* hip_flag, uint32_t* invalid_flag, int32_t* status);
 
 // Swaps a plan's buffer pointer for the caller's for the length of one enqueue and puts it back on every exit.
 template <class T>

@@ -5,7 +5,7 @@
 
 namespace fsgm {
 
-fsgm_status device_check_stream(hipStream_t s, const char* who) {
+static fsgm_status device_check_stream(hipStream_t s, const char* who) {
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     const hipError_t e = hipStreamIsCapturing(s, &cs);
     if (e == hipErrorStreamCaptureImplicit || (e == hipSuccess && cs != hipStreamCaptureStatusNone)) {
@@ -19,7 +19,8 @@ fsgm_status device_check_stream(hipStream_t s, const char* who) {
     return FSGM_OK;
 }
 
-fsgm_status device_check_ptr(const void* p, size_t bytes, size_t align, int device, bool required, const char* who, const char* what) {
+// a failed runtime query is cleared so that it does not surface in a later hipGetLastError
+static fsgm_status device_check_ptr(const void* p, size_t bytes, size_t align, int device, bool required, const char* who, const char* what) {
     if (!p) {
         if (required) return fail(FSGM_ERR_INVALID, "%s: %s is NULL", who, what);
         return FSGM_OK;
@@ -49,6 +50,14 @@ fsgm_status device_check_ptr(const void* p, size_t bytes, size_t align, int devi
     return FSGM_OK;
 }
 
+fsgm_status device_check_args(const char* who, int device, hipStream_t cs, std::initializer_list<DevicePtr> ptrs) {
+    fsgm_status st = use_device(device);
+    if (st != FSGM_OK || (st = device_check_stream(cs, who)) != FSGM_OK) return st;
+    for (const DevicePtr& d : ptrs)
+        if ((st = device_check_ptr(d.p, d.bytes, d.align, device, d.required, who, d.what)) != FSGM_OK) return st;
+    return FSGM_OK;
+}
+
 fsgm_status DeviceJoin::ensure() {
     if (!in) FSGM_HIP(hipEventCreateWithFlags(&in, hipEventDisableTiming));
     if (!out) FSGM_HIP(hipEventCreateWithFlags(&out, hipEventDisableTiming));
@@ -73,16 +82,18 @@ fsgm_status DeviceJoin::leave(hipStream_t plan, hipStream_t caller) {
     return FSGM_OK;
 }
 
-__global__ __launch_bounds__(64) void device_status_kernel(uint32_t* __restrict__ flag, int32_t* __restrict__ status) {
+__global__ __launch_bounds__(64) void device_status_kernel(uint32_t* __restrict__ hip_flag, uint32_t* __restrict__ invalid_flag,
+                                                           int32_t* __restrict__ status) {
     if (threadIdx.x != 0) return;
-    uint32_t f = 0;
-    if (flag) { f = *flag; *flag = 0; }
-    if (status) *status = f != 0 ? (int32_t)FSGM_ERR_HIP : 0;
+    uint32_t h = 0, v = 0;
+    if (hip_flag) { h = *hip_flag; *hip_flag = 0; }
+    if (invalid_flag) { v = *invalid_flag; *invalid_flag = 0; }
+    if (status) *status = h != 0 ? (int32_t)FSGM_ERR_HIP : v != 0 ? (int32_t)FSGM_ERR_INVALID : 0;
 }
 
-void launch_device_status(hipStream_t st, uint32_t* flag, int32_t* status) {
-    if (!flag && !status) return;
-    hipLaunchKernelGGL(device_status_kernel, dim3(1), dim3(64), 0, st, flag, status);
+void launch_device_status(hipStream_t st, uint32_t* hip_flag, uint32_t* invalid_flag, int32_t* status) {
+    if (!hip_flag && !invalid_flag && !status) return;
+    hipLaunchKernelGGL(device_status_kernel, dim3(1), dim3(64), 0, st, hip_flag, invalid_flag, status);
 }
 
 }  // namespace fsgm

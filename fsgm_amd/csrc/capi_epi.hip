@@ -343,10 +343,9 @@ fsgm_status fsgm_epi_plan_create(fsgm_epi_plan** out, int32_t W, int32_t H, int3
     return fsgm_epi_plan_create_sampling(out, W, H, D, batch, prm, FSGM_SAMPLING_VZ, 0);
 }
 
-fsgm_status fsgm_epi_plan_create_sampling(fsgm_epi_plan** out, int32_t W, int32_t H, int32_t D, int32_t batch,
-                                          const fsgm_epi_params* prm, int32_t sampling, int32_t direction) {
-    FSGM_REQUIRE(out, "fsgm_epi_plan_create: null plan pointer");
-    *out = nullptr;
+// what a plan can be refused for without a GPU (pr: vz_to_disp already cleared for the samplings that have none); the device
+// entry points that run on a cached plan ask this before they touch a device, as plan creation does
+static fsgm_status epi_plan_args(int W, int H, int D, int batch, const fsgm_epi_params& pr, int sampling, int direction) {
     FSGM_REQUIRE(sampling == FSGM_SAMPLING_VZ || sampling == FSGM_SAMPLING_LINEAR || sampling == FSGM_SAMPLING_RECTIFIED,
                  "fsgm_epi_plan_create: sampling must be FSGM_SAMPLING_VZ, _LINEAR or _RECTIFIED (got %d)", sampling);
     FSGM_REQUIRE(sampling != FSGM_SAMPLING_RECTIFIED || direction == -1 || direction == 1,
@@ -354,8 +353,6 @@ fsgm_status fsgm_epi_plan_create_sampling(fsgm_epi_plan** out, int32_t W, int32_
     FSGM_REQUIRE(W >= 1 && H >= 1, "fsgm_epi_plan_create: width/height must be >= 1 (got %d x %d)", W, H);
     FSGM_REQUIRE(D >= 1, "fsgm_epi_plan_create: dMax must be >= 1 (got %d)", D);
     FSGM_REQUIRE(batch >= 1, "fsgm_epi_plan_create: batch must be >= 1");
-    fsgm_epi_params pr = prm ? *prm : fsgm_epi_params_default();
-    if (sampling != FSGM_SAMPLING_VZ) pr.vz_to_disp = 0;         // bestD is the index * 256, never converted (:592-594)
     FSGM_REQUIRE(pr.paths == 4 || pr.paths == 8, "fsgm_epi_plan_create: paths must be 4 or 8 (got %d)", pr.paths);
     if (pr.fb_check && D > 511)
         return fail(FSGM_ERR_UNSUPPORTED, "fb_check needs dMax <= 511 (bestD must stay below INVALID_DISPARITY)");
@@ -363,6 +360,16 @@ fsgm_status fsgm_epi_plan_create_sampling(fsgm_epi_plan** out, int32_t W, int32_
         return fail(FSGM_ERR_UNSUPPORTED, "dMax %d exceeds the supported maximum %d", D, FSGM_GENERIC_MAX_D);
     if ((double)W * H * D >= 2147483648.0)
         return fail(FSGM_ERR_UNSUPPORTED, "cost volume %d x %d x %d exceeds 2^31 voxels per frame", W, H, D);
+    return FSGM_OK;
+}
+
+fsgm_status fsgm_epi_plan_create_sampling(fsgm_epi_plan** out, int32_t W, int32_t H, int32_t D, int32_t batch,
+                                          const fsgm_epi_params* prm, int32_t sampling, int32_t direction) {
+    FSGM_REQUIRE(out, "fsgm_epi_plan_create: null plan pointer");
+    *out = nullptr;
+    fsgm_epi_params pr = prm ? *prm : fsgm_epi_params_default();
+    if (sampling != FSGM_SAMPLING_VZ) pr.vz_to_disp = 0;         // bestD is the index * 256, never converted (:592-594)
+    { const fsgm_status as = epi_plan_args(W, H, D, batch, pr, sampling, direction); if (as != FSGM_OK) return as; }
     { const fsgm_status ds = use_device(pr.device); if (ds != FSGM_OK) return ds; }
 
     fsgm_epi_plan* p = new fsgm_epi_plan;
@@ -1440,9 +1447,7 @@ fsgm_status sgm_run_device(const SgmCall& c, hipStream_t cs, int32_t* status) {
     if ((st = prepare(p, FSGM_STAGE_AGGREGATE | FSGM_STAGE_WTA)) != FSGM_OK) return st;
     if ((st = ensure_ingest_flag(p)) != FSGM_OK) return st;
     if (c.S && (st = ensure_tap_buffers(p)) != FSGM_OK) return st;
-    if ((st = p->join.ensure()) != FSGM_OK) return st;
-    if ((st = p->join.enter(cs, p->stream)) != FSGM_OK) return st;
-    st = [&]() -> fsgm_status {
+    return device_call(p->join, cs, p->stream, [&]() -> fsgm_status {
         launch_sgm_ingest(p->stream, c.C, p->dC, c.n, c.W, c.H, c.D, c.prm.layout, c.prm.cost_bound, p->dIngestFlag);
         if (c.guide) FSGM_HIP(hipMemcpyAsync(p->dI1, c.guide, (size_t)c.n * p->NP, hipMemcpyDeviceToDevice, p->stream));
         Bind<uint32_t> bd(p->dBestD, c.bestD), mc(p->dMinC, c.minC);
@@ -1453,14 +1458,9 @@ fsgm_status sgm_run_device(const SgmCall& c, hipStream_t cs, int32_t* status) {
             tap_sum(p, f);
             FSGM_HIP(hipMemcpyAsync(c.S + (size_t)f * p->N, p->dS, p->N * 4, hipMemcpyDeviceToDevice, p->stream));
         }
+        launch_device_status(p->stream, p->dBandErr, p->dIngestFlag, status);
         return FSGM_OK;
-    }();
-    // the status word, then the caller's stream waits for the plan's (also after a failed enqueue, as epi_device_finish)
-    if (st == FSGM_OK) launch_sgm_status(p->stream, p->dBandErr, p->dIngestFlag, status);
-    const fsgm_status js = p->join.leave(p->stream, cs);
-    if (st != FSGM_OK) return st;
-    FSGM_HIP(hipGetLastError());
-    return js;
+    });
 }
 
 }  // namespace fsgm
@@ -1477,24 +1477,18 @@ fsgm_status fsgm_epi_plan_ingest_cost_device(fsgm_epi_plan* p, int32_t n, const 
     FSGM_REQUIRE(layout == FSGM_COST_LAYOUT_HWD || layout == FSGM_COST_LAYOUT_DHW,
                  "%s: layout must be FSGM_COST_LAYOUT_HWD (0) or FSGM_COST_LAYOUT_DHW (1), got %d", who, layout);
     FSGM_REQUIRE(cost_bound >= 1 && cost_bound <= 255, "%s: cost_bound must be 1..255 (got %d)", who, cost_bound);
-    const int dev = p->prm.device;
     const hipStream_t cs = (hipStream_t)stream;
     fsgm_status st;
-    FSGM_HIP(hipSetDevice(dev));
-    if ((st = device_check_stream(cs, who)) != FSGM_OK ||
-        (st = device_check_ptr(C, (size_t)n * p->N, 1, dev, true, who, "C")) != FSGM_OK ||
-        (st = device_check_ptr(status, 4, 4, dev, false, who, "status")) != FSGM_OK)
+    if ((st = device_check_args(who, p->prm.device, cs, {{C, (size_t)n * p->N, 1, true, "C"}, {status, 4, 4, false, "status"}})) != FSGM_OK)
         return st;
     if ((st = ensure_ingest_flag(p)) != FSGM_OK) return st;
     p->cmax.assign(n, cost_bound);
     select_kernel(p);
-    if ((st = p->join.ensure()) != FSGM_OK) return st;
-    if ((st = p->join.enter(cs, p->stream)) != FSGM_OK) return st;
-    launch_sgm_ingest(p->stream, C, p->dC, n, p->W, p->H, p->D, layout, cost_bound, p->dIngestFlag);
-    launch_sgm_status(p->stream, nullptr, p->dIngestFlag, status);
-    st = p->join.leave(p->stream, cs);
-    FSGM_HIP(hipGetLastError());
-    return st;
+    return device_call(p->join, cs, p->stream, [&] {
+        launch_sgm_ingest(p->stream, C, p->dC, n, p->W, p->H, p->D, layout, cost_bound, p->dIngestFlag);
+        launch_device_status(p->stream, nullptr, p->dIngestFlag, status);
+        return FSGM_OK;
+    });
 }
 
 // census() of common.cpp:3-27 alone (the one function of the path that the reference's own sources pin here)
@@ -1583,26 +1577,14 @@ static fsgm_status epi_device_args(const char* who, int32_t n, const fsgm_epi_in
 }
 
 // What a warm call must not do -- allocate, upload a table, synchronise -- happens here on a plan's first call, before the
-// join with the caller's stream.
-static fsgm_status epi_device_enter(fsgm_epi_plan* p, int P1, int P2, double vMax, hipStream_t cs) {
+// join with the caller's stream (device_call).
+static fsgm_status epi_device_prepare(fsgm_epi_plan* p, int P1, int P2, double vMax) {
     fsgm_status st;
     if ((st = fsgm_epi_plan_set_penalties(p, P1, P2, vMax)) != FSGM_OK) return st;
     if ((st = ensure_cost_buffers(p)) != FSGM_OK) return st;
     if ((st = ensure_vz(p)) != FSGM_OK) return st;
     p->have_img.assign(p->batch, 1);                             // the caller's images stand in for the plan's for this enqueue
-    if ((st = prepare(p, FSGM_STAGE_ALL)) != FSGM_OK) return st;
-    if ((st = p->join.ensure()) != FSGM_OK) return st;
-    return p->join.enter(cs, p->stream);
-}
-
-// the status word, then the caller's stream waits for the plan's (also after a failed enqueue: whatever was queued stays
-// ordered before the caller's later work)
-static fsgm_status epi_device_finish(fsgm_epi_plan* p, hipStream_t cs, int32_t* status, fsgm_status st) {
-    if (st == FSGM_OK) launch_device_status(p->stream, p->dBandErr, status);
-    const fsgm_status js = p->join.leave(p->stream, cs);
-    if (st != FSGM_OK) return st;
-    FSGM_HIP(hipGetLastError());
-    return js;
+    return prepare(p, FSGM_STAGE_ALL);
 }
 
 // a batch on device pointers through the caller's plan p, or (p null) through the cached plan for prm
@@ -1612,45 +1594,47 @@ static fsgm_status epi_run_device(const char* who, fsgm_epi_plan* p, const fsgm_
     const bool linear = (p ? p->sampling : sampling) == FSGM_SAMPLING_LINEAR;
     fsgm_status st = epi_device_args(who, n, in, out, linear);
     if (st != FSGM_OK) return st;
-    std::unique_lock<std::mutex> lk;
-    if (!p) {
-        fsgm_epi_params pr = prm ? *prm : fsgm_epi_params_default();
+    fsgm_epi_params pr = prm ? *prm : fsgm_epi_params_default();   // (the cached plan's key; a caller's plan has its own)
+    fsgm_epi_options o{};
+    if (p) {
+        FSGM_REQUIRE(p->sampling != FSGM_SAMPLING_RECTIFIED, "%s: a rectified plan runs through fsgm_stereo_sgm_device", who);
+        FSGM_REQUIRE(n == p->batch, "%s: n_frames %d differs from the plan's batch %d", who, n, p->batch);
+        FSGM_REQUIRE(in->width == p->W && in->height == p->H && in->dMax == p->D, "%s: shape %d x %d x %d differs from the plan's %d x %d x %d",
+                     who, in->width, in->height, in->dMax, p->W, p->H, p->D);
+        pr = p->prm;
+    } else {
         if (linear) pr.vz_to_disp = 0;
-        fsgm_epi_options o;
         if ((st = read_options(who, opt, &o)) != FSGM_OK) return st;
-        if ((st = cached_plan(lk, &p, in->width, in->height, in->dMax, n, pr, sampling, 0, o.adaptive_p2)) != FSGM_OK) return st;
+        FSGM_DEVICE_SLOT(pr.device);
+        if ((st = epi_plan_args(in->width, in->height, in->dMax, n, pr, sampling, 0)) != FSGM_OK) return st;
     }
-    FSGM_REQUIRE(p->sampling != FSGM_SAMPLING_RECTIFIED, "%s: a rectified plan runs through fsgm_stereo_sgm_device", who);
     const hipStream_t cs = (hipStream_t)stream;
-    FSGM_REQUIRE(n == p->batch, "%s: n_frames %d differs from the plan's batch %d", who, n, p->batch);
-    FSGM_REQUIRE(in->width == p->W && in->height == p->H && in->dMax == p->D, "%s: shape %d x %d x %d differs from the plan's %d x %d x %d",
-                 who, in->width, in->height, in->dMax, p->W, p->H, p->D);
-    const int dev = p->prm.device;
-    const size_t np = (size_t)n * p->NP;
-    const bool fb = p->prm.fb_check != 0;
-    FSGM_HIP(hipSetDevice(dev));
-    if ((st = device_check_stream(cs, who)) != FSGM_OK ||
-        (st = device_check_ptr(in->I1, np, 1, dev, true, who, "I1")) != FSGM_OK ||
-        (st = device_check_ptr(in->I2, np, 1, dev, true, who, "I2")) != FSGM_OK ||
-        (st = device_check_ptr(in->pixelPosD0, np * 16, 8, dev, true, who, "pixelPosD0")) != FSGM_OK ||
-        (st = device_check_ptr(in->normDir, np * 16, 8, dev, true, who, "normDir")) != FSGM_OK ||
-        (!linear && (st = device_check_ptr(in->offset, np * 8, 8, dev, true, who, "offset")) != FSGM_OK) ||
-        (st = device_check_ptr(out->bestD, np * 4, 4, dev, true, who, "bestD")) != FSGM_OK ||
-        (st = device_check_ptr(out->minC, np * 4, 4, dev, true, who, "minC")) != FSGM_OK ||
-        (fb && (st = device_check_ptr(out->conf, np, 1, dev, false, who, "conf")) != FSGM_OK) ||
-        (fb && (st = device_check_ptr(out->bestD2, np * 4, 4, dev, false, who, "bestD2")) != FSGM_OK) ||
-        (st = device_check_ptr(status, 4, 4, dev, false, who, "status")) != FSGM_OK)
+    const size_t np = (size_t)n * in->width * in->height;
+    const bool fb = pr.fb_check != 0;
+    if ((st = device_check_args(who, pr.device, cs, {{in->I1, np, 1, true, "I1"},
+                                                     {in->I2, np, 1, true, "I2"},
+                                                     {in->pixelPosD0, np * 16, 8, true, "pixelPosD0"},
+                                                     {in->normDir, np * 16, 8, true, "normDir"},
+                                                     {linear ? nullptr : in->offset, np * 8, 8, !linear, "offset"},
+                                                     {out->bestD, np * 4, 4, true, "bestD"},
+                                                     {out->minC, np * 4, 4, true, "minC"},
+                                                     {fb ? out->conf : nullptr, np, 1, false, "conf"},
+                                                     {fb ? out->bestD2 : nullptr, np * 4, 4, false, "bestD2"},
+                                                     {status, 4, 4, false, "status"}})) != FSGM_OK)
         return st;
-    if ((st = epi_device_enter(p, in->P1, in->P2, linear ? p->vMax : in->vMax, cs)) != FSGM_OK) return st;
-    {
+    std::unique_lock<std::mutex> lk;
+    if (!p && (st = cached_plan(lk, &p, in->width, in->height, in->dMax, n, pr, sampling, 0, o.adaptive_p2)) != FSGM_OK) return st;
+    if ((st = epi_device_prepare(p, in->P1, in->P2, linear ? p->vMax : in->vMax)) != FSGM_OK) return st;
+    return device_call(p->join, cs, p->stream, [&]() -> fsgm_status {
         Bind<uint8_t> i1(p->dI1, const_cast<uint8_t*>(in->I1)), i2(p->dI2, const_cast<uint8_t*>(in->I2));
         Bind<double> pd0(p->dPd0, const_cast<double*>(in->pixelPosD0)), nd(p->dNd, const_cast<double*>(in->normDir));
         Bind<double> off(p->dOff, linear ? nullptr : const_cast<double*>(in->offset));   // (linear: the plan's own 1.0 map)
         Bind<uint32_t> bd(p->dBestD, out->bestD), mc(p->dMinC, out->minC), d2(p->dD2, fb ? out->bestD2 : nullptr);
         Bind<uint8_t> conf(p->dConf, fb ? out->conf : nullptr);
-        st = enqueue(p, FSGM_STAGE_ALL);
-    }
-    return epi_device_finish(p, cs, status, st);
+        const fsgm_status es = enqueue(p, FSGM_STAGE_ALL);
+        if (es == FSGM_OK) launch_device_status(p->stream, p->dBandErr, nullptr, status);
+        return es;
+    });
 }
 
 fsgm_status fsgm_epi_plan_run_device(fsgm_epi_plan* p, int32_t n, const fsgm_epi_in* in, const fsgm_epi_out* out, void* stream,
@@ -1697,34 +1681,32 @@ static fsgm_status stereo_device(const char* who, int32_t n, const uint8_t* I1, 
     if (st != FSGM_OK) return st;
     if ((st = read_options(who, opt, &o)) != FSGM_OK) return st;
     FSGM_REQUIRE(d_min >= -FSGM_D_MIN_LIMIT && d_min <= FSGM_D_MIN_LIMIT, "%s: |d_min| must be <= %d (got %d)", who, FSGM_D_MIN_LIMIT, d_min);
-    // checks first, also on a shape's first call: nothing is allocated for a captured stream or a pointer that is refused
-    const int dev = pr.device;
     const size_t np = (size_t)n * (size_t)W * (size_t)H;
     const bool fb = pr.fb_check != 0;
     const hipStream_t cs = (hipStream_t)stream;
-    if ((st = use_device(dev)) != FSGM_OK) return st;
-    if ((st = device_check_stream(cs, who)) != FSGM_OK ||
-        (st = device_check_ptr(I1, np, 1, dev, true, who, "I1")) != FSGM_OK ||
-        (st = device_check_ptr(I2, np, 1, dev, true, who, "I2")) != FSGM_OK ||
-        (st = device_check_ptr(disp, np * 4, 4, dev, true, who, "disp")) != FSGM_OK ||
-        (st = device_check_ptr(minC, np * 4, 4, dev, true, who, "minC")) != FSGM_OK ||
-        (fb && (st = device_check_ptr(conf, np, 1, dev, false, who, "conf")) != FSGM_OK) ||
-        (fb && (st = device_check_ptr(disp2, np * 4, 4, dev, false, who, "disp2")) != FSGM_OK) ||
-        (st = device_check_ptr(status, 4, 4, dev, false, who, "status")) != FSGM_OK)
+    if ((st = device_check_args(who, pr.device, cs, {{I1, np, 1, true, "I1"},
+                                                     {I2, np, 1, true, "I2"},
+                                                     {disp, np * 4, 4, true, "disp"},
+                                                     {minC, np * 4, 4, true, "minC"},
+                                                     {fb ? conf : nullptr, np, 1, false, "conf"},
+                                                     {fb ? disp2 : nullptr, np * 4, 4, false, "disp2"},
+                                                     {status, 4, 4, false, "status"}})) != FSGM_OK)
         return st;
     std::unique_lock<std::mutex> lk;
     fsgm_epi_plan* p = nullptr;
     if ((st = cached_plan(lk, &p, W, H, dMax, n, pr, FSGM_SAMPLING_RECTIFIED, sp.direction, o.adaptive_p2)) != FSGM_OK) return st;
     p->d_min = d_min;
-    if ((st = epi_device_enter(p, P1, P2, p->vMax, cs)) != FSGM_OK) return st;
-    {
+    if ((st = epi_device_prepare(p, P1, P2, p->vMax)) != FSGM_OK) return st;
+    return device_call(p->join, cs, p->stream, [&]() -> fsgm_status {
         Bind<uint8_t> i1(p->dI1, const_cast<uint8_t*>(I1)), i2(p->dI2, const_cast<uint8_t*>(I2));
         Bind<uint32_t> bd(p->dBestD, disp), mc(p->dMinC, minC), d2(p->dD2, fb ? disp2 : nullptr);
         Bind<uint8_t> cf(p->dConf, fb ? conf : nullptr);
-        st = enqueue(p, FSGM_STAGE_ALL);
-        if (st == FSGM_OK && ranged) launch_stereo_range(p->stream, disp, fb ? disp2 : nullptr, np, d_min);
-    }
-    return epi_device_finish(p, cs, status, st);
+        const fsgm_status es = enqueue(p, FSGM_STAGE_ALL);
+        if (es != FSGM_OK) return es;
+        if (ranged) launch_stereo_range(p->stream, disp, fb ? disp2 : nullptr, np, d_min);
+        launch_device_status(p->stream, p->dBandErr, nullptr, status);
+        return FSGM_OK;
+    });
 }
 
 fsgm_status fsgm_stereo_sgm_device_opts(int32_t n, const uint8_t* I1, const uint8_t* I2, int32_t W, int32_t H, int32_t dMax, int32_t P1,
@@ -1850,24 +1832,24 @@ static fsgm_status device_drive(const char* who, bool pp, int32_t n, const uint8
     fsgm_epi_params pr;
     fsgm_status st = driver_args(who, pp, n, I0, I1, W, H, channels, g, dMax, prm, flow, flow2, &pr);
     if (st != FSGM_OK) return st;
+    FSGM_DEVICE_SLOT(pr.device);
+    if ((st = epi_plan_args(W, H, dMax, n, pr, FSGM_SAMPLING_VZ, 0)) != FSGM_OK) return st;
+    const size_t NP = (size_t)W * H, np = (size_t)n * NP;
+    const hipStream_t cs = (hipStream_t)stream;
+    if ((st = device_check_args(who, pr.device, cs, {{I0, np * channels, 1, true, "I0"},
+                                                     {I1, np * channels, 1, true, "I1"},
+                                                     {flow, np * 24, 8, true, "flow"},
+                                                     {pp ? flow2 : nullptr, np * 24, 8, pp, "flow2"},
+                                                     {pp ? D1 : nullptr, np * 8, 8, false, "D1"},
+                                                     {minC, np * 4, 4, false, "minC"},
+                                                     {status, 4, 4, false, "status"}})) != FSGM_OK)
+        return st;
     std::unique_lock<std::mutex> lk;
     fsgm_epi_plan* p = nullptr;
     if ((st = cached_plan(lk, &p, W, H, dMax, n, pr)) != FSGM_OK) return st;
-    const int dev = pr.device;
-    const size_t NP = p->NP, np = (size_t)n * NP;
-    const hipStream_t cs = (hipStream_t)stream;
-    if ((st = device_check_stream(cs, who)) != FSGM_OK ||
-        (st = device_check_ptr(I0, np * channels, 1, dev, true, who, "I0")) != FSGM_OK ||
-        (st = device_check_ptr(I1, np * channels, 1, dev, true, who, "I1")) != FSGM_OK ||
-        (st = device_check_ptr(flow, np * 24, 8, dev, true, who, "flow")) != FSGM_OK ||
-        (pp && (st = device_check_ptr(flow2, np * 24, 8, dev, true, who, "flow2")) != FSGM_OK) ||
-        (pp && (st = device_check_ptr(D1, np * 8, 8, dev, false, who, "D1")) != FSGM_OK) ||
-        (st = device_check_ptr(minC, np * 4, 4, dev, false, who, "minC")) != FSGM_OK ||
-        (st = device_check_ptr(status, 4, 4, dev, false, who, "status")) != FSGM_OK)
-        return st;
     if ((st = ensure_driver_buffers(p, 1, pp)) != FSGM_OK) return st;
-    if ((st = epi_device_enter(p, 6, 64, vMax, cs)) != FSGM_OK) return st;               // epipolar_sgm_of.m:19, test.m:36
-    {
+    if ((st = epi_device_prepare(p, 6, 64, vMax)) != FSGM_OK) return st;                 // epipolar_sgm_of.m:19, test.m:36
+    return device_call(p->join, cs, p->stream, [&]() -> fsgm_status {
         Bind<uint8_t> i1(p->dI1, channels == 1 ? const_cast<uint8_t*>(I0) : nullptr), i2(p->dI2, channels == 1 ? const_cast<uint8_t*>(I1) : nullptr);
         Bind<uint32_t> mc(p->dMinC, minC);
         if (channels == 3) {
@@ -1876,9 +1858,10 @@ static fsgm_status device_drive(const char* who, bool pp, int32_t n, const uint8
         }
         for (int f = 0; f < n; f++)
             launch_epi_maps(p->stream, geom_args(&g[f], W, H, p->dPd0 + f * 2 * NP, p->dNd + f * 2 * NP, p->dOff + f * NP, p->dRflow + f * 2 * NP));
-        st = enqueue_flow(p, pp, dMax, vMax, flow, flow2, D1 ? D1 : p->dD1);
-    }
-    return epi_device_finish(p, cs, status, st);
+        const fsgm_status es = enqueue_flow(p, pp, dMax, vMax, flow, flow2, D1 ? D1 : p->dD1);
+        if (es == FSGM_OK) launch_device_status(p->stream, p->dBandErr, nullptr, status);
+        return es;
+    });
 }
 
 fsgm_status fsgm_epipolar_sgm_of_device(int32_t n, const uint8_t* I0, const uint8_t* I1, int32_t W, int32_t H, int32_t channels,

@@ -127,22 +127,15 @@ static fsgm_status stage_host(const char* who, FlowStage stage, int32_t n, int32
     return FSGM_OK;
 }
 
-// sets the device, refuses a captured stream -- before any plan is looked up: nothing may be allocated under a capture
-static fsgm_status device_enter(const char* who, int device, hipStream_t cs) {
-    const fsgm_status st = use_device(device);
-    return st != FSGM_OK ? st : device_check_stream(cs, who);
-}
-
 static fsgm_status stage_device(const char* who, FlowStage stage, int32_t n, int32_t W, int32_t H, const StageArgs& a, int32_t device,
                                 void* stream) {
     fsgm_status st = flow_args(who, n, W, H, a.in && a.out && (stage != STAGE_FB || a.b), device);
     if (st != FSGM_OK || (st = stage_check(who, stage, a)) != FSGM_OK) return st;
     hipStream_t cs = (hipStream_t)stream;
-    if ((st = device_enter(who, device, cs)) != FSGM_OK) return st;
     const size_t bytes = 2 * (size_t)W * H * n * 8;
-    if ((st = device_check_ptr(a.in, bytes, 8, device, true, who, stage == STAGE_FB ? "f" : "flow")) != FSGM_OK ||
-        (st = device_check_ptr(a.b, bytes, 8, device, stage == STAGE_FB, who, "b")) != FSGM_OK ||
-        (st = device_check_ptr(a.out, bytes, 8, device, true, who, "the output flow")) != FSGM_OK)
+    if ((st = device_check_args(who, device, cs, {{a.in, bytes, 8, true, stage == STAGE_FB ? "f" : "flow"},
+                                                  {a.b, bytes, 8, stage == STAGE_FB, "b"},
+                                                  {a.out, bytes, 8, true, "the output flow"}})) != FSGM_OK)
         return st;
     if (stage == STAGE_FB) {                                     // no scratch: on the caller's stream itself
         launch_flow_fb_check(cs, a.in, a.b, a.out, W, H, a.p0, n);
@@ -152,15 +145,12 @@ static fsgm_status stage_device(const char* who, FlowStage stage, int32_t n, int
     std::unique_lock<std::mutex> lk;
     fsgm_flow_pp_plan* p;
     if ((st = flow_plan_get(lk, &p, W, H, n, device)) != FSGM_OK) return st;
-    if ((st = p->join.ensure()) != FSGM_OK) return st;
-    if ((st = p->join.enter(cs, p->stream)) != FSGM_OK) return st;
-    FSGM_HIP(hipStreamWaitEvent(p->stream, p->busy, 0));
-    stage_enqueue(p->stream, p, stage, a);
-    const hipError_t le = hipGetLastError();
-    (void)hipEventRecord(p->busy, p->stream);
-    const fsgm_status js = p->join.leave(p->stream, cs);
-    if (le != hipSuccess) return fail(FSGM_ERR_HIP, "%s: launch failed: %s", who, hipGetErrorString(le));
-    return js;
+    return device_call(p->join, cs, p->stream, [&]() -> fsgm_status {
+        FSGM_HIP(hipStreamWaitEvent(p->stream, p->busy, 0));
+        stage_enqueue(p->stream, p, stage, a);
+        FSGM_HIP(hipEventRecord(p->busy, p->stream));
+        return FSGM_OK;
+    });
 }
 
 // ---- the pipeline ----
@@ -297,25 +287,21 @@ fsgm_status fsgm_pyramidal_flow_pp_device(int32_t n, const uint8_t* I0, const ui
     FSGM_REQUIRE(channels == 1 || channels == 3, "%s: channels must be 1 (gray) or 3 (RGB planes), got %d", who, channels);
     hipStream_t cs = (hipStream_t)stream;
     const size_t np = (size_t)W * H * n, img = np * channels;
-    const int dev = prm->device;
-    if ((st = device_enter(who, dev, cs)) != FSGM_OK) return st;
-    if ((st = device_check_ptr(I0, img, 1, dev, true, who, "I0")) != FSGM_OK ||
-        (st = device_check_ptr(I1, img, 1, dev, true, who, "I1")) != FSGM_OK ||
-        (st = device_check_ptr(flow_pp, 3 * np * 8, 8, dev, true, who, "flow_pp")) != FSGM_OK ||
-        (st = device_check_ptr(flow_checked, 2 * np * 8, 8, dev, false, who, "flow_checked")) != FSGM_OK ||
-        (st = device_check_ptr(flow_fwd, 2 * np * 8, 8, dev, false, who, "flow_fwd")) != FSGM_OK ||
-        (st = device_check_ptr(flow_bwd, 2 * np * 8, 8, dev, false, who, "flow_bwd")) != FSGM_OK ||
-        (st = device_check_ptr(minC, np * 4, 4, dev, false, who, "minC")) != FSGM_OK ||
-        (st = device_check_ptr(status, 4, 4, dev, false, who, "status")) != FSGM_OK)
+    if ((st = device_check_args(who, prm->device, cs, {{I0, img, 1, true, "I0"},
+                                                       {I1, img, 1, true, "I1"},
+                                                       {flow_pp, 3 * np * 8, 8, true, "flow_pp"},
+                                                       {flow_checked, 2 * np * 8, 8, false, "flow_checked"},
+                                                       {flow_fwd, 2 * np * 8, 8, false, "flow_fwd"},
+                                                       {flow_bwd, 2 * np * 8, 8, false, "flow_bwd"},
+                                                       {minC, np * 4, 4, false, "minC"},
+                                                       {status, 4, 4, false, "status"}})) != FSGM_OK)
         return st;
     std::unique_lock<std::mutex> lk;
     fsgm_flow_pp_plan* p;
-    if ((st = flow_plan_get(lk, &p, W, H, n, dev)) != FSGM_OK) return st;
+    if ((st = flow_plan_get(lk, &p, W, H, n, prm->device)) != FSGM_OK) return st;
     return with_pair(n, W, H, channels, *prm, [&](const PyramidPair& pr) -> fsgm_status {
         hipStream_t s = pr.stream;
-        fsgm_status r;
-        if ((r = pr.join->ensure()) != FSGM_OK || (r = pr.join->enter(cs, s)) != FSGM_OK) return r;
-        auto work = [&]() -> fsgm_status {
+        return device_call(*pr.join, cs, s, [&]() -> fsgm_status {
             FSGM_HIP(hipMemcpyAsync(pr.in0, I0, img, hipMemcpyDeviceToDevice, s));
             FSGM_HIP(hipMemcpyAsync(pr.in1, I1, img, hipMemcpyDeviceToDevice, s));
             fsgm_status w = swap_enqueue(pr, I0, I1, img);
@@ -326,13 +312,10 @@ fsgm_status fsgm_pyramidal_flow_pp_device(int32_t n, const uint8_t* I0, const ui
             if (flow_fwd) FSGM_HIP(hipMemcpyAsync(flow_fwd, pr.flow, 2 * np * 8, hipMemcpyDeviceToDevice, s));
             if (flow_bwd) FSGM_HIP(hipMemcpyAsync(flow_bwd, pr.flow + 2 * np, 2 * np * 8, hipMemcpyDeviceToDevice, s));
             if (minC) FSGM_HIP(hipMemcpyAsync(minC, pr.minC, np * 4, hipMemcpyDeviceToDevice, s));
-            launch_device_status(s, nullptr, status);
             FSGM_HIP(hipEventRecord(p->busy, s));
+            launch_device_status(s, nullptr, nullptr, status);
             return FSGM_OK;
-        };
-        r = work();
-        const fsgm_status js = pr.join->leave(s, cs);            // on every exit: the caller's stream stays ordered behind what was queued
-        return r != FSGM_OK ? r : js;
+        });
     });
 }
 

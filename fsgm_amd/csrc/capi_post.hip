@@ -358,28 +358,24 @@ fsgm_status fsgm_epi_postprocess_device(int32_t n_frames, const double* D1, int3
     if (st != FSGM_OK) return st;
     const size_t np = (size_t)n_frames * W * H;
     hipStream_t cs = (hipStream_t)stream;
+    if ((st = device_check_args(who, device, cs, {{D1, np * 8, 8, true, "D1"},
+                                                  {Pd0, np * 16, 8, true, "Pd0"},
+                                                  {normDirect, np * 16, 8, true, "normDirect"},
+                                                  {O, np * 8, 8, true, "O"},
+                                                  {filterD1, np * 8, 8, true, "filterD1"},
+                                                  {filterD2, np * 8, 8, false, "filterD2"},
+                                                  {disp, np * 8, 8, false, "disp"},
+                                                  {status, 4, 4, false, "status"}})) != FSGM_OK)
+        return st;
     std::unique_lock<std::mutex> lk;
     fsgm_post_plan* p;
     if ((st = cached_plan(lk, &p, W, H, device, n_frames, false)) != FSGM_OK) return st;
-    if ((st = device_check_stream(cs, who)) != FSGM_OK) return st;
-    if ((st = device_check_ptr(D1, np * 8, 8, device, true, who, "D1")) != FSGM_OK ||
-        (st = device_check_ptr(Pd0, np * 16, 8, device, true, who, "Pd0")) != FSGM_OK ||
-        (st = device_check_ptr(normDirect, np * 16, 8, device, true, who, "normDirect")) != FSGM_OK ||
-        (st = device_check_ptr(O, np * 8, 8, device, true, who, "O")) != FSGM_OK ||
-        (st = device_check_ptr(filterD1, np * 8, 8, device, true, who, "filterD1")) != FSGM_OK ||
-        (st = device_check_ptr(filterD2, np * 8, 8, device, false, who, "filterD2")) != FSGM_OK ||
-        (st = device_check_ptr(disp, np * 8, 8, device, false, who, "disp")) != FSGM_OK ||
-        (st = device_check_ptr(status, 4, 4, device, false, who, "status")) != FSGM_OK)
-        return st;
-    if ((st = p->join.ensure()) != FSGM_OK) return st;
-    if ((st = p->join.enter(cs, p->stream)) != FSGM_OK) return st;
-    post_enqueue_batch(p->stream, post_plan_scratch(p), n_frames, W, H, D1, Pd0, normDirect, O, vMax, n, dMax, filterD1,
-                       filterD2 ? filterD2 : p->dD2, disp, status ? p->dNeg : nullptr);
-    if (status) launch_post_status(p->stream, p->dNeg, status);
-    const hipError_t le = hipGetLastError();
-    const fsgm_status js = p->join.leave(p->stream, cs);
-    if (le != hipSuccess) return fail(FSGM_ERR_HIP, "%s: launch failed: %s", who, hipGetErrorString(le));
-    return js;
+    return device_call(p->join, cs, p->stream, [&] {
+        post_enqueue_batch(p->stream, post_plan_scratch(p), n_frames, W, H, D1, Pd0, normDirect, O, vMax, n, dMax, filterD1,
+                           filterD2 ? filterD2 : p->dD2, disp, status ? p->dNeg : nullptr);
+        if (status) launch_device_status(p->stream, nullptr, p->dNeg, status);
+        return FSGM_OK;
+    });
 }
 
 fsgm_status fsgm_vmf_device(int32_t n_frames, const double* flow, int32_t W, int32_t H, int32_t channels, double* flowMed,
@@ -390,10 +386,7 @@ fsgm_status fsgm_vmf_device(int32_t n_frames, const double* flow, int32_t W, int
     FSGM_REQUIRE(channels >= 1 && channels <= 3, "%s: 1..3 channels (got %d)", who, channels);
     const size_t nv = (size_t)n_frames * channels * W * H;
     hipStream_t cs = (hipStream_t)stream;
-    FSGM_HIP(hipSetDevice(device));
-    if ((st = device_check_stream(cs, who)) != FSGM_OK) return st;
-    if ((st = device_check_ptr(flow, nv * 8, 8, device, true, who, "flow")) != FSGM_OK ||
-        (st = device_check_ptr(flowMed, nv * 8, 8, device, true, who, "flowMed")) != FSGM_OK)
+    if ((st = device_check_args(who, device, cs, {{flow, nv * 8, 8, true, "flow"}, {flowMed, nv * 8, 8, true, "flowMed"}})) != FSGM_OK)
         return st;
     launch_vmf(cs, flow, flowMed, W, H, n_frames * channels);   // no scratch: queued on the caller's stream itself
     FSGM_HIP(hipGetLastError());

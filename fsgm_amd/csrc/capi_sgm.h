@@ -14,7 +14,7 @@ struct SgmCall {
 
 // host pointers; cmax: the largest byte of each frame's volume (none above prm.cost_bound)
 fsgm_status sgm_run_host(const SgmCall& c, const int* cmax);
-// device pointers, checked (device_check_ptr / device_check_stream) by the caller; cs: the caller's stream
+// device pointers, checked (device_check_args) by the caller; cs: the caller's stream
 fsgm_status sgm_run_device(const SgmCall& c, hipStream_t cs, int32_t* status);
 
 }  // namespace fsgm

@@ -73,18 +73,14 @@ fsgm_status fsgm_sgm_device(int32_t n, const uint8_t* C, int32_t W, int32_t H, i
     SgmCall c;
     fsgm_status st = sgm_args(who, n, C, W, H, D, P1, P2, prm, guide, bestD, minC, S, &c);
     if (st != FSGM_OK) return st;
-    // checks first, also on a shape's first call: nothing is allocated for a captured stream or a pointer that is refused
-    const int dev = c.prm.device;
     const size_t np = (size_t)n * W * H, nv = np * D;
     const hipStream_t cs = (hipStream_t)stream;
-    if ((st = use_device(dev)) != FSGM_OK) return st;
-    if ((st = device_check_stream(cs, who)) != FSGM_OK ||
-        (st = device_check_ptr(C, nv, 1, dev, true, who, "C")) != FSGM_OK ||
-        (st = device_check_ptr(c.guide, np, 1, dev, false, who, "guide")) != FSGM_OK ||
-        (st = device_check_ptr(bestD, np * 4, 4, dev, true, who, "bestD")) != FSGM_OK ||
-        (st = device_check_ptr(minC, np * 4, 4, dev, true, who, "minC")) != FSGM_OK ||
-        (st = device_check_ptr(S, nv * 4, 4, dev, false, who, "S")) != FSGM_OK ||
-        (st = device_check_ptr(status, 4, 4, dev, false, who, "status")) != FSGM_OK)
+    if ((st = device_check_args(who, c.prm.device, cs, {{C, nv, 1, true, "C"},
+                                                        {c.guide, np, 1, false, "guide"},
+                                                        {bestD, np * 4, 4, true, "bestD"},
+                                                        {minC, np * 4, 4, true, "minC"},
+                                                        {S, nv * 4, 4, false, "S"},
+                                                        {status, 4, 4, false, "status"}})) != FSGM_OK)
         return st;
     return sgm_run_device(c, cs, status);
 }

@@ -191,12 +191,6 @@ static fsgm_status stage_host(const char* who, int32_t n, const double* D1, cons
     return FSGM_OK;
 }
 
-// sets the device, refuses a captured stream -- before any plan is looked up: nothing may be allocated under a capture
-static fsgm_status device_enter(const char* who, int device, hipStream_t cs) {
-    const fsgm_status st = use_device(device);
-    return st != FSGM_OK ? st : device_check_stream(cs, who);
-}
-
 static fsgm_status stage_device(const char* who, int32_t n, const double* D1, const double* D2in, int32_t W, int32_t H, int32_t d_min,
                                 int32_t direction, double thr, double* out, double* D2out, int32_t device, void* stream, int32_t* status) {
     fsgm_status st = map_args(who, n, W, H, D1 && (out || D2out) && !(D2in && (D2out || !out)), d_min, direction, device);
@@ -204,24 +198,20 @@ static fsgm_status stage_device(const char* who, int32_t n, const double* D1, co
     FSGM_REQUIRE(thr >= 0.0, "%s: thr must be >= 0 (got %g)", who, thr);
     const size_t bytes = (size_t)n * W * H * 8;
     hipStream_t cs = (hipStream_t)stream;
-    if ((st = device_enter(who, device, cs)) != FSGM_OK) return st;
-    if ((st = device_check_ptr(D1, bytes, 8, device, true, who, "D1")) != FSGM_OK ||
-        (st = device_check_ptr(D2in, bytes, 8, device, false, who, "D2")) != FSGM_OK ||
-        (st = device_check_ptr(out, bytes, 8, device, false, who, "the checked map")) != FSGM_OK ||
-        (st = device_check_ptr(D2out, bytes, 8, device, false, who, "the second-view map")) != FSGM_OK ||
-        (st = device_check_ptr(status, 4, 4, device, false, who, "status")) != FSGM_OK)
+    if ((st = device_check_args(who, device, cs, {{D1, bytes, 8, true, "D1"},
+                                                  {D2in, bytes, 8, false, "D2"},
+                                                  {out, bytes, 8, false, "the checked map"},
+                                                  {D2out, bytes, 8, false, "the second-view map"},
+                                                  {status, 4, 4, false, "status"}})) != FSGM_OK)
         return st;
     std::unique_lock<std::mutex> lk;
     fsgm_stereo_pp_plan* p;
     if ((st = plan_get(lk, &p, W, H, n, device)) != FSGM_OK) return st;
-    if ((st = p->join.ensure()) != FSGM_OK) return st;
-    if ((st = p->join.enter(cs, p->stream)) != FSGM_OK) return st;
-    stage_enqueue(p->stream, n, W, H, D1, D2in, d_min, direction, thr, out, D2out, status && !D2in ? p->dNeg : nullptr);
-    if (status) launch_post_status(p->stream, p->dNeg, status);   // (the check alone reads no flag: 0)
-    const hipError_t le = hipGetLastError();
-    const fsgm_status js = p->join.leave(p->stream, cs);
-    if (le != hipSuccess) return fail(FSGM_ERR_HIP, "%s: launch failed: %s", who, hipGetErrorString(le));
-    return js;
+    return device_call(p->join, cs, p->stream, [&] {
+        stage_enqueue(p->stream, n, W, H, D1, D2in, d_min, direction, thr, out, D2out, status && !D2in ? p->dNeg : nullptr);
+        if (status) launch_device_status(p->stream, nullptr, p->dNeg, status);   // (the check alone raises no flag: 0)
+        return FSGM_OK;
+    });
 }
 
 extern "C" {
@@ -313,35 +303,28 @@ fsgm_status fsgm_stereo_sgm_pp_device(int32_t n, const uint8_t* I1, const uint8_
     if (st != FSGM_OK) return st;
     hipStream_t cs = (hipStream_t)stream;
     const size_t np = (size_t)W * H * n;
-    const int dev = sp.device;
-    if ((st = device_enter(who, dev, cs)) != FSGM_OK) return st;
-    if ((st = device_check_ptr(I1, np, 1, dev, true, who, "I1")) != FSGM_OK ||
-        (st = device_check_ptr(I2, np, 1, dev, true, who, "I2")) != FSGM_OK ||
-        (st = device_check_ptr(disp_pp, np * 8, 8, dev, true, who, "disp_pp")) != FSGM_OK ||
-        (st = device_check_ptr(disp_checked, np * 8, 8, dev, false, who, "disp_checked")) != FSGM_OK ||
-        (st = device_check_ptr(disp, np * 4, 4, dev, false, who, "disp")) != FSGM_OK ||
-        (st = device_check_ptr(minC, np * 4, 4, dev, false, who, "minC")) != FSGM_OK ||
-        (st = device_check_ptr(disp2, np * 8, 8, dev, false, who, "disp2")) != FSGM_OK ||
-        (st = device_check_ptr(status, 4, 4, dev, false, who, "status")) != FSGM_OK)
+    if ((st = device_check_args(who, sp.device, cs, {{I1, np, 1, true, "I1"},
+                                                     {I2, np, 1, true, "I2"},
+                                                     {disp_pp, np * 8, 8, true, "disp_pp"},
+                                                     {disp_checked, np * 8, 8, false, "disp_checked"},
+                                                     {disp, np * 4, 4, false, "disp"},
+                                                     {minC, np * 4, 4, false, "minC"},
+                                                     {disp2, np * 8, 8, false, "disp2"},
+                                                     {status, 4, 4, false, "status"}})) != FSGM_OK)
         return st;
     std::unique_lock<std::mutex> lk;
     fsgm_stereo_pp_plan* p;
-    if ((st = plan_get(lk, &p, W, H, n, dev)) != FSGM_OK) return st;
-    if ((st = p->join.ensure()) != FSGM_OK) return st;
-    if ((st = p->join.enter(cs, p->stream)) != FSGM_OK) return st;
-    auto work = [&]() -> fsgm_status {
-        // the images are read where they lie, the matcher writes the caller's disp / minC (the plan's when it wants none)
+    if ((st = plan_get(lk, &p, W, H, n, sp.device)) != FSGM_OK) return st;
+    return device_call(p->join, cs, p->stream, [&]() -> fsgm_status {
+        // the images are read where they lie, the matcher writes the caller's disp / minC (the plan's when it wants none); it
+        // joins the plan's stream in its turn and queues the status word, which the chain behind it leaves alone
         int32_t* d = disp ? disp : p->dDisp;
         const fsgm_status ms = fsgm_stereo_sgm_device_range(n, I1, I2, W, H, dMax, P1, P2, &sp, opt, d_min, d, minC ? minC : p->dMinC, nullptr,
                                                             nullptr, p->stream, status);
         if (ms != FSGM_OK) return ms;
         chain_enqueue(p->stream, p, q, dMax, d_min, sp.direction, d, disp_pp, disp_checked, disp2);
-        FSGM_HIP(hipGetLastError());
         return FSGM_OK;
-    };
-    st = work();
-    const fsgm_status js = p->join.leave(p->stream, cs);             // on every exit: the caller's stream stays ordered behind what was queued
-    return st != FSGM_OK ? st : js;
+    });
 }
 
 // Average milliseconds, warm, HIP events on the plan's stream, for host images as fsgm_stereo_sgm_pp_host takes them: ms[0]

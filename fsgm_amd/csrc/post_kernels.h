@@ -43,8 +43,6 @@ void launch_vz_from_bestd(hipStream_t st, const uint32_t* bestD, double* D1, siz
 // O [nf][H][W], nd / rflow [nf][2][H][W]
 void launch_epi_pp_flow(hipStream_t st, const double* D1, const double* filterD1, const double* O, const double* nd,
                         const double* rflow, double* flow, double* flow2, int W, int H, int nf, double vMax, double n);
-// one wave: *status = *neg ? FSGM_ERR_INVALID : 0, *neg cleared (status may be null)
-void launch_post_status(hipStream_t st, uint32_t* neg, int32_t* status);
 
 // ---- the same chain on 2-D flows (the scalar vz-index map replaced by a two-channel flow) ----
 // Flows are f64 [nf][2][H][W], plane 0 = u (x), x fastest; a pixel is valid when neither channel is NaN.

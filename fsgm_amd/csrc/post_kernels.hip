@@ -376,13 +376,6 @@ __global__ __launch_bounds__(256) void flow_pack_kernel(const double* __restrict
     flow_pp[o + 2 * NP] = (isnan(checked[q]) || isnan(checked[q + NP])) ? 0.0 : 1.0;
 }
 
-__global__ __launch_bounds__(64) void post_status_kernel(uint32_t* __restrict__ neg, int32_t* __restrict__ status) {
-    if (threadIdx.x != 0) return;
-    const uint32_t v = *neg;
-    *neg = 0;
-    if (status) *status = v ? (int32_t)FSGM_ERR_INVALID : 0;
-}
-
 // =============================================================================================
 // launchers.  Frame-indexed grids put the frame in blockIdx.z, whose range is 65535: more frames (only tiny maps
 // can have that many below 2^31 pixels) take one launch per 65535.
@@ -403,10 +396,6 @@ void launch_epi_pp_flow(hipStream_t st, const double* D1, const double* filterD1
     const size_t NP = (size_t)W * H, n_px = NP * nf;
     hipLaunchKernelGGL(epi_pp_flow_kernel, dim3((unsigned)((n_px + 255) / 256)), dim3(256), 0, st, D1, filterD1, O, nd, rflow,
                        flow, flow2, NP, n_px, vMax, n);
-}
-
-void launch_post_status(hipStream_t st, uint32_t* neg, int32_t* status) {
-    hipLaunchKernelGGL(post_status_kernel, dim3(1), dim3(64), 0, st, neg, status);
 }
 
 template <int CH>

@@ -50,16 +50,22 @@ void pyramid_destroy(P* p) {
     delete p;
 }
 
+// what a plan can be refused for without a GPU: asked by plan creation and, before it touches a device, by pyramid_device
 template <class P>
-fsgm_status pyramid_create(P** out, int W, int H, int channels, int batch, const typename P::Params* prm) {
-    FSGM_REQUIRE(out, "%s_create: null plan pointer", P::plan_name);
-    *out = nullptr;
+fsgm_status pyramid_args(int W, int H, int channels, int batch, const typename P::Params* prm) {
     FSGM_REQUIRE(batch >= 1 && batch <= P::max_batch, "batch must be in 1..%d (got %d)", P::max_batch, batch);
     FSGM_REQUIRE(prm, "%s_create: null parameters", P::plan_name);
     FSGM_REQUIRE(W >= 1 && H >= 1, "width/height must be >= 1 (got %d x %d)", W, H);
     FSGM_REQUIRE(channels == 1 || channels == 3, "channels must be 1 (gray) or 3 (RGB planes), got %d", channels);
     FSGM_REQUIRE(prm->numPyd >= 1 && prm->numPyd <= 16, "numPyd must be in 1..16 (got %d)", prm->numPyd);
-    fsgm_status st = P::check(*prm, W, H);
+    return P::check(*prm, W, H);
+}
+
+template <class P>
+fsgm_status pyramid_create(P** out, int W, int H, int channels, int batch, const typename P::Params* prm) {
+    FSGM_REQUIRE(out, "%s_create: null plan pointer", P::plan_name);
+    *out = nullptr;
+    fsgm_status st = pyramid_args<P>(W, H, channels, batch, prm);
     if (st != FSGM_OK) return st;
     if ((st = use_device(prm->device)) != FSGM_OK) return st;
     P* p = new P;
@@ -273,35 +279,29 @@ fsgm_status pyramid_device(PyramidCache<P>& cache, int32_t n, const uint8_t* I0,
     FSGM_REQUIRE(W >= 1 && H >= 1, "%s: width/height must be >= 1 (got %d x %d)", who, W, H);
     FSGM_REQUIRE(channels == 1 || channels == 3, "%s: channels must be 1 (gray) or 3 (RGB planes), got %d", who, channels);
     FSGM_DEVICE_SLOT(prm->device);
+    fsgm_status st = pyramid_args<P>(W, H, channels, n, prm);
+    if (st != FSGM_OK) return st;
+    const size_t np = (size_t)n * W * H;
+    const hipStream_t cs = (hipStream_t)stream;
+    if ((st = device_check_args(who, prm->device, cs, {{I0, np * channels, 1, true, "I0"},
+                                                       {I1, np * channels, 1, true, "I1"},
+                                                       {flow, np * 16, 8, true, P::flow_name},
+                                                       {minC, np * 4, 4, false, "minC"},
+                                                       {status, 4, 4, false, "status"}})) != FSGM_OK)
+        return st;
     std::lock_guard<std::mutex> lk(cache.mu(prm->device));
     P* p = nullptr;
-    fsgm_status st;
     if ((st = cache.get(&p, W, H, channels, prm, n)) != FSGM_OK) return st;
-    const int dev = prm->device;
-    const size_t np = (size_t)n * W * H;
-    hipStream_t cs = (hipStream_t)stream, ps = p->core.stream;
-    FSGM_HIP(hipSetDevice(dev));
-    if ((st = device_check_stream(cs, who)) != FSGM_OK) return st;
-    if ((st = device_check_ptr(I0, np * channels, 1, dev, true, who, "I0")) != FSGM_OK ||
-        (st = device_check_ptr(I1, np * channels, 1, dev, true, who, "I1")) != FSGM_OK ||
-        (st = device_check_ptr(flow, np * 16, 8, dev, true, who, P::flow_name)) != FSGM_OK ||
-        (st = device_check_ptr(minC, np * 4, 4, dev, false, who, "minC")) != FSGM_OK ||
-        (st = device_check_ptr(status, 4, 4, dev, false, who, "status")) != FSGM_OK)
-        return st;
-    if ((st = p->core.join.ensure()) != FSGM_OK) return st;
-    if ((st = p->core.join.enter(cs, ps)) != FSGM_OK) return st;
-    {
+    const hipStream_t ps = p->core.stream;
+    return device_call(p->core.join, cs, ps, [&]() -> fsgm_status {
         Bind<uint8_t> i0(pyramid_input(p, 0), const_cast<uint8_t*>(I0));
         Bind<uint8_t> i1(pyramid_input(p, 1), const_cast<uint8_t*>(I1));
         Bind<double> fl(p->core.dFlow[0], flow);
         Bind<uint32_t> mc(p->minC(0), minC);
-        st = pyramid_enqueue(p);
-    }
-    if (st == FSGM_OK) launch_device_status(ps, nullptr, status);
-    const fsgm_status js = p->core.join.leave(ps, cs);
-    if (st != FSGM_OK) return st;
-    FSGM_HIP(hipGetLastError());
-    return js;
+        const fsgm_status es = pyramid_enqueue(p);
+        if (es == FSGM_OK) launch_device_status(ps, nullptr, nullptr, status);
+        return es;
+    });
 }
 
 }  // namespace fsgm

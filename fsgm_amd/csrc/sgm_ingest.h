@@ -53,8 +53,5 @@ void launch_sgm_ingest(hipStream_t st, const uint8_t* src, uint8_t* dst, int n, 
                        uint32_t* flag);
 // the LDS the launcher asks for (static, per workgroup)
 size_t sgm_ingest_lds_bytes(int layout);
-// One wave on st: *status = *handoff ? FSGM_ERR_HIP : *bound_flag ? FSGM_ERR_INVALID : 0, both flags cleared (each pointer
-// may be NULL)
-void launch_sgm_status(hipStream_t st, uint32_t* handoff, uint32_t* bound_flag, int32_t* status);
 
 }  // namespace fsgm

@@ -105,15 +105,6 @@ __global__ __launch_bounds__(256) void ingest_dhw_kernel(const uint8_t* __restri
     }
 }
 
-__global__ __launch_bounds__(64) void sgm_status_kernel(uint32_t* __restrict__ handoff, uint32_t* __restrict__ bound_flag,
-                                                        int32_t* __restrict__ status) {
-    if (threadIdx.x != 0) return;
-    uint32_t h = 0, b = 0;
-    if (handoff) { h = *handoff; *handoff = 0; }
-    if (bound_flag) { b = *bound_flag; *bound_flag = 0; }
-    if (status) *status = h != 0 ? (int32_t)FSGM_ERR_HIP : b != 0 ? (int32_t)FSGM_ERR_INVALID : 0;
-}
-
 size_t sgm_ingest_lds_bytes(int layout) {
     return layout == FSGM_COST_LAYOUT_DHW ? (size_t)INGEST_TD * INGEST_PITCH + 4 : 0;
 }
@@ -140,11 +131,6 @@ void launch_sgm_ingest(hipStream_t st, const uint8_t* src, uint8_t* dst, int n, 
         hipLaunchKernelGGL(ingest_dhw_kernel, dim3((unsigned)((size_t)txn * tdn * H), (unsigned)nf), dim3(256), 0, st,
                            src + (size_t)f0 * N, dst + (size_t)f0 * N, W, H, D, txn, tdn, c, sat ? 1 : 0, flag);
     }
-}
-
-void launch_sgm_status(hipStream_t st, uint32_t* handoff, uint32_t* bound_flag, int32_t* status) {
-    if (!handoff && !bound_flag && !status) return;
-    hipLaunchKernelGGL(sgm_status_kernel, dim3(1), dim3(64), 0, st, handoff, bound_flag, status);
 }
 
 }  // namespace fsgm

@@ -134,79 +134,80 @@ def _geometries(geometry, N):
 
 
 # ---------------------------------------------------------------------------------------------
-# custom ops: every tensor argument is batched (leading N) and on one GPU; outputs freshly allocated there
+# custom ops: every tensor argument is batched (leading N) and on one GPU; outputs freshly allocated there.  Each op's
+# outputs are stated once, in an _*_outputs function of the input shapes and flags that its body and its fake both call.
 # ---------------------------------------------------------------------------------------------
+def _frames(t):
+    """(N, H, W, device) of a batch of maps (N, H, W) or images (N, H, W) / (N, 3, H, W)."""
+    return t.shape[0], t.shape[-2], t.shape[-1], t.device
+
+
+def _fb_outputs(N, H, W, fb_check, dev, dtype=torch.uint32):
+    """(conf, the second view's map of `dtype`): empty (0,) placeholders without fb_check."""
+    shape = (N, H, W) if fb_check else (0,)
+    return torch.empty(shape, dtype=torch.uint8, device=dev), torch.empty(shape, dtype=dtype, device=dev)
+
+
+def _matcher_outputs(I1, fb_check, dtype=torch.uint32):
+    """(bestD of `dtype`, minC, conf, bestD2 of `dtype`, status) of the 1-D matchers."""
+    N, H, W, dev = _frames(I1)
+    return (torch.empty((N, H, W), dtype=dtype, device=dev), _u32((N, H, W), dev)) + _fb_outputs(N, H, W, fb_check, dev, dtype) + (_status(dev),)
+
+
+def _epi_structs(I1, I2, pd0, nd, off, W, H, dMax, vMax, P1, P2, bestD, minC, conf=None, bestD2=None):
+    """fsgm_epi_in / fsgm_epi_out over these tensors (off, conf, bestD2 may be None)."""
+    e, o = EpiIn(), EpiOut()
+    e.I1, e.I2, e.width, e.height, e.dMax, e.vMax = _p(I1), _p(I2), W, H, int(dMax), float(vMax)
+    e.pixelPosD0, e.normDir, e.offset, e.P1, e.P2 = _p(pd0), _p(nd), _p(off), int(P1), int(P2)
+    o.bestD, o.minC, o.conf, o.bestD2 = _p(bestD), _p(minC), _p(conf), _p(bestD2)
+    return e, o
+
+
+def _calc_cost_sgm_run(fn, I1, I2, pd0, nd, off, dMax, vMax, P1, P2, paths, subpixel, vz_to_disp, fb_check, adaptive_p2):
+    N, H, W, dev = _frames(I1)
+    I1, I2, pd0, nd = (_ready(t) for t in (I1, I2, pd0, nd))
+    off = None if off is None else _ready(off)
+    bestD, minC, conf, bestD2, status = _matcher_outputs(I1, fb_check)
+    e, o = _epi_structs(I1, I2, pd0, nd, off, W, H, dMax, vMax, P1, P2, bestD, minC, conf if fb_check else None,
+                        bestD2 if fb_check else None)
+    prm = _epi_params(paths, subpixel, vz_to_disp, dev.index, fb_check)
+    opt = _lib.options(adaptive_p2)
+    _call(dev, fn, N, C.byref(e), C.byref(o), C.byref(prm), C.byref(opt), _stream(dev), _p(status))
+    return bestD, minC, conf, bestD2, status
+
+
 @torch.library.custom_op("fsgm::calc_cost_sgm", mutates_args=())
 def _calc_cost_sgm_op(I1: torch.Tensor, I2: torch.Tensor, pd0: torch.Tensor, nd: torch.Tensor, off: torch.Tensor, dMax: int,
                       vMax: float, P1: int, P2: int, paths: int, subpixel: int, vz_to_disp: int,
                       fb_check: int, adaptive_p2: int = 0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
-    N, H, W = I1.shape
-    dev = I1.device
-    I1, I2, pd0, nd, off = (_ready(t) for t in (I1, I2, pd0, nd, off))
-    bestD, minC, status = _u32((N, H, W), dev), _u32((N, H, W), dev), _status(dev)
-    conf = torch.empty((N, H, W) if fb_check else (0,), dtype=torch.uint8, device=dev)
-    bestD2 = _u32((N, H, W) if fb_check else (0,), dev)
-    e, o = EpiIn(), EpiOut()
-    e.I1, e.I2, e.width, e.height, e.dMax, e.vMax = _p(I1), _p(I2), W, H, int(dMax), float(vMax)
-    e.pixelPosD0, e.normDir, e.offset, e.P1, e.P2 = _p(pd0), _p(nd), _p(off), int(P1), int(P2)
-    o.bestD, o.minC = _p(bestD), _p(minC)
-    if fb_check:
-        o.conf, o.bestD2 = _p(conf), _p(bestD2)
-    prm = _epi_params(paths, subpixel, vz_to_disp, dev.index, fb_check)
-    opt = _lib.options(adaptive_p2)
-    _call(dev, _L.fsgm_calc_cost_sgm_device_opts, N, C.byref(e), C.byref(o), C.byref(prm), C.byref(opt), _stream(dev), _p(status))
-    return bestD, minC, conf, bestD2, status
+    return _calc_cost_sgm_run(_L.fsgm_calc_cost_sgm_device_opts, I1, I2, pd0, nd, off, dMax, vMax, P1, P2, paths, subpixel, vz_to_disp,
+                              fb_check, adaptive_p2)
 
 
 @_calc_cost_sgm_op.register_fake
 def _(I1, I2, pd0, nd, off, dMax, vMax, P1, P2, paths, subpixel, vz_to_disp, fb_check, adaptive_p2=0):
-    N, H, W = I1.shape
-    dev = I1.device
-    return (_u32((N, H, W), dev), _u32((N, H, W), dev),
-            torch.empty((N, H, W) if fb_check else (0,), dtype=torch.uint8, device=dev),
-            _u32((N, H, W) if fb_check else (0,), dev), _status(dev))
-
-
-def _fb_outputs(N, H, W, fb_check, dev):
-    return (torch.empty((N, H, W) if fb_check else (0,), dtype=torch.uint8, device=dev), _u32((N, H, W) if fb_check else (0,), dev))
+    return _matcher_outputs(I1, fb_check)
 
 
 @torch.library.custom_op("fsgm::calc_cost_sgm_linear", mutates_args=())
 def _calc_cost_sgm_linear_op(I1: torch.Tensor, I2: torch.Tensor, pd0: torch.Tensor, nd: torch.Tensor, dMax: int, P1: int, P2: int,
                              paths: int, subpixel: int,
                              fb_check: int, adaptive_p2: int = 0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
-    N, H, W = I1.shape
-    dev = I1.device
-    I1, I2, pd0, nd = (_ready(t) for t in (I1, I2, pd0, nd))
-    bestD, minC, status = _u32((N, H, W), dev), _u32((N, H, W), dev), _status(dev)
-    conf, bestD2 = _fb_outputs(N, H, W, fb_check, dev)
-    e, o = EpiIn(), EpiOut()
-    e.I1, e.I2, e.width, e.height, e.dMax, e.vMax = _p(I1), _p(I2), W, H, int(dMax), 0.0
-    e.pixelPosD0, e.normDir, e.offset, e.P1, e.P2 = _p(pd0), _p(nd), None, int(P1), int(P2)
-    o.bestD, o.minC = _p(bestD), _p(minC)
-    if fb_check:
-        o.conf, o.bestD2 = _p(conf), _p(bestD2)
-    prm = _epi_params(paths, subpixel, 0, dev.index, fb_check)
-    opt = _lib.options(adaptive_p2)
-    _call(dev, _L.fsgm_calc_cost_sgm_linear_device_opts, N, C.byref(e), C.byref(o), C.byref(prm), C.byref(opt), _stream(dev), _p(status))
-    return bestD, minC, conf, bestD2, status
+    return _calc_cost_sgm_run(_L.fsgm_calc_cost_sgm_linear_device_opts, I1, I2, pd0, nd, None, dMax, 0.0, P1, P2, paths, subpixel, 0,
+                              fb_check, adaptive_p2)
 
 
 @_calc_cost_sgm_linear_op.register_fake
 def _(I1, I2, pd0, nd, dMax, P1, P2, paths, subpixel, fb_check, adaptive_p2=0):
-    N, H, W = I1.shape
-    dev = I1.device
-    return (_u32((N, H, W), dev), _u32((N, H, W), dev)) + _fb_outputs(N, H, W, fb_check, dev) + (_status(dev),)
+    return _matcher_outputs(I1, fb_check)
 
 
 @torch.library.custom_op("fsgm::stereo_sgm", mutates_args=())
 def _stereo_sgm_op(left: torch.Tensor, right: torch.Tensor, dMax: int, P1: int, P2: int, paths: int, subpixel: int, direction: int,
                    fb_check: int, adaptive_p2: int = 0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
-    N, H, W = left.shape
-    dev = left.device
+    N, H, W, dev = _frames(left)
     left, right = _ready(left), _ready(right)
-    disp, minC, status = _u32((N, H, W), dev), _u32((N, H, W), dev), _status(dev)
-    conf, disp2 = _fb_outputs(N, H, W, fb_check, dev)
+    disp, minC, conf, disp2, status = _matcher_outputs(left, fb_check)
     prm = _stereo_params(paths, subpixel, direction, fb_check, dev.index)
     opt = _lib.options(adaptive_p2)
     _call(dev, _L.fsgm_stereo_sgm_device_opts, N, _p(left), _p(right), W, H, int(dMax), int(P1), int(P2), C.byref(prm), C.byref(opt),
@@ -216,25 +217,16 @@ def _stereo_sgm_op(left: torch.Tensor, right: torch.Tensor, dMax: int, P1: int, 
 
 @_stereo_sgm_op.register_fake
 def _(left, right, dMax, P1, P2, paths, subpixel, direction, fb_check, adaptive_p2=0):
-    N, H, W = left.shape
-    dev = left.device
-    return (_u32((N, H, W), dev), _u32((N, H, W), dev)) + _fb_outputs(N, H, W, fb_check, dev) + (_status(dev),)
-
-
-def _fb_outputs_i32(N, H, W, fb_check, dev):
-    return (torch.empty((N, H, W) if fb_check else (0,), dtype=torch.uint8, device=dev),
-            torch.empty((N, H, W) if fb_check else (0,), dtype=torch.int32, device=dev))
+    return _matcher_outputs(left, fb_check)
 
 
 @torch.library.custom_op("fsgm::stereo_sgm_range", mutates_args=())
 def _stereo_sgm_range_op(left: torch.Tensor, right: torch.Tensor, dMax: int, d_min: int, P1: int, P2: int, paths: int, subpixel: int,
                          direction: int, fb_check: int,
                          adaptive_p2: int = 0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
-    N, H, W = left.shape
-    dev = left.device
+    N, H, W, dev = _frames(left)
     left, right = _ready(left), _ready(right)
-    disp, minC, status = torch.empty((N, H, W), dtype=torch.int32, device=dev), _u32((N, H, W), dev), _status(dev)
-    conf, disp2 = _fb_outputs_i32(N, H, W, fb_check, dev)
+    disp, minC, conf, disp2, status = _matcher_outputs(left, fb_check, torch.int32)
     prm = _stereo_params(paths, subpixel, direction, fb_check, dev.index)
     opt = _lib.options(adaptive_p2)
     _call(dev, _L.fsgm_stereo_sgm_device_range, N, _p(left), _p(right), W, H, int(dMax), int(P1), int(P2), C.byref(prm), C.byref(opt),
@@ -244,10 +236,20 @@ def _stereo_sgm_range_op(left: torch.Tensor, right: torch.Tensor, dMax: int, d_m
 
 @_stereo_sgm_range_op.register_fake
 def _(left, right, dMax, d_min, P1, P2, paths, subpixel, direction, fb_check, adaptive_p2=0):
-    N, H, W = left.shape
-    dev = left.device
-    return ((torch.empty((N, H, W), dtype=torch.int32, device=dev), _u32((N, H, W), dev)) + _fb_outputs_i32(N, H, W, fb_check, dev)
-            + (_status(dev),))
+    return _matcher_outputs(left, fb_check, torch.int32)
+
+
+def _sgm_out_shape(C_, layout):
+    if layout not in (0, 1):
+        raise ValueError(f"layout must be 0 (hwd) or 1 (dhw), got {layout}")
+    N, a, b, c = C_.shape
+    return (N, a, b, c) if layout == 0 else (N, b, c, a)
+
+
+def _sgm_outputs(C_, layout, return_sum):
+    N, H, W, D = _sgm_out_shape(C_, layout)
+    dev = C_.device
+    return _u32((N, H, W), dev), _u32((N, H, W), dev), _u32((N, H, W, D) if return_sum else (0,), dev), _status(dev)
 
 
 @torch.library.custom_op("fsgm::sgm", mutates_args=())
@@ -258,8 +260,7 @@ def _sgm_op(C_: torch.Tensor, guide: torch.Tensor, P1: int, P2: int, paths: int,
     dev = C_.device
     C_ = C_.contiguous()                                  # (any byte offset will do: the ingest kernel assumes no alignment)
     guide = guide.contiguous() if adaptive_p2 else None
-    bestD, minC, status = _u32((N, H, W), dev), _u32((N, H, W), dev), _status(dev)
-    S = _u32((N, H, W, D) if return_sum else (0,), dev)
+    bestD, minC, S, status = _sgm_outputs(C_, layout, return_sum)
     prm = _sgm_params(_L, paths=paths, subpixel=subpixel, device=dev.index, agg_mode=agg_mode, layout="dhw" if layout else "hwd",
                       cost_bound=cost_bound, adaptive_p2=adaptive_p2)
     _call(dev, _L.fsgm_sgm_device, N, _p(C_), W, H, D, int(P1), int(P2), C.byref(prm), _p(guide), _p(bestD), _p(minC),
@@ -267,29 +268,24 @@ def _sgm_op(C_: torch.Tensor, guide: torch.Tensor, P1: int, P2: int, paths: int,
     return bestD, minC, S, status
 
 
-def _sgm_out_shape(C_, layout):
-    if layout not in (0, 1):
-        raise ValueError(f"layout must be 0 (hwd) or 1 (dhw), got {layout}")
-    N, a, b, c = C_.shape
-    return (N, a, b, c) if layout == 0 else (N, b, c, a)
-
-
 @_sgm_op.register_fake
 def _(C_, guide, P1, P2, paths, layout, cost_bound, agg_mode, adaptive_p2, subpixel, return_sum):
-    N, H, W, D = _sgm_out_shape(C_, layout)
-    dev = C_.device
-    return _u32((N, H, W), dev), _u32((N, H, W), dev), _u32((N, H, W, D) if return_sum else (0,), dev), _status(dev)
+    return _sgm_outputs(C_, layout, return_sum)
+
+
+def _epipolar_sgm_of_outputs(I0):
+    N, H, W, dev = _frames(I0)
+    return _f64((N, 3, H, W), dev), _u32((N, H, W), dev), _status(dev)
 
 
 @torch.library.custom_op("fsgm::epipolar_sgm_of", mutates_args=())
 def _epipolar_sgm_of_op(I0: torch.Tensor, I1: torch.Tensor, geometry: List[float], dMax: int, vMax: float,
                         paths: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-    N, H, W = I0.shape[0], I0.shape[-2], I0.shape[-1]
+    N, H, W, dev = _frames(I0)
     ch = 1 if I0.dim() == 3 else 3
-    dev = I0.device
     g = _geometries(geometry, N)
     I0, I1 = _ready(I0), _ready(I1)
-    flow, minC, status = torch.empty((N, 3, H, W), dtype=torch.float64, device=dev), _u32((N, H, W), dev), _status(dev)
+    flow, minC, status = _epipolar_sgm_of_outputs(I0)
     prm = _epi_params(paths, 1, 1, dev.index, 0)
     _call(dev, _L.fsgm_epipolar_sgm_of_device, N, _p(I0), _p(I1), W, H, ch, g, int(dMax), float(vMax), C.byref(prm),
           _p(flow), _p(minC), _stream(dev), _p(status))
@@ -298,21 +294,22 @@ def _epipolar_sgm_of_op(I0: torch.Tensor, I1: torch.Tensor, geometry: List[float
 
 @_epipolar_sgm_of_op.register_fake
 def _(I0, I1, geometry, dMax, vMax, paths):
-    N, H, W = I0.shape[0], I0.shape[-2], I0.shape[-1]
-    dev = I0.device
-    return torch.empty((N, 3, H, W), dtype=torch.float64, device=dev), _u32((N, H, W), dev), _status(dev)
+    return _epipolar_sgm_of_outputs(I0)
+
+
+def _epipolar_flow_pp_outputs(I0):
+    N, H, W, dev = _frames(I0)
+    return _f64((N, 3, H, W), dev), _f64((N, 3, H, W), dev), _f64((N, H, W), dev), _u32((N, H, W), dev), _status(dev)
 
 
 @torch.library.custom_op("fsgm::epipolar_flow_pp", mutates_args=())
 def _epipolar_flow_pp_op(I0: torch.Tensor, I1: torch.Tensor, geometry: List[float], dMax: int, vMax: float,
                          paths: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
-    N, H, W = I0.shape[0], I0.shape[-2], I0.shape[-1]
+    N, H, W, dev = _frames(I0)
     ch = 1 if I0.dim() == 3 else 3
-    dev = I0.device
     g = _geometries(geometry, N)
     I0, I1 = _ready(I0), _ready(I1)
-    flow, flow2, D1 = _f64((N, 3, H, W), dev), _f64((N, 3, H, W), dev), _f64((N, H, W), dev)
-    minC, status = _u32((N, H, W), dev), _status(dev)
+    flow, flow2, D1, minC, status = _epipolar_flow_pp_outputs(I0)
     prm = _epi_params(paths, 1, 0, dev.index, 0)
     _call(dev, _L.fsgm_epipolar_flow_pp_device, N, _p(I0), _p(I1), W, H, ch, g, int(dMax), float(vMax), C.byref(prm),
           _p(flow), _p(flow2), _p(D1), _p(minC), _stream(dev), _p(status))
@@ -321,18 +318,20 @@ def _epipolar_flow_pp_op(I0: torch.Tensor, I1: torch.Tensor, geometry: List[floa
 
 @_epipolar_flow_pp_op.register_fake
 def _(I0, I1, geometry, dMax, vMax, paths):
-    N, H, W = I0.shape[0], I0.shape[-2], I0.shape[-1]
-    dev = I0.device
-    return _f64((N, 3, H, W), dev), _f64((N, 3, H, W), dev), _f64((N, H, W), dev), _u32((N, H, W), dev), _status(dev)
+    return _epipolar_flow_pp_outputs(I0)
+
+
+def _epi_postprocess_outputs(D1):
+    N, H, W, dev = _frames(D1)
+    return _f64((N, H, W), dev), _f64((N, H, W), dev), _f64((N, H, W), dev), _status(dev)
 
 
 @torch.library.custom_op("fsgm::epi_postprocess", mutates_args=())
 def _epi_postprocess_op(D1: torch.Tensor, Pd0: torch.Tensor, nd: torch.Tensor, O: torch.Tensor, vMax: float, n: float,
                         dMax: float) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
-    N, H, W = D1.shape
-    dev = D1.device
+    N, H, W, dev = _frames(D1)
     D1, Pd0, nd, O = (_ready(t) for t in (D1, Pd0, nd, O))
-    f1, f2, disp, status = _f64((N, H, W), dev), _f64((N, H, W), dev), _f64((N, H, W), dev), _status(dev)
+    f1, f2, disp, status = _epi_postprocess_outputs(D1)
     _call(dev, _L.fsgm_epi_postprocess_device, N, _p(D1), W, H, _p(Pd0), _p(nd), _p(O), float(vMax), float(n), float(dMax),
           _p(f1), _p(f2), _p(disp), dev.index, _stream(dev), _p(status))
     return f1, f2, disp, status
@@ -340,9 +339,12 @@ def _epi_postprocess_op(D1: torch.Tensor, Pd0: torch.Tensor, nd: torch.Tensor, O
 
 @_epi_postprocess_op.register_fake
 def _(D1, Pd0, nd, O, vMax, n, dMax):
-    N, H, W = D1.shape
-    dev = D1.device
-    return _f64((N, H, W), dev), _f64((N, H, W), dev), _f64((N, H, W), dev), _status(dev)
+    return _epi_postprocess_outputs(D1)
+
+
+def _like(t):
+    """the one output of the ops that map a flow to a flow of its shape"""
+    return torch.empty_like(t, memory_format=torch.contiguous_format)
 
 
 @torch.library.custom_op("fsgm::vmf", mutates_args=())
@@ -350,31 +352,29 @@ def _vmf_op(flow: torch.Tensor) -> torch.Tensor:
     N, ch, H, W = flow.shape
     dev = flow.device
     flow = _ready(flow)
-    out = _f64((N, ch, H, W), dev)
+    out = _like(flow)
     _call(dev, _L.fsgm_vmf_device, N, _p(flow), W, H, ch, _p(out), dev.index, _stream(dev))
     return out
 
 
 @_vmf_op.register_fake
 def _(flow):
-    return torch.empty_like(flow, memory_format=torch.contiguous_format)
+    return _like(flow)
+
+
+def _pyramid_outputs(I0):
+    N, H, W, dev = _frames(I0)
+    return _f64((N, 2, H, W), dev), _u32((N, H, W), dev), _status(dev)
 
 
 def _pyramid_run(fn, prm, I0, I1):
-    N, H, W = I0.shape[0], I0.shape[-2], I0.shape[-1]
+    N, H, W, dev = _frames(I0)
     ch = 1 if I0.dim() == 3 else 3
-    dev = I0.device
     prm.device = dev.index
     I0, I1 = _ready(I0), _ready(I1)
-    mv, minC, status = torch.empty((N, 2, H, W), dtype=torch.float64, device=dev), _u32((N, H, W), dev), _status(dev)
+    mv, minC, status = _pyramid_outputs(I0)
     _call(dev, fn, N, _p(I0), _p(I1), W, H, ch, C.byref(prm), _p(mv), _p(minC), _stream(dev), _p(status))
     return mv, minC, status
-
-
-def _pyramid_fake(I0):
-    N, H, W = I0.shape[0], I0.shape[-2], I0.shape[-1]
-    dev = I0.device
-    return torch.empty((N, 2, H, W), dtype=torch.float64, device=dev), _u32((N, H, W), dev), _status(dev)
 
 
 @torch.library.custom_op("fsgm::pyramidal_sgm", mutates_args=())
@@ -389,7 +389,7 @@ def _pyramidal_sgm_op(I0: torch.Tensor, I1: torch.Tensor, numPyd: int,
 
 @_pyramidal_sgm_op.register_fake
 def _(I0, I1, numPyd, params):
-    return _pyramid_fake(I0)
+    return _pyramid_outputs(I0)
 
 
 @torch.library.custom_op("fsgm::pyramidal_sgm_ng", mutates_args=())
@@ -404,15 +404,20 @@ def _pyramidal_sgm_ng_op(I0: torch.Tensor, I1: torch.Tensor, numPyd: int,
 
 @_pyramidal_sgm_ng_op.register_fake
 def _(I0, I1, numPyd, params):
-    return _pyramid_fake(I0)
+    return _pyramid_outputs(I0)
+
+
+def _pyramidal_flow_pp_outputs(I0):
+    N, H, W, dev = _frames(I0)
+    return (_f64((N, 3, H, W), dev), _f64((N, 2, H, W), dev), _f64((N, 2, H, W), dev), _f64((N, 2, H, W), dev),
+            _u32((N, H, W), dev), _status(dev))
 
 
 @torch.library.custom_op("fsgm::pyramidal_flow_pp", mutates_args=())
 def _pyramidal_flow_pp_op(I0: torch.Tensor, I1: torch.Tensor, matcher: int, numPyd: int, params: List[int], chain: List[float],
                           median: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
-    N, H, W = I0.shape[0], I0.shape[-2], I0.shape[-1]
+    N, H, W, dev = _frames(I0)
     ch = 1 if I0.dim() == 3 else 3
-    dev = I0.device
     prm = _L.fsgm_flow_pp_params_default(int(matcher))
     sub, fields = (prm.ng, NG_PYRAMID_FIELDS) if matcher == MATCHERS["ng"] else (prm.pyd, PYRAMID_FIELDS)
     sub.numPyd = int(numPyd)
@@ -422,8 +427,7 @@ def _pyramidal_flow_pp_op(I0: torch.Tensor, I1: torch.Tensor, matcher: int, numP
         setattr(prm, k, float(v))
     prm.median, prm.device = int(median), dev.index
     I0, I1 = _ready(I0), _ready(I1)
-    pp, checked, fwd, bwd = _f64((N, 3, H, W), dev), _f64((N, 2, H, W), dev), _f64((N, 2, H, W), dev), _f64((N, 2, H, W), dev)
-    minC, status = _u32((N, H, W), dev), _status(dev)
+    pp, checked, fwd, bwd, minC, status = _pyramidal_flow_pp_outputs(I0)
     _call(dev, _L.fsgm_pyramidal_flow_pp_device, N, _p(I0), _p(I1), W, H, ch, C.byref(prm), _p(pp), _p(checked), _p(fwd), _p(bwd),
           _p(minC), _stream(dev), _p(status))
     return pp, checked, fwd, bwd, minC, status
@@ -431,10 +435,7 @@ def _pyramidal_flow_pp_op(I0: torch.Tensor, I1: torch.Tensor, matcher: int, numP
 
 @_pyramidal_flow_pp_op.register_fake
 def _(I0, I1, matcher, numPyd, params, chain, median):
-    N, H, W = I0.shape[0], I0.shape[-2], I0.shape[-1]
-    dev = I0.device
-    return (_f64((N, 3, H, W), dev), _f64((N, 2, H, W), dev), _f64((N, 2, H, W), dev), _f64((N, 2, H, W), dev),
-            _u32((N, H, W), dev), _status(dev))
+    return _pyramidal_flow_pp_outputs(I0)
 
 
 @torch.library.custom_op("fsgm::flow_fb_check", mutates_args=())
@@ -442,25 +443,29 @@ def _flow_fb_check_op(f: torch.Tensor, b: torch.Tensor, thr: float) -> torch.Ten
     N, _, H, W = f.shape
     dev = f.device
     f, b = _ready(f), _ready(b)
-    out = _f64((N, 2, H, W), dev)
+    out = _like(f)
     _call(dev, _L.fsgm_flow_fb_check_device, N, _p(f), _p(b), W, H, float(thr), _p(out), dev.index, _stream(dev))
     return out
 
 
 @_flow_fb_check_op.register_fake
 def _(f, b, thr):
-    return torch.empty_like(f, memory_format=torch.contiguous_format)
+    return _like(f)
+
+
+def _stereo_sgm_pp_outputs(left):
+    N, H, W, dev = _frames(left)
+    return (_f64((N, H, W), dev), _f64((N, H, W), dev), torch.empty((N, H, W), dtype=torch.int32, device=dev), _u32((N, H, W), dev),
+            _f64((N, H, W), dev), _status(dev))
 
 
 @torch.library.custom_op("fsgm::stereo_sgm_pp", mutates_args=())
 def _stereo_sgm_pp_op(left: torch.Tensor, right: torch.Tensor, dMax: int, d_min: int, P1: int, P2: int, paths: int, subpixel: int,
                       direction: int, adaptive_p2: int, chain: List[float],
                       in_fill: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
-    N, H, W = left.shape
-    dev = left.device
+    N, H, W, dev = _frames(left)
     left, right = _ready(left), _ready(right)
-    disp_pp, checked, disp2 = _f64((N, H, W), dev), _f64((N, H, W), dev), _f64((N, H, W), dev)
-    disp, minC, status = torch.empty((N, H, W), dtype=torch.int32, device=dev), _u32((N, H, W), dev), _status(dev)
+    disp_pp, checked, disp, minC, disp2, status = _stereo_sgm_pp_outputs(left)
     prm = _stereo_params(paths, subpixel, direction, 0, dev.index)
     opt = _lib.options(adaptive_p2)
     pp = _stereo_pp_params(_L, in_fill, dict(zip(STEREO_PP_FIELDS, chain, strict=True)))
@@ -471,36 +476,30 @@ def _stereo_sgm_pp_op(left: torch.Tensor, right: torch.Tensor, dMax: int, d_min:
 
 @_stereo_sgm_pp_op.register_fake
 def _(left, right, dMax, d_min, P1, P2, paths, subpixel, direction, adaptive_p2, chain, in_fill):
-    N, H, W = left.shape
-    dev = left.device
-    return (_f64((N, H, W), dev), _f64((N, H, W), dev), torch.empty((N, H, W), dtype=torch.int32, device=dev), _u32((N, H, W), dev),
-            _f64((N, H, W), dev), _status(dev))
+    return _stereo_sgm_pp_outputs(left)
+
+
+def _stereo_fb_check_outputs(D1, fused):
+    N, H, W, dev = _frames(D1)
+    return _f64((N, H, W), dev), _f64((N, H, W) if fused else (0,), dev), _status(dev)
 
 
 @torch.library.custom_op("fsgm::stereo_fb_check", mutates_args=())
 def _stereo_fb_check_op(D1: torch.Tensor, D2: torch.Tensor, fused: int, d_min: int, direction: int,
                         thr: float) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-    N, H, W = D1.shape
-    dev = D1.device
+    """fused: D2 is not read, the second-view map is made from D1 and returned; else the check alone against D2."""
+    N, H, W, dev = _frames(D1)
     D1 = _ready(D1)
-    out, status = _f64((N, H, W), dev), _status(dev)
-    if fused:                                        # D2 is not read: the second-view map is made from D1 and returned
-        second = _f64((N, H, W), dev)
-        _call(dev, _L.fsgm_stereo_fb_check_device, N, _p(D1), None, W, H, int(d_min), int(direction), float(thr), _p(out), _p(second),
-              dev.index, _stream(dev), _p(status))
-    else:
-        D2 = _ready(D2)
-        second = _f64((0,), dev)
-        _call(dev, _L.fsgm_stereo_fb_check_device, N, _p(D1), _p(D2), W, H, int(d_min), int(direction), float(thr), _p(out), None,
-              dev.index, _stream(dev), _p(status))
+    D2 = None if fused else _ready(D2)                   # (a local: a contiguous copy must outlive the call)
+    out, second, status = _stereo_fb_check_outputs(D1, fused)
+    _call(dev, _L.fsgm_stereo_fb_check_device, N, _p(D1), _p(D2), W, H, int(d_min), int(direction), float(thr),
+          _p(out), _p(second) if fused else None, dev.index, _stream(dev), _p(status))
     return out, second, status
 
 
 @_stereo_fb_check_op.register_fake
 def _(D1, D2, fused, d_min, direction, thr):
-    N, H, W = D1.shape
-    dev = D1.device
-    return _f64((N, H, W), dev), _f64((N, H, W) if fused else (0,), dev), _status(dev)
+    return _stereo_fb_check_outputs(D1, fused)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -852,6 +851,7 @@ def flow_fb_check(f, b, thr=2.0):
         return torch.ops.fsgm.flow_fb_check(f.unsqueeze(0), b.unsqueeze(0), float(thr))[0]
     return torch.ops.fsgm.flow_fb_check(f, b, float(thr))
 
+
 def run_tensors(plan, I1, I2, pd0, nd, off, *, check=False, return_status=False):
     """All `plan.batch` frames of an EpiPlan (fsgm_epi_plan_run_device) in the plan's aggregation mode and penalties
     (set_agg_mode / set_penalties): I1, I2 (N, H, W) uint8, pd0 / nd (N, 2, H, W), off (N, H, W) float64 on the plan's GPU,
@@ -865,14 +865,10 @@ def run_tensors(plan, I1, I2, pd0, nd, off, *, check=False, return_status=False)
                            ("off", off, (N, H, W))):
         _shape(name, t, shape)
     I1, I2, pd0, nd, off = (_ready(t) for t in (I1, I2, pd0, nd, off))
-    bestD, minC, status = _u32((N, H, W), dev), _u32((N, H, W), dev), _status(dev)
-    conf = torch.empty((N, H, W), dtype=torch.uint8, device=dev) if plan.fb_check else None
-    bestD2 = _u32((N, H, W), dev) if plan.fb_check else None
+    bestD, minC, conf, bestD2, status = _matcher_outputs(I1, plan.fb_check)
     P1, P2, vMax = plan.penalties
-    e, o = EpiIn(), EpiOut()
-    e.I1, e.I2, e.width, e.height, e.dMax, e.vMax = _p(I1), _p(I2), W, H, plan.D, float(vMax)
-    e.pixelPosD0, e.normDir, e.offset, e.P1, e.P2 = _p(pd0), _p(nd), _p(off), int(P1), int(P2)
-    o.bestD, o.minC, o.conf, o.bestD2 = _p(bestD), _p(minC), _p(conf), _p(bestD2)
+    e, o = _epi_structs(I1, I2, pd0, nd, off, W, H, plan.D, vMax, P1, P2, bestD, minC, conf if plan.fb_check else None,
+                        bestD2 if plan.fb_check else None)
     _call(dev, _L.fsgm_epi_plan_run_device, plan._h, N, C.byref(e), C.byref(o), _stream(dev), _p(status))
     outs = (bestD, minC, conf, bestD2) if plan.fb_check else (bestD, minC)
     return _finish(outs, status, True, check, return_status)

@@ -206,6 +206,17 @@ def test_negative_map_sets_the_status(gpu_lib):
         fsgm_amd.epi_postprocess_batch(D1, pd0, nd, off, VMAX, D + 1, D)
 
 
+def test_the_negative_flag_is_cleared_by_the_call_that_reports_it(gpu_lib):
+    """one negative D1 value: FSGM_ERR_INVALID, and 0 from the very next call at the same shape on the same stream"""
+    D1, pd0, nd, off = _batch(9, 6, 2, seed=13)
+    bad = D1.copy()
+    bad[1, 2, 5] = -1.0
+    rest = [_t(a) for a in (pd0, nd, off)]
+    status = [torch_ops.epi_postprocess(_t(m), *rest, VMAX, D + 1, D, return_status=True)[-1] for m in (bad, D1)]
+    torch.cuda.synchronize()
+    assert [int(s.item()) for s in status] == [FSGM_ERR_INVALID, 0]
+
+
 # ---------------------------------------------------------------------------------------------- vmf
 @pytest.mark.parametrize("ch", [1, 2, 3])
 def test_vmf_batch(gpu_lib, oracle, ch):

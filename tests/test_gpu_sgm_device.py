@@ -223,6 +223,17 @@ def test_the_bound(gpu_lib, oracle):
         _same(got, _want(clean, 6, 32, 8), f"clean {layout}")
 
 
+def test_the_bound_flag_is_cleared_by_the_call_that_reports_it(gpu_lib):
+    """one cost above the bound: FSGM_ERR_INVALID, and 0 from the very next call at the same shape on the same stream"""
+    N, D, H, W = 2, 16, 5, 7
+    clean = _as("dhw", _volumes(W, H, D, N, seed=12, cmax=32))
+    over = clean.copy()
+    over[1, 9, 3, 4] = 200
+    status = [torch_ops.sgm(_t(v), 6, 32, layout="dhw", cost_bound=32, return_status=True)[-1] for v in (over, clean)]
+    torch.cuda.synchronize()
+    assert [int(s.item()) for s in status] == [FSGM_ERR_INVALID, 0]
+
+
 # ---------------------------------------------------------------------------------------------- 5. adaptive P2
 @pytest.mark.parametrize("paths", [4, 8])
 def test_adaptive_p2(gpu_lib, paths):

@@ -23,6 +23,7 @@ HEIGHTS = [1, 2, 3, 5]
 GEOMETRIES = list(itertools.product((0, -7, 40), (-1, +1)))
 THRESHOLDS = (2.0, 0.0)
 KINDS = ["random", "half", "constant", "two_plane", "nan_row", "all_nan"]
+NAMES = ("disp_pp", "disp_checked", "disp", "minC", "disp2")
 
 
 def _same(got, want, what):
@@ -105,6 +106,36 @@ def test_stages_report_a_negative_value(gpu_lib):
         torch_ops.stereo_fb_check(_t(w), check=True)
 
 
+def test_the_negative_flag_is_cleared_by_the_call_that_reports_it(gpu_lib):
+    """D2=None (the row kernel raises the flag): FSGM_ERR_INVALID for one negative D1 value, and 0 from the very next call at the
+    same shape on the same stream.  With D2 given no flag is read: 0 also for the negative value."""
+    w = np.stack([P.stage_maps(9, 6, seed=31 + f)["constant"] for f in range(2)])
+    bad = w.copy()
+    bad[1, 2, 5] = -0.25
+    status = [torch_ops.stereo_fb_check(_t(m), return_status=True)[-1] for m in (bad, w)]
+    status.append(torch_ops.stereo_fb_check(_t(bad), _t(w), return_status=True)[-1])
+    torch.cuda.synchronize()
+    assert [int(s.item()) for s in status] == [FSGM_ERR_INVALID, 0, 0]
+
+
+def test_stream_order_on_a_side_stream(gpu_lib):
+    """inputs made by torch kernels on a side stream, the op, and torch ops on its outputs, with no synchronisation in between"""
+    from fsgm_amd import synth
+    W, H, D, n = 24, 16, 8, 2
+    L, Rt = (np.stack(x) for x in zip(*[synth.image_pair(W, H, D, seed=51 + f) for f in range(n)]))
+    want = fsgm_amd.stereo_sgm_pp(L, Rt, D)
+    host = [torch.from_numpy(a).pin_memory() for a in (L, Rt)]
+    s = torch.cuda.Stream(device="cuda:0")
+    with torch.cuda.stream(s):
+        tL, tR = ((h.to("cuda:0", non_blocking=True).to(torch.int16) + 0).to(torch.uint8) for h in host)   # produced by kernels on s
+        outs = torch_ops.stereo_sgm_pp(tL, tR, D)
+        copies = [o.clone() for o in outs]
+        tL.zero_()                                               # queued after the call: must not reach it
+    s.synchronize()
+    for g, w, name in zip(copies, want, NAMES):
+        _same(g.cpu().numpy(), w, f"side stream {name}")
+
+
 def test_torch_stage_equals_the_numpy_path(gpu_lib):
     w = np.stack([P.stage_maps(130, 5, seed=21 + f)["random"] for f in range(3)])
     tw = _t(w)
@@ -120,9 +151,9 @@ def test_torch_stage_equals_the_numpy_path(gpu_lib):
     _same(D2.cpu().numpy(), D2want, "torch second-view map")
     _same(again.cpu().numpy(), want, "torch check against a given map")
     _same(torch_ops.stereo_fb_check(tw[1], None, -7, +1, 1.0).cpu().numpy(), want[1], "one frame")
-
-
-NAMES = ("disp_pp", "disp_checked", "disp", "minC", "disp2")
+    strided = torch.stack([D2, D2], dim=-1)[..., 0]               # D2 as a non-contiguous view: the op checks against a copy
+    assert not strided.is_contiguous()
+    _same(torch_ops.stereo_fb_check(tw, strided, -7, +1, 1.0).cpu().numpy(), want, "torch check against a non-contiguous map")
 
 
 @pytest.mark.parametrize("call", P.CALLS, ids=P.call_id)

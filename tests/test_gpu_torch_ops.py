@@ -309,6 +309,76 @@ def test_pinned_host_memory_is_refused(gpu_lib):
     assert b"not device memory" in lib.fsgm_last_error()
 
 
+def _nan_equal(a, b):
+    return np.array_equal(np.isnan(a), np.isnan(b)) and np.array_equal(np.nan_to_num(a, nan=-7.0), np.nan_to_num(b, nan=-7.0))
+
+
+def _refusal_case(family):
+    """(refused(lib) -> status with the first input in pinned host memory, got() -> torch_ops outputs, want() -> host outputs)
+    of one family of device entry points, at a shape no other test runs that family at: its plan does not exist yet."""
+    W, H, D = 33, 17, 16
+    if family == "fsgm_calc_cost_sgm_device":
+        D = 24                                       # (the epipolar driver's plan at D = 16 has this family's cache key)
+    p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+    pin = lambda a: torch.from_numpy(np.ascontiguousarray(a)).pin_memory()  # noqa: E731
+    if family == "fsgm_epi_postprocess_device":
+        maps = (synth.vz_index_map(W, H, D, seed=41)[None],) + tuple(m[None] for m in synth.epi_maps(W, H, "general", seed=42))
+        maps = maps[:3] + (maps[3] / 8,)
+        dev = [_t(a) for a in maps]
+        out = torch.empty((1, H, W), dtype=torch.float64, device=DEV)
+        pinned = pin(maps[0])
+        return (lambda lib: lib.fsgm_epi_postprocess_device(1, p(pinned), W, H, p(dev[1]), p(dev[2]), p(dev[3]), 0.3, D + 1.0, float(D),
+                                                            p(out), None, None, 0, None, None),
+                lambda: torch_ops.epi_postprocess(*dev, 0.3, D + 1, D, check=True),
+                lambda: fsgm_amd.epi_postprocess_batch(*maps, 0.3, D + 1, D))
+    if family == "fsgm_calc_cost_sgm_device":
+        (fr,) = _frames(W, H, D, 1, seed=43)
+        dev = [_t(a) for a in fr]
+        bd, mc = (torch.empty((H, W), dtype=torch.uint32, device=DEV) for _ in range(2))
+        pinned = pin(fr[0])
+        e, o = _lib.EpiIn(), _lib.EpiOut()
+        e.I1, e.I2, e.pixelPosD0, e.normDir, e.offset = p(pinned), p(dev[1]), p(dev[2]), p(dev[3]), p(dev[4])
+        e.width, e.height, e.dMax, e.vMax, e.P1, e.P2 = W, H, D, 0.3, 6, 64
+        o.bestD, o.minC = p(bd), p(mc)
+        return (lambda lib: lib.fsgm_calc_cost_sgm_device(1, C.byref(e), C.byref(o), None, None, None),
+                lambda: torch_ops.calc_cost_sgm(dev[0], dev[1], D, 0.3, dev[2], dev[3], dev[4], 6, 64, check=True),
+                lambda: fsgm_amd.calc_cost_sgm(fr[0], fr[1], D, 0.3, fr[2], fr[3], fr[4], 6, 64))
+    I0, I1 = synth.image_pair(W, H, 12, seed=44)
+    d0, d1, pinned = _t(I0), _t(I1), pin(I0[None])
+    minC = torch.empty((1, H, W), dtype=torch.uint32, device=DEV)
+    if family == "fsgm_pyramidal_sgm_device":
+        lib = _lib.load()
+        prm = lib.fsgm_pyramid_params_default()
+        prm.numPyd = 2
+        flow = torch.empty((1, 2, H, W), dtype=torch.float64, device=DEV)
+        return (lambda lib: lib.fsgm_pyramidal_sgm_device(1, p(pinned), p(d1), W, H, 1, C.byref(prm), p(flow), p(minC), None, None),
+                lambda: torch_ops.pyramidal_sgm(d0, d1, 2, check=True),
+                lambda: fsgm_amd.pyramidal_sgm(I0, I1, 2)[::2])         # (mv, minC) of (mv, mvPyd, minC)
+    assert family == "fsgm_epipolar_sgm_of_device"
+    g = synth.epi_geometry(W, H, "forward")
+    geo = torch_ops._geometries([float(x) for x in np.asarray(g[0]).reshape(-1)] + [float(x) for x in np.asarray(g[1]).reshape(-1)]
+                                + [g[2][0], g[2][1], float(g[3])], 1)
+    flow = torch.empty((1, 3, H, W), dtype=torch.float64, device=DEV)
+    return (lambda lib: lib.fsgm_epipolar_sgm_of_device(1, p(pinned), p(d1), W, H, 1, geo, D, 0.3, None, p(flow), p(minC), None, None),
+            lambda: torch_ops.epipolar_sgm_of(d0, d1, *g, D, 0.3, check=True),
+            lambda: fsgm_amd.epipolar_sgm_of(I0, I1, *g, D, 0.3))
+
+
+@pytest.mark.parametrize("family", ["fsgm_epi_postprocess_device", "fsgm_pyramidal_sgm_device", "fsgm_epipolar_sgm_of_device",
+                                    "fsgm_calc_cost_sgm_device"])
+def test_a_refused_first_call_does_not_disturb_the_next(gpu_lib, family):
+    """The entry points check the stream and every pointer before they look up or build a plan (capi_device.h,
+    device_check_args): a shape's first call, refused for one input in host memory, and then the valid call at that shape
+    against the host-pointer form, bit for bit.  (That the refused call built no plan is the order of the code; the ABI has
+    no plan count to assert it by.)"""
+    refused, got, want = _refusal_case(family)
+    lib = _lib.load()
+    assert refused(lib) == 1, lib.fsgm_last_error()
+    assert b"not device memory" in lib.fsgm_last_error()
+    for k, (g, w) in enumerate(zip(got(), want(), strict=True)):
+        assert _nan_equal(_n(g).reshape(w.shape), w), f"{family}: output {k}"
+
+
 def test_graph_capture_is_refused(gpu_lib):
     W, H, D = 32, 24, 16
     (fr,) = _frames(W, H, D, 1, seed=32)

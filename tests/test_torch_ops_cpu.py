@@ -161,3 +161,25 @@ def test_driver_device_argument_checks():
         assert fn(1, FAKE, FAKE, 0, 24, 1, C.byref(p), FAKE, None, None, None) == FSGM_ERR_INVALID and "width/height" in _err(lib)
         assert fn(1, FAKE, FAKE, 32, 24, 1, None, FAKE, None, None, None) == FSGM_ERR_INVALID and "null argument" in _err(lib)
         assert fn(1, FAKE, FAKE, 32, 24, 1, C.byref(p), None, None, None, None) == FSGM_ERR_INVALID and "null argument" in _err(lib)
+
+
+def test_cached_plan_entries_refuse_plan_arguments_before_any_device():
+    """What plan creation refuses without a GPU, the device entries on cached plans refuse before the device and pointer checks
+    (their plan is looked up only after those): the same status and message with or without a device, FAKE never queried."""
+    from fsgm_amd.epi import _params
+    lib = _lib.load()
+    e, o = _epi_args()
+    prm = _params(5, 1, 1, 0)
+    assert lib.fsgm_calc_cost_sgm_device(1, C.byref(e), C.byref(o), C.byref(prm), None, None) == FSGM_ERR_INVALID and "paths" in _err(lib)
+    prm = _params(4, 1, 1, 64)
+    assert lib.fsgm_calc_cost_sgm_device(1, C.byref(e), C.byref(o), C.byref(prm), None, None) == FSGM_ERR_INVALID
+    assert _err(lib) == "device 64 out of range"
+    e, o = _epi_args(D=1025)
+    assert lib.fsgm_calc_cost_sgm_device(1, C.byref(e), C.byref(o), None, None, None) == FSGM_ERR_UNSUPPORTED and "maximum" in _err(lib)
+    g = EpiGeometry()
+    assert lib.fsgm_epipolar_sgm_of_device(1, FAKE, FAKE, 32, 24, 1, C.byref(g), 1025, 0.3, None, FAKE, None, None, None) == FSGM_ERR_UNSUPPORTED
+    assert "maximum" in _err(lib)
+    prm = lib.fsgm_pyramid_params_default()
+    prm.numPyd = 17
+    assert lib.fsgm_pyramidal_sgm_device(1, FAKE, FAKE, 32, 24, 1, C.byref(prm), FAKE, None, None, None) == FSGM_ERR_INVALID
+    assert "numPyd" in _err(lib)
