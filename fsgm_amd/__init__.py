@@ -10,6 +10,7 @@ from .sgm import sgm_batch  # noqa: F401  (ahead of .epi: the name fsgm_amd.sgm 
 from .epi import (calc_cost_sgm, calc_cost_sgm_batch, EpiPlan, epipolar_maps, epipolar_sgm_of, epipolar_flow_pp, epipolar_from_F,  # noqa: F401
                   census, sgm, auto_pipeline, calc_cost_sgm_linear, calc_cost_sgm_linear_batch, stereo_sgm, stereo_maps)
 from .pyd import calc_pyd_cost_sgm, calc_pyd_cost_sgm_batch, PydPlan  # noqa: F401
+from .sgm2d import sgm2d_batch  # noqa: F401
 from .pyramid import (pyramidal_sgm, pyramidal_sgm_ng, pyramidal_sgm_batch, pyramidal_sgm_ng_batch, PyramidPlan, NgPyramidPlan,  # noqa: F401
                       pyramidal_flow_pp)
 from .post import (speckle_filter, calc_disp_from_first, forward_backward_check, scanline_in_fill, vzInd2Disp, vmf,  # noqa: F401

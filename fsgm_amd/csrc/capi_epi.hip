@@ -1187,8 +1187,10 @@ void fsgm_ng_shutdown_internal(void);
 void fsgm_ng_pyramid_shutdown_internal(void);
 void fsgm_flow_pp_shutdown_internal(void);
 void fsgm_stereo_pp_shutdown_internal(void);
+void fsgm_sgm2d_shutdown_internal(void);
 
 void fsgm_shutdown(void) {
+    fsgm_sgm2d_shutdown_internal();
     fsgm_stereo_pp_shutdown_internal();
     fsgm_flow_pp_shutdown_internal();
     fsgm_ng_pyramid_shutdown_internal();

@@ -11,15 +11,14 @@
 using namespace fsgm;
 
 
-// the search windows the 2-D kernels accept, checked before a device is touched: the sides, then the candidate count
-// (two steps, so that fsgm_pyd_plan_create keeps its order of checks: sides, batch, count)
-static fsgm_status pyd_check_sides(int32_t rX, int32_t rY, int32_t rAgg) {
+// the search windows the 2-D kernels accept (pyd_plan.h)
+fsgm_status fsgm::pyd_check_sides(int32_t rX, int32_t rY, int32_t rAgg) {
     FSGM_REQUIRE(rX >= 0 && rY >= 0 && rAgg >= 0, "window half sizes must be >= 0");
     if (2 * (long long)rX + 1 > FSGM_PYD_MAX_SIDE || 2 * (long long)rY + 1 > FSGM_PYD_MAX_SIDE)
         return fail(FSGM_ERR_UNSUPPORTED, "search window side exceeds %d", FSGM_PYD_MAX_SIDE);
     return FSGM_OK;
 }
-static fsgm_status pyd_check_count(int32_t rX, int32_t rY) {
+fsgm_status fsgm::pyd_check_count(int32_t rX, int32_t rY) {
     const long long D = (long long)(2 * rX + 1) * (2 * rY + 1);
     if (D > FSGM_PYD_MAX_D) return fail(FSGM_ERR_UNSUPPORTED, "search window %lld candidates exceeds %d", D, FSGM_PYD_MAX_D);
     return FSGM_OK;
@@ -49,9 +48,11 @@ fsgm_status fsgm_pyd_launch_lds(int32_t rX, int32_t rY, int32_t rAgg, int32_t* c
 void fsgm_pyd_plan_destroy(fsgm_pyd_plan* p) {
     if (!p) return;
     (void)hipSetDevice(p->device);
-    void* bufs[] = {p->dI1, p->dI2, p->dC, p->dL, p->dCen1, p->dCen2, p->dBestD, p->dMinC, p->dS, p->dDesc, p->dMv, p->dMvSub};
+    void* bufs[] = {p->dI1, p->dI2, p->dC, p->dL, p->dCen1, p->dCen2, p->dBestD, p->dMinC, p->dS, p->dDesc, p->dMv, p->dMvSub,
+                    p->dIngest, p->dIngestFlag, p->dFlow};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
+    p->join.destroy();
     if (p->ev0) (void)hipEventDestroy(p->ev0);
     if (p->ev1) (void)hipEventDestroy(p->ev1);
     if (p->stream && p->owns_stream) (void)hipStreamDestroy(p->stream);
@@ -60,6 +61,13 @@ void fsgm_pyd_plan_destroy(fsgm_pyd_plan* p) {
 
 fsgm_status fsgm_pyd_plan_create(fsgm_pyd_plan** out, int32_t W, int32_t H, int32_t mvW, int32_t mvH,
                                  int32_t rX, int32_t rY, int32_t rAgg, int32_t batch, int32_t device) {
+    return pyd_plan_create_flags(out, W, H, mvW, mvH, rX, rY, rAgg, batch, device, 0);
+}
+
+}  // extern "C"
+
+fsgm_status fsgm::pyd_plan_create_flags(fsgm_pyd_plan** out, int32_t W, int32_t H, int32_t mvW, int32_t mvH, int32_t rX, int32_t rY,
+                                        int32_t rAgg, int32_t batch, int32_t device, int flags) {
     FSGM_REQUIRE(out, "fsgm_pyd_plan_create: null plan pointer");
     *out = nullptr;
     FSGM_REQUIRE(W >= 1 && H >= 1, "width/height must be >= 1 (got %d x %d)", W, H);
@@ -73,17 +81,20 @@ fsgm_status fsgm_pyd_plan_create(fsgm_pyd_plan** out, int32_t W, int32_t H, int3
     { const fsgm_status ds = use_device(device); if (ds != FSGM_OK) return ds; }
     fsgm_pyd_plan* p = new fsgm_pyd_plan;
     p->W = W; p->H = H; p->mvW = mvW; p->mvH = mvH; p->rX = rX; p->rY = rY; p->rAgg = rAgg;
-    p->batch = batch; p->device = device;
+    p->batch = batch; p->device = device; p->flags = flags;
+    const bool agg_only = (flags & PYD_PLAN_AGG_ONLY) != 0;
     p->Sx = 2 * rX + 1; p->Sy = 2 * rY + 1; p->D = (int)D;
     p->RS = pyd_row_stride(p->Sx, p->Sy); p->PS = p->Sx * p->RS;
     p->NP = (size_t)W * H; p->N = p->NP * p->PS; p->MV = (size_t)mvW * mvH;
     const size_t B = batch;
     hipError_t e = hipSuccess;
     auto alloc = [&](void** ptr, size_t bytes) { if (e == hipSuccess) e = hipMalloc(ptr, bytes); };
-    alloc((void**)&p->dI1, B * p->NP);
-    alloc((void**)&p->dI2, B * p->NP);
-    alloc((void**)&p->dCen1, B * p->NP * 4);
-    alloc((void**)&p->dCen2, B * p->NP * 4);
+    if (!agg_only || (flags & PYD_PLAN_GUIDE)) alloc((void**)&p->dI1, B * p->NP);
+    if (!agg_only) {
+        alloc((void**)&p->dI2, B * p->NP);
+        alloc((void**)&p->dCen1, B * p->NP * 4);
+        alloc((void**)&p->dCen2, B * p->NP * 4);
+    }
     alloc((void**)&p->dMv, B * p->MV * 16);
     alloc((void**)&p->dC, B * p->N);
     alloc((void**)&p->dL, B * p->N * 8);
@@ -93,6 +104,7 @@ fsgm_status fsgm_pyd_plan_create(fsgm_pyd_plan** out, int32_t W, int32_t H, int3
     alloc((void**)&p->dMinC, B * p->NP * 4);
     alloc((void**)&p->dMvSub, B * p->NP * 16);
     if (e == hipSuccess) e = hipMemset(p->dC, 0, B * p->N);         // padding bytes of the rows layout stay defined
+    if (e == hipSuccess && agg_only) { e = hipMemset(p->dMv, 0, B * p->MV * 16); p->mv_zero = true; }
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking);
     if (e == hipSuccess) e = hipEventCreate(&p->ev0);
     if (e == hipSuccess) e = hipEventCreate(&p->ev1);
@@ -113,6 +125,8 @@ fsgm_status fsgm_pyd_plan_create(fsgm_pyd_plan** out, int32_t W, int32_t H, int3
     *out = p;
     return FSGM_OK;
 }
+
+extern "C" {
 
 fsgm_status fsgm_pyd_plan_set_params(fsgm_pyd_plan* p, int32_t P1, int32_t P2, int32_t diag, int32_t totalPass,
                                      int32_t adaptive, int32_t subpixel) {
@@ -169,7 +183,9 @@ static int fsgm_env_wide() {
 fsgm_status fsgm::pyd_enqueue(fsgm_pyd_plan* p, int stages, uint32_t* dS) {
     PydAggArgs g;
     PydWtaArgs w;
-    g.I1 = p->dI1; g.C = p->dC; g.mv = p->dMv; g.L = p->dL; g.desc = p->dDesc; g.dump = p->dDesc ? p->dDesc + (size_t)p->batch * p->NP * 8 : nullptr;
+    // (a plan without an image -- aggregation-only, no adaptive P2: the kernels fetch the intensity step of every path step and
+    // use it with adaptive P2 only; the volume stands in as batch * NP readable bytes)
+    g.I1 = p->dI1 ? p->dI1 : p->dC; g.C = p->dC; g.mv = p->dMv; g.L = p->dL; g.desc = p->dDesc; g.dump = p->dDesc ? p->dDesc + (size_t)p->batch * p->NP * 8 : nullptr;
     g.W = p->W; g.H = p->H; g.mvW = p->mvW; g.mvH = p->mvH; g.Sx = p->Sx; g.Sy = p->Sy;
     g.RS = p->RS; g.PS = p->PS;
     g.P1 = p->P1; g.P2 = p->P2; g.adaptive = p->adaptive;
@@ -180,7 +196,8 @@ fsgm_status fsgm::pyd_enqueue(fsgm_pyd_plan* p, int stages, uint32_t* dS) {
     // A single landscape frame is bounded by its longest serial chains, the horizontal lines: those take
     // the kernel's one-line-per-wave mapping (fewer instructions per step); batches keep the packed one.
     const bool wide_rows = rows && p->batch <= 2 && p->W > p->H && fsgm_env_wide() != 0;
-    plan_pyd_dirs(g, p->diagonal, p->totalPass, w.weight, rows ? 16 : 4, wide_rows || (rows && fsgm_env_wide() == 2));
+    const bool wide = wide_rows || (rows && fsgm_env_wide() == 2);
+    plan_pyd_dirs(g, p->diagonal, p->totalPass, w.weight, rows ? 16 : 4, wide);
     if (stages & FSGM_STAGE_COST) {
         launch_census(p->stream, p->dI1, p->dCen1, p->W, p->H, p->batch);       // :485-486
         launch_census(p->stream, p->dI2, p->dCen2, p->W, p->H, p->batch);
@@ -192,6 +209,7 @@ fsgm_status fsgm::pyd_enqueue(fsgm_pyd_plan* p, int stages, uint32_t* dS) {
         p->cmax = 24;
     }
     if (stages & FSGM_STAGE_AGGREGATE) {
+        p->agg_name = rows ? (wide ? "rows/wide" : "rows") : nowrap ? "generic" : "generic/wrap";
         if (rows) {
             // (making the descriptors on a side stream while the cost volume is built was tried: the event
             // fork/join costs more than the 0.06 ms it hides -- 1.71 vs 1.68 ms per 3-level pyramid)

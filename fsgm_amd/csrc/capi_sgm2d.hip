@@ -1,0 +1,249 @@
+// capi_sgm2d.hip -- C ABI of the 2-D matcher on batches of caller-supplied cost volumes, in host memory or in HBM
+// (include/fsgm.h: fsgm_sgm2d_batch_host, fsgm_sgm2d_device, fsgm_pyd_plan_ingest_cost_device).  Everything that can be
+// refused without a device is refused first; behind that both forms take one cached aggregation-only fsgm_pyd_plan, bring
+// the volumes into its padded layout with the kernels of sgm2d_ingest.hip and run pyd_enqueue's aggregation and WTA on it.
+#include "capi_common.h"
+#include "capi_device.h"
+#include "pyd_kernels.h"
+#include "pyd_plan.h"
+#include "pyramid_kernels.h"
+#include "sgm2d_ingest.h"
+#include <mutex>
+#include <string.h>
+
+using namespace fsgm;
+
+namespace {
+
+// a checked call: prm never the caller's NULL, guide non-NULL exactly with adaptive_p2, mvW x mvH the hint map's size
+// (the image's without preMv)
+struct Sgm2dCall {
+    int n, W, H, rX, rY, P1, P2, mvW, mvH;
+    fsgm_sgm2d_params prm;
+    const uint8_t* C;
+    const double* preMv;
+    const uint8_t* guide;
+    uint32_t *bestD, *minC;
+    double *mvSub, *flow;
+    uint32_t* S;
+};
+
+bool layout_ok(int layout) {
+    return layout == FSGM_COST2D_LAYOUT_HWD || layout == FSGM_COST2D_LAYOUT_DHW || layout == FSGM_COST2D_LAYOUT_DHW_YX;
+}
+
+// the checks both forms share, none of which needs a device
+fsgm_status sgm2d_args(const char* who, int32_t n, const uint8_t* C, int32_t W, int32_t H, int32_t rX, int32_t rY, int32_t P1, int32_t P2,
+                       const fsgm_sgm2d_params* prm, const double* preMv, int32_t mvW, int32_t mvH, const uint8_t* guide, uint32_t* bestD,
+                       uint32_t* minC, double* mvSub, double* flow, uint32_t* S, Sgm2dCall* c) {
+    FSGM_REQUIRE(n >= 1, "%s: n_frames must be >= 1 (got %d)", who, n);
+    FSGM_REQUIRE(W >= 1 && H >= 1, "%s: width/height must be >= 1 (got %d x %d)", who, W, H);
+    FSGM_REQUIRE(rX >= 0 && rY >= 0, "%s: halfX/halfY must be >= 0 (got %d, %d)", who, rX, rY);
+    fsgm_status st = pyd_check_sides(rX, rY, 0);
+    if (st == FSGM_OK) st = pyd_check_count(rX, rY);
+    if (st != FSGM_OK) return st;
+    const int D = (2 * rX + 1) * (2 * rY + 1);
+    if ((double)W * H * D >= 2147483648.0)
+        return fail(FSGM_ERR_UNSUPPORTED, "%s: cost volume %d x %d x %d exceeds 2^31 voxels per frame", who, W, H, D);
+    const fsgm_sgm2d_params sp = prm ? *prm : fsgm_sgm2d_params_default();
+    FSGM_REQUIRE(layout_ok(sp.layout), "%s: layout must be FSGM_COST2D_LAYOUT_HWD (0), _DHW (1) or _DHW_YX (2), got %d", who, sp.layout);
+    FSGM_REQUIRE(sp.cost_bound >= 1 && sp.cost_bound <= 255, "%s: cost_bound must be 1..255 (got %d)", who, sp.cost_bound);
+    FSGM_REQUIRE(sp.totalPass >= 1 && sp.totalPass <= 2, "%s: totalPass must be 1 or 2 (got %d)", who, sp.totalPass);
+    FSGM_REQUIRE(sp.diagonal == 0 || sp.diagonal == 1, "%s: diagonal must be 0 or 1 (got %d)", who, sp.diagonal);
+    FSGM_REQUIRE(sp.adaptive_p2 == 0 || sp.adaptive_p2 == 1, "%s: adaptive_p2 must be 0 or 1 (got %d)", who, sp.adaptive_p2);
+    FSGM_REQUIRE(sp.subpixel == 0 || sp.subpixel == 1, "%s: subpixel must be 0 or 1 (got %d)", who, sp.subpixel);
+    for (int r : sp.reserved) FSGM_REQUIRE(r == 0, "%s: the reserved words of fsgm_sgm2d_params must be zero", who);
+    FSGM_REQUIRE(sp.device >= 0 && sp.device < FSGM_MAX_DEVICES, "%s: device %d out of range", who, sp.device);
+    FSGM_REQUIRE(C && bestD && minC && mvSub, "%s: null argument (C, bestD, minC and mvSub are required)", who);
+    FSGM_REQUIRE(!preMv || (mvW >= W && mvH >= H), "%s: preMv (%d x %d) must be at least as large as the image (%d x %d): the "
+                 "reference indexes it with image coordinates (calc_pyd_cost_sgm.cpp:388-389)", who, mvW, mvH, W, H);
+    FSGM_REQUIRE(!sp.adaptive_p2 || guide, "%s: adaptive_p2 needs the guide image (guide is NULL)", who);
+    *c = Sgm2dCall{n, W, H, rX, rY, P1, P2, preMv ? mvW : W, preMv ? mvH : H, sp, C, preMv, sp.adaptive_p2 ? guide : nullptr,
+                   bestD, minC, mvSub, flow, S};
+    return FSGM_OK;
+}
+
+// Aggregation-only plans (pyd_plan.h), keyed by shape, window, hint-map size, batch, device and whether a guide is held.
+// The host and the device form share them: a call holds its device's lock for its length and queues on the plan's stream.
+PlanCache<fsgm_pyd_plan> g_sgm2d(6, fsgm_pyd_plan_destroy);
+thread_local const char* g_sgm2d_kernel = "";
+
+// the cached plan of a checked call, with the call's parameters and `cmax` set; the device's lock is the caller's
+fsgm_status sgm2d_plan(fsgm_pyd_plan** out, const Sgm2dCall& c, int cmax) {
+    const int dev = c.prm.device, flags = PYD_PLAN_AGG_ONLY | (c.guide ? PYD_PLAN_GUIDE : 0);
+    fsgm_pyd_plan* p = g_sgm2d.find(dev, [&](const fsgm_pyd_plan* q) {
+        return q->W == c.W && q->H == c.H && q->mvW == c.mvW && q->mvH == c.mvH && q->rX == c.rX && q->rY == c.rY && q->batch == c.n &&
+               q->flags == flags;
+    });
+    fsgm_status st;
+    if (!p) {
+        if ((st = pyd_plan_create_flags(&p, c.W, c.H, c.mvW, c.mvH, c.rX, c.rY, 0, c.n, dev, flags)) != FSGM_OK) return st;
+        g_sgm2d.insert(dev, p);
+    } else if ((st = use_device(dev)) != FSGM_OK) {
+        return st;
+    }
+    if ((st = fsgm_pyd_plan_set_params(p, c.P1, c.P2, c.prm.diagonal, c.prm.totalPass, c.prm.adaptive_p2, c.prm.subpixel)) != FSGM_OK) return st;
+    p->cmax = cmax;
+    *out = p;
+    return FSGM_OK;
+}
+
+fsgm_status ensure_ingest_flag(fsgm_pyd_plan* p) {
+    if (p->dIngestFlag) return FSGM_OK;
+    FSGM_HIP(hipMalloc((void**)&p->dIngestFlag, sizeof(uint32_t)));
+    FSGM_HIP(hipMemsetAsync(p->dIngestFlag, 0, sizeof(uint32_t), p->stream));
+    return FSGM_OK;
+}
+
+// zero hints for a call without preMv: the plan's own map, cleared when an earlier host call left its hints there
+fsgm_status zero_hints(fsgm_pyd_plan* p) {
+    if (p->mv_zero) return FSGM_OK;
+    FSGM_HIP(hipMemsetAsync(p->dMv, 0, (size_t)p->batch * p->MV * 16, p->stream));
+    p->mv_zero = true;
+    return FSGM_OK;
+}
+
+// aggregation + WTA on the plan's volume, then hint + window offset + mvSub (pyramidal_sgm.m:57-64) when a flow is wanted;
+// dS, dFlow may be NULL.  The plan's slots hold whatever the caller bound.
+fsgm_status sgm2d_enqueue(fsgm_pyd_plan* p, uint32_t* dS, double* dFlow) {
+    const fsgm_status st = pyd_enqueue(p, FSGM_STAGE_AGGREGATE | FSGM_STAGE_WTA, dS);
+    if (st != FSGM_OK) return st;
+    g_sgm2d_kernel = p->agg_name;
+    if (dFlow) {
+        PyrFlowArgs a;
+        a.bestD = p->dBestD; a.mvSub = p->dMvSub; a.mvPre = p->dMv; a.flow = dFlow; a.next = nullptr;
+        a.W = p->W; a.H = p->H; a.mvW = p->mvW; a.mvH = p->mvH; a.Sy = p->Sy; a.hor = p->rX; a.ver = p->rY; a.next_frame_stride = 0;
+        launch_pyr_flow(p->stream, a, p->batch);
+        FSGM_HIP(hipGetLastError());
+    }
+    return FSGM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+void fsgm_sgm2d_shutdown_internal(void) { g_sgm2d.clear(); }
+
+fsgm_sgm2d_params fsgm_sgm2d_params_default(void) {
+    fsgm_sgm2d_params p;
+    memset(&p, 0, sizeof(p));
+    p.diagonal = 1;                      // pyramidal_sgm.m:15-22
+    p.totalPass = 2;
+    p.subpixel = 1;
+    p.layout = FSGM_COST2D_LAYOUT_HWD;
+    p.cost_bound = 255;
+    return p;
+}
+
+const char* fsgm_sgm2d_last_kernel(void) { return g_sgm2d_kernel; }
+
+fsgm_status fsgm_sgm2d_batch_host(int32_t n, const uint8_t* C, int32_t W, int32_t H, int32_t rX, int32_t rY, int32_t P1, int32_t P2,
+                                  const fsgm_sgm2d_params* prm, const double* preMv, int32_t mvW, int32_t mvH, const uint8_t* guide,
+                                  uint32_t* bestD, uint32_t* minC, double* mvSub, double* flow, uint32_t* S) {
+    const char* who = "fsgm_sgm2d_batch_host";
+    Sgm2dCall c;
+    fsgm_status st = sgm2d_args(who, n, C, W, H, rX, rY, P1, P2, prm, preMv, mvW, mvH, guide, bestD, minC, mvSub, flow, S, &c);
+    if (st != FSGM_OK) return st;
+    // the true maximum of the batch (every layout holds the same bytes), as fsgm_pyd_plan_upload_cost takes it
+    const size_t NP = (size_t)W * H, ND = NP * (2 * rX + 1) * (2 * rY + 1);
+    int cmax = 0;
+    for (int f = 0; f < n; f++) {
+        const uint8_t* v = C + (size_t)f * ND;
+        int m = 0;
+        for (size_t i = 0; i < ND; i++) m = v[i] > m ? v[i] : m;
+        FSGM_REQUIRE(m <= c.prm.cost_bound, "%s: frame %d holds a cost of %d, above cost_bound %d", who, f, m, c.prm.cost_bound);
+        cmax = m > cmax ? m : cmax;
+    }
+    std::lock_guard<std::mutex> lk(g_sgm2d.mu(c.prm.device));
+    fsgm_pyd_plan* p = nullptr;
+    if ((st = sgm2d_plan(&p, c, cmax)) != FSGM_OK) return st;
+    const size_t B = n;
+    if (!p->dIngest) FSGM_HIP(hipMalloc((void**)&p->dIngest, B * ND));
+    if (S && !p->dS) FSGM_HIP(hipMalloc((void**)&p->dS, B * ND * 4));
+    if (flow && !p->dFlow) FSGM_HIP(hipMalloc((void**)&p->dFlow, B * NP * 16));
+    StreamGuard guard(p->stream);                                // every early exit drains the stream: the copies use caller memory
+    // staged as it came, brought into the plan's layout by the kernel the device form runs (the scan above has checked the bound)
+    FSGM_HIP(hipMemcpyAsync(p->dIngest, C, B * ND, hipMemcpyHostToDevice, p->stream));
+    launch_sgm2d_ingest(p->stream, p->dIngest, p->dC, n, W, H, p->Sx, p->Sy, c.prm.layout, 255, nullptr);
+    if (preMv) {
+        FSGM_HIP(hipMemcpyAsync(p->dMv, preMv, B * p->MV * 16, hipMemcpyHostToDevice, p->stream));
+        p->mv_zero = false;
+    } else if ((st = zero_hints(p)) != FSGM_OK) {
+        return st;
+    }
+    if (c.guide) FSGM_HIP(hipMemcpyAsync(p->dI1, c.guide, B * NP, hipMemcpyHostToDevice, p->stream));
+    if ((st = sgm2d_enqueue(p, S ? p->dS : nullptr, flow ? p->dFlow : nullptr)) != FSGM_OK) return st;
+    FSGM_HIP(hipMemcpyAsync(bestD, p->dBestD, B * NP * 4, hipMemcpyDeviceToHost, p->stream));
+    FSGM_HIP(hipMemcpyAsync(minC, p->dMinC, B * NP * 4, hipMemcpyDeviceToHost, p->stream));
+    FSGM_HIP(hipMemcpyAsync(mvSub, p->dMvSub, B * NP * 16, hipMemcpyDeviceToHost, p->stream));
+    if (flow) FSGM_HIP(hipMemcpyAsync(flow, p->dFlow, B * NP * 16, hipMemcpyDeviceToHost, p->stream));
+    if (S) FSGM_HIP(hipMemcpyAsync(S, p->dS, B * ND * 4, hipMemcpyDeviceToHost, p->stream));
+    FSGM_HIP(hipStreamSynchronize(p->stream));
+    guard.dismiss();
+    return FSGM_OK;
+}
+
+fsgm_status fsgm_sgm2d_device(int32_t n, const uint8_t* C, int32_t W, int32_t H, int32_t rX, int32_t rY, int32_t P1, int32_t P2,
+                              const fsgm_sgm2d_params* prm, const double* preMv, int32_t mvW, int32_t mvH, const uint8_t* guide,
+                              uint32_t* bestD, uint32_t* minC, double* mvSub, double* flow, uint32_t* S, void* stream, int32_t* status) {
+    const char* who = "fsgm_sgm2d_device";
+    Sgm2dCall c;
+    fsgm_status st = sgm2d_args(who, n, C, W, H, rX, rY, P1, P2, prm, preMv, mvW, mvH, guide, bestD, minC, mvSub, flow, S, &c);
+    if (st != FSGM_OK) return st;
+    const size_t np = (size_t)n * W * H, nv = np * (2 * rX + 1) * (2 * rY + 1), nmv = (size_t)n * c.mvW * c.mvH;
+    const hipStream_t cs = (hipStream_t)stream;
+    if ((st = device_check_args(who, c.prm.device, cs, {{C, nv, 1, true, "C"},
+                                                        {preMv, nmv * 16, 8, false, "preMv"},
+                                                        {c.guide, np, 1, false, "guide"},
+                                                        {bestD, np * 4, 4, true, "bestD"},
+                                                        {minC, np * 4, 4, true, "minC"},
+                                                        {mvSub, np * 16, 8, true, "mvSub"},
+                                                        {flow, np * 16, 8, false, "flow"},
+                                                        {S, nv * 4, 4, false, "S"},
+                                                        {status, 4, 4, false, "status"}})) != FSGM_OK)
+        return st;
+    std::lock_guard<std::mutex> lk(g_sgm2d.mu(c.prm.device));
+    fsgm_pyd_plan* p = nullptr;
+    // The device cannot be asked for the true maximum without a wait: the declared bound selects the aggregation, the ingest
+    // kernel saturates at it.  What a warm call must not do (allocate) happens before the join with the caller's stream.
+    if ((st = sgm2d_plan(&p, c, c.prm.cost_bound)) != FSGM_OK) return st;
+    if ((st = ensure_ingest_flag(p)) != FSGM_OK) return st;
+    return device_call(p->join, cs, p->stream, [&]() -> fsgm_status {
+        launch_sgm2d_ingest(p->stream, C, p->dC, n, W, H, p->Sx, p->Sy, c.prm.layout, c.prm.cost_bound, p->dIngestFlag);
+        if (!preMv) {
+            const fsgm_status zs = zero_hints(p);
+            if (zs != FSGM_OK) return zs;
+        }
+        // the caller's arrays stand in the plan's slots for the length of the enqueue
+        Bind<double> mv(p->dMv, const_cast<double*>(preMv)), ms(p->dMvSub, mvSub);
+        Bind<uint8_t> i1(p->dI1, const_cast<uint8_t*>(c.guide));
+        Bind<uint32_t> bd(p->dBestD, bestD), mc(p->dMinC, minC);
+        const fsgm_status es = sgm2d_enqueue(p, S, flow);
+        if (es != FSGM_OK) return es;
+        launch_device_status(p->stream, nullptr, p->dIngestFlag, status);
+        return FSGM_OK;
+    });
+}
+
+fsgm_status fsgm_pyd_plan_ingest_cost_device(fsgm_pyd_plan* p, int32_t n, const uint8_t* C, int32_t layout, int32_t cost_bound,
+                                             void* stream, int32_t* status) {
+    const char* who = "fsgm_pyd_plan_ingest_cost_device";
+    FSGM_REQUIRE(p && C, "%s: null argument", who);
+    FSGM_REQUIRE(n == p->batch, "%s: n_frames %d differs from the plan's batch %d", who, n, p->batch);
+    FSGM_REQUIRE(layout_ok(layout), "%s: layout must be FSGM_COST2D_LAYOUT_HWD (0), _DHW (1) or _DHW_YX (2), got %d", who, layout);
+    FSGM_REQUIRE(cost_bound >= 1 && cost_bound <= 255, "%s: cost_bound must be 1..255 (got %d)", who, cost_bound);
+    const hipStream_t cs = (hipStream_t)stream;
+    fsgm_status st;
+    if ((st = device_check_args(who, p->device, cs, {{C, (size_t)n * p->NP * p->D, 1, true, "C"}, {status, 4, 4, false, "status"}})) != FSGM_OK)
+        return st;
+    if ((st = ensure_ingest_flag(p)) != FSGM_OK) return st;
+    p->cmax = cost_bound;
+    return device_call(p->join, cs, p->stream, [&] {
+        launch_sgm2d_ingest(p->stream, C, p->dC, n, p->W, p->H, p->Sx, p->Sy, layout, cost_bound, p->dIngestFlag);
+        launch_device_status(p->stream, nullptr, p->dIngestFlag, status);
+        return FSGM_OK;
+    });
+}
+
+}  // extern "C"

@@ -147,7 +147,7 @@ class PydPlan:
         self.W, self.H, self.mvW, self.mvH = int(width), int(height), int(mvWidth), int(mvHeight)
         self.Sx, self.Sy = 2 * int(rX) + 1, 2 * int(rY) + 1
         self.D = self.Sx * self.Sy
-        self.batch = int(batch)
+        self.batch, self.device = int(batch), int(device)
         self._h = C.c_void_p()
         check(self.lib.fsgm_pyd_plan_create(C.byref(self._h), self.W, self.H, self.mvW, self.mvH, int(rX), int(rY),
                                             int(rAgg), self.batch, int(device)))
@@ -184,6 +184,12 @@ class PydPlan:
         if Cv.dtype != np.uint8 or Cv.shape != (self.H, self.W, self.D):
             raise TypeError(f"C must be uint8 of shape {(self.H, self.W, self.D)}")
         check(self.lib.fsgm_pyd_plan_upload_cost(self._h, frame, ptr(Cv)))
+
+    def ingest_cost(self, costs, **kw):
+        """All frames' cost volumes from a uint8 torch tensor on the GPU, in any layout of fsgm_amd.sgm2d, ordered on the current
+        stream (fsgm_amd.torch_ops.ingest_cost2d; import torch before the library is loaded)."""
+        from . import torch_ops
+        return torch_ops.ingest_cost2d(self, costs, **kw)
 
     def run(self, stages=_lib.STAGE_ALL):
         check(self.lib.fsgm_pyd_plan_run(self._h, int(stages)))

@@ -8,7 +8,7 @@ points of include/fsgm.h ("Device-pointer entry points") as torch custom ops and
 No host<->device copy and no host wait once a plan for the shape exists: the work is queued behind what the current stream
 already holds, and what is queued on that stream afterwards runs after it.  Ops registered: fsgm::calc_cost_sgm,
 fsgm::calc_cost_sgm_linear, fsgm::stereo_sgm, fsgm::stereo_sgm_range, fsgm::sgm (a caller's cost volumes; status also
-FSGM_ERR_INVALID when a cost was above the declared bound),
+FSGM_ERR_INVALID when a cost was above the declared bound), fsgm::sgm2d (the 2-D matcher on a caller's volumes; the same status),
 fsgm::epipolar_sgm_of, fsgm::pyramidal_sgm, fsgm::pyramidal_sgm_ng, fsgm::epipolar_flow_pp, fsgm::pyramidal_flow_pp (each also returns a 0-d int32
 status tensor: 0, or FSGM_ERR_HIP when an aggregation hand-off gave up; check=True in the wrappers synchronises and raises
 on it), fsgm::epi_postprocess (status FSGM_ERR_INVALID when a D1 value is negative), fsgm::vmf and fsgm::flow_fb_check; for rectified
@@ -31,6 +31,7 @@ from .epi import EpiGeometry, _d_min, _params as _epi_params, _stereo_params
 from .post import _bind as _bind_post
 from .stereo_pp import CHAIN_FIELDS as STEREO_PP_FIELDS, _bind as _bind_stereo_pp, pp_params as _stereo_pp_params
 from .sgm import _bind as _bind_sgm, layout_code as _layout_code, params as _sgm_params, shape_of as _sgm_shape
+from .sgm2d import _bind as _bind_sgm2d, layout_code as _layout2d_code, params as _sgm2d_params, shape_of as _sgm2d_shape, LAYOUTS as _LAYOUTS2D
 from .pyramid import PyramidParams, NgPyramidParams, FLOW_PP_FIELDS, MATCHERS, _bind as _bind_pyramid, _bind_flow_pp, _bind_ng
 
 FSGM_ERR_INVALID, FSGM_ERR_HIP = 1, 2
@@ -63,6 +64,7 @@ _bind_post(_L)
 _bind_flow_pp(_L)
 _bind_stereo_pp(_L)
 _bind_sgm(_L)
+_bind_sgm2d(_L)
 _L.fsgm_calc_cost_sgm_device.argtypes = [_i32, C.POINTER(EpiIn), C.POINTER(EpiOut), C.POINTER(EpiParams), _vp, _vp]
 _L.fsgm_calc_cost_sgm_linear_device.argtypes = [_i32, C.POINTER(EpiIn), C.POINTER(EpiOut), C.POINTER(EpiParams), _vp, _vp]
 _L.fsgm_stereo_sgm_device.argtypes = [_i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, C.POINTER(StereoParams), _vp, _vp, _vp, _vp, _vp, _vp]
@@ -271,6 +273,50 @@ def _sgm_op(C_: torch.Tensor, guide: torch.Tensor, P1: int, P2: int, paths: int,
 @_sgm_op.register_fake
 def _(C_, guide, P1, P2, paths, layout, cost_bound, agg_mode, adaptive_p2, subpixel, return_sum):
     return _sgm_outputs(C_, layout, return_sum)
+
+
+def _sgm2d_out_shape(C_, layout, half_x, half_y):
+    if layout not in (0, 1, 2):
+        raise ValueError(f"layout must be 0 (hwd), 1 (dhw) or 2 (dhw_yx), got {layout}")
+    n, H, W, D = _sgm2d_shape(tuple(C_.shape), "hwd" if layout == 0 else "dhw", half_x, half_y)
+    if n is None:
+        raise TypeError(f"fsgm::sgm2d takes batched costs (N, ...), got {tuple(C_.shape)}")
+    return n, H, W, D
+
+
+def _sgm2d_outputs(C_, layout, half_x, half_y, return_flow, return_sum):
+    N, H, W, D = _sgm2d_out_shape(C_, layout, half_x, half_y)
+    dev = C_.device
+    return (_u32((N, H, W), dev), _u32((N, H, W), dev), _f64((N, 2, H, W), dev), _f64((N, 2, H, W) if return_flow else (0,), dev),
+            _u32((N, H, W, D) if return_sum else (0,), dev), _status(dev))
+
+
+@torch.library.custom_op("fsgm::sgm2d", mutates_args=())
+def _sgm2d_op(C_: torch.Tensor, hints: torch.Tensor, guide: torch.Tensor, half_x: int, half_y: int, P1: int, P2: int, layout: int,
+              cost_bound: int, diagonal: int, total_pass: int, adaptive_p2: int, subpixel: int, return_flow: int,
+              return_sum: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """C_ (N, H, W, D) for layout 0, (N, D, H, W) for 1 (channel sx*Sy + sy) and 2 (channel sy*Sx + sx); hints (N, 2, mvH, mvW)
+    float64 or empty (zero hints); guide (N, H, W), read with adaptive_p2 only.  flow / S are empty unless asked for."""
+    N, H, W, D = _sgm2d_out_shape(C_, layout, half_x, half_y)
+    dev = C_.device
+    if not C_.is_contiguous():                            # (any byte offset will do: the ingest kernels assume no alignment)
+        raise TypeError("fsgm::sgm2d reads the costs where they lie: pass a contiguous tensor")
+    have_hints = hints.numel() != 0
+    hints = _ready(hints) if have_hints else None
+    mvH, mvW = (hints.shape[-2], hints.shape[-1]) if have_hints else (0, 0)
+    guide = guide.contiguous() if adaptive_p2 else None
+    bestD, minC, mvSub, flow, S, status = _sgm2d_outputs(C_, layout, half_x, half_y, return_flow, return_sum)
+    prm = _sgm2d_params(_L, diagonal=diagonal, total_pass=total_pass, adaptive_p2=adaptive_p2, subpixel=subpixel, device=dev.index,
+                        layout=[k for k, v in _LAYOUTS2D.items() if v == layout][0], cost_bound=cost_bound)
+    _call(dev, _L.fsgm_sgm2d_device, N, _p(C_), W, H, int(half_x), int(half_y), int(P1), int(P2), C.byref(prm), _p(hints), int(mvW),
+          int(mvH), _p(guide), _p(bestD), _p(minC), _p(mvSub), _p(flow) if return_flow else None, _p(S) if return_sum else None,
+          _stream(dev), _p(status))
+    return bestD, minC, mvSub, flow, S, status
+
+
+@_sgm2d_op.register_fake
+def _(C_, hints, guide, half_x, half_y, P1, P2, layout, cost_bound, diagonal, total_pass, adaptive_p2, subpixel, return_flow, return_sum):
+    return _sgm2d_outputs(C_, layout, half_x, half_y, return_flow, return_sum)
 
 
 def _epipolar_sgm_of_outputs(I0):
@@ -618,6 +664,53 @@ def sgm(Cvol, P1=7, P2=100, *, layout="dhw", paths=4, cost_bound=255, agg_mode=0
     return _finish(outs, status, batched, check, return_status, "a cost above cost_bound, or an aggregation hand-off that gave up")
 
 
+def sgm2d(costs, half_x, half_y, P1=6, P2=32, *, layout="dhw", hints=None, guide=None, cost_bound=255, diagonal=1, total_pass=2,
+          adaptive_p2=0, subpixel=1, return_flow=False, return_sum=False, check=False, return_status=False):
+    """(bestD, minC, mvSub[, flow][, S]) as fsgm_amd.sgm2d_batch, on cost volumes that are already in HBM: costs uint8 (D, H, W) or
+    a batch (N, D, H, W) for layout "dhw" (channel sx*Sy + sy) and "dhw_yx" (channel sy*Sx + sx, a correlation layer's order),
+    (H, W, D) / (N, H, W, D) for "hwd".  The tensor is read where it lies -- it must be contiguous, at any byte address -- every
+    output stays in HBM, the work is queued on the current stream.  hints float64 (.., 2, mvH, mvW) or None (zeros), guide uint8
+    (.., H, W) with adaptive_p2=1.  bestD, minC uint32 (.., H, W); mvSub and flow float64 (.., 2, H, W); S uint32 (.., H, W, D).
+    cost_bound: the caller's declaration that no cost is larger; the aggregation is selected for it and every cost is saturated at
+    it on the way in.  The status tensor (return_status=True) is FSGM_ERR_INVALID when a cost was above the bound (the outputs are
+    then those of the saturated volume); check=True synchronises and raises on it."""
+    code = _layout2d_code(layout)
+    named = {"costs": (costs, torch.uint8)}
+    if hints is not None:
+        named["hints"] = (hints, torch.float64)
+    if guide is not None:
+        named["guide"] = (guide, torch.uint8)
+    _tensors(named)
+    n, H, W, D = _sgm2d_shape(tuple(costs.shape), layout, half_x, half_y)
+    batched = n is not None
+    lead = (n,) if batched else ()
+    if not costs.is_contiguous():
+        raise TypeError("costs must be contiguous: the volume is read where it lies (no silent copy)")
+    if int(adaptive_p2) not in (0, 1):
+        raise ValueError(f"adaptive_p2 must be 0 or 1 (got {adaptive_p2!r})")
+    if hints is not None:
+        if hints.dim() != len(lead) + 3 or tuple(hints.shape[:-2]) != lead + (2,):
+            raise TypeError(f"hints must have shape {lead + (2, 'mvH', 'mvW')} (got {tuple(hints.shape)})")
+        if hints.shape[-2] < H or hints.shape[-1] < W:
+            raise ValueError(f"hints ({hints.shape[-2]} x {hints.shape[-1]}) must be at least as large as the image ({H} x {W})")
+    if guide is not None:                                  # (adaptive_p2 without one: the library refuses, status 1)
+        _shape("guide", guide, lead + (H, W))
+    if not batched:
+        costs = costs.unsqueeze(0)
+        hints = None if hints is None else hints.unsqueeze(0)
+        guide = None if guide is None else guide.unsqueeze(0)
+    dev = costs.device
+    if hints is None:
+        hints = torch.empty((0,), dtype=torch.float64, device=dev)
+    if guide is None or not adaptive_p2:
+        guide = torch.empty((0,), dtype=torch.uint8, device=dev)
+    bestD, minC, mvSub, flow, S, status = torch.ops.fsgm.sgm2d(costs, hints, guide, int(half_x), int(half_y), int(P1), int(P2), code,
+                                                               int(cost_bound), int(diagonal), int(total_pass), int(adaptive_p2),
+                                                               int(subpixel), int(bool(return_flow)), int(bool(return_sum)))
+    outs = (bestD, minC, mvSub) + ((flow,) if return_flow else ()) + ((S,) if return_sum else ())
+    return _finish(outs, status, batched, check, return_status, "a cost above cost_bound")
+
+
 def ingest_cost(plan, Cvol, *, layout="dhw", cost_bound=255, check=False, return_status=False):
     """All `plan.batch` cost volumes of an EpiPlan from a uint8 tensor on the plan's GPU (fsgm_epi_plan_ingest_cost_device): (N, D, H, W)
     for layout "dhw", (N, H, W, D) for "hwd", saturated at cost_bound, which the plan then selects its kernels by.  What
@@ -630,6 +723,24 @@ def ingest_cost(plan, Cvol, *, layout="dhw", cost_bound=255, check=False, return
     Cvol = Cvol.contiguous()
     status = _status(dev)
     _call(dev, _L.fsgm_epi_plan_ingest_cost_device, plan._h, plan.batch, _p(Cvol), code, int(cost_bound), _stream(dev), _p(status))
+    res = _finish((), status, True, check, return_status, "a cost above cost_bound")
+    return res[0] if return_status else None
+
+
+def ingest_cost2d(plan, costs, *, layout="dhw", cost_bound=255, check=False, return_status=False):
+    """All `plan.batch` cost volumes of a PydPlan from a uint8 tensor on the plan's GPU (fsgm_pyd_plan_ingest_cost_device):
+    (N, D, H, W) for layout "dhw" / "dhw_yx", (N, H, W, D) for "hwd", saturated at cost_bound, which the plan then selects its
+    aggregation by.  What PydPlan.upload_cost does from the host, frame by frame.  Returns the status tensor with
+    return_status=True, else None."""
+    code = _layout2d_code(layout)
+    dev = _tensors({"costs": (costs, torch.uint8)})
+    if dev.index != plan.device:
+        raise TypeError(f"the tensor is on {dev}, the plan on device {plan.device}")
+    _shape("costs", costs, (plan.batch, plan.H, plan.W, plan.D) if layout == "hwd" else (plan.batch, plan.D, plan.H, plan.W))
+    if not costs.is_contiguous():
+        raise TypeError("costs must be contiguous: the volume is read where it lies (no silent copy)")
+    status = _status(dev)
+    _call(dev, _L.fsgm_pyd_plan_ingest_cost_device, plan._h, plan.batch, _p(costs), code, int(cost_bound), _stream(dev), _p(status))
     res = _finish((), status, True, check, return_status, "a cost above cost_bound")
     return res[0] if return_status else None
 

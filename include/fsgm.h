@@ -449,6 +449,54 @@ fsgm_status fsgm_pyd_launch_lds(int32_t halfSearchWinSizeX, int32_t halfSearchWi
                                 int32_t* cost_kernel, uint64_t* cost_lds, uint64_t* patch_lds, uint64_t* agg_lds,
                                 uint64_t* rows_agg_lds);
 
+/* sgm2d(C) -- the 2-D matcher on caller-supplied cost volumes: the hinted-window aggregation, first-minimum WTA and x / y
+ * parabolas of calc_pyd_cost_sgm.cpp:114-372 (sgm2d) on a batch of u8 volumes the caller made (a flow network's correlation
+ * layer: (N, 81, H, W) for a 9x9 window).  The call shape is sgm2d.m's, whose only input is a ready volume.
+ * SEMANTICS ARE THE MEX'S, NOT sgm2d.m's: path arithmetic is mod 256 where sgm2d.m saturates (MATLAB uint8), and a path's
+ * first pixel stores minimum 0 (calc_pyd_cost_sgm.cpp:182 etc.) where sgm2d.m takes min(C) -- results differ from sgm2d.m's
+ * from the second pixel of every path on.  Float costs stay out, as for fsgm_sgm_batch_host.
+ * The window is (2*halfX+1) x (2*halfY+1) = Sx x Sy candidates; candidate (sx, sy) stands for the displacement
+ * (sx - halfX, sy - halfY) added to the pixel's hint, as in the MEX.  C: n_frames contiguous volumes in one of
+ *   FSGM_COST2D_LAYOUT_HWD     [H][W][Sx*Sy], candidate index sx*Sy + sy: the reference's order (calc_pyd_cost_sgm.cpp:392-393,
+ *                              x offset slow), what fsgm_pyd_plan_download_cost returns
+ *   FSGM_COST2D_LAYOUT_DHW     [Sx*Sy][H][W], channel sx*Sy + sy: a contiguous torch (N, D, H, W) tensor in the reference's order
+ *   FSGM_COST2D_LAYOUT_DHW_YX  [Sy*Sx][H][W], channel sy*Sx + sx: the y-slow order correlation layers emit
+ * each brought into the plan's own padded volume by one kernel pass on the device (the host form stages the bytes as they
+ * came and runs the same kernel).  Whatever the layout, bestD is the reference's candidate index sx*Sy + sy.
+ * preMv: the hints, f64 [n][2][mvHeight][mvWidth], plane 0 = x, at least as large as the image; NULL = zero hints (mvWidth
+ * and mvHeight are then not read): plain sgm2d.  guide: the first image, u8 [n][H][W], read with adaptive_p2 = 1 only
+ * (calc_pyd_cost_sgm.cpp:91-95); NULL with adaptive_p2 is FSGM_ERR_INVALID.
+ * bestD, minC u32 [n][H][W]; mvSub f64 [n][2][H][W] (zeros with subpixel = 0); flow (may be NULL) f64 [n][2][H][W] = hint +
+ * window offset + mvSub (pyramidal_sgm.m:57-64); S (may be NULL) u32 [n][H][W][Sx*Sy], the summed path costs in reference order.
+ * cost_bound, 1..255: the caller's declaration that no byte of C is larger; the aggregation kernels are chosen from it
+ * (cost_bound + P2 + max(P1, P2) <= 255 with penalties >= 0: no u8 narrowing changes a value, the row-packed kernels for
+ * windows up to 11x11; else the generic, wrapping ones).  The host form scans C and uses min(true maximum, cost_bound); a
+ * volume with a byte above a cost_bound below 255 is FSGM_ERR_INVALID and nothing is written.
+ * Refused before a device is touched: n_frames / width / height < 1, a negative half size, a layout outside the three,
+ * cost_bound outside 1..255, totalPass outside 1..2, diagonal / adaptive_p2 / subpixel other than 0 or 1, non-zero reserved
+ * words, a NULL C / bestD / minC / mvSub, a hint map smaller than the image (all FSGM_ERR_INVALID); a side above 64 or more
+ * than 1024 candidates, width*height*Sx*Sy >= 2^31 (FSGM_ERR_UNSUPPORTED). */
+#define FSGM_COST2D_LAYOUT_HWD 0
+#define FSGM_COST2D_LAYOUT_DHW 1
+#define FSGM_COST2D_LAYOUT_DHW_YX 2
+typedef struct {
+    int32_t diagonal, totalPass, adaptive_p2, subpixel, device, layout, cost_bound;
+    int32_t reserved[5];       /* must be zero */
+} fsgm_sgm2d_params;
+fsgm_sgm2d_params fsgm_sgm2d_params_default(void);   /* 1, 2, 0, 1, 0, FSGM_COST2D_LAYOUT_HWD, 255: pyramidal_sgm.m:15-22 */
+fsgm_status fsgm_sgm2d_batch_host(int32_t n_frames, const uint8_t* C, int32_t width, int32_t height, int32_t halfX, int32_t halfY,
+                                  int32_t P1, int32_t P2, const fsgm_sgm2d_params* prm, const double* preMv, int32_t mvWidth,
+                                  int32_t mvHeight, const uint8_t* guide, uint32_t* bestD, uint32_t* minC, double* mvSub,
+                                  double* flow, uint32_t* S);
+/* the aggregation that the calling thread's last fsgm_sgm2d_batch_host / fsgm_sgm2d_device ran, "" before the first: "rows"
+ * (row-packed, windows up to 11x11), "rows/wide" (its one-line-a-wave mapping: up to 2 landscape frames), "generic"
+ * (pyd_agg_kernel without wrapping) or "generic/wrap" */
+const char* fsgm_sgm2d_last_kernel(void);
+/* The static LDS (bytes per workgroup) of the kernel that brings volumes of this layout into a plan, answered without a
+ * device: 0 for FSGM_COST2D_LAYOUT_HWD (a copy or a repack in registers), one padded tile for the channel-major layouts
+ * whatever the window; the same refusals as fsgm_pyd_plan_create's window checks. */
+fsgm_status fsgm_sgm2d_ingest_lds(int32_t layout, int32_t halfX, int32_t halfY, uint64_t* bytes);
+
 /* ------------------------------------------------------------------------------------------
  * pyramidal_sgm  (pyramidal_sgm.m:1-77 -- the MATLAB driver around calc_pyd_cost_sgm)
  *
@@ -906,7 +954,7 @@ void fsgm_shard_frames(int32_t n_frames, int32_t n_devices, int32_t slot, int32_
  * hand-off poll of the aggregation gave up (what fsgm_epi_plan_sync reports on the host paths).
  * A stream that is being captured into a graph is refused with FSGM_ERR_UNSUPPORTED before anything is queued.
  * The debug taps (out->C / out->S, per-level pyramid flows) are not offered: a non-NULL C or S is FSGM_ERR_UNSUPPORTED
- * (fsgm_sgm_device alone offers S).
+ * (fsgm_sgm_device and fsgm_sgm2d_device alone offer S).
  * Results are bit for bit those of the host entry points for the same inputs.
  * ------------------------------------------------------------------------------------------ */
 /* All `batch` frames of a plan (n_frames must equal the plan's batch), cost stage + aggregation + WTA in the plan's
@@ -955,6 +1003,22 @@ fsgm_status fsgm_sgm_device(int32_t n_frames, const uint8_t* C, int32_t width, i
  * device memory into the plan's cost volumes (what fsgm_epi_plan_upload_cost fills from the host), saturated at cost_bound,
  * which becomes the bound the plan selects its kernels by.  status: 0 or FSGM_ERR_INVALID (a byte above cost_bound). */
 fsgm_status fsgm_epi_plan_ingest_cost_device(fsgm_epi_plan* plan, int32_t n_frames, const uint8_t* C, int32_t layout,
+                                             int32_t cost_bound, void* stream, int32_t* status);
+/* fsgm_sgm2d_batch_host on device pointers (one cached aggregation-only plan of batch n_frames per shape, window, hint-map
+ * size and adaptive_p2, shared with the host form).  C in any of the three layouts is brought into the
+ * plan's padded volume by one kernel pass that stores min(byte, prm->cost_bound) and writes the padding as 0; then the
+ * aggregation selected for cost_bound and the WTA run on it.  preMv (may be NULL: zero hints), guide (adaptive_p2), bestD,
+ * minC, mvSub, flow (may be NULL) and S (may be NULL) are read and written where they lie.  status: 0, or FSGM_ERR_INVALID
+ * when some byte of C was above cost_bound: the outputs are then those of the saturated volume.  Everything else follows the
+ * contract above. */
+fsgm_status fsgm_sgm2d_device(int32_t n_frames, const uint8_t* C, int32_t width, int32_t height, int32_t halfX, int32_t halfY,
+                              int32_t P1, int32_t P2, const fsgm_sgm2d_params* prm, const double* preMv, int32_t mvWidth,
+                              int32_t mvHeight, const uint8_t* guide, uint32_t* bestD, uint32_t* minC, double* mvSub, double* flow,
+                              uint32_t* S, void* stream, int32_t* status);
+/* The first step of fsgm_sgm2d_device on its own, into a caller's plan: n_frames (= the plan's batch) volumes in a
+ * FSGM_COST2D_LAYOUT_* from device memory into the plan's cost volumes (what fsgm_pyd_plan_upload_cost fills from the host),
+ * saturated at cost_bound, which becomes the bound the plan selects its aggregation by.  status: 0 or FSGM_ERR_INVALID. */
+fsgm_status fsgm_pyd_plan_ingest_cost_device(fsgm_pyd_plan* plan, int32_t n_frames, const uint8_t* C, int32_t layout,
                                              int32_t cost_bound, void* stream, int32_t* status);
 /* epipolar_sgm_of on n_frames image pairs, one plan of batch n_frames: g (HOST memory) holds n_frames geometries, each
  * passed to the maps kernel by value.  I0 / I1 u8 [n][channels][H][W]; flow f64 [n][3][H][W]; minC (may be NULL) u32 [n][H][W]. */
