@@ -10,6 +10,7 @@ hint maps are never smaller than the image; calc_pyd_cost_sgm_ng clamps (:392-39
 import numpy as np
 
 from fsgm_amd import synth
+from tests import budget_volumes
 from tests import edge_inputs as E
 from tests import fuzz_configs
 
@@ -104,6 +105,9 @@ def epi_cases():
     # wrapping penalties up to 255, degenerate shapes, other vMax
     c += [_epi(19, 13, 16, "general", P1, P2, 3, 4) for P1, P2 in ((255, 255), (255, 0), (0, 255), (0, 0), (128, 127))]
     c += [_epi(W, H, 20, "radial", 6, 64, 3, 4, vMax=0.25) for W, H in ((1, 14), (14, 1), (2, 2), (31, 17))]
+    # the 4-path penalty sets of tests/test_gpu_fused_budgets.py (P1 + P2 = 127, P1 = 0, P1 = P2, ...): the oracle's 4-path row at
+    # them, on the costs the MEX computes from the images itself
+    c += [_epi(23, 11, D, "general", P1, P2, 6, 7) for P1, P2 in budget_volumes.PAIR_PENALTIES for D in (16, 128)]
     return _dedupe(c)
 
 

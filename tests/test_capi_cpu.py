@@ -121,6 +121,35 @@ def test_auto_mode_table():
     assert auto_pipeline(0, 375, 128, 1, 8, 6, 64) == ""
 
 
+def test_auto_mode_at_the_fused_pipelines_byte_budgets():
+    """fsgm_epi_auto_pipeline at the edges of the fused pipelines' eligibility (choose_pipeline): the sweeps sum three y + P1 into
+    a byte (3 * (P1 + P2) <= 255), a pair two (2 * (P1 + P2) <= 255); both need cm + P2 + max(P1, P2) <= 255 and P1 <= P2.  One
+    unit outside any of them: the line kernels.  KITTI shape, 40 frames (auto mode takes a fused pipeline there at either path
+    count: test_auto_mode_table)."""
+    from fsgm_amd import auto_pipeline
+    sweeps = ("sweep16/nowrap", "sweep16par/nowrap", "sweep16mid/nowrap")
+
+    def at(paths, P1, P2, cmax):
+        return auto_pipeline(1242, 375, 128, 40, paths, P1, P2, cmax=cmax)
+
+    assert at(8, 6, 64, 24) in sweeps and at(4, 6, 64, 24) == "pairs16/nowrap"
+    assert at(8, 21, 64, 127) in sweeps                        # 3 * 85 = 255, 127 + 64 + 64 = 255
+    assert at(8, 22, 64, 127) == "packed16/nowrap"             # 3 * 86 = 258
+    assert at(4, 63, 64, 127) == "pairs16/nowrap"              # 2 * 127 = 254
+    assert at(4, 64, 64, 127) == "packed16/nowrap"             # 2 * 128 = 256
+    for paths in (8, 4):
+        assert at(paths, 21, 64, 128) == "packed16/wrap"       # one above the no-wrap budget
+        assert at(paths, 10, 9, 24) == "packed16/nowrap"       # P1 > P2
+    # every set tests/test_gpu_fused_budgets.py runs on the fused kernels is eligible at its largest cost, and not one above
+    from tests import budget_volumes as BV
+    for paths, sets in ((8, BV.SWEEP_PENALTIES), (4, BV.PAIR_PENALTIES)):
+        for P1, P2 in sets:
+            cmax = BV.nowrap_cmax(P1, P2)
+            assert at(paths, P1, P2, cmax) in (sweeps if paths == 8 else ("pairs16/nowrap",)), (paths, P1, P2)
+            if cmax < 255:
+                assert at(paths, P1, P2, cmax + 1) == "packed16/wrap", (paths, P1, P2)
+
+
 def test_round_half_away_as_one_addition_of_pred_half():
     """epi_cost.hip / fsgm_device.h round_clamp_small: max(trunc(v + pred(0.5)), 0) == max(C round(v), 0) for |v| < 2^30,
     checked on both sides of every half integer and integer (the doubles next to them), across magnitudes, and at random."""

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 from fsgm_amd import synth
+from tests import budget_volumes as BV
 from tests import py_restatement as R
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
@@ -73,6 +74,26 @@ def test_aggregate_vs_second_restatement(oracle, P1, P2, cmax, paths):
     got = oracle.epi_aggregate(Cv, P1, P2, paths)
     assert got[-1] == 0
     np.testing.assert_array_equal(got[:-1].reshape(H, W, D), R.sgm_raster(Cv, P1, P2, paths == 8))
+
+
+@pytest.mark.parametrize("paths,P1,P2", [(8, P1, P2) for P1, P2 in BV.SWEEP_PENALTIES] + [(4, P1, P2) for P1, P2 in BV.PAIR_PENALTIES])
+def test_aggregate_vs_second_restatement_at_the_fused_budgets(oracle, paths, P1, P2):
+    """The rows the fused kernels are compared with in tests/test_gpu_fused_budgets.py -- 8 paths, costs far above the census
+    cost's 24 -- have no counterpart in the reference's compiled code: the penalty sets on the byte budgets, each at the largest
+    cost the no-wrap condition admits, on all five volume kinds."""
+    W, H, D = 9, 7, 16
+    cmax = BV.nowrap_cmax(P1, P2)
+    top = 0
+    for i, kind in enumerate(BV.KINDS):
+        Cv = BV.volume(kind, W, H, D, cmax, seed=P1 + paths + i)
+        assert int(Cv.max()) == (0 if kind == "zeros" else cmax)
+        got = oracle.epi_aggregate(Cv, P1, P2, paths)
+        assert got[-1] == 0
+        np.testing.assert_array_equal(got[:-1].reshape(H, W, D), R.sgm_raster(Cv, P1, P2, paths == 8), err_msg=kind)
+        top = max(top, int(got.max()))
+    assert top <= paths * (cmax + P2)                            # no wrap: C <= L <= C + P2 on every path
+    if (P1, P2) == (0, 0):
+        assert top == paths * 255                                # 2040 at 8 paths: the documented limit of the kernels' WTA keys
 
 
 def test_wta_and_vz_vs_second_restatement(oracle):

@@ -69,7 +69,8 @@ def test_calc_cost_sgm_oracle_equals_reference(oracle, build):
     sub-pixel, so this pins the oracle's paths=4, subpixel=1, vz_to_disp=1 row only: its 8-path aggregation and its subpixel=0 /
     vz_to_disp=0 rows have no reference counterpart and stay unpinned.  Path counts, batch sizes and synthetic
     cost volumes of the GPU parametrisations do not map onto MEX arguments; their shapes, disparity ranges and penalties do.
-    195 cases: 134 from test_gpu_epi.py's parametrisations and the edge values; 20, every frame of the ten seeds of
+    207 cases: 146 from test_gpu_epi.py's parametrisations, the edge values and the 4-path penalty sets of
+    tests/test_gpu_fused_budgets.py (P1 + P2 = 127, P1 = 0, P1 = P2, ... at D = 16 and 128); 20, every frame of the ten seeds of
     test_gpu_edge_sweeps.py::test_epipolar_random_geometries (tests/edge_inputs.py: epipoles inside, outside, far away and on a
     pixel -- NaN directions, zero offsets --, H = I, both direction flags, 1xN and 63/64/65 shapes, flat and saturated images);
     40 from the two random sweeps' draws (24 + 16 seeds); and the KITTI shape with D = 64 at its full width of 1242 and 64 of
