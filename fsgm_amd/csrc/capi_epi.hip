@@ -322,6 +322,10 @@ fsgm_epi_params fsgm_epi_params_default(void) {
 void fsgm_epi_plan_destroy(fsgm_epi_plan* p) {
     if (!p) return;
     (void)hipSetDevice(p->prm.device);
+    // An evicted plan may still have device-form work queued (PlanCache::insert): drain it before anything is freed, not by
+    // way of what hipFree happens to wait for.
+    for (hipStream_t st : {p->stream, p->stream_h, p->stream_b})
+        if (st) (void)hipStreamSynchronize(st);
     void* bufs[] = {p->dI1, p->dI2, p->dCen1, p->dCen2, p->dPd0, p->dNd, p->dOff, p->dVz,
                     p->dCraw, p->dC, p->dL, p->dBestD, p->dMinC, p->dS, p->dD2enc, p->dD2, p->dConf, p->dLh, p->dX, p->dXup, p->dXupAll, p->dStateUp, p->dLx, p->dState, p->dCkpt, p->dCkptV, p->dRec, p->dS0, p->dRflow, p->dFlow, p->dRgb, p->dBits, p->dBandEdge, p->dBandTicket, p->dBandErr,
                     p->dD1, p->dFlow2, p->dIngest, p->dIngestFlag};

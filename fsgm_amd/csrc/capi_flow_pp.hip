@@ -27,6 +27,8 @@ struct fsgm_flow_pp_plan {
 static void flow_plan_destroy(fsgm_flow_pp_plan* p) {
     if (!p) return;
     (void)hipSetDevice(p->device);
+    if (p->stream) (void)hipStreamSynchronize(p->stream);       // queued device-form work of an evicted plan (fsgm_epi_plan_destroy)
+    if (p->busy) (void)hipEventSynchronize(p->busy);             // the pipeline forms use the scratch on their pyramid plan's stream
     void* bufs[] = {p->dS, p->dC, p->dPP, p->dParent, p->dSize, p->dLeft};
     for (void* b : bufs)
         if (b) (void)hipFree(b);

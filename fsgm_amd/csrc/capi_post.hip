@@ -63,6 +63,7 @@ extern "C" {
 void fsgm_post_plan_destroy(fsgm_post_plan* p) {
     if (!p) return;
     (void)hipSetDevice(p->device);
+    if (p->stream) (void)hipStreamSynchronize(p->stream);       // queued device-form work of an evicted plan (fsgm_epi_plan_destroy)
     void* bufs[] = {p->dIn, p->dA, p->dB, p->dD2, p->dOut, p->dDisp, p->dPd0, p->dNd, p->dO,
                     p->dParent, p->dSize, p->dScan, p->dLabels, p->dLeft, p->dNeg};
     for (void* b : bufs)

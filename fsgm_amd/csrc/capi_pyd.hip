@@ -48,6 +48,7 @@ fsgm_status fsgm_pyd_launch_lds(int32_t rX, int32_t rY, int32_t rAgg, int32_t* c
 void fsgm_pyd_plan_destroy(fsgm_pyd_plan* p) {
     if (!p) return;
     (void)hipSetDevice(p->device);
+    if (p->stream) (void)hipStreamSynchronize(p->stream);       // queued device-form work of an evicted plan (fsgm_epi_plan_destroy)
     void* bufs[] = {p->dI1, p->dI2, p->dC, p->dL, p->dCen1, p->dCen2, p->dBestD, p->dMinC, p->dS, p->dDesc, p->dMv, p->dMvSub,
                     p->dIngest, p->dIngestFlag, p->dFlow};
     for (void* b : bufs)

@@ -36,6 +36,7 @@ struct fsgm_stereo_pp_plan {
 static void stereo_pp_plan_destroy(fsgm_stereo_pp_plan* p) {
     if (!p) return;
     (void)hipSetDevice(p->device);
+    if (p->stream) (void)hipStreamSynchronize(p->stream);       // queued device-form work of an evicted plan (fsgm_epi_plan_destroy)
     void* bufs[] = {p->dW, p->dDisp, p->dMinC, p->dNeg, p->dStatus, p->dI1, p->dI2, p->dPP, p->dChecked, p->dDisp2};
     for (void* b : bufs)
         if (b) (void)hipFree(b);

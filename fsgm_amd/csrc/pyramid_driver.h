@@ -39,6 +39,7 @@ void pyramid_destroy(P* p) {
     if (!p) return;
     PyramidCore& c = p->core;
     (void)hipSetDevice(p->prm.device);
+    if (c.stream) (void)hipStreamSynchronize(c.stream);         // queued device-form work of an evicted plan (fsgm_epi_plan_destroy)
     p->destroy_levels();
     for (auto* v : {&c.dP0, &c.dP1})
         for (uint8_t* b : *v) if (b) (void)hipFree(b);
