@@ -127,6 +127,15 @@ def load():
     lib.fsgm_epi_auto_pipeline.restype = C.c_char_p
     lib.fsgm_measure_copy_bandwidth.argtypes = [i32, C.c_size_t, i32, C.POINTER(C.c_double)]
     lib.fsgm_measure_copy_bandwidth2.argtypes = [i32, C.c_size_t, i32, i32, C.POINTER(C.c_double)]
+    if hasattr(lib, "fsgm_epi_plan_set_runner_up"):              # (an older build behind FSGM_LIB_PATH has none of these)
+        lib.fsgm_epi_plan_set_runner_up.argtypes = [vp, i32]
+        lib.fsgm_epi_plan_download_runner_up.argtypes = [vp, i32, vp]
+        lib.fsgm_stereo_sgm_last_kernel.restype = C.c_char_p
+        lib.fsgm_stereo_sgm_host_ru.argtypes = [i32, vp, vp, i32, i32, i32, i32, i32, C.POINTER(StereoParams), opt, i32, vp, vp, vp, vp, vp]
+        lib.fsgm_stereo_sgm_device_ru.argtypes = [i32, vp, vp, i32, i32, i32, i32, i32, C.POINTER(StereoParams), opt, i32, vp, vp, vp, vp, vp,
+                                                  vp, vp]
+        lib.fsgm_uniqueness_filter_host.argtypes = [i32, vp, vp, vp, i32, i32, i32, vp, i32]
+        lib.fsgm_uniqueness_filter_device.argtypes = [i32, vp, vp, vp, i32, i32, i32, vp, i32, vp, vp]
     _lib = lib
     return lib
 

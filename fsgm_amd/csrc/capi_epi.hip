@@ -103,6 +103,8 @@ struct fsgm_epi_plan {
     bool vz_valid = false;
     int adaptive = 0;                    // adaptive P2 (calc_cost_sgm.cpp:68-72): line kernels at every batch size, the aggregation reads dI1
     std::vector<char> have_img;          // per frame: its image pair has been put into dI1 / dI2 (what an adaptive aggregation reads)
+    int runner_up = 0;                   // the WTA also writes the runner-up cost (fsgm_epi_plan_set_runner_up): line kernels at every batch size
+    uint32_t* dMinC2 = nullptr;          // [batch][NP], created when the switch first goes on
     int agg_mode = 0;                    // 0 auto, 1 per-direction line kernels, 2 fused sweeps (if eligible), 3 parallel sweeps, 4 / 5 band sweeps, 6 sweeps meeting in the middle
     int cus = 256;                       // compute units of the device (band sweeps: one workgroup per frame, two per CU)
     Pipeline pipe = PIPE_GENERIC;
@@ -169,13 +171,14 @@ static int pairs_min_batch(int W, int H, int D) { return switch_batch("FSGM_EPI_
 
 // What runs for a plan of this shape, batch and parameter set (cm: the largest cost in the volumes): a function of its
 // arguments and the FSGM_EPI_* environment only, so that fsgm_epi_auto_pipeline can answer without a plan.
+// adaptive: the plan's adaptive-P2 or runner-up switch is on -- either keeps it on the line kernels.
 static Pipeline choose_pipeline(int W, int H, int D, int batch, int paths, int P1, int P2, int cm, int agg_mode, int cus,
                                 int adaptive = 0) {
     if (!agg_line_split(D)) return PIPE_GENERIC;
     // (adaptive P2 lowers P2 per step, never raises it: the no-wrap test with the full P2 covers every step)
     const bool nowrap = P1 >= 0 && P2 >= 0 && cm + P2 + std::max(P1, P2) <= 255;
     Pipeline c = nowrap ? PIPE_PACKED_NOWRAP : PIPE_PACKED_WRAP;
-    if (adaptive) return c;                                      // the fused pipelines have no per-step P2: line kernels at every batch size
+    if (adaptive) return c;                                      // the fused pipelines have no per-step P2 (and their WTA tails no second minimum): line kernels at every batch size
     // 48 .. 224 (12, 20 or 28 costs a lane): the fused pipelines' register layout is 16 costs a lane -- line kernels at every
     // batch size and under every forced mode, as for a dMax the generic kernels take
     if (agg_packed_lpp(D) == 0) return c;
@@ -217,7 +220,7 @@ static Pipeline choose_pipeline(int W, int H, int D, int batch, int paths, int P
 // switches (A/B) are read here, once per process.
 static void select_kernel(fsgm_epi_plan* p) {
     const int cm = *std::max_element(p->cmax.begin(), p->cmax.end());
-    const Pipeline k = choose_pipeline(p->W, p->H, p->D, p->batch, p->prm.paths, p->P1, p->P2, cm, p->agg_mode, p->cus, p->adaptive);
+    const Pipeline k = choose_pipeline(p->W, p->H, p->D, p->batch, p->prm.paths, p->P1, p->P2, cm, p->agg_mode, p->cus, p->adaptive || p->runner_up);
     const int B = p->batch;
     const bool fine_ok = pair_x_fine_ok(p->D) != 0;
     PipelineForm f;
@@ -328,7 +331,7 @@ void fsgm_epi_plan_destroy(fsgm_epi_plan* p) {
         if (st) (void)hipStreamSynchronize(st);
     void* bufs[] = {p->dI1, p->dI2, p->dCen1, p->dCen2, p->dPd0, p->dNd, p->dOff, p->dVz,
                     p->dCraw, p->dC, p->dL, p->dBestD, p->dMinC, p->dS, p->dD2enc, p->dD2, p->dConf, p->dLh, p->dX, p->dXup, p->dXupAll, p->dStateUp, p->dLx, p->dState, p->dCkpt, p->dCkptV, p->dRec, p->dS0, p->dRflow, p->dFlow, p->dRgb, p->dBits, p->dBandEdge, p->dBandTicket, p->dBandErr,
-                    p->dD1, p->dFlow2, p->dIngest, p->dIngestFlag};
+                    p->dD1, p->dFlow2, p->dIngest, p->dIngestFlag, p->dMinC2};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     fsgm_post_plan_destroy(p->post);
@@ -751,6 +754,7 @@ static WtaArgs wta_args(const fsgm_epi_plan* p, int f0, int vz_to_disp) {
     a.off = frame_at(p->dOff, o); a.bestD = p->dBestD + o; a.minC = p->dMinC + o; a.vMax = p->vMax;
     a.W = p->W; a.H = p->H; a.D = p->D; a.ndirs = p->prm.paths;
     a.subpixel = p->prm.subpixel; a.vz_to_disp = vz_to_disp;
+    a.minC2 = p->runner_up ? p->dMinC2 + o : nullptr;            // (on: the plan is on the line kernels, select_kernel)
     return a;
 }
 
@@ -980,6 +984,8 @@ fsgm_status fsgm_epi_plan_set_agg_mode(fsgm_epi_plan* p, int32_t mode) {
     FSGM_REQUIRE(mode >= 0 && mode <= 6, "agg mode must be 0 (auto), 1 (per-direction kernels), 2 (fused sweeps), 3 (parallel sweeps), 4 (band sweeps), 5 (chained band sweeps) or 6 (sweeps meeting in the middle)");
     if (p->adaptive && mode >= 2)
         return fail(FSGM_ERR_UNSUPPORTED, "agg mode %d on an adaptive-P2 plan: only the line kernels (modes 0 and 1) take a per-step P2", mode);
+    if (p->runner_up && mode >= 2)
+        return fail(FSGM_ERR_UNSUPPORTED, "agg mode %d on a runner-up plan: only the line kernels' WTA (modes 0 and 1) writes the runner-up cost", mode);
     p->agg_mode = mode;
     select_kernel(p);
     return FSGM_OK;
@@ -992,6 +998,26 @@ fsgm_status fsgm_epi_plan_set_adaptive_p2(fsgm_epi_plan* p, int32_t on) {
         return fail(FSGM_ERR_UNSUPPORTED, "adaptive P2 on a plan forced to agg mode %d: only the line kernels (modes 0 and 1) take a per-step P2",
                     p->agg_mode);
     p->adaptive = on;
+    select_kernel(p);
+    return FSGM_OK;
+}
+
+fsgm_status fsgm_epi_plan_set_runner_up(fsgm_epi_plan* p, int32_t on) {
+    FSGM_REQUIRE(p, "null plan");
+    FSGM_REQUIRE(on == 0 || on == 1, "fsgm_epi_plan_set_runner_up: on must be 0 or 1 (got %d)", on);
+    if (on && p->agg_mode >= 2)
+        return fail(FSGM_ERR_UNSUPPORTED, "runner-up cost on a plan forced to agg mode %d: only the line kernels' WTA (modes 0 and 1) writes it",
+                    p->agg_mode);
+    if (on && !p->dMinC2) {                                      // all ones until a WTA has run: FSGM_NO_RUNNER_UP
+        const size_t bytes = (size_t)p->batch * p->NP * 4;
+        uint32_t* m = nullptr;
+        FSGM_HIP(hipSetDevice(p->prm.device));
+        FSGM_HIP(hipMalloc((void**)&m, bytes));
+        const hipError_t e = hipMemsetAsync(m, 0xFF, bytes, p->stream);
+        if (e != hipSuccess) { (void)hipFree(m); return hip_status(e, "fsgm_epi_plan_set_runner_up"); }
+        p->dMinC2 = m;
+    }
+    p->runner_up = on;
     select_kernel(p);
     return FSGM_OK;
 }
@@ -1038,6 +1064,15 @@ fsgm_status fsgm_epi_plan_download_fb(fsgm_epi_plan* p, int32_t f, uint8_t* conf
     FSGM_REQUIRE(p->prm.fb_check, "the plan was created without fb_check");
     if (conf) FSGM_HIP(hipMemcpy(conf, p->dConf + f * p->NP, p->NP, hipMemcpyDeviceToHost));
     if (bestD2) FSGM_HIP(hipMemcpy(bestD2, p->dD2 + f * p->NP, p->NP * 4, hipMemcpyDeviceToHost));
+    return FSGM_OK;
+}
+
+fsgm_status fsgm_epi_plan_download_runner_up(fsgm_epi_plan* p, int32_t f, uint32_t* minC2) {
+    FSGM_REQUIRE(p && minC2, "fsgm_epi_plan_download_runner_up: null argument");
+    FSGM_REQUIRE(f >= 0 && f < p->batch, "frame %d out of range (batch %d)", f, p->batch);
+    FSGM_REQUIRE(p->runner_up, "fsgm_epi_plan_download_runner_up: the plan's runner-up switch is off (fsgm_epi_plan_set_runner_up)");
+    { fsgm_status fs = frame_ready(p, f, 2); if (fs != FSGM_OK) return fs; }
+    FSGM_HIP(hipMemcpy(minC2, p->dMinC2 + f * p->NP, p->NP * 4, hipMemcpyDeviceToHost));
     return FSGM_OK;
 }
 
@@ -1162,20 +1197,22 @@ static PlanCache<fsgm_epi_plan> g_epi(4, fsgm_epi_plan_destroy);   // cached pla
 // (a plan serves one sampling mode and, rectified, one direction: the modes share no cached state)
 static fsgm_status cached_plan(std::unique_lock<std::mutex>& lk, fsgm_epi_plan** out, int W, int H, int D, int batch,
                                const fsgm_epi_params& pr, int sampling = FSGM_SAMPLING_VZ, int direction = 0, int adaptive = 0,
-                               int agg_mode = 0) {
+                               int agg_mode = 0, int runner_up = 0) {
     FSGM_DEVICE_SLOT(pr.device);
     lk = std::unique_lock<std::mutex>(g_epi.mu(pr.device));
     fsgm_epi_plan* p = g_epi.find(pr.device, [&](const fsgm_epi_plan* q) {
         return q->W == W && q->H == H && q->D == D && q->batch == batch && q->prm.paths == pr.paths &&
                q->prm.fb_check == pr.fb_check && q->prm.vz_to_disp == pr.vz_to_disp && q->sampling == sampling &&
                q->direction == direction && q->adaptive == adaptive &&   // (adaptive and non-adaptive callers never share a plan)
-               q->agg_mode == agg_mode;                                  // (nor do forced modes: only the sgm batch forms ask for one)
+               q->agg_mode == agg_mode &&                                // (nor do forced modes: only the sgm batch forms ask for one)
+               q->runner_up == runner_up;                                // (nor a runner-up caller and a plain one: the plain call keeps its pipeline)
     });
     if (p) p->prm = pr;
     else {
         fsgm_status st = fsgm_epi_plan_create_sampling(&p, W, H, D, batch, &pr, sampling, direction);
         if (st == FSGM_OK && adaptive && (st = fsgm_epi_plan_set_adaptive_p2(p, 1)) != FSGM_OK) fsgm_epi_plan_destroy(p);
         else if (st == FSGM_OK && agg_mode && (st = fsgm_epi_plan_set_agg_mode(p, agg_mode)) != FSGM_OK) fsgm_epi_plan_destroy(p);
+        else if (st == FSGM_OK && runner_up && (st = fsgm_epi_plan_set_runner_up(p, 1)) != FSGM_OK) fsgm_epi_plan_destroy(p);
         if (st != FSGM_OK) return st;
         g_epi.insert(pr.device, p);
     }
@@ -1299,6 +1336,9 @@ fsgm_stereo_params fsgm_stereo_params_default(void) {
     return p;
 }
 
+// the pipeline of this thread's last rectified-stereo one-shot call (fsgm_stereo_sgm_last_kernel), as fsgm_sgm_last_kernel's
+static thread_local const char* g_stereo_kernel = "";
+
 static fsgm_status stereo_args(const char* who, int32_t n, const uint8_t* I1, const uint8_t* I2, int32_t W, int32_t H, int32_t dMax,
                                const fsgm_stereo_params* prm, const uint32_t* disp, const uint32_t* minC, fsgm_stereo_params* sp,
                                fsgm_epi_params* pr) {
@@ -1323,7 +1363,7 @@ fsgm_status fsgm_stereo_sgm_host(int32_t n, const uint8_t* I1, const uint8_t* I2
 // int32 true disparities.
 static fsgm_status stereo_host(const char* who, int32_t n, const uint8_t* I1, const uint8_t* I2, int32_t W, int32_t H, int32_t dMax,
                                int32_t P1, int32_t P2, const fsgm_stereo_params* prm, const fsgm_epi_options* opt, int32_t d_min,
-                               bool ranged, uint32_t* disp, uint32_t* minC, uint8_t* conf, uint32_t* disp2) {
+                               bool ranged, uint32_t* disp, uint32_t* minC, uint8_t* conf, uint32_t* disp2, uint32_t* minC2 = nullptr) {
     fsgm_stereo_params sp;
     fsgm_epi_params pr;
     fsgm_epi_options o;
@@ -1333,7 +1373,7 @@ static fsgm_status stereo_host(const char* who, int32_t n, const uint8_t* I1, co
     FSGM_REQUIRE(d_min >= -FSGM_D_MIN_LIMIT && d_min <= FSGM_D_MIN_LIMIT, "%s: |d_min| must be <= %d (got %d)", who, FSGM_D_MIN_LIMIT, d_min);
     std::unique_lock<std::mutex> lk;
     fsgm_epi_plan* p = nullptr;
-    if ((st = cached_plan(lk, &p, W, H, dMax, n, pr, FSGM_SAMPLING_RECTIFIED, sp.direction, o.adaptive_p2)) != FSGM_OK) return st;
+    if ((st = cached_plan(lk, &p, W, H, dMax, n, pr, FSGM_SAMPLING_RECTIFIED, sp.direction, o.adaptive_p2, 0, minC2 != nullptr)) != FSGM_OK) return st;
     p->d_min = d_min;
     if ((st = fsgm_epi_plan_set_penalties(p, P1, P2, p->vMax)) != FSGM_OK) return st;
     if ((st = ensure_cost_buffers(p)) != FSGM_OK) return st;
@@ -1343,12 +1383,14 @@ static fsgm_status stereo_host(const char* who, int32_t n, const uint8_t* I1, co
     FSGM_HIP(hipMemcpyAsync(p->dI1, I1, np, hipMemcpyHostToDevice, p->stream));
     FSGM_HIP(hipMemcpyAsync(p->dI2, I2, np, hipMemcpyHostToDevice, p->stream));
     if ((st = enqueue(p, FSGM_STAGE_ALL)) != FSGM_OK) return st;
+    g_stereo_kernel = kPipelineName[p->pipe];
     if (ranged) {
         launch_stereo_range(p->stream, p->dBestD, pr.fb_check ? p->dD2 : nullptr, np, d_min);
         FSGM_HIP(hipGetLastError());
     }
     FSGM_HIP(hipMemcpyAsync(disp, p->dBestD, np * 4, hipMemcpyDeviceToHost, p->stream));
     FSGM_HIP(hipMemcpyAsync(minC, p->dMinC, np * 4, hipMemcpyDeviceToHost, p->stream));
+    if (minC2) FSGM_HIP(hipMemcpyAsync(minC2, p->dMinC2, np * 4, hipMemcpyDeviceToHost, p->stream));
     if (pr.fb_check && conf) FSGM_HIP(hipMemcpyAsync(conf, p->dConf, np, hipMemcpyDeviceToHost, p->stream));
     if (pr.fb_check && disp2) FSGM_HIP(hipMemcpyAsync(disp2, p->dD2, np * 4, hipMemcpyDeviceToHost, p->stream));
     FSGM_HIP(hipStreamSynchronize(p->stream));
@@ -1367,6 +1409,17 @@ fsgm_status fsgm_stereo_sgm_host_range(int32_t n, const uint8_t* I1, const uint8
                                        int32_t* disp, uint32_t* minC, uint8_t* conf, int32_t* disp2) {
     return stereo_host("fsgm_stereo_sgm_host_range", n, I1, I2, W, H, dMax, P1, P2, prm, opt, d_min, true, (uint32_t*)disp, minC, conf,
                        (uint32_t*)disp2);
+}
+
+const char* fsgm_stereo_sgm_last_kernel(void) { return g_stereo_kernel; }
+
+// the same through a cached plan with the runner-up switch on (never the plan of the call above: cached_plan's key)
+fsgm_status fsgm_stereo_sgm_host_ru(int32_t n, const uint8_t* I1, const uint8_t* I2, int32_t W, int32_t H, int32_t dMax, int32_t P1,
+                                    int32_t P2, const fsgm_stereo_params* prm, const fsgm_epi_options* opt, int32_t d_min,
+                                    int32_t* disp, uint32_t* minC, uint32_t* minC2, uint8_t* conf, int32_t* disp2) {
+    FSGM_REQUIRE(minC2, "fsgm_stereo_sgm_host_ru: null minC2");
+    return stereo_host("fsgm_stereo_sgm_host_ru", n, I1, I2, W, H, dMax, P1, P2, prm, opt, d_min, true, (uint32_t*)disp, minC, conf,
+                       (uint32_t*)disp2, minC2);
 }
 
 // sgm(C, P1, P2): sgm.m's call shape on the MEX's aggregation + WTA (MEX semantics: include/fsgm.h)
@@ -1679,7 +1732,7 @@ fsgm_status fsgm_stereo_sgm_device(int32_t n, const uint8_t* I1, const uint8_t* 
 static fsgm_status stereo_device(const char* who, int32_t n, const uint8_t* I1, const uint8_t* I2, int32_t W, int32_t H, int32_t dMax,
                                  int32_t P1, int32_t P2, const fsgm_stereo_params* prm, const fsgm_epi_options* opt, int32_t d_min,
                                  bool ranged, uint32_t* disp, uint32_t* minC, uint8_t* conf, uint32_t* disp2, void* stream,
-                                 int32_t* status) {
+                                 int32_t* status, uint32_t* minC2 = nullptr) {
     fsgm_stereo_params sp;
     fsgm_epi_params pr;
     fsgm_epi_options o;
@@ -1694,21 +1747,23 @@ static fsgm_status stereo_device(const char* who, int32_t n, const uint8_t* I1, 
                                                      {I2, np, 1, true, "I2"},
                                                      {disp, np * 4, 4, true, "disp"},
                                                      {minC, np * 4, 4, true, "minC"},
+                                                     {minC2, np * 4, 4, false, "minC2"},
                                                      {fb ? conf : nullptr, np, 1, false, "conf"},
                                                      {fb ? disp2 : nullptr, np * 4, 4, false, "disp2"},
                                                      {status, 4, 4, false, "status"}})) != FSGM_OK)
         return st;
     std::unique_lock<std::mutex> lk;
     fsgm_epi_plan* p = nullptr;
-    if ((st = cached_plan(lk, &p, W, H, dMax, n, pr, FSGM_SAMPLING_RECTIFIED, sp.direction, o.adaptive_p2)) != FSGM_OK) return st;
+    if ((st = cached_plan(lk, &p, W, H, dMax, n, pr, FSGM_SAMPLING_RECTIFIED, sp.direction, o.adaptive_p2, 0, minC2 != nullptr)) != FSGM_OK) return st;
     p->d_min = d_min;
     if ((st = epi_device_prepare(p, P1, P2, p->vMax)) != FSGM_OK) return st;
     return device_call(p->join, cs, p->stream, [&]() -> fsgm_status {
         Bind<uint8_t> i1(p->dI1, const_cast<uint8_t*>(I1)), i2(p->dI2, const_cast<uint8_t*>(I2));
-        Bind<uint32_t> bd(p->dBestD, disp), mc(p->dMinC, minC), d2(p->dD2, fb ? disp2 : nullptr);
+        Bind<uint32_t> bd(p->dBestD, disp), mc(p->dMinC, minC), d2(p->dD2, fb ? disp2 : nullptr), m2(p->dMinC2, minC2);
         Bind<uint8_t> cf(p->dConf, fb ? conf : nullptr);
         const fsgm_status es = enqueue(p, FSGM_STAGE_ALL);
         if (es != FSGM_OK) return es;
+        g_stereo_kernel = kPipelineName[p->pipe];
         if (ranged) launch_stereo_range(p->stream, disp, fb ? disp2 : nullptr, np, d_min);
         launch_device_status(p->stream, p->dBandErr, nullptr, status);
         return FSGM_OK;
@@ -1726,6 +1781,16 @@ fsgm_status fsgm_stereo_sgm_device_range(int32_t n, const uint8_t* I1, const uin
                                          int32_t* disp, uint32_t* minC, uint8_t* conf, int32_t* disp2, void* stream, int32_t* status) {
     return stereo_device("fsgm_stereo_sgm_device_range", n, I1, I2, W, H, dMax, P1, P2, prm, opt, d_min, true, (uint32_t*)disp, minC, conf,
                          (uint32_t*)disp2, stream, status);
+}
+
+// fsgm_stereo_sgm_host_ru on device pointers: minC2 is written where it lies, by the WTA itself
+fsgm_status fsgm_stereo_sgm_device_ru(int32_t n, const uint8_t* I1, const uint8_t* I2, int32_t W, int32_t H, int32_t dMax, int32_t P1,
+                                      int32_t P2, const fsgm_stereo_params* prm, const fsgm_epi_options* opt, int32_t d_min,
+                                      int32_t* disp, uint32_t* minC, uint32_t* minC2, uint8_t* conf, int32_t* disp2, void* stream,
+                                      int32_t* status) {
+    FSGM_REQUIRE(minC2, "fsgm_stereo_sgm_device_ru: null minC2");
+    return stereo_device("fsgm_stereo_sgm_device_ru", n, I1, I2, W, H, dMax, P1, P2, prm, opt, d_min, true, (uint32_t*)disp, minC, conf,
+                         (uint32_t*)disp2, stream, status, minC2);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -47,6 +47,9 @@ struct WtaArgs {
     int W, H, D;
     int ndirs;
     int subpixel, vz_to_disp;
+    // runner-up cost (line kernels' WTA only): [frames][NP] min { S[d] : |d - best| >= 2 }, 0xFFFFFFFF where no such d exists;
+    // null: not computed.  Last in the struct: every other member keeps its kernarg offset
+    uint32_t* minC2;
 };
 
 // fused-sweep aggregation (epi_sweep.hip)

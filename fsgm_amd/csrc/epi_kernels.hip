@@ -1138,7 +1138,8 @@ __device__ __forceinline__ uint32_t sum_at(const uint8_t* Lf, size_t dir_stride,
 }
 
 // packed WTA: LPP lanes per pixel, DPL d per lane (16, or 12 / 20 / 28 for D = 48 .. 224); sums kept as 2 x u16 (8 paths x 255 < 65536)
-template <int LPP, int DPL>
+// RU: also the runner-up cost a.minC2 = min { S[d] : |d - best| >= 2 } (all ones where no such d exists)
+template <int LPP, int DPL, bool RU = false>
 __device__ __forceinline__ void wta_packed_body(const WtaArgs& a) {
     constexpr int D = LPP * DPL, NK = DPL / 4;
     constexpr int PPB = 256 / LPP;                           // pixels per block
@@ -1180,6 +1181,24 @@ __device__ __forceinline__ void wta_packed_body(const WtaArgs& a) {
         key = min(key, min(min((s0 << 8) | d0, (s1 << 8) | (d0 + 1)), min((s2 << 8) | (d0 + 2), (s3 << 8) | (d0 + 3))));
     }
     key = group_min_u32<LPP>(key);
+    if constexpr (RU) {
+        // group_min_u32 is a butterfly: every lane of the pixel holds the winning key.  Each lane masks its own DPL sums, still
+        // in E[] / O[]: (d - best + 1) as u32 is 0, 1 or 2 exactly for the three d of the exclusion window, which may reach into
+        // the neighbouring lane's first or last d -- every lane tests against best itself, so nothing is exchanged.
+        const uint32_t lo = (key & 0xFF) - 1u;               // d - lo > 2  <=>  |d - best| >= 2 (wraps past 2 below the window)
+        uint32_t m2 = 0xFFFFFFFFu;
+#pragma unroll
+        for (int k = 0; k < NK; k++) {
+            const uint32_t d0 = (uint32_t)j * DPL + 4 * k;
+            const uint32_t s0 = E[k] & 0xFFFF, s1 = O[k] & 0xFFFF, s2 = E[k] >> 16, s3 = O[k] >> 16;
+            m2 = min(m2, d0 - lo > 2u ? s0 : 0xFFFFFFFFu);
+            m2 = min(m2, d0 + 1 - lo > 2u ? s1 : 0xFFFFFFFFu);
+            m2 = min(m2, d0 + 2 - lo > 2u ? s2 : 0xFFFFFFFFu);
+            m2 = min(m2, d0 + 3 - lo > 2u ? s3 : 0xFFFFFFFFu);
+        }
+        m2 = group_min_u32<LPP>(m2);
+        if (j == 0 && valid) a.minC2[f * (size_t)NP + p] = m2;
+    }
     __syncthreads();
     if (j == 0 && valid) {
         const uint32_t best = key & 0xFF, minc = key >> 8;
@@ -1198,9 +1217,15 @@ template <int LPP>
 __global__ __launch_bounds__(256) void wta_packed_kernel(WtaArgs a) { wta_packed_body<LPP, 16>(a); }
 template <int LPP, int DPL>
 __global__ __launch_bounds__(256) void wta_split_kernel(WtaArgs a) { wta_packed_body<LPP, DPL>(a); }
+// the same with the runner-up cost: kernels of their own, so that the ones above stay what they were
+template <int LPP>
+__global__ __launch_bounds__(256) void wta_packed_ru_kernel(WtaArgs a) { wta_packed_body<LPP, 16, true>(a); }
+template <int LPP, int DPL>
+__global__ __launch_bounds__(256) void wta_split_ru_kernel(WtaArgs a) { wta_packed_body<LPP, DPL, true>(a); }
 
 // generic WTA: one wave per pixel, lanes stride over d
-__global__ __launch_bounds__(256) void wta_generic_kernel(WtaArgs a) {
+template <bool RU>
+__device__ __forceinline__ void wta_generic_body(const WtaArgs& a) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int NP = a.W * a.H, D = a.D;
     const int p = blockIdx.x * 4 + wave;
@@ -1214,6 +1239,15 @@ __global__ __launch_bounds__(256) void wta_generic_kernel(WtaArgs a) {
     }
 #pragma unroll
     for (int s = 32; s >= 1; s >>= 1) key = min(key, (uint32_t)__shfl_xor((int)key, s));
+    if constexpr (RU) {                                      // second strided pass, the window around best (known to every lane) masked
+        const int best = (int)(key & 0xFFF);
+        uint32_t m2 = 0xFFFFFFFFu;
+        for (int d = lane; d < D; d += 64)
+            if (d < best - 1 || d > best + 1) m2 = min(m2, sum_at(Lf, a.l_dir_stride, a.ndirs, (size_t)p * D + d));
+#pragma unroll
+        for (int s = 32; s >= 1; s >>= 1) m2 = min(m2, (uint32_t)__shfl_xor((int)m2, s));
+        if (lane == 0) a.minC2[f * (size_t)NP + p] = m2;
+    }
     if (lane == 0) {
         const uint32_t best = key & 0xFFF, minc = key >> 12;
         uint32_t c_1 = 0, c1 = 0;
@@ -1224,6 +1258,8 @@ __global__ __launch_bounds__(256) void wta_generic_kernel(WtaArgs a) {
         wta_finish(a, f, p, best, minc, c_1, c1);
     }
 }
+__global__ __launch_bounds__(256) void wta_generic_kernel(WtaArgs a) { wta_generic_body<false>(a); }
+__global__ __launch_bounds__(256) void wta_generic_ru_kernel(WtaArgs a) { wta_generic_body<true>(a); }
 
 // =============================================================================================
 // forward-backward consistency check  (calc_cost_sgm.cpp:429-480 calc_disp_from_first, :482-536
@@ -1513,6 +1549,25 @@ void launch_wta(hipStream_t st, const WtaArgs& a, int frames, bool packed) {
         int lpp = 0, dpl = 0;
         if (!agg_line_split(a.D, &lpp, &dpl)) return;            // (the callers ask the same predicate)
         dim3 grid((NP + 256 / lpp - 1) / (256 / lpp), frames);
+        if (a.minC2) {                                           // the same grids, the kernels that also write the runner-up cost
+            switch (a.D) {
+                case 48: hipLaunchKernelGGL((wta_split_ru_kernel<4, 12>), grid, dim3(256), 0, st, a); return;
+                case 96: hipLaunchKernelGGL((wta_split_ru_kernel<8, 12>), grid, dim3(256), 0, st, a); return;
+                case 192: hipLaunchKernelGGL((wta_split_ru_kernel<16, 12>), grid, dim3(256), 0, st, a); return;
+                case 80: hipLaunchKernelGGL((wta_split_ru_kernel<4, 20>), grid, dim3(256), 0, st, a); return;
+                case 160: hipLaunchKernelGGL((wta_split_ru_kernel<8, 20>), grid, dim3(256), 0, st, a); return;
+                case 112: hipLaunchKernelGGL((wta_split_ru_kernel<4, 28>), grid, dim3(256), 0, st, a); return;
+                case 224: hipLaunchKernelGGL((wta_split_ru_kernel<8, 28>), grid, dim3(256), 0, st, a); return;
+            }
+            switch (lpp) {
+                case 1: hipLaunchKernelGGL(wta_packed_ru_kernel<1>, grid, dim3(256), 0, st, a); break;
+                case 2: hipLaunchKernelGGL(wta_packed_ru_kernel<2>, grid, dim3(256), 0, st, a); break;
+                case 4: hipLaunchKernelGGL(wta_packed_ru_kernel<4>, grid, dim3(256), 0, st, a); break;
+                case 8: hipLaunchKernelGGL(wta_packed_ru_kernel<8>, grid, dim3(256), 0, st, a); break;
+                case 16: hipLaunchKernelGGL(wta_packed_ru_kernel<16>, grid, dim3(256), 0, st, a); break;
+            }
+            return;
+        }
         switch (a.D) {
             case 48: hipLaunchKernelGGL((wta_split_kernel<4, 12>), grid, dim3(256), 0, st, a); return;
             case 96: hipLaunchKernelGGL((wta_split_kernel<8, 12>), grid, dim3(256), 0, st, a); return;
@@ -1531,7 +1586,8 @@ void launch_wta(hipStream_t st, const WtaArgs& a, int frames, bool packed) {
         }
     } else {
         dim3 grid((NP + 3) / 4, frames);
-        hipLaunchKernelGGL(wta_generic_kernel, grid, dim3(256), 0, st, a);
+        if (a.minC2) hipLaunchKernelGGL(wta_generic_ru_kernel, grid, dim3(256), 0, st, a);
+        else hipLaunchKernelGGL(wta_generic_kernel, grid, dim3(256), 0, st, a);
     }
 }
 

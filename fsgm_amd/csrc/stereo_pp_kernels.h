@@ -28,5 +28,9 @@ void launch_stereo_index(hipStream_t st, const int32_t* disp, double* w, size_t 
 // disp2 = -1 where D2 is -1 and d_min + D2 elsewhere
 void launch_stereo_pack(hipStream_t st, const double* filled, const double* checked, const double* D2, double* disp_pp,
                         double* disp_checked, double* disp2, size_t n_px, double d_min);
+// uniqueness test on the matcher's minC and runner-up cost minC2 (0xFFFFFFFF: no runner-up, never rejected), ratio in [0, 100]:
+// out = NaN where (u64)minC2 * (100 - ratio) < (u64)minC * 100, map elsewhere.  out may be map itself, nothing else may overlap
+void launch_stereo_uniqueness(hipStream_t st, const double* map, const uint32_t* minC, const uint32_t* minC2, double* out, size_t n_px,
+                              int ratio);
 
 }  // namespace fsgm

@@ -107,6 +107,21 @@ __global__ __launch_bounds__(256) void stereo_pack_kernel(const double* __restri
     }
 }
 
+// Uniqueness test (OpenCV's uniquenessRatio on the matcher's own sums): NaN where the runner-up cost is within `ratio` percent
+// of the winner's, the input elsewhere (NaN stays NaN).  Products in 64 bits: minC2 may be anything below 2^32.  map and out
+// may be the same array (no __restrict__ on them): every element is read before it is written, by the same lane.
+__global__ __launch_bounds__(256) void stereo_uniqueness_kernel(const double* map, const uint32_t* __restrict__ minC,
+                                                                const uint32_t* __restrict__ minC2, double* out, size_t n_px,
+                                                                uint32_t keep) {
+    const size_t stride = (size_t)gridDim.x * 256;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n_px; i += stride) {
+        const uint32_t c = minC[i], c2 = minC2[i];
+        const bool reject = c2 != 0xFFFFFFFFu && (uint64_t)c2 * keep < (uint64_t)c * 100u;
+        const double v = map[i];
+        out[i] = reject ? __builtin_nan("") : v;
+    }
+}
+
 // launchers: the frame index of a grid stays within 65535, more frames (tiny maps only) take one launch per 65535
 constexpr int STEREO_MAX_GRID_FRAMES = 65535;
 
@@ -132,6 +147,13 @@ void launch_stereo_pack(hipStream_t st, const double* filled, const double* chec
                         double* disp_checked, double* disp2, size_t n_px, double d_min) {
     hipLaunchKernelGGL(stereo_pack_kernel, dim3((unsigned)((n_px + 255) / 256)), dim3(256), 0, st, filled, checked, D2, disp_pp,
                        disp_checked, disp2, n_px, d_min);
+}
+
+void launch_stereo_uniqueness(hipStream_t st, const double* map, const uint32_t* minC, const uint32_t* minC2, double* out, size_t n_px,
+                              int ratio) {
+    const size_t blocks = (n_px + 255) / 256;                    // grid-stride: at most 8 blocks for each of 256 CUs
+    hipLaunchKernelGGL(stereo_uniqueness_kernel, dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(256), 0, st, map, minC, minC2, out,
+                       n_px, (uint32_t)(100 - ratio));
 }
 
 }  // namespace fsgm

@@ -184,7 +184,8 @@ def _d_min(d_min):
     return int(d_min)
 
 
-def stereo_sgm(left, right, dMax, P1=6, P2=64, *, paths=4, subpixel=1, direction=-1, fb_check=0, device=0, adaptive_p2=0, d_min=None):
+def stereo_sgm(left, right, dMax, P1=6, P2=64, *, paths=4, subpixel=1, direction=-1, fb_check=0, device=0, adaptive_p2=0, d_min=None,
+               runner_up=False):
     """disp, minC = stereo_sgm(left, right, dMax): semi-global matching of a rectified pair.  left, right (height, width) uint8
     or a batch (N, height, width); disp uint32 = disparity * 256 (whole disparities with subpixel=0), minC uint32, of the
     images' shape.  direction=-1: `left` is the left view and its match in `right` lies at x - d; +1: at x + d.  fb_check=1
@@ -194,7 +195,10 @@ def stereo_sgm(left, right, dMax, P1=6, P2=64, *, paths=4, subpixel=1, direction
     d_min: an integer (|d_min| <= 1024, may be negative) starts the search range there -- the dMax candidates are the disparities
     d_min .. d_min + dMax - 1, sampled at clamp(x + direction * d) -- and disp / disp2 come back as int32 TRUE disparities * 256
     (disp2: INT32_MIN where invalid).  The dtype follows the argument, not its value: d_min=0 gives int32 arrays with the values
-    of d_min=None, which takes the path and the uint32 outputs (disp2: 512 << 8 where invalid) this function always had."""
+    of d_min=None, which takes the path and the uint32 outputs (disp2: 512 << 8 where invalid) this function always had.
+    runner_up=True appends minC2 uint32 to the tuple: the runner-up cost min { S[d] : |d - best| >= 2 } of the winner-take-all
+    (NO_RUNNER_UP where no such d exists), what uniqueness_filter() takes next to minC.  Such a call runs the line kernels at
+    every batch size; disp, minC, conf and disp2 are those of the call without it."""
     d_min = _d_min(d_min)
     left, right = np.asarray(left), np.asarray(right)
     if left.dtype != np.uint8 or right.dtype != np.uint8 or left.ndim not in (2, 3):
@@ -214,6 +218,15 @@ def stereo_sgm(left, right, dMax, P1=6, P2=64, *, paths=4, subpixel=1, direction
     disp, minC = np.zeros(left.shape, dtype), np.zeros(left.shape, np.uint32)
     conf = np.zeros(left.shape, np.uint8) if fb_check else None
     disp2 = np.zeros(left.shape, dtype) if fb_check else None
+    if runner_up:
+        ranged = disp.view(np.int32), None if disp2 is None else disp2.view(np.int32)
+        minC2 = np.zeros(left.shape, np.uint32)
+        opt = _lib.options(adaptive_p2)
+        check(lib.fsgm_stereo_sgm_host_ru(n, ptr(left), ptr(right), W, H, int(dMax), int(P1), int(P2), C.byref(prm), C.byref(opt),
+                                          d_min or 0, ptr(ranged[0]), ptr(minC), ptr(minC2), ptr(conf), ptr(ranged[1])))
+        if d_min is None and fb_check:                       # the marker of the call without d_min
+            disp2[ranged[1] == np.iinfo(np.int32).min] = 512 << 8
+        return (disp, minC, conf, disp2, minC2) if fb_check else (disp, minC, minC2)
     if d_min is not None:
         opt = _lib.options(adaptive_p2)
         check(lib.fsgm_stereo_sgm_host_range(n, ptr(left), ptr(right), W, H, int(dMax), int(P1), int(P2), C.byref(prm), C.byref(opt),
@@ -226,6 +239,37 @@ def stereo_sgm(left, right, dMax, P1=6, P2=64, *, paths=4, subpixel=1, direction
         check(lib.fsgm_stereo_sgm_host(n, ptr(left), ptr(right), W, H, int(dMax), int(P1), int(P2), C.byref(prm), ptr(disp), ptr(minC),
                                        ptr(conf), ptr(disp2)))
     return (disp, minC, conf, disp2) if fb_check else (disp, minC)
+
+
+def stereo_last_kernel():
+    """The aggregation pipeline this thread's last stereo_sgm call (numpy or torch form) ran, '' before the first."""
+    return _lib.load().fsgm_stereo_sgm_last_kernel().decode()
+
+
+NO_RUNNER_UP = 0xFFFFFFFF                                      # FSGM_NO_RUNNER_UP
+
+
+def uniqueness_filter(map, minC, minC2, ratio, *, device=0):
+    """OpenCV's uniquenessRatio on the matcher's own costs: map float64 (values or NaN), minC and minC2 uint32
+    (stereo_sgm(runner_up=True)'s, or EpiPlan.download() / download_runner_up()), all (height, width) or (N, height, width).
+    Returns map with NaN where minC2 != NO_RUNNER_UP and minC2 * (100 - ratio) < minC * 100 (64-bit products); ratio is an
+    integer in [0, 100], 0 rejects nothing."""
+    m = np.ascontiguousarray(map)
+    if m.dtype != np.float64 or m.ndim not in (2, 3):
+        raise TypeError(f"map must be a float64 array (height, width) or (N, height, width) (got {m.dtype} {m.shape})")
+    c, c2 = np.ascontiguousarray(minC), np.ascontiguousarray(minC2)
+    for name, a in (("minC", c), ("minC2", c2)):
+        if a.dtype != np.uint32 or a.shape != m.shape:
+            raise TypeError(f"{name} must be uint32 of map's shape {m.shape} (got {a.dtype} {a.shape})")
+    if isinstance(ratio, bool) or int(ratio) != ratio or not 0 <= int(ratio) <= 100:
+        raise ValueError(f"ratio must be an integer in [0, 100] (got {ratio!r})")
+    if m.size == 0:
+        raise ValueError("empty map")
+    H, W = m.shape[-2:]
+    out = np.empty_like(m)
+    check(_lib.load().fsgm_uniqueness_filter_host(1 if m.ndim == 2 else m.shape[0], ptr(m), ptr(c), ptr(c2), W, H, int(ratio), ptr(out),
+                                                  int(device)))
+    return out
 
 
 def stereo_maps(width, height, direction=-1):
@@ -283,6 +327,7 @@ class EpiPlan:
             check(self.lib.fsgm_epi_plan_create_sampling(C.byref(self._h), self.W, self.H, self.D, self.batch, C.byref(prm),
                                                          self.sampling, int(direction)))
         self.adaptive_p2 = 0
+        self.runner_up = 0
         self.d_min = 0
         if adaptive_p2:
             try:
@@ -325,6 +370,13 @@ class EpiPlan:
         I1 of every slot (upload / upload_images), also when the costs came from upload_cost."""
         check(self.lib.fsgm_epi_plan_set_adaptive_p2(self._h, int(on)))
         self.adaptive_p2 = int(on)
+
+    def set_runner_up(self, on):
+        """The WTA also writes the runner-up cost (download_runner_up) on / off.  Such a plan runs the line kernels at every batch
+        size: refused (status 4) while modes 2-6 are forced, as set_agg_mode(2..6) is on such a plan.  Off: every output and
+        every kernel selection is what it was."""
+        check(self.lib.fsgm_epi_plan_set_runner_up(self._h, int(on)))
+        self.runner_up = int(on)
 
     def set_d_min(self, d_min):
         """A rectified plan's search range starts at disparity d_min (|d_min| <= 1024; 0 at creation): candidate i is sampled at
@@ -378,6 +430,13 @@ class EpiPlan:
         bestD2 = np.empty((self.H, self.W), np.uint32)
         check(self.lib.fsgm_epi_plan_download_fb(self._h, frame, ptr(conf), ptr(bestD2)))
         return conf, bestD2
+
+    def download_runner_up(self, frame):
+        """minC2 of the last WTA run: min { S[d] : |d - best| >= 2 }, NO_RUNNER_UP where no such d exists (status 1 while the
+        switch is off)."""
+        minC2 = np.empty((self.H, self.W), np.uint32)
+        check(self.lib.fsgm_epi_plan_download_runner_up(self._h, frame, ptr(minC2)))
+        return minC2
 
     def download_cost(self, frame):
         Cv = np.empty((self.H, self.W, self.D), np.uint8)

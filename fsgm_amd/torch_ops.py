@@ -12,7 +12,8 @@ FSGM_ERR_INVALID when a cost was above the declared bound), fsgm::sgm2d (the 2-D
 fsgm::epipolar_sgm_of, fsgm::pyramidal_sgm, fsgm::pyramidal_sgm_ng, fsgm::epipolar_flow_pp, fsgm::pyramidal_flow_pp (each also returns a 0-d int32
 status tensor: 0, or FSGM_ERR_HIP when an aggregation hand-off gave up; check=True in the wrappers synchronises and raises
 on it), fsgm::epi_postprocess (status FSGM_ERR_INVALID when a D1 value is negative), fsgm::vmf and fsgm::flow_fb_check; for rectified
-stereo fsgm::stereo_sgm_pp (the matcher and the chain of test.m:45-50) and fsgm::stereo_fb_check (status as fsgm::epi_postprocess).
+stereo fsgm::stereo_sgm_pp (the matcher and the chain of test.m:45-50) and fsgm::stereo_fb_check (status as fsgm::epi_postprocess),
+fsgm::stereo_sgm_ru (fsgm::stereo_sgm_range with the runner-up cost minC2 after minC) and fsgm::uniqueness_filter (status always 0).
 
 One process must hold one HIP runtime.  torch brings its own libamdhip64; libfsgm_hip.so binds to it by soname when torch is
 imported first.  When the library was loaded first, torch afterwards maps a second runtime, and a stream or pointer of one
@@ -548,6 +549,51 @@ def _(D1, D2, fused, d_min, direction, thr):
     return _stereo_fb_check_outputs(D1, fused)
 
 
+def _stereo_sgm_ru_outputs(left, fb_check):
+    """(disp int32, minC, minC2, conf, disp2 int32, status): fsgm::stereo_sgm_range's with the runner-up cost after minC"""
+    disp, minC, conf, disp2, status = _matcher_outputs(left, fb_check, torch.int32)
+    return disp, minC, torch.empty_like(minC), conf, disp2, status
+
+
+@torch.library.custom_op("fsgm::stereo_sgm_ru", mutates_args=())
+def _stereo_sgm_ru_op(left: torch.Tensor, right: torch.Tensor, dMax: int, d_min: int, P1: int, P2: int, paths: int, subpixel: int,
+                      direction: int, fb_check: int, adaptive_p2: int = 0
+                      ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    N, H, W, dev = _frames(left)
+    left, right = _ready(left), _ready(right)
+    disp, minC, minC2, conf, disp2, status = _stereo_sgm_ru_outputs(left, fb_check)
+    prm = _stereo_params(paths, subpixel, direction, fb_check, dev.index)
+    opt = _lib.options(adaptive_p2)
+    _call(dev, _L.fsgm_stereo_sgm_device_ru, N, _p(left), _p(right), W, H, int(dMax), int(P1), int(P2), C.byref(prm), C.byref(opt),
+          int(d_min), _p(disp), _p(minC), _p(minC2), _p(conf) if fb_check else None, _p(disp2) if fb_check else None, _stream(dev),
+          _p(status))
+    return disp, minC, minC2, conf, disp2, status
+
+
+@_stereo_sgm_ru_op.register_fake
+def _(left, right, dMax, d_min, P1, P2, paths, subpixel, direction, fb_check, adaptive_p2=0):
+    return _stereo_sgm_ru_outputs(left, fb_check)
+
+
+def _uniqueness_filter_outputs(map_):
+    return torch.empty_like(map_, memory_format=torch.contiguous_format), _status(map_.device)
+
+
+@torch.library.custom_op("fsgm::uniqueness_filter", mutates_args=())
+def _uniqueness_filter_op(map_: torch.Tensor, minC: torch.Tensor, minC2: torch.Tensor, ratio: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    N, H, W, dev = _frames(map_)
+    map_, minC, minC2 = _ready(map_), _ready(minC), _ready(minC2)
+    out, status = _uniqueness_filter_outputs(map_)
+    _call(dev, _L.fsgm_uniqueness_filter_device, N, _p(map_), _p(minC), _p(minC2), W, H, int(ratio), _p(out), dev.index, _stream(dev),
+          _p(status))
+    return out, status
+
+
+@_uniqueness_filter_op.register_fake
+def _(map_, minC, minC2, ratio):
+    return _uniqueness_filter_outputs(map_)
+
+
 # ---------------------------------------------------------------------------------------------
 # wrappers: the argument order of the numpy API, one frame or a batch with a leading N
 # ---------------------------------------------------------------------------------------------
@@ -746,13 +792,15 @@ def ingest_cost2d(plan, costs, *, layout="dhw", cost_bound=255, check=False, ret
 
 
 def stereo_sgm(left, right, dMax, P1=6, P2=64, *, paths=4, subpixel=1, direction=-1, fb_check=0, check=False, return_status=False,
-               adaptive_p2=0, d_min=None):
+               adaptive_p2=0, d_min=None, runner_up=False):
     """disp, minC = stereo_sgm(left, right, dMax) as fsgm_amd.stereo_sgm, on torch tensors on the GPU: left, right (H, W) uint8
     or a batch (N, H, W); disp (disparity * 256) and minC uint32 of the same shape, plus conf uint8 / disp2 uint32 with
     fb_check=1.  The outputs stay in HBM; the work is queued on the current stream.  adaptive_p2=1: edge-aware P2 on `left`.
     d_min: an integer starts the search range at that disparity (fsgm::stereo_sgm_range) and makes disp / disp2 int32 true
     disparities * 256 (disp2 INT32_MIN where invalid); the dtype follows the argument, not its value: None (fsgm::stereo_sgm)
-    keeps the uint32 outputs, 0 gives the same values as int32."""
+    keeps the uint32 outputs, 0 gives the same values as int32.  runner_up=True (fsgm::stereo_sgm_ru) appends minC2 uint32, the
+    runner-up cost min { S[d] : |d - best| >= 2 } (0xFFFFFFFF where no such d exists), to the outputs; the call then runs the
+    line kernels at every batch size."""
     d_min = _d_min(d_min)
     _tensors({"left": (left, torch.uint8), "right": (right, torch.uint8)})
     if left.dim() not in (2, 3):
@@ -766,6 +814,16 @@ def stereo_sgm(left, right, dMax, P1=6, P2=64, *, paths=4, subpixel=1, direction
     batched = left.dim() == 3
     if not batched:
         left, right = left.unsqueeze(0), right.unsqueeze(0)
+    if runner_up:
+        disp, minC, minC2, conf, disp2, status = torch.ops.fsgm.stereo_sgm_ru(left, right, int(dMax), d_min or 0, int(P1), int(P2), int(paths),
+                                                                               int(subpixel), int(direction), int(bool(fb_check)),
+                                                                               int(adaptive_p2))
+        if d_min is None:                                    # the uint32 outputs of the call without d_min (disp2: 512 << 8 where invalid)
+            disp = disp.view(torch.uint32)
+            if fb_check:
+                disp2 = torch.where(disp2 == -2 ** 31, 512 << 8, disp2).view(torch.uint32)
+        outs = (disp, minC, conf, disp2, minC2) if fb_check else (disp, minC, minC2)
+        return _finish(outs, status, batched, check, return_status)
     if d_min is None:
         disp, minC, conf, disp2, status = torch.ops.fsgm.stereo_sgm(left, right, int(dMax), int(P1), int(P2), int(paths), int(subpixel),
                                                                      int(direction), int(bool(fb_check)), int(adaptive_p2))
@@ -799,6 +857,23 @@ def stereo_sgm_pp(left, right, dMax, P1=6, P2=64, *, paths=4, subpixel=1, direct
     *outs, status = torch.ops.fsgm.stereo_sgm_pp(left, right, int(dMax), d_min, int(P1), int(P2), int(paths), int(subpixel), int(direction),
                                                  int(adaptive_p2), [float(getattr(defaults, k)) for k in STEREO_PP_FIELDS], int(in_fill))
     return _finish(outs, status, batched, check, return_status)
+
+
+def uniqueness_filter(map, minC, minC2, ratio):
+    """fsgm_amd.uniqueness_filter on torch tensors on the GPU: map float64, minC / minC2 uint32 (stereo_sgm(runner_up=True)'s),
+    (H, W) or (N, H, W); NaN where minC2 * (100 - ratio) < minC * 100 and minC2 is a runner-up, map elsewhere.  A new tensor;
+    the work is queued on the current stream."""
+    _tensors({"map": (map, torch.float64), "minC": (minC, torch.uint32), "minC2": (minC2, torch.uint32)})
+    if map.dim() not in (2, 3):
+        raise TypeError(f"map must be (H, W) or (N, H, W) (got {tuple(map.shape)})")
+    _shape("minC", minC, map.shape)
+    _shape("minC2", minC2, map.shape)
+    if isinstance(ratio, bool) or int(ratio) != ratio or not 0 <= int(ratio) <= 100:
+        raise ValueError(f"ratio must be an integer in [0, 100] (got {ratio!r})")
+    batched = map.dim() == 3
+    a, b, c = (map, minC, minC2) if batched else (map.unsqueeze(0), minC.unsqueeze(0), minC2.unsqueeze(0))
+    out, _ = torch.ops.fsgm.uniqueness_filter(a, b, c, int(ratio))
+    return out if batched else out[0]
 
 
 def stereo_fb_check(D1, D2=None, d_min=0, direction=-1, thr=2.0, *, return_second=False, check=False, return_status=False):

@@ -180,6 +180,36 @@ fsgm_status fsgm_stereo_sgm_host_range(int32_t n_frames, const uint8_t* I1, cons
                                        const fsgm_epi_options* opt, int32_t d_min, int32_t* disp, uint32_t* minC, uint8_t* conf,
                                        int32_t* disp2);
 
+/* The runner-up cost: how unambiguous the winner-take-all's choice was.  With S[d], d in [0, dMax), the u32 sums of the path
+ * volumes (fsgm_epi_plan_download_sum), best the WTA's index -- the first strict minimum, before the parabola, the vz
+ * conversion and d_min -- and minC = S[best]:
+ *   minC2 = min { S[d] : |d - best| >= 2 },  FSGM_NO_RUNNER_UP where no such d exists (dMax <= 2; dMax = 3 with best = 1).
+ * It belongs to the first view's WTA and depends on none of subpixel, vz_to_disp, fb_check, d_min, direction.  Only the WTA of
+ * the line kernels writes it: a plan or a call that asks for it runs "packed16/nowrap", "packed16/wrap" or "generic" at every
+ * batch size (fsgm_epi_plan_set_runner_up below).
+ * fsgm_stereo_sgm_host_ru: fsgm_stereo_sgm_host_range with minC2 u32 [n][H][W] after minC; minC2 must not be NULL.  Its cached
+ * plan is never the one of a call without minC2: those keep their pipelines and their outputs. */
+#define FSGM_NO_RUNNER_UP 0xFFFFFFFFu
+/* The pipeline the calling thread's last successful fsgm_stereo_sgm_* call ran, host or device form ("" before the first), in
+ * the names of fsgm_epi_plan_kernel_name: how a caller sees that a call with minC2 ran the line kernels and one without kept
+ * its fused pipeline. */
+const char* fsgm_stereo_sgm_last_kernel(void);
+fsgm_status fsgm_stereo_sgm_host_ru(int32_t n_frames, const uint8_t* I1, const uint8_t* I2, int32_t width, int32_t height,
+                                    int32_t dMax, int32_t P1, int32_t P2, const fsgm_stereo_params* prm,
+                                    const fsgm_epi_options* opt, int32_t d_min, int32_t* disp, uint32_t* minC, uint32_t* minC2,
+                                    uint8_t* conf, int32_t* disp2);
+/* The uniqueness test (OpenCV's uniquenessRatio) on such a pair of costs: out = NaN where
+ *   minC2 != FSGM_NO_RUNNER_UP  and  (u64)minC2 * (100 - ratio) < (u64)minC * 100,
+ * map elsewhere (NaN stays NaN).  map, out f64 and minC, minC2 u32, [n][H][W] each; ratio in [0, 100], 0 rejects nothing.  A
+ * ratio outside that range, a NULL pointer or a size below 1 is FSGM_ERR_INVALID before a device is touched.  out may be map
+ * itself; it may not overlap map otherwise, nor minC or minC2 (FSGM_ERR_INVALID).  The device form follows the device-pointer
+ * contract below; its status word is always 0. */
+fsgm_status fsgm_uniqueness_filter_host(int32_t n_frames, const double* map, const uint32_t* minC, const uint32_t* minC2,
+                                        int32_t width, int32_t height, int32_t ratio, double* out, int32_t device);
+fsgm_status fsgm_uniqueness_filter_device(int32_t n_frames, const double* map, const uint32_t* minC, const uint32_t* minC2,
+                                          int32_t width, int32_t height, int32_t ratio, double* out, int32_t device, void* stream,
+                                          int32_t* status);
+
 /* ---- device-resident plan: buffers for `batch` frames stay in HBM across calls ---- */
 typedef struct fsgm_epi_plan fsgm_epi_plan;
 
@@ -232,6 +262,11 @@ fsgm_status fsgm_epi_plan_set_agg_mode(fsgm_epi_plan* plan, int32_t mode);
  * fsgm_epi_plan_upload_images, and a run with a slot whose image was never uploaded returns FSGM_ERR_INVALID before
  * anything is queued.  With 0 every output and every kernel selection is what it was before the switch existed. */
 fsgm_status fsgm_epi_plan_set_adaptive_p2(fsgm_epi_plan* plan, int32_t on);
+/* The runner-up cost (FSGM_NO_RUNNER_UP above) for this plan, 0 at creation, under the rules of the switch above: with it on
+ * the plan resolves to the line kernels whatever its batch, fsgm_epi_plan_set_agg_mode(2..6) returns FSGM_ERR_UNSUPPORTED and
+ * changes nothing, and so does switching it on after such a mode was forced.  The first 1 allocates batch * W * H * 4 bytes.  With
+ * 0 every output and every kernel selection is what it was; with 1 bestD, minC, conf and bestD2 are those of mode 1. */
+fsgm_status fsgm_epi_plan_set_runner_up(fsgm_epi_plan* plan, int32_t on);
 /* The first disparity of a FSGM_SAMPLING_RECTIFIED plan's search range (0 at creation; fsgm_stereo_sgm_host_range above): read
  * by the next cost stage and forward-backward check.  The plan's own outputs stay candidate indices * 256 (fsgm_epi_plan_download,
  * _download_fb with 512 << 8 for invalid).  Any other plan: FSGM_ERR_UNSUPPORTED; |d_min| > FSGM_D_MIN_LIMIT: FSGM_ERR_INVALID;
@@ -255,6 +290,9 @@ fsgm_status fsgm_epi_plan_sync(fsgm_epi_plan* plan);
 /* HBM -> host (synchronous) */
 fsgm_status fsgm_epi_plan_download(fsgm_epi_plan* plan, int32_t frame, uint32_t* bestD, uint32_t* minC);
 fsgm_status fsgm_epi_plan_download_fb(fsgm_epi_plan* plan, int32_t frame, uint8_t* conf, uint32_t* bestD2);
+/* minC2 u32 [H][W] of the last FSGM_STAGE_WTA run (every sampling; aggregation-only plans too); FSGM_ERR_INVALID while the
+ * plan's runner-up switch is off */
+fsgm_status fsgm_epi_plan_download_runner_up(fsgm_epi_plan* plan, int32_t frame, uint32_t* minC2);
 fsgm_status fsgm_epi_plan_download_cost(fsgm_epi_plan* plan, int32_t frame, uint8_t* C);
 fsgm_status fsgm_epi_plan_download_sum(fsgm_epi_plan* plan, int32_t frame, uint32_t* S);
 /* debug tap: the census codes of the two images as FSGM_STAGE_COST left them (common.cpp:3-27; u32 [H][W],
@@ -988,6 +1026,11 @@ fsgm_status fsgm_stereo_sgm_device_range(int32_t n_frames, const uint8_t* I1, co
                                          int32_t dMax, int32_t P1, int32_t P2, const fsgm_stereo_params* prm,
                                          const fsgm_epi_options* opt, int32_t d_min, int32_t* disp, uint32_t* minC, uint8_t* conf,
                                          int32_t* disp2, void* stream, int32_t* status);
+/* fsgm_stereo_sgm_host_ru on device pointers: minC2 (required, checked like minC) is written where it lies by the WTA kernel */
+fsgm_status fsgm_stereo_sgm_device_ru(int32_t n_frames, const uint8_t* I1, const uint8_t* I2, int32_t width, int32_t height,
+                                      int32_t dMax, int32_t P1, int32_t P2, const fsgm_stereo_params* prm,
+                                      const fsgm_epi_options* opt, int32_t d_min, int32_t* disp, uint32_t* minC, uint32_t* minC2,
+                                      uint8_t* conf, int32_t* disp2, void* stream, int32_t* status);
 /* fsgm_sgm_batch_host on device pointers (one cached plan of batch n_frames per shape, paths, agg_mode and adaptive_p2): C in
  * either layout is brought into the plan's own volume by one kernel pass that stores min(byte, prm->cost_bound), then the
  * aggregation and WTA selected for cost_bound run on it -- saturating keeps every kernel inside the no-wrap budget it was
