@@ -89,10 +89,19 @@ namespace fsgm {
 #endif
 
 // 9th bits of the eight packed-u16 registers of a lane -> one dword (bit k of byte b = bit 8 of register 2k + (b&1), half b>>1)
+// (LEAN: three v_lshl_or_b32 in a row; otherwise the compiler's own choice of four shorter-latency instructions)
+template <bool LEAN = false>
 __device__ __forceinline__ uint32_t pack_hi_bits(const uint32_t (&R)[8]) {
     constexpr uint32_t SEL_HI = 0x07030501u;                 // v_perm(b, a): bytes a.1, b.1, a.3, b.3
     const uint32_t h0 = __builtin_amdgcn_perm(R[1], R[0], SEL_HI), h1 = __builtin_amdgcn_perm(R[3], R[2], SEL_HI);
     const uint32_t h2 = __builtin_amdgcn_perm(R[5], R[4], SEL_HI), h3 = __builtin_amdgcn_perm(R[7], R[6], SEL_HI);
+    if constexpr (LEAN) {
+        uint32_t h;
+        asm("v_lshl_or_b32 %0, %1, 1, %2" : "=v"(h) : "v"(h1), "v"(h0));
+        asm("v_lshl_or_b32 %0, %1, 2, %2" : "=v"(h) : "v"(h2), "v"(h));
+        asm("v_lshl_or_b32 %0, %1, 3, %2" : "=v"(h) : "v"(h3), "v"(h));
+        return h;
+    }
     return h0 | (h1 << 1) | (h2 << 2) | (h3 << 3);
 }
 // private u8 order + bit plane -> registers (values up to 511)
@@ -123,7 +132,9 @@ __device__ __forceinline__ void band_unpack_c(const uint4 w, uint32_t (&C)[8]) {
 // cancels in S = max(P2 + m' - n', 0) with m' = min n' = m + K0; a path start presets m' = K0 (m = 0 there).  n' <= 255 + 127,
 // far below 0x7C00: the fp16 3-input minimum still orders it as integers.  O: YB (first pass: its sum crosses to the final
 // pass) or n' (final pass: S is rebuilt from the n' of its own paths, see band_kernel).
-template <int LPP, bool MASKED, bool OUT_N>
+// LOW_P2M (first pass): P2 + m' is built in the low half only -- one add -- and the saturating subtractions read that half for
+// both of theirs (v_pk_sub_u16 op_sel_hi:[0,1]) instead of a register with the value replicated (mask, add, shift-add).
+template <int LPP, bool MASKED, bool OUT_N, bool LOW_P2M = false>
 __device__ __forceinline__ void step_x(uint32_t (&S)[8], const uint32_t (&C)[8], uint32_t (&O)[8], const uint32_t P1pk,
                                        const uint32_t P2pk, const uint32_t kx, const uint32_t K0, const LaneSel sel,
                                        const bool start) {
@@ -139,11 +150,21 @@ __device__ __forceinline__ void step_x(uint32_t (&S)[8], const uint32_t (&C)[8],
     const uint32_t mm = pk_min(pk_min3(N[0], N[1], N[2]), pk_min3(N[3], N[4], pk_min3(N[5], N[6], N[7])));
     uint32_t mx = group_min_u32<LPP>(min_halves(mm));
     if (MASKED && start) mx = K0;
-    const uint32_t p2m = __umul24(mx, 0x10001u) + P2pk;
+    if constexpr (LOW_P2M) {
+        const uint16_t p2l = (uint16_t)(mx + P2pk);                       // P2 + m' (< 2^16)
+        const u16x2 p2m = {p2l, p2l};
 #pragma unroll
-    for (int i = 0; i < 8; i++) {
-        S[i] = pk_subs(p2m, N[i]);
-        O[i] = OUT_N ? N[i] : YB[i];
+        for (int i = 0; i < 8; i++) {
+            S[i] = __builtin_bit_cast(uint32_t, __builtin_elementwise_sub_sat(p2m, __builtin_bit_cast(u16x2, N[i])));
+            O[i] = OUT_N ? N[i] : YB[i];
+        }
+    } else {
+        const uint32_t p2m = __umul24(mx, 0x10001u) + P2pk;
+#pragma unroll
+        for (int i = 0; i < 8; i++) {
+            S[i] = pk_subs(p2m, N[i]);
+            O[i] = OUT_N ? N[i] : YB[i];
+        }
     }
 }
 
@@ -214,6 +235,9 @@ __global__ __launch_bounds__(NWV * 64, FSGM_BAND_MINW) void band_kernel(BandArgs
     // more LDS (67 KB: still two workgroups per CU; the second pass needs that room for its WTA rows)
     constexpr bool R16 = P8 && MODE == 0 && !CHAIN && FSGM_BAND_R16 != 0;   // (the chained form has no registers to spare for it)
     constexpr int NSL = R16 ? 2 : NST;                       // states that cross rows as packed bytes
+    // first pass, 8 paths, sequential bands: the leaner forms of the step (step_x LOW_P2M, pack_hi_bits LEAN) and the C
+    // prefetch issued behind the unpack of the slot it lands in (ring_step)
+    constexpr bool LEAN = P8 && MODE == 0 && !CHAIN;
     __shared__ uint2 sNb[MODE == 2 ? D : 1];                  // final pass: the WTA's neighbour table (band_nb_entry)
     __shared__ uint4 sR16[R16 ? 2 : 1][2][R16 ? (R + 1) * LPP : 1];   // [step parity][plane: registers 0-3 / 4-7][row slot][lane of pixel]
     __shared__ uint4 sSt[2][NSL][(R + 1) * LPP];              // [step parity][state][row slot (row + 1; slot 0 = the row above the band)][lane of pixel]
@@ -394,7 +418,7 @@ __global__ __launch_bounds__(NWV * 64, FSGM_BAND_MINW) void band_kernel(BandArgs
 
         // one step of this wave's rows.  EDGE: a pixel of the wave is at / outside an image border or in row 0, or a row
         // of the wave lies below the image (selects allowed); the plain variant has none.
-        auto do_step = [&](const int u, const int hp, const uint4 cw, const uint4 cy, const uint32_t cb, const uint4 cb4, auto edge_tag) {
+        auto do_step = [&](const int u, const int hp, const uint4 cw, const uint4 cy, const uint32_t cb, const uint4 cb4, const uint32_t (&CU)[8], auto edge_tag) {
             constexpr bool EDGE = decltype(edge_tag)::value;
             const int par = u & 1;
             const int x = u - SKEW * r;
@@ -406,7 +430,10 @@ __global__ __launch_bounds__(NWV * 64, FSGM_BAND_MINW) void band_kernel(BandArgs
             if constexpr (R16) { nLo = sR16[par ^ 1][0][r * LPP + j]; nHi = sR16[par ^ 1][1][r * LPP + j]; }
             else nNow = sSt[par ^ 1][P8 ? 2 : 0][r * LPP + j];
             uint32_t CP[8], Y[8], YS[8], S[8];
-            band_unpack_c(cw, CP);
+            if constexpr (LEAN) {                              // (unpacked by ring_step)
+#pragma unroll
+                for (int i = 0; i < 8; i++) CP[i] = CU[i];
+            } else band_unpack_c(cw, CP);
             const bool top = EDGE && y == 0;                   // row 0 of the frame: every path from above starts (:152-180)
             // from the left (-1,0): :183-191
             {
@@ -415,7 +442,7 @@ __global__ __launch_bounds__(NWV * 64, FSGM_BAND_MINW) void band_kernel(BandArgs
 #pragma unroll
                     for (int i = 0; i < 8; i++) FS[i] = P2pk;
                 }
-                step_x<LPP, EDGE, MODE == 2>(FS, CP, YS, P1pk, P2pk, KX, K0, sel, st);
+                step_x<LPP, EDGE, MODE == 2, LEAN>(FS, CP, YS, P1pk, P2pk, KX, K0, sel, st);
             }
             if (MODE == 2) {
                 // the first pass's sum leaves the running sum right away: its five registers are free for the rest of the step
@@ -436,7 +463,7 @@ __global__ __launch_bounds__(NWV * 64, FSGM_BAND_MINW) void band_kernel(BandArgs
 #pragma unroll
                     for (int i = 0; i < 8; i++) S[i] = P2pk;
                 }
-                step_x<LPP, EDGE, MODE == 2>(S, CP, Y, P1pk, P2pk, KX, K0, sel, top);
+                step_x<LPP, EDGE, MODE == 2, LEAN>(S, CP, Y, P1pk, P2pk, KX, K0, sel, top);
                 newU = pack_p(S);
                 sSt[par][0][(r + 1) * LPP + j] = newU;
 #pragma unroll
@@ -452,7 +479,7 @@ __global__ __launch_bounds__(NWV * 64, FSGM_BAND_MINW) void band_kernel(BandArgs
 #pragma unroll
                         for (int i = 0; i < 8; i++) S[i] = P2pk;
                     }
-                    step_x<LPP, EDGE, MODE == 2>(S, CP, Y, P1pk, P2pk, KX, K0, sel, st);
+                    step_x<LPP, EDGE, MODE == 2, LEAN>(S, CP, Y, P1pk, P2pk, KX, K0, sel, st);
                     newD = pack_p(S);
                     sSt[par][1][(r + 1) * LPP + j] = newD;
 #pragma unroll
@@ -470,7 +497,7 @@ __global__ __launch_bounds__(NWV * 64, FSGM_BAND_MINW) void band_kernel(BandArgs
 #pragma unroll
                         for (int i = 0; i < 8; i++) S[i] = P2pk;
                     }
-                    step_x<LPP, EDGE, MODE == 2>(S, CP, Y, P1pk, P2pk, KX, K0, sel, st);
+                    step_x<LPP, EDGE, MODE == 2, LEAN>(S, CP, Y, P1pk, P2pk, KX, K0, sel, st);
                     if constexpr (R16) {
                         sR16[par][0][(r + 1) * LPP + j] = make_uint4(S[0], S[1], S[2], S[3]);
                         sR16[par][1][(r + 1) * LPP + j] = make_uint4(S[4], S[5], S[6], S[7]);
@@ -509,7 +536,7 @@ __global__ __launch_bounds__(NWV * 64, FSGM_BAND_MINW) void band_kernel(BandArgs
                         vol_store(Bf + so - SB, make_uint4(YS[4], YS[5], YS[6], YS[7]));
                     } else {
                         vol_store(Yf + so - SB, pack_p(YS));
-                        if (BITS) *(uint32_t*)(Bf + (so >> 2) - SB / 4) = pack_hi_bits(YS);
+                        if (BITS) *(uint32_t*)(Bf + (so >> 2) - SB / 4) = pack_hi_bits<LEAN>(YS);
                     }
                 }
             } else {
@@ -550,7 +577,7 @@ __global__ __launch_bounds__(NWV * 64, FSGM_BAND_MINW) void band_kernel(BandArgs
                 __builtin_amdgcn_wave_barrier();
             }
         };
-        auto step = [&](const int u, const int hp, const uint4 cw, const uint4 cy, const uint32_t cb, const uint4 cb4) {
+        auto step = [&](const int u, const int hp, const uint4 cw, const uint4 cy, const uint32_t cb, const uint4 cb4, const uint32_t (&CU)[8]) {
             if (wave == 0 && have_above) {                                            // "row -1" of step u: column u + SKEW of the band above
                 const uint4 v = settle(ringE[0], edge_at(u + SKEW), loader);
 #pragma unroll
@@ -561,8 +588,8 @@ __global__ __launch_bounds__(NWV * 64, FSGM_BAND_MINW) void band_kernel(BandArgs
                 }
             }
             if (wave_rows && u >= act_lo && u <= act_hi) {                            // wave-uniform
-                if (wave_plain_rows && u >= pl_lo && u <= pl_hi) do_step(u, hp, cw, cy, cb, cb4, std::false_type{});
-                else do_step(u, hp, cw, cy, cb, cb4, std::true_type{});
+                if (wave_plain_rows && u >= pl_lo && u <= pl_hi) do_step(u, hp, cw, cy, cb, cb4, CU, std::false_type{});
+                else do_step(u, hp, cw, cy, cb, cb4, CU, std::true_type{});
             }
             if constexpr (RECLDS) {
                 if ((u & 7) == 7) flush_records(u);                                   // workgroup-uniform
@@ -573,7 +600,10 @@ __global__ __launch_bounds__(NWV * 64, FSGM_BAND_MINW) void band_kernel(BandArgs
         };
 
         // step u = u0 + i (u0 a multiple of UN): its words from slot i % NR, the loads of step u + PF into slot (i + PF) % NR
-        // (the same slot when NR = PF: read out first)
+        // (the same slot when NR = PF: read out first.  LEAN: the costs are unpacked here, by every wave whether it takes part
+        // in the step or not, and the load is issued behind the unpack: the slot's words are spent by then and the new ones land
+        // in their registers.  Issued before the step has read them, the new words need registers of their own and are copied
+        // into the slot's at the loop's back edge, 6 moves an iteration)
         auto ring_step = [&](const int u, const int i) {
             const int k = i % NR, kl = (i + PF) % NR;
             const uint4 cw = ringC[k];
@@ -584,13 +614,20 @@ __global__ __launch_bounds__(NWV * 64, FSGM_BAND_MINW) void band_kernel(BandArgs
             asm("" : "+v"(vpf));                               // one register, one add: not split into a base and induction variables
             uint32_t off;                                      // = vox_off(u + PF)
             asm("v_med3_u32 %0, %1, %2, %3" : "=v"(off) : "v"(vpf), "v"(v_lo), "v"(v_hi));
+            uint32_t CU[8] = {};
+            if constexpr (LEAN) {
+                band_unpack_c(cw, CU);
+                // (the load's offset "depends" on the unpacked costs: the compiler neither sinks the unpack into the step's
+                // branches nor lifts the load over it)
+                asm("" : "+v"(off) : "v"(CU[0]), "v"(CU[1]), "v"(CU[2]), "v"(CU[3]), "v"(CU[4]), "v"(CU[5]), "v"(CU[6]), "v"(CU[7]));
+            }
             ringC[kl] = *(const uint4*)(Cf + off);
             if (MODE == 2) {
                 ringY[kl] = vol_load(Yf + off);
                 if (Y16) ringB4[kl] = vol_load(Bf + off);
                 else if (BITS) ringB[kl] = *(const uint32_t*)(Bf + (off >> 2));
             }
-            step(u, i & 1, cw, cy, cb, cb4);
+            step(u, i & 1, cw, cy, cb, cb4, CU);
         };
         int u0 = 0;
         for (; u0 + UN <= nsteps; u0 += UN) {
