@@ -125,6 +125,8 @@ def load():
     lib.fsgm_epi_plan_kernel_name.restype = C.c_char_p
     lib.fsgm_epi_auto_pipeline.argtypes = [i32] * 9
     lib.fsgm_epi_auto_pipeline.restype = C.c_char_p
+    if hasattr(lib, "fsgm_epi_cost_kernels"):                    # (an older build behind FSGM_LIB_PATH has none)
+        lib.fsgm_epi_cost_kernels.argtypes = [i32, i32, i32, i32, C.c_char_p, C.c_size_t]
     lib.fsgm_measure_copy_bandwidth.argtypes = [i32, C.c_size_t, i32, C.POINTER(C.c_double)]
     lib.fsgm_measure_copy_bandwidth2.argtypes = [i32, C.c_size_t, i32, i32, C.POINTER(C.c_double)]
     if hasattr(lib, "fsgm_epi_plan_set_runner_up"):              # (an older build behind FSGM_LIB_PATH has none of these)

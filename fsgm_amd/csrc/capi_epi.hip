@@ -1150,6 +1150,18 @@ const char* fsgm_epi_auto_pipeline_opts(int32_t width, int32_t height, int32_t d
     return kPipelineName[choose_pipeline(width, height, dMax, batch, paths, P1, P2, cmax, 0, cus, opt && opt->adaptive_p2)];
 }
 
+// the launchers' own selector (select_cost_kernels, epi_kernels.hip) for a shape a plan of this sampling would accept
+fsgm_status fsgm_epi_cost_kernels(int32_t W, int32_t H, int32_t dMax, int32_t sampling, char* buf, size_t buflen) {
+    FSGM_REQUIRE(buf && buflen > 0, "fsgm_epi_cost_kernels: null or empty buffer");
+    buf[0] = 0;
+    { const fsgm_status as = epi_plan_args(W, H, dMax, 1, fsgm_epi_params_default(), sampling, -1); if (as != FSGM_OK) return as; }
+    const bool rect = sampling == FSGM_SAMPLING_RECTIFIED;
+    const char* name = cost_kernels_name(select_cost_kernels(W, H, dMax, rect), rect);
+    FSGM_REQUIRE(strlen(name) < buflen, "fsgm_epi_cost_kernels: buffer of %zu bytes too small for \"%s\"", buflen, name);
+    memcpy(buf, name, strlen(name) + 1);
+    return FSGM_OK;
+}
+
 // The achievable HBM rate of this device, measured the way the aggregation kernels move bytes: a grid-stride
 // copy kernel, 16 B per lane per access (launch_copy16, epi_kernels.hip), device memory to device memory, read + written
 // bytes counted.  mode 0: that kernel; mode 1: hipMemcpyAsync D2D (the runtime's blit kernel), for comparison.

@@ -427,9 +427,8 @@ __global__ __launch_bounds__(256) void stereo_rawcost_kernel(const uint32_t* __r
 void launch_stereo_cost(hipStream_t st, const uint32_t* cen1, const uint32_t* cen2, uint8_t* Craw, uint8_t* C, int W, int H, int D,
                         int direction, int frames, int d_min) {
     const int dir = direction < 0 ? -1 : 1;
-    // FSGM_COST_FUSED=0: the two-kernel form, as for launch_epi_cost
-    const bool fused = [] { const char* e = getenv("FSGM_COST_FUSED"); return !(e && e[0] == '0'); }();
-    if (fused && costbox_ok(W, H, D)) {
+    const CostKernels k = select_cost_kernels(W, H, D, true);                // (FSGM_COST_FUSED=0: the two-kernel form, as for launch_epi_cost)
+    if (k.raw == COST_RAW_FUSED) {
         EpiCostArgs a{};
         a.cen1 = cen1; a.cen2 = cen2; a.W = W; a.H = H; a.D = D;
         launch_costbox(st, a, C, frames, dir, dir * d_min);
@@ -437,7 +436,7 @@ void launch_stereo_cost(hipStream_t st, const uint32_t* cen1, const uint32_t* ce
     }
     const size_t n = (size_t)W * H * D;                                      // < 2^31 (plan creation)
     hipLaunchKernelGGL(stereo_rawcost_kernel, dim3((unsigned)((n + 255) / 256), frames), dim3(256), 0, st, cen1, cen2, Craw, W, H, D, dir, d_min);
-    launch_box5x5(st, Craw, C, W, H, D, frames);
+    launch_box5x5(st, k.box, Craw, C, W, H, D, frames);
 }
 
 // The outputs of a search range that starts at d_min as true disparities: candidate index * 256 (+ the parabola's offset) becomes

@@ -148,6 +148,15 @@ int  agg_packed_lpp(int D);   // lanes per pixel at 16 d per lane -- what the fu
 // with dpl = 16; 48, 96, 192 (dpl 12), 80, 160 (20), 112, 224 (28); false for every other D: the generic kernels
 bool agg_line_split(int D, int* lpp = nullptr, int* dpl = nullptr);
 void launch_census(hipStream_t st, const uint8_t* img, uint32_t* cen, int W, int H, int frames);
+// The kernels of the cost stage for one frame shape: the one place that decides, for launch_epi_cost, launch_stereo_cost,
+// launch_box5x5 and fsgm_epi_cost_kernels (include/fsgm.h).  raw == COST_RAW_FUSED: one kernel, box == COST_BOX_FUSED; every
+// other raw kernel writes Craw for one of the three box kernels.  Reads FSGM_COST_FUSED (per call) and FSGM_BOX16 (once).
+enum { COST_RAW_FUSED = 0, COST_RAW_PX = 1, COST_RAW_VEC4 = 2, COST_RAW_SCALAR = 3, COST_RAW_STEREO = 4 };
+enum { COST_BOX_FUSED = 0, COST_BOX_16 = 1, COST_BOX_4 = 2, COST_BOX_1 = 3 };
+struct CostKernels { int raw, box; };
+CostKernels select_cost_kernels(int W, int H, int D, bool rectified);
+int select_box_kernel(int D);                 // COST_BOX_16 / _4 / _1: the box kernel of a raw volume in HBM
+const char* cost_kernels_name(CostKernels k, bool rectified);
 void launch_epi_cost(hipStream_t st, const EpiCostArgs& a, uint8_t* C, int frames);
 // the cost stage as one kernel (epi_cost.hip): raw costs + 5x5 box mean, a.Craw unused
 bool costbox_ok(int W, int H, int D);
@@ -159,7 +168,7 @@ void launch_stereo_cost(hipStream_t st, const uint32_t* cen1, const uint32_t* ce
                         int direction, int frames, int d_min = 0);
 // disp (and disp2 unless null) of n pixels in place as int32 true disparities: 256 * d_min + value, disp2's 512 << 8 -> INT32_MIN
 void launch_stereo_range(hipStream_t st, uint32_t* disp, uint32_t* disp2, size_t n, int d_min);
-void launch_box5x5(hipStream_t st, const uint8_t* Craw, uint8_t* C, int W, int H, int D, int frames);
+void launch_box5x5(hipStream_t st, int box, const uint8_t* Craw, uint8_t* C, int W, int H, int D, int frames);   // box: select_box_kernel(D)
 int  costbox_selftest(hipStream_t st);      // 0: the mean's fp16 multiply is exact on this device; > 0: mismatches; < 0: could not run
 void launch_aggregate(hipStream_t st, AggArgs a, int paths, int frames, int kernel_kind);
 void launch_wta(hipStream_t st, const WtaArgs& a, int frames, bool packed);

@@ -1386,33 +1386,71 @@ void launch_census(hipStream_t st, const uint8_t* img, uint32_t* cen, int W, int
     hipLaunchKernelGGL(census5x5_kernel, grid, dim3(256), 0, st, img, cen, W, H);
 }
 
-void launch_epi_cost(hipStream_t st, const EpiCostArgs& a, uint8_t* C, int frames) {
-    // FSGM_COST_FUSED=0: the two-kernel form (raw volume through HBM) -- A/B switch and the cross-check of the fused kernel in the tests
-    const bool fused = [] { const char* e = getenv("FSGM_COST_FUSED"); return !(e && e[0] == '0'); }();   // read per launch: the tests flip it
-    if (fused && costbox_ok(a.W, a.H, a.D)) { launch_epi_costbox(st, a, C, frames); return; }
-    const long long n = (long long)a.W * a.H * ((a.D + 3) / 4);
-    dim3 grid((unsigned)((n + 255) / 256), frames);
-    if ((a.D & 7) == 0 && a.W < (1 << 22) && a.H < (1 << 24)) {
-        hipLaunchKernelGGL(epi_rawcost_px_kernel, dim3((unsigned)(((long long)a.W * a.H + 255) / 256), frames), dim3(256), 0, st, a);
-    } else if ((a.D & 3) == 0) hipLaunchKernelGGL(epi_rawcost_kernel<true>, grid, dim3(256), 0, st, a);
-    else                       hipLaunchKernelGGL(epi_rawcost_kernel<false>, grid, dim3(256), 0, st, a);
-    launch_box5x5(st, a.Craw, C, a.W, a.H, a.D, frames);
+// ---- which kernels the cost stage runs (the launchers below and in epi_cost.hip switch on this; fsgm_epi_cost_kernels prints it) ----
+int select_box_kernel(int D) {
+    static const bool box16 = [] { const char* e = getenv("FSGM_BOX16"); return !(e && e[0] == '0'); }();   // A/B switch
+    if (box16 && (D & 15) == 0 && D <= 1024) return COST_BOX_16;            // D / 16 <= 64 lanes a pixel
+    if ((D & 3) == 0 && D <= 1024) return COST_BOX_4;                        // D / 4 <= 256 lanes a pixel
+    return COST_BOX_1;
 }
 
-// the 5x5 box mean of a raw volume in HBM (the two-kernel form of the cost stage)
-void launch_box5x5(hipStream_t st, const uint8_t* Craw, uint8_t* C, int W, int H, int D, int frames) {
-    static const bool box16 = [] { const char* e = getenv("FSGM_BOX16"); return !(e && e[0] == '0'); }();   // A/B switch
-    if (box16 && (D & 15) == 0 && D <= 1024) {
-        const int cols = 256 / (D >> 4);
-        dim3 g2((W + cols - 1) / cols, (H + BOX_ROWS - 1) / BOX_ROWS, frames);
-        hipLaunchKernelGGL(box5x5_sliding16_kernel, g2, dim3(256), 0, st, Craw, C, W, H, D);
-    } else if ((D & 3) == 0 && D <= 1024) {
-        const int cols = 256 / (D >> 2);
-        dim3 g2((W + cols - 1) / cols, (H + BOX_ROWS - 1) / BOX_ROWS, frames);
-        hipLaunchKernelGGL(box5x5_sliding_kernel, g2, dim3(256), 0, st, Craw, C, W, H, D);
-    } else {
-        const long long n = (long long)W * H * ((D + 3) / 4);
-        hipLaunchKernelGGL(box5x5_kernel, dim3((unsigned)((n + 255) / 256), frames), dim3(256), 0, st, Craw, C, W, H, D);
+CostKernels select_cost_kernels(int W, int H, int D, bool rectified) {
+    // FSGM_COST_FUSED=0: the two-kernel form (raw volume through HBM) -- A/B switch and the cross-check of the fused kernel in the tests
+    const bool fused = [] { const char* e = getenv("FSGM_COST_FUSED"); return !(e && e[0] == '0'); }();   // read per call: the tests flip it
+    if (fused && costbox_ok(W, H, D)) return {COST_RAW_FUSED, COST_BOX_FUSED};
+    int raw;
+    if (rectified) raw = COST_RAW_STEREO;
+    else if ((D & 7) == 0 && W < (1 << 22) && H < (1 << 24)) raw = COST_RAW_PX;   // (the px kernel's 24-bit multiplies)
+    else if ((D & 3) == 0) raw = COST_RAW_VEC4;
+    else raw = COST_RAW_SCALAR;
+    return {raw, select_box_kernel(D)};
+}
+
+const char* cost_kernels_name(CostKernels k, bool rectified) {
+    static const char* const names[5][4] = {{"costbox", "", "", ""},
+                                            {"", "px+box16", "px+box4", "px+box1"},
+                                            {"", "vec4+box16", "vec4+box4", "vec4+box1"},
+                                            {"", "scalar+box16", "scalar+box4", "scalar+box1"},
+                                            {"", "stereo+box16", "stereo+box4", "stereo+box1"}};
+    if (k.raw == COST_RAW_FUSED) return rectified ? "stereo-costbox" : "costbox";
+    return names[k.raw][k.box];
+}
+
+void launch_epi_cost(hipStream_t st, const EpiCostArgs& a, uint8_t* C, int frames) {
+    const CostKernels k = select_cost_kernels(a.W, a.H, a.D, false);
+    const long long n = (long long)a.W * a.H * ((a.D + 3) / 4);
+    dim3 grid((unsigned)((n + 255) / 256), frames);
+    switch (k.raw) {
+        case COST_RAW_FUSED: launch_epi_costbox(st, a, C, frames); return;
+        case COST_RAW_PX:
+            hipLaunchKernelGGL(epi_rawcost_px_kernel, dim3((unsigned)(((long long)a.W * a.H + 255) / 256), frames), dim3(256), 0, st, a);
+            break;
+        case COST_RAW_VEC4: hipLaunchKernelGGL(epi_rawcost_kernel<true>, grid, dim3(256), 0, st, a); break;
+        default:            hipLaunchKernelGGL(epi_rawcost_kernel<false>, grid, dim3(256), 0, st, a); break;
+    }
+    launch_box5x5(st, k.box, a.Craw, C, a.W, a.H, a.D, frames);
+}
+
+// the 5x5 box mean of a raw volume in HBM (the two-kernel form of the cost stage); box: select_box_kernel(D)
+void launch_box5x5(hipStream_t st, int box, const uint8_t* Craw, uint8_t* C, int W, int H, int D, int frames) {
+    switch (box) {
+        case COST_BOX_16: {
+            const int cols = 256 / (D >> 4);
+            dim3 g2((W + cols - 1) / cols, (H + BOX_ROWS - 1) / BOX_ROWS, frames);
+            hipLaunchKernelGGL(box5x5_sliding16_kernel, g2, dim3(256), 0, st, Craw, C, W, H, D);
+            break;
+        }
+        case COST_BOX_4: {
+            const int cols = 256 / (D >> 2);
+            dim3 g2((W + cols - 1) / cols, (H + BOX_ROWS - 1) / BOX_ROWS, frames);
+            hipLaunchKernelGGL(box5x5_sliding_kernel, g2, dim3(256), 0, st, Craw, C, W, H, D);
+            break;
+        }
+        default: {
+            const long long n = (long long)W * H * ((D + 3) / 4);
+            hipLaunchKernelGGL(box5x5_kernel, dim3((unsigned)((n + 255) / 256), frames), dim3(256), 0, st, Craw, C, W, H, D);
+            break;
+        }
     }
 }
 

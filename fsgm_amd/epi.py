@@ -42,6 +42,16 @@ def auto_pipeline(width, height, dMax, batch, paths=4, P1=6, P2=64, cmax=24, cus
     return _lib.load().fsgm_epi_auto_pipeline(int(width), int(height), int(dMax), int(batch), int(paths), int(P1), int(P2), int(cmax), int(cus)).decode()
 
 
+def cost_kernels(width, height, dMax, sampling=_lib.SAMPLING_VZ):
+    """Which kernels the cost stage of a width x height x dMax plan launches (fsgm_epi_cost_kernels): "costbox" /
+    "stereo-costbox" for the fused kernel, "<raw>+<box>" with raw in px / vec4 / scalar / stereo and box in box16 / box4 / box1
+    for the two-kernel form.  The launchers' own selector under the environment as it stands (FSGM_COST_FUSED, FSGM_BOX16), no
+    device needed; raises FsgmError for a shape plan creation refuses."""
+    buf = C.create_string_buffer(32)
+    check(_lib.load().fsgm_epi_cost_kernels(int(width), int(height), int(dMax), int(sampling), buf, len(buf)))
+    return buf.value.decode()
+
+
 def calc_cost_sgm_batch(frames, dMax, vMax, P1, P2, *, paths=4, subpixel=1, vz_to_disp=1, device=0,
                         return_volumes=False, fb_check=0, devices=None, adaptive_p2=0):
     """frames: list of (I1, I2, pixelPosD0, normDir, offset) of one shape, processed concurrently.

@@ -322,6 +322,24 @@ const char* fsgm_epi_auto_pipeline(int32_t width, int32_t height, int32_t dMax, 
 /* the same for a call with options: an adaptive-P2 call takes the line kernels at every batch size */
 const char* fsgm_epi_auto_pipeline_opts(int32_t width, int32_t height, int32_t dMax, int32_t batch, int32_t paths, int32_t P1,
                                         int32_t P2, int32_t cmax, int32_t cus, const fsgm_epi_options* opt);
+/* Which kernels FSGM_STAGE_COST launches for a plan of width x height x dMax and this sampling (FSGM_SAMPLING_*), written to buf
+ * as text: the launchers' own selector evaluated without a device, under the environment as it stands (FSGM_COST_FUSED=0 never
+ * fuses, read at every call; FSGM_BOX16=0 never takes the 16-byte box kernel, read once per process).
+ *   "costbox"         raw cost and 5x5 box mean in one kernel: dMax = 16, 32, 64, 128, 256 with width < 2^22, height < 2^24
+ *   "stereo-costbox"  the same kernel's rectified form (FSGM_SAMPLING_RECTIFIED)
+ *   "<raw>+<box>"     the two-kernel form, a raw-cost kernel into a volume in HBM and a box kernel over it:
+ *     raw  "px"      one pixel a lane, all d       dMax % 8 == 0 (and width < 2^22, height < 2^24)
+ *          "vec4"    four d a thread, one store    dMax % 4 == 0 otherwise
+ *          "scalar"  four d a thread, guarded      every other dMax
+ *          "stereo"  one voxel a thread            every dMax of a rectified plan
+ *     box  "box16"   sliding window, 16 d a lane   dMax % 16 == 0
+ *          "box4"    sliding window, 4 d a lane    dMax % 4 == 0 otherwise
+ *          "box1"    25 taps a thread              every other dMax
+ * FSGM_SAMPLING_VZ and _LINEAR run the same kernels.  Shapes that plan creation refuses are refused here with the same status
+ * (FSGM_ERR_INVALID: a size below 1, an unknown sampling; FSGM_ERR_UNSUPPORTED: dMax > 1024, 2^31 voxels or more), a NULL buf
+ * or a buflen too small for the name and its terminator with FSGM_ERR_INVALID; buf is "" then (if it can be written at all).
+ * 32 bytes hold every name.  New names may be added. */
+fsgm_status fsgm_epi_cost_kernels(int32_t width, int32_t height, int32_t dMax, int32_t sampling, char* buf, size_t buflen);
 /* device-to-device copy bandwidth probe (GB/s, read+written bytes counted) used by bench.py: the library's own
  * grid-stride copy kernel, 16 B per lane per access -- the access width of the aggregation kernels */
 fsgm_status fsgm_measure_copy_bandwidth(int32_t device, size_t bytes, int32_t iters, double* gbps);
