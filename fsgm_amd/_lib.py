@@ -138,6 +138,9 @@ def load():
                                                   vp, vp]
         lib.fsgm_uniqueness_filter_host.argtypes = [i32, vp, vp, vp, i32, i32, i32, vp, i32]
         lib.fsgm_uniqueness_filter_device.argtypes = [i32, vp, vp, vp, i32, i32, i32, vp, i32, vp, vp]
+    if hasattr(lib, "fsgm_uniqueness_filter_planes_host"):       # (likewise: the 2-D matcher's runner-up cost came later)
+        lib.fsgm_uniqueness_filter_planes_host.argtypes = [i32, vp, vp, vp, i32, i32, i32, i32, vp, i32]
+        lib.fsgm_uniqueness_filter_planes_device.argtypes = [i32, vp, vp, vp, i32, i32, i32, i32, vp, i32, vp, vp]
     _lib = lib
     return lib
 

@@ -1459,11 +1459,11 @@ namespace fsgm {
 
 static thread_local const char* g_sgm_kernel = "";
 
-// the cached plan of a checked call: its batch, mode and adaptive switch are part of the key
+// the cached plan of a checked call: its batch, mode, adaptive and runner-up switches are part of the key
 static fsgm_status sgm_plan(std::unique_lock<std::mutex>& lk, fsgm_epi_plan** p, const SgmCall& c) {
     fsgm_epi_params pr = fsgm_epi_params_default();
     pr.paths = c.prm.paths; pr.subpixel = c.prm.subpixel; pr.device = c.prm.device; pr.vz_to_disp = 0; pr.fb_check = 0;
-    return cached_plan(lk, p, c.W, c.H, c.D, c.n, pr, FSGM_SAMPLING_VZ, 0, c.prm.adaptive_p2, c.prm.agg_mode);
+    return cached_plan(lk, p, c.W, c.H, c.D, c.n, pr, FSGM_SAMPLING_VZ, 0, c.prm.adaptive_p2, c.prm.agg_mode, c.minC2 != nullptr);
 }
 
 static fsgm_status ensure_ingest_flag(fsgm_epi_plan* p) {
@@ -1494,6 +1494,7 @@ fsgm_status sgm_run_host(const SgmCall& c, const int* cmax) {
     g_sgm_kernel = kPipelineName[p->pipe];
     FSGM_HIP(hipMemcpyAsync(c.bestD, p->dBestD, (size_t)c.n * NP * 4, hipMemcpyDeviceToHost, p->stream));
     FSGM_HIP(hipMemcpyAsync(c.minC, p->dMinC, (size_t)c.n * NP * 4, hipMemcpyDeviceToHost, p->stream));
+    if (c.minC2) FSGM_HIP(hipMemcpyAsync(c.minC2, p->dMinC2, (size_t)c.n * NP * 4, hipMemcpyDeviceToHost, p->stream));
     FSGM_HIP(hipStreamSynchronize(p->stream));
     guard.dismiss();
     if ((st = check_handoff(p)) != FSGM_OK) return st;
@@ -1521,7 +1522,7 @@ fsgm_status sgm_run_device(const SgmCall& c, hipStream_t cs, int32_t* status) {
     return device_call(p->join, cs, p->stream, [&]() -> fsgm_status {
         launch_sgm_ingest(p->stream, c.C, p->dC, c.n, c.W, c.H, c.D, c.prm.layout, c.prm.cost_bound, p->dIngestFlag);
         if (c.guide) FSGM_HIP(hipMemcpyAsync(p->dI1, c.guide, (size_t)c.n * p->NP, hipMemcpyDeviceToDevice, p->stream));
-        Bind<uint32_t> bd(p->dBestD, c.bestD), mc(p->dMinC, c.minC);
+        Bind<uint32_t> bd(p->dBestD, c.bestD), mc(p->dMinC, c.minC), m2(p->dMinC2, c.minC2);
         const fsgm_status es = enqueue(p, FSGM_STAGE_AGGREGATE | FSGM_STAGE_WTA);
         if (es != FSGM_OK) return es;
         g_sgm_kernel = kPipelineName[p->pipe];

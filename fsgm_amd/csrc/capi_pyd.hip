@@ -50,7 +50,7 @@ void fsgm_pyd_plan_destroy(fsgm_pyd_plan* p) {
     (void)hipSetDevice(p->device);
     if (p->stream) (void)hipStreamSynchronize(p->stream);       // queued device-form work of an evicted plan (fsgm_epi_plan_destroy)
     void* bufs[] = {p->dI1, p->dI2, p->dC, p->dL, p->dCen1, p->dCen2, p->dBestD, p->dMinC, p->dS, p->dDesc, p->dMv, p->dMvSub,
-                    p->dIngest, p->dIngestFlag, p->dFlow};
+                    p->dIngest, p->dIngestFlag, p->dFlow, p->dMinC2};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     p->join.destroy();
@@ -134,6 +134,32 @@ fsgm_status fsgm_pyd_plan_set_params(fsgm_pyd_plan* p, int32_t P1, int32_t P2, i
     FSGM_REQUIRE(p, "null plan");
     p->P1 = P1; p->P2 = P2; p->diagonal = diag != 0; p->totalPass = totalPass;
     p->adaptive = adaptive != 0; p->subpixel = subpixel;
+    return FSGM_OK;
+}
+
+fsgm_status fsgm_pyd_plan_set_runner_up(fsgm_pyd_plan* p, int32_t on) {
+    FSGM_REQUIRE(p, "null plan");
+    FSGM_REQUIRE(on == 0 || on == 1, "fsgm_pyd_plan_set_runner_up: on must be 0 or 1 (got %d)", on);
+    if (on && !p->dMinC2) {                                      // all ones until a WTA has run: FSGM_NO_RUNNER_UP
+        const size_t bytes = (size_t)p->batch * p->NP * 4;
+        uint32_t* m = nullptr;
+        FSGM_HIP(hipSetDevice(p->device));
+        FSGM_HIP(hipMalloc((void**)&m, bytes));
+        const hipError_t e = hipMemsetAsync(m, 0xFF, bytes, p->stream);
+        if (e != hipSuccess) { (void)hipFree(m); return hip_status(e, "fsgm_pyd_plan_set_runner_up"); }
+        p->dMinC2 = m;
+    }
+    p->runner_up = on;
+    return FSGM_OK;
+}
+
+fsgm_status fsgm_pyd_plan_download_runner_up(fsgm_pyd_plan* p, int32_t f, uint32_t* minC2) {
+    FSGM_REQUIRE(p && minC2, "fsgm_pyd_plan_download_runner_up: null argument");
+    FSGM_REQUIRE(f >= 0 && f < p->batch, "frame %d out of range (batch %d)", f, p->batch);
+    FSGM_REQUIRE(p->runner_up, "fsgm_pyd_plan_download_runner_up: the plan's runner-up switch is off (fsgm_pyd_plan_set_runner_up)");
+    FSGM_HIP(hipSetDevice(p->device));
+    FSGM_HIP(hipStreamSynchronize(p->stream));
+    FSGM_HIP(hipMemcpy(minC2, p->dMinC2 + f * p->NP, p->NP * 4, hipMemcpyDeviceToHost));
     return FSGM_OK;
 }
 
@@ -224,6 +250,7 @@ fsgm_status fsgm::pyd_enqueue(fsgm_pyd_plan* p, int stages, uint32_t* dS) {
         w.L = p->dL; w.bestD = p->dBestD; w.minC = p->dMinC; w.mvSub = p->dMvSub; w.S = dS;
         w.W = p->W; w.H = p->H; w.Sx = p->Sx; w.Sy = p->Sy; w.RS = p->RS; w.PS = p->PS;
         w.ndirs = g.ndirs; w.subpixel = p->subpixel;
+        w.minC2 = p->runner_up ? p->dMinC2 : nullptr;
         launch_pyd_wta(p->stream, w, p->batch);
     }
     FSGM_HIP(hipGetLastError());
@@ -292,10 +319,14 @@ static PlanCache<fsgm_pyd_plan> g_pyd(6, fsgm_pyd_plan_destroy);   // cached pla
 
 void fsgm_pyd_shutdown_internal(void) { g_pyd.clear(); }
 
-fsgm_status fsgm_calc_pyd_cost_sgm_batch_host(int32_t n, const fsgm_pyd_in* in, const fsgm_pyd_out* out, int32_t device) {
-    FSGM_REQUIRE(n >= 1 && in && out, "fsgm_calc_pyd_cost_sgm: null argument");
+}  // extern "C"
+
+// minC2s: null (the plain call), or one non-null pointer per frame (the _ru form: a cached plan of its own, the switch on)
+static fsgm_status pyd_batch_host(int32_t n, const fsgm_pyd_in* in, const fsgm_pyd_out* out, uint32_t* const* minC2s, bool ru, int32_t device) {
+    FSGM_REQUIRE(n >= 1 && in && out && (minC2s || !ru), "fsgm_calc_pyd_cost_sgm: null argument");
     const fsgm_pyd_in& a = in[0];
     for (int i = 0; i < n; i++) {
+        FSGM_REQUIRE(!ru || minC2s[i], "fsgm_calc_pyd_cost_sgm: frame %d has a null minC2", i);
         FSGM_REQUIRE(in[i].I1 && in[i].I2 && in[i].preMv, "fsgm_calc_pyd_cost_sgm: frame %d has a null input", i);
         FSGM_REQUIRE(out[i].bestD && out[i].minC && out[i].mvSub, "fsgm_calc_pyd_cost_sgm: frame %d has a null output", i);
         const fsgm_pyd_in& b = in[i];
@@ -310,12 +341,14 @@ fsgm_status fsgm_calc_pyd_cost_sgm_batch_host(int32_t n, const fsgm_pyd_in* in, 
     std::lock_guard<std::mutex> lk(g_pyd.mu(device));
     fsgm_pyd_plan* p = g_pyd.find(device, [&](const fsgm_pyd_plan* q) {
         return q->W == a.width && q->H == a.height && q->mvW == a.mvWidth && q->mvH == a.mvHeight &&
-               q->rX == a.halfSearchWinSizeX && q->rY == a.halfSearchWinSizeY && q->rAgg == a.aggHalfWinSize && q->batch == n;
+               q->rX == a.halfSearchWinSizeX && q->rY == a.halfSearchWinSizeY && q->rAgg == a.aggHalfWinSize && q->batch == n &&
+               q->runner_up == (int)ru;                         // (a runner-up caller and a plain one never share a plan)
     });
     fsgm_status st;
     if (!p) {
         st = fsgm_pyd_plan_create(&p, a.width, a.height, a.mvWidth, a.mvHeight, a.halfSearchWinSizeX,
                                   a.halfSearchWinSizeY, a.aggHalfWinSize, n, device);
+        if (st == FSGM_OK && ru && (st = fsgm_pyd_plan_set_runner_up(p, 1)) != FSGM_OK) fsgm_pyd_plan_destroy(p);
         if (st != FSGM_OK) return st;
         g_pyd.insert(device, p);
     }
@@ -325,10 +358,24 @@ fsgm_status fsgm_calc_pyd_cost_sgm_batch_host(int32_t n, const fsgm_pyd_in* in, 
     if ((st = fsgm_pyd_plan_run(p, FSGM_STAGE_ALL)) != FSGM_OK) return st;
     for (int i = 0; i < n; i++) {
         if ((st = fsgm_pyd_plan_download(p, i, out[i].bestD, out[i].minC, out[i].mvSub)) != FSGM_OK) return st;
+        if (ru && (st = fsgm_pyd_plan_download_runner_up(p, i, minC2s[i])) != FSGM_OK) return st;
         if (out[i].C && (st = fsgm_pyd_plan_download_cost(p, i, out[i].C)) != FSGM_OK) return st;
         if (out[i].S && (st = fsgm_pyd_plan_download_sum(p, i, out[i].S)) != FSGM_OK) return st;
     }
     return FSGM_OK;
+}
+
+extern "C" {
+
+fsgm_status fsgm_calc_pyd_cost_sgm_batch_host(int32_t n, const fsgm_pyd_in* in, const fsgm_pyd_out* out, int32_t device) {
+    return pyd_batch_host(n, in, out, nullptr, false, device);
+}
+
+// the same through a cached plan with the runner-up switch on (never the plan of the call above: the key holds the switch)
+fsgm_status fsgm_calc_pyd_cost_sgm_batch_host_ru(int32_t n, const fsgm_pyd_in* in, const fsgm_pyd_out* out, uint32_t* const* minC2s,
+                                                 int32_t device) {
+    FSGM_REQUIRE(minC2s, "fsgm_calc_pyd_cost_sgm_batch_host_ru: null minC2s");
+    return pyd_batch_host(n, in, out, minC2s, true, device);
 }
 
 fsgm_status fsgm_calc_pyd_cost_sgm_host(const fsgm_pyd_in* in, const fsgm_pyd_out* out, int32_t device) {

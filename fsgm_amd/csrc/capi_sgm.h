@@ -10,6 +10,7 @@ struct SgmCall {
     fsgm_sgm_params prm;                 // checked, never the caller's NULL
     const uint8_t *C, *guide;            // guide: non-NULL exactly when prm.adaptive_p2
     uint32_t *bestD, *minC, *S;          // S may be NULL
+    uint32_t* minC2;                     // the _ru forms' runner-up cost (never NULL there), NULL in the plain forms
 };
 
 // host pointers; cmax: the largest byte of each frame's volume (none above prm.cost_bound)

@@ -11,9 +11,11 @@ using namespace fsgm;
 
 // the checks both forms share: prm (NULL: the defaults) into c->prm, the scalars and the pointers every call needs
 static fsgm_status sgm_args(const char* who, int32_t n, const uint8_t* C, int32_t W, int32_t H, int32_t D, int32_t P1, int32_t P2,
-                            const fsgm_sgm_params* prm, const uint8_t* guide, uint32_t* bestD, uint32_t* minC, uint32_t* S, SgmCall* c) {
+                            const fsgm_sgm_params* prm, const uint8_t* guide, uint32_t* bestD, uint32_t* minC, uint32_t* S, uint32_t* minC2, bool ru,
+                            SgmCall* c) {
     FSGM_REQUIRE(n >= 1, "%s: n_frames must be >= 1 (got %d)", who, n);
     FSGM_REQUIRE(C && bestD && minC, "%s: null argument", who);
+    FSGM_REQUIRE(!ru || minC2, "%s: null minC2", who);
     FSGM_REQUIRE(W >= 1 && H >= 1, "%s: width/height must be >= 1 (got %d x %d)", who, W, H);
     FSGM_REQUIRE(D >= 1 && D <= 1024, "%s: dMax must be 1..1024 (got %d)", who, D);
     const fsgm_sgm_params sp = prm ? *prm : fsgm_sgm_params_default();
@@ -30,9 +32,12 @@ static fsgm_status sgm_args(const char* who, int32_t n, const uint8_t* C, int32_
     if (sp.adaptive_p2 && sp.agg_mode >= 2)
         return fail(FSGM_ERR_UNSUPPORTED, "%s: agg_mode %d with adaptive_p2: only the line kernels (modes 0 and 1) take a per-step P2", who,
                     sp.agg_mode);
+    if (ru && sp.agg_mode >= 2)
+        return fail(FSGM_ERR_UNSUPPORTED, "%s: agg_mode %d with minC2: only the line kernels' WTA (modes 0 and 1) writes the runner-up cost", who,
+                    sp.agg_mode);
     if ((double)W * H * D >= 2147483648.0)
         return fail(FSGM_ERR_UNSUPPORTED, "%s: cost volume %d x %d x %d exceeds 2^31 voxels per frame", who, W, H, D);
-    *c = SgmCall{n, W, H, D, P1, P2, sp, C, sp.adaptive_p2 ? guide : nullptr, bestD, minC, S};
+    *c = SgmCall{n, W, H, D, P1, P2, sp, C, sp.adaptive_p2 ? guide : nullptr, bestD, minC, S, ru ? minC2 : nullptr};
     return FSGM_OK;
 }
 
@@ -48,10 +53,14 @@ fsgm_sgm_params fsgm_sgm_params_default(void) {
     return p;
 }
 
-fsgm_status fsgm_sgm_batch_host(int32_t n, const uint8_t* C, int32_t W, int32_t H, int32_t D, int32_t P1, int32_t P2,
-                                const fsgm_sgm_params* prm, const uint8_t* guide, uint32_t* bestD, uint32_t* minC, uint32_t* S) {
+}  // extern "C"
+
+// both host forms; ru: the _ru form
+static fsgm_status sgm_host(const char* who, int32_t n, const uint8_t* C, int32_t W, int32_t H, int32_t D, int32_t P1, int32_t P2,
+                            const fsgm_sgm_params* prm, const uint8_t* guide, uint32_t* bestD, uint32_t* minC, uint32_t* minC2, bool ru,
+                            uint32_t* S) {
     SgmCall c;
-    const fsgm_status st = sgm_args("fsgm_sgm_batch_host", n, C, W, H, D, P1, P2, prm, guide, bestD, minC, S, &c);
+    const fsgm_status st = sgm_args(who, n, C, W, H, D, P1, P2, prm, guide, bestD, minC, S, minC2, ru, &c);
     if (st != FSGM_OK) return st;
     // the true maximum of every frame, as fsgm_epi_plan_upload_cost takes it (either layout holds the same bytes)
     const size_t N = (size_t)W * H * D;
@@ -60,18 +69,18 @@ fsgm_status fsgm_sgm_batch_host(int32_t n, const uint8_t* C, int32_t W, int32_t 
         const uint8_t* v = C + (size_t)f * N;
         int m = 0;
         for (size_t i = 0; i < N; i++) m = v[i] > m ? v[i] : m;
-        FSGM_REQUIRE(m <= c.prm.cost_bound, "fsgm_sgm_batch_host: frame %d holds a cost of %d, above cost_bound %d", f, m, c.prm.cost_bound);
+        FSGM_REQUIRE(m <= c.prm.cost_bound, "%s: frame %d holds a cost of %d, above cost_bound %d", who, f, m, c.prm.cost_bound);
         cmax[f] = m;
     }
     return sgm_run_host(c, cmax.data());
 }
 
-fsgm_status fsgm_sgm_device(int32_t n, const uint8_t* C, int32_t W, int32_t H, int32_t D, int32_t P1, int32_t P2,
-                            const fsgm_sgm_params* prm, const uint8_t* guide, uint32_t* bestD, uint32_t* minC, uint32_t* S, void* stream,
-                            int32_t* status) {
-    const char* who = "fsgm_sgm_device";
+// both device forms
+static fsgm_status sgm_device(const char* who, int32_t n, const uint8_t* C, int32_t W, int32_t H, int32_t D, int32_t P1, int32_t P2,
+                              const fsgm_sgm_params* prm, const uint8_t* guide, uint32_t* bestD, uint32_t* minC, uint32_t* minC2, bool ru,
+                              uint32_t* S, void* stream, int32_t* status) {
     SgmCall c;
-    fsgm_status st = sgm_args(who, n, C, W, H, D, P1, P2, prm, guide, bestD, minC, S, &c);
+    fsgm_status st = sgm_args(who, n, C, W, H, D, P1, P2, prm, guide, bestD, minC, S, minC2, ru, &c);
     if (st != FSGM_OK) return st;
     const size_t np = (size_t)n * W * H, nv = np * D;
     const hipStream_t cs = (hipStream_t)stream;
@@ -79,10 +88,36 @@ fsgm_status fsgm_sgm_device(int32_t n, const uint8_t* C, int32_t W, int32_t H, i
                                                         {c.guide, np, 1, false, "guide"},
                                                         {bestD, np * 4, 4, true, "bestD"},
                                                         {minC, np * 4, 4, true, "minC"},
+                                                        {c.minC2, np * 4, 4, ru, "minC2"},
                                                         {S, nv * 4, 4, false, "S"},
                                                         {status, 4, 4, false, "status"}})) != FSGM_OK)
         return st;
     return sgm_run_device(c, cs, status);
+}
+
+extern "C" {
+
+fsgm_status fsgm_sgm_batch_host(int32_t n, const uint8_t* C, int32_t W, int32_t H, int32_t D, int32_t P1, int32_t P2,
+                                const fsgm_sgm_params* prm, const uint8_t* guide, uint32_t* bestD, uint32_t* minC, uint32_t* S) {
+    return sgm_host("fsgm_sgm_batch_host", n, C, W, H, D, P1, P2, prm, guide, bestD, minC, nullptr, false, S);
+}
+
+fsgm_status fsgm_sgm_batch_host_ru(int32_t n, const uint8_t* C, int32_t W, int32_t H, int32_t D, int32_t P1, int32_t P2,
+                                   const fsgm_sgm_params* prm, const uint8_t* guide, uint32_t* bestD, uint32_t* minC, uint32_t* minC2,
+                                   uint32_t* S) {
+    return sgm_host("fsgm_sgm_batch_host_ru", n, C, W, H, D, P1, P2, prm, guide, bestD, minC, minC2, true, S);
+}
+
+fsgm_status fsgm_sgm_device(int32_t n, const uint8_t* C, int32_t W, int32_t H, int32_t D, int32_t P1, int32_t P2,
+                            const fsgm_sgm_params* prm, const uint8_t* guide, uint32_t* bestD, uint32_t* minC, uint32_t* S, void* stream,
+                            int32_t* status) {
+    return sgm_device("fsgm_sgm_device", n, C, W, H, D, P1, P2, prm, guide, bestD, minC, nullptr, false, S, stream, status);
+}
+
+fsgm_status fsgm_sgm_device_ru(int32_t n, const uint8_t* C, int32_t W, int32_t H, int32_t D, int32_t P1, int32_t P2,
+                               const fsgm_sgm_params* prm, const uint8_t* guide, uint32_t* bestD, uint32_t* minC, uint32_t* minC2,
+                               uint32_t* S, void* stream, int32_t* status) {
+    return sgm_device("fsgm_sgm_device_ru", n, C, W, H, D, P1, P2, prm, guide, bestD, minC, minC2, true, S, stream, status);
 }
 
 }  // extern "C"

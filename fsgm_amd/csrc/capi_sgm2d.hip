@@ -26,6 +26,7 @@ struct Sgm2dCall {
     uint32_t *bestD, *minC;
     double *mvSub, *flow;
     uint32_t* S;
+    uint32_t* minC2;                     // the _ru forms' runner-up cost (never NULL there), NULL in the plain forms
 };
 
 bool layout_ok(int layout) {
@@ -35,7 +36,7 @@ bool layout_ok(int layout) {
 // the checks both forms share, none of which needs a device
 fsgm_status sgm2d_args(const char* who, int32_t n, const uint8_t* C, int32_t W, int32_t H, int32_t rX, int32_t rY, int32_t P1, int32_t P2,
                        const fsgm_sgm2d_params* prm, const double* preMv, int32_t mvW, int32_t mvH, const uint8_t* guide, uint32_t* bestD,
-                       uint32_t* minC, double* mvSub, double* flow, uint32_t* S, Sgm2dCall* c) {
+                       uint32_t* minC, double* mvSub, double* flow, uint32_t* S, uint32_t* minC2, bool ru, Sgm2dCall* c) {
     FSGM_REQUIRE(n >= 1, "%s: n_frames must be >= 1 (got %d)", who, n);
     FSGM_REQUIRE(W >= 1 && H >= 1, "%s: width/height must be >= 1 (got %d x %d)", who, W, H);
     FSGM_REQUIRE(rX >= 0 && rY >= 0, "%s: halfX/halfY must be >= 0 (got %d, %d)", who, rX, rY);
@@ -55,29 +56,32 @@ fsgm_status sgm2d_args(const char* who, int32_t n, const uint8_t* C, int32_t W, 
     for (int r : sp.reserved) FSGM_REQUIRE(r == 0, "%s: the reserved words of fsgm_sgm2d_params must be zero", who);
     FSGM_REQUIRE(sp.device >= 0 && sp.device < FSGM_MAX_DEVICES, "%s: device %d out of range", who, sp.device);
     FSGM_REQUIRE(C && bestD && minC && mvSub, "%s: null argument (C, bestD, minC and mvSub are required)", who);
+    FSGM_REQUIRE(!ru || minC2, "%s: null argument (minC2 is required)", who);
     FSGM_REQUIRE(!preMv || (mvW >= W && mvH >= H), "%s: preMv (%d x %d) must be at least as large as the image (%d x %d): the "
                  "reference indexes it with image coordinates (calc_pyd_cost_sgm.cpp:388-389)", who, mvW, mvH, W, H);
     FSGM_REQUIRE(!sp.adaptive_p2 || guide, "%s: adaptive_p2 needs the guide image (guide is NULL)", who);
     *c = Sgm2dCall{n, W, H, rX, rY, P1, P2, preMv ? mvW : W, preMv ? mvH : H, sp, C, preMv, sp.adaptive_p2 ? guide : nullptr,
-                   bestD, minC, mvSub, flow, S};
+                   bestD, minC, mvSub, flow, S, ru ? minC2 : nullptr};
     return FSGM_OK;
 }
 
-// Aggregation-only plans (pyd_plan.h), keyed by shape, window, hint-map size, batch, device and whether a guide is held.
+// Aggregation-only plans (pyd_plan.h), keyed by shape, window, hint-map size, batch, device, whether a guide is held and the
+// runner-up switch (a call that asks for minC2 never takes the plan of one that does not).
 // The host and the device form share them: a call holds its device's lock for its length and queues on the plan's stream.
 PlanCache<fsgm_pyd_plan> g_sgm2d(6, fsgm_pyd_plan_destroy);
 thread_local const char* g_sgm2d_kernel = "";
 
 // the cached plan of a checked call, with the call's parameters and `cmax` set; the device's lock is the caller's
 fsgm_status sgm2d_plan(fsgm_pyd_plan** out, const Sgm2dCall& c, int cmax) {
-    const int dev = c.prm.device, flags = PYD_PLAN_AGG_ONLY | (c.guide ? PYD_PLAN_GUIDE : 0);
+    const int dev = c.prm.device, flags = PYD_PLAN_AGG_ONLY | (c.guide ? PYD_PLAN_GUIDE : 0), ru = c.minC2 != nullptr;
     fsgm_pyd_plan* p = g_sgm2d.find(dev, [&](const fsgm_pyd_plan* q) {
         return q->W == c.W && q->H == c.H && q->mvW == c.mvW && q->mvH == c.mvH && q->rX == c.rX && q->rY == c.rY && q->batch == c.n &&
-               q->flags == flags;
+               q->flags == flags && q->runner_up == ru;
     });
     fsgm_status st;
     if (!p) {
         if ((st = pyd_plan_create_flags(&p, c.W, c.H, c.mvW, c.mvH, c.rX, c.rY, 0, c.n, dev, flags)) != FSGM_OK) return st;
+        if (ru && (st = fsgm_pyd_plan_set_runner_up(p, 1)) != FSGM_OK) { fsgm_pyd_plan_destroy(p); return st; }
         g_sgm2d.insert(dev, p);
     } else if ((st = use_device(dev)) != FSGM_OK) {
         return st;
@@ -119,31 +123,12 @@ fsgm_status sgm2d_enqueue(fsgm_pyd_plan* p, uint32_t* dS, double* dFlow) {
     return FSGM_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-void fsgm_sgm2d_shutdown_internal(void) { g_sgm2d.clear(); }
-
-fsgm_sgm2d_params fsgm_sgm2d_params_default(void) {
-    fsgm_sgm2d_params p;
-    memset(&p, 0, sizeof(p));
-    p.diagonal = 1;                      // pyramidal_sgm.m:15-22
-    p.totalPass = 2;
-    p.subpixel = 1;
-    p.layout = FSGM_COST2D_LAYOUT_HWD;
-    p.cost_bound = 255;
-    return p;
-}
-
-const char* fsgm_sgm2d_last_kernel(void) { return g_sgm2d_kernel; }
-
-fsgm_status fsgm_sgm2d_batch_host(int32_t n, const uint8_t* C, int32_t W, int32_t H, int32_t rX, int32_t rY, int32_t P1, int32_t P2,
-                                  const fsgm_sgm2d_params* prm, const double* preMv, int32_t mvW, int32_t mvH, const uint8_t* guide,
-                                  uint32_t* bestD, uint32_t* minC, double* mvSub, double* flow, uint32_t* S) {
-    const char* who = "fsgm_sgm2d_batch_host";
+// both host forms; minC2 non-NULL: the _ru form
+fsgm_status sgm2d_host(const char* who, int32_t n, const uint8_t* C, int32_t W, int32_t H, int32_t rX, int32_t rY, int32_t P1, int32_t P2,
+                       const fsgm_sgm2d_params* prm, const double* preMv, int32_t mvW, int32_t mvH, const uint8_t* guide, uint32_t* bestD,
+                       uint32_t* minC, uint32_t* minC2, bool ru, double* mvSub, double* flow, uint32_t* S) {
     Sgm2dCall c;
-    fsgm_status st = sgm2d_args(who, n, C, W, H, rX, rY, P1, P2, prm, preMv, mvW, mvH, guide, bestD, minC, mvSub, flow, S, &c);
+    fsgm_status st = sgm2d_args(who, n, C, W, H, rX, rY, P1, P2, prm, preMv, mvW, mvH, guide, bestD, minC, mvSub, flow, S, minC2, ru, &c);
     if (st != FSGM_OK) return st;
     // the true maximum of the batch (every layout holds the same bytes), as fsgm_pyd_plan_upload_cost takes it
     const size_t NP = (size_t)W * H, ND = NP * (2 * rX + 1) * (2 * rY + 1);
@@ -176,6 +161,7 @@ fsgm_status fsgm_sgm2d_batch_host(int32_t n, const uint8_t* C, int32_t W, int32_
     if ((st = sgm2d_enqueue(p, S ? p->dS : nullptr, flow ? p->dFlow : nullptr)) != FSGM_OK) return st;
     FSGM_HIP(hipMemcpyAsync(bestD, p->dBestD, B * NP * 4, hipMemcpyDeviceToHost, p->stream));
     FSGM_HIP(hipMemcpyAsync(minC, p->dMinC, B * NP * 4, hipMemcpyDeviceToHost, p->stream));
+    if (c.minC2) FSGM_HIP(hipMemcpyAsync(c.minC2, p->dMinC2, B * NP * 4, hipMemcpyDeviceToHost, p->stream));
     FSGM_HIP(hipMemcpyAsync(mvSub, p->dMvSub, B * NP * 16, hipMemcpyDeviceToHost, p->stream));
     if (flow) FSGM_HIP(hipMemcpyAsync(flow, p->dFlow, B * NP * 16, hipMemcpyDeviceToHost, p->stream));
     if (S) FSGM_HIP(hipMemcpyAsync(S, p->dS, B * ND * 4, hipMemcpyDeviceToHost, p->stream));
@@ -184,12 +170,12 @@ fsgm_status fsgm_sgm2d_batch_host(int32_t n, const uint8_t* C, int32_t W, int32_
     return FSGM_OK;
 }
 
-fsgm_status fsgm_sgm2d_device(int32_t n, const uint8_t* C, int32_t W, int32_t H, int32_t rX, int32_t rY, int32_t P1, int32_t P2,
-                              const fsgm_sgm2d_params* prm, const double* preMv, int32_t mvW, int32_t mvH, const uint8_t* guide,
-                              uint32_t* bestD, uint32_t* minC, double* mvSub, double* flow, uint32_t* S, void* stream, int32_t* status) {
-    const char* who = "fsgm_sgm2d_device";
+// both device forms; minC2 non-NULL: the _ru form, written where it lies by the WTA itself
+fsgm_status sgm2d_device(const char* who, int32_t n, const uint8_t* C, int32_t W, int32_t H, int32_t rX, int32_t rY, int32_t P1, int32_t P2,
+                         const fsgm_sgm2d_params* prm, const double* preMv, int32_t mvW, int32_t mvH, const uint8_t* guide, uint32_t* bestD,
+                         uint32_t* minC, uint32_t* minC2, bool ru, double* mvSub, double* flow, uint32_t* S, void* stream, int32_t* status) {
     Sgm2dCall c;
-    fsgm_status st = sgm2d_args(who, n, C, W, H, rX, rY, P1, P2, prm, preMv, mvW, mvH, guide, bestD, minC, mvSub, flow, S, &c);
+    fsgm_status st = sgm2d_args(who, n, C, W, H, rX, rY, P1, P2, prm, preMv, mvW, mvH, guide, bestD, minC, mvSub, flow, S, minC2, ru, &c);
     if (st != FSGM_OK) return st;
     const size_t np = (size_t)n * W * H, nv = np * (2 * rX + 1) * (2 * rY + 1), nmv = (size_t)n * c.mvW * c.mvH;
     const hipStream_t cs = (hipStream_t)stream;
@@ -198,6 +184,7 @@ fsgm_status fsgm_sgm2d_device(int32_t n, const uint8_t* C, int32_t W, int32_t H,
                                                         {c.guide, np, 1, false, "guide"},
                                                         {bestD, np * 4, 4, true, "bestD"},
                                                         {minC, np * 4, 4, true, "minC"},
+                                                        {c.minC2, np * 4, 4, ru, "minC2"},
                                                         {mvSub, np * 16, 8, true, "mvSub"},
                                                         {flow, np * 16, 8, false, "flow"},
                                                         {S, nv * 4, 4, false, "S"},
@@ -218,12 +205,60 @@ fsgm_status fsgm_sgm2d_device(int32_t n, const uint8_t* C, int32_t W, int32_t H,
         // the caller's arrays stand in the plan's slots for the length of the enqueue
         Bind<double> mv(p->dMv, const_cast<double*>(preMv)), ms(p->dMvSub, mvSub);
         Bind<uint8_t> i1(p->dI1, const_cast<uint8_t*>(c.guide));
-        Bind<uint32_t> bd(p->dBestD, bestD), mc(p->dMinC, minC);
+        Bind<uint32_t> bd(p->dBestD, bestD), mc(p->dMinC, minC), m2(p->dMinC2, c.minC2);
         const fsgm_status es = sgm2d_enqueue(p, S, flow);
         if (es != FSGM_OK) return es;
         launch_device_status(p->stream, nullptr, p->dIngestFlag, status);
         return FSGM_OK;
     });
+}
+
+}  // namespace
+
+extern "C" {
+
+void fsgm_sgm2d_shutdown_internal(void) { g_sgm2d.clear(); }
+
+fsgm_sgm2d_params fsgm_sgm2d_params_default(void) {
+    fsgm_sgm2d_params p;
+    memset(&p, 0, sizeof(p));
+    p.diagonal = 1;                      // pyramidal_sgm.m:15-22
+    p.totalPass = 2;
+    p.subpixel = 1;
+    p.layout = FSGM_COST2D_LAYOUT_HWD;
+    p.cost_bound = 255;
+    return p;
+}
+
+const char* fsgm_sgm2d_last_kernel(void) { return g_sgm2d_kernel; }
+
+fsgm_status fsgm_sgm2d_batch_host(int32_t n, const uint8_t* C, int32_t W, int32_t H, int32_t rX, int32_t rY, int32_t P1, int32_t P2,
+                                  const fsgm_sgm2d_params* prm, const double* preMv, int32_t mvW, int32_t mvH, const uint8_t* guide,
+                                  uint32_t* bestD, uint32_t* minC, double* mvSub, double* flow, uint32_t* S) {
+    return sgm2d_host("fsgm_sgm2d_batch_host", n, C, W, H, rX, rY, P1, P2, prm, preMv, mvW, mvH, guide, bestD, minC, nullptr, false, mvSub,
+                      flow, S);
+}
+
+fsgm_status fsgm_sgm2d_batch_host_ru(int32_t n, const uint8_t* C, int32_t W, int32_t H, int32_t rX, int32_t rY, int32_t P1, int32_t P2,
+                                     const fsgm_sgm2d_params* prm, const double* preMv, int32_t mvW, int32_t mvH, const uint8_t* guide,
+                                     uint32_t* bestD, uint32_t* minC, uint32_t* minC2, double* mvSub, double* flow, uint32_t* S) {
+    return sgm2d_host("fsgm_sgm2d_batch_host_ru", n, C, W, H, rX, rY, P1, P2, prm, preMv, mvW, mvH, guide, bestD, minC, minC2, true, mvSub,
+                      flow, S);
+}
+
+fsgm_status fsgm_sgm2d_device(int32_t n, const uint8_t* C, int32_t W, int32_t H, int32_t rX, int32_t rY, int32_t P1, int32_t P2,
+                              const fsgm_sgm2d_params* prm, const double* preMv, int32_t mvW, int32_t mvH, const uint8_t* guide,
+                              uint32_t* bestD, uint32_t* minC, double* mvSub, double* flow, uint32_t* S, void* stream, int32_t* status) {
+    return sgm2d_device("fsgm_sgm2d_device", n, C, W, H, rX, rY, P1, P2, prm, preMv, mvW, mvH, guide, bestD, minC, nullptr, false, mvSub,
+                        flow, S, stream, status);
+}
+
+fsgm_status fsgm_sgm2d_device_ru(int32_t n, const uint8_t* C, int32_t W, int32_t H, int32_t rX, int32_t rY, int32_t P1, int32_t P2,
+                                 const fsgm_sgm2d_params* prm, const double* preMv, int32_t mvW, int32_t mvH, const uint8_t* guide,
+                                 uint32_t* bestD, uint32_t* minC, uint32_t* minC2, double* mvSub, double* flow, uint32_t* S, void* stream,
+                                 int32_t* status) {
+    return sgm2d_device("fsgm_sgm2d_device_ru", n, C, W, H, rX, rY, P1, P2, prm, preMv, mvW, mvH, guide, bestD, minC, minC2, true, mvSub,
+                        flow, S, stream, status);
 }
 
 fsgm_status fsgm_pyd_plan_ingest_cost_device(fsgm_pyd_plan* p, int32_t n, const uint8_t* C, int32_t layout, int32_t cost_bound,

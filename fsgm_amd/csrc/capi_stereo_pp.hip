@@ -221,67 +221,95 @@ static bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
     return x < y + nb && y < x + na;
 }
 static fsgm_status uniqueness_args(const char* who, int32_t n, const double* map, const uint32_t* minC, const uint32_t* minC2, int32_t W,
-                                   int32_t H, int32_t ratio, const double* out, int32_t device) {
+                                   int32_t H, int32_t planes, int32_t ratio, const double* out, int32_t device) {
     FSGM_REQUIRE(n >= 1, "%s: n_frames must be >= 1 (got %d)", who, n);
     FSGM_REQUIRE(map && minC && minC2 && out, "%s: null argument", who);
     FSGM_REQUIRE(W >= 1 && H >= 1, "%s: width/height must be >= 1 (got %d x %d)", who, W, H);
+    FSGM_REQUIRE(planes == 1 || planes == 2, "%s: planes must be 1 (a map) or 2 (a flow), got %d", who, planes);
     FSGM_REQUIRE(ratio >= 0 && ratio <= 100, "%s: ratio must be in [0, 100] (got %d)", who, ratio);
-    if ((double)n * W * H >= 2147483648.0)
-        return fail(FSGM_ERR_UNSUPPORTED, "%s: n_frames * width * height = %.0f reaches 2^31 (32-bit pixel indices)", who, (double)n * W * H);
-    const size_t np = (size_t)n * W * H;
-    FSGM_REQUIRE((const void*)out == (const void*)map || !ranges_overlap(out, np * 8, map, np * 8),
+    if ((double)n * planes * W * H >= 2147483648.0)
+        return fail(FSGM_ERR_UNSUPPORTED, "%s: n_frames * planes * width * height = %.0f reaches 2^31 (32-bit pixel indices)", who,
+                    (double)n * planes * W * H);
+    const size_t np = (size_t)n * W * H, nm = np * planes;
+    FSGM_REQUIRE((const void*)out == (const void*)map || !ranges_overlap(out, nm * 8, map, nm * 8),
                  "%s: out must be map itself or not overlap it", who);
-    FSGM_REQUIRE(!ranges_overlap(out, np * 8, minC, np * 4) && !ranges_overlap(out, np * 8, minC2, np * 4),
+    FSGM_REQUIRE(!ranges_overlap(out, nm * 8, minC, np * 4) && !ranges_overlap(out, nm * 8, minC2, np * 4),
                  "%s: out must not overlap minC or minC2", who);
     FSGM_DEVICE_SLOT(device);
     return FSGM_OK;
 }
 
-extern "C" {
+static void uniqueness_enqueue(hipStream_t st, const double* map, const uint32_t* minC, const uint32_t* minC2, double* out, size_t np,
+                               size_t frame_px, int planes, int ratio) {
+    if (planes == 2) launch_flow_uniqueness(st, map, minC, minC2, out, np, frame_px, ratio);
+    else launch_stereo_uniqueness(st, map, minC, minC2, out, np, ratio);
+}
 
-fsgm_status fsgm_uniqueness_filter_host(int32_t n, const double* map, const uint32_t* minC, const uint32_t* minC2, int32_t W, int32_t H,
-                                        int32_t ratio, double* out, int32_t device) {
-    const char* who = "fsgm_uniqueness_filter";
-    fsgm_status st = uniqueness_args(who, n, map, minC, minC2, W, H, ratio, out, device);
+// both host forms (the cached plan is that of n * planes maps: its map scratch holds every plane)
+static fsgm_status uniqueness_host(const char* who, int32_t n, const double* map, const uint32_t* minC, const uint32_t* minC2, int32_t W,
+                                   int32_t H, int32_t planes, int32_t ratio, double* out, int32_t device) {
+    fsgm_status st = uniqueness_args(who, n, map, minC, minC2, W, H, planes, ratio, out, device);
     if (st != FSGM_OK) return st;
-    const size_t np = (size_t)n * W * H;
+    const size_t np = (size_t)n * W * H, nm = np * planes;
     std::unique_lock<std::mutex> lk;
     fsgm_stereo_pp_plan* p;
-    if ((st = plan_get(lk, &p, W, H, n, device)) != FSGM_OK) return st;
-    uint32_t* c2 = (uint32_t*)p->dDisp;                          // (the chain's int32 disparity scratch: np words)
+    if ((st = plan_get(lk, &p, W, H, n * planes, device)) != FSGM_OK) return st;
+    uint32_t* c2 = (uint32_t*)p->dDisp;                          // (the chain's int32 disparity scratch: at least np words)
     StreamGuard guard(p->stream);   // an early exit drains the stream: queued copies use the caller's memory
-    FSGM_HIP(hipMemcpyAsync(p->dW, map, np * 8, hipMemcpyHostToDevice, p->stream));
+    FSGM_HIP(hipMemcpyAsync(p->dW, map, nm * 8, hipMemcpyHostToDevice, p->stream));
     FSGM_HIP(hipMemcpyAsync(p->dMinC, minC, np * 4, hipMemcpyHostToDevice, p->stream));
     FSGM_HIP(hipMemcpyAsync(c2, minC2, np * 4, hipMemcpyHostToDevice, p->stream));
-    launch_stereo_uniqueness(p->stream, p->dW, p->dMinC, c2, p->dW, np, ratio);
+    uniqueness_enqueue(p->stream, p->dW, p->dMinC, c2, p->dW, np, (size_t)W * H, planes, ratio);
     FSGM_HIP(hipGetLastError());
-    FSGM_HIP(hipMemcpyAsync(out, p->dW, np * 8, hipMemcpyDeviceToHost, p->stream));
+    FSGM_HIP(hipMemcpyAsync(out, p->dW, nm * 8, hipMemcpyDeviceToHost, p->stream));
     FSGM_HIP(hipStreamSynchronize(p->stream));
     guard.dismiss();
     return FSGM_OK;
 }
 
-fsgm_status fsgm_uniqueness_filter_device(int32_t n, const double* map, const uint32_t* minC, const uint32_t* minC2, int32_t W, int32_t H,
-                                          int32_t ratio, double* out, int32_t device, void* stream, int32_t* status) {
-    const char* who = "fsgm_uniqueness_filter_device";
-    fsgm_status st = uniqueness_args(who, n, map, minC, minC2, W, H, ratio, out, device);
+static fsgm_status uniqueness_device(const char* who, int32_t n, const double* map, const uint32_t* minC, const uint32_t* minC2, int32_t W,
+                                     int32_t H, int32_t planes, int32_t ratio, double* out, int32_t device, void* stream, int32_t* status) {
+    fsgm_status st = uniqueness_args(who, n, map, minC, minC2, W, H, planes, ratio, out, device);
     if (st != FSGM_OK) return st;
-    const size_t np = (size_t)n * W * H;
+    const size_t np = (size_t)n * W * H, nm = np * planes;
     hipStream_t cs = (hipStream_t)stream;
-    if ((st = device_check_args(who, device, cs, {{map, np * 8, 8, true, "map"},
+    if ((st = device_check_args(who, device, cs, {{map, nm * 8, 8, true, "map"},
                                                   {minC, np * 4, 4, true, "minC"},
                                                   {minC2, np * 4, 4, true, "minC2"},
-                                                  {out, np * 8, 8, true, "out"},
+                                                  {out, nm * 8, 8, true, "out"},
                                                   {status, 4, 4, false, "status"}})) != FSGM_OK)
         return st;
     std::unique_lock<std::mutex> lk;
     fsgm_stereo_pp_plan* p;
     if ((st = plan_get(lk, &p, W, H, n, device)) != FSGM_OK) return st;
     return device_call(p->join, cs, p->stream, [&] {
-        launch_stereo_uniqueness(p->stream, map, minC, minC2, out, np, ratio);
+        uniqueness_enqueue(p->stream, map, minC, minC2, out, np, (size_t)W * H, planes, ratio);
         if (status) launch_device_status(p->stream, nullptr, p->dNeg, status);   // (no flag is ever raised here: 0)
         return FSGM_OK;
     });
+}
+
+extern "C" {
+
+fsgm_status fsgm_uniqueness_filter_host(int32_t n, const double* map, const uint32_t* minC, const uint32_t* minC2, int32_t W, int32_t H,
+                                        int32_t ratio, double* out, int32_t device) {
+    return uniqueness_host("fsgm_uniqueness_filter", n, map, minC, minC2, W, H, 1, ratio, out, device);
+}
+
+fsgm_status fsgm_uniqueness_filter_device(int32_t n, const double* map, const uint32_t* minC, const uint32_t* minC2, int32_t W, int32_t H,
+                                          int32_t ratio, double* out, int32_t device, void* stream, int32_t* status) {
+    return uniqueness_device("fsgm_uniqueness_filter_device", n, map, minC, minC2, W, H, 1, ratio, out, device, stream, status);
+}
+
+fsgm_status fsgm_uniqueness_filter_planes_host(int32_t n, const double* map, const uint32_t* minC, const uint32_t* minC2, int32_t W,
+                                               int32_t H, int32_t planes, int32_t ratio, double* out, int32_t device) {
+    return uniqueness_host("fsgm_uniqueness_filter_planes", n, map, minC, minC2, W, H, planes, ratio, out, device);
+}
+
+fsgm_status fsgm_uniqueness_filter_planes_device(int32_t n, const double* map, const uint32_t* minC, const uint32_t* minC2, int32_t W,
+                                                 int32_t H, int32_t planes, int32_t ratio, double* out, int32_t device, void* stream,
+                                                 int32_t* status) {
+    return uniqueness_device("fsgm_uniqueness_filter_planes_device", n, map, minC, minC2, W, H, planes, ratio, out, device, stream, status);
 }
 
 fsgm_stereo_pp_params fsgm_stereo_pp_params_default(void) {

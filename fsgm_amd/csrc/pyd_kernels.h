@@ -47,6 +47,7 @@ struct PydWtaArgs {
     int ndirs;
     uint32_t weight[8];     // per slot: 1 for pass-0 paths, totalPass-1 for pass-1 paths
     int subpixel;
+    uint32_t* minC2;        // optional runner-up cost [frames][NP] (FSGM_NO_RUNNER_UP of include/fsgm.h); null: the kernels without it
 };
 
 // Volume layouts.  "rows": each of the Sx candidate rows padded to RS = 4*ceil(Sy/4) bytes, so one

@@ -310,6 +310,11 @@ __device__ __forceinline__ uint32_t pyd_sum_at(const PydWtaArgs& a, const uint8_
 }
 
 
+// RU: also the runner-up cost, the minimum of the sums at a Chebyshev distance >= 2 from the winner (include/fsgm.h), from a
+// second strided pass once the winner is known.  NK > 0 (windows of up to 64 * NK candidates): the first pass keeps the lane's
+// sums in NK registers and the second pass reads those; NK = 0: the second pass sums the path bytes again (16 sums a lane
+// would have to be kept at 1023 candidates; the bytes come from cache).
+template <bool RU, int NK>
 __global__ __launch_bounds__(256) void pyd_wta_kernel(PydWtaArgs a) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int NP = a.W * a.H, Sy = a.Sy, Sx = a.Sx, D = Sx * Sy;
@@ -320,10 +325,25 @@ __global__ __launch_bounds__(256) void pyd_wta_kernel(PydWtaArgs a) {
     const uint8_t* __restrict__ Lf = a.L + f * a.ndirs * vol;
     auto at = [&](uint32_t d) { return (size_t)p * a.PS + (d / Sy) * a.RS + d % Sy; };
     uint32_t lo = 0xFFFFFFFFu, idx = 0xFFFFFFFFu;
-    for (int d = lane; d < D; d += 64) {
-        const uint32_t s = pyd_sum_at(a, Lf, vol, at(d));
-        if (a.S) a.S[(f * NP + p) * D + d] = s;
-        if (s < lo) { lo = s; idx = d; }                     // ascending d per lane: first minimum
+    [[maybe_unused]] uint32_t keep[NK > 0 ? NK : 1];
+    if constexpr (NK > 0) {
+#pragma unroll
+        for (int i = 0; i < NK; i++) {
+            const int d = lane + 64 * i;
+            keep[i] = 0xFFFFFFFFu;                           // a lane without a candidate here: the identity
+            if (d < D) {
+                const uint32_t s = pyd_sum_at(a, Lf, vol, at(d));
+                if (a.S) a.S[(f * NP + p) * D + d] = s;
+                if (s < lo) { lo = s; idx = d; }
+                keep[i] = s;
+            }
+        }
+    } else {
+        for (int d = lane; d < D; d += 64) {
+            const uint32_t s = pyd_sum_at(a, Lf, vol, at(d));
+            if (a.S) a.S[(f * NP + p) * D + d] = s;
+            if (s < lo) { lo = s; idx = d; }                 // ascending d per lane: first minimum
+        }
     }
     uint32_t glo = lo;
 #pragma unroll
@@ -331,6 +351,25 @@ __global__ __launch_bounds__(256) void pyd_wta_kernel(PydWtaArgs a) {
     uint32_t gidx = lo == glo ? idx : 0xFFFFFFFFu;
 #pragma unroll
     for (int s = 32; s >= 1; s >>= 1) gidx = min(gidx, (uint32_t)__shfl_xor((int)gidx, s));
+    if constexpr (RU) {
+        const int bx = (int)gidx / Sy, by = (int)gidx - bx * Sy;
+        uint32_t c2 = 0xFFFFFFFFu;                           // FSGM_NO_RUNNER_UP: the identity of the minimum
+        if constexpr (NK > 0) {
+#pragma unroll
+            for (int i = 0; i < NK; i++) {
+                const int d = lane + 64 * i, sx = d / Sy, sy = d - sx * Sy;
+                if (max(abs(sx - bx), abs(sy - by)) >= 2) c2 = min(c2, keep[i]);      // (d >= D: keep[i] is the identity)
+            }
+        } else {
+            for (int d = lane; d < D; d += 64) {
+                const int sx = d / Sy, sy = d - sx * Sy;
+                if (max(abs(sx - bx), abs(sy - by)) >= 2) c2 = min(c2, pyd_sum_at(a, Lf, vol, at(d)));
+            }
+        }
+#pragma unroll
+        for (int s = 32; s >= 1; s >>= 1) c2 = min(c2, (uint32_t)__shfl_xor((int)c2, s));
+        if (lane == 0) a.minC2[f * NP + p] = c2;
+    }
     if (lane == 0) {
         a.bestD[f * NP + p] = gidx;
         a.minC[f * NP + p] = glo;
@@ -423,7 +462,9 @@ void launch_pyd_aggregate(hipStream_t st, const PydAggArgs& a, int frames, bool 
 void launch_pyd_wta(hipStream_t st, const PydWtaArgs& a, int frames) {
     if (pyd_rows_wta_ok(a)) { launch_pyd_rows_wta(st, a, frames); return; }
     dim3 grid((a.W * a.H + 3) / 4, frames);
-    hipLaunchKernelGGL(pyd_wta_kernel, grid, dim3(256), 0, st, a);
+    if (!a.minC2)                  hipLaunchKernelGGL((pyd_wta_kernel<false, 0>), grid, dim3(256), 0, st, a);
+    else if (a.Sx * a.Sy <= 256)   hipLaunchKernelGGL((pyd_wta_kernel<true, 4>), grid, dim3(256), 0, st, a);     // 3 of 4 kept at 13x13
+    else                           hipLaunchKernelGGL((pyd_wta_kernel<true, 0>), grid, dim3(256), 0, st, a);
 }
 
 }  // namespace fsgm

@@ -26,6 +26,10 @@ struct fsgm_pyd_plan {
     uint8_t* dIngest = nullptr;          // the caller's bytes as they came from the host, ahead of the ingest kernel
     uint32_t* dIngestFlag = nullptr;     // raised by the ingest kernel: some byte was above the declared bound
     double* dFlow = nullptr;             // hint + window offset + mvSub, f64 [batch][2][NP] (the host form's)
+    // the runner-up cost (fsgm_pyd_plan_set_runner_up): with the switch on the WTA also writes dMinC2, u32 [batch][NP], made on
+    // first use and all ones (FSGM_NO_RUNNER_UP) until a WTA has run; the cost and aggregation kernels do not depend on it
+    int runner_up = 0;
+    uint32_t* dMinC2 = nullptr;
     bool mv_zero = false;                // dMv holds zeros (aggregation-only plans: the hints of a call without preMv)
     fsgm::DeviceJoin join;               // the events of the plan's device calls
     const char* agg_name = "";           // the aggregation pyd_enqueue last queued: "rows", "rows/wide", "generic", "generic/wrap"

@@ -639,8 +639,11 @@ __global__ __launch_bounds__(256) void pyd_rows_agg_kernel(PydAggArgs a) {
 // WTA + y/x parabola  (calc_pyd_cost_sgm.cpp:298-364).  4 pixels per wave; lane j sums the path
 // costs of candidate row j (byte dot products over the directions), the first minimum in candidate
 // order is the minimum of (sum << 8 | index) keys.
+// RU: also the runner-up cost (include/fsgm.h) -- every lane of the group holds the winner's key, so a second pass over the lane's own
+// sums under the Chebyshev mask and a second group minimum give it.  The sums are u16 here, the marker FSGM_NO_RUNNER_UP is all ones:
+// reduced as u32 with the marker as identity, no sum can be taken for it.
 // =============================================================================================
-template <int NW>
+template <int NW, bool RU>
 __global__ __launch_bounds__(256) void pyd_rows_wta_kernel(PydWtaArgs a) {
     constexpr int PIXDW = 16 * 2 * NW + 1;                 // LDS dwords per pixel: 16 candidate rows of 4*NW u16 sums; odd, so
     __shared__ uint32_t sSum[4 * 4 * PIXDW];               // that the wave's four pixels sit in different banks
@@ -697,6 +700,17 @@ __global__ __launch_bounds__(256) void pyd_rows_wta_kernel(PydWtaArgs a) {
         }
     }
     key = group_min_u32<16>(key);
+    if constexpr (RU) {
+        const int gi = (int)(key & 0xFFu);
+        const int bx = (int)(((uint32_t)gi * ((1u << 20) / (uint32_t)Sy + 1u)) >> 20), by = gi - bx * Sy;   // gi / Sy, as below
+        const bool far_x = abs(j - bx) >= 2;
+        uint32_t c2 = 0xFFFFFFFFu;
+#pragma unroll
+        for (int s = 0; s < 4 * NW; s++)
+            if (s < Sy && j < Sx && (far_x || abs(s - by) >= 2)) c2 = min(c2, S[s]);
+        c2 = group_min_u32<16>(c2);
+        if (j == 0 && active) a.minC2[f * NP + p] = c2;
+    }
     __builtin_amdgcn_wave_barrier();
     if (j < 2 && active) {                                   // lane 0: outputs and the y parabola, lane 1: the x parabola
         const uint32_t gidx = key & 0xFFu, glo = key >> 8;
@@ -763,7 +777,8 @@ void launch_pyd_rows_aggregate(hipStream_t st, const PydAggArgs& a, int frames) 
 
 void launch_pyd_rows_wta(hipStream_t st, const PydWtaArgs& a, int frames) {
     dim3 grid((unsigned)((a.W * a.H + 15) / 16), frames);
-    FSGM_ROWS_DISPATCH(a.RS / 4, hipLaunchKernelGGL((pyd_rows_wta_kernel<NW>), grid, dim3(256), 0, st, a));
+    if (a.minC2) FSGM_ROWS_DISPATCH(a.RS / 4, hipLaunchKernelGGL((pyd_rows_wta_kernel<NW, true>), grid, dim3(256), 0, st, a));
+    else         FSGM_ROWS_DISPATCH(a.RS / 4, hipLaunchKernelGGL((pyd_rows_wta_kernel<NW, false>), grid, dim3(256), 0, st, a));
 }
 
 }  // namespace fsgm

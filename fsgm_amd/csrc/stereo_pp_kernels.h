@@ -32,5 +32,9 @@ void launch_stereo_pack(hipStream_t st, const double* filled, const double* chec
 // out = NaN where (u64)minC2 * (100 - ratio) < (u64)minC * 100, map elsewhere.  out may be map itself, nothing else may overlap
 void launch_stereo_uniqueness(hipStream_t st, const double* map, const uint32_t* minC, const uint32_t* minC2, double* out, size_t n_px,
                               int ratio);
+// the same on a two-plane flow: map, out f64 [n][2][frame_px], minC, minC2 u32 [n][frame_px], n_px = n * frame_px; both planes of a
+// rejected pixel become NaN
+void launch_flow_uniqueness(hipStream_t st, const double* map, const uint32_t* minC, const uint32_t* minC2, double* out, size_t n_px,
+                            size_t frame_px, int ratio);
 
 }  // namespace fsgm

@@ -122,6 +122,22 @@ __global__ __launch_bounds__(256) void stereo_uniqueness_kernel(const double* ma
     }
 }
 
+// The same test for a two-plane flow, map and out [n][2][frame_px], minC and minC2 [n][frame_px]: both planes of a rejected pixel
+// become NaN.  One lane a pixel; it reads both of the pixel's values before it writes either, so out may be map itself.
+__global__ __launch_bounds__(256) void flow_uniqueness_kernel(const double* map, const uint32_t* __restrict__ minC,
+                                                              const uint32_t* __restrict__ minC2, double* out, size_t n_px,
+                                                              size_t frame_px, uint32_t keep) {
+    const size_t stride = (size_t)gridDim.x * 256;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n_px; i += stride) {
+        const uint32_t c = minC[i], c2 = minC2[i];
+        const bool reject = c2 != 0xFFFFFFFFu && (uint64_t)c2 * keep < (uint64_t)c * 100u;
+        const size_t f = i / frame_px, at = i + f * frame_px;                 // f * 2 * frame_px + the pixel's index in its frame
+        const double vx = map[at], vy = map[at + frame_px];
+        out[at] = reject ? __builtin_nan("") : vx;
+        out[at + frame_px] = reject ? __builtin_nan("") : vy;
+    }
+}
+
 // launchers: the frame index of a grid stays within 65535, more frames (tiny maps only) take one launch per 65535
 constexpr int STEREO_MAX_GRID_FRAMES = 65535;
 
@@ -154,6 +170,13 @@ void launch_stereo_uniqueness(hipStream_t st, const double* map, const uint32_t*
     const size_t blocks = (n_px + 255) / 256;                    // grid-stride: at most 8 blocks for each of 256 CUs
     hipLaunchKernelGGL(stereo_uniqueness_kernel, dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(256), 0, st, map, minC, minC2, out,
                        n_px, (uint32_t)(100 - ratio));
+}
+
+void launch_flow_uniqueness(hipStream_t st, const double* map, const uint32_t* minC, const uint32_t* minC2, double* out, size_t n_px,
+                            size_t frame_px, int ratio) {
+    const size_t blocks = (n_px + 255) / 256;
+    hipLaunchKernelGGL(flow_uniqueness_kernel, dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(256), 0, st, map, minC, minC2, out,
+                       n_px, frame_px, (uint32_t)(100 - ratio));
 }
 
 }  // namespace fsgm

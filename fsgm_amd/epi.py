@@ -259,26 +259,36 @@ def stereo_last_kernel():
 NO_RUNNER_UP = 0xFFFFFFFF                                      # FSGM_NO_RUNNER_UP
 
 
-def uniqueness_filter(map, minC, minC2, ratio, *, device=0):
+def uniqueness_filter(map, minC, minC2, ratio, *, device=0, planes=1):
     """OpenCV's uniquenessRatio on the matcher's own costs: map float64 (values or NaN), minC and minC2 uint32
     (stereo_sgm(runner_up=True)'s, or EpiPlan.download() / download_runner_up()), all (height, width) or (N, height, width).
     Returns map with NaN where minC2 != NO_RUNNER_UP and minC2 * (100 - ratio) < minC * 100 (64-bit products); ratio is an
-    integer in [0, 100], 0 rejects nothing."""
+    integer in [0, 100], 0 rejects nothing.  planes=2: map is a flow, (2, height, width) or (N, 2, height, width) next to costs
+    of (height, width) / (N, height, width) -- sgm2d_batch(runner_up=True)'s -- and both planes of a rejected pixel become NaN."""
+    if isinstance(planes, bool) or planes not in (1, 2):
+        raise ValueError(f"planes must be 1 or 2 (got {planes!r})")
     m = np.ascontiguousarray(map)
-    if m.dtype != np.float64 or m.ndim not in (2, 3):
+    if planes == 2:
+        if m.dtype != np.float64 or m.ndim not in (3, 4) or m.shape[-3] != 2:
+            raise TypeError(f"map must be a float64 flow (2, height, width) or (N, 2, height, width) with planes=2 (got {m.dtype} {m.shape})")
+    elif m.dtype != np.float64 or m.ndim not in (2, 3):
         raise TypeError(f"map must be a float64 array (height, width) or (N, height, width) (got {m.dtype} {m.shape})")
+    cshape = m.shape if planes == 1 else m.shape[:-3] + m.shape[-2:]
     c, c2 = np.ascontiguousarray(minC), np.ascontiguousarray(minC2)
     for name, a in (("minC", c), ("minC2", c2)):
-        if a.dtype != np.uint32 or a.shape != m.shape:
-            raise TypeError(f"{name} must be uint32 of map's shape {m.shape} (got {a.dtype} {a.shape})")
+        if a.dtype != np.uint32 or a.shape != cshape:
+            raise TypeError(f"{name} must be uint32 of map's shape {cshape} (got {a.dtype} {a.shape})")
     if isinstance(ratio, bool) or int(ratio) != ratio or not 0 <= int(ratio) <= 100:
         raise ValueError(f"ratio must be an integer in [0, 100] (got {ratio!r})")
     if m.size == 0:
         raise ValueError("empty map")
     H, W = m.shape[-2:]
     out = np.empty_like(m)
-    check(_lib.load().fsgm_uniqueness_filter_host(1 if m.ndim == 2 else m.shape[0], ptr(m), ptr(c), ptr(c2), W, H, int(ratio), ptr(out),
-                                                  int(device)))
+    n = 1 if c.ndim == 2 else c.shape[0]
+    if planes == 2:
+        check(_lib.load().fsgm_uniqueness_filter_planes_host(n, ptr(m), ptr(c), ptr(c2), W, H, 2, int(ratio), ptr(out), int(device)))
+    else:
+        check(_lib.load().fsgm_uniqueness_filter_host(n, ptr(m), ptr(c), ptr(c2), W, H, int(ratio), ptr(out), int(device)))
     return out
 
 

@@ -42,6 +42,10 @@ def _bind(lib):
     lib.fsgm_pyd_plan_time.argtypes = [vp, i32, i32, i32, C.POINTER(C.c_float)]
     u64p = C.POINTER(C.c_uint64)
     lib.fsgm_pyd_launch_lds.argtypes = [i32, i32, i32, C.POINTER(i32), u64p, u64p, u64p, u64p]
+    if hasattr(lib, "fsgm_pyd_plan_set_runner_up"):              # (an older build behind FSGM_LIB_PATH has none)
+        lib.fsgm_pyd_plan_set_runner_up.argtypes = [vp, i32]
+        lib.fsgm_pyd_plan_download_runner_up.argtypes = [vp, i32, vp]
+        lib.fsgm_calc_pyd_cost_sgm_batch_host_ru.argtypes = [i32, C.POINTER(PydIn), C.POINTER(PydOut), C.POINTER(vp), i32]
     lib._pyd_bound = True
 
 
@@ -75,10 +79,12 @@ def _check_inputs(I1, I2, preMv):
 
 
 def calc_pyd_cost_sgm(I1, I2, preMv, halfSearchWinSizeX, halfSearchWinSizeY, aggHalfWinSize, subPixelRefine,
-                      P1, P2, enableDiagnalPath, totalPass, adpativeP2, *, device=0, return_volumes=False):
+                      P1, P2, enableDiagnalPath, totalPass, adpativeP2, *, device=0, return_volumes=False,
+                      runner_up=False):
     """[bestD, minC, mvSub] = calc_pyd_cost_sgm(I1, I2, preMv, halfSearchWinSizeX, halfSearchWinSizeY,
     aggHalfWinSize, subPixelRefine, P1, P2, enableDiagnalPath, totalPass, adpativeP2) -- the MEX's
-    12 arguments in order."""
+    12 arguments in order.  runner_up=True appends minC2 uint32 (height, width) to the tuple: the smallest sum at a Chebyshev
+    distance >= 2 from the winner in the search window, NO_RUNNER_UP where the window holds no such candidate."""
     lib = _lib.load()
     _bind(lib)
     I1, I2, preMv = _check_inputs(I1, I2, preMv)
@@ -101,21 +107,30 @@ def calc_pyd_cost_sgm(I1, I2, preMv, halfSearchWinSizeX, halfSearchWinSizeY, agg
     S = np.zeros((H, W, D), np.uint32) if return_volumes else None
     o = PydOut()
     o.bestD, o.minC, o.mvSub, o.C, o.S = ptr(bestD), ptr(minC), ptr(mvSub), ptr(Cv), ptr(S)
+    if runner_up:
+        minC2 = np.zeros((H, W), np.uint32)
+        check(lib.fsgm_calc_pyd_cost_sgm_batch_host_ru(1, C.byref(a), C.byref(o), (C.c_void_p * 1)(ptr(minC2)), int(device)))
+        return ((bestD, minC, mvSub, Cv, S) if return_volumes else (bestD, minC, mvSub)) + (minC2,)
     check(lib.fsgm_calc_pyd_cost_sgm_host(C.byref(a), C.byref(o), int(device)))
     return (bestD, minC, mvSub, Cv, S) if return_volumes else (bestD, minC, mvSub)
 
 
 def calc_pyd_cost_sgm_batch(frames, halfSearchWinSizeX, halfSearchWinSizeY, aggHalfWinSize, subPixelRefine,
-                            P1, P2, enableDiagnalPath, totalPass, adpativeP2, *, device=0, devices=None):
+                            P1, P2, enableDiagnalPath, totalPass, adpativeP2, *, device=0, devices=None,
+                            runner_up=False):
     """frames: list of (I1, I2, preMv) of one shape and one parameter set, processed together; returns a list of
     (bestD, minC, mvSub).  devices: a device list -- frame i runs on devices[i % len(devices)], one host thread per entry
-    inside the library, no collective (fsgm_calc_pyd_cost_sgm_batch_devices_host)."""
+    inside the library, no collective (fsgm_calc_pyd_cost_sgm_batch_devices_host).  runner_up=True appends minC2 to each
+    tuple (one device only)."""
     lib = _lib.load()
     _bind(lib)
     n = len(frames)
     if n == 0:
         return []
+    if runner_up and devices is not None:
+        raise ValueError("runner_up=True runs on one device: pass device=, not devices=")
     ins, outs, keep, res = (PydIn * n)(), (PydOut * n)(), [], []
+    m2 = (C.c_void_p * n)()
     for i, (I1, I2, preMv) in enumerate(frames):
         I1, I2, preMv = _check_inputs(I1, I2, preMv)
         H, W = I1.shape
@@ -129,10 +144,17 @@ def calc_pyd_cost_sgm_batch(frames, halfSearchWinSizeX, halfSearchWinSizeY, aggH
         o = outs[i]
         o.bestD, o.minC, o.mvSub, o.C, o.S = ptr(bestD), ptr(minC), ptr(mvSub), None, None
         keep.append((I1, I2, preMv))
-        res.append((bestD, minC, mvSub))
+        if runner_up:
+            minC2 = np.zeros((H, W), np.uint32)
+            m2[i] = minC2.ctypes.data
+            res.append((bestD, minC, mvSub, minC2))
+        else:
+            res.append((bestD, minC, mvSub))
     if devices is not None:
         nd, darr = _lib.device_array(devices)
         check(lib.fsgm_calc_pyd_cost_sgm_batch_devices_host(n, ins, outs, nd, darr))
+    elif runner_up:
+        check(lib.fsgm_calc_pyd_cost_sgm_batch_host_ru(n, ins, outs, m2, int(device)))
     else:
         check(lib.fsgm_calc_pyd_cost_sgm_batch_host(n, ins, outs, int(device)))
     return res
@@ -172,6 +194,16 @@ class PydPlan:
     def set_params(self, P1, P2, diagonal=1, totalPass=2, adaptiveP2=0, subpixel=0):
         check(self.lib.fsgm_pyd_plan_set_params(self._h, int(P1), int(P2), int(diagonal), int(totalPass),
                                                 int(adaptiveP2), int(subpixel)))
+
+    def set_runner_up(self, on):
+        """The WTA also writes the runner-up cost (download_runner_up) on / off; no other kernel or output changes."""
+        check(self.lib.fsgm_pyd_plan_set_runner_up(self._h, int(on)))
+
+    def download_runner_up(self, frame):
+        """minC2 uint32 (H, W) of the last WTA with the switch on (all NO_RUNNER_UP before one); FsgmError while it is off."""
+        minC2 = np.empty((self.H, self.W), np.uint32)
+        check(self.lib.fsgm_pyd_plan_download_runner_up(self._h, frame, ptr(minC2)))
+        return minC2
 
     def upload(self, frame, I1, I2, preMv):
         I1, I2, preMv = _check_inputs(I1, I2, preMv)

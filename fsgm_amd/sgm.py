@@ -20,6 +20,9 @@ def _bind(lib):
     lib.fsgm_sgm_params_default.restype = SgmParams
     lib.fsgm_sgm_batch_host.argtypes = [i32, vp, i32, i32, i32, i32, i32, C.POINTER(SgmParams), vp, vp, vp, vp]
     lib.fsgm_sgm_device.argtypes = [i32, vp, i32, i32, i32, i32, i32, C.POINTER(SgmParams), vp, vp, vp, vp, vp, vp]
+    if hasattr(lib, "fsgm_sgm_batch_host_ru"):                   # (an older build behind FSGM_LIB_PATH has none): minC2 after minC
+        lib.fsgm_sgm_batch_host_ru.argtypes = [i32, vp, i32, i32, i32, i32, i32, C.POINTER(SgmParams), vp, vp, vp, vp, vp]
+        lib.fsgm_sgm_device_ru.argtypes = [i32, vp, i32, i32, i32, i32, i32, C.POINTER(SgmParams), vp, vp, vp, vp, vp, vp, vp]
     lib.fsgm_sgm_last_kernel.restype = C.c_char_p
     lib.fsgm_sgm_ingest_lds.argtypes = [i32, i32, C.POINTER(C.c_uint64)]
     lib.fsgm_epi_plan_ingest_cost_device.argtypes = [vp, i32, vp, i32, i32, vp, vp]
@@ -62,13 +65,15 @@ def ingest_lds(layout, dMax):
 
 
 def sgm_batch(Cvol, P1=7, P2=100, *, paths=4, layout="hwd", cost_bound=255, agg_mode=0, adaptive_p2=0, guide=None, subpixel=1,
-              return_sum=False, device=0):
+              return_sum=False, device=0, runner_up=False):
     """[bestD, minC] = sgm(C, P1, P2) (fsgm_amd.sgm) on a batch of volumes in one call, through one cached plan of that batch:
     C uint8 (N, H, W, D) for layout "hwd" or (N, D, H, W) for "dhw" (a cost-volume network's output; transposed on the device);
     one volume without the leading N.  bestD, minC uint32 (N, H, W); return_sum adds S uint32 (N, H, W, D).
     cost_bound (1..255): no cost is larger -- small bounds open the fused pipelines, as census costs do; a volume above a bound
     below 255 is refused (status 1).  agg_mode: EpiPlan.set_agg_mode's.  adaptive_p2=1 reads the edge-aware P2 from guide, the
-    first image, uint8 (N, H, W)."""
+    first image, uint8 (N, H, W).  runner_up=True (fsgm_sgm_batch_host_ru) returns minC2 uint32 (N, H, W) after minC, the
+    runner-up cost min { S[d] : |d - best| >= 2 } (NO_RUNNER_UP where no such d exists): such a call runs the line kernels at
+    every batch size (last_kernel() shows it), and agg_mode 2..6 with it is refused (status 4)."""
     lib = _bind(_lib.load())
     code = layout_code(layout)
     Cvol = np.ascontiguousarray(Cvol)
@@ -85,6 +90,11 @@ def sgm_batch(Cvol, P1=7, P2=100, *, paths=4, layout="hwd", cost_bound=255, agg_
     assert prm.layout == code
     bestD, minC = np.empty((N, H, W), np.uint32), np.empty((N, H, W), np.uint32)
     S = np.empty((N, H, W, D), np.uint32) if return_sum else None
-    check(lib.fsgm_sgm_batch_host(N, ptr(Cvol), W, H, D, int(P1), int(P2), C.byref(prm), ptr(guide), ptr(bestD), ptr(minC), ptr(S)))
-    outs = (bestD, minC, S) if return_sum else (bestD, minC)
+    minC2 = np.empty((N, H, W), np.uint32) if runner_up else None
+    if runner_up:
+        check(lib.fsgm_sgm_batch_host_ru(N, ptr(Cvol), W, H, D, int(P1), int(P2), C.byref(prm), ptr(guide), ptr(bestD), ptr(minC),
+                                         ptr(minC2), ptr(S)))
+    else:
+        check(lib.fsgm_sgm_batch_host(N, ptr(Cvol), W, H, D, int(P1), int(P2), C.byref(prm), ptr(guide), ptr(bestD), ptr(minC), ptr(S)))
+    outs = (bestD, minC) + ((minC2,) if runner_up else ()) + ((S,) if return_sum else ())
     return outs if n is not None else tuple(o[0] for o in outs)

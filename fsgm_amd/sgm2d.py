@@ -22,6 +22,9 @@ def _bind(lib):
     head = [i32, vp, i32, i32, i32, i32, i32, i32, C.POINTER(Sgm2dParams), vp, i32, i32, vp, vp, vp, vp, vp, vp]
     lib.fsgm_sgm2d_batch_host.argtypes = head
     lib.fsgm_sgm2d_device.argtypes = head + [vp, vp]
+    if hasattr(lib, "fsgm_sgm2d_batch_host_ru"):                 # (an older build behind FSGM_LIB_PATH has none): minC2 after minC
+        lib.fsgm_sgm2d_batch_host_ru.argtypes = head[:15] + [vp] + head[15:]
+        lib.fsgm_sgm2d_device_ru.argtypes = head[:15] + [vp] + head[15:] + [vp, vp]
     lib.fsgm_sgm2d_last_kernel.restype = C.c_char_p
     lib.fsgm_sgm2d_ingest_lds.argtypes = [i32, i32, i32, C.POINTER(C.c_uint64)]
     lib.fsgm_pyd_plan_ingest_cost_device.argtypes = [vp, i32, vp, i32, i32, vp, vp]
@@ -72,15 +75,18 @@ def ingest_lds(layout, half_x, half_y):
 
 
 def sgm2d_batch(costs, half_x, half_y, P1=6, P2=32, *, layout="dhw", hints=None, guide=None, cost_bound=255, diagonal=1, total_pass=2,
-                adaptive_p2=0, subpixel=1, return_flow=False, return_sum=False, device=0):
-    """(bestD, minC, mvSub[, flow][, S]) of the 2-D matcher on cost volumes the caller made: costs uint8 (N, D, H, W) for layout
+                adaptive_p2=0, subpixel=1, return_flow=False, return_sum=False, device=0, runner_up=False):
+    """(bestD, minC[, minC2], mvSub[, flow][, S]) of the 2-D matcher on cost volumes the caller made: costs uint8 (N, D, H, W) for layout
     "dhw" (channel sx*Sy + sy, the reference's candidate order) or "dhw_yx" (channel sy*Sx + sx, the y-slow order correlation
     layers emit), (N, H, W, D) for "hwd" (candidate index sx*Sy + sy); one volume without the leading N.  The window is
     Sx x Sy = (2*half_x+1) x (2*half_y+1), candidate (sx, sy) the displacement (sx - half_x, sy - half_y) added to the hint.
     hints float64 (N, 2, mvH, mvW), at least as large as the image (None: zeros); guide uint8 (N, H, W), the first image, read
     with adaptive_p2=1.  bestD (the index sx*Sy + sy in every layout), minC uint32 (N, H, W); mvSub, flow float64 (N, 2, H, W),
     flow = hint + window offset + mvSub; S uint32 (N, H, W, D).  cost_bound (1..255): no cost is larger -- with
-    cost_bound + P2 + max(P1, P2) <= 255 the non-wrapping kernels run; a volume above a bound below 255 is refused (status 1)."""
+    cost_bound + P2 + max(P1, P2) <= 255 the non-wrapping kernels run; a volume above a bound below 255 is refused (status 1).
+    runner_up=True (fsgm_sgm2d_batch_host_ru) returns minC2 uint32 (N, H, W) after minC: the smallest sum at a Chebyshev distance
+    >= 2 from the winner, NO_RUNNER_UP where the window holds no such candidate -- what uniqueness_filter(flow, minC, minC2, ratio,
+    planes=2) takes; every other output is that of the call without it."""
     lib = _bind(_lib.load())
     layout_code(layout)
     costs = np.ascontiguousarray(costs)
@@ -107,7 +113,12 @@ def sgm2d_batch(costs, half_x, half_y, P1=6, P2=32, *, layout="dhw", hints=None,
     mvSub = np.empty((N, 2, H, W), np.float64)
     flow = np.empty((N, 2, H, W), np.float64) if return_flow else None
     S = np.empty((N, H, W, D), np.uint32) if return_sum else None
-    check(lib.fsgm_sgm2d_batch_host(N, ptr(costs), W, H, int(half_x), int(half_y), int(P1), int(P2), C.byref(prm), ptr(hints), mvW, mvH,
-                                    ptr(guide), ptr(bestD), ptr(minC), ptr(mvSub), ptr(flow), ptr(S)))
-    outs = (bestD, minC, mvSub) + ((flow,) if return_flow else ()) + ((S,) if return_sum else ())
+    minC2 = np.empty((N, H, W), np.uint32) if runner_up else None
+    if runner_up:
+        check(lib.fsgm_sgm2d_batch_host_ru(N, ptr(costs), W, H, int(half_x), int(half_y), int(P1), int(P2), C.byref(prm), ptr(hints), mvW,
+                                           mvH, ptr(guide), ptr(bestD), ptr(minC), ptr(minC2), ptr(mvSub), ptr(flow), ptr(S)))
+    else:
+        check(lib.fsgm_sgm2d_batch_host(N, ptr(costs), W, H, int(half_x), int(half_y), int(P1), int(P2), C.byref(prm), ptr(hints), mvW,
+                                        mvH, ptr(guide), ptr(bestD), ptr(minC), ptr(mvSub), ptr(flow), ptr(S)))
+    outs = (bestD, minC) + ((minC2,) if runner_up else ()) + (mvSub,) + ((flow,) if return_flow else ()) + ((S,) if return_sum else ())
     return outs if n is not None else tuple(o[0] for o in outs)

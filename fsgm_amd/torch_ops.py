@@ -13,7 +13,9 @@ fsgm::epipolar_sgm_of, fsgm::pyramidal_sgm, fsgm::pyramidal_sgm_ng, fsgm::epipol
 status tensor: 0, or FSGM_ERR_HIP when an aggregation hand-off gave up; check=True in the wrappers synchronises and raises
 on it), fsgm::epi_postprocess (status FSGM_ERR_INVALID when a D1 value is negative), fsgm::vmf and fsgm::flow_fb_check; for rectified
 stereo fsgm::stereo_sgm_pp (the matcher and the chain of test.m:45-50) and fsgm::stereo_fb_check (status as fsgm::epi_postprocess),
-fsgm::stereo_sgm_ru (fsgm::stereo_sgm_range with the runner-up cost minC2 after minC) and fsgm::uniqueness_filter (status always 0).
+fsgm::stereo_sgm_ru (fsgm::stereo_sgm_range with the runner-up cost minC2 after minC) and fsgm::uniqueness_filter (status always 0);
+fsgm::sgm_ru and fsgm::sgm2d_ru (fsgm::sgm / fsgm::sgm2d with minC2 after minC) and fsgm::uniqueness_filter_planes (a map or a
+two-plane flow; status always 0).
 
 One process must hold one HIP runtime.  torch brings its own libamdhip64; libfsgm_hip.so binds to it by soname when torch is
 imported first.  When the library was loaded first, torch afterwards maps a second runtime, and a stream or pointer of one
@@ -276,6 +278,30 @@ def _(C_, guide, P1, P2, paths, layout, cost_bound, agg_mode, adaptive_p2, subpi
     return _sgm_outputs(C_, layout, return_sum)
 
 
+@torch.library.custom_op("fsgm::sgm_ru", mutates_args=())
+def _sgm_ru_op(C_: torch.Tensor, guide: torch.Tensor, P1: int, P2: int, paths: int, layout: int, cost_bound: int, agg_mode: int,
+               adaptive_p2: int, subpixel: int, return_sum: int
+               ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """fsgm::sgm with the runner-up cost minC2 after minC (fsgm_sgm_device_ru): (bestD, minC, minC2, S, status)"""
+    N, H, W, D = _sgm_out_shape(C_, layout)
+    dev = C_.device
+    C_ = C_.contiguous()
+    guide = guide.contiguous() if adaptive_p2 else None
+    bestD, minC, S, status = _sgm_outputs(C_, layout, return_sum)
+    minC2 = torch.empty_like(minC)
+    prm = _sgm_params(_L, paths=paths, subpixel=subpixel, device=dev.index, agg_mode=agg_mode, layout="dhw" if layout else "hwd",
+                      cost_bound=cost_bound, adaptive_p2=adaptive_p2)
+    _call(dev, _L.fsgm_sgm_device_ru, N, _p(C_), W, H, D, int(P1), int(P2), C.byref(prm), _p(guide), _p(bestD), _p(minC), _p(minC2),
+          _p(S) if return_sum else None, _stream(dev), _p(status))
+    return bestD, minC, minC2, S, status
+
+
+@_sgm_ru_op.register_fake
+def _(C_, guide, P1, P2, paths, layout, cost_bound, agg_mode, adaptive_p2, subpixel, return_sum):
+    bestD, minC, S, status = _sgm_outputs(C_, layout, return_sum)
+    return bestD, minC, torch.empty_like(minC), S, status
+
+
 def _sgm2d_out_shape(C_, layout, half_x, half_y):
     if layout not in (0, 1, 2):
         raise ValueError(f"layout must be 0 (hwd), 1 (dhw) or 2 (dhw_yx), got {layout}")
@@ -318,6 +344,35 @@ def _sgm2d_op(C_: torch.Tensor, hints: torch.Tensor, guide: torch.Tensor, half_x
 @_sgm2d_op.register_fake
 def _(C_, hints, guide, half_x, half_y, P1, P2, layout, cost_bound, diagonal, total_pass, adaptive_p2, subpixel, return_flow, return_sum):
     return _sgm2d_outputs(C_, layout, half_x, half_y, return_flow, return_sum)
+
+
+@torch.library.custom_op("fsgm::sgm2d_ru", mutates_args=())
+def _sgm2d_ru_op(C_: torch.Tensor, hints: torch.Tensor, guide: torch.Tensor, half_x: int, half_y: int, P1: int, P2: int, layout: int,
+                 cost_bound: int, diagonal: int, total_pass: int, adaptive_p2: int, subpixel: int, return_flow: int, return_sum: int
+                 ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """fsgm::sgm2d with the runner-up cost minC2 after minC (fsgm_sgm2d_device_ru): (bestD, minC, minC2, mvSub, flow, S, status)"""
+    N, H, W, D = _sgm2d_out_shape(C_, layout, half_x, half_y)
+    dev = C_.device
+    if not C_.is_contiguous():
+        raise TypeError("fsgm::sgm2d_ru reads the costs where they lie: pass a contiguous tensor")
+    have_hints = hints.numel() != 0
+    hints = _ready(hints) if have_hints else None
+    mvH, mvW = (hints.shape[-2], hints.shape[-1]) if have_hints else (0, 0)
+    guide = guide.contiguous() if adaptive_p2 else None
+    bestD, minC, mvSub, flow, S, status = _sgm2d_outputs(C_, layout, half_x, half_y, return_flow, return_sum)
+    minC2 = torch.empty_like(minC)
+    prm = _sgm2d_params(_L, diagonal=diagonal, total_pass=total_pass, adaptive_p2=adaptive_p2, subpixel=subpixel, device=dev.index,
+                        layout=[k for k, v in _LAYOUTS2D.items() if v == layout][0], cost_bound=cost_bound)
+    _call(dev, _L.fsgm_sgm2d_device_ru, N, _p(C_), W, H, int(half_x), int(half_y), int(P1), int(P2), C.byref(prm), _p(hints), int(mvW),
+          int(mvH), _p(guide), _p(bestD), _p(minC), _p(minC2), _p(mvSub), _p(flow) if return_flow else None,
+          _p(S) if return_sum else None, _stream(dev), _p(status))
+    return bestD, minC, minC2, mvSub, flow, S, status
+
+
+@_sgm2d_ru_op.register_fake
+def _(C_, hints, guide, half_x, half_y, P1, P2, layout, cost_bound, diagonal, total_pass, adaptive_p2, subpixel, return_flow, return_sum):
+    bestD, minC, mvSub, flow, S, status = _sgm2d_outputs(C_, layout, half_x, half_y, return_flow, return_sum)
+    return bestD, minC, torch.empty_like(minC), mvSub, flow, S, status
 
 
 def _epipolar_sgm_of_outputs(I0):
@@ -575,6 +630,19 @@ def _(left, right, dMax, d_min, P1, P2, paths, subpixel, direction, fb_check, ad
     return _stereo_sgm_ru_outputs(left, fb_check)
 
 
+def _uniqueness_planes_check(map_, minC, minC2, planes):
+    """the raw op's own shape check: the kernel indexes N * planes * H * W elements of map_ and N * H * W of the costs"""
+    if planes not in (1, 2):
+        raise ValueError(f"fsgm::uniqueness_filter_planes: planes must be 1 or 2 (got {planes})")
+    if minC.dim() != 3 or tuple(minC2.shape) != tuple(minC.shape):
+        raise TypeError(f"fsgm::uniqueness_filter_planes: minC and minC2 must be (N, H, W) of one shape (got {tuple(minC.shape)}, "
+                        f"{tuple(minC2.shape)})")
+    N, H, W = minC.shape
+    want = (N, H, W) if planes == 1 else (N, 2, H, W)
+    if tuple(map_.shape) != want:
+        raise TypeError(f"fsgm::uniqueness_filter_planes: map_ must be {want} with planes {planes} (got {tuple(map_.shape)})")
+
+
 def _uniqueness_filter_outputs(map_):
     return torch.empty_like(map_, memory_format=torch.contiguous_format), _status(map_.device)
 
@@ -591,6 +659,25 @@ def _uniqueness_filter_op(map_: torch.Tensor, minC: torch.Tensor, minC2: torch.T
 
 @_uniqueness_filter_op.register_fake
 def _(map_, minC, minC2, ratio):
+    return _uniqueness_filter_outputs(map_)
+
+
+@torch.library.custom_op("fsgm::uniqueness_filter_planes", mutates_args=())
+def _uniqueness_filter_planes_op(map_: torch.Tensor, minC: torch.Tensor, minC2: torch.Tensor, ratio: int,
+                                 planes: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """map_ (N, H, W) with planes 1, (N, 2, H, W) with planes 2; minC, minC2 (N, H, W)"""
+    _uniqueness_planes_check(map_, minC, minC2, planes)
+    N, H, W, dev = _frames(minC)
+    map_, minC, minC2 = _ready(map_), _ready(minC), _ready(minC2)
+    out, status = _uniqueness_filter_outputs(map_)
+    _call(dev, _L.fsgm_uniqueness_filter_planes_device, N, _p(map_), _p(minC), _p(minC2), W, H, int(planes), int(ratio), _p(out), dev.index,
+          _stream(dev), _p(status))
+    return out, status
+
+
+@_uniqueness_filter_planes_op.register_fake
+def _(map_, minC, minC2, ratio, planes):
+    _uniqueness_planes_check(map_, minC, minC2, planes)
     return _uniqueness_filter_outputs(map_)
 
 
@@ -680,14 +767,15 @@ def calc_cost_sgm_linear(I1, I2, dMax, pixelPosD0, normlizeDirection, P1, P2, *,
 
 
 def sgm(Cvol, P1=7, P2=100, *, layout="dhw", paths=4, cost_bound=255, agg_mode=0, adaptive_p2=0, guide=None, subpixel=1,
-        return_sum=False, check=False, return_status=False):
+        return_sum=False, check=False, return_status=False, runner_up=False):
     """bestD, minC = sgm(C, P1, P2) as fsgm_amd.sgm_batch, on a cost volume that is already in HBM: C uint8 (D, H, W) or a batch
     (N, D, H, W) for layout "dhw" (a cost-volume network's output), (H, W, D) / (N, H, W, D) for "hwd".  The volume is read where
     it lies, every output stays in HBM, the work is queued on the current stream.  bestD, minC uint32 (.., H, W); return_sum
     adds S uint32 (.., H, W, D).  cost_bound: the caller's declaration that no cost is larger; the kernels are selected for it
     and every cost is saturated at it on the way in.  The status tensor (return_status=True) is FSGM_ERR_INVALID when a cost was
     above the bound (the outputs are then those of the saturated volume), FSGM_ERR_HIP when an aggregation hand-off gave up;
-    check=True synchronises and raises on either.  adaptive_p2=1 needs guide, the first image, uint8 (.., H, W)."""
+    check=True synchronises and raises on either.  adaptive_p2=1 needs guide, the first image, uint8 (.., H, W).  runner_up=True
+    (fsgm::sgm_ru) returns minC2 uint32 after minC, as fsgm_amd.sgm_batch does."""
     code = _layout_code(layout)
     named = {"C": (Cvol, torch.uint8)}
     if guide is not None:
@@ -704,22 +792,27 @@ def sgm(Cvol, P1=7, P2=100, *, layout="dhw", paths=4, cost_bound=255, agg_mode=0
         guide = None if guide is None else guide.unsqueeze(0)
     if guide is None or not adaptive_p2:
         guide = torch.empty((0,), dtype=torch.uint8, device=Cvol.device)
-    bestD, minC, S, status = torch.ops.fsgm.sgm(Cvol, guide, int(P1), int(P2), int(paths), code, int(cost_bound), int(agg_mode),
-                                                int(adaptive_p2), int(subpixel), int(bool(return_sum)))
-    outs = (bestD, minC, S) if return_sum else (bestD, minC)
+    args = (Cvol, guide, int(P1), int(P2), int(paths), code, int(cost_bound), int(agg_mode), int(adaptive_p2), int(subpixel),
+            int(bool(return_sum)))
+    if runner_up:
+        bestD, minC, minC2, S, status = torch.ops.fsgm.sgm_ru(*args)
+    else:
+        bestD, minC, S, status = torch.ops.fsgm.sgm(*args)
+    outs = (bestD, minC) + ((minC2,) if runner_up else ()) + ((S,) if return_sum else ())
     return _finish(outs, status, batched, check, return_status, "a cost above cost_bound, or an aggregation hand-off that gave up")
 
 
 def sgm2d(costs, half_x, half_y, P1=6, P2=32, *, layout="dhw", hints=None, guide=None, cost_bound=255, diagonal=1, total_pass=2,
-          adaptive_p2=0, subpixel=1, return_flow=False, return_sum=False, check=False, return_status=False):
-    """(bestD, minC, mvSub[, flow][, S]) as fsgm_amd.sgm2d_batch, on cost volumes that are already in HBM: costs uint8 (D, H, W) or
+          adaptive_p2=0, subpixel=1, return_flow=False, return_sum=False, check=False, return_status=False, runner_up=False):
+    """(bestD, minC[, minC2], mvSub[, flow][, S]) as fsgm_amd.sgm2d_batch, on cost volumes that are already in HBM: costs uint8 (D, H, W) or
     a batch (N, D, H, W) for layout "dhw" (channel sx*Sy + sy) and "dhw_yx" (channel sy*Sx + sx, a correlation layer's order),
     (H, W, D) / (N, H, W, D) for "hwd".  The tensor is read where it lies -- it must be contiguous, at any byte address -- every
     output stays in HBM, the work is queued on the current stream.  hints float64 (.., 2, mvH, mvW) or None (zeros), guide uint8
     (.., H, W) with adaptive_p2=1.  bestD, minC uint32 (.., H, W); mvSub and flow float64 (.., 2, H, W); S uint32 (.., H, W, D).
     cost_bound: the caller's declaration that no cost is larger; the aggregation is selected for it and every cost is saturated at
     it on the way in.  The status tensor (return_status=True) is FSGM_ERR_INVALID when a cost was above the bound (the outputs are
-    then those of the saturated volume); check=True synchronises and raises on it."""
+    then those of the saturated volume); check=True synchronises and raises on it.  runner_up=True (fsgm::sgm2d_ru) returns minC2
+    uint32 (.., H, W) after minC, as fsgm_amd.sgm2d_batch does."""
     code = _layout2d_code(layout)
     named = {"costs": (costs, torch.uint8)}
     if hints is not None:
@@ -750,10 +843,13 @@ def sgm2d(costs, half_x, half_y, P1=6, P2=32, *, layout="dhw", hints=None, guide
         hints = torch.empty((0,), dtype=torch.float64, device=dev)
     if guide is None or not adaptive_p2:
         guide = torch.empty((0,), dtype=torch.uint8, device=dev)
-    bestD, minC, mvSub, flow, S, status = torch.ops.fsgm.sgm2d(costs, hints, guide, int(half_x), int(half_y), int(P1), int(P2), code,
-                                                               int(cost_bound), int(diagonal), int(total_pass), int(adaptive_p2),
-                                                               int(subpixel), int(bool(return_flow)), int(bool(return_sum)))
-    outs = (bestD, minC, mvSub) + ((flow,) if return_flow else ()) + ((S,) if return_sum else ())
+    args = (costs, hints, guide, int(half_x), int(half_y), int(P1), int(P2), code, int(cost_bound), int(diagonal), int(total_pass),
+            int(adaptive_p2), int(subpixel), int(bool(return_flow)), int(bool(return_sum)))
+    if runner_up:
+        bestD, minC, minC2, mvSub, flow, S, status = torch.ops.fsgm.sgm2d_ru(*args)
+    else:
+        bestD, minC, mvSub, flow, S, status = torch.ops.fsgm.sgm2d(*args)
+    outs = (bestD, minC) + ((minC2,) if runner_up else ()) + (mvSub,) + ((flow,) if return_flow else ()) + ((S,) if return_sum else ())
     return _finish(outs, status, batched, check, return_status, "a cost above cost_bound")
 
 
@@ -859,20 +955,32 @@ def stereo_sgm_pp(left, right, dMax, P1=6, P2=64, *, paths=4, subpixel=1, direct
     return _finish(outs, status, batched, check, return_status)
 
 
-def uniqueness_filter(map, minC, minC2, ratio):
+def uniqueness_filter(map, minC, minC2, ratio, *, planes=1):
     """fsgm_amd.uniqueness_filter on torch tensors on the GPU: map float64, minC / minC2 uint32 (stereo_sgm(runner_up=True)'s),
     (H, W) or (N, H, W); NaN where minC2 * (100 - ratio) < minC * 100 and minC2 is a runner-up, map elsewhere.  A new tensor;
-    the work is queued on the current stream."""
+    the work is queued on the current stream.  planes=2 (fsgm::uniqueness_filter_planes): map is a flow (2, H, W) or (N, 2, H, W)
+    next to costs (H, W) / (N, H, W) -- sgm2d(runner_up=True)'s -- and both planes of a rejected pixel become NaN."""
     _tensors({"map": (map, torch.float64), "minC": (minC, torch.uint32), "minC2": (minC2, torch.uint32)})
-    if map.dim() not in (2, 3):
-        raise TypeError(f"map must be (H, W) or (N, H, W) (got {tuple(map.shape)})")
-    _shape("minC", minC, map.shape)
-    _shape("minC2", minC2, map.shape)
+    if isinstance(planes, bool) or planes not in (1, 2):
+        raise ValueError(f"planes must be 1 or 2 (got {planes!r})")
+    if planes == 2:
+        if map.dim() not in (3, 4) or map.shape[-3] != 2:
+            raise TypeError(f"map must be (2, H, W) or (N, 2, H, W) with planes=2 (got {tuple(map.shape)})")
+        cshape = tuple(map.shape[:-3]) + tuple(map.shape[-2:])
+    else:
+        if map.dim() not in (2, 3):
+            raise TypeError(f"map must be (H, W) or (N, H, W) (got {tuple(map.shape)})")
+        cshape = tuple(map.shape)
+    _shape("minC", minC, cshape)
+    _shape("minC2", minC2, cshape)
     if isinstance(ratio, bool) or int(ratio) != ratio or not 0 <= int(ratio) <= 100:
         raise ValueError(f"ratio must be an integer in [0, 100] (got {ratio!r})")
-    batched = map.dim() == 3
+    batched = len(cshape) == 3
     a, b, c = (map, minC, minC2) if batched else (map.unsqueeze(0), minC.unsqueeze(0), minC2.unsqueeze(0))
-    out, _ = torch.ops.fsgm.uniqueness_filter(a, b, c, int(ratio))
+    if planes == 2:
+        out, _ = torch.ops.fsgm.uniqueness_filter_planes(a, b, c, int(ratio), 2)
+    else:
+        out, _ = torch.ops.fsgm.uniqueness_filter(a, b, c, int(ratio))
     return out if batched else out[0]
 
 

@@ -209,6 +209,26 @@ fsgm_status fsgm_uniqueness_filter_host(int32_t n_frames, const double* map, con
 fsgm_status fsgm_uniqueness_filter_device(int32_t n_frames, const double* map, const uint32_t* minC, const uint32_t* minC2,
                                           int32_t width, int32_t height, int32_t ratio, double* out, int32_t device, void* stream,
                                           int32_t* status);
+/* The runner-up cost of the 2-D matcher (calc_pyd_cost_sgm, sgm2d(C), the fsgm_pyd_plan).  For one pixel let S[sx*Sy + sy] be the
+ * u32 sums its WTA minimises -- exactly what the S tap returns, wrapping penalties included -- and best = bx*Sy + by the WTA's
+ * index, the first strict minimum in candidate order:
+ *   minC2 = min { S[sx*Sy + sy] : max(|sx - bx|, |sy - by|) >= 2 },  FSGM_NO_RUNNER_UP where that set is empty.
+ * The set is empty for every window with both sides <= 2, and for a side of 3 with the best in its middle while the other side
+ * is <= 3.  The excluded ring is the eight candidates the x and y parabolas and their diagonals draw on: the same minimum, not
+ * a competitor.  With Sy == 1 the rule is the 1-D rule |d - best| >= 2 above.  bestD, minC, mvSub, flow and S of a call that
+ * asks for minC2 are bit-identical to those of the same call without it; the cost and aggregation kernels are the same.
+ * Entry points: fsgm_pyd_plan_set_runner_up / _download_runner_up, fsgm_calc_pyd_cost_sgm_batch_host_ru,
+ * fsgm_sgm2d_batch_host_ru / fsgm_sgm2d_device_ru; on 1-D volumes fsgm_sgm_batch_host_ru / fsgm_sgm_device_ru (the 1-D rule).
+ *
+ * The uniqueness test above on `planes` planes per frame: planes = 1 is fsgm_uniqueness_filter_host itself, planes = 2 takes a
+ * flow -- map, out f64 [n][2][H][W], minC, minC2 u32 [n][H][W] -- and writes NaN into both planes of a rejected pixel.  planes
+ * outside 1..2 is FSGM_ERR_INVALID before a device is touched; the overlap rules are the ones above on the arrays' full sizes. */
+fsgm_status fsgm_uniqueness_filter_planes_host(int32_t n_frames, const double* map, const uint32_t* minC, const uint32_t* minC2,
+                                               int32_t width, int32_t height, int32_t planes, int32_t ratio, double* out,
+                                               int32_t device);
+fsgm_status fsgm_uniqueness_filter_planes_device(int32_t n_frames, const double* map, const uint32_t* minC, const uint32_t* minC2,
+                                                 int32_t width, int32_t height, int32_t planes, int32_t ratio, double* out,
+                                                 int32_t device, void* stream, int32_t* status);
 
 /* ---- device-resident plan: buffers for `batch` frames stay in HBM across calls ---- */
 typedef struct fsgm_epi_plan fsgm_epi_plan;
@@ -382,6 +402,13 @@ fsgm_sgm_params fsgm_sgm_params_default(void);   /* 4, 1, 0, 0 (auto), FSGM_COST
 fsgm_status fsgm_sgm_batch_host(int32_t n_frames, const uint8_t* C, int32_t width, int32_t height, int32_t dMax, int32_t P1,
                                 int32_t P2, const fsgm_sgm_params* prm, const uint8_t* guide, uint32_t* bestD, uint32_t* minC,
                                 uint32_t* S);
+/* fsgm_sgm_batch_host with the runner-up cost (FSGM_NO_RUNNER_UP above, the 1-D rule) minC2 u32 [n][H][W] after minC; minC2
+ * must not be NULL (FSGM_ERR_INVALID).  The cached plan has the epipolar plan's runner-up switch on and is never the plan of a
+ * call without minC2: such a call runs the line kernels at every batch size (fsgm_sgm_last_kernel shows it), a plain call keeps
+ * its plan and pipeline.  agg_mode 2..6 with it is FSGM_ERR_UNSUPPORTED before a device is touched. */
+fsgm_status fsgm_sgm_batch_host_ru(int32_t n_frames, const uint8_t* C, int32_t width, int32_t height, int32_t dMax, int32_t P1,
+                                   int32_t P2, const fsgm_sgm_params* prm, const uint8_t* guide, uint32_t* bestD, uint32_t* minC,
+                                   uint32_t* minC2, uint32_t* S);
 /* the pipeline (fsgm_epi_plan_kernel_name's names) that the calling thread's last fsgm_sgm_batch_host / fsgm_sgm_device ran,
  * "" before the first */
 const char* fsgm_sgm_last_kernel(void);
@@ -462,6 +489,10 @@ typedef struct {
 fsgm_status fsgm_calc_pyd_cost_sgm_host(const fsgm_pyd_in* in, const fsgm_pyd_out* out, int32_t device);
 fsgm_status fsgm_calc_pyd_cost_sgm_batch_host(int32_t n_frames, const fsgm_pyd_in* in,
                                               const fsgm_pyd_out* out, int32_t device);
+/* The same with the 2-D runner-up cost (FSGM_NO_RUNNER_UP above): minC2s[i] u32 [H][W] of frame i; minC2s or one of its
+ * pointers NULL is FSGM_ERR_INVALID.  fsgm_pyd_out stays as it is.  The cached plan is never the one of the call above. */
+fsgm_status fsgm_calc_pyd_cost_sgm_batch_host_ru(int32_t n_frames, const fsgm_pyd_in* in, const fsgm_pyd_out* out,
+                                                 uint32_t* const* minC2s, int32_t device);
 
 typedef struct fsgm_pyd_plan fsgm_pyd_plan;
 fsgm_status fsgm_pyd_plan_create(fsgm_pyd_plan** plan, int32_t width, int32_t height,
@@ -482,6 +513,11 @@ fsgm_status fsgm_pyd_plan_download_cost(fsgm_pyd_plan* plan, int32_t frame, uint
 fsgm_status fsgm_pyd_plan_download_sum(fsgm_pyd_plan* plan, int32_t frame, uint32_t* S);
 fsgm_status fsgm_pyd_plan_time(fsgm_pyd_plan* plan, int32_t stages, int32_t warmup,
                                int32_t iters, float* ms_avg);
+/* The 2-D runner-up cost (FSGM_NO_RUNNER_UP above) for this plan, 0 at creation: with the switch on every WTA also writes minC2,
+ * u32 [batch][H][W], allocated on first use and all ones until a WTA has run.  The switch changes neither the cost nor the
+ * aggregation kernel, nor any other output.  fsgm_pyd_plan_download_runner_up is FSGM_ERR_INVALID while the switch is off. */
+fsgm_status fsgm_pyd_plan_set_runner_up(fsgm_pyd_plan* plan, int32_t on);
+fsgm_status fsgm_pyd_plan_download_runner_up(fsgm_pyd_plan* plan, int32_t frame, uint32_t* minC2);
 
 /* Search windows and launches.  Every entry point on this path accepts a search window with sides 2*half+1 <= 64 (so 63 at
  * the most) and at most 1024 candidates (31x33 = 1023 is the largest count); anything else is FSGM_ERR_UNSUPPORTED before a
@@ -544,6 +580,13 @@ fsgm_status fsgm_sgm2d_batch_host(int32_t n_frames, const uint8_t* C, int32_t wi
                                   int32_t P1, int32_t P2, const fsgm_sgm2d_params* prm, const double* preMv, int32_t mvWidth,
                                   int32_t mvHeight, const uint8_t* guide, uint32_t* bestD, uint32_t* minC, double* mvSub,
                                   double* flow, uint32_t* S);
+/* fsgm_sgm2d_batch_host with the 2-D runner-up cost (FSGM_NO_RUNNER_UP above) minC2 u32 [n][H][W] after minC; minC2 must not be
+ * NULL (FSGM_ERR_INVALID before a device is touched).  Its cached plan is never the one of a call without minC2; the
+ * aggregation, and with it fsgm_sgm2d_last_kernel, is the one the plain call runs. */
+fsgm_status fsgm_sgm2d_batch_host_ru(int32_t n_frames, const uint8_t* C, int32_t width, int32_t height, int32_t halfX, int32_t halfY,
+                                     int32_t P1, int32_t P2, const fsgm_sgm2d_params* prm, const double* preMv, int32_t mvWidth,
+                                     int32_t mvHeight, const uint8_t* guide, uint32_t* bestD, uint32_t* minC, uint32_t* minC2,
+                                     double* mvSub, double* flow, uint32_t* S);
 /* the aggregation that the calling thread's last fsgm_sgm2d_batch_host / fsgm_sgm2d_device ran, "" before the first: "rows"
  * (row-packed, windows up to 11x11), "rows/wide" (its one-line-a-wave mapping: up to 2 landscape frames), "generic"
  * (pyd_agg_kernel without wrapping) or "generic/wrap" */
@@ -1060,6 +1103,11 @@ fsgm_status fsgm_stereo_sgm_device_ru(int32_t n_frames, const uint8_t* I1, const
 fsgm_status fsgm_sgm_device(int32_t n_frames, const uint8_t* C, int32_t width, int32_t height, int32_t dMax, int32_t P1, int32_t P2,
                             const fsgm_sgm_params* prm, const uint8_t* guide, uint32_t* bestD, uint32_t* minC, uint32_t* S,
                             void* stream, int32_t* status);
+/* fsgm_sgm_batch_host_ru on device pointers: minC2 (required, device memory, checked like minC) is written where it lies by the
+ * WTA itself, on the caller's stream; everything else as fsgm_sgm_device. */
+fsgm_status fsgm_sgm_device_ru(int32_t n_frames, const uint8_t* C, int32_t width, int32_t height, int32_t dMax, int32_t P1, int32_t P2,
+                               const fsgm_sgm_params* prm, const uint8_t* guide, uint32_t* bestD, uint32_t* minC, uint32_t* minC2,
+                               uint32_t* S, void* stream, int32_t* status);
 /* The first step of fsgm_sgm_device on its own, into a caller's plan: n_frames (= the plan's batch) volumes in `layout` from
  * device memory into the plan's cost volumes (what fsgm_epi_plan_upload_cost fills from the host), saturated at cost_bound,
  * which becomes the bound the plan selects its kernels by.  status: 0 or FSGM_ERR_INVALID (a byte above cost_bound). */
@@ -1076,6 +1124,12 @@ fsgm_status fsgm_sgm2d_device(int32_t n_frames, const uint8_t* C, int32_t width,
                               int32_t P1, int32_t P2, const fsgm_sgm2d_params* prm, const double* preMv, int32_t mvWidth,
                               int32_t mvHeight, const uint8_t* guide, uint32_t* bestD, uint32_t* minC, double* mvSub, double* flow,
                               uint32_t* S, void* stream, int32_t* status);
+/* fsgm_sgm2d_batch_host_ru on device pointers: minC2 (required, device memory, checked like minC) is written where it lies by
+ * the WTA itself, on the caller's stream; everything else as fsgm_sgm2d_device. */
+fsgm_status fsgm_sgm2d_device_ru(int32_t n_frames, const uint8_t* C, int32_t width, int32_t height, int32_t halfX, int32_t halfY,
+                                 int32_t P1, int32_t P2, const fsgm_sgm2d_params* prm, const double* preMv, int32_t mvWidth,
+                                 int32_t mvHeight, const uint8_t* guide, uint32_t* bestD, uint32_t* minC, uint32_t* minC2,
+                                 double* mvSub, double* flow, uint32_t* S, void* stream, int32_t* status);
 /* The first step of fsgm_sgm2d_device on its own, into a caller's plan: n_frames (= the plan's batch) volumes in a
  * FSGM_COST2D_LAYOUT_* from device memory into the plan's cost volumes (what fsgm_pyd_plan_upload_cost fills from the host),
  * saturated at cost_bound, which becomes the bound the plan selects its aggregation by.  status: 0 or FSGM_ERR_INVALID. */
