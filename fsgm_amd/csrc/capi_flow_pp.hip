@@ -5,6 +5,7 @@
 #include "capi_device.h"
 #include "flow_pp.h"
 #include "post_kernels.h"
+#include "stereo_pp_kernels.h"
 #include <math.h>
 #include <mutex>
 
@@ -197,15 +198,127 @@ static fsgm_status swap_enqueue(const PyramidPair& pr, const uint8_t* I0, const 
     return FSGM_OK;
 }
 
-static fsgm_status with_pair(int n, int W, int H, int channels, const fsgm_flow_pp_params& prm, const PairBody& body) {
+static fsgm_status with_pair(int n, int W, int H, int channels, const fsgm_flow_pp_params& prm, int ru, const PairBody& body) {
     if (prm.matcher == FSGM_MATCHER_NG) {
         fsgm_ng_pyramid_params q = prm.ng;
         q.device = prm.device;
-        return ng_pyramid_with_pair(n, W, H, channels, &q, body);
+        return ng_pyramid_with_pair(n, W, H, channels, &q, ru, body);
     }
     fsgm_pyramid_params q = prm.pyd;
     q.device = prm.device;
-    return pyd_pyramid_with_pair(n, W, H, channels, &q, body);
+    return pyd_pyramid_with_pair(n, W, H, channels, &q, ru, body);
+}
+
+// The _u forms' extra arguments (on: the call is one of them).  The plan of 2n pairs runs with the runner-up switch on, and the
+// uniqueness test of include/fsgm.h blanks the ambiguous pixels of the forward and of the backward flow, each by its own minC
+// and minC2, ahead of the chain: one launch over the 2n flows, in place in the plan's level-1 flow -- behind the copies that hand
+// out the raw flows, which every form queues anyway, so no flow is copied for the filter's sake.  The level loop writes every
+// pixel of that buffer again on its next run.  Ratio 0 rejects nothing: no launch.
+struct Uniqueness {
+    bool on;
+    int32_t ratio;
+    uint32_t* minC2;
+};
+
+static fsgm_status uniqueness_check(const char* who, const Uniqueness& u) {
+    if (!u.on) return FSGM_OK;
+    FSGM_REQUIRE(u.ratio >= 0 && u.ratio <= 100, "%s: uniqueness_ratio must be in [0, 100] (got %d)", who, u.ratio);
+    FSGM_REQUIRE(u.minC2, "%s: null argument (minC2 is required)", who);
+    return FSGM_OK;
+}
+
+static void uniqueness_enqueue(hipStream_t st, const PyramidPair& pr, const Uniqueness& u, size_t np, size_t frame_px) {
+    if (u.on && u.ratio > 0) launch_flow_uniqueness(st, pr.flow, pr.minC, pr.minC2, const_cast<double*>(pr.flow), 2 * np, frame_px, u.ratio);
+}
+
+static fsgm_status flow_pp_host(const char* who, int32_t n, const uint8_t* I0, const uint8_t* I1, int32_t W, int32_t H, int32_t channels,
+                                const fsgm_flow_pp_params* prm, const Uniqueness& u, const FlowOutputs& o) {
+    fsgm_status st = params_check(who, prm);
+    if (st != FSGM_OK || (st = uniqueness_check(who, u)) != FSGM_OK) return st;
+    if ((st = flow_args(who, n, W, H, I0 && I1 && o.flow_pp, prm->device)) != FSGM_OK) return st;
+    std::unique_lock<std::mutex> lk;
+    fsgm_flow_pp_plan* p;
+    if ((st = flow_plan_get(lk, &p, W, H, n, prm->device)) != FSGM_OK) return st;
+    const size_t np = p->NP * n;
+    if ((st = ensure_pp(p, who)) != FSGM_OK) return st;
+    return with_pair(n, W, H, channels, *prm, u.on, [&](const PyramidPair& pr) -> fsgm_status {
+        hipStream_t s = pr.stream;
+        const size_t img = np * channels;
+        StreamGuard guard(s);   // an early exit drains the stream: queued copies use the caller's memory
+        FSGM_HIP(hipMemcpyAsync(pr.in0, I0, img, hipMemcpyHostToDevice, s));
+        FSGM_HIP(hipMemcpyAsync(pr.in1, I1, img, hipMemcpyHostToDevice, s));
+        fsgm_status r = swap_enqueue(pr, pr.in0, pr.in1, img);
+        if (r != FSGM_OK || (r = pr.run(pr.plan)) != FSGM_OK) return r;
+        FSGM_HIP(hipStreamWaitEvent(s, p->busy, 0));
+        if (u.on) {                                              // the raw flows leave ahead of the filter
+            if (o.flow_fwd) FSGM_HIP(hipMemcpyAsync(o.flow_fwd, pr.flow, 2 * np * 8, hipMemcpyDeviceToHost, s));
+            if (o.flow_bwd) FSGM_HIP(hipMemcpyAsync(o.flow_bwd, pr.flow + 2 * np, 2 * np * 8, hipMemcpyDeviceToHost, s));
+            uniqueness_enqueue(s, pr, u, np, p->NP);
+        }
+        chain_enqueue(s, p, *prm, pr.flow, p->dPP, nullptr);
+        FSGM_HIP(hipGetLastError());
+        FSGM_HIP(hipMemcpyAsync(o.flow_pp, p->dPP, 3 * np * 8, hipMemcpyDeviceToHost, s));
+        if (o.flow_checked) FSGM_HIP(hipMemcpyAsync(o.flow_checked, p->dS, 2 * np * 8, hipMemcpyDeviceToHost, s));
+        if (!u.on) {
+            if (o.flow_fwd) FSGM_HIP(hipMemcpyAsync(o.flow_fwd, pr.flow, 2 * np * 8, hipMemcpyDeviceToHost, s));
+            if (o.flow_bwd) FSGM_HIP(hipMemcpyAsync(o.flow_bwd, pr.flow + 2 * np, 2 * np * 8, hipMemcpyDeviceToHost, s));
+        }
+        if (o.minC) FSGM_HIP(hipMemcpyAsync(o.minC, pr.minC, np * 4, hipMemcpyDeviceToHost, s));
+        if (u.on) FSGM_HIP(hipMemcpyAsync(u.minC2, pr.minC2, np * 4, hipMemcpyDeviceToHost, s));
+        FSGM_HIP(hipEventRecord(p->busy, s));
+        FSGM_HIP(hipStreamSynchronize(s));
+        guard.dismiss();
+        return FSGM_OK;
+    });
+}
+
+static fsgm_status flow_pp_device(const char* who, int32_t n, const uint8_t* I0, const uint8_t* I1, int32_t W, int32_t H, int32_t channels,
+                                  const fsgm_flow_pp_params* prm, const Uniqueness& u, const FlowOutputs& o, void* stream, int32_t* status) {
+    fsgm_status st = params_check(who, prm);
+    if (st != FSGM_OK || (st = uniqueness_check(who, u)) != FSGM_OK) return st;
+    if ((st = flow_args(who, n, W, H, I0 && I1 && o.flow_pp, prm->device)) != FSGM_OK) return st;
+    FSGM_REQUIRE(channels == 1 || channels == 3, "%s: channels must be 1 (gray) or 3 (RGB planes), got %d", who, channels);
+    hipStream_t cs = (hipStream_t)stream;
+    const size_t np = (size_t)W * H * n, img = np * channels;
+    if ((st = device_check_args(who, prm->device, cs, {{I0, img, 1, true, "I0"},
+                                                       {I1, img, 1, true, "I1"},
+                                                       {o.flow_pp, 3 * np * 8, 8, true, "flow_pp"},
+                                                       {o.flow_checked, 2 * np * 8, 8, false, "flow_checked"},
+                                                       {o.flow_fwd, 2 * np * 8, 8, false, "flow_fwd"},
+                                                       {o.flow_bwd, 2 * np * 8, 8, false, "flow_bwd"},
+                                                       {o.minC, np * 4, 4, false, "minC"},
+                                                       {u.on ? u.minC2 : nullptr, np * 4, 4, u.on, "minC2"},
+                                                       {status, 4, 4, false, "status"}})) != FSGM_OK)
+        return st;
+    std::unique_lock<std::mutex> lk;
+    fsgm_flow_pp_plan* p;
+    if ((st = flow_plan_get(lk, &p, W, H, n, prm->device)) != FSGM_OK) return st;
+    return with_pair(n, W, H, channels, *prm, u.on, [&](const PyramidPair& pr) -> fsgm_status {
+        hipStream_t s = pr.stream;
+        return device_call(*pr.join, cs, s, [&]() -> fsgm_status {
+            FSGM_HIP(hipMemcpyAsync(pr.in0, I0, img, hipMemcpyDeviceToDevice, s));
+            FSGM_HIP(hipMemcpyAsync(pr.in1, I1, img, hipMemcpyDeviceToDevice, s));
+            fsgm_status w = swap_enqueue(pr, I0, I1, img);
+            if (w != FSGM_OK || (w = pr.run(pr.plan)) != FSGM_OK) return w;
+            FSGM_HIP(hipStreamWaitEvent(s, p->busy, 0));
+            if (u.on) {                                          // the raw flows leave ahead of the filter
+                if (o.flow_fwd) FSGM_HIP(hipMemcpyAsync(o.flow_fwd, pr.flow, 2 * np * 8, hipMemcpyDeviceToDevice, s));
+                if (o.flow_bwd) FSGM_HIP(hipMemcpyAsync(o.flow_bwd, pr.flow + 2 * np, 2 * np * 8, hipMemcpyDeviceToDevice, s));
+                uniqueness_enqueue(s, pr, u, np, (size_t)W * H);
+            }
+            chain_enqueue(s, p, *prm, pr.flow, o.flow_pp, o.flow_checked);
+            FSGM_HIP(hipGetLastError());
+            if (!u.on) {
+                if (o.flow_fwd) FSGM_HIP(hipMemcpyAsync(o.flow_fwd, pr.flow, 2 * np * 8, hipMemcpyDeviceToDevice, s));
+                if (o.flow_bwd) FSGM_HIP(hipMemcpyAsync(o.flow_bwd, pr.flow + 2 * np, 2 * np * 8, hipMemcpyDeviceToDevice, s));
+            }
+            if (o.minC) FSGM_HIP(hipMemcpyAsync(o.minC, pr.minC, np * 4, hipMemcpyDeviceToDevice, s));
+            if (u.on) FSGM_HIP(hipMemcpyAsync(u.minC2, pr.minC2, np * 4, hipMemcpyDeviceToDevice, s));
+            FSGM_HIP(hipEventRecord(p->busy, s));
+            launch_device_status(s, nullptr, nullptr, status);
+            return FSGM_OK;
+        });
+    });
 }
 
 extern "C" {
@@ -249,76 +362,30 @@ fsgm_status fsgm_flow_in_fill_device(int32_t n, const double* flow, int32_t W, i
 fsgm_status fsgm_pyramidal_flow_pp_host(int32_t n, const uint8_t* I0, const uint8_t* I1, int32_t W, int32_t H, int32_t channels,
                                         const fsgm_flow_pp_params* prm, double* flow_pp, double* flow_checked, double* flow_fwd,
                                         double* flow_bwd, uint32_t* minC) {
-    const char* who = "fsgm_pyramidal_flow_pp";
-    fsgm_status st = params_check(who, prm);
-    if (st != FSGM_OK || (st = flow_args(who, n, W, H, I0 && I1 && flow_pp, prm->device)) != FSGM_OK) return st;
-    std::unique_lock<std::mutex> lk;
-    fsgm_flow_pp_plan* p;
-    if ((st = flow_plan_get(lk, &p, W, H, n, prm->device)) != FSGM_OK) return st;
-    const size_t np = p->NP * n;
-    if ((st = ensure_pp(p, who)) != FSGM_OK) return st;
-    return with_pair(n, W, H, channels, *prm, [&](const PyramidPair& pr) -> fsgm_status {
-        hipStream_t s = pr.stream;
-        const size_t img = np * channels;
-        StreamGuard guard(s);   // an early exit drains the stream: queued copies use the caller's memory
-        FSGM_HIP(hipMemcpyAsync(pr.in0, I0, img, hipMemcpyHostToDevice, s));
-        FSGM_HIP(hipMemcpyAsync(pr.in1, I1, img, hipMemcpyHostToDevice, s));
-        fsgm_status r = swap_enqueue(pr, pr.in0, pr.in1, img);
-        if (r != FSGM_OK || (r = pr.run(pr.plan)) != FSGM_OK) return r;
-        FSGM_HIP(hipStreamWaitEvent(s, p->busy, 0));
-        chain_enqueue(s, p, *prm, pr.flow, p->dPP, nullptr);
-        FSGM_HIP(hipGetLastError());
-        FSGM_HIP(hipMemcpyAsync(flow_pp, p->dPP, 3 * np * 8, hipMemcpyDeviceToHost, s));
-        if (flow_checked) FSGM_HIP(hipMemcpyAsync(flow_checked, p->dS, 2 * np * 8, hipMemcpyDeviceToHost, s));
-        if (flow_fwd) FSGM_HIP(hipMemcpyAsync(flow_fwd, pr.flow, 2 * np * 8, hipMemcpyDeviceToHost, s));
-        if (flow_bwd) FSGM_HIP(hipMemcpyAsync(flow_bwd, pr.flow + 2 * np, 2 * np * 8, hipMemcpyDeviceToHost, s));
-        if (minC) FSGM_HIP(hipMemcpyAsync(minC, pr.minC, np * 4, hipMemcpyDeviceToHost, s));
-        FSGM_HIP(hipEventRecord(p->busy, s));
-        FSGM_HIP(hipStreamSynchronize(s));
-        guard.dismiss();
-        return FSGM_OK;
-    });
+    return flow_pp_host("fsgm_pyramidal_flow_pp", n, I0, I1, W, H, channels, prm, Uniqueness{false, 0, nullptr},
+                        FlowOutputs{flow_pp, flow_checked, flow_fwd, flow_bwd, minC});
 }
 
 fsgm_status fsgm_pyramidal_flow_pp_device(int32_t n, const uint8_t* I0, const uint8_t* I1, int32_t W, int32_t H, int32_t channels,
                                           const fsgm_flow_pp_params* prm, double* flow_pp, double* flow_checked, double* flow_fwd,
                                           double* flow_bwd, uint32_t* minC, void* stream, int32_t* status) {
-    const char* who = "fsgm_pyramidal_flow_pp_device";
-    fsgm_status st = params_check(who, prm);
-    if (st != FSGM_OK || (st = flow_args(who, n, W, H, I0 && I1 && flow_pp, prm->device)) != FSGM_OK) return st;
-    FSGM_REQUIRE(channels == 1 || channels == 3, "%s: channels must be 1 (gray) or 3 (RGB planes), got %d", who, channels);
-    hipStream_t cs = (hipStream_t)stream;
-    const size_t np = (size_t)W * H * n, img = np * channels;
-    if ((st = device_check_args(who, prm->device, cs, {{I0, img, 1, true, "I0"},
-                                                       {I1, img, 1, true, "I1"},
-                                                       {flow_pp, 3 * np * 8, 8, true, "flow_pp"},
-                                                       {flow_checked, 2 * np * 8, 8, false, "flow_checked"},
-                                                       {flow_fwd, 2 * np * 8, 8, false, "flow_fwd"},
-                                                       {flow_bwd, 2 * np * 8, 8, false, "flow_bwd"},
-                                                       {minC, np * 4, 4, false, "minC"},
-                                                       {status, 4, 4, false, "status"}})) != FSGM_OK)
-        return st;
-    std::unique_lock<std::mutex> lk;
-    fsgm_flow_pp_plan* p;
-    if ((st = flow_plan_get(lk, &p, W, H, n, prm->device)) != FSGM_OK) return st;
-    return with_pair(n, W, H, channels, *prm, [&](const PyramidPair& pr) -> fsgm_status {
-        hipStream_t s = pr.stream;
-        return device_call(*pr.join, cs, s, [&]() -> fsgm_status {
-            FSGM_HIP(hipMemcpyAsync(pr.in0, I0, img, hipMemcpyDeviceToDevice, s));
-            FSGM_HIP(hipMemcpyAsync(pr.in1, I1, img, hipMemcpyDeviceToDevice, s));
-            fsgm_status w = swap_enqueue(pr, I0, I1, img);
-            if (w != FSGM_OK || (w = pr.run(pr.plan)) != FSGM_OK) return w;
-            FSGM_HIP(hipStreamWaitEvent(s, p->busy, 0));
-            chain_enqueue(s, p, *prm, pr.flow, flow_pp, flow_checked);
-            FSGM_HIP(hipGetLastError());
-            if (flow_fwd) FSGM_HIP(hipMemcpyAsync(flow_fwd, pr.flow, 2 * np * 8, hipMemcpyDeviceToDevice, s));
-            if (flow_bwd) FSGM_HIP(hipMemcpyAsync(flow_bwd, pr.flow + 2 * np, 2 * np * 8, hipMemcpyDeviceToDevice, s));
-            if (minC) FSGM_HIP(hipMemcpyAsync(minC, pr.minC, np * 4, hipMemcpyDeviceToDevice, s));
-            FSGM_HIP(hipEventRecord(p->busy, s));
-            launch_device_status(s, nullptr, nullptr, status);
-            return FSGM_OK;
-        });
-    });
+    return flow_pp_device("fsgm_pyramidal_flow_pp_device", n, I0, I1, W, H, channels, prm, Uniqueness{false, 0, nullptr},
+                          FlowOutputs{flow_pp, flow_checked, flow_fwd, flow_bwd, minC}, stream, status);
+}
+
+fsgm_status fsgm_pyramidal_flow_pp_host_u(int32_t n, const uint8_t* I0, const uint8_t* I1, int32_t W, int32_t H, int32_t channels,
+                                          const fsgm_flow_pp_params* prm, int32_t uniqueness_ratio, double* flow_pp, double* flow_checked,
+                                          double* flow_fwd, double* flow_bwd, uint32_t* minC, uint32_t* minC2) {
+    return flow_pp_host("fsgm_pyramidal_flow_pp_host_u", n, I0, I1, W, H, channels, prm, Uniqueness{true, uniqueness_ratio, minC2},
+                        FlowOutputs{flow_pp, flow_checked, flow_fwd, flow_bwd, minC});
+}
+
+fsgm_status fsgm_pyramidal_flow_pp_device_u(int32_t n, const uint8_t* I0, const uint8_t* I1, int32_t W, int32_t H, int32_t channels,
+                                            const fsgm_flow_pp_params* prm, int32_t uniqueness_ratio, double* flow_pp, double* flow_checked,
+                                            double* flow_fwd, double* flow_bwd, uint32_t* minC, uint32_t* minC2, void* stream,
+                                            int32_t* status) {
+    return flow_pp_device("fsgm_pyramidal_flow_pp_device_u", n, I0, I1, W, H, channels, prm, Uniqueness{true, uniqueness_ratio, minC2},
+                          FlowOutputs{flow_pp, flow_checked, flow_fwd, flow_bwd, minC}, stream, status);
 }
 
 fsgm_status fsgm_pyramidal_flow_pp_time(int32_t n, const uint8_t* I0, const uint8_t* I1, int32_t W, int32_t H, int32_t channels,
@@ -332,7 +399,7 @@ fsgm_status fsgm_pyramidal_flow_pp_time(int32_t n, const uint8_t* I0, const uint
     if ((st = flow_plan_get(lk, &p, W, H, n, prm->device)) != FSGM_OK) return st;
     const size_t np = p->NP * n;
     if ((st = ensure_pp(p, who)) != FSGM_OK) return st;
-    return with_pair(n, W, H, channels, *prm, [&](const PyramidPair& pr) -> fsgm_status {
+    return with_pair(n, W, H, channels, *prm, 0, [&](const PyramidPair& pr) -> fsgm_status {
         hipStream_t s = pr.stream;
         const size_t img = np * channels;
         StreamGuard guard(s);

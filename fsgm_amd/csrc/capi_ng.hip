@@ -85,10 +85,14 @@ void fsgm_ng_shutdown_internal(void) {
     }
 }
 
-fsgm_status fsgm_calc_pyd_cost_sgm_ng_batch_host(int32_t n, const fsgm_ng_in* in, const fsgm_ng_out* out, int32_t device) {
-    FSGM_REQUIRE(n >= 1 && in && out, "fsgm_calc_pyd_cost_sgm_ng: null argument");
+}  // extern "C"
+
+// minC2s: null (the plain call), or one non-null pointer per frame (the _ru forms: the WTA kernel with the runner-up cost)
+static fsgm_status ng_batch_host(int32_t n, const fsgm_ng_in* in, const fsgm_ng_out* out, uint32_t* const* minC2s, bool ru, int32_t device) {
+    FSGM_REQUIRE(n >= 1 && in && out && (minC2s || !ru), "fsgm_calc_pyd_cost_sgm_ng: null argument");
     const fsgm_ng_in& a = in[0];
     for (int i = 0; i < n; i++) {
+        FSGM_REQUIRE(!ru || minC2s[i], "fsgm_calc_pyd_cost_sgm_ng: frame %d has a null minC2", i);
         FSGM_REQUIRE(in[i].I1 && in[i].I2 && in[i].preMv && out[i].minC && out[i].flow,
                      "fsgm_calc_pyd_cost_sgm_ng: frame %d has a null pointer", i);
         const fsgm_ng_in& b = in[i];
@@ -107,13 +111,14 @@ fsgm_status fsgm_calc_pyd_cost_sgm_ng_batch_host(int32_t n, const fsgm_ng_in* in
     if (st != FSGM_OK) return st;
     const size_t NP = (size_t)W * H, MV = (size_t)a.mvWidth * a.mvHeight, N = NP * D, B = n;
     DevBufs d(device);
-    uint8_t *dI1, *dI2; uint32_t* dMinC; double *dMv, *dFlow;
+    uint8_t *dI1, *dI2; uint32_t *dMinC, *dMinC2 = nullptr; double *dMv, *dFlow;
     NgLevelBufs nb;
     d.want((void**)&dI1, B * NP);
     d.want((void**)&dI2, B * NP);
     d.want((void**)&dMv, B * MV * 16);
     d.want((void**)&dMinC, B * NP * 4);
     d.want((void**)&dFlow, B * NP * 16);
+    if (ru) d.want((void**)&dMinC2, B * NP * 4);
     for (const NgBuf& b : ng_level_bufs(nb, W, H, (int)D, n)) d.want(b.slot, b.bytes);
     if ((st = hip_status(d.commit(device), "fsgm_calc_pyd_cost_sgm_ng")) != FSGM_OK) return st;
     for (int i = 0; i < n; i++) {
@@ -121,7 +126,7 @@ fsgm_status fsgm_calc_pyd_cost_sgm_ng_batch_host(int32_t n, const fsgm_ng_in* in
         FSGM_HIP(hipMemcpyAsync(dI2 + i * NP, in[i].I2, NP, hipMemcpyHostToDevice, d.stream));
         FSGM_HIP(hipMemcpyAsync(dMv + i * 2 * MV, in[i].preMv, MV * 16, hipMemcpyHostToDevice, d.stream));
     }
-    const NgLevel lv = {dI1, dI2, dMv, dMinC, dFlow, W, H, a.mvWidth, a.mvHeight, r, rAgg, a.P1, a.P2, a.subPixelRefine};
+    const NgLevel lv = {dI1, dI2, dMv, dMinC, dFlow, W, H, a.mvWidth, a.mvHeight, r, rAgg, a.P1, a.P2, a.subPixelRefine, dMinC2};
     NgMatcherSet ms;
     FSGM_HIP(ng_level_enqueue(d.stream, nb, lv, n, &ms));
     bool want_S = false;
@@ -137,12 +142,30 @@ fsgm_status fsgm_calc_pyd_cost_sgm_ng_batch_host(int32_t n, const fsgm_ng_in* in
         FSGM_HIP(hipMemcpy(out[i].minC, dMinC + i * NP, NP * 4, hipMemcpyDeviceToHost));
         FSGM_HIP(hipMemcpy(out[i].flow, dFlow + i * 2 * NP, NP * 16, hipMemcpyDeviceToHost));
         if (out[i].S) FSGM_HIP(hipMemcpy(out[i].S, nb.S + i * N, N * 4, hipMemcpyDeviceToHost));
+        if (ru) FSGM_HIP(hipMemcpy(minC2s[i], dMinC2 + i * NP, NP * 4, hipMemcpyDeviceToHost));
     }
     return FSGM_OK;
 }
 
+extern "C" {
+
+fsgm_status fsgm_calc_pyd_cost_sgm_ng_batch_host(int32_t n, const fsgm_ng_in* in, const fsgm_ng_out* out, int32_t device) {
+    return ng_batch_host(n, in, out, nullptr, false, device);
+}
+
 fsgm_status fsgm_calc_pyd_cost_sgm_ng_host(const fsgm_ng_in* in, const fsgm_ng_out* out, int32_t device) {
-    return fsgm_calc_pyd_cost_sgm_ng_batch_host(1, in, out, device);
+    return ng_batch_host(1, in, out, nullptr, false, device);
+}
+
+fsgm_status fsgm_calc_pyd_cost_sgm_ng_batch_host_ru(int32_t n, const fsgm_ng_in* in, const fsgm_ng_out* out, uint32_t* const* minC2s,
+                                                    int32_t device) {
+    FSGM_REQUIRE(minC2s, "fsgm_calc_pyd_cost_sgm_ng_batch_host_ru: null minC2s");
+    return ng_batch_host(n, in, out, minC2s, true, device);
+}
+
+fsgm_status fsgm_calc_pyd_cost_sgm_ng_host_ru(const fsgm_ng_in* in, const fsgm_ng_out* out, uint32_t* minC2, int32_t device) {
+    FSGM_REQUIRE(minC2, "fsgm_calc_pyd_cost_sgm_ng_host_ru: null minC2");
+    return ng_batch_host(1, in, out, &minC2, true, device);
 }
 
 const char* fsgm_ng_auto_matcher(int32_t width, int32_t height, int32_t D, int32_t frames, uint64_t list_sum, uint64_t sample_pixels,

@@ -17,6 +17,7 @@ struct fsgm_ng_pyramid_plan {
     std::vector<uint8_t*> dG0, dG1;                  // gray pair per level
     std::vector<double*> dMv;                        // hint map per level: [2][mvH][mvW]
     std::vector<uint32_t*> dMinC;                    // [h][w]
+    uint32_t* dMinC2 = nullptr;                      // level 1's runner-up cost [H][W], made by set_runner_up
     NgLevelBufs nb{};
 
     static fsgm_status check(const Params& prm, int W, int H) {
@@ -28,6 +29,18 @@ struct fsgm_ng_pyramid_plan {
     }
     uint8_t*& gray(int img, int l) { return (img ? dG1 : dG0)[l]; }
     uint32_t*& minC(int l) { return dMinC[l]; }
+    uint32_t*& minC2() { return dMinC2; }
+    fsgm_status set_runner_up(int on) {
+        if (on && !dMinC2) {                         // all ones until a WTA has run: FSGM_NO_RUNNER_UP
+            const size_t bytes = (size_t)core.batch * core.W * core.H * 4;
+            uint32_t* m = nullptr;
+            FSGM_HIP(hipMalloc((void**)&m, bytes));
+            const hipError_t e = hipMemsetAsync(m, 0xFF, bytes, core.stream);
+            if (e != hipSuccess) { (void)hipFree(m); return hip_status(e, "fsgm_ng_pyramid_plan_set_runner_up"); }
+            dMinC2 = m;
+        }
+        return FSGM_OK;
+    }
 
     fsgm_status create_levels() {
         const int n = prm.numPyd, D = 9 * (2 * prm.halfSearchWinSize + 1) * (2 * prm.halfSearchWinSize + 1);
@@ -51,13 +64,15 @@ struct fsgm_ng_pyramid_plan {
             for (uint8_t* b : *v) if (b) (void)hipFree(b);
         for (double* b : dMv) if (b) (void)hipFree(b);
         for (uint32_t* b : dMinC) if (b) (void)hipFree(b);
+        if (dMinC2) (void)hipFree(dMinC2);
         for (const NgBuf& b : ng_level_bufs(nb, 0, 0, 0, 0)) if (*b.slot) (void)hipFree(*b.slot);     // (the slots only)
     }
 
     fsgm_status enqueue_level(int l) {
         const int w = core.Ws[l], h = core.Hs[l];
         const NgLevel lv = {dG0[l], dG1[l], dMv[l], dMinC[l], core.dFlow[l], w, h, core.mvW[l], core.mvH[l],
-                            prm.halfSearchWinSize, prm.aggSize / 2, prm.P1, prm.P2, prm.subPixelRefine};
+                            prm.halfSearchWinSize, prm.aggSize / 2, prm.P1, prm.P2, prm.subPixelRefine,
+                            l == 0 && core.runner_up ? dMinC2 : nullptr};
         FSGM_HIP(ng_level_enqueue(core.stream, nb, lv, core.batch));
         if (l > 0)                                                               // pyramidal_sgm.m:72
             launch_pyr_upsample2(core.stream, core.dFlow[l], dMv[l - 1], w, h, core.batch, (size_t)2 * core.mvW[l - 1] * core.mvH[l - 1]);
@@ -67,8 +82,8 @@ struct fsgm_ng_pyramid_plan {
 
 static PyramidCache<fsgm_ng_pyramid_plan> g_ngpyr;
 
-fsgm_status fsgm::ng_pyramid_with_pair(int n, int W, int H, int channels, const fsgm_ng_pyramid_params* prm, const PairBody& body) {
-    return pyramid_with_pair(g_ngpyr, n, W, H, channels, prm, body);
+fsgm_status fsgm::ng_pyramid_with_pair(int n, int W, int H, int channels, const fsgm_ng_pyramid_params* prm, int ru, const PairBody& body) {
+    return pyramid_with_pair(g_ngpyr, n, W, H, channels, prm, ru, body);
 }
 
 extern "C" {
@@ -123,6 +138,12 @@ fsgm_status fsgm_ng_pyramid_plan_time(fsgm_ng_pyramid_plan* p, int32_t warmup, i
     return pyramid_time(p, warmup, iters, ms_avg);
 }
 
+fsgm_status fsgm_ng_pyramid_plan_set_runner_up(fsgm_ng_pyramid_plan* p, int32_t on) { return pyramid_set_runner_up(p, on); }
+
+fsgm_status fsgm_ng_pyramid_plan_download_runner_up(fsgm_ng_pyramid_plan* p, int32_t frame, uint32_t* minC2) {
+    return pyramid_download_runner_up(p, frame, minC2);
+}
+
 void fsgm_ng_pyramid_shutdown_internal(void) { g_ngpyr.clear(); }
 
 // one call = the whole loop; plans are cached per shape like fsgm_pyramidal_sgm_host's
@@ -134,6 +155,18 @@ fsgm_status fsgm_pyramidal_sgm_ng_host(const uint8_t* I0, const uint8_t* I1, int
 fsgm_status fsgm_pyramidal_sgm_ng_device(int32_t n, const uint8_t* I0, const uint8_t* I1, int32_t width, int32_t height, int32_t channels,
                                          const fsgm_ng_pyramid_params* prm, double* flow, uint32_t* minC, void* stream, int32_t* status) {
     return pyramid_device(g_ngpyr, n, I0, I1, width, height, channels, prm, flow, minC, stream, status);
+}
+
+fsgm_status fsgm_pyramidal_sgm_ng_host_ru(const uint8_t* I0, const uint8_t* I1, int32_t width, int32_t height, int32_t channels,
+                                          const fsgm_ng_pyramid_params* prm, double* flow, uint32_t* minC, uint32_t* minC2,
+                                          double* const* flowPyd) {
+    return pyramid_host(g_ngpyr, I0, I1, width, height, channels, prm, flow, minC, flowPyd, minC2, true);
+}
+
+fsgm_status fsgm_pyramidal_sgm_ng_device_ru(int32_t n, const uint8_t* I0, const uint8_t* I1, int32_t width, int32_t height, int32_t channels,
+                                            const fsgm_ng_pyramid_params* prm, double* flow, uint32_t* minC, uint32_t* minC2, void* stream,
+                                            int32_t* status) {
+    return pyramid_device(g_ngpyr, n, I0, I1, width, height, channels, prm, flow, minC, stream, status, minC2, true);
 }
 
 }  // extern "C"

@@ -18,6 +18,8 @@ struct fsgm_pyramid_plan {
     static fsgm_status check(const Params&, int, int) { return FSGM_OK; }
     uint8_t*& gray(int img, int l) { return img ? lv[l]->dI2 : lv[l]->dI1; }
     uint32_t*& minC(int l) { return lv[l]->dMinC; }
+    uint32_t*& minC2() { return lv[0]->dMinC2; }     // the last level's WTA takes it from its plan (PydWtaArgs::minC2)
+    fsgm_status set_runner_up(int on) { return fsgm_pyd_plan_set_runner_up(lv[0], on); }
 
     fsgm_status create_levels() {
         const int n = prm.numPyd;
@@ -55,8 +57,8 @@ struct fsgm_pyramid_plan {
 
 static PyramidCache<fsgm_pyramid_plan> g_pyr;
 
-fsgm_status fsgm::pyd_pyramid_with_pair(int n, int W, int H, int channels, const fsgm_pyramid_params* prm, const PairBody& body) {
-    return pyramid_with_pair(g_pyr, n, W, H, channels, prm, body);
+fsgm_status fsgm::pyd_pyramid_with_pair(int n, int W, int H, int channels, const fsgm_pyramid_params* prm, int ru, const PairBody& body) {
+    return pyramid_with_pair(g_pyr, n, W, H, channels, prm, ru, body);
 }
 
 extern "C" {
@@ -147,6 +149,12 @@ fsgm_status fsgm_pyramid_plan_time(fsgm_pyramid_plan* p, int32_t warmup, int32_t
     return pyramid_time(p, warmup, iters, ms_avg);
 }
 
+fsgm_status fsgm_pyramid_plan_set_runner_up(fsgm_pyramid_plan* p, int32_t on) { return pyramid_set_runner_up(p, on); }
+
+fsgm_status fsgm_pyramid_plan_download_runner_up(fsgm_pyramid_plan* p, int32_t frame, uint32_t* minC2) {
+    return pyramid_download_runner_up(p, frame, minC2);
+}
+
 void fsgm_pyramid_shutdown_internal(void) { g_pyr.clear(); }
 
 // one call = pyramidal_sgm(I0, I1, numPyd)
@@ -158,6 +166,17 @@ fsgm_status fsgm_pyramidal_sgm_host(const uint8_t* I0, const uint8_t* I1, int32_
 fsgm_status fsgm_pyramidal_sgm_device(int32_t n, const uint8_t* I0, const uint8_t* I1, int32_t width, int32_t height, int32_t channels,
                                       const fsgm_pyramid_params* prm, double* mv, uint32_t* minC, void* stream, int32_t* status) {
     return pyramid_device(g_pyr, n, I0, I1, width, height, channels, prm, mv, minC, stream, status);
+}
+
+fsgm_status fsgm_pyramidal_sgm_host_ru(const uint8_t* I0, const uint8_t* I1, int32_t width, int32_t height, int32_t channels,
+                                       const fsgm_pyramid_params* prm, double* mv, uint32_t* minC, uint32_t* minC2, double* const* mvPyd) {
+    return pyramid_host(g_pyr, I0, I1, width, height, channels, prm, mv, minC, mvPyd, minC2, true);
+}
+
+fsgm_status fsgm_pyramidal_sgm_device_ru(int32_t n, const uint8_t* I0, const uint8_t* I1, int32_t width, int32_t height, int32_t channels,
+                                         const fsgm_pyramid_params* prm, double* mv, uint32_t* minC, uint32_t* minC2, void* stream,
+                                         int32_t* status) {
+    return pyramid_device(g_pyr, n, I0, I1, width, height, channels, prm, mv, minC, stream, status, minC2, true);
 }
 
 }  // extern "C"

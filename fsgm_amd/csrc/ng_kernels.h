@@ -62,6 +62,8 @@ struct NgWtaArgs {
     uint32_t* minC;         // [frames][NP]
     double* flow;           // [frames][2][NP]
     int W, H, D;
+    uint32_t* minC2 = nullptr;   // optional runner-up cost [frames][NP] (FSGM_NO_RUNNER_UP of include/fsgm.h, the neighbour-guided rule);
+                                 // null: the kernel without it
 };
 
 struct NgSubpixArgs {
@@ -122,6 +124,7 @@ struct NgLevel {
     int r, rAgg;            // halfSearchWinSize, aggSize / 2: D = 9 (2r+1)^2 candidates
     int P1, P2;
     int subPixelRefine;
+    uint32_t* minC2 = nullptr;   // [frames][H][W] the WTA's runner-up cost, when asked for (NgWtaArgs)
 };
 // The aggregation kernels a level launches: ng_matcher_set fills it from the level's shape, its frame count and the
 // A/B switches, once per level enqueue.  With more than one member the device picks: ng_decide_kernel feeds the dedupe kernel's

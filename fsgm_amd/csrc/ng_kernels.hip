@@ -1181,6 +1181,14 @@ __global__ __launch_bounds__(256 * PARTS) void ng_agg_split_kernel(NgAggArgs a) 
 // WTA -> winning candidate's motion vector (calc_pyd_cost_sgm_ng.cpp:281-299); one wave per pixel.  With the kept-entry
 // table of launch_ng_dedupe the search runs over the K groups of repeats instead of the D candidates: a group's sum sits
 // at its first member's index, every member ties with it, so the first minimum over d is the smallest (sum, first index).
+//
+// RU (a.minC2 set): also the runner-up cost of include/fsgm.h, the smallest sum among the candidates whose motion vector lies two
+// or more (Chebyshev) from the winner's.  After the two reductions all 16 lanes of a pixel know gidx: each reads the winner's
+// vector (one address a pixel), walks the same entries again -- a kept entry stands for its whole group of repeats, which share
+// its vector -- and a third 16-lane minimum follows.  The first round's entry (index and sum) stays in registers, so the lists of
+// real hint maps (n <= 16) read nothing twice but gain the vectors' loads; later rounds reload from lists the first pass just
+// pulled into L2.  Differences in 64 bits: the general path admits |mv| up to 2^31.  RU = false is the kernel as it was.
+template <bool RU>
 __global__ __launch_bounds__(256) void ng_wta_kernel(NgWtaArgs a) {
     // 16 lanes a pixel, 4 pixels a wave: the kept lists are mostly shorter than 16, and D = 81 candidates take 6 rounds
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -1197,10 +1205,12 @@ __global__ __launch_bounds__(256) void ng_wta_kernel(NgWtaArgs a) {
     const bool l4 = cmp && a.L4 && a.kstat && ng_is_compact(a.kstat[NG_KSTAT_CHOICE]);   // launch-uniform: a compact kernel ran
     const int16_t* Lp = a.L4 + (f * (size_t)NP + p) * NG_L4_PER_PIXEL;
     uint32_t lo = 0xFFFFFFFFu, idx = 0xFFFFFFFFu;
+    uint32_t d0 = 0, s0 = 0;                                  // RU: this lane's entry of the first round
     for (int e = l16; e < n; e += 16) {
         const uint32_t d = cmp ? (uint32_t)(cmp[e] >> 8) : (uint32_t)e;
         const uint32_t s = l4 ? (uint32_t)((int)Lp[e] + (int)Lp[64 + e] + (int)Lp[128 + e] + (int)Lp[192 + e]) : Sp[d];
         if (s < lo || idx == 0xFFFFFFFFu || (s == lo && d < idx)) { lo = s; idx = d; }
+        if (RU && e < 16) { d0 = d; s0 = s; }
     }
     uint32_t glo = lo;
 #pragma unroll
@@ -1208,7 +1218,33 @@ __global__ __launch_bounds__(256) void ng_wta_kernel(NgWtaArgs a) {
     uint32_t gidx = (lo == glo && idx != 0xFFFFFFFFu) ? idx : 0xFFFFFFFFu;
 #pragma unroll
     for (int s = 8; s >= 1; s >>= 1) gidx = min(gidx, (uint32_t)__shfl_xor((int)gidx, s));
+    uint32_t lo2 = 0xFFFFFFFFu;                               // FSGM_NO_RUNNER_UP
+    if (RU) {
+        const size_t base = f * (size_t)NP * D + (size_t)p * D;   // (p is clamped: the idle quarter-waves of the last wave read pixel NP - 1)
+        const bool k4 = l4 && a.K4 && a.flags && a.flags[1] == 0;   // launch-uniform, as below
+        auto mv_of = [&](uint32_t d, int& x, int& y) {
+            if (k4) { const Cand c = ng_unkey4(a.K4[base + d]); x = c.mvx; y = c.mvy; }
+            else { const Cand* c = a.C + base + d; x = c->mvx; y = c->mvy; }
+        };
+        int bx, by;
+        mv_of(gidx, bx, by);
+        for (int e = l16; e < n; e += 16) {
+            uint32_t d = d0, s = s0;
+            if (e >= 16) {
+                d = cmp ? (uint32_t)(cmp[e] >> 8) : (uint32_t)e;
+                s = l4 ? (uint32_t)((int)Lp[e] + (int)Lp[64 + e] + (int)Lp[128 + e] + (int)Lp[192 + e]) : Sp[d];
+            }
+            int x, y;
+            mv_of(d, x, y);
+            const long long dx = (long long)x - bx, dy = (long long)y - by;
+            const bool far = dx >= 2 || dx <= -2 || dy >= 2 || dy <= -2;
+            if (far) lo2 = min(lo2, s);
+        }
+#pragma unroll
+        for (int s = 8; s >= 1; s >>= 1) lo2 = min(lo2, (uint32_t)__shfl_xor((int)lo2, s));
+    }
     if (l16 == 0 && pact) {
+        if (RU) a.minC2[f * NP + p] = lo2;
         // the winner's motion vector: from its 4-byte key where the launch kept those (compact matcher, every key in range:
         // the 12-byte list does not exist then), from the Cand list otherwise
         const bool k4 = l4 && a.K4 && a.flags && a.flags[1] == 0;
@@ -1962,7 +1998,9 @@ void launch_ng_l4_to_s(hipStream_t st, uint32_t* S, const int16_t* L4, const uin
 }
 
 static void launch_ng_wta(hipStream_t st, const NgWtaArgs& a, int frames) {
-    hipLaunchKernelGGL(ng_wta_kernel, dim3((a.W * a.H + 15) / 16, frames), dim3(256), 0, st, a);
+    const dim3 grid((a.W * a.H + 15) / 16, frames);
+    if (a.minC2) hipLaunchKernelGGL(ng_wta_kernel<true>, grid, dim3(256), 0, st, a);
+    else         hipLaunchKernelGGL(ng_wta_kernel<false>, grid, dim3(256), 0, st, a);
 }
 
 static void launch_ng_subpixel(hipStream_t st, const NgSubpixArgs& a, int frames) {
@@ -2017,6 +2055,7 @@ hipError_t ng_level_enqueue(hipStream_t st, const NgLevelBufs& b, const NgLevel&
     NgWtaArgs wa;
     wa.C = b.C; wa.S = b.S; wa.minC = lv.minC; wa.flow = lv.flow; wa.W = W; wa.H = H; wa.D = D;
     wa.cm = ga.cm; wa.dk = ga.dk; wa.L4 = ga.L4; wa.kstat = ga.kstat; wa.K4 = ca.K4; wa.flags = ca.flags;
+    wa.minC2 = lv.minC2;
     launch_ng_wta(st, wa, frames);
     if (lv.subPixelRefine) {                                                  // :516-517
         NgSubpixArgs sa;

@@ -11,6 +11,8 @@
 //   fsgm_status create_levels(); void destroy_levels();                its own per-level state (core is set up before, released after)
 //   uint8_t*& gray(int img, int l); uint32_t*& minC(int l);            the slots of level l's gray images (img 0 / 1) and minC
 //   fsgm_status enqueue_level(int l);                                  level l on core.stream, the hint map of level l - 1 included
+//   fsgm_status set_runner_up(int on); uint32_t*& minC2();              the runner-up cost of level 1 (include/fsgm.h): with core.runner_up
+//                                                                      set, level 1's WTA also writes the slot's buffer, made on first use
 // The entry points reach the gray images and minC through those slots, so that Bind<> in the device entry point swaps what
 // the kernels read and write.
 #pragma once
@@ -32,6 +34,7 @@ struct PyramidCore {
     hipStream_t stream = nullptr;                // every level runs on it, in order
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     DeviceJoin join;                             // device-pointer entry point: ordering with the caller's stream
+    int runner_up = 0;                           // level 1's WTA also writes minC2 (pyramid_set_runner_up); part of the cached plans' key
 };
 
 template <class P>
@@ -148,6 +151,29 @@ fsgm_status pyramid_download_frame(P* p, int frame, int level, double* flow, uin
     return FSGM_OK;
 }
 
+// The runner-up cost of level 1, 0 at creation: no other level's WTA and no other output changes with it
+template <class P>
+fsgm_status pyramid_set_runner_up(P* p, int on) {
+    FSGM_REQUIRE(p, "null plan");
+    FSGM_REQUIRE(on == 0 || on == 1, "%s_set_runner_up: on must be 0 or 1 (got %d)", P::plan_name, on);
+    FSGM_HIP(hipSetDevice(p->prm.device));
+    const fsgm_status st = p->set_runner_up(on);
+    if (st == FSGM_OK) p->core.runner_up = on;
+    return st;
+}
+
+template <class P>
+fsgm_status pyramid_download_runner_up(P* p, int frame, uint32_t* minC2) {
+    FSGM_REQUIRE(p && minC2, "%s_download_runner_up: null argument", P::plan_name);
+    FSGM_REQUIRE(frame >= 0 && frame < p->core.batch, "frame %d out of range (batch %d)", frame, p->core.batch);
+    FSGM_REQUIRE(p->core.runner_up, "%s_download_runner_up: the plan's runner-up switch is off (%s_set_runner_up)", P::plan_name, P::plan_name);
+    FSGM_HIP(hipSetDevice(p->prm.device));
+    FSGM_HIP(hipStreamSynchronize(p->core.stream));
+    const size_t np = (size_t)p->core.W * p->core.H;
+    FSGM_HIP(hipMemcpy(minC2, p->minC2() + (size_t)frame * np, np * 4, hipMemcpyDeviceToHost));
+    return FSGM_OK;
+}
+
 // impyramid 'reduce' (:28-31) and rgb2gray (:44-45) of every level, all frames' planes in one launch
 template <class P>
 void pyramid_enqueue_images(P* p) {
@@ -191,17 +217,20 @@ fsgm_status pyramid_time(P* p, int warmup, int iters, float* ms_avg) {
     return time_enqueues(c.stream, c.ev0, c.ev1, warmup, iters, [&] { return pyramid_enqueue(p); }, ms_avg);
 }
 
-// The plans behind the host- and device-pointer entry points: the last two per device, keyed by shape, parameters and batch
+// The plans behind the host- and device-pointer entry points: the last two per device, keyed by shape, parameters, batch and the
+// runner-up switch (a call that asks for minC2 never takes the plan of one that does not, nor the reverse)
 template <class P>
 struct PyramidCache : PlanCache<P> {
     PyramidCache() : PlanCache<P>(2, pyramid_destroy<P>) {}
     // the cached plan of this shape, parameter set and batch (the caller holds the device's lock)
-    fsgm_status get(P** out, int W, int H, int channels, const typename P::Params* prm, int batch) {
+    fsgm_status get(P** out, int W, int H, int channels, const typename P::Params* prm, int batch, int ru = 0) {
         *out = this->find(prm->device, [&](const P* q) {
-            return q->core.W == W && q->core.H == H && q->core.channels == channels && q->core.batch == batch && memcmp(&q->prm, prm, sizeof *prm) == 0;
+            return q->core.W == W && q->core.H == H && q->core.channels == channels && q->core.batch == batch && memcmp(&q->prm, prm, sizeof *prm) == 0 &&
+                   q->core.runner_up == ru;
         });
         if (*out) return FSGM_OK;
-        const fsgm_status st = pyramid_create(out, W, H, channels, batch, prm);
+        fsgm_status st = pyramid_create(out, W, H, channels, batch, prm);
+        if (st == FSGM_OK && ru && (st = pyramid_set_runner_up(*out, 1)) != FSGM_OK) { pyramid_destroy(*out); *out = nullptr; }
         if (st == FSGM_OK) this->insert(prm->device, *out);
         return st;
     }
@@ -216,36 +245,39 @@ struct PyramidPair {
     uint8_t *in0, *in1;                          // level-1 inputs, u8 [2n][channels][H][W]: first / second image of each frame
     const double* flow;                          // level-1 flow  [2n][2][H][W]
     const uint32_t* minC;                        // level-1 minC  [2n][H][W]
+    const uint32_t* minC2;                       // level-1 runner-up cost [2n][H][W]; null in a plan without the switch
     void* plan;
     fsgm_status (*run)(void* plan);              // the level loop on `stream`
 };
 
-// body(pair) under the device's lock, on the cached plan for 2n frames of this shape and these parameters
+// body(pair) under the device's lock, on the cached plan for 2n frames of this shape, these parameters and this runner-up switch
 template <class P, class Body>
-fsgm_status pyramid_with_pair(PyramidCache<P>& cache, int n, int W, int H, int channels, const typename P::Params* prm, Body&& body) {
+fsgm_status pyramid_with_pair(PyramidCache<P>& cache, int n, int W, int H, int channels, const typename P::Params* prm, int ru, Body&& body) {
     FSGM_REQUIRE(n >= 1 && n <= P::max_batch / 2, "%s: n_frames must be in 1..%d (got %d)", P::entry_name, P::max_batch / 2, n);
     FSGM_DEVICE_SLOT(prm->device);
     std::lock_guard<std::mutex> lk(cache.mu(prm->device));
     P* p = nullptr;
     fsgm_status st;
-    if ((st = cache.get(&p, W, H, channels, prm, 2 * n)) != FSGM_OK) return st;
+    if ((st = cache.get(&p, W, H, channels, prm, 2 * n, ru)) != FSGM_OK) return st;
     FSGM_HIP(hipSetDevice(prm->device));
     PyramidCore& c = p->core;
-    const PyramidPair pr{c.stream, c.ev0, c.ev1, &c.join, pyramid_input(p, 0), pyramid_input(p, 1), c.dFlow[0], p->minC(0), p,
+    const PyramidPair pr{c.stream, c.ev0, c.ev1, &c.join, pyramid_input(p, 0), pyramid_input(p, 1), c.dFlow[0], p->minC(0), ru ? p->minC2() : nullptr, p,
                          [](void* q) { return pyramid_enqueue(static_cast<P*>(q)); }};
     return body(pr);
 }
 
-// host pointers: one call = the whole loop on a cached plan
+// host pointers: one call = the whole loop on a cached plan.  ru: the _ru form, minC2 (never NULL there) of level 1 comes down too
 template <class P>
 fsgm_status pyramid_host(PyramidCache<P>& cache, const uint8_t* I0, const uint8_t* I1, int W, int H, int channels,
-                         const typename P::Params* prm, double* flow, uint32_t* minC, double* const* flowPyd) {
+                         const typename P::Params* prm, double* flow, uint32_t* minC, double* const* flowPyd, uint32_t* minC2 = nullptr,
+                         bool ru = false) {
     FSGM_REQUIRE(I0 && I1 && prm && flow, "%s: null argument", P::entry_name);
+    FSGM_REQUIRE(!ru || minC2, "%s_ru: null argument (minC2 is required)", P::entry_name);
     FSGM_DEVICE_SLOT(prm->device);
     std::lock_guard<std::mutex> lk(cache.mu(prm->device));
     P* p = nullptr;
     fsgm_status st;
-    if ((st = cache.get(&p, W, H, channels, prm, 1)) != FSGM_OK) return st;
+    if ((st = cache.get(&p, W, H, channels, prm, 1, ru)) != FSGM_OK) return st;
     // One call = one stream-ordered sequence with a single host wait (like fsgm_calc_cost_sgm_batch_host): the image pair goes up
     // asynchronously, the level loop follows, every requested map comes down behind it.  (Round 3's form waited after the
     // upload, after the run and once per downloaded map, with blocking copies: 6.3 ms per call around 1.4 ms of kernels.)
@@ -259,6 +291,7 @@ fsgm_status pyramid_host(PyramidCache<P>& cache, const uint8_t* I0, const uint8_
     const size_t np1 = (size_t)W * H;
     FSGM_HIP(hipMemcpyAsync(flow, c.dFlow[0], 2 * np1 * sizeof(double), hipMemcpyDeviceToHost, c.stream));
     if (minC) FSGM_HIP(hipMemcpyAsync(minC, p->minC(0), np1 * 4, hipMemcpyDeviceToHost, c.stream));
+    if (ru) FSGM_HIP(hipMemcpyAsync(minC2, p->minC2(), np1 * 4, hipMemcpyDeviceToHost, c.stream));
     if (flowPyd)
         for (int l = 0; l < prm->numPyd; l++)
             if (flowPyd[l] && flowPyd[l] != flow)
@@ -272,11 +305,13 @@ fsgm_status pyramid_host(PyramidCache<P>& cache, const uint8_t* I0, const uint8_
 // first reduce / gray / census kernels, the level-1 flow and minC are written in place -- no copy at either end
 template <class P>
 fsgm_status pyramid_device(PyramidCache<P>& cache, int32_t n, const uint8_t* I0, const uint8_t* I1, int W, int H, int channels,
-                           const typename P::Params* prm, double* flow, uint32_t* minC, void* stream, int32_t* status) {
+                           const typename P::Params* prm, double* flow, uint32_t* minC, void* stream, int32_t* status, uint32_t* minC2 = nullptr,
+                           bool ru = false) {
     char who[64];
-    snprintf(who, sizeof who, "%s_device", P::entry_name);
+    snprintf(who, sizeof who, "%s_device%s", P::entry_name, ru ? "_ru" : "");
     FSGM_REQUIRE(n >= 1, "%s: n_frames must be >= 1 (got %d)", who, n);
     FSGM_REQUIRE(I0 && I1 && prm && flow, "%s: null argument", who);
+    FSGM_REQUIRE(!ru || minC2, "%s: null argument (minC2 is required)", who);
     FSGM_REQUIRE(W >= 1 && H >= 1, "%s: width/height must be >= 1 (got %d x %d)", who, W, H);
     FSGM_REQUIRE(channels == 1 || channels == 3, "%s: channels must be 1 (gray) or 3 (RGB planes), got %d", who, channels);
     FSGM_DEVICE_SLOT(prm->device);
@@ -288,17 +323,19 @@ fsgm_status pyramid_device(PyramidCache<P>& cache, int32_t n, const uint8_t* I0,
                                                        {I1, np * channels, 1, true, "I1"},
                                                        {flow, np * 16, 8, true, P::flow_name},
                                                        {minC, np * 4, 4, false, "minC"},
+                                                       {ru ? minC2 : nullptr, np * 4, 4, ru, "minC2"},
                                                        {status, 4, 4, false, "status"}})) != FSGM_OK)
         return st;
     std::lock_guard<std::mutex> lk(cache.mu(prm->device));
     P* p = nullptr;
-    if ((st = cache.get(&p, W, H, channels, prm, n)) != FSGM_OK) return st;
+    if ((st = cache.get(&p, W, H, channels, prm, n, ru)) != FSGM_OK) return st;
     const hipStream_t ps = p->core.stream;
     return device_call(p->core.join, cs, ps, [&]() -> fsgm_status {
         Bind<uint8_t> i0(pyramid_input(p, 0), const_cast<uint8_t*>(I0));
         Bind<uint8_t> i1(pyramid_input(p, 1), const_cast<uint8_t*>(I1));
         Bind<double> fl(p->core.dFlow[0], flow);
         Bind<uint32_t> mc(p->minC(0), minC);
+        Bind<uint32_t> m2(ru ? p->minC2() : p->minC(0), ru ? minC2 : nullptr);   // (a null value binds nothing)
         const fsgm_status es = pyramid_enqueue(p);
         if (es == FSGM_OK) launch_device_status(ps, nullptr, nullptr, status);
         return es;

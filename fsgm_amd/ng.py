@@ -52,6 +52,9 @@ def _bind(lib):
     lib.fsgm_ng_sample_pixels.restype = C.c_uint64
     lib.fsgm_ng_last_decision.argtypes = [C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
                                           C.POINTER(C.c_uint32)]
+    if hasattr(lib, "fsgm_calc_pyd_cost_sgm_ng_host_ru"):        # (an older build behind FSGM_LIB_PATH has neither)
+        lib.fsgm_calc_pyd_cost_sgm_ng_host_ru.argtypes = [C.POINTER(NgIn), C.POINTER(NgOut), C.c_void_p, C.c_int32]
+        lib.fsgm_calc_pyd_cost_sgm_ng_batch_host_ru.argtypes = [C.c_int32, C.POINTER(NgIn), C.POINTER(NgOut), C.POINTER(C.c_void_p), C.c_int32]
     lib._ng_bound = True
 
 
@@ -63,7 +66,10 @@ def _images(I1, I2):
 
 
 def calc_pyd_cost_sgm_ng(I1, I2, preMv, halfSearchWinSize, aggSize, subPixelRefine, P1, P2, *, device=0,
-                         return_sum=False):
+                         return_sum=False, runner_up=False):
+    """runner_up=True: (minC, flow, minC2) -- or (minC, flow, minC2, S) with return_sum -- with the runner-up cost minC2 uint32
+    (height, width) of include/fsgm.h ("the neighbour-guided rule"): the smallest sum among the candidates whose motion vector
+    lies two or more away from the winner's, 0xFFFFFFFF where there is none."""
     lib = _lib.load()
     _bind(lib)
     I1, I2 = _images(I1, I2)
@@ -83,6 +89,10 @@ def calc_pyd_cost_sgm_ng(I1, I2, preMv, halfSearchWinSize, aggSize, subPixelRefi
     S = np.zeros((H, W, D), np.uint32) if return_sum else None
     o = NgOut()
     o.minC, o.flow, o.S = ptr(minC), ptr(flow), ptr(S)
+    if runner_up:
+        minC2 = np.zeros((H, W), np.uint32)
+        check(lib.fsgm_calc_pyd_cost_sgm_ng_host_ru(C.byref(a), C.byref(o), ptr(minC2), int(device)))
+        return (minC, flow, minC2, S) if return_sum else (minC, flow, minC2)
     check(lib.fsgm_calc_pyd_cost_sgm_ng_host(C.byref(a), C.byref(o), int(device)))
     return (minC, flow, S) if return_sum else (minC, flow)
 
@@ -150,9 +160,13 @@ def calc_cost_sgm_ng(I1, I2, preMv=None, halfSearchWinSize=1, aggSize=2, subPixe
     return minC, flow
 
 
-def calc_pyd_cost_sgm_ng_batch(frames, halfSearchWinSize, aggSize, subPixelRefine, P1, P2, *, device=0, devices=None):
+def calc_pyd_cost_sgm_ng_batch(frames, halfSearchWinSize, aggSize, subPixelRefine, P1, P2, *, device=0, devices=None,
+                               runner_up=False):
     """frames: list of (I1, I2, preMv) of one shape; one launch sequence for all of them.
-    Returns a list of (minC, flow).  devices: a device list (frame i on devices[i % len], fsgm_amd.calc_cost_sgm_batch)."""
+    Returns a list of (minC, flow), with runner_up=True of (minC, flow, minC2) (calc_pyd_cost_sgm_ng).  devices: a device list
+    (frame i on devices[i % len], fsgm_amd.calc_cost_sgm_batch); the device-list form has no runner-up cost."""
+    if runner_up and devices is not None:
+        raise ValueError("runner_up=True is not offered with a device list")
     lib = _lib.load()
     _bind(lib)
     n = len(frames)
@@ -170,8 +184,11 @@ def calc_pyd_cost_sgm_ng_batch(frames, halfSearchWinSize, aggSize, subPixelRefin
         minC, flow = np.zeros((H, W), np.uint32), np.zeros((2, H, W), np.float64)
         outs[i].minC, outs[i].flow, outs[i].S = ptr(minC), ptr(flow), None
         keep.append((I1, I2, preMv))
-        res.append((minC, flow))
-    if devices is not None:
+        res.append((minC, flow, np.zeros((H, W), np.uint32)) if runner_up else (minC, flow))
+    if runner_up:
+        m2 = (C.c_void_p * n)(*[r[2].ctypes.data for r in res])
+        check(lib.fsgm_calc_pyd_cost_sgm_ng_batch_host_ru(n, ins, outs, m2, int(device)))
+    elif devices is not None:
         nd, darr = _lib.device_array(devices)
         check(lib.fsgm_calc_pyd_cost_sgm_ng_batch_devices_host(n, ins, outs, nd, darr))
     else:

@@ -37,6 +37,10 @@ def _bind(lib):
     lib.fsgm_pyramid_plan_download_gray.argtypes = [vp, i32, vp, vp]
     lib.fsgm_pyramid_plan_download_gray_frame.argtypes = [vp, i32, i32, vp, vp]
     lib.fsgm_pyramid_plan_time.argtypes = [vp, i32, i32, C.POINTER(C.c_float)]
+    if hasattr(lib, "fsgm_pyramidal_sgm_host_ru"):               # (an older build behind FSGM_LIB_PATH has none of these)
+        lib.fsgm_pyramidal_sgm_host_ru.argtypes = [vp, vp, i32, i32, i32, C.POINTER(PyramidParams), vp, vp, vp, vp]
+        lib.fsgm_pyramid_plan_set_runner_up.argtypes = [vp, i32]
+        lib.fsgm_pyramid_plan_download_runner_up.argtypes = [vp, i32, vp]
     lib._pyramid_bound = True
 
 
@@ -68,8 +72,21 @@ def _check_images(I0, I1):
     return I0, I1, (1 if I0.ndim == 2 else 3)
 
 
-def pyramidal_sgm(I0, I1, numPyd=5, *, device=0, out=None, **overrides):
-    """[mvCurLevel, mvPyd, minC] = pyramidal_sgm(I0, I1, numPyd) (pyramidal_sgm.m:1).  Keyword overrides
+def _minC2_of(out, H, W):
+    """the minC2 array of a runner-up call: the fourth member of out=, else a new one"""
+    if out is None:
+        return np.empty((H, W), np.uint32)
+    if len(out) != 4:
+        raise ValueError("out does not match this call's shapes")
+    m2 = out[3]
+    if m2.shape != (H, W) or m2.dtype != np.uint32 or not m2.flags.c_contiguous:
+        raise ValueError("out does not match this call's shapes")
+    return m2
+
+
+def pyramidal_sgm(I0, I1, numPyd=5, *, device=0, out=None, runner_up=False, **overrides):
+    """[mvCurLevel, mvPyd, minC] = pyramidal_sgm(I0, I1, numPyd) (pyramidal_sgm.m:1).  runner_up=True: (mv, mvPyd, minC, minC2)
+    with level 1's runner-up cost minC2 uint32 (height, width) (include/fsgm.h, the 2-D rule).  Keyword overrides
     name the function's hard-coded parameters (P1, P2, aggHalfWinSize, verSearchHalfWinSize,
     horSearchHalfWinSize, enableDiagonal, totalPass, adaptiveP2; pyramidal_sgm.m:15-22).
     out: a previous call's result tuple to write into instead of allocating (the results of that call are overwritten): a loop
@@ -80,8 +97,9 @@ def pyramidal_sgm(I0, I1, numPyd=5, *, device=0, out=None, **overrides):
     H, W = I0.shape[-2:]
     prm = _params(lib.fsgm_pyramid_params_default, numPyd, device, overrides, "pyramidal_sgm")
     sizes = _level_sizes(W, H, prm.numPyd)
+    minC2 = _minC2_of(out, H, W) if runner_up else None
     if out is not None:
-        mv, mvPyd, minC = out
+        mv, mvPyd, minC = out[:3] if runner_up else out
         ok = (mv.shape == (2, H, W) and mv.dtype == np.float64 and minC.shape == (H, W) and minC.dtype == np.uint32 and len(mvPyd) == len(sizes)
               and all(a.shape == (2, h, w) and a.dtype == np.float64 and a.flags.c_contiguous for a, (w, h) in zip(mvPyd, sizes)))
         if not ok or not mv.flags.c_contiguous or not minC.flags.c_contiguous:
@@ -91,6 +109,9 @@ def pyramidal_sgm(I0, I1, numPyd=5, *, device=0, out=None, **overrides):
         minC = np.empty((H, W), np.uint32)
         mvPyd = [np.empty((2, h, w), np.float64) for (w, h) in sizes]
     ptrs = (C.c_void_p * len(mvPyd))(*[a.ctypes.data for a in mvPyd])
+    if runner_up:
+        check(lib.fsgm_pyramidal_sgm_host_ru(ptr(I0), ptr(I1), W, H, ch, C.byref(prm), ptr(mv), ptr(minC), ptr(minC2), ptrs))
+        return mv, mvPyd, minC, minC2
     check(lib.fsgm_pyramidal_sgm_host(ptr(I0), ptr(I1), W, H, ch, C.byref(prm), ptr(mv), ptr(minC), ptrs))
     return mv, mvPyd, minC
 
@@ -189,6 +210,16 @@ class _Plan:
         check(self._call("download_frame", int(frame), int(level), ptr(flow), ptr(minC)))
         return flow, minC
 
+    def set_runner_up(self, on=True):
+        """Level 1's WTA also writes the runner-up cost minC2 (include/fsgm.h, the matcher's own rule); nothing else changes."""
+        check(self._call("set_runner_up", 1 if on else 0))
+
+    def download_runner_up(self, frame=0):
+        """minC2 uint32 (height, width) of level 1 of the last run; refused while the switch is off."""
+        minC2 = np.empty((self.H, self.W), np.uint32)
+        check(self._call("download_runner_up", int(frame), ptr(minC2)))
+        return minC2
+
     def time(self, warmup=1, iters=5):
         ms = C.c_float()
         check(self._call("time", int(warmup), int(iters), C.byref(ms)))
@@ -242,6 +273,10 @@ def _bind_ng(lib):
     lib.fsgm_ng_pyramid_plan_download.argtypes = [vp, i32, vp, vp]
     lib.fsgm_ng_pyramid_plan_time.argtypes = [vp, i32, i32, C.POINTER(C.c_float)]
     lib.fsgm_pyramidal_sgm_ng_host.argtypes = [vp, vp, i32, i32, i32, C.POINTER(NgPyramidParams), vp, vp, vp]
+    if hasattr(lib, "fsgm_pyramidal_sgm_ng_host_ru"):            # (an older build behind FSGM_LIB_PATH has none of these)
+        lib.fsgm_pyramidal_sgm_ng_host_ru.argtypes = [vp, vp, i32, i32, i32, C.POINTER(NgPyramidParams), vp, vp, vp, vp]
+        lib.fsgm_ng_pyramid_plan_set_runner_up.argtypes = [vp, i32]
+        lib.fsgm_ng_pyramid_plan_download_runner_up.argtypes = [vp, i32, vp]
     lib._ng_pyramid_bound = True
 
 
@@ -269,7 +304,7 @@ def pyramidal_sgm_ng_batch(pairs, numPyd=3, *, devices=(0,), **overrides):
     return _pairs_over_devices(lib.fsgm_pyramidal_sgm_ng_batch_devices_host, prm, pairs, devices)
 
 
-def pyramidal_sgm_ng(I0, I1, numPyd=3, *, device=0, out=None, **overrides):
+def pyramidal_sgm_ng(I0, I1, numPyd=3, *, device=0, out=None, runner_up=False, **overrides):
     """The level loop of pyramidal_sgm.m (:24-76) with calc_pyd_cost_sgm_ng swapped in for calc_pyd_cost_sgm
     (BASELINE config 4): the neighbour-guided MEX takes the previous level's flow as its hint map and returns
     the flow itself (calc_pyd_cost_sgm_ng.cpp:458-480).  Defaults are the argument values of ng_sgm.m:20
@@ -277,15 +312,17 @@ def pyramidal_sgm_ng(I0, I1, numPyd=3, *, device=0, out=None, **overrides):
     by impyramid 'reduce' / rgb2gray, hints of a finer level = 2*imresize(flow, 2, 'nearest') (pyramidal_sgm.m:72);
     everything stays on the device between levels.
 
-    Returns (flow of level 1, [flow per level, coarsest first], minC of level 1)."""
+    Returns (flow of level 1, [flow per level, coarsest first], minC of level 1); with runner_up=True also minC2 of level 1,
+    the neighbour-guided runner-up cost of include/fsgm.h."""
     lib = _lib.load()
     _bind_ng(lib)
     I0, I1, ch = _check_images(I0, I1)
     H, W = I0.shape[-2:]
     prm = _params(lib.fsgm_ng_pyramid_params_default, numPyd, device, overrides, "pyramidal_sgm_ng")
     sizes = _level_sizes(W, H, prm.numPyd)
+    minC2 = _minC2_of(out, H, W) if runner_up else None
     if out is not None:                                      # a previous call's result tuple, overwritten (see pyramidal_sgm)
-        flow, lv, minC = out
+        flow, lv, minC = out[:3] if runner_up else out
         lv = list(lv)[::-1]                                  # returned coarsest first, filled finest first
         ok = (flow.shape == (2, H, W) and flow.dtype == np.float64 and minC.shape == (H, W) and minC.dtype == np.uint32 and len(lv) == len(sizes)
               and all(a.shape == (2, h, w) and a.dtype == np.float64 and a.flags.c_contiguous for a, (w, h) in zip(lv, sizes)))
@@ -296,6 +333,9 @@ def pyramidal_sgm_ng(I0, I1, numPyd=3, *, device=0, out=None, **overrides):
         minC = np.empty((H, W), np.uint32)
         lv = [np.empty((2, h, w), np.float64) for (w, h) in sizes]
     ptrs = (C.c_void_p * len(lv))(*[a.ctypes.data for a in lv])
+    if runner_up:
+        check(lib.fsgm_pyramidal_sgm_ng_host_ru(ptr(I0), ptr(I1), W, H, ch, C.byref(prm), ptr(flow), ptr(minC), ptr(minC2), ptrs))
+        return flow, lv[::-1], minC, minC2
     check(lib.fsgm_pyramidal_sgm_ng_host(ptr(I0), ptr(I1), W, H, ch, C.byref(prm), ptr(flow), ptr(minC), ptrs))
     return flow, lv[::-1], minC
 
@@ -319,6 +359,9 @@ def _bind_flow_pp(lib):
     lib.fsgm_pyramidal_flow_pp_host.argtypes = [i32, vp, vp, i32, i32, i32, prm, vp, vp, vp, vp, vp]
     lib.fsgm_pyramidal_flow_pp_device.argtypes = [i32, vp, vp, i32, i32, i32, prm, vp, vp, vp, vp, vp, vp, vp]
     lib.fsgm_pyramidal_flow_pp_time.argtypes = [i32, vp, vp, i32, i32, i32, prm, i32, i32, C.POINTER(C.c_float)]
+    if hasattr(lib, "fsgm_pyramidal_flow_pp_host_u"):            # (an older build behind FSGM_LIB_PATH has neither)
+        lib.fsgm_pyramidal_flow_pp_host_u.argtypes = [i32, vp, vp, i32, i32, i32, prm, i32, vp, vp, vp, vp, vp, vp]
+        lib.fsgm_pyramidal_flow_pp_device_u.argtypes = [i32, vp, vp, i32, i32, i32, prm, i32, vp, vp, vp, vp, vp, vp, vp, vp]
     lib._flow_pp_bound = True
 
 
@@ -356,7 +399,14 @@ def _flow_pp_images(I0, I1, batch):
     return I0, I1, 1 if per == 2 else 3, batch
 
 
-def pyramidal_flow_pp(I0, I1, numPyd=None, matcher="pyd", *, median=0, batch=None, device=0, **overrides):
+def uniqueness_ratio_of(ratio):
+    """the ratio as the C ABI takes it: an integer in [0, 100]"""
+    if isinstance(ratio, bool) or int(ratio) != ratio or not 0 <= int(ratio) <= 100:
+        raise ValueError(f"uniqueness_ratio must be an integer in [0, 100] (got {ratio!r})")
+    return int(ratio)
+
+
+def pyramidal_flow_pp(I0, I1, numPyd=None, matcher="pyd", *, median=0, batch=None, device=0, uniqueness_ratio=None, **overrides):
     """The consistency-checked, filtered flow of a pyramidal matcher (matcher="pyd": pyramidal_sgm, "ng": pyramidal_sgm_ng):
     forward and backward flow from one run of a plan of twice the batch, then on the device the chain of test.m:45-49 on
     vectors -- speckle filter of both flows, forward-backward check, island removal, KITTI hole fill, and vmf's median with
@@ -366,7 +416,12 @@ def pyramidal_flow_pp(I0, I1, numPyd=None, matcher="pyd", *, median=0, batch=Non
 
     Returns (flow_pp, flow_checked, flow_fwd, flow_bwd, minC): flow_pp (.., 3, height, width) float64 -- the filled u, v and
     the validity plane (1 where flow_checked is a number); flow_checked (.., 2, height, width) with NaN where rejected; the
-    raw flows of both directions; minC (.., height, width) uint32 of the forward run."""
+    raw flows of both directions; minC (.., height, width) uint32 of the forward run.
+
+    uniqueness_ratio=r (an integer in [0, 100]): the matcher also reports its runner-up cost, and the uniqueness test of
+    fsgm_amd.uniqueness_filter blanks the ambiguous pixels of the forward and of the backward flow, each by its own costs, ahead
+    of the chain.  The call then returns the five outputs plus minC2 of the forward run; the raw flows stay raw, and r = 0 gives
+    the same five outputs as a call without the keyword."""
     lib = _lib.load()
     _bind(lib)
     _bind_ng(lib)
@@ -376,6 +431,12 @@ def pyramidal_flow_pp(I0, I1, numPyd=None, matcher="pyd", *, median=0, batch=Non
     pp = np.empty((N, 3, H, W), np.float64)
     checked, fwd, bwd = (np.empty((N, 2, H, W), np.float64) for _ in range(3))
     minC = np.empty((N, H, W), np.uint32)
+    if uniqueness_ratio is not None:
+        minC2 = np.empty((N, H, W), np.uint32)
+        check(lib.fsgm_pyramidal_flow_pp_host_u(N, ptr(I0), ptr(I1), W, H, ch, C.byref(prm), uniqueness_ratio_of(uniqueness_ratio), ptr(pp),
+                                                ptr(checked), ptr(fwd), ptr(bwd), ptr(minC), ptr(minC2)))
+        outs = (pp, checked, fwd, bwd, minC, minC2)
+        return outs if batched else tuple(o[0] for o in outs)
     check(lib.fsgm_pyramidal_flow_pp_host(N, ptr(I0), ptr(I1), W, H, ch, C.byref(prm), ptr(pp), ptr(checked), ptr(fwd), ptr(bwd), ptr(minC)))
     outs = (pp, checked, fwd, bwd, minC)
     return outs if batched else tuple(o[0] for o in outs)

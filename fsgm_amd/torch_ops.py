@@ -15,7 +15,8 @@ on it), fsgm::epi_postprocess (status FSGM_ERR_INVALID when a D1 value is negati
 stereo fsgm::stereo_sgm_pp (the matcher and the chain of test.m:45-50) and fsgm::stereo_fb_check (status as fsgm::epi_postprocess),
 fsgm::stereo_sgm_ru (fsgm::stereo_sgm_range with the runner-up cost minC2 after minC) and fsgm::uniqueness_filter (status always 0);
 fsgm::sgm_ru and fsgm::sgm2d_ru (fsgm::sgm / fsgm::sgm2d with minC2 after minC) and fsgm::uniqueness_filter_planes (a map or a
-two-plane flow; status always 0).
+two-plane flow; status always 0); fsgm::pyramidal_sgm_ru and fsgm::pyramidal_sgm_ng_ru (the pyramids with level 1's minC2 after
+minC) and fsgm::pyramidal_flow_pp_u (fsgm::pyramidal_flow_pp with a uniqueness ratio ahead of the chain and minC2 after minC).
 
 One process must hold one HIP runtime.  torch brings its own libamdhip64; libfsgm_hip.so binds to it by soname when torch is
 imported first.  When the library was loaded first, torch afterwards maps a second runtime, and a stream or pointer of one
@@ -35,7 +36,8 @@ from .post import _bind as _bind_post
 from .stereo_pp import CHAIN_FIELDS as STEREO_PP_FIELDS, _bind as _bind_stereo_pp, pp_params as _stereo_pp_params
 from .sgm import _bind as _bind_sgm, layout_code as _layout_code, params as _sgm_params, shape_of as _sgm_shape
 from .sgm2d import _bind as _bind_sgm2d, layout_code as _layout2d_code, params as _sgm2d_params, shape_of as _sgm2d_shape, LAYOUTS as _LAYOUTS2D
-from .pyramid import PyramidParams, NgPyramidParams, FLOW_PP_FIELDS, MATCHERS, _bind as _bind_pyramid, _bind_flow_pp, _bind_ng
+from .pyramid import (PyramidParams, NgPyramidParams, FLOW_PP_FIELDS, MATCHERS, _bind as _bind_pyramid, _bind_flow_pp, _bind_ng,
+                      uniqueness_ratio_of as _uniqueness_ratio_of)
 
 FSGM_ERR_INVALID, FSGM_ERR_HIP = 1, 2
 
@@ -85,6 +87,9 @@ _L.fsgm_epipolar_flow_pp_device.argtypes = [_i32, _vp, _vp, _i32, _i32, _i32, C.
                                              C.POINTER(EpiParams), _vp, _vp, _vp, _vp, _vp, _vp]
 _L.fsgm_pyramidal_sgm_device.argtypes = [_i32, _vp, _vp, _i32, _i32, _i32, C.POINTER(PyramidParams), _vp, _vp, _vp, _vp]
 _L.fsgm_pyramidal_sgm_ng_device.argtypes = [_i32, _vp, _vp, _i32, _i32, _i32, C.POINTER(NgPyramidParams), _vp, _vp, _vp, _vp]
+if hasattr(_L, "fsgm_pyramidal_sgm_device_ru"):                  # (an older build behind FSGM_LIB_PATH has neither)
+    _L.fsgm_pyramidal_sgm_device_ru.argtypes = [_i32, _vp, _vp, _i32, _i32, _i32, C.POINTER(PyramidParams), _vp, _vp, _vp, _vp, _vp]
+    _L.fsgm_pyramidal_sgm_ng_device_ru.argtypes = [_i32, _vp, _vp, _i32, _i32, _i32, C.POINTER(NgPyramidParams), _vp, _vp, _vp, _vp, _vp]
 
 # the overridable fields of the pyramids' parameter structs, in the order the ops take them
 PYRAMID_FIELDS = ("P1", "P2", "aggHalfWinSize", "verSearchHalfWinSize", "horSearchHalfWinSize", "enableDiagonal", "totalPass", "adaptiveP2")
@@ -469,14 +474,55 @@ def _pyramid_outputs(I0):
     return _f64((N, 2, H, W), dev), _u32((N, H, W), dev), _status(dev)
 
 
-def _pyramid_run(fn, prm, I0, I1):
+def _pyramid_run(fn, prm, I0, I1, runner_up=False):
     N, H, W, dev = _frames(I0)
     ch = 1 if I0.dim() == 3 else 3
     prm.device = dev.index
     I0, I1 = _ready(I0), _ready(I1)
+    if runner_up:
+        mv, minC, minC2, status = _pyramid_ru_outputs(I0)
+        _call(dev, fn, N, _p(I0), _p(I1), W, H, ch, C.byref(prm), _p(mv), _p(minC), _p(minC2), _stream(dev), _p(status))
+        return mv, minC, minC2, status
     mv, minC, status = _pyramid_outputs(I0)
     _call(dev, fn, N, _p(I0), _p(I1), W, H, ch, C.byref(prm), _p(mv), _p(minC), _stream(dev), _p(status))
     return mv, minC, status
+
+
+def _pyramid_ru_outputs(I0):
+    N, H, W, dev = _frames(I0)
+    return _f64((N, 2, H, W), dev), _u32((N, H, W), dev), _u32((N, H, W), dev), _status(dev)
+
+
+def _pyramid_prm(default, fields, numPyd, params):
+    prm = default()
+    prm.numPyd = int(numPyd)
+    for k, v in zip(fields, params, strict=True):
+        setattr(prm, k, int(v))
+    return prm
+
+
+@torch.library.custom_op("fsgm::pyramidal_sgm_ru", mutates_args=())
+def _pyramidal_sgm_ru_op(I0: torch.Tensor, I1: torch.Tensor, numPyd: int,
+                         params: List[int]) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    prm = _pyramid_prm(_L.fsgm_pyramid_params_default, PYRAMID_FIELDS, numPyd, params)
+    return _pyramid_run(_L.fsgm_pyramidal_sgm_device_ru, prm, I0, I1, True)
+
+
+@_pyramidal_sgm_ru_op.register_fake
+def _(I0, I1, numPyd, params):
+    return _pyramid_ru_outputs(I0)
+
+
+@torch.library.custom_op("fsgm::pyramidal_sgm_ng_ru", mutates_args=())
+def _pyramidal_sgm_ng_ru_op(I0: torch.Tensor, I1: torch.Tensor, numPyd: int,
+                            params: List[int]) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    prm = _pyramid_prm(_L.fsgm_ng_pyramid_params_default, NG_PYRAMID_FIELDS, numPyd, params)
+    return _pyramid_run(_L.fsgm_pyramidal_sgm_ng_device_ru, prm, I0, I1, True)
+
+
+@_pyramidal_sgm_ng_ru_op.register_fake
+def _(I0, I1, numPyd, params):
+    return _pyramid_ru_outputs(I0)
 
 
 @torch.library.custom_op("fsgm::pyramidal_sgm", mutates_args=())
@@ -515,11 +561,7 @@ def _pyramidal_flow_pp_outputs(I0):
             _u32((N, H, W), dev), _status(dev))
 
 
-@torch.library.custom_op("fsgm::pyramidal_flow_pp", mutates_args=())
-def _pyramidal_flow_pp_op(I0: torch.Tensor, I1: torch.Tensor, matcher: int, numPyd: int, params: List[int], chain: List[float],
-                          median: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
-    N, H, W, dev = _frames(I0)
-    ch = 1 if I0.dim() == 3 else 3
+def _flow_pp_prm(matcher, numPyd, params, chain, median, dev):
     prm = _L.fsgm_flow_pp_params_default(int(matcher))
     sub, fields = (prm.ng, NG_PYRAMID_FIELDS) if matcher == MATCHERS["ng"] else (prm.pyd, PYRAMID_FIELDS)
     sub.numPyd = int(numPyd)
@@ -528,6 +570,36 @@ def _pyramidal_flow_pp_op(I0: torch.Tensor, I1: torch.Tensor, matcher: int, numP
     for k, v in zip(FLOW_PP_FIELDS, chain, strict=True):
         setattr(prm, k, float(v))
     prm.median, prm.device = int(median), dev.index
+    return prm
+
+
+@torch.library.custom_op("fsgm::pyramidal_flow_pp_u", mutates_args=())
+def _pyramidal_flow_pp_u_op(I0: torch.Tensor, I1: torch.Tensor, matcher: int, numPyd: int, params: List[int], chain: List[float],
+                            median: int, uniqueness_ratio: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor,
+                                                                         torch.Tensor, torch.Tensor, torch.Tensor]:
+    N, H, W, dev = _frames(I0)
+    ch = 1 if I0.dim() == 3 else 3
+    prm = _flow_pp_prm(matcher, numPyd, params, chain, median, dev)
+    I0, I1 = _ready(I0), _ready(I1)
+    pp, checked, fwd, bwd, minC, status = _pyramidal_flow_pp_outputs(I0)
+    minC2 = torch.empty_like(minC)
+    _call(dev, _L.fsgm_pyramidal_flow_pp_device_u, N, _p(I0), _p(I1), W, H, ch, C.byref(prm), int(uniqueness_ratio), _p(pp), _p(checked),
+          _p(fwd), _p(bwd), _p(minC), _p(minC2), _stream(dev), _p(status))
+    return pp, checked, fwd, bwd, minC, minC2, status
+
+
+@_pyramidal_flow_pp_u_op.register_fake
+def _(I0, I1, matcher, numPyd, params, chain, median, uniqueness_ratio):
+    pp, checked, fwd, bwd, minC, status = _pyramidal_flow_pp_outputs(I0)
+    return pp, checked, fwd, bwd, minC, torch.empty_like(minC), status
+
+
+@torch.library.custom_op("fsgm::pyramidal_flow_pp", mutates_args=())
+def _pyramidal_flow_pp_op(I0: torch.Tensor, I1: torch.Tensor, matcher: int, numPyd: int, params: List[int], chain: List[float],
+                          median: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    N, H, W, dev = _frames(I0)
+    ch = 1 if I0.dim() == 3 else 3
+    prm = _flow_pp_prm(matcher, numPyd, params, chain, median, dev)
     I0, I1 = _ready(I0), _ready(I1)
     pp, checked, fwd, bwd, minC, status = _pyramidal_flow_pp_outputs(I0)
     _call(dev, _L.fsgm_pyramidal_flow_pp_device, N, _p(I0), _p(I1), W, H, ch, C.byref(prm), _p(pp), _p(checked), _p(fwd), _p(bwd),
@@ -1100,28 +1172,37 @@ def _overrides(fields, defaults, overrides, name):
     return [int(overrides.get(k, getattr(defaults, k))) for k in fields]
 
 
-def pyramidal_sgm(I0, I1, numPyd=5, *, batch=None, check=False, return_status=False, **overrides):
+def pyramidal_sgm(I0, I1, numPyd=5, *, batch=None, check=False, return_status=False, runner_up=False, **overrides):
     """(mv, minC) of level 1 of pyramidal_sgm(I0, I1, numPyd) as fsgm_amd.pyramidal_sgm, on torch tensors on the GPU (the per-level
     flows are not offered).  Images (H, W) or RGB (3, H, W) uint8, or a batch with a leading N; batch=None infers it (a 3-D tensor
-    with 3 planes is one RGB pair).  mv (.., 2, H, W) float64, minC (.., H, W) uint32.  Keyword overrides as fsgm_amd.pyramidal_sgm."""
+    with 3 planes is one RGB pair).  mv (.., 2, H, W) float64, minC (.., H, W) uint32.  Keyword overrides as fsgm_amd.pyramidal_sgm.
+    runner_up=True: (mv, minC, minC2) with level 1's runner-up cost (fsgm::pyramidal_sgm_ru)."""
     I0, I1, batched = _pyramid_images(I0, I1, batch)
     params = _overrides(PYRAMID_FIELDS, _L.fsgm_pyramid_params_default(), overrides, "pyramidal_sgm")
+    if runner_up:
+        mv, minC, minC2, status = torch.ops.fsgm.pyramidal_sgm_ru(I0, I1, int(numPyd), params)
+        return _finish((mv, minC, minC2), status, batched, check, return_status)
     mv, minC, status = torch.ops.fsgm.pyramidal_sgm(I0, I1, int(numPyd), params)
     return _finish((mv, minC), status, batched, check, return_status)
 
 
-def pyramidal_sgm_ng(I0, I1, numPyd=3, *, batch=None, check=False, return_status=False, **overrides):
+def pyramidal_sgm_ng(I0, I1, numPyd=3, *, batch=None, check=False, return_status=False, runner_up=False, **overrides):
     """(flow, minC) of level 1 of the pyramidal loop around calc_pyd_cost_sgm_ng as fsgm_amd.pyramidal_sgm_ng, on torch tensors
-    on the GPU; shapes and batch as pyramidal_sgm."""
+    on the GPU; shapes and batch as pyramidal_sgm.  runner_up=True: (flow, minC, minC2) (fsgm::pyramidal_sgm_ng_ru)."""
     I0, I1, batched = _pyramid_images(I0, I1, batch)
     params = _overrides(NG_PYRAMID_FIELDS, _L.fsgm_ng_pyramid_params_default(), overrides, "pyramidal_sgm_ng")
+    if runner_up:
+        flow, minC, minC2, status = torch.ops.fsgm.pyramidal_sgm_ng_ru(I0, I1, int(numPyd), params)
+        return _finish((flow, minC, minC2), status, batched, check, return_status)
     flow, minC, status = torch.ops.fsgm.pyramidal_sgm_ng(I0, I1, int(numPyd), params)
     return _finish((flow, minC), status, batched, check, return_status)
 
 
-def pyramidal_flow_pp(I0, I1, numPyd=None, matcher="pyd", *, median=0, batch=None, check=False, return_status=False, **overrides):
+def pyramidal_flow_pp(I0, I1, numPyd=None, matcher="pyd", *, median=0, batch=None, check=False, return_status=False,
+                      uniqueness_ratio=None, **overrides):
     """(flow_pp, flow_checked, flow_fwd, flow_bwd, minC) as fsgm_amd.pyramidal_flow_pp, on torch tensors on the GPU; images and
-    batch as pyramidal_sgm.  flow_pp (.., 3, H, W), the flows (.., 2, H, W) float64, minC (.., H, W) uint32."""
+    batch as pyramidal_sgm.  flow_pp (.., 3, H, W), the flows (.., 2, H, W) float64, minC (.., H, W) uint32.
+    uniqueness_ratio=r: the five outputs plus minC2, with the uniqueness test ahead of the chain (fsgm::pyramidal_flow_pp_u)."""
     if matcher not in MATCHERS:
         raise ValueError(f"matcher must be 'pyd' or 'ng' (got {matcher!r})")
     I0, I1, batched = _pyramid_images(I0, I1, batch)
@@ -1129,6 +1210,10 @@ def pyramidal_flow_pp(I0, I1, numPyd=None, matcher="pyd", *, median=0, batch=Non
     sub, fields = (defaults.ng, NG_PYRAMID_FIELDS) if matcher == "ng" else (defaults.pyd, PYRAMID_FIELDS)
     chain = [float(overrides.pop(k, getattr(defaults, k))) for k in FLOW_PP_FIELDS]
     params = _overrides(fields, sub, overrides, "pyramidal_flow_pp")
+    if uniqueness_ratio is not None:
+        *outs, status = torch.ops.fsgm.pyramidal_flow_pp_u(I0, I1, MATCHERS[matcher], int(sub.numPyd if numPyd is None else numPyd), params,
+                                                           chain, int(median), _uniqueness_ratio_of(uniqueness_ratio))
+        return _finish(outs, status, batched, check, return_status)
     *outs, status = torch.ops.fsgm.pyramidal_flow_pp(I0, I1, MATCHERS[matcher], int(sub.numPyd if numPyd is None else numPyd), params,
                                                      chain, int(median))
     return _finish(outs, status, batched, check, return_status)

@@ -229,6 +229,22 @@ fsgm_status fsgm_uniqueness_filter_planes_host(int32_t n_frames, const double* m
 fsgm_status fsgm_uniqueness_filter_planes_device(int32_t n_frames, const double* map, const uint32_t* minC, const uint32_t* minC2,
                                                  int32_t width, int32_t height, int32_t planes, int32_t ratio, double* out,
                                                  int32_t device, void* stream, int32_t* status);
+/* The runner-up cost of the neighbour-guided matcher (calc_pyd_cost_sgm_ng, the level of fsgm_pyramidal_sgm_ng).  A pixel has
+ * D = 9 (2r+1)^2 candidates, each with an integer motion vector (mvx_d, mvy_d) and a u32 sum S[d] -- what the S tap returns.  The
+ * winner is the first minimum of S over d, as without the switch; let (bx, by) be its vector:
+ *   minC2 = min { S[d] : max(|mvx_d - bx|, |mvy_d - by|) >= 2 },  FSGM_NO_RUNNER_UP where that set is empty.
+ * The distance is between motion vectors, not list indices (the differences are exact for every int32 vector): the same
+ * "Chebyshev distance >= 2" as the 2-D rule.  Repeats of the winner's vector -- the nine neighbours' hints overlap, so lists are
+ * full of them -- are never runners-up, whatever their sums.  The consequence: where all nine neighbours' hints (those of
+ * (x +- 8, y +- 8), clamped to the map) agree on h, every candidate lies within distance 1 of h when r <= 1.  With r = 0, or
+ * with r = 1 and h itself the winner, no runner-up exists and the uniqueness test keeps the pixel: the matcher considered one
+ * hypothesis there, which says nothing against it.  With r = 1 and a winner on the ring around h, the ring's other side is two
+ * away and competes, by the rule as it stands.
+ * minC, flow and S of a call that asks for minC2 are bit-identical to those of the same call without it, with and without
+ * subPixelRefine; minC2 does not depend on subPixelRefine.
+ * Entry points: fsgm_calc_pyd_cost_sgm_ng_host_ru / _batch_host_ru; for level 1 of the pyramids (both matchers, each by its
+ * own rule) fsgm_pyramidal_sgm_host_ru / _device_ru, fsgm_pyramidal_sgm_ng_host_ru / _device_ru, fsgm_pyramid_plan_set_runner_up
+ * / _download_runner_up and the same pair of fsgm_ng_pyramid_plan_*; with the filter fsgm_pyramidal_flow_pp_host_u / _device_u. */
 
 /* ---- device-resident plan: buffers for `batch` frames stay in HBM across calls ---- */
 typedef struct fsgm_epi_plan fsgm_epi_plan;
@@ -659,6 +675,16 @@ fsgm_status fsgm_pyramid_plan_download_gray(fsgm_pyramid_plan* plan, int32_t lev
 fsgm_status fsgm_pyramid_plan_download_gray_frame(fsgm_pyramid_plan* plan, int32_t frame, int32_t level, uint8_t* gray0, uint8_t* gray1);
 /* average milliseconds of one whole pyramid run (HIP events on the plan's stream) */
 fsgm_status fsgm_pyramid_plan_time(fsgm_pyramid_plan* plan, int32_t warmup, int32_t iters, float* ms_avg);
+/* The 2-D runner-up cost (FSGM_NO_RUNNER_UP above) of level 1, 0 at creation: with the switch on the last level's WTA also writes
+ * minC2 u32 [H][W] per frame; no other level, kernel or output changes.  _download_runner_up (synchronous) is FSGM_ERR_INVALID
+ * while the switch is off. */
+fsgm_status fsgm_pyramid_plan_set_runner_up(fsgm_pyramid_plan* plan, int32_t on);
+fsgm_status fsgm_pyramid_plan_download_runner_up(fsgm_pyramid_plan* plan, int32_t frame, uint32_t* minC2);
+/* fsgm_pyramidal_sgm_host with minC2 u32 [H][W] of level 1 after minC; minC2 must not be NULL (FSGM_ERR_INVALID before a device
+ * is touched).  Its cached plan is never the one of a call without minC2, nor the reverse. */
+fsgm_status fsgm_pyramidal_sgm_host_ru(const uint8_t* I0, const uint8_t* I1, int32_t width, int32_t height,
+                                       int32_t channels, const fsgm_pyramid_params* prm,
+                                       double* mv, uint32_t* minC, uint32_t* minC2, double* const* mvPyd);
 
 /* ---- the pyramidal level loop with the neighbour-guided matcher ----
  * BASELINE config 4 names calc_pyd_cost_sgm_ng for the pyramidal path.  The reference ships that MEX as a swap-in
@@ -697,6 +723,13 @@ fsgm_status fsgm_ng_pyramid_plan_time(fsgm_ng_pyramid_plan* plan, int32_t warmup
 fsgm_status fsgm_pyramidal_sgm_ng_host(const uint8_t* I0, const uint8_t* I1, int32_t width, int32_t height,
                                        int32_t channels, const fsgm_ng_pyramid_params* prm,
                                        double* flow, uint32_t* minC, double* const* flowPyd);
+/* The neighbour-guided runner-up cost (FSGM_NO_RUNNER_UP above) of level 1: switch, download and one-call form as for
+ * fsgm_pyramid_plan_set_runner_up / _download_runner_up / fsgm_pyramidal_sgm_host_ru */
+fsgm_status fsgm_ng_pyramid_plan_set_runner_up(fsgm_ng_pyramid_plan* plan, int32_t on);
+fsgm_status fsgm_ng_pyramid_plan_download_runner_up(fsgm_ng_pyramid_plan* plan, int32_t frame, uint32_t* minC2);
+fsgm_status fsgm_pyramidal_sgm_ng_host_ru(const uint8_t* I0, const uint8_t* I1, int32_t width, int32_t height,
+                                          int32_t channels, const fsgm_ng_pyramid_params* prm,
+                                          double* flow, uint32_t* minC, uint32_t* minC2, double* const* flowPyd);
 
 
 /* ------------------------------------------------------------------------------------------
@@ -837,6 +870,20 @@ fsgm_status fsgm_pyramidal_flow_pp_host(int32_t n_frames, const uint8_t* I0, con
 fsgm_status fsgm_pyramidal_flow_pp_device(int32_t n_frames, const uint8_t* I0, const uint8_t* I1, int32_t width, int32_t height,
                                           int32_t channels, const fsgm_flow_pp_params* prm, double* flow_pp, double* flow_checked,
                                           double* flow_fwd, double* flow_bwd, uint32_t* minC, void* stream, int32_t* status);
+/* The same with the uniqueness test (fsgm_uniqueness_filter_planes_host above, its exact inequality) ahead of the chain.  The
+ * plan of 2n pairs runs with its runner-up switch on -- a cached plan of its own -- and both planes of an ambiguous pixel of f
+ * and of b are blanked, each flow by its own minC and minC2, before the first speckle filter; the chain treats them like any
+ * other rejected pixel.  uniqueness_ratio in [0, 100] (FSGM_ERR_INVALID otherwise); 0 rejects nothing and gives the outputs of
+ * the plain forms bit for bit.  flow_fwd and flow_bwd are the raw flows, as above; minC and minC2 u32 [n][H][W] are the forward
+ * run's, minC2 (the matcher's own rule: 2-D or neighbour-guided) must not be NULL.  Refusals come before a device is touched. */
+fsgm_status fsgm_pyramidal_flow_pp_host_u(int32_t n_frames, const uint8_t* I0, const uint8_t* I1, int32_t width, int32_t height,
+                                          int32_t channels, const fsgm_flow_pp_params* prm, int32_t uniqueness_ratio,
+                                          double* flow_pp, double* flow_checked, double* flow_fwd, double* flow_bwd, uint32_t* minC,
+                                          uint32_t* minC2);
+fsgm_status fsgm_pyramidal_flow_pp_device_u(int32_t n_frames, const uint8_t* I0, const uint8_t* I1, int32_t width, int32_t height,
+                                            int32_t channels, const fsgm_flow_pp_params* prm, int32_t uniqueness_ratio,
+                                            double* flow_pp, double* flow_checked, double* flow_fwd, double* flow_bwd, uint32_t* minC,
+                                            uint32_t* minC2, void* stream, int32_t* status);
 /* average milliseconds (HIP events on the plan's stream, images uploaded once before) of the batch-2n pyramid run, ms[0],
  * and of the chain behind it, ms[1], for host images as fsgm_pyramidal_flow_pp_host takes them */
 fsgm_status fsgm_pyramidal_flow_pp_time(int32_t n_frames, const uint8_t* I0, const uint8_t* I1, int32_t width, int32_t height,
@@ -941,6 +988,12 @@ typedef struct {
 fsgm_status fsgm_calc_pyd_cost_sgm_ng_host(const fsgm_ng_in* in, const fsgm_ng_out* out, int32_t device);
 fsgm_status fsgm_calc_pyd_cost_sgm_ng_batch_host(int32_t n_frames, const fsgm_ng_in* in,
                                                  const fsgm_ng_out* out, int32_t device);
+/* The same with the neighbour-guided runner-up cost (FSGM_NO_RUNNER_UP above): minC2 u32 [H][W], minC2s[i] that of frame i.  A
+ * NULL minC2, minC2s or one NULL among its entries is FSGM_ERR_INVALID before a device is touched.  fsgm_ng_in and fsgm_ng_out
+ * are what they were.  The device-list form below has no such sibling. */
+fsgm_status fsgm_calc_pyd_cost_sgm_ng_host_ru(const fsgm_ng_in* in, const fsgm_ng_out* out, uint32_t* minC2, int32_t device);
+fsgm_status fsgm_calc_pyd_cost_sgm_ng_batch_host_ru(int32_t n_frames, const fsgm_ng_in* in, const fsgm_ng_out* out,
+                                                    uint32_t* const* minC2s, int32_t device);
 
 /* Diagnostics: which aggregation kernel a level of calc_pyd_cost_sgm_ng takes.  All of them give the same results; the choice
  * is one of speed, made per level from the level's shape, the frame count, the FSGM_NG_* environment and -- on the device -- the
@@ -1179,6 +1232,14 @@ fsgm_status fsgm_pyramidal_sgm_device(int32_t n_frames, const uint8_t* I0, const
 fsgm_status fsgm_pyramidal_sgm_ng_device(int32_t n_frames, const uint8_t* I0, const uint8_t* I1, int32_t width,
                                          int32_t height, int32_t channels, const fsgm_ng_pyramid_params* prm,
                                          double* flow, uint32_t* minC, void* stream, int32_t* status);
+/* the same with level 1's runner-up cost minC2 u32 [n][H][W] (required, device memory, checked like minC), written where it lies
+ * by the last level's WTA; a cached plan of its own */
+fsgm_status fsgm_pyramidal_sgm_device_ru(int32_t n_frames, const uint8_t* I0, const uint8_t* I1, int32_t width,
+                                         int32_t height, int32_t channels, const fsgm_pyramid_params* prm,
+                                         double* mv, uint32_t* minC, uint32_t* minC2, void* stream, int32_t* status);
+fsgm_status fsgm_pyramidal_sgm_ng_device_ru(int32_t n_frames, const uint8_t* I0, const uint8_t* I1, int32_t width,
+                                            int32_t height, int32_t channels, const fsgm_ng_pyramid_params* prm,
+                                            double* flow, uint32_t* minC, uint32_t* minC2, void* stream, int32_t* status);
 
 #ifdef __cplusplus
 }
