@@ -1150,7 +1150,7 @@ const char* fsgm_epi_auto_pipeline_opts(int32_t width, int32_t height, int32_t d
     return kPipelineName[choose_pipeline(width, height, dMax, batch, paths, P1, P2, cmax, 0, cus, opt && opt->adaptive_p2)];
 }
 
-// the launchers' own selector (select_cost_kernels, epi_kernels.hip) for a shape a plan of this sampling would accept
+// the launchers' own selector (select_cost_kernels, epi_cost.hip) for a shape a plan of this sampling would accept
 fsgm_status fsgm_epi_cost_kernels(int32_t W, int32_t H, int32_t dMax, int32_t sampling, char* buf, size_t buflen) {
     FSGM_REQUIRE(buf && buflen > 0, "fsgm_epi_cost_kernels: null or empty buffer");
     buf[0] = 0;

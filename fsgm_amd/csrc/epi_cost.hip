@@ -1,6 +1,7 @@
-// epi_cost.hip -- the cost stage of calc_cost_sgm as ONE kernel: raw census cost along the epipolar line
-// (calc_cost_sgm.cpp:343-381) and its 5x5 box mean with replicate border (:387-407) without the raw volume ever
-// reaching HBM.  gfx950 only.
+// epi_cost.hip -- the cost stage of calc_cost_sgm, every form of it and the selector between them (select_cost_kernels).
+// First as ONE kernel: raw census cost along the epipolar line (calc_cost_sgm.cpp:343-381) and its 5x5 box mean with
+// replicate border (:387-407) without the raw volume ever reaching HBM.  gfx950 only.  The two-kernel form -- a raw-cost
+// kernel into a volume in HBM, then one of three box kernels -- follows it: every D the fused kernel does not take.
 //
 // Who does what.  A lane owns one pixel column x and 16 consecutive d; wave w of a workgroup owns d = 16 w .. 16 w + 15
 // (D / 16 waves: 8 at D = 128), all waves the same 64 columns.  Neighbouring lanes are neighbouring pixels at the same d,
@@ -391,6 +392,368 @@ static void launch_costbox(hipStream_t st, const EpiCostArgs& a, uint8_t* C, int
 }
 
 void launch_epi_costbox(hipStream_t st, const EpiCostArgs& a, uint8_t* C, int frames) { launch_costbox(st, a, C, frames, 0); }
+
+// =============================================================================================
+// The two-kernel form: raw Hamming cost along the epipolar line  (calc_cost_sgm.cpp:343-381) into a raw volume in HBM.
+// One thread = one pixel x 4 consecutive d.  fp64 geometry in the reference's association
+// order with explicit round-to-nearest mul/add (no FMA contraction).
+// =============================================================================================
+template <bool VEC4>                                       // VEC4: D % 4 == 0, no per-element guards, one u32 store
+__global__ __launch_bounds__(256) void epi_rawcost_kernel(EpiCostArgs a) {
+    const int W = a.W, H = a.H, D = a.D;
+    const int NP = W * H;
+    const int Dq = (D + 3) >> 2;
+    const uint32_t gid = blockIdx.x * 256u + threadIdx.x;        // NP * Dq < 2^31 (checked on the host)
+    if (gid >= (uint32_t)NP * (uint32_t)Dq) return;
+    const int p = (int)(gid / (uint32_t)Dq), q = (int)(gid - (uint32_t)p * (uint32_t)Dq);
+    const size_t f = blockIdx.y;
+    const double* __restrict__ p0 = a.pd0 + f * 2 * (size_t)NP;
+    const double* __restrict__ nd = a.nd + f * 2 * (size_t)NP;
+    const double bx = __dsub_rn(p0[p], 1.0), by = __dsub_rn(p0[NP + p], 1.0);          // :348-349
+    const double ux = nd[p], uy = nd[NP + p];
+    const double off = a.off[f * (size_t)NP + p];
+    const uint32_t* __restrict__ cen2 = a.cen2 + f * (size_t)NP;
+    const uint32_t c1 = a.cen1[f * (size_t)NP + p];
+    uint8_t* out = a.Craw + f * (size_t)NP * D + (uint32_t)p * (uint32_t)D + 4u * q;
+    const double* __restrict__ vz = a.vz + 4 * q;
+    uint32_t packed = 0;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        if (VEC4 || 4 * q + k < D) {
+            const double s = __dmul_rn(off, vz[k]);                                        // offset * vzInd
+            const double ox = __dmul_rn(s, ux), oy = __dmul_rn(s, uy);                    // :365-366
+            int x2 = round_to_i32_x86(__dadd_rn(bx, ox));                                 // :371
+            int y2 = round_to_i32_x86(__dadd_rn(by, oy));                                 // :372
+            x2 = clampi(x2, 0, W - 1);
+            y2 = clampi(y2, 0, H - 1);
+            const uint32_t cost = __popc(c1 ^ cen2[y2 * W + x2]);                         // :377-378
+            packed |= cost << (8 * k);
+        }
+    }
+    if (VEC4) {
+        *(uint32_t*)out = packed;
+    } else {
+        for (int k = 0; k < 4; k++)
+            if (4 * q + k < D) out[k] = (uint8_t)(packed >> (8 * k));
+    }
+}
+
+// Same for D % 8 == 0, one thread = one pixel, all d.  Neighbouring lanes are neighbouring pixels at the
+// same d, so the gather of the second image's census word touches two or three cache lines per wave
+// whatever the direction of the epipolar lines (with d across lanes every lane lands in its own line and
+// the kernel is bound by the L1 tag rate); vzInd(d) is wave-uniform and comes from scalar loads; the
+// per-pixel maps are read once, coalesced.  The 8 costs of a chunk are packed and parked in a per-wave
+// LDS tile [64 px][128 B + 8 pad] and written out as full 128-B lines.  ~30 VALU instructions per voxel,
+// most of them the reference's own fp64 sequence (3 mul, 2 add, 2 x round-half-away + truncate).
+// SMALL: every sample position of the wave is below 2^30 in magnitude (checked per pixel from the maps and
+// max |vzInd|), so the rounding needs no range test.
+constexpr int RC_SEG = 128, RC_PAD = RC_SEG + 8;
+template <bool SMALL>
+__device__ __forceinline__ void epi_rawcost_px_body(const EpiCostArgs& a, uint8_t* tilew, const uint32_t pw, const uint32_t p,
+                                                    const double bx, const double by, const double ux, const double uy, const double off) {
+    const int W = a.W, H = a.H, D = a.D;
+    const uint32_t NP = (uint32_t)W * (uint32_t)H;
+    const int lane = threadIdx.x & 63;
+    const size_t f = blockIdx.y;
+    const char* __restrict__ cen2 = (const char*)(a.cen2 + f * (size_t)NP);
+    const uint32_t c1 = a.cen1[f * (size_t)NP + p];
+    const double* __restrict__ vzt = a.vz;
+    const int xhi = W - 1, yhi = H - 1;
+    const uint32_t W4 = 4u * (uint32_t)W;
+    uint8_t* const myrow = tilew + lane * RC_PAD;
+    uint8_t* const outw = a.Craw + f * (size_t)NP * D + (size_t)pw * D;
+    // byte offsets of the 8 census words chunk (d0 + c) of this pixel samples: the reference's fp64 sequence per voxel
+    auto sample_offsets = [&](const int dbase, uint32_t (&boff)[8]) {
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+            const double s = __dmul_rn(off, vzt[dbase + k]);                                  // offset * vzInd
+            const double ox = __dmul_rn(s, ux), oy = __dmul_rn(s, uy);                        // :365-366
+            const double vx = __dadd_rn(bx, ox), vy = __dadd_rn(by, oy);
+            const int x2 = SMALL ? round_clamp_small(vx, xhi) : clamp0(round_to_i32_x86(vx), xhi);   // :371, :374
+            const int y2 = SMALL ? round_clamp_small(vy, yhi) : clamp0(round_to_i32_x86(vy), yhi);   // :372, :375
+            boff[k] = __umul24((uint32_t)y2, W4) + ((uint32_t)x2 << 2);                       // 4W, H < 2^24 (launcher)
+        }
+    };
+    for (int d0 = 0; d0 < D; d0 += RC_SEG) {
+        const int sb = min(RC_SEG, D - d0);
+        // Software pipeline over the chunks of 8 d: the gathered census words of chunk c are requested before the
+        // arithmetic of chunk c+1 (some 200 instructions) and consumed after it, so the gather's latency -- L2 hits, a
+        // few hundred cycles -- no longer parks the wave once per chunk (round 3 counters: 29 % of the wave time in
+        // s_waitcnt with the loads waited for where they were issued).
+        uint32_t boff[8], word[8];
+        sample_offsets(d0, boff);
+#pragma unroll
+        for (int k = 0; k < 8; k++) word[k] = *(const uint32_t*)(cen2 + boff[k]);
+        for (int c = 0; c < sb; c += 8) {
+            uint32_t nword[8];
+            if (c + 8 < sb) {                                                                 // wave-uniform
+                sample_offsets(d0 + c + 8, boff);
+#pragma unroll
+                for (int k = 0; k < 8; k++) nword[k] = *(const uint32_t*)(cen2 + boff[k]);
+            }
+            uint32_t packed[2] = {0, 0};
+#pragma unroll
+            for (int k = 0; k < 8; k++) {
+                const uint32_t cost = __popc(c1 ^ word[k]);                                   // :377-378
+                asm("v_lshl_or_b32 %0, %1, %2, %0" : "+v"(packed[k >> 2]) : "v"(cost), "n"(8 * (k & 3)));
+            }
+            *(uint2*)(myrow + c) = make_uint2(packed[0], packed[1]);
+#pragma unroll
+            for (int k = 0; k < 8; k++) word[k] = nword[k];
+        }
+        __builtin_amdgcn_wave_barrier();
+        for (uint32_t e = lane * 8u; e < 64u * (uint32_t)sb; e += 512u) {                     // tile -> HBM, whole lines
+            const uint32_t px = e / (uint32_t)sb, o = e - px * (uint32_t)sb;
+            if (pw + px < NP) *(uint2*)(outw + (size_t)px * D + d0 + o) = *(const uint2*)(tilew + px * RC_PAD + o);
+        }
+        __builtin_amdgcn_wave_barrier();
+    }
+}
+
+__global__ __launch_bounds__(256) void epi_rawcost_px_kernel(EpiCostArgs a) {
+    __shared__ __attribute__((aligned(16))) uint8_t tile[4][64 * RC_PAD];
+    const uint32_t NP = (uint32_t)a.W * (uint32_t)a.H;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t pw = (blockIdx.x * 4u + wave) * 64u;          // first pixel of this wave
+    if (pw >= NP) return;                                        // wave-uniform
+    const uint32_t p = min(pw + lane, NP - 1);                   // lanes past the end redo the last pixel, never stored
+    const size_t f = blockIdx.y;
+    const double* __restrict__ p0 = a.pd0 + f * 2 * (size_t)NP;
+    const double* __restrict__ nd = a.nd + f * 2 * (size_t)NP;
+    const double bx = __dsub_rn(p0[p], 1.0), by = __dsub_rn(p0[NP + p], 1.0);          // :348-349
+    const double ux = nd[p], uy = nd[NP + p];
+    const double off = a.off[f * (size_t)NP + p];
+    // |off * vz * u| <= reach * (1 + 3 ulp); NaN or inf anywhere fails the compares
+    const double reach = __dmul_rn(__dmul_rn(fabs(off), a.vzmax), fmax(fabs(ux), fabs(uy)));
+    const bool small = fabs(bx) < 536870912.0 && fabs(by) < 536870912.0 && reach < 536870912.0 &&
+                       fabs(ux) <= 1.7e308 && fabs(uy) <= 1.7e308;
+    if (__builtin_amdgcn_ballot_w64(!small) == 0) epi_rawcost_px_body<true>(a, tile[wave], pw, p, bx, by, ux, uy, off);
+    else                                          epi_rawcost_px_body<false>(a, tile[wave], pw, p, bx, by, ux, uy, off);
+}
+
+// =============================================================================================
+// 5x5 box mean, replicate border  (calc_cost_sgm.cpp:387-407).
+// (u8)(1.0*sum/25 + 0.5) == (2*sum + 25) / 50 in integers: the exact value has denominator 50,
+// so it is never within 1/50 of an integer from below except at the integer itself, which
+// needs 2*sum+25 (odd) divisible by 50 -- impossible.
+// One thread = one pixel x 4 consecutive d (SWAR: even/odd bytes summed in 16-bit fields).
+// =============================================================================================
+__global__ __launch_bounds__(256) void box5x5_kernel(const uint8_t* __restrict__ Craw,
+                                                     uint8_t* __restrict__ C, int W, int H, int D) {
+    const int NP = W * H;
+    const int Dq = (D + 3) >> 2;
+    const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (gid >= (long long)NP * Dq) return;
+    const int p = (int)(gid / Dq), q = (int)(gid - (long long)p * Dq);
+    const int y = p / W, x = p - y * W;
+    const uint8_t* raw = Craw + (size_t)blockIdx.y * NP * D;
+    uint8_t* out = C + (size_t)blockIdx.y * NP * D + (size_t)p * D + 4 * q;
+    if ((D & 3) == 0) {
+        uint32_t se = 0, so = 0;
+#pragma unroll
+        for (int dy = -2; dy <= 2; dy++) {
+            const int y1 = clampi(y + dy, 0, H - 1);
+#pragma unroll
+            for (int dx = -2; dx <= 2; dx++) {
+                const int x1 = clampi(x + dx, 0, W - 1);
+                const uint32_t w = *(const uint32_t*)(raw + ((size_t)y1 * W + x1) * D + 4 * q);
+                se += w & 0x00FF00FFu;
+                so += (w >> 8) & 0x00FF00FFu;
+            }
+        }
+        const uint32_t b0 = (2 * (se & 0xFFFF) + 25) / 50, b2 = (2 * (se >> 16) + 25) / 50;
+        const uint32_t b1 = (2 * (so & 0xFFFF) + 25) / 50, b3 = (2 * (so >> 16) + 25) / 50;
+        *(uint32_t*)out = (b0 & 0xFF) | ((b1 & 0xFF) << 8) | ((b2 & 0xFF) << 16) | ((b3 & 0xFF) << 24);
+    } else {
+        for (int k = 0; k < 4; k++) {
+            const int d = 4 * q + k;
+            if (d >= D) break;
+            uint32_t s = 0;
+            for (int dy = -2; dy <= 2; dy++) {
+                const int y1 = clampi(y + dy, 0, H - 1);
+                for (int dx = -2; dx <= 2; dx++) {
+                    const int x1 = clampi(x + dx, 0, W - 1);
+                    s += raw[((size_t)y1 * W + x1) * D + d];
+                }
+            }
+            out[k] = (uint8_t)((2 * s + 25) / 50);
+        }
+    }
+}
+
+// =============================================================================================
+// 5x5 box mean, sliding-window form for D % 4 == 0 (same result as box5x5_kernel).
+// One thread = one pixel column x 4 consecutive d, walking down BOX_ROWS rows: per row one
+// horizontal 5-sum (5 u32 loads, even/odd bytes in 16-bit fields) and a 5-deep ring of those sums
+// for the vertical part: 5 loads per output instead of 25.
+// =============================================================================================
+constexpr int BOX_ROWS = 32;
+__global__ __launch_bounds__(256) void box5x5_sliding_kernel(const uint8_t* __restrict__ Craw,
+                                                             uint8_t* __restrict__ C, int W, int H, int D) {
+    const int Dq = D >> 2;
+    const int cols = 256 / Dq;                               // pixel columns per block (Dq <= 256 here)
+    const int q = threadIdx.x % Dq, xi = threadIdx.x / Dq;
+    const int x = blockIdx.x * cols + xi;
+    if (xi >= cols || x >= W) return;
+    const int y0 = blockIdx.y * BOX_ROWS, y1 = min(y0 + BOX_ROWS, H);
+    const size_t NP = (size_t)W * H;
+    const uint8_t* raw = Craw + (size_t)blockIdx.z * NP * D + 4 * q;
+    uint8_t* out = C + (size_t)blockIdx.z * NP * D + 4 * q;
+    int xs[5];
+#pragma unroll
+    for (int k = 0; k < 5; k++) xs[k] = clampi(x + k - 2, 0, W - 1);
+    auto hsum = [&](int y, uint32_t& he, uint32_t& ho) {     // horizontal 5-sum of row clamp(y)
+        const uint8_t* r = raw + (size_t)clampi(y, 0, H - 1) * W * D;
+        he = 0; ho = 0;
+#pragma unroll
+        for (int k = 0; k < 5; k++) {
+            const uint32_t w = *(const uint32_t*)(r + (size_t)xs[k] * D);
+            he += w & 0x00FF00FFu;
+            ho += (w >> 8) & 0x00FF00FFu;
+        }
+    };
+    uint32_t re[5], ro[5];                                   // ring: rows y-2 .. y+2 around the output row
+#pragma unroll
+    for (int k = 0; k < 4; k++) hsum(y0 - 2 + k, re[k], ro[k]);
+    for (int yb = y0; yb < y1; yb += 5) {
+#pragma unroll
+        for (int k = 0; k < 5; k++) {                        // static ring slot = (k + 4) % 5
+            const int y = yb + k;
+            if (y < y1) {
+                hsum(y + 2, re[(k + 4) % 5], ro[(k + 4) % 5]);
+                const uint32_t se = re[0] + re[1] + re[2] + re[3] + re[4];
+                const uint32_t so = ro[0] + ro[1] + ro[2] + ro[3] + ro[4];
+                const uint32_t b0 = (2 * (se & 0xFFFF) + 25) / 50, b2 = (2 * (se >> 16) + 25) / 50;
+                const uint32_t b1 = (2 * (so & 0xFFFF) + 25) / 50, b3 = (2 * (so >> 16) + 25) / 50;
+                *(uint32_t*)(out + ((size_t)y * W + x) * D) = (b0 & 0xFF) | ((b1 & 0xFF) << 8) | ((b2 & 0xFF) << 16) | ((b3 & 0xFF) << 24);
+            }
+        }
+    }
+}
+
+// =============================================================================================
+// The same sliding window with 16 bytes per lane (D % 16 == 0): one thread = one pixel column x 16 consecutive d, D/16
+// adjacent lanes a pixel -- every access a 16-byte one, a wave's load 64/(D/16) whole pixels (the dword form above moves
+// 4 bytes a lane and reaches 3.5 TB/s; 16-byte accesses are what this chip's memory pipeline is built for).
+// =============================================================================================
+__global__ __launch_bounds__(256) void box5x5_sliding16_kernel(const uint8_t* __restrict__ Craw,
+                                                               uint8_t* __restrict__ C, int W, int H, int D) {
+    const int Dq = D >> 4;                                   // lanes per pixel
+    const int cols = 256 / Dq;                               // pixel columns per block (Dq <= 64 here)
+    const int q = threadIdx.x % Dq, xi = threadIdx.x / Dq;
+    const int x = blockIdx.x * cols + xi;
+    if (xi >= cols || x >= W) return;
+    const int y0 = blockIdx.y * BOX_ROWS, y1 = min(y0 + BOX_ROWS, H);
+    const size_t NP = (size_t)W * H;
+    const uint8_t* raw = Craw + (size_t)blockIdx.z * NP * D + 16 * q;
+    uint8_t* out = C + (size_t)blockIdx.z * NP * D + 16 * q;
+    uint32_t xo[5];
+#pragma unroll
+    for (int k = 0; k < 5; k++) xo[k] = (uint32_t)clampi(x + k - 2, 0, W - 1) * (uint32_t)D;
+    struct Sum { uint32_t e[4], o[4]; };                     // even / odd bytes of the 4 dwords in 16-bit fields
+    auto hsum = [&](int y, Sum& h) {                         // horizontal 5-sum of row clamp(y)
+        const uint8_t* r = raw + (size_t)clampi(y, 0, H - 1) * W * D;
+#pragma unroll
+        for (int i = 0; i < 4; i++) { h.e[i] = 0; h.o[i] = 0; }
+#pragma unroll
+        for (int k = 0; k < 5; k++) {
+            const uint4 v = *(const uint4*)(r + xo[k]);       // neighbouring lanes re-read these lines: through the L1
+            const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+            for (int i = 0; i < 4; i++) { h.e[i] += w[i] & 0x00FF00FFu; h.o[i] += (w[i] >> 8) & 0x00FF00FFu; }
+        }
+    };
+    Sum ring[5];                                             // rows y-2 .. y+2 around the output row
+#pragma unroll
+    for (int k = 0; k < 4; k++) hsum(y0 - 2 + k, ring[k]);
+    for (int yb = y0; yb < y1; yb += 5) {
+#pragma unroll
+        for (int k = 0; k < 5; k++) {                        // static ring slot = (k + 4) % 5
+            const int y = yb + k;
+            if (y < y1) {
+                hsum(y + 2, ring[(k + 4) % 5]);
+                uint32_t o4[4];
+#pragma unroll
+                for (int i = 0; i < 4; i++) {
+                    const uint32_t se = ring[0].e[i] + ring[1].e[i] + ring[2].e[i] + ring[3].e[i] + ring[4].e[i];
+                    const uint32_t so = ring[0].o[i] + ring[1].o[i] + ring[2].o[i] + ring[3].o[i] + ring[4].o[i];
+                    const uint32_t b0 = (2 * (se & 0xFFFF) + 25) / 50, b2 = (2 * (se >> 16) + 25) / 50;
+                    const uint32_t b1 = (2 * (so & 0xFFFF) + 25) / 50, b3 = (2 * (so >> 16) + 25) / 50;
+                    o4[i] = (b0 & 0xFF) | ((b1 & 0xFF) << 8) | ((b2 & 0xFF) << 16) | ((b3 & 0xFF) << 24);
+                }
+                *(uint4*)(out + ((size_t)y * W + x) * D) = make_uint4(o4[0], o4[1], o4[2], o4[3]);
+            }
+        }
+    }
+}
+
+// ---- which kernels the cost stage runs (the launchers here switch on this; fsgm_epi_cost_kernels prints it) ----
+int select_box_kernel(int D) {
+    static const bool box16 = [] { const char* e = getenv("FSGM_BOX16"); return !(e && e[0] == '0'); }();   // A/B switch
+    if (box16 && (D & 15) == 0 && D <= 1024) return COST_BOX_16;            // D / 16 <= 64 lanes a pixel
+    if ((D & 3) == 0 && D <= 1024) return COST_BOX_4;                        // D / 4 <= 256 lanes a pixel
+    return COST_BOX_1;
+}
+
+CostKernels select_cost_kernels(int W, int H, int D, bool rectified) {
+    // FSGM_COST_FUSED=0: the two-kernel form (raw volume through HBM) -- A/B switch and the cross-check of the fused kernel in the tests
+    const bool fused = [] { const char* e = getenv("FSGM_COST_FUSED"); return !(e && e[0] == '0'); }();   // read per call: the tests flip it
+    if (fused && costbox_ok(W, H, D)) return {COST_RAW_FUSED, COST_BOX_FUSED};
+    int raw;
+    if (rectified) raw = COST_RAW_STEREO;
+    else if ((D & 7) == 0 && W < (1 << 22) && H < (1 << 24)) raw = COST_RAW_PX;   // (the px kernel's 24-bit multiplies)
+    else if ((D & 3) == 0) raw = COST_RAW_VEC4;
+    else raw = COST_RAW_SCALAR;
+    return {raw, select_box_kernel(D)};
+}
+
+const char* cost_kernels_name(CostKernels k, bool rectified) {
+    static const char* const names[5][4] = {{"costbox", "", "", ""},
+                                            {"", "px+box16", "px+box4", "px+box1"},
+                                            {"", "vec4+box16", "vec4+box4", "vec4+box1"},
+                                            {"", "scalar+box16", "scalar+box4", "scalar+box1"},
+                                            {"", "stereo+box16", "stereo+box4", "stereo+box1"}};
+    if (k.raw == COST_RAW_FUSED) return rectified ? "stereo-costbox" : "costbox";
+    return names[k.raw][k.box];
+}
+
+void launch_epi_cost(hipStream_t st, const EpiCostArgs& a, uint8_t* C, int frames) {
+    const CostKernels k = select_cost_kernels(a.W, a.H, a.D, false);
+    const long long n = (long long)a.W * a.H * ((a.D + 3) / 4);
+    dim3 grid((unsigned)((n + 255) / 256), frames);
+    switch (k.raw) {
+        case COST_RAW_FUSED: launch_epi_costbox(st, a, C, frames); return;
+        case COST_RAW_PX:
+            hipLaunchKernelGGL(epi_rawcost_px_kernel, dim3((unsigned)(((long long)a.W * a.H + 255) / 256), frames), dim3(256), 0, st, a);
+            break;
+        case COST_RAW_VEC4: hipLaunchKernelGGL(epi_rawcost_kernel<true>, grid, dim3(256), 0, st, a); break;
+        default:            hipLaunchKernelGGL(epi_rawcost_kernel<false>, grid, dim3(256), 0, st, a); break;
+    }
+    launch_box5x5(st, k.box, a.Craw, C, a.W, a.H, a.D, frames);
+}
+
+// the 5x5 box mean of a raw volume in HBM (the two-kernel form of the cost stage); box: select_box_kernel(D)
+void launch_box5x5(hipStream_t st, int box, const uint8_t* Craw, uint8_t* C, int W, int H, int D, int frames) {
+    switch (box) {
+        case COST_BOX_16: {
+            const int cols = 256 / (D >> 4);
+            dim3 g2((W + cols - 1) / cols, (H + BOX_ROWS - 1) / BOX_ROWS, frames);
+            hipLaunchKernelGGL(box5x5_sliding16_kernel, g2, dim3(256), 0, st, Craw, C, W, H, D);
+            break;
+        }
+        case COST_BOX_4: {
+            const int cols = 256 / (D >> 2);
+            dim3 g2((W + cols - 1) / cols, (H + BOX_ROWS - 1) / BOX_ROWS, frames);
+            hipLaunchKernelGGL(box5x5_sliding_kernel, g2, dim3(256), 0, st, Craw, C, W, H, D);
+            break;
+        }
+        default: {
+            const long long n = (long long)W * H * ((D + 3) / 4);
+            hipLaunchKernelGGL(box5x5_kernel, dim3((unsigned)((n + 255) / 256), frames), dim3(256), 0, st, Craw, C, W, H, D);
+            break;
+        }
+    }
+}
 
 // Rectified pair, any dMax: raw costs of one (pixel, d) per thread into the raw volume for the box kernels; index d stands for
 // disparity d_min + d

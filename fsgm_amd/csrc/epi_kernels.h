@@ -1,10 +1,25 @@
-// epi_kernels.h -- launch interface of the calc_cost_sgm-path kernels (epi_kernels.hip)
+// epi_kernels.h -- launch interface of the calc_cost_sgm-path kernels: epi_kernels.hip (census, forward-backward check),
+// epi_cost.hip, epi_lines.hip + epi_lines_split.hip, epi_wta.hip, epi_sweep.hip, epi_band.hip
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
 
 #define FSGM_GENERIC_MAX_D 1024
+
+// The disparity ranges of the line kernels and the packed WTA, one row a class: X(D, LPP, DPL) -- LPP adjacent lanes own a pixel,
+// DPL consecutive costs each.  16 costs a lane for D = 16 << k; 12, 20 or 28 for the seven ranges between them (144, 176, 208 and
+// 240 would take 36 .. 60 costs a lane -- 18 .. 30 state registers and a ring of as many dwords a prefetched step: not offered,
+// the generic kernels take them).  agg_line_split, agg_packed_lpp, launch_aggregate and launch_wta are all derived from this list:
+// a new class is a new row here.
+#define FSGM_LINE_CLASSES(X)                                          \
+    X(16, 1, 16) X(32, 2, 16) X(64, 4, 16) X(128, 8, 16) X(256, 16, 16) \
+    X(48, 4, 12) X(96, 8, 12) X(192, 16, 12) X(80, 4, 20) X(160, 8, 20) X(112, 4, 28) X(224, 8, 28)
+#define FSGM_LINE_CLASS_OK(D, LPP, DPL)                                                                   \
+    static_assert((LPP) * (DPL) == (D) && ((LPP) & ((LPP) - 1)) == 0 && (LPP) <= 16 && (DPL) % 4 == 0, \
+                  "line class: LPP (a power of two, one DPP row at most) lanes of DPL (whole dwords) costs make up D");
+FSGM_LINE_CLASSES(FSGM_LINE_CLASS_OK)
+#undef FSGM_LINE_CLASS_OK
 
 namespace fsgm {
 

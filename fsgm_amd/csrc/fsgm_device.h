@@ -89,6 +89,39 @@ __device__ __forceinline__ uint4 load_nt(const void* p) {
     const u32x4 t = __builtin_nontemporal_load((const u32x4*)p);
     return make_uint4(t.x, t.y, t.z, t.w);
 }
+// the line kernels' path volumes past the caches (stores in epi_lines.h / epi_lines.hip, loads in wta_packed_kernel, epi_wta.hip):
+// aggregation 0.236 -> 0.210 ms for one 1242x375x128 frame, 0.73 -> 0.645 for four; WTA 0.083 -> 0.076 (three runs each)
+#ifndef FSGM_LINE_NT
+#define FSGM_LINE_NT 1
+#endif
+// N dwords at a 4-byte aligned address past the caches, as pieces of 4, 2 and 1 dwords (a three-element vector would be stored
+// as four): what the splits with 12, 20 or 28 costs a lane move (agg_line_split).  Exactly 4 N bytes are read or written.
+typedef uint32_t u32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));
+typedef uint32_t u32x2_a4 __attribute__((ext_vector_type(2), aligned(4)));
+template <int N>
+__device__ __forceinline__ void store_nt_words(uint8_t* p, const uint32_t* w) {
+    if constexpr (N >= 4) {
+        const u32x4_a4 t = {w[0], w[1], w[2], w[3]};
+        __builtin_nontemporal_store(t, (u32x4_a4*)p);
+        store_nt_words<N - 4>(p + 16, w + 4);
+    } else if constexpr (N >= 2) {
+        const u32x2_a4 t = {w[0], w[1]};
+        __builtin_nontemporal_store(t, (u32x2_a4*)p);
+        store_nt_words<N - 2>(p + 8, w + 2);
+    } else if constexpr (N == 1) __builtin_nontemporal_store(w[0], (uint32_t*)p);
+}
+template <int N>
+__device__ __forceinline__ void load_nt_words(const uint8_t* p, uint32_t* w) {
+    if constexpr (N >= 4) {
+        const u32x4_a4 t = __builtin_nontemporal_load((const u32x4_a4*)p);
+        w[0] = t.x; w[1] = t.y; w[2] = t.z; w[3] = t.w;
+        load_nt_words<N - 4>(p + 16, w + 4);
+    } else if constexpr (N >= 2) {
+        const u32x2_a4 t = __builtin_nontemporal_load((const u32x2_a4*)p);
+        w[0] = t.x; w[1] = t.y;
+        load_nt_words<N - 2>(p + 8, w + 2);
+    } else if constexpr (N == 1) w[0] = __builtin_nontemporal_load((const uint32_t*)p);
+}
 
 // ---- DPP controls (gfx9 encoding) ----
 constexpr int DPP_QUAD_1032 = 0xB1;        // quad_perm:[1,0,3,2]

@@ -1,5 +1,5 @@
 """fsgm_epi_cost_kernels (fsgm_amd.epi.cost_kernels): which kernels the cost stage launches, as far as no device is needed.
-The function prints the selector the launchers themselves switch on (select_cost_kernels, epi_kernels.hip); this file holds the
+The function prints the selector the launchers themselves switch on (select_cost_kernels, epi_cost.hip); this file holds the
 table it must follow, written down independently:
 
     dMax = 16, 32, 64, 128, 256, width < 2^22, height < 2^24, FSGM_COST_FUSED not 0   "costbox" ("stereo-costbox" rectified)

@@ -5,7 +5,7 @@ calc_cost_sgm.cpp:343-407), rectified plans with stereo_restatement.box_mean(rec
 kernels it means to run by the name fsgm_amd.epi.cost_kernels gives (the launchers' own selector; its table:
 tests/test_cost_kernels_cpu.py).
 
-The box kernels' geometry, restated once (epi_kernels.hip): a workgroup of 256 lanes covers BOX_ROWS = 32 rows of `cols` columns
+The box kernels' geometry, restated once (epi_cost.hip): a workgroup of 256 lanes covers BOX_ROWS = 32 rows of `cols` columns
 and walks its rows in rounds of 5 through a ring of 5 horizontal sums, preloaded from rows y0 - 2 .. y0 + 1;
 
     box16 (D % 16 == 0): D / 16 lanes a pixel, cols = 256 // (D // 16)      D    16  48  80  96  112  144  160  224  256  1024

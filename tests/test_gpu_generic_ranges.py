@@ -1,4 +1,4 @@
-"""GPU tests of the generic line kernel and the generic WTA (agg_generic_kernel, wta_generic_kernel, epi_kernels.hip) at the
+"""GPU tests of the generic line kernel and the generic WTA (agg_generic_kernel, epi_lines.hip; wta_generic_kernel, epi_wta.hip) at the
 disparity ranges they serve from 144 to FSGM_GENERIC_MAX_D = 1024: 3 to 16 strides of 64 lanes, the d == D - 1 end in a late
 stride, a ragged last stride (257, 1023), the LDS rows filled to their last byte (1024), winners beyond the 8 bits the packed WTA
 keeps for d, and the cost stage's two-kernel form beyond 256.  Every compared output is an integer array compared for equality

@@ -1,4 +1,4 @@
-"""The packed line kernels' disparity ranges beyond 16 << k (agg_line_split, epi_kernels.hip: 48, 96, 192 as 12 costs a lane; 80,
+"""The packed line kernels' disparity ranges beyond 16 << k (agg_line_split, epi_lines.hip: 48, 96, 192 as 12 costs a lane; 80,
 160 as 20; 112, 224 as 28), as far as no device is needed: what fsgm_epi_auto_pipeline answers for them, that every other range
 keeps its answer, and the CPU oracle against the reference's own compiled code at two of the new ranges, so that the oracle
 stands as the yardstick of tests/test_gpu_line_splits.py there."""
