@@ -129,6 +129,8 @@ def load():
         lib.fsgm_epi_cost_kernels.argtypes = [i32, i32, i32, i32, C.c_char_p, C.c_size_t]
     lib.fsgm_measure_copy_bandwidth.argtypes = [i32, C.c_size_t, i32, C.POINTER(C.c_double)]
     lib.fsgm_measure_copy_bandwidth2.argtypes = [i32, C.c_size_t, i32, i32, C.POINTER(C.c_double)]
+    if hasattr(lib, "fsgm_epi_plan_set_exact"):                  # (an older build behind FSGM_LIB_PATH has none)
+        lib.fsgm_epi_plan_set_exact.argtypes = [vp, i32]
     if hasattr(lib, "fsgm_epi_plan_set_runner_up"):              # (an older build behind FSGM_LIB_PATH has none of these)
         lib.fsgm_epi_plan_set_runner_up.argtypes = [vp, i32]
         lib.fsgm_epi_plan_download_runner_up.argtypes = [vp, i32, vp]

@@ -68,12 +68,15 @@ struct PerDevice {
 
 // The plans behind the host- and device-pointer entry points of one kind: per device the last `cap` that were made, oldest
 // evicted first.  find / insert want the device's lock held (mu(device), for the length of the call that uses the plan).
+// pinned (may be null): a plan it answers true for is never evicted -- a captured graph names its buffers, its stream and its
+// events --, does not count against `cap`, and lives until clear().
 template <class P>
 struct PlanCache {
     PerDevice<std::vector<P*>> plans;
     const size_t cap;
     void (*const destroy)(P*);
-    PlanCache(size_t cap_, void (*destroy_)(P*)) : cap(cap_), destroy(destroy_) {}
+    bool (*const pinned)(const P*);
+    PlanCache(size_t cap_, void (*destroy_)(P*), bool (*pinned_)(const P*) = nullptr) : cap(cap_), destroy(destroy_), pinned(pinned_) {}
 
     std::mutex& mu(int device) { return plans.mu[device]; }
     template <class Match>
@@ -84,9 +87,11 @@ struct PlanCache {
     }
     void insert(int device, P* p) {
         std::vector<P*>& v = plans.v[device];
-        if (v.size() >= cap) {
-            destroy(v.front());
-            v.erase(v.begin());
+        size_t loose = 0;
+        for (P* q : v) loose += !(pinned && pinned(q));
+        if (loose >= cap) {                                      // the oldest plan that no graph names
+            for (auto it = v.begin(); it != v.end(); ++it)
+                if (!(pinned && pinned(*it))) { destroy(*it); v.erase(it); break; }
         }
         v.push_back(p);
     }

@@ -18,8 +18,12 @@ struct DevicePtr {
 // The checks of every device entry point behind its own argument checks, in this order: `device` made current
 // (use_device), the caller's stream `cs` refused while it is captured into a graph (FSGM_ERR_UNSUPPORTED: nothing may be
 // queued then), each pointer checked in list order (FSGM_ERR_INVALID).  Entry points call it before they look up or build
-// a plan: a call refused here has allocated nothing.
-fsgm_status device_check_args(const char* who, int device, hipStream_t cs, std::initializer_list<DevicePtr> ptrs);
+// a plan: a call refused here has allocated nothing.  captured (non-null): a captured stream is let through and *captured says
+// whether it is one -- for an entry point whose warm call only queues work (no allocation, no host wait) and joins the plan's
+// stream to the caller's by events, which a capture records as a fork and a join.  Such an entry point refuses a captured call
+// that its cached plan cannot serve as it stands, and pins the plan it records (PlanCache).
+fsgm_status device_check_args(const char* who, int device, hipStream_t cs, std::initializer_list<DevicePtr> ptrs,
+                              bool* captured = nullptr);
 
 // The two events of a plan's device calls: `in` recorded on the caller's stream and waited for by the plan's stream,
 // `out` recorded on the plan's stream and waited for by the caller's.  Created on a plan's first device call.

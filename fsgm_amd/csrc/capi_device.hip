@@ -5,11 +5,13 @@
 
 namespace fsgm {
 
-static fsgm_status device_check_stream(hipStream_t s, const char* who) {
+static fsgm_status device_check_stream(hipStream_t s, const char* who, bool* captured) {
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     const hipError_t e = hipStreamIsCapturing(s, &cs);
     if (e == hipErrorStreamCaptureImplicit || (e == hipSuccess && cs != hipStreamCaptureStatusNone)) {
         (void)hipGetLastError();
+        // (the legacy stream while another stream of the thread is captured cannot join a capture: refused for every entry)
+        if (captured && e == hipSuccess && cs == hipStreamCaptureStatusActive) { *captured = true; return FSGM_OK; }
         return fail(FSGM_ERR_UNSUPPORTED, "%s: the stream is being captured into a graph (graph capture is not supported)", who);
     }
     if (e != hipSuccess) {
@@ -50,9 +52,10 @@ static fsgm_status device_check_ptr(const void* p, size_t bytes, size_t align, i
     return FSGM_OK;
 }
 
-fsgm_status device_check_args(const char* who, int device, hipStream_t cs, std::initializer_list<DevicePtr> ptrs) {
+fsgm_status device_check_args(const char* who, int device, hipStream_t cs, std::initializer_list<DevicePtr> ptrs, bool* captured) {
+    if (captured) *captured = false;
     fsgm_status st = use_device(device);
-    if (st != FSGM_OK || (st = device_check_stream(cs, who)) != FSGM_OK) return st;
+    if (st != FSGM_OK || (st = device_check_stream(cs, who, captured)) != FSGM_OK) return st;
     for (const DevicePtr& d : ptrs)
         if ((st = device_check_ptr(d.p, d.bytes, d.align, device, d.required, who, d.what)) != FSGM_OK) return st;
     return FSGM_OK;

@@ -34,10 +34,13 @@ enum Pipeline {
     PIPE_PAIRS,                                          // 4 paths: horizontal pair, vertical pair with the WTA inside
     PIPE_BAND,                                           // band sweeps: one workgroup per frame
     PIPE_BAND_CHAIN,                                     // band sweeps: one workgroup per (band, frame)
+    PIPE_PACKED_EXACT, PIPE_GENERIC_EXACT,               // line kernels + WTA kernel with exact path arithmetic (fsgm_epi_plan_set_exact)
 };
 static const char* const kPipelineName[] = {"generic", "packed16/nowrap", "packed16/wrap", "sweep16/nowrap", "sweep16par/nowrap",
-                                            "sweep16mid/nowrap", "pairs16/nowrap", "band16/nowrap", "band16chain/nowrap"};
-static bool pipe_lines(Pipeline k) { return k <= PIPE_PACKED_WRAP; }
+                                            "sweep16mid/nowrap", "pairs16/nowrap", "band16/nowrap", "band16chain/nowrap",
+                                            "packed16/exact", "generic/exact"};
+static bool pipe_exact(Pipeline k) { return k == PIPE_PACKED_EXACT || k == PIPE_GENERIC_EXACT; }
+static bool pipe_lines(Pipeline k) { return k <= PIPE_PACKED_WRAP || pipe_exact(k); }
 static bool pipe_sweep(Pipeline k) { return k == PIPE_SWEEP || k == PIPE_SWEEP_PAR || k == PIPE_SWEEP_MID; }
 
 // The sub-forms of the selected pipeline, settled with it by select_kernel: decisions only, never device pointers (the
@@ -105,11 +108,13 @@ struct fsgm_epi_plan {
     std::vector<char> have_img;          // per frame: its image pair has been put into dI1 / dI2 (what an adaptive aggregation reads)
     int runner_up = 0;                   // the WTA also writes the runner-up cost (fsgm_epi_plan_set_runner_up): line kernels at every batch size
     uint32_t* dMinC2 = nullptr;          // [batch][NP], created when the switch first goes on
+    int exact = 0;                       // exact path arithmetic (fsgm_epi_plan_set_exact): line kernels at every batch size, never with runner_up
     int agg_mode = 0;                    // 0 auto, 1 per-direction line kernels, 2 fused sweeps (if eligible), 3 parallel sweeps, 4 / 5 band sweeps, 6 sweeps meeting in the middle
     int cus = 256;                       // compute units of the device (band sweeps: one workgroup per frame, two per CU)
     Pipeline pipe = PIPE_GENERIC;
     PipelineForm form;
     DeviceJoin join;                     // device-pointer entry points: the events that order the plan's stream with the caller's
+    bool pinned = false;                 // a captured graph names this cached plan's buffers, stream and events: never evicted (PlanCache)
 };
 
 // batch sizes at which auto mode moves from the line kernels to the parallel sweeps and on to the full sweep pipeline
@@ -172,8 +177,10 @@ static int pairs_min_batch(int W, int H, int D) { return switch_batch("FSGM_EPI_
 // What runs for a plan of this shape, batch and parameter set (cm: the largest cost in the volumes): a function of its
 // arguments and the FSGM_EPI_* environment only, so that fsgm_epi_auto_pipeline can answer without a plan.
 // adaptive: the plan's adaptive-P2 or runner-up switch is on -- either keeps it on the line kernels.
+// exact: the plan's exact switch is on -- the line kernels that do not narrow, whatever the costs and penalties.
 static Pipeline choose_pipeline(int W, int H, int D, int batch, int paths, int P1, int P2, int cm, int agg_mode, int cus,
-                                int adaptive = 0) {
+                                int adaptive = 0, int exact = 0) {
+    if (exact) return agg_line_split(D) ? PIPE_PACKED_EXACT : PIPE_GENERIC_EXACT;   // no fused pipeline carries 9-bit path costs
     if (!agg_line_split(D)) return PIPE_GENERIC;
     // (adaptive P2 lowers P2 per step, never raises it: the no-wrap test with the full P2 covers every step)
     const bool nowrap = P1 >= 0 && P2 >= 0 && cm + P2 + std::max(P1, P2) <= 255;
@@ -220,7 +227,8 @@ static Pipeline choose_pipeline(int W, int H, int D, int batch, int paths, int P
 // switches (A/B) are read here, once per process.
 static void select_kernel(fsgm_epi_plan* p) {
     const int cm = *std::max_element(p->cmax.begin(), p->cmax.end());
-    const Pipeline k = choose_pipeline(p->W, p->H, p->D, p->batch, p->prm.paths, p->P1, p->P2, cm, p->agg_mode, p->cus, p->adaptive || p->runner_up);
+    const Pipeline k = choose_pipeline(p->W, p->H, p->D, p->batch, p->prm.paths, p->P1, p->P2, cm, p->agg_mode, p->cus, p->adaptive || p->runner_up,
+                                       p->exact);
     const int B = p->batch;
     const bool fine_ok = pair_x_fine_ok(p->D) != 0;
     PipelineForm f;
@@ -471,6 +479,8 @@ static fsgm_status ensure_image_buffers(fsgm_epi_plan* p) {
 
 fsgm_status fsgm_epi_plan_set_penalties(fsgm_epi_plan* p, int32_t P1, int32_t P2, double vMax) {
     FSGM_REQUIRE(p, "null plan");
+    FSGM_REQUIRE(!p->exact || (P1 >= 0 && P1 <= 255 && P2 >= 0 && P2 <= 255),
+                 "fsgm_epi_plan_set_penalties: an exact plan takes P1 and P2 in 0..255 (got %d, %d)", P1, P2);
     p->P1 = P1; p->P2 = P2;
     if (vMax != p->vMax) p->vz_valid = false;
     p->vMax = vMax;
@@ -773,11 +783,15 @@ static SweepSumArgs sum_args(const fsgm_epi_plan* p, int f0) {
 
 // per-direction line kernels: the path volumes L, then a WTA kernel over them
 static fsgm_status agg_lines(fsgm_epi_plan* p) {
-    const int kind = p->pipe == PIPE_GENERIC ? AGG_GENERIC : p->pipe == PIPE_PACKED_WRAP ? AGG_PACKED_WRAP : AGG_PACKED_NOWRAP;
+    const int kind = p->pipe == PIPE_GENERIC ? AGG_GENERIC : p->pipe == PIPE_PACKED_WRAP ? AGG_PACKED_WRAP
+                   : p->pipe == PIPE_PACKED_EXACT ? AGG_PACKED_EXACT : p->pipe == PIPE_GENERIC_EXACT ? AGG_GENERIC_EXACT : AGG_PACKED_NOWRAP;
     launch_aggregate(p->stream, agg_args(p, p->dL, p->prm.paths), p->prm.paths, p->batch, kind);
     return FSGM_OK;
 }
 static void tap_lines(fsgm_epi_plan* p, int f) {
+    if (pipe_exact(p->pipe))                             // the volumes hold L - C: the frame's costs come back in
+        return launch_sum_paths_exact(p->stream, p->dL + (size_t)f * p->N * p->prm.paths, p->dC + (size_t)f * p->N, p->dS, p->N, p->N,
+                                      p->prm.paths);
     launch_sum_paths(p->stream, p->dL + (size_t)f * p->N * p->prm.paths, p->dS, p->N, p->N, p->prm.paths);
 }
 
@@ -955,7 +969,8 @@ static fsgm_status enqueue(fsgm_epi_plan* p, int stages) {
             launch_sweep_finish(p->stream, a, p->dRec, p->dS0, p->batch);
         } else {                                         // a WTA kernel over the path volumes
             a.L = p->dL; a.l_frame_stride = p->N * p->prm.paths; a.l_dir_stride = p->N;
-            launch_wta(p->stream, a, p->batch, agg_line_split(p->D));
+            const WtaCostArgs x{pipe_exact(p->pipe) ? p->dC : nullptr, p->N};
+            launch_wta(p->stream, a, p->batch, agg_line_split(p->D), x);
         }
     }
     if ((stages & FSGM_STAGE_WTA) && p->prm.fb_check) {
@@ -986,6 +1001,8 @@ fsgm_status fsgm_epi_plan_set_agg_mode(fsgm_epi_plan* p, int32_t mode) {
         return fail(FSGM_ERR_UNSUPPORTED, "agg mode %d on an adaptive-P2 plan: only the line kernels (modes 0 and 1) take a per-step P2", mode);
     if (p->runner_up && mode >= 2)
         return fail(FSGM_ERR_UNSUPPORTED, "agg mode %d on a runner-up plan: only the line kernels' WTA (modes 0 and 1) writes the runner-up cost", mode);
+    if (p->exact && mode >= 2)
+        return fail(FSGM_ERR_UNSUPPORTED, "agg mode %d on an exact plan: only the line kernels (modes 0 and 1) carry path costs above 255", mode);
     p->agg_mode = mode;
     select_kernel(p);
     return FSGM_OK;
@@ -1008,6 +1025,8 @@ fsgm_status fsgm_epi_plan_set_runner_up(fsgm_epi_plan* p, int32_t on) {
     if (on && p->agg_mode >= 2)
         return fail(FSGM_ERR_UNSUPPORTED, "runner-up cost on a plan forced to agg mode %d: only the line kernels' WTA (modes 0 and 1) writes it",
                     p->agg_mode);
+    if (on && p->exact)
+        return fail(FSGM_ERR_UNSUPPORTED, "runner-up cost on an exact plan: the exact WTA writes no second minimum");
     if (on && !p->dMinC2) {                                      // all ones until a WTA has run: FSGM_NO_RUNNER_UP
         const size_t bytes = (size_t)p->batch * p->NP * 4;
         uint32_t* m = nullptr;
@@ -1018,6 +1037,21 @@ fsgm_status fsgm_epi_plan_set_runner_up(fsgm_epi_plan* p, int32_t on) {
         p->dMinC2 = m;
     }
     p->runner_up = on;
+    select_kernel(p);
+    return FSGM_OK;
+}
+
+fsgm_status fsgm_epi_plan_set_exact(fsgm_epi_plan* p, int32_t on) {
+    FSGM_REQUIRE(p, "null plan");
+    FSGM_REQUIRE(on == 0 || on == 1, "fsgm_epi_plan_set_exact: on must be 0 or 1 (got %d)", on);
+    if (on && p->agg_mode >= 2)
+        return fail(FSGM_ERR_UNSUPPORTED, "exact path arithmetic on a plan forced to agg mode %d: only the line kernels (modes 0 and 1) carry path costs above 255",
+                    p->agg_mode);
+    if (on && p->runner_up)
+        return fail(FSGM_ERR_UNSUPPORTED, "exact path arithmetic on a runner-up plan: the exact WTA writes no second minimum");
+    FSGM_REQUIRE(!on || (p->P1 >= 0 && p->P1 <= 255 && p->P2 >= 0 && p->P2 <= 255),
+                 "fsgm_epi_plan_set_exact: an exact plan takes P1 and P2 in 0..255 (the plan holds %d, %d)", p->P1, p->P2);
+    p->exact = on;
     select_kernel(p);
     return FSGM_OK;
 }
@@ -1203,13 +1237,14 @@ fsgm_status fsgm_measure_copy_bandwidth(int32_t device, size_t bytes, int32_t it
 // host-pointer entry points (the MEX boundary).  Plans are cached per shape for the lifetime of
 // the process so repeated MEX calls do not re-allocate HBM (SURVEY 8b "ownership").
 // ---------------------------------------------------------------------------------------------
-static PlanCache<fsgm_epi_plan> g_epi(4, fsgm_epi_plan_destroy);   // cached plans per device (the cap bounds the HBM held by stale shapes)
+// cached plans per device (the cap bounds the HBM held by stale shapes; a plan recorded into a graph is held beside them)
+static PlanCache<fsgm_epi_plan> g_epi(4, fsgm_epi_plan_destroy, [](const fsgm_epi_plan* p) { return p->pinned; });
 
 // The cached plan of this shape for an entry point: `lk` holds its device's lock for the length of the call, the device is current.
 // (a plan serves one sampling mode and, rectified, one direction: the modes share no cached state)
 static fsgm_status cached_plan(std::unique_lock<std::mutex>& lk, fsgm_epi_plan** out, int W, int H, int D, int batch,
                                const fsgm_epi_params& pr, int sampling = FSGM_SAMPLING_VZ, int direction = 0, int adaptive = 0,
-                               int agg_mode = 0, int runner_up = 0) {
+                               int agg_mode = 0, int runner_up = 0, int exact = 0, bool must_exist = false) {
     FSGM_DEVICE_SLOT(pr.device);
     lk = std::unique_lock<std::mutex>(g_epi.mu(pr.device));
     fsgm_epi_plan* p = g_epi.find(pr.device, [&](const fsgm_epi_plan* q) {
@@ -1217,14 +1252,19 @@ static fsgm_status cached_plan(std::unique_lock<std::mutex>& lk, fsgm_epi_plan**
                q->prm.fb_check == pr.fb_check && q->prm.vz_to_disp == pr.vz_to_disp && q->sampling == sampling &&
                q->direction == direction && q->adaptive == adaptive &&   // (adaptive and non-adaptive callers never share a plan)
                q->agg_mode == agg_mode &&                                // (nor do forced modes: only the sgm batch forms ask for one)
-               q->runner_up == runner_up;                                // (nor a runner-up caller and a plain one: the plain call keeps its pipeline)
+               q->runner_up == runner_up &&                              // (nor a runner-up caller and a plain one: the plain call keeps its pipeline)
+               q->exact == exact;                                        // (nor an exact caller and a plain one)
     });
     if (p) p->prm = pr;
+    else if (must_exist)                                         // (a captured call: creating a plan allocates, copies and waits)
+        return fail(FSGM_ERR_UNSUPPORTED, "the stream is being captured into a graph and no call of this shape and these switches has run yet: "
+                                          "run it once outside the capture");
     else {
         fsgm_status st = fsgm_epi_plan_create_sampling(&p, W, H, D, batch, &pr, sampling, direction);
         if (st == FSGM_OK && adaptive && (st = fsgm_epi_plan_set_adaptive_p2(p, 1)) != FSGM_OK) fsgm_epi_plan_destroy(p);
         else if (st == FSGM_OK && agg_mode && (st = fsgm_epi_plan_set_agg_mode(p, agg_mode)) != FSGM_OK) fsgm_epi_plan_destroy(p);
         else if (st == FSGM_OK && runner_up && (st = fsgm_epi_plan_set_runner_up(p, 1)) != FSGM_OK) fsgm_epi_plan_destroy(p);
+        else if (st == FSGM_OK && exact && (st = fsgm_epi_plan_set_exact(p, 1)) != FSGM_OK) fsgm_epi_plan_destroy(p);
         if (st != FSGM_OK) return st;
         g_epi.insert(pr.device, p);
     }
@@ -1459,11 +1499,12 @@ namespace fsgm {
 
 static thread_local const char* g_sgm_kernel = "";
 
-// the cached plan of a checked call: its batch, mode, adaptive and runner-up switches are part of the key
+// the cached plan of a checked call: its batch, mode, adaptive, runner-up and exact switches are part of the key
 static fsgm_status sgm_plan(std::unique_lock<std::mutex>& lk, fsgm_epi_plan** p, const SgmCall& c) {
     fsgm_epi_params pr = fsgm_epi_params_default();
     pr.paths = c.prm.paths; pr.subpixel = c.prm.subpixel; pr.device = c.prm.device; pr.vz_to_disp = 0; pr.fb_check = 0;
-    return cached_plan(lk, p, c.W, c.H, c.D, c.n, pr, FSGM_SAMPLING_VZ, 0, c.prm.adaptive_p2, c.prm.agg_mode, c.minC2 != nullptr);
+    return cached_plan(lk, p, c.W, c.H, c.D, c.n, pr, FSGM_SAMPLING_VZ, 0, c.prm.adaptive_p2, c.prm.agg_mode, c.minC2 != nullptr, c.exact,
+                       c.captured != 0);
 }
 
 static fsgm_status ensure_ingest_flag(fsgm_epi_plan* p) {
@@ -1508,6 +1549,15 @@ fsgm_status sgm_run_device(const SgmCall& c, hipStream_t cs, int32_t* status) {
     fsgm_epi_plan* p = nullptr;
     fsgm_status st = sgm_plan(lk, &p, c);
     if (st != FSGM_OK) return st;
+    if (c.captured) {
+        // Under a capture nothing may be allocated or waited for: everything the call below would create must exist (an earlier
+        // call of the host form, or one without S or without a guide, leaves some of it out).  Refused before anything is queued.
+        const bool warm = p->dL && p->dIngestFlag && p->join.in && p->join.out && (!c.S || p->dS) && (!c.guide || (p->dI1 && p->dI2));
+        if (!warm)
+            return fail(FSGM_ERR_UNSUPPORTED, "fsgm_sgm_device_exact: the stream is being captured into a graph and the cached plan lacks buffers "
+                                              "this call needs: run the same call once outside the capture");
+        p->pinned = true;                                        // the graph names the plan's buffers, stream and events from here on
+    }
     // What a warm call must not do happens here, before the join with the caller's stream.  The device cannot be asked for the
     // true maximum without a wait: the declared bound selects the kernels, the ingest kernel saturates at it.
     p->cmax.assign(c.n, c.prm.cost_bound);

@@ -11,6 +11,8 @@ struct SgmCall {
     const uint8_t *C, *guide;            // guide: non-NULL exactly when prm.adaptive_p2
     uint32_t *bestD, *minC, *S;          // S may be NULL
     uint32_t* minC2;                     // the _ru forms' runner-up cost (never NULL there), NULL in the plain forms
+    int exact;                           // the _exact forms: exact path arithmetic, P1 and P2 checked to lie in 0..255 (never with minC2)
+    int captured = 0;                    // fsgm_sgm_device_exact alone: the caller's stream is being captured into a graph
 };
 
 // host pointers; cmax: the largest byte of each frame's volume (none above prm.cost_bound)

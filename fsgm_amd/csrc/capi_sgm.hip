@@ -1,5 +1,5 @@
 // capi_sgm.hip -- C ABI of sgm(C, P1, P2) on batches of caller-supplied cost volumes, in host memory or in HBM (include/fsgm.h:
-// fsgm_sgm_batch_host, fsgm_sgm_device).  Everything that can be refused without a device is refused here; the cached plans
+// fsgm_sgm_batch_host, fsgm_sgm_device, their _ru and _exact forms).  Everything that can be refused without a device is refused here; the cached plans
 // and their pipelines live in capi_epi.hip (capi_sgm.h).
 #include "capi_sgm.h"
 #include "capi_device.h"
@@ -12,7 +12,7 @@ using namespace fsgm;
 // the checks both forms share: prm (NULL: the defaults) into c->prm, the scalars and the pointers every call needs
 static fsgm_status sgm_args(const char* who, int32_t n, const uint8_t* C, int32_t W, int32_t H, int32_t D, int32_t P1, int32_t P2,
                             const fsgm_sgm_params* prm, const uint8_t* guide, uint32_t* bestD, uint32_t* minC, uint32_t* S, uint32_t* minC2, bool ru,
-                            SgmCall* c) {
+                            bool exact, SgmCall* c) {
     FSGM_REQUIRE(n >= 1, "%s: n_frames must be >= 1 (got %d)", who, n);
     FSGM_REQUIRE(C && bestD && minC, "%s: null argument", who);
     FSGM_REQUIRE(!ru || minC2, "%s: null minC2", who);
@@ -35,9 +35,16 @@ static fsgm_status sgm_args(const char* who, int32_t n, const uint8_t* C, int32_
     if (ru && sp.agg_mode >= 2)
         return fail(FSGM_ERR_UNSUPPORTED, "%s: agg_mode %d with minC2: only the line kernels' WTA (modes 0 and 1) writes the runner-up cost", who,
                     sp.agg_mode);
+    if (exact) {                                                 // (the plain forms take any P1, P2: the reference narrows whatever they are)
+        FSGM_REQUIRE(P1 >= 0 && P1 <= 255, "%s: exact path arithmetic takes P1 in 0..255 (got %d)", who, P1);
+        FSGM_REQUIRE(P2 >= 0 && P2 <= 255, "%s: exact path arithmetic takes P2 in 0..255 (got %d)", who, P2);
+        if (sp.agg_mode >= 2)
+            return fail(FSGM_ERR_UNSUPPORTED, "%s: agg_mode %d with exact path arithmetic: only the line kernels (modes 0 and 1) carry path costs above 255",
+                        who, sp.agg_mode);
+    }
     if ((double)W * H * D >= 2147483648.0)
         return fail(FSGM_ERR_UNSUPPORTED, "%s: cost volume %d x %d x %d exceeds 2^31 voxels per frame", who, W, H, D);
-    *c = SgmCall{n, W, H, D, P1, P2, sp, C, sp.adaptive_p2 ? guide : nullptr, bestD, minC, S, ru ? minC2 : nullptr};
+    *c = SgmCall{n, W, H, D, P1, P2, sp, C, sp.adaptive_p2 ? guide : nullptr, bestD, minC, S, ru ? minC2 : nullptr, exact ? 1 : 0};
     return FSGM_OK;
 }
 
@@ -55,12 +62,12 @@ fsgm_sgm_params fsgm_sgm_params_default(void) {
 
 }  // extern "C"
 
-// both host forms; ru: the _ru form
+// every host form; ru: the _ru form, exact: the _exact form
 static fsgm_status sgm_host(const char* who, int32_t n, const uint8_t* C, int32_t W, int32_t H, int32_t D, int32_t P1, int32_t P2,
                             const fsgm_sgm_params* prm, const uint8_t* guide, uint32_t* bestD, uint32_t* minC, uint32_t* minC2, bool ru,
-                            uint32_t* S) {
+                            uint32_t* S, bool exact = false) {
     SgmCall c;
-    const fsgm_status st = sgm_args(who, n, C, W, H, D, P1, P2, prm, guide, bestD, minC, S, minC2, ru, &c);
+    const fsgm_status st = sgm_args(who, n, C, W, H, D, P1, P2, prm, guide, bestD, minC, S, minC2, ru, exact, &c);
     if (st != FSGM_OK) return st;
     // the true maximum of every frame, as fsgm_epi_plan_upload_cost takes it (either layout holds the same bytes)
     const size_t N = (size_t)W * H * D;
@@ -75,23 +82,26 @@ static fsgm_status sgm_host(const char* who, int32_t n, const uint8_t* C, int32_
     return sgm_run_host(c, cmax.data());
 }
 
-// both device forms
+// every device form
 static fsgm_status sgm_device(const char* who, int32_t n, const uint8_t* C, int32_t W, int32_t H, int32_t D, int32_t P1, int32_t P2,
                               const fsgm_sgm_params* prm, const uint8_t* guide, uint32_t* bestD, uint32_t* minC, uint32_t* minC2, bool ru,
-                              uint32_t* S, void* stream, int32_t* status) {
+                              uint32_t* S, void* stream, int32_t* status, bool exact = false) {
     SgmCall c;
-    fsgm_status st = sgm_args(who, n, C, W, H, D, P1, P2, prm, guide, bestD, minC, S, minC2, ru, &c);
+    fsgm_status st = sgm_args(who, n, C, W, H, D, P1, P2, prm, guide, bestD, minC, S, minC2, ru, exact, &c);
     if (st != FSGM_OK) return st;
     const size_t np = (size_t)n * W * H, nv = np * D;
     const hipStream_t cs = (hipStream_t)stream;
+    bool captured = false;
     if ((st = device_check_args(who, c.prm.device, cs, {{C, nv, 1, true, "C"},
                                                         {c.guide, np, 1, false, "guide"},
                                                         {bestD, np * 4, 4, true, "bestD"},
                                                         {minC, np * 4, 4, true, "minC"},
                                                         {c.minC2, np * 4, 4, ru, "minC2"},
                                                         {S, nv * 4, 4, false, "S"},
-                                                        {status, 4, 4, false, "status"}})) != FSGM_OK)
+                                                        {status, 4, 4, false, "status"}},
+                                /* a warm exact call may be captured into a graph (include/fsgm.h) */ exact ? &captured : nullptr)) != FSGM_OK)
         return st;
+    c.captured = captured;
     return sgm_run_device(c, cs, status);
 }
 
@@ -118,6 +128,17 @@ fsgm_status fsgm_sgm_device_ru(int32_t n, const uint8_t* C, int32_t W, int32_t H
                                const fsgm_sgm_params* prm, const uint8_t* guide, uint32_t* bestD, uint32_t* minC, uint32_t* minC2,
                                uint32_t* S, void* stream, int32_t* status) {
     return sgm_device("fsgm_sgm_device_ru", n, C, W, H, D, P1, P2, prm, guide, bestD, minC, minC2, true, S, stream, status);
+}
+
+fsgm_status fsgm_sgm_batch_host_exact(int32_t n, const uint8_t* C, int32_t W, int32_t H, int32_t D, int32_t P1, int32_t P2,
+                                      const fsgm_sgm_params* prm, const uint8_t* guide, uint32_t* bestD, uint32_t* minC, uint32_t* S) {
+    return sgm_host("fsgm_sgm_batch_host_exact", n, C, W, H, D, P1, P2, prm, guide, bestD, minC, nullptr, false, S, true);
+}
+
+fsgm_status fsgm_sgm_device_exact(int32_t n, const uint8_t* C, int32_t W, int32_t H, int32_t D, int32_t P1, int32_t P2,
+                                  const fsgm_sgm_params* prm, const uint8_t* guide, uint32_t* bestD, uint32_t* minC, uint32_t* S,
+                                  void* stream, int32_t* status) {
+    return sgm_device("fsgm_sgm_device_exact", n, C, W, H, D, P1, P2, prm, guide, bestD, minC, nullptr, false, S, stream, status, true);
 }
 
 }  // extern "C"

@@ -50,6 +50,9 @@ struct AggArgs {
     int adaptive = 0;       // line kernels only: 1 selects the ADAPT instantiations
     const uint8_t* I1 = nullptr;   // [frames][NP] the call's first image (read when adaptive)
     size_t i_frame_stride = 0;     // bytes between frames of I1
+    // exact path arithmetic (include/fsgm.h, "exact"): no narrowing of a path cost; L then holds y = L_r - C, one byte in [0, P2],
+    // per path.  Set by launch_aggregate for AGG_PACKED_EXACT / AGG_GENERIC_EXACT.  Last in the struct, as in WtaArgs
+    int exact = 0;
 };
 
 struct WtaArgs {
@@ -65,6 +68,13 @@ struct WtaArgs {
     // runner-up cost (line kernels' WTA only): [frames][NP] min { S[d] : |d - best| >= 2 }, 0xFFFFFFFF where no such d exists;
     // null: not computed.  Last in the struct: every other member keeps its kernarg offset
     uint32_t* minC2;
+};
+// exact path arithmetic (include/fsgm.h, "exact"): the volumes of WtaArgs::L hold y_r = L_r - C, and the WTA rebuilds
+// S = ndirs * C + the sum of the y_r from the frames' cost volumes here.  An argument of its own, after WtaArgs: no kernel that
+// takes a WtaArgs sees its arguments move
+struct WtaCostArgs {
+    const uint8_t* C;       // [frames] cost volumes; null: L holds the path costs themselves
+    size_t c_frame_stride;
 };
 
 // fused-sweep aggregation (epi_sweep.hip)
@@ -156,7 +166,8 @@ struct FbArgs {                // forward-backward check (calc_cost_sgm.cpp:429-
     int rect_shift = 0;       // rect * d_min of a search range that starts at d_min: Pd0 = (x + 1 + rect_shift, y + 1)
 };
 
-enum { AGG_PACKED_NOWRAP = 0, AGG_PACKED_WRAP = 1, AGG_GENERIC = 2, AGG_SWEEP = 3, AGG_PAIRS = 4, AGG_BAND = 5 };
+enum { AGG_PACKED_NOWRAP = 0, AGG_PACKED_WRAP = 1, AGG_GENERIC = 2, AGG_SWEEP = 3, AGG_PAIRS = 4, AGG_BAND = 5,
+       AGG_PACKED_EXACT = 6, AGG_GENERIC_EXACT = 7 };   // the line kernels without narrowing: P1, P2 in 0..255, any costs
 
 int  agg_packed_lpp(int D);   // lanes per pixel at 16 d per lane -- what the fused pipelines need --, 0 if D is not 16<<k, k<=4
 // the general line kernels' and the packed WTA's split of D: lpp lanes of dpl costs a pixel (either may be null).  16 << k as above
@@ -186,7 +197,8 @@ void launch_stereo_range(hipStream_t st, uint32_t* disp, uint32_t* disp2, size_t
 void launch_box5x5(hipStream_t st, int box, const uint8_t* Craw, uint8_t* C, int W, int H, int D, int frames);   // box: select_box_kernel(D)
 int  costbox_selftest(hipStream_t st);      // 0: the mean's fp16 multiply is exact on this device; > 0: mismatches; < 0: could not run
 void launch_aggregate(hipStream_t st, AggArgs a, int paths, int frames, int kernel_kind);
-void launch_wta(hipStream_t st, const WtaArgs& a, int frames, bool packed);
+// x.C set: an exact plan's volumes (never with a.minC2: the plan refuses the pair)
+void launch_wta(hipStream_t st, const WtaArgs& a, int frames, bool packed, WtaCostArgs x = WtaCostArgs{nullptr, 0});
 int    sweep_rows_per_launch(int D);
 size_t sweep_state_bytes(int W, int D);   // one state buffer of one frame
 void launch_sweep(hipStream_t st, const SweepArgs& a, int frames, int mode, int tall = 0);
@@ -209,5 +221,7 @@ void launch_vz_convert(hipStream_t st, uint32_t* bestD, const double* off, int W
 int  fused_step_selftest(hipStream_t st);   // 0: pk_max3 / pk_min3 of the fused step are exact u16 operations here
 void launch_copy16(hipStream_t st, void* dst, const void* src, size_t bytes);   // bytes % 4096 == 0; bandwidth probe
 void launch_sum_paths(hipStream_t st, const uint8_t* L, uint32_t* S, size_t n, size_t dir_stride, int ndirs);
+// the same over an exact plan's volumes: S = ndirs * C + the sum of the y_r in L
+void launch_sum_paths_exact(hipStream_t st, const uint8_t* L, const uint8_t* C, uint32_t* S, size_t n, size_t dir_stride, int ndirs);
 
 }  // namespace fsgm

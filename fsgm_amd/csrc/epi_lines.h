@@ -31,6 +31,12 @@ namespace fsgm {
 // WRAP=false requires 0<=P1, 0<=P2, max(C)+P2+max(P1,P2) <= 255: then none of the reference's
 // u8 narrowings changes a value and 16-bit lanes are exact.  WRAP=true reduces mod 256 at every
 // point where the reference narrows to unsigned char.
+//
+// EXACT (with WRAP=false; include/fsgm.h, "exact"): the same 16-bit arithmetic with no budget -- 0 <= P1, P2 <= 255 and any
+// costs.  Nothing narrows, so 0 <= L - C <= P2, L <= 255 + P2 <= 510, L + P1 <= 765 and t - m >= 0 (every candidate of t is a
+// path cost of the previous pixel, at least its minimum m): no half of a register ever wraps.  The absent neighbours of d = 0
+// and d = D-1 are 0xFFFF halves that meet a minimum with a real L BEFORE P1 is added, so they never turn into a small number.
+// What goes to the path volume is y = L - C (one byte, [0, P2]) instead of L, which no longer fits one; the WTA adds C back.
 // =============================================================================================
 #ifndef FSGM_AGG_PFX
 #define FSGM_AGG_PFX 16
@@ -44,7 +50,7 @@ namespace fsgm {
 // byte load a step into a ring of its own, PF steps ahead with the same clamped cursor (the LPP lanes of a pixel read the same
 // byte: one request), the predecessor's byte carried in a register; the choice is a compare and a select, no branch.  A path
 // start takes no step and reads no pair (:152-180), so what the carried byte holds there never matters.
-template <int D, int DPL, bool WRAP, int BASE, bool ADAPT = false>
+template <int D, int DPL, bool WRAP, int BASE, bool ADAPT = false, bool EXACT = false>
 __device__ __forceinline__ void agg_packed_body(const AggArgs& a, const int slot, const bool mirror) {
     constexpr int LPP = D / DPL;        // lanes per pixel
     constexpr int NK = DPL / 4;         // cost dwords per lane
@@ -54,6 +60,7 @@ __device__ __forceinline__ void agg_packed_body(const AggArgs& a, const int slot
     constexpr int PF = (BASE == 0 && NK == 1) ? FSGM_AGG_PFX : FSGM_AGG_PFO;
     constexpr uint32_t SENT = 0xFFFFFFFFu;
     constexpr uint32_t MASK = 0x00FF00FFu;
+    static_assert(!(EXACT && WRAP), "exact arithmetic is the no-wrap form without its budget");
     static_assert(LPP >= 1 && LPP <= 32 && (LPP & (LPP - 1)) == 0 && DPL % 4 == 0 && NK >= 1 && NK <= 7 && (NK <= 2 || NK == 4 || LPP <= 16),
                   "lane split");
     // NK = 3, 5, 7 (D = 48 .. 224, agg_line_split): a lane's costs start at pix * D + j * DPL, a multiple of 4 only
@@ -141,6 +148,7 @@ __device__ __forceinline__ void agg_packed_body(const AggArgs& a, const int slot
 
         const uint32_t mpk = m | (m << 16);
         uint32_t NE[NK], NO[NK];
+        uint32_t YE[EXACT ? NK : 1], YO[EXACT ? NK : 1];        // EXACT: y = L - C, what the path volume holds
         if (!WRAP) {
             const uint32_t p2lane = start ? 0u : (ADAPT && edge) ? P2apk : P2pk;   // min(.,0)=0 -> L = C at a path start
 #pragma unroll
@@ -150,8 +158,15 @@ __device__ __forceinline__ void agg_packed_body(const AggArgs& a, const int slot
                 const uint32_t tE = pk_min(LE[k], pk_add(nbE, P1pk));
                 const uint32_t tO = pk_min(LO[k], pk_add(nbO, P1pk));
                 // C + min(t, m+P2) - m  ==  C + min(t-m, P2)   (no wrap: t >= m)
-                NE[k] = pk_add(CE[k], pk_min(pk_sub(tE, mpk), p2lane));
-                NO[k] = pk_add(CO[k], pk_min(pk_sub(tO, mpk), p2lane));
+                if constexpr (EXACT) {
+                    YE[k] = pk_min(pk_sub(tE, mpk), p2lane);
+                    YO[k] = pk_min(pk_sub(tO, mpk), p2lane);
+                    NE[k] = pk_add(CE[k], YE[k]);
+                    NO[k] = pk_add(CO[k], YO[k]);
+                } else {
+                    NE[k] = pk_add(CE[k], pk_min(pk_sub(tE, mpk), p2lane));
+                    NO[k] = pk_add(CO[k], pk_min(pk_sub(tO, mpk), p2lane));
+                }
             }
         } else {
             const uint32_t jump = (m + ((ADAPT && edge) ? P2ab : P2b)) & 0xFFu;   // :46 u8(LpreMin + P2)
@@ -194,7 +209,8 @@ __device__ __forceinline__ void agg_packed_body(const AggArgs& a, const int slot
 #pragma unroll
         for (int k = 0; k < NK; k++) {
             LE[k] = NE[k]; LO[k] = NO[k];
-            o.v[k] = __builtin_amdgcn_perm(NO[k], NE[k], 0x06020400u);  // bytes E.lo, O.lo, E.hi, O.hi
+            if constexpr (EXACT) o.v[k] = __builtin_amdgcn_perm(YO[k], YE[k], 0x06020400u);
+            else o.v[k] = __builtin_amdgcn_perm(NO[k], NE[k], 0x06020400u);  // bytes E.lo, O.lo, E.hi, O.hi
         }
         return o;
     };
@@ -263,6 +279,7 @@ inline void plan_dirs(AggArgs& a, int paths, int lines_per_block_x, int lines_pe
 }
 
 // the rows of FSGM_LINE_CLASSES with 12, 20 or 28 costs a lane (epi_lines_split.hip); launch_aggregate sends them there
+// (a.exact: the exact kernels, wrap unused)
 void launch_split_lines(hipStream_t st, AggArgs& a, int paths, int frames, bool wrap);
 
 }  // namespace fsgm

@@ -329,7 +329,8 @@ template <int D> struct AggSplit {
 };
 
 // ADAPT: every direction on the general body (the hand-written bodies have no per-step P2), the along-x lines split finely
-template <int D, bool WRAP, bool FINE, bool ADAPT>
+// EXACT: the same (the hand-written bodies' sentinels and fp16 minima are sized for the no-wrap budget, and they store L)
+template <int D, bool WRAP, bool FINE, bool ADAPT, bool EXACT = false>
 __device__ __forceinline__ void agg_packed_dispatch(const AggArgs& a) {
     // which direction slot does this block belong to (block-uniform)
     int slot = 0;
@@ -341,13 +342,13 @@ __device__ __forceinline__ void agg_packed_dispatch(const AggArgs& a) {
     constexpr int DO = AggSplit<D>::other, DX = FINE ? AggSplit<D>::along_x : DO;
     switch (code & 3) {                 // 0: along x, 1: along y, 2: x+1,y+1, 3: x-1,y+1
         case 0:
-            if constexpr ((D == 32 || D == 64 || D == 128) && !WRAP && FINE && FSGM_AGG_XLEAN && !ADAPT) {
+            if constexpr ((D == 32 || D == 64 || D == 128) && !WRAP && FINE && FSGM_AGG_XLEAN && !ADAPT && !EXACT) {
                 if (mirror) agg_x_lean_body<D, true>(a, slot); else agg_x_lean_body<D, false>(a, slot);
-            } else agg_packed_body<D, DX, WRAP, 0, ADAPT>(a, slot, mirror);
+            } else agg_packed_body<D, DX, WRAP, 0, ADAPT, EXACT>(a, slot, mirror);
             break;
 #define FSGM_AGG_OTHER(BASE) \
-            if constexpr (!WRAP && DO == 16 && D >= 32 && D <= 256 && FSGM_AGG_LEAN && !ADAPT) agg_lean_body<D, BASE>(a, slot, mirror); \
-            else agg_packed_body<D, DO, WRAP, BASE, ADAPT>(a, slot, mirror);
+            if constexpr (!WRAP && DO == 16 && D >= 32 && D <= 256 && FSGM_AGG_LEAN && !ADAPT && !EXACT) agg_lean_body<D, BASE>(a, slot, mirror); \
+            else agg_packed_body<D, DO, WRAP, BASE, ADAPT, EXACT>(a, slot, mirror);
         case 1: FSGM_AGG_OTHER(1) break;
         case 2: FSGM_AGG_OTHER(2) break;
         default: FSGM_AGG_OTHER(3) break;
@@ -360,6 +361,10 @@ __global__ __launch_bounds__(256) void agg_packed_kernel(AggArgs a) { agg_packed
 
 template <int D, bool WRAP>
 __global__ __launch_bounds__(256) void agg_packed_adaptive_kernel(AggArgs a) { agg_packed_dispatch<D, WRAP, true, true>(a); }
+
+// exact path arithmetic (epi_lines.h, EXACT), with or without adaptive P2: kernels of their own, the ones above stay what they were
+template <int D, bool ADAPT>
+__global__ __launch_bounds__(256) void agg_packed_exact_kernel(AggArgs a) { agg_packed_dispatch<D, false, true, ADAPT, true>(a); }
 
 // =============================================================================================
 // Path aggregation, generic kernel: any D (<= FSGM_GENERIC_MAX_D), exact u8 semantics.
@@ -431,6 +436,71 @@ __global__ __launch_bounds__(256) void agg_generic_kernel(AggArgs a) {
     }
 }
 
+// The generic kernel with exact path arithmetic (include/fsgm.h, "exact"): path costs as u16 in LDS, no narrowing anywhere, the
+// true minimum over d; the path volume takes y = L - C (one byte, [0, P2]).  0 <= P1, P2 <= 255: L <= 510, every sum below 2^16.
+template <bool ADAPT>
+__global__ __launch_bounds__(256) void agg_generic_exact_kernel(AggArgs a) {
+    __shared__ uint16_t sL[4][2][FSGM_GENERIC_MAX_D + 2];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int slot = 0;
+#pragma unroll
+    for (int i = 1; i < 8; i++)
+        if (i < a.ndirs && (int)blockIdx.x >= a.blk_begin[i]) slot = i;
+    const int code = a.dir_code[slot];
+    const int base = code & 3;
+    const bool mirror = (code & 4) != 0;
+    const int W = a.W, H = a.H, D = a.D;
+    const int NP = W * H;
+    const int nlines = base == 0 ? H : W;
+    const int len = base == 0 ? W : H;
+    const int line = ((int)blockIdx.x - a.blk_begin[slot]) * 4 + wave;
+    if (line >= nlines) return;                              // wave-uniform
+    const uint8_t* __restrict__ Cf = a.C + (size_t)blockIdx.y * a.c_frame_stride;
+    uint8_t* __restrict__ Lf = a.L + (size_t)blockIdx.y * a.l_frame_stride + (size_t)slot * a.l_dir_stride;
+    int x = base >= 2 ? line : 0, pix = base == 0 ? line * W : line;
+    const int dpix = base == 0 ? 1 : (base == 1 ? W : (base == 2 ? W + 1 : W - 1));
+    uint16_t* pre = sL[wave][0];
+    uint16_t* cur = sL[wave][1];
+    uint32_t m = 0;
+    const uint8_t* __restrict__ If = ADAPT ? a.I1 + (size_t)blockIdx.y * a.i_frame_stride : nullptr;
+    int ipre = 0;                                            // ADAPT: the previous pixel of the path (unused at a path start)
+    for (int t = 0; t < len; t++) {
+        const bool start = (t == 0) || (base == 2 && x == 0) || (base == 3 && x == W - 1);
+        const size_t off = (size_t)(mirror ? NP - 1 - pix : pix) * D;
+        uint32_t lo = 0xFFFFFFFFu;
+        bool edge = false;
+        if constexpr (ADAPT) {                               // calc_cost_sgm.cpp:68-72
+            const int icur = If[mirror ? NP - 1 - pix : pix];
+            const int diff = icur - ipre;
+            edge = (diff < 0 ? -diff : diff) > 25;
+            ipre = icur;
+        }
+        const uint32_t p2 = (uint32_t)(edge ? a.P2 / 8 : a.P2);
+        for (int d = lane; d < D; d += 64) {
+            const uint32_t c = Cf[off + d];
+            uint32_t y = 0;                                  // a path start: L = C
+            if (!start) {
+                uint32_t best = pre[d];
+                if (d > 0) best = min(best, (uint32_t)pre[d - 1] + (uint32_t)a.P1);
+                if (d < D - 1) best = min(best, (uint32_t)pre[d + 1] + (uint32_t)a.P1);
+                y = min(best - m, p2);                       // best >= m: every candidate is a cost of the previous pixel or above one
+            }
+            cur[d] = (uint16_t)(c + y);
+            Lf[off + d] = (uint8_t)y;
+            lo = min(lo, c + y);
+        }
+#pragma unroll
+        for (int s = 32; s >= 1; s >>= 1) lo = min(lo, (uint32_t)__shfl_xor((int)lo, s));
+        m = start ? 0u : lo;
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_s_waitcnt(0xC07F);                  // lgkmcnt(0): LDS writes visible to the wave
+        uint16_t* tmp = pre; pre = cur; cur = tmp;
+        pix += dpix;
+        if (base == 2) { x++; if (x == W) { x = 0; pix -= W; } }
+        else if (base == 3) { x--; if (x < 0) { x = W - 1; pix += W; } }
+    }
+}
+
 // =============================================================================================
 // launchers and the lookups of FSGM_LINE_CLASSES
 // =============================================================================================
@@ -462,6 +532,13 @@ static bool agg_fine() {
 template <int D>
 static void launch_packed(hipStream_t st, AggArgs& a, int paths, int frames, bool wrap) {
     constexpr int DO = AggSplit<D>::other, DX = AggSplit<D>::along_x;
+    if (a.exact) {                                               // the general body for every direction, along x split finely
+        plan_dirs(a, paths, 4 * (64 / (D / DX)), 4 * (64 / (D / DO)));
+        dim3 grid(a.blk_begin[8], frames);
+        if (a.adaptive) hipLaunchKernelGGL((agg_packed_exact_kernel<D, true>), grid, dim3(256), 0, st, a);
+        else            hipLaunchKernelGGL((agg_packed_exact_kernel<D, false>), grid, dim3(256), 0, st, a);
+        return;
+    }
     if (a.adaptive) {                                            // the general body for every direction, along x split finely
         plan_dirs(a, paths, 4 * (64 / (D / DX)), 4 * (64 / (D / DO)));
         dim3 grid(a.blk_begin[8], frames);
@@ -489,6 +566,14 @@ static void launch_class(hipStream_t st, AggArgs& a, int paths, int frames, bool
 }
 
 void launch_aggregate(hipStream_t st, AggArgs a, int paths, int frames, int kernel_kind) {
+    a.exact = kernel_kind == AGG_PACKED_EXACT || kernel_kind == AGG_GENERIC_EXACT;
+    if (kernel_kind == AGG_GENERIC_EXACT) {
+        plan_dirs(a, paths, 4, 4);
+        dim3 grid(a.blk_begin[8], frames);
+        if (a.adaptive) hipLaunchKernelGGL(agg_generic_exact_kernel<true>, grid, dim3(256), 0, st, a);
+        else            hipLaunchKernelGGL(agg_generic_exact_kernel<false>, grid, dim3(256), 0, st, a);
+        return;
+    }
     if (kernel_kind == AGG_GENERIC) {
         plan_dirs(a, paths, 4, 4);
         dim3 grid(a.blk_begin[8], frames);

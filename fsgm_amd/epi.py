@@ -348,6 +348,7 @@ class EpiPlan:
                                                          self.sampling, int(direction)))
         self.adaptive_p2 = 0
         self.runner_up = 0
+        self.exact = 0
         self.d_min = 0
         if adaptive_p2:
             try:
@@ -397,6 +398,14 @@ class EpiPlan:
         every kernel selection is what it was."""
         check(self.lib.fsgm_epi_plan_set_runner_up(self._h, int(on)))
         self.runner_up = int(on)
+
+    def set_exact(self, on):
+        """Exact path arithmetic (include/fsgm.h, fsgm_sgm_batch_host_exact) on / off: path costs that are never narrowed to a
+        byte, for costs and penalties outside the no-wrap budget.  Such a plan runs "packed16/exact" or "generic/exact" at every
+        batch size and takes P1, P2 in 0..255 (status 1 otherwise): refused (status 4) while modes 2-6 are forced or the
+        runner-up switch is on, as set_agg_mode(2..6) and set_runner_up(1) are on such a plan.  It composes with adaptive P2."""
+        check(self.lib.fsgm_epi_plan_set_exact(self._h, int(on)))
+        self.exact = int(on)
 
     def set_d_min(self, d_min):
         """A rectified plan's search range starts at disparity d_min (|d_min| <= 1024; 0 at creation): candidate i is sampled at

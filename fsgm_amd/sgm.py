@@ -23,10 +23,23 @@ def _bind(lib):
     if hasattr(lib, "fsgm_sgm_batch_host_ru"):                   # (an older build behind FSGM_LIB_PATH has none): minC2 after minC
         lib.fsgm_sgm_batch_host_ru.argtypes = [i32, vp, i32, i32, i32, i32, i32, C.POINTER(SgmParams), vp, vp, vp, vp, vp]
         lib.fsgm_sgm_device_ru.argtypes = [i32, vp, i32, i32, i32, i32, i32, C.POINTER(SgmParams), vp, vp, vp, vp, vp, vp, vp]
+    if hasattr(lib, "fsgm_sgm_batch_host_exact"):                # (nor these): the plain forms' argument lists
+        lib.fsgm_sgm_batch_host_exact.argtypes = lib.fsgm_sgm_batch_host.argtypes
+        lib.fsgm_sgm_device_exact.argtypes = lib.fsgm_sgm_device.argtypes
     lib.fsgm_sgm_last_kernel.restype = C.c_char_p
     lib.fsgm_sgm_ingest_lds.argtypes = [i32, i32, C.POINTER(C.c_uint64)]
     lib.fsgm_epi_plan_ingest_cost_device.argtypes = [vp, i32, vp, i32, i32, vp, vp]
     return lib
+
+
+ARITHS = ("mod256", "exact")
+
+
+def arith_exact(arith):
+    """True for arith="exact", False for "mod256" (the MEX's unsigned char path costs)."""
+    if arith not in ARITHS:
+        raise ValueError(f"arith must be 'mod256' or 'exact' (got {arith!r})")
+    return arith == "exact"
 
 
 def layout_code(layout):
@@ -65,7 +78,7 @@ def ingest_lds(layout, dMax):
 
 
 def sgm_batch(Cvol, P1=7, P2=100, *, paths=4, layout="hwd", cost_bound=255, agg_mode=0, adaptive_p2=0, guide=None, subpixel=1,
-              return_sum=False, device=0, runner_up=False):
+              return_sum=False, device=0, runner_up=False, arith="mod256"):
     """[bestD, minC] = sgm(C, P1, P2) (fsgm_amd.sgm) on a batch of volumes in one call, through one cached plan of that batch:
     C uint8 (N, H, W, D) for layout "hwd" or (N, D, H, W) for "dhw" (a cost-volume network's output; transposed on the device);
     one volume without the leading N.  bestD, minC uint32 (N, H, W); return_sum adds S uint32 (N, H, W, D).
@@ -73,8 +86,15 @@ def sgm_batch(Cvol, P1=7, P2=100, *, paths=4, layout="hwd", cost_bound=255, agg_
     below 255 is refused (status 1).  agg_mode: EpiPlan.set_agg_mode's.  adaptive_p2=1 reads the edge-aware P2 from guide, the
     first image, uint8 (N, H, W).  runner_up=True (fsgm_sgm_batch_host_ru) returns minC2 uint32 (N, H, W) after minC, the
     runner-up cost min { S[d] : |d - best| >= 2 } (NO_RUNNER_UP where no such d exists): such a call runs the line kernels at
-    every batch size (last_kernel() shows it), and agg_mode 2..6 with it is refused (status 4)."""
+    every batch size (last_kernel() shows it), and agg_mode 2..6 with it is refused (status 4).
+    arith="exact" (fsgm_sgm_batch_host_exact): path costs as integers that are never narrowed -- the SGM recurrence itself where
+    the default "mod256" reproduces the MEX's unsigned char overflow, i.e. whenever max(C) + P2 + max(P1, P2) > 255 (inside that
+    budget the two agree bit for bit).  P1 and P2 must lie in 0..255 (status 1); such a call runs "packed16/exact" or
+    "generic/exact" at every batch size, agg_mode 2..6 with it is refused (status 4), and so is runner_up=True (ValueError)."""
     lib = _bind(_lib.load())
+    exact = arith_exact(arith)
+    if exact and runner_up:
+        raise ValueError("arith='exact' has no runner-up cost: runner_up=True needs arith='mod256'")
     code = layout_code(layout)
     Cvol = np.ascontiguousarray(Cvol)
     if Cvol.dtype != np.uint8:
@@ -94,6 +114,9 @@ def sgm_batch(Cvol, P1=7, P2=100, *, paths=4, layout="hwd", cost_bound=255, agg_
     if runner_up:
         check(lib.fsgm_sgm_batch_host_ru(N, ptr(Cvol), W, H, D, int(P1), int(P2), C.byref(prm), ptr(guide), ptr(bestD), ptr(minC),
                                          ptr(minC2), ptr(S)))
+    elif exact:
+        check(lib.fsgm_sgm_batch_host_exact(N, ptr(Cvol), W, H, D, int(P1), int(P2), C.byref(prm), ptr(guide), ptr(bestD), ptr(minC),
+                                            ptr(S)))
     else:
         check(lib.fsgm_sgm_batch_host(N, ptr(Cvol), W, H, D, int(P1), int(P2), C.byref(prm), ptr(guide), ptr(bestD), ptr(minC), ptr(S)))
     outs = (bestD, minC) + ((minC2,) if runner_up else ()) + ((S,) if return_sum else ())

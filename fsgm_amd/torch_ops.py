@@ -16,7 +16,8 @@ stereo fsgm::stereo_sgm_pp (the matcher and the chain of test.m:45-50) and fsgm:
 fsgm::stereo_sgm_ru (fsgm::stereo_sgm_range with the runner-up cost minC2 after minC) and fsgm::uniqueness_filter (status always 0);
 fsgm::sgm_ru and fsgm::sgm2d_ru (fsgm::sgm / fsgm::sgm2d with minC2 after minC) and fsgm::uniqueness_filter_planes (a map or a
 two-plane flow; status always 0); fsgm::pyramidal_sgm_ru and fsgm::pyramidal_sgm_ng_ru (the pyramids with level 1's minC2 after
-minC) and fsgm::pyramidal_flow_pp_u (fsgm::pyramidal_flow_pp with a uniqueness ratio ahead of the chain and minC2 after minC).
+minC) and fsgm::pyramidal_flow_pp_u (fsgm::pyramidal_flow_pp with a uniqueness ratio ahead of the chain and minC2 after minC);
+fsgm::sgm_exact (fsgm::sgm with exact path arithmetic, fsgm_sgm_device_exact: the same arguments and outputs).
 
 One process must hold one HIP runtime.  torch brings its own libamdhip64; libfsgm_hip.so binds to it by soname when torch is
 imported first.  When the library was loaded first, torch afterwards maps a second runtime, and a stream or pointer of one
@@ -34,7 +35,7 @@ from ._lib import EpiIn, EpiOut, EpiOptions, EpiParams, FsgmError, StereoParams
 from .epi import EpiGeometry, _d_min, _params as _epi_params, _stereo_params
 from .post import _bind as _bind_post
 from .stereo_pp import CHAIN_FIELDS as STEREO_PP_FIELDS, _bind as _bind_stereo_pp, pp_params as _stereo_pp_params
-from .sgm import _bind as _bind_sgm, layout_code as _layout_code, params as _sgm_params, shape_of as _sgm_shape
+from .sgm import _bind as _bind_sgm, arith_exact as _arith_exact, layout_code as _layout_code, params as _sgm_params, shape_of as _sgm_shape
 from .sgm2d import _bind as _bind_sgm2d, layout_code as _layout2d_code, params as _sgm2d_params, shape_of as _sgm2d_shape, LAYOUTS as _LAYOUTS2D
 from .pyramid import (PyramidParams, NgPyramidParams, FLOW_PP_FIELDS, MATCHERS, _bind as _bind_pyramid, _bind_flow_pp, _bind_ng,
                       uniqueness_ratio_of as _uniqueness_ratio_of)
@@ -279,6 +280,27 @@ def _sgm_op(C_: torch.Tensor, guide: torch.Tensor, P1: int, P2: int, paths: int,
 
 
 @_sgm_op.register_fake
+def _(C_, guide, P1, P2, paths, layout, cost_bound, agg_mode, adaptive_p2, subpixel, return_sum):
+    return _sgm_outputs(C_, layout, return_sum)
+
+
+@torch.library.custom_op("fsgm::sgm_exact", mutates_args=())
+def _sgm_exact_op(C_: torch.Tensor, guide: torch.Tensor, P1: int, P2: int, paths: int, layout: int, cost_bound: int, agg_mode: int,
+                  adaptive_p2: int, subpixel: int, return_sum: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """fsgm::sgm with exact path arithmetic (fsgm_sgm_device_exact): P1, P2 in 0..255, the line kernels at every batch size"""
+    N, H, W, D = _sgm_out_shape(C_, layout)
+    dev = C_.device
+    C_ = C_.contiguous()
+    guide = guide.contiguous() if adaptive_p2 else None
+    bestD, minC, S, status = _sgm_outputs(C_, layout, return_sum)
+    prm = _sgm_params(_L, paths=paths, subpixel=subpixel, device=dev.index, agg_mode=agg_mode, layout="dhw" if layout else "hwd",
+                      cost_bound=cost_bound, adaptive_p2=adaptive_p2)
+    _call(dev, _L.fsgm_sgm_device_exact, N, _p(C_), W, H, D, int(P1), int(P2), C.byref(prm), _p(guide), _p(bestD), _p(minC),
+          _p(S) if return_sum else None, _stream(dev), _p(status))
+    return bestD, minC, S, status
+
+
+@_sgm_exact_op.register_fake
 def _(C_, guide, P1, P2, paths, layout, cost_bound, agg_mode, adaptive_p2, subpixel, return_sum):
     return _sgm_outputs(C_, layout, return_sum)
 
@@ -839,7 +861,7 @@ def calc_cost_sgm_linear(I1, I2, dMax, pixelPosD0, normlizeDirection, P1, P2, *,
 
 
 def sgm(Cvol, P1=7, P2=100, *, layout="dhw", paths=4, cost_bound=255, agg_mode=0, adaptive_p2=0, guide=None, subpixel=1,
-        return_sum=False, check=False, return_status=False, runner_up=False):
+        return_sum=False, check=False, return_status=False, runner_up=False, arith="mod256"):
     """bestD, minC = sgm(C, P1, P2) as fsgm_amd.sgm_batch, on a cost volume that is already in HBM: C uint8 (D, H, W) or a batch
     (N, D, H, W) for layout "dhw" (a cost-volume network's output), (H, W, D) / (N, H, W, D) for "hwd".  The volume is read where
     it lies, every output stays in HBM, the work is queued on the current stream.  bestD, minC uint32 (.., H, W); return_sum
@@ -847,7 +869,12 @@ def sgm(Cvol, P1=7, P2=100, *, layout="dhw", paths=4, cost_bound=255, agg_mode=0
     and every cost is saturated at it on the way in.  The status tensor (return_status=True) is FSGM_ERR_INVALID when a cost was
     above the bound (the outputs are then those of the saturated volume), FSGM_ERR_HIP when an aggregation hand-off gave up;
     check=True synchronises and raises on either.  adaptive_p2=1 needs guide, the first image, uint8 (.., H, W).  runner_up=True
-    (fsgm::sgm_ru) returns minC2 uint32 after minC, as fsgm_amd.sgm_batch does."""
+    (fsgm::sgm_ru) returns minC2 uint32 after minC, as fsgm_amd.sgm_batch does.  arith="exact" (fsgm::sgm_exact): path costs that
+    are never narrowed to a byte, as fsgm_amd.sgm_batch(arith="exact") -- P1, P2 in 0..255, the line kernels at every batch size;
+    with runner_up=True it raises ValueError."""
+    exact = _arith_exact(arith)
+    if exact and runner_up:
+        raise ValueError("arith='exact' has no runner-up cost: runner_up=True needs arith='mod256'")
     code = _layout_code(layout)
     named = {"C": (Cvol, torch.uint8)}
     if guide is not None:
@@ -868,6 +895,8 @@ def sgm(Cvol, P1=7, P2=100, *, layout="dhw", paths=4, cost_bound=255, agg_mode=0
             int(bool(return_sum)))
     if runner_up:
         bestD, minC, minC2, S, status = torch.ops.fsgm.sgm_ru(*args)
+    elif exact:
+        bestD, minC, S, status = torch.ops.fsgm.sgm_exact(*args)
     else:
         bestD, minC, S, status = torch.ops.fsgm.sgm(*args)
     outs = (bestD, minC) + ((minC2,) if runner_up else ()) + ((S,) if return_sum else ())

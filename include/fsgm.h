@@ -303,6 +303,15 @@ fsgm_status fsgm_epi_plan_set_adaptive_p2(fsgm_epi_plan* plan, int32_t on);
  * changes nothing, and so does switching it on after such a mode was forced.  The first 1 allocates batch * W * H * 4 bytes.  With
  * 0 every output and every kernel selection is what it was; with 1 bestD, minC, conf and bestD2 are those of mode 1. */
 fsgm_status fsgm_epi_plan_set_runner_up(fsgm_epi_plan* plan, int32_t on);
+/* Exact path arithmetic ("exact" under fsgm_sgm_batch_host_exact below) for this plan, 0 at creation, under the rules of the two
+ * switches above: with it on the plan resolves to "packed16/exact" (the dMax classes of the line kernels) or "generic/exact"
+ * (every other dMax) whatever its batch, costs and penalties; fsgm_epi_plan_set_agg_mode(2..6) returns FSGM_ERR_UNSUPPORTED and
+ * changes nothing, and so does switching it on after such a mode was forced.  It composes with adaptive P2 and not with the
+ * runner-up cost: either of the two switches going on while the other is on is FSGM_ERR_UNSUPPORTED.  An exact plan takes P1
+ * and P2 in 0..255: fsgm_epi_plan_set_penalties with anything else, and switching it on over such penalties, is
+ * FSGM_ERR_INVALID.  Its path volumes hold L_r - C, so fsgm_epi_plan_download_sum rebuilds S from them and the plan's cost
+ * volume.  With 0 every output and every kernel selection is what it was. */
+fsgm_status fsgm_epi_plan_set_exact(fsgm_epi_plan* plan, int32_t on);
 /* The first disparity of a FSGM_SAMPLING_RECTIFIED plan's search range (0 at creation; fsgm_stereo_sgm_host_range above): read
  * by the next cost stage and forward-backward check.  The plan's own outputs stay candidate indices * 256 (fsgm_epi_plan_download,
  * _download_fb with 512 << 8 for invalid).  Any other plan: FSGM_ERR_UNSUPPORTED; |d_min| > FSGM_D_MIN_LIMIT: FSGM_ERR_INVALID;
@@ -347,7 +356,8 @@ void*       fsgm_epi_plan_stream(fsgm_epi_plan* plan);
  * pipeline), "packed16/nowrap", "packed16/wrap" (per-direction line kernels: dMax = 16, 32, 64, 128, 256 at 16 costs a lane,
  * and 48, 96, 192 / 80, 160 / 112, 224 at 12 / 20 / 28 costs a lane -- these seven take the line kernels at every batch size
  * and under every forced mode, the fused pipelines being built for 16 costs a lane), "generic" (any other dMax, 144, 176, 208
- * and 240 included).  New names may be added: dispatch on these with a default branch. */
+ * and 240 included); on a plan with exact path arithmetic (fsgm_epi_plan_set_exact) "packed16/exact" (the same dMax classes) and
+ * "generic/exact" (any other dMax).  New names may be added: dispatch on these with a default branch. */
 const char* fsgm_epi_plan_kernel_name(fsgm_epi_plan* plan);
 /* The same answer without a plan: what auto mode takes for `batch` frames of width x height x dMax with these penalties, costs
  * up to cmax (24 for volumes built by the cost stage) and a device of `cus` compute units (MI355X: 256).  The switch points
@@ -425,8 +435,28 @@ fsgm_status fsgm_sgm_batch_host(int32_t n_frames, const uint8_t* C, int32_t widt
 fsgm_status fsgm_sgm_batch_host_ru(int32_t n_frames, const uint8_t* C, int32_t width, int32_t height, int32_t dMax, int32_t P1,
                                    int32_t P2, const fsgm_sgm_params* prm, const uint8_t* guide, uint32_t* bestD, uint32_t* minC,
                                    uint32_t* minC2, uint32_t* S);
-/* the pipeline (fsgm_epi_plan_kernel_name's names) that the calling thread's last fsgm_sgm_batch_host / fsgm_sgm_device ran,
- * "" before the first */
+/* fsgm_sgm_batch_host with EXACT path arithmetic: the SGM recurrence on integers, for volumes and penalties outside the no-wrap
+ * budget cmax + P2 + max(P1, P2) <= 255, where the call above reproduces the MEX's unsigned char overflow (a volume of bytes up
+ * to 255 at sgm.m's default P1 = 7, P2 = 100 is far outside it).  Everything is the MEX's (calc_cost_sgm.cpp:86-316) except that
+ * a path cost is never narrowed:
+ *   path start (:152-180)  L[d] = C[d], stored minimum m = 0 (the quirk is kept);
+ *   step                   L[d] = C[d] + min(Lp[d], Lp[d-1] + P1 (d > 0), Lp[d+1] + P1 (d < dMax-1), m_p + P2) - m_p, then
+ *                          m = min over d of L[d], the true minimum (the reference's initial 255, :39, is no clamp here);
+ *   adaptive P2            P2 / 8 in place of P2 where |I1[cur] - I1[pre]| > 25, per step, as in the call above;
+ *   S, WTA, sub-pixel      S = sum over the paths of L in u32; first minimum, the bestIdx > 1 && bestIdx < dMax rule, the
+ *                          parabola and bestD = index * 256 (+ sub-pixel) exactly as the call above computes them from S;
+ *   passes and paths       pass 1 the point mirror of pass 0, diagonals re-entering at the opposite border, 4 or 8 paths.
+ * Then 0 <= L - C <= P2, L <= 255 + P2 and S <= 8 * (255 + P2).  Inside the no-wrap budget the outputs are those of the call
+ * above, bit for bit.  P1 and P2 must lie in 0..255 (P1 > P2 is allowed), anything else is FSGM_ERR_INVALID before a device is
+ * touched; cost_bound is treated as above (the host form scans C, the device form saturates at it) and selects nothing.
+ * The cached plan has the epipolar plan's exact switch on (fsgm_epi_plan_set_exact) and is never the plan of a plain call; it
+ * runs the line kernels at every batch size -- fsgm_sgm_last_kernel answers "packed16/exact" or "generic/exact" -- and
+ * agg_mode 2..6 with it is FSGM_ERR_UNSUPPORTED before a device is touched.  There is no exact form with minC2. */
+fsgm_status fsgm_sgm_batch_host_exact(int32_t n_frames, const uint8_t* C, int32_t width, int32_t height, int32_t dMax, int32_t P1,
+                                      int32_t P2, const fsgm_sgm_params* prm, const uint8_t* guide, uint32_t* bestD, uint32_t* minC,
+                                      uint32_t* S);
+/* the pipeline (fsgm_epi_plan_kernel_name's names) that the calling thread's last fsgm_sgm_batch_host / fsgm_sgm_device (any
+ * of their forms) ran, "" before the first */
 const char* fsgm_sgm_last_kernel(void);
 /* The static LDS (bytes per workgroup) of the kernel that brings volumes of this layout into a plan, answered without a
  * device: 0 for FSGM_COST_LAYOUT_HWD (a copy), one padded tile for FSGM_COST_LAYOUT_DHW whatever dMax (1..1024) is. */
@@ -1161,6 +1191,22 @@ fsgm_status fsgm_sgm_device(int32_t n_frames, const uint8_t* C, int32_t width, i
 fsgm_status fsgm_sgm_device_ru(int32_t n_frames, const uint8_t* C, int32_t width, int32_t height, int32_t dMax, int32_t P1, int32_t P2,
                                const fsgm_sgm_params* prm, const uint8_t* guide, uint32_t* bestD, uint32_t* minC, uint32_t* minC2,
                                uint32_t* S, void* stream, int32_t* status);
+/* fsgm_sgm_batch_host_exact on device pointers: exact path arithmetic (see there), everything else -- ingest saturating at
+ * cost_bound, the status word, S -- as fsgm_sgm_device, with one exception to this section's contract: a stream that is being
+ * captured into a graph is accepted.  Once the same call (shape, n_frames, paths, switches, with or without S and guide) has run
+ * outside a capture, the cached plan and its buffers exist and a call allocates nothing and waits for nothing: the capture records
+ * the plan's stream as a branch between two events.  A captured call whose plan or buffers do not exist yet is
+ * FSGM_ERR_UNSUPPORTED before anything is queued or allocated.
+ * Lifetime: the graph names the caller's arrays AND the cached plan's buffers, stream and events.  The plan is pinned from the
+ * captured call on -- never evicted by later calls of other shapes, held beside the usual number of cached plans -- and is
+ * destroyed by fsgm_shutdown alone: the graph may be replayed while the caller's arrays live and until fsgm_shutdown.
+ * Ordering: a replay is ordered by the stream the graph is launched on, not by the plan's stream.  A later or earlier
+ * fsgm_sgm_device_exact call of the same shape on that same stream is ordered against the replay by its event join; calls of the
+ * same shape and switches from another stream or thread, and fsgm_sgm_batch_host_exact of that shape, share the plan's buffers
+ * with the graph and are NOT ordered against a replay: the caller must keep them apart (an event or a synchronise). */
+fsgm_status fsgm_sgm_device_exact(int32_t n_frames, const uint8_t* C, int32_t width, int32_t height, int32_t dMax, int32_t P1,
+                                  int32_t P2, const fsgm_sgm_params* prm, const uint8_t* guide, uint32_t* bestD, uint32_t* minC,
+                                  uint32_t* S, void* stream, int32_t* status);
 /* The first step of fsgm_sgm_device on its own, into a caller's plan: n_frames (= the plan's batch) volumes in `layout` from
  * device memory into the plan's cost volumes (what fsgm_epi_plan_upload_cost fills from the host), saturated at cost_bound,
  * which becomes the bound the plan selects its kernels by.  status: 0 or FSGM_ERR_INVALID (a byte above cost_bound). */
