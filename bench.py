@@ -7,8 +7,14 @@ over one batch of --frames-per-gpu (default 512) cost volumes that are already r
 across ranks with no collective in the data path (weak scaling: per-GPU batch fixed).
 
   python bench.py --gpus 1 --steps 20 --warmup 3
+  python bench.py --gpus 1 --steps 20 --warmup 3 --full
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the result line (metric, value,
+ms_per_step, the configuration it ran).  Everything else the benchmark measures or checks takes runs of its own and is
+behind --full: the self-check of the timed output against the line kernels, the stage times and the roofline block
+(copy-bandwidth probes included), the whole-MEX and host-call legs and the CPU baselines.
 """
 import argparse
 import json
@@ -331,35 +337,37 @@ def in_process(args):
         pl.sync()
     dt = time.perf_counter() - t0
     dumped = dump_outputs(args.dump_outputs, plans[0], B) if args.dump_outputs else None
-    # self-check: frame 0 of every entry against the line kernels on the same volume
-    ok = True
-    for slot, pl in enumerate(plans):
-        got = pl.download(0)
-        with EpiPlan(W, H, D, 1, paths=PATHS, device=devs[slot]) as ref:
-            ref.set_penalties(P1, P2, VMAX)
-            ref.set_agg_mode(1)
-            ref.upload_cost(0, check[slot])
-            ref.upload_offset(0, off)
-            ref.run(stages)
-            r = ref.download(0)
-        ok = ok and np.array_equal(got[0], r[0]) and np.array_equal(got[1], r[1])
-    assert ok, "an entry's bestD/minC differ from the line kernels' on the same volume"
     bus = [_pci_bus_id(d) for d in devs]
     vps = N * B * W * H * D * PATHS
-    alg = B * W * H * D * PATHS
-    stage_ms = [pl.time(STAGE_AGGREGATE, warmup=1, iters=3) for pl in plans[:1]][0]
-    achieved = alg / (stage_ms * 1e-3) / 1e9
     out = {"metric": f"aggregated cost-volume voxel-paths/s (HxWxDx{PATHS} paths), KITTI 1242x375 D=128", "value": vps * args.steps / dt,
            "unit": "voxel-paths/s", "n_gpus": len(set(bus)), "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u8", "data": "synthetic",
            "config": {"workload": f"KITTI 1242x375 D=128, {PATHS} paths, aggregation stage (C resident in HBM -> bestD/minC)",
                       "frames_per_gpu": B, "total_frames": N * B, "in_process_entries": N, "device_list": devs, "kernel": plans[0].kernel_name,
                       "sharding": "frames by device-list entry inside one process, no collective", "pci_bus_ids": bus, "distinct_devices": len(set(bus))},
-           "roofline": {"bound": "hbm", "kernel": "aggregation stage of entry 0 alone", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                        "frac": achieved / HBM_PEAK_GBS, "traffic": None, "algorithmic_bytes": alg, "stage_ms": stage_ms},
-           "checked": True, "argv": " ".join(sys.argv[1:])}
+           "full": bool(args.full), "argv": " ".join(sys.argv[1:])}
     if dumped:
         out["dump_outputs"] = dumped
+    if args.full:
+        # self-check: frame 0 of every entry against the line kernels on the same volume
+        ok = True
+        for slot, pl in enumerate(plans):
+            got = pl.download(0)
+            with EpiPlan(W, H, D, 1, paths=PATHS, device=devs[slot]) as ref:
+                ref.set_penalties(P1, P2, VMAX)
+                ref.set_agg_mode(1)
+                ref.upload_cost(0, check[slot])
+                ref.upload_offset(0, off)
+                ref.run(stages)
+                r = ref.download(0)
+            ok = ok and np.array_equal(got[0], r[0]) and np.array_equal(got[1], r[1])
+        assert ok, "an entry's bestD/minC differ from the line kernels' on the same volume"
+        alg = B * W * H * D * PATHS
+        stage_ms = plans[0].time(STAGE_AGGREGATE, warmup=1, iters=3)
+        achieved = alg / (stage_ms * 1e-3) / 1e9
+        out["roofline"] = {"bound": "hbm", "kernel": "aggregation stage of entry 0 alone", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                           "frac": achieved / HBM_PEAK_GBS, "traffic": None, "algorithmic_bytes": alg, "stage_ms": stage_ms}
+        out["checked"] = True
     for pl in plans:
         pl.close()
     print(json.dumps(out), flush=True)
@@ -380,9 +388,13 @@ def main():
     ap.add_argument("--agg-mode", type=int, default=0, choices=[0, 1, 2, 3, 4, 5, 6],
                     help="force an aggregation pipeline (fsgm_epi_plan_set_agg_mode): 0 auto (default), 1 line kernels, 2 fused sweeps / pairs, "
                          "3 parallel sweeps, 4 band sweeps, 5 chained band sweeps, 6 parallel sweeps meeting in the middle")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what the headline figure does not need: the self-check of the timed output against "
+                         "the line kernels (checked), the stage times and the roofline block, the whole-MEX and host-call legs, the CPU "
+                         "baselines.  Off by default: a plain run sets up, warms up, times the steps and prints the result line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baselines out")
     ap.add_argument("--no-extras", action="store_true",
-                    help="only the timed loop, the self-check and the roofline block (no whole-MEX / host-call legs): for profiler runs")
+                    help="with --full: only the timed loop, the self-check and the roofline block (no whole-MEX / host-call legs): for profiler runs")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N>1 (nccl = RCCL; gloo to rehearse on one GPU)")
     ap.add_argument("--paths", type=int, default=8, choices=[4, 8],
                     help="8 = the headline metric (default); 4 = the reference's shipped configuration (no diagonal "
@@ -472,8 +484,9 @@ def main():
             plan.copy_cost(f, f % 4, 37 * (f // 4))         # the same rotation, device to device (no PCIe transfer per frame)
         plan.upload_offset(f, off)
     plan.sync()
-    check_frames = sorted({int(round(i * (B - 1) / 15)) for i in range(16)}) if B > 1 else [0]     # 16 frames spread over the batch
-    check_vols = [frame_volume(f) for f in check_frames]
+    if args.full:
+        check_frames = sorted({int(round(i * (B - 1) / 15)) for i in range(16)}) if B > 1 else [0]     # 16 frames spread over the batch
+        check_vols = [frame_volume(f) for f in check_frames]
     del bases
     stages = STAGE_AGGREGATE | STAGE_WTA
 
@@ -497,6 +510,33 @@ def main():
         dt = float(t.item())
     dumped = dump_outputs(args.dump_outputs, plan, B) if args.dump_outputs and rank == 0 else None
 
+    def result_line():
+        """What a plain run prints: the headline figure and the configuration it ran (nothing here launches a kernel)."""
+        total_frames = args.total_frames if strong else world * B
+        out = {
+            "metric": f"aggregated cost-volume voxel-paths/s (HxWxDx{PATHS} paths), KITTI 1242x375 D=128",
+            "value": total_frames * W * H * D * PATHS * args.steps / dt, "unit": "voxel-paths/s", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True,
+            "scaling": "strong" if strong else "weak", "vs_baseline": None, "dtype": "u8", "data": "synthetic",
+            "config": {"workload": f"KITTI 1242x375 D=128, {PATHS} paths, aggregation stage (C resident in HBM -> bestD/minC)",
+                       "frames_per_gpu": B, "total_frames": total_frames, "P1": P1, "P2": P2, "kernel": plan.kernel_name,
+                       "step": f"aggregate({PATHS} paths) + sum/WTA/subpixel", "sharding": "frames, no collective",
+                       "pci_bus_ids": bus_ids, "distinct_devices": len(set(bus_ids))},
+            "full": bool(args.full), "argv": " ".join(sys.argv[1:]),
+        }
+        if dumped:
+            out["dump_outputs"] = dumped
+        return out
+
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(result_line()), flush=True)
+        plan.close()
+        if world > 1:
+            dist.destroy_process_group()
+        return
+
+    # --full from here on: checks and measurements beside the headline figure, each with runs of its own
     # self-check of what the timed loop left behind: two frames of the timed plan against the per-direction line
     # kernels (agg mode 1: a different implementation of the same recurrence, itself checked against the oracle
     # in tests/) on a second plan holding the same volumes
@@ -525,9 +565,6 @@ def main():
     except Exception:
         hbm_used_gb = None
     if rank == 0:
-        total_frames = args.total_frames if strong else world * B
-        voxel_paths_step = total_frames * W * H * D * PATHS
-        value = voxel_paths_step * args.steps / dt
         alg_bytes_launch = B * W * H * D * PATHS            # 1 byte of C per voxel-path
         # which kernels the stage is made of depends on the pipeline the plan picked for this batch size;
         # where the argmin is a kernel of its own (parallel sweeps, line kernels) it belongs to the timed stage
@@ -542,16 +579,9 @@ def main():
         stage_time_ms = agg_ms + (wta_ms if stage_kernels[1] else 0.0)
         achieved = alg_bytes_launch / (stage_time_ms * 1e-3) / 1e9
         bpv, traffic_src = measured_traffic(plan.kernel_name, PATHS)
-        out = {
-            "metric": f"aggregated cost-volume voxel-paths/s (HxWxDx{PATHS} paths), KITTI 1242x375 D=128",
-            "value": value, "unit": "voxel-paths/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True,
-            "scaling": "strong" if strong else "weak", "vs_baseline": None, "dtype": "u8", "data": "synthetic",
-            "config": {"workload": f"KITTI 1242x375 D=128, {PATHS} paths, aggregation stage (C resident in HBM -> bestD/minC)",
-                       "frames_per_gpu": B, "total_frames": total_frames, "P1": P1, "P2": P2, "kernel": plan.kernel_name,
-                       "step": f"aggregate({PATHS} paths) + sum/WTA/subpixel", "sharding": "frames, no collective",
-                       "pci_bus_ids": bus_ids, "distinct_devices": len(set(bus_ids)), "hbm_in_use_GB_after_timed_loop": hbm_used_gb},
-            "argv": " ".join(sys.argv[1:]),
+        out = result_line()
+        out["config"]["hbm_in_use_GB_after_timed_loop"] = hbm_used_gb
+        out.update({
             # band sweeps: the stage is two kernels back to back on the plan's stream (first pass, second pass + WTA),
             # each 4 voxel-paths per voxel: HIP events around the pair = the sum of their durations (rocprofv3 kernel
             # stats of this command: profiles/).  Block sweeps / pair pipeline (smaller batches): kernel types that run
@@ -569,9 +599,7 @@ def main():
                          "algorithmic_bytes": alg_bytes_launch, "stage_ms": agg_ms, "finish_ms": wta_ms},
             "checked": bool(checked),
             "check": f"frames {check_frames} of the timed plan == line kernels ({ref_kernel}) on the same volumes, bestD and minC, all pixels",
-        }
-        if dumped:
-            out["dump_outputs"] = dumped
+        })
         try:
             import ctypes as C
             g = C.c_double()

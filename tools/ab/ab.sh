@@ -5,6 +5,6 @@ set -o pipefail
 B=$1; shift
 for r in $(seq 1 ${AB_ROUNDS:-3}); do
   for L in "$@"; do
-    FSGM_LIB_PATH=$PWD/$L timeout -k 10 300 python bench.py --steps 10 --warmup 2 --no-cpu-baseline --frames-per-gpu $B $AB_ARGS 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$L', '%.4g'%d['value'], '%.3f ms'%d['ms_per_step'], 'checked', d.get('checked'))" || exit 1
+    FSGM_LIB_PATH=$PWD/$L timeout -k 10 300 python bench.py --steps 10 --warmup 2 --full --no-cpu-baseline --frames-per-gpu $B $AB_ARGS 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$L', '%.4g'%d['value'], '%.3f ms'%d['ms_per_step'], 'checked', d.get('checked'))" || exit 1
   done
 done
