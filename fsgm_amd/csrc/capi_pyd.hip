@@ -132,8 +132,19 @@ extern "C" {
 fsgm_status fsgm_pyd_plan_set_params(fsgm_pyd_plan* p, int32_t P1, int32_t P2, int32_t diag, int32_t totalPass,
                                      int32_t adaptive, int32_t subpixel) {
     FSGM_REQUIRE(p, "null plan");
+    FSGM_REQUIRE(!p->exact || (P1 >= 0 && P1 <= 255), "fsgm_pyd_plan_set_params: exact path arithmetic needs P1 in 0..255 (got %d)", P1);
+    FSGM_REQUIRE(!p->exact || (P2 >= 0 && P2 <= 255), "fsgm_pyd_plan_set_params: exact path arithmetic needs P2 in 0..255 (got %d)", P2);
     p->P1 = P1; p->P2 = P2; p->diagonal = diag != 0; p->totalPass = totalPass;
     p->adaptive = adaptive != 0; p->subpixel = subpixel;
+    return FSGM_OK;
+}
+
+fsgm_status fsgm_pyd_plan_set_exact(fsgm_pyd_plan* p, int32_t on) {
+    FSGM_REQUIRE(p, "null plan");
+    FSGM_REQUIRE(on == 0 || on == 1, "fsgm_pyd_plan_set_exact: on must be 0 or 1 (got %d)", on);
+    FSGM_REQUIRE(!on || (p->P1 >= 0 && p->P1 <= 255), "fsgm_pyd_plan_set_exact: exact path arithmetic needs P1 in 0..255 (the plan's is %d)", p->P1);
+    FSGM_REQUIRE(!on || (p->P2 >= 0 && p->P2 <= 255), "fsgm_pyd_plan_set_exact: exact path arithmetic needs P2 in 0..255 (the plan's is %d)", p->P2);
+    p->exact = on;
     return FSGM_OK;
 }
 
@@ -208,6 +219,10 @@ static int fsgm_env_wide() {
 }
 
 fsgm_status fsgm::pyd_enqueue(fsgm_pyd_plan* p, int stages, uint32_t* dS) {
+    // the path volumes hold L after a plain aggregation and y = L - C after an exact one: a WTA reads what its own kind wrote
+    if ((stages & FSGM_STAGE_WTA) && !(stages & FSGM_STAGE_AGGREGATE) && p->exact != p->agg_exact)
+        return fail(FSGM_ERR_INVALID, "the exact switch was toggled since the last aggregation: the path volumes hold %s, run "
+                    "FSGM_STAGE_AGGREGATE before a WTA alone", p->agg_exact ? "y = L - C" : "L");
     PydAggArgs g;
     PydWtaArgs w;
     // (a plan without an image -- aggregation-only, no adaptive P2: the kernels fetch the intensity step of every path step and
@@ -219,7 +234,8 @@ fsgm_status fsgm::pyd_enqueue(fsgm_pyd_plan* p, int stages, uint32_t* dS) {
     // cmax: 24 for volumes built here (census 5x5 Hamming mean; out-of-image taps add 5), else as uploaded
     const int cm = (stages & FSGM_STAGE_COST) ? 24 : p->cmax;
     const bool nowrap = p->P1 >= 0 && p->P2 >= 0 && cm + p->P2 + (p->P1 > p->P2 ? p->P1 : p->P2) <= 255;
-    const bool rows = nowrap && p->dDesc != nullptr;        // row-packed aggregation (pyd_rows.hip)
+    const bool exact = p->exact != 0;                        // pyd_exact.hip's two kernels, whatever the budget and the window
+    const bool rows = !exact && nowrap && p->dDesc != nullptr;   // row-packed aggregation (pyd_rows.hip)
     // A single landscape frame is bounded by its longest serial chains, the horizontal lines: those take
     // the kernel's one-line-per-wave mapping (fewer instructions per step); batches keep the packed one.
     const bool wide_rows = rows && p->batch <= 2 && p->W > p->H && fsgm_env_wide() != 0;
@@ -236,8 +252,11 @@ fsgm_status fsgm::pyd_enqueue(fsgm_pyd_plan* p, int stages, uint32_t* dS) {
         p->cmax = 24;
     }
     if (stages & FSGM_STAGE_AGGREGATE) {
-        p->agg_name = rows ? (wide ? "rows/wide" : "rows") : nowrap ? "generic" : "generic/wrap";
-        if (rows) {
+        p->agg_name = exact ? "generic/exact" : rows ? (wide ? "rows/wide" : "rows") : nowrap ? "generic" : "generic/wrap";
+        p->agg_exact = p->exact;
+        if (exact) {
+            launch_pyd_agg_exact(p->stream, g, p->batch);
+        } else if (rows) {
             // (making the descriptors on a side stream while the cost volume is built was tried: the event
             // fork/join costs more than the 0.06 ms it hides -- 1.71 vs 1.68 ms per 3-level pyramid)
             launch_pyd_rows_desc(p->stream, g, p->batch);
@@ -251,7 +270,8 @@ fsgm_status fsgm::pyd_enqueue(fsgm_pyd_plan* p, int stages, uint32_t* dS) {
         w.W = p->W; w.H = p->H; w.Sx = p->Sx; w.Sy = p->Sy; w.RS = p->RS; w.PS = p->PS;
         w.ndirs = g.ndirs; w.subpixel = p->subpixel;
         w.minC2 = p->runner_up ? p->dMinC2 : nullptr;
-        launch_pyd_wta(p->stream, w, p->batch);
+        if (exact) launch_pyd_wta_exact(p->stream, w, p->dC, p->batch);
+        else launch_pyd_wta(p->stream, w, p->batch);
     }
     FSGM_HIP(hipGetLastError());
     return FSGM_OK;

@@ -26,7 +26,8 @@ struct Sgm2dCall {
     uint32_t *bestD, *minC;
     double *mvSub, *flow;
     uint32_t* S;
-    uint32_t* minC2;                     // the _ru forms' runner-up cost (never NULL there), NULL in the plain forms
+    uint32_t* minC2;                     // the _ru forms' runner-up cost (never NULL there), NULL in the plain forms; _exact: as given
+    bool exact;                          // the _exact forms: exact path arithmetic (fsgm_pyd_plan_set_exact)
 };
 
 bool layout_ok(int layout) {
@@ -36,10 +37,12 @@ bool layout_ok(int layout) {
 // the checks both forms share, none of which needs a device
 fsgm_status sgm2d_args(const char* who, int32_t n, const uint8_t* C, int32_t W, int32_t H, int32_t rX, int32_t rY, int32_t P1, int32_t P2,
                        const fsgm_sgm2d_params* prm, const double* preMv, int32_t mvW, int32_t mvH, const uint8_t* guide, uint32_t* bestD,
-                       uint32_t* minC, double* mvSub, double* flow, uint32_t* S, uint32_t* minC2, bool ru, Sgm2dCall* c) {
+                       uint32_t* minC, double* mvSub, double* flow, uint32_t* S, uint32_t* minC2, bool ru, bool exact, Sgm2dCall* c) {
     FSGM_REQUIRE(n >= 1, "%s: n_frames must be >= 1 (got %d)", who, n);
     FSGM_REQUIRE(W >= 1 && H >= 1, "%s: width/height must be >= 1 (got %d x %d)", who, W, H);
     FSGM_REQUIRE(rX >= 0 && rY >= 0, "%s: halfX/halfY must be >= 0 (got %d, %d)", who, rX, rY);
+    FSGM_REQUIRE(!exact || (P1 >= 0 && P1 <= 255), "%s: exact path arithmetic needs P1 in 0..255 (got %d)", who, P1);
+    FSGM_REQUIRE(!exact || (P2 >= 0 && P2 <= 255), "%s: exact path arithmetic needs P2 in 0..255 (got %d)", who, P2);
     fsgm_status st = pyd_check_sides(rX, rY, 0);
     if (st == FSGM_OK) st = pyd_check_count(rX, rY);
     if (st != FSGM_OK) return st;
@@ -61,12 +64,13 @@ fsgm_status sgm2d_args(const char* who, int32_t n, const uint8_t* C, int32_t W, 
                  "reference indexes it with image coordinates (calc_pyd_cost_sgm.cpp:388-389)", who, mvW, mvH, W, H);
     FSGM_REQUIRE(!sp.adaptive_p2 || guide, "%s: adaptive_p2 needs the guide image (guide is NULL)", who);
     *c = Sgm2dCall{n, W, H, rX, rY, P1, P2, preMv ? mvW : W, preMv ? mvH : H, sp, C, preMv, sp.adaptive_p2 ? guide : nullptr,
-                   bestD, minC, mvSub, flow, S, ru ? minC2 : nullptr};
+                   bestD, minC, mvSub, flow, S, ru ? minC2 : nullptr, exact};
     return FSGM_OK;
 }
 
 // Aggregation-only plans (pyd_plan.h), keyed by shape, window, hint-map size, batch, device, whether a guide is held and the
-// runner-up switch (a call that asks for minC2 never takes the plan of one that does not).
+// runner-up switch (a call that asks for minC2 never takes the plan of one that does not) and the exact switch (an exact call and a
+// plain one never share a plan: its path volumes hold y = L - C, theirs L).
 // The host and the device form share them: a call holds its device's lock for its length and queues on the plan's stream.
 PlanCache<fsgm_pyd_plan> g_sgm2d(6, fsgm_pyd_plan_destroy);
 thread_local const char* g_sgm2d_kernel = "";
@@ -76,12 +80,13 @@ fsgm_status sgm2d_plan(fsgm_pyd_plan** out, const Sgm2dCall& c, int cmax) {
     const int dev = c.prm.device, flags = PYD_PLAN_AGG_ONLY | (c.guide ? PYD_PLAN_GUIDE : 0), ru = c.minC2 != nullptr;
     fsgm_pyd_plan* p = g_sgm2d.find(dev, [&](const fsgm_pyd_plan* q) {
         return q->W == c.W && q->H == c.H && q->mvW == c.mvW && q->mvH == c.mvH && q->rX == c.rX && q->rY == c.rY && q->batch == c.n &&
-               q->flags == flags && q->runner_up == ru;
+               q->flags == flags && q->runner_up == ru && q->exact == (int)c.exact;
     });
     fsgm_status st;
     if (!p) {
         if ((st = pyd_plan_create_flags(&p, c.W, c.H, c.mvW, c.mvH, c.rX, c.rY, 0, c.n, dev, flags)) != FSGM_OK) return st;
         if (ru && (st = fsgm_pyd_plan_set_runner_up(p, 1)) != FSGM_OK) { fsgm_pyd_plan_destroy(p); return st; }
+        if (c.exact && (st = fsgm_pyd_plan_set_exact(p, 1)) != FSGM_OK) { fsgm_pyd_plan_destroy(p); return st; }
         g_sgm2d.insert(dev, p);
     } else if ((st = use_device(dev)) != FSGM_OK) {
         return st;
@@ -123,12 +128,12 @@ fsgm_status sgm2d_enqueue(fsgm_pyd_plan* p, uint32_t* dS, double* dFlow) {
     return FSGM_OK;
 }
 
-// both host forms; minC2 non-NULL: the _ru form
+// the host forms; ru: minC2 is wanted (the _ru form, where it is required, or an _exact call that passed one)
 fsgm_status sgm2d_host(const char* who, int32_t n, const uint8_t* C, int32_t W, int32_t H, int32_t rX, int32_t rY, int32_t P1, int32_t P2,
                        const fsgm_sgm2d_params* prm, const double* preMv, int32_t mvW, int32_t mvH, const uint8_t* guide, uint32_t* bestD,
-                       uint32_t* minC, uint32_t* minC2, bool ru, double* mvSub, double* flow, uint32_t* S) {
+                       uint32_t* minC, uint32_t* minC2, bool ru, bool exact, double* mvSub, double* flow, uint32_t* S) {
     Sgm2dCall c;
-    fsgm_status st = sgm2d_args(who, n, C, W, H, rX, rY, P1, P2, prm, preMv, mvW, mvH, guide, bestD, minC, mvSub, flow, S, minC2, ru, &c);
+    fsgm_status st = sgm2d_args(who, n, C, W, H, rX, rY, P1, P2, prm, preMv, mvW, mvH, guide, bestD, minC, mvSub, flow, S, minC2, ru, exact, &c);
     if (st != FSGM_OK) return st;
     // the true maximum of the batch (every layout holds the same bytes), as fsgm_pyd_plan_upload_cost takes it
     const size_t NP = (size_t)W * H, ND = NP * (2 * rX + 1) * (2 * rY + 1);
@@ -170,12 +175,12 @@ fsgm_status sgm2d_host(const char* who, int32_t n, const uint8_t* C, int32_t W, 
     return FSGM_OK;
 }
 
-// both device forms; minC2 non-NULL: the _ru form, written where it lies by the WTA itself
+// the device forms; ru as above: minC2 is written where it lies by the WTA itself
 fsgm_status sgm2d_device(const char* who, int32_t n, const uint8_t* C, int32_t W, int32_t H, int32_t rX, int32_t rY, int32_t P1, int32_t P2,
                          const fsgm_sgm2d_params* prm, const double* preMv, int32_t mvW, int32_t mvH, const uint8_t* guide, uint32_t* bestD,
-                         uint32_t* minC, uint32_t* minC2, bool ru, double* mvSub, double* flow, uint32_t* S, void* stream, int32_t* status) {
+                         uint32_t* minC, uint32_t* minC2, bool ru, bool exact, double* mvSub, double* flow, uint32_t* S, void* stream, int32_t* status) {
     Sgm2dCall c;
-    fsgm_status st = sgm2d_args(who, n, C, W, H, rX, rY, P1, P2, prm, preMv, mvW, mvH, guide, bestD, minC, mvSub, flow, S, minC2, ru, &c);
+    fsgm_status st = sgm2d_args(who, n, C, W, H, rX, rY, P1, P2, prm, preMv, mvW, mvH, guide, bestD, minC, mvSub, flow, S, minC2, ru, exact, &c);
     if (st != FSGM_OK) return st;
     const size_t np = (size_t)n * W * H, nv = np * (2 * rX + 1) * (2 * rY + 1), nmv = (size_t)n * c.mvW * c.mvH;
     const hipStream_t cs = (hipStream_t)stream;
@@ -235,21 +240,21 @@ const char* fsgm_sgm2d_last_kernel(void) { return g_sgm2d_kernel; }
 fsgm_status fsgm_sgm2d_batch_host(int32_t n, const uint8_t* C, int32_t W, int32_t H, int32_t rX, int32_t rY, int32_t P1, int32_t P2,
                                   const fsgm_sgm2d_params* prm, const double* preMv, int32_t mvW, int32_t mvH, const uint8_t* guide,
                                   uint32_t* bestD, uint32_t* minC, double* mvSub, double* flow, uint32_t* S) {
-    return sgm2d_host("fsgm_sgm2d_batch_host", n, C, W, H, rX, rY, P1, P2, prm, preMv, mvW, mvH, guide, bestD, minC, nullptr, false, mvSub,
+    return sgm2d_host("fsgm_sgm2d_batch_host", n, C, W, H, rX, rY, P1, P2, prm, preMv, mvW, mvH, guide, bestD, minC, nullptr, false, false, mvSub,
                       flow, S);
 }
 
 fsgm_status fsgm_sgm2d_batch_host_ru(int32_t n, const uint8_t* C, int32_t W, int32_t H, int32_t rX, int32_t rY, int32_t P1, int32_t P2,
                                      const fsgm_sgm2d_params* prm, const double* preMv, int32_t mvW, int32_t mvH, const uint8_t* guide,
                                      uint32_t* bestD, uint32_t* minC, uint32_t* minC2, double* mvSub, double* flow, uint32_t* S) {
-    return sgm2d_host("fsgm_sgm2d_batch_host_ru", n, C, W, H, rX, rY, P1, P2, prm, preMv, mvW, mvH, guide, bestD, minC, minC2, true, mvSub,
+    return sgm2d_host("fsgm_sgm2d_batch_host_ru", n, C, W, H, rX, rY, P1, P2, prm, preMv, mvW, mvH, guide, bestD, minC, minC2, true, false, mvSub,
                       flow, S);
 }
 
 fsgm_status fsgm_sgm2d_device(int32_t n, const uint8_t* C, int32_t W, int32_t H, int32_t rX, int32_t rY, int32_t P1, int32_t P2,
                               const fsgm_sgm2d_params* prm, const double* preMv, int32_t mvW, int32_t mvH, const uint8_t* guide,
                               uint32_t* bestD, uint32_t* minC, double* mvSub, double* flow, uint32_t* S, void* stream, int32_t* status) {
-    return sgm2d_device("fsgm_sgm2d_device", n, C, W, H, rX, rY, P1, P2, prm, preMv, mvW, mvH, guide, bestD, minC, nullptr, false, mvSub,
+    return sgm2d_device("fsgm_sgm2d_device", n, C, W, H, rX, rY, P1, P2, prm, preMv, mvW, mvH, guide, bestD, minC, nullptr, false, false, mvSub,
                         flow, S, stream, status);
 }
 
@@ -257,8 +262,24 @@ fsgm_status fsgm_sgm2d_device_ru(int32_t n, const uint8_t* C, int32_t W, int32_t
                                  const fsgm_sgm2d_params* prm, const double* preMv, int32_t mvW, int32_t mvH, const uint8_t* guide,
                                  uint32_t* bestD, uint32_t* minC, uint32_t* minC2, double* mvSub, double* flow, uint32_t* S, void* stream,
                                  int32_t* status) {
-    return sgm2d_device("fsgm_sgm2d_device_ru", n, C, W, H, rX, rY, P1, P2, prm, preMv, mvW, mvH, guide, bestD, minC, minC2, true, mvSub,
+    return sgm2d_device("fsgm_sgm2d_device_ru", n, C, W, H, rX, rY, P1, P2, prm, preMv, mvW, mvH, guide, bestD, minC, minC2, true, false, mvSub,
                         flow, S, stream, status);
+}
+
+// exact path arithmetic: minC2 may be NULL (not wanted); one pair of entries with and without the runner-up cost
+fsgm_status fsgm_sgm2d_batch_host_exact(int32_t n, const uint8_t* C, int32_t W, int32_t H, int32_t rX, int32_t rY, int32_t P1, int32_t P2,
+                                        const fsgm_sgm2d_params* prm, const double* preMv, int32_t mvW, int32_t mvH, const uint8_t* guide,
+                                        uint32_t* bestD, uint32_t* minC, uint32_t* minC2, double* mvSub, double* flow, uint32_t* S) {
+    return sgm2d_host("fsgm_sgm2d_batch_host_exact", n, C, W, H, rX, rY, P1, P2, prm, preMv, mvW, mvH, guide, bestD, minC, minC2,
+                      minC2 != nullptr, true, mvSub, flow, S);
+}
+
+fsgm_status fsgm_sgm2d_device_exact(int32_t n, const uint8_t* C, int32_t W, int32_t H, int32_t rX, int32_t rY, int32_t P1, int32_t P2,
+                                    const fsgm_sgm2d_params* prm, const double* preMv, int32_t mvW, int32_t mvH, const uint8_t* guide,
+                                    uint32_t* bestD, uint32_t* minC, uint32_t* minC2, double* mvSub, double* flow, uint32_t* S,
+                                    void* stream, int32_t* status) {
+    return sgm2d_device("fsgm_sgm2d_device_exact", n, C, W, H, rX, rY, P1, P2, prm, preMv, mvW, mvH, guide, bestD, minC, minC2,
+                        minC2 != nullptr, true, mvSub, flow, S, stream, status);
 }
 
 fsgm_status fsgm_pyd_plan_ingest_cost_device(fsgm_pyd_plan* p, int32_t n, const uint8_t* C, int32_t layout, int32_t cost_bound,

@@ -93,4 +93,14 @@ void launch_pyd_rows_desc(hipStream_t st, const PydAggArgs& a, int frames);
 void launch_pyd_rows_aggregate(hipStream_t st, const PydAggArgs& a, int frames);
 void launch_pyd_rows_wta(hipStream_t st, const PydWtaArgs& a, int frames);
 
+// ---- exact path arithmetic (pyd_exact.hip): 0 <= P1, P2 <= 255, either layout, any window ----
+// The aggregation writes y = L - C (one byte, in [0, P2]) where the plain kernels write L; the WTA reads C as one more volume
+// and rebuilds S.  Path slots as plan_pyd_dirs lays them out with lines_per_block = 4 and no wide rows.
+struct PydWtaExactArgs {
+    PydWtaArgs w;           // w.L: the y volumes
+    const uint8_t* C;       // [frames][NP][PS]
+};
+void launch_pyd_agg_exact(hipStream_t st, const PydAggArgs& a, int frames);
+void launch_pyd_wta_exact(hipStream_t st, const PydWtaArgs& w, const uint8_t* C, int frames);
+
 }  // namespace fsgm

@@ -30,9 +30,12 @@ struct fsgm_pyd_plan {
     // first use and all ones (FSGM_NO_RUNNER_UP) until a WTA has run; the cost and aggregation kernels do not depend on it
     int runner_up = 0;
     uint32_t* dMinC2 = nullptr;
+    // exact path arithmetic (fsgm_pyd_plan_set_exact): the kernels of pyd_exact.hip, whose path volumes hold y = L - C.  agg_exact
+    // is the switch as the last queued aggregation saw it, i.e. what dL holds: a WTA alone is refused while the two differ
+    int exact = 0, agg_exact = 0;
     bool mv_zero = false;                // dMv holds zeros (aggregation-only plans: the hints of a call without preMv)
     fsgm::DeviceJoin join;               // the events of the plan's device calls
-    const char* agg_name = "";           // the aggregation pyd_enqueue last queued: "rows", "rows/wide", "generic", "generic/wrap"
+    const char* agg_name = "";           // the aggregation pyd_enqueue last queued: "rows", "rows/wide", "generic", "generic/wrap", "generic/exact"
 };
 
 namespace fsgm {

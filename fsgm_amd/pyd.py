@@ -46,6 +46,8 @@ def _bind(lib):
         lib.fsgm_pyd_plan_set_runner_up.argtypes = [vp, i32]
         lib.fsgm_pyd_plan_download_runner_up.argtypes = [vp, i32, vp]
         lib.fsgm_calc_pyd_cost_sgm_batch_host_ru.argtypes = [i32, C.POINTER(PydIn), C.POINTER(PydOut), C.POINTER(vp), i32]
+    if hasattr(lib, "fsgm_pyd_plan_set_exact"):                  # (nor this)
+        lib.fsgm_pyd_plan_set_exact.argtypes = [vp, i32]
     lib._pyd_bound = True
 
 
@@ -198,6 +200,12 @@ class PydPlan:
     def set_runner_up(self, on):
         """The WTA also writes the runner-up cost (download_runner_up) on / off; no other kernel or output changes."""
         check(self.lib.fsgm_pyd_plan_set_runner_up(self._h, int(on)))
+
+    def set_exact(self, on):
+        """Exact path arithmetic on / off (fsgm_pyd_plan_set_exact): aggregation and WTA become the "generic/exact" kernels, whose
+        path costs are never narrowed to a byte; P1, P2 must lie in 0..255.  A WTA alone (run(STAGE_WTA), download_sum) right after
+        a toggle, before an aggregation, raises FsgmError: the path volumes still hold the other kind."""
+        check(self.lib.fsgm_pyd_plan_set_exact(self._h, int(on)))
 
     def download_runner_up(self, frame):
         """minC2 uint32 (H, W) of the last WTA with the switch on (all NO_RUNNER_UP before one); FsgmError while it is off."""

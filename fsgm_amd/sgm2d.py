@@ -25,10 +25,23 @@ def _bind(lib):
     if hasattr(lib, "fsgm_sgm2d_batch_host_ru"):                 # (an older build behind FSGM_LIB_PATH has none): minC2 after minC
         lib.fsgm_sgm2d_batch_host_ru.argtypes = head[:15] + [vp] + head[15:]
         lib.fsgm_sgm2d_device_ru.argtypes = head[:15] + [vp] + head[15:] + [vp, vp]
+    if hasattr(lib, "fsgm_sgm2d_batch_host_exact"):              # (nor these): the _ru forms' argument lists, minC2 may be NULL
+        lib.fsgm_sgm2d_batch_host_exact.argtypes = head[:15] + [vp] + head[15:]
+        lib.fsgm_sgm2d_device_exact.argtypes = head[:15] + [vp] + head[15:] + [vp, vp]
     lib.fsgm_sgm2d_last_kernel.restype = C.c_char_p
     lib.fsgm_sgm2d_ingest_lds.argtypes = [i32, i32, i32, C.POINTER(C.c_uint64)]
     lib.fsgm_pyd_plan_ingest_cost_device.argtypes = [vp, i32, vp, i32, i32, vp, vp]
     return lib
+
+
+ARITHS = ("wrap", "exact")
+
+
+def arith_exact(arith):
+    """True for arith="exact", False for "wrap" (the MEX's unsigned char path costs)."""
+    if arith not in ARITHS:
+        raise ValueError(f"arith must be 'wrap' or 'exact' (got {arith!r})")
+    return arith == "exact"
 
 
 def layout_code(layout):
@@ -62,8 +75,8 @@ def shape_of(shape, layout, half_x, half_y):
 
 
 def last_kernel():
-    """The aggregation that this thread's last sgm2d_batch / torch_ops.sgm2d call ran: "rows", "rows/wide", "generic" or
-    "generic/wrap"."""
+    """The aggregation that this thread's last sgm2d_batch / torch_ops.sgm2d call ran: "rows", "rows/wide", "generic",
+    "generic/wrap" or, with arith="exact", "generic/exact"."""
     return _bind(_lib.load()).fsgm_sgm2d_last_kernel().decode()
 
 
@@ -75,7 +88,7 @@ def ingest_lds(layout, half_x, half_y):
 
 
 def sgm2d_batch(costs, half_x, half_y, P1=6, P2=32, *, layout="dhw", hints=None, guide=None, cost_bound=255, diagonal=1, total_pass=2,
-                adaptive_p2=0, subpixel=1, return_flow=False, return_sum=False, device=0, runner_up=False):
+                adaptive_p2=0, subpixel=1, return_flow=False, return_sum=False, device=0, runner_up=False, arith="wrap"):
     """(bestD, minC[, minC2], mvSub[, flow][, S]) of the 2-D matcher on cost volumes the caller made: costs uint8 (N, D, H, W) for layout
     "dhw" (channel sx*Sy + sy, the reference's candidate order) or "dhw_yx" (channel sy*Sx + sx, the y-slow order correlation
     layers emit), (N, H, W, D) for "hwd" (candidate index sx*Sy + sy); one volume without the leading N.  The window is
@@ -86,8 +99,13 @@ def sgm2d_batch(costs, half_x, half_y, P1=6, P2=32, *, layout="dhw", hints=None,
     cost_bound + P2 + max(P1, P2) <= 255 the non-wrapping kernels run; a volume above a bound below 255 is refused (status 1).
     runner_up=True (fsgm_sgm2d_batch_host_ru) returns minC2 uint32 (N, H, W) after minC: the smallest sum at a Chebyshev distance
     >= 2 from the winner, NO_RUNNER_UP where the window holds no such candidate -- what uniqueness_filter(flow, minC, minC2, ratio,
-    planes=2) takes; every other output is that of the call without it."""
+    planes=2) takes; every other output is that of the call without it.
+    arith="exact" (fsgm_sgm2d_batch_host_exact): path costs as integers that are never narrowed -- the SGM recurrence itself where
+    the default "wrap" reproduces the MEX's unsigned char overflow, i.e. whenever max(costs) + P2 + max(P1, P2) > 255 (inside that
+    budget the two agree bit for bit).  P1 and P2 must lie in 0..255 (status 1); such a call runs "generic/exact" at every window
+    and bound, and runner_up=True combines with it."""
     lib = _bind(_lib.load())
+    exact = arith_exact(arith)
     layout_code(layout)
     costs = np.ascontiguousarray(costs)
     if costs.dtype != np.uint8:
@@ -114,7 +132,10 @@ def sgm2d_batch(costs, half_x, half_y, P1=6, P2=32, *, layout="dhw", hints=None,
     flow = np.empty((N, 2, H, W), np.float64) if return_flow else None
     S = np.empty((N, H, W, D), np.uint32) if return_sum else None
     minC2 = np.empty((N, H, W), np.uint32) if runner_up else None
-    if runner_up:
+    if exact:
+        check(lib.fsgm_sgm2d_batch_host_exact(N, ptr(costs), W, H, int(half_x), int(half_y), int(P1), int(P2), C.byref(prm), ptr(hints),
+                                              mvW, mvH, ptr(guide), ptr(bestD), ptr(minC), ptr(minC2), ptr(mvSub), ptr(flow), ptr(S)))
+    elif runner_up:
         check(lib.fsgm_sgm2d_batch_host_ru(N, ptr(costs), W, H, int(half_x), int(half_y), int(P1), int(P2), C.byref(prm), ptr(hints), mvW,
                                            mvH, ptr(guide), ptr(bestD), ptr(minC), ptr(minC2), ptr(mvSub), ptr(flow), ptr(S)))
     else:

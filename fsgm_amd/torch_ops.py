@@ -17,7 +17,8 @@ fsgm::stereo_sgm_ru (fsgm::stereo_sgm_range with the runner-up cost minC2 after 
 fsgm::sgm_ru and fsgm::sgm2d_ru (fsgm::sgm / fsgm::sgm2d with minC2 after minC) and fsgm::uniqueness_filter_planes (a map or a
 two-plane flow; status always 0); fsgm::pyramidal_sgm_ru and fsgm::pyramidal_sgm_ng_ru (the pyramids with level 1's minC2 after
 minC) and fsgm::pyramidal_flow_pp_u (fsgm::pyramidal_flow_pp with a uniqueness ratio ahead of the chain and minC2 after minC);
-fsgm::sgm_exact (fsgm::sgm with exact path arithmetic, fsgm_sgm_device_exact: the same arguments and outputs).
+fsgm::sgm_exact (fsgm::sgm with exact path arithmetic, fsgm_sgm_device_exact: the same arguments and outputs),
+fsgm::sgm2d_exact (fsgm::sgm2d_ru with exact path arithmetic, fsgm_sgm2d_device_exact: a runner_up flag added, minC2 empty without it).
 
 One process must hold one HIP runtime.  torch brings its own libamdhip64; libfsgm_hip.so binds to it by soname when torch is
 imported first.  When the library was loaded first, torch afterwards maps a second runtime, and a stream or pointer of one
@@ -36,7 +37,7 @@ from .epi import EpiGeometry, _d_min, _params as _epi_params, _stereo_params
 from .post import _bind as _bind_post
 from .stereo_pp import CHAIN_FIELDS as STEREO_PP_FIELDS, _bind as _bind_stereo_pp, pp_params as _stereo_pp_params
 from .sgm import _bind as _bind_sgm, arith_exact as _arith_exact, layout_code as _layout_code, params as _sgm_params, shape_of as _sgm_shape
-from .sgm2d import _bind as _bind_sgm2d, layout_code as _layout2d_code, params as _sgm2d_params, shape_of as _sgm2d_shape, LAYOUTS as _LAYOUTS2D
+from .sgm2d import _bind as _bind_sgm2d, arith_exact as _arith2d_exact, layout_code as _layout2d_code, params as _sgm2d_params, shape_of as _sgm2d_shape, LAYOUTS as _LAYOUTS2D
 from .pyramid import (PyramidParams, NgPyramidParams, FLOW_PP_FIELDS, MATCHERS, _bind as _bind_pyramid, _bind_flow_pp, _bind_ng,
                       uniqueness_ratio_of as _uniqueness_ratio_of)
 
@@ -400,6 +401,37 @@ def _sgm2d_ru_op(C_: torch.Tensor, hints: torch.Tensor, guide: torch.Tensor, hal
 def _(C_, hints, guide, half_x, half_y, P1, P2, layout, cost_bound, diagonal, total_pass, adaptive_p2, subpixel, return_flow, return_sum):
     bestD, minC, mvSub, flow, S, status = _sgm2d_outputs(C_, layout, half_x, half_y, return_flow, return_sum)
     return bestD, minC, torch.empty_like(minC), mvSub, flow, S, status
+
+
+@torch.library.custom_op("fsgm::sgm2d_exact", mutates_args=())
+def _sgm2d_exact_op(C_: torch.Tensor, hints: torch.Tensor, guide: torch.Tensor, half_x: int, half_y: int, P1: int, P2: int, layout: int,
+                    cost_bound: int, diagonal: int, total_pass: int, adaptive_p2: int, subpixel: int, return_flow: int, return_sum: int,
+                    runner_up: bool
+                    ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """fsgm::sgm2d_ru with exact path arithmetic (fsgm_sgm2d_device_exact): P1, P2 in 0..255; minC2 is empty unless runner_up"""
+    N, H, W, D = _sgm2d_out_shape(C_, layout, half_x, half_y)
+    dev = C_.device
+    if not C_.is_contiguous():
+        raise TypeError("fsgm::sgm2d_exact reads the costs where they lie: pass a contiguous tensor")
+    have_hints = hints.numel() != 0
+    hints = _ready(hints) if have_hints else None
+    mvH, mvW = (hints.shape[-2], hints.shape[-1]) if have_hints else (0, 0)
+    guide = guide.contiguous() if adaptive_p2 else None
+    bestD, minC, mvSub, flow, S, status = _sgm2d_outputs(C_, layout, half_x, half_y, return_flow, return_sum)
+    minC2 = torch.empty_like(minC) if runner_up else _u32((0,), dev)
+    prm = _sgm2d_params(_L, diagonal=diagonal, total_pass=total_pass, adaptive_p2=adaptive_p2, subpixel=subpixel, device=dev.index,
+                        layout=[k for k, v in _LAYOUTS2D.items() if v == layout][0], cost_bound=cost_bound)
+    _call(dev, _L.fsgm_sgm2d_device_exact, N, _p(C_), W, H, int(half_x), int(half_y), int(P1), int(P2), C.byref(prm), _p(hints), int(mvW),
+          int(mvH), _p(guide), _p(bestD), _p(minC), _p(minC2) if runner_up else None, _p(mvSub), _p(flow) if return_flow else None,
+          _p(S) if return_sum else None, _stream(dev), _p(status))
+    return bestD, minC, minC2, mvSub, flow, S, status
+
+
+@_sgm2d_exact_op.register_fake
+def _(C_, hints, guide, half_x, half_y, P1, P2, layout, cost_bound, diagonal, total_pass, adaptive_p2, subpixel, return_flow, return_sum,
+      runner_up):
+    bestD, minC, mvSub, flow, S, status = _sgm2d_outputs(C_, layout, half_x, half_y, return_flow, return_sum)
+    return bestD, minC, torch.empty_like(minC) if runner_up else _u32((0,), C_.device), mvSub, flow, S, status
 
 
 def _epipolar_sgm_of_outputs(I0):
@@ -904,7 +936,8 @@ def sgm(Cvol, P1=7, P2=100, *, layout="dhw", paths=4, cost_bound=255, agg_mode=0
 
 
 def sgm2d(costs, half_x, half_y, P1=6, P2=32, *, layout="dhw", hints=None, guide=None, cost_bound=255, diagonal=1, total_pass=2,
-          adaptive_p2=0, subpixel=1, return_flow=False, return_sum=False, check=False, return_status=False, runner_up=False):
+          adaptive_p2=0, subpixel=1, return_flow=False, return_sum=False, check=False, return_status=False, runner_up=False,
+          arith="wrap"):
     """(bestD, minC[, minC2], mvSub[, flow][, S]) as fsgm_amd.sgm2d_batch, on cost volumes that are already in HBM: costs uint8 (D, H, W) or
     a batch (N, D, H, W) for layout "dhw" (channel sx*Sy + sy) and "dhw_yx" (channel sy*Sx + sx, a correlation layer's order),
     (H, W, D) / (N, H, W, D) for "hwd".  The tensor is read where it lies -- it must be contiguous, at any byte address -- every
@@ -913,7 +946,10 @@ def sgm2d(costs, half_x, half_y, P1=6, P2=32, *, layout="dhw", hints=None, guide
     cost_bound: the caller's declaration that no cost is larger; the aggregation is selected for it and every cost is saturated at
     it on the way in.  The status tensor (return_status=True) is FSGM_ERR_INVALID when a cost was above the bound (the outputs are
     then those of the saturated volume); check=True synchronises and raises on it.  runner_up=True (fsgm::sgm2d_ru) returns minC2
-    uint32 (.., H, W) after minC, as fsgm_amd.sgm2d_batch does."""
+    uint32 (.., H, W) after minC, as fsgm_amd.sgm2d_batch does.  arith="exact" (fsgm::sgm2d_exact): path costs that are never
+    narrowed to a byte, as fsgm_amd.sgm2d_batch(arith="exact") -- P1, P2 in 0..255, "generic/exact" at every window and bound, with or
+    without runner_up."""
+    exact = _arith2d_exact(arith)
     code = _layout2d_code(layout)
     named = {"costs": (costs, torch.uint8)}
     if hints is not None:
@@ -946,7 +982,9 @@ def sgm2d(costs, half_x, half_y, P1=6, P2=32, *, layout="dhw", hints=None, guide
         guide = torch.empty((0,), dtype=torch.uint8, device=dev)
     args = (costs, hints, guide, int(half_x), int(half_y), int(P1), int(P2), code, int(cost_bound), int(diagonal), int(total_pass),
             int(adaptive_p2), int(subpixel), int(bool(return_flow)), int(bool(return_sum)))
-    if runner_up:
+    if exact:
+        bestD, minC, minC2, mvSub, flow, S, status = torch.ops.fsgm.sgm2d_exact(*args, bool(runner_up))
+    elif runner_up:
         bestD, minC, minC2, mvSub, flow, S, status = torch.ops.fsgm.sgm2d_ru(*args)
     else:
         bestD, minC, mvSub, flow, S, status = torch.ops.fsgm.sgm2d(*args)

@@ -218,7 +218,8 @@ fsgm_status fsgm_uniqueness_filter_device(int32_t n_frames, const double* map, c
  * a competitor.  With Sy == 1 the rule is the 1-D rule |d - best| >= 2 above.  bestD, minC, mvSub, flow and S of a call that
  * asks for minC2 are bit-identical to those of the same call without it; the cost and aggregation kernels are the same.
  * Entry points: fsgm_pyd_plan_set_runner_up / _download_runner_up, fsgm_calc_pyd_cost_sgm_batch_host_ru,
- * fsgm_sgm2d_batch_host_ru / fsgm_sgm2d_device_ru; on 1-D volumes fsgm_sgm_batch_host_ru / fsgm_sgm_device_ru (the 1-D rule).
+ * fsgm_sgm2d_batch_host_ru / fsgm_sgm2d_device_ru, fsgm_sgm2d_batch_host_exact / fsgm_sgm2d_device_exact (minC2 non-NULL; S then
+ * the exact sums); on 1-D volumes fsgm_sgm_batch_host_ru / fsgm_sgm_device_ru (the 1-D rule).
  *
  * The uniqueness test above on `planes` planes per frame: planes = 1 is fsgm_uniqueness_filter_host itself, planes = 2 takes a
  * flow -- map, out f64 [n][2][H][W], minC, minC2 u32 [n][H][W] -- and writes NaN into both planes of a rejected pixel.  planes
@@ -564,6 +565,14 @@ fsgm_status fsgm_pyd_plan_time(fsgm_pyd_plan* plan, int32_t stages, int32_t warm
  * aggregation kernel, nor any other output.  fsgm_pyd_plan_download_runner_up is FSGM_ERR_INVALID while the switch is off. */
 fsgm_status fsgm_pyd_plan_set_runner_up(fsgm_pyd_plan* plan, int32_t on);
 fsgm_status fsgm_pyd_plan_download_runner_up(fsgm_pyd_plan* plan, int32_t frame, uint32_t* minC2);
+/* Exact path arithmetic ("exact" under fsgm_sgm2d_batch_host_exact below) for this plan, 0 at creation: with the switch on
+ * FSGM_STAGE_AGGREGATE and FSGM_STAGE_WTA run the two kernels of that section ("generic/exact") at every window and every cost
+ * bound, on volumes the plan built from an image pair as on uploaded or ingested ones; the cost stage does not depend on it.
+ * P1 and P2 must lie in 0..255: with the switch on fsgm_pyd_plan_set_params refuses anything else, and so does this call for
+ * the penalties the plan holds (FSGM_ERR_INVALID, nothing changed).  The path volumes of an exact aggregation hold y = L - C,
+ * those of a plain one L: a run of FSGM_STAGE_WTA without FSGM_STAGE_AGGREGATE, fsgm_pyd_plan_download_sum included, is
+ * FSGM_ERR_INVALID while the switch differs from what the last aggregation ran with.  The runner-up switch combines with it. */
+fsgm_status fsgm_pyd_plan_set_exact(fsgm_pyd_plan* plan, int32_t on);
 
 /* Search windows and launches.  Every entry point on this path accepts a search window with sides 2*half+1 <= 64 (so 63 at
  * the most) and at most 1024 candidates (31x33 = 1023 is the largest count); anything else is FSGM_ERR_UNSUPPORTED before a
@@ -633,9 +642,25 @@ fsgm_status fsgm_sgm2d_batch_host_ru(int32_t n_frames, const uint8_t* C, int32_t
                                      int32_t P1, int32_t P2, const fsgm_sgm2d_params* prm, const double* preMv, int32_t mvWidth,
                                      int32_t mvHeight, const uint8_t* guide, uint32_t* bestD, uint32_t* minC, uint32_t* minC2,
                                      double* mvSub, double* flow, uint32_t* S);
+/* sgm2d(C) with EXACT path arithmetic: the recurrence of calc_pyd_cost_sgm.cpp:34-89, 114-296 on integers that are never
+ * narrowed to unsigned char, where the calls above reproduce the MEX's mod-256 overflow whenever
+ * max(C) + P2 + max(P1, P2) > 255 (inside that budget the two agree bit for bit):
+ *   path start   L[c] = C[c], stored minimum 0 (the MEX's quirk stays)
+ *   step         L[c] = C[c] + min(Lp[ctr], min over the 5x5 around ctr except ctr of Lp + P1, m_p + P2) - m_p, ctr the
+ *                hint-shifted centre (int)(s + delta + 0.5) of :46-47, cells outside the window absent, m = min_c L[c]
+ * Adaptive P2, the path set, diagonal, totalPass, the mirrored pass, the first-minimum WTA and the parabolas are those of the
+ * plain call.  P1 and P2 must lie in 0..255 (FSGM_ERR_INVALID before a device is touched); then L <= 255 + P2 <= 510 and
+ * S <= 8 * 510 = 4080.  The argument list is fsgm_sgm2d_batch_host_ru's, with minC2 optional: NULL means not wanted.
+ * cost_bound keeps its meaning (a volume above it is refused) but selects no kernel: every exact call runs "generic/exact".
+ * The cached plan has the plan's exact switch on (fsgm_pyd_plan_set_exact) and is never the plan of a plain call, nor is the
+ * plan of a call with minC2 that of one without. */
+fsgm_status fsgm_sgm2d_batch_host_exact(int32_t n_frames, const uint8_t* C, int32_t width, int32_t height, int32_t halfX,
+                                        int32_t halfY, int32_t P1, int32_t P2, const fsgm_sgm2d_params* prm, const double* preMv,
+                                        int32_t mvWidth, int32_t mvHeight, const uint8_t* guide, uint32_t* bestD, uint32_t* minC,
+                                        uint32_t* minC2, double* mvSub, double* flow, uint32_t* S);
 /* the aggregation that the calling thread's last fsgm_sgm2d_batch_host / fsgm_sgm2d_device ran, "" before the first: "rows"
  * (row-packed, windows up to 11x11), "rows/wide" (its one-line-a-wave mapping: up to 2 landscape frames), "generic"
- * (pyd_agg_kernel without wrapping) or "generic/wrap" */
+ * (pyd_agg_kernel without wrapping), "generic/wrap", or "generic/exact" (the _exact forms) */
 const char* fsgm_sgm2d_last_kernel(void);
 /* The static LDS (bytes per workgroup) of the kernel that brings volumes of this layout into a plan, answered without a
  * device: 0 for FSGM_COST2D_LAYOUT_HWD (a copy or a repack in registers), one padded tile for the channel-major layouts
@@ -1229,6 +1254,14 @@ fsgm_status fsgm_sgm2d_device_ru(int32_t n_frames, const uint8_t* C, int32_t wid
                                  int32_t P1, int32_t P2, const fsgm_sgm2d_params* prm, const double* preMv, int32_t mvWidth,
                                  int32_t mvHeight, const uint8_t* guide, uint32_t* bestD, uint32_t* minC, uint32_t* minC2,
                                  double* mvSub, double* flow, uint32_t* S, void* stream, int32_t* status);
+/* fsgm_sgm2d_batch_host_exact on device pointers: exact path arithmetic (see there).  minC2 may be NULL (not wanted); when
+ * given it is device memory, checked like minC and written by the WTA itself.  The ingest saturates at cost_bound and raises
+ * the status word as in fsgm_sgm2d_device; the outputs are then those of the saturated volume under the exact recurrence.
+ * Everything else follows the contract above: a stream that is being captured is refused. */
+fsgm_status fsgm_sgm2d_device_exact(int32_t n_frames, const uint8_t* C, int32_t width, int32_t height, int32_t halfX, int32_t halfY,
+                                    int32_t P1, int32_t P2, const fsgm_sgm2d_params* prm, const double* preMv, int32_t mvWidth,
+                                    int32_t mvHeight, const uint8_t* guide, uint32_t* bestD, uint32_t* minC, uint32_t* minC2,
+                                    double* mvSub, double* flow, uint32_t* S, void* stream, int32_t* status);
 /* The first step of fsgm_sgm2d_device on its own, into a caller's plan: n_frames (= the plan's batch) volumes in a
  * FSGM_COST2D_LAYOUT_* from device memory into the plan's cost volumes (what fsgm_pyd_plan_upload_cost fills from the host),
  * saturated at cost_bound, which becomes the bound the plan selects its aggregation by.  status: 0 or FSGM_ERR_INVALID. */
