@@ -13,7 +13,7 @@ from .epi import (calc_cost_sgm, calc_cost_sgm_batch, EpiPlan, epipolar_maps, ep
 from .pyd import calc_pyd_cost_sgm, calc_pyd_cost_sgm_batch, PydPlan  # noqa: F401
 from .sgm2d import sgm2d_batch  # noqa: F401
 from .pyramid import (pyramidal_sgm, pyramidal_sgm_ng, pyramidal_sgm_batch, pyramidal_sgm_ng_batch, PyramidPlan, NgPyramidPlan,  # noqa: F401
-                      pyramidal_flow_pp)
+                      pyramidal_flow_pp, flow_level_hints)
 from .post import (speckle_filter, calc_disp_from_first, forward_backward_check, scanline_in_fill, vzInd2Disp, vmf,  # noqa: F401
                    epi_postprocess, epi_postprocess_batch, PostPlan, flow_speckle_filter, flow_fb_check, flow_in_fill)
 from .stereo_pp import stereo_sgm_pp, stereo_disp_from_first, stereo_fb_check  # noqa: F401

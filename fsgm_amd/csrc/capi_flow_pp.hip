@@ -198,15 +198,15 @@ static fsgm_status swap_enqueue(const PyramidPair& pr, const uint8_t* I0, const 
     return FSGM_OK;
 }
 
-static fsgm_status with_pair(int n, int W, int H, int channels, const fsgm_flow_pp_params& prm, int ru, const PairBody& body) {
+static fsgm_status with_pair(int n, int W, int H, int channels, const fsgm_flow_pp_params& prm, int ru, int lm, const PairBody& body) {
     if (prm.matcher == FSGM_MATCHER_NG) {
         fsgm_ng_pyramid_params q = prm.ng;
         q.device = prm.device;
-        return ng_pyramid_with_pair(n, W, H, channels, &q, ru, body);
+        return ng_pyramid_with_pair(n, W, H, channels, &q, ru, lm, body);
     }
     fsgm_pyramid_params q = prm.pyd;
     q.device = prm.device;
-    return pyd_pyramid_with_pair(n, W, H, channels, &q, ru, body);
+    return pyd_pyramid_with_pair(n, W, H, channels, &q, ru, lm, body);
 }
 
 // The _u forms' extra arguments (on: the call is one of them).  The plan of 2n pairs runs with the runner-up switch on, and the
@@ -227,12 +227,20 @@ static fsgm_status uniqueness_check(const char* who, const Uniqueness& u) {
     return FSGM_OK;
 }
 
+// The _lm forms: the _u forms' arguments with the level median of the 2n-pair plan (both directions run with it).  minC2 may be
+// NULL exactly when the ratio is 0; the plan then runs without the runner-up switch
+static fsgm_status level_median_args(const char* who, int32_t ratio, const uint32_t* minC2, int32_t lm) {
+    FSGM_REQUIRE(ratio >= 0 && ratio <= 100, "%s: uniqueness_ratio must be in [0, 100] (got %d)", who, ratio);
+    FSGM_REQUIRE(minC2 || ratio == 0, "%s: null argument (minC2 is required with a non-zero uniqueness_ratio)", who);
+    return level_median_check(who, lm);
+}
+
 static void uniqueness_enqueue(hipStream_t st, const PyramidPair& pr, const Uniqueness& u, size_t np, size_t frame_px) {
     if (u.on && u.ratio > 0) launch_flow_uniqueness(st, pr.flow, pr.minC, pr.minC2, const_cast<double*>(pr.flow), 2 * np, frame_px, u.ratio);
 }
 
 static fsgm_status flow_pp_host(const char* who, int32_t n, const uint8_t* I0, const uint8_t* I1, int32_t W, int32_t H, int32_t channels,
-                                const fsgm_flow_pp_params* prm, const Uniqueness& u, const FlowOutputs& o) {
+                                const fsgm_flow_pp_params* prm, const Uniqueness& u, const FlowOutputs& o, int lm = 0) {
     fsgm_status st = params_check(who, prm);
     if (st != FSGM_OK || (st = uniqueness_check(who, u)) != FSGM_OK) return st;
     if ((st = flow_args(who, n, W, H, I0 && I1 && o.flow_pp, prm->device)) != FSGM_OK) return st;
@@ -241,7 +249,7 @@ static fsgm_status flow_pp_host(const char* who, int32_t n, const uint8_t* I0, c
     if ((st = flow_plan_get(lk, &p, W, H, n, prm->device)) != FSGM_OK) return st;
     const size_t np = p->NP * n;
     if ((st = ensure_pp(p, who)) != FSGM_OK) return st;
-    return with_pair(n, W, H, channels, *prm, u.on, [&](const PyramidPair& pr) -> fsgm_status {
+    return with_pair(n, W, H, channels, *prm, u.on, lm, [&](const PyramidPair& pr) -> fsgm_status {
         hipStream_t s = pr.stream;
         const size_t img = np * channels;
         StreamGuard guard(s);   // an early exit drains the stream: queued copies use the caller's memory
@@ -273,7 +281,8 @@ static fsgm_status flow_pp_host(const char* who, int32_t n, const uint8_t* I0, c
 }
 
 static fsgm_status flow_pp_device(const char* who, int32_t n, const uint8_t* I0, const uint8_t* I1, int32_t W, int32_t H, int32_t channels,
-                                  const fsgm_flow_pp_params* prm, const Uniqueness& u, const FlowOutputs& o, void* stream, int32_t* status) {
+                                  const fsgm_flow_pp_params* prm, const Uniqueness& u, const FlowOutputs& o, void* stream, int32_t* status,
+                                  int lm = 0) {
     fsgm_status st = params_check(who, prm);
     if (st != FSGM_OK || (st = uniqueness_check(who, u)) != FSGM_OK) return st;
     if ((st = flow_args(who, n, W, H, I0 && I1 && o.flow_pp, prm->device)) != FSGM_OK) return st;
@@ -293,7 +302,7 @@ static fsgm_status flow_pp_device(const char* who, int32_t n, const uint8_t* I0,
     std::unique_lock<std::mutex> lk;
     fsgm_flow_pp_plan* p;
     if ((st = flow_plan_get(lk, &p, W, H, n, prm->device)) != FSGM_OK) return st;
-    return with_pair(n, W, H, channels, *prm, u.on, [&](const PyramidPair& pr) -> fsgm_status {
+    return with_pair(n, W, H, channels, *prm, u.on, lm, [&](const PyramidPair& pr) -> fsgm_status {
         hipStream_t s = pr.stream;
         return device_call(*pr.join, cs, s, [&]() -> fsgm_status {
             FSGM_HIP(hipMemcpyAsync(pr.in0, I0, img, hipMemcpyDeviceToDevice, s));
@@ -388,6 +397,27 @@ fsgm_status fsgm_pyramidal_flow_pp_device_u(int32_t n, const uint8_t* I0, const 
                           FlowOutputs{flow_pp, flow_checked, flow_fwd, flow_bwd, minC}, stream, status);
 }
 
+fsgm_status fsgm_pyramidal_flow_pp_host_lm(int32_t n, const uint8_t* I0, const uint8_t* I1, int32_t W, int32_t H, int32_t channels,
+                                           const fsgm_flow_pp_params* prm, int32_t uniqueness_ratio, int32_t level_median, double* flow_pp,
+                                           double* flow_checked, double* flow_fwd, double* flow_bwd, uint32_t* minC, uint32_t* minC2) {
+    const char* who = "fsgm_pyramidal_flow_pp_host_lm";
+    const fsgm_status st = level_median_args(who, uniqueness_ratio, minC2, level_median);
+    if (st != FSGM_OK) return st;
+    return flow_pp_host(who, n, I0, I1, W, H, channels, prm, Uniqueness{minC2 != nullptr, uniqueness_ratio, minC2},
+                        FlowOutputs{flow_pp, flow_checked, flow_fwd, flow_bwd, minC}, level_median);
+}
+
+fsgm_status fsgm_pyramidal_flow_pp_device_lm(int32_t n, const uint8_t* I0, const uint8_t* I1, int32_t W, int32_t H, int32_t channels,
+                                             const fsgm_flow_pp_params* prm, int32_t uniqueness_ratio, int32_t level_median, double* flow_pp,
+                                             double* flow_checked, double* flow_fwd, double* flow_bwd, uint32_t* minC, uint32_t* minC2,
+                                             void* stream, int32_t* status) {
+    const char* who = "fsgm_pyramidal_flow_pp_device_lm";
+    const fsgm_status st = level_median_args(who, uniqueness_ratio, minC2, level_median);
+    if (st != FSGM_OK) return st;
+    return flow_pp_device(who, n, I0, I1, W, H, channels, prm, Uniqueness{minC2 != nullptr, uniqueness_ratio, minC2},
+                          FlowOutputs{flow_pp, flow_checked, flow_fwd, flow_bwd, minC}, stream, status, level_median);
+}
+
 fsgm_status fsgm_pyramidal_flow_pp_time(int32_t n, const uint8_t* I0, const uint8_t* I1, int32_t W, int32_t H, int32_t channels,
                                         const fsgm_flow_pp_params* prm, int32_t warmup, int32_t iters, float* ms) {
     const char* who = "fsgm_pyramidal_flow_pp_time";
@@ -399,7 +429,7 @@ fsgm_status fsgm_pyramidal_flow_pp_time(int32_t n, const uint8_t* I0, const uint
     if ((st = flow_plan_get(lk, &p, W, H, n, prm->device)) != FSGM_OK) return st;
     const size_t np = p->NP * n;
     if ((st = ensure_pp(p, who)) != FSGM_OK) return st;
-    return with_pair(n, W, H, channels, *prm, 0, [&](const PyramidPair& pr) -> fsgm_status {
+    return with_pair(n, W, H, channels, *prm, 0, 0, [&](const PyramidPair& pr) -> fsgm_status {
         hipStream_t s = pr.stream;
         const size_t img = np * channels;
         StreamGuard guard(s);

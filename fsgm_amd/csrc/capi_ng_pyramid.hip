@@ -74,16 +74,19 @@ struct fsgm_ng_pyramid_plan {
                             prm.halfSearchWinSize, prm.aggSize / 2, prm.P1, prm.P2, prm.subPixelRefine,
                             l == 0 && core.runner_up ? dMinC2 : nullptr};
         FSGM_HIP(ng_level_enqueue(core.stream, nb, lv, core.batch));
-        if (l > 0)                                                               // pyramidal_sgm.m:72
-            launch_pyr_upsample2(core.stream, core.dFlow[l], dMv[l - 1], w, h, core.batch, (size_t)2 * core.mvW[l - 1] * core.mvH[l - 1]);
+        const size_t stride = l > 0 ? (size_t)2 * core.mvW[l - 1] * core.mvH[l - 1] : 0;
+        if (l > 0 && core.level_median)                                          // pyramidal_sgm.m:70-72, :70-71 live
+            launch_pyr_median_upsample2(core.stream, core.dFlow[l], dMv[l - 1], w, h, core.batch, stride, core.level_median);
+        else if (l > 0)                                                          // pyramidal_sgm.m:72
+            launch_pyr_upsample2(core.stream, core.dFlow[l], dMv[l - 1], w, h, core.batch, stride);
         return FSGM_OK;
     }
 };
 
 static PyramidCache<fsgm_ng_pyramid_plan> g_ngpyr;
 
-fsgm_status fsgm::ng_pyramid_with_pair(int n, int W, int H, int channels, const fsgm_ng_pyramid_params* prm, int ru, const PairBody& body) {
-    return pyramid_with_pair(g_ngpyr, n, W, H, channels, prm, ru, body);
+fsgm_status fsgm::ng_pyramid_with_pair(int n, int W, int H, int channels, const fsgm_ng_pyramid_params* prm, int ru, int lm, const PairBody& body) {
+    return pyramid_with_pair(g_ngpyr, n, W, H, channels, prm, ru, lm, body);
 }
 
 extern "C" {
@@ -144,6 +147,8 @@ fsgm_status fsgm_ng_pyramid_plan_download_runner_up(fsgm_ng_pyramid_plan* p, int
     return pyramid_download_runner_up(p, frame, minC2);
 }
 
+fsgm_status fsgm_ng_pyramid_plan_set_level_median(fsgm_ng_pyramid_plan* p, int32_t size) { return pyramid_set_level_median(p, size); }
+
 void fsgm_ng_pyramid_shutdown_internal(void) { g_ngpyr.clear(); }
 
 // one call = the whole loop; plans are cached per shape like fsgm_pyramidal_sgm_host's
@@ -167,6 +172,20 @@ fsgm_status fsgm_pyramidal_sgm_ng_device_ru(int32_t n, const uint8_t* I0, const 
                                             const fsgm_ng_pyramid_params* prm, double* flow, uint32_t* minC, uint32_t* minC2, void* stream,
                                             int32_t* status) {
     return pyramid_device(g_ngpyr, n, I0, I1, width, height, channels, prm, flow, minC, stream, status, minC2, true);
+}
+
+fsgm_status fsgm_pyramidal_sgm_ng_host_lm(const uint8_t* I0, const uint8_t* I1, int32_t width, int32_t height, int32_t channels,
+                                          const fsgm_ng_pyramid_params* prm, int32_t level_median, double* flow, uint32_t* minC,
+                                          uint32_t* minC2, double* const* flowPyd) {
+    return pyramid_host(g_ngpyr, I0, I1, width, height, channels, prm, flow, minC, flowPyd, minC2, minC2 != nullptr,
+                        level_median, true);
+}
+
+fsgm_status fsgm_pyramidal_sgm_ng_device_lm(int32_t n, const uint8_t* I0, const uint8_t* I1, int32_t width, int32_t height, int32_t channels,
+                                            const fsgm_ng_pyramid_params* prm, int32_t level_median, double* flow, uint32_t* minC,
+                                            uint32_t* minC2, void* stream, int32_t* status) {
+    return pyramid_device(g_ngpyr, n, I0, I1, width, height, channels, prm, flow, minC, stream, status, minC2, minC2 != nullptr,
+                          level_median, true);
 }
 
 }  // extern "C"

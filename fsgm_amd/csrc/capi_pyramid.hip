@@ -46,19 +46,21 @@ struct fsgm_pyramid_plan {
         if (st != FSGM_OK) return st;
         PyrFlowArgs a;
         a.bestD = q->dBestD; a.mvSub = q->dMvSub; a.mvPre = q->dMv; a.flow = core.dFlow[l];
-        a.next = l > 0 ? lv[l - 1]->dMv : nullptr;
+        const bool median = l > 0 && core.level_median;                          // :70-71 live: the hints come from the filtered flow
+        a.next = l > 0 && !median ? lv[l - 1]->dMv : nullptr;
         a.next_frame_stride = l > 0 ? 2 * lv[l - 1]->MV : 0;
         a.W = q->W; a.H = q->H; a.mvW = q->mvW; a.mvH = q->mvH;
         a.Sy = q->Sy; a.hor = prm.horSearchHalfWinSize; a.ver = prm.verSearchHalfWinSize;
         launch_pyr_flow(core.stream, a, core.batch);                              // :57-72
+        if (median) launch_pyr_median_upsample2(core.stream, core.dFlow[l], lv[l - 1]->dMv, q->W, q->H, core.batch, 2 * lv[l - 1]->MV, core.level_median);
         return FSGM_OK;
     }
 };
 
 static PyramidCache<fsgm_pyramid_plan> g_pyr;
 
-fsgm_status fsgm::pyd_pyramid_with_pair(int n, int W, int H, int channels, const fsgm_pyramid_params* prm, int ru, const PairBody& body) {
-    return pyramid_with_pair(g_pyr, n, W, H, channels, prm, ru, body);
+fsgm_status fsgm::pyd_pyramid_with_pair(int n, int W, int H, int channels, const fsgm_pyramid_params* prm, int ru, int lm, const PairBody& body) {
+    return pyramid_with_pair(g_pyr, n, W, H, channels, prm, ru, lm, body);
 }
 
 extern "C" {
@@ -155,6 +157,8 @@ fsgm_status fsgm_pyramid_plan_download_runner_up(fsgm_pyramid_plan* p, int32_t f
     return pyramid_download_runner_up(p, frame, minC2);
 }
 
+fsgm_status fsgm_pyramid_plan_set_level_median(fsgm_pyramid_plan* p, int32_t size) { return pyramid_set_level_median(p, size); }
+
 void fsgm_pyramid_shutdown_internal(void) { g_pyr.clear(); }
 
 // one call = pyramidal_sgm(I0, I1, numPyd)
@@ -177,6 +181,67 @@ fsgm_status fsgm_pyramidal_sgm_device_ru(int32_t n, const uint8_t* I0, const uin
                                          const fsgm_pyramid_params* prm, double* mv, uint32_t* minC, uint32_t* minC2, void* stream,
                                          int32_t* status) {
     return pyramid_device(g_pyr, n, I0, I1, width, height, channels, prm, mv, minC, stream, status, minC2, true);
+}
+
+fsgm_status fsgm_pyramidal_sgm_host_lm(const uint8_t* I0, const uint8_t* I1, int32_t width, int32_t height, int32_t channels,
+                                       const fsgm_pyramid_params* prm, int32_t level_median, double* mv, uint32_t* minC, uint32_t* minC2,
+                                       double* const* mvPyd) {
+    return pyramid_host(g_pyr, I0, I1, width, height, channels, prm, mv, minC, mvPyd, minC2, minC2 != nullptr, level_median, true);
+}
+
+fsgm_status fsgm_pyramidal_sgm_device_lm(int32_t n, const uint8_t* I0, const uint8_t* I1, int32_t width, int32_t height, int32_t channels,
+                                         const fsgm_pyramid_params* prm, int32_t level_median, double* mv, uint32_t* minC, uint32_t* minC2,
+                                         void* stream, int32_t* status) {
+    return pyramid_device(g_pyr, n, I0, I1, width, height, channels, prm, mv, minC, stream, status, minC2, minC2 != nullptr,
+                          level_median, true);
+}
+
+// ---- the level-hint kernel on its own: one entry point per MATLAB expression, like the post-processing layer ----
+static fsgm_status hints_args(const char* who, int32_t n, const double* flow, int32_t W, int32_t H, int32_t size, double* next, int32_t device) {
+    FSGM_REQUIRE(n >= 1, "%s: n_frames must be >= 1 (got %d)", who, n);
+    FSGM_REQUIRE(flow && next, "%s: null argument", who);
+    FSGM_REQUIRE(W >= 1 && H >= 1, "%s: width/height must be >= 1 (got %d x %d)", who, W, H);
+    const fsgm_status st = level_median_check(who, size);
+    if (st != FSGM_OK) return st;
+    if (4.0 * n * W * H >= 2147483648.0)
+        return fail(FSGM_ERR_UNSUPPORTED, "%s: 4 * n_frames * width * height = %.0f reaches 2^31 (32-bit pixel indices)", who, 4.0 * n * W * H);
+    FSGM_DEVICE_SLOT(device);
+    return FSGM_OK;
+}
+
+static void hints_enqueue(hipStream_t st, int n, const double* flow, int W, int H, int size, double* next) {
+    const size_t stride = 8 * (size_t)W * H;                 // `next` frames are contiguous: [2][2H][2W]
+    if (size) launch_pyr_median_upsample2(st, flow, next, W, H, n, stride, size);
+    else launch_pyr_upsample2(st, flow, next, W, H, n, stride);
+}
+
+fsgm_status fsgm_flow_level_hints_host(int32_t n, const double* flow, int32_t W, int32_t H, int32_t size, double* next, int32_t device) {
+    fsgm_status st = hints_args("fsgm_flow_level_hints", n, flow, W, H, size, next, device);
+    if (st != FSGM_OK || (st = use_device(device)) != FSGM_OK) return st;
+    const size_t in_bytes = 2 * (size_t)n * W * H * sizeof(double);
+    double* d = nullptr;                                     // the flows, then the hint maps (four times their size)
+    FSGM_HIP(hipMalloc((void**)&d, 5 * in_bytes));
+    hipError_t e = hipMemcpy(d, flow, in_bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        hints_enqueue(nullptr, n, d, W, H, size, d + in_bytes / sizeof(double));
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpy(next, d + in_bytes / sizeof(double), 4 * in_bytes, hipMemcpyDeviceToHost);   // (waits for the kernel)
+    (void)hipFree(d);
+    return hip_status(e, "fsgm_flow_level_hints");
+}
+
+fsgm_status fsgm_flow_level_hints_device(int32_t n, const double* flow, int32_t W, int32_t H, int32_t size, double* next, int32_t device,
+                                         void* stream) {
+    const char* who = "fsgm_flow_level_hints_device";
+    fsgm_status st = hints_args(who, n, flow, W, H, size, next, device);
+    if (st != FSGM_OK) return st;
+    const size_t nv = 2 * (size_t)n * W * H;
+    hipStream_t cs = (hipStream_t)stream;
+    if ((st = device_check_args(who, device, cs, {{flow, nv * 8, 8, true, "flow"}, {next, 4 * nv * 8, 8, true, "next"}})) != FSGM_OK) return st;
+    hints_enqueue(cs, n, flow, W, H, size, next);            // no scratch: queued on the caller's stream itself
+    FSGM_HIP(hipGetLastError());
+    return FSGM_OK;
 }
 
 }  // extern "C"

@@ -13,6 +13,8 @@
 //   fsgm_status enqueue_level(int l);                                  level l on core.stream, the hint map of level l - 1 included
 //   fsgm_status set_runner_up(int on); uint32_t*& minC2();              the runner-up cost of level 1 (include/fsgm.h): with core.runner_up
 //                                                                      set, level 1's WTA also writes the slot's buffer, made on first use
+// With core.level_median = 3 or 5, enqueue_level makes the hint map of level l - 1 from the median-filtered flow of level l
+// (launch_pyr_median_upsample2: pyramidal_sgm.m:70-71 live); core.dFlow[l] stays the unfiltered flow (:66).
 // The entry points reach the gray images and minC through those slots, so that Bind<> in the device entry point swaps what
 // the kernels read and write.
 #pragma once
@@ -35,6 +37,7 @@ struct PyramidCore {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     DeviceJoin join;                             // device-pointer entry point: ordering with the caller's stream
     int runner_up = 0;                           // level 1's WTA also writes minC2 (pyramid_set_runner_up); part of the cached plans' key
+    int level_median = 0;                        // 0, 3 or 5: medfilt2 window of the flow that becomes the next level's hints; part of the key too
 };
 
 template <class P>
@@ -174,6 +177,23 @@ fsgm_status pyramid_download_runner_up(P* p, int frame, uint32_t* minC2) {
     return FSGM_OK;
 }
 
+// The median between levels: 0 (off, at creation), 3 or 5.  Any numPyd, toggled between runs, no buffer of its own
+inline fsgm_status level_median_check(const char* who, int size) {
+    FSGM_REQUIRE(size == 0 || size == 3 || size == 5, "%s: level_median must be 0, 3 or 5 (got %d)", who, size);
+    return FSGM_OK;
+}
+
+template <class P>
+fsgm_status pyramid_set_level_median(P* p, int size) {
+    char who[64];
+    snprintf(who, sizeof who, "%s_set_level_median", P::plan_name);
+    const fsgm_status st = level_median_check(who, size);
+    if (st != FSGM_OK) return st;
+    FSGM_REQUIRE(p, "%s: null plan", who);
+    p->core.level_median = size;
+    return FSGM_OK;
+}
+
 // impyramid 'reduce' (:28-31) and rgb2gray (:44-45) of every level, all frames' planes in one launch
 template <class P>
 void pyramid_enqueue_images(P* p) {
@@ -217,21 +237,21 @@ fsgm_status pyramid_time(P* p, int warmup, int iters, float* ms_avg) {
     return time_enqueues(c.stream, c.ev0, c.ev1, warmup, iters, [&] { return pyramid_enqueue(p); }, ms_avg);
 }
 
-// The plans behind the host- and device-pointer entry points: the last two per device, keyed by shape, parameters, batch and the
-// runner-up switch (a call that asks for minC2 never takes the plan of one that does not, nor the reverse)
+// The plans behind the host- and device-pointer entry points: the last two per device, keyed by shape, parameters, batch, the
+// runner-up switch (a call that asks for minC2 never takes the plan of one that does not, nor the reverse) and the level median
 template <class P>
 struct PyramidCache : PlanCache<P> {
     PyramidCache() : PlanCache<P>(2, pyramid_destroy<P>) {}
     // the cached plan of this shape, parameter set and batch (the caller holds the device's lock)
-    fsgm_status get(P** out, int W, int H, int channels, const typename P::Params* prm, int batch, int ru = 0) {
+    fsgm_status get(P** out, int W, int H, int channels, const typename P::Params* prm, int batch, int ru = 0, int lm = 0) {
         *out = this->find(prm->device, [&](const P* q) {
             return q->core.W == W && q->core.H == H && q->core.channels == channels && q->core.batch == batch && memcmp(&q->prm, prm, sizeof *prm) == 0 &&
-                   q->core.runner_up == ru;
+                   q->core.runner_up == ru && q->core.level_median == lm;
         });
         if (*out) return FSGM_OK;
         fsgm_status st = pyramid_create(out, W, H, channels, batch, prm);
         if (st == FSGM_OK && ru && (st = pyramid_set_runner_up(*out, 1)) != FSGM_OK) { pyramid_destroy(*out); *out = nullptr; }
-        if (st == FSGM_OK) this->insert(prm->device, *out);
+        if (st == FSGM_OK) { (*out)->core.level_median = lm; this->insert(prm->device, *out); }
         return st;
     }
 };
@@ -250,15 +270,16 @@ struct PyramidPair {
     fsgm_status (*run)(void* plan);              // the level loop on `stream`
 };
 
-// body(pair) under the device's lock, on the cached plan for 2n frames of this shape, these parameters and this runner-up switch
+// body(pair) under the device's lock, on the cached plan for 2n frames of this shape, these parameters, this runner-up switch and
+// this level median
 template <class P, class Body>
-fsgm_status pyramid_with_pair(PyramidCache<P>& cache, int n, int W, int H, int channels, const typename P::Params* prm, int ru, Body&& body) {
+fsgm_status pyramid_with_pair(PyramidCache<P>& cache, int n, int W, int H, int channels, const typename P::Params* prm, int ru, int lm, Body&& body) {
     FSGM_REQUIRE(n >= 1 && n <= P::max_batch / 2, "%s: n_frames must be in 1..%d (got %d)", P::entry_name, P::max_batch / 2, n);
     FSGM_DEVICE_SLOT(prm->device);
     std::lock_guard<std::mutex> lk(cache.mu(prm->device));
     P* p = nullptr;
     fsgm_status st;
-    if ((st = cache.get(&p, W, H, channels, prm, 2 * n, ru)) != FSGM_OK) return st;
+    if ((st = cache.get(&p, W, H, channels, prm, 2 * n, ru, lm)) != FSGM_OK) return st;
     FSGM_HIP(hipSetDevice(prm->device));
     PyramidCore& c = p->core;
     const PyramidPair pr{c.stream, c.ev0, c.ev1, &c.join, pyramid_input(p, 0), pyramid_input(p, 1), c.dFlow[0], p->minC(0), ru ? p->minC2() : nullptr, p,
@@ -266,18 +287,25 @@ fsgm_status pyramid_with_pair(PyramidCache<P>& cache, int n, int W, int H, int c
     return body(pr);
 }
 
-// host pointers: one call = the whole loop on a cached plan.  ru: the _ru form, minC2 (never NULL there) of level 1 comes down too
+// host pointers: one call = the whole loop on a cached plan.  ru: minC2 of level 1 comes down too (the _ru form, where it is never
+// NULL, or an _lm form that was given one).  lm: the level median, checked when the call is an _lm form
 template <class P>
 fsgm_status pyramid_host(PyramidCache<P>& cache, const uint8_t* I0, const uint8_t* I1, int W, int H, int channels,
                          const typename P::Params* prm, double* flow, uint32_t* minC, double* const* flowPyd, uint32_t* minC2 = nullptr,
-                         bool ru = false) {
+                         bool ru = false, int lm = 0, bool lm_form = false) {
     FSGM_REQUIRE(I0 && I1 && prm && flow, "%s: null argument", P::entry_name);
     FSGM_REQUIRE(!ru || minC2, "%s_ru: null argument (minC2 is required)", P::entry_name);
+    if (lm_form) {
+        char who[64];
+        snprintf(who, sizeof who, "%s_host_lm", P::entry_name);
+        const fsgm_status ls = level_median_check(who, lm);
+        if (ls != FSGM_OK) return ls;
+    }
     FSGM_DEVICE_SLOT(prm->device);
     std::lock_guard<std::mutex> lk(cache.mu(prm->device));
     P* p = nullptr;
     fsgm_status st;
-    if ((st = cache.get(&p, W, H, channels, prm, 1, ru)) != FSGM_OK) return st;
+    if ((st = cache.get(&p, W, H, channels, prm, 1, ru, lm)) != FSGM_OK) return st;
     // One call = one stream-ordered sequence with a single host wait (like fsgm_calc_cost_sgm_batch_host): the image pair goes up
     // asynchronously, the level loop follows, every requested map comes down behind it.  (Round 3's form waited after the
     // upload, after the run and once per downloaded map, with blocking copies: 6.3 ms per call around 1.4 ms of kernels.)
@@ -306,9 +334,13 @@ fsgm_status pyramid_host(PyramidCache<P>& cache, const uint8_t* I0, const uint8_
 template <class P>
 fsgm_status pyramid_device(PyramidCache<P>& cache, int32_t n, const uint8_t* I0, const uint8_t* I1, int W, int H, int channels,
                            const typename P::Params* prm, double* flow, uint32_t* minC, void* stream, int32_t* status, uint32_t* minC2 = nullptr,
-                           bool ru = false) {
+                           bool ru = false, int lm = 0, bool lm_form = false) {
     char who[64];
-    snprintf(who, sizeof who, "%s_device%s", P::entry_name, ru ? "_ru" : "");
+    snprintf(who, sizeof who, "%s_device%s", P::entry_name, lm_form ? "_lm" : ru ? "_ru" : "");
+    if (lm_form) {
+        const fsgm_status ls = level_median_check(who, lm);
+        if (ls != FSGM_OK) return ls;
+    }
     FSGM_REQUIRE(n >= 1, "%s: n_frames must be >= 1 (got %d)", who, n);
     FSGM_REQUIRE(I0 && I1 && prm && flow, "%s: null argument", who);
     FSGM_REQUIRE(!ru || minC2, "%s: null argument (minC2 is required)", who);
@@ -328,7 +360,7 @@ fsgm_status pyramid_device(PyramidCache<P>& cache, int32_t n, const uint8_t* I0,
         return st;
     std::lock_guard<std::mutex> lk(cache.mu(prm->device));
     P* p = nullptr;
-    if ((st = cache.get(&p, W, H, channels, prm, n, ru)) != FSGM_OK) return st;
+    if ((st = cache.get(&p, W, H, channels, prm, n, ru, lm)) != FSGM_OK) return st;
     const hipStream_t ps = p->core.stream;
     return device_call(p->core.join, cs, ps, [&]() -> fsgm_status {
         Bind<uint8_t> i0(pyramid_input(p, 0), const_cast<uint8_t*>(I0));

@@ -24,5 +24,8 @@ void launch_pyr_flow(hipStream_t st, const PyrFlowArgs& a, int frames = 1);   //
 // next[2][2H][2W] = 2 * flow[2][H][W] at (y/2, x/2): 2*imresize(mv, 2, 'nearest') (pyramidal_sgm.m:72)
 // (flow [frames][2][H][W]; frame f of `next` starts next_frame_stride doubles after frame f-1)
 void launch_pyr_upsample2(hipStream_t st, const double* flow, double* next, int W, int H, int frames = 1, size_t next_frame_stride = 0);
+// the same with medfilt2(flow(:,:,c), [size size]) ahead of the doubling (pyramidal_sgm.m:70-71 live), size 3 or 5: zero padding,
+// the middle value of the sorted window, NaN above every number (vmf's rule).  One thread per source pixel; flow is only read.
+void launch_pyr_median_upsample2(hipStream_t st, const double* flow, double* next, int W, int H, int frames, size_t next_frame_stride, int size);
 
 }  // namespace fsgm

@@ -106,4 +106,77 @@ void launch_pyr_upsample2(hipStream_t st, const double* flow, double* next, int 
     hipLaunchKernelGGL(pyr_upsample2_kernel, dim3((4 * W * H + 255) / 256, frames), dim3(256), 0, st, flow, next, W, H, next_frame_stride);
 }
 
+// pyramidal_sgm.m:70-72 with the commented-out lines :70-71 live: medfilt2(mv(:,:,c), [S S]) of both channels, then
+// 2*imresize(..., 2, 'nearest').  medfilt2 by vmf_kernel's rule (post_kernels.hip): zero padding outside the level, the
+// (S*S+1)/2-th smallest of the window, NaN above every number -- it enters the selection as +Inf and the result is NaN when
+// more than half the window is.  One thread per source pixel on pyr_flow_kernel's tile, both channels one after the other
+// in one register array (selection by fmin / fmax exchanges at compile-time indices only), then pyr_flow_kernel's four
+// double2 stores of the doubled medians.  flow is the level's unfiltered flow (mvPyd{l}, :66) and is only read.
+template <int S>
+__device__ __forceinline__ double pyr_window_median(const double* __restrict__ plane, int x, int y, int W, int H) {
+    constexpr int R = S / 2, N = S * S, M = N / 2;           // w[M] of the sorted window is the median
+    double w[N];
+    int nans = 0;
+#pragma unroll
+    for (int dy = -R; dy <= R; dy++)
+#pragma unroll
+        for (int dx = -R; dx <= R; dx++) {
+            const int yy = y + dy, xx = x + dx;
+            const bool in_img = yy >= 0 && yy < H && xx >= 0 && xx < W;
+            const double v = in_img ? plane[(size_t)(in_img ? yy : 0) * W + (in_img ? xx : 0)] : 0.0;   // zero padding
+            nans += isnan(v) ? 1 : 0;
+            w[(dy + R) * S + dx + R] = isnan(v) ? __longlong_as_double(0x7FF0000000000000LL) : v;
+        }
+#define FSGM_PYR_XCHG(i, j) { const double a_ = w[i], b_ = w[j]; w[i] = fmin(a_, b_); w[j] = fmax(a_, b_); }
+    if constexpr (S == 3) {
+        // the 19-exchange median-of-9 network (Paeth, Graphics Gems; the minimum known): sort the three columns, then the
+        // largest of the minima, the median of the medians and the smallest of the maxima, and the median of those three
+        FSGM_PYR_XCHG(1, 2) FSGM_PYR_XCHG(4, 5) FSGM_PYR_XCHG(7, 8)
+        FSGM_PYR_XCHG(0, 1) FSGM_PYR_XCHG(3, 4) FSGM_PYR_XCHG(6, 7)
+        FSGM_PYR_XCHG(1, 2) FSGM_PYR_XCHG(4, 5) FSGM_PYR_XCHG(7, 8)
+        FSGM_PYR_XCHG(0, 3) FSGM_PYR_XCHG(5, 8) FSGM_PYR_XCHG(4, 7)
+        FSGM_PYR_XCHG(3, 6) FSGM_PYR_XCHG(1, 4) FSGM_PYR_XCHG(2, 5)
+        FSGM_PYR_XCHG(4, 7) FSGM_PYR_XCHG(4, 2) FSGM_PYR_XCHG(6, 4)
+        FSGM_PYR_XCHG(4, 2)
+    } else {
+        // vmf_kernel's partial selection: after pass i, w[i] holds the (i+1)-th smallest
+#pragma unroll
+        for (int i = 0; i <= M; i++)
+#pragma unroll
+            for (int j = i + 1; j < N; j++) FSGM_PYR_XCHG(i, j)
+    }
+#undef FSGM_PYR_XCHG
+    return nans > M ? __longlong_as_double(0x7FF8000000000000LL) : w[M];
+}
+
+template <int S>
+__global__ __launch_bounds__(256) void pyr_median_upsample2_kernel(const double* __restrict__ flow, double* __restrict__ next, int W, int H,
+                                                                   size_t next_frame_stride) {
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (x >= W || y >= H) return;
+    const size_t n = (size_t)W * H;
+    flow += blockIdx.z * 2 * n;                              // frame
+    next += blockIdx.z * next_frame_stride;
+    const double mx = __dmul_rn(2.0, pyr_window_median<S>(flow, x, y, W, H));
+    const double my = __dmul_rn(2.0, pyr_window_median<S>(flow + n, x, y, W, H));
+    const size_t W2 = 2 * (size_t)W, n2 = 4 * n, o = (size_t)(2 * y) * W2 + 2 * x;                       // :72
+    const double2 dx = make_double2(mx, mx), dy = make_double2(my, my);
+    *(double2*)(next + o) = dx;
+    *(double2*)(next + o + W2) = dx;
+    *(double2*)(next + n2 + o) = dy;
+    *(double2*)(next + n2 + o + W2) = dy;
+}
+
+void launch_pyr_median_upsample2(hipStream_t st, const double* flow, double* next, int W, int H, int frames, size_t next_frame_stride, int size) {
+    constexpr int MAX_GRID_Z = 65535;                        // the frame is blockIdx.z: more frames take one launch per 65535
+    const size_t n = (size_t)W * H;
+    for (int z0 = 0; z0 < frames; z0 += MAX_GRID_Z) {
+        const dim3 grid((W + 63) / 64, (H + 3) / 4, frames - z0 < MAX_GRID_Z ? frames - z0 : MAX_GRID_Z);
+        const double* f = flow + (size_t)z0 * 2 * n;
+        double* nx = next + (size_t)z0 * next_frame_stride;
+        if (size == 3) hipLaunchKernelGGL(pyr_median_upsample2_kernel<3>, grid, dim3(256), 0, st, f, nx, W, H, next_frame_stride);
+        else hipLaunchKernelGGL(pyr_median_upsample2_kernel<5>, grid, dim3(256), 0, st, f, nx, W, H, next_frame_stride);
+    }
+}
+
 }  // namespace fsgm

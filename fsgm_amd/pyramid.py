@@ -41,6 +41,10 @@ def _bind(lib):
         lib.fsgm_pyramidal_sgm_host_ru.argtypes = [vp, vp, i32, i32, i32, C.POINTER(PyramidParams), vp, vp, vp, vp]
         lib.fsgm_pyramid_plan_set_runner_up.argtypes = [vp, i32]
         lib.fsgm_pyramid_plan_download_runner_up.argtypes = [vp, i32, vp]
+    if hasattr(lib, "fsgm_pyramidal_sgm_host_lm"):
+        lib.fsgm_pyramidal_sgm_host_lm.argtypes = [vp, vp, i32, i32, i32, C.POINTER(PyramidParams), i32, vp, vp, vp, vp]
+        lib.fsgm_pyramid_plan_set_level_median.argtypes = [vp, i32]
+        lib.fsgm_flow_level_hints_host.argtypes = [i32, vp, i32, i32, i32, vp, i32]
     lib._pyramid_bound = True
 
 
@@ -72,6 +76,36 @@ def _check_images(I0, I1):
     return I0, I1, (1 if I0.ndim == 2 else 3)
 
 
+def level_median_of(size):
+    """the window of the median between levels as the C ABI takes it: 0 (off), 3 or 5"""
+    if isinstance(size, bool) or size not in (0, 3, 5):
+        raise ValueError(f"level_median must be 0, 3 or 5 (got {size!r})")
+    return int(size)
+
+
+def _no_level_median_with_devices(kw):
+    """the device-list forms have no level median (nor a runner-up cost)"""
+    if kw.pop("level_median", 0):
+        raise ValueError("level_median runs on one device: pass device= to the single-pair call, not devices=")
+
+
+def flow_level_hints(flow, size=3, *, device=0):
+    """The hint map the next finer pyramid level starts from: 2 * imresize(medfilt2(flow(:,:,c), [size size]), 2, 'nearest') per
+    channel (pyramidal_sgm.m:70-72 with :70-71 live), the kernel the plans launch with level_median=size.  flow (2, height,
+    width) float64 or a batch (N, 2, height, width); returns (.., 2, 2*height, 2*width).  size 0 is the plain doubling of :72.
+    medfilt2 by vmf's rule: zero padding, the middle value of the sorted window, NaN above every number."""
+    size = level_median_of(size)
+    lib = _lib.load()
+    _bind(lib)
+    flow = np.ascontiguousarray(flow, np.float64)
+    if flow.ndim not in (3, 4) or flow.shape[-3] != 2:
+        raise TypeError(f"flow must be (2, height, width) or (N, 2, height, width) (got {flow.shape})")
+    H, W = flow.shape[-2:]
+    nxt = np.empty(flow.shape[:-2] + (2 * H, 2 * W), np.float64)
+    check(lib.fsgm_flow_level_hints_host(1 if flow.ndim == 3 else flow.shape[0], ptr(flow), W, H, size, ptr(nxt), int(device)))
+    return nxt
+
+
 def _minC2_of(out, H, W):
     """the minC2 array of a runner-up call: the fourth member of out=, else a new one"""
     if out is None:
@@ -84,13 +118,16 @@ def _minC2_of(out, H, W):
     return m2
 
 
-def pyramidal_sgm(I0, I1, numPyd=5, *, device=0, out=None, runner_up=False, **overrides):
+def pyramidal_sgm(I0, I1, numPyd=5, *, device=0, out=None, runner_up=False, level_median=0, **overrides):
     """[mvCurLevel, mvPyd, minC] = pyramidal_sgm(I0, I1, numPyd) (pyramidal_sgm.m:1).  runner_up=True: (mv, mvPyd, minC, minC2)
     with level 1's runner-up cost minC2 uint32 (height, width) (include/fsgm.h, the 2-D rule).  Keyword overrides
     name the function's hard-coded parameters (P1, P2, aggHalfWinSize, verSearchHalfWinSize,
     horSearchHalfWinSize, enableDiagonal, totalPass, adaptiveP2; pyramidal_sgm.m:15-22).
     out: a previous call's result tuple to write into instead of allocating (the results of that call are overwritten): a loop
-    over frames then hands the library pages that are already resident, as a MEX gateway's zero-filled outputs are."""
+    over frames then hands the library pages that are already resident, as a MEX gateway's zero-filled outputs are.
+    level_median=3 or 5: every level's flow is median-filtered (medfilt2 with that window, pyramidal_sgm.m:70-71 live) on its way to
+    the next finer level's hints; the returned flows stay unfiltered.  It combines with runner_up."""
+    level_median = level_median_of(level_median)
     lib = _lib.load()
     _bind(lib)
     I0, I1, ch = _check_images(I0, I1)
@@ -109,6 +146,10 @@ def pyramidal_sgm(I0, I1, numPyd=5, *, device=0, out=None, runner_up=False, **ov
         minC = np.empty((H, W), np.uint32)
         mvPyd = [np.empty((2, h, w), np.float64) for (w, h) in sizes]
     ptrs = (C.c_void_p * len(mvPyd))(*[a.ctypes.data for a in mvPyd])
+    if level_median:
+        check(lib.fsgm_pyramidal_sgm_host_lm(ptr(I0), ptr(I1), W, H, ch, C.byref(prm), level_median, ptr(mv), ptr(minC),
+                                             ptr(minC2) if runner_up else None, ptrs))
+        return (mv, mvPyd, minC, minC2) if runner_up else (mv, mvPyd, minC)
     if runner_up:
         check(lib.fsgm_pyramidal_sgm_host_ru(ptr(I0), ptr(I1), W, H, ch, C.byref(prm), ptr(mv), ptr(minC), ptr(minC2), ptrs))
         return mv, mvPyd, minC, minC2
@@ -148,6 +189,7 @@ def _pairs_over_devices(fn, prm, pairs, devices):
 def pyramidal_sgm_batch(pairs, numPyd=5, *, devices=(0,), **overrides):
     """pyramidal_sgm for a list of (I0, I1) pairs of one shape, pair i on devices[i % len(devices)] (one host thread per
     entry inside the library, no collective); returns a list of (mvCurLevel, mvPyd, minC) like pyramidal_sgm."""
+    _no_level_median_with_devices(overrides)
     lib = _lib.load()
     _bind(lib)
     lib.fsgm_pyramidal_sgm_batch_devices_host.argtypes = [C.c_int32, C.POINTER(PyramidPair), C.c_int32, C.c_int32, C.c_int32,
@@ -214,6 +256,11 @@ class _Plan:
         """Level 1's WTA also writes the runner-up cost minC2 (include/fsgm.h, the matcher's own rule); nothing else changes."""
         check(self._call("set_runner_up", 1 if on else 0))
 
+    def set_level_median(self, size):
+        """The median between levels: 0 (off), 3 or 5 -- medfilt2's window on each level's flow on its way to the next finer level's
+        hints (pyramidal_sgm.m:70-71 live).  download() keeps returning the unfiltered flows.  Toggled freely between runs."""
+        check(self._call("set_level_median", level_median_of(size)))
+
     def download_runner_up(self, frame=0):
         """minC2 uint32 (height, width) of level 1 of the last run; refused while the switch is off."""
         minC2 = np.empty((self.H, self.W), np.uint32)
@@ -277,6 +324,9 @@ def _bind_ng(lib):
         lib.fsgm_pyramidal_sgm_ng_host_ru.argtypes = [vp, vp, i32, i32, i32, C.POINTER(NgPyramidParams), vp, vp, vp, vp]
         lib.fsgm_ng_pyramid_plan_set_runner_up.argtypes = [vp, i32]
         lib.fsgm_ng_pyramid_plan_download_runner_up.argtypes = [vp, i32, vp]
+    if hasattr(lib, "fsgm_pyramidal_sgm_ng_host_lm"):
+        lib.fsgm_pyramidal_sgm_ng_host_lm.argtypes = [vp, vp, i32, i32, i32, C.POINTER(NgPyramidParams), i32, vp, vp, vp, vp]
+        lib.fsgm_ng_pyramid_plan_set_level_median.argtypes = [vp, i32]
     lib._ng_pyramid_bound = True
 
 
@@ -296,6 +346,7 @@ class NgPyramidPlan(_Plan):
 def pyramidal_sgm_ng_batch(pairs, numPyd=3, *, devices=(0,), **overrides):
     """pyramidal_sgm_ng for a list of (I0, I1) pairs of one shape, pair i on devices[i % len(devices)]; returns a list of
     (flow of level 1, [flow per level], minC of level 1) like pyramidal_sgm_ng."""
+    _no_level_median_with_devices(overrides)
     lib = _lib.load()
     _bind_ng(lib)
     lib.fsgm_pyramidal_sgm_ng_batch_devices_host.argtypes = [C.c_int32, C.POINTER(PyramidPair), C.c_int32, C.c_int32, C.c_int32,
@@ -304,7 +355,7 @@ def pyramidal_sgm_ng_batch(pairs, numPyd=3, *, devices=(0,), **overrides):
     return _pairs_over_devices(lib.fsgm_pyramidal_sgm_ng_batch_devices_host, prm, pairs, devices)
 
 
-def pyramidal_sgm_ng(I0, I1, numPyd=3, *, device=0, out=None, runner_up=False, **overrides):
+def pyramidal_sgm_ng(I0, I1, numPyd=3, *, device=0, out=None, runner_up=False, level_median=0, **overrides):
     """The level loop of pyramidal_sgm.m (:24-76) with calc_pyd_cost_sgm_ng swapped in for calc_pyd_cost_sgm
     (BASELINE config 4): the neighbour-guided MEX takes the previous level's flow as its hint map and returns
     the flow itself (calc_pyd_cost_sgm_ng.cpp:458-480).  Defaults are the argument values of ng_sgm.m:20
@@ -313,7 +364,8 @@ def pyramidal_sgm_ng(I0, I1, numPyd=3, *, device=0, out=None, runner_up=False, *
     everything stays on the device between levels.
 
     Returns (flow of level 1, [flow per level, coarsest first], minC of level 1); with runner_up=True also minC2 of level 1,
-    the neighbour-guided runner-up cost of include/fsgm.h."""
+    the neighbour-guided runner-up cost of include/fsgm.h.  level_median=3 or 5: the median between levels of pyramidal_sgm."""
+    level_median = level_median_of(level_median)
     lib = _lib.load()
     _bind_ng(lib)
     I0, I1, ch = _check_images(I0, I1)
@@ -333,6 +385,10 @@ def pyramidal_sgm_ng(I0, I1, numPyd=3, *, device=0, out=None, runner_up=False, *
         minC = np.empty((H, W), np.uint32)
         lv = [np.empty((2, h, w), np.float64) for (w, h) in sizes]
     ptrs = (C.c_void_p * len(lv))(*[a.ctypes.data for a in lv])
+    if level_median:
+        check(lib.fsgm_pyramidal_sgm_ng_host_lm(ptr(I0), ptr(I1), W, H, ch, C.byref(prm), level_median, ptr(flow), ptr(minC),
+                                                ptr(minC2) if runner_up else None, ptrs))
+        return (flow, lv[::-1], minC, minC2) if runner_up else (flow, lv[::-1], minC)
     if runner_up:
         check(lib.fsgm_pyramidal_sgm_ng_host_ru(ptr(I0), ptr(I1), W, H, ch, C.byref(prm), ptr(flow), ptr(minC), ptr(minC2), ptrs))
         return flow, lv[::-1], minC, minC2
@@ -362,6 +418,9 @@ def _bind_flow_pp(lib):
     if hasattr(lib, "fsgm_pyramidal_flow_pp_host_u"):            # (an older build behind FSGM_LIB_PATH has neither)
         lib.fsgm_pyramidal_flow_pp_host_u.argtypes = [i32, vp, vp, i32, i32, i32, prm, i32, vp, vp, vp, vp, vp, vp]
         lib.fsgm_pyramidal_flow_pp_device_u.argtypes = [i32, vp, vp, i32, i32, i32, prm, i32, vp, vp, vp, vp, vp, vp, vp, vp]
+    if hasattr(lib, "fsgm_pyramidal_flow_pp_host_lm"):
+        lib.fsgm_pyramidal_flow_pp_host_lm.argtypes = [i32, vp, vp, i32, i32, i32, prm, i32, i32, vp, vp, vp, vp, vp, vp]
+        lib.fsgm_pyramidal_flow_pp_device_lm.argtypes = [i32, vp, vp, i32, i32, i32, prm, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]
     lib._flow_pp_bound = True
 
 
@@ -406,7 +465,8 @@ def uniqueness_ratio_of(ratio):
     return int(ratio)
 
 
-def pyramidal_flow_pp(I0, I1, numPyd=None, matcher="pyd", *, median=0, batch=None, device=0, uniqueness_ratio=None, **overrides):
+def pyramidal_flow_pp(I0, I1, numPyd=None, matcher="pyd", *, median=0, batch=None, device=0, uniqueness_ratio=None, level_median=0,
+                      **overrides):
     """The consistency-checked, filtered flow of a pyramidal matcher (matcher="pyd": pyramidal_sgm, "ng": pyramidal_sgm_ng):
     forward and backward flow from one run of a plan of twice the batch, then on the device the chain of test.m:45-49 on
     vectors -- speckle filter of both flows, forward-backward check, island removal, KITTI hole fill, and vmf's median with
@@ -421,7 +481,11 @@ def pyramidal_flow_pp(I0, I1, numPyd=None, matcher="pyd", *, median=0, batch=Non
     uniqueness_ratio=r (an integer in [0, 100]): the matcher also reports its runner-up cost, and the uniqueness test of
     fsgm_amd.uniqueness_filter blanks the ambiguous pixels of the forward and of the backward flow, each by its own costs, ahead
     of the chain.  The call then returns the five outputs plus minC2 of the forward run; the raw flows stay raw, and r = 0 gives
-    the same five outputs as a call without the keyword."""
+    the same five outputs as a call without the keyword.
+
+    level_median=3 or 5: both directions run with the median between levels (pyramidal_sgm's keyword); flow_fwd and flow_bwd are
+    the raw level-1 flows of those runs.  It combines with uniqueness_ratio."""
+    level_median = level_median_of(level_median)
     lib = _lib.load()
     _bind(lib)
     _bind_ng(lib)
@@ -431,6 +495,13 @@ def pyramidal_flow_pp(I0, I1, numPyd=None, matcher="pyd", *, median=0, batch=Non
     pp = np.empty((N, 3, H, W), np.float64)
     checked, fwd, bwd = (np.empty((N, 2, H, W), np.float64) for _ in range(3))
     minC = np.empty((N, H, W), np.uint32)
+    if level_median:
+        minC2 = np.empty((N, H, W), np.uint32) if uniqueness_ratio is not None else None
+        ratio = uniqueness_ratio_of(uniqueness_ratio) if uniqueness_ratio is not None else 0
+        check(lib.fsgm_pyramidal_flow_pp_host_lm(N, ptr(I0), ptr(I1), W, H, ch, C.byref(prm), ratio, level_median, ptr(pp), ptr(checked),
+                                                 ptr(fwd), ptr(bwd), ptr(minC), ptr(minC2) if minC2 is not None else None))
+        outs = (pp, checked, fwd, bwd, minC) + ((minC2,) if minC2 is not None else ())
+        return outs if batched else tuple(o[0] for o in outs)
     if uniqueness_ratio is not None:
         minC2 = np.empty((N, H, W), np.uint32)
         check(lib.fsgm_pyramidal_flow_pp_host_u(N, ptr(I0), ptr(I1), W, H, ch, C.byref(prm), uniqueness_ratio_of(uniqueness_ratio), ptr(pp),

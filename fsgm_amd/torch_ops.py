@@ -18,7 +18,9 @@ fsgm::sgm_ru and fsgm::sgm2d_ru (fsgm::sgm / fsgm::sgm2d with minC2 after minC) 
 two-plane flow; status always 0); fsgm::pyramidal_sgm_ru and fsgm::pyramidal_sgm_ng_ru (the pyramids with level 1's minC2 after
 minC) and fsgm::pyramidal_flow_pp_u (fsgm::pyramidal_flow_pp with a uniqueness ratio ahead of the chain and minC2 after minC);
 fsgm::sgm_exact (fsgm::sgm with exact path arithmetic, fsgm_sgm_device_exact: the same arguments and outputs),
-fsgm::sgm2d_exact (fsgm::sgm2d_ru with exact path arithmetic, fsgm_sgm2d_device_exact: a runner_up flag added, minC2 empty without it).
+fsgm::sgm2d_exact (fsgm::sgm2d_ru with exact path arithmetic, fsgm_sgm2d_device_exact: a runner_up flag added, minC2 empty without it);
+fsgm::pyramidal_sgm_lm, fsgm::pyramidal_sgm_ng_lm and fsgm::pyramidal_flow_pp_lm (the _ru / _u ops with the median between levels:
+a level_median argument, minC2 empty when not asked for) and fsgm::flow_level_hints (the hint map of the next finer level).
 
 One process must hold one HIP runtime.  torch brings its own libamdhip64; libfsgm_hip.so binds to it by soname when torch is
 imported first.  When the library was loaded first, torch afterwards maps a second runtime, and a stream or pointer of one
@@ -39,7 +41,7 @@ from .stereo_pp import CHAIN_FIELDS as STEREO_PP_FIELDS, _bind as _bind_stereo_p
 from .sgm import _bind as _bind_sgm, arith_exact as _arith_exact, layout_code as _layout_code, params as _sgm_params, shape_of as _sgm_shape
 from .sgm2d import _bind as _bind_sgm2d, arith_exact as _arith2d_exact, layout_code as _layout2d_code, params as _sgm2d_params, shape_of as _sgm2d_shape, LAYOUTS as _LAYOUTS2D
 from .pyramid import (PyramidParams, NgPyramidParams, FLOW_PP_FIELDS, MATCHERS, _bind as _bind_pyramid, _bind_flow_pp, _bind_ng,
-                      uniqueness_ratio_of as _uniqueness_ratio_of)
+                      uniqueness_ratio_of as _uniqueness_ratio_of, level_median_of as _level_median_of)
 
 FSGM_ERR_INVALID, FSGM_ERR_HIP = 1, 2
 
@@ -92,6 +94,10 @@ _L.fsgm_pyramidal_sgm_ng_device.argtypes = [_i32, _vp, _vp, _i32, _i32, _i32, C.
 if hasattr(_L, "fsgm_pyramidal_sgm_device_ru"):                  # (an older build behind FSGM_LIB_PATH has neither)
     _L.fsgm_pyramidal_sgm_device_ru.argtypes = [_i32, _vp, _vp, _i32, _i32, _i32, C.POINTER(PyramidParams), _vp, _vp, _vp, _vp, _vp]
     _L.fsgm_pyramidal_sgm_ng_device_ru.argtypes = [_i32, _vp, _vp, _i32, _i32, _i32, C.POINTER(NgPyramidParams), _vp, _vp, _vp, _vp, _vp]
+if hasattr(_L, "fsgm_pyramidal_sgm_device_lm"):
+    _L.fsgm_pyramidal_sgm_device_lm.argtypes = [_i32, _vp, _vp, _i32, _i32, _i32, C.POINTER(PyramidParams), _i32, _vp, _vp, _vp, _vp, _vp]
+    _L.fsgm_pyramidal_sgm_ng_device_lm.argtypes = [_i32, _vp, _vp, _i32, _i32, _i32, C.POINTER(NgPyramidParams), _i32, _vp, _vp, _vp, _vp, _vp]
+    _L.fsgm_flow_level_hints_device.argtypes = [_i32, _vp, _i32, _i32, _i32, _vp, _i32, _vp]
 
 # the overridable fields of the pyramids' parameter structs, in the order the ops take them
 PYRAMID_FIELDS = ("P1", "P2", "aggHalfWinSize", "verSearchHalfWinSize", "horSearchHalfWinSize", "enableDiagonal", "totalPass", "adaptiveP2")
@@ -579,6 +585,68 @@ def _(I0, I1, numPyd, params):
     return _pyramid_ru_outputs(I0)
 
 
+def _pyramid_lm_outputs(I0, runner_up):
+    N, H, W, dev = _frames(I0)
+    return _f64((N, 2, H, W), dev), _u32((N, H, W), dev), _u32((N, H, W) if runner_up else (0,), dev), _status(dev)
+
+
+def _pyramid_lm_run(fn, prm, I0, I1, level_median, runner_up):
+    N, H, W, dev = _frames(I0)
+    ch = 1 if I0.dim() == 3 else 3
+    prm.device = dev.index
+    I0, I1 = _ready(I0), _ready(I1)
+    mv, minC, minC2, status = _pyramid_lm_outputs(I0, runner_up)
+    _call(dev, fn, N, _p(I0), _p(I1), W, H, ch, C.byref(prm), int(level_median), _p(mv), _p(minC), _p(minC2) if runner_up else None,
+          _stream(dev), _p(status))
+    return mv, minC, minC2, status
+
+
+@torch.library.custom_op("fsgm::pyramidal_sgm_lm", mutates_args=())
+def _pyramidal_sgm_lm_op(I0: torch.Tensor, I1: torch.Tensor, numPyd: int, params: List[int], level_median: int,
+                         runner_up: bool) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """fsgm::pyramidal_sgm_ru with the median between levels (fsgm_pyramidal_sgm_device_lm); minC2 is empty unless runner_up"""
+    prm = _pyramid_prm(_L.fsgm_pyramid_params_default, PYRAMID_FIELDS, numPyd, params)
+    return _pyramid_lm_run(_L.fsgm_pyramidal_sgm_device_lm, prm, I0, I1, level_median, runner_up)
+
+
+@_pyramidal_sgm_lm_op.register_fake
+def _(I0, I1, numPyd, params, level_median, runner_up):
+    return _pyramid_lm_outputs(I0, runner_up)
+
+
+@torch.library.custom_op("fsgm::pyramidal_sgm_ng_lm", mutates_args=())
+def _pyramidal_sgm_ng_lm_op(I0: torch.Tensor, I1: torch.Tensor, numPyd: int, params: List[int], level_median: int,
+                            runner_up: bool) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """fsgm::pyramidal_sgm_ng_ru with the median between levels (fsgm_pyramidal_sgm_ng_device_lm); minC2 is empty unless runner_up"""
+    prm = _pyramid_prm(_L.fsgm_ng_pyramid_params_default, NG_PYRAMID_FIELDS, numPyd, params)
+    return _pyramid_lm_run(_L.fsgm_pyramidal_sgm_ng_device_lm, prm, I0, I1, level_median, runner_up)
+
+
+@_pyramidal_sgm_ng_lm_op.register_fake
+def _(I0, I1, numPyd, params, level_median, runner_up):
+    return _pyramid_lm_outputs(I0, runner_up)
+
+
+def _level_hints_output(flow):
+    N, _, H, W = flow.shape
+    return _f64((N, 2, 2 * H, 2 * W), flow.device)
+
+
+@torch.library.custom_op("fsgm::flow_level_hints", mutates_args=())
+def _flow_level_hints_op(flow: torch.Tensor, size: int) -> torch.Tensor:
+    N, _, H, W = flow.shape
+    dev = flow.device
+    flow = _ready(flow)
+    out = _level_hints_output(flow)
+    _call(dev, _L.fsgm_flow_level_hints_device, N, _p(flow), W, H, int(size), _p(out), dev.index, _stream(dev))
+    return out
+
+
+@_flow_level_hints_op.register_fake
+def _(flow, size):
+    return _level_hints_output(flow)
+
+
 @torch.library.custom_op("fsgm::pyramidal_sgm", mutates_args=())
 def _pyramidal_sgm_op(I0: torch.Tensor, I1: torch.Tensor, numPyd: int,
                       params: List[int]) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
@@ -646,6 +714,33 @@ def _pyramidal_flow_pp_u_op(I0: torch.Tensor, I1: torch.Tensor, matcher: int, nu
 def _(I0, I1, matcher, numPyd, params, chain, median, uniqueness_ratio):
     pp, checked, fwd, bwd, minC, status = _pyramidal_flow_pp_outputs(I0)
     return pp, checked, fwd, bwd, minC, torch.empty_like(minC), status
+
+
+def _pyramidal_flow_pp_lm_outputs(I0, want_minC2):
+    pp, checked, fwd, bwd, minC, status = _pyramidal_flow_pp_outputs(I0)
+    return pp, checked, fwd, bwd, minC, torch.empty_like(minC) if want_minC2 else _u32((0,), I0.device), status
+
+
+@torch.library.custom_op("fsgm::pyramidal_flow_pp_lm", mutates_args=())
+def _pyramidal_flow_pp_lm_op(I0: torch.Tensor, I1: torch.Tensor, matcher: int, numPyd: int, params: List[int], chain: List[float],
+                             median: int, uniqueness_ratio: int, want_minC2: bool,
+                             level_median: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor,
+                                                         torch.Tensor, torch.Tensor]:
+    """fsgm::pyramidal_flow_pp_u with the median between levels (fsgm_pyramidal_flow_pp_device_lm); minC2 is empty unless
+    want_minC2, which a non-zero uniqueness_ratio needs"""
+    N, H, W, dev = _frames(I0)
+    ch = 1 if I0.dim() == 3 else 3
+    prm = _flow_pp_prm(matcher, numPyd, params, chain, median, dev)
+    I0, I1 = _ready(I0), _ready(I1)
+    pp, checked, fwd, bwd, minC, minC2, status = _pyramidal_flow_pp_lm_outputs(I0, want_minC2)
+    _call(dev, _L.fsgm_pyramidal_flow_pp_device_lm, N, _p(I0), _p(I1), W, H, ch, C.byref(prm), int(uniqueness_ratio), int(level_median),
+          _p(pp), _p(checked), _p(fwd), _p(bwd), _p(minC), _p(minC2) if want_minC2 else None, _stream(dev), _p(status))
+    return pp, checked, fwd, bwd, minC, minC2, status
+
+
+@_pyramidal_flow_pp_lm_op.register_fake
+def _(I0, I1, matcher, numPyd, params, chain, median, uniqueness_ratio, want_minC2, level_median):
+    return _pyramidal_flow_pp_lm_outputs(I0, want_minC2)
 
 
 @torch.library.custom_op("fsgm::pyramidal_flow_pp", mutates_args=())
@@ -1221,6 +1316,18 @@ def vmf(flow):
     return torch.ops.fsgm.vmf(flow)
 
 
+def flow_level_hints(flow, size=3):
+    """fsgm_amd.flow_level_hints on a torch tensor on the GPU: flow (2, H, W) or (N, 2, H, W) float64 -> the next finer level's
+    hint map (.., 2, 2H, 2W).  No status: the kernel has no failure to report."""
+    size = _level_median_of(size)
+    _tensors({"flow": (flow, torch.float64)})
+    if flow.dim() not in (3, 4) or flow.shape[-3] != 2:
+        raise TypeError(f"flow must be (2, H, W) or (N, 2, H, W) (got {tuple(flow.shape)})")
+    if flow.dim() == 3:
+        return torch.ops.fsgm.flow_level_hints(flow.unsqueeze(0), size)[0]
+    return torch.ops.fsgm.flow_level_hints(flow, size)
+
+
 def _pyramid_images(I0, I1, batch):
     _tensors({"I0": (I0, torch.uint8), "I1": (I1, torch.uint8)})
     _shape("I1", I1, I0.shape)
@@ -1239,13 +1346,22 @@ def _overrides(fields, defaults, overrides, name):
     return [int(overrides.get(k, getattr(defaults, k))) for k in fields]
 
 
-def pyramidal_sgm(I0, I1, numPyd=5, *, batch=None, check=False, return_status=False, runner_up=False, **overrides):
+def _pyramid_lm(op, I0, I1, numPyd, params, level_median, runner_up, batched, check, return_status):
+    mv, minC, minC2, status = op(I0, I1, int(numPyd), params, level_median, bool(runner_up))
+    return _finish((mv, minC, minC2) if runner_up else (mv, minC), status, batched, check, return_status)
+
+
+def pyramidal_sgm(I0, I1, numPyd=5, *, batch=None, check=False, return_status=False, runner_up=False, level_median=0, **overrides):
     """(mv, minC) of level 1 of pyramidal_sgm(I0, I1, numPyd) as fsgm_amd.pyramidal_sgm, on torch tensors on the GPU (the per-level
     flows are not offered).  Images (H, W) or RGB (3, H, W) uint8, or a batch with a leading N; batch=None infers it (a 3-D tensor
     with 3 planes is one RGB pair).  mv (.., 2, H, W) float64, minC (.., H, W) uint32.  Keyword overrides as fsgm_amd.pyramidal_sgm.
-    runner_up=True: (mv, minC, minC2) with level 1's runner-up cost (fsgm::pyramidal_sgm_ru)."""
+    runner_up=True: (mv, minC, minC2) with level 1's runner-up cost (fsgm::pyramidal_sgm_ru).  level_median=3 or 5: the median
+    between levels of fsgm_amd.pyramidal_sgm (fsgm::pyramidal_sgm_lm); it combines with runner_up."""
+    level_median = _level_median_of(level_median)
     I0, I1, batched = _pyramid_images(I0, I1, batch)
     params = _overrides(PYRAMID_FIELDS, _L.fsgm_pyramid_params_default(), overrides, "pyramidal_sgm")
+    if level_median:
+        return _pyramid_lm(torch.ops.fsgm.pyramidal_sgm_lm, I0, I1, numPyd, params, level_median, runner_up, batched, check, return_status)
     if runner_up:
         mv, minC, minC2, status = torch.ops.fsgm.pyramidal_sgm_ru(I0, I1, int(numPyd), params)
         return _finish((mv, minC, minC2), status, batched, check, return_status)
@@ -1253,11 +1369,15 @@ def pyramidal_sgm(I0, I1, numPyd=5, *, batch=None, check=False, return_status=Fa
     return _finish((mv, minC), status, batched, check, return_status)
 
 
-def pyramidal_sgm_ng(I0, I1, numPyd=3, *, batch=None, check=False, return_status=False, runner_up=False, **overrides):
+def pyramidal_sgm_ng(I0, I1, numPyd=3, *, batch=None, check=False, return_status=False, runner_up=False, level_median=0, **overrides):
     """(flow, minC) of level 1 of the pyramidal loop around calc_pyd_cost_sgm_ng as fsgm_amd.pyramidal_sgm_ng, on torch tensors
-    on the GPU; shapes and batch as pyramidal_sgm.  runner_up=True: (flow, minC, minC2) (fsgm::pyramidal_sgm_ng_ru)."""
+    on the GPU; shapes and batch as pyramidal_sgm.  runner_up=True: (flow, minC, minC2) (fsgm::pyramidal_sgm_ng_ru).
+    level_median=3 or 5: the median between levels (fsgm::pyramidal_sgm_ng_lm)."""
+    level_median = _level_median_of(level_median)
     I0, I1, batched = _pyramid_images(I0, I1, batch)
     params = _overrides(NG_PYRAMID_FIELDS, _L.fsgm_ng_pyramid_params_default(), overrides, "pyramidal_sgm_ng")
+    if level_median:
+        return _pyramid_lm(torch.ops.fsgm.pyramidal_sgm_ng_lm, I0, I1, numPyd, params, level_median, runner_up, batched, check, return_status)
     if runner_up:
         flow, minC, minC2, status = torch.ops.fsgm.pyramidal_sgm_ng_ru(I0, I1, int(numPyd), params)
         return _finish((flow, minC, minC2), status, batched, check, return_status)
@@ -1266,10 +1386,12 @@ def pyramidal_sgm_ng(I0, I1, numPyd=3, *, batch=None, check=False, return_status
 
 
 def pyramidal_flow_pp(I0, I1, numPyd=None, matcher="pyd", *, median=0, batch=None, check=False, return_status=False,
-                      uniqueness_ratio=None, **overrides):
+                      uniqueness_ratio=None, level_median=0, **overrides):
     """(flow_pp, flow_checked, flow_fwd, flow_bwd, minC) as fsgm_amd.pyramidal_flow_pp, on torch tensors on the GPU; images and
     batch as pyramidal_sgm.  flow_pp (.., 3, H, W), the flows (.., 2, H, W) float64, minC (.., H, W) uint32.
-    uniqueness_ratio=r: the five outputs plus minC2, with the uniqueness test ahead of the chain (fsgm::pyramidal_flow_pp_u)."""
+    uniqueness_ratio=r: the five outputs plus minC2, with the uniqueness test ahead of the chain (fsgm::pyramidal_flow_pp_u).
+    level_median=3 or 5: both directions run with the median between levels (fsgm::pyramidal_flow_pp_lm)."""
+    level_median = _level_median_of(level_median)
     if matcher not in MATCHERS:
         raise ValueError(f"matcher must be 'pyd' or 'ng' (got {matcher!r})")
     I0, I1, batched = _pyramid_images(I0, I1, batch)
@@ -1277,6 +1399,13 @@ def pyramidal_flow_pp(I0, I1, numPyd=None, matcher="pyd", *, median=0, batch=Non
     sub, fields = (defaults.ng, NG_PYRAMID_FIELDS) if matcher == "ng" else (defaults.pyd, PYRAMID_FIELDS)
     chain = [float(overrides.pop(k, getattr(defaults, k))) for k in FLOW_PP_FIELDS]
     params = _overrides(fields, sub, overrides, "pyramidal_flow_pp")
+    if level_median:
+        want = uniqueness_ratio is not None
+        pp, checked, fwd, bwd, minC, minC2, status = torch.ops.fsgm.pyramidal_flow_pp_lm(
+            I0, I1, MATCHERS[matcher], int(sub.numPyd if numPyd is None else numPyd), params, chain, int(median),
+            _uniqueness_ratio_of(uniqueness_ratio) if want else 0, want, level_median)
+        outs = (pp, checked, fwd, bwd, minC) + ((minC2,) if want else ())
+        return _finish(outs, status, batched, check, return_status)
     if uniqueness_ratio is not None:
         *outs, status = torch.ops.fsgm.pyramidal_flow_pp_u(I0, I1, MATCHERS[matcher], int(sub.numPyd if numPyd is None else numPyd), params,
                                                            chain, int(median), _uniqueness_ratio_of(uniqueness_ratio))

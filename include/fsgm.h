@@ -740,6 +740,28 @@ fsgm_status fsgm_pyramid_plan_download_runner_up(fsgm_pyramid_plan* plan, int32_
 fsgm_status fsgm_pyramidal_sgm_host_ru(const uint8_t* I0, const uint8_t* I1, int32_t width, int32_t height,
                                        int32_t channels, const fsgm_pyramid_params* prm,
                                        double* mv, uint32_t* minC, uint32_t* minC2, double* const* mvPyd);
+/* The median between levels: pyramidal_sgm.m:66-72 with the commented-out lines :70-71 live and a window size.  mvPyd{l} and
+ * every level-1 output stay the unfiltered flow (:66 stores it ahead of :70); for l > 1 the hint map of level l - 1 becomes
+ *   2 * imresize(medfilt2(mv(:,:,c), [size size]), 2, 'nearest')      per channel c
+ * so the median changes only what the finer levels start from.  size 0 is off (the reference as shipped, and the default), 3 is
+ * medfilt2's default window, 5 is vmf.m's; anything else is FSGM_ERR_INVALID.  medfilt2 by the rule of fsgm_vmf_host: zero padding
+ * outside the level's W x H, the (size*size+1)/2-th smallest value, NaN above every number (NaN only when more than half the
+ * window is), +-Inf as numbers; the sign of a zero that ties at the median is unspecified.  The doubling is exact.  With numPyd 1
+ * or size 0 every output equals the plain run bit for bit.  The switch may be set at any numPyd and toggled between runs. */
+fsgm_status fsgm_pyramid_plan_set_level_median(fsgm_pyramid_plan* plan, int32_t size);
+/* fsgm_pyramidal_sgm_host_ru with the level median after prm.  minC2 may be NULL (not wanted: the plan then runs without the
+ * runner-up switch).  level_median is part of the cached plans' key, next to the runner-up switch: a plain or _ru call never gets
+ * a plan whose median is on, nor the reverse.  A bad size is refused before a device is touched. */
+fsgm_status fsgm_pyramidal_sgm_host_lm(const uint8_t* I0, const uint8_t* I1, int32_t width, int32_t height,
+                                       int32_t channels, const fsgm_pyramid_params* prm, int32_t level_median,
+                                       double* mv, uint32_t* minC, uint32_t* minC2, double* const* mvPyd);
+/* The hint map of the next finer level from n_frames flows, on its own: flow f64 [n][2][H][W] -> next f64 [n][2][2H][2W].  For
+ * size 3 or 5 exactly the launch the plans make with the switch on; size 0 is 2 * imresize(flow, 2, 'nearest') (:72).  The
+ * device form needs no scratch: the kernel is queued on `stream` itself.  4 * n_frames * width * height must stay below 2^31. */
+fsgm_status fsgm_flow_level_hints_host(int32_t n_frames, const double* flow, int32_t width, int32_t height, int32_t size,
+                                       double* next, int32_t device);
+fsgm_status fsgm_flow_level_hints_device(int32_t n_frames, const double* flow, int32_t width, int32_t height, int32_t size,
+                                         double* next, int32_t device, void* stream);
 
 /* ---- the pyramidal level loop with the neighbour-guided matcher ----
  * BASELINE config 4 names calc_pyd_cost_sgm_ng for the pyramidal path.  The reference ships that MEX as a swap-in
@@ -784,6 +806,11 @@ fsgm_status fsgm_ng_pyramid_plan_set_runner_up(fsgm_ng_pyramid_plan* plan, int32
 fsgm_status fsgm_ng_pyramid_plan_download_runner_up(fsgm_ng_pyramid_plan* plan, int32_t frame, uint32_t* minC2);
 fsgm_status fsgm_pyramidal_sgm_ng_host_ru(const uint8_t* I0, const uint8_t* I1, int32_t width, int32_t height,
                                           int32_t channels, const fsgm_ng_pyramid_params* prm,
+                                          double* flow, uint32_t* minC, uint32_t* minC2, double* const* flowPyd);
+/* The median between levels, as fsgm_pyramid_plan_set_level_median / fsgm_pyramidal_sgm_host_lm */
+fsgm_status fsgm_ng_pyramid_plan_set_level_median(fsgm_ng_pyramid_plan* plan, int32_t size);
+fsgm_status fsgm_pyramidal_sgm_ng_host_lm(const uint8_t* I0, const uint8_t* I1, int32_t width, int32_t height,
+                                          int32_t channels, const fsgm_ng_pyramid_params* prm, int32_t level_median,
                                           double* flow, uint32_t* minC, uint32_t* minC2, double* const* flowPyd);
 
 
@@ -939,6 +966,17 @@ fsgm_status fsgm_pyramidal_flow_pp_device_u(int32_t n_frames, const uint8_t* I0,
                                             int32_t channels, const fsgm_flow_pp_params* prm, int32_t uniqueness_ratio,
                                             double* flow_pp, double* flow_checked, double* flow_fwd, double* flow_bwd, uint32_t* minC,
                                             uint32_t* minC2, void* stream, int32_t* status);
+/* The _u forms with the level median (fsgm_pyramid_plan_set_level_median above) after uniqueness_ratio: the plan of 2n pairs runs
+ * both directions with it, and flow_fwd / flow_bwd are the raw level-1 flows of those runs.  minC2 may be NULL exactly when
+ * uniqueness_ratio is 0 (the plan then runs without the runner-up switch).  level_median 0 gives the _u forms' outputs. */
+fsgm_status fsgm_pyramidal_flow_pp_host_lm(int32_t n_frames, const uint8_t* I0, const uint8_t* I1, int32_t width, int32_t height,
+                                           int32_t channels, const fsgm_flow_pp_params* prm, int32_t uniqueness_ratio,
+                                           int32_t level_median, double* flow_pp, double* flow_checked, double* flow_fwd,
+                                           double* flow_bwd, uint32_t* minC, uint32_t* minC2);
+fsgm_status fsgm_pyramidal_flow_pp_device_lm(int32_t n_frames, const uint8_t* I0, const uint8_t* I1, int32_t width, int32_t height,
+                                             int32_t channels, const fsgm_flow_pp_params* prm, int32_t uniqueness_ratio,
+                                             int32_t level_median, double* flow_pp, double* flow_checked, double* flow_fwd,
+                                             double* flow_bwd, uint32_t* minC, uint32_t* minC2, void* stream, int32_t* status);
 /* average milliseconds (HIP events on the plan's stream, images uploaded once before) of the batch-2n pyramid run, ms[0],
  * and of the chain behind it, ms[1], for host images as fsgm_pyramidal_flow_pp_host takes them */
 fsgm_status fsgm_pyramidal_flow_pp_time(int32_t n_frames, const uint8_t* I0, const uint8_t* I1, int32_t width, int32_t height,
@@ -1318,6 +1356,13 @@ fsgm_status fsgm_pyramidal_sgm_device_ru(int32_t n_frames, const uint8_t* I0, co
                                          double* mv, uint32_t* minC, uint32_t* minC2, void* stream, int32_t* status);
 fsgm_status fsgm_pyramidal_sgm_ng_device_ru(int32_t n_frames, const uint8_t* I0, const uint8_t* I1, int32_t width,
                                             int32_t height, int32_t channels, const fsgm_ng_pyramid_params* prm,
+                                            double* flow, uint32_t* minC, uint32_t* minC2, void* stream, int32_t* status);
+/* the same with the level median after prm (fsgm_pyramidal_sgm_host_lm); minC2 may be NULL: not wanted */
+fsgm_status fsgm_pyramidal_sgm_device_lm(int32_t n_frames, const uint8_t* I0, const uint8_t* I1, int32_t width,
+                                         int32_t height, int32_t channels, const fsgm_pyramid_params* prm, int32_t level_median,
+                                         double* mv, uint32_t* minC, uint32_t* minC2, void* stream, int32_t* status);
+fsgm_status fsgm_pyramidal_sgm_ng_device_lm(int32_t n_frames, const uint8_t* I0, const uint8_t* I1, int32_t width,
+                                            int32_t height, int32_t channels, const fsgm_ng_pyramid_params* prm, int32_t level_median,
                                             double* flow, uint32_t* minC, uint32_t* minC2, void* stream, int32_t* status);
 
 #ifdef __cplusplus

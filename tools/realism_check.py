@@ -7,7 +7,9 @@ ground-truth magnitude, over the valid pixels).
 
 Build container only: the images are the reference's (KITTI licence) and are neither committed nor shipped to the GPU box;
 this is a plausibility bound on the restated toolbox functions, NOT a parity pin.
-usage: tools/realism_check.py [numPyd ...]        (default: 3 as test_psgm.m:33, and 5 = pyramidal_sgm.m:12's default)"""
+usage: tools/realism_check.py [--level-median S] [numPyd ...]   (default: 3 as test_psgm.m:33, and 5 = pyramidal_sgm.m:12's default)
+--level-median 3 | 5 scores the loop with the median between levels (pyramidal_sgm.m:70-71 live) instead: its numpy restatement
+around the same single-level oracle (tests/level_median_restatement.py), which the GPU tests prove equal to the library."""
 import os, struct, sys, time, zlib
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -83,15 +85,25 @@ def main():
           f"|flow| up to {np.sqrt(gu ** 2 + gv ** 2)[valid].max():.1f} px")
     P0 = np.ascontiguousarray(np.moveaxis(I0, 2, 0)) if I0.ndim == 3 else I0                            # (3, H, W) planes, x fastest
     P1 = np.ascontiguousarray(np.moveaxis(I1, 2, 0)) if I1.ndim == 3 else I1
-    for n in [int(a) for a in sys.argv[1:]] or [3, 5]:
+    args, median = sys.argv[1:], 0
+    if "--level-median" in args:
+        i = args.index("--level-median")
+        median = int(args[i + 1])
+        assert median in (0, 3, 5), "--level-median takes 0, 3 or 5"
+        del args[i:i + 2]
+    for n in [int(a) for a in args] or [3, 5]:
         t0 = time.time()
-        mv, minC, lv = pyoracle.pyramidal_sgm(P0, P1, n)                                                 # pyramidal_sgm.m defaults: P1=6, P2=32, 11x11, 8 paths, 2 passes
+        if median:
+            from tests import level_median_restatement
+            mv = level_median_restatement.pyramidal_sgm_lm(pyoracle, P0, P1, n, median)[0]
+        else:
+            mv, minC, lv = pyoracle.pyramidal_sgm(P0, P1, n)                                             # pyramidal_sgm.m defaults: P1=6, P2=32, 11x11, 8 paths, 2 passes
         out, aepe = flow_error(gu, gv, valid, mv[0], mv[1])
         zo, za = flow_error(gu, gv, valid, np.zeros_like(gu), np.zeros_like(gu))
         reach = 5 * (2 ** n - 1)                                                                         # +-5 per level, doubled from level to level
         near = valid & (np.maximum(np.abs(gu), np.abs(gv)) <= reach)
         no, na = flow_error(gu, gv, near, mv[0], mv[1])
-        print(f"oracle pyramidal_sgm(I0, I1, {n}): outlier {out:.4f}, AEPE {aepe:.3f} px   (zero flow: {zo:.4f} / {za:.3f}); "
+        print(f"oracle pyramidal_sgm(I0, I1, {n}){f' with a {median}x{median} median between levels' if median else ''}: outlier {out:.4f}, AEPE {aepe:.3f} px   (zero flow: {zo:.4f} / {za:.3f}); "
               f"pixels whose true flow is within the pyramid's reach of +-{reach} px ({near.sum() / valid.sum() * 100:.0f} % of the valid ones): "
               f"outlier {no:.4f}, AEPE {na:.3f}   [{time.time() - t0:.0f} s on one core]", flush=True)
 
