@@ -16,36 +16,58 @@ class PyramidParams(C.Structure):
                 ("totalPass", C.c_int32), ("adaptiveP2", C.c_int32), ("device", C.c_int32)]
 
 
+class NgPyramidParams(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("numPyd", "P1", "P2", "halfSearchWinSize", "aggSize", "subPixelRefine", "device")]
+
+
+_vp, _i32 = C.c_void_p, C.c_int32
+# The plan functions that both matchers have, as _Plan._call names them: (suffix, arguments after the plan, the one-shot entry
+# that came in the same build).  An older build behind FSGM_LIB_PATH has no "_ru" or no "_lm" entry and none of their rows.
+_PLAN_FUNCTIONS = (("upload_frame", [_i32, _vp, _vp], ""), ("download_frame", [_i32, _i32, _vp, _vp], ""), ("destroy", [], ""),
+                   ("level_size", [_i32, C.POINTER(_i32), C.POINTER(_i32)], ""), ("upload", [_vp, _vp], ""), ("run", [], ""),
+                   ("download", [_i32, _vp, _vp], ""), ("time", [_i32, _i32, C.POINTER(C.c_float)], ""),
+                   ("set_runner_up", [_i32], "_ru"), ("download_runner_up", [_i32, _vp], "_ru"), ("set_level_median", [_i32], "_lm"))
+
+
+def _bind_matcher(lib, plan, host, Params):
+    """What the two matchers declare alike: the plan functions `plan` + suffix and the one-shot entries `host`, `host`_ru, `host`_lm."""
+    prm = C.POINTER(Params)
+    getattr(lib, plan + "create").argtypes = [C.POINTER(_vp), _i32, _i32, _i32, prm]
+    getattr(lib, plan + "destroy").restype = None
+    images = [_vp, _vp, _i32, _i32, _i32, prm]
+    getattr(lib, host).argtypes = images + [_vp, _vp, _vp]
+    have = {"": True, "_ru": hasattr(lib, host + "_ru"), "_lm": hasattr(lib, host + "_lm")}
+    if have["_ru"]:
+        getattr(lib, host + "_ru").argtypes = images + [_vp, _vp, _vp, _vp]
+    if have["_lm"]:
+        getattr(lib, host + "_lm").argtypes = images + [_i32, _vp, _vp, _vp, _vp]
+    for suffix, argtypes, since in _PLAN_FUNCTIONS:
+        if have[since]:
+            getattr(lib, plan + suffix).argtypes = [_vp] + argtypes
+
+
 def _bind(lib):
     if getattr(lib, "_pyramid_bound", False):
         return
-    vp, i32 = C.c_void_p, C.c_int32
     lib.fsgm_pyramid_params_default.restype = PyramidParams
-    lib.fsgm_pyramidal_sgm_host.argtypes = [vp, vp, i32, i32, i32, C.POINTER(PyramidParams), vp, vp, vp]
-    lib.fsgm_pyramid_plan_create.argtypes = [C.POINTER(vp), i32, i32, i32, C.POINTER(PyramidParams)]
-    lib.fsgm_pyramid_plan_create_batch.argtypes = [C.POINTER(vp), i32, i32, i32, C.POINTER(PyramidParams), i32]
-    lib.fsgm_pyramid_plan_upload_frame.argtypes = [vp, i32, vp, vp]
-    lib.fsgm_pyramid_plan_download_frame.argtypes = [vp, i32, i32, vp, vp]
-    lib.fsgm_pyramid_plan_destroy.argtypes = [vp]
-    lib.fsgm_pyramid_plan_destroy.restype = None
-    lib.fsgm_pyramid_plan_level_size.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32)]
-    lib.fsgm_pyramid_plan_upload.argtypes = [vp, vp, vp]
-    lib.fsgm_pyramid_plan_run.argtypes = [vp]
-    lib.fsgm_pyramid_plan_run_images.argtypes = [vp]
-    lib.fsgm_pyramid_plan_sync.argtypes = [vp]
-    lib.fsgm_pyramid_plan_download.argtypes = [vp, i32, vp, vp]
-    lib.fsgm_pyramid_plan_download_gray.argtypes = [vp, i32, vp, vp]
-    lib.fsgm_pyramid_plan_download_gray_frame.argtypes = [vp, i32, i32, vp, vp]
-    lib.fsgm_pyramid_plan_time.argtypes = [vp, i32, i32, C.POINTER(C.c_float)]
-    if hasattr(lib, "fsgm_pyramidal_sgm_host_ru"):               # (an older build behind FSGM_LIB_PATH has none of these)
-        lib.fsgm_pyramidal_sgm_host_ru.argtypes = [vp, vp, i32, i32, i32, C.POINTER(PyramidParams), vp, vp, vp, vp]
-        lib.fsgm_pyramid_plan_set_runner_up.argtypes = [vp, i32]
-        lib.fsgm_pyramid_plan_download_runner_up.argtypes = [vp, i32, vp]
+    _bind_matcher(lib, "fsgm_pyramid_plan_", "fsgm_pyramidal_sgm_host", PyramidParams)
+    lib.fsgm_pyramid_plan_create_batch.argtypes = [C.POINTER(_vp), _i32, _i32, _i32, C.POINTER(PyramidParams), _i32]     # (prm, batch)
+    lib.fsgm_pyramid_plan_run_images.argtypes = [_vp]
+    lib.fsgm_pyramid_plan_sync.argtypes = [_vp]
+    lib.fsgm_pyramid_plan_download_gray.argtypes = [_vp, _i32, _vp, _vp]
+    lib.fsgm_pyramid_plan_download_gray_frame.argtypes = [_vp, _i32, _i32, _vp, _vp]
     if hasattr(lib, "fsgm_pyramidal_sgm_host_lm"):
-        lib.fsgm_pyramidal_sgm_host_lm.argtypes = [vp, vp, i32, i32, i32, C.POINTER(PyramidParams), i32, vp, vp, vp, vp]
-        lib.fsgm_pyramid_plan_set_level_median.argtypes = [vp, i32]
-        lib.fsgm_flow_level_hints_host.argtypes = [i32, vp, i32, i32, i32, vp, i32]
+        lib.fsgm_flow_level_hints_host.argtypes = [_i32, _vp, _i32, _i32, _i32, _vp, _i32]
     lib._pyramid_bound = True
+
+
+def _bind_ng(lib):
+    if getattr(lib, "_ng_pyramid_bound", False):
+        return
+    lib.fsgm_ng_pyramid_params_default.restype = NgPyramidParams
+    _bind_matcher(lib, "fsgm_ng_pyramid_plan_", "fsgm_pyramidal_sgm_ng_host", NgPyramidParams)
+    lib.fsgm_ng_pyramid_plan_create_batch.argtypes = [C.POINTER(_vp), _i32, _i32, _i32, _i32, C.POINTER(NgPyramidParams)]  # (batch, prm)
+    lib._ng_pyramid_bound = True
 
 
 def _params(default, numPyd, device, overrides, what):
@@ -106,16 +128,53 @@ def flow_level_hints(flow, size=3, *, device=0):
     return nxt
 
 
-def _minC2_of(out, H, W):
-    """the minC2 array of a runner-up call: the fourth member of out=, else a new one"""
-    if out is None:
-        return np.empty((H, W), np.uint32)
-    if len(out) != 4:
+def _entry(lib, plain, second, level_median, minC2, ratio=()):
+    """The C entry of a one-shot call, chosen by the newer switches: (function, its integers after the parameter struct, its minC2
+    argument after minC), the last two as tuples to splice into the plain entry's arguments.  With every switch off that is the
+    entry `plain` and nothing more, so such a call runs on an older build (FSGM_LIB_PATH) too; a runner-up cost alone -- minC2
+    an array -- takes `plain` + `second` ("_ru", or "_u" with the flow chain's `ratio` = (r,)); level_median takes "_lm", where
+    minC2 may be None (NULL)."""
+    if level_median:
+        return getattr(lib, plain + "_lm"), ratio + (level_median,), (ptr(minC2),)
+    if minC2 is not None:
+        return getattr(lib, plain + second), ratio, (ptr(minC2),)
+    return getattr(lib, plain), (), ()
+
+
+def _outputs(out, sizes, runner_up, coarsest_first):
+    """(mv, the per-level flows finest first, minC, minC2 or None) of a one-shot call: new arrays, or those of out=, a previous
+    call's result tuple (its level list coarsest first or not), when they are what this call writes."""
+    W, H = sizes[0]
+    if out is None:                                          # every element is written by the call
+        return (np.empty((2, H, W), np.float64), [np.empty((2, h, w), np.float64) for (w, h) in sizes], np.empty((H, W), np.uint32),
+                np.empty((H, W), np.uint32) if runner_up else None)
+    mv, levels, minC, *minC2 = out
+    if coarsest_first:
+        levels = list(levels)[::-1]
+    flows = [(mv, (W, H))] + list(zip(levels, sizes))
+    ok = (len(minC2) == (1 if runner_up else 0) and len(levels) == len(sizes)
+          and all(a.shape == (2, h, w) and a.dtype == np.float64 and a.flags.c_contiguous for a, (w, h) in flows)
+          and all(a.shape == (H, W) and a.dtype == np.uint32 and a.flags.c_contiguous for a in [minC] + minC2))
+    if not ok:
         raise ValueError("out does not match this call's shapes")
-    m2 = out[3]
-    if m2.shape != (H, W) or m2.dtype != np.uint32 or not m2.flags.c_contiguous:
-        raise ValueError("out does not match this call's shapes")
-    return m2
+    return mv, levels, minC, (minC2[0] if runner_up else None)
+
+
+def _one_shot(bind, default, stem, what, coarsest_first, I0, I1, numPyd, device, out, runner_up, level_median, overrides):
+    """pyramidal_sgm and pyramidal_sgm_ng: `stem` names the C entries (stem + "_host", "_host_ru", "_host_lm"), `default` the
+    function of the default parameters, `what` the call in messages; the level list is returned, and taken in out=, coarsest
+    first or finest first."""
+    level_median = level_median_of(level_median)
+    lib = _lib.load()
+    bind(lib)
+    I0, I1, ch = _check_images(I0, I1)
+    H, W = I0.shape[-2:]
+    prm = _params(getattr(lib, default), numPyd, device, overrides, what)
+    mv, levels, minC, minC2 = _outputs(out, _level_sizes(W, H, prm.numPyd), runner_up, coarsest_first)
+    ptrs = (C.c_void_p * len(levels))(*[a.ctypes.data for a in levels])
+    fn, switches, second = _entry(lib, stem + "_host", "_ru", level_median, minC2)
+    check(fn(ptr(I0), ptr(I1), W, H, ch, C.byref(prm), *switches, ptr(mv), ptr(minC), *second, ptrs))
+    return (mv, levels[::-1] if coarsest_first else levels, minC) + ((minC2,) if runner_up else ())
 
 
 def pyramidal_sgm(I0, I1, numPyd=5, *, device=0, out=None, runner_up=False, level_median=0, **overrides):
@@ -127,34 +186,8 @@ def pyramidal_sgm(I0, I1, numPyd=5, *, device=0, out=None, runner_up=False, leve
     over frames then hands the library pages that are already resident, as a MEX gateway's zero-filled outputs are.
     level_median=3 or 5: every level's flow is median-filtered (medfilt2 with that window, pyramidal_sgm.m:70-71 live) on its way to
     the next finer level's hints; the returned flows stay unfiltered.  It combines with runner_up."""
-    level_median = level_median_of(level_median)
-    lib = _lib.load()
-    _bind(lib)
-    I0, I1, ch = _check_images(I0, I1)
-    H, W = I0.shape[-2:]
-    prm = _params(lib.fsgm_pyramid_params_default, numPyd, device, overrides, "pyramidal_sgm")
-    sizes = _level_sizes(W, H, prm.numPyd)
-    minC2 = _minC2_of(out, H, W) if runner_up else None
-    if out is not None:
-        mv, mvPyd, minC = out[:3] if runner_up else out
-        ok = (mv.shape == (2, H, W) and mv.dtype == np.float64 and minC.shape == (H, W) and minC.dtype == np.uint32 and len(mvPyd) == len(sizes)
-              and all(a.shape == (2, h, w) and a.dtype == np.float64 and a.flags.c_contiguous for a, (w, h) in zip(mvPyd, sizes)))
-        if not ok or not mv.flags.c_contiguous or not minC.flags.c_contiguous:
-            raise ValueError("out does not match this call's shapes")
-    else:
-        mv = np.empty((2, H, W), np.float64)                 # every element is written by the call
-        minC = np.empty((H, W), np.uint32)
-        mvPyd = [np.empty((2, h, w), np.float64) for (w, h) in sizes]
-    ptrs = (C.c_void_p * len(mvPyd))(*[a.ctypes.data for a in mvPyd])
-    if level_median:
-        check(lib.fsgm_pyramidal_sgm_host_lm(ptr(I0), ptr(I1), W, H, ch, C.byref(prm), level_median, ptr(mv), ptr(minC),
-                                             ptr(minC2) if runner_up else None, ptrs))
-        return (mv, mvPyd, minC, minC2) if runner_up else (mv, mvPyd, minC)
-    if runner_up:
-        check(lib.fsgm_pyramidal_sgm_host_ru(ptr(I0), ptr(I1), W, H, ch, C.byref(prm), ptr(mv), ptr(minC), ptr(minC2), ptrs))
-        return mv, mvPyd, minC, minC2
-    check(lib.fsgm_pyramidal_sgm_host(ptr(I0), ptr(I1), W, H, ch, C.byref(prm), ptr(mv), ptr(minC), ptrs))
-    return mv, mvPyd, minC
+    return _one_shot(_bind, "fsgm_pyramid_params_default", "fsgm_pyramidal_sgm", "pyramidal_sgm", False, I0, I1, numPyd, device, out,
+                     runner_up, level_median, overrides)
 
 
 class PyramidPair(C.Structure):
@@ -299,37 +332,6 @@ class PyramidPlan(_Plan):
         return g0, g1
 
 
-class NgPyramidParams(C.Structure):
-    _fields_ = [(n, C.c_int32) for n in ("numPyd", "P1", "P2", "halfSearchWinSize", "aggSize", "subPixelRefine", "device")]
-
-
-def _bind_ng(lib):
-    if getattr(lib, "_ng_pyramid_bound", False):
-        return
-    vp, i32 = C.c_void_p, C.c_int32
-    lib.fsgm_ng_pyramid_params_default.restype = NgPyramidParams
-    lib.fsgm_ng_pyramid_plan_create.argtypes = [C.POINTER(vp), i32, i32, i32, C.POINTER(NgPyramidParams)]
-    lib.fsgm_ng_pyramid_plan_create_batch.argtypes = [C.POINTER(vp), i32, i32, i32, i32, C.POINTER(NgPyramidParams)]
-    lib.fsgm_ng_pyramid_plan_upload_frame.argtypes = [vp, i32, vp, vp]
-    lib.fsgm_ng_pyramid_plan_download_frame.argtypes = [vp, i32, i32, vp, vp]
-    lib.fsgm_ng_pyramid_plan_destroy.argtypes = [vp]
-    lib.fsgm_ng_pyramid_plan_destroy.restype = None
-    lib.fsgm_ng_pyramid_plan_level_size.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32)]
-    lib.fsgm_ng_pyramid_plan_upload.argtypes = [vp, vp, vp]
-    lib.fsgm_ng_pyramid_plan_run.argtypes = [vp]
-    lib.fsgm_ng_pyramid_plan_download.argtypes = [vp, i32, vp, vp]
-    lib.fsgm_ng_pyramid_plan_time.argtypes = [vp, i32, i32, C.POINTER(C.c_float)]
-    lib.fsgm_pyramidal_sgm_ng_host.argtypes = [vp, vp, i32, i32, i32, C.POINTER(NgPyramidParams), vp, vp, vp]
-    if hasattr(lib, "fsgm_pyramidal_sgm_ng_host_ru"):            # (an older build behind FSGM_LIB_PATH has none of these)
-        lib.fsgm_pyramidal_sgm_ng_host_ru.argtypes = [vp, vp, i32, i32, i32, C.POINTER(NgPyramidParams), vp, vp, vp, vp]
-        lib.fsgm_ng_pyramid_plan_set_runner_up.argtypes = [vp, i32]
-        lib.fsgm_ng_pyramid_plan_download_runner_up.argtypes = [vp, i32, vp]
-    if hasattr(lib, "fsgm_pyramidal_sgm_ng_host_lm"):
-        lib.fsgm_pyramidal_sgm_ng_host_lm.argtypes = [vp, vp, i32, i32, i32, C.POINTER(NgPyramidParams), i32, vp, vp, vp, vp]
-        lib.fsgm_ng_pyramid_plan_set_level_median.argtypes = [vp, i32]
-    lib._ng_pyramid_bound = True
-
-
 class NgPyramidPlan(_Plan):
     """Device-resident level loop around calc_pyd_cost_sgm_ng for one image shape (see pyramidal_sgm_ng); `batch` image
     pairs stay resident and go through every level together."""
@@ -365,35 +367,8 @@ def pyramidal_sgm_ng(I0, I1, numPyd=3, *, device=0, out=None, runner_up=False, l
 
     Returns (flow of level 1, [flow per level, coarsest first], minC of level 1); with runner_up=True also minC2 of level 1,
     the neighbour-guided runner-up cost of include/fsgm.h.  level_median=3 or 5: the median between levels of pyramidal_sgm."""
-    level_median = level_median_of(level_median)
-    lib = _lib.load()
-    _bind_ng(lib)
-    I0, I1, ch = _check_images(I0, I1)
-    H, W = I0.shape[-2:]
-    prm = _params(lib.fsgm_ng_pyramid_params_default, numPyd, device, overrides, "pyramidal_sgm_ng")
-    sizes = _level_sizes(W, H, prm.numPyd)
-    minC2 = _minC2_of(out, H, W) if runner_up else None
-    if out is not None:                                      # a previous call's result tuple, overwritten (see pyramidal_sgm)
-        flow, lv, minC = out[:3] if runner_up else out
-        lv = list(lv)[::-1]                                  # returned coarsest first, filled finest first
-        ok = (flow.shape == (2, H, W) and flow.dtype == np.float64 and minC.shape == (H, W) and minC.dtype == np.uint32 and len(lv) == len(sizes)
-              and all(a.shape == (2, h, w) and a.dtype == np.float64 and a.flags.c_contiguous for a, (w, h) in zip(lv, sizes)))
-        if not ok or not flow.flags.c_contiguous or not minC.flags.c_contiguous:
-            raise ValueError("out does not match this call's shapes")
-    else:
-        flow = np.empty((2, H, W), np.float64)
-        minC = np.empty((H, W), np.uint32)
-        lv = [np.empty((2, h, w), np.float64) for (w, h) in sizes]
-    ptrs = (C.c_void_p * len(lv))(*[a.ctypes.data for a in lv])
-    if level_median:
-        check(lib.fsgm_pyramidal_sgm_ng_host_lm(ptr(I0), ptr(I1), W, H, ch, C.byref(prm), level_median, ptr(flow), ptr(minC),
-                                                ptr(minC2) if runner_up else None, ptrs))
-        return (flow, lv[::-1], minC, minC2) if runner_up else (flow, lv[::-1], minC)
-    if runner_up:
-        check(lib.fsgm_pyramidal_sgm_ng_host_ru(ptr(I0), ptr(I1), W, H, ch, C.byref(prm), ptr(flow), ptr(minC), ptr(minC2), ptrs))
-        return flow, lv[::-1], minC, minC2
-    check(lib.fsgm_pyramidal_sgm_ng_host(ptr(I0), ptr(I1), W, H, ch, C.byref(prm), ptr(flow), ptr(minC), ptrs))
-    return flow, lv[::-1], minC
+    return _one_shot(_bind_ng, "fsgm_ng_pyramid_params_default", "fsgm_pyramidal_sgm_ng", "pyramidal_sgm_ng", True, I0, I1, numPyd, device,
+                     out, runner_up, level_median, overrides)
 
 
 class FlowPPParams(C.Structure):
@@ -495,21 +470,11 @@ def pyramidal_flow_pp(I0, I1, numPyd=None, matcher="pyd", *, median=0, batch=Non
     pp = np.empty((N, 3, H, W), np.float64)
     checked, fwd, bwd = (np.empty((N, 2, H, W), np.float64) for _ in range(3))
     minC = np.empty((N, H, W), np.uint32)
-    if level_median:
-        minC2 = np.empty((N, H, W), np.uint32) if uniqueness_ratio is not None else None
-        ratio = uniqueness_ratio_of(uniqueness_ratio) if uniqueness_ratio is not None else 0
-        check(lib.fsgm_pyramidal_flow_pp_host_lm(N, ptr(I0), ptr(I1), W, H, ch, C.byref(prm), ratio, level_median, ptr(pp), ptr(checked),
-                                                 ptr(fwd), ptr(bwd), ptr(minC), ptr(minC2) if minC2 is not None else None))
-        outs = (pp, checked, fwd, bwd, minC) + ((minC2,) if minC2 is not None else ())
-        return outs if batched else tuple(o[0] for o in outs)
-    if uniqueness_ratio is not None:
-        minC2 = np.empty((N, H, W), np.uint32)
-        check(lib.fsgm_pyramidal_flow_pp_host_u(N, ptr(I0), ptr(I1), W, H, ch, C.byref(prm), uniqueness_ratio_of(uniqueness_ratio), ptr(pp),
-                                                ptr(checked), ptr(fwd), ptr(bwd), ptr(minC), ptr(minC2)))
-        outs = (pp, checked, fwd, bwd, minC, minC2)
-        return outs if batched else tuple(o[0] for o in outs)
-    check(lib.fsgm_pyramidal_flow_pp_host(N, ptr(I0), ptr(I1), W, H, ch, C.byref(prm), ptr(pp), ptr(checked), ptr(fwd), ptr(bwd), ptr(minC)))
-    outs = (pp, checked, fwd, bwd, minC)
+    minC2 = np.empty((N, H, W), np.uint32) if uniqueness_ratio is not None else None
+    ratio = (uniqueness_ratio_of(uniqueness_ratio) if uniqueness_ratio is not None else 0,)
+    fn, switches, second = _entry(lib, "fsgm_pyramidal_flow_pp_host", "_u", level_median, minC2, ratio)
+    check(fn(N, ptr(I0), ptr(I1), W, H, ch, C.byref(prm), *switches, ptr(pp), ptr(checked), ptr(fwd), ptr(bwd), ptr(minC), *second))
+    outs = (pp, checked, fwd, bwd, minC) + ((minC2,) if minC2 is not None else ())
     return outs if batched else tuple(o[0] for o in outs)
 
 

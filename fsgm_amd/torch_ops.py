@@ -154,10 +154,27 @@ def _geometries(geometry, N):
 # ---------------------------------------------------------------------------------------------
 # custom ops: every tensor argument is batched (leading N) and on one GPU; outputs freshly allocated there.  Each op's
 # outputs are stated once, in an _*_outputs function of the input shapes and flags that its body and its fake both call.
+# The ops of one family (a matcher and its _ru / _exact / _u / _lm forms) share one body, an _*_run function that takes the C
+# entry: an op function carries the schema -- torch derives it from the annotated signature -- names its own entry and says how
+# the entry treats the runner-up cost, `minC2`: None -- the entry has no such argument and the op no such output; True -- a full
+# map after minC; False -- the entry is handed NULL there and the op returns an empty (0,) placeholder.  An entry is looked up
+# when its op runs, so a call with the newer switches off touches no newer symbol (an older build behind FSGM_LIB_PATH).
 # ---------------------------------------------------------------------------------------------
 def _frames(t):
     """(N, H, W, device) of a batch of maps (N, H, W) or images (N, H, W) / (N, 3, H, W)."""
     return t.shape[0], t.shape[-2], t.shape[-1], t.device
+
+
+def _minC2_output(minC, minC2):
+    """the minC2 slot of an op's outputs, as a tuple to splice in after minC: nothing, a map like minC, or the placeholder"""
+    if minC2 is None:
+        return ()
+    return (torch.empty_like(minC) if minC2 else _u32((0,), minC.device),)
+
+
+def _minC2_arg(slot, minC2):
+    """the same slot as the C entry's arguments: nothing, the map's address, or NULL"""
+    return tuple(_p(t) if minC2 else None for t in slot)
 
 
 def _fb_outputs(N, H, W, fb_check, dev, dtype=torch.uint32):
@@ -220,41 +237,61 @@ def _(I1, I2, pd0, nd, dMax, P1, P2, paths, subpixel, fb_check, adaptive_p2=0):
     return _matcher_outputs(I1, fb_check)
 
 
+def _stereo_outputs(left, fb_check, ranged, minC2=None):
+    """(disp, minC[, minC2], conf, disp2, status); disp / disp2 int32 true disparities for the entries that take d_min, else uint32"""
+    disp, minC, conf, disp2, status = _matcher_outputs(left, fb_check, torch.int32 if ranged else torch.uint32)
+    return (disp, minC) + _minC2_output(minC, minC2) + (conf, disp2, status)
+
+
+def _stereo_run(fn, left, right, dMax, P1, P2, paths, subpixel, direction, fb_check, adaptive_p2, *, d_min=None, minC2=None):
+    """d_min: None for the entry without that argument (fsgm_stereo_sgm_device_opts)"""
+    N, H, W, dev = _frames(left)
+    left, right = _ready(left), _ready(right)
+    disp, minC, *slot, conf, disp2, status = _stereo_outputs(left, fb_check, d_min is not None, minC2)
+    prm = _stereo_params(paths, subpixel, direction, fb_check, dev.index)
+    opt = _lib.options(adaptive_p2)
+    _call(dev, fn, N, _p(left), _p(right), W, H, int(dMax), int(P1), int(P2), C.byref(prm), C.byref(opt),
+          *(() if d_min is None else (int(d_min),)), _p(disp), _p(minC), *_minC2_arg(slot, minC2), _p(conf) if fb_check else None,
+          _p(disp2) if fb_check else None, _stream(dev), _p(status))
+    return (disp, minC, *slot, conf, disp2, status)
+
+
 @torch.library.custom_op("fsgm::stereo_sgm", mutates_args=())
 def _stereo_sgm_op(left: torch.Tensor, right: torch.Tensor, dMax: int, P1: int, P2: int, paths: int, subpixel: int, direction: int,
                    fb_check: int, adaptive_p2: int = 0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
-    N, H, W, dev = _frames(left)
-    left, right = _ready(left), _ready(right)
-    disp, minC, conf, disp2, status = _matcher_outputs(left, fb_check)
-    prm = _stereo_params(paths, subpixel, direction, fb_check, dev.index)
-    opt = _lib.options(adaptive_p2)
-    _call(dev, _L.fsgm_stereo_sgm_device_opts, N, _p(left), _p(right), W, H, int(dMax), int(P1), int(P2), C.byref(prm), C.byref(opt),
-          _p(disp), _p(minC), _p(conf) if fb_check else None, _p(disp2) if fb_check else None, _stream(dev), _p(status))
-    return disp, minC, conf, disp2, status
+    return _stereo_run(_L.fsgm_stereo_sgm_device_opts, left, right, dMax, P1, P2, paths, subpixel, direction, fb_check, adaptive_p2)
 
 
 @_stereo_sgm_op.register_fake
 def _(left, right, dMax, P1, P2, paths, subpixel, direction, fb_check, adaptive_p2=0):
-    return _matcher_outputs(left, fb_check)
+    return _stereo_outputs(left, fb_check, False)
 
 
 @torch.library.custom_op("fsgm::stereo_sgm_range", mutates_args=())
 def _stereo_sgm_range_op(left: torch.Tensor, right: torch.Tensor, dMax: int, d_min: int, P1: int, P2: int, paths: int, subpixel: int,
                          direction: int, fb_check: int,
                          adaptive_p2: int = 0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
-    N, H, W, dev = _frames(left)
-    left, right = _ready(left), _ready(right)
-    disp, minC, conf, disp2, status = _matcher_outputs(left, fb_check, torch.int32)
-    prm = _stereo_params(paths, subpixel, direction, fb_check, dev.index)
-    opt = _lib.options(adaptive_p2)
-    _call(dev, _L.fsgm_stereo_sgm_device_range, N, _p(left), _p(right), W, H, int(dMax), int(P1), int(P2), C.byref(prm), C.byref(opt),
-          int(d_min), _p(disp), _p(minC), _p(conf) if fb_check else None, _p(disp2) if fb_check else None, _stream(dev), _p(status))
-    return disp, minC, conf, disp2, status
+    return _stereo_run(_L.fsgm_stereo_sgm_device_range, left, right, dMax, P1, P2, paths, subpixel, direction, fb_check, adaptive_p2,
+                       d_min=d_min)
 
 
 @_stereo_sgm_range_op.register_fake
 def _(left, right, dMax, d_min, P1, P2, paths, subpixel, direction, fb_check, adaptive_p2=0):
-    return _matcher_outputs(left, fb_check, torch.int32)
+    return _stereo_outputs(left, fb_check, True)
+
+
+@torch.library.custom_op("fsgm::stereo_sgm_ru", mutates_args=())
+def _stereo_sgm_ru_op(left: torch.Tensor, right: torch.Tensor, dMax: int, d_min: int, P1: int, P2: int, paths: int, subpixel: int,
+                      direction: int, fb_check: int, adaptive_p2: int = 0
+                      ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """fsgm::stereo_sgm_range with the runner-up cost minC2 after minC (fsgm_stereo_sgm_device_ru)"""
+    return _stereo_run(_L.fsgm_stereo_sgm_device_ru, left, right, dMax, P1, P2, paths, subpixel, direction, fb_check, adaptive_p2,
+                       d_min=d_min, minC2=True)
+
+
+@_stereo_sgm_ru_op.register_fake
+def _(left, right, dMax, d_min, P1, P2, paths, subpixel, direction, fb_check, adaptive_p2=0):
+    return _stereo_outputs(left, fb_check, True, True)
 
 
 def _sgm_out_shape(C_, layout):
@@ -264,26 +301,32 @@ def _sgm_out_shape(C_, layout):
     return (N, a, b, c) if layout == 0 else (N, b, c, a)
 
 
-def _sgm_outputs(C_, layout, return_sum):
+def _sgm_outputs(C_, layout, return_sum, minC2=None):
+    """(bestD, minC[, minC2], S, status); S is empty unless return_sum"""
     N, H, W, D = _sgm_out_shape(C_, layout)
     dev = C_.device
-    return _u32((N, H, W), dev), _u32((N, H, W), dev), _u32((N, H, W, D) if return_sum else (0,), dev), _status(dev)
+    minC = _u32((N, H, W), dev)
+    return (_u32((N, H, W), dev), minC) + _minC2_output(minC, minC2) + (_u32((N, H, W, D) if return_sum else (0,), dev), _status(dev))
+
+
+def _sgm_run(fn, C_, guide, P1, P2, paths, layout, cost_bound, agg_mode, adaptive_p2, subpixel, return_sum, minC2=None):
+    N, H, W, D = _sgm_out_shape(C_, layout)
+    dev = C_.device
+    C_ = C_.contiguous()                                  # (any byte offset will do: the ingest kernel assumes no alignment)
+    guide = guide.contiguous() if adaptive_p2 else None
+    bestD, minC, *slot, S, status = _sgm_outputs(C_, layout, return_sum, minC2)
+    prm = _sgm_params(_L, paths=paths, subpixel=subpixel, device=dev.index, agg_mode=agg_mode, layout="dhw" if layout else "hwd",
+                      cost_bound=cost_bound, adaptive_p2=adaptive_p2)
+    _call(dev, fn, N, _p(C_), W, H, D, int(P1), int(P2), C.byref(prm), _p(guide), _p(bestD), _p(minC), *_minC2_arg(slot, minC2),
+          _p(S) if return_sum else None, _stream(dev), _p(status))
+    return (bestD, minC, *slot, S, status)
 
 
 @torch.library.custom_op("fsgm::sgm", mutates_args=())
 def _sgm_op(C_: torch.Tensor, guide: torch.Tensor, P1: int, P2: int, paths: int, layout: int, cost_bound: int, agg_mode: int,
             adaptive_p2: int, subpixel: int, return_sum: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
     """C_ (N, H, W, D) for layout 0 or (N, D, H, W) for layout 1; guide (N, H, W), read with adaptive_p2 only."""
-    N, H, W, D = _sgm_out_shape(C_, layout)
-    dev = C_.device
-    C_ = C_.contiguous()                                  # (any byte offset will do: the ingest kernel assumes no alignment)
-    guide = guide.contiguous() if adaptive_p2 else None
-    bestD, minC, S, status = _sgm_outputs(C_, layout, return_sum)
-    prm = _sgm_params(_L, paths=paths, subpixel=subpixel, device=dev.index, agg_mode=agg_mode, layout="dhw" if layout else "hwd",
-                      cost_bound=cost_bound, adaptive_p2=adaptive_p2)
-    _call(dev, _L.fsgm_sgm_device, N, _p(C_), W, H, D, int(P1), int(P2), C.byref(prm), _p(guide), _p(bestD), _p(minC),
-          _p(S) if return_sum else None, _stream(dev), _p(status))
-    return bestD, minC, S, status
+    return _sgm_run(_L.fsgm_sgm_device, C_, guide, P1, P2, paths, layout, cost_bound, agg_mode, adaptive_p2, subpixel, return_sum)
 
 
 @_sgm_op.register_fake
@@ -295,16 +338,7 @@ def _(C_, guide, P1, P2, paths, layout, cost_bound, agg_mode, adaptive_p2, subpi
 def _sgm_exact_op(C_: torch.Tensor, guide: torch.Tensor, P1: int, P2: int, paths: int, layout: int, cost_bound: int, agg_mode: int,
                   adaptive_p2: int, subpixel: int, return_sum: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
     """fsgm::sgm with exact path arithmetic (fsgm_sgm_device_exact): P1, P2 in 0..255, the line kernels at every batch size"""
-    N, H, W, D = _sgm_out_shape(C_, layout)
-    dev = C_.device
-    C_ = C_.contiguous()
-    guide = guide.contiguous() if adaptive_p2 else None
-    bestD, minC, S, status = _sgm_outputs(C_, layout, return_sum)
-    prm = _sgm_params(_L, paths=paths, subpixel=subpixel, device=dev.index, agg_mode=agg_mode, layout="dhw" if layout else "hwd",
-                      cost_bound=cost_bound, adaptive_p2=adaptive_p2)
-    _call(dev, _L.fsgm_sgm_device_exact, N, _p(C_), W, H, D, int(P1), int(P2), C.byref(prm), _p(guide), _p(bestD), _p(minC),
-          _p(S) if return_sum else None, _stream(dev), _p(status))
-    return bestD, minC, S, status
+    return _sgm_run(_L.fsgm_sgm_device_exact, C_, guide, P1, P2, paths, layout, cost_bound, agg_mode, adaptive_p2, subpixel, return_sum)
 
 
 @_sgm_exact_op.register_fake
@@ -317,23 +351,12 @@ def _sgm_ru_op(C_: torch.Tensor, guide: torch.Tensor, P1: int, P2: int, paths: i
                adaptive_p2: int, subpixel: int, return_sum: int
                ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
     """fsgm::sgm with the runner-up cost minC2 after minC (fsgm_sgm_device_ru): (bestD, minC, minC2, S, status)"""
-    N, H, W, D = _sgm_out_shape(C_, layout)
-    dev = C_.device
-    C_ = C_.contiguous()
-    guide = guide.contiguous() if adaptive_p2 else None
-    bestD, minC, S, status = _sgm_outputs(C_, layout, return_sum)
-    minC2 = torch.empty_like(minC)
-    prm = _sgm_params(_L, paths=paths, subpixel=subpixel, device=dev.index, agg_mode=agg_mode, layout="dhw" if layout else "hwd",
-                      cost_bound=cost_bound, adaptive_p2=adaptive_p2)
-    _call(dev, _L.fsgm_sgm_device_ru, N, _p(C_), W, H, D, int(P1), int(P2), C.byref(prm), _p(guide), _p(bestD), _p(minC), _p(minC2),
-          _p(S) if return_sum else None, _stream(dev), _p(status))
-    return bestD, minC, minC2, S, status
+    return _sgm_run(_L.fsgm_sgm_device_ru, C_, guide, P1, P2, paths, layout, cost_bound, agg_mode, adaptive_p2, subpixel, return_sum, True)
 
 
 @_sgm_ru_op.register_fake
 def _(C_, guide, P1, P2, paths, layout, cost_bound, agg_mode, adaptive_p2, subpixel, return_sum):
-    bestD, minC, S, status = _sgm_outputs(C_, layout, return_sum)
-    return bestD, minC, torch.empty_like(minC), S, status
+    return _sgm_outputs(C_, layout, return_sum, True)
 
 
 def _sgm2d_out_shape(C_, layout, half_x, half_y):
@@ -345,11 +368,37 @@ def _sgm2d_out_shape(C_, layout, half_x, half_y):
     return n, H, W, D
 
 
-def _sgm2d_outputs(C_, layout, half_x, half_y, return_flow, return_sum):
+def _sgm2d_outputs(C_, layout, half_x, half_y, return_flow, return_sum, minC2=None):
+    """(bestD, minC[, minC2], mvSub, flow, S, status); flow / S are empty unless asked for"""
     N, H, W, D = _sgm2d_out_shape(C_, layout, half_x, half_y)
     dev = C_.device
-    return (_u32((N, H, W), dev), _u32((N, H, W), dev), _f64((N, 2, H, W), dev), _f64((N, 2, H, W) if return_flow else (0,), dev),
-            _u32((N, H, W, D) if return_sum else (0,), dev), _status(dev))
+    minC = _u32((N, H, W), dev)
+    return ((_u32((N, H, W), dev), minC) + _minC2_output(minC, minC2)
+            + (_f64((N, 2, H, W), dev), _f64((N, 2, H, W) if return_flow else (0,), dev), _u32((N, H, W, D) if return_sum else (0,), dev),
+               _status(dev)))
+
+
+_LAYOUT2D_NAMES = {code: name for name, code in _LAYOUTS2D.items()}
+
+
+def _sgm2d_run(fn, who, C_, hints, guide, half_x, half_y, P1, P2, layout, cost_bound, diagonal, total_pass, adaptive_p2, subpixel,
+               return_flow, return_sum, minC2=None):
+    """who: the op's name, for the one message that carries it"""
+    N, H, W, D = _sgm2d_out_shape(C_, layout, half_x, half_y)
+    dev = C_.device
+    if not C_.is_contiguous():                            # (any byte offset will do: the ingest kernels assume no alignment)
+        raise TypeError(f"fsgm::{who} reads the costs where they lie: pass a contiguous tensor")
+    have_hints = hints.numel() != 0
+    hints = _ready(hints) if have_hints else None
+    mvH, mvW = (hints.shape[-2], hints.shape[-1]) if have_hints else (0, 0)
+    guide = guide.contiguous() if adaptive_p2 else None
+    bestD, minC, *slot, mvSub, flow, S, status = _sgm2d_outputs(C_, layout, half_x, half_y, return_flow, return_sum, minC2)
+    prm = _sgm2d_params(_L, diagonal=diagonal, total_pass=total_pass, adaptive_p2=adaptive_p2, subpixel=subpixel, device=dev.index,
+                        layout=_LAYOUT2D_NAMES[layout], cost_bound=cost_bound)
+    _call(dev, fn, N, _p(C_), W, H, int(half_x), int(half_y), int(P1), int(P2), C.byref(prm), _p(hints), int(mvW), int(mvH), _p(guide),
+          _p(bestD), _p(minC), *_minC2_arg(slot, minC2), _p(mvSub), _p(flow) if return_flow else None, _p(S) if return_sum else None,
+          _stream(dev), _p(status))
+    return (bestD, minC, *slot, mvSub, flow, S, status)
 
 
 @torch.library.custom_op("fsgm::sgm2d", mutates_args=())
@@ -358,21 +407,8 @@ def _sgm2d_op(C_: torch.Tensor, hints: torch.Tensor, guide: torch.Tensor, half_x
               return_sum: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
     """C_ (N, H, W, D) for layout 0, (N, D, H, W) for 1 (channel sx*Sy + sy) and 2 (channel sy*Sx + sx); hints (N, 2, mvH, mvW)
     float64 or empty (zero hints); guide (N, H, W), read with adaptive_p2 only.  flow / S are empty unless asked for."""
-    N, H, W, D = _sgm2d_out_shape(C_, layout, half_x, half_y)
-    dev = C_.device
-    if not C_.is_contiguous():                            # (any byte offset will do: the ingest kernels assume no alignment)
-        raise TypeError("fsgm::sgm2d reads the costs where they lie: pass a contiguous tensor")
-    have_hints = hints.numel() != 0
-    hints = _ready(hints) if have_hints else None
-    mvH, mvW = (hints.shape[-2], hints.shape[-1]) if have_hints else (0, 0)
-    guide = guide.contiguous() if adaptive_p2 else None
-    bestD, minC, mvSub, flow, S, status = _sgm2d_outputs(C_, layout, half_x, half_y, return_flow, return_sum)
-    prm = _sgm2d_params(_L, diagonal=diagonal, total_pass=total_pass, adaptive_p2=adaptive_p2, subpixel=subpixel, device=dev.index,
-                        layout=[k for k, v in _LAYOUTS2D.items() if v == layout][0], cost_bound=cost_bound)
-    _call(dev, _L.fsgm_sgm2d_device, N, _p(C_), W, H, int(half_x), int(half_y), int(P1), int(P2), C.byref(prm), _p(hints), int(mvW),
-          int(mvH), _p(guide), _p(bestD), _p(minC), _p(mvSub), _p(flow) if return_flow else None, _p(S) if return_sum else None,
-          _stream(dev), _p(status))
-    return bestD, minC, mvSub, flow, S, status
+    return _sgm2d_run(_L.fsgm_sgm2d_device, "sgm2d", C_, hints, guide, half_x, half_y, P1, P2, layout, cost_bound, diagonal, total_pass,
+                      adaptive_p2, subpixel, return_flow, return_sum)
 
 
 @_sgm2d_op.register_fake
@@ -385,28 +421,13 @@ def _sgm2d_ru_op(C_: torch.Tensor, hints: torch.Tensor, guide: torch.Tensor, hal
                  cost_bound: int, diagonal: int, total_pass: int, adaptive_p2: int, subpixel: int, return_flow: int, return_sum: int
                  ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
     """fsgm::sgm2d with the runner-up cost minC2 after minC (fsgm_sgm2d_device_ru): (bestD, minC, minC2, mvSub, flow, S, status)"""
-    N, H, W, D = _sgm2d_out_shape(C_, layout, half_x, half_y)
-    dev = C_.device
-    if not C_.is_contiguous():
-        raise TypeError("fsgm::sgm2d_ru reads the costs where they lie: pass a contiguous tensor")
-    have_hints = hints.numel() != 0
-    hints = _ready(hints) if have_hints else None
-    mvH, mvW = (hints.shape[-2], hints.shape[-1]) if have_hints else (0, 0)
-    guide = guide.contiguous() if adaptive_p2 else None
-    bestD, minC, mvSub, flow, S, status = _sgm2d_outputs(C_, layout, half_x, half_y, return_flow, return_sum)
-    minC2 = torch.empty_like(minC)
-    prm = _sgm2d_params(_L, diagonal=diagonal, total_pass=total_pass, adaptive_p2=adaptive_p2, subpixel=subpixel, device=dev.index,
-                        layout=[k for k, v in _LAYOUTS2D.items() if v == layout][0], cost_bound=cost_bound)
-    _call(dev, _L.fsgm_sgm2d_device_ru, N, _p(C_), W, H, int(half_x), int(half_y), int(P1), int(P2), C.byref(prm), _p(hints), int(mvW),
-          int(mvH), _p(guide), _p(bestD), _p(minC), _p(minC2), _p(mvSub), _p(flow) if return_flow else None,
-          _p(S) if return_sum else None, _stream(dev), _p(status))
-    return bestD, minC, minC2, mvSub, flow, S, status
+    return _sgm2d_run(_L.fsgm_sgm2d_device_ru, "sgm2d_ru", C_, hints, guide, half_x, half_y, P1, P2, layout, cost_bound, diagonal, total_pass,
+                      adaptive_p2, subpixel, return_flow, return_sum, True)
 
 
 @_sgm2d_ru_op.register_fake
 def _(C_, hints, guide, half_x, half_y, P1, P2, layout, cost_bound, diagonal, total_pass, adaptive_p2, subpixel, return_flow, return_sum):
-    bestD, minC, mvSub, flow, S, status = _sgm2d_outputs(C_, layout, half_x, half_y, return_flow, return_sum)
-    return bestD, minC, torch.empty_like(minC), mvSub, flow, S, status
+    return _sgm2d_outputs(C_, layout, half_x, half_y, return_flow, return_sum, True)
 
 
 @torch.library.custom_op("fsgm::sgm2d_exact", mutates_args=())
@@ -415,29 +436,14 @@ def _sgm2d_exact_op(C_: torch.Tensor, hints: torch.Tensor, guide: torch.Tensor, 
                     runner_up: bool
                     ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
     """fsgm::sgm2d_ru with exact path arithmetic (fsgm_sgm2d_device_exact): P1, P2 in 0..255; minC2 is empty unless runner_up"""
-    N, H, W, D = _sgm2d_out_shape(C_, layout, half_x, half_y)
-    dev = C_.device
-    if not C_.is_contiguous():
-        raise TypeError("fsgm::sgm2d_exact reads the costs where they lie: pass a contiguous tensor")
-    have_hints = hints.numel() != 0
-    hints = _ready(hints) if have_hints else None
-    mvH, mvW = (hints.shape[-2], hints.shape[-1]) if have_hints else (0, 0)
-    guide = guide.contiguous() if adaptive_p2 else None
-    bestD, minC, mvSub, flow, S, status = _sgm2d_outputs(C_, layout, half_x, half_y, return_flow, return_sum)
-    minC2 = torch.empty_like(minC) if runner_up else _u32((0,), dev)
-    prm = _sgm2d_params(_L, diagonal=diagonal, total_pass=total_pass, adaptive_p2=adaptive_p2, subpixel=subpixel, device=dev.index,
-                        layout=[k for k, v in _LAYOUTS2D.items() if v == layout][0], cost_bound=cost_bound)
-    _call(dev, _L.fsgm_sgm2d_device_exact, N, _p(C_), W, H, int(half_x), int(half_y), int(P1), int(P2), C.byref(prm), _p(hints), int(mvW),
-          int(mvH), _p(guide), _p(bestD), _p(minC), _p(minC2) if runner_up else None, _p(mvSub), _p(flow) if return_flow else None,
-          _p(S) if return_sum else None, _stream(dev), _p(status))
-    return bestD, minC, minC2, mvSub, flow, S, status
+    return _sgm2d_run(_L.fsgm_sgm2d_device_exact, "sgm2d_exact", C_, hints, guide, half_x, half_y, P1, P2, layout, cost_bound, diagonal,
+                      total_pass, adaptive_p2, subpixel, return_flow, return_sum, bool(runner_up))
 
 
 @_sgm2d_exact_op.register_fake
 def _(C_, hints, guide, half_x, half_y, P1, P2, layout, cost_bound, diagonal, total_pass, adaptive_p2, subpixel, return_flow, return_sum,
       runner_up):
-    bestD, minC, mvSub, flow, S, status = _sgm2d_outputs(C_, layout, half_x, half_y, return_flow, return_sum)
-    return bestD, minC, torch.empty_like(minC) if runner_up else _u32((0,), C_.device), mvSub, flow, S, status
+    return _sgm2d_outputs(C_, layout, half_x, half_y, return_flow, return_sum, bool(runner_up))
 
 
 def _epipolar_sgm_of_outputs(I0):
@@ -445,18 +451,27 @@ def _epipolar_sgm_of_outputs(I0):
     return _f64((N, 3, H, W), dev), _u32((N, H, W), dev), _status(dev)
 
 
-@torch.library.custom_op("fsgm::epipolar_sgm_of", mutates_args=())
-def _epipolar_sgm_of_op(I0: torch.Tensor, I1: torch.Tensor, geometry: List[float], dMax: int, vMax: float,
-                        paths: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+def _epipolar_flow_pp_outputs(I0):
+    N, H, W, dev = _frames(I0)
+    return _f64((N, 3, H, W), dev), _f64((N, 3, H, W), dev), _f64((N, H, W), dev), _u32((N, H, W), dev), _status(dev)
+
+
+def _epipolar_run(fn, outputs, vz_to_disp, I0, I1, geometry, dMax, vMax, paths):
+    """The epipolar drivers: `outputs` (I0) are the maps the entry writes, in its argument order, and the status"""
     N, H, W, dev = _frames(I0)
     ch = 1 if I0.dim() == 3 else 3
     g = _geometries(geometry, N)
     I0, I1 = _ready(I0), _ready(I1)
-    flow, minC, status = _epipolar_sgm_of_outputs(I0)
-    prm = _epi_params(paths, 1, 1, dev.index, 0)
-    _call(dev, _L.fsgm_epipolar_sgm_of_device, N, _p(I0), _p(I1), W, H, ch, g, int(dMax), float(vMax), C.byref(prm),
-          _p(flow), _p(minC), _stream(dev), _p(status))
-    return flow, minC, status
+    *maps, status = outputs(I0)
+    prm = _epi_params(paths, 1, vz_to_disp, dev.index, 0)
+    _call(dev, fn, N, _p(I0), _p(I1), W, H, ch, g, int(dMax), float(vMax), C.byref(prm), *(_p(m) for m in maps), _stream(dev), _p(status))
+    return (*maps, status)
+
+
+@torch.library.custom_op("fsgm::epipolar_sgm_of", mutates_args=())
+def _epipolar_sgm_of_op(I0: torch.Tensor, I1: torch.Tensor, geometry: List[float], dMax: int, vMax: float,
+                        paths: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    return _epipolar_run(_L.fsgm_epipolar_sgm_of_device, _epipolar_sgm_of_outputs, 1, I0, I1, geometry, dMax, vMax, paths)
 
 
 @_epipolar_sgm_of_op.register_fake
@@ -464,23 +479,10 @@ def _(I0, I1, geometry, dMax, vMax, paths):
     return _epipolar_sgm_of_outputs(I0)
 
 
-def _epipolar_flow_pp_outputs(I0):
-    N, H, W, dev = _frames(I0)
-    return _f64((N, 3, H, W), dev), _f64((N, 3, H, W), dev), _f64((N, H, W), dev), _u32((N, H, W), dev), _status(dev)
-
-
 @torch.library.custom_op("fsgm::epipolar_flow_pp", mutates_args=())
 def _epipolar_flow_pp_op(I0: torch.Tensor, I1: torch.Tensor, geometry: List[float], dMax: int, vMax: float,
                          paths: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
-    N, H, W, dev = _frames(I0)
-    ch = 1 if I0.dim() == 3 else 3
-    g = _geometries(geometry, N)
-    I0, I1 = _ready(I0), _ready(I1)
-    flow, flow2, D1, minC, status = _epipolar_flow_pp_outputs(I0)
-    prm = _epi_params(paths, 1, 0, dev.index, 0)
-    _call(dev, _L.fsgm_epipolar_flow_pp_device, N, _p(I0), _p(I1), W, H, ch, g, int(dMax), float(vMax), C.byref(prm),
-          _p(flow), _p(flow2), _p(D1), _p(minC), _stream(dev), _p(status))
-    return flow, flow2, D1, minC, status
+    return _epipolar_run(_L.fsgm_epipolar_flow_pp_device, _epipolar_flow_pp_outputs, 0, I0, I1, geometry, dMax, vMax, paths)
 
 
 @_epipolar_flow_pp_op.register_fake
@@ -529,28 +531,23 @@ def _(flow):
     return _like(flow)
 
 
-def _pyramid_outputs(I0):
+def _pyramid_outputs(I0, minC2=None):
+    """(mv, minC[, minC2], status) of level 1"""
     N, H, W, dev = _frames(I0)
-    return _f64((N, 2, H, W), dev), _u32((N, H, W), dev), _status(dev)
+    minC = _u32((N, H, W), dev)
+    return (_f64((N, 2, H, W), dev), minC) + _minC2_output(minC, minC2) + (_status(dev),)
 
 
-def _pyramid_run(fn, prm, I0, I1, runner_up=False):
+def _pyramid_run(fn, prm, I0, I1, *, level_median=None, minC2=None):
+    """level_median: None for an entry without that argument (the plain and the _ru ones)"""
     N, H, W, dev = _frames(I0)
     ch = 1 if I0.dim() == 3 else 3
     prm.device = dev.index
     I0, I1 = _ready(I0), _ready(I1)
-    if runner_up:
-        mv, minC, minC2, status = _pyramid_ru_outputs(I0)
-        _call(dev, fn, N, _p(I0), _p(I1), W, H, ch, C.byref(prm), _p(mv), _p(minC), _p(minC2), _stream(dev), _p(status))
-        return mv, minC, minC2, status
-    mv, minC, status = _pyramid_outputs(I0)
-    _call(dev, fn, N, _p(I0), _p(I1), W, H, ch, C.byref(prm), _p(mv), _p(minC), _stream(dev), _p(status))
-    return mv, minC, status
-
-
-def _pyramid_ru_outputs(I0):
-    N, H, W, dev = _frames(I0)
-    return _f64((N, 2, H, W), dev), _u32((N, H, W), dev), _u32((N, H, W), dev), _status(dev)
+    mv, minC, *slot, status = _pyramid_outputs(I0, minC2)
+    _call(dev, fn, N, _p(I0), _p(I1), W, H, ch, C.byref(prm), *(() if level_median is None else (int(level_median),)), _p(mv), _p(minC),
+          *_minC2_arg(slot, minC2), _stream(dev), _p(status))
+    return (mv, minC, *slot, status)
 
 
 def _pyramid_prm(default, fields, numPyd, params):
@@ -561,70 +558,80 @@ def _pyramid_prm(default, fields, numPyd, params):
     return prm
 
 
+def _pyd_prm(numPyd, params):
+    return _pyramid_prm(_L.fsgm_pyramid_params_default, PYRAMID_FIELDS, numPyd, params)
+
+
+def _ng_prm(numPyd, params):
+    return _pyramid_prm(_L.fsgm_ng_pyramid_params_default, NG_PYRAMID_FIELDS, numPyd, params)
+
+
+@torch.library.custom_op("fsgm::pyramidal_sgm", mutates_args=())
+def _pyramidal_sgm_op(I0: torch.Tensor, I1: torch.Tensor, numPyd: int,
+                      params: List[int]) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    return _pyramid_run(_L.fsgm_pyramidal_sgm_device, _pyd_prm(numPyd, params), I0, I1)
+
+
+@_pyramidal_sgm_op.register_fake
+def _(I0, I1, numPyd, params):
+    return _pyramid_outputs(I0)
+
+
+@torch.library.custom_op("fsgm::pyramidal_sgm_ng", mutates_args=())
+def _pyramidal_sgm_ng_op(I0: torch.Tensor, I1: torch.Tensor, numPyd: int,
+                         params: List[int]) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    return _pyramid_run(_L.fsgm_pyramidal_sgm_ng_device, _ng_prm(numPyd, params), I0, I1)
+
+
+@_pyramidal_sgm_ng_op.register_fake
+def _(I0, I1, numPyd, params):
+    return _pyramid_outputs(I0)
+
+
 @torch.library.custom_op("fsgm::pyramidal_sgm_ru", mutates_args=())
 def _pyramidal_sgm_ru_op(I0: torch.Tensor, I1: torch.Tensor, numPyd: int,
                          params: List[int]) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
-    prm = _pyramid_prm(_L.fsgm_pyramid_params_default, PYRAMID_FIELDS, numPyd, params)
-    return _pyramid_run(_L.fsgm_pyramidal_sgm_device_ru, prm, I0, I1, True)
+    return _pyramid_run(_L.fsgm_pyramidal_sgm_device_ru, _pyd_prm(numPyd, params), I0, I1, minC2=True)
 
 
 @_pyramidal_sgm_ru_op.register_fake
 def _(I0, I1, numPyd, params):
-    return _pyramid_ru_outputs(I0)
+    return _pyramid_outputs(I0, True)
 
 
 @torch.library.custom_op("fsgm::pyramidal_sgm_ng_ru", mutates_args=())
 def _pyramidal_sgm_ng_ru_op(I0: torch.Tensor, I1: torch.Tensor, numPyd: int,
                             params: List[int]) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
-    prm = _pyramid_prm(_L.fsgm_ng_pyramid_params_default, NG_PYRAMID_FIELDS, numPyd, params)
-    return _pyramid_run(_L.fsgm_pyramidal_sgm_ng_device_ru, prm, I0, I1, True)
+    return _pyramid_run(_L.fsgm_pyramidal_sgm_ng_device_ru, _ng_prm(numPyd, params), I0, I1, minC2=True)
 
 
 @_pyramidal_sgm_ng_ru_op.register_fake
 def _(I0, I1, numPyd, params):
-    return _pyramid_ru_outputs(I0)
-
-
-def _pyramid_lm_outputs(I0, runner_up):
-    N, H, W, dev = _frames(I0)
-    return _f64((N, 2, H, W), dev), _u32((N, H, W), dev), _u32((N, H, W) if runner_up else (0,), dev), _status(dev)
-
-
-def _pyramid_lm_run(fn, prm, I0, I1, level_median, runner_up):
-    N, H, W, dev = _frames(I0)
-    ch = 1 if I0.dim() == 3 else 3
-    prm.device = dev.index
-    I0, I1 = _ready(I0), _ready(I1)
-    mv, minC, minC2, status = _pyramid_lm_outputs(I0, runner_up)
-    _call(dev, fn, N, _p(I0), _p(I1), W, H, ch, C.byref(prm), int(level_median), _p(mv), _p(minC), _p(minC2) if runner_up else None,
-          _stream(dev), _p(status))
-    return mv, minC, minC2, status
+    return _pyramid_outputs(I0, True)
 
 
 @torch.library.custom_op("fsgm::pyramidal_sgm_lm", mutates_args=())
 def _pyramidal_sgm_lm_op(I0: torch.Tensor, I1: torch.Tensor, numPyd: int, params: List[int], level_median: int,
                          runner_up: bool) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
     """fsgm::pyramidal_sgm_ru with the median between levels (fsgm_pyramidal_sgm_device_lm); minC2 is empty unless runner_up"""
-    prm = _pyramid_prm(_L.fsgm_pyramid_params_default, PYRAMID_FIELDS, numPyd, params)
-    return _pyramid_lm_run(_L.fsgm_pyramidal_sgm_device_lm, prm, I0, I1, level_median, runner_up)
+    return _pyramid_run(_L.fsgm_pyramidal_sgm_device_lm, _pyd_prm(numPyd, params), I0, I1, level_median=level_median, minC2=bool(runner_up))
 
 
 @_pyramidal_sgm_lm_op.register_fake
 def _(I0, I1, numPyd, params, level_median, runner_up):
-    return _pyramid_lm_outputs(I0, runner_up)
+    return _pyramid_outputs(I0, bool(runner_up))
 
 
 @torch.library.custom_op("fsgm::pyramidal_sgm_ng_lm", mutates_args=())
 def _pyramidal_sgm_ng_lm_op(I0: torch.Tensor, I1: torch.Tensor, numPyd: int, params: List[int], level_median: int,
                             runner_up: bool) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
     """fsgm::pyramidal_sgm_ng_ru with the median between levels (fsgm_pyramidal_sgm_ng_device_lm); minC2 is empty unless runner_up"""
-    prm = _pyramid_prm(_L.fsgm_ng_pyramid_params_default, NG_PYRAMID_FIELDS, numPyd, params)
-    return _pyramid_lm_run(_L.fsgm_pyramidal_sgm_ng_device_lm, prm, I0, I1, level_median, runner_up)
+    return _pyramid_run(_L.fsgm_pyramidal_sgm_ng_device_lm, _ng_prm(numPyd, params), I0, I1, level_median=level_median, minC2=bool(runner_up))
 
 
 @_pyramidal_sgm_ng_lm_op.register_fake
 def _(I0, I1, numPyd, params, level_median, runner_up):
-    return _pyramid_lm_outputs(I0, runner_up)
+    return _pyramid_outputs(I0, bool(runner_up))
 
 
 def _level_hints_output(flow):
@@ -647,40 +654,12 @@ def _(flow, size):
     return _level_hints_output(flow)
 
 
-@torch.library.custom_op("fsgm::pyramidal_sgm", mutates_args=())
-def _pyramidal_sgm_op(I0: torch.Tensor, I1: torch.Tensor, numPyd: int,
-                      params: List[int]) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-    prm = _L.fsgm_pyramid_params_default()
-    prm.numPyd = int(numPyd)
-    for k, v in zip(PYRAMID_FIELDS, params, strict=True):
-        setattr(prm, k, int(v))
-    return _pyramid_run(_L.fsgm_pyramidal_sgm_device, prm, I0, I1)
-
-
-@_pyramidal_sgm_op.register_fake
-def _(I0, I1, numPyd, params):
-    return _pyramid_outputs(I0)
-
-
-@torch.library.custom_op("fsgm::pyramidal_sgm_ng", mutates_args=())
-def _pyramidal_sgm_ng_op(I0: torch.Tensor, I1: torch.Tensor, numPyd: int,
-                         params: List[int]) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-    prm = _L.fsgm_ng_pyramid_params_default()
-    prm.numPyd = int(numPyd)
-    for k, v in zip(NG_PYRAMID_FIELDS, params, strict=True):
-        setattr(prm, k, int(v))
-    return _pyramid_run(_L.fsgm_pyramidal_sgm_ng_device, prm, I0, I1)
-
-
-@_pyramidal_sgm_ng_op.register_fake
-def _(I0, I1, numPyd, params):
-    return _pyramid_outputs(I0)
-
-
-def _pyramidal_flow_pp_outputs(I0):
+def _pyramidal_flow_pp_outputs(I0, minC2=None):
+    """(flow_pp, flow_checked, flow_fwd, flow_bwd, minC[, minC2], status)"""
     N, H, W, dev = _frames(I0)
-    return (_f64((N, 3, H, W), dev), _f64((N, 2, H, W), dev), _f64((N, 2, H, W), dev), _f64((N, 2, H, W), dev),
-            _u32((N, H, W), dev), _status(dev))
+    minC = _u32((N, H, W), dev)
+    return ((_f64((N, 3, H, W), dev), _f64((N, 2, H, W), dev), _f64((N, 2, H, W), dev), _f64((N, 2, H, W), dev), minC)
+            + _minC2_output(minC, minC2) + (_status(dev),))
 
 
 def _flow_pp_prm(matcher, numPyd, params, chain, median, dev):
@@ -695,30 +674,39 @@ def _flow_pp_prm(matcher, numPyd, params, chain, median, dev):
     return prm
 
 
-@torch.library.custom_op("fsgm::pyramidal_flow_pp_u", mutates_args=())
-def _pyramidal_flow_pp_u_op(I0: torch.Tensor, I1: torch.Tensor, matcher: int, numPyd: int, params: List[int], chain: List[float],
-                            median: int, uniqueness_ratio: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor,
-                                                                         torch.Tensor, torch.Tensor, torch.Tensor]:
+def _flow_pp_run(fn, I0, I1, matcher, numPyd, params, chain, median, *switches, minC2=None):
+    """switches: the integers the entry takes after the parameter struct (uniqueness_ratio, then level_median)"""
     N, H, W, dev = _frames(I0)
     ch = 1 if I0.dim() == 3 else 3
     prm = _flow_pp_prm(matcher, numPyd, params, chain, median, dev)
     I0, I1 = _ready(I0), _ready(I1)
-    pp, checked, fwd, bwd, minC, status = _pyramidal_flow_pp_outputs(I0)
-    minC2 = torch.empty_like(minC)
-    _call(dev, _L.fsgm_pyramidal_flow_pp_device_u, N, _p(I0), _p(I1), W, H, ch, C.byref(prm), int(uniqueness_ratio), _p(pp), _p(checked),
-          _p(fwd), _p(bwd), _p(minC), _p(minC2), _stream(dev), _p(status))
-    return pp, checked, fwd, bwd, minC, minC2, status
+    pp, checked, fwd, bwd, minC, *slot, status = _pyramidal_flow_pp_outputs(I0, minC2)
+    _call(dev, fn, N, _p(I0), _p(I1), W, H, ch, C.byref(prm), *(int(s) for s in switches), _p(pp), _p(checked), _p(fwd), _p(bwd), _p(minC),
+          *_minC2_arg(slot, minC2), _stream(dev), _p(status))
+    return (pp, checked, fwd, bwd, minC, *slot, status)
+
+
+@torch.library.custom_op("fsgm::pyramidal_flow_pp", mutates_args=())
+def _pyramidal_flow_pp_op(I0: torch.Tensor, I1: torch.Tensor, matcher: int, numPyd: int, params: List[int], chain: List[float],
+                          median: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    return _flow_pp_run(_L.fsgm_pyramidal_flow_pp_device, I0, I1, matcher, numPyd, params, chain, median)
+
+
+@_pyramidal_flow_pp_op.register_fake
+def _(I0, I1, matcher, numPyd, params, chain, median):
+    return _pyramidal_flow_pp_outputs(I0)
+
+
+@torch.library.custom_op("fsgm::pyramidal_flow_pp_u", mutates_args=())
+def _pyramidal_flow_pp_u_op(I0: torch.Tensor, I1: torch.Tensor, matcher: int, numPyd: int, params: List[int], chain: List[float],
+                            median: int, uniqueness_ratio: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor,
+                                                                         torch.Tensor, torch.Tensor, torch.Tensor]:
+    return _flow_pp_run(_L.fsgm_pyramidal_flow_pp_device_u, I0, I1, matcher, numPyd, params, chain, median, uniqueness_ratio, minC2=True)
 
 
 @_pyramidal_flow_pp_u_op.register_fake
 def _(I0, I1, matcher, numPyd, params, chain, median, uniqueness_ratio):
-    pp, checked, fwd, bwd, minC, status = _pyramidal_flow_pp_outputs(I0)
-    return pp, checked, fwd, bwd, minC, torch.empty_like(minC), status
-
-
-def _pyramidal_flow_pp_lm_outputs(I0, want_minC2):
-    pp, checked, fwd, bwd, minC, status = _pyramidal_flow_pp_outputs(I0)
-    return pp, checked, fwd, bwd, minC, torch.empty_like(minC) if want_minC2 else _u32((0,), I0.device), status
+    return _pyramidal_flow_pp_outputs(I0, True)
 
 
 @torch.library.custom_op("fsgm::pyramidal_flow_pp_lm", mutates_args=())
@@ -728,37 +716,13 @@ def _pyramidal_flow_pp_lm_op(I0: torch.Tensor, I1: torch.Tensor, matcher: int, n
                                                          torch.Tensor, torch.Tensor]:
     """fsgm::pyramidal_flow_pp_u with the median between levels (fsgm_pyramidal_flow_pp_device_lm); minC2 is empty unless
     want_minC2, which a non-zero uniqueness_ratio needs"""
-    N, H, W, dev = _frames(I0)
-    ch = 1 if I0.dim() == 3 else 3
-    prm = _flow_pp_prm(matcher, numPyd, params, chain, median, dev)
-    I0, I1 = _ready(I0), _ready(I1)
-    pp, checked, fwd, bwd, minC, minC2, status = _pyramidal_flow_pp_lm_outputs(I0, want_minC2)
-    _call(dev, _L.fsgm_pyramidal_flow_pp_device_lm, N, _p(I0), _p(I1), W, H, ch, C.byref(prm), int(uniqueness_ratio), int(level_median),
-          _p(pp), _p(checked), _p(fwd), _p(bwd), _p(minC), _p(minC2) if want_minC2 else None, _stream(dev), _p(status))
-    return pp, checked, fwd, bwd, minC, minC2, status
+    return _flow_pp_run(_L.fsgm_pyramidal_flow_pp_device_lm, I0, I1, matcher, numPyd, params, chain, median, uniqueness_ratio, level_median,
+                        minC2=bool(want_minC2))
 
 
 @_pyramidal_flow_pp_lm_op.register_fake
 def _(I0, I1, matcher, numPyd, params, chain, median, uniqueness_ratio, want_minC2, level_median):
-    return _pyramidal_flow_pp_lm_outputs(I0, want_minC2)
-
-
-@torch.library.custom_op("fsgm::pyramidal_flow_pp", mutates_args=())
-def _pyramidal_flow_pp_op(I0: torch.Tensor, I1: torch.Tensor, matcher: int, numPyd: int, params: List[int], chain: List[float],
-                          median: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
-    N, H, W, dev = _frames(I0)
-    ch = 1 if I0.dim() == 3 else 3
-    prm = _flow_pp_prm(matcher, numPyd, params, chain, median, dev)
-    I0, I1 = _ready(I0), _ready(I1)
-    pp, checked, fwd, bwd, minC, status = _pyramidal_flow_pp_outputs(I0)
-    _call(dev, _L.fsgm_pyramidal_flow_pp_device, N, _p(I0), _p(I1), W, H, ch, C.byref(prm), _p(pp), _p(checked), _p(fwd), _p(bwd),
-          _p(minC), _stream(dev), _p(status))
-    return pp, checked, fwd, bwd, minC, status
-
-
-@_pyramidal_flow_pp_op.register_fake
-def _(I0, I1, matcher, numPyd, params, chain, median):
-    return _pyramidal_flow_pp_outputs(I0)
+    return _pyramidal_flow_pp_outputs(I0, bool(want_minC2))
 
 
 @torch.library.custom_op("fsgm::flow_fb_check", mutates_args=())
@@ -823,32 +787,6 @@ def _stereo_fb_check_op(D1: torch.Tensor, D2: torch.Tensor, fused: int, d_min: i
 @_stereo_fb_check_op.register_fake
 def _(D1, D2, fused, d_min, direction, thr):
     return _stereo_fb_check_outputs(D1, fused)
-
-
-def _stereo_sgm_ru_outputs(left, fb_check):
-    """(disp int32, minC, minC2, conf, disp2 int32, status): fsgm::stereo_sgm_range's with the runner-up cost after minC"""
-    disp, minC, conf, disp2, status = _matcher_outputs(left, fb_check, torch.int32)
-    return disp, minC, torch.empty_like(minC), conf, disp2, status
-
-
-@torch.library.custom_op("fsgm::stereo_sgm_ru", mutates_args=())
-def _stereo_sgm_ru_op(left: torch.Tensor, right: torch.Tensor, dMax: int, d_min: int, P1: int, P2: int, paths: int, subpixel: int,
-                      direction: int, fb_check: int, adaptive_p2: int = 0
-                      ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
-    N, H, W, dev = _frames(left)
-    left, right = _ready(left), _ready(right)
-    disp, minC, minC2, conf, disp2, status = _stereo_sgm_ru_outputs(left, fb_check)
-    prm = _stereo_params(paths, subpixel, direction, fb_check, dev.index)
-    opt = _lib.options(adaptive_p2)
-    _call(dev, _L.fsgm_stereo_sgm_device_ru, N, _p(left), _p(right), W, H, int(dMax), int(P1), int(P2), C.byref(prm), C.byref(opt),
-          int(d_min), _p(disp), _p(minC), _p(minC2), _p(conf) if fb_check else None, _p(disp2) if fb_check else None, _stream(dev),
-          _p(status))
-    return disp, minC, minC2, conf, disp2, status
-
-
-@_stereo_sgm_ru_op.register_fake
-def _(left, right, dMax, d_min, P1, P2, paths, subpixel, direction, fb_check, adaptive_p2=0):
-    return _stereo_sgm_ru_outputs(left, fb_check)
 
 
 def _uniqueness_planes_check(map_, minC, minC2, planes):
@@ -1087,20 +1025,27 @@ def sgm2d(costs, half_x, half_y, P1=6, P2=32, *, layout="dhw", hints=None, guide
     return _finish(outs, status, batched, check, return_status, "a cost above cost_bound")
 
 
+def _ingest(plan, t, name, layout, code, must_be_contiguous, fn, cost_bound, check, return_status):
+    """`plan.batch` cost volumes from the uint8 tensor `t` (called `name` in messages) through a plan's ingest entry `fn`; `code` is
+    the entry's number for `layout`.  A tensor that is not contiguous is refused with must_be_contiguous, else copied."""
+    dev = _tensors({name: (t, torch.uint8)})
+    if dev.index != plan.device:
+        raise TypeError(f"the tensor is on {dev}, the plan on device {plan.device}")
+    _shape(name, t, (plan.batch, plan.H, plan.W, plan.D) if layout == "hwd" else (plan.batch, plan.D, plan.H, plan.W))
+    if must_be_contiguous and not t.is_contiguous():
+        raise TypeError(f"{name} must be contiguous: the volume is read where it lies (no silent copy)")
+    t = t.contiguous()
+    status = _status(dev)
+    _call(dev, fn, plan._h, plan.batch, _p(t), code, int(cost_bound), _stream(dev), _p(status))
+    res = _finish((), status, True, check, return_status, "a cost above cost_bound")
+    return res[0] if return_status else None
+
+
 def ingest_cost(plan, Cvol, *, layout="dhw", cost_bound=255, check=False, return_status=False):
     """All `plan.batch` cost volumes of an EpiPlan from a uint8 tensor on the plan's GPU (fsgm_epi_plan_ingest_cost_device): (N, D, H, W)
     for layout "dhw", (N, H, W, D) for "hwd", saturated at cost_bound, which the plan then selects its kernels by.  What
     EpiPlan.upload_cost does from the host, frame by frame.  Returns the status tensor with return_status=True, else None."""
-    code = _layout_code(layout)
-    dev = _tensors({"C": (Cvol, torch.uint8)})
-    if dev.index != plan.device:
-        raise TypeError(f"the tensor is on {dev}, the plan on device {plan.device}")
-    _shape("C", Cvol, (plan.batch, plan.H, plan.W, plan.D) if layout == "hwd" else (plan.batch, plan.D, plan.H, plan.W))
-    Cvol = Cvol.contiguous()
-    status = _status(dev)
-    _call(dev, _L.fsgm_epi_plan_ingest_cost_device, plan._h, plan.batch, _p(Cvol), code, int(cost_bound), _stream(dev), _p(status))
-    res = _finish((), status, True, check, return_status, "a cost above cost_bound")
-    return res[0] if return_status else None
+    return _ingest(plan, Cvol, "C", layout, _layout_code(layout), False, _L.fsgm_epi_plan_ingest_cost_device, cost_bound, check, return_status)
 
 
 def ingest_cost2d(plan, costs, *, layout="dhw", cost_bound=255, check=False, return_status=False):
@@ -1108,17 +1053,24 @@ def ingest_cost2d(plan, costs, *, layout="dhw", cost_bound=255, check=False, ret
     (N, D, H, W) for layout "dhw" / "dhw_yx", (N, H, W, D) for "hwd", saturated at cost_bound, which the plan then selects its
     aggregation by.  What PydPlan.upload_cost does from the host, frame by frame.  Returns the status tensor with
     return_status=True, else None."""
-    code = _layout2d_code(layout)
-    dev = _tensors({"costs": (costs, torch.uint8)})
-    if dev.index != plan.device:
-        raise TypeError(f"the tensor is on {dev}, the plan on device {plan.device}")
-    _shape("costs", costs, (plan.batch, plan.H, plan.W, plan.D) if layout == "hwd" else (plan.batch, plan.D, plan.H, plan.W))
-    if not costs.is_contiguous():
-        raise TypeError("costs must be contiguous: the volume is read where it lies (no silent copy)")
-    status = _status(dev)
-    _call(dev, _L.fsgm_pyd_plan_ingest_cost_device, plan._h, plan.batch, _p(costs), code, int(cost_bound), _stream(dev), _p(status))
-    res = _finish((), status, True, check, return_status, "a cost above cost_bound")
-    return res[0] if return_status else None
+    return _ingest(plan, costs, "costs", layout, _layout2d_code(layout), True, _L.fsgm_pyd_plan_ingest_cost_device, cost_bound, check,
+                   return_status)
+
+
+def _stereo_inputs(left, right, dMax, paths, subpixel, direction, fb_check, adaptive_p2):
+    """The checks the rectified-stereo wrappers share, before anything is queued; returns (left, right with a leading N, batched)."""
+    _tensors({"left": (left, torch.uint8), "right": (right, torch.uint8)})
+    if left.dim() not in (2, 3):
+        raise TypeError(f"left must be (H, W) or (N, H, W) (got {tuple(left.shape)})")
+    _shape("right", right, left.shape)
+    if int(dMax) < 1:
+        raise ValueError(f"dMax must be >= 1 (got {dMax!r})")
+    _stereo_params(paths, subpixel, direction, fb_check, 0)                 # the value checks
+    if int(adaptive_p2) not in (0, 1):
+        raise ValueError(f"adaptive_p2 must be 0 or 1 (got {adaptive_p2!r})")
+    if left.dim() == 3:
+        return left, right, True
+    return left.unsqueeze(0), right.unsqueeze(0), False
 
 
 def stereo_sgm(left, right, dMax, P1=6, P2=64, *, paths=4, subpixel=1, direction=-1, fb_check=0, check=False, return_status=False,
@@ -1132,36 +1084,19 @@ def stereo_sgm(left, right, dMax, P1=6, P2=64, *, paths=4, subpixel=1, direction
     runner-up cost min { S[d] : |d - best| >= 2 } (0xFFFFFFFF where no such d exists), to the outputs; the call then runs the
     line kernels at every batch size."""
     d_min = _d_min(d_min)
-    _tensors({"left": (left, torch.uint8), "right": (right, torch.uint8)})
-    if left.dim() not in (2, 3):
-        raise TypeError(f"left must be (H, W) or (N, H, W) (got {tuple(left.shape)})")
-    _shape("right", right, left.shape)
-    if int(dMax) < 1:
-        raise ValueError(f"dMax must be >= 1 (got {dMax!r})")
-    _stereo_params(paths, subpixel, direction, fb_check, 0)                 # the value checks, before anything is queued
-    if int(adaptive_p2) not in (0, 1):
-        raise ValueError(f"adaptive_p2 must be 0 or 1 (got {adaptive_p2!r})")
-    batched = left.dim() == 3
-    if not batched:
-        left, right = left.unsqueeze(0), right.unsqueeze(0)
+    left, right, batched = _stereo_inputs(left, right, dMax, paths, subpixel, direction, fb_check, adaptive_p2)
+    rest = (int(P1), int(P2), int(paths), int(subpixel), int(direction), int(bool(fb_check)), int(adaptive_p2))
     if runner_up:
-        disp, minC, minC2, conf, disp2, status = torch.ops.fsgm.stereo_sgm_ru(left, right, int(dMax), d_min or 0, int(P1), int(P2), int(paths),
-                                                                               int(subpixel), int(direction), int(bool(fb_check)),
-                                                                               int(adaptive_p2))
+        disp, minC, minC2, conf, disp2, status = torch.ops.fsgm.stereo_sgm_ru(left, right, int(dMax), d_min or 0, *rest)
         if d_min is None:                                    # the uint32 outputs of the call without d_min (disp2: 512 << 8 where invalid)
             disp = disp.view(torch.uint32)
             if fb_check:
                 disp2 = torch.where(disp2 == -2 ** 31, 512 << 8, disp2).view(torch.uint32)
-        outs = (disp, minC, conf, disp2, minC2) if fb_check else (disp, minC, minC2)
-        return _finish(outs, status, batched, check, return_status)
-    if d_min is None:
-        disp, minC, conf, disp2, status = torch.ops.fsgm.stereo_sgm(left, right, int(dMax), int(P1), int(P2), int(paths), int(subpixel),
-                                                                     int(direction), int(bool(fb_check)), int(adaptive_p2))
+    elif d_min is None:
+        disp, minC, conf, disp2, status = torch.ops.fsgm.stereo_sgm(left, right, int(dMax), *rest)
     else:
-        disp, minC, conf, disp2, status = torch.ops.fsgm.stereo_sgm_range(left, right, int(dMax), d_min, int(P1), int(P2), int(paths),
-                                                                           int(subpixel), int(direction), int(bool(fb_check)),
-                                                                           int(adaptive_p2))
-    outs = (disp, minC, conf, disp2) if fb_check else (disp, minC)
+        disp, minC, conf, disp2, status = torch.ops.fsgm.stereo_sgm_range(left, right, int(dMax), d_min, *rest)
+    outs = ((disp, minC, conf, disp2) if fb_check else (disp, minC)) + ((minC2,) if runner_up else ())
     return _finish(outs, status, batched, check, return_status)
 
 
@@ -1171,19 +1106,8 @@ def stereo_sgm_pp(left, right, dMax, P1=6, P2=64, *, paths=4, subpixel=1, direct
     uint8 or a batch (N, H, W).  The images are read where they lie, every output stays in HBM, the work is queued on the
     current stream.  disp_pp / disp_checked / disp2 float64, disp int32 (true disparity * 256), minC uint32."""
     d_min = _d_min(0 if d_min is None else d_min)
-    _tensors({"left": (left, torch.uint8), "right": (right, torch.uint8)})
-    if left.dim() not in (2, 3):
-        raise TypeError(f"left must be (H, W) or (N, H, W) (got {tuple(left.shape)})")
-    _shape("right", right, left.shape)
-    if int(dMax) < 1:
-        raise ValueError(f"dMax must be >= 1 (got {dMax!r})")
-    _stereo_params(paths, subpixel, direction, 0, 0)                        # the value checks, before anything is queued
-    if int(adaptive_p2) not in (0, 1):
-        raise ValueError(f"adaptive_p2 must be 0 or 1 (got {adaptive_p2!r})")
+    left, right, batched = _stereo_inputs(left, right, dMax, paths, subpixel, direction, 0, adaptive_p2)
     defaults = _stereo_pp_params(_L, in_fill, chain)                        # (unknown names raise here)
-    batched = left.dim() == 3
-    if not batched:
-        left, right = left.unsqueeze(0), right.unsqueeze(0)
     *outs, status = torch.ops.fsgm.stereo_sgm_pp(left, right, int(dMax), d_min, int(P1), int(P2), int(paths), int(subpixel), int(direction),
                                                  int(adaptive_p2), [float(getattr(defaults, k)) for k in STEREO_PP_FIELDS], int(in_fill))
     return _finish(outs, status, batched, check, return_status)
@@ -1346,9 +1270,20 @@ def _overrides(fields, defaults, overrides, name):
     return [int(overrides.get(k, getattr(defaults, k))) for k in fields]
 
 
-def _pyramid_lm(op, I0, I1, numPyd, params, level_median, runner_up, batched, check, return_status):
-    mv, minC, minC2, status = op(I0, I1, int(numPyd), params, level_median, bool(runner_up))
-    return _finish((mv, minC, minC2) if runner_up else (mv, minC), status, batched, check, return_status)
+def _pyramidal(ops, fields, default, name, I0, I1, numPyd, batch, check, return_status, runner_up, level_median, overrides):
+    """pyramidal_sgm and pyramidal_sgm_ng: ops = the matcher's (plain, _ru, _lm) ops"""
+    plain, ru, lm = ops
+    level_median = _level_median_of(level_median)
+    I0, I1, batched = _pyramid_images(I0, I1, batch)
+    params = _overrides(fields, default(), overrides, name)
+    if level_median:
+        *outs, status = lm(I0, I1, int(numPyd), params, level_median, bool(runner_up))
+        outs = outs if runner_up else outs[:2]               # (minC2 is the empty placeholder then)
+    elif runner_up:
+        *outs, status = ru(I0, I1, int(numPyd), params)
+    else:
+        *outs, status = plain(I0, I1, int(numPyd), params)
+    return _finish(outs, status, batched, check, return_status)
 
 
 def pyramidal_sgm(I0, I1, numPyd=5, *, batch=None, check=False, return_status=False, runner_up=False, level_median=0, **overrides):
@@ -1357,32 +1292,18 @@ def pyramidal_sgm(I0, I1, numPyd=5, *, batch=None, check=False, return_status=Fa
     with 3 planes is one RGB pair).  mv (.., 2, H, W) float64, minC (.., H, W) uint32.  Keyword overrides as fsgm_amd.pyramidal_sgm.
     runner_up=True: (mv, minC, minC2) with level 1's runner-up cost (fsgm::pyramidal_sgm_ru).  level_median=3 or 5: the median
     between levels of fsgm_amd.pyramidal_sgm (fsgm::pyramidal_sgm_lm); it combines with runner_up."""
-    level_median = _level_median_of(level_median)
-    I0, I1, batched = _pyramid_images(I0, I1, batch)
-    params = _overrides(PYRAMID_FIELDS, _L.fsgm_pyramid_params_default(), overrides, "pyramidal_sgm")
-    if level_median:
-        return _pyramid_lm(torch.ops.fsgm.pyramidal_sgm_lm, I0, I1, numPyd, params, level_median, runner_up, batched, check, return_status)
-    if runner_up:
-        mv, minC, minC2, status = torch.ops.fsgm.pyramidal_sgm_ru(I0, I1, int(numPyd), params)
-        return _finish((mv, minC, minC2), status, batched, check, return_status)
-    mv, minC, status = torch.ops.fsgm.pyramidal_sgm(I0, I1, int(numPyd), params)
-    return _finish((mv, minC), status, batched, check, return_status)
+    return _pyramidal((torch.ops.fsgm.pyramidal_sgm, torch.ops.fsgm.pyramidal_sgm_ru, torch.ops.fsgm.pyramidal_sgm_lm), PYRAMID_FIELDS,
+                      _L.fsgm_pyramid_params_default, "pyramidal_sgm", I0, I1, numPyd, batch, check, return_status, runner_up, level_median,
+                      overrides)
 
 
 def pyramidal_sgm_ng(I0, I1, numPyd=3, *, batch=None, check=False, return_status=False, runner_up=False, level_median=0, **overrides):
     """(flow, minC) of level 1 of the pyramidal loop around calc_pyd_cost_sgm_ng as fsgm_amd.pyramidal_sgm_ng, on torch tensors
     on the GPU; shapes and batch as pyramidal_sgm.  runner_up=True: (flow, minC, minC2) (fsgm::pyramidal_sgm_ng_ru).
     level_median=3 or 5: the median between levels (fsgm::pyramidal_sgm_ng_lm)."""
-    level_median = _level_median_of(level_median)
-    I0, I1, batched = _pyramid_images(I0, I1, batch)
-    params = _overrides(NG_PYRAMID_FIELDS, _L.fsgm_ng_pyramid_params_default(), overrides, "pyramidal_sgm_ng")
-    if level_median:
-        return _pyramid_lm(torch.ops.fsgm.pyramidal_sgm_ng_lm, I0, I1, numPyd, params, level_median, runner_up, batched, check, return_status)
-    if runner_up:
-        flow, minC, minC2, status = torch.ops.fsgm.pyramidal_sgm_ng_ru(I0, I1, int(numPyd), params)
-        return _finish((flow, minC, minC2), status, batched, check, return_status)
-    flow, minC, status = torch.ops.fsgm.pyramidal_sgm_ng(I0, I1, int(numPyd), params)
-    return _finish((flow, minC), status, batched, check, return_status)
+    return _pyramidal((torch.ops.fsgm.pyramidal_sgm_ng, torch.ops.fsgm.pyramidal_sgm_ng_ru, torch.ops.fsgm.pyramidal_sgm_ng_lm),
+                      NG_PYRAMID_FIELDS, _L.fsgm_ng_pyramid_params_default, "pyramidal_sgm_ng", I0, I1, numPyd, batch, check, return_status,
+                      runner_up, level_median, overrides)
 
 
 def pyramidal_flow_pp(I0, I1, numPyd=None, matcher="pyd", *, median=0, batch=None, check=False, return_status=False,
@@ -1399,19 +1320,15 @@ def pyramidal_flow_pp(I0, I1, numPyd=None, matcher="pyd", *, median=0, batch=Non
     sub, fields = (defaults.ng, NG_PYRAMID_FIELDS) if matcher == "ng" else (defaults.pyd, PYRAMID_FIELDS)
     chain = [float(overrides.pop(k, getattr(defaults, k))) for k in FLOW_PP_FIELDS]
     params = _overrides(fields, sub, overrides, "pyramidal_flow_pp")
+    args = (I0, I1, MATCHERS[matcher], int(sub.numPyd if numPyd is None else numPyd), params, chain, int(median))
+    want = uniqueness_ratio is not None
     if level_median:
-        want = uniqueness_ratio is not None
-        pp, checked, fwd, bwd, minC, minC2, status = torch.ops.fsgm.pyramidal_flow_pp_lm(
-            I0, I1, MATCHERS[matcher], int(sub.numPyd if numPyd is None else numPyd), params, chain, int(median),
-            _uniqueness_ratio_of(uniqueness_ratio) if want else 0, want, level_median)
-        outs = (pp, checked, fwd, bwd, minC) + ((minC2,) if want else ())
-        return _finish(outs, status, batched, check, return_status)
-    if uniqueness_ratio is not None:
-        *outs, status = torch.ops.fsgm.pyramidal_flow_pp_u(I0, I1, MATCHERS[matcher], int(sub.numPyd if numPyd is None else numPyd), params,
-                                                           chain, int(median), _uniqueness_ratio_of(uniqueness_ratio))
-        return _finish(outs, status, batched, check, return_status)
-    *outs, status = torch.ops.fsgm.pyramidal_flow_pp(I0, I1, MATCHERS[matcher], int(sub.numPyd if numPyd is None else numPyd), params,
-                                                     chain, int(median))
+        *outs, status = torch.ops.fsgm.pyramidal_flow_pp_lm(*args, _uniqueness_ratio_of(uniqueness_ratio) if want else 0, want, level_median)
+        outs = outs if want else outs[:5]                    # (minC2 is the empty placeholder then)
+    elif want:
+        *outs, status = torch.ops.fsgm.pyramidal_flow_pp_u(*args, _uniqueness_ratio_of(uniqueness_ratio))
+    else:
+        *outs, status = torch.ops.fsgm.pyramidal_flow_pp(*args)
     return _finish(outs, status, batched, check, return_status)
 
 

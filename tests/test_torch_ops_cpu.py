@@ -183,3 +183,227 @@ def test_cached_plan_entries_refuse_plan_arguments_before_any_device():
     prm.numPyd = 17
     assert lib.fsgm_pyramidal_sgm_device(1, FAKE, FAKE, 32, 24, 1, C.byref(prm), FAKE, None, None, None) == FSGM_ERR_INVALID
     assert "numPyd" in _err(lib)
+
+
+# ---- the op surface: every fsgm:: op's schema and its fake's outputs, as recorded on the commit before the bodies were shared ----
+SCHEMAS = {'calc_cost_sgm': 'fsgm::calc_cost_sgm(Tensor I1, Tensor I2, Tensor pd0, Tensor nd, Tensor off, SymInt dMax, float vMax, SymInt P1, SymInt P2, SymInt paths, SymInt subpixel, SymInt '
+                  'vz_to_disp, SymInt fb_check, SymInt adaptive_p2=0) -> (Tensor, Tensor, Tensor, Tensor, Tensor)',
+ 'calc_cost_sgm_linear': 'fsgm::calc_cost_sgm_linear(Tensor I1, Tensor I2, Tensor pd0, Tensor nd, SymInt dMax, SymInt P1, SymInt P2, SymInt paths, SymInt subpixel, SymInt fb_check, SymInt '
+                         'adaptive_p2=0) -> (Tensor, Tensor, Tensor, Tensor, Tensor)',
+ 'epi_postprocess': 'fsgm::epi_postprocess(Tensor D1, Tensor Pd0, Tensor nd, Tensor O, float vMax, float n, float dMax) -> (Tensor, Tensor, Tensor, Tensor)',
+ 'epipolar_flow_pp': 'fsgm::epipolar_flow_pp(Tensor I0, Tensor I1, float[] geometry, SymInt dMax, float vMax, SymInt paths) -> (Tensor, Tensor, Tensor, Tensor, Tensor)',
+ 'epipolar_sgm_of': 'fsgm::epipolar_sgm_of(Tensor I0, Tensor I1, float[] geometry, SymInt dMax, float vMax, SymInt paths) -> (Tensor, Tensor, Tensor)',
+ 'flow_fb_check': 'fsgm::flow_fb_check(Tensor f, Tensor b, float thr) -> Tensor',
+ 'flow_level_hints': 'fsgm::flow_level_hints(Tensor flow, SymInt size) -> Tensor',
+ 'pyramidal_flow_pp': 'fsgm::pyramidal_flow_pp(Tensor I0, Tensor I1, SymInt matcher, SymInt numPyd, SymInt[] params, float[] chain, SymInt median) -> (Tensor, Tensor, Tensor, Tensor, '
+                      'Tensor, Tensor)',
+ 'pyramidal_flow_pp_lm': 'fsgm::pyramidal_flow_pp_lm(Tensor I0, Tensor I1, SymInt matcher, SymInt numPyd, SymInt[] params, float[] chain, SymInt median, SymInt uniqueness_ratio, bool '
+                         'want_minC2, SymInt level_median) -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)',
+ 'pyramidal_flow_pp_u': 'fsgm::pyramidal_flow_pp_u(Tensor I0, Tensor I1, SymInt matcher, SymInt numPyd, SymInt[] params, float[] chain, SymInt median, SymInt uniqueness_ratio) -> (Tensor, '
+                        'Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)',
+ 'pyramidal_sgm': 'fsgm::pyramidal_sgm(Tensor I0, Tensor I1, SymInt numPyd, SymInt[] params) -> (Tensor, Tensor, Tensor)',
+ 'pyramidal_sgm_lm': 'fsgm::pyramidal_sgm_lm(Tensor I0, Tensor I1, SymInt numPyd, SymInt[] params, SymInt level_median, bool runner_up) -> (Tensor, Tensor, Tensor, Tensor)',
+ 'pyramidal_sgm_ng': 'fsgm::pyramidal_sgm_ng(Tensor I0, Tensor I1, SymInt numPyd, SymInt[] params) -> (Tensor, Tensor, Tensor)',
+ 'pyramidal_sgm_ng_lm': 'fsgm::pyramidal_sgm_ng_lm(Tensor I0, Tensor I1, SymInt numPyd, SymInt[] params, SymInt level_median, bool runner_up) -> (Tensor, Tensor, Tensor, Tensor)',
+ 'pyramidal_sgm_ng_ru': 'fsgm::pyramidal_sgm_ng_ru(Tensor I0, Tensor I1, SymInt numPyd, SymInt[] params) -> (Tensor, Tensor, Tensor, Tensor)',
+ 'pyramidal_sgm_ru': 'fsgm::pyramidal_sgm_ru(Tensor I0, Tensor I1, SymInt numPyd, SymInt[] params) -> (Tensor, Tensor, Tensor, Tensor)',
+ 'sgm': 'fsgm::sgm(Tensor C_, Tensor guide, SymInt P1, SymInt P2, SymInt paths, SymInt layout, SymInt cost_bound, SymInt agg_mode, SymInt adaptive_p2, SymInt subpixel, SymInt return_sum) '
+        '-> (Tensor, Tensor, Tensor, Tensor)',
+ 'sgm2d': 'fsgm::sgm2d(Tensor C_, Tensor hints, Tensor guide, SymInt half_x, SymInt half_y, SymInt P1, SymInt P2, SymInt layout, SymInt cost_bound, SymInt diagonal, SymInt total_pass, '
+          'SymInt adaptive_p2, SymInt subpixel, SymInt return_flow, SymInt return_sum) -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)',
+ 'sgm2d_exact': 'fsgm::sgm2d_exact(Tensor C_, Tensor hints, Tensor guide, SymInt half_x, SymInt half_y, SymInt P1, SymInt P2, SymInt layout, SymInt cost_bound, SymInt diagonal, SymInt '
+                'total_pass, SymInt adaptive_p2, SymInt subpixel, SymInt return_flow, SymInt return_sum, bool runner_up) -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)',
+ 'sgm2d_ru': 'fsgm::sgm2d_ru(Tensor C_, Tensor hints, Tensor guide, SymInt half_x, SymInt half_y, SymInt P1, SymInt P2, SymInt layout, SymInt cost_bound, SymInt diagonal, SymInt '
+             'total_pass, SymInt adaptive_p2, SymInt subpixel, SymInt return_flow, SymInt return_sum) -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)',
+ 'sgm_exact': 'fsgm::sgm_exact(Tensor C_, Tensor guide, SymInt P1, SymInt P2, SymInt paths, SymInt layout, SymInt cost_bound, SymInt agg_mode, SymInt adaptive_p2, SymInt subpixel, SymInt '
+              'return_sum) -> (Tensor, Tensor, Tensor, Tensor)',
+ 'sgm_ru': 'fsgm::sgm_ru(Tensor C_, Tensor guide, SymInt P1, SymInt P2, SymInt paths, SymInt layout, SymInt cost_bound, SymInt agg_mode, SymInt adaptive_p2, SymInt subpixel, SymInt '
+           'return_sum) -> (Tensor, Tensor, Tensor, Tensor, Tensor)',
+ 'stereo_fb_check': 'fsgm::stereo_fb_check(Tensor D1, Tensor D2, SymInt fused, SymInt d_min, SymInt direction, float thr) -> (Tensor, Tensor, Tensor)',
+ 'stereo_sgm': 'fsgm::stereo_sgm(Tensor left, Tensor right, SymInt dMax, SymInt P1, SymInt P2, SymInt paths, SymInt subpixel, SymInt direction, SymInt fb_check, SymInt adaptive_p2=0) -> '
+               '(Tensor, Tensor, Tensor, Tensor, Tensor)',
+ 'stereo_sgm_pp': 'fsgm::stereo_sgm_pp(Tensor left, Tensor right, SymInt dMax, SymInt d_min, SymInt P1, SymInt P2, SymInt paths, SymInt subpixel, SymInt direction, SymInt adaptive_p2, '
+                  'float[] chain, SymInt in_fill) -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)',
+ 'stereo_sgm_range': 'fsgm::stereo_sgm_range(Tensor left, Tensor right, SymInt dMax, SymInt d_min, SymInt P1, SymInt P2, SymInt paths, SymInt subpixel, SymInt direction, SymInt fb_check, '
+                     'SymInt adaptive_p2=0) -> (Tensor, Tensor, Tensor, Tensor, Tensor)',
+ 'stereo_sgm_ru': 'fsgm::stereo_sgm_ru(Tensor left, Tensor right, SymInt dMax, SymInt d_min, SymInt P1, SymInt P2, SymInt paths, SymInt subpixel, SymInt direction, SymInt fb_check, SymInt '
+                  'adaptive_p2=0) -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)',
+ 'uniqueness_filter': 'fsgm::uniqueness_filter(Tensor map_, Tensor minC, Tensor minC2, SymInt ratio) -> (Tensor, Tensor)',
+ 'uniqueness_filter_planes': 'fsgm::uniqueness_filter_planes(Tensor map_, Tensor minC, Tensor minC2, SymInt ratio, SymInt planes) -> (Tensor, Tensor)',
+ 'vmf': 'fsgm::vmf(Tensor flow) -> Tensor'}
+
+FAKE_OUTPUTS = {'calc_cost_sgm fb_check=0': 'uint32[2,8,8] uint32[2,8,8] uint8[0] uint32[0] int32[]',
+ 'calc_cost_sgm_linear fb_check=0': 'uint32[2,8,8] uint32[2,8,8] uint8[0] uint32[0] int32[]',
+ 'stereo_sgm fb_check=0': 'uint32[2,8,8] uint32[2,8,8] uint8[0] uint32[0] int32[]',
+ 'stereo_sgm_range fb_check=0': 'int32[2,8,8] uint32[2,8,8] uint8[0] int32[0] int32[]',
+ 'stereo_sgm_ru fb_check=0': 'int32[2,8,8] uint32[2,8,8] uint32[2,8,8] uint8[0] int32[0] int32[]',
+ 'calc_cost_sgm fb_check=1': 'uint32[2,8,8] uint32[2,8,8] uint8[2,8,8] uint32[2,8,8] int32[]',
+ 'calc_cost_sgm_linear fb_check=1': 'uint32[2,8,8] uint32[2,8,8] uint8[2,8,8] uint32[2,8,8] int32[]',
+ 'stereo_sgm fb_check=1': 'uint32[2,8,8] uint32[2,8,8] uint8[2,8,8] uint32[2,8,8] int32[]',
+ 'stereo_sgm_range fb_check=1': 'int32[2,8,8] uint32[2,8,8] uint8[2,8,8] int32[2,8,8] int32[]',
+ 'stereo_sgm_ru fb_check=1': 'int32[2,8,8] uint32[2,8,8] uint32[2,8,8] uint8[2,8,8] int32[2,8,8] int32[]',
+ 'sgm layout=0 return_sum=0': 'uint32[2,8,8] uint32[2,8,8] uint32[0] int32[]',
+ 'sgm layout=0 return_sum=1': 'uint32[2,8,8] uint32[2,8,8] uint32[2,8,8,4] int32[]',
+ 'sgm layout=1 return_sum=0': 'uint32[2,8,8] uint32[2,8,8] uint32[0] int32[]',
+ 'sgm layout=1 return_sum=1': 'uint32[2,8,8] uint32[2,8,8] uint32[2,8,8,4] int32[]',
+ 'sgm_exact layout=0 return_sum=0': 'uint32[2,8,8] uint32[2,8,8] uint32[0] int32[]',
+ 'sgm_exact layout=0 return_sum=1': 'uint32[2,8,8] uint32[2,8,8] uint32[2,8,8,4] int32[]',
+ 'sgm_exact layout=1 return_sum=0': 'uint32[2,8,8] uint32[2,8,8] uint32[0] int32[]',
+ 'sgm_exact layout=1 return_sum=1': 'uint32[2,8,8] uint32[2,8,8] uint32[2,8,8,4] int32[]',
+ 'sgm_ru layout=0 return_sum=0': 'uint32[2,8,8] uint32[2,8,8] uint32[2,8,8] uint32[0] int32[]',
+ 'sgm_ru layout=0 return_sum=1': 'uint32[2,8,8] uint32[2,8,8] uint32[2,8,8] uint32[2,8,8,4] int32[]',
+ 'sgm_ru layout=1 return_sum=0': 'uint32[2,8,8] uint32[2,8,8] uint32[2,8,8] uint32[0] int32[]',
+ 'sgm_ru layout=1 return_sum=1': 'uint32[2,8,8] uint32[2,8,8] uint32[2,8,8] uint32[2,8,8,4] int32[]',
+ 'sgm2d layout=0 return_flow=1 return_sum=1': 'uint32[2,8,8] uint32[2,8,8] float64[2,2,8,8] float64[2,2,8,8] uint32[2,8,8,9] int32[]',
+ 'sgm2d layout=1 return_flow=0 return_sum=0': 'uint32[2,8,8] uint32[2,8,8] float64[2,2,8,8] float64[0] uint32[0] int32[]',
+ 'sgm2d layout=1 return_flow=1 return_sum=0': 'uint32[2,8,8] uint32[2,8,8] float64[2,2,8,8] float64[2,2,8,8] uint32[0] int32[]',
+ 'sgm2d layout=1 return_flow=0 return_sum=1': 'uint32[2,8,8] uint32[2,8,8] float64[2,2,8,8] float64[0] uint32[2,8,8,9] int32[]',
+ 'sgm2d layout=2 return_flow=1 return_sum=1': 'uint32[2,8,8] uint32[2,8,8] float64[2,2,8,8] float64[2,2,8,8] uint32[2,8,8,9] int32[]',
+ 'sgm2d_ru layout=0 return_flow=1 return_sum=1': 'uint32[2,8,8] uint32[2,8,8] uint32[2,8,8] float64[2,2,8,8] float64[2,2,8,8] uint32[2,8,8,9] int32[]',
+ 'sgm2d_ru layout=1 return_flow=0 return_sum=0': 'uint32[2,8,8] uint32[2,8,8] uint32[2,8,8] float64[2,2,8,8] float64[0] uint32[0] int32[]',
+ 'sgm2d_ru layout=1 return_flow=1 return_sum=0': 'uint32[2,8,8] uint32[2,8,8] uint32[2,8,8] float64[2,2,8,8] float64[2,2,8,8] uint32[0] int32[]',
+ 'sgm2d_ru layout=1 return_flow=0 return_sum=1': 'uint32[2,8,8] uint32[2,8,8] uint32[2,8,8] float64[2,2,8,8] float64[0] uint32[2,8,8,9] int32[]',
+ 'sgm2d_ru layout=2 return_flow=1 return_sum=1': 'uint32[2,8,8] uint32[2,8,8] uint32[2,8,8] float64[2,2,8,8] float64[2,2,8,8] uint32[2,8,8,9] int32[]',
+ 'sgm2d_exact layout=0 return_flow=1 return_sum=1 runner_up=False': 'uint32[2,8,8] uint32[2,8,8] uint32[0] float64[2,2,8,8] float64[2,2,8,8] uint32[2,8,8,9] int32[]',
+ 'sgm2d_exact layout=0 return_flow=1 return_sum=1 runner_up=True': 'uint32[2,8,8] uint32[2,8,8] uint32[2,8,8] float64[2,2,8,8] float64[2,2,8,8] uint32[2,8,8,9] int32[]',
+ 'sgm2d_exact layout=1 return_flow=0 return_sum=0 runner_up=False': 'uint32[2,8,8] uint32[2,8,8] uint32[0] float64[2,2,8,8] float64[0] uint32[0] int32[]',
+ 'sgm2d_exact layout=1 return_flow=0 return_sum=0 runner_up=True': 'uint32[2,8,8] uint32[2,8,8] uint32[2,8,8] float64[2,2,8,8] float64[0] uint32[0] int32[]',
+ 'sgm2d_exact layout=1 return_flow=1 return_sum=0 runner_up=False': 'uint32[2,8,8] uint32[2,8,8] uint32[0] float64[2,2,8,8] float64[2,2,8,8] uint32[0] int32[]',
+ 'sgm2d_exact layout=1 return_flow=1 return_sum=0 runner_up=True': 'uint32[2,8,8] uint32[2,8,8] uint32[2,8,8] float64[2,2,8,8] float64[2,2,8,8] uint32[0] int32[]',
+ 'sgm2d_exact layout=1 return_flow=0 return_sum=1 runner_up=False': 'uint32[2,8,8] uint32[2,8,8] uint32[0] float64[2,2,8,8] float64[0] uint32[2,8,8,9] int32[]',
+ 'sgm2d_exact layout=1 return_flow=0 return_sum=1 runner_up=True': 'uint32[2,8,8] uint32[2,8,8] uint32[2,8,8] float64[2,2,8,8] float64[0] uint32[2,8,8,9] int32[]',
+ 'sgm2d_exact layout=2 return_flow=1 return_sum=1 runner_up=False': 'uint32[2,8,8] uint32[2,8,8] uint32[0] float64[2,2,8,8] float64[2,2,8,8] uint32[2,8,8,9] int32[]',
+ 'sgm2d_exact layout=2 return_flow=1 return_sum=1 runner_up=True': 'uint32[2,8,8] uint32[2,8,8] uint32[2,8,8] float64[2,2,8,8] float64[2,2,8,8] uint32[2,8,8,9] int32[]',
+ 'epipolar_sgm_of gray': 'float64[2,3,8,8] uint32[2,8,8] int32[]',
+ 'epipolar_flow_pp gray': 'float64[2,3,8,8] float64[2,3,8,8] float64[2,8,8] uint32[2,8,8] int32[]',
+ 'pyramidal_sgm gray': 'float64[2,2,8,8] uint32[2,8,8] int32[]',
+ 'pyramidal_sgm_ng gray': 'float64[2,2,8,8] uint32[2,8,8] int32[]',
+ 'pyramidal_sgm_ru gray': 'float64[2,2,8,8] uint32[2,8,8] uint32[2,8,8] int32[]',
+ 'pyramidal_sgm_ng_ru gray': 'float64[2,2,8,8] uint32[2,8,8] uint32[2,8,8] int32[]',
+ 'pyramidal_sgm_lm gray runner_up=False': 'float64[2,2,8,8] uint32[2,8,8] uint32[0] int32[]',
+ 'pyramidal_sgm_ng_lm gray runner_up=False': 'float64[2,2,8,8] uint32[2,8,8] uint32[0] int32[]',
+ 'pyramidal_sgm_lm gray runner_up=True': 'float64[2,2,8,8] uint32[2,8,8] uint32[2,8,8] int32[]',
+ 'pyramidal_sgm_ng_lm gray runner_up=True': 'float64[2,2,8,8] uint32[2,8,8] uint32[2,8,8] int32[]',
+ 'pyramidal_flow_pp gray matcher=0': 'float64[2,3,8,8] float64[2,2,8,8] float64[2,2,8,8] float64[2,2,8,8] uint32[2,8,8] int32[]',
+ 'pyramidal_flow_pp_u gray matcher=0': 'float64[2,3,8,8] float64[2,2,8,8] float64[2,2,8,8] float64[2,2,8,8] uint32[2,8,8] uint32[2,8,8] int32[]',
+ 'pyramidal_flow_pp_lm gray matcher=0 want_minC2=False': 'float64[2,3,8,8] float64[2,2,8,8] float64[2,2,8,8] float64[2,2,8,8] uint32[2,8,8] uint32[0] int32[]',
+ 'pyramidal_flow_pp_lm gray matcher=0 want_minC2=True': 'float64[2,3,8,8] float64[2,2,8,8] float64[2,2,8,8] float64[2,2,8,8] uint32[2,8,8] uint32[2,8,8] int32[]',
+ 'pyramidal_flow_pp gray matcher=1': 'float64[2,3,8,8] float64[2,2,8,8] float64[2,2,8,8] float64[2,2,8,8] uint32[2,8,8] int32[]',
+ 'pyramidal_flow_pp_u gray matcher=1': 'float64[2,3,8,8] float64[2,2,8,8] float64[2,2,8,8] float64[2,2,8,8] uint32[2,8,8] uint32[2,8,8] int32[]',
+ 'pyramidal_flow_pp_lm gray matcher=1 want_minC2=False': 'float64[2,3,8,8] float64[2,2,8,8] float64[2,2,8,8] float64[2,2,8,8] uint32[2,8,8] uint32[0] int32[]',
+ 'pyramidal_flow_pp_lm gray matcher=1 want_minC2=True': 'float64[2,3,8,8] float64[2,2,8,8] float64[2,2,8,8] float64[2,2,8,8] uint32[2,8,8] uint32[2,8,8] int32[]',
+ 'epipolar_sgm_of rgb': 'float64[2,3,8,8] uint32[2,8,8] int32[]',
+ 'epipolar_flow_pp rgb': 'float64[2,3,8,8] float64[2,3,8,8] float64[2,8,8] uint32[2,8,8] int32[]',
+ 'pyramidal_sgm rgb': 'float64[2,2,8,8] uint32[2,8,8] int32[]',
+ 'pyramidal_sgm_ng rgb': 'float64[2,2,8,8] uint32[2,8,8] int32[]',
+ 'pyramidal_sgm_ru rgb': 'float64[2,2,8,8] uint32[2,8,8] uint32[2,8,8] int32[]',
+ 'pyramidal_sgm_ng_ru rgb': 'float64[2,2,8,8] uint32[2,8,8] uint32[2,8,8] int32[]',
+ 'pyramidal_sgm_lm rgb runner_up=False': 'float64[2,2,8,8] uint32[2,8,8] uint32[0] int32[]',
+ 'pyramidal_sgm_ng_lm rgb runner_up=False': 'float64[2,2,8,8] uint32[2,8,8] uint32[0] int32[]',
+ 'pyramidal_sgm_lm rgb runner_up=True': 'float64[2,2,8,8] uint32[2,8,8] uint32[2,8,8] int32[]',
+ 'pyramidal_sgm_ng_lm rgb runner_up=True': 'float64[2,2,8,8] uint32[2,8,8] uint32[2,8,8] int32[]',
+ 'pyramidal_flow_pp rgb matcher=0': 'float64[2,3,8,8] float64[2,2,8,8] float64[2,2,8,8] float64[2,2,8,8] uint32[2,8,8] int32[]',
+ 'pyramidal_flow_pp_u rgb matcher=0': 'float64[2,3,8,8] float64[2,2,8,8] float64[2,2,8,8] float64[2,2,8,8] uint32[2,8,8] uint32[2,8,8] int32[]',
+ 'pyramidal_flow_pp_lm rgb matcher=0 want_minC2=False': 'float64[2,3,8,8] float64[2,2,8,8] float64[2,2,8,8] float64[2,2,8,8] uint32[2,8,8] uint32[0] int32[]',
+ 'pyramidal_flow_pp_lm rgb matcher=0 want_minC2=True': 'float64[2,3,8,8] float64[2,2,8,8] float64[2,2,8,8] float64[2,2,8,8] uint32[2,8,8] uint32[2,8,8] int32[]',
+ 'pyramidal_flow_pp rgb matcher=1': 'float64[2,3,8,8] float64[2,2,8,8] float64[2,2,8,8] float64[2,2,8,8] uint32[2,8,8] int32[]',
+ 'pyramidal_flow_pp_u rgb matcher=1': 'float64[2,3,8,8] float64[2,2,8,8] float64[2,2,8,8] float64[2,2,8,8] uint32[2,8,8] uint32[2,8,8] int32[]',
+ 'pyramidal_flow_pp_lm rgb matcher=1 want_minC2=False': 'float64[2,3,8,8] float64[2,2,8,8] float64[2,2,8,8] float64[2,2,8,8] uint32[2,8,8] uint32[0] int32[]',
+ 'pyramidal_flow_pp_lm rgb matcher=1 want_minC2=True': 'float64[2,3,8,8] float64[2,2,8,8] float64[2,2,8,8] float64[2,2,8,8] uint32[2,8,8] uint32[2,8,8] int32[]',
+ 'epi_postprocess': 'float64[2,8,8] float64[2,8,8] float64[2,8,8] int32[]',
+ 'vmf': 'float64[2,2,8,8]',
+ 'flow_level_hints': 'float64[2,2,16,16]',
+ 'flow_fb_check': 'float64[2,2,8,8]',
+ 'stereo_sgm_pp': 'float64[2,8,8] float64[2,8,8] int32[2,8,8] uint32[2,8,8] float64[2,8,8] int32[]',
+ 'stereo_fb_check fused=0': 'float64[2,8,8] float64[0] int32[]',
+ 'stereo_fb_check fused=1': 'float64[2,8,8] float64[2,8,8] int32[]',
+ 'uniqueness_filter': 'float64[2,8,8] int32[]',
+ 'uniqueness_filter_planes planes=1': 'float64[2,8,8] int32[]',
+ 'uniqueness_filter_planes planes=2': 'float64[2,2,8,8] int32[]'}
+
+N_, H_, W_, D_ = 2, 8, 8, 4                # 8x8 images, 4 disparities, a batch of 2; the 2-D ops search a 3x3 window (9 candidates)
+PYD_PARAMS, NG_PARAMS, CHAIN = [6, 32, 2, 5, 5, 1, 2, 0], [6, 32, 1, 2, 0], [2.0, 100.0, 2.0, 0.1]
+
+
+def _fake_cases():
+    """(label, op name, arguments) for every op, once per value of each switch that changes its outputs; call under a fake mode"""
+    def t(dtype, *shape):
+        return torch.empty(shape, dtype=dtype, device="cuda")
+    u8, u32, f64 = torch.uint8, torch.uint32, torch.float64
+    img, rgb, cost = t(u8, N_, H_, W_), t(u8, N_, 3, H_, W_), t(u32, N_, H_, W_)
+    m1, m2, none8, none64 = t(f64, N_, H_, W_), t(f64, N_, 2, H_, W_), t(u8, 0), t(f64, 0)
+    cases = []
+    for fb in (0, 1):
+        cases += [(f"calc_cost_sgm fb_check={fb}", "calc_cost_sgm", (img, img, m2, m2, m1, D_, 0.3, 6, 64, 4, 1, 1, fb, 0)),
+                  (f"calc_cost_sgm_linear fb_check={fb}", "calc_cost_sgm_linear", (img, img, m2, m2, D_, 6, 64, 4, 1, fb, 0)),
+                  (f"stereo_sgm fb_check={fb}", "stereo_sgm", (img, img, D_, 6, 64, 4, 1, -1, fb, 0)),
+                  (f"stereo_sgm_range fb_check={fb}", "stereo_sgm_range", (img, img, D_, 0, 6, 64, 4, 1, -1, fb, 0)),
+                  (f"stereo_sgm_ru fb_check={fb}", "stereo_sgm_ru", (img, img, D_, 0, 6, 64, 4, 1, -1, fb, 0))]
+    for op in ("sgm", "sgm_exact", "sgm_ru"):
+        for layout, vol in ((0, t(u8, N_, H_, W_, D_)), (1, t(u8, N_, D_, H_, W_))):
+            for rs in (0, 1):
+                cases.append((f"{op} layout={layout} return_sum={rs}", op, (vol, none8, 7, 100, 4, layout, 255, 0, 0, 1, rs)))
+    for op in ("sgm2d", "sgm2d_ru", "sgm2d_exact"):
+        for layout, vol in ((0, t(u8, N_, H_, W_, 9)), (1, t(u8, N_, 9, H_, W_)), (2, t(u8, N_, 9, H_, W_))):
+            for rf, rs in ((0, 0), (1, 0), (0, 1)) if layout == 1 else ((1, 1),):
+                args = (vol, none64, none8, 1, 1, 6, 32, layout, 255, 1, 2, 0, 1, rf, rs)
+                if op != "sgm2d_exact":
+                    cases.append((f"{op} layout={layout} return_flow={rf} return_sum={rs}", op, args))
+                else:
+                    cases += [(f"{op} layout={layout} return_flow={rf} return_sum={rs} runner_up={ru}", op, args + (ru,)) for ru in (False, True)]
+    for name, I in (("gray", img), ("rgb", rgb)):
+        cases += [(f"epipolar_sgm_of {name}", "epipolar_sgm_of", (I, I, [0.0] * (N_ * torch_ops.GEOMETRY_NUMBERS), D_, 0.3, 4)),
+                  (f"epipolar_flow_pp {name}", "epipolar_flow_pp", (I, I, [0.0] * (N_ * torch_ops.GEOMETRY_NUMBERS), D_, 0.3, 4)),
+                  (f"pyramidal_sgm {name}", "pyramidal_sgm", (I, I, 2, PYD_PARAMS)),
+                  (f"pyramidal_sgm_ng {name}", "pyramidal_sgm_ng", (I, I, 2, NG_PARAMS)),
+                  (f"pyramidal_sgm_ru {name}", "pyramidal_sgm_ru", (I, I, 2, PYD_PARAMS)),
+                  (f"pyramidal_sgm_ng_ru {name}", "pyramidal_sgm_ng_ru", (I, I, 2, NG_PARAMS))]
+        for ru in (False, True):
+            cases += [(f"pyramidal_sgm_lm {name} runner_up={ru}", "pyramidal_sgm_lm", (I, I, 2, PYD_PARAMS, 3, ru)),
+                      (f"pyramidal_sgm_ng_lm {name} runner_up={ru}", "pyramidal_sgm_ng_lm", (I, I, 2, NG_PARAMS, 3, ru))]
+        for matcher, prm in ((0, PYD_PARAMS), (1, NG_PARAMS)):
+            cases += [(f"pyramidal_flow_pp {name} matcher={matcher}", "pyramidal_flow_pp", (I, I, matcher, 2, prm, CHAIN, 0)),
+                      (f"pyramidal_flow_pp_u {name} matcher={matcher}", "pyramidal_flow_pp_u", (I, I, matcher, 2, prm, CHAIN, 0, 5))]
+            cases += [(f"pyramidal_flow_pp_lm {name} matcher={matcher} want_minC2={want}", "pyramidal_flow_pp_lm",
+                       (I, I, matcher, 2, prm, CHAIN, 0, 5 if want else 0, want, 3)) for want in (False, True)]
+    cases += [("epi_postprocess", "epi_postprocess", (m1, m2, m2, m1, 0.3, 1.0, float(D_))),
+              ("vmf", "vmf", (m2,)),
+              ("flow_level_hints", "flow_level_hints", (m2, 3)),
+              ("flow_fb_check", "flow_fb_check", (m2, m2, 2.0)),
+              ("stereo_sgm_pp", "stereo_sgm_pp", (img, img, D_, 0, 6, 64, 4, 1, -1, 0, [0.0] * len(torch_ops.STEREO_PP_FIELDS), 1)),
+              ("stereo_fb_check fused=0", "stereo_fb_check", (m1, m1, 0, 0, -1, 2.0)),
+              ("stereo_fb_check fused=1", "stereo_fb_check", (m1, m1, 1, 0, -1, 2.0)),
+              ("uniqueness_filter", "uniqueness_filter", (m1, cost, cost, 5)),
+              ("uniqueness_filter_planes planes=1", "uniqueness_filter_planes", (m1, cost, cost, 5, 1)),
+              ("uniqueness_filter_planes planes=2", "uniqueness_filter_planes", (m2, cost, cost, 5, 2))]
+    return cases
+
+
+def _live_schemas():
+    return {name: str(getattr(torch.ops.fsgm, name).default._schema) for name in dir(torch.ops.fsgm)
+            if hasattr(getattr(torch.ops.fsgm, name), "default")}
+
+
+def _live_fake_outputs():
+    with _fake_mode():
+        res = {}
+        for label, op, args in _fake_cases():
+            r = getattr(torch.ops.fsgm, op)(*args)
+            res[label] = " ".join(str(o.dtype).removeprefix("torch.") + str(list(o.shape)).replace(" ", "")
+                                  for o in (r if isinstance(r, tuple) else (r,)))
+    return res
+
+
+def test_every_op_keeps_its_schema_and_its_fakes_outputs():
+    """SCHEMAS and FAKE_OUTPUTS were printed by _live_schemas() / _live_fake_outputs() on the commit before the op bodies were shared
+    (every op of the package is in both), so a change of an op's name, arguments, defaults or outputs shows here."""
+    live = _live_schemas()
+    assert sorted(live) == sorted(SCHEMAS)
+    for name in SCHEMAS:
+        assert live[name] == SCHEMAS[name], name
+    with _fake_mode():
+        assert {op for _, op, _ in _fake_cases()} == set(SCHEMAS)
+    got = _live_fake_outputs()
+    assert list(got) == list(FAKE_OUTPUTS)
+    for label in FAKE_OUTPUTS:
+        assert got[label] == FAKE_OUTPUTS[label], label
