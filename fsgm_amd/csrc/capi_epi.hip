@@ -368,6 +368,8 @@ static fsgm_status epi_plan_args(int W, int H, int D, int batch, const fsgm_epi_
     FSGM_REQUIRE(W >= 1 && H >= 1, "fsgm_epi_plan_create: width/height must be >= 1 (got %d x %d)", W, H);
     FSGM_REQUIRE(D >= 1, "fsgm_epi_plan_create: dMax must be >= 1 (got %d)", D);
     FSGM_REQUIRE(batch >= 1, "fsgm_epi_plan_create: batch must be >= 1");
+    // (the line, census, cost, WTA and sweep kernels take the frame as blockIdx.y / .z)
+    if (batch > 65535) return fail(FSGM_ERR_UNSUPPORTED, "fsgm_epi_plan_create: batch %d exceeds 65535 frames (the frame is a grid dimension)", batch);
     FSGM_REQUIRE(pr.paths == 4 || pr.paths == 8, "fsgm_epi_plan_create: paths must be 4 or 8 (got %d)", pr.paths);
     if (pr.fb_check && D > 511)
         return fail(FSGM_ERR_UNSUPPORTED, "fb_check needs dMax <= 511 (bestD must stay below INVALID_DISPARITY)");

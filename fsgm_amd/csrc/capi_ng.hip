@@ -90,6 +90,7 @@ void fsgm_ng_shutdown_internal(void) {
 // minC2s: null (the plain call), or one non-null pointer per frame (the _ru forms: the WTA kernel with the runner-up cost)
 static fsgm_status ng_batch_host(int32_t n, const fsgm_ng_in* in, const fsgm_ng_out* out, uint32_t* const* minC2s, bool ru, int32_t device) {
     FSGM_REQUIRE(n >= 1 && in && out && (minC2s || !ru), "fsgm_calc_pyd_cost_sgm_ng: null argument");
+    if (n > 65535) return fail(FSGM_ERR_UNSUPPORTED, "fsgm_calc_pyd_cost_sgm_ng: n_frames %d exceeds 65535 (the frame is a grid dimension)", n);
     const fsgm_ng_in& a = in[0];
     for (int i = 0; i < n; i++) {
         FSGM_REQUIRE(!ru || minC2s[i], "fsgm_calc_pyd_cost_sgm_ng: frame %d has a null minC2", i);
@@ -205,6 +206,7 @@ int64_t fsgm_sgm_ng_rand_draws(int32_t W, int32_t H) { return (int64_t)W * H * 8
 
 fsgm_status fsgm_calc_cost_sgm_ng_batch_host(int32_t n, const fsgm_otf_in* in, const fsgm_otf_out* out, int32_t device) {
     FSGM_REQUIRE(n >= 1 && in && out, "fsgm_calc_cost_sgm_ng: null argument");
+    if (n > 65535) return fail(FSGM_ERR_UNSUPPORTED, "fsgm_calc_cost_sgm_ng: n_frames %d exceeds 65535 (the frame is a grid dimension)", n);
     const int W = in[0].width, H = in[0].height;
     FSGM_REQUIRE(W >= 1 && H >= 1, "bad image size");
     for (int i = 0; i < n; i++) {

@@ -76,6 +76,8 @@ fsgm_status fsgm::pyd_plan_create_flags(fsgm_pyd_plan** out, int32_t W, int32_t 
                  "indexes it with image coordinates (calc_pyd_cost_sgm.cpp:388-389)", mvW, mvH, W, H);
     { const fsgm_status ws = pyd_check_sides(rX, rY, rAgg); if (ws != FSGM_OK) return ws; }
     FSGM_REQUIRE(batch >= 1, "batch must be >= 1");
+    // (the cost, aggregation and WTA kernels take the frame as blockIdx.y)
+    if (batch > 65535) return fail(FSGM_ERR_UNSUPPORTED, "fsgm_pyd_plan_create: batch %d exceeds 65535 frames (the frame is a grid dimension)", batch);
     { const fsgm_status ws = pyd_check_count(rX, rY); if (ws != FSGM_OK) return ws; }
     const long long D = (long long)(2 * rX + 1) * (2 * rY + 1);
     if ((double)W * H * D >= 2147483648.0) return fail(FSGM_ERR_UNSUPPORTED, "cost volume exceeds 2^31 voxels per frame");
@@ -344,6 +346,7 @@ void fsgm_pyd_shutdown_internal(void) { g_pyd.clear(); }
 // minC2s: null (the plain call), or one non-null pointer per frame (the _ru form: a cached plan of its own, the switch on)
 static fsgm_status pyd_batch_host(int32_t n, const fsgm_pyd_in* in, const fsgm_pyd_out* out, uint32_t* const* minC2s, bool ru, int32_t device) {
     FSGM_REQUIRE(n >= 1 && in && out && (minC2s || !ru), "fsgm_calc_pyd_cost_sgm: null argument");
+    if (n > 65535) return fail(FSGM_ERR_UNSUPPORTED, "fsgm_calc_pyd_cost_sgm: n_frames %d exceeds 65535 (the frame is a grid dimension)", n);
     const fsgm_pyd_in& a = in[0];
     for (int i = 0; i < n; i++) {
         FSGM_REQUIRE(!ru || minC2s[i], "fsgm_calc_pyd_cost_sgm: frame %d has a null minC2", i);

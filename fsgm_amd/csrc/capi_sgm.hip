@@ -44,6 +44,7 @@ static fsgm_status sgm_args(const char* who, int32_t n, const uint8_t* C, int32_
     }
     if ((double)W * H * D >= 2147483648.0)
         return fail(FSGM_ERR_UNSUPPORTED, "%s: cost volume %d x %d x %d exceeds 2^31 voxels per frame", who, W, H, D);
+    if (n > 65535) return fail(FSGM_ERR_UNSUPPORTED, "%s: n_frames %d exceeds 65535 (the frame is a grid dimension)", who, n);
     *c = SgmCall{n, W, H, D, P1, P2, sp, C, sp.adaptive_p2 ? guide : nullptr, bestD, minC, S, ru ? minC2 : nullptr, exact ? 1 : 0};
     return FSGM_OK;
 }

@@ -49,6 +49,8 @@ fsgm_status sgm2d_args(const char* who, int32_t n, const uint8_t* C, int32_t W, 
     const int D = (2 * rX + 1) * (2 * rY + 1);
     if ((double)W * H * D >= 2147483648.0)
         return fail(FSGM_ERR_UNSUPPORTED, "%s: cost volume %d x %d x %d exceeds 2^31 voxels per frame", who, W, H, D);
+    // (the ingest, aggregation, WTA and flow kernels take the frame as blockIdx.y)
+    if (n > 65535) return fail(FSGM_ERR_UNSUPPORTED, "%s: n_frames %d exceeds 65535 (the frame is a grid dimension)", who, n);
     const fsgm_sgm2d_params sp = prm ? *prm : fsgm_sgm2d_params_default();
     FSGM_REQUIRE(layout_ok(sp.layout), "%s: layout must be FSGM_COST2D_LAYOUT_HWD (0), _DHW (1) or _DHW_YX (2), got %d", who, sp.layout);
     FSGM_REQUIRE(sp.cost_bound >= 1 && sp.cost_bound <= 255, "%s: cost_bound must be 1..255 (got %d)", who, sp.cost_bound);

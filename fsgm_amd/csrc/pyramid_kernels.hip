@@ -103,7 +103,11 @@ __global__ __launch_bounds__(256) void pyr_upsample2_kernel(const double* __rest
 }
 
 void launch_pyr_upsample2(hipStream_t st, const double* flow, double* next, int W, int H, int frames, size_t next_frame_stride) {
-    hipLaunchKernelGGL(pyr_upsample2_kernel, dim3((4 * W * H + 255) / 256, frames), dim3(256), 0, st, flow, next, W, H, next_frame_stride);
+    constexpr int MAX_GRID_Y = 65535;                        // the frame is blockIdx.y: more frames take one launch per 65535
+    const size_t np = (size_t)W * H;
+    for (int f0 = 0; f0 < frames; f0 += MAX_GRID_Y)
+        hipLaunchKernelGGL(pyr_upsample2_kernel, dim3((4 * W * H + 255) / 256, frames - f0 < MAX_GRID_Y ? frames - f0 : MAX_GRID_Y), dim3(256), 0, st,
+                           flow + (size_t)f0 * 2 * np, next + (size_t)f0 * next_frame_stride, W, H, next_frame_stride);
 }
 
 // pyramidal_sgm.m:70-72 with the commented-out lines :70-71 live: medfilt2(mv(:,:,c), [S S]) of both channels, then

@@ -217,3 +217,72 @@ def test_device_list_helpers():
         maps = synth.epi_maps(16, 8, "axis")
         with pytest.raises(fsgm_amd.FsgmError):
             calc_cost_sgm_batch([(I1, I2) + maps] * 2, 8, 0.3, 6, 64, devices=[0, 0])
+
+
+def test_batch_wide_refusals_come_before_any_device():
+    """The entries whose kernels index a whole batch's pixels with 32 bits, or take the frame as a grid dimension, refuse a batch
+    beyond that with FSGM_ERR_UNSUPPORTED before anything is allocated or queued: no device is needed to see it."""
+    import ctypes as C
+    from fsgm_amd import _lib
+    lib = _lib.load()
+    lib.fsgm_last_error.restype = C.c_char_p
+    err = lambda: lib.fsgm_last_error().decode()                # noqa: E731
+    P = C.c_void_p(4096)                                         # never dereferenced: the size check comes first
+    i32, f64 = C.c_int32, C.c_double
+    UNSUPPORTED = 4
+    W, H = 32768, 32768                                          # 2^30 pixels a frame
+    # 2 * n * W * H >= 2^31: the flow chain's entries, host and device forms
+    assert lib.fsgm_flow_speckle_filter_host(i32(1), P, i32(W), i32(H), f64(2.0), f64(100.0), P, i32(0)) == UNSUPPORTED and "2^31" in err()
+    assert lib.fsgm_flow_fb_check_host(i32(1), P, P, i32(W), i32(H), f64(2.0), P, i32(0)) == UNSUPPORTED and "2^31" in err()
+    assert lib.fsgm_flow_in_fill_host(i32(1), P, i32(W), i32(H), P, i32(0)) == UNSUPPORTED and "2^31" in err()
+    assert lib.fsgm_flow_fb_check_device(i32(1), P, P, i32(W), i32(H), f64(2.0), P, i32(0), None) == UNSUPPORTED and "2^31" in err()
+    # n * W * H >= 2^31: the uniqueness filter; n * planes * W * H with planes
+    assert lib.fsgm_uniqueness_filter_host(i32(2), P, P, P, i32(W), i32(H), i32(10), P, i32(0)) == UNSUPPORTED and "2^31" in err()
+    assert lib.fsgm_uniqueness_filter_planes_host(i32(1), P, P, P, i32(W), i32(H), i32(2), i32(10), P, i32(0)) == UNSUPPORTED and "2^31" in err()
+    # 4 * n * W * H >= 2^31: the level hints, host and device forms, plain and median
+    for size in (0, 3):
+        assert lib.fsgm_flow_level_hints_host(i32(2), P, i32(16384), i32(16384), i32(size), P, i32(0)) == UNSUPPORTED and "2^31" in err()
+        assert lib.fsgm_flow_level_hints_device(i32(2), P, i32(16384), i32(16384), i32(size), P, i32(0), None) == UNSUPPORTED and "2^31" in err()
+    # the frame is a grid dimension of the epipolar plan's kernels: more than 65535 frames are refused at plan creation and by sgm(C)
+    h = C.c_void_p()
+    assert lib.fsgm_epi_plan_create(C.byref(h), i32(8), i32(8), i32(16), i32(65536), None) == UNSUPPORTED and "65535" in err()
+    assert not h.value
+    from fsgm_amd.sgm import _bind
+    _bind(lib)
+    for fn in (lib.fsgm_sgm_device, lib.fsgm_sgm_device_exact):
+        assert fn(65536, P, 8, 8, 16, 6, 64, None, None, P, P, None, None, None) == UNSUPPORTED and "65535" in err()
+    assert lib.fsgm_sgm_batch_host(65536, P, 8, 8, 16, 6, 64, None, None, P, P, None) == UNSUPPORTED and "65535" in err()
+
+
+def test_batch_wide_refusals_of_the_stereo_chain_and_the_2d_matchers():
+    """map_args' n * W * H >= 2^31 of the rectified chain's entries (the width limit of 8192 comes first, so the frames stay
+    narrower), and the 65535-frame bound of the entries whose kernels take the frame as blockIdx.y: sgm2d, the 2-D matcher's plan
+    and batch form, the neighbour-guided batch forms.  (The pyramid drivers bound their batch at 4096 / 1024: max_batch.)"""
+    import ctypes as C
+    from fsgm_amd import _lib
+    lib = _lib.load()
+    lib.fsgm_last_error.restype = C.c_char_p
+    err = lambda: lib.fsgm_last_error().decode()                # noqa: E731
+    P = C.c_void_p(4096)                                         # never dereferenced: the size checks come first
+    i32, f64 = C.c_int32, C.c_double
+    UNSUPPORTED = 4
+    n, W, H = 64, 8192, 4096                                     # exactly 2^31 pixels
+    assert lib.fsgm_stereo_fb_check_host(i32(n), P, P, i32(W), i32(H), i32(0), i32(-1), f64(2.0), P, None, i32(0)) == UNSUPPORTED and "2^31" in err()
+    assert lib.fsgm_stereo_fb_check_device(i32(n), P, P, i32(W), i32(H), i32(0), i32(-1), f64(2.0), P, None, i32(0), None, None) == UNSUPPORTED and "2^31" in err()
+    assert lib.fsgm_stereo_disp_from_first_host(i32(n), P, i32(W), i32(H), i32(0), i32(-1), P, i32(0)) == UNSUPPORTED and "2^31" in err()
+    assert lib.fsgm_stereo_disp_from_first_device(i32(n), P, i32(W), i32(H), i32(0), i32(-1), P, i32(0), None, None) == UNSUPPORTED and "2^31" in err()
+    assert lib.fsgm_stereo_sgm_pp_device(i32(n), P, P, i32(W), i32(H), i32(16), i32(6), i32(64), None, None, i32(0), None, P, P, P, P, P, None,
+                                         None) == UNSUPPORTED and "2^31" in err()
+    # more than 65535 frames
+    big = i32(65536)
+    assert lib.fsgm_sgm2d_device(big, P, i32(4), i32(4), i32(1), i32(1), i32(6), i32(32), None, None, i32(0), i32(0), None, P, P, P, None, None,
+                                 None, None) == UNSUPPORTED and "65535" in err()
+    assert lib.fsgm_sgm2d_batch_host(big, P, i32(4), i32(4), i32(1), i32(1), i32(6), i32(32), None, None, i32(0), i32(0), None, P, P, P, None,
+                                     None) == UNSUPPORTED and "65535" in err()
+    h = C.c_void_p()
+    assert lib.fsgm_pyd_plan_create(C.byref(h), i32(4), i32(4), i32(4), i32(4), i32(1), i32(1), i32(2), big, i32(0)) == UNSUPPORTED and "65535" in err()
+    assert not h.value
+    for fn in (lib.fsgm_calc_pyd_cost_sgm_batch_host, lib.fsgm_calc_pyd_cost_sgm_ng_batch_host, lib.fsgm_calc_cost_sgm_ng_batch_host):
+        # (another module may have bound the structs' pointer types by now: the fake pointer in whatever type is asked for)
+        a, b = (C.cast(P, fn.argtypes[k]) if fn.argtypes else P for k in (1, 2))
+        assert fn(big, a, b, i32(0)) == UNSUPPORTED and "65535" in err()
