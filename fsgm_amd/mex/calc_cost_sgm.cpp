@@ -34,12 +34,27 @@ static void batch_call(int nlhs, mxArray* plhs[], const mxArray* prhs[]) {
     const double* off = need_f64(fn, prhs[6], "offsetFromPosD0", W * H * n);
     const int P1 = need_int(fn, prhs[7], "P1"), P2 = need_int(fn, prhs[8], "P2");
     if (dMax < 1) mexErrMsgIdAndTxt("fsgm:range", "%s: dMax must be >= 1", fn);
-    mxArray* bestD = new_array(W, H, n, mxUINT32_CLASS);
-    mxArray* minC = new_array(W, H, n, mxUINT32_CLASS);
+    // the environment is an argument too: read and refused before anything is created
+    fsgm_epi_params prm = fsgm_epi_params_default();
+    prm.device = fsgm_env_int("FSGM_DEVICE", 0);
+    prm.paths = fsgm_env_int("FSGM_EPI_PATHS", 4);
+    prm.fb_check = fsgm_env_int("FSGM_EPI_FB_CHECK", 0) != 0;
+    int32_t devs[64];
+    const char* list = getenv("FSGM_DEVICES");
+    int32_t nd_list = (list && *list) ? fsgm_parse_device_list(list, devs, 64) : 0;
+    if (nd_list < 0) mexErrMsgIdAndTxt("fsgm:invalid", "%s: FSGM_DEVICES=\"%s\" is not a list of device ordinals", fn, list);
+    if (nd_list == 0) { devs[0] = prm.device; nd_list = 1; }
+    fsgm_epi_options opt = fsgm_epi_options_default();
+    opt.adaptive_p2 = fsgm_env_int("FSGM_EPI_ADAPTIVE_P2", 0) != 0;
+    if (opt.adaptive_p2 && nd_list > 1)
+        mexErrMsgIdAndTxt("fsgm:unsupported", "%s: FSGM_EPI_ADAPTIVE_P2=1 is not offered with a device list (FSGM_DEVICES)", fn);
+    Created made;
+    mxArray* bestD = made.add(new_array(W, H, n, mxUINT32_CLASS));
+    mxArray* minC = made.add(new_array(W, H, n, mxUINT32_CLASS));
     plhs[0] = bestD;
     if (nlhs > 1) plhs[1] = minC;
-    if (nlhs > 2) plhs[2] = new_array(W, H, n, mxUINT8_CLASS);
-    if (nlhs > 3) plhs[3] = new_array(W, H, n, mxUINT32_CLASS);
+    if (nlhs > 2) plhs[2] = made.add(new_array(W, H, n, mxUINT8_CLASS));
+    if (nlhs > 3) plhs[3] = made.add(new_array(W, H, n, mxUINT32_CLASS));
     std::vector<fsgm_epi_in> in(n);
     std::vector<fsgm_epi_out> out(n);
     const size_t NP = W * H;
@@ -52,23 +67,12 @@ static void batch_call(int nlhs, mxArray* plhs[], const mxArray* prhs[]) {
         out[i].conf = nlhs > 2 ? (uint8_t*)mxGetData(plhs[2]) + i * NP : NULL;
         out[i].bestD2 = nlhs > 3 ? (uint32_t*)mxGetData(plhs[3]) + i * NP : NULL;
     }
-    fsgm_epi_params prm = fsgm_epi_params_default();
-    prm.device = fsgm_env_int("FSGM_DEVICE", 0);
-    prm.paths = fsgm_env_int("FSGM_EPI_PATHS", 4);
-    prm.fb_check = fsgm_env_int("FSGM_EPI_FB_CHECK", 0) != 0;
-    int32_t devs[64];
-    const char* list = getenv("FSGM_DEVICES");
-    int32_t nd_list = (list && *list) ? fsgm_parse_device_list(list, devs, 64) : 0;
-    if (nd_list < 0) mexErrMsgIdAndTxt("fsgm:invalid", "%s: FSGM_DEVICES=\"%s\" is not a list of device ordinals", fn, list);
-    if (nd_list == 0) { devs[0] = prm.device; nd_list = 1; }
-    fsgm_epi_options opt = fsgm_epi_options_default();
-    opt.adaptive_p2 = fsgm_env_int("FSGM_EPI_ADAPTIVE_P2", 0) != 0;
-    if (opt.adaptive_p2 && nd_list > 1) mexErrMsgIdAndTxt("fsgm:unsupported", "%s: FSGM_EPI_ADAPTIVE_P2=1 is not offered with a device list", fn);
     fsgm_register_atexit();
     if (opt.adaptive_p2) prm.device = devs[0];
     const fsgm_status st = opt.adaptive_p2 ? fsgm_calc_cost_sgm_batch_host_opts((int32_t)n, in.data(), out.data(), &prm, &opt)
                                            : fsgm_calc_cost_sgm_batch_devices_host((int32_t)n, in.data(), out.data(), &prm, nd_list, devs);
-    if (nlhs <= 1) mxDestroyArray(minC);
+    if (st != FSGM_OK) made.drop_all(nlhs, plhs);
+    else if (nlhs <= 1) mxDestroyArray(minC);
     check_status(fn, st);
 }
 
@@ -92,12 +96,13 @@ extern "C" void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* 
 
     // outputs as the reference creates them (:569-572); conf and bestD2 stay zero because the
     // forward-backward check is commented out there (:589-590)
-    mxArray* bestD = new_array(W, H, 1, mxUINT32_CLASS);
-    mxArray* minC = new_array(W, H, 1, mxUINT32_CLASS);
+    Created made;
+    mxArray* bestD = made.add(new_array(W, H, 1, mxUINT32_CLASS));
+    mxArray* minC = made.add(new_array(W, H, 1, mxUINT32_CLASS));
     plhs[0] = bestD;
     if (nlhs > 1) plhs[1] = minC;
-    if (nlhs > 2) plhs[2] = new_array(W, H, 1, mxUINT8_CLASS);
-    if (nlhs > 3) plhs[3] = new_array(W, H, 1, mxUINT32_CLASS);
+    if (nlhs > 2) plhs[2] = made.add(new_array(W, H, 1, mxUINT8_CLASS));
+    if (nlhs > 3) plhs[3] = made.add(new_array(W, H, 1, mxUINT32_CLASS));
 
     fsgm_epi_out out;
     out.bestD = (uint32_t*)mxGetData(bestD);
@@ -113,6 +118,7 @@ extern "C" void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* 
     opt.adaptive_p2 = fsgm_env_int("FSGM_EPI_ADAPTIVE_P2", 0) != 0;
     fsgm_register_atexit();
     const fsgm_status st = fsgm_calc_cost_sgm_host_opts(&in, &out, &prm, &opt);
-    if (nlhs <= 1) mxDestroyArray(minC);
+    if (st != FSGM_OK) made.drop_all(nlhs, plhs);
+    else if (nlhs <= 1) mxDestroyArray(minC);
     check_status(fn, st);
 }

@@ -27,12 +27,13 @@ extern "C" void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* 
     if (in.dMax < 1) mexErrMsgIdAndTxt("fsgm:range", "%s: dMax must be >= 1", fn);
 
     // outputs as the reference creates them (:569-572); conf and bestD2 stay zero unless FSGM_EPI_FB_CHECK=1
-    mxArray* bestD = new_array(W, H, 1, mxUINT32_CLASS);
-    mxArray* minC = new_array(W, H, 1, mxUINT32_CLASS);
+    Created made;
+    mxArray* bestD = made.add(new_array(W, H, 1, mxUINT32_CLASS));
+    mxArray* minC = made.add(new_array(W, H, 1, mxUINT32_CLASS));
     plhs[0] = bestD;
     if (nlhs > 1) plhs[1] = minC;
-    if (nlhs > 2) plhs[2] = new_array(W, H, 1, mxUINT8_CLASS);
-    if (nlhs > 3) plhs[3] = new_array(W, H, 1, mxUINT32_CLASS);
+    if (nlhs > 2) plhs[2] = made.add(new_array(W, H, 1, mxUINT8_CLASS));
+    if (nlhs > 3) plhs[3] = made.add(new_array(W, H, 1, mxUINT32_CLASS));
 
     fsgm_epi_out out;
     out.bestD = (uint32_t*)mxGetData(bestD);
@@ -48,6 +49,7 @@ extern "C" void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* 
     opt.adaptive_p2 = fsgm_env_int("FSGM_EPI_ADAPTIVE_P2", 0) != 0;
     fsgm_register_atexit();
     const fsgm_status st = fsgm_calc_cost_sgm_linear_host_opts(&in, &out, &prm, &opt);
-    if (nlhs <= 1) mxDestroyArray(minC);
+    if (st != FSGM_OK) made.drop_all(nlhs, plhs);
+    else if (nlhs <= 1) mxDestroyArray(minC);
     check_status(fn, st);
 }

@@ -26,12 +26,19 @@ extern "C" void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* 
     in.enableDiagnalPath = need_scalar(fn, prhs[9], "enableDiagnalPath") != 0;  // :464 bool
     in.totalPass = need_int(fn, prhs[10], "totalPass");
     in.adpativeP2 = need_scalar(fn, prhs[11], "adpativeP2") != 0;               // :466 bool
+    // the window the library accepts (README: sides 2*half+1 up to 63, at most 1024 candidates), refused here so that the
+    // product below stays far inside int
+    if (in.halfSearchWinSizeX > 31) mexErrMsgIdAndTxt("fsgm:range", "%s: halfSearchWinSizeX must be at most 31 (a side of 63)", fn);
+    if (in.halfSearchWinSizeY > 31) mexErrMsgIdAndTxt("fsgm:range", "%s: halfSearchWinSizeY must be at most 31 (a side of 63)", fn);
     const int dMax = (2 * in.halfSearchWinSizeX + 1) * (2 * in.halfSearchWinSizeY + 1);
+    if (dMax > 1024)
+        mexErrMsgIdAndTxt("fsgm:range", "%s: halfSearchWinSizeX and halfSearchWinSizeY give %d candidates, at most 1024", fn, dMax);
     mexPrintf("width: %d, height: %d, dMax: %d, winRadiusAgg: %d\n", (int)W, (int)H, dMax, in.aggHalfWinSize);   // :491
 
-    mxArray* bestD = new_array(W, H, 1, mxUINT32_CLASS);              // :474-476
-    mxArray* minC = new_array(W, H, 1, mxUINT32_CLASS);
-    mxArray* mvSub = new_array(W, H, 2, mxDOUBLE_CLASS);
+    Created made;
+    mxArray* bestD = made.add(new_array(W, H, 1, mxUINT32_CLASS));    // :474-476
+    mxArray* minC = made.add(new_array(W, H, 1, mxUINT32_CLASS));
+    mxArray* mvSub = made.add(new_array(W, H, 2, mxDOUBLE_CLASS));
     plhs[0] = bestD;
     if (nlhs > 1) plhs[1] = minC;
     if (nlhs > 2) plhs[2] = mvSub;
@@ -42,7 +49,10 @@ extern "C" void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* 
     out.C = NULL; out.S = NULL;
     fsgm_register_atexit();
     const fsgm_status st = fsgm_calc_pyd_cost_sgm_host(&in, &out, fsgm_env_int("FSGM_DEVICE", 0));
-    if (nlhs <= 1) mxDestroyArray(minC);
-    if (nlhs <= 2) mxDestroyArray(mvSub);
+    if (st != FSGM_OK) made.drop_all(nlhs, plhs);
+    else {
+        if (nlhs <= 1) mxDestroyArray(minC);
+        if (nlhs <= 2) mxDestroyArray(mvSub);
+    }
     check_status(fn, st);
 }

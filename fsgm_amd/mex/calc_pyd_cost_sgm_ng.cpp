@@ -23,12 +23,16 @@ extern "C" void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* 
     in.subPixelRefine = need_int(fn, prhs[5], "subPixelRefine");
     in.P1 = need_int(fn, prhs[6], "P1");
     in.P2 = need_int(fn, prhs[7], "P2");
-    if (in.halfSearchWinSize < 0 || in.aggSize < 0) mexErrMsgIdAndTxt("fsgm:range", "%s: window sizes must be >= 0", fn);
+    if (in.halfSearchWinSize < 0 || in.aggSize < 0)
+        mexErrMsgIdAndTxt("fsgm:range", "%s: halfSearchWinSize and aggSize must be >= 0", fn);
+    // 9 * (2*half+1)^2 candidates, at most 512 in the library: refused here so that the product below stays inside int
+    if (in.halfSearchWinSize > 3) mexErrMsgIdAndTxt("fsgm:range", "%s: halfSearchWinSize must be at most 3 (441 candidates)", fn);
     const int cph = (2 * in.halfSearchWinSize + 1) * (2 * in.halfSearchWinSize + 1);
     mexPrintf("width: %d, height: %d, dMax: %d, winRadiusAgg: %d\n", (int)W, (int)H, 9 * cph, in.aggSize / 2);   // :499
 
-    mxArray* minC = new_array(W, H, 1, mxUINT32_CLASS);               // :476-477
-    mxArray* flow = new_array(W, H, 2, mxDOUBLE_CLASS);
+    Created made;
+    mxArray* minC = made.add(new_array(W, H, 1, mxUINT32_CLASS));     // :476-477
+    mxArray* flow = made.add(new_array(W, H, 2, mxDOUBLE_CLASS));
     plhs[0] = minC;
     if (nlhs > 1) plhs[1] = flow;
     fsgm_ng_out out;
@@ -37,6 +41,7 @@ extern "C" void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* 
     out.S = NULL;
     fsgm_register_atexit();
     const fsgm_status st = fsgm_calc_pyd_cost_sgm_ng_host(&in, &out, fsgm_env_int("FSGM_DEVICE", 0));
-    if (nlhs <= 1) mxDestroyArray(flow);
+    if (st != FSGM_OK) made.drop_all(nlhs, plhs);
+    else if (nlhs <= 1) mxDestroyArray(flow);
     check_status(fn, st);
 }

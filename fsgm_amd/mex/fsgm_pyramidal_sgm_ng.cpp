@@ -43,19 +43,21 @@ extern "C" void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* 
     prm.subPixelRefine = fsgm_env_int("FSGM_NG_SUBPIXEL", prm.subPixelRefine);
     prm.device = fsgm_env_int("FSGM_DEVICE", 0);
 
-    mxArray* flow = new_array(W, H, 2, mxDOUBLE_CLASS);
-    mxArray* minC = new_array(W, H, 1, mxUINT32_CLASS);
+    Created made;
+    mxArray* flow = made.add(new_array(W, H, 2, mxDOUBLE_CLASS));
+    mxArray* minC = made.add(new_array(W, H, 1, mxUINT32_CLASS));
     plhs[0] = flow;
     if (nlhs > 1) plhs[1] = minC;
     double* lv[16] = {0};
     size_t w = W, h = H;
     for (int l = 0; l < prm.numPyd; l++) {
-        if (nlhs > 2 + l) { plhs[2 + l] = new_array(w, h, 2, mxDOUBLE_CLASS); lv[l] = mxGetPr(plhs[2 + l]); }
+        if (nlhs > 2 + l) { plhs[2 + l] = made.add(new_array(w, h, 2, mxDOUBLE_CLASS)); lv[l] = mxGetPr(plhs[2 + l]); }
         w = (w + 1) / 2; h = (h + 1) / 2;                                        // impyramid: ceil(size/2)
     }
     fsgm_register_atexit();
     const fsgm_status st = fsgm_pyramidal_sgm_ng_host(I0, I1, (int32_t)W, (int32_t)H, (int32_t)ch, &prm, mxGetPr(flow),
                                                       (uint32_t*)mxGetData(minC), lv);
-    if (nlhs <= 1) mxDestroyArray(minC);
+    if (st != FSGM_OK) made.drop_all(nlhs, plhs);
+    else if (nlhs <= 1) mxDestroyArray(minC);
     check_status(fn, st);
 }

@@ -1,4 +1,4 @@
-// gateway_common.h -- argument plumbing shared by the four mexFunction gateways.
+// gateway_common.h -- argument plumbing shared by the mexFunction gateways.
 // The reference validates nothing (a wrong class or size is a crash); the gateways check every
 // argument and raise fsgm:* errors through mexErrMsgIdAndTxt (SURVEY 8b "errors").
 #pragma once
@@ -63,6 +63,19 @@ static inline mxArray* new_array(size_t W, size_t H, size_t planes, mxClassID cl
     const mwSize dims[3] = {W, H, planes};
     return mxCreateNumericArray(planes > 1 ? 3 : 2, dims, cls, mxREAL);
 }
+
+// The arrays one call creates.  A call the library refuses hands nothing back: drop_all() frees them before the error is raised
+// (MATLAB would at the error; a host without its memory manager would keep them).
+struct Created {
+    mxArray* a[24];
+    int n = 0;
+    mxArray* add(mxArray* x) { a[n++] = x; return x; }
+    void drop_all(int nlhs, mxArray* plhs[]) {
+        for (int i = 0; i < n; i++) mxDestroyArray(a[i]);
+        n = 0;
+        for (int i = 0; i < (nlhs > 1 ? nlhs : 1); i++) plhs[i] = NULL;
+    }
+};
 
 static inline void check_status(const char* fn, fsgm_status st) {
     if (st == FSGM_OK) return;

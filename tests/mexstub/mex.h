@@ -14,7 +14,10 @@ extern "C" {
 #endif
 
 typedef size_t mwSize;
-typedef enum { mxUNKNOWN_CLASS = 0, mxDOUBLE_CLASS = 6, mxUINT8_CLASS = 9, mxUINT32_CLASS = 13 } mxClassID;
+typedef enum {                                   /* MATLAB's own numbering */
+    mxUNKNOWN_CLASS = 0, mxLOGICAL_CLASS = 3, mxDOUBLE_CLASS = 6, mxSINGLE_CLASS = 7, mxINT8_CLASS = 8, mxUINT8_CLASS = 9,
+    mxINT16_CLASS = 10, mxUINT16_CLASS = 11, mxINT32_CLASS = 12, mxUINT32_CLASS = 13, mxINT64_CLASS = 14, mxUINT64_CLASS = 15
+} mxClassID;
 typedef enum { mxREAL = 0, mxCOMPLEX = 1 } mxComplexity;
 typedef struct mxArray_tag mxArray;
 
@@ -23,7 +26,7 @@ mxArray*  mxCreateDoubleScalar(double v);
 void      mxDestroyArray(mxArray* a);
 void*     mxGetData(const mxArray* a);
 double*   mxGetPr(const mxArray* a);
-double    mxGetScalar(const mxArray* a);
+double    mxGetScalar(const mxArray* a);           /* first element, converted to double like MATLAB */
 size_t    mxGetM(const mxArray* a);
 size_t    mxGetN(const mxArray* a);              /* product of dims 2..end, like MATLAB */
 mwSize    mxGetNumberOfDimensions(const mxArray* a);
@@ -42,6 +45,7 @@ const char* mexstub_last_error_id(void);
 const char* mexstub_last_error_msg(void);
 const char* mexstub_printed(void);
 void        mexstub_run_atexit(void);
+long        mexstub_live_arrays(void);               /* mxArrays created and not yet destroyed */
 
 #ifdef __cplusplus
 }
