@@ -6,12 +6,12 @@ multi-path SGM aggregation hot path, behind the reference's MEX argument lists.
 
 Everything computes on the GPU through libfsgm_hip.so (C ABI in include/fsgm.h).
 """
-from .sgm import sgm_batch  # noqa: F401  (ahead of .epi: the name fsgm_amd.sgm stays the function imported below, not this submodule)
+from .sgm import sgm_batch, sgm_batch_float  # noqa: F401  (ahead of .epi: the name fsgm_amd.sgm stays the function imported below, not this submodule)
 from .epi import (calc_cost_sgm, calc_cost_sgm_batch, EpiPlan, epipolar_maps, epipolar_sgm_of, epipolar_flow_pp, epipolar_from_F,  # noqa: F401
                   census, sgm, auto_pipeline, calc_cost_sgm_linear, calc_cost_sgm_linear_batch, stereo_sgm, stereo_maps,
                   uniqueness_filter, NO_RUNNER_UP)
 from .pyd import calc_pyd_cost_sgm, calc_pyd_cost_sgm_batch, PydPlan  # noqa: F401
-from .sgm2d import sgm2d_batch  # noqa: F401
+from .sgm2d import sgm2d_batch, sgm2d_batch_float  # noqa: F401
 from .pyramid import (pyramidal_sgm, pyramidal_sgm_ng, pyramidal_sgm_batch, pyramidal_sgm_ng_batch, PyramidPlan, NgPyramidPlan,  # noqa: F401
                       pyramidal_flow_pp, flow_level_hints)
 from .post import (speckle_filter, calc_disp_from_first, forward_backward_check, scanline_in_fill, vzInd2Disp, vmf,  # noqa: F401

@@ -1529,10 +1529,18 @@ fsgm_status sgm_run_host(const SgmCall& c, const int* cmax) {
             if ((st = fsgm_epi_plan_upload_images(p, f, c.guide + f * NP, c.guide + f * NP)) != FSGM_OK) return st;
     if ((st = prepare(p, FSGM_STAGE_AGGREGATE | FSGM_STAGE_WTA)) != FSGM_OK) return st;
     const bool dhw = c.prm.layout == FSGM_COST_LAYOUT_DHW;       // staged as it came, transposed on the device
-    if (dhw && !p->dIngest) FSGM_HIP(hipMalloc((void**)&p->dIngest, nv));
+    if (dhw && c.fmt.dtype < 0 && !p->dIngest) FSGM_HIP(hipMalloc((void**)&p->dIngest, nv));
+    if (c.fmt.dtype >= 0 && (st = ensure_ingest_flag(p)) != FSGM_OK) return st;
     StreamGuard guard(p->stream);                                // every early exit drains the stream: the copies use caller memory
-    FSGM_HIP(hipMemcpyAsync(dhw ? p->dIngest : p->dC, c.C, nv, hipMemcpyHostToDevice, p->stream));
-    if (dhw) launch_sgm_ingest(p->stream, p->dIngest, p->dC, c.n, c.W, c.H, c.D, FSGM_COST_LAYOUT_DHW, 255, nullptr);
+    if (c.fmt.dtype >= 0) {
+        // a float volume: staged frame by frame, quantised by the kernel the device form runs; the flag is read before any output is written
+        const fsgm_status fs = stage_float_volumes(p->stream, c.C, c.fmt, c.n, p->N, p->dIngestFlag, "fsgm_sgm_float_batch_host",
+            [&](const void* d, int f) { launch_sgm_ingest_float(p->stream, d, c.fmt, p->dC + (size_t)f * p->N, 1, c.W, c.H, c.D, c.prm.layout, c.prm.cost_bound, p->dIngestFlag); });
+        if (fs != FSGM_OK) return fs;
+    } else {
+        FSGM_HIP(hipMemcpyAsync(dhw ? p->dIngest : p->dC, c.C, nv, hipMemcpyHostToDevice, p->stream));
+        if (dhw) launch_sgm_ingest(p->stream, p->dIngest, p->dC, c.n, c.W, c.H, c.D, FSGM_COST_LAYOUT_DHW, 255, nullptr);
+    }
     if ((st = enqueue(p, FSGM_STAGE_AGGREGATE | FSGM_STAGE_WTA)) != FSGM_OK) return st;
     g_sgm_kernel = kPipelineName[p->pipe];
     FSGM_HIP(hipMemcpyAsync(c.bestD, p->dBestD, (size_t)c.n * NP * 4, hipMemcpyDeviceToHost, p->stream));
@@ -1572,7 +1580,8 @@ fsgm_status sgm_run_device(const SgmCall& c, hipStream_t cs, int32_t* status) {
     if ((st = ensure_ingest_flag(p)) != FSGM_OK) return st;
     if (c.S && (st = ensure_tap_buffers(p)) != FSGM_OK) return st;
     return device_call(p->join, cs, p->stream, [&]() -> fsgm_status {
-        launch_sgm_ingest(p->stream, c.C, p->dC, c.n, c.W, c.H, c.D, c.prm.layout, c.prm.cost_bound, p->dIngestFlag);
+        if (c.fmt.dtype >= 0) launch_sgm_ingest_float(p->stream, c.C, c.fmt, p->dC, c.n, c.W, c.H, c.D, c.prm.layout, c.prm.cost_bound, p->dIngestFlag);
+        else launch_sgm_ingest(p->stream, c.C, p->dC, c.n, c.W, c.H, c.D, c.prm.layout, c.prm.cost_bound, p->dIngestFlag);
         if (c.guide) FSGM_HIP(hipMemcpyAsync(p->dI1, c.guide, (size_t)c.n * p->NP, hipMemcpyDeviceToDevice, p->stream));
         Bind<uint32_t> bd(p->dBestD, c.bestD), mc(p->dMinC, c.minC), m2(p->dMinC2, c.minC2);
         const fsgm_status es = enqueue(p, FSGM_STAGE_AGGREGATE | FSGM_STAGE_WTA);
@@ -1610,6 +1619,31 @@ fsgm_status fsgm_epi_plan_ingest_cost_device(fsgm_epi_plan* p, int32_t n, const 
     select_kernel(p);
     return device_call(p->join, cs, p->stream, [&] {
         launch_sgm_ingest(p->stream, C, p->dC, n, p->W, p->H, p->D, layout, cost_bound, p->dIngestFlag);
+        launch_device_status(p->stream, nullptr, p->dIngestFlag, status);
+        return FSGM_OK;
+    });
+}
+
+fsgm_status fsgm_epi_plan_ingest_float_dptr(fsgm_epi_plan* p, int32_t n, const void* C, const fsgm_cost_format* fmt, int32_t layout,
+                                            int32_t cost_bound, void* stream, int32_t* status) {
+    const char* who = "fsgm_epi_plan_ingest_float_dptr";
+    FSGM_REQUIRE(p && C, "%s: null argument", who);
+    CostFormat cf;
+    fsgm_status st = check_cost_format(who, fmt, &cf);
+    if (st != FSGM_OK) return st;
+    FSGM_REQUIRE(n == p->batch, "%s: n_frames %d differs from the plan's batch %d", who, n, p->batch);
+    FSGM_REQUIRE(layout == FSGM_COST_LAYOUT_HWD || layout == FSGM_COST_LAYOUT_DHW,
+                 "%s: layout must be FSGM_COST_LAYOUT_HWD (0) or FSGM_COST_LAYOUT_DHW (1), got %d", who, layout);
+    FSGM_REQUIRE(cost_bound >= 1 && cost_bound <= 255, "%s: cost_bound must be 1..255 (got %d)", who, cost_bound);
+    const hipStream_t cs = (hipStream_t)stream;
+    const size_t es = cost_elem_size(cf.dtype);
+    if ((st = device_check_args(who, p->prm.device, cs, {{C, (size_t)n * p->N * es, es, true, "C"}, {status, 4, 4, false, "status"}})) != FSGM_OK)
+        return st;
+    if ((st = ensure_ingest_flag(p)) != FSGM_OK) return st;
+    p->cmax.assign(n, cost_bound);
+    select_kernel(p);
+    return device_call(p->join, cs, p->stream, [&] {
+        launch_sgm_ingest_float(p->stream, C, cf, p->dC, n, p->W, p->H, p->D, layout, cost_bound, p->dIngestFlag);
         launch_device_status(p->stream, nullptr, p->dIngestFlag, status);
         return FSGM_OK;
     });

@@ -2,6 +2,7 @@
 // cached plans and their pipelines): a checked call.
 #pragma once
 #include "capi_common.h"
+#include "cost_float_ingest.h"
 
 namespace fsgm {
 
@@ -13,9 +14,10 @@ struct SgmCall {
     uint32_t* minC2;                     // the _ru forms' runner-up cost (never NULL there), NULL in the plain forms
     int exact;                           // the _exact forms: exact path arithmetic, P1 and P2 checked to lie in 0..255 (never with minC2)
     int captured = 0;                    // fsgm_sgm_device_exact alone: the caller's stream is being captured into a graph
+    CostFormat fmt;                      // the float forms: C holds elements of fmt.dtype (-1 in the u8 forms), quantised by the ingest
 };
 
-// host pointers; cmax: the largest byte of each frame's volume (none above prm.cost_bound)
+// host pointers; cmax: the largest byte of each frame's volume (none above prm.cost_bound), of a float volume prm.cost_bound
 fsgm_status sgm_run_host(const SgmCall& c, const int* cmax);
 // device pointers, checked (device_check_args) by the caller; cs: the caller's stream
 fsgm_status sgm_run_device(const SgmCall& c, hipStream_t cs, int32_t* status);

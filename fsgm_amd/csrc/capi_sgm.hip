@@ -1,5 +1,5 @@
 // capi_sgm.hip -- C ABI of sgm(C, P1, P2) on batches of caller-supplied cost volumes, in host memory or in HBM (include/fsgm.h:
-// fsgm_sgm_batch_host, fsgm_sgm_device, their _ru and _exact forms).  Everything that can be refused without a device is refused here; the cached plans
+// fsgm_sgm_batch_host, fsgm_sgm_device, their _ru and _exact forms, the float forms).  Everything that can be refused without a device is refused here; the cached plans
 // and their pipelines live in capi_epi.hip (capi_sgm.h).
 #include "capi_sgm.h"
 #include "capi_device.h"
@@ -106,7 +106,55 @@ static fsgm_status sgm_device(const char* who, int32_t n, const uint8_t* C, int3
     return sgm_run_device(c, cs, status);
 }
 
+// The float forms (include/fsgm.h, "Float cost volumes"): the checks of the u8 forms with the format's in front; minC2 is wanted
+// when given, exact is a switch.  The checked call carries the format, and only the ingest launch behind it differs.
+static fsgm_status sgm_float_args(const char* who, int32_t n, const void* C, const fsgm_cost_format* fmt, int32_t W, int32_t H, int32_t D,
+                                  int32_t P1, int32_t P2, const fsgm_sgm_params* prm, const uint8_t* guide, uint32_t* bestD, uint32_t* minC,
+                                  uint32_t* minC2, uint32_t* S, int32_t exact, SgmCall* c) {
+    FSGM_REQUIRE(exact == 0 || exact == 1, "%s: exact must be 0 or 1 (got %d)", who, exact);
+    CostFormat cf;
+    fsgm_status st = check_cost_format(who, fmt, &cf);
+    if (st != FSGM_OK) return st;
+    const bool ru = minC2 != nullptr;
+    if ((st = sgm_args(who, n, static_cast<const uint8_t*>(C), W, H, D, P1, P2, prm, guide, bestD, minC, S, minC2, ru, exact != 0, c)) != FSGM_OK)
+        return st;
+    if (exact && ru) return fail(FSGM_ERR_UNSUPPORTED, "%s: exact path arithmetic has no runner-up cost (pass minC2 = NULL with exact)", who);
+    c->fmt = cf;
+    return FSGM_OK;
+}
+
 extern "C" {
+
+fsgm_status fsgm_sgm_float_batch_host(int32_t n, const void* C, const fsgm_cost_format* fmt, int32_t W, int32_t H, int32_t D, int32_t P1,
+                                      int32_t P2, const fsgm_sgm_params* prm, const uint8_t* guide, uint32_t* bestD, uint32_t* minC,
+                                      uint32_t* minC2, uint32_t* S, int32_t exact) {
+    SgmCall c;
+    const fsgm_status st = sgm_float_args("fsgm_sgm_float_batch_host", n, C, fmt, W, H, D, P1, P2, prm, guide, bestD, minC, minC2, S, exact, &c);
+    if (st != FSGM_OK) return st;
+    // no scan for the true maximum: the declared bound selects the kernels, as in the device forms
+    const std::vector<int> cmax(n, c.prm.cost_bound);
+    return sgm_run_host(c, cmax.data());
+}
+
+fsgm_status fsgm_sgm_float_dptr(int32_t n, const void* C, const fsgm_cost_format* fmt, int32_t W, int32_t H, int32_t D, int32_t P1, int32_t P2,
+                                const fsgm_sgm_params* prm, const uint8_t* guide, uint32_t* bestD, uint32_t* minC, uint32_t* minC2,
+                                uint32_t* S, int32_t exact, void* stream, int32_t* status) {
+    const char* who = "fsgm_sgm_float_dptr";
+    SgmCall c;
+    fsgm_status st = sgm_float_args(who, n, C, fmt, W, H, D, P1, P2, prm, guide, bestD, minC, minC2, S, exact, &c);
+    if (st != FSGM_OK) return st;
+    const size_t np = (size_t)n * W * H, nv = np * D, es = cost_elem_size(c.fmt.dtype);
+    const hipStream_t cs = (hipStream_t)stream;
+    if ((st = device_check_args(who, c.prm.device, cs, {{C, nv * es, es, true, "C"},
+                                                        {c.guide, np, 1, false, "guide"},
+                                                        {bestD, np * 4, 4, true, "bestD"},
+                                                        {minC, np * 4, 4, true, "minC"},
+                                                        {c.minC2, np * 4, 4, false, "minC2"},
+                                                        {S, nv * 4, 4, false, "S"},
+                                                        {status, 4, 4, false, "status"}})) != FSGM_OK)
+        return st;
+    return sgm_run_device(c, cs, status);
+}
 
 fsgm_status fsgm_sgm_batch_host(int32_t n, const uint8_t* C, int32_t W, int32_t H, int32_t D, int32_t P1, int32_t P2,
                                 const fsgm_sgm_params* prm, const uint8_t* guide, uint32_t* bestD, uint32_t* minC, uint32_t* S) {

@@ -1,5 +1,5 @@
 // capi_sgm2d.hip -- C ABI of the 2-D matcher on batches of caller-supplied cost volumes, in host memory or in HBM
-// (include/fsgm.h: fsgm_sgm2d_batch_host, fsgm_sgm2d_device, fsgm_pyd_plan_ingest_cost_device).  Everything that can be
+// (include/fsgm.h: fsgm_sgm2d_batch_host, fsgm_sgm2d_device, fsgm_pyd_plan_ingest_cost_device, and their float forms).  Everything that can be
 // refused without a device is refused first; behind that both forms take one cached aggregation-only fsgm_pyd_plan, bring
 // the volumes into its padded layout with the kernels of sgm2d_ingest.hip and run pyd_enqueue's aggregation and WTA on it.
 #include "capi_common.h"
@@ -7,6 +7,7 @@
 #include "pyd_kernels.h"
 #include "pyd_plan.h"
 #include "pyramid_kernels.h"
+#include "cost_float_ingest.h"
 #include "sgm2d_ingest.h"
 #include <mutex>
 #include <string.h>
@@ -28,6 +29,7 @@ struct Sgm2dCall {
     uint32_t* S;
     uint32_t* minC2;                     // the _ru forms' runner-up cost (never NULL there), NULL in the plain forms; _exact: as given
     bool exact;                          // the _exact forms: exact path arithmetic (fsgm_pyd_plan_set_exact)
+    CostFormat fmt;                      // the float forms: C holds elements of fmt.dtype (-1 in the u8 forms), quantised by the ingest
 };
 
 bool layout_ok(int layout) {
@@ -133,14 +135,18 @@ fsgm_status sgm2d_enqueue(fsgm_pyd_plan* p, uint32_t* dS, double* dFlow) {
 // the host forms; ru: minC2 is wanted (the _ru form, where it is required, or an _exact call that passed one)
 fsgm_status sgm2d_host(const char* who, int32_t n, const uint8_t* C, int32_t W, int32_t H, int32_t rX, int32_t rY, int32_t P1, int32_t P2,
                        const fsgm_sgm2d_params* prm, const double* preMv, int32_t mvW, int32_t mvH, const uint8_t* guide, uint32_t* bestD,
-                       uint32_t* minC, uint32_t* minC2, bool ru, bool exact, double* mvSub, double* flow, uint32_t* S) {
+                       uint32_t* minC, uint32_t* minC2, bool ru, bool exact, double* mvSub, double* flow, uint32_t* S,
+                       const CostFormat& fmt = CostFormat()) {
     Sgm2dCall c;
     fsgm_status st = sgm2d_args(who, n, C, W, H, rX, rY, P1, P2, prm, preMv, mvW, mvH, guide, bestD, minC, mvSub, flow, S, minC2, ru, exact, &c);
     if (st != FSGM_OK) return st;
-    // the true maximum of the batch (every layout holds the same bytes), as fsgm_pyd_plan_upload_cost takes it
+    c.fmt = fmt;
+    const bool is_float = fmt.dtype >= 0;
+    // the true maximum of the batch (every layout holds the same bytes), as fsgm_pyd_plan_upload_cost takes it; a float volume
+    // is not scanned: its declared bound selects the aggregation, as in the device forms
     const size_t NP = (size_t)W * H, ND = NP * (2 * rX + 1) * (2 * rY + 1);
-    int cmax = 0;
-    for (int f = 0; f < n; f++) {
+    int cmax = is_float ? c.prm.cost_bound : 0;
+    for (int f = 0; f < n && !is_float; f++) {
         const uint8_t* v = C + (size_t)f * ND;
         int m = 0;
         for (size_t i = 0; i < ND; i++) m = v[i] > m ? v[i] : m;
@@ -151,13 +157,22 @@ fsgm_status sgm2d_host(const char* who, int32_t n, const uint8_t* C, int32_t W, 
     fsgm_pyd_plan* p = nullptr;
     if ((st = sgm2d_plan(&p, c, cmax)) != FSGM_OK) return st;
     const size_t B = n;
-    if (!p->dIngest) FSGM_HIP(hipMalloc((void**)&p->dIngest, B * ND));
+    if (!is_float && !p->dIngest) FSGM_HIP(hipMalloc((void**)&p->dIngest, B * ND));
+    if (is_float && (st = ensure_ingest_flag(p)) != FSGM_OK) return st;
     if (S && !p->dS) FSGM_HIP(hipMalloc((void**)&p->dS, B * ND * 4));
     if (flow && !p->dFlow) FSGM_HIP(hipMalloc((void**)&p->dFlow, B * NP * 16));
     StreamGuard guard(p->stream);                                // every early exit drains the stream: the copies use caller memory
     // staged as it came, brought into the plan's layout by the kernel the device form runs (the scan above has checked the bound)
-    FSGM_HIP(hipMemcpyAsync(p->dIngest, C, B * ND, hipMemcpyHostToDevice, p->stream));
-    launch_sgm2d_ingest(p->stream, p->dIngest, p->dC, n, W, H, p->Sx, p->Sy, c.prm.layout, 255, nullptr);
+    if (is_float) {
+        // staged frame by frame, quantised by the kernel the device form runs; the flag is read before any output is written
+        const fsgm_status fs = stage_float_volumes(p->stream, C, fmt, n, ND, p->dIngestFlag, who, [&](const void* d, int f) {
+            launch_sgm2d_ingest_float(p->stream, d, fmt, p->dC + (size_t)f * p->N, 1, W, H, p->Sx, p->Sy, c.prm.layout, c.prm.cost_bound, p->dIngestFlag);
+        });
+        if (fs != FSGM_OK) return fs;
+    } else {
+        FSGM_HIP(hipMemcpyAsync(p->dIngest, C, B * ND, hipMemcpyHostToDevice, p->stream));
+        launch_sgm2d_ingest(p->stream, p->dIngest, p->dC, n, W, H, p->Sx, p->Sy, c.prm.layout, 255, nullptr);
+    }
     if (preMv) {
         FSGM_HIP(hipMemcpyAsync(p->dMv, preMv, B * p->MV * 16, hipMemcpyHostToDevice, p->stream));
         p->mv_zero = false;
@@ -180,13 +195,16 @@ fsgm_status sgm2d_host(const char* who, int32_t n, const uint8_t* C, int32_t W, 
 // the device forms; ru as above: minC2 is written where it lies by the WTA itself
 fsgm_status sgm2d_device(const char* who, int32_t n, const uint8_t* C, int32_t W, int32_t H, int32_t rX, int32_t rY, int32_t P1, int32_t P2,
                          const fsgm_sgm2d_params* prm, const double* preMv, int32_t mvW, int32_t mvH, const uint8_t* guide, uint32_t* bestD,
-                         uint32_t* minC, uint32_t* minC2, bool ru, bool exact, double* mvSub, double* flow, uint32_t* S, void* stream, int32_t* status) {
+                         uint32_t* minC, uint32_t* minC2, bool ru, bool exact, double* mvSub, double* flow, uint32_t* S, void* stream, int32_t* status,
+                         const CostFormat& fmt = CostFormat()) {
     Sgm2dCall c;
     fsgm_status st = sgm2d_args(who, n, C, W, H, rX, rY, P1, P2, prm, preMv, mvW, mvH, guide, bestD, minC, mvSub, flow, S, minC2, ru, exact, &c);
     if (st != FSGM_OK) return st;
+    c.fmt = fmt;
     const size_t np = (size_t)n * W * H, nv = np * (2 * rX + 1) * (2 * rY + 1), nmv = (size_t)n * c.mvW * c.mvH;
+    const size_t es = fmt.dtype >= 0 ? cost_elem_size(fmt.dtype) : 1;    // the volume's element size: its alignment
     const hipStream_t cs = (hipStream_t)stream;
-    if ((st = device_check_args(who, c.prm.device, cs, {{C, nv, 1, true, "C"},
+    if ((st = device_check_args(who, c.prm.device, cs, {{C, nv * es, es, true, "C"},
                                                         {preMv, nmv * 16, 8, false, "preMv"},
                                                         {c.guide, np, 1, false, "guide"},
                                                         {bestD, np * 4, 4, true, "bestD"},
@@ -204,7 +222,8 @@ fsgm_status sgm2d_device(const char* who, int32_t n, const uint8_t* C, int32_t W
     if ((st = sgm2d_plan(&p, c, c.prm.cost_bound)) != FSGM_OK) return st;
     if ((st = ensure_ingest_flag(p)) != FSGM_OK) return st;
     return device_call(p->join, cs, p->stream, [&]() -> fsgm_status {
-        launch_sgm2d_ingest(p->stream, C, p->dC, n, W, H, p->Sx, p->Sy, c.prm.layout, c.prm.cost_bound, p->dIngestFlag);
+        if (fmt.dtype >= 0) launch_sgm2d_ingest_float(p->stream, C, fmt, p->dC, n, W, H, p->Sx, p->Sy, c.prm.layout, c.prm.cost_bound, p->dIngestFlag);
+        else launch_sgm2d_ingest(p->stream, C, p->dC, n, W, H, p->Sx, p->Sy, c.prm.layout, c.prm.cost_bound, p->dIngestFlag);
         if (!preMv) {
             const fsgm_status zs = zero_hints(p);
             if (zs != FSGM_OK) return zs;
@@ -282,6 +301,57 @@ fsgm_status fsgm_sgm2d_device_exact(int32_t n, const uint8_t* C, int32_t W, int3
                                     void* stream, int32_t* status) {
     return sgm2d_device("fsgm_sgm2d_device_exact", n, C, W, H, rX, rY, P1, P2, prm, preMv, mvW, mvH, guide, bestD, minC, minC2,
                         minC2 != nullptr, true, mvSub, flow, S, stream, status);
+}
+
+// The float forms (include/fsgm.h, "Float cost volumes"): the format is checked first, then the u8 forms' bodies run with it;
+// minC2 is wanted when given, exact is a switch.
+fsgm_status fsgm_sgm2d_float_batch_host(int32_t n, const void* C, const fsgm_cost_format* fmt, int32_t W, int32_t H, int32_t rX, int32_t rY,
+                                        int32_t P1, int32_t P2, const fsgm_sgm2d_params* prm, const double* preMv, int32_t mvW, int32_t mvH,
+                                        const uint8_t* guide, uint32_t* bestD, uint32_t* minC, uint32_t* minC2, double* mvSub, double* flow,
+                                        uint32_t* S, int32_t exact) {
+    const char* who = "fsgm_sgm2d_float_batch_host";
+    FSGM_REQUIRE(exact == 0 || exact == 1, "%s: exact must be 0 or 1 (got %d)", who, exact);
+    CostFormat cf;
+    const fsgm_status st = check_cost_format(who, fmt, &cf);
+    if (st != FSGM_OK) return st;
+    return sgm2d_host(who, n, static_cast<const uint8_t*>(C), W, H, rX, rY, P1, P2, prm, preMv, mvW, mvH, guide, bestD, minC, minC2,
+                      minC2 != nullptr, exact != 0, mvSub, flow, S, cf);
+}
+
+fsgm_status fsgm_sgm2d_float_dptr(int32_t n, const void* C, const fsgm_cost_format* fmt, int32_t W, int32_t H, int32_t rX, int32_t rY,
+                                  int32_t P1, int32_t P2, const fsgm_sgm2d_params* prm, const double* preMv, int32_t mvW, int32_t mvH,
+                                  const uint8_t* guide, uint32_t* bestD, uint32_t* minC, uint32_t* minC2, double* mvSub, double* flow,
+                                  uint32_t* S, int32_t exact, void* stream, int32_t* status) {
+    const char* who = "fsgm_sgm2d_float_dptr";
+    FSGM_REQUIRE(exact == 0 || exact == 1, "%s: exact must be 0 or 1 (got %d)", who, exact);
+    CostFormat cf;
+    const fsgm_status st = check_cost_format(who, fmt, &cf);
+    if (st != FSGM_OK) return st;
+    return sgm2d_device(who, n, static_cast<const uint8_t*>(C), W, H, rX, rY, P1, P2, prm, preMv, mvW, mvH, guide, bestD, minC, minC2,
+                        minC2 != nullptr, exact != 0, mvSub, flow, S, stream, status, cf);
+}
+
+fsgm_status fsgm_pyd_plan_ingest_float_dptr(fsgm_pyd_plan* p, int32_t n, const void* C, const fsgm_cost_format* fmt, int32_t layout,
+                                            int32_t cost_bound, void* stream, int32_t* status) {
+    const char* who = "fsgm_pyd_plan_ingest_float_dptr";
+    FSGM_REQUIRE(p && C, "%s: null argument", who);
+    CostFormat cf;
+    fsgm_status st = check_cost_format(who, fmt, &cf);
+    if (st != FSGM_OK) return st;
+    FSGM_REQUIRE(n == p->batch, "%s: n_frames %d differs from the plan's batch %d", who, n, p->batch);
+    FSGM_REQUIRE(layout_ok(layout), "%s: layout must be FSGM_COST2D_LAYOUT_HWD (0), _DHW (1) or _DHW_YX (2), got %d", who, layout);
+    FSGM_REQUIRE(cost_bound >= 1 && cost_bound <= 255, "%s: cost_bound must be 1..255 (got %d)", who, cost_bound);
+    const hipStream_t cs = (hipStream_t)stream;
+    const size_t es = cost_elem_size(cf.dtype);
+    if ((st = device_check_args(who, p->device, cs, {{C, (size_t)n * p->NP * p->D * es, es, true, "C"}, {status, 4, 4, false, "status"}})) != FSGM_OK)
+        return st;
+    if ((st = ensure_ingest_flag(p)) != FSGM_OK) return st;
+    p->cmax = cost_bound;
+    return device_call(p->join, cs, p->stream, [&] {
+        launch_sgm2d_ingest_float(p->stream, C, cf, p->dC, n, p->W, p->H, p->Sx, p->Sy, layout, cost_bound, p->dIngestFlag);
+        launch_device_status(p->stream, nullptr, p->dIngestFlag, status);
+        return FSGM_OK;
+    });
 }
 
 fsgm_status fsgm_pyd_plan_ingest_cost_device(fsgm_pyd_plan* p, int32_t n, const uint8_t* C, int32_t layout, int32_t cost_bound,

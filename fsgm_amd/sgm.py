@@ -8,6 +8,7 @@ from . import _lib
 from ._lib import check, ptr
 
 LAYOUTS = {"hwd": 0, "dhw": 1}          # FSGM_COST_LAYOUT_HWD / _DHW
+COST_DTYPES = {"float32": 0, "float16": 1, "bfloat16": 2}       # FSGM_COST_F32 / _F16 / _BF16
 
 
 class SgmParams(C.Structure):
@@ -15,9 +16,34 @@ class SgmParams(C.Structure):
                 ("cost_bound", C.c_int32), ("adaptive_p2", C.c_int32), ("reserved", C.c_int32 * 5)]
 
 
+class CostFormat(C.Structure):
+    _fields_ = [("dtype", C.c_int32), ("scale", C.c_float), ("offset", C.c_float), ("reserved", C.c_int32 * 5)]
+
+
+def cost_format(dtype, scale, offset=0.0):
+    """fsgm_cost_format for a float volume: dtype "float32" / "float16" / "bfloat16" (or a numpy / torch dtype of that name); a
+    voxel c becomes the byte clamp(rint(fp32(c) * scale + offset), 0, cost_bound), scale and offset rounded to float32 first
+    (include/fsgm.h, "Float cost volumes").  The library refuses a zero or non-finite scale and a non-finite offset (status 1)."""
+    try:
+        name = np.dtype(dtype).name
+    except TypeError:                                            # (a torch dtype, or "bfloat16", which numpy does not know)
+        name = str(dtype).rsplit(".", 1)[-1]
+    if name not in COST_DTYPES:
+        raise TypeError(f"a float cost volume must be float32, float16 or bfloat16 (got {dtype})")
+    f = CostFormat()
+    f.dtype, f.scale, f.offset = COST_DTYPES[name], float(scale), float(offset)
+    return f
+
+
 def _bind(lib):
     vp, i32 = C.c_void_p, C.c_int32
     lib.fsgm_sgm_params_default.restype = SgmParams
+    if hasattr(lib, "fsgm_sgm_float_dptr"):                      # (an older build behind FSGM_LIB_PATH has none): fmt behind C, exact a switch
+        fmt = C.POINTER(CostFormat)
+        lib.fsgm_cost_format_default.restype = CostFormat
+        lib.fsgm_sgm_float_batch_host.argtypes = [i32, vp, fmt, i32, i32, i32, i32, i32, C.POINTER(SgmParams), vp, vp, vp, vp, vp, i32]
+        lib.fsgm_sgm_float_dptr.argtypes = lib.fsgm_sgm_float_batch_host.argtypes + [vp, vp]
+        lib.fsgm_epi_plan_ingest_float_dptr.argtypes = [vp, i32, vp, fmt, i32, i32, vp, vp]
     lib.fsgm_sgm_batch_host.argtypes = [i32, vp, i32, i32, i32, i32, i32, C.POINTER(SgmParams), vp, vp, vp, vp]
     lib.fsgm_sgm_device.argtypes = [i32, vp, i32, i32, i32, i32, i32, C.POINTER(SgmParams), vp, vp, vp, vp, vp, vp]
     if hasattr(lib, "fsgm_sgm_batch_host_ru"):                   # (an older build behind FSGM_LIB_PATH has none): minC2 after minC
@@ -119,5 +145,39 @@ def sgm_batch(Cvol, P1=7, P2=100, *, paths=4, layout="hwd", cost_bound=255, agg_
                                             ptr(S)))
     else:
         check(lib.fsgm_sgm_batch_host(N, ptr(Cvol), W, H, D, int(P1), int(P2), C.byref(prm), ptr(guide), ptr(bestD), ptr(minC), ptr(S)))
+    outs = (bestD, minC) + ((minC2,) if runner_up else ()) + ((S,) if return_sum else ())
+    return outs if n is not None else tuple(o[0] for o in outs)
+
+
+def sgm_batch_float(costs, scale, offset=0.0, P1=7, P2=100, *, paths=4, layout="hwd", cost_bound=255, agg_mode=0, adaptive_p2=0, guide=None,
+                    subpixel=1, return_sum=False, device=0, runner_up=False, arith="mod256"):
+    """sgm_batch on float costs (fsgm_sgm_float_batch_host): costs float32 or float16 in the shapes sgm_batch takes, each voxel
+    quantised on the device to the byte clamp(rint(float32(c) * scale + offset), 0, cost_bound) -- one float32 multiply, one
+    float32 add, ties to even; a negative scale turns a similarity into a cost -- and the u8 path run on those bytes: the outputs
+    are those of sgm_batch on them with the same cost_bound, bit for bit.  A voxel that rounds below 0 or above cost_bound, or a
+    NaN, refuses the volume (status 1, nothing written).  The kernels are chosen from cost_bound as declared (no scan for the true
+    maximum).  Everything else -- layout, agg_mode, adaptive_p2 / guide, runner_up, arith, return_sum -- as sgm_batch."""
+    lib = _bind(_lib.load())
+    exact = arith_exact(arith)
+    if exact and runner_up:
+        raise ValueError("arith='exact' has no runner-up cost: runner_up=True needs arith='mod256'")
+    layout_code(layout)
+    costs = np.ascontiguousarray(costs)
+    if costs.dtype not in (np.float32, np.float16):
+        raise TypeError(f"costs must be float32 or float16 (got {costs.dtype}); uint8 volumes go to sgm_batch")
+    fmt = cost_format(costs.dtype, scale, offset)
+    n, H, W, D = shape_of(costs.shape, layout)
+    N = 1 if n is None else n
+    if guide is not None:
+        guide = np.ascontiguousarray(guide)
+        if guide.dtype != np.uint8 or guide.shape != (() if n is None else (n,)) + (H, W):
+            raise TypeError(f"guide must be uint8 of shape {(() if n is None else (n,)) + (H, W)}")
+    prm = params(lib, paths=paths, subpixel=subpixel, device=device, agg_mode=agg_mode, layout=layout, cost_bound=cost_bound,
+                 adaptive_p2=adaptive_p2)
+    bestD, minC = np.empty((N, H, W), np.uint32), np.empty((N, H, W), np.uint32)
+    S = np.empty((N, H, W, D), np.uint32) if return_sum else None
+    minC2 = np.empty((N, H, W), np.uint32) if runner_up else None
+    check(lib.fsgm_sgm_float_batch_host(N, ptr(costs), C.byref(fmt), W, H, D, int(P1), int(P2), C.byref(prm), ptr(guide), ptr(bestD), ptr(minC),
+                                        ptr(minC2), ptr(S), int(exact)))
     outs = (bestD, minC) + ((minC2,) if runner_up else ()) + ((S,) if return_sum else ())
     return outs if n is not None else tuple(o[0] for o in outs)

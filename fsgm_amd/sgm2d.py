@@ -7,6 +7,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import check, ptr
+from .sgm import CostFormat, cost_format
 
 LAYOUTS = {"hwd": 0, "dhw": 1, "dhw_yx": 2}      # FSGM_COST2D_LAYOUT_HWD / _DHW / _DHW_YX
 
@@ -28,6 +29,11 @@ def _bind(lib):
     if hasattr(lib, "fsgm_sgm2d_batch_host_exact"):              # (nor these): the _ru forms' argument lists, minC2 may be NULL
         lib.fsgm_sgm2d_batch_host_exact.argtypes = head[:15] + [vp] + head[15:]
         lib.fsgm_sgm2d_device_exact.argtypes = head[:15] + [vp] + head[15:] + [vp, vp]
+    if hasattr(lib, "fsgm_sgm2d_float_dptr"):                    # (nor these): fmt behind C, minC2 may be NULL, exact a switch
+        fhead = head[:2] + [C.POINTER(CostFormat)] + head[2:15] + [vp] + head[15:] + [i32]
+        lib.fsgm_sgm2d_float_batch_host.argtypes = fhead
+        lib.fsgm_sgm2d_float_dptr.argtypes = fhead + [vp, vp]
+        lib.fsgm_pyd_plan_ingest_float_dptr.argtypes = [vp, i32, vp, C.POINTER(CostFormat), i32, i32, vp, vp]
     lib.fsgm_sgm2d_last_kernel.restype = C.c_char_p
     lib.fsgm_sgm2d_ingest_lds.argtypes = [i32, i32, i32, C.POINTER(C.c_uint64)]
     lib.fsgm_pyd_plan_ingest_cost_device.argtypes = [vp, i32, vp, i32, i32, vp, vp]
@@ -141,5 +147,50 @@ def sgm2d_batch(costs, half_x, half_y, P1=6, P2=32, *, layout="dhw", hints=None,
     else:
         check(lib.fsgm_sgm2d_batch_host(N, ptr(costs), W, H, int(half_x), int(half_y), int(P1), int(P2), C.byref(prm), ptr(hints), mvW,
                                         mvH, ptr(guide), ptr(bestD), ptr(minC), ptr(mvSub), ptr(flow), ptr(S)))
+    outs = (bestD, minC) + ((minC2,) if runner_up else ()) + (mvSub,) + ((flow,) if return_flow else ()) + ((S,) if return_sum else ())
+    return outs if n is not None else tuple(o[0] for o in outs)
+
+
+def sgm2d_batch_float(costs, half_x, half_y, scale, offset=0.0, P1=6, P2=32, *, layout="dhw", hints=None, guide=None, cost_bound=255,
+                      diagonal=1, total_pass=2, adaptive_p2=0, subpixel=1, return_flow=False, return_sum=False, device=0, runner_up=False,
+                      arith="wrap"):
+    """sgm2d_batch on float costs (fsgm_sgm2d_float_batch_host): costs float32 or float16 in the shapes sgm2d_batch takes -- a
+    correlation layer's (N, 81, H, W) for a 9x9 window -- each voxel quantised on the device to the byte
+    clamp(rint(float32(c) * scale + offset), 0, cost_bound) (one float32 multiply, one float32 add, ties to even; a negative scale
+    turns a correlation into a cost) and the u8 path run on those bytes: the outputs are those of sgm2d_batch on them with the same
+    cost_bound, bit for bit.  A voxel that rounds below 0 or above cost_bound, or a NaN, refuses the volume (status 1, nothing
+    written).  The aggregation is chosen from cost_bound as declared.  Everything else as sgm2d_batch."""
+    lib = _bind(_lib.load())
+    exact = arith_exact(arith)
+    layout_code(layout)
+    costs = np.ascontiguousarray(costs)
+    if costs.dtype not in (np.float32, np.float16):
+        raise TypeError(f"costs must be float32 or float16 (got {costs.dtype}); uint8 volumes go to sgm2d_batch")
+    fmt = cost_format(costs.dtype, scale, offset)
+    n, H, W, D = shape_of(costs.shape, layout, half_x, half_y)
+    N = 1 if n is None else n
+    lead = () if n is None else (n,)
+    mvW = mvH = 0
+    if hints is not None:
+        hints = np.ascontiguousarray(hints)
+        if hints.dtype != np.float64 or hints.ndim != len(lead) + 3 or hints.shape[:-2] != lead + (2,):
+            raise TypeError(f"hints must be float64 of shape {lead + (2, 'mvH', 'mvW')} (got {hints.dtype} {hints.shape})")
+        mvH, mvW = hints.shape[-2:]
+        if mvH < H or mvW < W:
+            raise ValueError(f"hints ({mvH} x {mvW}) must be at least as large as the image ({H} x {W})")
+    if guide is not None:
+        guide = np.ascontiguousarray(guide)
+        if guide.dtype != np.uint8 or guide.shape != lead + (H, W):
+            raise TypeError(f"guide must be uint8 of shape {lead + (H, W)}")
+    prm = params(lib, diagonal=diagonal, total_pass=total_pass, adaptive_p2=adaptive_p2, subpixel=subpixel, device=device, layout=layout,
+                 cost_bound=cost_bound)
+    bestD, minC = np.empty((N, H, W), np.uint32), np.empty((N, H, W), np.uint32)
+    mvSub = np.empty((N, 2, H, W), np.float64)
+    flow = np.empty((N, 2, H, W), np.float64) if return_flow else None
+    S = np.empty((N, H, W, D), np.uint32) if return_sum else None
+    minC2 = np.empty((N, H, W), np.uint32) if runner_up else None
+    check(lib.fsgm_sgm2d_float_batch_host(N, ptr(costs), C.byref(fmt), W, H, int(half_x), int(half_y), int(P1), int(P2), C.byref(prm),
+                                          ptr(hints), mvW, mvH, ptr(guide), ptr(bestD), ptr(minC), ptr(minC2), ptr(mvSub), ptr(flow), ptr(S),
+                                          int(exact)))
     outs = (bestD, minC) + ((minC2,) if runner_up else ()) + (mvSub,) + ((flow,) if return_flow else ()) + ((S,) if return_sum else ())
     return outs if n is not None else tuple(o[0] for o in outs)

@@ -21,6 +21,8 @@ fsgm::sgm_exact (fsgm::sgm with exact path arithmetic, fsgm_sgm_device_exact: th
 fsgm::sgm2d_exact (fsgm::sgm2d_ru with exact path arithmetic, fsgm_sgm2d_device_exact: a runner_up flag added, minC2 empty without it);
 fsgm::pyramidal_sgm_lm, fsgm::pyramidal_sgm_ng_lm and fsgm::pyramidal_flow_pp_lm (the _ru / _u ops with the median between levels:
 a level_median argument, minC2 empty when not asked for) and fsgm::flow_level_hints (the hint map of the next finer level).
+In a namespace of their own, fsgm_float::sgm and fsgm_float::sgm2d: the sgm and sgm2d families on float32 / float16 / bfloat16
+volumes, quantised to bytes in the pass that brings them into the plan (runner_up and exact are flags; sgm_float, sgm2d_float).
 
 One process must hold one HIP runtime.  torch brings its own libamdhip64; libfsgm_hip.so binds to it by soname when torch is
 imported first.  When the library was loaded first, torch afterwards maps a second runtime, and a stream or pointer of one
@@ -38,7 +40,7 @@ from ._lib import EpiIn, EpiOut, EpiOptions, EpiParams, FsgmError, StereoParams
 from .epi import EpiGeometry, _d_min, _params as _epi_params, _stereo_params
 from .post import _bind as _bind_post
 from .stereo_pp import CHAIN_FIELDS as STEREO_PP_FIELDS, _bind as _bind_stereo_pp, pp_params as _stereo_pp_params
-from .sgm import _bind as _bind_sgm, arith_exact as _arith_exact, layout_code as _layout_code, params as _sgm_params, shape_of as _sgm_shape
+from .sgm import _bind as _bind_sgm, arith_exact as _arith_exact, cost_format as _cost_format, layout_code as _layout_code, params as _sgm_params, shape_of as _sgm_shape
 from .sgm2d import _bind as _bind_sgm2d, arith_exact as _arith2d_exact, layout_code as _layout2d_code, params as _sgm2d_params, shape_of as _sgm2d_shape, LAYOUTS as _LAYOUTS2D
 from .pyramid import (PyramidParams, NgPyramidParams, FLOW_PP_FIELDS, MATCHERS, _bind as _bind_pyramid, _bind_flow_pp, _bind_ng,
                       uniqueness_ratio_of as _uniqueness_ratio_of, level_median_of as _level_median_of)
@@ -387,7 +389,7 @@ def _sgm2d_run(fn, who, C_, hints, guide, half_x, half_y, P1, P2, layout, cost_b
     N, H, W, D = _sgm2d_out_shape(C_, layout, half_x, half_y)
     dev = C_.device
     if not C_.is_contiguous():                            # (any byte offset will do: the ingest kernels assume no alignment)
-        raise TypeError(f"fsgm::{who} reads the costs where they lie: pass a contiguous tensor")
+        raise TypeError(f"{who} reads the costs where they lie: pass a contiguous tensor")
     have_hints = hints.numel() != 0
     hints = _ready(hints) if have_hints else None
     mvH, mvW = (hints.shape[-2], hints.shape[-1]) if have_hints else (0, 0)
@@ -407,7 +409,7 @@ def _sgm2d_op(C_: torch.Tensor, hints: torch.Tensor, guide: torch.Tensor, half_x
               return_sum: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
     """C_ (N, H, W, D) for layout 0, (N, D, H, W) for 1 (channel sx*Sy + sy) and 2 (channel sy*Sx + sx); hints (N, 2, mvH, mvW)
     float64 or empty (zero hints); guide (N, H, W), read with adaptive_p2 only.  flow / S are empty unless asked for."""
-    return _sgm2d_run(_L.fsgm_sgm2d_device, "sgm2d", C_, hints, guide, half_x, half_y, P1, P2, layout, cost_bound, diagonal, total_pass,
+    return _sgm2d_run(_L.fsgm_sgm2d_device, "fsgm::sgm2d", C_, hints, guide, half_x, half_y, P1, P2, layout, cost_bound, diagonal, total_pass,
                       adaptive_p2, subpixel, return_flow, return_sum)
 
 
@@ -421,7 +423,7 @@ def _sgm2d_ru_op(C_: torch.Tensor, hints: torch.Tensor, guide: torch.Tensor, hal
                  cost_bound: int, diagonal: int, total_pass: int, adaptive_p2: int, subpixel: int, return_flow: int, return_sum: int
                  ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
     """fsgm::sgm2d with the runner-up cost minC2 after minC (fsgm_sgm2d_device_ru): (bestD, minC, minC2, mvSub, flow, S, status)"""
-    return _sgm2d_run(_L.fsgm_sgm2d_device_ru, "sgm2d_ru", C_, hints, guide, half_x, half_y, P1, P2, layout, cost_bound, diagonal, total_pass,
+    return _sgm2d_run(_L.fsgm_sgm2d_device_ru, "fsgm::sgm2d_ru", C_, hints, guide, half_x, half_y, P1, P2, layout, cost_bound, diagonal, total_pass,
                       adaptive_p2, subpixel, return_flow, return_sum, True)
 
 
@@ -436,13 +438,62 @@ def _sgm2d_exact_op(C_: torch.Tensor, hints: torch.Tensor, guide: torch.Tensor, 
                     runner_up: bool
                     ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
     """fsgm::sgm2d_ru with exact path arithmetic (fsgm_sgm2d_device_exact): P1, P2 in 0..255; minC2 is empty unless runner_up"""
-    return _sgm2d_run(_L.fsgm_sgm2d_device_exact, "sgm2d_exact", C_, hints, guide, half_x, half_y, P1, P2, layout, cost_bound, diagonal,
+    return _sgm2d_run(_L.fsgm_sgm2d_device_exact, "fsgm::sgm2d_exact", C_, hints, guide, half_x, half_y, P1, P2, layout, cost_bound, diagonal,
                       total_pass, adaptive_p2, subpixel, return_flow, return_sum, bool(runner_up))
 
 
 @_sgm2d_exact_op.register_fake
 def _(C_, hints, guide, half_x, half_y, P1, P2, layout, cost_bound, diagonal, total_pass, adaptive_p2, subpixel, return_flow, return_sum,
       runner_up):
+    return _sgm2d_outputs(C_, layout, half_x, half_y, return_flow, return_sum, bool(runner_up))
+
+
+# Float cost volumes (include/fsgm.h, "Float cost volumes"): one op per family in a namespace of their own, fsgm_float::sgm and
+# fsgm_float::sgm2d, each covering what the three u8 ops of its family cover -- runner_up and exact are flags, minC2 is the
+# empty placeholder without runner_up.  The bodies are the u8 families': only the C entry, which quantises on the way in, differs.
+_FLOAT_DTYPES = (torch.float32, torch.float16, torch.bfloat16)
+
+
+def _float_entry(name, C_, scale, offset, exact):
+    """The float entry `name` of the library as a callable with the argument list of its family's u8 _ru entry: the cost format
+    of C_ goes in behind the volume, the exact switch in front of the stream.  The entry is looked up when the op runs."""
+    if C_.dtype not in _FLOAT_DTYPES:
+        raise TypeError(f"a float cost volume must be float32, float16 or bfloat16 (got {C_.dtype})")
+    fmt = _cost_format(C_.dtype, scale, offset)
+
+    def call(N, Cp, *rest):
+        *mid, stream, status = rest
+        return getattr(_L, name)(N, Cp, C.byref(fmt), *mid, int(bool(exact)), stream, status)
+    return call
+
+
+@torch.library.custom_op("fsgm_float::sgm", mutates_args=())
+def _sgm_float_op(C_: torch.Tensor, guide: torch.Tensor, scale: float, offset: float, P1: int, P2: int, paths: int, layout: int,
+                  cost_bound: int, agg_mode: int, adaptive_p2: int, subpixel: int, return_sum: int, runner_up: bool, exact: bool
+                  ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """fsgm::sgm / sgm_ru / sgm_exact on a float32 / float16 / bfloat16 volume (fsgm_sgm_float_dptr): (bestD, minC, minC2, S, status)"""
+    return _sgm_run(_float_entry("fsgm_sgm_float_dptr", C_, scale, offset, exact), C_, guide, P1, P2, paths, layout, cost_bound, agg_mode,
+                    adaptive_p2, subpixel, return_sum, bool(runner_up))
+
+
+@_sgm_float_op.register_fake
+def _(C_, guide, scale, offset, P1, P2, paths, layout, cost_bound, agg_mode, adaptive_p2, subpixel, return_sum, runner_up, exact):
+    return _sgm_outputs(C_, layout, return_sum, bool(runner_up))
+
+
+@torch.library.custom_op("fsgm_float::sgm2d", mutates_args=())
+def _sgm2d_float_op(C_: torch.Tensor, hints: torch.Tensor, guide: torch.Tensor, scale: float, offset: float, half_x: int, half_y: int,
+                    P1: int, P2: int, layout: int, cost_bound: int, diagonal: int, total_pass: int, adaptive_p2: int, subpixel: int,
+                    return_flow: int, return_sum: int, runner_up: bool, exact: bool
+                    ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """fsgm::sgm2d / sgm2d_ru / sgm2d_exact on a float volume (fsgm_sgm2d_float_dptr): (bestD, minC, minC2, mvSub, flow, S, status)"""
+    return _sgm2d_run(_float_entry("fsgm_sgm2d_float_dptr", C_, scale, offset, exact), "fsgm_float::sgm2d", C_, hints, guide, half_x, half_y,
+                      P1, P2, layout, cost_bound, diagonal, total_pass, adaptive_p2, subpixel, return_flow, return_sum, bool(runner_up))
+
+
+@_sgm2d_float_op.register_fake
+def _(C_, hints, guide, scale, offset, half_x, half_y, P1, P2, layout, cost_bound, diagonal, total_pass, adaptive_p2, subpixel, return_flow,
+      return_sum, runner_up, exact):
     return _sgm2d_outputs(C_, layout, half_x, half_y, return_flow, return_sum, bool(runner_up))
 
 
@@ -844,13 +895,16 @@ def _(map_, minC, minC2, ratio, planes):
 # wrappers: the argument order of the numpy API, one frame or a batch with a leading N
 # ---------------------------------------------------------------------------------------------
 def _tensors(named, device=None):
-    """TypeError unless every value is a GPU tensor of the dtype asked for, all on one device; returns that device."""
+    """TypeError unless every value is a GPU tensor of the dtype asked for (a tuple: of one of them), all on one device; returns that device."""
     for name, (t, dtype) in named.items():
         if not isinstance(t, torch.Tensor):
             raise TypeError(f"{name} must be a torch.Tensor (got {type(t).__name__})")
         if t.device.type != "cuda":
             raise TypeError(f"{name} is on {t.device}: pass tensors on the GPU (no silent transfer)")
-        if t.dtype != dtype:
+        if isinstance(dtype, tuple):
+            if t.dtype not in dtype:
+                raise TypeError(f"{name} must be one of {', '.join(str(d) for d in dtype)} (got {t.dtype})")
+        elif t.dtype != dtype:
             raise TypeError(f"{name} must be {dtype} (got {t.dtype})")
         if device is None:
             device = t.device
@@ -937,11 +991,31 @@ def sgm(Cvol, P1=7, P2=100, *, layout="dhw", paths=4, cost_bound=255, agg_mode=0
     (fsgm::sgm_ru) returns minC2 uint32 after minC, as fsgm_amd.sgm_batch does.  arith="exact" (fsgm::sgm_exact): path costs that
     are never narrowed to a byte, as fsgm_amd.sgm_batch(arith="exact") -- P1, P2 in 0..255, the line kernels at every batch size;
     with runner_up=True it raises ValueError."""
+    return _sgm_call(Cvol, None, P1, P2, layout, paths, cost_bound, agg_mode, adaptive_p2, guide, subpixel, return_sum, check, return_status,
+                     runner_up, arith)
+
+
+def sgm_float(Cvol, scale, offset=0.0, P1=7, P2=100, *, layout="dhw", paths=4, cost_bound=255, agg_mode=0, adaptive_p2=0, guide=None,
+              subpixel=1, return_sum=False, check=False, return_status=False, runner_up=False, arith="mod256"):
+    """sgm on a float cost volume (fsgm_float::sgm, fsgm_sgm_float_dptr): C float32, float16 or bfloat16 in the shapes sgm takes,
+    e.g. a cost-volume network's (N, D, H, W) output.  Each voxel c is quantised in the kernel pass that brings the volume into
+    the plan -- q = clamp(rint(float32(c) * scale + offset), 0, cost_bound): one float32 multiply, one float32 add, ties to even,
+    scale and offset rounded to float32 first; a negative scale turns a similarity into a cost -- and the u8 path runs on the
+    bytes: every output is, bit for bit, that of sgm on q with the same cost_bound.  A voxel that rounds below 0 or above
+    cost_bound, or a NaN, sets the status to FSGM_ERR_INVALID (the outputs are those of the clamped volume); check=True raises on
+    it.  The volume is read where it lies: a contiguous slice of a larger tensor will do.  Everything else as sgm."""
+    return _sgm_call(Cvol, (float(scale), float(offset)), P1, P2, layout, paths, cost_bound, agg_mode, adaptive_p2, guide, subpixel,
+                     return_sum, check, return_status, runner_up, arith)
+
+
+def _sgm_call(Cvol, quant, P1, P2, layout, paths, cost_bound, agg_mode, adaptive_p2, guide, subpixel, return_sum, check, return_status,
+              runner_up, arith):
+    """sgm (quant None: a uint8 volume) and sgm_float (quant = (scale, offset): a float volume, through fsgm_float::sgm)"""
     exact = _arith_exact(arith)
     if exact and runner_up:
         raise ValueError("arith='exact' has no runner-up cost: runner_up=True needs arith='mod256'")
     code = _layout_code(layout)
-    named = {"C": (Cvol, torch.uint8)}
+    named = {"C": (Cvol, torch.uint8 if quant is None else _FLOAT_DTYPES)}
     if guide is not None:
         named["guide"] = (guide, torch.uint8)
     _tensors(named)
@@ -958,7 +1032,9 @@ def sgm(Cvol, P1=7, P2=100, *, layout="dhw", paths=4, cost_bound=255, agg_mode=0
         guide = torch.empty((0,), dtype=torch.uint8, device=Cvol.device)
     args = (Cvol, guide, int(P1), int(P2), int(paths), code, int(cost_bound), int(agg_mode), int(adaptive_p2), int(subpixel),
             int(bool(return_sum)))
-    if runner_up:
+    if quant is not None:
+        bestD, minC, minC2, S, status = torch.ops.fsgm_float.sgm(*args[:2], *quant, *args[2:], bool(runner_up), exact)
+    elif runner_up:
         bestD, minC, minC2, S, status = torch.ops.fsgm.sgm_ru(*args)
     elif exact:
         bestD, minC, S, status = torch.ops.fsgm.sgm_exact(*args)
@@ -982,9 +1058,30 @@ def sgm2d(costs, half_x, half_y, P1=6, P2=32, *, layout="dhw", hints=None, guide
     uint32 (.., H, W) after minC, as fsgm_amd.sgm2d_batch does.  arith="exact" (fsgm::sgm2d_exact): path costs that are never
     narrowed to a byte, as fsgm_amd.sgm2d_batch(arith="exact") -- P1, P2 in 0..255, "generic/exact" at every window and bound, with or
     without runner_up."""
+    return _sgm2d_call(costs, None, half_x, half_y, P1, P2, layout, hints, guide, cost_bound, diagonal, total_pass, adaptive_p2, subpixel,
+                       return_flow, return_sum, check, return_status, runner_up, arith)
+
+
+def sgm2d_float(costs, half_x, half_y, scale, offset=0.0, P1=6, P2=32, *, layout="dhw", hints=None, guide=None, cost_bound=255, diagonal=1,
+                total_pass=2, adaptive_p2=0, subpixel=1, return_flow=False, return_sum=False, check=False, return_status=False,
+                runner_up=False, arith="wrap"):
+    """sgm2d on a float cost volume (fsgm_float::sgm2d, fsgm_sgm2d_float_dptr): costs float32, float16 or bfloat16 in the shapes
+    sgm2d takes, e.g. a correlation layer's (N, 81, H, W) for a 9x9 window with layout "dhw_yx".  Each voxel c is quantised in the
+    kernel pass that brings the volume into the plan -- q = clamp(rint(float32(c) * scale + offset), 0, cost_bound), as
+    sgm_float; a negative scale turns a correlation into a cost -- and the u8 path runs on the bytes: every output is, bit for
+    bit, that of sgm2d on q with the same cost_bound.  A voxel that rounds below 0 or above cost_bound, or a NaN, sets the status to
+    FSGM_ERR_INVALID (the outputs are those of the clamped volume).  The tensor must be contiguous and may be a slice of a larger
+    one.  Everything else as sgm2d."""
+    return _sgm2d_call(costs, (float(scale), float(offset)), half_x, half_y, P1, P2, layout, hints, guide, cost_bound, diagonal, total_pass,
+                       adaptive_p2, subpixel, return_flow, return_sum, check, return_status, runner_up, arith)
+
+
+def _sgm2d_call(costs, quant, half_x, half_y, P1, P2, layout, hints, guide, cost_bound, diagonal, total_pass, adaptive_p2, subpixel,
+                return_flow, return_sum, check, return_status, runner_up, arith):
+    """sgm2d (quant None: a uint8 volume) and sgm2d_float (quant = (scale, offset): a float volume, through fsgm_float::sgm2d)"""
     exact = _arith2d_exact(arith)
     code = _layout2d_code(layout)
-    named = {"costs": (costs, torch.uint8)}
+    named = {"costs": (costs, torch.uint8 if quant is None else _FLOAT_DTYPES)}
     if hints is not None:
         named["hints"] = (hints, torch.float64)
     if guide is not None:
@@ -1015,7 +1112,9 @@ def sgm2d(costs, half_x, half_y, P1=6, P2=32, *, layout="dhw", hints=None, guide
         guide = torch.empty((0,), dtype=torch.uint8, device=dev)
     args = (costs, hints, guide, int(half_x), int(half_y), int(P1), int(P2), code, int(cost_bound), int(diagonal), int(total_pass),
             int(adaptive_p2), int(subpixel), int(bool(return_flow)), int(bool(return_sum)))
-    if exact:
+    if quant is not None:
+        bestD, minC, minC2, mvSub, flow, S, status = torch.ops.fsgm_float.sgm2d(*args[:3], *quant, *args[3:], bool(runner_up), exact)
+    elif exact:
         bestD, minC, minC2, mvSub, flow, S, status = torch.ops.fsgm.sgm2d_exact(*args, bool(runner_up))
     elif runner_up:
         bestD, minC, minC2, mvSub, flow, S, status = torch.ops.fsgm.sgm2d_ru(*args)
@@ -1025,10 +1124,11 @@ def sgm2d(costs, half_x, half_y, P1=6, P2=32, *, layout="dhw", hints=None, guide
     return _finish(outs, status, batched, check, return_status, "a cost above cost_bound")
 
 
-def _ingest(plan, t, name, layout, code, must_be_contiguous, fn, cost_bound, check, return_status):
+def _ingest(plan, t, name, layout, code, must_be_contiguous, fn, cost_bound, check, return_status, quant=None):
     """`plan.batch` cost volumes from the uint8 tensor `t` (called `name` in messages) through a plan's ingest entry `fn`; `code` is
-    the entry's number for `layout`.  A tensor that is not contiguous is refused with must_be_contiguous, else copied."""
-    dev = _tensors({name: (t, torch.uint8)})
+    the entry's number for `layout`.  A tensor that is not contiguous is refused with must_be_contiguous, else copied.
+    quant = (scale, offset): `t` is a float volume and `fn` the entry's float form, which takes the cost format behind the volume."""
+    dev = _tensors({name: (t, torch.uint8 if quant is None else _FLOAT_DTYPES)})
     if dev.index != plan.device:
         raise TypeError(f"the tensor is on {dev}, the plan on device {plan.device}")
     _shape(name, t, (plan.batch, plan.H, plan.W, plan.D) if layout == "hwd" else (plan.batch, plan.D, plan.H, plan.W))
@@ -1036,7 +1136,8 @@ def _ingest(plan, t, name, layout, code, must_be_contiguous, fn, cost_bound, che
         raise TypeError(f"{name} must be contiguous: the volume is read where it lies (no silent copy)")
     t = t.contiguous()
     status = _status(dev)
-    _call(dev, fn, plan._h, plan.batch, _p(t), code, int(cost_bound), _stream(dev), _p(status))
+    fmt = () if quant is None else (C.byref(_cost_format(t.dtype, *quant)),)
+    _call(dev, fn, plan._h, plan.batch, _p(t), *fmt, code, int(cost_bound), _stream(dev), _p(status))
     res = _finish((), status, True, check, return_status, "a cost above cost_bound")
     return res[0] if return_status else None
 
@@ -1055,6 +1156,20 @@ def ingest_cost2d(plan, costs, *, layout="dhw", cost_bound=255, check=False, ret
     return_status=True, else None."""
     return _ingest(plan, costs, "costs", layout, _layout2d_code(layout), True, _L.fsgm_pyd_plan_ingest_cost_device, cost_bound, check,
                    return_status)
+
+
+def ingest_cost_float(plan, Cvol, scale, offset=0.0, *, layout="dhw", cost_bound=255, check=False, return_status=False):
+    """ingest_cost for a float32 / float16 / bfloat16 tensor (fsgm_epi_plan_ingest_float_dptr): every voxel quantised to
+    clamp(rint(float32(c) * scale + offset), 0, cost_bound) on the way into the plan, as sgm_float does; the status is
+    FSGM_ERR_INVALID when a voxel rounded outside 0..cost_bound or was a NaN."""
+    return _ingest(plan, Cvol, "C", layout, _layout_code(layout), False, _L.fsgm_epi_plan_ingest_float_dptr, cost_bound, check, return_status,
+                   (float(scale), float(offset)))
+
+
+def ingest_cost2d_float(plan, costs, scale, offset=0.0, *, layout="dhw", cost_bound=255, check=False, return_status=False):
+    """ingest_cost2d for a float32 / float16 / bfloat16 tensor (fsgm_pyd_plan_ingest_float_dptr), quantised as sgm2d_float does."""
+    return _ingest(plan, costs, "costs", layout, _layout2d_code(layout), True, _L.fsgm_pyd_plan_ingest_float_dptr, cost_bound, check,
+                   return_status, (float(scale), float(offset)))
 
 
 def _stereo_inputs(left, right, dMax, paths, subpixel, direction, fb_check, adaptive_p2):

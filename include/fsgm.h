@@ -601,7 +601,8 @@ fsgm_status fsgm_pyd_launch_lds(int32_t halfSearchWinSizeX, int32_t halfSearchWi
  * layer: (N, 81, H, W) for a 9x9 window).  The call shape is sgm2d.m's, whose only input is a ready volume.
  * SEMANTICS ARE THE MEX'S, NOT sgm2d.m's: path arithmetic is mod 256 where sgm2d.m saturates (MATLAB uint8), and a path's
  * first pixel stores minimum 0 (calc_pyd_cost_sgm.cpp:182 etc.) where sgm2d.m takes min(C) -- results differ from sgm2d.m's
- * from the second pixel of every path on.  Float costs stay out, as for fsgm_sgm_batch_host.
+ * from the second pixel of every path on.  Float volumes enter through fsgm_sgm2d_float_dptr / fsgm_sgm2d_float_batch_host
+ * ("Float cost volumes" below), which quantise them to these bytes on the device.
  * The window is (2*halfX+1) x (2*halfY+1) = Sx x Sy candidates; candidate (sx, sy) stands for the displacement
  * (sx - halfX, sy - halfY) added to the pixel's hint, as in the MEX.  C: n_frames contiguous volumes in one of
  *   FSGM_COST2D_LAYOUT_HWD     [H][W][Sx*Sy], candidate index sx*Sy + sy: the reference's order (calc_pyd_cost_sgm.cpp:392-393,
@@ -1364,6 +1365,72 @@ fsgm_status fsgm_pyramidal_sgm_device_lm(int32_t n_frames, const uint8_t* I0, co
 fsgm_status fsgm_pyramidal_sgm_ng_device_lm(int32_t n_frames, const uint8_t* I0, const uint8_t* I1, int32_t width,
                                             int32_t height, int32_t channels, const fsgm_ng_pyramid_params* prm, int32_t level_median,
                                             double* flow, uint32_t* minC, uint32_t* minC2, void* stream, int32_t* status);
+
+/* ------------------------------------------------------------------------------------------
+ * Float cost volumes for sgm(C) and sgm2d(C): a learned matching cost arrives as float32, float16 or bfloat16.  The entries
+ * below take such a volume, quantise it to the u8 volume of the entries above in the one kernel pass that brings it into the
+ * plan (5 bytes of traffic per fp32 voxel: 4 read, 1 written), and run the existing u8 path on it.
+ *
+ * THE RULE.  A cost format is {dtype, scale, offset}: dtype one of FSGM_COST_F32 / _F16 / _BF16, scale and offset fp32, both
+ * finite, scale != 0 (a negative scale turns a similarity into a cost).  For a voxel c and the call's cost_bound B in 1..255:
+ *   1. x = c widened to fp32 (exact for all three types);
+ *   2. t = x * scale, one IEEE fp32 multiply, round to nearest even;
+ *   3. u = t + offset, one IEEE fp32 add -- the two are never contracted into a fused multiply-add;
+ *   4. r = rint(u), ties to even (np.rint);
+ *   5. q = 0 if r < 0; q = B if r > B or u is NaN; otherwise q = (uint8) r.  -0.0 gives 0 and is not out of range.
+ * A voxel with r < 0, r > B or NaN raises the ingest flag, as a byte above the bound does in the u8 entries: the device forms
+ * set the status word to FSGM_ERR_INVALID and their outputs are those of the clamped volume; the host forms return
+ * FSGM_ERR_INVALID and write no output.  fp32 subnormal inputs and products are outside the contract (a device may flush them);
+ * fp16 and bf16 subnormals are normal fp32 values once widened and are inside it.
+ * UNPINNED BY CONSTRUCTION: the reference has no float volumes.  The rule is restated in numpy (tests/cost_quant_restatement.py),
+ * and since everything behind the ingest is the u8 path, the yardstick is equality: the outputs of a float call are, bit for
+ * bit, those of the u8 call on the restatement's bytes with the same cost_bound.
+ *
+ * The kernels are chosen from the declared cost_bound exactly as in the u8 device forms -- in the host float forms too, which
+ * do not scan for the true maximum: a result never depends on the pipeline that computed it.
+ * Refused before a device is touched: everything the u8 forms refuse, and (FSGM_ERR_INVALID) a NULL fmt, an unknown dtype, a
+ * non-finite or zero scale, a non-finite offset, non-zero reserved words.  C is aligned on its element size (4 or 2 bytes) and
+ * no further: it may be a slice of a larger tensor.
+ * ------------------------------------------------------------------------------------------ */
+#define FSGM_COST_F32 0
+#define FSGM_COST_F16 1
+#define FSGM_COST_BF16 2
+typedef struct {
+    int32_t dtype;             /* FSGM_COST_* */
+    float scale, offset;
+    int32_t reserved[5];       /* must be zero */
+} fsgm_cost_format;
+fsgm_cost_format fsgm_cost_format_default(void);   /* FSGM_COST_F32, 1, 0 */
+/* fsgm_epi_plan_ingest_cost_device / fsgm_pyd_plan_ingest_cost_device for a float volume: n_frames (= the plan's batch) volumes
+ * of fmt->dtype in `layout` from device memory, quantised into the plan's cost volumes; cost_bound becomes the bound the plan
+ * selects its kernels by.  status: 0 or FSGM_ERR_INVALID (a flagged voxel).  The contract of the device-pointer entry points. */
+fsgm_status fsgm_epi_plan_ingest_float_dptr(fsgm_epi_plan* plan, int32_t n_frames, const void* C, const fsgm_cost_format* fmt,
+                                            int32_t layout, int32_t cost_bound, void* stream, int32_t* status);
+fsgm_status fsgm_pyd_plan_ingest_float_dptr(fsgm_pyd_plan* plan, int32_t n_frames, const void* C, const fsgm_cost_format* fmt,
+                                            int32_t layout, int32_t cost_bound, void* stream, int32_t* status);
+/* sgm(C) on float volumes in device memory: what fsgm_sgm_device, _ru and _exact cover together.  minC2 may be NULL (not
+ * wanted); exact = 1 selects exact path arithmetic (fsgm_sgm_batch_host_exact).  The cached plans and the internal bodies are
+ * those of the u8 forms: only the ingest launch differs.  Refusals are theirs: exact with minC2, and agg_mode 2..6 with exact,
+ * minC2 or adaptive_p2, are FSGM_ERR_UNSUPPORTED; a stream that is being captured is refused, with exact too. */
+fsgm_status fsgm_sgm_float_dptr(int32_t n_frames, const void* C, const fsgm_cost_format* fmt, int32_t width, int32_t height, int32_t dMax,
+                                int32_t P1, int32_t P2, const fsgm_sgm_params* prm, const uint8_t* guide, uint32_t* bestD, uint32_t* minC,
+                                uint32_t* minC2, uint32_t* S, int32_t exact, void* stream, int32_t* status);
+/* sgm2d(C) on float volumes in device memory: what fsgm_sgm2d_device, _ru and _exact cover together (minC2 may be NULL with or
+ * without exact). */
+fsgm_status fsgm_sgm2d_float_dptr(int32_t n_frames, const void* C, const fsgm_cost_format* fmt, int32_t width, int32_t height,
+                                  int32_t halfX, int32_t halfY, int32_t P1, int32_t P2, const fsgm_sgm2d_params* prm, const double* preMv,
+                                  int32_t mvWidth, int32_t mvHeight, const uint8_t* guide, uint32_t* bestD, uint32_t* minC,
+                                  uint32_t* minC2, double* mvSub, double* flow, uint32_t* S, int32_t exact, void* stream,
+                                  int32_t* status);
+/* The same on host memory: the caller's floats are staged frame by frame and quantised by the same kernels; the ingest flag is
+ * read before any output is written (a flagged volume: FSGM_ERR_INVALID, the outputs untouched). */
+fsgm_status fsgm_sgm_float_batch_host(int32_t n_frames, const void* C, const fsgm_cost_format* fmt, int32_t width, int32_t height,
+                                      int32_t dMax, int32_t P1, int32_t P2, const fsgm_sgm_params* prm, const uint8_t* guide,
+                                      uint32_t* bestD, uint32_t* minC, uint32_t* minC2, uint32_t* S, int32_t exact);
+fsgm_status fsgm_sgm2d_float_batch_host(int32_t n_frames, const void* C, const fsgm_cost_format* fmt, int32_t width, int32_t height,
+                                        int32_t halfX, int32_t halfY, int32_t P1, int32_t P2, const fsgm_sgm2d_params* prm,
+                                        const double* preMv, int32_t mvWidth, int32_t mvHeight, const uint8_t* guide, uint32_t* bestD,
+                                        uint32_t* minC, uint32_t* minC2, double* mvSub, double* flow, uint32_t* S, int32_t exact);
 
 #ifdef __cplusplus
 }
