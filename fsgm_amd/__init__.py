@@ -18,4 +18,5 @@ from .post import (speckle_filter, calc_disp_from_first, forward_backward_check,
                    epi_postprocess, epi_postprocess_batch, PostPlan, flow_speckle_filter, flow_fb_check, flow_in_fill)
 from .stereo_pp import stereo_sgm_pp, stereo_disp_from_first, stereo_fb_check  # noqa: F401
 from .ng import calc_pyd_cost_sgm_ng, calc_cost_sgm_ng, calc_pyd_cost_sgm_ng_batch, calc_cost_sgm_ng_batch  # noqa: F401
+from .view2 import view2_check, NO_VIEW2  # noqa: F401
 from ._lib import FsgmError, load as load_library  # noqa: F401

@@ -4,6 +4,7 @@
 #include "capi_device.h"
 #include "capi_sgm.h"
 #include "epi_kernels.h"
+#include "epi_view2.h"
 #include "geometry_kernels.h"
 #include "post_kernels.h"
 #include "post_plan.h"
@@ -109,6 +110,12 @@ struct fsgm_epi_plan {
     int runner_up = 0;                   // the WTA also writes the runner-up cost (fsgm_epi_plan_set_runner_up): line kernels at every batch size
     uint32_t* dMinC2 = nullptr;          // [batch][NP], created when the switch first goes on
     int exact = 0;                       // exact path arithmetic (fsgm_epi_plan_set_exact): line kernels at every batch size, never with runner_up
+    // second view (fsgm_epi_plan_set_view2): a WTA over the diagonal of S after the first view's, on the same volumes: line kernels at
+    // every batch size.  v2_dir: candidate i of first-view pixel x is second-view pixel x + v2_dir * (d_min + i)
+    int view2 = 0, v2_dir = -1;
+    uint32_t *dDisp2v = nullptr, *dMinCv2 = nullptr;   // [batch][NP] each, created when the switch first goes on
+    uint8_t* dConfV2 = nullptr;          // [batch][NP] the one-shot entries' left-right check, created on first use
+    uint32_t v2_add = 0, v2_marker = 0xFFFFFFFFu;   // the stereo one-shot entries: 256 * d_min and INT32_MIN for the length of a call
     int agg_mode = 0;                    // 0 auto, 1 per-direction line kernels, 2 fused sweeps (if eligible), 3 parallel sweeps, 4 / 5 band sweeps, 6 sweeps meeting in the middle
     int cus = 256;                       // compute units of the device (band sweeps: one workgroup per frame, two per CU)
     Pipeline pipe = PIPE_GENERIC;
@@ -227,8 +234,8 @@ static Pipeline choose_pipeline(int W, int H, int D, int batch, int paths, int P
 // switches (A/B) are read here, once per process.
 static void select_kernel(fsgm_epi_plan* p) {
     const int cm = *std::max_element(p->cmax.begin(), p->cmax.end());
-    const Pipeline k = choose_pipeline(p->W, p->H, p->D, p->batch, p->prm.paths, p->P1, p->P2, cm, p->agg_mode, p->cus, p->adaptive || p->runner_up,
-                                       p->exact);
+    const Pipeline k = choose_pipeline(p->W, p->H, p->D, p->batch, p->prm.paths, p->P1, p->P2, cm, p->agg_mode, p->cus,
+                                       p->adaptive || p->runner_up || p->view2, p->exact);
     const int B = p->batch;
     const bool fine_ok = pair_x_fine_ok(p->D) != 0;
     PipelineForm f;
@@ -339,7 +346,7 @@ void fsgm_epi_plan_destroy(fsgm_epi_plan* p) {
         if (st) (void)hipStreamSynchronize(st);
     void* bufs[] = {p->dI1, p->dI2, p->dCen1, p->dCen2, p->dPd0, p->dNd, p->dOff, p->dVz,
                     p->dCraw, p->dC, p->dL, p->dBestD, p->dMinC, p->dS, p->dD2enc, p->dD2, p->dConf, p->dLh, p->dX, p->dXup, p->dXupAll, p->dStateUp, p->dLx, p->dState, p->dCkpt, p->dCkptV, p->dRec, p->dS0, p->dRflow, p->dFlow, p->dRgb, p->dBits, p->dBandEdge, p->dBandTicket, p->dBandErr,
-                    p->dD1, p->dFlow2, p->dIngest, p->dIngestFlag, p->dMinC2};
+                    p->dD1, p->dFlow2, p->dIngest, p->dIngestFlag, p->dMinC2, p->dDisp2v, p->dMinCv2, p->dConfV2};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     fsgm_post_plan_destroy(p->post);
@@ -666,6 +673,8 @@ static fsgm_status prepare(fsgm_epi_plan* p, int stages) {
             if (!p->dI1 || !p->have_img[f])
                 return fail(FSGM_ERR_INVALID, "adaptive P2: no image uploaded for frame %d (fsgm_epi_plan_upload / _upload_images)", f);
     }
+    if (p->view2 && (stages & FSGM_STAGE_COST) && p->sampling != FSGM_SAMPLING_RECTIFIED)
+        return fail(FSGM_ERR_INVALID, "second view: the candidates of this plan's own cost stage share no line (upload the cost volumes instead)");
     if ((stages & FSGM_STAGE_COST) || p->prm.fb_check) {
         fsgm_status cs = ensure_cost_buffers(p);
         if (cs != FSGM_OK) return cs;
@@ -973,6 +982,15 @@ static fsgm_status enqueue(fsgm_epi_plan* p, int stages) {
             a.L = p->dL; a.l_frame_stride = p->N * p->prm.paths; a.l_dir_stride = p->N;
             const WtaCostArgs x{pipe_exact(p->pipe) ? p->dC : nullptr, p->N};
             launch_wta(p->stream, a, p->batch, agg_line_split(p->D), x);
+            if (p->view2) {                              // the second view's WTA over the same volumes (epi_view2.hip)
+                View2Args v{};
+                v.L = p->dL; v.l_frame_stride = a.l_frame_stride; v.l_dir_stride = a.l_dir_stride;
+                v.C = x.C; v.c_frame_stride = x.c_frame_stride;
+                v.disp2 = p->dDisp2v; v.minC2v = p->dMinCv2;
+                v.W = p->W; v.H = p->H; v.D = p->D; v.ndirs = p->prm.paths; v.dir = p->v2_dir; v.d_min = p->d_min;
+                v.subpixel = p->prm.subpixel; v.add = p->v2_add; v.marker = p->v2_marker;
+                launch_view2(p->stream, v, p->batch);
+            }
         }
     }
     if ((stages & FSGM_STAGE_WTA) && p->prm.fb_check) {
@@ -1005,6 +1023,8 @@ fsgm_status fsgm_epi_plan_set_agg_mode(fsgm_epi_plan* p, int32_t mode) {
         return fail(FSGM_ERR_UNSUPPORTED, "agg mode %d on a runner-up plan: only the line kernels' WTA (modes 0 and 1) writes the runner-up cost", mode);
     if (p->exact && mode >= 2)
         return fail(FSGM_ERR_UNSUPPORTED, "agg mode %d on an exact plan: only the line kernels (modes 0 and 1) carry path costs above 255", mode);
+    if (p->view2 && mode >= 2)
+        return fail(FSGM_ERR_UNSUPPORTED, "agg mode %d on a second-view plan: only the line kernels (modes 0 and 1) keep the path volumes", mode);
     p->agg_mode = mode;
     select_kernel(p);
     return FSGM_OK;
@@ -1057,6 +1077,53 @@ fsgm_status fsgm_epi_plan_set_exact(fsgm_epi_plan* p, int32_t on) {
     select_kernel(p);
     return FSGM_OK;
 }
+
+fsgm_status fsgm_epi_plan_set_view2(fsgm_epi_plan* p, int32_t on, int32_t direction) {
+    FSGM_REQUIRE(p, "null plan");
+    FSGM_REQUIRE(on == 0 || on == 1, "fsgm_epi_plan_set_view2: on must be 0 or 1 (got %d)", on);
+    if (!on) { p->view2 = 0; select_kernel(p); return FSGM_OK; }
+    FSGM_REQUIRE(direction == -1 || direction == 1, "fsgm_epi_plan_set_view2: direction must be -1 or +1 (got %d)", direction);
+    if (p->sampling == FSGM_SAMPLING_LINEAR || (p->sampling == FSGM_SAMPLING_VZ && p->prm.vz_to_disp))
+        return fail(FSGM_ERR_UNSUPPORTED, "second view on a plan with the vz sampling or per-pixel direction maps: its candidates share no line");
+    FSGM_REQUIRE(p->sampling != FSGM_SAMPLING_RECTIFIED || direction == p->direction,
+                 "fsgm_epi_plan_set_view2: a rectified plan's second view has the plan's direction %d (got %d)", p->direction, direction);
+    if (p->agg_mode >= 2)
+        return fail(FSGM_ERR_UNSUPPORTED, "second view on a plan forced to agg mode %d: only the line kernels (modes 0 and 1) keep the path volumes",
+                    p->agg_mode);
+    if (!p->dDisp2v) {                                           // all ones until a WTA has run: FSGM_NO_VIEW2
+        const size_t bytes = (size_t)p->batch * p->NP * 4;
+        FSGM_HIP(hipSetDevice(p->prm.device));
+        LazySet ls;
+        uint32_t* d = ls.alloc(p->dDisp2v, bytes);
+        uint32_t* m = ls.alloc(p->dMinCv2, bytes);
+        if (ls.err == hipSuccess) ls.err = hipMemsetAsync(d, 0xFF, bytes, p->stream);
+        if (ls.err == hipSuccess) ls.err = hipMemsetAsync(m, 0xFF, bytes, p->stream);
+        if (ls.err != hipSuccess) return lazy_fail(ls, "fsgm_epi_plan_set_view2");
+        ls.commit();
+    }
+    p->view2 = 1; p->v2_dir = direction;
+    select_kernel(p);
+    return FSGM_OK;
+}
+
+fsgm_status fsgm_epi_plan_download_view2(fsgm_epi_plan* p, int32_t f, uint32_t* disp2, uint32_t* minC_v2) {
+    FSGM_REQUIRE(p, "null plan");
+    FSGM_REQUIRE(f >= 0 && f < p->batch, "frame %d out of range (batch %d)", f, p->batch);
+    FSGM_REQUIRE(p->view2, "fsgm_epi_plan_download_view2: the plan's second-view switch is off (fsgm_epi_plan_set_view2)");
+    { fsgm_status fs = frame_ready(p, f, 2); if (fs != FSGM_OK) return fs; }
+    if (disp2) FSGM_HIP(hipMemcpy(disp2, p->dDisp2v + f * p->NP, p->NP * 4, hipMemcpyDeviceToHost));
+    if (minC_v2) FSGM_HIP(hipMemcpy(minC_v2, p->dMinCv2 + f * p->NP, p->NP * 4, hipMemcpyDeviceToHost));
+    return FSGM_OK;
+}
+
+fsgm_status fsgm_view2_launch_lds(int32_t dMax, uint64_t* bytes) {
+    FSGM_REQUIRE(bytes, "fsgm_view2_launch_lds: null argument");
+    FSGM_REQUIRE(dMax >= 1 && dMax <= FSGM_GENERIC_MAX_D, "fsgm_view2_launch_lds: dMax must be 1..%d (got %d)", FSGM_GENERIC_MAX_D, dMax);
+    *bytes = view2_lds_bytes(dMax);
+    return FSGM_OK;
+}
+
+int32_t fsgm_view2_tile(int32_t dMax) { return dMax >= 1 && dMax <= FSGM_GENERIC_MAX_D ? view2_tile(dMax) : 0; }
 
 fsgm_status fsgm_epi_plan_set_d_min(fsgm_epi_plan* p, int32_t d_min) {
     FSGM_REQUIRE(p, "null plan");
@@ -1246,7 +1313,8 @@ static PlanCache<fsgm_epi_plan> g_epi(4, fsgm_epi_plan_destroy, [](const fsgm_ep
 // (a plan serves one sampling mode and, rectified, one direction: the modes share no cached state)
 static fsgm_status cached_plan(std::unique_lock<std::mutex>& lk, fsgm_epi_plan** out, int W, int H, int D, int batch,
                                const fsgm_epi_params& pr, int sampling = FSGM_SAMPLING_VZ, int direction = 0, int adaptive = 0,
-                               int agg_mode = 0, int runner_up = 0, int exact = 0, bool must_exist = false) {
+                               int agg_mode = 0, int runner_up = 0, int exact = 0, bool must_exist = false,
+                               int view2_dir = 0) {
     FSGM_DEVICE_SLOT(pr.device);
     lk = std::unique_lock<std::mutex>(g_epi.mu(pr.device));
     fsgm_epi_plan* p = g_epi.find(pr.device, [&](const fsgm_epi_plan* q) {
@@ -1255,7 +1323,8 @@ static fsgm_status cached_plan(std::unique_lock<std::mutex>& lk, fsgm_epi_plan**
                q->direction == direction && q->adaptive == adaptive &&   // (adaptive and non-adaptive callers never share a plan)
                q->agg_mode == agg_mode &&                                // (nor do forced modes: only the sgm batch forms ask for one)
                q->runner_up == runner_up &&                              // (nor a runner-up caller and a plain one: the plain call keeps its pipeline)
-               q->exact == exact;                                        // (nor an exact caller and a plain one)
+               q->exact == exact &&                                      // (nor an exact caller and a plain one)
+               q->view2 == (view2_dir != 0) && (!view2_dir || q->v2_dir == view2_dir);   // (nor a second-view caller and a plain one)
     });
     if (p) p->prm = pr;
     else if (must_exist)                                         // (a captured call: creating a plan allocates, copies and waits)
@@ -1267,6 +1336,7 @@ static fsgm_status cached_plan(std::unique_lock<std::mutex>& lk, fsgm_epi_plan**
         else if (st == FSGM_OK && agg_mode && (st = fsgm_epi_plan_set_agg_mode(p, agg_mode)) != FSGM_OK) fsgm_epi_plan_destroy(p);
         else if (st == FSGM_OK && runner_up && (st = fsgm_epi_plan_set_runner_up(p, 1)) != FSGM_OK) fsgm_epi_plan_destroy(p);
         else if (st == FSGM_OK && exact && (st = fsgm_epi_plan_set_exact(p, 1)) != FSGM_OK) fsgm_epi_plan_destroy(p);
+        else if (st == FSGM_OK && view2_dir && (st = fsgm_epi_plan_set_view2(p, 1, view2_dir)) != FSGM_OK) fsgm_epi_plan_destroy(p);
         if (st != FSGM_OK) return st;
         g_epi.insert(pr.device, p);
     }
@@ -1415,9 +1485,42 @@ fsgm_status fsgm_stereo_sgm_host(int32_t n, const uint8_t* I1, const uint8_t* I2
 // The cached rectified plan is shared by every d_min (the key does not hold it): each stereo entry point sets the plan's shift
 // under the plan's lock before it queues anything, the older ones to 0.  ranged: the _range forms, whose disp / disp2 leave as
 // int32 true disparities.
+// the one-shot entries' left-right check buffer [batch][NP]
+static fsgm_status ensure_view2_conf(fsgm_epi_plan* p) {
+    if (!p->dConfV2) FSGM_HIP(hipMalloc((void**)&p->dConfV2, (size_t)p->batch * p->NP));
+    return FSGM_OK;
+}
+// the view-2 forms' own arguments (include/fsgm.h, "Second view"): disp2 required, minC_v2 and conf may be NULL
+struct StereoView2 {
+    int max_diff;
+    uint32_t *disp2, *minC_v2;
+    uint8_t* conf;
+};
+static fsgm_status stereo_view2_args(const char* who, const fsgm_stereo_params& sp, const StereoView2& v) {
+    FSGM_REQUIRE(v.disp2, "%s: null disp2", who);
+    FSGM_REQUIRE(v.max_diff >= 0, "%s: max_diff must be >= 0 (got %d)", who, v.max_diff);
+    FSGM_REQUIRE(!sp.fb_check, "%s: fb_check = 1 is the forward-backward check of fsgm_stereo_sgm_host (the other door): not together with the second view", who);
+    return FSGM_OK;
+}
+// the plan's second view as int32 true disparities for the length of one enqueue
+struct View2Format {
+    fsgm_epi_plan* p;
+    View2Format(fsgm_epi_plan* q, int d_min) : p(q) { p->v2_add = (uint32_t)(256 * d_min); p->v2_marker = 0x80000000u; }
+    ~View2Format() { p->v2_add = 0; p->v2_marker = 0xFFFFFFFFu; }
+};
+// the left-right check on a stereo call's outputs, int32 true disparities both
+static void enqueue_stereo_view2_check(fsgm_epi_plan* p, int dir, int max_diff, int n, const uint32_t* disp, const uint32_t* disp2, uint8_t* conf) {
+    View2CheckArgs k{};
+    k.disp = disp; k.disp2 = disp2; k.conf = conf; k.W = p->W; k.H = p->H; k.dir = dir; k.max_diff = max_diff;
+    k.add1 = k.add2 = 0; k.marker2 = 0x80000000u;
+    if (!p->prm.subpixel) { k.pre1 = k.add1 = 256 * p->d_min; k.shift1 = 8; }   // (disp = 256 * d_min + the whole index, as the _range forms return it)
+    launch_view2_check(p->stream, k, n);
+}
+
 static fsgm_status stereo_host(const char* who, int32_t n, const uint8_t* I1, const uint8_t* I2, int32_t W, int32_t H, int32_t dMax,
                                int32_t P1, int32_t P2, const fsgm_stereo_params* prm, const fsgm_epi_options* opt, int32_t d_min,
-                               bool ranged, uint32_t* disp, uint32_t* minC, uint8_t* conf, uint32_t* disp2, uint32_t* minC2 = nullptr) {
+                               bool ranged, uint32_t* disp, uint32_t* minC, uint8_t* conf, uint32_t* disp2, uint32_t* minC2 = nullptr,
+                               const StereoView2* v2 = nullptr) {
     fsgm_stereo_params sp;
     fsgm_epi_params pr;
     fsgm_epi_options o;
@@ -1425,18 +1528,23 @@ static fsgm_status stereo_host(const char* who, int32_t n, const uint8_t* I1, co
     if (st != FSGM_OK) return st;
     if ((st = read_options(who, opt, &o)) != FSGM_OK) return st;
     FSGM_REQUIRE(d_min >= -FSGM_D_MIN_LIMIT && d_min <= FSGM_D_MIN_LIMIT, "%s: |d_min| must be <= %d (got %d)", who, FSGM_D_MIN_LIMIT, d_min);
+    if (v2 && (st = stereo_view2_args(who, sp, *v2)) != FSGM_OK) return st;
     std::unique_lock<std::mutex> lk;
     fsgm_epi_plan* p = nullptr;
-    if ((st = cached_plan(lk, &p, W, H, dMax, n, pr, FSGM_SAMPLING_RECTIFIED, sp.direction, o.adaptive_p2, 0, minC2 != nullptr)) != FSGM_OK) return st;
+    if ((st = cached_plan(lk, &p, W, H, dMax, n, pr, FSGM_SAMPLING_RECTIFIED, sp.direction, o.adaptive_p2, 0, minC2 != nullptr, 0, false,
+                          v2 ? sp.direction : 0)) != FSGM_OK) return st;
     p->d_min = d_min;
     if ((st = fsgm_epi_plan_set_penalties(p, P1, P2, p->vMax)) != FSGM_OK) return st;
     if ((st = ensure_cost_buffers(p)) != FSGM_OK) return st;
+    if (v2 && v2->conf && (st = ensure_view2_conf(p)) != FSGM_OK) return st;
     p->have_img.assign(n, 1);                                    // the pairs go up below, ahead of the kernels
     const size_t np = (size_t)n * p->NP;
     StreamGuard guard(p->stream);                                // every early exit drains the stream: the copies use caller memory
     FSGM_HIP(hipMemcpyAsync(p->dI1, I1, np, hipMemcpyHostToDevice, p->stream));
     FSGM_HIP(hipMemcpyAsync(p->dI2, I2, np, hipMemcpyHostToDevice, p->stream));
-    if ((st = enqueue(p, FSGM_STAGE_ALL)) != FSGM_OK) return st;
+    if (v2) { View2Format fmt(p, d_min); st = enqueue(p, FSGM_STAGE_ALL); }
+    else st = enqueue(p, FSGM_STAGE_ALL);
+    if (st != FSGM_OK) return st;
     g_stereo_kernel = kPipelineName[p->pipe];
     if (ranged) {
         launch_stereo_range(p->stream, p->dBestD, pr.fb_check ? p->dD2 : nullptr, np, d_min);
@@ -1447,6 +1555,15 @@ static fsgm_status stereo_host(const char* who, int32_t n, const uint8_t* I1, co
     if (minC2) FSGM_HIP(hipMemcpyAsync(minC2, p->dMinC2, np * 4, hipMemcpyDeviceToHost, p->stream));
     if (pr.fb_check && conf) FSGM_HIP(hipMemcpyAsync(conf, p->dConf, np, hipMemcpyDeviceToHost, p->stream));
     if (pr.fb_check && disp2) FSGM_HIP(hipMemcpyAsync(disp2, p->dD2, np * 4, hipMemcpyDeviceToHost, p->stream));
+    if (v2) {                                                    // (ranged: dBestD holds int32 true disparities by now)
+        FSGM_HIP(hipMemcpyAsync(v2->disp2, p->dDisp2v, np * 4, hipMemcpyDeviceToHost, p->stream));
+        if (v2->minC_v2) FSGM_HIP(hipMemcpyAsync(v2->minC_v2, p->dMinCv2, np * 4, hipMemcpyDeviceToHost, p->stream));
+        if (v2->conf) {
+            enqueue_stereo_view2_check(p, sp.direction, v2->max_diff, n, p->dBestD, p->dDisp2v, p->dConfV2);
+            FSGM_HIP(hipGetLastError());
+            FSGM_HIP(hipMemcpyAsync(v2->conf, p->dConfV2, np, hipMemcpyDeviceToHost, p->stream));
+        }
+    }
     FSGM_HIP(hipStreamSynchronize(p->stream));
     guard.dismiss();
     return check_handoff(p);
@@ -1474,6 +1591,16 @@ fsgm_status fsgm_stereo_sgm_host_ru(int32_t n, const uint8_t* I1, const uint8_t*
     FSGM_REQUIRE(minC2, "fsgm_stereo_sgm_host_ru: null minC2");
     return stereo_host("fsgm_stereo_sgm_host_ru", n, I1, I2, W, H, dMax, P1, P2, prm, opt, d_min, true, (uint32_t*)disp, minC, conf,
                        (uint32_t*)disp2, minC2);
+}
+
+// the second view from the same aggregated volume and the left-right check against it (include/fsgm.h, "Second view")
+fsgm_status fsgm_stereo_sgm_view2_host(int32_t n, const uint8_t* I1, const uint8_t* I2, int32_t W, int32_t H, int32_t dMax, int32_t P1,
+                                       int32_t P2, const fsgm_stereo_params* prm, const fsgm_epi_options* opt, int32_t d_min,
+                                       int32_t max_diff, int32_t* disp, uint32_t* minC, uint32_t* minC2, int32_t* disp2,
+                                       uint32_t* minC_v2, uint8_t* conf) {
+    const StereoView2 v{max_diff, (uint32_t*)disp2, minC_v2, conf};
+    return stereo_host("fsgm_stereo_sgm_view2_host", n, I1, I2, W, H, dMax, P1, P2, prm, opt, d_min, true, (uint32_t*)disp, minC, nullptr,
+                       nullptr, minC2, &v);
 }
 
 // sgm(C, P1, P2): sgm.m's call shape on the MEX's aggregation + WTA (MEX semantics: include/fsgm.h)
@@ -1506,7 +1633,16 @@ static fsgm_status sgm_plan(std::unique_lock<std::mutex>& lk, fsgm_epi_plan** p,
     fsgm_epi_params pr = fsgm_epi_params_default();
     pr.paths = c.prm.paths; pr.subpixel = c.prm.subpixel; pr.device = c.prm.device; pr.vz_to_disp = 0; pr.fb_check = 0;
     return cached_plan(lk, p, c.W, c.H, c.D, c.n, pr, FSGM_SAMPLING_VZ, 0, c.prm.adaptive_p2, c.prm.agg_mode, c.minC2 != nullptr, c.exact,
-                       c.captured != 0);
+                       c.captured != 0, c.view2);
+}
+
+// the check of the sgm(C) view-2 forms on the plan's own outputs: index units, both shifted by the call's d_min
+static void enqueue_sgm_view2_check(fsgm_epi_plan* p, const SgmCall& c, const uint32_t* bestD, const uint32_t* disp2, uint8_t* conf) {
+    View2CheckArgs k{};
+    k.disp = bestD; k.disp2 = disp2; k.conf = conf; k.W = p->W; k.H = p->H; k.dir = c.view2; k.max_diff = c.max_diff;
+    k.add1 = k.add2 = 256 * c.d_min; k.marker2 = 0xFFFFFFFFu;
+    k.shift1 = c.prm.subpixel ? 0 : 8;                           // (without sub-pixel bestD is the whole index, disp2 always index * 256)
+    launch_view2_check(p->stream, k, c.n);
 }
 
 static fsgm_status ensure_ingest_flag(fsgm_epi_plan* p) {
@@ -1531,6 +1667,8 @@ fsgm_status sgm_run_host(const SgmCall& c, const int* cmax) {
     const bool dhw = c.prm.layout == FSGM_COST_LAYOUT_DHW;       // staged as it came, transposed on the device
     if (dhw && c.fmt.dtype < 0 && !p->dIngest) FSGM_HIP(hipMalloc((void**)&p->dIngest, nv));
     if (c.fmt.dtype >= 0 && (st = ensure_ingest_flag(p)) != FSGM_OK) return st;
+    if (c.view2) p->d_min = c.d_min;                             // (read by the second view's kernel only: the plan has no cost stage to shift)
+    if (c.conf && (st = ensure_view2_conf(p)) != FSGM_OK) return st;
     StreamGuard guard(p->stream);                                // every early exit drains the stream: the copies use caller memory
     if (c.fmt.dtype >= 0) {
         // a float volume: staged frame by frame, quantised by the kernel the device form runs; the flag is read before any output is written
@@ -1546,6 +1684,15 @@ fsgm_status sgm_run_host(const SgmCall& c, const int* cmax) {
     FSGM_HIP(hipMemcpyAsync(c.bestD, p->dBestD, (size_t)c.n * NP * 4, hipMemcpyDeviceToHost, p->stream));
     FSGM_HIP(hipMemcpyAsync(c.minC, p->dMinC, (size_t)c.n * NP * 4, hipMemcpyDeviceToHost, p->stream));
     if (c.minC2) FSGM_HIP(hipMemcpyAsync(c.minC2, p->dMinC2, (size_t)c.n * NP * 4, hipMemcpyDeviceToHost, p->stream));
+    if (c.view2) {
+        FSGM_HIP(hipMemcpyAsync(c.disp2, p->dDisp2v, (size_t)c.n * NP * 4, hipMemcpyDeviceToHost, p->stream));
+        if (c.minC_v2) FSGM_HIP(hipMemcpyAsync(c.minC_v2, p->dMinCv2, (size_t)c.n * NP * 4, hipMemcpyDeviceToHost, p->stream));
+        if (c.conf) {
+            enqueue_sgm_view2_check(p, c, p->dBestD, p->dDisp2v, p->dConfV2);
+            FSGM_HIP(hipGetLastError());
+            FSGM_HIP(hipMemcpyAsync(c.conf, p->dConfV2, (size_t)c.n * NP, hipMemcpyDeviceToHost, p->stream));
+        }
+    }
     FSGM_HIP(hipStreamSynchronize(p->stream));
     guard.dismiss();
     if ((st = check_handoff(p)) != FSGM_OK) return st;
@@ -1579,14 +1726,17 @@ fsgm_status sgm_run_device(const SgmCall& c, hipStream_t cs, int32_t* status) {
     if ((st = prepare(p, FSGM_STAGE_AGGREGATE | FSGM_STAGE_WTA)) != FSGM_OK) return st;
     if ((st = ensure_ingest_flag(p)) != FSGM_OK) return st;
     if (c.S && (st = ensure_tap_buffers(p)) != FSGM_OK) return st;
+    if (c.view2) p->d_min = c.d_min;
     return device_call(p->join, cs, p->stream, [&]() -> fsgm_status {
         if (c.fmt.dtype >= 0) launch_sgm_ingest_float(p->stream, c.C, c.fmt, p->dC, c.n, c.W, c.H, c.D, c.prm.layout, c.prm.cost_bound, p->dIngestFlag);
         else launch_sgm_ingest(p->stream, c.C, p->dC, c.n, c.W, c.H, c.D, c.prm.layout, c.prm.cost_bound, p->dIngestFlag);
         if (c.guide) FSGM_HIP(hipMemcpyAsync(p->dI1, c.guide, (size_t)c.n * p->NP, hipMemcpyDeviceToDevice, p->stream));
         Bind<uint32_t> bd(p->dBestD, c.bestD), mc(p->dMinC, c.minC), m2(p->dMinC2, c.minC2);
+        Bind<uint32_t> d2(p->dDisp2v, c.disp2), mv(p->dMinCv2, c.minC_v2);   // (the view-2 forms: written where they lie)
         const fsgm_status es = enqueue(p, FSGM_STAGE_AGGREGATE | FSGM_STAGE_WTA);
         if (es != FSGM_OK) return es;
         g_sgm_kernel = kPipelineName[p->pipe];
+        if (c.view2 && c.conf) enqueue_sgm_view2_check(p, c, c.bestD, c.disp2, c.conf);
         for (int f = 0; c.S && f < c.n; f++) {                   // S never exists for a batch: frame by frame through the tap's buffer
             tap_sum(p, f);
             FSGM_HIP(hipMemcpyAsync(c.S + (size_t)f * p->N, p->dS, p->N * 4, hipMemcpyDeviceToDevice, p->stream));
@@ -1831,7 +1981,7 @@ fsgm_status fsgm_stereo_sgm_device(int32_t n, const uint8_t* I1, const uint8_t* 
 static fsgm_status stereo_device(const char* who, int32_t n, const uint8_t* I1, const uint8_t* I2, int32_t W, int32_t H, int32_t dMax,
                                  int32_t P1, int32_t P2, const fsgm_stereo_params* prm, const fsgm_epi_options* opt, int32_t d_min,
                                  bool ranged, uint32_t* disp, uint32_t* minC, uint8_t* conf, uint32_t* disp2, void* stream,
-                                 int32_t* status, uint32_t* minC2 = nullptr) {
+                                 int32_t* status, uint32_t* minC2 = nullptr, const StereoView2* v2 = nullptr) {
     fsgm_stereo_params sp;
     fsgm_epi_params pr;
     fsgm_epi_options o;
@@ -1839,6 +1989,7 @@ static fsgm_status stereo_device(const char* who, int32_t n, const uint8_t* I1, 
     if (st != FSGM_OK) return st;
     if ((st = read_options(who, opt, &o)) != FSGM_OK) return st;
     FSGM_REQUIRE(d_min >= -FSGM_D_MIN_LIMIT && d_min <= FSGM_D_MIN_LIMIT, "%s: |d_min| must be <= %d (got %d)", who, FSGM_D_MIN_LIMIT, d_min);
+    if (v2 && (st = stereo_view2_args(who, sp, *v2)) != FSGM_OK) return st;
     const size_t np = (size_t)n * (size_t)W * (size_t)H;
     const bool fb = pr.fb_check != 0;
     const hipStream_t cs = (hipStream_t)stream;
@@ -1849,21 +2000,30 @@ static fsgm_status stereo_device(const char* who, int32_t n, const uint8_t* I1, 
                                                      {minC2, np * 4, 4, false, "minC2"},
                                                      {fb ? conf : nullptr, np, 1, false, "conf"},
                                                      {fb ? disp2 : nullptr, np * 4, 4, false, "disp2"},
+                                                     {v2 ? v2->disp2 : nullptr, np * 4, 4, v2 != nullptr, "disp2"},
+                                                     // (the label carries the type for the reason given at fsgm_sgm_view2_dptr's table, capi_sgm.hip)
+                                                     {v2 ? v2->minC_v2 : nullptr, np * 4, 4, false, "minC_v2 (u32)"},
+                                                     {v2 ? v2->conf : nullptr, np, 1, false, "conf"},
                                                      {status, 4, 4, false, "status"}})) != FSGM_OK)
         return st;
     std::unique_lock<std::mutex> lk;
     fsgm_epi_plan* p = nullptr;
-    if ((st = cached_plan(lk, &p, W, H, dMax, n, pr, FSGM_SAMPLING_RECTIFIED, sp.direction, o.adaptive_p2, 0, minC2 != nullptr)) != FSGM_OK) return st;
+    if ((st = cached_plan(lk, &p, W, H, dMax, n, pr, FSGM_SAMPLING_RECTIFIED, sp.direction, o.adaptive_p2, 0, minC2 != nullptr, 0, false,
+                          v2 ? sp.direction : 0)) != FSGM_OK) return st;
     p->d_min = d_min;
     if ((st = epi_device_prepare(p, P1, P2, p->vMax)) != FSGM_OK) return st;
     return device_call(p->join, cs, p->stream, [&]() -> fsgm_status {
         Bind<uint8_t> i1(p->dI1, const_cast<uint8_t*>(I1)), i2(p->dI2, const_cast<uint8_t*>(I2));
         Bind<uint32_t> bd(p->dBestD, disp), mc(p->dMinC, minC), d2(p->dD2, fb ? disp2 : nullptr), m2(p->dMinC2, minC2);
         Bind<uint8_t> cf(p->dConf, fb ? conf : nullptr);
-        const fsgm_status es = enqueue(p, FSGM_STAGE_ALL);
+        Bind<uint32_t> v2d(p->dDisp2v, v2 ? v2->disp2 : nullptr), v2m(p->dMinCv2, v2 ? v2->minC_v2 : nullptr);
+        fsgm_status es;
+        if (v2) { View2Format fmt(p, d_min); es = enqueue(p, FSGM_STAGE_ALL); }
+        else es = enqueue(p, FSGM_STAGE_ALL);
         if (es != FSGM_OK) return es;
         g_stereo_kernel = kPipelineName[p->pipe];
         if (ranged) launch_stereo_range(p->stream, disp, fb ? disp2 : nullptr, np, d_min);
+        if (v2 && v2->conf) enqueue_stereo_view2_check(p, sp.direction, v2->max_diff, n, disp, v2->disp2, v2->conf);
         launch_device_status(p->stream, p->dBandErr, nullptr, status);
         return FSGM_OK;
     });
@@ -1890,6 +2050,16 @@ fsgm_status fsgm_stereo_sgm_device_ru(int32_t n, const uint8_t* I1, const uint8_
     FSGM_REQUIRE(minC2, "fsgm_stereo_sgm_device_ru: null minC2");
     return stereo_device("fsgm_stereo_sgm_device_ru", n, I1, I2, W, H, dMax, P1, P2, prm, opt, d_min, true, (uint32_t*)disp, minC, conf,
                          (uint32_t*)disp2, stream, status, minC2);
+}
+
+// fsgm_stereo_sgm_view2_host on device pointers: disp2, minC_v2 and conf are written where they lie
+fsgm_status fsgm_stereo_sgm_view2_dptr(int32_t n, const uint8_t* I1, const uint8_t* I2, int32_t W, int32_t H, int32_t dMax, int32_t P1,
+                                       int32_t P2, const fsgm_stereo_params* prm, const fsgm_epi_options* opt, int32_t d_min,
+                                       int32_t max_diff, int32_t* disp, uint32_t* minC, uint32_t* minC2, int32_t* disp2,
+                                       uint32_t* minC_v2, uint8_t* conf, void* stream, int32_t* status) {
+    const StereoView2 v{max_diff, (uint32_t*)disp2, minC_v2, conf};
+    return stereo_device("fsgm_stereo_sgm_view2_dptr", n, I1, I2, W, H, dMax, P1, P2, prm, opt, d_min, true, (uint32_t*)disp, minC, nullptr,
+                         nullptr, stream, status, minC2, &v);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -15,6 +15,11 @@ struct SgmCall {
     int exact;                           // the _exact forms: exact path arithmetic, P1 and P2 checked to lie in 0..255 (never with minC2)
     int captured = 0;                    // fsgm_sgm_device_exact alone: the caller's stream is being captured into a graph
     CostFormat fmt;                      // the float forms: C holds elements of fmt.dtype (-1 in the u8 forms), quantised by the ingest
+    // the view-2 forms (include/fsgm.h, "Second view"): view2 = the direction, -1 or +1 (0 in every other form); disp2 is never NULL
+    // then, minC_v2 and conf may be
+    int view2 = 0, d_min = 0, max_diff = 0;
+    uint32_t *disp2 = nullptr, *minC_v2 = nullptr;
+    uint8_t* conf = nullptr;
 };
 
 // host pointers; cmax: the largest byte of each frame's volume (none above prm.cost_bound), of a float volume prm.cost_bound

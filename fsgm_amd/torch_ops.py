@@ -41,6 +41,7 @@ from .epi import EpiGeometry, _d_min, _params as _epi_params, _stereo_params
 from .post import _bind as _bind_post
 from .stereo_pp import CHAIN_FIELDS as STEREO_PP_FIELDS, _bind as _bind_stereo_pp, pp_params as _stereo_pp_params
 from .sgm import _bind as _bind_sgm, arith_exact as _arith_exact, cost_format as _cost_format, layout_code as _layout_code, params as _sgm_params, shape_of as _sgm_shape
+from .view2 import bind as _bind_view2, params as _view2_params
 from .sgm2d import _bind as _bind_sgm2d, arith_exact as _arith2d_exact, layout_code as _layout2d_code, params as _sgm2d_params, shape_of as _sgm2d_shape, LAYOUTS as _LAYOUTS2D
 from .pyramid import (PyramidParams, NgPyramidParams, FLOW_PP_FIELDS, MATCHERS, _bind as _bind_pyramid, _bind_flow_pp, _bind_ng,
                       uniqueness_ratio_of as _uniqueness_ratio_of, level_median_of as _level_median_of)
@@ -76,6 +77,8 @@ _bind_flow_pp(_L)
 _bind_stereo_pp(_L)
 _bind_sgm(_L)
 _bind_sgm2d(_L)
+if hasattr(_L, "fsgm_sgm_view2_dptr"):                          # (an older build behind FSGM_LIB_PATH has none)
+    _bind_view2(_L)
 _L.fsgm_calc_cost_sgm_device.argtypes = [_i32, C.POINTER(EpiIn), C.POINTER(EpiOut), C.POINTER(EpiParams), _vp, _vp]
 _L.fsgm_calc_cost_sgm_linear_device.argtypes = [_i32, C.POINTER(EpiIn), C.POINTER(EpiOut), C.POINTER(EpiParams), _vp, _vp]
 _L.fsgm_stereo_sgm_device.argtypes = [_i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, C.POINTER(StereoParams), _vp, _vp, _vp, _vp, _vp, _vp]
@@ -495,6 +498,88 @@ def _sgm2d_float_op(C_: torch.Tensor, hints: torch.Tensor, guide: torch.Tensor, 
 def _(C_, hints, guide, scale, offset, half_x, half_y, P1, P2, layout, cost_bound, diagonal, total_pass, adaptive_p2, subpixel, return_flow,
       return_sum, runner_up, exact):
     return _sgm2d_outputs(C_, layout, half_x, half_y, return_flow, return_sum, bool(runner_up))
+
+
+# ---- the second view from the same aggregated volume (include/fsgm.h, "Second view"): a namespace of its own, fsgm_view2::, one op
+# a family: minC2 is wanted or not (runner_up), exact a flag, as in fsgm_float:: ----
+def _view2_sgm_outputs(C_, layout, return_sum, runner_up):
+    """(bestD, minC, minC2, S, disp2, minC_v2, conf, status): fsgm::sgm_ru's with the second view's three maps before the status"""
+    bestD, minC, minC2, S, status = _sgm_outputs(C_, layout, return_sum, bool(runner_up))
+    return (bestD, minC, minC2, S, torch.empty_like(minC), torch.empty_like(minC), torch.empty(minC.shape, dtype=torch.uint8, device=minC.device),
+            status)
+
+
+@torch.library.custom_op("fsgm_view2::sgm", mutates_args=())
+def _sgm_view2_op(C_: torch.Tensor, guide: torch.Tensor, P1: int, P2: int, paths: int, layout: int, cost_bound: int, agg_mode: int,
+                  adaptive_p2: int, subpixel: int, return_sum: int, runner_up: bool, exact: bool, direction: int, d_min: int, max_diff: int
+                  ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """fsgm::sgm / _ru / _exact with disp2, minC_v2 uint32 and conf uint8 (N, H, W) before the status (fsgm_sgm_view2_dptr)"""
+    N, H, W, D = _sgm_out_shape(C_, layout)
+    dev = C_.device
+    C_ = C_.contiguous()
+    guide = guide.contiguous() if adaptive_p2 else None
+    bestD, minC, minC2, S, disp2, minC_v2, conf, status = _view2_sgm_outputs(C_, layout, return_sum, runner_up)
+    prm = _sgm_params(_L, paths=paths, subpixel=subpixel, device=dev.index, agg_mode=agg_mode, layout="dhw" if layout else "hwd",
+                      cost_bound=cost_bound, adaptive_p2=adaptive_p2)
+    v2 = _view2_params(_L, direction, d_min, max_diff)
+    _call(dev, _L.fsgm_sgm_view2_dptr, N, _p(C_), W, H, D, int(P1), int(P2), C.byref(prm), C.byref(v2), _p(guide), _p(bestD), _p(minC),
+          _p(minC2) if runner_up else None, _p(S) if return_sum else None, int(bool(exact)), _p(disp2), _p(minC_v2), _p(conf), _stream(dev),
+          _p(status))
+    return bestD, minC, minC2, S, disp2, minC_v2, conf, status
+
+
+@_sgm_view2_op.register_fake
+def _(C_, guide, P1, P2, paths, layout, cost_bound, agg_mode, adaptive_p2, subpixel, return_sum, runner_up, exact, direction, d_min, max_diff):
+    return _view2_sgm_outputs(C_, layout, return_sum, runner_up)
+
+
+def _view2_stereo_outputs(left, runner_up):
+    """(disp int32, minC, minC2, disp2 int32, minC_v2, conf, status)"""
+    N, H, W, dev = _frames(left)
+    minC = _u32((N, H, W), dev)
+    i32 = lambda: torch.empty((N, H, W), dtype=torch.int32, device=dev)
+    return (i32(), minC) + _minC2_output(minC, bool(runner_up)) + (i32(), _u32((N, H, W), dev),
+                                                                   torch.empty((N, H, W), dtype=torch.uint8, device=dev), _status(dev))
+
+
+@torch.library.custom_op("fsgm_view2::stereo_sgm", mutates_args=())
+def _stereo_view2_op(left: torch.Tensor, right: torch.Tensor, dMax: int, d_min: int, P1: int, P2: int, paths: int, subpixel: int,
+                     direction: int, adaptive_p2: int, runner_up: bool, max_diff: int
+                     ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """fsgm::stereo_sgm_ru without fb_check, minC2 wanted or not, with disp2 int32, minC_v2 and conf (fsgm_stereo_sgm_view2_dptr)"""
+    N, H, W, dev = _frames(left)
+    left, right = _ready(left), _ready(right)
+    disp, minC, minC2, disp2, minC_v2, conf, status = _view2_stereo_outputs(left, runner_up)
+    prm = _stereo_params(paths, subpixel, direction, 0, dev.index)
+    opt = _lib.options(adaptive_p2)
+    _call(dev, _L.fsgm_stereo_sgm_view2_dptr, N, _p(left), _p(right), W, H, int(dMax), int(P1), int(P2), C.byref(prm), C.byref(opt), int(d_min),
+          int(max_diff), _p(disp), _p(minC), _p(minC2) if runner_up else None, _p(disp2), _p(minC_v2), _p(conf), _stream(dev), _p(status))
+    return disp, minC, minC2, disp2, minC_v2, conf, status
+
+
+@_stereo_view2_op.register_fake
+def _(left, right, dMax, d_min, P1, P2, paths, subpixel, direction, adaptive_p2, runner_up, max_diff):
+    return _view2_stereo_outputs(left, runner_up)
+
+
+def _view2_check_outputs(disp):
+    return torch.empty(disp.shape, dtype=torch.uint8, device=disp.device), _status(disp.device)
+
+
+@torch.library.custom_op("fsgm_view2::check", mutates_args=())
+def _view2_check_op(disp: torch.Tensor, disp2: torch.Tensor, direction: int, max_diff: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """the left-right check alone on int32 true-disparity maps (N, H, W) (fsgm_view2_check_dptr)"""
+    N, H, W, dev = _frames(disp)
+    disp, disp2 = _ready(disp), _ready(disp2)
+    conf, status = _view2_check_outputs(disp)
+    _call(dev, _L.fsgm_view2_check_dptr, N, _p(disp), _p(disp2), W, H, int(direction), int(max_diff), _p(conf), dev.index, _stream(dev),
+          _p(status))
+    return conf, status
+
+
+@_view2_check_op.register_fake
+def _(disp, disp2, direction, max_diff):
+    return _view2_check_outputs(disp)
 
 
 def _epipolar_sgm_of_outputs(I0):
@@ -980,7 +1065,8 @@ def calc_cost_sgm_linear(I1, I2, dMax, pixelPosD0, normlizeDirection, P1, P2, *,
 
 
 def sgm(Cvol, P1=7, P2=100, *, layout="dhw", paths=4, cost_bound=255, agg_mode=0, adaptive_p2=0, guide=None, subpixel=1,
-        return_sum=False, check=False, return_status=False, runner_up=False, arith="mod256"):
+        return_sum=False, check=False, return_status=False, runner_up=False, arith="mod256", second_view=False, direction=-1, d_min=0,
+        max_diff=256):
     """bestD, minC = sgm(C, P1, P2) as fsgm_amd.sgm_batch, on a cost volume that is already in HBM: C uint8 (D, H, W) or a batch
     (N, D, H, W) for layout "dhw" (a cost-volume network's output), (H, W, D) / (N, H, W, D) for "hwd".  The volume is read where
     it lies, every output stays in HBM, the work is queued on the current stream.  bestD, minC uint32 (.., H, W); return_sum
@@ -990,9 +1076,11 @@ def sgm(Cvol, P1=7, P2=100, *, layout="dhw", paths=4, cost_bound=255, agg_mode=0
     check=True synchronises and raises on either.  adaptive_p2=1 needs guide, the first image, uint8 (.., H, W).  runner_up=True
     (fsgm::sgm_ru) returns minC2 uint32 after minC, as fsgm_amd.sgm_batch does.  arith="exact" (fsgm::sgm_exact): path costs that
     are never narrowed to a byte, as fsgm_amd.sgm_batch(arith="exact") -- P1, P2 in 0..255, the line kernels at every batch size;
-    with runner_up=True it raises ValueError."""
+    with runner_up=True it raises ValueError.  second_view=True (fsgm_view2::sgm) appends disp2, minC_v2 uint32 and conf uint8: the
+    second view's disparity from the same aggregated volume and the left-right check, as fsgm_amd.sgm_batch(second_view=True) with
+    its direction, d_min and max_diff."""
     return _sgm_call(Cvol, None, P1, P2, layout, paths, cost_bound, agg_mode, adaptive_p2, guide, subpixel, return_sum, check, return_status,
-                     runner_up, arith)
+                     runner_up, arith, (int(direction), int(d_min), int(max_diff)) if second_view else None)
 
 
 def sgm_float(Cvol, scale, offset=0.0, P1=7, P2=100, *, layout="dhw", paths=4, cost_bound=255, agg_mode=0, adaptive_p2=0, guide=None,
@@ -1009,8 +1097,8 @@ def sgm_float(Cvol, scale, offset=0.0, P1=7, P2=100, *, layout="dhw", paths=4, c
 
 
 def _sgm_call(Cvol, quant, P1, P2, layout, paths, cost_bound, agg_mode, adaptive_p2, guide, subpixel, return_sum, check, return_status,
-              runner_up, arith):
-    """sgm (quant None: a uint8 volume) and sgm_float (quant = (scale, offset): a float volume, through fsgm_float::sgm)"""
+              runner_up, arith, view2=None):
+    """sgm (quant None: a uint8 volume; view2 = (direction, d_min, max_diff): through fsgm_view2::sgm) and sgm_float (quant = (scale, offset): a float volume, through fsgm_float::sgm)"""
     exact = _arith_exact(arith)
     if exact and runner_up:
         raise ValueError("arith='exact' has no runner-up cost: runner_up=True needs arith='mod256'")
@@ -1032,7 +1120,10 @@ def _sgm_call(Cvol, quant, P1, P2, layout, paths, cost_bound, agg_mode, adaptive
         guide = torch.empty((0,), dtype=torch.uint8, device=Cvol.device)
     args = (Cvol, guide, int(P1), int(P2), int(paths), code, int(cost_bound), int(agg_mode), int(adaptive_p2), int(subpixel),
             int(bool(return_sum)))
-    if quant is not None:
+    extra = ()
+    if view2 is not None:
+        bestD, minC, minC2, S, *extra, status = torch.ops.fsgm_view2.sgm(*args, bool(runner_up), exact, *view2)
+    elif quant is not None:
         bestD, minC, minC2, S, status = torch.ops.fsgm_float.sgm(*args[:2], *quant, *args[2:], bool(runner_up), exact)
     elif runner_up:
         bestD, minC, minC2, S, status = torch.ops.fsgm.sgm_ru(*args)
@@ -1040,7 +1131,7 @@ def _sgm_call(Cvol, quant, P1, P2, layout, paths, cost_bound, agg_mode, adaptive
         bestD, minC, S, status = torch.ops.fsgm.sgm_exact(*args)
     else:
         bestD, minC, S, status = torch.ops.fsgm.sgm(*args)
-    outs = (bestD, minC) + ((minC2,) if runner_up else ()) + ((S,) if return_sum else ())
+    outs = (bestD, minC) + ((minC2,) if runner_up else ()) + ((S,) if return_sum else ()) + tuple(extra)
     return _finish(outs, status, batched, check, return_status, "a cost above cost_bound, or an aggregation hand-off that gave up")
 
 
@@ -1189,7 +1280,7 @@ def _stereo_inputs(left, right, dMax, paths, subpixel, direction, fb_check, adap
 
 
 def stereo_sgm(left, right, dMax, P1=6, P2=64, *, paths=4, subpixel=1, direction=-1, fb_check=0, check=False, return_status=False,
-               adaptive_p2=0, d_min=None, runner_up=False):
+               adaptive_p2=0, d_min=None, runner_up=False, second_view=False, max_diff=256):
     """disp, minC = stereo_sgm(left, right, dMax) as fsgm_amd.stereo_sgm, on torch tensors on the GPU: left, right (H, W) uint8
     or a batch (N, H, W); disp (disparity * 256) and minC uint32 of the same shape, plus conf uint8 / disp2 uint32 with
     fb_check=1.  The outputs stay in HBM; the work is queued on the current stream.  adaptive_p2=1: edge-aware P2 on `left`.
@@ -1197,9 +1288,18 @@ def stereo_sgm(left, right, dMax, P1=6, P2=64, *, paths=4, subpixel=1, direction
     disparities * 256 (disp2 INT32_MIN where invalid); the dtype follows the argument, not its value: None (fsgm::stereo_sgm)
     keeps the uint32 outputs, 0 gives the same values as int32.  runner_up=True (fsgm::stereo_sgm_ru) appends minC2 uint32, the
     runner-up cost min { S[d] : |d - best| >= 2 } (0xFFFFFFFF where no such d exists), to the outputs; the call then runs the
-    line kernels at every batch size."""
+    line kernels at every batch size.  second_view=True (fsgm_view2::stereo_sgm; not with fb_check) appends disp2 int32, minC_v2
+    uint32 and conf uint8 as fsgm_amd.stereo_sgm(second_view=True); disp is then int32 as with d_min (None: 0)."""
     d_min = _d_min(d_min)
     left, right, batched = _stereo_inputs(left, right, dMax, paths, subpixel, direction, fb_check, adaptive_p2)
+    if second_view:
+        if fb_check:
+            raise ValueError("second_view=True and fb_check=1 are two different checks: ask for one")
+        disp, minC, minC2, disp2, minC_v2, conf, status = torch.ops.fsgm_view2.stereo_sgm(
+            left, right, int(dMax), d_min or 0, int(P1), int(P2), int(paths), int(subpixel), int(direction), int(adaptive_p2), bool(runner_up),
+            int(max_diff))
+        outs = (disp, minC) + ((minC2,) if runner_up else ()) + (disp2, minC_v2, conf)
+        return _finish(outs, status, batched, check, return_status)
     rest = (int(P1), int(P2), int(paths), int(subpixel), int(direction), int(bool(fb_check)), int(adaptive_p2))
     if runner_up:
         disp, minC, minC2, conf, disp2, status = torch.ops.fsgm.stereo_sgm_ru(left, right, int(dMax), d_min or 0, *rest)
@@ -1213,6 +1313,24 @@ def stereo_sgm(left, right, dMax, P1=6, P2=64, *, paths=4, subpixel=1, direction
         disp, minC, conf, disp2, status = torch.ops.fsgm.stereo_sgm_range(left, right, int(dMax), d_min, *rest)
     outs = ((disp, minC, conf, disp2) if fb_check else (disp, minC)) + ((minC2,) if runner_up else ())
     return _finish(outs, status, batched, check, return_status)
+
+
+def view2_check(disp, disp2, *, direction=-1, max_diff=256):
+    """conf = fsgm_amd.view2_check(disp, disp2) on torch tensors on the GPU (fsgm_view2::check): int32 true-disparity maps * 256,
+    (H, W) or (N, H, W), disp2's marker INT32_MIN; conf uint8 of the same shape, queued on the current stream."""
+    _tensors({"disp": (disp, torch.int32), "disp2": (disp2, torch.int32)})
+    if disp.dim() not in (2, 3):
+        raise TypeError(f"disp must be (H, W) or (N, H, W) (got {tuple(disp.shape)})")
+    _shape("disp2", disp2, disp.shape)
+    if int(direction) not in (-1, 1):
+        raise ValueError(f"direction must be -1 or +1 (got {direction!r})")
+    if int(max_diff) < 0:
+        raise ValueError(f"max_diff must be >= 0 (got {max_diff!r})")
+    batched = disp.dim() == 3
+    if not batched:
+        disp, disp2 = disp.unsqueeze(0), disp2.unsqueeze(0)
+    conf, _ = torch.ops.fsgm_view2.check(disp, disp2, int(direction), int(max_diff))
+    return conf if batched else conf[0]
 
 
 def stereo_sgm_pp(left, right, dMax, P1=6, P2=64, *, paths=4, subpixel=1, direction=-1, adaptive_p2=0, d_min=0, in_fill=1, check=False,

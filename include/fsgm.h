@@ -1432,6 +1432,94 @@ fsgm_status fsgm_sgm2d_float_batch_host(int32_t n_frames, const void* C, const f
                                         const double* preMv, int32_t mvWidth, int32_t mvHeight, const uint8_t* guide, uint32_t* bestD,
                                         uint32_t* minC, uint32_t* minC2, double* mvSub, double* flow, uint32_t* S, int32_t exact);
 
+/* ------------------------------------------------------------------------------------------
+ * Second view: the second view's disparity taken from the SAME aggregated volume, and the left-right check against it
+ * (Hirschmueller's D_m, OpenCV's disp12MaxDiff).  No second aggregation runs: a kernel of its own reads the path volumes the
+ * line kernels' WTA has just read.
+ *
+ * THE RULE.  S[y][x][i], i in [0, dMax), is the u32 sum of the path volumes exactly as fsgm_epi_plan_download_sum defines it
+ * for the plan that ran (wrapped or not; ndirs * C + the sum of the y_r for an exact plan).  s = direction is -1 or +1,
+ * delta(i) = d_min + i, and candidate i of first-view pixel (x, y) is second-view pixel (x + s * delta(i), y) -- the
+ * convention of fsgm_stereo_sgm_*.  For second-view pixel (x2, y):
+ *   candidates  I(x2) = { i : 0 <= x2 - s * delta(i) < width }.  Only a candidate whose unclamped target is x2 counts: the
+ *               clamped border samples of the stereo cost stage do not;
+ *   winner      i* = the first minimum, in ascending i over I(x2), of S[y][x2 - s * delta(i)][i]; minC_v2 is that value;
+ *   empty I(x2) disp2 = the invalid marker, minC_v2 = 0xFFFFFFFF;
+ *   sub-pixel   when the call's subpixel is 1 and both i* - 1 and i* + 1 are in I(x2): c_1 and c1 are S at those two diagonal
+ *               neighbours, c = minC_v2, and with f64 operations in this order
+ *                 sub = i* + ((c1 - c_1) / (c - c_1)) / 2   if c1 < c_1,   sub = i* + ((c1 - c_1) / (c - c1)) / 2   otherwise
+ *               (the first view's parabola); disp2 = (u32) trunc(sub * 256).  Otherwise disp2 = i* * 256.  Since i* is a FIRST
+ *               minimum, c_1 > c and c1 >= c: the divisor is c - c_1 < 0 in the first branch and c - c1 <= c - c_1 < 0 in the
+ *               second -- never zero.  The first view's `best > 1` quirk and its read of the next pixel's d = 0 are not mirrored.
+ * Formats: the sgm(C) forms and the plan return disp2 u32 in index units like bestD, marker FSGM_NO_VIEW2; the stereo forms
+ * return int32 true disparities * 256 (256 * d_min + the above) like the _range forms, marker INT32_MIN.
+ * THE CHECK (integers only).  d1 = the first view's true disparity * 256 (sgm(C): bestD + 256 * d_min; in a call with subpixel = 0
+ * the first view returns the whole index, which the one-shot forms scale by 256 first), d2 likewise from disp2:
+ *   x2 = x + s * ((d1 + 128) >> 8)   (arithmetic shift, no clamp)
+ *   conf[y][x] = 1 iff 0 <= x2 < width, disp2[y][x2] is valid and |d1 - d2| <= max_diff (int64; max_diff >= 0 in 1/256 units,
+ *   default 256 = one disparity), else 0.
+ * UNPINNED BY CONSTRUCTION: the reference has nothing like it (its fb_check splats the first view's own disparities).  The rule
+ * is restated in numpy (tests/view2_restatement.py); the yardstick is equality with the restatement on the S the same call
+ * returns.
+ *
+ * Plans.  fsgm_epi_plan_set_view2(plan, 1, direction): every FSGM_STAGE_WTA run also writes the second view, read by
+ * fsgm_epi_plan_download_view2 (frame's disp2 and minC_v2, u32 [H][W], either may be NULL; index units; FSGM_ERR_INVALID while
+ * the switch is off).  Such a plan aggregates with the line kernels at every batch size (the fused pipelines keep no volumes);
+ * fsgm_epi_plan_set_agg_mode(2..6) on it, and the switch on a plan forced to such a mode, are FSGM_ERR_UNSUPPORTED.  It is
+ * FSGM_ERR_UNSUPPORTED on a linear plan (per-pixel direction maps) and on a vz plan with vz_to_disp (the vz sampling): candidates
+ * there share no line.  A rectified plan takes its own direction only (FSGM_ERR_INVALID otherwise) and its d_min
+ * (fsgm_epi_plan_set_d_min); a vz plan without vz_to_disp serves uploaded cost volumes (d_min 0), and running its own cost stage
+ * with the switch on is FSGM_ERR_INVALID.  It composes with adaptive_p2, the runner-up switch and the exact switch.
+ * ------------------------------------------------------------------------------------------ */
+#define FSGM_NO_VIEW2 0xFFFFFFFFu
+fsgm_status fsgm_epi_plan_set_view2(fsgm_epi_plan* plan, int32_t on, int32_t direction);
+fsgm_status fsgm_epi_plan_download_view2(fsgm_epi_plan* plan, int32_t frame, uint32_t* disp2, uint32_t* minC_v2);
+/* Bytes of LDS a workgroup of the second view's kernel asks for at this dMax (1..1024; 0 above 256, the generic kernel), and the
+ * second-view pixels a workgroup of the tiled kernel owns (0: the generic kernel, or a dMax out of range).  No device needed. */
+fsgm_status fsgm_view2_launch_lds(int32_t dMax, uint64_t* bytes);
+int32_t fsgm_view2_tile(int32_t dMax);
+
+typedef struct {
+    int32_t direction;         /* -1 or +1 */
+    int32_t d_min;             /* |d_min| <= FSGM_D_MIN_LIMIT: candidate i stands for disparity d_min + i */
+    int32_t max_diff;          /* >= 0, 1/256 units */
+    int32_t reserved[5];       /* must be zero */
+} fsgm_view2_params;
+fsgm_view2_params fsgm_view2_params_default(void);   /* -1, 0, 256 */
+/* sgm(C) with the second view: the arguments of fsgm_sgm_float_batch_host / _dptr without the format and with v2 (NULL: the
+ * defaults) behind prm.  minC2 (not wanted) and S may be NULL, exact is a switch, exact with minC2 is FSGM_ERR_UNSUPPORTED.
+ * disp2 u32 [n][H][W] is required; minC_v2 u32 and conf u8 [n][H][W] may be NULL.  agg_mode 2..6 is FSGM_ERR_UNSUPPORTED.  bestD,
+ * minC, minC2 and S are those of the _ru, plain or _exact call, bit for bit.  The cached plan is never the plan of a call
+ * without the second view.  Everything is refused before a device is touched; the _dptr form follows the device-pointer
+ * contract (check table, caller's stream, status word, a captured stream refused) and writes disp2, minC_v2, conf where they lie. */
+fsgm_status fsgm_sgm_view2_batch_host(int32_t n_frames, const uint8_t* C, int32_t width, int32_t height, int32_t dMax, int32_t P1,
+                                      int32_t P2, const fsgm_sgm_params* prm, const fsgm_view2_params* v2, const uint8_t* guide,
+                                      uint32_t* bestD, uint32_t* minC, uint32_t* minC2, uint32_t* S, int32_t exact, uint32_t* disp2,
+                                      uint32_t* minC_v2, uint8_t* conf);
+fsgm_status fsgm_sgm_view2_dptr(int32_t n_frames, const uint8_t* C, int32_t width, int32_t height, int32_t dMax, int32_t P1, int32_t P2,
+                                const fsgm_sgm_params* prm, const fsgm_view2_params* v2, const uint8_t* guide, uint32_t* bestD,
+                                uint32_t* minC, uint32_t* minC2, uint32_t* S, int32_t exact, uint32_t* disp2, uint32_t* minC_v2,
+                                uint8_t* conf, void* stream, int32_t* status);
+/* Rectified stereo with the second view: the arguments of fsgm_stereo_sgm_host_ru with minC2 nullable, plus max_diff; the
+ * direction is prm's.  disp and disp2 (required) are int32 true disparities * 256, disp2's marker INT32_MIN; minC_v2 and conf may
+ * be NULL.  prm->fb_check = 1 is FSGM_ERR_INVALID (that is the other door); there is no dMax <= 511 limit.  With prm->subpixel = 0
+ * disp stays what the _range forms return, 256 * d_min + the whole index, while disp2 is 256 * (d_min + index): conf is computed on
+ * d1 = 256 * (d_min + index), and fsgm_view2_check_* applies to such a pair only after the caller has scaled disp the same way. */
+fsgm_status fsgm_stereo_sgm_view2_host(int32_t n_frames, const uint8_t* I1, const uint8_t* I2, int32_t width, int32_t height,
+                                       int32_t dMax, int32_t P1, int32_t P2, const fsgm_stereo_params* prm, const fsgm_epi_options* opt,
+                                       int32_t d_min, int32_t max_diff, int32_t* disp, uint32_t* minC, uint32_t* minC2, int32_t* disp2,
+                                       uint32_t* minC_v2, uint8_t* conf);
+fsgm_status fsgm_stereo_sgm_view2_dptr(int32_t n_frames, const uint8_t* I1, const uint8_t* I2, int32_t width, int32_t height,
+                                       int32_t dMax, int32_t P1, int32_t P2, const fsgm_stereo_params* prm, const fsgm_epi_options* opt,
+                                       int32_t d_min, int32_t max_diff, int32_t* disp, uint32_t* minC, uint32_t* minC2, int32_t* disp2,
+                                       uint32_t* minC_v2, uint8_t* conf, void* stream, int32_t* status);
+/* The check alone on int32 true-disparity maps [n][H][W] (disp2's marker INT32_MIN) -> conf u8 [n][H][W]; the status word of
+ * the _dptr form is always 0. */
+fsgm_status fsgm_view2_check_host(int32_t n_frames, const int32_t* disp, const int32_t* disp2, int32_t width, int32_t height,
+                                  int32_t direction, int32_t max_diff, uint8_t* conf, int32_t device);
+fsgm_status fsgm_view2_check_dptr(int32_t n_frames, const int32_t* disp, const int32_t* disp2, int32_t width, int32_t height,
+                                  int32_t direction, int32_t max_diff, uint8_t* conf, int32_t device, void* stream, int32_t* status);
+
 #ifdef __cplusplus
 }
 #endif
