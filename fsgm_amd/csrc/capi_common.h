@@ -121,6 +121,19 @@ fsgm_status time_enqueues(hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, in
     return FSGM_OK;
 }
 
+// cmax[f] = the largest byte of frame f of n host volumes of `voxels` bytes each (the sgm(C) / sgm2d(C) host forms' u8 volumes);
+// a frame that holds one above the call's declared cost_bound is refused
+inline fsgm_status frame_cost_maxima(const char* who, const uint8_t* C, int n, size_t voxels, int cost_bound, int* cmax) {
+    for (int f = 0; f < n; f++) {
+        const uint8_t* v = C + (size_t)f * voxels;
+        int m = 0;
+        for (size_t i = 0; i < voxels; i++) m = v[i] > m ? v[i] : m;
+        FSGM_REQUIRE(m <= cost_bound, "%s: frame %d holds a cost of %d, above cost_bound %d", who, f, m, cost_bound);
+        cmax[f] = m;
+    }
+    return FSGM_OK;
+}
+
 // Scope guard for host-pointer entry points: work queued on `st` may still read the caller's input
 // buffers or write its output buffers (async copies), so every exit that is not the normal one
 // (which has synchronised already and calls dismiss()) drains the stream before the caller gets

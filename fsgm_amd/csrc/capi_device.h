@@ -55,6 +55,15 @@ fsgm_status device_call(DeviceJoin& j, hipStream_t caller, hipStream_t plan, Wor
 // pointer may be NULL; nothing is launched when all three are)
 void launch_device_status(hipStream_t st, uint32_t* hip_flag, uint32_t* invalid_flag, int32_t* status);
 
+// A plan's ingest flag -- the word an ingest kernel raises for a value outside the declared bound, launch_device_status's
+// invalid_flag -- created cleared on `st` at its first use
+inline fsgm_status ensure_ingest_flag(uint32_t** flag, hipStream_t st) {
+    if (*flag) return FSGM_OK;
+    FSGM_HIP(hipMalloc((void**)flag, sizeof(uint32_t)));
+    FSGM_HIP(hipMemsetAsync(*flag, 0, sizeof(uint32_t), st));
+    return FSGM_OK;
+}
+
 // Swaps a plan's buffer pointer for the caller's for the length of one enqueue and puts it back on every exit.
 template <class T>
 struct Bind {

@@ -1,14 +1,35 @@
 // capi_sgm.hip -- C ABI of sgm(C, P1, P2) on batches of caller-supplied cost volumes, in host memory or in HBM (include/fsgm.h:
-// fsgm_sgm_batch_host, fsgm_sgm_device, their _ru and _exact forms, the float forms).  Everything that can be refused without a device is refused here; the cached plans
-// and their pipelines live in capi_epi.hip (capi_sgm.h).
-#include "capi_sgm.h"
-#include "capi_device.h"
+// fsgm_sgm_batch_host, fsgm_sgm_device, their _ru and _exact forms, the float and the view-2 forms, fsgm_sgm_host and the plan-level
+// ingest entries).  Everything that can be refused without a device is refused first, into a checked call (SgmCall); behind that both
+// forms run on a cached plan of capi_epi.hip (epi_plan.h).
+#include "epi_plan.h"
+#include "cost_float_ingest.h"
 #include "epi_view2.h"
+#include "sgm_ingest.h"
 #include <algorithm>
 #include <string.h>
 #include <vector>
 
 using namespace fsgm;
+
+namespace {
+// a checked call
+struct SgmCall {
+    int n, W, H, D, P1, P2;
+    fsgm_sgm_params prm;                 // checked, never the caller's NULL
+    const uint8_t *C, *guide;            // guide: non-NULL exactly when prm.adaptive_p2
+    uint32_t *bestD, *minC, *S;          // S may be NULL
+    uint32_t* minC2;                     // the _ru forms' runner-up cost (never NULL there), NULL in the plain forms
+    int exact;                           // the _exact forms: exact path arithmetic, P1 and P2 checked to lie in 0..255 (never with minC2)
+    int captured = 0;                    // fsgm_sgm_device_exact alone: the caller's stream is being captured into a graph
+    CostFormat fmt;                      // the float forms: C holds elements of fmt.dtype (-1 in the u8 forms), quantised by the ingest
+    // the view-2 forms (include/fsgm.h, "Second view"): view2 = the direction, -1 or +1 (0 in every other form); disp2 is never NULL
+    // then, minC_v2 and conf may be
+    int view2 = 0, d_min = 0, max_diff = 0;
+    uint32_t *disp2 = nullptr, *minC_v2 = nullptr;
+    uint8_t* conf = nullptr;
+};
+}  // namespace
 
 // the checks both forms share: prm (NULL: the defaults) into c->prm, the scalars and the pointers every call needs
 static fsgm_status sgm_args(const char* who, int32_t n, const uint8_t* C, int32_t W, int32_t H, int32_t D, int32_t P1, int32_t P2,
@@ -64,23 +85,132 @@ fsgm_sgm_params fsgm_sgm_params_default(void) {
 
 }  // extern "C"
 
+static thread_local const char* g_sgm_kernel = "";
+
+// the cached plan of a checked call: its batch, mode, adaptive, runner-up and exact switches are part of the key
+static fsgm_status sgm_plan(std::unique_lock<std::mutex>& lk, fsgm_epi_plan** p, const SgmCall& c) {
+    EpiPlanKey k;
+    k.W = c.W; k.H = c.H; k.D = c.D; k.batch = c.n;
+    k.prm.paths = c.prm.paths; k.prm.subpixel = c.prm.subpixel; k.prm.device = c.prm.device; k.prm.vz_to_disp = 0; k.prm.fb_check = 0;
+    k.adaptive = c.prm.adaptive_p2; k.agg_mode = c.prm.agg_mode; k.runner_up = c.minC2 != nullptr; k.exact = c.exact; k.view2_dir = c.view2;
+    return cached_plan(lk, p, k, c.captured != 0);
+}
+
+// the check of the sgm(C) view-2 forms on the plan's own outputs: index units, both shifted by the call's d_min
+static void enqueue_sgm_view2_check(fsgm_epi_plan* p, const SgmCall& c, const uint32_t* bestD, const uint32_t* disp2, uint8_t* conf) {
+    View2CheckArgs k{};
+    k.disp = bestD; k.disp2 = disp2; k.conf = conf; k.W = p->W; k.H = p->H; k.dir = c.view2; k.max_diff = c.max_diff;
+    k.add1 = k.add2 = 256 * c.d_min; k.marker2 = 0xFFFFFFFFu;
+    k.shift1 = c.prm.subpixel ? 0 : 8;                           // (without sub-pixel bestD is the whole index, disp2 always index * 256)
+    launch_view2_check(p->stream, k, c.n);
+}
+
+// host pointers; cmax: the largest byte of each frame's volume (none above prm.cost_bound), of a float volume prm.cost_bound
+static fsgm_status sgm_run_host(const SgmCall& c, const int* cmax) {
+    std::unique_lock<std::mutex> lk;
+    fsgm_epi_plan* p = nullptr;
+    fsgm_status st = sgm_plan(lk, &p, c);
+    if (st != FSGM_OK) return st;
+    const size_t NP = p->NP, nv = (size_t)c.n * p->N;
+    for (int f = 0; f < c.n; f++) p->cmax[f] = cmax[f];
+    if ((st = fsgm_epi_plan_set_penalties(p, c.P1, c.P2, p->vMax)) != FSGM_OK) return st;    // (selects the kernels for cmax)
+    if (c.guide)                                                 // the aggregation reads I1 only: the guide stands for both images
+        for (int f = 0; f < c.n; f++)
+            if ((st = fsgm_epi_plan_upload_images(p, f, c.guide + f * NP, c.guide + f * NP)) != FSGM_OK) return st;
+    if ((st = epi_prepare(p, FSGM_STAGE_AGGREGATE | FSGM_STAGE_WTA)) != FSGM_OK) return st;
+    const bool dhw = c.prm.layout == FSGM_COST_LAYOUT_DHW;       // staged as it came, transposed on the device
+    if (dhw && c.fmt.dtype < 0 && !p->dIngest) FSGM_HIP(hipMalloc((void**)&p->dIngest, nv));
+    if (c.fmt.dtype >= 0 && (st = ensure_ingest_flag(&p->dIngestFlag, p->stream)) != FSGM_OK) return st;
+    if (c.view2) p->d_min = c.d_min;                             // (read by the second view's kernel only: the plan has no cost stage to shift)
+    if (c.conf && (st = epi_ensure_view2_conf(p)) != FSGM_OK) return st;
+    StreamGuard guard(p->stream);                                // every early exit drains the stream: the copies use caller memory
+    if (c.fmt.dtype >= 0) {
+        // a float volume: staged frame by frame, quantised by the kernel the device form runs; the flag is read before any output is written
+        const fsgm_status fs = stage_float_volumes(p->stream, c.C, c.fmt, c.n, p->N, p->dIngestFlag, "fsgm_sgm_float_batch_host",
+            [&](const void* d, int f) { launch_sgm_ingest_float(p->stream, d, c.fmt, p->dC + (size_t)f * p->N, 1, c.W, c.H, c.D, c.prm.layout, c.prm.cost_bound, p->dIngestFlag); });
+        if (fs != FSGM_OK) return fs;
+    } else {
+        FSGM_HIP(hipMemcpyAsync(dhw ? p->dIngest : p->dC, c.C, nv, hipMemcpyHostToDevice, p->stream));
+        if (dhw) launch_sgm_ingest(p->stream, p->dIngest, p->dC, c.n, c.W, c.H, c.D, FSGM_COST_LAYOUT_DHW, 255, nullptr);
+    }
+    if ((st = epi_enqueue(p, FSGM_STAGE_AGGREGATE | FSGM_STAGE_WTA)) != FSGM_OK) return st;
+    g_sgm_kernel = kPipelineName[p->pipe];
+    FSGM_HIP(hipMemcpyAsync(c.bestD, p->dBestD, (size_t)c.n * NP * 4, hipMemcpyDeviceToHost, p->stream));
+    FSGM_HIP(hipMemcpyAsync(c.minC, p->dMinC, (size_t)c.n * NP * 4, hipMemcpyDeviceToHost, p->stream));
+    if (c.minC2) FSGM_HIP(hipMemcpyAsync(c.minC2, p->dMinC2, (size_t)c.n * NP * 4, hipMemcpyDeviceToHost, p->stream));
+    if (c.view2) {
+        FSGM_HIP(hipMemcpyAsync(c.disp2, p->dDisp2v, (size_t)c.n * NP * 4, hipMemcpyDeviceToHost, p->stream));
+        if (c.minC_v2) FSGM_HIP(hipMemcpyAsync(c.minC_v2, p->dMinCv2, (size_t)c.n * NP * 4, hipMemcpyDeviceToHost, p->stream));
+        if (c.conf) {
+            enqueue_sgm_view2_check(p, c, p->dBestD, p->dDisp2v, p->dConfV2);
+            FSGM_HIP(hipGetLastError());
+            FSGM_HIP(hipMemcpyAsync(c.conf, p->dConfV2, (size_t)c.n * NP, hipMemcpyDeviceToHost, p->stream));
+        }
+    }
+    FSGM_HIP(hipStreamSynchronize(p->stream));
+    guard.dismiss();
+    if ((st = epi_check_handoff(p)) != FSGM_OK) return st;
+    for (int f = 0; c.S && f < c.n; f++)
+        if ((st = fsgm_epi_plan_download_sum(p, f, c.S + (size_t)f * p->N)) != FSGM_OK) return st;
+    return FSGM_OK;
+}
+
+// device pointers, checked (device_check_args) by the caller; cs: the caller's stream
+static fsgm_status sgm_run_device(const SgmCall& c, hipStream_t cs, int32_t* status) {
+    std::unique_lock<std::mutex> lk;
+    fsgm_epi_plan* p = nullptr;
+    fsgm_status st = sgm_plan(lk, &p, c);
+    if (st != FSGM_OK) return st;
+    if (c.captured) {
+        // Under a capture nothing may be allocated or waited for: everything the call below would create must exist (an earlier
+        // call of the host form, or one without S or without a guide, leaves some of it out).  Refused before anything is queued.
+        const bool warm = p->dL && p->dIngestFlag && p->join.in && p->join.out && (!c.S || p->dS) && (!c.guide || (p->dI1 && p->dI2));
+        if (!warm)
+            return fail(FSGM_ERR_UNSUPPORTED, "fsgm_sgm_device_exact: the stream is being captured into a graph and the cached plan lacks buffers "
+                                              "this call needs: run the same call once outside the capture");
+        p->pinned = true;                                        // the graph names the plan's buffers, stream and events from here on
+    }
+    // What a warm call must not do happens here, before the join with the caller's stream.  The device cannot be asked for the
+    // true maximum without a wait: the declared bound selects the kernels, the ingest kernel saturates at it.
+    p->cmax.assign(c.n, c.prm.cost_bound);
+    if ((st = fsgm_epi_plan_set_penalties(p, c.P1, c.P2, p->vMax)) != FSGM_OK) return st;
+    if (c.guide) {
+        if ((st = epi_ensure_image_buffers(p)) != FSGM_OK) return st;
+        p->have_img.assign(c.n, 1);                              // the guide goes into dI1 below, ahead of the kernels
+    }
+    if ((st = epi_prepare(p, FSGM_STAGE_AGGREGATE | FSGM_STAGE_WTA)) != FSGM_OK) return st;
+    if ((st = ensure_ingest_flag(&p->dIngestFlag, p->stream)) != FSGM_OK) return st;
+    if (c.S && (st = epi_ensure_tap_buffers(p)) != FSGM_OK) return st;
+    if (c.view2) p->d_min = c.d_min;
+    return device_call(p->join, cs, p->stream, [&]() -> fsgm_status {
+        if (c.fmt.dtype >= 0) launch_sgm_ingest_float(p->stream, c.C, c.fmt, p->dC, c.n, c.W, c.H, c.D, c.prm.layout, c.prm.cost_bound, p->dIngestFlag);
+        else launch_sgm_ingest(p->stream, c.C, p->dC, c.n, c.W, c.H, c.D, c.prm.layout, c.prm.cost_bound, p->dIngestFlag);
+        if (c.guide) FSGM_HIP(hipMemcpyAsync(p->dI1, c.guide, (size_t)c.n * p->NP, hipMemcpyDeviceToDevice, p->stream));
+        Bind<uint32_t> bd(p->dBestD, c.bestD), mc(p->dMinC, c.minC), m2(p->dMinC2, c.minC2);
+        Bind<uint32_t> d2(p->dDisp2v, c.disp2), mv(p->dMinCv2, c.minC_v2);   // (the view-2 forms: written where they lie)
+        const fsgm_status es = epi_enqueue(p, FSGM_STAGE_AGGREGATE | FSGM_STAGE_WTA);
+        if (es != FSGM_OK) return es;
+        g_sgm_kernel = kPipelineName[p->pipe];
+        if (c.view2 && c.conf) enqueue_sgm_view2_check(p, c, c.bestD, c.disp2, c.conf);
+        for (int f = 0; c.S && f < c.n; f++) {                   // S never exists for a batch: frame by frame through the tap's buffer
+            epi_tap_sum(p, f);
+            FSGM_HIP(hipMemcpyAsync(c.S + (size_t)f * p->N, p->dS, p->N * 4, hipMemcpyDeviceToDevice, p->stream));
+        }
+        launch_device_status(p->stream, p->dBandErr, p->dIngestFlag, status);
+        return FSGM_OK;
+    });
+}
+
 // every host form; ru: the _ru form, exact: the _exact form
 static fsgm_status sgm_host(const char* who, int32_t n, const uint8_t* C, int32_t W, int32_t H, int32_t D, int32_t P1, int32_t P2,
                             const fsgm_sgm_params* prm, const uint8_t* guide, uint32_t* bestD, uint32_t* minC, uint32_t* minC2, bool ru,
                             uint32_t* S, bool exact = false) {
     SgmCall c;
-    const fsgm_status st = sgm_args(who, n, C, W, H, D, P1, P2, prm, guide, bestD, minC, S, minC2, ru, exact, &c);
+    fsgm_status st = sgm_args(who, n, C, W, H, D, P1, P2, prm, guide, bestD, minC, S, minC2, ru, exact, &c);
     if (st != FSGM_OK) return st;
     // the true maximum of every frame, as fsgm_epi_plan_upload_cost takes it (either layout holds the same bytes)
-    const size_t N = (size_t)W * H * D;
     std::vector<int> cmax(n, 0);
-    for (int f = 0; f < n; f++) {
-        const uint8_t* v = C + (size_t)f * N;
-        int m = 0;
-        for (size_t i = 0; i < N; i++) m = v[i] > m ? v[i] : m;
-        FSGM_REQUIRE(m <= c.prm.cost_bound, "%s: frame %d holds a cost of %d, above cost_bound %d", who, f, m, c.prm.cost_bound);
-        cmax[f] = m;
-    }
+    if ((st = frame_cost_maxima(who, C, n, (size_t)W * H * D, c.prm.cost_bound, cmax.data())) != FSGM_OK) return st;
     return sgm_run_host(c, cmax.data());
 }
 
@@ -224,17 +354,10 @@ fsgm_status fsgm_sgm_view2_batch_host(int32_t n, const uint8_t* C, int32_t W, in
                                       uint8_t* conf) {
     const char* who = "fsgm_sgm_view2_batch_host";
     SgmCall c;
-    const fsgm_status st = sgm_view2_args(who, n, C, W, H, D, P1, P2, prm, v2, guide, bestD, minC, minC2, S, exact, disp2, minC_v2, conf, &c);
+    fsgm_status st = sgm_view2_args(who, n, C, W, H, D, P1, P2, prm, v2, guide, bestD, minC, minC2, S, exact, disp2, minC_v2, conf, &c);
     if (st != FSGM_OK) return st;
-    const size_t N = (size_t)W * H * D;                          // the true maximum of every frame, as fsgm_sgm_batch_host takes it
-    std::vector<int> cmax(n, 0);
-    for (int f = 0; f < n; f++) {
-        const uint8_t* v = C + (size_t)f * N;
-        int m = 0;
-        for (size_t i = 0; i < N; i++) m = v[i] > m ? v[i] : m;
-        FSGM_REQUIRE(m <= c.prm.cost_bound, "%s: frame %d holds a cost of %d, above cost_bound %d", who, f, m, c.prm.cost_bound);
-        cmax[f] = m;
-    }
+    std::vector<int> cmax(n, 0);                                 // the true maximum of every frame, as fsgm_sgm_batch_host takes it
+    if ((st = frame_cost_maxima(who, C, n, (size_t)W * H * D, c.prm.cost_bound, cmax.data())) != FSGM_OK) return st;
     return sgm_run_host(c, cmax.data());
 }
 
@@ -337,6 +460,77 @@ fsgm_status fsgm_sgm_device_exact(int32_t n, const uint8_t* C, int32_t W, int32_
                                   const fsgm_sgm_params* prm, const uint8_t* guide, uint32_t* bestD, uint32_t* minC, uint32_t* S,
                                   void* stream, int32_t* status) {
     return sgm_device("fsgm_sgm_device_exact", n, C, W, H, D, P1, P2, prm, guide, bestD, minC, nullptr, false, S, stream, status, true);
+}
+
+// sgm(C, P1, P2): sgm.m's call shape on the MEX's aggregation + WTA (MEX semantics: include/fsgm.h)
+fsgm_status fsgm_sgm_host(const uint8_t* C, int32_t W, int32_t H, int32_t D, int32_t P1, int32_t P2, int32_t paths,
+                          uint32_t* bestD, uint32_t* minC, uint32_t* S, int32_t device) {
+    FSGM_REQUIRE(C && bestD && minC, "fsgm_sgm: null argument");
+    fsgm_epi_params pr = fsgm_epi_params_default();
+    pr.paths = paths; pr.device = device; pr.vz_to_disp = 0; pr.subpixel = 1;
+    std::unique_lock<std::mutex> lk;
+    fsgm_epi_plan* p = nullptr;
+    EpiPlanKey key;
+    key.W = W; key.H = H; key.D = D; key.batch = 1; key.prm = pr;
+    fsgm_status st = cached_plan(lk, &p, key);
+    if (st != FSGM_OK) return st;
+    if ((st = fsgm_epi_plan_set_penalties(p, P1, P2, p->vMax)) != FSGM_OK) return st;
+    if ((st = fsgm_epi_plan_upload_cost(p, 0, C)) != FSGM_OK) return st;
+    if ((st = fsgm_epi_plan_run(p, FSGM_STAGE_AGGREGATE | FSGM_STAGE_WTA)) != FSGM_OK) return st;
+    if ((st = fsgm_epi_plan_download(p, 0, bestD, minC)) != FSGM_OK) return st;
+    if (S && (st = fsgm_epi_plan_download_sum(p, 0, S)) != FSGM_OK) return st;
+    return FSGM_OK;
+}
+
+const char* fsgm_sgm_last_kernel(void) { return g_sgm_kernel; }
+
+// the scalar checks of both plan-level ingest entries, behind their null and format checks
+static fsgm_status epi_ingest_args(const char* who, const fsgm_epi_plan* p, int32_t n, int32_t layout, int32_t cost_bound) {
+    FSGM_REQUIRE(n == p->batch, "%s: n_frames %d differs from the plan's batch %d", who, n, p->batch);
+    FSGM_REQUIRE(layout == FSGM_COST_LAYOUT_HWD || layout == FSGM_COST_LAYOUT_DHW,
+                 "%s: layout must be FSGM_COST_LAYOUT_HWD (0) or FSGM_COST_LAYOUT_DHW (1), got %d", who, layout);
+    FSGM_REQUIRE(cost_bound >= 1 && cost_bound <= 255, "%s: cost_bound must be 1..255 (got %d)", who, cost_bound);
+    return FSGM_OK;
+}
+
+fsgm_status fsgm_epi_plan_ingest_cost_device(fsgm_epi_plan* p, int32_t n, const uint8_t* C, int32_t layout, int32_t cost_bound,
+                                             void* stream, int32_t* status) {
+    const char* who = "fsgm_epi_plan_ingest_cost_device";
+    FSGM_REQUIRE(p && C, "%s: null argument", who);
+    fsgm_status st = epi_ingest_args(who, p, n, layout, cost_bound);
+    if (st != FSGM_OK) return st;
+    const hipStream_t cs = (hipStream_t)stream;
+    if ((st = device_check_args(who, p->prm.device, cs, {{C, (size_t)n * p->N, 1, true, "C"}, {status, 4, 4, false, "status"}})) != FSGM_OK)
+        return st;
+    if ((st = ensure_ingest_flag(&p->dIngestFlag, p->stream)) != FSGM_OK) return st;
+    p->cmax.assign(n, cost_bound);
+    epi_select_kernel(p);
+    return device_call(p->join, cs, p->stream, [&] {
+        launch_sgm_ingest(p->stream, C, p->dC, n, p->W, p->H, p->D, layout, cost_bound, p->dIngestFlag);
+        launch_device_status(p->stream, nullptr, p->dIngestFlag, status);
+        return FSGM_OK;
+    });
+}
+
+fsgm_status fsgm_epi_plan_ingest_float_dptr(fsgm_epi_plan* p, int32_t n, const void* C, const fsgm_cost_format* fmt, int32_t layout,
+                                            int32_t cost_bound, void* stream, int32_t* status) {
+    const char* who = "fsgm_epi_plan_ingest_float_dptr";
+    FSGM_REQUIRE(p && C, "%s: null argument", who);
+    CostFormat cf;
+    fsgm_status st = check_cost_format(who, fmt, &cf);
+    if (st != FSGM_OK || (st = epi_ingest_args(who, p, n, layout, cost_bound)) != FSGM_OK) return st;
+    const hipStream_t cs = (hipStream_t)stream;
+    const size_t es = cost_elem_size(cf.dtype);
+    if ((st = device_check_args(who, p->prm.device, cs, {{C, (size_t)n * p->N * es, es, true, "C"}, {status, 4, 4, false, "status"}})) != FSGM_OK)
+        return st;
+    if ((st = ensure_ingest_flag(&p->dIngestFlag, p->stream)) != FSGM_OK) return st;
+    p->cmax.assign(n, cost_bound);
+    epi_select_kernel(p);
+    return device_call(p->join, cs, p->stream, [&] {
+        launch_sgm_ingest_float(p->stream, C, cf, p->dC, n, p->W, p->H, p->D, layout, cost_bound, p->dIngestFlag);
+        launch_device_status(p->stream, nullptr, p->dIngestFlag, status);
+        return FSGM_OK;
+    });
 }
 
 }  // extern "C"

@@ -9,8 +9,10 @@
 #include "pyramid_kernels.h"
 #include "cost_float_ingest.h"
 #include "sgm2d_ingest.h"
+#include <algorithm>
 #include <mutex>
 #include <string.h>
+#include <vector>
 
 using namespace fsgm;
 
@@ -101,10 +103,11 @@ fsgm_status sgm2d_plan(fsgm_pyd_plan** out, const Sgm2dCall& c, int cmax) {
     return FSGM_OK;
 }
 
-fsgm_status ensure_ingest_flag(fsgm_pyd_plan* p) {
-    if (p->dIngestFlag) return FSGM_OK;
-    FSGM_HIP(hipMalloc((void**)&p->dIngestFlag, sizeof(uint32_t)));
-    FSGM_HIP(hipMemsetAsync(p->dIngestFlag, 0, sizeof(uint32_t), p->stream));
+// the scalar checks of both plan-level ingest entries, behind their null and format checks
+fsgm_status pyd_ingest_args(const char* who, const fsgm_pyd_plan* p, int32_t n, int32_t layout, int32_t cost_bound) {
+    FSGM_REQUIRE(n == p->batch, "%s: n_frames %d differs from the plan's batch %d", who, n, p->batch);
+    FSGM_REQUIRE(layout_ok(layout), "%s: layout must be FSGM_COST2D_LAYOUT_HWD (0), _DHW (1) or _DHW_YX (2), got %d", who, layout);
+    FSGM_REQUIRE(cost_bound >= 1 && cost_bound <= 255, "%s: cost_bound must be 1..255 (got %d)", who, cost_bound);
     return FSGM_OK;
 }
 
@@ -145,20 +148,18 @@ fsgm_status sgm2d_host(const char* who, int32_t n, const uint8_t* C, int32_t W, 
     // the true maximum of the batch (every layout holds the same bytes), as fsgm_pyd_plan_upload_cost takes it; a float volume
     // is not scanned: its declared bound selects the aggregation, as in the device forms
     const size_t NP = (size_t)W * H, ND = NP * (2 * rX + 1) * (2 * rY + 1);
-    int cmax = is_float ? c.prm.cost_bound : 0;
-    for (int f = 0; f < n && !is_float; f++) {
-        const uint8_t* v = C + (size_t)f * ND;
-        int m = 0;
-        for (size_t i = 0; i < ND; i++) m = v[i] > m ? v[i] : m;
-        FSGM_REQUIRE(m <= c.prm.cost_bound, "%s: frame %d holds a cost of %d, above cost_bound %d", who, f, m, c.prm.cost_bound);
-        cmax = m > cmax ? m : cmax;
+    int cmax = c.prm.cost_bound;
+    if (!is_float) {
+        std::vector<int> fmax(n, 0);
+        if ((st = frame_cost_maxima(who, C, n, ND, c.prm.cost_bound, fmax.data())) != FSGM_OK) return st;
+        cmax = *std::max_element(fmax.begin(), fmax.end());
     }
     std::lock_guard<std::mutex> lk(g_sgm2d.mu(c.prm.device));
     fsgm_pyd_plan* p = nullptr;
     if ((st = sgm2d_plan(&p, c, cmax)) != FSGM_OK) return st;
     const size_t B = n;
     if (!is_float && !p->dIngest) FSGM_HIP(hipMalloc((void**)&p->dIngest, B * ND));
-    if (is_float && (st = ensure_ingest_flag(p)) != FSGM_OK) return st;
+    if (is_float && (st = ensure_ingest_flag(&p->dIngestFlag, p->stream)) != FSGM_OK) return st;
     if (S && !p->dS) FSGM_HIP(hipMalloc((void**)&p->dS, B * ND * 4));
     if (flow && !p->dFlow) FSGM_HIP(hipMalloc((void**)&p->dFlow, B * NP * 16));
     StreamGuard guard(p->stream);                                // every early exit drains the stream: the copies use caller memory
@@ -220,7 +221,7 @@ fsgm_status sgm2d_device(const char* who, int32_t n, const uint8_t* C, int32_t W
     // The device cannot be asked for the true maximum without a wait: the declared bound selects the aggregation, the ingest
     // kernel saturates at it.  What a warm call must not do (allocate) happens before the join with the caller's stream.
     if ((st = sgm2d_plan(&p, c, c.prm.cost_bound)) != FSGM_OK) return st;
-    if ((st = ensure_ingest_flag(p)) != FSGM_OK) return st;
+    if ((st = ensure_ingest_flag(&p->dIngestFlag, p->stream)) != FSGM_OK) return st;
     return device_call(p->join, cs, p->stream, [&]() -> fsgm_status {
         if (fmt.dtype >= 0) launch_sgm2d_ingest_float(p->stream, C, fmt, p->dC, n, W, H, p->Sx, p->Sy, c.prm.layout, c.prm.cost_bound, p->dIngestFlag);
         else launch_sgm2d_ingest(p->stream, C, p->dC, n, W, H, p->Sx, p->Sy, c.prm.layout, c.prm.cost_bound, p->dIngestFlag);
@@ -337,15 +338,12 @@ fsgm_status fsgm_pyd_plan_ingest_float_dptr(fsgm_pyd_plan* p, int32_t n, const v
     FSGM_REQUIRE(p && C, "%s: null argument", who);
     CostFormat cf;
     fsgm_status st = check_cost_format(who, fmt, &cf);
-    if (st != FSGM_OK) return st;
-    FSGM_REQUIRE(n == p->batch, "%s: n_frames %d differs from the plan's batch %d", who, n, p->batch);
-    FSGM_REQUIRE(layout_ok(layout), "%s: layout must be FSGM_COST2D_LAYOUT_HWD (0), _DHW (1) or _DHW_YX (2), got %d", who, layout);
-    FSGM_REQUIRE(cost_bound >= 1 && cost_bound <= 255, "%s: cost_bound must be 1..255 (got %d)", who, cost_bound);
+    if (st != FSGM_OK || (st = pyd_ingest_args(who, p, n, layout, cost_bound)) != FSGM_OK) return st;
     const hipStream_t cs = (hipStream_t)stream;
     const size_t es = cost_elem_size(cf.dtype);
     if ((st = device_check_args(who, p->device, cs, {{C, (size_t)n * p->NP * p->D * es, es, true, "C"}, {status, 4, 4, false, "status"}})) != FSGM_OK)
         return st;
-    if ((st = ensure_ingest_flag(p)) != FSGM_OK) return st;
+    if ((st = ensure_ingest_flag(&p->dIngestFlag, p->stream)) != FSGM_OK) return st;
     p->cmax = cost_bound;
     return device_call(p->join, cs, p->stream, [&] {
         launch_sgm2d_ingest_float(p->stream, C, cf, p->dC, n, p->W, p->H, p->Sx, p->Sy, layout, cost_bound, p->dIngestFlag);
@@ -358,14 +356,12 @@ fsgm_status fsgm_pyd_plan_ingest_cost_device(fsgm_pyd_plan* p, int32_t n, const 
                                              void* stream, int32_t* status) {
     const char* who = "fsgm_pyd_plan_ingest_cost_device";
     FSGM_REQUIRE(p && C, "%s: null argument", who);
-    FSGM_REQUIRE(n == p->batch, "%s: n_frames %d differs from the plan's batch %d", who, n, p->batch);
-    FSGM_REQUIRE(layout_ok(layout), "%s: layout must be FSGM_COST2D_LAYOUT_HWD (0), _DHW (1) or _DHW_YX (2), got %d", who, layout);
-    FSGM_REQUIRE(cost_bound >= 1 && cost_bound <= 255, "%s: cost_bound must be 1..255 (got %d)", who, cost_bound);
+    fsgm_status st = pyd_ingest_args(who, p, n, layout, cost_bound);
+    if (st != FSGM_OK) return st;
     const hipStream_t cs = (hipStream_t)stream;
-    fsgm_status st;
     if ((st = device_check_args(who, p->device, cs, {{C, (size_t)n * p->NP * p->D, 1, true, "C"}, {status, 4, 4, false, "status"}})) != FSGM_OK)
         return st;
-    if ((st = ensure_ingest_flag(p)) != FSGM_OK) return st;
+    if ((st = ensure_ingest_flag(&p->dIngestFlag, p->stream)) != FSGM_OK) return st;
     p->cmax = cost_bound;
     return device_call(p->join, cs, p->stream, [&] {
         launch_sgm2d_ingest(p->stream, C, p->dC, n, p->W, p->H, p->Sx, p->Sy, layout, cost_bound, p->dIngestFlag);

@@ -68,7 +68,7 @@ namespace fsgm {
 //   MODE 2: point-mirrored frame, final: S = 8*(C + P2) - (Y_up + Y_dn + Y_h) in registers,
 //           WTA per pixel, writes one record {best, minC, S[best-1], S[best+1]} + S[0] per pixel.
 //   MODE 3: the same final on the pass-0 frame (X = Y_up of the rows it covers): the down half of the sweeps that meet
-//           in the middle (capi_epi.hip, PIPE_SWEEP_MID).
+//           in the middle (capi_epi_enqueue.hip, PIPE_SWEEP_MID).
 // =============================================================================================
 #ifndef FSGM_SWEEP_L16
 #define FSGM_SWEEP_L16 1        // diagonal states in LDS as 2 x u16 per dword (A/B knob; 0: packed bytes, half the LDS)

@@ -1,5 +1,5 @@
 // post_plan.h -- the post-processing chain's one batched enqueue and its plan (capi_post.hip), shared with the pipeline
-// of test.m's frame body (fsgm_epipolar_flow_pp_*, capi_epi.hip)
+// of test.m's frame body (fsgm_epipolar_flow_pp_*, capi_epi_driver.hip)
 #pragma once
 #include "capi_common.h"
 

@@ -2,7 +2,7 @@
 tests/test_call_sequences_cpu.py (the draws alone) and tests/test_gpu_call_sequences.py (the calls, one after the other, each on
 the plan its predecessor left behind).
 
-First the epi family: everything behind g_epi (fsgm_amd/csrc/capi_epi.hip); the other caches follow below it.  A step is a Step tuple: the entry form, the shape and the
+First the epi family: everything behind g_epi (cached_plan, fsgm_amd/csrc/capi_epi.hip; its callers in capi_epi.hip, capi_stereo.hip, capi_sgm.hip and capi_epi_driver.hip); the other caches follow below it.  A step is a Step tuple: the entry form, the shape and the
 batch, the parameters that are part of the cache key, the ones that are not, what it asks back and the seed of its data.  Each
 function consumes its RandomState in a fixed order; the order is part of the test suite's definition (tests/fuzz_configs.py).
 

@@ -1,9 +1,9 @@
 """Batch-sized device arrays of the batched entry families, and the large-batch cases derived from them (data and arithmetic
 only: importable without a device).
 
-Every size below restates the host code that creates the array -- fsgm_epi_plan_create_sampling, ensure_cost_buffers,
+Every size below restates the host code that creates the array -- fsgm_epi_plan_create_sampling, epi_ensure_cost_buffers,
 ensure_agg_buffers and the *_bytes helpers of epi_sweep.hip / epi_band.hip for the epipolar plan (capi_epi.hip), sgm_run_device
-for sgm(C), post_plan_create_batch (capi_post.hip) for the post-processing chain, hints_enqueue (capi_pyramid.hip) for the level
+(capi_sgm.hip) for sgm(C), post_plan_create_batch (capi_post.hip) for the post-processing chain, hints_enqueue (capi_pyramid.hip) for the level
 hints -- and none comes from a run.  A case names one array and one mark (2^31, 2^32 or 2^34 bytes) and derives the smallest batch
 N such that (a) the array's N frames exceed the mark, (b) the mark falls strictly inside a frame, (c) at least two whole frames lie
 beyond it; (d) the call's peak -- the plan's arrays, the caller's tensors and the reference side -- stays under CAP.
@@ -49,11 +49,11 @@ def epi_plan_arrays(W, H, D, paths, pipeline, *, cost_stage=False, rectified=Fal
         a += [Array("dD2enc", NP * 4, 4), Array("dD2", NP * 4, 4), Array("dConf", NP, 1)]
     if runner_up:
         a.append(Array("dMinC2", NP * 4, 4))
-    if cost_stage or fb_check:                                   # ensure_cost_buffers
+    if cost_stage or fb_check:                                   # epi_ensure_cost_buffers
         a += [Array("dI1", NP, 1), Array("dI2", NP, 1), Array("dCen1", NP * 4, 4), Array("dCen2", NP * 4, 4), Array("dCraw", N, 1)]
         if not rectified:
             a += [Array("dPd0", NP * 16, 8), Array("dNd", NP * 16, 8)]
-    elif guide:                                                  # ensure_image_buffers
+    elif guide:                                                  # epi_ensure_image_buffers
         a += [Array("dI1", NP, 1), Array("dI2", NP, 1)]
     lines = pipeline in LINE_PIPES
     pairs = pipeline == "pairs16/nowrap"
@@ -142,7 +142,7 @@ FAMILIES = {
     "epi_plan/fused": ("arrays", "EpiPlan upload_cost -> run -> download, the fused pipelines (capi_epi.hip ensure_agg_buffers)"),
     "epi_plan/lines": ("arrays", "EpiPlan on the line kernels: dL = paths volumes a frame"),
     "epi_plan/generic": ("arrays", "EpiPlan at a dMax outside the line classes: agg_generic_kernel, wta_generic_kernel"),
-    "epi_plan/cost": ("arrays", "the cost stage from images: stereo_sgm, calc_cost_sgm_batch (ensure_cost_buffers)"),
+    "epi_plan/cost": ("arrays", "the cost stage from images: stereo_sgm, calc_cost_sgm_batch (epi_ensure_cost_buffers)"),
     "sgm_device": ("arrays", "torch_ops.sgm: the caller's volumes and the cached plan's (sgm_run_device)"),
     "ingest_hwd": ("arrays", "launch_sgm_ingest's hwd copy in launches of 2^34 bytes (sgm_ingest.hip)"),
     "sgm2d_device": ("arrays", "torch_ops.sgm2d: the caller's volumes and the cached fsgm_pyd_plan's (capi_sgm2d.hip, capi_pyd.hip:93-106)"),
@@ -154,8 +154,8 @@ FAMILIES = {
     "level_hints": ("arrays", "flow_level_hints: launch_pyr_upsample2 / launch_pyr_median_upsample2 on the caller's tensors"),
     "pyramids": ("arrays", "pyramidal_sgm / pyramidal_sgm_ng on a batch: every level is a plan of the whole batch (capi_pyramid.hip "
                            "create_levels, capi_ng_pyramid.hip:52-58)"),
-    "sum_tap": ("per-frame", "S of fsgm_sgm_device / download_sum: one frame through dS at a time (capi_epi.hip sgm_run_device "
-                             "'S never exists for a batch', ensure_tap_buffers allocates p->N * 4)"),
+    "sum_tap": ("per-frame", "S of fsgm_sgm_device / download_sum: one frame through dS at a time (capi_sgm.hip sgm_run_device "
+                             "'S never exists for a batch', capi_epi.hip epi_ensure_tap_buffers allocates p->N * 4)"),
 }
 
 Case = namedtuple("Case", "id family W H D paths pipeline n target target_bpf mark arrays caller_bytes ref_bytes sub_batch")

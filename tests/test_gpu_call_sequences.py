@@ -4,7 +4,8 @@ penalties, costs, bounds, ranges, outputs -- left behind, or one that was evicte
 The seeded sequences come from tests/call_sequences.py (their draws are checked in tests/test_call_sequences_cpu.py); every
 returned array is compared for equality with the oracle's or a restatement's answer for the step's own arguments, and where the
 call reports the kernel that ran, with what a fresh plan would choose.  The directed cases below them run A, B, A on one key, one
-per hazard read from cached_plan, prepare, set_penalties, stereo_host and sgm_run_* (fsgm_amd/csrc/capi_epi.hip)."""
+per hazard read from cached_plan, epi_prepare, set_penalties (fsgm_amd/csrc/capi_epi.hip), stereo_host (capi_stereo.hip) and
+sgm_run_* (capi_sgm.hip)."""
 import ctypes as C
 import threading
 
@@ -305,7 +306,7 @@ def test_two_host_threads_across_the_cache(gpu_lib, oracle, side):
 def test_a_small_bound_then_a_cost_stage_on_one_key(gpu_lib, oracle, side):
     """sgm(C) with costs up to 4 leaves cmax = 4, for which (120, 125) does not wrap (4 + 250 <= 255); calc_cost_sgm without the
     vz conversion on that plan brings census costs up to 24 (24 + 250 > 255: a path state of up to 24 + 125 plus P1 passes a
-    byte): prepare() must put cmax back to 24 and select the wrapping kernels.  In device and in host form."""
+    byte): epi_prepare() must put cmax back to 24 and select the wrapping kernels.  In device and in host form."""
     W, H, D = 61, 9, 16
     P = dict(P1=120, P2=125)
     cost = _base("calc_cost_sgm", W, H, D, 1, 8, want_S=True, want_C=True, **P)

@@ -18,8 +18,8 @@ an arena can show.  What it does see: the ingest kernels' loads of C, the cost k
 every post stage's neighbour reads.
 tests/test_footprint_table_cpu.py asserts that every fsgm_*_device* function of include/fsgm.h has a row here.
 
-The per-frame pointer structs fsgm_epi_in / fsgm_epi_out hold one pointer per array for the whole contiguous batch (capi_epi.hip
-checks n * H * W elements behind each): each such pointer gets one carved tensor.
+The per-frame pointer structs fsgm_epi_in / fsgm_epi_out hold one pointer per array for the whole contiguous batch (epi_run_device,
+capi_epi.hip, checks n * H * W elements behind each): each such pointer gets one carved tensor.
 """
 import contextlib
 import ctypes as C

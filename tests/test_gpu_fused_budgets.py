@@ -11,7 +11,7 @@ bit for bit and with no pixel excluded: S of every voxel (debug tap), minC and b
   * five volumes a case (tests/budget_volumes.py): uniform, zeroed columns, one strong minimum a pixel, the constant volume (the
     largest sum bytes in nearly every voxel, every d tied: the first-minimum rule) and all zeros;
   * D = 16 .. 256 (1 .. 16 lanes a pixel) on the smallest frames that cross one column strip and one row block of the sweeps;
-  * the small-batch sub-forms (5 frames) and the large-batch ones (17 frames) of select_kernel;
+  * the small-batch sub-forms (5 frames) and the large-batch ones (17 frames) of epi_select_kernel;
   * penalty sets and costs just outside the budgets, which must take the line kernels and still match;
   * fsgm::sgm on a caller's volume with cost_bound at the case's largest cost.
 
@@ -86,7 +86,7 @@ def test_pairs_at_the_largest_cost(gpu_lib, oracle, P1, P2, D):
 @pytest.mark.parametrize("D", (64, 128))
 @pytest.mark.parametrize("paths,P1,P2,modes", [(8, 21, 64, SWEEPS), (4, 63, 64, PAIRS)])
 def test_large_batch_forms_at_the_largest_cost(gpu_lib, oracle, paths, P1, P2, modes, D):
-    """17 frames: past every small-batch switch of select_kernel (the along-x pair's finer split below 16 frames, or up to 10;
+    """17 frames: past every small-batch switch of epi_select_kernel (the along-x pair's finer split below 16 frames, or up to 10;
     8-wave workgroups up to 10; the along-x pair as line kernels up to 5) -- the coarse, non-tall forms without x lines."""
     W, H = BV.sweep_shape(D)
     vols = BV.volumes(W, H, D, BV.nowrap_cmax(P1, P2), seed=1000 + D, n=17)
